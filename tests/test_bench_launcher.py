@@ -66,3 +66,39 @@ def test_torch_generators_equal_numpy_generators(sars_paths):
     assert np.array_equal(a, ta.numpy().astype(np.uint8)) and np.array_equal(b, tb.numpy().astype(np.uint8))
     ta2, tb2 = synth.paired_codes_torch(g, 300, 150, 5, err=0.01, isnv=isnv, row0=1234)
     assert np.array_equal(a[1234:1534], ta2.numpy().astype(np.uint8)) and np.array_equal(b[1234:1534], tb2.numpy().astype(np.uint8))
+
+
+def test_dump_outputs_stays_within_budget_and_samples_the_same_cells():
+    """--dump-outputs: float64 arrays stacked over the dumped samples; an output too large for 64 MiB keeps one fixed, seeded
+    choice of cells in every array, so two runs (two builds) write the same files for the same results."""
+    import tempfile
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from bronko_amd.engine import SampleResult
+
+    def fake(n_cells, n_files, seed):
+        r = SampleResult(1, n_files, n_cells)
+        g = np.random.default_rng(seed)
+        for a in r.arrays():
+            a[:] = g.integers(0, 1 << 40, a.size, dtype=np.uint64)
+        r.stats[:] = g.integers(0, 1000, r.stats.shape, dtype=np.uint64)
+        return r
+
+    for n_cells, n_files in ((29903, 1), (3000000, 100)):
+        dumped = [(508 + j, fake(n_cells, n_files, j)) for j in range(4)]
+        with tempfile.TemporaryDirectory() as d:
+            files, nbytes = bench.dump_outputs(os.path.join(d, "a"), dumped, 0, 1)
+            bench.dump_outputs(os.path.join(d, "b"), dumped, 0, 1)
+            assert nbytes == sum(os.path.getsize(os.path.join(d, "a", f)) for f in files) <= 64 << 20
+            got = {f[:-4]: np.load(os.path.join(d, "a", f)) for f in files}
+            assert all(a.dtype == np.float64 for a in got.values())
+            assert all(np.array_equal(got[f[:-4]], np.load(os.path.join(d, "b", f))) for f in files)
+            cells = got["cell_index"].astype(np.int64)
+            if n_cells * 4 * 4 * 8 < 32 << 20:
+                assert np.array_equal(cells, np.arange(n_cells * 4))
+            assert got["sample_in_step"].tolist() == [508, 509, 510, 511]
+            for j, (_, r) in enumerate(dumped):
+                for name in ("fwd_depth", "rev_depth", "fwd_nk", "rev_nk"):
+                    assert np.array_equal(got[name][j], getattr(r, name)[cells].astype(np.float64))
+                assert np.array_equal(got["stats"][j], r.stats.astype(np.float64))

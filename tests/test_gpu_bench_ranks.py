@@ -81,3 +81,25 @@ def test_config5_whole_samples_per_rank():
     assert one["check"] == two["check"] and one["check"]["kmers_scanned"] == [READS * 120]
     assert max(one["check"]["perfect_kmers"]) > 1000
     assert "no collective" in two["config"]["parallelism"]
+
+
+def test_dump_outputs_are_the_oracle_pileup(oracle, sars_paths, tmp_path):
+    """--dump-outputs writes what the timed path computed in its last step: two samples of the one batch, each the oracle's
+    pileup and statistics of that batch's reads; --steps sets the timed steps and ms_per_step is their time per step."""
+    out = _bench(["--steps", "3", "--batches", "1", "--samples-per-step", "2", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert out["dump_outputs"]["samples"] == 2 and out["dump_outputs"]["bytes"] <= 64 << 20
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in out["dump_outputs"]["files"]}
+    assert got["sample_in_step"].tolist() == [0, 1]
+    genome, isnv = synth.sample_genome(synth.read_fasta_bytes(sars_paths[0]), 2)
+    reads = synth.codes_to_ascii(synth.single_end_codes(genome, READS, 150, 2 * 1000003, err=0.005, isnv=isnv))
+    ix = oracle.Index.build(21, [sars_paths[0]])
+    try:
+        pile = oracle.sample_pileup(ix, [reads])
+    finally:
+        ix.close()
+    assert np.array_equal(got["cell_index"], np.arange(pile.fwd_depth.size))
+    for j in range(2):
+        for name in ("fwd_depth", "rev_depth", "fwd_nk", "rev_nk"):
+            assert np.array_equal(got[name][j], getattr(pile, name).astype(np.float64)), name
+        assert np.array_equal(got["stats"][j], pile.stats.astype(np.float64))
