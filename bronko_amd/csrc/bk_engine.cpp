@@ -2257,9 +2257,11 @@ static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t
             // finalize / Level 2 kernels, which are chains of short launches that wait for latency, not for CUs.  With siblings in
             // flight three quarters of the CUs scan and the rest keep those chains moving (config 2, three samples in flight: 8.35
             // -> 9.06 G reads/s; one sample alone is 4% slower that way and keeps the whole chip).
-            // (round 6, tiles dealt as the workgroups come: with four or more samples in flight -- a host that raises HIP's hardware
-            // queues from their default of four -- five eighths; 12.1 against 11.3 G reads/s, flat from 8 to 11 sixteenths)
-            int share = e->family->load() >= 4 ? e->n_cus * 5 / 8 : e->n_cus - e->n_cus / 4;
+            // (Round 6 gave four or more samples in flight five eighths: 12.1 against 11.3 G reads/s then, flat from 8 to 11
+            // sixteenths.  Swept again at the sources whose scan writes out only the filled bucket slots: 6 / 8 / 10 / 12 / 14 / 16
+            // sixteenths gave 7.47 / 7.97 / 8.24 / 8.50 / 8.42 / 8.28 G reads/s, two interleaved rounds within 0.4 % of each other:
+            // three quarters, whatever the number of siblings.)
+            int share = e->n_cus - e->n_cus / 4;
             if (const char* fr = test_env("BK_ITEM_SHARE")) share = std::max(1, std::min(e->n_cus, e->n_cus * atoi(fr) / 16));   // measurement aid: sixteenths of the CUs
             grid = bk::items_grid(take, e->family->load() > 1 ? share : e->n_cus);
             if (const char* gr = test_env("BK_ITEM_GRID")) grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, (uint32_t)atoi(gr)));

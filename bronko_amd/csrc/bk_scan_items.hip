@@ -717,8 +717,10 @@ __global__ __launch_bounds__(kItemBlock) void scan_items_kernel(ScanArgs a) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::"v"(pf_sink) : "memory");   // the prefetch register stays reserved up to here
 
-    // ---- the buckets, as they are, into this workgroup's region: the whole bucket area in 16-byte units (slots that hold nothing
-    // go out as they are -- tab says how many of a bin's slots count), then the table ----
+    // ---- the buckets into this workgroup's region, in 16-byte units: only the units that hold a counted slot (tab says how many of
+    // a bin's slots count; a reader never looks past them), then the table.  (Until the whole bucket area went out: 11.5 MB per
+    // launch of config 2 whatever the fill, where a workgroup's 6,800 E and 4,500 V items fill 29 of an E bucket's 48 slots and
+    // 10 of a V bucket's 24 on average.) ----
     if (threadIdx.x == 0) *block_kmers = 0;
     __syncthreads();
     BK_DBG_CLOCK(a, 2);
@@ -731,9 +733,10 @@ __global__ __launch_bounds__(kItemBlock) void scan_items_kernel(ScanArgs a) {
         const uint32_t ue = cap_e / 8u, uv = cap_v / 8u, n_eu = n_eb * ue, G = a.ig.grid_max;   // 16-byte units per bucket
         for (uint32_t i = threadIdx.x; i < a.ig.wg_stride / 8u; i += kItemBlock) {
             size_t dst;
-            if (i < n_eu) { const uint32_t bin = i / ue; dst = ((size_t)bin * G + blockIdx.x) * ue + (i - bin * ue); }
-            else { const uint32_t i2 = i - n_eu, bin = i2 / uv; dst = (size_t)n_eu * G + ((size_t)bin * G + blockIdx.x) * uv + (i2 - bin * uv); }
-            out4[dst] = buck4[i];
+            uint32_t bin, u, cap;   // unit u of bin `bin`'s bucket
+            if (i < n_eu) { bin = i / ue; u = i - bin * ue; cap = cap_e; dst = ((size_t)bin * G + blockIdx.x) * ue + u; }
+            else { const uint32_t i2 = i - n_eu, vb = i2 / uv; bin = n_eb + vb; u = i2 - vb * uv; cap = cap_v; dst = (size_t)n_eu * G + ((size_t)vb * G + blockIdx.x) * uv + u; }
+            if (8u * u < min(cnt[bin], cap)) out4[dst] = buck4[i];
         }
         for (uint32_t bin = threadIdx.x; bin < n_bins; bin += kItemBlock)
             c->tab[(size_t)bin * G + blockIdx.x] = (unsigned short)min(cnt[bin], (bin < n_eb ? cap_e : cap_v) + kItemGCap);
@@ -765,7 +768,8 @@ __global__ __launch_bounds__(kBinBlock) void bin_count_kernel(BinArgs b) {
     const unsigned short* const bin_items = b.items + (is_e ? (size_t)bin * G * b.ig.cap_e : (size_t)n_eb * G * b.ig.cap_e + (size_t)(bin - n_eb) * G * b.ig.cap_v);
     // A thread per scan workgroup: this bin's bucket in that workgroup's region.  The bucket's first 48 / 24 slots are asked for
     // together with the table entry that says how many of them hold items, before anything else is done -- one trip to memory,
-    // not two (every bin's workgroup reads what 255 others wrote: nothing of it is in this XCD's L2).
+    // not two (every bin's workgroup reads what 255 others wrote: nothing of it is in this XCD's L2).  Units past the count were
+    // not written by this launch (the scan writes out filled units only): what they hold is never taken.
     const bool mine = threadIdx.x < b.n_wg && !BK_ABLATE(b, 1);
     const unsigned short* reg0 = bin_items + (size_t)(mine ? threadIdx.x : 0u) * cap;
     uint32_t hdr0 = 0u;
