@@ -55,6 +55,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_engine_set_stream", "bk_total_cells", "bk_n_files", "bk_n_slots", "bk_counter_len", "bk_can_shard", "bk_sample_begin",
            "bk_push_reads_packed", "bk_push_reads_packed_device", "bk_push_reads_ascii", "bk_push_reads_ascii_device", "bk_counters_device_ptr", "bk_sample_finalize",
            "bk_sample_finalize_shard", "bk_shard_measure", "bk_shard_transport", "bk_shard_received", "bk_transport_overflow", "bk_shard_sums_device_ptr", "bk_sample_merge_shards", "bk_kmer_table_partition", "bk_kmer_table_replace",
+           "bk_kmer_dump_enable", "bk_kmer_dump_size", "bk_kmer_dump_download",
            "bk_pileup_device_ptr", "bk_sample_download", "bk_sample_finish", "bk_pack_reads", "bk_pack_reads_flat",
            "bk_timing_enable", "bk_timing_read", "bk_call_params_default", "bk_sample_call", "bk_sample_download_calls", "bk_sample_download_noise",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
@@ -128,6 +129,12 @@ def load(testing=None):
     L.bk_kmer_table_partition.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.bk_kmer_table_replace.restype = C.c_int
     L.bk_kmer_table_replace.argtypes = [vp, vp, vp, u64]
+    L.bk_kmer_dump_enable.restype = C.c_int
+    L.bk_kmer_dump_enable.argtypes = [vp, u32]
+    L.bk_kmer_dump_size.restype = C.c_int
+    L.bk_kmer_dump_size.argtypes = [vp, C.c_int, C.POINTER(u64), C.POINTER(u64)]
+    L.bk_kmer_dump_download.restype = C.c_int
+    L.bk_kmer_dump_download.argtypes = [vp, C.c_int, vp, vp, u64]
     L.bk_shard_sums_device_ptr.restype = C.c_int
     L.bk_shard_sums_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bk_sample_merge_shards.restype = C.c_int

@@ -257,6 +257,39 @@ bool build_phf(const std::vector<uint64_t>& keys, std::vector<uint16_t>& pilots,
 
 }  // namespace
 
+// An open-addressing table of u64 keys (~0 = free) and u32 counts whose load stays below one half as a sample fills it
+// (ensure_table_room): full_kmer_stats' statistics table and the k-mer dump's count table (bk_kmer_dump_enable).  Its device-side
+// companion `out` holds the overflow flag at [4] and the tallies of new keys at [8 ..] (ktab_insert_key, kmer_dump_count_kernel).
+struct GrowTable {
+    DevBuf<unsigned long long> keys;
+    DevBuf<unsigned int> cnt;
+    uint32_t log2 = 0;                      // current capacity (grows with the sample: ensure_table_room)
+    unsigned long long* h_fill = nullptr;   // pinned copy of the tallies, refreshed after every push
+    hipEvent_t fill_ev = nullptr;
+    bool fill_pending = false;              // a copy of the tallies is in flight / unread
+    uint64_t fill_known = 0, fill_unknown_upper = 0;   // keys in the table at the last reading; k-mers pushed since (upper bound on new keys)
+    std::vector<std::pair<unsigned long long*, unsigned int*>> old;   // outgrown tables, freed at the next sample / destroy
+    ~GrowTable() {
+        for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); }
+        if (h_fill) (void)hipHostFree(h_fill);
+        if (fill_ev) (void)hipEventDestroy(fill_ev);
+    }
+};
+
+// bk_kmer_dump_enable: the sample's count table of every strand-specific k-mer (bk_kmer_dump.hip) and, per finalized mate file, its
+// selected entries sorted by k-mer
+struct KmerDump {
+    GrowTable t;
+    DevBuf<unsigned long long> out;         // [mate][2] kept, distinct + [4] overflow flag + [8 ..] tallies of new keys
+    DevBuf<unsigned long long> sel_keys, keys[2];   // selected (unsorted, padded with ~0) -> sorted, per mate file
+    DevBuf<unsigned int> sel_cnt, cnt[2];
+    DevBuf<unsigned char> sort_tmp;
+    uint64_t upper[2] = {0, 0};             // k-mers pushed per mate file in this sample (bounds its distinct keys)
+    uint64_t n_sorted[2] = {0, 0};          // length of the sorted arrays of the last finalize (selected entries, then padding)
+    bool in_sample = false;                 // enabled when the current / last sample began
+    int finalized_mates = 0;                // mate files the last finalize selected (0: none, or finalized by shards)
+};
+
 struct bk_engine {
     bk_params params{};
     // engines that share this one's index tables (itself and its forks, alive): with samples in flight next to each other the
@@ -299,18 +332,12 @@ struct bk_engine {
     DevBuf<unsigned int> deferred, n_deferred, deferred_mask;
     DevBuf<unsigned long long> deferred_n;   // dense planes: the deferred k-mers' counts (K2a zeroes the counters it reads)
     DevBuf<unsigned int> fin_partials;      // per-workgroup finalize tallies (small genome sets only)
-    DevBuf<unsigned long long> ktab_keys;   // full_kmer_stats: open-addressing table of non-index-touching k-mers
-    DevBuf<unsigned int> ktab_cnt;
+    GrowTable ktab;                         // full_kmer_stats: open-addressing table of non-index-touching k-mers
     DevBuf<unsigned long long> ktab_out;    // [2 mates][2] distinct, kept  + [4] overflow flag + [8 ..] tallies of new keys
-    uint32_t ktab_log2 = 0;                 // current capacity (grows with the sample: ensure_ktab_room)
-    unsigned long long* h_fill = nullptr;   // pinned copy of the tallies, refreshed after every push
-    hipEvent_t fill_ev = nullptr;
-    bool fill_pending = false;              // a copy of the tallies is in flight / unread
-    uint64_t fill_known = 0, fill_unknown_upper = 0;   // keys in the table at the last reading; k-mers pushed since (upper bound on new keys)
-    std::vector<std::pair<unsigned long long*, unsigned int*>> ktab_old;   // outgrown tables, freed at the next sample / destroy
     DevBuf<unsigned long long> xchg_keys, xchg_cursors;   // bk_kmer_table_partition: the table's entries grouped by owner rank
     DevBuf<unsigned int> xchg_cnt;
     bool ktab_exchanged = false;            // bk_kmer_table_replace was called in this sample
+    std::unique_ptr<KmerDump> dump;         // bk_kmer_dump_enable (null: no table, no launch)
     DevBuf<uint32_t> slot_of, estat_off, estat;
     DevBuf<bk::SlotRec> slot_rec;
     DevBuf<uint4> ent_files, slot_files, id_own_files, estat_files;
@@ -485,11 +512,11 @@ static int alloc_sample_state(bk_engine* e) {
     BK_HIP(hipMemset(e->xport_flag.p, 0, 4 * sizeof(unsigned long long)));
     if (prm->full_kmer_stats) {
         if (prm->kmer_table_log2 < 10 || prm->kmer_table_log2 > 31) return fail(BK_ERR_INVALID, "kmer_table_log2 out of range");
-        BK_HIP(e->ktab_keys.alloc((size_t)1 << prm->kmer_table_log2));
-        BK_HIP(e->ktab_cnt.alloc((size_t)1 << prm->kmer_table_log2));
-        e->ktab_log2 = prm->kmer_table_log2;
-        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->h_fill), bk::ktab_fill_words() * sizeof(unsigned long long), hipHostMallocDefault));
-        BK_HIP(hipEventCreateWithFlags(&e->fill_ev, hipEventDisableTiming));
+        BK_HIP(e->ktab.keys.alloc((size_t)1 << prm->kmer_table_log2));
+        BK_HIP(e->ktab.cnt.alloc((size_t)1 << prm->kmer_table_log2));
+        e->ktab.log2 = prm->kmer_table_log2;
+        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->ktab.h_fill), bk::ktab_fill_words() * sizeof(unsigned long long), hipHostMallocDefault));
+        BK_HIP(hipEventCreateWithFlags(&e->ktab.fill_ev, hipEventDisableTiming));
     }
     BK_HIP(e->ktab_out.alloc(8 + bk::ktab_fill_words()));
     // one row of per-genome tallies per finalize workgroup (8192 rows: 10 MB at 100 genomes); without it every workgroup adds its
@@ -555,7 +582,7 @@ static int alloc_sample_state(bk_engine* e) {
     // the scan's V items straight into the regional finalize (bk_finalize_lean.hip): where that kernel runs (one genome file, dense
     // planes, no statistics table, no pseudo k-mers, an answer table; FinalizeArgs are checked again at finalize), a V bin is the 64
     // row positions of one of its workgroups, and Level 2 is the only other writer of the V part (ScanArgs::n_direct: no nbatch_kernel)
-    e->fuse_ok = e->use_items && e->n_files == 1 && e->max_seqs_per_file == 1 && (uint64_t)e->n_lds_bins >= e->total_cells && !e->ktab_keys.p && e->n_prows == 0 &&
+    e->fuse_ok = e->use_items && e->n_files == 1 && e->max_seqs_per_file == 1 && (uint64_t)e->n_lds_bins >= e->total_cells && !e->ktab.keys.p && e->n_prows == 0 &&
                  e->n_u == e->n_full && e->n_full > 0 && e->dirty_ans.p && e->W > 1 && e->v_span > 0 && e->v_span <= 32 && e->fin_partials.p && e->lean_e_list.p &&
                  prm->cs < (1ull << 32) && e->ig.vq_log2 == 6 && !test_env("BK_NO_LEAN_FINALIZE") && !test_env("BK_NO_FUSE") && !test_env("BK_NO_N_DIRECT");
     if (e->fuse_ok)
@@ -2029,10 +2056,7 @@ void bk_engine_destroy(bk_engine* e) {
         if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
-    for (auto& o : e->ktab_old) { (void)hipFree(o.first); (void)hipFree(o.second); }
     for (auto& st : e->stage) { if (st.done) (void)hipEventDestroy(st.done); if (st.h) (void)hipHostFree(st.h); }
-    if (e->h_fill) (void)hipHostFree(e->h_fill);
-    if (e->fill_ev) (void)hipEventDestroy(e->fill_ev);
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
@@ -2053,6 +2077,19 @@ uint64_t bk_n_slots(const bk_engine* e) { return e ? e->n_slots : 0; }
 uint64_t bk_counter_len(const bk_engine* e) { return e ? e->plane_len : 0; }
 int bk_can_shard(const bk_engine* e) { return e && !e->sparse ? 1 : 0; }
 
+// a sample starts from an empty table (the capacity the last one grew to stays)
+static int clear_table(bk_engine* e, GrowTable& t) {
+    if (!t.old.empty()) {   // tables the previous sample outgrew
+        BK_HIP(hipStreamSynchronize(e->stream));
+        for (auto& o : t.old) { (void)hipFree(o.first); (void)hipFree(o.second); }
+        t.old.clear();
+    }
+    BK_HIP(hipMemsetAsync(t.keys.p, 0xff, t.keys.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(t.cnt.p, 0, t.cnt.n * sizeof(unsigned int), e->stream));
+    t.fill_known = 0; t.fill_unknown_upper = 0; t.fill_pending = false;
+    return BK_OK;
+}
+
 int bk_sample_begin(bk_engine* e) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     BK_HIP(hipSetDevice(e->device));
@@ -2065,15 +2102,13 @@ int bk_sample_begin(bk_engine* e) {
     bk::launch_zero_small(e->stats.p, e->stats.n, e->kstats.p, e->kstats.n, e->ktab_out.p, e->ktab_out.n, e->present.p, e->present.n,
                           e->n_deferred.p, e->n_deferred.n, e->pileup.p, e->gather_mode ? 0 : e->pileup.n, e->stream);
     if (sel_rows) bk::launch_zero_genome_rows(e->pileup.p, (size_t)e->total_cells * 4, e->file_cell_lo_d.p, e->n_files, (uint32_t)e->total_cells, e->last_sel.p, e->stream);
-    if (e->ktab_keys.p) {
-        if (!e->ktab_old.empty()) {   // tables the previous sample outgrew
-            BK_HIP(hipStreamSynchronize(e->stream));
-            for (auto& o : e->ktab_old) { (void)hipFree(o.first); (void)hipFree(o.second); }
-            e->ktab_old.clear();
-        }
-        BK_HIP(hipMemsetAsync(e->ktab_keys.p, 0xff, e->ktab_keys.n * sizeof(unsigned long long), e->stream));
-        BK_HIP(hipMemsetAsync(e->ktab_cnt.p, 0, e->ktab_cnt.n * sizeof(unsigned int), e->stream));
-        e->fill_known = 0; e->fill_unknown_upper = 0; e->fill_pending = false;
+    if (e->ktab.keys.p) { if (int rc = clear_table(e, e->ktab)) return rc; }
+    if (e->dump) {
+        if (int rc = clear_table(e, e->dump->t)) return rc;
+        BK_HIP(hipMemsetAsync(e->dump->out.p, 0, e->dump->out.n * sizeof(unsigned long long), e->stream));
+        e->dump->upper[0] = e->dump->upper[1] = 0;
+        e->dump->in_sample = true;
+        e->dump->finalized_mates = 0;
     }
     e->ktab_exchanged = false;
     e->reduced_shards[0] = e->reduced_shards[1] = 0;
@@ -2132,50 +2167,67 @@ static int zero_plane_if_stale(bk_engine* e, int mate) {
 }
 
 // full_kmer_stats: the statistics table holds every distinct k-mer that touches no window bucket -- as many as the sample has
-// sequencing errors, unknown in advance.  Its load stays below one half: before a batch of at most `upper` k-mers is pushed,
-// the keys it holds (read back from the device tallies after every push; the engine only waits for that reading when the
-// bound says the batch might not fit) plus `upper` must fit, else the table is rehashed into one four times larger.
-static int ensure_ktab_room(bk_engine* e, uint64_t upper) {
-    if (!e->ktab_keys.p) return BK_OK;
-    const uint64_t cap = 1ull << e->ktab_log2;
-    if (e->fill_known + e->fill_unknown_upper + upper > cap / 2) {
-        if (e->fill_pending) {
-            BK_HIP(hipEventSynchronize(e->fill_ev));
+// sequencing errors, unknown in advance (the k-mer dump's table: every distinct k-mer).  Its load stays below one half: before a
+// batch of at most `upper` k-mers is pushed, the keys it holds (read back from the device tallies at out[8 ..] after every push;
+// the engine only waits for that reading when the bound says the batch might not fit) plus `upper` must fit, else the table is
+// rehashed into one four times larger.
+static int ensure_table_room(bk_engine* e, GrowTable& t, unsigned long long* out, uint64_t upper) {
+    if (!t.keys.p) return BK_OK;
+    const uint64_t cap = 1ull << t.log2;
+    if (t.fill_known + t.fill_unknown_upper + upper > cap / 2) {
+        if (t.fill_pending) {
+            BK_HIP(hipEventSynchronize(t.fill_ev));
             uint64_t f = 0;
-            for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) f += e->h_fill[i];
-            e->fill_known = f; e->fill_unknown_upper = 0; e->fill_pending = false;
+            for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) f += t.h_fill[i];
+            t.fill_known = f; t.fill_unknown_upper = 0; t.fill_pending = false;
         }
-        uint32_t nl = e->ktab_log2;
-        while (nl < 31 && e->fill_known + e->fill_unknown_upper + upper > (1ull << nl) / 2) nl += 2;
+        uint32_t nl = t.log2;
+        while (nl < 31 && t.fill_known + t.fill_unknown_upper + upper > (1ull << nl) / 2) nl += 2;
         if (nl > 31) nl = 31;
-        if (nl != e->ktab_log2) {
+        if (nl != t.log2) {
             unsigned long long* nk = nullptr; unsigned int* nc = nullptr;
             BK_HIP(hipMalloc(reinterpret_cast<void**>(&nk), ((size_t)1 << nl) * sizeof(unsigned long long)));
             BK_HIP(hipMalloc(reinterpret_cast<void**>(&nc), ((size_t)1 << nl) * sizeof(unsigned int)));
             BK_HIP(hipMemsetAsync(nk, 0xff, ((size_t)1 << nl) * sizeof(unsigned long long), e->stream));
             BK_HIP(hipMemsetAsync(nc, 0, ((size_t)1 << nl) * sizeof(unsigned int), e->stream));
-            bk::launch_ktab_rehash(e->ktab_keys.p, e->ktab_cnt.p, e->ktab_log2, nk, nc, nl, e->ktab_out.p + 4, e->stream);
-            e->ktab_old.emplace_back(e->ktab_keys.p, e->ktab_cnt.p);   // still read by the rehash in flight
-            e->ktab_keys.p = nk; e->ktab_keys.n = (size_t)1 << nl;
-            e->ktab_cnt.p = nc; e->ktab_cnt.n = (size_t)1 << nl;
-            e->ktab_log2 = nl;
+            bk::launch_ktab_rehash(t.keys.p, t.cnt.p, t.log2, nk, nc, nl, out + 4, e->stream);
+            t.old.emplace_back(t.keys.p, t.cnt.p);   // still read by the rehash in flight
+            t.keys.p = nk; t.keys.n = (size_t)1 << nl;
+            t.cnt.p = nc; t.cnt.n = (size_t)1 << nl;
+            t.log2 = nl;
         }
     }
-    e->fill_unknown_upper += upper;
+    t.fill_unknown_upper += upper;
     return BK_OK;
 }
-static int note_ktab_fill(bk_engine* e) {   // after a push: a fresh copy of the tallies
-    if (!e->ktab_keys.p) return BK_OK;
-    BK_HIP(hipMemcpyAsync(e->h_fill, e->ktab_out.p + 8, bk::ktab_fill_words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipEventRecord(e->fill_ev, e->stream));
-    e->fill_pending = true;
+static int note_table_fill(bk_engine* e, GrowTable& t, const unsigned long long* out) {   // after a push: a fresh copy of the tallies
+    if (!t.keys.p) return BK_OK;
+    BK_HIP(hipMemcpyAsync(t.h_fill, out + 8, bk::ktab_fill_words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipEventRecord(t.fill_ev, e->stream));
+    t.fill_pending = true;
     return BK_OK;
+}
+static int ensure_ktab_room(bk_engine* e, uint64_t upper) { return ensure_table_room(e, e->ktab, e->ktab_out.p, upper); }
+static int note_ktab_fill(bk_engine* e) { return note_table_fill(e, e->ktab, e->ktab_out.p); }
+
+// bk_kmer_dump_enable: every k-mer of the batch into the count table, on the engine stream behind the scan that read the same records
+// (a staging slot is reused only after the stream has passed both)
+static int dump_push(bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
+                     const unsigned long long* n_records_dev, uint64_t upper) {
+    KmerDump& d = *e->dump;
+    if (int rc = ensure_table_room(e, d.t, d.out.p, upper)) return rc;
+    d.upper[mate] += upper;
+    bk::launch_kmer_dump_count(d_words, d_lens, n, n_records_dev, stride_words, e->k, (uint32_t)mate, d.t.keys.p, d.t.cnt.p, d.t.log2, d.out.p + 4,
+                               e->n_cus, e->stream);
+    BK_HIP(hipGetLastError());
+    return note_table_fill(e, d.t, d.out.p);
 }
 
 static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
                        const unsigned long long* n_records_dev = nullptr, uint64_t kmers_upper = 0) {
     if (int rc = zero_plane_if_stale(e, mate)) return rc;
     if (int rc = ensure_ktab_room(e, kmers_upper ? kmers_upper : n * (uint64_t)stride_words * 16)) return rc;
+    if (e->dump) { if (int rc = dump_push(e, mate, d_words, stride_words, d_lens, n, n_records_dev, kmers_upper ? kmers_upper : n * (uint64_t)stride_words * 16)) return rc; }
     bk::ScanArgs a{};
     a.n_records_dev = n_records_dev;
     a.ixp = e->d_view.p;
@@ -2190,7 +2242,7 @@ static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t
     a.slabs = e->slabs.p;
     a.n_lds_bins = e->n_lds_bins;
     a.ref_in_lds = e->ref_in_lds ? 1 : 0;
-    a.ktab_keys = e->ktab_keys.p; a.ktab_cnt = e->ktab_cnt.p; a.ktab_log2 = e->ktab_log2;
+    a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2;
     a.ktab_overflow = e->ktab_out.p + 4; a.mate = (uint32_t)mate;
     a.occ = e->occ.p; a.n_files = e->n_files;
     e->plane_used[mate] = true;
@@ -2562,7 +2614,7 @@ static int finalize_part(bk_engine* e, int n_mates, uint64_t elem_lo, uint64_t e
             a.file_cell_lo = e->file_cell_lo_d.p; a.max_file_cells = (uint32_t)e->max_file_cells_idx;
             a.n_deferred = e->n_deferred.p + m;
             a.deferred_mask = two_pass && e->deferred_mask.p ? e->deferred_mask.p + (size_t)m * (e->deferred_mask.n / 2) : nullptr;
-            a.ktab_keys = e->ktab_keys.p; a.ktab_cnt = e->ktab_cnt.p; a.ktab_log2 = e->ktab_log2;
+            a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2;
             a.ktab_overflow = e->ktab_out.p + 4; a.mate = (uint32_t)m;
             if (e->sparse) { a.v_list = e->v_list[m].p; a.p_list = e->p_list[m].p; a.e_list = e->e_list[m].p; a.n_list = e->n_list[m].p; }
             a.deferred_n = e->deferred_n.p ? e->deferred_n.p + (two_pass ? (size_t)m * (e->deferred_n.n / 2) : 0) : nullptr;
@@ -2630,9 +2682,9 @@ static int finalize_part(bk_engine* e, int n_mates, uint64_t elem_lo, uint64_t e
             e->plane_used[m] = false;
         }
     }
-    if (e->ktab_keys.p) {
+    if (e->ktab.keys.p) {
         bk_engine::Span sp(e, 1);
-        bk::launch_ktab_stats(e->ktab_keys.p, e->ktab_cnt.p, e->ktab_log2, e->params.ci, e->params.cx, e->ktab_out.p, e->stream);
+        bk::launch_ktab_stats(e->ktab.keys.p, e->ktab.cnt.p, e->ktab.log2, e->params.ci, e->params.cx, e->ktab_out.p, e->stream);
     }
     BK_HIP(hipGetLastError());
     e->in_sample = false;
@@ -2691,17 +2743,63 @@ static int finalize_part(bk_engine* e, int n_mates, uint64_t elem_lo, uint64_t e
     return BK_OK;
 }
 
+// bk_kmer_dump_enable, at the end of a whole-sample finalize (asynchronous, so that samples in flight never wait between their reads
+// and their results): per mate file, the entries with ci <= count <= cx as (k-mer, min(count, cs)), padded with ~0 keys up to a
+// bound on the mate file's distinct keys (the sort's length must be known on the host), sorted by k-mer -- the padding sorts last.
+static int dump_finalize(bk_engine* e, int n_mates) {
+    KmerDump& d = *e->dump;
+    if (!d.in_sample) return BK_OK;   // (enabled after this sample began: nothing was counted)
+    bk_engine::Span sp(e, 1);
+    // bounds on the keys in the table: the tallies of the last push when their copy has arrived (not waited for), else what the
+    // growth rule knows; the table's load stays below one half; and a mate file holds no more distinct k-mers than it was pushed
+    if (d.t.fill_pending && hipEventQuery(d.t.fill_ev) == hipSuccess) {
+        uint64_t f = 0;
+        for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) f += d.t.h_fill[i];
+        d.t.fill_known = f; d.t.fill_unknown_upper = 0; d.t.fill_pending = false;
+    }
+    const uint64_t keys_upper = std::min<uint64_t>((1ull << d.t.log2) / 2, d.t.fill_known + d.t.fill_unknown_upper);
+    uint64_t bound[2] = {0, 0}, most = 1;
+    size_t tmp_bytes = 0;
+    for (int m = 0; m < n_mates; m++) {
+        bound[m] = std::max<uint64_t>(1, std::min<uint64_t>(keys_upper, d.upper[m]));
+        most = std::max(most, bound[m]);
+        size_t b = 0;
+        BK_HIP(bk::kmer_dump_sort(nullptr, b, d.sel_keys.p, d.keys[m].p, d.sel_cnt.p, d.cnt[m].p, bound[m], e->k, e->stream));
+        tmp_bytes = std::max(tmp_bytes, b);
+    }
+    // every buffer is sized before the first launch (a buffer that grows is freed and allocated again)
+    if (d.sel_keys.n < most) { BK_HIP(d.sel_keys.alloc(most)); BK_HIP(d.sel_cnt.alloc(most)); }
+    for (int m = 0; m < n_mates; m++)
+        if (d.keys[m].n < bound[m]) { BK_HIP(d.keys[m].alloc(bound[m])); BK_HIP(d.cnt[m].alloc(bound[m])); }
+    if (d.sort_tmp.n < tmp_bytes) BK_HIP(d.sort_tmp.alloc(tmp_bytes));
+    for (int m = 0; m < n_mates; m++) {
+        BK_HIP(hipMemsetAsync(d.sel_keys.p, 0xff, bound[m] * sizeof(unsigned long long), e->stream));
+        bk::launch_kmer_dump_select(d.t.keys.p, d.t.cnt.p, d.t.log2, (uint32_t)m, e->params.ci, e->params.cs, e->params.cx, d.sel_keys.p, d.sel_cnt.p,
+                                    bound[m], d.out.p + 2 * m, e->stream);
+        size_t b = d.sort_tmp.n;
+        BK_HIP(bk::kmer_dump_sort(d.sort_tmp.p, b, d.sel_keys.p, d.keys[m].p, d.sel_cnt.p, d.cnt[m].p, bound[m], e->k, e->stream));
+        d.n_sorted[m] = bound[m];
+    }
+    BK_HIP(hipGetLastError());
+    if (test_env("BK_DUMP_STATS"))   // measurement aid (testing build): the table's capacity and the sort's lengths
+        fprintf(stderr, "[bk] k-mer dump: table 2^%u slots, sorted %llu + %llu entries\n", d.t.log2, (unsigned long long)bound[0], (unsigned long long)bound[1]);
+    d.finalized_mates = n_mates;
+    return BK_OK;
+}
+
 int bk_sample_finalize(bk_engine* e, int n_mates) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     if (e->reduced_shards[0] > 1 || e->reduced_shards[1] > 1) return fail(BK_ERR_STATE, "this sample's planes went through bk_shard_transport: finalize it with bk_sample_finalize_shard");
-    return finalize_part(e, n_mates, 0, e->plane_len);
+    int rc = finalize_part(e, n_mates, 0, e->plane_len);
+    if (rc == BK_OK && e->dump) rc = dump_finalize(e, n_mates);
+    return rc;
 }
 
 int bk_sample_finalize_shard(bk_engine* e, int n_mates, int shard, int n_shards) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     if (n_shards < 1 || (int)bk::kMaxShards % n_shards != 0 || shard < 0 || shard >= n_shards)
         return fail(BK_ERR_INVALID, "n_shards must divide %u and 0 <= shard < n_shards", bk::kMaxShards);
-    if (e->ktab_keys.p && n_shards > 1 && !e->ktab_exchanged)
+    if (e->ktab.keys.p && n_shards > 1 && !e->ktab_exchanged)
         return fail(BK_ERR_STATE, "full_kmer_stats with a sharded finalize: exchange the ranks' k-mer statistics tables first "
                                   "(bk_kmer_table_partition, all-to-all, bk_kmer_table_replace)");
     const uint64_t part = e->plane_len / (uint64_t)n_shards;
@@ -2711,7 +2809,7 @@ int bk_sample_finalize_shard(bk_engine* e, int n_mates, int shard, int n_shards)
                         e->reduced_shard[m], e->reduced_shards[m]);
     int rc = finalize_part(e, n_mates, part * shard, part * (shard + 1));
     if (rc != BK_OK) return rc;
-    if (e->ktab_keys.p) bk::launch_ktab_totals_to_kstats(e->ktab_out.p, e->kstats.p, n_mates, e->stream);   // (the ranks' totals add up)
+    if (e->ktab.keys.p) bk::launch_ktab_totals_to_kstats(e->ktab_out.p, e->kstats.p, n_mates, e->stream);   // (the ranks' totals add up)
     for (int m = 0; m < n_mates; m++) {   // the records this rank pushed join the device tally, so that the sum over ranks is the sample's
         if (e->pushed_records[m]) bk::launch_add_const_u64(e->kstats.p + m * 4 + 0, e->pushed_records[m], e->stream);
         e->pushed_records[m] = 0;
@@ -2724,12 +2822,12 @@ int bk_sample_finalize_shard(bk_engine* e, int n_mates, int shard, int n_shards)
 int bk_kmer_table_partition(bk_engine* e, int n_parts, void** d_keys, void** d_counts, uint64_t* part_off) {
     if (!e || !d_keys || !d_counts || !part_off) return fail(BK_ERR_INVALID, "null argument");
     if (n_parts < 1 || n_parts > (int)bk::kMaxShards) return fail(BK_ERR_INVALID, "1 <= n_parts <= %u", bk::kMaxShards);
-    if (!e->ktab_keys.p) return fail(BK_ERR_STATE, "the engine was created without full_kmer_stats");
+    if (!e->ktab.keys.p) return fail(BK_ERR_STATE, "the engine was created without full_kmer_stats");
     if (!e->in_sample) return fail(BK_ERR_STATE, "bk_kmer_table_partition comes between the pushes and the finalize of a sample");
     BK_HIP(hipSetDevice(e->device));
     if (!e->xchg_cursors.p) BK_HIP(e->xchg_cursors.alloc(bk::kMaxShards));
     BK_HIP(hipMemsetAsync(e->xchg_cursors.p, 0, bk::kMaxShards * sizeof(unsigned long long), e->stream));
-    bk::launch_ktab_count_parts(e->ktab_keys.p, e->ktab_log2, (uint32_t)n_parts, e->xchg_cursors.p, e->stream);
+    bk::launch_ktab_count_parts(e->ktab.keys.p, e->ktab.log2, (uint32_t)n_parts, e->xchg_cursors.p, e->stream);
     unsigned long long counts[bk::kMaxShards];
     BK_HIP(hipMemcpyAsync(counts, e->xchg_cursors.p, (size_t)n_parts * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
     BK_HIP(hipStreamSynchronize(e->stream));
@@ -2742,7 +2840,7 @@ int bk_kmer_table_partition(bk_engine* e, int n_parts, void** d_keys, void** d_c
         BK_HIP(e->xchg_cnt.alloc(e->xchg_keys.n));
     }
     BK_HIP(hipMemcpyAsync(e->xchg_cursors.p, first, (size_t)n_parts * sizeof(unsigned long long), hipMemcpyHostToDevice, e->stream));
-    bk::launch_ktab_scatter_parts(e->ktab_keys.p, e->ktab_cnt.p, e->ktab_log2, (uint32_t)n_parts, e->xchg_cursors.p, e->xchg_keys.p, e->xchg_cnt.p, e->stream);
+    bk::launch_ktab_scatter_parts(e->ktab.keys.p, e->ktab.cnt.p, e->ktab.log2, (uint32_t)n_parts, e->xchg_cursors.p, e->xchg_keys.p, e->xchg_cnt.p, e->stream);
     BK_HIP(hipGetLastError());
     BK_HIP(hipStreamSynchronize(e->stream));   // (`first` is read by the copy above; the caller reads the arrays on its own stream)
     *d_keys = e->xchg_keys.p; *d_counts = e->xchg_cnt.p;
@@ -2751,18 +2849,18 @@ int bk_kmer_table_partition(bk_engine* e, int n_parts, void** d_keys, void** d_c
 
 int bk_kmer_table_replace(bk_engine* e, const void* d_keys, const void* d_counts, uint64_t n) {
     if (!e || (n && (!d_keys || !d_counts))) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->ktab_keys.p) return fail(BK_ERR_STATE, "the engine was created without full_kmer_stats");
+    if (!e->ktab.keys.p) return fail(BK_ERR_STATE, "the engine was created without full_kmer_stats");
     if (!e->in_sample) return fail(BK_ERR_STATE, "bk_kmer_table_replace comes between the pushes and the finalize of a sample");
     BK_HIP(hipSetDevice(e->device));
     // an empty table with room for the n entries (and, like after any push, for what finalize adds: the load stays below a half)
-    BK_HIP(hipMemsetAsync(e->ktab_keys.p, 0xff, e->ktab_keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(e->ktab_cnt.p, 0, e->ktab_cnt.n * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(e->ktab.keys.p, 0xff, e->ktab.keys.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(e->ktab.cnt.p, 0, e->ktab.cnt.n * sizeof(unsigned int), e->stream));
     BK_HIP(hipMemsetAsync(e->ktab_out.p + 8, 0, bk::ktab_fill_words() * sizeof(unsigned long long), e->stream));
-    if (e->fill_pending) { BK_HIP(hipEventSynchronize(e->fill_ev)); e->fill_pending = false; }
-    e->fill_known = 0; e->fill_unknown_upper = 0;
+    if (e->ktab.fill_pending) { BK_HIP(hipEventSynchronize(e->ktab.fill_ev)); e->ktab.fill_pending = false; }
+    e->ktab.fill_known = 0; e->ktab.fill_unknown_upper = 0;
     if (int rc = ensure_ktab_room(e, n)) return rc;
-    bk::launch_ktab_import(static_cast<const unsigned long long*>(d_keys), static_cast<const unsigned int*>(d_counts), n, e->ktab_keys.p, e->ktab_cnt.p,
-                           e->ktab_log2, e->ktab_out.p + 4, e->stream);
+    bk::launch_ktab_import(static_cast<const unsigned long long*>(d_keys), static_cast<const unsigned int*>(d_counts), n, e->ktab.keys.p, e->ktab.cnt.p,
+                           e->ktab.log2, e->ktab_out.p + 4, e->stream);
     BK_HIP(hipGetLastError());
     e->ktab_exchanged = true;
     return note_ktab_fill(e);
@@ -2911,7 +3009,7 @@ int bk_sample_download(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t*
     if (kmer_stats) {
         for (int m = 0; m < n_mates; m++) {
             kmer_stats[m * 4 + 0] += e->pushed_records[m];   // + the device-side tally of bk_push_reads_ascii batches
-            if (e->ktab_keys.p) {
+            if (e->ktab.keys.p) {
                 // index-touching k-mers are in the counter plane (kept tally in [3], distinct tally in [2] by finalize);
                 // the rest are in the hash table
                 if (kt[4] || kmer_stats[m * 4 + 2] >= (1ull << 56)) { kmer_stats[m * 4 + 2] = kmer_stats[m * 4 + 3] = ~0ull; }   // (2^56: a rank's table overflowed, sharded finalize)
@@ -2929,6 +3027,63 @@ int bk_sample_finish(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t* r
     int rc = bk_sample_finalize(e, n_mates);
     if (rc != BK_OK) return rc;
     return bk_sample_download(e, n_mates, fwd_depth, rev_depth, fwd_nk, rev_nk, stats, present, kmer_stats);
+}
+
+// ---- the sample's k-mer count table (bk_kmer_dump.hip) --------------------------------------------------------------
+int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (table_log2 != 0 && (table_log2 < 10 || table_log2 > 31)) return fail(BK_ERR_INVALID, "table_log2 must be 0 or 10..31");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_kmer_dump_enable comes between samples");
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still read the table being replaced)
+    e->dump.reset();
+    if (table_log2 == 0) return BK_OK;
+    std::unique_ptr<KmerDump> d(new KmerDump());
+    BK_HIP(d->t.keys.alloc((size_t)1 << table_log2));
+    BK_HIP(d->t.cnt.alloc((size_t)1 << table_log2));
+    d->t.log2 = table_log2;
+    BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->t.h_fill), bk::ktab_fill_words() * sizeof(unsigned long long), hipHostMallocDefault));
+    BK_HIP(hipEventCreateWithFlags(&d->t.fill_ev, hipEventDisableTiming));
+    BK_HIP(d->out.alloc(8 + bk::ktab_fill_words()));
+    BK_HIP(hipMemset(d->out.p, 0, d->out.n * sizeof(unsigned long long)));
+    e->dump = std::move(d);
+    return BK_OK;
+}
+
+static int dump_results(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct) {
+    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
+    if (!e->dump || !e->dump->in_sample) return fail(BK_ERR_STATE, "the k-mer dump was not enabled for this sample (bk_kmer_dump_enable before bk_sample_begin)");
+    if (e->in_sample) return fail(BK_ERR_STATE, "the k-mer dump is read after bk_sample_finalize");
+    if (mate >= e->dump->finalized_mates)
+        return fail(BK_ERR_STATE, "mate file %d of this sample was not finalized by bk_sample_finalize (a sharded finalize keeps no k-mer dump)", mate);
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long o[8];
+    BK_HIP(hipMemcpyAsync(o, e->dump->out.p, sizeof o, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    if (o[4] || o[2 * mate] > e->dump->n_sorted[mate]) { *n_kept = *n_distinct = UINT64_MAX; return BK_OK; }   // (only a table that could not grow past 2^31 slots)
+    *n_kept = o[2 * mate];
+    *n_distinct = o[2 * mate + 1];
+    return BK_OK;
+}
+
+int bk_kmer_dump_size(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct) {
+    if (!e || !n_kept || !n_distinct) return fail(BK_ERR_INVALID, "null argument");
+    return dump_results(e, mate, n_kept, n_distinct);
+}
+
+int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* counts, uint64_t cap) {
+    if (!e || ((!kmers || !counts) && cap)) return fail(BK_ERR_INVALID, "null argument");
+    uint64_t kept = 0, distinct = 0;
+    if (int rc = dump_results(e, mate, &kept, &distinct)) return rc;
+    if (kept == UINT64_MAX) return fail(BK_ERR_RANGE, "the k-mer count table overflowed at 2^31 slots: no dump for this sample");
+    const uint64_t n = std::min(cap, kept);
+    if (!n) return BK_OK;
+    std::vector<unsigned int> c32(n);
+    BK_HIP(hipMemcpyAsync(kmers, e->dump->keys[mate].p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipMemcpyAsync(c32.data(), e->dump->cnt[mate].p, n * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    for (uint64_t i = 0; i < n; i++) counts[i] = c32[i];
+    return BK_OK;
 }
 
 // ---- after the pileup, on the device (bk_caller.hip) -----------------------------------------------------------

@@ -282,6 +282,17 @@ void launch_ktab_import(const unsigned long long* in_keys, const unsigned int* i
                         unsigned long long* overflow, hipStream_t stream);
 void launch_ktab_totals_to_kstats(unsigned long long* ktab_out, unsigned long long* kstats, int n_mates, hipStream_t stream);
 uint32_t ktab_fill_words();   // tallies of new keys behind the overflow word: ktab_out[8 ..]
+// the sample's k-mer count table (bk_kmer_dump.hip; bk_kmer_dump_enable): count every k-mer of a batch of records (n_records_dev: the
+// ASCII paths' record count, known on the device only); per mate file, select ci <= count <= cx as (k-mer, min(count, cs)) into
+// out_* (at most cap; res[0] = kept, res[1] = distinct); sort the pairs by k-mer (rocprim; tmp == nullptr: tmp_bytes is sized)
+void launch_kmer_dump_count(const uint32_t* words, const uint16_t* lens, uint64_t n_records, const unsigned long long* n_records_dev,
+                            uint32_t stride_words, int k, uint32_t mate, unsigned long long* keys, unsigned int* cnt, uint32_t log2n,
+                            unsigned long long* overflow, int n_cus, hipStream_t stream);
+void launch_kmer_dump_select(const unsigned long long* keys, const unsigned int* cnt, uint32_t log2n, uint32_t mate, unsigned long long ci,
+                             unsigned long long cs, unsigned long long cx, unsigned long long* out_keys, unsigned int* out_cnt, uint64_t cap,
+                             unsigned long long* res, hipStream_t stream);
+hipError_t kmer_dump_sort(void* tmp, size_t& tmp_bytes, unsigned long long* keys_in, unsigned long long* keys_out, unsigned int* vals_in,
+                          unsigned int* vals_out, uint64_t n, int k, hipStream_t stream);
 void launch_finalize(const FinalizeArgs& a, hipStream_t stream);
 // K2a / K2e organised by region of the reference (bk_finalize_lean.hip): one genome file, dense planes, one pass
 bool finalize_lean_ok(const FinalizeArgs& a);

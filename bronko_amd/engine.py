@@ -259,6 +259,25 @@ class Engine:
         """... and the table rebuilt from the entries this rank owns (device pointers; equal keys add up)."""
         _check(self._L.bk_kmer_table_replace(self.h, keys_ptr, counts_ptr, n), self._L)
 
+    def kmer_dump_enable(self, log2=26):
+        """Count every strand-specific k-mer of the samples from the next sample_begin on (bk_kmer_dump_enable; 0 disables):
+        the KMC -b -ci -cs -cx table that `bronko call --keep-kmer-info` writes out."""
+        _check(self._L.bk_kmer_dump_enable(self.h, log2), self._L)
+
+    def kmer_dump_size(self, mate=0):
+        """(n_kept, n_distinct) of a finalized mate file (2**64 - 1 for both if the table overflowed)."""
+        kept, distinct = C.c_uint64(), C.c_uint64()
+        _check(self._L.bk_kmer_dump_size(self.h, mate, C.byref(kept), C.byref(distinct)), self._L)
+        return kept.value, distinct.value
+
+    def kmer_dump(self, mate=0):
+        """(kmers u64[], counts u64[]) of a finalized mate file: the kept k-mers ascending (MSB-first 2-bit codes), min(count, cs)."""
+        kept, _ = self.kmer_dump_size(mate)
+        km = np.zeros(max(kept, 1), np.uint64)
+        ct = np.zeros(max(kept, 1), np.uint64)
+        _check(self._L.bk_kmer_dump_download(self.h, mate, km.ctypes.data, ct.ctypes.data, kept), self._L)
+        return km[:kept], ct[:kept]
+
     @property
     def full_kmer_stats(self):
         return bool(self.params.full_kmer_stats)

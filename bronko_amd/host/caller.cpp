@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
+#include <thread>
 
 #include "lcb.hpp"
 
@@ -222,6 +223,47 @@ std::string clean_sample_id(const std::string& path) {
     const size_t dot = name.find_last_of('.');
     if (dot != std::string::npos && dot != 0) name.resize(dot);
     return name;
+}
+
+// --keep-kmer-info (call.rs:1202-1211): one "KMER\tCOUNT\n" line per entry, in the order given (the engine's: ascending k-mer).
+// Pieces of the table are formatted on `threads` threads, a piece at a time per thread, and written in order.
+void write_kmer_counts(const std::string& out_path, int k, const uint64_t* kmers, const uint64_t* counts, uint64_t n, int threads) {
+    if (k < 1 || k > 32) throw std::runtime_error("write_kmer_counts: k out of range");
+    File f(out_path);
+    if (!f.fp) throw std::runtime_error("Failed to create k-mer count file " + out_path);
+    const unsigned nt = (unsigned)std::max(1, threads);
+    const uint64_t piece = 1u << 16;   // entries per piece (about 2 MB of text at k = 21)
+    const uint64_t n_pieces = (n + piece - 1) / piece;
+    auto format = [&](uint64_t p, std::string& out) {
+        const uint64_t i0 = p * piece, i1 = std::min(n, i0 + piece);
+        out.resize((size_t)(i1 - i0) * ((size_t)k + 22));
+        char* q = &out[0];
+        for (uint64_t i = i0; i < i1; i++) {
+            const uint64_t v = kmers[i];
+            for (int j = 0; j < k; j++) *q++ = "ACGT"[(v >> (2 * (k - 1 - j))) & 3];
+            *q++ = '\t';
+            char d[24];
+            int nd = 0;
+            uint64_t c = counts[i];
+            do { d[nd++] = (char)('0' + c % 10); c /= 10; } while (c);
+            while (nd) *q++ = d[--nd];
+            *q++ = '\n';
+        }
+        out.resize((size_t)(q - &out[0]));
+    };
+    // rounds of nt pieces: formatted side by side, written one after the other
+    std::vector<std::string> buf(nt);
+    for (uint64_t p0 = 0; p0 < n_pieces; p0 += nt) {
+        const unsigned m = (unsigned)std::min<uint64_t>(nt, n_pieces - p0);
+        if (m == 1) format(p0, buf[0]);
+        else {
+            std::vector<std::thread> th;
+            for (unsigned t = 0; t < m; t++) th.emplace_back([&, t] { format(p0 + t, buf[t]); });
+            for (auto& t : th) t.join();
+        }
+        for (unsigned t = 0; t < m; t++)
+            if (fwrite(buf[t].data(), 1, buf[t].size(), f.fp) != buf[t].size()) throw std::runtime_error("Failed to write k-mer count file " + out_path);
+    }
 }
 
 void write_vcf(const std::string& out_path, const std::string& reads_path, const Index& ix, int file_id, const std::vector<VcfRecord>& recs) {

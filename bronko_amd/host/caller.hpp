@@ -59,6 +59,9 @@ CallSummary call_variants(const Index& ix, int file_id, const Pileup& p, const C
 std::string clean_sample_id(const std::string& path);                               // util.rs:30-50
 void write_vcf(const std::string& out_path, const std::string& reads_path_as_given, const Index& ix, int file_id,
                const std::vector<VcfRecord>& recs);                                 // call.rs:735-774
+// --keep-kmer-info: <output>/<stem>_counts.txt of one reads file (call.rs:1202-1211), "KMER\tCOUNT\n" per entry, k-mers as MSB-first
+// 2-bit codes (A=0 C=1 G=2 T=3) written in upper-case ACGT, in the order given; formatted on `threads` threads
+void write_kmer_counts(const std::string& out_path, int k, const uint64_t* kmers, const uint64_t* counts, uint64_t n, int threads);
 void write_pileup_tsv(const std::string& out_path, const Index& ix, int file_id, const Pileup& p);  // call.rs:648-695
 
 struct OverviewRow {                 // call.rs:138-149

@@ -51,6 +51,7 @@ void logf(int lvl, const char* tag, const char* target, const std::string& msg) 
 #define LOG_ERROR(t, m) logf(0, "ERROR", t, m)
 #define LOG_WARN(t, m) logf(1, "WARN", t, m)
 #define LOG_INFO(t, m) logf(2, "INFO", t, m)
+#define LOG_DEBUG(t, m) logf(3, "DEBUG", t, m)
 #define LOG_TRACE(t, m) logf(4, "TRACE", t, m)
 
 // `error!(..); std::process::exit(1)`.  Every thread leaves through _exit() (streams flushed first; the first error wins):
@@ -112,7 +113,9 @@ struct Args {
           "            [--use-full-kmer] [--n-fixed N] [--min-af F] [--no-end-filter] [--no-strand-filter]\n"
           "            [--no-strand-balance-filter] [--balance-ratio F] [--n-per-strand N] [--strand_odds F]\n"
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
-          "            [--alignment] [--keep-kmer-info] [-t <THREADS>] [--debug] [--verbose]\n", stderr);
+          "            [--alignment] [--keep-kmer-info] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
+          "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n", stderr);
     exit(code);
 }
 
@@ -765,6 +768,10 @@ int run_call(const Args& a) {
     for (int d : devices) if (std::find(shard_devices.begin(), shard_devices.end(), d) == shard_devices.end()) shard_devices.push_back(d);
     bool shard_mode = shard_devices.size() >= 2 && n_samples_total < shard_devices.size();
     if (const char* sh = getenv("BRONKO_SHARD")) shard_mode = atoi(sh) != 0;
+    if (shard_mode && a.keep_kmer_info) {   // (the k-mer counts of a sample are one engine's: whole samples go to the GPUs in turn)
+        LOG_DEBUG(T, "--keep-kmer-info: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
     if (devices.size() > std::max<size_t>(n_samples_total, 1)) devices.resize(std::max<size_t>(n_samples_total, 1));   // no more lanes than samples
     auto make_engine = [&](int device, Engine& out, bool selected_only = true) {
@@ -900,6 +907,8 @@ int run_call(const Args& a) {
         LOG_INFO(T, std::to_string(total_reads) + " reads counted from " + mates[0]);
         return total_reads;
     };
+    constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
+    const int dump_threads = (int)std::max<size_t>(1, std::min<size_t>(16, (size_t)a.threads / std::max<size_t>(1, lanes.size())));
     auto complete = [&](bk_engine* e, const std::vector<std::string>& mates, size_t sample_id, bool finalized = false) {
         const int n_mates = (int)mates.size();
         Pileup p;
@@ -919,6 +928,19 @@ int run_call(const Args& a) {
         if (a.pileup) { p.fwd_depth.resize(cells4); p.rev_depth.resize(cells4); }
         hip_check(bk_sample_download(e, n_mates, a.pileup ? p.fwd_depth.data() : nullptr, a.pileup ? p.rev_depth.data() : nullptr, nullptr, nullptr,
                                      stats.data(), present.data(), kstats.data()), "bk_sample_download");
+        if (a.keep_kmer_info) {   // call.rs:1202-1211, kept by --keep-kmer-info (:404-420): <output>/<stem>_counts.txt per reads file
+            for (int m = 0; m < n_mates; m++) {
+                uint64_t n_kept = 0, n_distinct = 0;
+                hip_check(bk_kmer_dump_size(e, m, &n_kept, &n_distinct), "bk_kmer_dump_size");
+                if (n_kept == ~0ull) die(T, "k-mer count table overflowed: --keep-kmer-info cannot write the counts of " + mates[(size_t)m]);
+                std::vector<uint64_t> km(std::max<uint64_t>(n_kept, 1)), ct(std::max<uint64_t>(n_kept, 1));
+                hip_check(bk_kmer_dump_download(e, m, km.data(), ct.data(), n_kept), "bk_kmer_dump_download");
+                const std::string path = a.output + "/" + clean_sample_id(mates[(size_t)m]) + "_counts.txt";
+                LOG_DEBUG(T, "Writing " + std::to_string(n_kept) + " k-mer counts (" + std::to_string(n_distinct) + " distinct k-mers) to " + path);
+                try { write_kmer_counts(path, (int)a.kmer, km.data(), ct.data(), n_kept, dump_threads); }
+                catch (const std::exception& ex) { die(T, ex.what()); }
+            }
+        }
         uint64_t longest = 1;   // at most three alternative bases per position of the selected genome
         for (size_t f = 0; f < n_files; f++) longest = std::max<uint64_t>(longest, ix.genome_len(f));
         std::vector<bk_call_record> drecs((size_t)(3 * longest));
@@ -994,6 +1016,9 @@ int run_call(const Args& a) {
     for (size_t i = 0; i < samples.size() && !lanes.empty(); i++) lanes[i % lanes.size()].mine.push_back(i);
     auto run_lane = [&](Lane& ln) {
         if (ln.mine.size() > 1) hip_check(bk_engine_fork(ln.eng.e, &ln.fork.e), "bk_engine_fork");
+        if (a.keep_kmer_info)   // (the table grows with the sample)
+            for (bk_engine* e : {ln.eng.e, ln.fork.e})
+                if (e) hip_check(bk_kmer_dump_enable(e, kDumpTableLog2), "bk_kmer_dump_enable");
         std::thread worker;     // completes the lane's previous sample
         for (size_t n = 0; n < ln.mine.size(); n++) {
             const size_t i = ln.mine[n];

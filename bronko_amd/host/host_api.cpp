@@ -114,6 +114,11 @@ int bh_call_and_write(const void* h, int file_id, const uint64_t* fwd_depth, con
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
+int bh_write_kmer_counts(const char* path, int k, const uint64_t* kmers, const uint64_t* counts, uint64_t n, int threads) {
+    try { bronko::write_kmer_counts(path, k, kmers, counts, n, threads); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
 void bh_clean_sample_id(const char* path, char* buf, size_t n) {
     const std::string s = bronko::clean_sample_id(path);
     snprintf(buf, n, "%s", s.c_str());

@@ -148,6 +148,8 @@ def _caller_lib():
         L.bh_baseline_noise_max.argtypes = [vp, vp, C.c_uint64, vp]
         L.bh_call_and_write.restype = C.c_int
         L.bh_call_and_write.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(CallParams), C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
+        L.bh_write_kmer_counts.restype = C.c_int
+        L.bh_write_kmer_counts.argtypes = [C.c_char_p, C.c_int, vp, vp, C.c_uint64, C.c_int]
         L.bh_clean_sample_id.restype = None
         L.bh_clean_sample_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L._caller_ready = True
@@ -186,3 +188,13 @@ def clean_sample_id(path):
     buf = C.create_string_buffer(4096)
     _caller_lib().bh_clean_sample_id(path.encode(), buf, 4096)
     return buf.value.decode()
+
+
+def write_kmer_counts(path, k, kmers, counts, threads=4):
+    """The --keep-kmer-info writer (caller.cpp write_kmer_counts): "KMER\tCOUNT\n" per entry, in the order given."""
+    km = np.ascontiguousarray(kmers, np.uint64)
+    ct = np.ascontiguousarray(counts, np.uint64)
+    assert len(km) == len(ct)
+    L = _caller_lib()
+    if L.bh_write_kmer_counts(path.encode(), k, km.ctypes.data, ct.ctypes.data, len(km), threads) != 0:
+        raise RuntimeError("bronko host: " + L.bh_last_error().decode(errors="replace"))

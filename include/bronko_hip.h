@@ -248,6 +248,20 @@ int bk_sample_download(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t*
 int bk_sample_finish(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t* rev_depth, uint64_t* fwd_nk,
                      uint64_t* rev_nk, uint64_t* stats, uint8_t* present, uint64_t* kmer_stats);
 
+/* ---- the sample's k-mer counts (optional; `bronko call --keep-kmer-info`, call.rs:1202-1211, :404-420) ------------------
+ * Count table of every strand-specific k-mer of the pushed records, per mate file: the KMC -k -b -ci -cs -cx contract of
+ * SURVEY.md A.3 (a k-mer is kept iff ci <= its true count <= cx; the count reported is min(count, cs)).  A second pass over the
+ * records of every push (all four push paths), on the engine's stream; the select and the sort run inside bk_sample_finalize.
+ * table_log2 = initial capacity 2^table_log2 slots (10..31; it grows like full_kmer_stats' table); 0 disables and frees.
+ * Between samples only (BK_ERR_STATE inside one).  Per engine: forks enable their own. */
+int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2);
+/* After bk_sample_finalize / _finish: synchronises; n_kept = entries that pass ci/cx, n_distinct = distinct k-mers of the mate.
+ * BK_ERR_STATE if the dump was not enabled for this sample, the mate was not finalized, or the sample was finalized by shards.
+ * n_kept = n_distinct = UINT64_MAX if the table overflowed at 2^31 slots.  Valid until the engine's next bk_sample_begin. */
+int bk_kmer_dump_size(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct);
+/* Copies min(cap, n_kept) entries, ascending by k-mer: MSB-first 2-bit codes (A=0 C=1 G=2 T=3), counts = min(count, cs). */
+int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* counts, uint64_t cap);
+
 /* ---- after the pileup, on the device (optional) ----------------------------------------------
  * For the sample just finalized, asynchronously on the engine's stream:
  *     pick_best_genome / pick_best_genome_paired   call.rs:422-502  (ties -> lowest file id; statistics summed over mates)
