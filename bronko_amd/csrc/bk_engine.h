@@ -1,0 +1,358 @@
+// bk_engine.h -- private to the host side of the engine (bk_engine.cpp, bk_index_tables.cpp): error reporting, device buffers,
+// host-thread helpers, the index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/bronko_hip.h"
+#include "bk_device.h"
+#include "bk_kernels.h"
+
+// (the library's exports are the C ABI of bronko_hip.h: nothing declared here leaves it)
+#pragma GCC visibility push(hidden)
+
+extern thread_local std::string g_err;   // bk_last_error
+
+int fail(int code, const char* fmt, ...);
+
+#define BK_HIP(expr)                                                                                  \
+    do {                                                                                              \
+        hipError_t _e = (expr);                                                                       \
+        if (_e != hipSuccess) return fail(BK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+// One device allocation, freed with its owner.  Not copyable: a copy would free the same memory twice.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t count) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = count;
+        return hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T));
+    }
+    template <class A>
+    hipError_t upload(const std::vector<T, A>& h) {
+        hipError_t e = alloc(h.size());
+        if (e != hipSuccess || h.empty()) return e;
+        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+static_assert(!std::is_copy_constructible_v<DevBuf<int>> && !std::is_copy_assignable_v<DevBuf<int>>, "DevBuf owns its memory");
+
+struct TimedSpan { hipEvent_t a, b; int kind; };
+
+// fn(begin, end) over [0, n) on up to hardware_concurrency() threads (capped at 256): host-side table construction only
+template <typename F>
+void parallel_for(size_t n, F&& fn) {
+    unsigned nt = std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 256u);
+    if (n < (size_t)nt * 1024) { fn((size_t)0, n); return; }
+    std::vector<std::thread> th;
+    const size_t per = (n + nt - 1) / nt;
+    for (unsigned i = 0; i < nt; i++) {
+        const size_t b = std::min(n, i * per), en = std::min(n, b + per);
+        if (b < en) th.emplace_back([&fn, b, en] { fn(b, en); });
+    }
+    for (auto& t : th) t.join();
+}
+
+// A host array whose elements are not initialised by its constructor (the GB-sized tables of a many-genome index: a serial
+// value-initialisation was 0.3 s each; they are filled by parallel_for)
+template <class T>
+struct NoInitAlloc : std::allocator<T> {
+    template <class U> struct rebind { using other = NoInitAlloc<U>; };
+    template <class U, class... A>
+    void construct(U* p, A&&... a) {
+        if constexpr (sizeof...(A) == 0) ::new (static_cast<void*>(p)) U;
+        else ::new (static_cast<void*>(p)) U(std::forward<A>(a)...);
+    }
+};
+template <class T> using HostVec = std::vector<T, NoInitAlloc<T>>;
+template <class T>
+HostVec<T> filled(size_t n, const T& v) {
+    HostVec<T> a(n);
+    parallel_for(n, [&](size_t i0, size_t i1) { std::fill(a.begin() + (ptrdiff_t)i0, a.begin() + (ptrdiff_t)i1, v); });
+    return a;
+}
+
+// Testing / measurement aids exist only in the -DBK_TESTING build (libbronko_hip_testing.so, loaded by the tests that force a
+// path and by the profiling tools); the release library reads no environment variable.
+#ifdef BK_TESTING
+inline const char* test_env(const char* name) { return getenv(name); }
+#else
+inline const char* test_env(const char*) { return nullptr; }
+#endif
+
+// BK_CREATE_TIMING=1 (testing build): wall-clock of the phases of bk_engine_create on stderr (host-side table construction)
+struct PhaseClock {
+    bool on = test_env("BK_CREATE_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char* what) {
+        if (!on) return;
+        const auto n = std::chrono::steady_clock::now();
+        fprintf(stderr, "[bk_engine_create] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count());
+        t = n;
+    }
+};
+
+// An open-addressing table of u64 keys (~0 = free) and u32 counts whose load stays below one half as a sample fills it
+// (ensure_table_room): full_kmer_stats' statistics table and the k-mer dump's count table (bk_kmer_dump_enable).  Its device-side
+// companion `out` holds the overflow flag at [4] and the tallies of new keys at [8 ..] (ktab_insert_key, kmer_dump_count_kernel).
+struct GrowTable {
+    DevBuf<unsigned long long> keys;
+    DevBuf<unsigned int> cnt;
+    uint32_t log2 = 0;                      // current capacity (grows with the sample: ensure_table_room)
+    unsigned long long* h_fill = nullptr;   // pinned copy of the tallies, refreshed after every push
+    hipEvent_t fill_ev = nullptr;
+    bool fill_pending = false;              // a copy of the tallies is in flight / unread
+    uint64_t fill_known = 0, fill_unknown_upper = 0;   // keys in the table at the last reading; k-mers pushed since (upper bound on new keys)
+    std::vector<std::pair<unsigned long long*, unsigned int*>> old;   // outgrown tables, freed at the next sample / destroy
+    ~GrowTable() {
+        for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); }
+        if (h_fill) (void)hipHostFree(h_fill);
+        if (fill_ev) (void)hipEventDestroy(fill_ev);
+    }
+};
+
+// bk_kmer_dump_enable: the sample's count table of every strand-specific k-mer (bk_kmer_dump.hip) and, per finalized mate file, its
+// selected entries sorted by k-mer
+struct KmerDump {
+    GrowTable t;
+    DevBuf<unsigned long long> out;         // [mate][2] kept, distinct + [4] overflow flag + [8 ..] tallies of new keys
+    DevBuf<unsigned long long> sel_keys, keys[2];   // selected (unsorted, padded with ~0) -> sorted, per mate file
+    DevBuf<unsigned int> sel_cnt, cnt[2];
+    DevBuf<unsigned char> sort_tmp;
+    uint64_t upper[2] = {0, 0};             // k-mers pushed per mate file in this sample (bounds its distinct keys)
+    uint64_t n_sorted[2] = {0, 0};          // length of the sorted arrays of the last finalize (selected entries, then padding)
+    bool in_sample = false;                 // enabled when the current / last sample began
+    int finalized_mates = 0;                // mate files the last finalize selected (0: none, or finalized by shards)
+};
+
+// What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
+// by an engine and its forks, freed with the last of them.
+struct IndexTables {
+    // engines that share these tables (the creating one and its forks, alive): with samples in flight next to each other the
+    // binned scan leaves a quarter of the CUs to the siblings' small kernels (push_device)
+    mutable std::atomic<int> family{1};
+    int k = 0, wstart = 0, W = 0, n_files = 0;
+    uint64_t total_cells = 0, n_slots = 0;
+    uint32_t log2s = 4, log2nb = 0, log2p = 0, m = 1, n_u = 0, n_full = 0, n_lds_bins = 0;
+    uint64_t n_prows = 0;  // V rows of the pseudo k-mers (bk_device.h)
+    int v_omin = 0, v_span = 0;
+    uint64_t v_off = 0, plane_len = 0;      // counter_plane_layout (bk_device.h)
+    DevBuf<uint32_t> prow_id;
+    DevBuf<uint8_t> prow_t;
+    bool ref_in_lds = false;
+    int lo_bases = 0, n_cus = 256;
+
+    DevBuf<bk::KmerPos> kmer_pos;
+    DevBuf<bk::IndexView> d_view;   // device copy of view()
+    DevBuf<uint64_t> kmer_of;
+    DevBuf<bk::IdRec> id_rec;
+    DevBuf<bk::DirtyAns> dirty_ans;
+    DevBuf<uint8_t> cell_flags;
+    DevBuf<uint32_t> ref_words, cell_codes, cell_has, cell_clean, cell_clean3, cell_yf, cell_yr, id_at, cell_fast, cell_nat, cell_natrow;
+    DevBuf<uint2> cell_blk, seed_tab, seed_tab2;
+    uint32_t seed_log2 = 0, seed2_log2 = 0;
+    DevBuf<uint32_t> rc_words;              // the reference read backwards and complemented (scan_items_kernel: reads against the reference)
+    struct HalfBufs { DevBuf<uint16_t> pilots; DevBuf<bk::HalfDir> dir; DevBuf<bk::NbEntry> cand; uint32_t m = 1, log2nb = 0, log2p = 0; DevBuf<uint32_t> bits; uint32_t bits_log2 = 0, bits_exact = 0; } half_lo, half_hi;
+    DevBuf<uint32_t> slot_of, estat_off, estat;
+    DevBuf<bk::SlotRec> slot_rec;
+    DevBuf<uint4> ent_files, slot_files, id_own_files, estat_files;
+    DevBuf<uint16_t> cell_file;
+    DevBuf<uint32_t> slot_alias;
+    DevBuf<uint64_t> merged_slots;          // [n_merged_slots][2]: slot | window position << 32, the slot's key
+    uint32_t n_merged_slots = 0;
+    bool gather_ok = false;                 // IndexView::gather_ok
+    DevBuf<uint32_t> id_rest_off, id_rest;
+    DevBuf<uint8_t> amb;
+    DevBuf<uint16_t> pilots;
+    DevBuf<bk::TableSlot> table;
+    DevBuf<uint32_t> ent_off, ent_len;
+    DevBuf<bk::DevEntry> entries;
+    // multi-genome indexes: the LDS window (difference array + Level 1's arrays) sits on the genome the sample looks like
+    DevBuf<uint32_t> occ;                   // [n_full][n_files] first occurrence of each reference k-mer in each genome file
+    DevBuf<uint32_t> file_cell_lo_d;        // [n_files]
+    std::vector<uint32_t> file_cell_lo;     // first cell of each genome file
+    // after the pileup (bk_sample_call): sequence geometry
+    DevBuf<uint64_t> genome_len, seq_cell, seq_len_d;
+    DevBuf<int32_t> seq_first, n_seqs_d;
+    int max_seqs_per_file = 0;
+    uint64_t max_file_cells = 0;
+    uint64_t max_file_cells_idx = 0;        // cells of the genome file with the most (pileup rows)
+    // testing aids read at create (a fork sees its parent's values)
+    int ablate = 0;   // BK_SCAN_ABLATE (measurement aid): see scan_count_kernel
+    int item_v_mode = -1;                   // BK_ITEM_V_MODE: force BinArgs::v_mode
+    uint64_t max_launch_records = 0;   // BK_MAX_LAUNCH_RECORDS: split pushes into launches of at most this many records
+
+    bk::IndexView view() const {
+        bk::IndexView v{};
+        v.kmer_pos = kmer_pos.p; v.pilots = pilots.p; v.m = m; v.log2nb = log2nb; v.log2p = log2p;
+        v.kmer_of = kmer_of.p; v.id_rec = id_rec.p; v.dirty_ans = dirty_ans.p; v.cell_flags = cell_flags.p; v.ref_words = ref_words.p; v.cell_codes = cell_codes.p; v.cell_has = cell_has.p; v.cell_clean = cell_clean.p; v.cell_clean3 = cell_clean3.p; v.cell_yf = cell_yf.p; v.cell_yr = cell_yr.p; v.id_at = id_at.p; v.cell_fast = cell_fast.p; v.cell_nat = cell_nat.p; v.cell_natrow = cell_natrow.p; v.cell_blk = cell_blk.p; v.seed_tab = seed_tab.p; v.seed_log2 = seed_log2; v.total_cells = (uint32_t)total_cells; v.n_u = n_u;
+        v.n_full = n_full; v.n_prows = n_prows; v.prow_id = prow_id.p; v.prow_t = prow_t.p; v.v_omin = v_omin; v.v_span = v_span; v.v_off = v_off;
+        v.lo = bk::HalfView{half_lo.pilots.p, half_lo.dir.p, half_lo.cand.p, half_lo.m, half_lo.log2nb, half_lo.log2p, half_lo.bits.p, half_lo.bits_log2, half_lo.bits_exact};
+        v.hi = bk::HalfView{half_hi.pilots.p, half_hi.dir.p, half_hi.cand.p, half_hi.m, half_hi.log2nb, half_hi.log2p, half_hi.bits.p, half_hi.bits_log2, half_hi.bits_exact};
+        v.lo_bases = lo_bases; v.slot_of = slot_of.p; v.slot_rec = slot_rec.p; v.ent_files = ent_files.p; v.slot_files = slot_files.p; v.slot_alias = slot_alias.p; v.gather_ok = gather_ok ? 1u : 0u; v.id_own_files = id_own_files.p; v.cell_file = cell_file.p; v.id_rest_off = id_rest_off.p; v.id_rest = id_rest.p; v.estat_files = estat_files.p; v.amb = amb.p; v.estat_off = estat_off.p; v.estat = estat.p;
+        v.table = table.p; v.ent_off = ent_off.p; v.ent_len = ent_len.p;
+        v.entries = entries.p; v.n_slots = n_slots; v.log2s = log2s; v.k = k; v.wstart = wstart; v.W = W; v.n_files = n_files;
+        return v;
+    }
+};
+
+// Builds `tab` (all but d_view, which the caller uploads last) from a validated index on the current device; the laps of `pc`
+// time its stages.  BK_OK or the error code, with bk_last_error set.
+int build_index_tables(const bk_index_desc* ix, const bk_params* prm, IndexTables& tab, PhaseClock& pc);
+
+// One engine: its parameters, its stream and all that a sample writes.  The index tables are `ix`, shared with the engine it was
+// forked from and its forks.
+struct bk_engine {
+    bk_params params{};
+    std::shared_ptr<const IndexTables> ix;
+    DevBuf<unsigned long long> shard_sums;  // sharded finalize: [stats 2*n_files*3 | present 2*n_files | kstats 8 | transport flag]
+    // sharded finalize, transport of the planes (bk_shard_transport / bk_shard_received): the packed plane of the mate file being
+    // exchanged, the part the reduce-scatter leaves here, and per mate file the received part widened to u64 again -- what
+    // bk_sample_finalize_shard maps (the plane itself stays as the scans left it)
+    DevBuf<unsigned char> xport_send, xport_recv;
+    DevBuf<unsigned long long> reduced[2];
+    DevBuf<unsigned long long> xport_flag;  // [0] a packer of this sample met a counter too large for its width, [1] sticky copy after
+                                            // the ranks' sums were merged, [2..3] bk_shard_measure: max E count, max |V element|
+    bool xport_ever = false;                // some sample of this engine went through bk_shard_transport (bk_sample_download then looks at the flag)
+    int reduced_shards[2] = {0, 0};         // > 0: reduced[m] holds part `reduced_shard[m]` of that many for the current sample
+    int reduced_shard[2] = {0, 0};
+    int device = 0;
+
+    DevBuf<unsigned int> deferred, n_deferred, deferred_mask;
+    DevBuf<unsigned long long> deferred_n;   // dense planes: the deferred k-mers' counts (K2a zeroes the counters it reads)
+    DevBuf<unsigned int> fin_partials;      // per-workgroup finalize tallies (small genome sets only)
+    GrowTable ktab;                         // full_kmer_stats: open-addressing table of non-index-touching k-mers
+    DevBuf<unsigned long long> ktab_out;    // [2 mates][2] distinct, kept  + [4] overflow flag + [8 ..] tallies of new keys
+    DevBuf<unsigned long long> xchg_keys, xchg_cursors;   // bk_kmer_table_partition: the table's entries grouped by owner rank
+    DevBuf<unsigned int> xchg_cnt;
+    bool ktab_exchanged = false;            // bk_kmer_table_replace was called in this sample
+    std::unique_ptr<KmerDump> dump;         // bk_kmer_dump_enable (null: no table, no launch)
+    // gathered votes (bk_gather.hip): this engine's voting pass is gather_votes_kernel (sparse planes of a many-genome index)
+    bool gather_mode = false;
+    DevBuf<unsigned int> row_bits;              // one bit per V row of the reference k-mers: touched by the sample (set by prefix_rows_kernel for voter_table_kernel)
+    DevBuf<uint32_t> vote_tab;                  // [n_full][W][8] the voters of every (reference k-mer, window position) of the sample (bk_gather.hip; every genome's rows)
+    DevBuf<unsigned long long> alias_hits[2];   // per mate file: the deferred k-mers that reach a bucket through an alias key
+    DevBuf<unsigned int> n_alias_hits;          // [2]
+    static constexpr unsigned int kAliasCap = 1u << 20;
+    DevBuf<int> last_sel;                   // pileup_selected_only with gathered votes: the genome whose rows the previous sample wrote (-1: none) -- all that
+                                            // the next sample has to zero
+    DevBuf<unsigned int> slabs;             // [n_cus][n_lds_bins] workgroup histograms of the last scan launch (scan_count_kernel only)
+    // the binned scan (bk_scan_items.hip; dense planes with the window's reference in LDS): the scan workgroups' items and where
+    // each bin's segment starts, the overflow list and its fill
+    bool use_items = false;
+    bk::ItemGeom ig{};
+    DevBuf<unsigned short> items, item_tab;
+    DevBuf<unsigned short> item_gext;       // [items_max_grid][bins][kItemGCap] the bins' extensions in device memory
+    DevBuf<unsigned int> ov;
+    DevBuf<unsigned long long> ov_n;
+    uint32_t ov_par = 0;                    // parity of the next scan_items launch (which of the two overflow counts it appends to)
+    DevBuf<unsigned int> lean_e_list, lean_n_list;   // bk_finalize_lean.hip: the reference k-mers finalize_ecell_kernel leaves to finalize_exact_kernel
+    bool v_clean[2] = {false, false};       // the V part of the mate file's plane is known to be all zero (dense planes between samples)
+    // The V items of a mate file's first scan launch are not added to the plane: they wait (`pending`) for the regional finalize,
+    // which takes its counts from them (FinalizeArgs::f_items) -- the whole story for a mate file whose reads are one launch.  A
+    // second launch into the engine's item buffers first sends them to the plane after all (flush_pending_items: bin_count_kernel,
+    // V bins only), and the mate file's later launches go straight there as before.
+    bool fuse_ok = false;                   // this engine's index, planes and parameters admit it (alloc_sample_state)
+    struct PendingItems { bool on = false; int mate = 0; bk::BinArgs b{}; } pending;
+    bool fuse_off[2] = {false, false};      // this sample's mate file has had a second launch: no more waiting
+    bool touch_used[2] = {false, false};    // Level 2 set bits in fuse_touch[m] that no regional finalize has cleared
+    DevBuf<unsigned int> fuse_touch[2];     // a bit per V row Level 2 wrote to while the launch's items wait
+    DevBuf<unsigned int> n_bits, n_any;     // scan -> Level 2: one bit per k-mer of each record of a launch / per record (bk_kernels.h ScanArgs): the N runs; all zero between launches
+    DevBuf<unsigned int> l2_bits;           // Level 2's first pass -> its second: the k-mers looked at one by one, same layout
+    DevBuf<unsigned int> l2_any;            // ... one bit per record: its row has bits
+    DevBuf<unsigned int> l2_plan;           // one word: the workgroups of level2_kernel that work (ScanArgs::l2_plan)
+    DevBuf<uint2> l2_diag;                  // ... and each record's diagonal
+    uint64_t kmers_since_fold = 0;
+    DevBuf<unsigned long long> counters[2];
+    // sparse finalize (large indexes): per mate file the touch bitmaps the counter writers set and the lists finalize walks
+    bool sparse = false;
+    DevBuf<unsigned int> touch_v[2], touch_b[2], touch_p[2], touch_e[2], v_list[2], p_list[2], e_list[2], n_list[2];
+    bool plane_used[2] = {false, false};   // counters were added to since the planes were last known to be all zero
+    DevBuf<unsigned long long> pileup;      // 4 planes
+    DevBuf<unsigned long long> stats;       // [2][n_files][3]
+    DevBuf<unsigned char> present;          // [2][n_files]
+    DevBuf<unsigned long long> kstats;      // [2][4]
+    // bk_push_reads_packed: two staging slots, so that the copy of a batch overlaps the scan of the previous one
+    struct StageSlot {
+        DevBuf<uint32_t> words; DevBuf<uint16_t> lens;
+        uint8_t* h = nullptr; size_t h_cap = 0;     // pinned host copy of the caller's batch (words, then lens)
+        hipEvent_t done = nullptr; bool busy = false;
+    } stage[2];
+    int next_stage = 0;
+
+    // asynchronous ASCII ingest (bk_push_reads_ascii): pinned staging + device buffers per slot
+    struct IngestSlot {
+        uint8_t* h_bases = nullptr; size_t h_bases_cap = 0;
+        unsigned long long* h_off = nullptr; size_t h_off_cap = 0;
+        DevBuf<uint8_t> d_bases;
+        DevBuf<unsigned long long> d_off, d_nrec;
+        DevBuf<uint32_t> d_work;           // pack_words_kernel's work list
+        DevBuf<uint32_t> d_words;
+        DevBuf<uint16_t> d_lens;
+        hipEvent_t uploaded = nullptr, done = nullptr;
+        bool busy = false;
+    };
+    IngestSlot slots[3];
+    IngestSlot dev_ascii;                   // bk_push_reads_ascii_device: the packed records of the batch being scanned (device buffers only)
+    int next_slot = 0;
+    hipStream_t copy_stream = nullptr;
+
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    bool in_sample = false;
+    int finalized_mates = 0;                // mate files of the sample whose finalize was enqueued last (0: none since bk_sample_begin / create)
+    uint64_t pushed_records[2] = {0, 0};
+    // multi-genome indexes: the LDS window (difference array + Level 1's arrays) sits on the genome the sample looks like
+    DevBuf<unsigned int> win_votes;         // [n_files]
+    DevBuf<uint32_t> win_sel;               // {win_file, win_lo} of the current sample, chosen on the device
+    uint32_t win_lo = 0;
+    int win_file = 0;
+    bool win_chosen = false;                // for the current sample
+    bool plane_stale[2] = {true, true};   // the mate's counter plane still holds an earlier sample (zeroed at its first push / at finalize)
+
+    // after the pileup (bk_sample_call): per-engine scratch and results
+    DevBuf<double> call_noise, noise_maf, noise_tbl, noise_sums;   // (get_baseline_noise, the walk taken apart: CallArgs)
+    DevBuf<unsigned int> noise_cnt, noise_state;
+    DevBuf<bk_call_record> call_records;
+    DevBuf<bk_call_summary> call_out;
+    DevBuf<bk_call_summary> sel_out;        // pileup_selected_only: the genome selected between the two finalize passes
+    DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
+    bool timing = false;
+    unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};
+    std::vector<TimedSpan> spans;
+    std::vector<hipEvent_t> free_events;
+
+    hipEvent_t get_event() {
+        if (!free_events.empty()) { hipEvent_t e = free_events.back(); free_events.pop_back(); return e; }
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        return e;
+    }
+    struct Span {
+        bk_engine* e; int kind; hipEvent_t a = nullptr;
+        Span(bk_engine* eng, int k) : e(eng), kind(k) {
+            if (e->timing && (e->timing_kinds >> k) & 1 && e->timing_seen[k]++ % e->timing_every == 0) { a = e->get_event(); (void)hipEventRecord(a, e->stream); }
+        }
+        ~Span() {
+            if (a) { hipEvent_t b = e->get_event(); (void)hipEventRecord(b, e->stream); e->spans.push_back({a, b, kind}); }
+        }
+    };
+};
+
+#pragma GCC visibility pop
