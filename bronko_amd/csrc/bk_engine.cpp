@@ -32,21 +32,21 @@ int fail(int code, const char* fmt, ...) {
 static int alloc_sample_state(bk_engine* e) {
     const bk_params* prm = &e->params;
     const IndexTables& ix = *e->ix;
-    for (int m = 0; m < 2; m++) BK_HIP(e->counters[m].alloc(ix.plane_len));
+    for (MatePlane& p : e->mate) BK_HIP(p.counters.alloc(ix.plane_len));
     // A plane of a large index is a thousandth full after a sample: above 16 M counters (128 MB) the writers note what they touch
     // and finalize walks lists and clears what it read instead of scanning and zeroing planes (BK_SPARSE_FINALIZE forces it in
     // the testing build)
     e->sparse = ix.W > 0 && (ix.plane_len >= (16ull << 20) || test_env("BK_SPARSE_FINALIZE") != nullptr);
     if (e->sparse) {
         const uint64_t n_rows = bk::v_real_rows(ix.n_full, ix.v_span);
-        for (int m = 0; m < 2; m++) {
-            BK_HIP(hipMemset(e->counters[m].p, 0, e->counters[m].n * sizeof(unsigned long long)));
-            BK_HIP(e->touch_v[m].alloc(n_rows / 32 + 1)); BK_HIP(e->touch_p[m].alloc(ix.n_prows / 32 + 1)); BK_HIP(e->touch_e[m].alloc((size_t)ix.n_u / 32 + 1));
-            BK_HIP(hipMemset(e->touch_v[m].p, 0, e->touch_v[m].n * 4)); BK_HIP(hipMemset(e->touch_p[m].p, 0, e->touch_p[m].n * 4));
-            BK_HIP(hipMemset(e->touch_e[m].p, 0, e->touch_e[m].n * 4));
-            BK_HIP(e->touch_b[m].alloc((size_t)ix.total_cells / 64 / 32 + 2)); BK_HIP(hipMemset(e->touch_b[m].p, 0, e->touch_b[m].n * 4));
-            BK_HIP(e->v_list[m].alloc(n_rows)); BK_HIP(e->p_list[m].alloc(ix.n_prows)); BK_HIP(e->e_list[m].alloc(ix.n_u));
-            BK_HIP(e->n_list[m].alloc(8));
+        for (MatePlane& p : e->mate) {
+            BK_HIP(hipMemset(p.counters.p, 0, p.counters.n * sizeof(unsigned long long)));
+            BK_HIP(p.touch_v.alloc(n_rows / 32 + 1)); BK_HIP(p.touch_p.alloc(ix.n_prows / 32 + 1)); BK_HIP(p.touch_e.alloc((size_t)ix.n_u / 32 + 1));
+            BK_HIP(hipMemset(p.touch_v.p, 0, p.touch_v.n * 4)); BK_HIP(hipMemset(p.touch_p.p, 0, p.touch_p.n * 4));
+            BK_HIP(hipMemset(p.touch_e.p, 0, p.touch_e.n * 4));
+            BK_HIP(p.touch_b.alloc((size_t)ix.total_cells / 64 / 32 + 2)); BK_HIP(hipMemset(p.touch_b.p, 0, p.touch_b.n * 4));
+            BK_HIP(p.v_list.alloc(n_rows)); BK_HIP(p.p_list.alloc(ix.n_prows)); BK_HIP(p.e_list.alloc(ix.n_u));
+            BK_HIP(p.n_list.alloc(8));
         }
     }
     BK_HIP(e->shard_sums.alloc((size_t)2 * ix.n_files * 5 + 9));
@@ -72,13 +72,13 @@ static int alloc_sample_state(bk_engine* e) {
         // clean again when its sample is finalized -- no 37 MB memset per sample (config 2); the deferred k-mers' counts
         // travel with their indices
         BK_HIP(e->deferred_n.alloc(e->deferred.n));
-        for (int m = 0; m < 2; m++) BK_HIP(hipMemset(e->counters[m].p, 0, std::max<size_t>(e->counters[m].n, 1) * sizeof(unsigned long long)));
+        for (MatePlane& p : e->mate) BK_HIP(hipMemset(p.counters.p, 0, std::max<size_t>(p.counters.n, 1) * sizeof(unsigned long long)));
     }
     if (ix.n_files == 1 && !e->sparse && ix.n_full > 0) { BK_HIP(e->lean_e_list.alloc((size_t)ix.n_full)); BK_HIP(e->lean_n_list.alloc(8)); BK_HIP(hipMemset(e->lean_n_list.p, 0, 8 * sizeof(unsigned int))); }
     BK_HIP(e->pileup.alloc(ix.total_cells * 4 * 4));
     e->gather_mode = ix.gather_ok && e->sparse && ix.cell_file.p && ix.dirty_ans.p && ix.W > 1 && ix.file_cell_lo_d.p && !test_env("BK_NO_GATHER");
     if (e->gather_mode) {
-        for (int m = 0; m < 2; m++) BK_HIP(e->alias_hits[m].alloc((size_t)bk_engine::kAliasCap * 3));
+        for (MatePlane& p : e->mate) BK_HIP(p.alias_hits.alloc((size_t)bk_engine::kAliasCap * 3));
         BK_HIP(e->n_alias_hits.alloc(2));
         BK_HIP(e->last_sel.upload(std::vector<int>(1, -1)));
         BK_HIP(hipMemset(e->pileup.p, 0, std::max<size_t>(e->pileup.n, 1) * sizeof(unsigned long long)));   // (selected-only: the rows of genomes never selected stay zero)
@@ -128,10 +128,7 @@ static int alloc_sample_state(bk_engine* e) {
                  ix.n_u == ix.n_full && ix.n_full > 0 && ix.dirty_ans.p && ix.W > 1 && ix.v_span > 0 && ix.v_span <= 32 && e->fin_partials.p && e->lean_e_list.p &&
                  prm->cs < (1ull << 32) && e->ig.vq_log2 == 6 && !test_env("BK_NO_LEAN_FINALIZE") && !test_env("BK_NO_FUSE") && !test_env("BK_NO_N_DIRECT");
     if (e->fuse_ok)
-        for (int m = 0; m < 2; m++) {
-            BK_HIP(e->fuse_touch[m].alloc(((size_t)ix.n_full + (size_t)ix.v_span + 63) / 64 * 12 + 16));
-            BK_HIP(hipMemset(e->fuse_touch[m].p, 0, e->fuse_touch[m].n * sizeof(unsigned int)));
-        }
+        for (MatePlane& p : e->mate) { BK_HIP(p.fuse_touch.alloc(((size_t)ix.n_full + (size_t)ix.v_span + 63) / 64 * 12 + 16)); BK_HIP(hipMemset(p.fuse_touch.p, 0, p.fuse_touch.n * sizeof(unsigned int))); }
     BK_HIP(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
     e->stream = e->own_stream;
     return BK_OK;
@@ -229,10 +226,8 @@ void bk_engine_destroy(bk_engine* e) {
     for (auto& s : e->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto ev : e->free_events) (void)hipEventDestroy(ev);
     for (auto& sl : e->slots) {
-        if (sl.h_bases) (void)hipHostFree(sl.h_bases);
-        if (sl.h_off) (void)hipHostFree(sl.h_off);
-        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
-        if (sl.done) (void)hipEventDestroy(sl.done);
+        if (sl.h_bases) (void)hipHostFree(sl.h_bases); if (sl.h_off) (void)hipHostFree(sl.h_off);
+        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded); if (sl.done) (void)hipEventDestroy(sl.done);
     }
     for (auto& st : e->stage) { if (st.done) (void)hipEventDestroy(st.done); if (st.h) (void)hipHostFree(st.h); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
@@ -272,7 +267,6 @@ int bk_sample_begin(bk_engine* e) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     BK_HIP(hipSetDevice(e->device));
     bk_engine::Span sp(e, 2);
-    e->plane_stale[0] = e->plane_stale[1] = true;   // a plane is zeroed when its mate file is first pushed (or finalized unpushed)
     e->win_chosen = false;
     // gathered votes (bk_gather.hip) store the rows they own: every genome's rows -- nothing to zero; the selected genome's -- the rows
     // the previous sample wrote are all that is not zero
@@ -284,21 +278,18 @@ int bk_sample_begin(bk_engine* e) {
     if (e->dump) {
         if (int rc = clear_table(e, e->dump->t)) return rc;
         BK_HIP(hipMemsetAsync(e->dump->out.p, 0, e->dump->out.n * sizeof(unsigned long long), e->stream));
-        e->dump->upper[0] = e->dump->upper[1] = 0;
-        e->dump->in_sample = true;
-        e->dump->finalized_mates = 0;
+        e->dump->upper[0] = e->dump->upper[1] = 0; e->dump->in_sample = true; e->dump->finalized_mates = 0;
     }
-    e->ktab_exchanged = false;
-    e->reduced_shards[0] = e->reduced_shards[1] = 0;
-    e->pushed_records[0] = e->pushed_records[1] = 0;
-    e->in_sample = true;
-    e->finalized_mates = 0;
+    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
-    for (int m = 0; m < 2; m++) {
-        e->fuse_off[m] = false;
-        if (e->touch_used[m]) { BK_HIP(hipMemsetAsync(e->fuse_touch[m].p, 0, e->fuse_touch[m].n * sizeof(unsigned int), e->stream)); e->touch_used[m] = false; }
-    }
+    for (MatePlane& p : e->mate) { if (int rc = p.begin_sample(e)) return rc; }
+    return BK_OK;
+}
+
+int MatePlane::begin_sample(bk_engine* e) {
+    stale = true; fuse_off = false; reduced_shards = 0; pushed_records = 0;
+    if (touch_used) { BK_HIP(hipMemsetAsync(fuse_touch.p, 0, fuse_touch.n * sizeof(unsigned int), e->stream)); touch_used = false; }
     return BK_OK;
 }
 
@@ -308,39 +299,22 @@ static int flush_pending_items(bk_engine* e) {
     if (!e->pending.on) return BK_OK;
     bk_engine::Span sp(e, 3);
     bk::BinArgs b = e->pending.b;
-    b.part = 2;
-    b.v_mode = e->ix->item_v_mode >= 0 && e->ix->item_v_mode != 2 ? e->ix->item_v_mode : 1;
-    e->pending.on = false;
-    e->fuse_off[e->pending.mate] = true;
+    b.part = 2; b.v_mode = e->ix->item_v_mode >= 0 && e->ix->item_v_mode != 2 ? e->ix->item_v_mode : 1;
+    e->pending.on = false; e->mate[e->pending.mate].no_more_waiting();
     BK_HIP(bk::launch_bin_count(b, e->stream));
     return BK_OK;
 }
 
-static int zero_plane_if_stale(bk_engine* e, int mate) {
-    if (e->sparse) {
-        // the planes are all zero between samples (finalize clears what it read); only a sample that was begun and never
-        // finalized leaves something behind
-        if (e->plane_stale[mate] && e->plane_used[mate]) {
-            bk_engine::Span sp(e, 2);
-            BK_HIP(hipMemsetAsync(e->counters[mate].p, 0, std::max<size_t>(e->counters[mate].n, 1) * sizeof(unsigned long long), e->stream));
-            BK_HIP(hipMemsetAsync(e->touch_v[mate].p, 0, e->touch_v[mate].n * 4, e->stream));
-            BK_HIP(hipMemsetAsync(e->touch_p[mate].p, 0, e->touch_p[mate].n * 4, e->stream));
-            BK_HIP(hipMemsetAsync(e->touch_b[mate].p, 0, e->touch_b[mate].n * 4, e->stream));
-            BK_HIP(hipMemsetAsync(e->touch_e[mate].p, 0, e->touch_e[mate].n * 4, e->stream));
-            e->plane_used[mate] = false;
-        }
-        e->plane_stale[mate] = false;
-        return BK_OK;
+int MatePlane::zero_if_stale(bk_engine* e) {
+    if (!stale) return BK_OK;
+    if (used) {   // (a sample that was abandoned, or a dense plane finalized in shards: whole samples leave their planes clean)
+        bk_engine::Span sp(e, 2);
+        BK_HIP(hipMemsetAsync(counters.p, 0, std::max<size_t>(counters.n, 1) * sizeof(unsigned long long), e->stream));
+        if (e->sparse) for (DevBuf<unsigned int>* t : {&touch_v, &touch_p, &touch_b, &touch_e}) BK_HIP(hipMemsetAsync(t->p, 0, t->n * 4, e->stream));
+        used = false;
     }
-    if (e->plane_stale[mate]) {
-        if (e->plane_used[mate]) {   // (a sample that was abandoned, or finalized in shards: whole samples leave their planes clean)
-            bk_engine::Span sp(e, 2);
-            BK_HIP(hipMemsetAsync(e->counters[mate].p, 0, std::max<size_t>(e->counters[mate].n, 1) * sizeof(unsigned long long), e->stream));
-            e->plane_used[mate] = false;
-        }
-        e->plane_stale[mate] = false;
-        e->v_clean[mate] = true;   // all zero now: the sample's first bin_count launch stores where it would add
-    }
+    stale = false;
+    v_clean = true;   // all zero now: the sample's first bin_count launch stores where it would add
     return BK_OK;
 }
 
@@ -353,12 +327,7 @@ static int ensure_table_room(bk_engine* e, GrowTable& t, unsigned long long* out
     if (!t.keys.p) return BK_OK;
     const uint64_t cap = 1ull << t.log2;
     if (t.fill_known + t.fill_unknown_upper + upper > cap / 2) {
-        if (t.fill_pending) {
-            BK_HIP(hipEventSynchronize(t.fill_ev));
-            uint64_t f = 0;
-            for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) f += t.h_fill[i];
-            t.fill_known = f; t.fill_unknown_upper = 0; t.fill_pending = false;
-        }
+        if (t.fill_pending) { BK_HIP(hipEventSynchronize(t.fill_ev)); t.read_fill(); }
         uint32_t nl = t.log2;
         while (nl < 31 && t.fill_known + t.fill_unknown_upper + upper > (1ull << nl) / 2) nl += 2;
         if (nl > 31) nl = 31;
@@ -401,175 +370,280 @@ static int dump_push(bk_engine* e, int mate, const uint32_t* d_words, uint32_t s
     return note_table_fill(e, d.t, d.out.p);
 }
 
-static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
-                       const unsigned long long* n_records_dev = nullptr, uint64_t kmers_upper = 0) {
+#ifdef BK_TESTING   // (the testing build's reports)
+// BK_L2_COUNT (debugging aid): how much a scan launch leaves to Level 2
+static int l2_count_report(bk_engine* e, const bk::ScanArgs& a) {
+    if (!test_env("BK_L2_COUNT")) return BK_OK;
+    const uint64_t take = a.n_records;
+    std::vector<unsigned int> hb((size_t)take * a.l2_words), ha((size_t)(take + 31) / 32);
+    BK_HIP(hipMemcpyAsync(hb.data(), e->n_bits.p, hb.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipMemcpyAsync(ha.data(), e->n_any.p, ha.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    uint64_t nk = 0, nr = 0, runs = 0;
+    for (size_t i = 0; i < hb.size(); i++) { nk += (uint64_t)__builtin_popcount(hb[i]); runs += (uint64_t)__builtin_popcount(hb[i] & ~(hb[i] << 1)); }
+    for (unsigned int w : ha) nr += (uint64_t)__builtin_popcount(w);
+    fprintf(stderr, "[bk] left to level 2 by the scan: %llu of %llu records marked, %llu k-mers in %llu N runs (per 32-bit word)\n", (unsigned long long)nr,
+            (unsigned long long)take, (unsigned long long)nk, (unsigned long long)runs);
+    return BK_OK;
+}
+// BK_L2_STATS: the scan and Level 2 tally what they see in `dbg` (allocated by the first push that asks for it); every finalize prints
+// the tallies, the clocks of the last scan launch's workgroups and what finalize deferred, and zeroes them
+static int l2_stats_arm(bk_engine* e) {
+    if (test_env("BK_L2_STATS") && !e->dbg.p) { BK_HIP(e->dbg.alloc(32 + 4 * 1024)); BK_HIP(hipMemsetAsync(e->dbg.p, 0, (32 + 4 * 1024) * sizeof(unsigned long long), e->stream)); }
+    return BK_OK;
+}
+static int l2_stats_report(bk_engine* e) {
+    if (!e->dbg.p) return BK_OK;
     const IndexTables& ix = *e->ix;
-    if (int rc = zero_plane_if_stale(e, mate)) return rc;
-    if (int rc = ensure_ktab_room(e, kmers_upper ? kmers_upper : n * (uint64_t)stride_words * 16)) return rc;
-    if (e->dump) { if (int rc = dump_push(e, mate, d_words, stride_words, d_lens, n, n_records_dev, kmers_upper ? kmers_upper : n * (uint64_t)stride_words * 16)) return rc; }
+    unsigned long long h[32]; unsigned int nd[2] = {0, 0};
+    BK_HIP(hipMemcpyAsync(nd, e->n_deferred.p, sizeof nd, hipMemcpyDeviceToHost, e->stream));
+    std::vector<unsigned long long> clk(4 * 1024);
+    BK_HIP(hipMemcpyAsync(h, e->dbg.p, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipMemcpyAsync(clk.data(), e->dbg.p + 32, clk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipMemsetAsync(e->dbg.p, 0, (32 + 4 * 1024) * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    // the scan's workgroups on the clock (the sample's last launch): when each started, had its reference, ran out of tiles, ended
+    unsigned long long t0 = ~0ull;
+    int n_wg = 0;
+    for (int b = 0; b < 512; b++) if (clk[4 * b]) { t0 = std::min(t0, clk[4 * b]); n_wg = b + 1; }   // (the second half holds the prologue clocks)
+    if (n_wg) {
+        double mx[4] = {0, 0, 0, 0}, mean[4] = {0, 0, 0, 0}, mn[4] = {1e30, 1e30, 1e30, 1e30};
+        for (int b = 0; b < n_wg; b++)
+            for (int j = 0; j < 4; j++) {
+                const double us = (double)(clk[4 * b + j] - t0) * 0.01;
+                mx[j] = std::max(mx[j], us); mn[j] = std::min(mn[j], us); mean[j] += us / n_wg;
+            }
+        fprintf(stderr, "[bk] scan workgroups (%d), us after the first start, min / mean / max: start %.1f / %.1f / %.1f, reference staged %.1f / %.1f / %.1f, "
+                "tiles done %.1f / %.1f / %.1f, end %.1f / %.1f / %.1f\n", n_wg, mn[0], mean[0], mx[0], mn[1], mean[1], mx[1], mn[2], mean[2], mx[2], mn[3], mean[3], mx[3]);
+        double m2[4] = {0, 0, 0, 0};
+        int n2 = 0;
+        for (int b = 0; b < std::min(n_wg, 512); b++) if (clk[2048 + 4 * b]) { n2++; for (int j = 0; j < 4; j++) m2[j] += (double)(clk[2048 + 4 * b + j] - t0) * 0.01; }
+        if (n2) fprintf(stderr, "[bk]   ... mean: first tile's copy sent %.1f, window's loads stored %.1f, wave 0 has its first tile %.1f, buckets written out %.1f\n",
+                        m2[0] / n2, m2[1] / n2, m2[2] / n2, m2[3] / n2);
+        if (test_env("BK_L2_STATS")[0] == '2')
+            for (int b = 0; b < n_wg; b++) fprintf(stderr, "[bk]   wg %d: %.1f %.1f %.1f %.1f\n", b, (clk[4 * b] - t0) * 0.01, (clk[4 * b + 1] - t0) * 0.01, (clk[4 * b + 2] - t0) * 0.01, (clk[4 * b + 3] - t0) * 0.01);
+    }
+    fprintf(stderr, "[bk] finalize: %u + %u k-mers deferred to the general kernel\n", nd[0], nd[1]);
+    if (e->gather_mode) {
+        unsigned int ah[2] = {0u, 0u};
+        BK_HIP(hipMemcpy(ah, e->n_alias_hits.p, sizeof ah, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[bk] votes gathered cell by cell (bk_gather.hip); alias hits among the deferred k-mers: %u + %u\n", ah[0], ah[1]);
+    }
+    if (e->sparse) {
+        unsigned int nl[8];
+        BK_HIP(hipMemcpy(nl, e->mate[0].n_list.p, sizeof nl, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[bk] sparse finalize (mate file 0): %u V rows of %llu, %u pseudo rows of %llu, %u reference k-mers of %u and %u pseudo k-mers of %u touched\n",
+                nl[0], (unsigned long long)bk::v_real_rows(ix.n_full, ix.v_span), nl[4], (unsigned long long)ix.n_prows, nl[2], ix.n_full, nl[3], ix.n_u - ix.n_full);
+    }
+    fprintf(stderr, "[bk] scan: %llu mismatches counted, %llu items processed, %llu E gaps before a mismatch, %llu behind the last\n", h[23], h[24], h[25], h[26]);
+    fprintf(stderr, "[bk] scan N batches: %llu with %llu pieces (%.1f per batch), %llu of them forced by a tile's end\n", h[20], h[21], h[20] ? (double)h[21] / (double)h[20] : 0.0, h[22]);
+    fprintf(stderr, "[bk] scan marked: no-diagonal %llu, dirty-head %llu, clean-head %llu, pairs %llu | level 2: k-mers %llu in %llu chunks, simple %llu, dead %llu, "
+            "dirty answers %llu (one difference but id unknown: %llu), neither half present %llu, slow %llu (diffs 0/1/2/3+ with a diagonal: %llu/%llu/%llu/%llu) -> member %llu, neighbour %llu, nothing %llu\n",
+            h[0], h[1], h[2], h[3], h[4], h[11], h[5], h[6], h[16], h[17], h[18], h[7], h[12], h[13], h[14], h[15], h[8], h[9], h[10]);
+    return BK_OK;
+}
+#else
+static int l2_count_report(bk_engine*, const bk::ScanArgs&) { return BK_OK; }
+static int l2_stats_arm(bk_engine*) { return BK_OK; }
+static int l2_stats_report(bk_engine*) { return BK_OK; }
+#endif
+
+// The scan's arguments that every launch of a push shares.  Built for each push: a rehash of the statistics table
+// (ensure_table_room) moves ktab.keys and raises ktab.log2 in the middle of a sample.
+static bk::ScanArgs scan_args(const bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
+                              const unsigned long long* n_records_dev) {
+    const IndexTables& ix = *e->ix;
+    const MatePlane& pl = e->mate[mate];
     bk::ScanArgs a{};
-    a.n_records_dev = n_records_dev;
-    a.ixp = ix.d_view.p;
+    a.n_records_dev = n_records_dev; a.ixp = ix.d_view.p;
     a.k = ix.k; a.wstart = ix.wstart; a.W = ix.W; a.v_omin = ix.v_omin; a.v_span = ix.v_span; a.v_off = ix.v_off; a.total_cells = (uint32_t)ix.total_cells; a.n_u = ix.n_u;
     a.ref_words = ix.ref_words.p; a.cell_codes = ix.cell_codes.p; a.cell_has = ix.cell_has.p; a.cell_clean = ix.cell_clean.p; a.cell_clean3 = ix.cell_clean3.p; a.cell_yf = ix.cell_yf.p; a.cell_yr = ix.cell_yr.p; a.id_at = ix.id_at.p; a.cell_fast = ix.cell_fast.p; a.cell_nat = ix.cell_nat.p; a.cell_natrow = ix.cell_natrow.p; a.cell_blk = ix.cell_blk.p; a.seed_tab = ix.seed_tab.p; a.seed_log2 = ix.seed_log2;
     a.seed_tab2 = ix.seed_tab2.p; a.seed2_log2 = ix.seed2_log2; a.rc_words = ix.rc_words.p;
     a.n_direct = e->use_items && ix.n_files == 1 && ix.max_seqs_per_file == 1 && (uint64_t)ix.n_lds_bins >= ix.total_cells && !test_env("BK_NO_N_DIRECT");
     a.words = d_words; a.lens = d_lens; a.n_records = n; a.stride_words = stride_words;
-    a.counters = e->counters[mate].p;
-    a.kmer_total = e->kstats.p + mate * 4 + 1;
-    a.ablate = ix.ablate;
-    a.slabs = e->slabs.p;
-    a.n_lds_bins = ix.n_lds_bins;
-    a.ref_in_lds = ix.ref_in_lds ? 1 : 0;
+    a.counters = pl.counters.p; a.kmer_total = e->kstats.p + mate * 4 + 1;
+    a.ablate = ix.ablate; a.slabs = e->slabs.p; a.n_lds_bins = ix.n_lds_bins; a.ref_in_lds = ix.ref_in_lds ? 1 : 0;
     a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2;
     a.ktab_overflow = e->ktab_out.p + 4; a.mate = (uint32_t)mate;
     a.occ = ix.occ.p; a.n_files = ix.n_files;
-    e->plane_used[mate] = true;
     if (e->sparse) {
-        a.touch_v = e->touch_v[mate].p; a.touch_b = e->touch_b[mate].p; a.touch_p = e->touch_p[mate].p; a.touch_e = e->touch_e[mate].p;
+        a.touch_v = pl.touch_v.p; a.touch_b = pl.touch_b.p; a.touch_p = pl.touch_p.p; a.touch_e = pl.touch_e.p;
         a.rl_recip = ~0ull / (unsigned long long)(ix.v_span + 1) + 1ull;   // ceil(2^64 / row length): exact quotients for 32-bit counter indices
     }
-    if (test_env("BK_L2_STATS") && !e->dbg.p) { BK_HIP(e->dbg.alloc(32 + 4 * 1024)); BK_HIP(hipMemsetAsync(e->dbg.p, 0, (32 + 4 * 1024) * sizeof(unsigned long long), e->stream)); }
-    a.dbg = e->dbg.p;
-    if (ix.W <= 0) {
-        // empty window: nothing can touch the index (map_kmers finds no bucket, call.rs:1291-1307); KMC's total k-mer count is all
-        bk::launch_count_kmers(a, e->stream);
-        BK_HIP(hipGetLastError());
-        if (!n_records_dev) e->pushed_records[mate] += n;
-        return note_ktab_fill(e);
-    }
+    a.dbg = e->dbg.p; a.l2_words = bk::scan_l2_words(stride_words, ix.k); a.l2_min_grid = (uint32_t)std::max(1, ix.n_cus / 2);
+    if (e->use_items) { a.ig = e->ig; a.items = e->items.p; a.tab = e->item_tab.p; a.gext = e->item_gext.p; a.ov = e->ov.p; a.ov_n = e->ov_n.p; a.ov_cap = (uint32_t)e->ov.n; }
+    return a;
+}
+// Multi-genome indexes: the first records of the sample vote for the genome they look like; the LDS window goes on that genome and
+// stays there for the sample.  Vote and choice are made on the device (the scan reads the window from device memory): no host round
+// trip between a sample's first push and its scan.  Any choice gives the same counts -- this is about speed.
+static int choose_window(bk_engine* e, bk::ScanArgs& a, uint64_t n) {
+    const IndexTables& ix = *e->ix;
     if (ix.occ.p && !e->win_chosen && n > 0) {
-        // first records of the sample vote for the genome they look like; the LDS window goes on that genome and stays there for
-        // the sample.  Vote and choice are made on the device (the scan reads the window from device memory): no host round trip
-        // between a sample's first push and its scan.  Any choice gives the same counts -- this is about speed.
-        a.win_file = 0; a.win_lo = 0; a.win_dev = nullptr;
         BK_HIP(hipMemsetAsync(e->win_votes.p, 0, e->win_votes.n * sizeof(unsigned int), e->stream));
-        int forced = -1;
-        if (const char* wf = test_env("BK_WINDOW_FILE")) forced = std::max(0, atoi(wf));   // testing aid
+        const char* wf = test_env("BK_WINDOW_FILE");   // testing aid
+        const int forced = wf ? std::max(0, atoi(wf)) : -1;
         bk::launch_pick_window(a, 16384, e->win_votes.p, ix.file_cell_lo_d.p, forced, e->win_sel.p, e->stream);
         e->win_chosen = true;
     }
-    a.win_file = 0; a.win_lo = 0;
     a.win_dev = ix.occ.p ? e->win_sel.p : nullptr;
-    // a launch takes at most scan_max_records records (bound on what one workgroup's 16-bit LDS bins can receive), and no
-    // more than keeps Level 2's bitmap below 1 GiB
-    a.l2_words = bk::scan_l2_words(stride_words, ix.k);
-    const uint64_t l2_cap = std::max<uint64_t>(64, ((1ull << 30) / sizeof(unsigned int)) / a.l2_words);
+    return BK_OK;
+}
+// How many of the `left` records the next launch scans (at most `l2_cap`), and on how many workgroups (`grid`)
+static uint64_t next_launch(const bk_engine* e, uint64_t left, uint64_t l2_cap, uint32_t& grid) {
+    const IndexTables& ix = *e->ix;
+    grid = bk::scan_grid(left, ix.n_cus);
+    // (the slab scan: no more than one workgroup's 16-bit LDS bins can receive; the binned scan has none to keep from wrapping)
+    uint64_t take = e->use_items ? std::min<uint64_t>(left, l2_cap) : std::min<uint64_t>(std::min<uint64_t>(left, bk::scan_max_records(grid)), l2_cap);
+    if (ix.max_launch_records) take = std::min<uint64_t>(take, ix.max_launch_records);
     if (e->use_items) {
-        a.ig = e->ig; a.items = e->items.p; a.tab = e->item_tab.p; a.gext = e->item_gext.p; a.ov = e->ov.p; a.ov_n = e->ov_n.p; a.ov_cap = (uint32_t)e->ov.n;
+        // A scan workgroup fills its CU (16 waves of 128 registers, 127 KB of LDS): on every CU it shuts out the other samples'
+        // finalize / Level 2 kernels, which are chains of short launches that wait for latency, not for CUs.  With siblings in
+        // flight three quarters of the CUs scan and the rest keep those chains moving (config 2, three samples in flight: 8.35
+        // -> 9.06 G reads/s; one sample alone is 4% slower that way and keeps the whole chip).  DESIGN.md §4 has the sweeps of the
+        // share: three quarters, whatever the number of siblings.
+        int share = ix.n_cus - ix.n_cus / 4;
+        if (const char* fr = test_env("BK_ITEM_SHARE")) share = std::max(1, std::min(ix.n_cus, ix.n_cus * atoi(fr) / 16));   // measurement aid: sixteenths of the CUs
+        grid = bk::items_grid(take, ix.family.load() > 1 ? share : ix.n_cus);
+        if (const char* gr = test_env("BK_ITEM_GRID")) grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, (uint32_t)atoi(gr)));
     }
-    for (uint64_t base = 0; base < n;) {
-        uint32_t grid = bk::scan_grid(n - base, ix.n_cus);
-        uint64_t take = std::min<uint64_t>(std::min<uint64_t>(n - base, bk::scan_max_records(grid)), l2_cap);
-        if (e->use_items) take = std::min<uint64_t>(n - base, l2_cap);   // (no 16-bit LDS bins to keep from wrapping)
-        if (ix.max_launch_records) take = std::min<uint64_t>(take, ix.max_launch_records);
-        if (e->l2_bits.n < take * a.l2_words || e->l2_diag.n < take) {
-            BK_HIP(hipStreamSynchronize(e->stream));
-            const uint64_t recs = std::min<uint64_t>(std::max<uint64_t>(take + take / 4, 1 << 16), l2_cap);
-            BK_HIP(e->l2_bits.alloc((size_t)recs * a.l2_words));
-            BK_HIP(e->n_bits.alloc((size_t)recs * a.l2_words));
-            BK_HIP(e->l2_diag.alloc((size_t)recs));
-            BK_HIP(e->l2_any.alloc((size_t)(recs + 31) / 32));
-            BK_HIP(e->n_any.alloc((size_t)(recs + 31) / 32));
-            BK_HIP(hipMemsetAsync(e->l2_bits.p, 0, e->l2_bits.n * sizeof(unsigned int), e->stream));
-            BK_HIP(hipMemsetAsync(e->l2_any.p, 0, e->l2_any.n * sizeof(unsigned int), e->stream));
-            BK_HIP(hipMemsetAsync(e->n_bits.p, 0, e->n_bits.n * sizeof(unsigned int), e->stream));
-            BK_HIP(hipMemsetAsync(e->n_any.p, 0, e->n_any.n * sizeof(unsigned int), e->stream));
-        }
-        a.l2_bits = e->l2_bits.p; a.l2_diag = e->l2_diag.p; a.l2_any = e->l2_any.p; a.n_bits = e->n_bits.p; a.n_any = e->n_any.p;
-        // (one genome file, the binned scan, four or more samples in flight: Level 2 on as many workgroups as its marks are worth)
-        a.l2_plan = e->use_items && ix.n_files == 1 && ix.family.load() >= 4 && !test_env("BK_NO_L2_PLAN") ? e->l2_plan.p : nullptr;
-        a.l2_min_grid = (uint32_t)std::max(1, ix.n_cus / 2);
-        a.rec_base = base; a.n_records = take;
-        if (int rc = flush_pending_items(e)) return rc;   // (the scan below overwrites the item buffers)
-        const bool wait_v = e->fuse_ok && a.n_direct && !e->fuse_off[mate] && ix.item_v_mode < 0;
-        if (e->use_items) {
-            // A scan workgroup fills its CU (16 waves of 128 registers, 127 KB of LDS): on every CU it shuts out the other samples'
-            // finalize / Level 2 kernels, which are chains of short launches that wait for latency, not for CUs.  With siblings in
-            // flight three quarters of the CUs scan and the rest keep those chains moving (config 2, three samples in flight: 8.35
-            // -> 9.06 G reads/s; one sample alone is 4% slower that way and keeps the whole chip).
-            // (Round 6 gave four or more samples in flight five eighths: 12.1 against 11.3 G reads/s then, flat from 8 to 11
-            // sixteenths.  Swept again at the sources whose scan writes out only the filled bucket slots: 6 / 8 / 10 / 12 / 14 / 16
-            // sixteenths gave 7.47 / 7.97 / 8.24 / 8.50 / 8.42 / 8.28 G reads/s, two interleaved rounds within 0.4 % of each other:
-            // three quarters, whatever the number of siblings.)
-            int share = ix.n_cus - ix.n_cus / 4;
-            if (const char* fr = test_env("BK_ITEM_SHARE")) share = std::max(1, std::min(ix.n_cus, ix.n_cus * atoi(fr) / 16));   // measurement aid: sixteenths of the CUs
-            grid = bk::items_grid(take, ix.family.load() > 1 ? share : ix.n_cus);
-            if (const char* gr = test_env("BK_ITEM_GRID")) grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, (uint32_t)atoi(gr)));
-        }
-        {
-            bk_engine::Span sp(e, 0);
-            if (e->use_items) { a.ov_par = e->ov_par; BK_HIP(bk::launch_scan_items(a, grid, e->stream)); }
-            else BK_HIP(bk::launch_scan_count(a, grid, e->stream));
-        }
-        if (e->use_items) {
-            bk_engine::Span sp(e, 3);
-            // the scan's items, bin by bin -> u64 plane (before nbatch / level2 add to it: a sample's first launch finds the V part all zero)
-            bk::BinArgs b{};
-            b.ig = e->ig; b.items = e->items.p; b.tab = e->item_tab.p; b.gext = e->item_gext.p; b.n_wg = grid; b.ov = e->ov.p; b.ov_n = e->ov_n.p; b.ov_cap = (uint32_t)e->ov.n;
-            b.ov_par = e->ov_par; e->ov_par ^= 1u;
-            b.id_at = ix.id_at.p; b.cell_codes = ix.cell_codes.p + bk::scan_ref_pad_words(); b.win_lo = a.win_lo; b.win_dev = a.win_dev;
-            b.total_cells = (uint32_t)ix.total_cells; b.counters = e->counters[mate].p; b.v_off = ix.v_off;
-            b.v_real_len = bk::v_real_len(ix.n_full, ix.v_span); b.rl = (uint32_t)ix.v_span + 1u;
-            b.v_mode = ix.item_v_mode >= 0 ? ix.item_v_mode : (e->v_clean[mate] ? 2 : 1);
-            e->v_clean[mate] = false;
-            if (const char* ba = test_env("BK_BIN_ABLATE")) b.ablate = atoi(ba);
-            if (wait_v) {
-                // the mate file's first launch: its V items wait for the regional finalize (or for the next launch, which sends them
-                // to the plane); Level 2 below notes the V rows it writes to
-                e->pending.on = true; e->pending.mate = mate; e->pending.b = b;
-                b.part = 1;
-                a.touch_v = e->fuse_touch[mate].p; e->touch_used[mate] = true;
-                a.rl_recip = ~0ull / (unsigned long long)(ix.v_span + 1) + 1ull;
-            } else {
-                e->fuse_off[mate] = true;
-                if (e->fuse_ok) a.touch_v = nullptr;   // (a push of several launches: set by the first)
+    return take;
+}
+// Level 2's buffers for a launch of a.n_records records: grown (the stream drained first) when the launch does not fit them
+static int make_l2_room(bk_engine* e, bk::ScanArgs& a, uint64_t l2_cap) {
+    if (e->l2_bits.n < a.n_records * a.l2_words || e->l2_diag.n < a.n_records) {
+        BK_HIP(hipStreamSynchronize(e->stream));
+        const uint64_t recs = std::min<uint64_t>(std::max<uint64_t>(a.n_records + a.n_records / 4, 1 << 16), l2_cap);
+        BK_HIP(e->l2_bits.alloc((size_t)recs * a.l2_words)); BK_HIP(e->n_bits.alloc((size_t)recs * a.l2_words)); BK_HIP(e->l2_diag.alloc((size_t)recs));
+        BK_HIP(e->l2_any.alloc((size_t)(recs + 31) / 32)); BK_HIP(e->n_any.alloc((size_t)(recs + 31) / 32));
+        for (DevBuf<unsigned int>* b : {&e->l2_bits, &e->l2_any, &e->n_bits, &e->n_any}) BK_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(unsigned int), e->stream));
+    }
+    a.l2_bits = e->l2_bits.p; a.l2_diag = e->l2_diag.p; a.l2_any = e->l2_any.p; a.n_bits = e->n_bits.p; a.n_any = e->n_any.p;
+    return BK_OK;
+}
+// The binned scan's items, bin by bin -> u64 plane (before Level 2 adds to it: a sample's first launch finds the V part all zero).
+// `wait_v`: the mate file's first launch, whose V items wait for the regional finalize (or for the next launch, which sends them to
+// the plane); Level 2 then notes the V rows it writes to.
+static int bin_items(bk_engine* e, bk::ScanArgs& a, int mate, uint32_t grid, bool wait_v) {
+    const IndexTables& ix = *e->ix;
+    MatePlane& pl = e->mate[mate];
+    bk_engine::Span sp(e, 3);
+    bk::BinArgs b{};
+    b.ig = e->ig; b.items = e->items.p; b.tab = e->item_tab.p; b.gext = e->item_gext.p; b.n_wg = grid; b.ov = e->ov.p; b.ov_n = e->ov_n.p; b.ov_cap = (uint32_t)e->ov.n;
+    b.ov_par = e->ov_par; e->ov_par ^= 1u;
+    b.id_at = ix.id_at.p; b.cell_codes = ix.cell_codes.p + bk::scan_ref_pad_words(); b.win_lo = a.win_lo; b.win_dev = a.win_dev; b.total_cells = (uint32_t)ix.total_cells;
+    b.counters = pl.counters.p; b.v_off = ix.v_off; b.v_real_len = bk::v_real_len(ix.n_full, ix.v_span); b.rl = (uint32_t)ix.v_span + 1u;
+    const bool v_clean = pl.take_v_clean();   // (whatever the mode: the next launch adds)
+    b.v_mode = ix.item_v_mode >= 0 ? ix.item_v_mode : (v_clean ? 2 : 1);
+    if (const char* ba = test_env("BK_BIN_ABLATE")) b.ablate = atoi(ba);
+    if (wait_v) {
+        e->pending.on = true; e->pending.mate = mate; e->pending.b = b;
+        b.part = 1;
+        a.touch_v = pl.fuse_touch.p; a.rl_recip = ~0ull / (unsigned long long)(ix.v_span + 1) + 1ull;
+        pl.items_wait();
+    } else {
+        pl.no_more_waiting();
+        if (e->fuse_ok) a.touch_v = nullptr;   // (a push of several launches: set by the first)
+    }
+    BK_HIP(bk::launch_bin_count(b, e->stream));
+    return BK_OK;
+}
+// Level 2 over the k-mers the scan left marked (it clears the marks it takes); behind the slab scan, its per-cell bin slabs -> u64 plane
+static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32_t grid) {
+    const IndexTables& ix = *e->ix;
+    bk_engine::Span sp(e, 3);
+    if (int rc = l2_count_report(e, a)) return rc;
+    if (ix.ablate == 1 || ix.ablate == 4) {   // measurement aids: without Level 2
+        BK_HIP(hipMemsetAsync(e->n_bits.p, 0, (size_t)a.n_records * a.l2_words * sizeof(unsigned int), e->stream));
+        BK_HIP(hipMemsetAsync(e->n_any.p, 0, e->n_any.n * sizeof(unsigned int), e->stream));
+    }
+    else BK_HIP(bk::launch_level2(a, ix.n_cus, e->stream));
+    if (!e->use_items) {
+        bk::FoldArgs f{};
+        f.slabs = e->slabs.p; f.n_slabs = grid; f.n_lds_bins = ix.n_lds_bins; f.id_at = ix.id_at.p; f.cell_codes = ix.cell_codes.p + bk::scan_ref_pad_words(); f.win_lo = a.win_lo; f.win_dev = a.win_dev; f.touch_e = a.touch_e;
+        f.counters = e->mate[mate].counters.p;
+        bk::launch_fold(f, e->stream);
+    }
+    return BK_OK;
+}
+static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
+                       const unsigned long long* n_records_dev = nullptr, uint64_t kmers_upper = 0) {
+    MatePlane& pl = e->mate[mate];
+    if (int rc = pl.zero_if_stale(e)) return rc;
+    const uint64_t upper = kmers_upper ? kmers_upper : n * (uint64_t)stride_words * 16;
+    if (int rc = ensure_ktab_room(e, upper)) return rc;
+    if (e->dump) { if (int rc = dump_push(e, mate, d_words, stride_words, d_lens, n, n_records_dev, upper)) return rc; }
+    pl.written();
+    if (int rc = l2_stats_arm(e)) return rc;
+    bk::ScanArgs a = scan_args(e, mate, d_words, stride_words, d_lens, n, n_records_dev);
+    if (e->ix->W <= 0) {
+        // empty window: nothing can touch the index (map_kmers finds no bucket, call.rs:1291-1307); KMC's total k-mer count is all
+        bk::launch_count_kmers(a, e->stream);
+    } else {
+        if (int rc = choose_window(e, a, n)) return rc;
+        // a launch keeps Level 2's bitmap below 1 GiB
+        const uint64_t l2_cap = std::max<uint64_t>(64, ((1ull << 30) / sizeof(unsigned int)) / a.l2_words);
+        for (uint64_t base = 0; base < n; base += a.n_records) {
+            uint32_t grid = 0;
+            a.rec_base = base; a.n_records = next_launch(e, n - base, l2_cap, grid);
+            if (int rc = make_l2_room(e, a, l2_cap)) return rc;
+            if (int rc = flush_pending_items(e)) return rc;   // (the scan below overwrites the item buffers)
+            const bool wait_v = e->fuse_ok && a.n_direct && !pl.fuse_off && e->ix->item_v_mode < 0;
+            // (one genome file, the binned scan, four or more samples in flight: Level 2 on as many workgroups as its marks are worth)
+            a.l2_plan = e->use_items && e->ix->n_files == 1 && e->ix->family.load() >= 4 && !test_env("BK_NO_L2_PLAN") ? e->l2_plan.p : nullptr;
+            {
+                bk_engine::Span sp(e, 0);
+                if (e->use_items) { a.ov_par = e->ov_par; BK_HIP(bk::launch_scan_items(a, grid, e->stream)); }
+                else BK_HIP(bk::launch_scan_count(a, grid, e->stream));
             }
-            BK_HIP(bk::launch_bin_count(b, e->stream));
+            if (e->use_items) { if (int rc = bin_items(e, a, mate, grid, wait_v)) return rc; }
+            if (int rc = level2_and_fold(e, a, mate, grid)) return rc;
         }
-        if (ix.W > 0) {
-            bk_engine::Span sp(e, 3);
-            // the k-mers the scan left marked (it clears the marks it takes)
-            if (test_env("BK_L2_COUNT")) {   // debugging aid: how much is left to Level 2
-                std::vector<unsigned int> hb((size_t)take * a.l2_words), ha((size_t)(take + 31) / 32);
-                BK_HIP(hipMemcpyAsync(hb.data(), e->n_bits.p, hb.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
-                BK_HIP(hipMemcpyAsync(ha.data(), e->n_any.p, ha.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
-                BK_HIP(hipStreamSynchronize(e->stream));
-                uint64_t nk = 0, nr = 0, runs = 0;
-                for (size_t i = 0; i < hb.size(); i++) { nk += (uint64_t)__builtin_popcount(hb[i]); runs += (uint64_t)__builtin_popcount(hb[i] & ~(hb[i] << 1)); }
-                for (unsigned int w : ha) nr += (uint64_t)__builtin_popcount(w);
-                fprintf(stderr, "[bk] left to level 2 by the scan: %llu of %llu records marked, %llu k-mers in %llu N runs (per 32-bit word)\n", (unsigned long long)nr,
-                        (unsigned long long)take, (unsigned long long)nk, (unsigned long long)runs);
-            }
-            if (ix.ablate == 1 || ix.ablate == 4) {   // measurement aids: without Level 2
-                BK_HIP(hipMemsetAsync(e->n_bits.p, 0, (size_t)take * a.l2_words * sizeof(unsigned int), e->stream));
-                BK_HIP(hipMemsetAsync(e->n_any.p, 0, e->n_any.n * sizeof(unsigned int), e->stream));
-            }
-            else BK_HIP(bk::launch_level2(a, ix.n_cus, e->stream));
-            if (!e->use_items) {
-                // per-cell bin slabs -> u64 plane
-                bk::FoldArgs f{};
-                f.slabs = e->slabs.p; f.n_slabs = grid; f.n_lds_bins = ix.n_lds_bins; f.id_at = ix.id_at.p; f.cell_codes = ix.cell_codes.p + bk::scan_ref_pad_words(); f.win_lo = a.win_lo; f.win_dev = a.win_dev; f.touch_e = a.touch_e;
-                f.counters = e->counters[mate].p;
-                bk::launch_fold(f, e->stream);
-            }
-        }
-        base += take;
     }
     BK_HIP(hipGetLastError());
-    if (!n_records_dev) e->pushed_records[mate] += n;
+    if (!n_records_dev) pl.pushed_records += n;
     return note_ktab_fill(e);
 }
 
-int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads) {
+// The checks the four bk_push_reads_* entry points share, in this order (`batch_ok`: the batch's pointers and shape are valid;
+// `too_large`: it holds 2^32 bases or more).  kPush: push the batch; BK_OK: it is empty; else the error.
+static constexpr int kPush = 1;
+static int push_checks(bk_engine* e, int mate, uint64_t n, bool batch_ok, const char* bad_batch, bool too_large) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     if (!e->in_sample) return fail(BK_ERR_STATE, "bk_push_reads_* called before bk_sample_begin");
     if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (n_reads == 0) return BK_OK;
-    if (!buf || !offsets) return fail(BK_ERR_INVALID, "bad read batch");
-    const uint64_t base0 = offsets[0], total = offsets[n_reads] - base0;
-    if (total >= (1ull << 32)) return fail(BK_ERR_INVALID, "batch too large: push at most 2^32 bases per call");
+    if (n == 0) return BK_OK;
+    if (!batch_ok) return fail(BK_ERR_INVALID, "%s", bad_batch);
+    if (too_large) return fail(BK_ERR_INVALID, "batch too large: push at most 2^32 bases per call");
     BK_HIP(hipSetDevice(e->device));
+    return kPush;
+}
+static int packed_checks(bk_engine* e, int mate, const void* words, uint32_t stride_words, const void* lens, uint64_t n) {
+    return push_checks(e, mate, n, words && lens && stride_words != 0 && stride_words <= 4096, "bad record batch",
+                       stride_words != 0 && n > (1ull << 32) / ((uint64_t)stride_words * 16));
+}
+// ASCII reads: the packer's records hold up to 16 bases per word and at most 65535 bases (a longer run of bases is cut into records
+// that overlap by k - 1): words per record, and a bound on the records a batch becomes
+struct PackGeom {
+    uint32_t stride; uint64_t cap;
+    PackGeom(int k, uint64_t n_reads, uint64_t total, uint64_t longest)
+        : stride((uint32_t)std::min<uint64_t>((std::max<uint64_t>(longest, (uint64_t)k) + 15) / 16, 4095)),
+          cap(n_reads + total / (uint64_t)k + total / (std::min<uint64_t>((uint64_t)stride * 16, 65535) - (uint64_t)(k - 1)) + 16) {}
+};
+// the packer (records pushed: tallied on the device) into the slot's record buffers, then the push of those records
+static int pack_and_push(bk_engine* e, int mate, bk_engine::IngestSlot& sl, const uint8_t* bases, uint32_t shift, const unsigned long long* offsets,
+                         uint64_t n_reads, uint64_t total, PackGeom g) {
+    bk::PackArgs pa{};
+    pa.shift = shift; pa.bases = bases; pa.offsets = offsets; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = g.stride;
+    pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = g.cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
+    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream); }
+    return push_device(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, g.cap, sl.d_nrec.p, total);   // (a batch holds fewer k-mers than bases)
+}
+
+int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads) {
+    const bool too_large = buf && offsets && n_reads && offsets[n_reads] - offsets[0] >= (1ull << 32);
+    if (int rc = push_checks(e, mate, n_reads, buf && offsets, "bad read batch", too_large); rc != kPush) return rc;
+    const uint64_t base0 = offsets[0], total = offsets[n_reads] - base0;
     if (!e->copy_stream) BK_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
     bk_engine::IngestSlot& sl = e->slots[e->next_slot];
     e->next_slot = (e->next_slot + 1) % 3;
@@ -588,19 +662,17 @@ int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64
         BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_off), sl.h_off_cap * sizeof(unsigned long long), hipHostMallocDefault));
     }
     std::memcpy(sl.h_bases, buf + base0, total);
-    uint64_t longest = (uint64_t)e->ix->k;
+    uint64_t longest = 0;
     for (uint64_t i = 0; i <= n_reads; i++) {
         sl.h_off[i] = offsets[i] - base0;
         if (i) longest = std::max(longest, offsets[i] - offsets[i - 1]);
     }
-    const uint32_t stride = (uint32_t)std::min<uint64_t>((longest + 15) / 16, 4095);
-    const uint64_t maxb = std::min<uint64_t>((uint64_t)stride * 16, 65535);
-    const uint64_t cap = n_reads + total / (uint64_t)e->ix->k + total / (maxb - (uint64_t)(e->ix->k - 1)) + 16;   // bound on the records
+    const PackGeom g(e->ix->k, n_reads, total, longest);
 
     if (sl.d_bases.n < total + 1) BK_HIP(sl.d_bases.alloc(total + total / 4 + 4096));
     if (sl.d_off.n < n_reads + 1) BK_HIP(sl.d_off.alloc(n_reads + n_reads / 4 + 1024));
-    if (sl.d_words.n < cap * stride) BK_HIP(sl.d_words.alloc(cap * stride + cap * stride / 4));
-    if (sl.d_lens.n < cap) BK_HIP(sl.d_lens.alloc(cap + cap / 4));
+    if (sl.d_words.n < g.cap * g.stride) BK_HIP(sl.d_words.alloc(g.cap * g.stride + g.cap * g.stride / 4));
+    if (sl.d_lens.n < g.cap) BK_HIP(sl.d_lens.alloc(g.cap + g.cap / 4));
     if (!sl.d_nrec.p) BK_HIP(sl.d_nrec.alloc(4));
     if (sl.d_work.n < n_reads) BK_HIP(sl.d_work.alloc(n_reads + n_reads / 4 + 1024));
 
@@ -608,15 +680,7 @@ int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64
     BK_HIP(hipMemcpyAsync(sl.d_off.p, sl.h_off, (n_reads + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, e->copy_stream));
     BK_HIP(hipEventRecord(sl.uploaded, e->copy_stream));
     BK_HIP(hipStreamWaitEvent(e->stream, sl.uploaded, 0));
-    {
-        bk::PackArgs pa{};
-        pa.bases = sl.d_bases.p; pa.offsets = sl.d_off.p; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = stride;
-        pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
-        bk_engine::Span sp(e, 2);
-        bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream);   // (records pushed: tallied on the device)
-    }
-    int rc = push_device(e, mate, sl.d_words.p, stride, sl.d_lens.p, cap, sl.d_nrec.p, total);   // (a batch holds fewer k-mers than bases)
-    if (rc != BK_OK) return rc;
+    if (int rc = pack_and_push(e, mate, sl, sl.d_bases.p, 0, sl.d_off.p, n_reads, total, g)) return rc;
     BK_HIP(hipEventRecord(sl.done, e->stream));
     sl.busy = true;
     return BK_OK;
@@ -624,61 +688,33 @@ int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64
 
 int bk_push_reads_ascii_device(bk_engine* e, int mate, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t total_bases,
                                uint32_t longest_read) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (!e->in_sample) return fail(BK_ERR_STATE, "bk_push_reads_* called before bk_sample_begin");
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (n_reads == 0) return BK_OK;
-    if (!d_bases || !d_offsets) return fail(BK_ERR_INVALID, "bad read batch");
-    if (total_bases >= (1ull << 32)) return fail(BK_ERR_INVALID, "batch too large: push at most 2^32 bases per call");
-    BK_HIP(hipSetDevice(e->device));
+    if (int rc = push_checks(e, mate, n_reads, d_bases && d_offsets, "bad read batch", total_bases >= (1ull << 32)); rc != kPush) return rc;
     // (everything is ordered by the engine's stream: the records of the previous batch were consumed by its scan before this
     // batch's packer starts, so one set of record buffers does)
     bk_engine::IngestSlot& sl = e->dev_ascii;
-    const uint64_t longest = std::max<uint64_t>(longest_read, (uint64_t)e->ix->k);
-    const uint32_t stride = (uint32_t)std::min<uint64_t>((longest + 15) / 16, 4095);
-    const uint64_t maxb = std::min<uint64_t>((uint64_t)stride * 16, 65535);
-    const uint64_t cap = n_reads + total_bases / (uint64_t)e->ix->k + total_bases / (maxb - (uint64_t)(e->ix->k - 1)) + 16;   // bound on the records
-    if (sl.d_words.n < cap * stride || sl.d_lens.n < cap || sl.d_work.n < n_reads) {
+    const PackGeom g(e->ix->k, n_reads, total_bases, longest_read);
+    if (sl.d_words.n < g.cap * g.stride || sl.d_lens.n < g.cap || sl.d_work.n < n_reads) {
         BK_HIP(hipStreamSynchronize(e->stream));
-        BK_HIP(sl.d_words.alloc(cap * stride + cap * stride / 4));
-        BK_HIP(sl.d_lens.alloc(cap + cap / 4));
+        BK_HIP(sl.d_words.alloc(g.cap * g.stride + g.cap * g.stride / 4));
+        BK_HIP(sl.d_lens.alloc(g.cap + g.cap / 4));
         BK_HIP(sl.d_work.alloc(n_reads + n_reads / 4 + 1024));
     }
     if (!sl.d_nrec.p) BK_HIP(sl.d_nrec.alloc(4));
-    {
-        bk::PackArgs pa{};
-        // the packer stages the lines with 16-byte loads from a 16-byte boundary: a pointer into the middle of an allocation (any
-        // alignment) is rounded down and the offsets carry the difference (a device allocation starts on a 256-byte boundary, so the
-        // bytes in front belong to the same allocation)
-        pa.shift = (uint32_t)(reinterpret_cast<uintptr_t>(d_bases) & 15u);
-        pa.bases = static_cast<const uint8_t*>(d_bases) - pa.shift; pa.offsets = static_cast<const unsigned long long*>(d_offsets); pa.n_reads = n_reads;
-        pa.k = e->ix->k; pa.stride_words = stride;
-        pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
-        bk_engine::Span sp(e, 2);
-        bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream);   // (records pushed: tallied on the device)
-    }
-    return push_device(e, mate, sl.d_words.p, stride, sl.d_lens.p, cap, sl.d_nrec.p, total_bases);
+    // the packer stages the lines with 16-byte loads from a 16-byte boundary: a pointer into the middle of an allocation (any
+    // alignment) is rounded down and the offsets carry the difference (a device allocation starts on a 256-byte boundary, so the
+    // bytes in front belong to the same allocation)
+    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(d_bases) & 15u);
+    return pack_and_push(e, mate, sl, static_cast<const uint8_t*>(d_bases) - shift, shift, static_cast<const unsigned long long*>(d_offsets), n_reads,
+                         total_bases, g);
 }
 
 int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, uint64_t n) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (!e->in_sample) return fail(BK_ERR_STATE, "bk_push_reads_* called before bk_sample_begin");
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (n == 0) return BK_OK;
-    if (!d_words || !d_lens || stride_words == 0 || stride_words > 4096) return fail(BK_ERR_INVALID, "bad record batch");
-    if (n > (1ull << 32) / ((uint64_t)stride_words * 16)) return fail(BK_ERR_INVALID, "batch too large: push at most 2^32 bases per call");
-    BK_HIP(hipSetDevice(e->device));
+    if (int rc = packed_checks(e, mate, d_words, stride_words, d_lens, n); rc != kPush) return rc;
     return push_device(e, mate, static_cast<const uint32_t*>(d_words), stride_words, static_cast<const uint16_t*>(d_lens), n);
 }
 
 int bk_push_reads_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, uint64_t n) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (!e->in_sample) return fail(BK_ERR_STATE, "bk_push_reads_* called before bk_sample_begin");
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (n == 0) return BK_OK;
-    if (!words || !lens || stride_words == 0 || stride_words > 4096) return fail(BK_ERR_INVALID, "bad record batch");
-    if (n > (1ull << 32) / ((uint64_t)stride_words * 16)) return fail(BK_ERR_INVALID, "batch too large: push at most 2^32 bases per call");
-    BK_HIP(hipSetDevice(e->device));
+    if (int rc = packed_checks(e, mate, words, stride_words, lens, n); rc != kPush) return rc;
     const size_t nw = (size_t)n * stride_words;
     bk_engine::StageSlot& sl = e->stage[e->next_stage];
     e->next_stage ^= 1;
@@ -716,11 +752,10 @@ int bk_counters_device_ptr(bk_engine* e, int mate, void** d_ptr) {
     if (e->pending.on) { BK_HIP(hipSetDevice(e->device)); if (int rc = flush_pending_items(e)) return rc; }
     if (e->in_sample) {   // a mate file nothing was pushed for yet: its plane is zeroed lazily -- now, before the caller reduces it
         BK_HIP(hipSetDevice(e->device));
-        if (int rc = zero_plane_if_stale(e, mate)) return rc;
+        if (int rc = e->mate[mate].zero_if_stale(e)) return rc;
     }
-    e->plane_used[mate] = true;   // (the caller may write it: collectives)
-    e->v_clean[mate] = false;     // ... so the next bin_count launch adds to the V part instead of storing over it
-    *d_ptr = e->counters[mate].p;
+    e->mate[mate].handed_out();   // (so the next bin_count launch adds to the V part instead of storing over it)
+    *d_ptr = e->mate[mate].counters.p;
     return BK_OK;
 }
 
@@ -730,197 +765,148 @@ int bk_pileup_device_ptr(bk_engine* e, void** d_ptr) {
     return BK_OK;
 }
 
+// One finalize call: the part of the planes it maps; pileup_selected_only's two passes (the statistics of every genome, the genome's
+// selection, its votes); gathered votes (the statistics pass, then gather_votes_kernel); whole dense planes, which it leaves zeroed
+struct FinalizeCall { int n_mates; uint64_t elem_lo, elem_hi; bool two_pass = false, gather = false, clean_dense = false; };
+// sparse planes: the touch bitmaps -> the lists finalize walks
+static int compact_sparse_lists(bk_engine* e, int n_mates) {
+    const IndexTables& ix = *e->ix;
+    for (int m = 0; m < n_mates; m++) {
+        MatePlane& pl = e->mate[m];
+        bk_engine::Span sp(e, 1);
+        BK_HIP(hipMemsetAsync(pl.n_list.p, 0, 8 * sizeof(unsigned int), e->stream));
+#ifdef BK_TESTING
+        if (ix.ablate == 15) BK_HIP(hipMemsetAsync(pl.touch_b.p, 0xff, pl.touch_b.n * 4, e->stream));   // (15: every block counts as touched)
+#endif
+        bk::launch_expand_touched_blocks(pl.touch_b.p, (uint32_t)((ix.total_cells + 63) / 64), ix.cell_blk.p, pl.touch_v.p, (uint32_t)ix.k,
+                                         (uint64_t)ix.n_full + (uint64_t)ix.v_span, e->stream);
+        bk::launch_compact_touched(pl.touch_v.p, bk::v_real_rows(ix.n_full, ix.v_span), pl.touch_p.p, ix.n_prows, pl.touch_e.p, ix.n_u,
+                                   ix.n_full, pl.v_list.p, pl.p_list.p, pl.e_list.p, pl.n_list.p, e->stream);
+    }
+    return BK_OK;
+}
+static bk::FinalizeArgs finalize_args(const bk_engine* e, const FinalizeCall& c, int m, int pass) {
+    const IndexTables& ix = *e->ix;
+    const MatePlane& pl = e->mate[m];
+    bk::FinalizeArgs a{};
+    a.ix = ix.view();
+    // (a part that came through bk_shard_received lives in its own buffer: element i of the plane is reduced[i - elem_lo])
+    a.counters = pl.reduced_shards > 0 ? pl.reduced.p - c.elem_lo : pl.counters.p;
+    a.elem_lo = c.elem_lo; a.elem_hi = c.elem_hi; a.ci = e->params.ci; a.cs = e->params.cs; a.cx = e->params.cx; a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
+    a.stats = e->stats.p + (size_t)m * ix.n_files * 3; a.present = e->present.p + (size_t)m * ix.n_files; a.kept_total = e->kstats.p + m * 4 + 3; a.distinct_total = e->kstats.p + m * 4 + 2;
+    a.partials = e->fin_partials.p; a.n_deferred = e->n_deferred.p + m;
+    a.deferred = e->deferred.p + (c.two_pass ? (size_t)m * (e->deferred.n / 2) : 0);   // (kept from the first pass to the second)
+    a.file_cell_lo = ix.file_cell_lo_d.p; a.max_file_cells = (uint32_t)ix.max_file_cells_idx;
+    a.deferred_mask = c.two_pass && e->deferred_mask.p ? e->deferred_mask.p + (size_t)m * (e->deferred_mask.n / 2) : nullptr;
+    a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2; a.ktab_overflow = e->ktab_out.p + 4; a.mate = (uint32_t)m;
+    if (e->sparse) { a.v_list = pl.v_list.p; a.p_list = pl.p_list.p; a.e_list = pl.e_list.p; a.n_list = pl.n_list.p; }
+    a.deferred_n = e->deferred_n.p ? e->deferred_n.p + (c.two_pass ? (size_t)m * (e->deferred_n.n / 2) : 0) : nullptr;
+    a.clear_v = c.clean_dense && pass == (c.two_pass ? 1 : 0);
+    a.mode = c.two_pass ? pass + 1 : c.gather ? (pass == 0 ? 1 : 3) : 0;
+    if (c.gather) {
+        if (const char* ga = test_env("BK_GATHER_ABLATE")) a.gather_ablate = atoi(ga);
+        a.merged_slots = ix.merged_slots.p; a.n_merged_slots = ix.n_merged_slots;
+        a.gather = pass == 1 ? 1 : 0; a.alias_hits = pl.alias_hits.p; a.n_alias_hits = e->n_alias_hits.p + m; a.alias_cap = bk_engine::kAliasCap;
+    }
+    a.sel = c.two_pass ? &e->sel_out.p->file_id : nullptr; a.sel_file = -1;
+    // dense planes mapped whole: K2a zeroes the V counters it reads; the E part (two counters per reference k-mer) is zeroed by
+    // the reduce kernel of the mate file's last statistics pass (it runs behind K2e, the E part's only reader in that pass;
+    // a second, votes-only pass reads it again: then clean_planes' memset does it)
+    const bool ride = c.clean_dense && !c.two_pass && e->fin_partials.p && pl.used;
+    a.no_lean = test_env("BK_NO_LEAN_FINALIZE") != nullptr; a.lean_e_list = e->lean_e_list.p; a.lean_n_list = e->lean_n_list.p;
+    a.zero_e = ride ? pl.counters.p : nullptr; a.zero_e_n = ride ? (size_t)std::min<uint64_t>(ix.v_off, ix.plane_len) : 0;
+    return a;
+}
+// the end of a whole-sample finalize: what the maps read is zeroed again, so the planes are all zero for the next sample; the
+// statistics table's distinct and kept k-mers are counted
+static int clean_planes(bk_engine* e, const FinalizeCall& c) {
+    const IndexTables& ix = *e->ix;
+    for (int m = 0; m < c.n_mates && c.clean_dense; m++) {   // K2a zeroed the V counters; the E part (two counters per reference k-mer) goes here
+        MatePlane& pl = e->mate[m];
+        if (pl.used) {
+            bk_engine::Span sp(e, 2);
+            BK_HIP(hipMemsetAsync(pl.counters.p, 0, (size_t)std::min<uint64_t>(ix.v_off, ix.plane_len) * sizeof(unsigned long long), e->stream));
+        }
+        pl.finalized_clean();
+    }
+    for (int m = 0; m < c.n_mates && e->sparse; m++) {   // the maps are done: clear_touched zeroes what they read
+        MatePlane& pl = e->mate[m];
+        bk_engine::Span sp(e, 1);
+        bk::launch_clear_touched(pl.counters.p, ix.v_off, bk::v_real_len(ix.n_full, ix.v_span), (uint32_t)ix.v_span + 1u, pl.v_list.p, pl.p_list.p,
+                                 pl.e_list.p, pl.n_list.p, ix.n_u, e->stream);
+        pl.finalized_clean();
+    }
+    if (e->ktab.keys.p) { bk_engine::Span sp(e, 1); bk::launch_ktab_stats(e->ktab.keys.p, e->ktab.cnt.p, e->ktab.log2, e->params.ci, e->params.cx, e->ktab_out.p, e->stream); }
+    return BK_OK;
+}
 static int finalize_part(bk_engine* e, int n_mates, uint64_t elem_lo, uint64_t elem_hi) {
     const IndexTables& ix = *e->ix;
     if (!e->in_sample) return fail(BK_ERR_STATE, "bk_sample_finalize called before bk_sample_begin");
     if (n_mates < 1 || n_mates > 2) return fail(BK_ERR_INVALID, "n_mates must be 1 or 2");
     BK_HIP(hipSetDevice(e->device));
+    const bool whole = elem_lo == 0 && elem_hi == ix.plane_len;
+    const bool via_reduced = e->mate[0].reduced_shards > 0 || e->mate[1].reduced_shards > 0;   // (the planes themselves are not what is mapped: they are zeroed at the next push)
     // bk_params.pileup_selected_only (several genome files): first the statistics of every genome without a single vote, then the
-    // genome is selected on the device (call.rs:422-502), then the votes -- only the BucketInfos of that genome
-    const bool two_pass = e->params.pileup_selected_only != 0 && ix.n_files > 1;
-    if (two_pass && (elem_lo != 0 || elem_hi != ix.plane_len)) return fail(BK_ERR_UNSUPPORTED, "pileup_selected_only cannot be combined with a sharded finalize");
-    if (e->sparse && (elem_lo != 0 || elem_hi != ix.plane_len)) return fail(BK_ERR_UNSUPPORTED, "an index this large cannot be finalized in shards");
-    const bool via_reduced = e->reduced_shards[0] > 0 || e->reduced_shards[1] > 0;   // (the planes themselves are not what is mapped: they are zeroed at the next push)
-    const bool clean_dense = !e->sparse && elem_lo == 0 && elem_hi == ix.plane_len && !via_reduced;   // this call maps whole planes: it leaves them zeroed
-    if (e->sparse) {
-        for (int m = 0; m < n_mates; m++) {
+    // genome is selected on the device (call.rs:422-502), then the votes -- only the BucketInfos of that genome.  Gathered votes
+    // (bk_gather.hip): the statistics pass as ever, then gather_votes_kernel for the selected genome's cells or for all
+    FinalizeCall c{n_mates, elem_lo, elem_hi};
+    c.two_pass = e->params.pileup_selected_only != 0 && ix.n_files > 1;
+    c.gather = e->gather_mode && whole && !via_reduced;
+    c.clean_dense = !e->sparse && whole && !via_reduced;   // (this call maps whole planes: it leaves them zeroed)
+    if (c.two_pass && !whole) return fail(BK_ERR_UNSUPPORTED, "pileup_selected_only cannot be combined with a sharded finalize");
+    if (e->sparse && !whole) return fail(BK_ERR_UNSUPPORTED, "an index this large cannot be finalized in shards");
+    if (e->sparse) { if (int rc = compact_sparse_lists(e, n_mates)) return rc; }
+    if (c.gather) BK_HIP(hipMemsetAsync(e->n_alias_hits.p, 0, 2 * sizeof(unsigned int), e->stream));
+    auto sync_debug = [e](const char* what) -> int {   // testing build, BK_SYNC_DEBUG: which launch of the gathered voting pass faults
+        if (test_env("BK_SYNC_DEBUG")) { fprintf(stderr, "[bk] %s ...", what); BK_HIP(hipStreamSynchronize(e->stream)); fprintf(stderr, " ok\n"); }
+        return BK_OK;
+    };
+    for (int pass = 0; pass < ((c.two_pass || c.gather) ? 2 : 1); pass++) {
+        const bool votes = c.gather && pass == 1;
+        if (votes) {   // difference arrays -> counts (the rows are zeroed behind the sample)
             bk_engine::Span sp(e, 1);
-            BK_HIP(hipMemsetAsync(e->n_list[m].p, 0, 8 * sizeof(unsigned int), e->stream));
-#ifdef BK_TESTING
-            if (ix.ablate == 15) BK_HIP(hipMemsetAsync(e->touch_b[m].p, 0xff, e->touch_b[m].n * 4, e->stream));   // (15: every block counts as touched)
-#endif
-            bk::launch_expand_touched_blocks(e->touch_b[m].p, (uint32_t)((ix.total_cells + 63) / 64), ix.cell_blk.p, e->touch_v[m].p, (uint32_t)ix.k,
-                                             (uint64_t)ix.n_full + (uint64_t)ix.v_span, e->stream);
-            bk::launch_compact_touched(e->touch_v[m].p, bk::v_real_rows(ix.n_full, ix.v_span), e->touch_p[m].p, ix.n_prows, e->touch_e[m].p, ix.n_u,
-                                       ix.n_full, e->v_list[m].p, e->p_list[m].p, e->e_list[m].p, e->n_list[m].p, e->stream);
-        }
-    }
-    // gathered votes (bk_gather.hip): the statistics pass as ever, then gather_votes_kernel for the selected genome's cells or for all
-    const bool gather = e->gather_mode && elem_lo == 0 && elem_hi == ix.plane_len && !via_reduced;
-    if (gather) BK_HIP(hipMemsetAsync(e->n_alias_hits.p, 0, 2 * sizeof(unsigned int), e->stream));
-    for (int pass = 0; pass < ((two_pass || gather) ? 2 : 1); pass++) {
-        auto dbg_sync = [&](const char* what) -> int {   // testing build, BK_SYNC_DEBUG: which launch of the gathered voting pass faults
-            if (test_env("BK_SYNC_DEBUG")) { fprintf(stderr, "[bk] %s ...", what); BK_HIP(hipStreamSynchronize(e->stream)); fprintf(stderr, " ok\n"); }
-            return BK_OK;
-        };
-        if (gather && pass == 1) {   // difference arrays -> counts (the rows are zeroed behind the sample)
-            bk_engine::Span sp(e, 1);
-            if (int rc = dbg_sync("statistics pass")) return rc;
-            // (every genome's rows by the table of voters: which V rows the sample's mate files touched, as bits)
-            unsigned int* row_bits = nullptr;
-            if (e->row_bits.p) {   // (allocated with the engine: alloc_sample_state)
-                BK_HIP(hipMemsetAsync(e->row_bits.p, 0, e->row_bits.n * sizeof(unsigned int), e->stream));
-                row_bits = e->row_bits.p;
-            }
-            for (int m = 0; m < n_mates; m++) bk::launch_prefix_rows(e->counters[m].p, ix.view(), e->v_list[m].p, e->n_list[m].p, row_bits, e->stream);
-            if (int rc = dbg_sync("prefix_rows")) return rc;
+            if (int rc = sync_debug("statistics pass")) return rc;
+            // (every genome's rows by the table of voters, allocated with the engine: which V rows the sample's mate files touched, as bits)
+            if (e->row_bits.p) BK_HIP(hipMemsetAsync(e->row_bits.p, 0, e->row_bits.n * sizeof(unsigned int), e->stream));
+            for (int m = 0; m < n_mates; m++) bk::launch_prefix_rows(e->mate[m].counters.p, ix.view(), e->mate[m].v_list.p, e->mate[m].n_list.p, e->row_bits.p, e->stream);
+            if (int rc = sync_debug("prefix_rows")) return rc;
         }
         for (int m = 0; m < n_mates; m++) {   // R1 then R2 into the same arrays (call.rs:316-317)
-            bk::FinalizeArgs a{};
-            a.ix = ix.view();
-            a.counters = e->counters[m].p;
-            // (a part that came through bk_shard_received lives in its own buffer: element i of the plane is reduced[i - elem_lo])
-            if (e->reduced_shards[m] > 0) a.counters = e->reduced[m].p - elem_lo;
-            a.elem_lo = elem_lo; a.elem_hi = elem_hi;
-            a.ci = e->params.ci; a.cs = e->params.cs; a.cx = e->params.cx;
-            a.pileup = e->pileup.p;
-            a.plane = (size_t)ix.total_cells * 4;
-            a.stats = e->stats.p + (size_t)m * ix.n_files * 3;
-            a.present = e->present.p + (size_t)m * ix.n_files;
-            a.kept_total = e->kstats.p + m * 4 + 3;
-            a.distinct_total = e->kstats.p + m * 4 + 2;
-            a.partials = e->fin_partials.p;
-            a.deferred = e->deferred.p + (two_pass ? (size_t)m * (e->deferred.n / 2) : 0);   // (kept from the first pass to the second)
-            a.file_cell_lo = ix.file_cell_lo_d.p; a.max_file_cells = (uint32_t)ix.max_file_cells_idx;
-            a.n_deferred = e->n_deferred.p + m;
-            a.deferred_mask = two_pass && e->deferred_mask.p ? e->deferred_mask.p + (size_t)m * (e->deferred_mask.n / 2) : nullptr;
-            a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2;
-            a.ktab_overflow = e->ktab_out.p + 4; a.mate = (uint32_t)m;
-            if (e->sparse) { a.v_list = e->v_list[m].p; a.p_list = e->p_list[m].p; a.e_list = e->e_list[m].p; a.n_list = e->n_list[m].p; }
-            a.deferred_n = e->deferred_n.p ? e->deferred_n.p + (two_pass ? (size_t)m * (e->deferred_n.n / 2) : 0) : nullptr;
-            a.clear_v = clean_dense && pass == (two_pass ? 1 : 0);
-            a.mode = two_pass ? pass + 1 : gather ? (pass == 0 ? 1 : 3) : 0;
-            if (gather) if (const char* ga = test_env("BK_GATHER_ABLATE")) a.gather_ablate = atoi(ga);
-            if (gather) { a.merged_slots = ix.merged_slots.p; a.n_merged_slots = ix.n_merged_slots; }
-            if (gather) { a.gather = pass == 1 ? 1 : 0; a.alias_hits = e->alias_hits[m].p; a.n_alias_hits = e->n_alias_hits.p + m; a.alias_cap = bk_engine::kAliasCap; }
-            a.sel = two_pass ? &e->sel_out.p->file_id : nullptr;
-            a.sel_file = -1;
-            // dense planes mapped whole: K2a zeroes the V counters it reads; the E part (two counters per reference k-mer) is zeroed by
-            // the reduce kernel of the mate file's last statistics pass (it runs behind K2e, the E part's only reader in that pass;
-            // a second, votes-only pass reads it again: then the memset below does it)
-            const bool ride = clean_dense && !two_pass && e->fin_partials.p && e->plane_used[m];
-            a.no_lean = test_env("BK_NO_LEAN_FINALIZE") != nullptr;
-            a.lean_e_list = e->lean_e_list.p; a.lean_n_list = e->lean_n_list.p;
-            a.zero_e = ride ? e->counters[m].p : nullptr;
-            a.zero_e_n = ride ? (size_t)std::min<uint64_t>(ix.v_off, ix.plane_len) : 0;
-            if (ride) e->plane_used[m] = false;
-            if (pass == 0) { if (int rc = zero_plane_if_stale(e, m)) return rc; }
+            bk::FinalizeArgs a = finalize_args(e, c, m, pass);
+            if (a.zero_e) e->mate[m].finalized_clean();   // (this pass's kernels leave the whole plane zeroed)
+            if (pass == 0) { if (int rc = e->mate[m].zero_if_stale(e)) return rc; }
             if (e->pending.on && e->pending.mate == m) {
                 // the mate file's reads were one launch: the regional finalize takes the V counts from the scan's items
                 const bk::BinArgs& pb = e->pending.b;
                 a.f_items = pb.items; a.f_tab = pb.tab; a.f_gext = pb.gext; a.f_ov = pb.ov; a.f_ov_n = pb.ov_n; a.f_ov_cap = pb.ov_cap; a.f_ov_par = pb.ov_par;
-                a.f_n_wg = pb.n_wg; a.f_ig = pb.ig; a.f_touch = e->fuse_touch[m].p;
-                if (clean_dense && !two_pass && bk::finalize_runs_by_region(a)) { e->pending.on = false; e->touch_used[m] = false; }
+                a.f_n_wg = pb.n_wg; a.f_ig = pb.ig; a.f_touch = e->mate[m].fuse_touch.p;
+                if (c.clean_dense && !c.two_pass && bk::finalize_runs_by_region(a)) { e->pending.on = false; e->mate[m].items_taken(); }
                 else { a.f_items = nullptr; if (int rc = flush_pending_items(e)) return rc; }
             }
             bk_engine::Span sp(e, 1);
-            if (gather && pass == 1 && m == 0) {   // (both mate files' counts at once: it stores)
-                const unsigned long long* c1 = n_mates == 2 ? e->counters[1].p : nullptr;
+            if (votes && m == 0) {   // (both mate files' counts at once: it stores)
+                const unsigned long long* c1 = n_mates == 2 ? e->mate[1].counters.p : nullptr;
                 // many genomes that share their k-mers: the voters once per (k-mer, window position), not once per occurrence
-                const bool by_table = bk::vote_table_fits(a) && e->row_bits.p && e->vote_tab.n >= bk::vote_table_words(a.ix);
-                if (by_table) bk::launch_gather_votes_table(a, c1, e->vote_tab.p, e->row_bits.p, e->stream);
+                if (bk::vote_table_fits(a) && e->row_bits.p && e->vote_tab.n >= bk::vote_table_words(a.ix)) bk::launch_gather_votes_table(a, c1, e->vote_tab.p, e->row_bits.p, e->stream);
                 else bk::launch_gather_votes(a, c1, e->stream);
-                if (int rc = dbg_sync("gather_votes")) return rc;
+                if (int rc = sync_debug("gather_votes")) return rc;
             }
-            if (gather && pass == 1 && ix.n_merged_slots) { bk::launch_merged_votes(a, e->stream); if (int rc = dbg_sync("merged_votes")) return rc; }
+            if (votes && ix.n_merged_slots) { bk::launch_merged_votes(a, e->stream); if (int rc = sync_debug("merged_votes")) return rc; }
             bk::launch_finalize(a, e->stream);
-            if (gather && pass == 1) if (int rc = dbg_sync("alias-only general kernels")) return rc;
+            if (votes) if (int rc = sync_debug("alias-only general kernels")) return rc;
         }
-        if (two_pass && pass == 0) {
-            bk::CallArgs c{};
-            c.n_files = ix.n_files; c.n_mates = n_mates; c.stats = e->stats.p; c.present = e->present.p; c.genome_len = ix.genome_len.p;
-            c.out = e->sel_out.p;
+        if (c.two_pass && pass == 0) {
+            bk::CallArgs s{};
+            s.n_files = ix.n_files; s.n_mates = n_mates; s.stats = e->stats.p; s.present = e->present.p; s.genome_len = ix.genome_len.p; s.out = e->sel_out.p;
             bk_engine::Span sp(e, 1);
-            bk::launch_select_genome(c, e->stream);
-            if (gather) bk::launch_copy_int(e->last_sel.p, &e->sel_out.p->file_id, e->stream);   // (the rows the next sample zeroes)
+            bk::launch_select_genome(s, e->stream);
+            if (c.gather) bk::launch_copy_int(e->last_sel.p, &e->sel_out.p->file_id, e->stream);   // (the rows the next sample zeroes)
         }
     }
-    if (clean_dense) {   // K2a zeroed the V counters; the E part (two counters per reference k-mer) goes here
-        for (int m = 0; m < n_mates; m++) {
-            if (e->plane_used[m]) {
-                bk_engine::Span sp(e, 2);
-                BK_HIP(hipMemsetAsync(e->counters[m].p, 0, (size_t)std::min<uint64_t>(ix.v_off, ix.plane_len) * sizeof(unsigned long long), e->stream));
-            }
-            e->plane_used[m] = false;
-        }
-    }
-    if (e->sparse) {   // the maps are done: what they read is zeroed again, the planes are all zero for the next sample
-        for (int m = 0; m < n_mates; m++) {
-            bk_engine::Span sp(e, 1);
-            bk::launch_clear_touched(e->counters[m].p, ix.v_off, bk::v_real_len(ix.n_full, ix.v_span), (uint32_t)ix.v_span + 1u, e->v_list[m].p,
-                                     e->p_list[m].p, e->e_list[m].p, e->n_list[m].p, ix.n_u, e->stream);
-            e->plane_used[m] = false;
-        }
-    }
-    if (e->ktab.keys.p) {
-        bk_engine::Span sp(e, 1);
-        bk::launch_ktab_stats(e->ktab.keys.p, e->ktab.cnt.p, e->ktab.log2, e->params.ci, e->params.cx, e->ktab_out.p, e->stream);
-    }
+    if (int rc = clean_planes(e, c)) return rc;
     BK_HIP(hipGetLastError());
-    e->in_sample = false;
-    e->finalized_mates = n_mates;
-    if (e->dbg.p) {   // BK_L2_STATS (testing build)
-        unsigned long long h[32];
-        unsigned int nd[2] = {0, 0};
-        BK_HIP(hipMemcpyAsync(nd, e->n_deferred.p, sizeof nd, hipMemcpyDeviceToHost, e->stream));
-        std::vector<unsigned long long> clk(4 * 1024);
-        BK_HIP(hipMemcpyAsync(h, e->dbg.p, sizeof h, hipMemcpyDeviceToHost, e->stream));
-        BK_HIP(hipMemcpyAsync(clk.data(), e->dbg.p + 32, clk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-        BK_HIP(hipMemsetAsync(e->dbg.p, 0, (32 + 4 * 1024) * sizeof(unsigned long long), e->stream));
-        BK_HIP(hipStreamSynchronize(e->stream));
-        {   // the scan's workgroups on the clock (the sample's last launch): when each started, had its reference, ran out of tiles, ended
-            unsigned long long t0 = ~0ull;
-            int n_wg = 0;
-            for (int b = 0; b < 512; b++) if (clk[4 * b]) { t0 = std::min(t0, clk[4 * b]); n_wg = b + 1; }   // (the second half holds the prologue clocks)
-            if (n_wg) {
-                double mx[4] = {0, 0, 0, 0}, mean[4] = {0, 0, 0, 0}, mn[4] = {1e30, 1e30, 1e30, 1e30};
-                for (int b = 0; b < n_wg; b++)
-                    for (int j = 0; j < 4; j++) {
-                        const double us = (double)(clk[4 * b + j] - t0) * 0.01;
-                        mx[j] = std::max(mx[j], us); mn[j] = std::min(mn[j], us); mean[j] += us / n_wg;
-                    }
-                fprintf(stderr, "[bk] scan workgroups (%d), us after the first start, min / mean / max: start %.1f / %.1f / %.1f, reference staged %.1f / %.1f / %.1f, "
-                        "tiles done %.1f / %.1f / %.1f, end %.1f / %.1f / %.1f\n", n_wg, mn[0], mean[0], mx[0], mn[1], mean[1], mx[1], mn[2], mean[2], mx[2], mn[3], mean[3], mx[3]);
-                {
-                    double m2[4] = {0, 0, 0, 0};
-                    int n2 = 0;
-                    for (int b = 0; b < std::min(n_wg, 512); b++) if (clk[2048 + 4 * b]) { n2++; for (int j = 0; j < 4; j++) m2[j] += (double)(clk[2048 + 4 * b + j] - t0) * 0.01; }
-                    if (n2) fprintf(stderr, "[bk]   ... mean: first tile's copy sent %.1f, window's loads stored %.1f, wave 0 has its first tile %.1f, buckets written out %.1f\n",
-                                    m2[0] / n2, m2[1] / n2, m2[2] / n2, m2[3] / n2);
-                }
-                if (test_env("BK_L2_STATS")[0] == '2')
-                    for (int b = 0; b < n_wg; b++) fprintf(stderr, "[bk]   wg %d: %.1f %.1f %.1f %.1f\n", b, (clk[4 * b] - t0) * 0.01, (clk[4 * b + 1] - t0) * 0.01, (clk[4 * b + 2] - t0) * 0.01, (clk[4 * b + 3] - t0) * 0.01);
-            }
-        }
-        fprintf(stderr, "[bk] finalize: %u + %u k-mers deferred to the general kernel\n", nd[0], nd[1]);
-        if (e->gather_mode) {
-            unsigned int ah[2] = {0u, 0u};
-            BK_HIP(hipMemcpy(ah, e->n_alias_hits.p, sizeof ah, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[bk] votes gathered cell by cell (bk_gather.hip); alias hits among the deferred k-mers: %u + %u\n", ah[0], ah[1]);
-        }
-        if (e->sparse) {
-            unsigned int nl[8];
-            BK_HIP(hipMemcpy(nl, e->n_list[0].p, sizeof nl, hipMemcpyDeviceToHost));
-            fprintf(stderr, "[bk] sparse finalize (mate file 0): %u V rows of %llu, %u pseudo rows of %llu, %u reference k-mers of %u and %u pseudo k-mers of %u touched\n",
-                    nl[0], (unsigned long long)bk::v_real_rows(ix.n_full, ix.v_span), nl[4], (unsigned long long)ix.n_prows, nl[2], ix.n_full, nl[3], ix.n_u - ix.n_full);
-        }
-        fprintf(stderr, "[bk] scan: %llu mismatches counted, %llu items processed, %llu E gaps before a mismatch, %llu behind the last\n", h[23], h[24], h[25], h[26]);
-        fprintf(stderr, "[bk] scan N batches: %llu with %llu pieces (%.1f per batch), %llu of them forced by a tile's end\n", h[20], h[21], h[20] ? (double)h[21] / (double)h[20] : 0.0, h[22]);
-        fprintf(stderr, "[bk] scan marked: no-diagonal %llu, dirty-head %llu, clean-head %llu, pairs %llu | level 2: k-mers %llu in %llu chunks, simple %llu, dead %llu, "
-                "dirty answers %llu (one difference but id unknown: %llu), neither half present %llu, slow %llu (diffs 0/1/2/3+ with a diagonal: %llu/%llu/%llu/%llu) -> member %llu, neighbour %llu, nothing %llu\n",
-                h[0], h[1], h[2], h[3], h[4], h[11], h[5], h[6], h[16], h[17], h[18], h[7], h[12], h[13], h[14], h[15], h[8], h[9], h[10]);
-    }
-    return BK_OK;
+    e->in_sample = false; e->finalized_mates = n_mates;
+    return l2_stats_report(e);
 }
 
 // bk_kmer_dump_enable, at the end of a whole-sample finalize (asynchronous, so that samples in flight never wait between their reads
@@ -932,11 +918,7 @@ static int dump_finalize(bk_engine* e, int n_mates) {
     bk_engine::Span sp(e, 1);
     // bounds on the keys in the table: the tallies of the last push when their copy has arrived (not waited for), else what the
     // growth rule knows; the table's load stays below one half; and a mate file holds no more distinct k-mers than it was pushed
-    if (d.t.fill_pending && hipEventQuery(d.t.fill_ev) == hipSuccess) {
-        uint64_t f = 0;
-        for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) f += d.t.h_fill[i];
-        d.t.fill_known = f; d.t.fill_unknown_upper = 0; d.t.fill_pending = false;
-    }
+    if (d.t.fill_pending && hipEventQuery(d.t.fill_ev) == hipSuccess) d.t.read_fill();
     const uint64_t keys_upper = std::min<uint64_t>((1ull << d.t.log2) / 2, d.t.fill_known + d.t.fill_unknown_upper);
     uint64_t bound[2] = {0, 0}, most = 1;
     size_t tmp_bytes = 0;
@@ -969,7 +951,7 @@ static int dump_finalize(bk_engine* e, int n_mates) {
 
 int bk_sample_finalize(bk_engine* e, int n_mates) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->reduced_shards[0] > 1 || e->reduced_shards[1] > 1) return fail(BK_ERR_STATE, "this sample's planes went through bk_shard_transport: finalize it with bk_sample_finalize_shard");
+    if (e->mate[0].reduced_shards > 1 || e->mate[1].reduced_shards > 1) return fail(BK_ERR_STATE, "this sample's planes went through bk_shard_transport: finalize it with bk_sample_finalize_shard");
     int rc = finalize_part(e, n_mates, 0, e->ix->plane_len);
     if (rc == BK_OK && e->dump) rc = dump_finalize(e, n_mates);
     return rc;
@@ -984,15 +966,15 @@ int bk_sample_finalize_shard(bk_engine* e, int n_mates, int shard, int n_shards)
                                   "(bk_kmer_table_partition, all-to-all, bk_kmer_table_replace)");
     const uint64_t part = e->ix->plane_len / (uint64_t)n_shards;
     for (int m = 0; m < n_mates; m++)
-        if (e->reduced_shards[m] > 0 && (e->reduced_shards[m] != n_shards || e->reduced_shard[m] != shard))
+        if (e->mate[m].reduced_shards > 0 && (e->mate[m].reduced_shards != n_shards || e->mate[m].reduced_shard != shard))
             return fail(BK_ERR_STATE, "bk_sample_finalize_shard(%d of %d): mate file %d received part %d of %d (bk_shard_received)", shard, n_shards, m,
-                        e->reduced_shard[m], e->reduced_shards[m]);
+                        e->mate[m].reduced_shard, e->mate[m].reduced_shards);
     int rc = finalize_part(e, n_mates, part * shard, part * (shard + 1));
     if (rc != BK_OK) return rc;
     if (e->ktab.keys.p) bk::launch_ktab_totals_to_kstats(e->ktab_out.p, e->kstats.p, n_mates, e->stream);   // (the ranks' totals add up)
     for (int m = 0; m < n_mates; m++) {   // the records this rank pushed join the device tally, so that the sum over ranks is the sample's
-        if (e->pushed_records[m]) bk::launch_add_const_u64(e->kstats.p + m * 4 + 0, e->pushed_records[m], e->stream);
-        e->pushed_records[m] = 0;
+        if (e->mate[m].pushed_records) bk::launch_add_const_u64(e->kstats.p + m * 4 + 0, e->mate[m].pushed_records, e->stream);
+        e->mate[m].pushed_records = 0;
     }
     bk::launch_pack_sums(e->shard_sums.p, e->stats.p, e->present.p, e->kstats.p, e->ix->n_files, e->xport_flag.p, e->stream);
     BK_HIP(hipGetLastError());
@@ -1075,9 +1057,9 @@ int bk_shard_measure(bk_engine* e, int mate, void** d_max) {
     if (int rc = shard_args_ok(e, mate, 1, 64)) return rc;
     BK_HIP(hipSetDevice(e->device));
     if (int rc = flush_pending_items(e)) return rc;
-    if (int rc = zero_plane_if_stale(e, mate)) return rc;
+    if (int rc = e->mate[mate].zero_if_stale(e)) return rc;
     BK_HIP(hipMemsetAsync(e->xport_flag.p + 2, 0, 2 * sizeof(unsigned long long), e->stream));
-    bk::launch_xport_measure(e->counters[mate].p, e->ix->plane_len, e->ix->v_off, e->xport_flag.p + 2, e->stream);
+    bk::launch_xport_measure(e->mate[mate].counters.p, e->ix->plane_len, e->ix->v_off, e->xport_flag.p + 2, e->stream);
     BK_HIP(hipGetLastError());
     *d_max = e->xport_flag.p + 2;
     return BK_OK;
@@ -1089,10 +1071,10 @@ int bk_shard_transport(bk_engine* e, int mate, int n_shards, int width, void** d
     const IndexTables& ix = *e->ix;
     BK_HIP(hipSetDevice(e->device));
     if (int rc = flush_pending_items(e)) return rc;
-    if (int rc = zero_plane_if_stale(e, mate)) return rc;   // (a mate file nothing was pushed for: its plane is zeroed lazily -- now)
-    e->plane_used[mate] = true;
+    if (int rc = e->mate[mate].zero_if_stale(e)) return rc;   // (a mate file nothing was pushed for: its plane is zeroed lazily -- now)
+    e->mate[mate].written();
     e->xport_ever = true;
-    if (e->reduced_shards[0] == 0 && e->reduced_shards[1] == 0)   // first transport of this sample
+    if (e->mate[0].reduced_shards == 0 && e->mate[1].reduced_shards == 0)   // first transport of this sample
         BK_HIP(hipMemsetAsync(e->xport_flag.p, 0, sizeof(unsigned long long), e->stream));
     const uint64_t pb = bk::xport_part_bytes(ix.plane_len, ix.v_off, (uint32_t)n_shards, width);
     // Width 16 spends four lanes on an E count: with many shards (or a plane that is mostly E counts) its part is no smaller than
@@ -1101,14 +1083,14 @@ int bk_shard_transport(bk_engine* e, int mate, int n_shards, int width, void** d
         return fail(BK_ERR_INVALID, "width 16 does not shrink the plane at %d shards (every E count takes four 16-bit lanes): use width 32", n_shards);
     // The buffers are sized ONCE, for the worst case over every shard count and width (the whole plane for `reduced`; the
     // largest packed plane and part for the transport), and stay where they are for the engine's lifetime: a host may keep views.
-    if (e->reduced[mate].n < ix.plane_len) {
+    if (e->mate[mate].reduced.n < ix.plane_len) {
         BK_HIP(hipStreamSynchronize(e->stream));
-        BK_HIP(e->reduced[mate].alloc(ix.plane_len));
+        BK_HIP(e->mate[mate].reduced.alloc(ix.plane_len));
     }
     *part_bytes = pb;
     if (width == 64) {   // nothing to pack: the plane itself is the send buffer and the received part is the reduced part
-        *d_send = e->counters[mate].p;
-        *d_recv = e->reduced[mate].p;
+        *d_send = e->mate[mate].counters.p;
+        *d_recv = e->mate[mate].reduced.p;
         return BK_OK;
     }
     if (!e->xport_send.p) {
@@ -1124,7 +1106,7 @@ int bk_shard_transport(bk_engine* e, int mate, int n_shards, int width, void** d
         BK_HIP(e->xport_recv.alloc(max_part));
     }
     bk_engine::Span sp(e, 2);
-    bk::launch_xport_pack(e->counters[mate].p, ix.plane_len, ix.v_off, (uint32_t)n_shards, width, e->xport_send.p, e->xport_flag.p, e->stream);
+    bk::launch_xport_pack(e->mate[mate].counters.p, ix.plane_len, ix.v_off, (uint32_t)n_shards, width, e->xport_send.p, e->xport_flag.p, e->stream);
     BK_HIP(hipGetLastError());
     *d_send = e->xport_send.p;
     *d_recv = e->xport_recv.p;
@@ -1135,15 +1117,15 @@ int bk_shard_received(bk_engine* e, int mate, int shard, int n_shards, int width
     if (int rc = shard_args_ok(e, mate, n_shards, width)) return rc;
     if (shard < 0 || shard >= n_shards) return fail(BK_ERR_INVALID, "0 <= shard < n_shards");
     const uint64_t part = e->ix->plane_len / (uint64_t)n_shards;
-    if (e->reduced[mate].n < part || (width != 64 && !e->xport_recv.p)) return fail(BK_ERR_STATE, "bk_shard_received without bk_shard_transport");
+    if (e->mate[mate].reduced.n < part || (width != 64 && !e->xport_recv.p)) return fail(BK_ERR_STATE, "bk_shard_received without bk_shard_transport");
     BK_HIP(hipSetDevice(e->device));
     if (width != 64) {
         bk_engine::Span sp(e, 2);
-        bk::launch_xport_unpack(e->xport_recv.p, e->ix->plane_len, e->ix->v_off, (uint32_t)n_shards, (uint32_t)shard, width, e->reduced[mate].p, e->stream);
+        bk::launch_xport_unpack(e->xport_recv.p, e->ix->plane_len, e->ix->v_off, (uint32_t)n_shards, (uint32_t)shard, width, e->mate[mate].reduced.p, e->stream);
         BK_HIP(hipGetLastError());
     }
-    e->reduced_shards[mate] = n_shards;
-    e->reduced_shard[mate] = shard;
+    e->mate[mate].reduced_shards = n_shards;
+    e->mate[mate].reduced_shard = shard;
     return BK_OK;
 }
 
@@ -1189,7 +1171,7 @@ int bk_sample_download(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t*
                                       "invalid -- repeat the sample with a wider bk_shard_transport (bk_shard_measure tells which width is safe)");
     if (kmer_stats) {
         for (int m = 0; m < n_mates; m++) {
-            kmer_stats[m * 4 + 0] += e->pushed_records[m];   // + the device-side tally of bk_push_reads_ascii batches
+            kmer_stats[m * 4 + 0] += e->mate[m].pushed_records;   // + the device-side tally of bk_push_reads_ascii batches
             if (e->ktab.keys.p) {
                 // index-touching k-mers are in the counter plane (kept tally in [3], distinct tally in [2] by finalize);
                 // the rest are in the hash table

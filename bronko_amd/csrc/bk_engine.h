@@ -121,6 +121,10 @@ struct GrowTable {
     bool fill_pending = false;              // a copy of the tallies is in flight / unread
     uint64_t fill_known = 0, fill_unknown_upper = 0;   // keys in the table at the last reading; k-mers pushed since (upper bound on new keys)
     std::vector<std::pair<unsigned long long*, unsigned int*>> old;   // outgrown tables, freed at the next sample / destroy
+    void read_fill() {   // (the copy of the tallies has arrived)
+        fill_known = 0; fill_unknown_upper = 0; fill_pending = false;
+        for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) fill_known += h_fill[i];
+    }
     ~GrowTable() {
         for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); }
         if (h_fill) (void)hipHostFree(h_fill);
@@ -217,22 +221,53 @@ struct IndexTables {
 // time its stages.  BK_OK or the error code, with bk_last_error set.
 int build_index_tables(const bk_index_desc* ix, const bk_params* prm, IndexTables& tab, PhaseClock& pc);
 
+// One mate file's counter plane and what a sample keeps beside it (bk_engine::mate).  The plane's states, and what moves it:
+//   stale    it may hold an earlier sample (begin_sample).  zero_if_stale makes it current at the mate file's first push, pointer,
+//            transport or finalize pass, zeroing it only when it is `used`.
+//   used     counters may be non-zero: a push or a transport wrote it (written), or a caller holds it (handed_out).  A finalize of
+//            the whole sample leaves it all zero (finalized_clean: dense planes by K2a and the E part's zeroing, sparse planes by
+//            clear_touched); a sharded or abandoned sample leaves it used for the next zero_if_stale.
+//   v_clean  the V part is known all zero (zero_if_stale): the sample's first bin_count launch stores where it would add
+//            (take_v_clean); a caller's pointer (handed_out) clears it.
+// Fuse (bk_finalize_lean.hip): the V items of the mate file's first scan launch wait (bk_engine::pending) for the regional finalize,
+// which takes its counts from them; Level 2 notes the V rows it writes meanwhile in fuse_touch (items_wait).  A second launch sends
+// the items to the plane first (flush_pending_items) and the mate file waits no more in this sample (no_more_waiting).  The regional
+// finalize clears the rows it read (items_taken); begin_sample clears what an unfinalized sample left.
+struct MatePlane {
+    DevBuf<unsigned long long> counters;
+    DevBuf<unsigned int> touch_v, touch_b, touch_p, touch_e, v_list, p_list, e_list, n_list;   // sparse planes: touch bitmaps, finalize's lists
+    DevBuf<unsigned int> fuse_touch;        // a bit per V row Level 2 wrote to while the launch's items wait
+    DevBuf<unsigned long long> alias_hits;  // gathered votes: the deferred k-mers that reach a bucket through an alias key
+    // sharded finalize: the part of the plane the reduce-scatter leaves here, widened to u64 again (bk_shard_received) -- what
+    // bk_sample_finalize_shard maps; reduced_shards > 0: it holds part `reduced_shard` of that many for the current sample
+    DevBuf<unsigned long long> reduced;
+    int reduced_shards = 0, reduced_shard = 0;
+    uint64_t pushed_records = 0;            // records pushed packed in this sample (the ASCII pushes tally theirs on the device)
+    bool stale = true, used = false, v_clean = false, fuse_off = false, touch_used = false;
+    int begin_sample(bk_engine* e);   // (bk_engine.cpp: these two issue work on the engine's stream)
+    int zero_if_stale(bk_engine* e);
+    void written() { used = true; }
+    void handed_out() { used = true; v_clean = false; }   // (the caller may write it: collectives)
+    void finalized_clean() { used = false; }
+    bool take_v_clean() { const bool c = v_clean; v_clean = false; return c; }
+    void items_wait() { touch_used = true; }
+    void no_more_waiting() { fuse_off = true; }
+    void items_taken() { touch_used = false; }
+};
+
 // One engine: its parameters, its stream and all that a sample writes.  The index tables are `ix`, shared with the engine it was
 // forked from and its forks.
 struct bk_engine {
     bk_params params{};
     std::shared_ptr<const IndexTables> ix;
     DevBuf<unsigned long long> shard_sums;  // sharded finalize: [stats 2*n_files*3 | present 2*n_files | kstats 8 | transport flag]
+    MatePlane mate[2];                      // R1, R2
     // sharded finalize, transport of the planes (bk_shard_transport / bk_shard_received): the packed plane of the mate file being
-    // exchanged, the part the reduce-scatter leaves here, and per mate file the received part widened to u64 again -- what
-    // bk_sample_finalize_shard maps (the plane itself stays as the scans left it)
+    // exchanged and the part the reduce-scatter leaves here (MatePlane::reduced: the plane itself stays as the scans left it)
     DevBuf<unsigned char> xport_send, xport_recv;
-    DevBuf<unsigned long long> reduced[2];
     DevBuf<unsigned long long> xport_flag;  // [0] a packer of this sample met a counter too large for its width, [1] sticky copy after
                                             // the ranks' sums were merged, [2..3] bk_shard_measure: max E count, max |V element|
     bool xport_ever = false;                // some sample of this engine went through bk_shard_transport (bk_sample_download then looks at the flag)
-    int reduced_shards[2] = {0, 0};         // > 0: reduced[m] holds part `reduced_shard[m]` of that many for the current sample
-    int reduced_shard[2] = {0, 0};
     int device = 0;
 
     DevBuf<unsigned int> deferred, n_deferred, deferred_mask;
@@ -248,8 +283,7 @@ struct bk_engine {
     bool gather_mode = false;
     DevBuf<unsigned int> row_bits;              // one bit per V row of the reference k-mers: touched by the sample (set by prefix_rows_kernel for voter_table_kernel)
     DevBuf<uint32_t> vote_tab;                  // [n_full][W][8] the voters of every (reference k-mer, window position) of the sample (bk_gather.hip; every genome's rows)
-    DevBuf<unsigned long long> alias_hits[2];   // per mate file: the deferred k-mers that reach a bucket through an alias key
-    DevBuf<unsigned int> n_alias_hits;          // [2]
+    DevBuf<unsigned int> n_alias_hits;          // [2] (MatePlane::alias_hits)
     static constexpr unsigned int kAliasCap = 1u << 20;
     DevBuf<int> last_sel;                   // pileup_selected_only with gathered votes: the genome whose rows the previous sample wrote (-1: none) -- all that
                                             // the next sample has to zero
@@ -264,27 +298,14 @@ struct bk_engine {
     DevBuf<unsigned long long> ov_n;
     uint32_t ov_par = 0;                    // parity of the next scan_items launch (which of the two overflow counts it appends to)
     DevBuf<unsigned int> lean_e_list, lean_n_list;   // bk_finalize_lean.hip: the reference k-mers finalize_ecell_kernel leaves to finalize_exact_kernel
-    bool v_clean[2] = {false, false};       // the V part of the mate file's plane is known to be all zero (dense planes between samples)
-    // The V items of a mate file's first scan launch are not added to the plane: they wait (`pending`) for the regional finalize,
-    // which takes its counts from them (FinalizeArgs::f_items) -- the whole story for a mate file whose reads are one launch.  A
-    // second launch into the engine's item buffers first sends them to the plane after all (flush_pending_items: bin_count_kernel,
-    // V bins only), and the mate file's later launches go straight there as before.
-    bool fuse_ok = false;                   // this engine's index, planes and parameters admit it (alloc_sample_state)
+    bool fuse_ok = false;                   // the index, planes and parameters admit the fuse (MatePlane; alloc_sample_state)
     struct PendingItems { bool on = false; int mate = 0; bk::BinArgs b{}; } pending;
-    bool fuse_off[2] = {false, false};      // this sample's mate file has had a second launch: no more waiting
-    bool touch_used[2] = {false, false};    // Level 2 set bits in fuse_touch[m] that no regional finalize has cleared
-    DevBuf<unsigned int> fuse_touch[2];     // a bit per V row Level 2 wrote to while the launch's items wait
     DevBuf<unsigned int> n_bits, n_any;     // scan -> Level 2: one bit per k-mer of each record of a launch / per record (bk_kernels.h ScanArgs): the N runs; all zero between launches
     DevBuf<unsigned int> l2_bits;           // Level 2's first pass -> its second: the k-mers looked at one by one, same layout
     DevBuf<unsigned int> l2_any;            // ... one bit per record: its row has bits
     DevBuf<unsigned int> l2_plan;           // one word: the workgroups of level2_kernel that work (ScanArgs::l2_plan)
     DevBuf<uint2> l2_diag;                  // ... and each record's diagonal
-    uint64_t kmers_since_fold = 0;
-    DevBuf<unsigned long long> counters[2];
-    // sparse finalize (large indexes): per mate file the touch bitmaps the counter writers set and the lists finalize walks
-    bool sparse = false;
-    DevBuf<unsigned int> touch_v[2], touch_b[2], touch_p[2], touch_e[2], v_list[2], p_list[2], e_list[2], n_list[2];
-    bool plane_used[2] = {false, false};   // counters were added to since the planes were last known to be all zero
+    bool sparse = false;                    // sparse planes (large indexes): MatePlane's touch bitmaps and lists
     DevBuf<unsigned long long> pileup;      // 4 planes
     DevBuf<unsigned long long> stats;       // [2][n_files][3]
     DevBuf<unsigned char> present;          // [2][n_files]
@@ -317,14 +338,10 @@ struct bk_engine {
     hipStream_t own_stream = nullptr, stream = nullptr;
     bool in_sample = false;
     int finalized_mates = 0;                // mate files of the sample whose finalize was enqueued last (0: none since bk_sample_begin / create)
-    uint64_t pushed_records[2] = {0, 0};
     // multi-genome indexes: the LDS window (difference array + Level 1's arrays) sits on the genome the sample looks like
     DevBuf<unsigned int> win_votes;         // [n_files]
-    DevBuf<uint32_t> win_sel;               // {win_file, win_lo} of the current sample, chosen on the device
-    uint32_t win_lo = 0;
-    int win_file = 0;
+    DevBuf<uint32_t> win_sel;               // {window's genome file, window's first cell} of the current sample, chosen on the device
     bool win_chosen = false;                // for the current sample
-    bool plane_stale[2] = {true, true};   // the mate's counter plane still holds an earlier sample (zeroed at its first push / at finalize)
 
     // after the pileup (bk_sample_call): per-engine scratch and results
     DevBuf<double> call_noise, noise_maf, noise_tbl, noise_sums;   // (get_baseline_noise, the walk taken apart: CallArgs)
