@@ -53,7 +53,7 @@ class BuiltIndex(C.Structure):  # bk_built_index
 # every symbol include/bronko_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_error", "bk_params_default", "bk_engine_create", "bk_engine_destroy", "bk_engine_fork", "bk_engine_fork_params", "bk_engine_get_stream",
            "bk_engine_set_stream", "bk_total_cells", "bk_n_files", "bk_n_slots", "bk_counter_len", "bk_can_shard", "bk_sample_begin",
-           "bk_push_reads_packed", "bk_push_reads_packed_device", "bk_push_reads_ascii", "bk_push_reads_ascii_device", "bk_counters_device_ptr", "bk_sample_finalize",
+           "bk_push_reads_packed", "bk_push_reads_packed_device", "bk_push_reads_ascii", "bk_push_reads_ascii_device", "bk_push_reads_ascii_qual", "bk_push_reads_ascii_qual_device", "bk_counters_device_ptr", "bk_sample_finalize",
            "bk_sample_finalize_shard", "bk_shard_measure", "bk_shard_transport", "bk_shard_received", "bk_transport_overflow", "bk_shard_sums_device_ptr", "bk_sample_merge_shards", "bk_kmer_table_partition", "bk_kmer_table_replace",
            "bk_kmer_dump_enable", "bk_kmer_dump_size", "bk_kmer_dump_download",
            "bk_pileup_device_ptr", "bk_sample_download", "bk_sample_finish", "bk_pack_reads", "bk_pack_reads_flat",
@@ -111,6 +111,10 @@ def load(testing=None):
     L.bk_push_reads_packed_device.argtypes = [vp, C.c_int, vp, u32, vp, u64]
     L.bk_push_reads_ascii.restype = C.c_int
     L.bk_push_reads_ascii.argtypes = [vp, C.c_int, vp, vp, u64]
+    L.bk_push_reads_ascii_qual.restype = C.c_int
+    L.bk_push_reads_ascii_qual.argtypes = [vp, C.c_int, vp, vp, vp, u64, C.c_int]
+    L.bk_push_reads_ascii_qual_device.restype = C.c_int
+    L.bk_push_reads_ascii_qual_device.argtypes = [vp, C.c_int, vp, vp, vp, u64, u64, u32, C.c_int]
     L.bk_counters_device_ptr.restype = C.c_int
     L.bk_counters_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.bk_sample_finalize.restype = C.c_int

@@ -226,7 +226,7 @@ void bk_engine_destroy(bk_engine* e) {
     for (auto& s : e->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto ev : e->free_events) (void)hipEventDestroy(ev);
     for (auto& sl : e->slots) {
-        if (sl.h_bases) (void)hipHostFree(sl.h_bases); if (sl.h_off) (void)hipHostFree(sl.h_off);
+        if (sl.h_bases) (void)hipHostFree(sl.h_bases); if (sl.h_off) (void)hipHostFree(sl.h_off); if (sl.h_quals) (void)hipHostFree(sl.h_quals);
         if (sl.uploaded) (void)hipEventDestroy(sl.uploaded); if (sl.done) (void)hipEventDestroy(sl.done);
     }
     for (auto& st : e->stage) { if (st.done) (void)hipEventDestroy(st.done); if (st.h) (void)hipHostFree(st.h); }
@@ -631,16 +631,21 @@ struct PackGeom {
           cap(n_reads + total / (uint64_t)k + total / (std::min<uint64_t>((uint64_t)stride * 16, 65535) - (uint64_t)(k - 1)) + 16) {}
 };
 // the packer (records pushed: tallied on the device) into the slot's record buffers, then the push of those records
+// (q: the quality lines and threshold of a bk_push_reads_ascii_qual* batch, or null)
 static int pack_and_push(bk_engine* e, int mate, bk_engine::IngestSlot& sl, const uint8_t* bases, uint32_t shift, const unsigned long long* offsets,
-                         uint64_t n_reads, uint64_t total, PackGeom g) {
+                         uint64_t n_reads, uint64_t total, PackGeom g, const bk::QualArgs* q = nullptr) {
     bk::PackArgs pa{};
     pa.shift = shift; pa.bases = bases; pa.offsets = offsets; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = g.stride;
     pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = g.cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
-    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream); }
+    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream, q); }
     return push_device(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, g.cap, sl.d_nrec.p, total);   // (a batch holds fewer k-mers than bases)
 }
 
-int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads) {
+// --min-base-qual: a quality byte below '!' + min_qual (Phred+33) makes its base an N; 0 is off
+static constexpr int kMaxMinQual = 93;   // ('!' + 93 = '~', the last printable quality symbol)
+
+// bk_push_reads_ascii and bk_push_reads_ascii_qual (qual: null, or the quality lines at the same offsets; thr = '!' + min_qual)
+static int push_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint8_t* qual, const uint64_t* offsets, uint64_t n_reads, uint32_t thr) {
     const bool too_large = buf && offsets && n_reads && offsets[n_reads] - offsets[0] >= (1ull << 32);
     if (int rc = push_checks(e, mate, n_reads, buf && offsets, "bad read batch", too_large); rc != kPush) return rc;
     const uint64_t base0 = offsets[0], total = offsets[n_reads] - base0;
@@ -661,7 +666,13 @@ int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64
         sl.h_off_cap = n_reads + n_reads / 4 + 1024;
         BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_off), sl.h_off_cap * sizeof(unsigned long long), hipHostMallocDefault));
     }
+    if (qual && sl.h_quals_cap < total + 1) {
+        if (sl.h_quals) BK_HIP(hipHostFree(sl.h_quals));
+        sl.h_quals_cap = total + total / 4 + 4096;
+        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_quals), sl.h_quals_cap, hipHostMallocDefault));
+    }
     std::memcpy(sl.h_bases, buf + base0, total);
+    if (qual) std::memcpy(sl.h_quals, qual + base0, total);
     uint64_t longest = 0;
     for (uint64_t i = 0; i <= n_reads; i++) {
         sl.h_off[i] = offsets[i] - base0;
@@ -670,6 +681,7 @@ int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64
     const PackGeom g(e->ix->k, n_reads, total, longest);
 
     if (sl.d_bases.n < total + 1) BK_HIP(sl.d_bases.alloc(total + total / 4 + 4096));
+    if (qual && sl.d_quals.n < total + 1) BK_HIP(sl.d_quals.alloc(total + total / 4 + 4096));
     if (sl.d_off.n < n_reads + 1) BK_HIP(sl.d_off.alloc(n_reads + n_reads / 4 + 1024));
     if (sl.d_words.n < g.cap * g.stride) BK_HIP(sl.d_words.alloc(g.cap * g.stride + g.cap * g.stride / 4));
     if (sl.d_lens.n < g.cap) BK_HIP(sl.d_lens.alloc(g.cap + g.cap / 4));
@@ -677,17 +689,35 @@ int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64
     if (sl.d_work.n < n_reads) BK_HIP(sl.d_work.alloc(n_reads + n_reads / 4 + 1024));
 
     BK_HIP(hipMemcpyAsync(sl.d_bases.p, sl.h_bases, total, hipMemcpyHostToDevice, e->copy_stream));
+    if (qual) BK_HIP(hipMemcpyAsync(sl.d_quals.p, sl.h_quals, total, hipMemcpyHostToDevice, e->copy_stream));
     BK_HIP(hipMemcpyAsync(sl.d_off.p, sl.h_off, (n_reads + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, e->copy_stream));
     BK_HIP(hipEventRecord(sl.uploaded, e->copy_stream));
     BK_HIP(hipStreamWaitEvent(e->stream, sl.uploaded, 0));
-    if (int rc = pack_and_push(e, mate, sl, sl.d_bases.p, 0, sl.d_off.p, n_reads, total, g)) return rc;
+    const bk::QualArgs q{sl.d_quals.p, 0u, thr};
+    if (int rc = pack_and_push(e, mate, sl, sl.d_bases.p, 0, sl.d_off.p, n_reads, total, g, qual ? &q : nullptr)) return rc;
     BK_HIP(hipEventRecord(sl.done, e->stream));
     sl.busy = true;
     return BK_OK;
 }
 
-int bk_push_reads_ascii_device(bk_engine* e, int mate, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t total_bases,
-                               uint32_t longest_read) {
+int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads) {
+    return push_ascii(e, mate, buf, nullptr, offsets, n_reads, 0u);
+}
+
+int bk_push_reads_ascii_qual(bk_engine* e, int mate, const uint8_t* buf, const uint8_t* qual, const uint64_t* offsets, uint64_t n_reads, int min_qual) {
+    if (min_qual < 0 || min_qual > kMaxMinQual) return fail(BK_ERR_INVALID, "min_qual must be between 0 and %d", kMaxMinQual);
+    if (min_qual == 0) return bk_push_reads_ascii(e, mate, buf, offsets, n_reads);
+    if (!qual && e && e->in_sample && mate >= 0 && mate <= 1 && n_reads) return fail(BK_ERR_INVALID, "bad read batch: no quality lines");
+    return push_ascii(e, mate, buf, qual, offsets, n_reads, (uint32_t)('!' + min_qual));
+}
+
+// sequence lines (d_bases) or quality lines (d_quals) from a pointer of any alignment: the packer stages them with 16-byte loads
+// from a 16-byte boundary, so the pointer is rounded down and the offsets carry the difference (a device allocation starts on a
+// 256-byte boundary, so the bytes in front belong to the same allocation)
+static uint32_t align_shift(const void* p) { return (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u); }
+
+static int push_ascii_device(bk_engine* e, int mate, const void* d_bases, const void* d_quals, const void* d_offsets, uint64_t n_reads,
+                             uint64_t total_bases, uint32_t longest_read, uint32_t thr) {
     if (int rc = push_checks(e, mate, n_reads, d_bases && d_offsets, "bad read batch", total_bases >= (1ull << 32)); rc != kPush) return rc;
     // (everything is ordered by the engine's stream: the records of the previous batch were consumed by its scan before this
     // batch's packer starts, so one set of record buffers does)
@@ -700,12 +730,23 @@ int bk_push_reads_ascii_device(bk_engine* e, int mate, const void* d_bases, cons
         BK_HIP(sl.d_work.alloc(n_reads + n_reads / 4 + 1024));
     }
     if (!sl.d_nrec.p) BK_HIP(sl.d_nrec.alloc(4));
-    // the packer stages the lines with 16-byte loads from a 16-byte boundary: a pointer into the middle of an allocation (any
-    // alignment) is rounded down and the offsets carry the difference (a device allocation starts on a 256-byte boundary, so the
-    // bytes in front belong to the same allocation)
-    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(d_bases) & 15u);
+    const uint32_t shift = align_shift(d_bases);
+    const bk::QualArgs q{static_cast<const uint8_t*>(d_quals) - align_shift(d_quals), align_shift(d_quals), thr};
     return pack_and_push(e, mate, sl, static_cast<const uint8_t*>(d_bases) - shift, shift, static_cast<const unsigned long long*>(d_offsets), n_reads,
-                         total_bases, g);
+                         total_bases, g, d_quals ? &q : nullptr);
+}
+
+int bk_push_reads_ascii_device(bk_engine* e, int mate, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t total_bases,
+                               uint32_t longest_read) {
+    return push_ascii_device(e, mate, d_bases, nullptr, d_offsets, n_reads, total_bases, longest_read, 0u);
+}
+
+int bk_push_reads_ascii_qual_device(bk_engine* e, int mate, const void* d_bases, const void* d_quals, const void* d_offsets, uint64_t n_reads,
+                                    uint64_t total_bases, uint32_t longest_read, int min_qual) {
+    if (min_qual < 0 || min_qual > kMaxMinQual) return fail(BK_ERR_INVALID, "min_qual must be between 0 and %d", kMaxMinQual);
+    if (min_qual == 0) return bk_push_reads_ascii_device(e, mate, d_bases, d_offsets, n_reads, total_bases, longest_read);
+    if (!d_quals && e && e->in_sample && mate >= 0 && mate <= 1 && n_reads) return fail(BK_ERR_INVALID, "bad read batch: no quality lines");
+    return push_ascii_device(e, mate, d_bases, d_quals, d_offsets, n_reads, total_bases, longest_read, (uint32_t)('!' + min_qual));
 }
 
 int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, uint64_t n) {

@@ -323,6 +323,8 @@ struct bk_engine {
         uint8_t* h_bases = nullptr; size_t h_bases_cap = 0;
         unsigned long long* h_off = nullptr; size_t h_off_cap = 0;
         DevBuf<uint8_t> d_bases;
+        uint8_t* h_quals = nullptr; size_t h_quals_cap = 0;   // bk_push_reads_ascii_qual: the quality lines (first use allocates)
+        DevBuf<uint8_t> d_quals;
         DevBuf<unsigned long long> d_off, d_nrec;
         DevBuf<uint32_t> d_work;           // pack_words_kernel's work list
         DevBuf<uint32_t> d_words;

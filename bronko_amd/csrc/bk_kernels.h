@@ -221,7 +221,15 @@ struct PackArgs {
     unsigned long long* n_real;     // the tally of records that hold a run (set by the launcher: its `tally` argument)
     uint32_t* work;                 // [n_reads] scratch: the reads that are not one clean run that fits a record (or null: no word-per-thread kernel)
 };
-void launch_pack_reads(const PackArgs& a, unsigned long long* tally, hipStream_t stream);   // tally: the sample's count of records that hold a run (+= this batch's)
+// --min-base-qual: the reads' quality lines, same offsets as the sequence lines (byte i of line r at quals + shift + offsets[r] + i;
+// quals 16-byte aligned, like PackArgs::bases); a letter whose quality byte is below thr ('!' + Q) splits the read as an N does
+struct QualArgs {
+    const uint8_t* quals;
+    uint32_t shift;
+    uint32_t thr;                   // 34..126
+};
+// tally: the sample's count of records that hold a run (+= this batch's); q: null, or the quality-aware twins of the packer
+void launch_pack_reads(const PackArgs& a, unsigned long long* tally, hipStream_t stream, const QualArgs* q = nullptr);
 // votes[f] += number of the first records' middle k-mers that occur in genome file f (which genome does the sample look like?)
 void launch_pick_window(const ScanArgs& a, uint64_t n_probe, unsigned int* votes, const uint32_t* file_cell_lo, int forced, uint32_t* win,
                         hipStream_t stream);

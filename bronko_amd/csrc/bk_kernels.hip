@@ -110,21 +110,25 @@ __device__ __forceinline__ int acgt_code(unsigned char c) {
     }
 }
 
-// One read, byte by byte: its runs of letters as records appended behind the n_reads slots (a.n_records[0]); returns how many.
-__device__ __forceinline__ unsigned long long pack_read_slow(const PackArgs& a, uint64_t r) {
+// One read, byte by byte: its runs of letters as records in the slots next_slot() hands out (a slot >= a.cap is not written);
+// returns how many were written.  kQual (the --min-base-qual twin): a letter whose quality byte is below q.thr splits the read as
+// an N does.
+template <bool kQual, typename NextSlot>
+__device__ __forceinline__ unsigned long long pack_runs(const PackArgs& a, const QualArgs& q, uint64_t r, NextSlot&& next_slot) {
     const uint64_t maxb = min((uint64_t)a.stride_words * 16, (uint64_t)65535);
     const uint64_t o0 = a.offsets[r], len = a.offsets[r + 1] - o0;
     const uint8_t* s = a.bases + a.shift + o0;
+    const uint8_t* qs = kQual ? q.quals + q.shift + o0 : nullptr;
     unsigned long long real = 0;
     uint64_t start = 0;
     for (uint64_t p = 0; p <= len; ++p) {
-        if (p < len && acgt_code(s[p]) >= 0) continue;
+        if (p < len && acgt_code(s[p]) >= 0 && (!kQual || qs[p] >= q.thr)) continue;
         const uint64_t run = p - start;            // maximal ACGT run [start, p)
         if (run >= (uint64_t)a.k) {
             uint64_t pos = 0;
             for (;;) {
                 const uint64_t take = min(maxb, run - pos);
-                const unsigned long long rec = atomicAdd(a.n_records, 1ull);
+                const unsigned long long rec = next_slot();
                 if (rec < a.cap) {
                     uint32_t* w = a.words + rec * a.stride_words;
                     uint32_t acc = 0;
@@ -145,6 +149,11 @@ __device__ __forceinline__ unsigned long long pack_read_slow(const PackArgs& a, 
     }
     return real;
 }
+// ... appended behind the n_reads slots through the device counter (a.n_records[0])
+template <bool kQual>
+__device__ __forceinline__ unsigned long long pack_read_slow(const PackArgs& a, const QualArgs& q, uint64_t r) {
+    return pack_runs<kQual>(a, q, r, [&] { return atomicAdd(a.n_records, 1ull); });
+}
 
 constexpr int kPackBlock = 256;
 constexpr uint32_t kPackMaxWords = 16;     // records of up to 256 bases take the word-per-thread kernel (a block holds at least 32 reads)
@@ -154,42 +163,79 @@ constexpr uint32_t kPackLdsBytes = kPackBlock * kPackWpt * 16u + 96u;   // the b
 // 16 letters (four realigned words) -> 16 codes; ok: every one of the first nb is a letter.  What lies behind the nb letters is
 // turned into codes and judged like the rest where it shares four bytes with them, and cut off afterwards: a read flagged for a
 // symbol that is not its own only takes the byte-by-byte kernel, which looks at exactly its letters.
-__device__ __forceinline__ uint32_t pack16(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t nb, bool& ok) {
+// kQual: qx holds the letters' four realigned quality words, thr4 the threshold in every byte; a letter whose quality byte is
+// below it counts as "not a letter".  Per byte, q >= thr is bit 7 of ((q | 0x80) - thr) | q (thr <= 126: no borrow leaves a byte,
+// and a byte of 128 or more is at least thr): four compares in four instructions, no branch.
+template <bool kQual = false>
+__device__ __forceinline__ uint32_t pack16(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t nb, bool& ok,
+                                           const uint32_t* qx = nullptr, uint32_t thr4 = 0u) {
     uint32_t out = 0u;
     const uint32_t x4[4] = {x0, x1, x2, x3};
 #pragma unroll
     for (uint32_t j = 0; j < 4u; ++j) {
         const uint32_t x = x4[j];
         const uint32_t c = ((x >> 1) ^ (x >> 2)) & 0x03030303u;                       // four codes, one per byte
-        ok &= (x & 0xdfdfdfdfu) == __builtin_amdgcn_perm(0x54474341u, 0x54474341u, c) || nb <= 4u * j;   // the letters A C G T the codes stand for
+        bool good = (x & 0xdfdfdfdfu) == __builtin_amdgcn_perm(0x54474341u, 0x54474341u, c);   // the letters A C G T the codes stand for
+        if constexpr (kQual) good = good && ((((qx[j] | 0x80808080u) - thr4) | qx[j]) & 0x80808080u) == 0x80808080u;
+        ok &= good || nb <= 4u * j;
         const uint32_t c2 = c | (c >> 6);
         out |= ((c2 | (c2 >> 12)) & 0xffu) << (8u * j);
     }
     return nb < 16u ? out & ((1u << (2u * nb)) - 1u) : out;
 }
 
-__global__ __launch_bounds__(kPackBlock) void pack_words_kernel(PackArgs a, uint32_t rpb /* reads per block */, uint32_t tpr /* threads per read =
-                                                                ceil(stride_words / kPackWpt) */, uint32_t tpr_recip /* ceil(2^32 / tpr) */) {
-    __shared__ __attribute__((aligned(16))) unsigned char lines[kPackLdsBytes];
-    __shared__ unsigned long long off_s[kPackBlock + 1];       // offsets of the block's reads (rpb + 1 of them)
-    __shared__ unsigned int bad_s[kPackBlock];                 // per read of the block: some word met a symbol that is not a letter
+// (kQual) which of 16 letters (four realigned words, their quality words qx) are ACGT/acgt at or above the threshold: bit i for
+// letter i.  Per byte: d == 0 exactly when bit 7 of ~(((d & 0x7f) + 0x7f) | d) is set; the four bit-7 flags of a word are gathered
+// by one multiply (0x204081 moves bits 0, 8, 16, 24 to 21..24 without carries).
+__device__ __forceinline__ uint32_t valid16(const uint32_t* x4, const uint32_t* qx, uint32_t thr4) {
+    uint32_t v = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t x = x4[j];
+        const uint32_t c = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
+        const uint32_t d = (x & 0xdfdfdfdfu) ^ __builtin_amdgcn_perm(0x54474341u, 0x54474341u, c);
+        const uint32_t eq = ~(((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u;
+        const uint32_t ge = (((qx[j] | 0x80808080u) - thr4) | qx[j]) & 0x80808080u;
+        v |= ((((eq & ge) >> 7) * 0x00204081u) >> 21 & 0xfu) << (4u * j);
+    }
+    return v;
+}
+
+// The body of pack_words_kernel and of its quality-aware twin pack_words_qual_kernel (kQual: the block's quality bytes are staged
+// in qlines next to its letters, with the same 16-byte loads from their own 16-byte boundary -- the qualities are an allocation
+// of their own, with a shift of their own -- and realigned the same way; a letter below the threshold flags its read like an N).
+// kQual: blk_s[3] -- the block's appended records, the reads that are not one record, the block's first appended slot; vm_s[t],
+// pw_s[2t, 2t + 1] -- thread t's 32 letters: which are valid (bit i: letter i), their codes
+template <bool kQual>
+__device__ __forceinline__ void pack_words(const PackArgs& a, const QualArgs& qa, uint32_t rpb, uint32_t tpr, uint32_t tpr_recip,
+                                           unsigned char* lines, unsigned char* qlines, unsigned long long* off_s, unsigned int* bad_s,
+                                           unsigned long long* blk_s, uint32_t* vm_s, uint32_t* pw_s) {
     const uint32_t sw = a.stride_words;
     const uint64_t r0 = (uint64_t)blockIdx.x * rpb, r1 = min(r0 + (uint64_t)rpb, a.n_reads);
     const uint32_t nr = (uint32_t)(r1 - r0);
     // nr + 1 offsets: with records of one or two words a full block holds 256 reads, one offset more than it has threads
     for (uint32_t i = threadIdx.x; i <= nr; i += kPackBlock) off_s[i] = a.offsets[r0 + i] + a.shift;
     if (threadIdx.x < rpb) bad_s[threadIdx.x] = 0u;
+    if (kQual && threadIdx.x < 3u) blk_s[threadIdx.x] = 0ull;
     __syncthreads();
     const uint64_t b0 = off_s[0], b1 = off_s[nr], end = a.offsets[a.n_reads] + a.shift;
     const uint64_t a0 = b0 & ~15ull;                       // the block's lines from a 16-byte boundary (a.bases is 16-byte aligned)
     const uint64_t span = b1 - a0;                         // bytes of the block's lines from there
-    const bool fits = span + 48u <= kPackLdsBytes;         // (reads no longer than their records: always; guards a malformed batch)
+    // (kQual) the same for the quality lines: byte i of a line lies at qa.quals + qa.shift + offsets[r] + i
+    const uint64_t qd = kQual ? (uint64_t)qa.shift - (uint64_t)a.shift : 0ull;   // staged line offset -> quality offset (mod 2^64)
+    const uint64_t qa0 = kQual ? (b0 + qd) & ~15ull : 0ull, qspan = kQual ? b1 + qd - qa0 : 0ull, qend = kQual ? end + qd : 0ull;
+    const bool fits = (kQual ? max(span, qspan) : span) + 48u <= kPackLdsBytes;   // (reads no longer than their records: always; guards a malformed batch)
     if (fits) {
         // whole 16-byte units that lie inside the batch (two more than the lines take: the last read's last words are judged with
         // what follows them), then the batch's last few bytes one by one
         const uint64_t n16 = (span + 15) / 16 + 2, full16 = (end - a0) / 16;
         for (uint64_t i = threadIdx.x; i < min(n16, full16); i += kPackBlock) reinterpret_cast<uint4*>(lines)[i] = reinterpret_cast<const uint4*>(a.bases + a0)[i];
         if (n16 > full16) for (uint64_t i = full16 * 16 + threadIdx.x; i < min(end - a0, n16 * 16); i += kPackBlock) lines[i] = a.bases[a0 + i];
+        if constexpr (kQual) {
+            const uint64_t m16 = (qspan + 15) / 16 + 2, qfull16 = (qend - qa0) / 16;
+            for (uint64_t i = threadIdx.x; i < min(m16, qfull16); i += kPackBlock) reinterpret_cast<uint4*>(qlines)[i] = reinterpret_cast<const uint4*>(qa.quals + qa0)[i];
+            if (m16 > qfull16) for (uint64_t i = qfull16 * 16 + threadIdx.x; i < min(qend - qa0, m16 * 16); i += kPackBlock) qlines[i] = qa.quals[qa0 + i];
+        }
     }
     __syncthreads();
     const uint32_t t = threadIdx.x;
@@ -201,6 +247,7 @@ __global__ __launch_bounds__(kPackBlock) void pack_words_kernel(PackArgs a, uint
     const uint32_t len = simple ? (uint32_t)len64 : 0u;
     uint32_t out[kPackWpt];
     bool ok = true;
+    uint32_t vm = 0u;   // (kQual) which of the thread's 32 letters are valid
     {
         const uint32_t p = (uint32_t)(o0 - a0) + 16u * q0;  // where the thread's letters start in the staged lines
         const uint32_t* wsrc = reinterpret_cast<const uint32_t*>(lines) + ((simple ? p : 0u) >> 2);
@@ -208,23 +255,111 @@ __global__ __launch_bounds__(kPackBlock) void pack_words_kernel(PackArgs a, uint
         uint32_t w[4 * kPackWpt + 1];
 #pragma unroll
         for (uint32_t i = 0; i <= 4u * kPackWpt; ++i) w[i] = wsrc[i];   // (whatever lies behind the letters is cut off below)
+        uint32_t qw[kQual ? 4 * kPackWpt + 1 : 1];
+        uint32_t qsh = 0u, thr4 = 0u;
+        if constexpr (kQual) {
+            const uint32_t pq = (uint32_t)(o0 + qd - qa0) + 16u * q0;   // ... and their quality bytes in the staged quality lines
+            const uint32_t* qsrc = reinterpret_cast<const uint32_t*>(qlines) + ((simple ? pq : 0u) >> 2);
+            qsh = pq & 3u;
+            thr4 = qa.thr * 0x01010101u;
+#pragma unroll
+            for (uint32_t i = 0; i <= 4u * kPackWpt; ++i) qw[i] = qsrc[i];
+        }
 #pragma unroll
         for (uint32_t u = 0; u < kPackWpt; ++u) {
             const uint32_t at = 16u * (q0 + u);
             const uint32_t nb = len > at ? min(len - at, 16u) : 0u;   // letters of this word
-            out[u] = pack16(__builtin_amdgcn_alignbyte(w[4 * u + 1], w[4 * u], sh), __builtin_amdgcn_alignbyte(w[4 * u + 2], w[4 * u + 1], sh),
-                            __builtin_amdgcn_alignbyte(w[4 * u + 3], w[4 * u + 2], sh), __builtin_amdgcn_alignbyte(w[4 * u + 4], w[4 * u + 3], sh), nb, ok);
+            if constexpr (kQual) {
+                const uint32_t qx[4] = {__builtin_amdgcn_alignbyte(qw[4 * u + 1], qw[4 * u], qsh), __builtin_amdgcn_alignbyte(qw[4 * u + 2], qw[4 * u + 1], qsh),
+                                        __builtin_amdgcn_alignbyte(qw[4 * u + 3], qw[4 * u + 2], qsh), __builtin_amdgcn_alignbyte(qw[4 * u + 4], qw[4 * u + 3], qsh)};
+                const uint32_t x[4] = {__builtin_amdgcn_alignbyte(w[4 * u + 1], w[4 * u], sh), __builtin_amdgcn_alignbyte(w[4 * u + 2], w[4 * u + 1], sh),
+                                       __builtin_amdgcn_alignbyte(w[4 * u + 3], w[4 * u + 2], sh), __builtin_amdgcn_alignbyte(w[4 * u + 4], w[4 * u + 3], sh)};
+                out[u] = pack16<true>(x[0], x[1], x[2], x[3], nb, ok, qx, thr4);
+                vm |= (valid16(x, qx, thr4) & (nb >= 16u ? 0xffffu : (1u << nb) - 1u)) << (16u * u);
+            } else {
+                out[u] = pack16(__builtin_amdgcn_alignbyte(w[4 * u + 1], w[4 * u], sh), __builtin_amdgcn_alignbyte(w[4 * u + 2], w[4 * u + 1], sh),
+                                __builtin_amdgcn_alignbyte(w[4 * u + 3], w[4 * u + 2], sh), __builtin_amdgcn_alignbyte(w[4 * u + 4], w[4 * u + 3], sh), nb, ok);
+            }
             if (nb == 0u) out[u] = 0u;
         }
     }
     if (mine && !ok) atomicOr(&bad_s[rl], 1u);
+    if constexpr (kQual) {
+        vm_s[threadIdx.x] = vm;
+#pragma unroll
+        for (uint32_t u = 0; u < kPackWpt; ++u) pw_s[kPackWpt * threadIdx.x + u] = out[u];
+    }
     if (mine) {
         uint32_t* dst = a.words + (r0 + rl) * sw + q0;     // (a slot that stays empty holds whatever: its length says 0)
 #pragma unroll
         for (uint32_t u = 0; u < kPackWpt; ++u) if (q0 + u < sw) dst[u] = out[u];
     }
     __syncthreads();
-    if (mine && q0 == 0u) {
+    if constexpr (kQual) {
+        // With masking most reads have a masked base (any base below Q 20 in a 150-base read), and taking them byte by byte as
+        // pack_words_kernel takes a read with an N ran 4.2 ms per million reads when a quarter had one.  A read the block staged
+        // (simple) is taken apart from the validity bits and codes the threads left in LDS: its runs of k or more valid letters
+        // (a run of a read no longer than its record fits one record) are cut from the codes, no byte loop.  The block counts
+        // its records first, reserves them with one atomic and writes them into its own range of slots.  Anything else (a
+        // malformed batch) goes byte by byte.
+        const bool head = mine && q0 == 0u, good = head && simple && !bad_s[rl];
+        const bool bytewise = head && !good && !simple && len64 >= (uint64_t)a.k;
+        if (head) a.lens[r0 + rl] = good ? (uint16_t)len : (uint16_t)0;
+        const uint32_t* vmr = vm_s + rl * tpr;          // the read's validity bits, 32 per thread
+        const uint32_t* pwr = pw_s + kPackWpt * rl * tpr;   // ... and its 2-bit codes, 16 per word
+        auto for_runs = [&](auto&& f) {                 // f(s, e): every maximal run of valid letters [s, e) with e - s >= k
+            uint32_t p = 0u;
+            while (p < len) {
+                const uint32_t c = vmr[p >> 5] >> (p & 31u);
+                if (c == 0u) { p = (p | 31u) + 1u; continue; }
+                p += __builtin_ctz(c);
+                if (p >= len) break;
+                const uint32_t s0 = p;
+                for (;;) {   // to the run's end, chunk by chunk
+                    const uint32_t rem = 32u - (p & 31u), z = ~(vmr[p >> 5] >> (p & 31u));
+                    const uint32_t n1 = z ? min((uint32_t)__builtin_ctz(z), rem) : rem;
+                    p += n1;
+                    if (n1 < rem || p >= len) break;
+                }
+                if (p - s0 >= (uint32_t)a.k) f(s0, p);
+            }
+        };
+        unsigned long long cnt = 0ull, local = 0ull;
+        if (head && !good && simple) for_runs([&](uint32_t, uint32_t) { ++cnt; });
+        if (cnt) local = atomicAdd(&blk_s[0], cnt);
+        if (head && !good && !bytewise) atomicAdd(&blk_s[1], 1ull);
+        if (bytewise) atomicAdd(a.n_real, pack_read_slow<true>(a, qa, r0 + rl) - 1ull);
+        __syncthreads();
+        if (threadIdx.x == 0 && blk_s[1]) {
+            const unsigned long long base = blk_s[0] ? atomicAdd(a.n_records, blk_s[0]) : 0ull;
+            const unsigned long long kept = base >= a.cap ? 0ull : min(blk_s[0], a.cap - base);   // (slots past the end are dropped)
+            blk_s[2] = base;
+            atomicAdd(a.n_real, kept - blk_s[1]);   // (the launcher counted every read as a record that holds a run)
+        }
+        __syncthreads();
+        if (cnt) {
+            unsigned long long slot = blk_s[2] + local;
+            const uint32_t nw = (len + 15u) >> 4;
+            for_runs([&](uint32_t s0, uint32_t e) {
+                const unsigned long long rec = slot++;
+                if (rec >= a.cap) return;
+                uint32_t* w = a.words + rec * sw;
+                const uint32_t take = e - s0;
+                for (uint32_t j = 0; j < sw; ++j) {
+                    uint32_t x = 0u;
+                    if (16u * j < take) {
+                        const uint32_t at = s0 + 16u * j, i = at >> 4, b = 2u * (at & 15u);
+                        const uint32_t lo = pwr[i], hi = i + 1u < nw ? pwr[i + 1u] : 0u;
+                        x = b ? (lo >> b) | (hi << (32u - b)) : lo;
+                        const uint32_t left = take - 16u * j;
+                        if (left < 16u) x &= (1u << (2u * left)) - 1u;
+                    }
+                    w[j] = x;
+                }
+                a.lens[rec] = (uint16_t)take;
+            });
+        }
+    } else if (mine && q0 == 0u) {
         const bool good = simple && !bad_s[rl];
         a.lens[r0 + rl] = good ? (uint16_t)len : (uint16_t)0;
         if (!good) {
@@ -232,20 +367,42 @@ __global__ __launch_bounds__(kPackBlock) void pack_words_kernel(PackArgs a, uint
             // tally per block was 40,000 additions to one address, 0.5 ms per million reads)
             // anything that may still hold a run of k letters: byte by byte, by this thread, here (a kernel of its own behind this
             // one -- a work list, a launch whose grid found it empty on the benchmark -- was 4.6 us of K0's 49)
-            const unsigned long long real = len64 >= (uint64_t)a.k ? pack_read_slow(a, r0 + rl) : 0ull;
+            const unsigned long long real = len64 >= (uint64_t)a.k ? pack_read_slow<kQual>(a, qa, r0 + rl) : 0ull;
             atomicAdd(a.n_real, real - 1ull);
         }
     }
 }
 
+__global__ __launch_bounds__(kPackBlock) void pack_words_kernel(PackArgs a, uint32_t rpb /* reads per block */, uint32_t tpr /* threads per read =
+                                                                ceil(stride_words / kPackWpt) */, uint32_t tpr_recip /* ceil(2^32 / tpr) */) {
+    __shared__ __attribute__((aligned(16))) unsigned char lines[kPackLdsBytes];
+    __shared__ unsigned long long off_s[kPackBlock + 1];       // offsets of the block's reads (rpb + 1 of them)
+    __shared__ unsigned int bad_s[kPackBlock];                 // per read of the block: some word met a symbol that is not a letter
+    pack_words<false>(a, QualArgs{}, rpb, tpr, tpr_recip, lines, nullptr, off_s, bad_s, nullptr, nullptr, nullptr);
+}
+
+// --min-base-qual: the same with the reads' quality lines (QualArgs); 16.5 KB of LDS a block instead of 8.5
+__global__ __launch_bounds__(kPackBlock) void pack_words_qual_kernel(PackArgs a, QualArgs q, uint32_t rpb, uint32_t tpr, uint32_t tpr_recip) {
+    __shared__ __attribute__((aligned(16))) unsigned char lines[kPackLdsBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char qlines[kPackLdsBytes];
+    __shared__ unsigned long long off_s[kPackBlock + 1];
+    __shared__ unsigned int bad_s[kPackBlock];
+    __shared__ unsigned long long blk_s[3];
+    __shared__ uint32_t vm_s[kPackBlock], pw_s[kPackBlock * kPackWpt];
+    pack_words<true>(a, q, rpb, tpr, tpr_recip, lines, qlines, off_s, bad_s, blk_s, vm_s, pw_s);
+}
+
 // One thread per read (long reads: records of more than kPackMaxWords words): the slot of its index stays empty.
-__global__ __launch_bounds__(kPackBlock) void pack_slow_kernel(PackArgs a) {
+template <bool kQual>
+__device__ __forceinline__ void pack_slow(const PackArgs& a, const QualArgs& q) {
     for (uint64_t r = (uint64_t)blockIdx.x * kPackBlock + threadIdx.x; r < a.n_reads; r += (uint64_t)gridDim.x * kPackBlock) {
         a.lens[r] = 0;   // its records, if any, go behind the n_reads slots
-        const unsigned long long real = pack_read_slow(a, r);
+        const unsigned long long real = pack_read_slow<kQual>(a, q, r);
         if (real) atomicAdd(a.n_real, real);
     }
 }
+__global__ __launch_bounds__(kPackBlock) void pack_slow_kernel(PackArgs a) { pack_slow<false>(a, QualArgs{}); }
+__global__ __launch_bounds__(kPackBlock) void pack_slow_qual_kernel(PackArgs a, QualArgs q) { pack_slow<true>(a, q); }
 
 __global__ void add_u64_kernel(unsigned long long* dst, const unsigned long long* src) { *dst += *src; }
 __global__ void add_const_u64_kernel(unsigned long long* dst, unsigned long long v) { *dst += v; }
@@ -261,7 +418,8 @@ void launch_add_u64(unsigned long long* dst, const unsigned long long* src, hipS
 __global__ void pack_begin_kernel(unsigned long long* dst, unsigned long long v0, unsigned long long* tally, unsigned long long v1) { dst[0] = v0; dst[1] = 0ull; dst[2] = 0ull; *tally += v1; }
 // a.n_records[0] = record slots in use when the kernels end; `tally` (the sample's count of records that hold a run -- what KMC would
 // call its input sequences) grows by this batch's: a launch of its own that added a batch-local count to it afterwards was 4.5 us
-void launch_pack_reads(const PackArgs& a0, unsigned long long* tally, hipStream_t stream) {
+// q: the reads' quality lines and threshold (--min-base-qual: the quality-aware twins), or null
+void launch_pack_reads(const PackArgs& a0, unsigned long long* tally, hipStream_t stream, const QualArgs* q) {
     if (a0.n_reads == 0) return;
     PackArgs a = a0;
     a.n_real = tally;
@@ -271,10 +429,13 @@ void launch_pack_reads(const PackArgs& a0, unsigned long long* tally, hipStream_
     if (by_word) {
         const uint32_t tpr = (a.stride_words + kPackWpt - 1) / kPackWpt, rpb = (uint32_t)kPackBlock / tpr;
         const uint32_t recip = (uint32_t)(((1ull << 32) + tpr - 1) / tpr);
-        hipLaunchKernelGGL(pack_words_kernel, dim3((unsigned)((a.n_reads + rpb - 1) / rpb)), dim3(kPackBlock), 0, stream, a, rpb, tpr, recip);
+        if (q) hipLaunchKernelGGL(pack_words_qual_kernel, dim3((unsigned)((a.n_reads + rpb - 1) / rpb)), dim3(kPackBlock), 0, stream, a, *q, rpb, tpr, recip);
+        else hipLaunchKernelGGL(pack_words_kernel, dim3((unsigned)((a.n_reads + rpb - 1) / rpb)), dim3(kPackBlock), 0, stream, a, rpb, tpr, recip);
     } else {
         a.work = nullptr;   // long reads: every read byte by byte
-        hipLaunchKernelGGL(pack_slow_kernel, dim3((unsigned)std::min<uint64_t>((a.n_reads + kPackBlock - 1) / kPackBlock, 65535)), dim3(kPackBlock), 0, stream, a);
+        const dim3 grid((unsigned)std::min<uint64_t>((a.n_reads + kPackBlock - 1) / kPackBlock, 65535));
+        if (q) hipLaunchKernelGGL(pack_slow_qual_kernel, grid, dim3(kPackBlock), 0, stream, a, *q);
+        else hipLaunchKernelGGL(pack_slow_kernel, grid, dim3(kPackBlock), 0, stream, a);
     }
 }
 

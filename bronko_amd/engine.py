@@ -188,8 +188,9 @@ class Engine:
         assert words.ndim == 2 and words.shape[0] == len(lens)
         _check(self._L.bk_push_reads_packed(self.h, mate, words.ctypes.data, words.shape[1], lens.ctypes.data, len(lens)), self._L)
 
-    def push_reads_ascii(self, mate, reads):
-        """bk_push_reads_ascii: list of ASCII reads, packed on the GPU, asynchronous."""
+    def push_reads_ascii(self, mate, reads, quals=None, min_qual=0):
+        """bk_push_reads_ascii: list of ASCII reads, packed on the GPU, asynchronous.  With quals (one quality line per read, same
+        lengths) and min_qual > 0: bk_push_reads_ascii_qual -- a base whose quality byte is below '!' + min_qual counts as N."""
         reads = [bytes(r) for r in reads]
         if not reads:
             return
@@ -197,12 +198,28 @@ class Engine:
         flat = np.ascontiguousarray(flat) if len(flat) else np.zeros(1, np.uint8)
         off = np.zeros(len(reads) + 1, np.uint64)
         off[1:] = np.cumsum([len(r) for r in reads])
-        _check(self._L.bk_push_reads_ascii(self.h, mate, flat.ctypes.data, off.ctypes.data, len(reads)), self._L)
+        if quals is None and min_qual == 0:
+            _check(self._L.bk_push_reads_ascii(self.h, mate, flat.ctypes.data, off.ctypes.data, len(reads)), self._L)
+            return
+        qflat = None
+        if quals is not None:
+            quals = [bytes(q) for q in quals]
+            if len(quals) != len(reads) or any(len(q) != len(r) for q, r in zip(quals, reads)):
+                raise ValueError("push_reads_ascii: every quality line must be as long as its read")
+            qflat = np.frombuffer(b"".join(quals), np.uint8)
+            qflat = np.ascontiguousarray(qflat) if len(qflat) else np.zeros(1, np.uint8)
+        _check(self._L.bk_push_reads_ascii_qual(self.h, mate, flat.ctypes.data, None if qflat is None else qflat.ctypes.data, off.ctypes.data,
+                                                len(reads), min_qual), self._L)
 
-    def push_reads_ascii_device(self, mate, d_bases_ptr, d_offsets_ptr, n_reads, total_bases, longest_read):
-        """bk_push_reads_ascii_device: sequence lines resident in device memory, packed (K0) and scanned on the engine's stream."""
-        _check(self._L.bk_push_reads_ascii_device(self.h, mate, C.c_void_p(d_bases_ptr), C.c_void_p(d_offsets_ptr), n_reads, total_bases,
-                                                  longest_read), self._L)
+    def push_reads_ascii_device(self, mate, d_bases_ptr, d_offsets_ptr, n_reads, total_bases, longest_read, quals=None, min_qual=0):
+        """bk_push_reads_ascii_device: sequence lines resident in device memory, packed (K0) and scanned on the engine's stream.
+        quals: device pointer of the quality lines (same offsets; bk_push_reads_ascii_qual_device with min_qual)."""
+        if quals is None and min_qual == 0:
+            _check(self._L.bk_push_reads_ascii_device(self.h, mate, C.c_void_p(d_bases_ptr), C.c_void_p(d_offsets_ptr), n_reads, total_bases,
+                                                      longest_read), self._L)
+            return
+        _check(self._L.bk_push_reads_ascii_qual_device(self.h, mate, C.c_void_p(d_bases_ptr), C.c_void_p(quals), C.c_void_p(d_offsets_ptr),
+                                                       n_reads, total_bases, longest_read, min_qual), self._L)
 
     def push_reads_device(self, mate, d_words_ptr, stride_words, d_lens_ptr, n_records):
         _check(self._L.bk_push_reads_packed_device(self.h, mate, C.c_void_p(d_words_ptr), stride_words,

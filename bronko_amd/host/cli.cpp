@@ -98,6 +98,7 @@ struct Args {
     long min_depth = 300;
     long min_variant_depth = 3;
     double noise_multiplier = 1.5;
+    long min_base_qual = 0;         // --min-base-qual: bases below this Phred+33 quality are N before k-mer counting (0: off)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -113,9 +114,11 @@ struct Args {
           "            [--use-full-kmer] [--n-fixed N] [--min-af F] [--no-end-filter] [--no-strand-filter]\n"
           "            [--no-strand-balance-filter] [--balance-ratio F] [--n-per-strand N] [--strand_odds F]\n"
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
-          "            [--alignment] [--keep-kmer-info] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
-          "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n", stderr);
+          "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
+          "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
+          "                    are counted; 0..93, default 0 (off)\n", stderr);
     exit(code);
 }
 
@@ -199,6 +202,12 @@ Args parse_args(int argc, char** argv) {
         else if (opt == "--pileup") a.pileup = true;
         else if (opt == "--alignment") a.alignment = true;
         else if (opt == "--keep-kmer-info") a.keep_kmer_info = true;
+        else if (opt == "--min-base-qual") {   // (any integer here: a value outside 0..93 is refused by check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            a.min_base_qual = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+        }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
     return a;
@@ -295,6 +304,7 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     else if (a.noise_multiplier > 2.0) LOG_WARN(T, "Strand balance ratio is set above 2, may experience a drop in recall (we recommend ~1.5)");
     else if (a.noise_multiplier == 1.0) LOG_WARN(T, "Noise multiplier for variant detection set to 1.0, all variants will pass this filter");
     if (a.first_pairs.size() != a.second_pairs.size()) die(T, "Number of paired end sequences do not match, exiting.");
+    if (a.min_base_qual < 0 || a.min_base_qual > 93) die(T, "Minimum base quality must be between 0 and 93 (Phred+33), got " + std::to_string(a.min_base_qual));
 }
 
 struct Engine {
@@ -312,9 +322,10 @@ void hip_check(int rc, const char* what) {
 // call.rs:301-307); the engine is only ever called from this thread.  Returns reads seen.
 struct FastqBatch {
     std::string buf; std::vector<uint64_t> off{0};   // sequence lines back to back (the line loop: streams, one thread) ...
+    std::string qual;                                // (--min-base-qual) ... and their quality lines, at the same offsets
     PackedBatch packed; bool is_packed = false;      // ... or 2-bit records, parsed and packed on several threads (fastq_pack.hpp)
     bool last = false; std::string error;
-    size_t bytes() const { return is_packed ? packed.bytes() : buf.size(); }
+    size_t bytes() const { return is_packed ? packed.bytes() : buf.size() + qual.size(); }
 };
 // The sequence text that samples read ahead of their turn hold in their queues, all of them together: counted as it is queued
 // (a batch's real bytes, not an estimate from the compressed size: amplicon FASTQ inflates 8-10x), released as lanes consume.
@@ -385,7 +396,7 @@ struct BatchQueue {
             std::unique_lock<std::mutex> lk(m);
             if (!spare.empty()) { b = std::move(spare.back()); spare.pop_back(); }
         }
-        b.buf.clear(); b.off.clear(); b.off.push_back(0); b.packed.clear(); b.is_packed = false; b.last = false; b.error.clear();
+        b.buf.clear(); b.off.clear(); b.off.push_back(0); b.qual.clear(); b.packed.clear(); b.is_packed = false; b.last = false; b.error.clear();
         return b;
     }
 };
@@ -393,6 +404,7 @@ struct BatchQueue {
 unsigned g_inflate_threads = 1;
 unsigned g_ahead_inflate_threads = 1;   // ... for the files that are read ahead of their turn: -t over the files ReadAhead has open at once
 int g_kmer = 21;   // (set by call: the records a reader thread packs drop runs shorter than k)
+int g_min_qual = 0;   // --min-base-qual (set by call): bases below '!' + g_min_qual are N
 void parse_fastq(const std::string& path, BatchQueue& out, unsigned inflate_threads) {
     constexpr uint64_t kBatchReads = 1u << 16;   // (10 MB of bases: the engine pins three staging slots of that size per lane)
     FastqBatch cur;
@@ -402,7 +414,7 @@ void parse_fastq(const std::string& path, BatchQueue& out, unsigned inflate_thre
             // a few MB of text make a piece, pieces are gathered into batches of a quarter of a million records (a scan launch has
             // a fixed cost: small pushes are slow pushes)
             constexpr uint64_t kBatchRecords = 1u << 18;
-            FastqPacker in(path, g_kmer, inflate_threads);
+            FastqPacker in(path, g_kmer, inflate_threads, g_min_qual);
             PackedBatch b;
             cur.is_packed = true;
             while (in.next(b)) {
@@ -421,11 +433,29 @@ void parse_fastq(const std::string& path, BatchQueue& out, unsigned inflate_thre
         } else {
             GzLineReader in(path, inflate_threads);
             uint64_t n = 0;
+            // --min-base-qual: a record's quality line (line 3) goes into the batch too, and the batch ends behind it
+            auto check = [&](uint64_t ln, size_t qn) {
+                const size_t sn = cur.off.back() - cur.off[cur.off.size() - 2];
+                if (qn != sn)
+                    throw std::runtime_error(path + ": record " + std::to_string(ln / 4 + 1) + ": quality line of " + std::to_string(qn) +
+                                             " bytes for a sequence of " + std::to_string(sn) + " (--min-base-qual)");
+            };
             for (uint64_t ln = 0;; ln++) {               // 4-line FASTQ records: @id / sequence / + / quality
-                if ((ln & 3) != 1) { if (!in.skip_next()) break; continue; }
+                if (g_min_qual > 0 && (ln & 3) == 3) {
+                    const size_t q0 = cur.qual.size();
+                    const bool got = in.append_next(cur.qual);   // (none: a record cut short, an empty quality line)
+                    check(ln, cur.qual.size() - q0);
+                    if (!got) break;
+                    if (n % kBatchReads == 0) { out.put(std::move(cur)); cur = out.fresh(); if (out.abandoned.load()) break; }
+                    continue;
+                }
+                if ((ln & 3) != 1) {
+                    if (!in.skip_next()) { if (g_min_qual > 0 && (ln & 3) == 2) check(ln, 0); break; }
+                    continue;
+                }
                 if (!in.append_next(cur.buf)) break;     // (the sequence line goes straight into the batch)
                 cur.off.push_back(cur.buf.size());
-                if (++n % kBatchReads == 0) { out.put(std::move(cur)); cur = out.fresh(); if (out.abandoned.load()) break; }
+                if (++n % kBatchReads == 0 && g_min_qual == 0) { out.put(std::move(cur)); cur = out.fresh(); if (out.abandoned.load()) break; }
             }
         }
     } catch (const std::exception& e) {
@@ -558,6 +588,10 @@ uint64_t push_fastqs(const std::vector<bk_engine*>& engs, const std::vector<std:
                 if (b.packed.n_records)
                     hip_check(bk_push_reads_packed(engs[n_batches++ % engs.size()], (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(), b.packed.n_records), "bk_push_reads_packed");
                 n_reads += b.packed.n_reads;
+            } else if (error.empty() && b.off.size() > 1 && g_min_qual > 0) {
+                hip_check(bk_push_reads_ascii_qual(engs[n_batches++ % engs.size()], (int)m, reinterpret_cast<const uint8_t*>(b.buf.data()),
+                                                   reinterpret_cast<const uint8_t*>(b.qual.data()), b.off.data(), b.off.size() - 1, g_min_qual), "bk_push_reads_ascii_qual");
+                n_reads += b.off.size() - 1;
             } else if (error.empty() && b.off.size() > 1) {
                 hip_check(bk_push_reads_ascii(engs[n_batches++ % engs.size()], (int)m, reinterpret_cast<const uint8_t*>(b.buf.data()), b.off.data(), b.off.size() - 1), "bk_push_reads_ascii");
                 n_reads += b.off.size() - 1;
@@ -713,6 +747,7 @@ int run_call(const Args& a) {
         g_inflate_threads = g_ahead_inflate_threads;
     }
     g_kmer = (int)a.kmer;   // (a database of another k is refused below: the readers may pack before it is read)
+    g_min_qual = (int)a.min_base_qual;
     std::unique_ptr<ReadAhead> ahead;
     if (!getenv("BRONKO_NO_READ_AHEAD")) {
         const uint64_t ram = (uint64_t)sysconf(_SC_PHYS_PAGES) * (uint64_t)sysconf(_SC_PAGE_SIZE);

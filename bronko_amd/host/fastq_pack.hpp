@@ -59,7 +59,10 @@ inline const AcgtLut& acgt_lut() { static const AcgtLut l; return l; }
 // that overlap by k - 1).  A line that is one run and fits a record -- nearly every line -- takes the short way: sixteen table
 // look-ups a word, no branch per symbol (the byte-at-a-time packer of the C ABI made 1 us a read of it: with the text inflated
 // on 32 threads the packing was the slower half).
-inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out) {
+// kQual (--min-base-qual): qual[i] is line i's quality line (same length); a symbol whose quality byte is below thr is an N.
+template <bool kQual>
+inline void pack_lines_t(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out,
+                         const std::vector<const uint8_t*>* qual, uint8_t thr) {
     out.clear();
     out.n_reads = ptr.size();
     uint64_t longest = (uint64_t)k;
@@ -88,6 +91,7 @@ inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector
     };
     for (size_t r = 0; r < ptr.size(); r++) {
         const uint8_t* s = ptr[r];
+        const uint8_t* q = kQual ? (*qual)[r] : nullptr;
         const uint64_t l = len[r];
         if (l >= (uint64_t)k && l <= maxb) {
             // the short way: packed as if it were one run, sixteen symbols a word; "anything else" shows in bit 2 of a code
@@ -99,11 +103,13 @@ inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector
             for (; i + 16 <= l; i += 16, wi++) {
                 uint32_t x = 0, y = 0;
                 for (uint32_t j = 0; j < 16; j++) { const uint32_t c = lut[s[i + j]]; y |= c; x |= (c & 3u) << (2 * j); }
+                if (kQual) for (uint32_t j = 0; j < 16; j++) y |= (uint32_t)(q[i + j] < thr) << 2;   // (a masked symbol: "anything else")
                 w[wi] = x; bad |= y;
             }
             if (i < l) {
                 uint32_t x = 0, y = 0;
                 for (uint32_t j = 0; i + j < l; j++) { const uint32_t c = lut[s[i + j]]; y |= c; x |= (c & 3u) << (2 * j); }
+                if (kQual) for (uint32_t j = 0; i + j < l; j++) y |= (uint32_t)(q[i + j] < thr) << 2;
                 w[wi++] = x; bad |= y;
             }
             if (!(bad & 4u)) {
@@ -115,7 +121,7 @@ inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector
         // the long way: run by run (what the C ABI's packer does)
         uint64_t start = 0;
         for (uint64_t i = 0; i <= l; i++) {
-            if (i == l || lut[s[i]] > 3) {
+            if (i == l || lut[s[i]] > 3 || (kQual && q[i] < thr)) {
                 const uint64_t rl = i - start;
                 if (rl >= (uint64_t)k) {
                     uint64_t pos = 0;
@@ -135,10 +141,26 @@ inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector
     out.lens.resize((size_t)n);
 }
 
+inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out) {
+    pack_lines_t<false>(ptr, len, k, out, nullptr, 0);
+}
+// The same with quality lines: min_qual > 0 packs the lines with every symbol whose quality byte is below '!' + min_qual
+// (Phred+33) replaced by N; 0 ignores `qual`.
+inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out,
+                       const std::vector<const uint8_t*>& qual, int min_qual) {
+    if (min_qual < 0 || min_qual > 93) throw std::invalid_argument("min_qual must be between 0 and 93 (Phred+33)");
+    if (min_qual > 0) pack_lines_t<true>(ptr, len, k, out, &qual, (uint8_t)('!' + min_qual));
+    else pack_lines_t<false>(ptr, len, k, out, nullptr, 0);
+}
+
 class FastqPacker {
 public:
-    // threads: parse / pack threads (and, for gzip input, as many inflate threads again: they take turns)
-    FastqPacker(const std::string& path, int k, unsigned threads) : path_(path), k_(k), threads_(std::max(1u, threads)) {
+    // threads: parse / pack threads (and, for gzip input, as many inflate threads again: they take turns); min_qual > 0
+    // (--min-base-qual): every base whose quality byte is below '!' + min_qual is packed as an N (pack_lines), and a quality line
+    // that is not as long as its sequence line is an error
+    FastqPacker(const std::string& path, int k, unsigned threads, int min_qual = 0)
+        : path_(path), k_(k), threads_(std::max(1u, threads)), min_qual_(min_qual) {
+        if (min_qual < 0 || min_qual > 93) throw std::invalid_argument("min_qual must be between 0 and 93 (Phred+33)");
         struct stat st;
         const bool regular = ::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0;
         if (threads_ > 1 && regular) {
@@ -197,7 +219,8 @@ private:
         size_t n = 0;
         std::vector<uint32_t> nl;           // positions of its '\n'
         uint64_t line_base = 0;             // number of the line that its first '\n' ends
-        std::string head;                   // what the pieces before it hold of that line
+        std::string head;                   // what the pieces before it hold of that line (min_qual > 0: of that line's record, from
+                                            // the record's first line on)
         bool last = false;                  // the text's end: what is left behind the last '\n' is a line too
         PackedBatch out;
         std::string error;
@@ -262,7 +285,8 @@ private:
     // ---- stage B: the piece's sequence lines, packed ----------------------------------------------------------------------
     void stage_b(Job& j) {
         try {
-            if (j.error.empty()) {
+            if (j.error.empty() && min_qual_ > 0) stage_b_records(j);
+            else if (j.error.empty()) {
                 static thread_local std::vector<const uint8_t*> ptr;   // (a worker's own: their memory is used again, piece after piece)
                 static thread_local std::vector<uint64_t> len;
                 ptr.clear(); len.clear();
@@ -294,6 +318,65 @@ private:
         j.piece = pargz::Piece();   // (its buffer goes back to the pool)
         { std::unique_lock<std::mutex> lk(m_); if (spare_nl_.size() < 256) spare_nl_.push_back(std::move(j.nl)); }
         j.done_b.set_value();
+    }
+
+    // ---- stage B with qualities (min_qual > 0): the records whose quality line ends in the piece --------------------------------
+    // A record is lines 4r .. 4r + 3 (@id / sequence / + / quality).  The piece's head holds its first record's lines up to the
+    // piece (sequence(): the carry is the unfinished record); every other record it finishes lies in the piece itself.  The text's
+    // last piece also takes a last record that ends without a '\n' or is cut short (no quality line: an empty one).
+    static const uint8_t* strip_cr(const uint8_t* s, size_t& n) { while (n && s[n - 1] == '\r') n--; return s; }
+    void check_record(uint64_t rec_line, size_t seq_n, size_t qual_n) const {
+        if (seq_n != qual_n)
+            throw std::runtime_error(path_ + ": record " + std::to_string(rec_line / 4 + 1) + ": quality line of " + std::to_string(qual_n) +
+                                     " bytes for a sequence of " + std::to_string(seq_n) + " (--min-base-qual)");
+    }
+    void stage_b_records(Job& j) {
+        static thread_local std::vector<const uint8_t*> ptr, qptr;
+        static thread_local std::vector<uint64_t> len;
+        ptr.clear(); qptr.clear(); len.clear();
+        ptr.reserve(j.nl.size() / 4 + 2); qptr.reserve(j.nl.size() / 4 + 2); len.reserve(j.nl.size() / 4 + 2);
+        const uint64_t L = j.line_base, n = j.nl.size();
+        // a record from its lines (ls[0..m), m <= 4; an absent quality line is an empty one)
+        auto add = [&](uint64_t rec_line, const uint8_t* const* ls, const size_t* ln, size_t m) {
+            if (m < 2) return;   // (no sequence line: nothing to pack, as without qualities)
+            size_t sn = ln[1], qn = m > 3 ? ln[3] : 0;
+            const uint8_t* sq = strip_cr(ls[1], sn);
+            const uint8_t* qu = m > 3 ? strip_cr(ls[3], qn) : nullptr;
+            check_record(rec_line, sn, qn);
+            ptr.push_back(sq); qptr.push_back(qu); len.push_back(sn);
+        };
+        // text -> its first lines (what follows the last '\n' is a line if `open` -- the text was cut at a '\n' -- or not empty)
+        auto split = [](const uint8_t* t, size_t tn, bool open, const uint8_t** ls, size_t* ln) {
+            size_t m = 0, from = 0;
+            for (size_t i = 0; i < tn && m < 4; i++)
+                if (t[i] == '\n') { ls[m] = t + from; ln[m++] = i - from; from = i + 1; }
+            if (m < 4 && (open || from < tn)) { ls[m] = t + from; ln[m++] = tn - from; }
+            return m;
+        };
+        const uint8_t* ls[4]; size_t ln[4];
+        std::string first, tail;
+        uint64_t r = L & ~3ull;   // the first record the piece may finish
+        if (r + 3 < L + n) {      // its quality line ends here: the head and the piece's text up to that '\n'
+            first = j.head;
+            first.append(reinterpret_cast<const char*>(j.d), j.nl[r + 3 - L]);
+            add(r, ls, ln, split(reinterpret_cast<const uint8_t*>(first.data()), first.size(), true, ls, ln));   // (four lines)
+            r += 4;
+            for (; r + 3 < L + n; r += 4) {   // whole in the piece: line x (x > L) is [nl[x - L - 1] + 1, nl[x - L])
+                for (size_t t = 0; t < 4; t++) {
+                    const size_t i = (size_t)(r + t - L), from = j.nl[i - 1] + 1;
+                    ls[t] = j.d + from; ln[t] = j.nl[i] - from;
+                }
+                add(r, ls, ln, 4);
+            }
+        }
+        if (j.last) {   // what is left: the text's last record, unfinished or without its final '\n'
+            const uint8_t* t; size_t tn;
+            if (r == (L & ~3ull)) { tail = j.head; tail.append(reinterpret_cast<const char*>(j.d), j.n); t = reinterpret_cast<const uint8_t*>(tail.data()); tn = tail.size(); }
+            else { const size_t from = j.nl[r - L - 1] + 1; t = j.d + from; tn = j.n - from; }
+            add(r, ls, ln, split(t, tn, false, ls, ln));
+        }
+        { std::unique_lock<std::mutex> lk(m_); if (!spare_.empty()) { j.out = std::move(spare_.back()); spare_.pop_back(); } }
+        pack_lines(ptr, len, k_, j.out, qptr, min_qual_);
     }
 
     // ---- pieces in, jobs out ------------------------------------------------------------------------------------------------
@@ -340,9 +423,15 @@ private:
         std::shared_ptr<Job> held;   // the newest piece: it is sent on once it is known whether it is the text's last
         auto send = [&](std::shared_ptr<Job> j, bool last) {
             j->line_base = lines; j->head = head; j->last = last;
+            const uint64_t before = lines;
             lines += j->nl.size();
-            if (j->nl.empty()) head.append(reinterpret_cast<const char*>(j->d), j->n);
-            else head.assign(reinterpret_cast<const char*>(j->d + j->nl.back() + 1), j->n - j->nl.back() - 1);
+            // the carry: the line in progress, or with qualities the record in progress (from its first line, lines & ~3, on)
+            const uint64_t from_line = min_qual_ > 0 ? lines & ~3ull : lines;
+            if (from_line <= before) head.append(reinterpret_cast<const char*>(j->d), j->n);
+            else {
+                const size_t at = j->nl[from_line - 1 - before] + 1;
+                head.assign(reinterpret_cast<const char*>(j->d + at), j->n - at);
+            }
             Job* jp = j.get();
             {
                 std::unique_lock<std::mutex> lk(m_);
@@ -374,9 +463,26 @@ private:
     bool next_serial(PackedBatch& out) {
         if (serial_end_) return false;
         constexpr uint64_t kBatchReads = 1u << 16;
-        buf_.clear(); off_.assign(1, 0);
-        for (; off_.size() <= kBatchReads;) {
-            if ((serial_line_ & 3u) != 1u) { if (!lines_->skip_next()) { serial_end_ = true; break; } serial_line_++; continue; }
+        const bool qual = min_qual_ > 0;   // (the quality line, line 3 mod 4, goes into qbuf_ at the sequence line's offset)
+        buf_.clear(); off_.assign(1, 0); qbuf_.clear();
+        for (; off_.size() <= kBatchReads || (qual && (serial_line_ & 3u) != 0u);) {   // (with qualities: whole records)
+            const uint64_t at = serial_line_ & 3u;
+            if (at == 3u && qual) {
+                const size_t q0 = qbuf_.size();
+                const bool got = lines_->append_next(qbuf_);   // (none: a record cut short, an empty quality line)
+                check_record(serial_line_ - 3, off_.back() - off_[off_.size() - 2], qbuf_.size() - q0);
+                if (!got) { serial_end_ = true; break; }
+                serial_line_++; continue;
+            }
+            if (at != 1u) {
+                if (!lines_->skip_next()) {
+                    serial_end_ = true;
+                    // (a record cut short after its sequence line has no quality line: an empty one)
+                    if (qual && at == 2u) check_record(serial_line_ - 2, off_.back() - off_[off_.size() - 2], 0);
+                    break;
+                }
+                serial_line_++; continue;
+            }
             if (!lines_->append_next(buf_)) { serial_end_ = true; break; }
             serial_line_++;
             off_.push_back(buf_.size());
@@ -385,13 +491,20 @@ private:
         std::vector<const uint8_t*> ptr(off_.size() - 1);
         std::vector<uint64_t> len(off_.size() - 1);
         for (size_t i = 0; i + 1 < off_.size(); i++) { ptr[i] = reinterpret_cast<const uint8_t*>(buf_.data()) + off_[i]; len[i] = off_[i + 1] - off_[i]; }
-        pack_lines(ptr, len, k_, out);
+        if (qual) {
+            std::vector<const uint8_t*> qptr(off_.size() - 1);
+            for (size_t i = 0; i + 1 < off_.size(); i++) qptr[i] = reinterpret_cast<const uint8_t*>(qbuf_.data()) + off_[i];
+            pack_lines(ptr, len, k_, out, qptr, min_qual_);
+        } else {
+            pack_lines(ptr, len, k_, out);
+        }
         return true;
     }
 
     std::string path_;
     int k_;
     unsigned threads_;
+    int min_qual_;
     std::unique_ptr<ParallelGunzip> gz_;
     std::unique_ptr<GzLineReader> lines_;
     int fd_ = -1;
@@ -407,7 +520,7 @@ private:
     std::thread feeder_, sequencer_;
     bool quit_ = false, feed_done_ = false, seq_done_ = false;
     std::string error_;
-    std::string buf_;
+    std::string buf_, qbuf_;
     std::vector<uint64_t> off_;
     uint64_t serial_line_ = 0;
     bool serial_end_ = false;

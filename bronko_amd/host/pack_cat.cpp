@@ -1,18 +1,30 @@
-// pack_cat -- what fastq_pack.hpp makes of a FASTQ(.gz) file, as text: pack_cat FILE K THREADS [quiet] writes every packed record's bases,
-// one per line, in the order they come, then "reads N records M"; exit code 1 and a message on stderr for a damaged file.
+// pack_cat -- what fastq_pack.hpp makes of a FASTQ(.gz) file, as text: pack_cat FILE K THREADS [quiet] [--min-qual=Q] writes every
+// packed record's bases, one per line, in the order they come, then "reads N records M"; exit code 1 and a message on stderr for a
+// damaged file.  --min-qual=Q: bases whose quality byte is below '!' + Q are N (FastqPacker's min_qual; 0 is off).
 // tests/test_fastq_pack.py compares the parallel reader (THREADS > 1) with the line loop (THREADS = 1).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "fastq_pack.hpp"
 
 int main(int argc, char** argv) {
-    if (argc < 4) { fprintf(stderr, "usage: pack_cat FILE K THREADS\n"); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: pack_cat FILE K THREADS [quiet] [--min-qual=Q]\n"); return 2; }
     const int k = atoi(argv[2]);
     const unsigned threads = (unsigned)atoi(argv[3]);
-    const bool quiet = argc > 4;   // (a fourth argument: only the counts -- timing the reader, not the printing)
+    bool quiet = false;   // (another argument: only the counts -- timing the reader, not the printing)
+    int min_qual = 0;
+    for (int i = 4; i < argc; i++) {
+        if (strncmp(argv[i], "--min-qual=", 11) == 0) {
+            char* end = nullptr;
+            const long v = strtol(argv[i] + 11, &end, 10);
+            if (end == argv[i] + 11 || *end || v < 0 || v > 93) { fprintf(stderr, "pack_cat: --min-qual must be 0..93\n"); return 2; }
+            min_qual = (int)v;
+        }
+        else quiet = true;
+    }
     try {
-        bronko::FastqPacker in(argv[1], k, threads);
+        bronko::FastqPacker in(argv[1], k, threads, min_qual);
         bronko::PackedBatch b;
         uint64_t reads = 0, records = 0;
         std::string line;

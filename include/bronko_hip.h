@@ -169,6 +169,15 @@ int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uin
  * are in flight, so FASTQ parsing overlaps the copy, the packing and the scan.  bk_sample_finish waits for all. */
 int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads);
 
+/* Base-quality masking (`bronko call --min-base-qual`).  `qual` holds the reads' quality lines at the same offsets as `buf`
+ * (Phred+33); a base whose quality byte is below '!' + min_qual is treated as N, so the batch gives exactly the records of the
+ * same call on the sequence lines with those bases replaced by N.  min_qual is 0..93 (BK_ERR_INVALID otherwise); 0 is the
+ * unqualified call (`qual` is not read).  The _device form takes the quality lines in device memory, any alignment. */
+int bk_push_reads_ascii_qual(bk_engine* e, int mate, const uint8_t* buf, const uint8_t* qual, const uint64_t* offsets, uint64_t n_reads,
+                             int min_qual);
+int bk_push_reads_ascii_qual_device(bk_engine* e, int mate, const void* d_bases, const void* d_quals, const void* d_offsets,
+                                    uint64_t n_reads, uint64_t total_bases, uint32_t longest_read, int min_qual);
+
 /* Multi-GPU hook: the only additive quantity is the per-k-mer occurrence counter plane.
  * (Its u64 elements are difference arrays and counters whose sums wrap modulo 2^64 -- opaque to the host, linear.)
  * A host that shards one sample's reads over several GPUs all-reduces (sum, u64) each plane in place between
