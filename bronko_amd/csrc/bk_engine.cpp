@@ -280,6 +280,10 @@ int bk_sample_begin(bk_engine* e) {
         BK_HIP(hipMemsetAsync(e->dump->out.p, 0, e->dump->out.n * sizeof(unsigned long long), e->stream));
         e->dump->upper[0] = e->dump->upper[1] = 0; e->dump->in_sample = true; e->dump->finalized_mates = 0;
     }
+    if (e->primers) {
+        BK_HIP(hipMemsetAsync(e->primers->stats.p, 0, e->primers->stats.n * sizeof(unsigned long long), e->stream));
+        e->primers->in_sample = true;
+    }
     e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
@@ -630,14 +634,33 @@ struct PackGeom {
         : stride((uint32_t)std::min<uint64_t>((std::max<uint64_t>(longest, (uint64_t)k) + 15) / 16, 4095)),
           cap(n_reads + total / (uint64_t)k + total / (std::min<uint64_t>((uint64_t)stride * 16, 65535) - (uint64_t)(k - 1)) + 16) {}
 };
+// bk_primers_set: the primers come off the records that touch a read end (primer_trim_kernel, in place), on the engine stream
+// between the packer or the copy that made the records and everything that reads them
+static void trim_records(bk_engine* e, int mate, uint32_t* d_words, uint32_t stride_words, uint16_t* d_lens, const uint8_t* d_ends, uint64_t n,
+                         const unsigned long long* n_records_dev = nullptr) {
+    bk_engine::Span sp(e, 2);
+    bk::TrimArgs t{};
+    t.words = d_words; t.lens = d_lens; t.ends = d_ends; t.n_records = n; t.n_records_dev = n_records_dev; t.stride_words = stride_words;
+    t.k = e->ix->k; t.table = e->primers->table.p; t.n_primers = e->primers->n; t.max_mismatches = e->primers->max_mismatches;
+    t.stats = e->primers->stats.p + mate * 3; t.n_real = e->kstats.p + mate * 4 + 0;
+    bk::launch_primer_trim(t, e->ix->n_cus, e->stream);
+}
+
 // the packer (records pushed: tallied on the device) into the slot's record buffers, then the push of those records
-// (q: the quality lines and threshold of a bk_push_reads_ascii_qual* batch, or null)
+// (q: the quality lines and threshold of a bk_push_reads_ascii_qual* batch, or null); with primers set the packer also writes the
+// records' end flags and the primers are trimmed in between
 static int pack_and_push(bk_engine* e, int mate, bk_engine::IngestSlot& sl, const uint8_t* bases, uint32_t shift, const unsigned long long* offsets,
                          uint64_t n_reads, uint64_t total, PackGeom g, const bk::QualArgs* q = nullptr) {
     bk::PackArgs pa{};
     pa.shift = shift; pa.bases = bases; pa.offsets = offsets; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = g.stride;
     pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = g.cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
-    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream, q); }
+    uint8_t* ends = nullptr;
+    if (e->primers) {
+        if (sl.d_ends.n < g.cap) { BK_HIP(hipStreamSynchronize(e->stream)); BK_HIP(sl.d_ends.alloc(g.cap + g.cap / 4)); }
+        ends = sl.d_ends.p;
+    }
+    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream, q, ends); }
+    if (ends) trim_records(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, ends, g.cap, sl.d_nrec.p);
     return push_device(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, g.cap, sl.d_nrec.p, total);   // (a batch holds fewer k-mers than bases)
 }
 
@@ -749,13 +772,45 @@ int bk_push_reads_ascii_qual_device(bk_engine* e, int mate, const void* d_bases,
     return push_ascii_device(e, mate, d_bases, d_quals, d_offsets, n_reads, total_bases, longest_read, (uint32_t)('!' + min_qual));
 }
 
-int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, uint64_t n) {
-    if (int rc = packed_checks(e, mate, d_words, stride_words, d_lens, n); rc != kPush) return rc;
-    return push_device(e, mate, static_cast<const uint32_t*>(d_words), stride_words, static_cast<const uint16_t*>(d_lens), n);
+// the packed pushes: `ends` null (the plain calls: refused while primers are set, since those records would go untrimmed) or the
+// records' end flags (read only while primers are set)
+static int no_end_flags(const char* fn) {
+    return fail(BK_ERR_STATE, "%s: primers are set (bk_primers_set) and these records carry no end flags: push them with %s_ends", fn, fn);
 }
 
-int bk_push_reads_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, uint64_t n) {
+static int push_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends, uint64_t n) {
+    if (int rc = packed_checks(e, mate, d_words, stride_words, d_lens, n); rc != kPush) return rc;
+    if (!e->primers) return push_device(e, mate, static_cast<const uint32_t*>(d_words), stride_words, static_cast<const uint16_t*>(d_lens), n);
+    if (!d_ends) return no_end_flags("bk_push_reads_packed_device");
+    // the caller's records are not the engine's to rewrite: they are trimmed in a copy (the buffers of bk_push_reads_ascii_device:
+    // everything that uses them is ordered by the engine's stream)
+    bk_engine::IngestSlot& sl = e->dev_ascii;
+    const size_t nw = (size_t)n * stride_words;
+    if (sl.d_words.n < nw || sl.d_lens.n < n) {
+        BK_HIP(hipStreamSynchronize(e->stream));
+        if (sl.d_words.n < nw) BK_HIP(sl.d_words.alloc(nw + nw / 4));
+        if (sl.d_lens.n < n) BK_HIP(sl.d_lens.alloc(n + n / 4));
+    }
+    BK_HIP(hipMemcpyAsync(sl.d_words.p, d_words, nw * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
+    BK_HIP(hipMemcpyAsync(sl.d_lens.p, d_lens, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToDevice, e->stream));
+    trim_records(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, static_cast<const uint8_t*>(d_ends), n);
+    return push_device(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, n);
+}
+
+int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, uint64_t n) {
+    return push_packed_device(e, mate, d_words, stride_words, d_lens, nullptr, n);
+}
+
+int bk_push_reads_packed_ends_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends,
+                                     uint64_t n) {
+    if (e && e->primers && !d_ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
+    return push_packed_device(e, mate, d_words, stride_words, d_lens, d_ends, n);
+}
+
+static int push_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends, uint64_t n) {
     if (int rc = packed_checks(e, mate, words, stride_words, lens, n); rc != kPush) return rc;
+    if (e->primers && !ends) return no_end_flags("bk_push_reads_packed");
+    if (!e->primers) ends = nullptr;
     const size_t nw = (size_t)n * stride_words;
     bk_engine::StageSlot& sl = e->stage[e->next_stage];
     e->next_stage ^= 1;
@@ -763,28 +818,42 @@ int bk_push_reads_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t
     if (sl.busy) { BK_HIP(hipEventSynchronize(sl.done)); sl.busy = false; }   // the scan that read this slot two pushes ago
     if (sl.words.n < nw) BK_HIP(sl.words.alloc(nw + nw / 4));
     if (sl.lens.n < n) BK_HIP(sl.lens.alloc(n + n / 4));
+    if (ends && sl.ends.n < n) BK_HIP(sl.ends.alloc(n + n / 4));
     {
         // the caller's buffer is free when this call returns: the batch is copied into the slot's pinned host buffer, from where
         // it travels asynchronously (an asynchronous copy straight from pageable memory would still be reading the caller's pages)
-        const size_t bytes_w = nw * sizeof(uint32_t), bytes_l = (size_t)n * sizeof(uint16_t);
-        if (sl.h_cap < bytes_w + bytes_l) {
+        const size_t bytes_w = nw * sizeof(uint32_t), bytes_l = (size_t)n * sizeof(uint16_t), bytes_e = ends ? (size_t)n : 0;
+        if (sl.h_cap < bytes_w + bytes_l + bytes_e) {
             if (sl.h) BK_HIP(hipHostFree(sl.h));
             sl.h = nullptr;
-            sl.h_cap = bytes_w + bytes_l + (bytes_w + bytes_l) / 4;
+            sl.h_cap = bytes_w + bytes_l + bytes_e + (bytes_w + bytes_l + bytes_e) / 4;
             BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h), sl.h_cap, hipHostMallocDefault));
         }
         std::memcpy(sl.h, words, bytes_w);
         std::memcpy(sl.h + bytes_w, lens, bytes_l);
+        if (ends) std::memcpy(sl.h + bytes_w + bytes_l, ends, bytes_e);
         bk_engine::Span sp(e, 2);
         BK_HIP(hipMemcpyAsync(sl.words.p, sl.h, bytes_w, hipMemcpyHostToDevice, e->stream));
         BK_HIP(hipMemcpyAsync(sl.lens.p, sl.h + bytes_w, bytes_l, hipMemcpyHostToDevice, e->stream));
+        if (ends) BK_HIP(hipMemcpyAsync(sl.ends.p, sl.h + bytes_w + bytes_l, bytes_e, hipMemcpyHostToDevice, e->stream));
     }
+    if (ends) trim_records(e, mate, sl.words.p, stride_words, sl.lens.p, sl.ends.p, n);
     int rc = push_device(e, mate, sl.words.p, stride_words, sl.lens.p, n);
     if (rc != BK_OK) return rc;
     BK_HIP(hipEventRecord(sl.done, e->stream));
     sl.busy = true;
     if (test_env("BK_SYNC_PUSH")) BK_HIP(hipStreamSynchronize(e->stream));
     return BK_OK;
+}
+
+int bk_push_reads_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, uint64_t n) {
+    return push_packed(e, mate, words, stride_words, lens, nullptr, n);
+}
+
+int bk_push_reads_packed_ends(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends,
+                              uint64_t n) {
+    if (e && e->primers && !ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
+    return push_packed(e, mate, words, stride_words, lens, ends, n);
 }
 
 int bk_counters_device_ptr(bk_engine* e, int mate, void** d_ptr) {
@@ -1233,6 +1302,55 @@ int bk_sample_finish(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t* r
     return bk_sample_download(e, n_mates, fwd_depth, rev_depth, fwd_nk, rev_nk, stats, present, kmer_stats);
 }
 
+// ---- amplicon primers (bk_primers.hip) ----------------------------------------------------------------------------
+int bk_primers_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, int max_mismatches) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_primers_set comes between samples");
+    if (max_mismatches < 0 || max_mismatches > (int)bk::kMaxPrimerMismatches) return fail(BK_ERR_INVALID, "max_mismatches must be between 0 and %u", bk::kMaxPrimerMismatches);
+    if (n > bk::kMaxPrimers) return fail(BK_ERR_INVALID, "%u primers: at most %u", n, bk::kMaxPrimers);
+    if (n && (!seqs || !lens)) return fail(BK_ERR_INVALID, "null argument");
+    std::vector<uint32_t> tab((size_t)n * bk::kPrimerEntryWords, 0u);
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t L = lens[p];
+        if (L < bk::kPrimerMinLen || L > bk::kPrimerMaxLen) return fail(BK_ERR_INVALID, "primer %u: %u bases (a primer has %u to %u)", p + 1, L, bk::kPrimerMinLen, bk::kPrimerMaxLen);
+        if (!seqs[p]) return fail(BK_ERR_INVALID, "primer %u: null sequence", p + 1);
+        uint32_t* t = tab.data() + (size_t)p * bk::kPrimerEntryWords;
+        for (uint32_t i = 0; i < L; i++) {
+            const int c = bronko::acgt_code(seqs[p][i]);
+            if (c < 0) return fail(BK_ERR_INVALID, "primer %u: symbol %u is not one of ACGT/acgt", p + 1, i + 1);
+            t[i >> 4] |= (uint32_t)c << (2 * (i & 15));
+            const uint32_t j = 64 - 1 - i;   // base i's complement, counted from the end of the 64-base window
+            t[4 + (j >> 4)] |= (uint32_t)(3 - c) << (2 * (j & 15));
+        }
+        t[8] = L;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still read the table being replaced)
+    e->primers.reset();
+    if (n == 0) return BK_OK;
+    std::unique_ptr<Primers> pr(new Primers());
+    BK_HIP(pr->table.alloc(tab.size()));
+    BK_HIP(hipMemcpy(pr->table.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BK_HIP(pr->stats.alloc(6));
+    BK_HIP(hipMemset(pr->stats.p, 0, 6 * sizeof(unsigned long long)));
+    pr->n = n; pr->max_mismatches = (uint32_t)max_mismatches;
+    e->primers = std::move(pr);
+    return BK_OK;
+}
+
+int bk_primer_stats(bk_engine* e, int mate, uint64_t out[3]) {
+    if (!e || !out) return fail(BK_ERR_INVALID, "null argument");
+    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
+    if (!e->primers || !e->primers->in_sample) return fail(BK_ERR_STATE, "no primers were set for this sample (bk_primers_set before bk_sample_begin)");
+    if (e->in_sample) return fail(BK_ERR_STATE, "the primer counters are read after bk_sample_finalize");
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long o[3];
+    BK_HIP(hipMemcpyAsync(o, e->primers->stats.p + mate * 3, sizeof o, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 3; i++) out[i] = o[i];
+    return BK_OK;
+}
+
 // ---- the sample's k-mer count table (bk_kmer_dump.hip) --------------------------------------------------------------
 int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
@@ -1375,22 +1493,25 @@ int bk_sample_download_noise(bk_engine* e, double* out, uint64_t cap, uint64_t* 
 namespace {
 struct Packer {
     int k; uint32_t stride; uint32_t* words; uint16_t* lens; uint64_t cap; uint64_t n = 0;
-    void emit(const uint8_t* s, uint64_t len) {   // one record of <= 16*stride ACGT symbols
+    uint8_t* ends = nullptr;   // bk_pack_reads_flat_ends: [cap] the records' end flags
+    void emit(const uint8_t* s, uint64_t len, uint8_t flags) {   // one record of <= 16*stride ACGT symbols
         if (n < cap) {
             uint32_t* w = words + n * stride;
             std::memset(w, 0, (size_t)stride * 4);
             for (uint64_t i = 0; i < len; i++) w[i >> 4] |= (uint32_t)bronko::acgt_code(s[i]) << (2 * (i & 15));
             lens[n] = (uint16_t)len;
+            if (ends) ends[n] = flags;
         }
         n++;
     }
-    void run(const uint8_t* s, uint64_t len) {    // one maximal ACGT run
+    void run(const uint8_t* s, uint64_t len, uint8_t flags) {    // one maximal ACGT run (flags: it starts / ends its read)
         if (len < (uint64_t)k) return;
         const uint64_t maxb = std::min<uint64_t>((uint64_t)stride * 16, 65535);
+        if (len > maxb) flags = 0;   // (cut into chunks: no chunk is flagged)
         uint64_t pos = 0;
         for (;;) {
             const uint64_t take = std::min(maxb, len - pos);
-            emit(s + pos, take);
+            emit(s + pos, take, flags);
             if (pos + take >= len) break;
             pos += take - (uint64_t)(k - 1);      // next chunk re-reads k-1 bases: no k-mer lost or doubled
         }
@@ -1398,7 +1519,10 @@ struct Packer {
     void read(const uint8_t* s, uint64_t len) {
         uint64_t start = 0;
         for (uint64_t i = 0; i <= len; i++) {
-            if (i == len || bronko::acgt_code(s[i]) < 0) { run(s + start, i - start); start = i + 1; }
+            if (i == len || bronko::acgt_code(s[i]) < 0) {
+                run(s + start, i - start, (uint8_t)((start == 0 ? bk::kEndFirst : 0u) | (i == len ? bk::kEndLast : 0u)));
+                start = i + 1;
+            }
         }
     }
 };
@@ -1416,6 +1540,15 @@ uint64_t bk_pack_reads_flat(const uint8_t* buf, const uint64_t* offsets, uint64_
                             uint32_t* out_words, uint16_t* out_lens, uint64_t cap_records) {
     if (k < 1 || stride_words == 0 || (uint64_t)stride_words * 16 < (uint64_t)k) return 0;
     Packer p{k, stride_words, out_words, out_lens, (out_words && out_lens) ? cap_records : 0};
+    for (uint64_t r = 0; r < n_reads; r++) p.read(buf + offsets[r], offsets[r + 1] - offsets[r]);
+    return p.n;
+}
+
+uint64_t bk_pack_reads_flat_ends(const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads, int32_t k, uint32_t stride_words,
+                                 uint32_t* out_words, uint16_t* out_lens, uint8_t* out_ends, uint64_t cap_records) {
+    if (k < 1 || stride_words == 0 || (uint64_t)stride_words * 16 < (uint64_t)k) return 0;
+    Packer p{k, stride_words, out_words, out_lens, (out_words && out_lens) ? cap_records : 0};
+    p.ends = out_ends;
     for (uint64_t r = 0; r < n_reads; r++) p.read(buf + offsets[r], offsets[r + 1] - offsets[r]);
     return p.n;
 }

@@ -146,6 +146,15 @@ struct KmerDump {
     int finalized_mates = 0;                // mate files the last finalize selected (0: none, or finalized by shards)
 };
 
+// bk_primers_set: the primer table (bk_primers.hip) and the sample's trim counters
+struct Primers {
+    DevBuf<uint32_t> table;                 // [n][bk::kPrimerEntryWords]
+    uint32_t n = 0;
+    uint32_t max_mismatches = 0;
+    DevBuf<unsigned long long> stats;       // [2][3] per mate file: reads trimmed at 5', at 3', bases masked (zeroed by bk_sample_begin)
+    bool in_sample = false;                 // set when the current / last sample began
+};
+
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
 // by an engine and its forks, freed with the last of them.
 struct IndexTables {
@@ -278,6 +287,7 @@ struct bk_engine {
     DevBuf<unsigned long long> xchg_keys, xchg_cursors;   // bk_kmer_table_partition: the table's entries grouped by owner rank
     DevBuf<unsigned int> xchg_cnt;
     bool ktab_exchanged = false;            // bk_kmer_table_replace was called in this sample
+    std::unique_ptr<Primers> primers;       // bk_primers_set (null: no primers, no launch, no end flags)
     std::unique_ptr<KmerDump> dump;         // bk_kmer_dump_enable (null: no table, no launch)
     // gathered votes (bk_gather.hip): this engine's voting pass is gather_votes_kernel (sparse planes of a many-genome index)
     bool gather_mode = false;
@@ -313,7 +323,8 @@ struct bk_engine {
     // bk_push_reads_packed: two staging slots, so that the copy of a batch overlaps the scan of the previous one
     struct StageSlot {
         DevBuf<uint32_t> words; DevBuf<uint16_t> lens;
-        uint8_t* h = nullptr; size_t h_cap = 0;     // pinned host copy of the caller's batch (words, then lens)
+        DevBuf<uint8_t> ends;                       // bk_push_reads_packed_ends with primers set: the records' end flags
+        uint8_t* h = nullptr; size_t h_cap = 0;     // pinned host copy of the caller's batch (words, then lens, then end flags)
         hipEvent_t done = nullptr; bool busy = false;
     } stage[2];
     int next_stage = 0;
@@ -329,6 +340,7 @@ struct bk_engine {
         DevBuf<uint32_t> d_work;           // pack_words_kernel's work list
         DevBuf<uint32_t> d_words;
         DevBuf<uint16_t> d_lens;
+        DevBuf<uint8_t> d_ends;            // primers set: the records' end flags (the *_ends_kernel variants of K0)
         hipEvent_t uploaded = nullptr, done = nullptr;
         bool busy = false;
     };

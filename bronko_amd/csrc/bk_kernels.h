@@ -228,8 +228,33 @@ struct QualArgs {
     uint32_t shift;
     uint32_t thr;                   // 34..126
 };
-// tally: the sample's count of records that hold a run (+= this batch's); q: null, or the quality-aware twins of the packer
-void launch_pack_reads(const PackArgs& a, unsigned long long* tally, hipStream_t stream, const QualArgs* q = nullptr);
+// tally: the sample's count of records that hold a run (+= this batch's); q: null, or the quality-aware twins of the packer;
+// ends: null, or [cap] out -- the end flags of every record written (the *_ends_kernel variants, launched only with primers set)
+void launch_pack_reads(const PackArgs& a, unsigned long long* tally, hipStream_t stream, const QualArgs* q = nullptr, uint8_t* ends = nullptr);
+
+// ---- primer trimming (bk_primers.hip) ----
+// A record's end flags: its first base is its read's first letter / its last base is its read's last letter (a chunk of a run
+// that was cut into several records carries neither).
+constexpr uint32_t kEndFirst = 1u, kEndLast = 2u;
+constexpr uint32_t kPrimerMinLen = 12, kPrimerMaxLen = 64, kMaxPrimers = 1024, kMaxPrimerMismatches = 3;
+// A primer table entry: the primer's 2-bit codes at bases [0, len) of words 0..3, its reverse complement at positions
+// [64 - len, 64) of words 4..7 (so that it ends where a window of a record's last 64 bases ends), len in word 8; unused bits 0.
+constexpr uint32_t kPrimerEntryWords = 9;
+struct TrimArgs {
+    uint32_t* words;                // [n_records][stride_words], rewritten in place
+    uint16_t* lens;                 // [n_records]
+    const uint8_t* ends;            // [n_records] end flags
+    uint64_t n_records;
+    const unsigned long long* n_records_dev;   // null, or the device's count of record slots in use (K0)
+    uint32_t stride_words;
+    int32_t k;
+    const uint32_t* table;          // [n_primers][kPrimerEntryWords]
+    uint32_t n_primers;
+    uint32_t max_mismatches;
+    unsigned long long* stats;      // [3] += reads trimmed at 5', reads trimmed at 3', bases masked
+    unsigned long long* n_real;     // the sample's tally of records that hold a run: -= records left with fewer than k bases
+};
+void launch_primer_trim(const TrimArgs& a, int n_cus, hipStream_t stream);
 // votes[f] += number of the first records' middle k-mers that occur in genome file f (which genome does the sample look like?)
 void launch_pick_window(const ScanArgs& a, uint64_t n_probe, unsigned int* votes, const uint32_t* file_cell_lo, int forced, uint32_t* win,
                         hipStream_t stream);

@@ -112,9 +112,10 @@ __device__ __forceinline__ int acgt_code(unsigned char c) {
 
 // One read, byte by byte: its runs of letters as records in the slots next_slot() hands out (a slot >= a.cap is not written);
 // returns how many were written.  kQual (the --min-base-qual twin): a letter whose quality byte is below q.thr splits the read as
-// an N does.
-template <bool kQual, typename NextSlot>
-__device__ __forceinline__ unsigned long long pack_runs(const PackArgs& a, const QualArgs& q, uint64_t r, NextSlot&& next_slot) {
+// an N does.  kEnds (primers set): ends[slot] = the record's end flags -- its run starts the read / ends the read; a run cut into
+// chunks flags none of them.
+template <bool kQual, bool kEnds, typename NextSlot>
+__device__ __forceinline__ unsigned long long pack_runs(const PackArgs& a, const QualArgs& q, uint8_t* ends, uint64_t r, NextSlot&& next_slot) {
     const uint64_t maxb = min((uint64_t)a.stride_words * 16, (uint64_t)65535);
     const uint64_t o0 = a.offsets[r], len = a.offsets[r + 1] - o0;
     const uint8_t* s = a.bases + a.shift + o0;
@@ -139,6 +140,7 @@ __device__ __forceinline__ unsigned long long pack_runs(const PackArgs& a, const
                     if (take & 15) w[take >> 4] = acc;
                     for (uint64_t j = (take + 15) >> 4; j < a.stride_words; ++j) w[j] = 0;
                     a.lens[rec] = (uint16_t)take;
+                    if constexpr (kEnds) ends[rec] = run <= maxb ? (uint8_t)((start == 0 ? kEndFirst : 0u) | (p == len ? kEndLast : 0u)) : (uint8_t)0;
                     ++real;
                 }
                 if (pos + take >= run) break;
@@ -150,9 +152,9 @@ __device__ __forceinline__ unsigned long long pack_runs(const PackArgs& a, const
     return real;
 }
 // ... appended behind the n_reads slots through the device counter (a.n_records[0])
-template <bool kQual>
-__device__ __forceinline__ unsigned long long pack_read_slow(const PackArgs& a, const QualArgs& q, uint64_t r) {
-    return pack_runs<kQual>(a, q, r, [&] { return atomicAdd(a.n_records, 1ull); });
+template <bool kQual, bool kEnds>
+__device__ __forceinline__ unsigned long long pack_read_slow(const PackArgs& a, const QualArgs& q, uint8_t* ends, uint64_t r) {
+    return pack_runs<kQual, kEnds>(a, q, ends, r, [&] { return atomicAdd(a.n_records, 1ull); });
 }
 
 constexpr int kPackBlock = 256;
@@ -206,8 +208,9 @@ __device__ __forceinline__ uint32_t valid16(const uint32_t* x4, const uint32_t* 
 // of their own, with a shift of their own -- and realigned the same way; a letter below the threshold flags its read like an N).
 // kQual: blk_s[3] -- the block's appended records, the reads that are not one record, the block's first appended slot; vm_s[t],
 // pw_s[2t, 2t + 1] -- thread t's 32 letters: which are valid (bit i: letter i), their codes
-template <bool kQual>
-__device__ __forceinline__ void pack_words(const PackArgs& a, const QualArgs& qa, uint32_t rpb, uint32_t tpr, uint32_t tpr_recip,
+// kEnds: the *_ends_kernel variants (primers set) also write every record's end flags to ends[slot]
+template <bool kQual, bool kEnds>
+__device__ __forceinline__ void pack_words(const PackArgs& a, const QualArgs& qa, uint8_t* ends, uint32_t rpb, uint32_t tpr, uint32_t tpr_recip,
                                            unsigned char* lines, unsigned char* qlines, unsigned long long* off_s, unsigned int* bad_s,
                                            unsigned long long* blk_s, uint32_t* vm_s, uint32_t* pw_s) {
     const uint32_t sw = a.stride_words;
@@ -305,6 +308,7 @@ __device__ __forceinline__ void pack_words(const PackArgs& a, const QualArgs& qa
         const bool head = mine && q0 == 0u, good = head && simple && !bad_s[rl];
         const bool bytewise = head && !good && !simple && len64 >= (uint64_t)a.k;
         if (head) a.lens[r0 + rl] = good ? (uint16_t)len : (uint16_t)0;
+        if constexpr (kEnds) { if (good) ends[r0 + rl] = (uint8_t)(kEndFirst | kEndLast); }
         const uint32_t* vmr = vm_s + rl * tpr;          // the read's validity bits, 32 per thread
         const uint32_t* pwr = pw_s + kPackWpt * rl * tpr;   // ... and its 2-bit codes, 16 per word
         auto for_runs = [&](auto&& f) {                 // f(s, e): every maximal run of valid letters [s, e) with e - s >= k
@@ -328,7 +332,7 @@ __device__ __forceinline__ void pack_words(const PackArgs& a, const QualArgs& qa
         if (head && !good && simple) for_runs([&](uint32_t, uint32_t) { ++cnt; });
         if (cnt) local = atomicAdd(&blk_s[0], cnt);
         if (head && !good && !bytewise) atomicAdd(&blk_s[1], 1ull);
-        if (bytewise) atomicAdd(a.n_real, pack_read_slow<true>(a, qa, r0 + rl) - 1ull);
+        if (bytewise) atomicAdd(a.n_real, pack_read_slow<true, kEnds>(a, qa, ends, r0 + rl) - 1ull);
         __syncthreads();
         if (threadIdx.x == 0 && blk_s[1]) {
             const unsigned long long base = blk_s[0] ? atomicAdd(a.n_records, blk_s[0]) : 0ull;
@@ -357,17 +361,19 @@ __device__ __forceinline__ void pack_words(const PackArgs& a, const QualArgs& qa
                     w[j] = x;
                 }
                 a.lens[rec] = (uint16_t)take;
+                if constexpr (kEnds) ends[rec] = (uint8_t)((s0 == 0u ? kEndFirst : 0u) | (e == len ? kEndLast : 0u));
             });
         }
     } else if (mine && q0 == 0u) {
         const bool good = simple && !bad_s[rl];
         a.lens[r0 + rl] = good ? (uint16_t)len : (uint16_t)0;
+        if constexpr (kEnds) { if (good) ends[r0 + rl] = (uint8_t)(kEndFirst | kEndLast); }
         if (!good) {
             // (the launcher counted every read as a record that holds a run: one atomic per read that is not, none per block -- a
             // tally per block was 40,000 additions to one address, 0.5 ms per million reads)
             // anything that may still hold a run of k letters: byte by byte, by this thread, here (a kernel of its own behind this
             // one -- a work list, a launch whose grid found it empty on the benchmark -- was 4.6 us of K0's 49)
-            const unsigned long long real = len64 >= (uint64_t)a.k ? pack_read_slow<kQual>(a, qa, r0 + rl) : 0ull;
+            const unsigned long long real = len64 >= (uint64_t)a.k ? pack_read_slow<kQual, kEnds>(a, qa, ends, r0 + rl) : 0ull;
             atomicAdd(a.n_real, real - 1ull);
         }
     }
@@ -378,7 +384,14 @@ __global__ __launch_bounds__(kPackBlock) void pack_words_kernel(PackArgs a, uint
     __shared__ __attribute__((aligned(16))) unsigned char lines[kPackLdsBytes];
     __shared__ unsigned long long off_s[kPackBlock + 1];       // offsets of the block's reads (rpb + 1 of them)
     __shared__ unsigned int bad_s[kPackBlock];                 // per read of the block: some word met a symbol that is not a letter
-    pack_words<false>(a, QualArgs{}, rpb, tpr, tpr_recip, lines, nullptr, off_s, bad_s, nullptr, nullptr, nullptr);
+    pack_words<false, false>(a, QualArgs{}, nullptr, rpb, tpr, tpr_recip, lines, nullptr, off_s, bad_s, nullptr, nullptr, nullptr);
+}
+// primers set: the same, and every record's end flags
+__global__ __launch_bounds__(kPackBlock) void pack_words_ends_kernel(PackArgs a, uint8_t* ends, uint32_t rpb, uint32_t tpr, uint32_t tpr_recip) {
+    __shared__ __attribute__((aligned(16))) unsigned char lines[kPackLdsBytes];
+    __shared__ unsigned long long off_s[kPackBlock + 1];
+    __shared__ unsigned int bad_s[kPackBlock];
+    pack_words<false, true>(a, QualArgs{}, ends, rpb, tpr, tpr_recip, lines, nullptr, off_s, bad_s, nullptr, nullptr, nullptr);
 }
 
 // --min-base-qual: the same with the reads' quality lines (QualArgs); 16.5 KB of LDS a block instead of 8.5
@@ -389,20 +402,31 @@ __global__ __launch_bounds__(kPackBlock) void pack_words_qual_kernel(PackArgs a,
     __shared__ unsigned int bad_s[kPackBlock];
     __shared__ unsigned long long blk_s[3];
     __shared__ uint32_t vm_s[kPackBlock], pw_s[kPackBlock * kPackWpt];
-    pack_words<true>(a, q, rpb, tpr, tpr_recip, lines, qlines, off_s, bad_s, blk_s, vm_s, pw_s);
+    pack_words<true, false>(a, q, nullptr, rpb, tpr, tpr_recip, lines, qlines, off_s, bad_s, blk_s, vm_s, pw_s);
+}
+__global__ __launch_bounds__(kPackBlock) void pack_words_qual_ends_kernel(PackArgs a, QualArgs q, uint8_t* ends, uint32_t rpb, uint32_t tpr, uint32_t tpr_recip) {
+    __shared__ __attribute__((aligned(16))) unsigned char lines[kPackLdsBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char qlines[kPackLdsBytes];
+    __shared__ unsigned long long off_s[kPackBlock + 1];
+    __shared__ unsigned int bad_s[kPackBlock];
+    __shared__ unsigned long long blk_s[3];
+    __shared__ uint32_t vm_s[kPackBlock], pw_s[kPackBlock * kPackWpt];
+    pack_words<true, true>(a, q, ends, rpb, tpr, tpr_recip, lines, qlines, off_s, bad_s, blk_s, vm_s, pw_s);
 }
 
 // One thread per read (long reads: records of more than kPackMaxWords words): the slot of its index stays empty.
-template <bool kQual>
-__device__ __forceinline__ void pack_slow(const PackArgs& a, const QualArgs& q) {
+template <bool kQual, bool kEnds>
+__device__ __forceinline__ void pack_slow(const PackArgs& a, const QualArgs& q, uint8_t* ends) {
     for (uint64_t r = (uint64_t)blockIdx.x * kPackBlock + threadIdx.x; r < a.n_reads; r += (uint64_t)gridDim.x * kPackBlock) {
         a.lens[r] = 0;   // its records, if any, go behind the n_reads slots
-        const unsigned long long real = pack_read_slow<kQual>(a, q, r);
+        const unsigned long long real = pack_read_slow<kQual, kEnds>(a, q, ends, r);
         if (real) atomicAdd(a.n_real, real);
     }
 }
-__global__ __launch_bounds__(kPackBlock) void pack_slow_kernel(PackArgs a) { pack_slow<false>(a, QualArgs{}); }
-__global__ __launch_bounds__(kPackBlock) void pack_slow_qual_kernel(PackArgs a, QualArgs q) { pack_slow<true>(a, q); }
+__global__ __launch_bounds__(kPackBlock) void pack_slow_kernel(PackArgs a) { pack_slow<false, false>(a, QualArgs{}, nullptr); }
+__global__ __launch_bounds__(kPackBlock) void pack_slow_qual_kernel(PackArgs a, QualArgs q) { pack_slow<true, false>(a, q, nullptr); }
+__global__ __launch_bounds__(kPackBlock) void pack_slow_ends_kernel(PackArgs a, uint8_t* ends) { pack_slow<false, true>(a, QualArgs{}, ends); }
+__global__ __launch_bounds__(kPackBlock) void pack_slow_qual_ends_kernel(PackArgs a, QualArgs q, uint8_t* ends) { pack_slow<true, true>(a, q, ends); }
 
 __global__ void add_u64_kernel(unsigned long long* dst, const unsigned long long* src) { *dst += *src; }
 __global__ void add_const_u64_kernel(unsigned long long* dst, unsigned long long v) { *dst += v; }
@@ -419,7 +443,8 @@ __global__ void pack_begin_kernel(unsigned long long* dst, unsigned long long v0
 // a.n_records[0] = record slots in use when the kernels end; `tally` (the sample's count of records that hold a run -- what KMC would
 // call its input sequences) grows by this batch's: a launch of its own that added a batch-local count to it afterwards was 4.5 us
 // q: the reads' quality lines and threshold (--min-base-qual: the quality-aware twins), or null
-void launch_pack_reads(const PackArgs& a0, unsigned long long* tally, hipStream_t stream, const QualArgs* q) {
+// ends: the records' end flags (primers set: the *_ends_kernel variants), or null
+void launch_pack_reads(const PackArgs& a0, unsigned long long* tally, hipStream_t stream, const QualArgs* q, uint8_t* ends) {
     if (a0.n_reads == 0) return;
     PackArgs a = a0;
     a.n_real = tally;
@@ -429,12 +454,17 @@ void launch_pack_reads(const PackArgs& a0, unsigned long long* tally, hipStream_
     if (by_word) {
         const uint32_t tpr = (a.stride_words + kPackWpt - 1) / kPackWpt, rpb = (uint32_t)kPackBlock / tpr;
         const uint32_t recip = (uint32_t)(((1ull << 32) + tpr - 1) / tpr);
-        if (q) hipLaunchKernelGGL(pack_words_qual_kernel, dim3((unsigned)((a.n_reads + rpb - 1) / rpb)), dim3(kPackBlock), 0, stream, a, *q, rpb, tpr, recip);
-        else hipLaunchKernelGGL(pack_words_kernel, dim3((unsigned)((a.n_reads + rpb - 1) / rpb)), dim3(kPackBlock), 0, stream, a, rpb, tpr, recip);
+        const dim3 wgrid((unsigned)((a.n_reads + rpb - 1) / rpb));
+        if (q && ends) hipLaunchKernelGGL(pack_words_qual_ends_kernel, wgrid, dim3(kPackBlock), 0, stream, a, *q, ends, rpb, tpr, recip);
+        else if (ends) hipLaunchKernelGGL(pack_words_ends_kernel, wgrid, dim3(kPackBlock), 0, stream, a, ends, rpb, tpr, recip);
+        else if (q) hipLaunchKernelGGL(pack_words_qual_kernel, wgrid, dim3(kPackBlock), 0, stream, a, *q, rpb, tpr, recip);
+        else hipLaunchKernelGGL(pack_words_kernel, wgrid, dim3(kPackBlock), 0, stream, a, rpb, tpr, recip);
     } else {
         a.work = nullptr;   // long reads: every read byte by byte
         const dim3 grid((unsigned)std::min<uint64_t>((a.n_reads + kPackBlock - 1) / kPackBlock, 65535));
-        if (q) hipLaunchKernelGGL(pack_slow_qual_kernel, grid, dim3(kPackBlock), 0, stream, a, *q);
+        if (q && ends) hipLaunchKernelGGL(pack_slow_qual_ends_kernel, grid, dim3(kPackBlock), 0, stream, a, *q, ends);
+        else if (ends) hipLaunchKernelGGL(pack_slow_ends_kernel, grid, dim3(kPackBlock), 0, stream, a, ends);
+        else if (q) hipLaunchKernelGGL(pack_slow_qual_kernel, grid, dim3(kPackBlock), 0, stream, a, *q);
         else hipLaunchKernelGGL(pack_slow_kernel, grid, dim3(kPackBlock), 0, stream, a);
     }
 }

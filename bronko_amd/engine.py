@@ -66,6 +66,27 @@ def pack_reads(reads, k, stride_words=None):
     return words[:n], lens[:n]
 
 
+def pack_reads_ends(reads, k, stride_words=None):
+    """bk_pack_reads_flat_ends: pack_reads plus the records' end flags u8[n] (bit 0: the record starts its read, bit 1: ends it)."""
+    L = _ffi.load()
+    reads = [bytes(r) for r in reads]
+    if stride_words is None:
+        longest = max([len(r) for r in reads] + [k])
+        stride_words = min((longest + 15) // 16, 4095)
+    flat = np.frombuffer(b"".join(reads), np.uint8) if reads else np.zeros(0, np.uint8)
+    flat = np.ascontiguousarray(flat) if len(flat) else np.zeros(1, np.uint8)
+    off = np.zeros(len(reads) + 1, np.uint64)
+    if reads:
+        off[1:] = np.cumsum([len(r) for r in reads])
+    n = L.bk_pack_reads_flat_ends(flat.ctypes.data, off.ctypes.data, len(reads), k, stride_words, None, None, None, 0)
+    words = np.zeros((max(n, 1), stride_words), np.uint32)
+    lens = np.zeros(max(n, 1), np.uint16)
+    ends = np.zeros(max(n, 1), np.uint8)
+    L.bk_pack_reads_flat_ends(flat.ctypes.data, off.ctypes.data, len(reads), k, stride_words, words.ctypes.data, lens.ctypes.data,
+                              ends.ctypes.data, n)
+    return words[:n], lens[:n], ends[:n]
+
+
 def build_index_device(k, files, device=0):
     """bk_build_index: build_indexes (build.rs:145-231) on the GPU.  files = [(file_name, [(seq_name, seq_bytes), ...]), ...];
     returns (bucket_ids u64[n], bucket_off u64[n + 1], entries BucketInfo[m]) -- what Engine() takes."""
@@ -187,6 +208,35 @@ class Engine:
             return
         assert words.ndim == 2 and words.shape[0] == len(lens)
         _check(self._L.bk_push_reads_packed(self.h, mate, words.ctypes.data, words.shape[1], lens.ctypes.data, len(lens)), self._L)
+
+    def primers_set(self, primers, max_mismatches=1):
+        """bk_primers_set: primers (bytes, 5'->3') trimmed from the ends of every read pushed from now on; [] clears them."""
+        primers = [bytes(p) for p in primers]
+        bufs = [C.create_string_buffer(p, max(len(p), 1)) for p in primers]
+        ptrs = (C.c_void_p * max(len(bufs), 1))(*[C.addressof(b) for b in bufs])
+        lens = np.array([len(p) for p in primers] + [0], np.uint32)
+        _check(self._L.bk_primers_set(self.h, C.addressof(ptrs), lens.ctypes.data, len(primers), max_mismatches), self._L)
+
+    def primer_stats(self, mate):
+        """bk_primer_stats: [reads trimmed at 5', reads trimmed at 3', bases masked] of the sample just finalized."""
+        out = np.zeros(3, np.uint64)
+        _check(self._L.bk_primer_stats(self.h, mate, out.ctypes.data), self._L)
+        return out.tolist()
+
+    def push_reads_ends(self, mate, words, lens, ends):
+        """bk_push_reads_packed_ends: packed records with their end flags (pack_reads_ends)."""
+        words = np.ascontiguousarray(words, np.uint32)
+        lens = np.ascontiguousarray(lens, np.uint16)
+        ends = np.ascontiguousarray(ends, np.uint8)
+        if len(lens) == 0:
+            return
+        assert words.ndim == 2 and words.shape[0] == len(lens) == len(ends)
+        _check(self._L.bk_push_reads_packed_ends(self.h, mate, words.ctypes.data, words.shape[1], lens.ctypes.data, ends.ctypes.data,
+                                                 len(lens)), self._L)
+
+    def push_reads_ends_device(self, mate, d_words_ptr, stride_words, d_lens_ptr, d_ends_ptr, n_records):
+        _check(self._L.bk_push_reads_packed_ends_device(self.h, mate, C.c_void_p(d_words_ptr), stride_words, C.c_void_p(d_lens_ptr),
+                                                        C.c_void_p(d_ends_ptr), n_records), self._L)
 
     def push_reads_ascii(self, mate, reads, quals=None, min_qual=0):
         """bk_push_reads_ascii: list of ASCII reads, packed on the GPU, asynchronous.  With quals (one quality line per read, same

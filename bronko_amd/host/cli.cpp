@@ -99,6 +99,9 @@ struct Args {
     long min_variant_depth = 3;
     double noise_multiplier = 1.5;
     long min_base_qual = 0;         // --min-base-qual: bases below this Phred+33 quality are N before k-mer counting (0: off)
+    std::string primers;            // --primers: FASTA of amplicon primers trimmed from the read ends (empty: none)
+    bool has_primers = false, has_primer_mismatches = false;
+    long primer_mismatches = 1;     // --primer-mismatches: Hamming distance a primer match may have (0..3)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -114,11 +117,15 @@ struct Args {
           "            [--use-full-kmer] [--n-fixed N] [--min-af F] [--no-end-filter] [--no-strand-filter]\n"
           "            [--no-strand-balance-filter] [--balance-ratio F] [--n-per-strand N] [--strand_odds F]\n"
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
-          "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
+          "            [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
-          "                    are counted; 0..93, default 0 (off)\n", stderr);
+          "                    are counted; 0..93, default 0 (off)\n"
+          "  --primers FASTA   treat amplicon primers at the read ends as N: a primer (ACGT, 12..64 bases, at most 1024 of them) that\n"
+          "                    lies whole at a read's 5' end, or whose reverse complement lies whole at its 3' end\n"
+          "  --primer-mismatches M  mismatches a primer match may have (no indels); 0..3, default 1\n", stderr);
     exit(code);
 }
 
@@ -208,6 +215,14 @@ Args parse_args(int argc, char** argv) {
             a.min_base_qual = strtol(v.c_str(), &end, 10);
             if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
         }
+        else if (opt == "--primers") { a.primers = one(); a.has_primers = true; }
+        else if (opt == "--primer-mismatches") {   // (any integer here: a value outside 0..3 is refused by check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            a.primer_mismatches = strtol(v.c_str(), &end, 10);
+            a.has_primer_mismatches = true;
+            if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+        }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
     return a;
@@ -281,6 +296,36 @@ int run_build(const Args& a) {
 }
 
 // ---- bronko call ----------------------------------------------------------------------------------------------
+// --primers: the file's records, one primer each (FASTA, plain or gzip; a sequence may span lines), checked against what
+// bk_primers_set takes; every violation ends the run with a message that names the file and the record
+std::vector<std::string> g_primers;   // (set by check_call_args)
+int g_primer_mismatches = 1;
+std::vector<std::string> read_primers(const char* T, const std::string& path) {
+    constexpr size_t kMinLen = 12, kMaxLen = 64, kMaxPrimers = 1024;
+    std::vector<std::string> out, names;
+    try {
+        GzLineReader in(path);
+        std::string line;
+        while (in.next(line)) {
+            if (line.empty()) continue;
+            if (line[0] == '>') { names.push_back(line.substr(1)); out.emplace_back(); continue; }
+            if (out.empty()) die(T, path + ": primer file does not start with a FASTA header ('>')");
+            out.back() += line;
+        }
+    } catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the primer file " + path); }
+    if (out.empty()) die(T, path + ": primer file holds no records");
+    if (out.size() > kMaxPrimers) die(T, path + ": " + std::to_string(out.size()) + " primer records, at most " + std::to_string(kMaxPrimers) + " are supported");
+    for (size_t i = 0; i < out.size(); i++) {
+        const std::string where = path + ": record " + std::to_string(i + 1) + " (" + names[i] + ")";
+        for (size_t j = 0; j < out[i].size(); j++)
+            if (!strchr("ACGTacgt", out[i][j]) || !out[i][j])
+                die(T, where + ": symbol '" + std::string(1, out[i][j]) + "' at position " + std::to_string(j + 1) + " is not one of ACGT (degenerate primers are not supported)");
+        if (out[i].size() < kMinLen || out[i].size() > kMaxLen)
+            die(T, where + ": primer of " + std::to_string(out[i].size()) + " bases, must be between " + std::to_string(kMinLen) + " and " + std::to_string(kMaxLen));
+    }
+    return out;
+}
+
 void check_call_args(const Args& a) {   // call.rs:30-136
     const char* T = "bronko::call";
     if (a.kmer % 2 != 1 || a.kmer > 31 || a.kmer < 15) die(T, "Invalid kmer size, must be odd and between [15-31]");
@@ -305,6 +350,9 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     else if (a.noise_multiplier == 1.0) LOG_WARN(T, "Noise multiplier for variant detection set to 1.0, all variants will pass this filter");
     if (a.first_pairs.size() != a.second_pairs.size()) die(T, "Number of paired end sequences do not match, exiting.");
     if (a.min_base_qual < 0 || a.min_base_qual > 93) die(T, "Minimum base quality must be between 0 and 93 (Phred+33), got " + std::to_string(a.min_base_qual));
+    if (a.has_primer_mismatches && !a.has_primers) die(T, "--primer-mismatches needs --primers");
+    if (a.primer_mismatches < 0 || a.primer_mismatches > 3) die(T, "Primer mismatches must be between 0 and 3, got " + std::to_string(a.primer_mismatches));
+    if (a.has_primers) { g_primers = read_primers(T, a.primers); g_primer_mismatches = (int)a.primer_mismatches; }
 }
 
 struct Engine {
@@ -323,7 +371,8 @@ void hip_check(int rc, const char* what) {
 struct FastqBatch {
     std::string buf; std::vector<uint64_t> off{0};   // sequence lines back to back (the line loop: streams, one thread) ...
     std::string qual;                                // (--min-base-qual) ... and their quality lines, at the same offsets
-    PackedBatch packed; bool is_packed = false;      // ... or 2-bit records, parsed and packed on several threads (fastq_pack.hpp)
+    PackedBatch packed; bool is_packed = false;      // ... or 2-bit records, parsed and packed on several threads (fastq_pack.hpp;
+                                                     // --primers: with their end flags)
     bool last = false; std::string error;
     size_t bytes() const { return is_packed ? packed.bytes() : buf.size() + qual.size(); }
 };
@@ -414,7 +463,7 @@ void parse_fastq(const std::string& path, BatchQueue& out, unsigned inflate_thre
             // a few MB of text make a piece, pieces are gathered into batches of a quarter of a million records (a scan launch has
             // a fixed cost: small pushes are slow pushes)
             constexpr uint64_t kBatchRecords = 1u << 18;
-            FastqPacker in(path, g_kmer, inflate_threads, g_min_qual);
+            FastqPacker in(path, g_kmer, inflate_threads, g_min_qual, !g_primers.empty());
             PackedBatch b;
             cur.is_packed = true;
             while (in.next(b)) {
@@ -426,6 +475,7 @@ void parse_fastq(const std::string& path, BatchQueue& out, unsigned inflate_thre
                 else {
                     cur.packed.words.insert(cur.packed.words.end(), b.words.begin(), b.words.end());
                     cur.packed.lens.insert(cur.packed.lens.end(), b.lens.begin(), b.lens.end());
+                    cur.packed.ends.insert(cur.packed.ends.end(), b.ends.begin(), b.ends.end());
                     cur.packed.n_records += b.n_records; cur.packed.n_reads += b.n_reads;
                 }
                 if (cur.packed.n_records >= kBatchRecords) { out.put(std::move(cur)); cur = out.fresh(); cur.is_packed = true; if (out.abandoned.load()) break; }
@@ -585,7 +635,10 @@ uint64_t push_fastqs(const std::vector<bk_engine*>& engs, const std::vector<std:
             FastqBatch b = queues[m].take();
             if (!b.error.empty() && error.empty()) error = b.error;
             if (error.empty() && b.is_packed) {
-                if (b.packed.n_records)
+                if (b.packed.n_records && !g_primers.empty())
+                    hip_check(bk_push_reads_packed_ends(engs[n_batches++ % engs.size()], (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(),
+                                                        b.packed.ends.data(), b.packed.n_records), "bk_push_reads_packed_ends");
+                else if (b.packed.n_records)
                     hip_check(bk_push_reads_packed(engs[n_batches++ % engs.size()], (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(), b.packed.n_records), "bk_push_reads_packed");
                 n_reads += b.packed.n_reads;
             } else if (error.empty() && b.off.size() > 1 && g_min_qual > 0) {
@@ -942,6 +995,27 @@ int run_call(const Args& a) {
         LOG_INFO(T, std::to_string(total_reads) + " reads counted from " + mates[0]);
         return total_reads;
     };
+    // --primers: every engine that takes reads trims them (bk_primers_set is per engine); under --verbose, what was trimmed per reads file
+    auto set_primers = [&](bk_engine* e) {
+        if (g_primers.empty() || !e) return;
+        std::vector<const uint8_t*> seqs;
+        std::vector<uint32_t> lens;
+        for (const auto& p : g_primers) { seqs.push_back(reinterpret_cast<const uint8_t*>(p.data())); lens.push_back((uint32_t)p.size()); }
+        hip_check(bk_primers_set(e, seqs.data(), lens.data(), (uint32_t)seqs.size(), g_primer_mismatches), "bk_primers_set");
+    };
+    auto log_primer_stats = [&](const std::vector<bk_engine*>& engs, const std::vector<std::string>& mates) {
+        if (g_primers.empty() || g_level < 4) return;
+        for (size_t m = 0; m < mates.size(); m++) {
+            uint64_t sum[3] = {0, 0, 0};
+            for (bk_engine* e : engs) {
+                uint64_t o[3];
+                hip_check(bk_primer_stats(e, (int)m, o), "bk_primer_stats");
+                for (int i = 0; i < 3; i++) sum[i] += o[i];
+            }
+            LOG_TRACE(T, "primers: " + std::to_string(sum[0]) + " reads trimmed at the 5' end, " + std::to_string(sum[1]) + " at the 3' end, " +
+                             std::to_string(sum[2]) + " bases masked in " + mates[m]);
+        }
+    };
     constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
     const int dump_threads = (int)std::max<size_t>(1, std::min<size_t>(16, (size_t)a.threads / std::max<size_t>(1, lanes.size())));
     auto complete = [&](bk_engine* e, const std::vector<std::string>& mates, size_t sample_id, bool finalized = false) {
@@ -953,6 +1027,7 @@ int run_call(const Args& a) {
         // finalize, then reference selection + baseline noise + variant calls, all on the device and asynchronous
         // (bk_sample_call); the pileup arrays only travel when --pileup wants them written
         if (!finalized) hip_check(bk_sample_finalize(e, n_mates), "bk_sample_finalize");   // (a sharded sample: sharded_finalize has done it)
+        if (!finalized) log_primer_stats(std::vector<bk_engine*>{e}, mates);
         bk_call_params dcp;
         bk_call_params_default(&dcp);
         dcp.k = cp.k; dcp.no_end_filter = cp.no_end_filter; dcp.no_strand_filter = cp.no_strand_filter;
@@ -1038,11 +1113,13 @@ int run_call(const Args& a) {
     };
 
     if (shard_mode) {
+        for (bk_engine* e : shards.engs) set_primers(e);
         for (size_t i = 0; i < samples.size(); i++) {
             const auto& mates = samples[i];
             LOG_INFO(T, mates.size() == 1 ? "Processing " + mates[0] : "Processing paired reads " + mates[0] + ", " + mates[1]);
             ingest(shards.engs, mates, i);
             sharded_finalize(shards, (int)mates.size(), cells4);
+            log_primer_stats(shards.engs, mates);
             complete(shards.engs[0], mates, i, true);
         }
         for (auto c : shards.comms) nccl_check(ncclCommDestroy(c), "ncclCommDestroy");
@@ -1051,6 +1128,7 @@ int run_call(const Args& a) {
     for (size_t i = 0; i < samples.size() && !lanes.empty(); i++) lanes[i % lanes.size()].mine.push_back(i);
     auto run_lane = [&](Lane& ln) {
         if (ln.mine.size() > 1) hip_check(bk_engine_fork(ln.eng.e, &ln.fork.e), "bk_engine_fork");
+        for (bk_engine* e : {ln.eng.e, ln.fork.e}) set_primers(e);
         if (a.keep_kmer_info)   // (the table grows with the sample)
             for (bk_engine* e : {ln.eng.e, ln.fork.e})
                 if (e) hip_check(bk_kmer_dump_enable(e, kDumpTableLog2), "bk_kmer_dump_enable");

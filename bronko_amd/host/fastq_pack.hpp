@@ -41,10 +41,11 @@ namespace bronko {
 struct PackedBatch {
     std::vector<uint32_t> words;   // [n_records][stride]
     std::vector<uint16_t> lens;    // [n_records]
+    std::vector<uint8_t> ends;     // [n_records] end flags (bk_push_reads_packed_ends), filled only for a reader asked for them (--primers)
     uint32_t stride = 0;
     uint64_t n_records = 0, n_reads = 0;   // records packed; sequence lines seen (a read with an N is several records, a short one none)
-    size_t bytes() const { return words.size() * 4 + lens.size() * 2; }
-    void clear() { words.clear(); lens.clear(); stride = 0; n_records = 0; n_reads = 0; }
+    size_t bytes() const { return words.size() * 4 + lens.size() * 2 + ends.size(); }
+    void clear() { words.clear(); lens.clear(); ends.clear(); stride = 0; n_records = 0; n_reads = 0; }
 };
 
 // 2-bit code of a sequence symbol (A C G T, either case), 4 = anything else (KMC splits a read there)
@@ -60,9 +61,11 @@ inline const AcgtLut& acgt_lut() { static const AcgtLut l; return l; }
 // look-ups a word, no branch per symbol (the byte-at-a-time packer of the C ABI made 1 us a read of it: with the text inflated
 // on 32 threads the packing was the slower half).
 // kQual (--min-base-qual): qual[i] is line i's quality line (same length); a symbol whose quality byte is below thr is an N.
+// want_ends (--primers): out.ends holds every record's end flags -- bit 0: its run starts the line, bit 1: its run ends the line; the
+// chunks of a run that was cut carry neither.
 template <bool kQual>
 inline void pack_lines_t(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out,
-                         const std::vector<const uint8_t*>* qual, uint8_t thr) {
+                         const std::vector<const uint8_t*>* qual, uint8_t thr, bool want_ends = false) {
     out.clear();
     out.n_reads = ptr.size();
     uint64_t longest = (uint64_t)k;
@@ -73,12 +76,17 @@ inline void pack_lines_t(const std::vector<const uint8_t*>& ptr, const std::vect
     const uint8_t* const lut = acgt_lut().c;
     out.words.resize((ptr.size() + 16) * (size_t)stride);
     out.lens.resize(ptr.size() + 16);
+    if (want_ends) out.ends.resize(out.lens.size());
     uint64_t n = 0;
     auto room = [&]() {
-        if (n == out.lens.size()) { out.lens.resize(n + n / 2 + 64); out.words.resize(out.lens.size() * (size_t)stride); }
+        if (n == out.lens.size()) {
+            out.lens.resize(n + n / 2 + 64); out.words.resize(out.lens.size() * (size_t)stride);
+            if (want_ends) out.ends.resize(out.lens.size());
+        }
     };
-    auto emit = [&](const uint8_t* s, uint64_t l) {   // one record of l <= maxb ACGT symbols
+    auto emit = [&](const uint8_t* s, uint64_t l, uint8_t flags) {   // one record of l <= maxb ACGT symbols
         room();
+        if (want_ends) out.ends[n] = flags;
         uint32_t* w = out.words.data() + n * stride;
         uint64_t i = 0;
         for (uint32_t wi = 0; wi < stride; wi++) {
@@ -114,6 +122,7 @@ inline void pack_lines_t(const std::vector<const uint8_t*>& ptr, const std::vect
             }
             if (!(bad & 4u)) {
                 for (; wi < stride; wi++) w[wi] = 0u;
+                if (want_ends) out.ends[n] = 3;
                 out.lens[n++] = (uint16_t)l;
                 continue;
             }
@@ -124,10 +133,11 @@ inline void pack_lines_t(const std::vector<const uint8_t*>& ptr, const std::vect
             if (i == l || lut[s[i]] > 3 || (kQual && q[i] < thr)) {
                 const uint64_t rl = i - start;
                 if (rl >= (uint64_t)k) {
+                    const uint8_t flags = rl <= maxb ? (uint8_t)((start == 0 ? 1 : 0) | (i == l ? 2 : 0)) : (uint8_t)0;
                     uint64_t pos = 0;
                     for (;;) {
                         const uint64_t take = std::min(maxb, rl - pos);
-                        emit(s + start + pos, take);
+                        emit(s + start + pos, take, flags);
                         if (pos + take >= rl) break;
                         pos += take - (uint64_t)(k - 1);      // next chunk re-reads k-1 bases: no k-mer lost or doubled
                     }
@@ -139,27 +149,28 @@ inline void pack_lines_t(const std::vector<const uint8_t*>& ptr, const std::vect
     out.n_records = n;
     out.words.resize((size_t)n * stride);
     out.lens.resize((size_t)n);
+    if (want_ends) out.ends.resize((size_t)n);
 }
 
-inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out) {
-    pack_lines_t<false>(ptr, len, k, out, nullptr, 0);
+inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out, bool want_ends = false) {
+    pack_lines_t<false>(ptr, len, k, out, nullptr, 0, want_ends);
 }
 // The same with quality lines: min_qual > 0 packs the lines with every symbol whose quality byte is below '!' + min_qual
 // (Phred+33) replaced by N; 0 ignores `qual`.
 inline void pack_lines(const std::vector<const uint8_t*>& ptr, const std::vector<uint64_t>& len, int k, PackedBatch& out,
-                       const std::vector<const uint8_t*>& qual, int min_qual) {
+                       const std::vector<const uint8_t*>& qual, int min_qual, bool want_ends = false) {
     if (min_qual < 0 || min_qual > 93) throw std::invalid_argument("min_qual must be between 0 and 93 (Phred+33)");
-    if (min_qual > 0) pack_lines_t<true>(ptr, len, k, out, &qual, (uint8_t)('!' + min_qual));
-    else pack_lines_t<false>(ptr, len, k, out, nullptr, 0);
+    if (min_qual > 0) pack_lines_t<true>(ptr, len, k, out, &qual, (uint8_t)('!' + min_qual), want_ends);
+    else pack_lines_t<false>(ptr, len, k, out, nullptr, 0, want_ends);
 }
 
 class FastqPacker {
 public:
     // threads: parse / pack threads (and, for gzip input, as many inflate threads again: they take turns); min_qual > 0
     // (--min-base-qual): every base whose quality byte is below '!' + min_qual is packed as an N (pack_lines), and a quality line
-    // that is not as long as its sequence line is an error
-    FastqPacker(const std::string& path, int k, unsigned threads, int min_qual = 0)
-        : path_(path), k_(k), threads_(std::max(1u, threads)), min_qual_(min_qual) {
+    // that is not as long as its sequence line is an error; want_ends (--primers): the batches carry their records' end flags
+    FastqPacker(const std::string& path, int k, unsigned threads, int min_qual = 0, bool want_ends = false)
+        : path_(path), k_(k), threads_(std::max(1u, threads)), min_qual_(min_qual), want_ends_(want_ends) {
         if (min_qual < 0 || min_qual > 93) throw std::invalid_argument("min_qual must be between 0 and 93 (Phred+33)");
         struct stat st;
         const bool regular = ::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0;
@@ -312,7 +323,7 @@ private:
                     if (!tail.empty()) add(reinterpret_cast<const uint8_t*>(tail.data()), tail.size());
                 }
                 { std::unique_lock<std::mutex> lk(m_); if (!spare_.empty()) { j.out = std::move(spare_.back()); spare_.pop_back(); } }
-                pack_lines(ptr, len, k_, j.out);
+                pack_lines(ptr, len, k_, j.out, want_ends_);
             }
         } catch (const std::exception& e) { j.error = e.what(); }
         j.piece = pargz::Piece();   // (its buffer goes back to the pool)
@@ -376,7 +387,7 @@ private:
             add(r, ls, ln, split(t, tn, false, ls, ln));
         }
         { std::unique_lock<std::mutex> lk(m_); if (!spare_.empty()) { j.out = std::move(spare_.back()); spare_.pop_back(); } }
-        pack_lines(ptr, len, k_, j.out, qptr, min_qual_);
+        pack_lines(ptr, len, k_, j.out, qptr, min_qual_, want_ends_);
     }
 
     // ---- pieces in, jobs out ------------------------------------------------------------------------------------------------
@@ -494,9 +505,9 @@ private:
         if (qual) {
             std::vector<const uint8_t*> qptr(off_.size() - 1);
             for (size_t i = 0; i + 1 < off_.size(); i++) qptr[i] = reinterpret_cast<const uint8_t*>(qbuf_.data()) + off_[i];
-            pack_lines(ptr, len, k_, out, qptr, min_qual_);
+            pack_lines(ptr, len, k_, out, qptr, min_qual_, want_ends_);
         } else {
-            pack_lines(ptr, len, k_, out);
+            pack_lines(ptr, len, k_, out, want_ends_);
         }
         return true;
     }
@@ -505,6 +516,7 @@ private:
     int k_;
     unsigned threads_;
     int min_qual_;
+    bool want_ends_;
     std::unique_ptr<ParallelGunzip> gz_;
     std::unique_ptr<GzLineReader> lines_;
     int fd_ = -1;

@@ -271,6 +271,32 @@ int bk_kmer_dump_size(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_dist
 /* Copies min(cap, n_kept) entries, ascending by k-mer: MSB-first 2-bit codes (A=0 C=1 G=2 T=3), counts = min(count, cs). */
 int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* counts, uint64_t cap);
 
+/* ---- amplicon primers (`bronko call --primers`; additive, still v8) ---------------------------------------------
+ * n primers, each ACGT/acgt only, 12..64 bases, written 5'->3' as synthesised; at most 1024; max_mismatches 0..3 (BK_ERR_INVALID
+ * on a violation).  n = 0 clears them.  Between samples only (BK_ERR_STATE inside one).  Per engine: forks set their own.
+ * While primers are set, every read pushed is trimmed.  A letter is valid if it is ACGT/acgt (and, with min_qual, at or above
+ * the threshold); at the 5' end the longest primer P with Hamming(read[0:L], P) <= max_mismatches (case folded) that lies inside
+ * the read's leading run of valid letters is treated as N, at the 3' end the longest P whose reverse complement matches
+ * read[n-L:n] inside the trailing run; the 3' match is made on the read as pushed.  If both lie in one run and overlap, the whole
+ * read is N.  Only whole primers anchored at a read end match: no indels, no internal or partial occurrences, and none at the
+ * ends of a run so long that it is cut into several records.  Every result equals that of the same pushes, without primers, of
+ * the reads with those letters replaced by N. */
+int bk_primers_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, int max_mismatches);
+/* Packed records with their end flags, one byte a record: bit 0 = the record's first base is its read's first letter, bit 1 =
+ * its last base is its read's last letter (a chunk of a cut run carries neither); bk_pack_reads_flat_ends writes them.  With
+ * primers set the flag-less bk_push_reads_packed / _device return BK_ERR_STATE (their records would go untrimmed); with none
+ * set these behave as the plain calls and `ends` is not read.  The _device form trims a copy: the caller's records stay as
+ * they are. */
+int bk_push_reads_packed_ends(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends,
+                              uint64_t n_records);
+int bk_push_reads_packed_ends_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends,
+                                     uint64_t n_records);
+/* After bk_sample_finalize / _finish, until the engine's next bk_sample_begin (synchronises): out = {reads trimmed at the 5'
+ * end, reads trimmed at the 3' end, bases masked} of the mate file.  The counters are taken on the records: an end whose run
+ * of valid letters is shorter than k makes no record (it holds no k-mer, trimmed or not) and is not counted.  BK_ERR_STATE if
+ * no primers were set when the sample began. */
+int bk_primer_stats(bk_engine* e, int mate, uint64_t out[3]);
+
 /* ---- after the pileup, on the device (optional) ----------------------------------------------
  * For the sample just finalized, asynchronously on the engine's stream:
  *     pick_best_genome / pick_best_genome_paired   call.rs:422-502  (ties -> lowest file id; statistics summed over mates)
@@ -344,6 +370,9 @@ uint64_t bk_pack_reads(const uint8_t* const* reads, const uint64_t* read_lens, u
 /* Same for reads stored back to back in one buffer: read i = buf[offsets[i] .. offsets[i+1]) */
 uint64_t bk_pack_reads_flat(const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads, int32_t k,
                             uint32_t stride_words, uint32_t* out_words, uint16_t* out_lens, uint64_t cap_records);
+/* ... and the records' end flags (bk_push_reads_packed_ends), out_ends[cap_records] (may be null) */
+uint64_t bk_pack_reads_flat_ends(const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads, int32_t k,
+                                 uint32_t stride_words, uint32_t* out_words, uint16_t* out_lens, uint8_t* out_ends, uint64_t cap_records);
 
 /* ---- measurement ------------------------------------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by HIP events on the launch stream.  bk_timing_read
