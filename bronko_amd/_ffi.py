@@ -57,6 +57,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_sample_finalize_shard", "bk_shard_measure", "bk_shard_transport", "bk_shard_received", "bk_transport_overflow", "bk_shard_sums_device_ptr", "bk_sample_merge_shards", "bk_kmer_table_partition", "bk_kmer_table_replace",
            "bk_kmer_dump_enable", "bk_kmer_dump_size", "bk_kmer_dump_download",
            "bk_primers_set", "bk_push_reads_packed_ends", "bk_push_reads_packed_ends_device", "bk_primer_stats", "bk_pack_reads_flat_ends",
+           "bk_adapters_set", "bk_adapter_stats",
            "bk_pileup_device_ptr", "bk_sample_download", "bk_sample_finish", "bk_pack_reads", "bk_pack_reads_flat",
            "bk_timing_enable", "bk_timing_read", "bk_call_params_default", "bk_sample_call", "bk_sample_download_calls", "bk_sample_download_noise",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
@@ -164,6 +165,10 @@ def load(testing=None):
     L.bk_push_reads_packed_ends_device.argtypes = [vp, C.c_int, vp, u32, vp, vp, u64]
     L.bk_primer_stats.restype = C.c_int
     L.bk_primer_stats.argtypes = [vp, C.c_int, vp]
+    L.bk_adapters_set.restype = C.c_int
+    L.bk_adapters_set.argtypes = [vp, vp, vp, u32, u32, C.c_double]
+    L.bk_adapter_stats.restype = C.c_int
+    L.bk_adapter_stats.argtypes = [vp, C.c_int, vp]
     L.bk_call_params_default.argtypes = [C.POINTER(CallParams)]
     L.bk_sample_call.restype = C.c_int
     L.bk_sample_call.argtypes = [vp, C.c_int, C.POINTER(CallParams)]

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -283,6 +284,10 @@ int bk_sample_begin(bk_engine* e) {
     if (e->primers) {
         BK_HIP(hipMemsetAsync(e->primers->stats.p, 0, e->primers->stats.n * sizeof(unsigned long long), e->stream));
         e->primers->in_sample = true;
+    }
+    if (e->adapters) {
+        BK_HIP(hipMemsetAsync(e->adapters->stats.p, 0, e->adapters->stats.n * sizeof(unsigned long long), e->stream));
+        e->adapters->in_sample = true;
     }
     e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
@@ -634,33 +639,51 @@ struct PackGeom {
         : stride((uint32_t)std::min<uint64_t>((std::max<uint64_t>(longest, (uint64_t)k) + 15) / 16, 4095)),
           cap(n_reads + total / (uint64_t)k + total / (std::min<uint64_t>((uint64_t)stride * 16, 65535) - (uint64_t)(k - 1)) + 16) {}
 };
-// bk_primers_set: the primers come off the records that touch a read end (primer_trim_kernel, in place), on the engine stream
-// between the packer or the copy that made the records and everything that reads them
-static void trim_records(bk_engine* e, int mate, uint32_t* d_words, uint32_t stride_words, uint16_t* d_lens, const uint8_t* d_ends, uint64_t n,
-                         const unsigned long long* n_records_dev = nullptr) {
+// bk_adapters_set, bk_primers_set: the adapters, then the primers, come off the records that touch a read end (adapter_find_kernel
+// and adapter_trim_kernel, primer_trim_kernel: in place), on the engine stream between the packer or the copy that made the records
+// and everything that reads them
+static int trim_records(bk_engine* e, int mate, uint32_t* d_words, uint32_t stride_words, uint16_t* d_lens, const uint8_t* d_ends, uint64_t n,
+                        const unsigned long long* n_records_dev = nullptr) {
+    if (e->adapters) {
+        Adapters& ad = *e->adapters;
+        if (ad.cut.n < n) {   // (the kernels leave kNoCut everywhere: filled once per allocation)
+            BK_HIP(hipStreamSynchronize(e->stream));
+            BK_HIP(ad.cut.alloc(n + n / 4));
+            BK_HIP(hipMemsetAsync(ad.cut.p, 0xFF, ad.cut.n * sizeof(uint32_t), e->stream));
+        }
+        bk_engine::Span sp(e, 2);
+        bk::AdapterArgs t{};
+        t.words = d_words; t.lens = d_lens; t.ends = d_ends; t.cut = ad.cut.p; t.n_records = n; t.n_records_dev = n_records_dev;
+        t.stride_words = stride_words; t.k = e->ix->k; t.n_adapters = ad.n; t.min_overlap = ad.min_overlap; t.allowed_steps = ad.allowed_steps;
+        t.stats = ad.stats.p + mate * 2; t.n_real = e->kstats.p + mate * 4 + 0;
+        std::copy(ad.entry, ad.entry + bk::kMaxAdapters, t.adapters);
+        bk::launch_adapter_trim(t, e->ix->n_cus, e->stream);
+    }
+    if (!e->primers) return BK_OK;
     bk_engine::Span sp(e, 2);
     bk::TrimArgs t{};
     t.words = d_words; t.lens = d_lens; t.ends = d_ends; t.n_records = n; t.n_records_dev = n_records_dev; t.stride_words = stride_words;
     t.k = e->ix->k; t.table = e->primers->table.p; t.n_primers = e->primers->n; t.max_mismatches = e->primers->max_mismatches;
     t.stats = e->primers->stats.p + mate * 3; t.n_real = e->kstats.p + mate * 4 + 0;
     bk::launch_primer_trim(t, e->ix->n_cus, e->stream);
+    return BK_OK;
 }
 
 // the packer (records pushed: tallied on the device) into the slot's record buffers, then the push of those records
-// (q: the quality lines and threshold of a bk_push_reads_ascii_qual* batch, or null); with primers set the packer also writes the
-// records' end flags and the primers are trimmed in between
+// (q: the quality lines and threshold of a bk_push_reads_ascii_qual* batch, or null); with primers or adapters set the packer also
+// writes the records' end flags and the records are trimmed in between
 static int pack_and_push(bk_engine* e, int mate, bk_engine::IngestSlot& sl, const uint8_t* bases, uint32_t shift, const unsigned long long* offsets,
                          uint64_t n_reads, uint64_t total, PackGeom g, const bk::QualArgs* q = nullptr) {
     bk::PackArgs pa{};
     pa.shift = shift; pa.bases = bases; pa.offsets = offsets; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = g.stride;
     pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = g.cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
     uint8_t* ends = nullptr;
-    if (e->primers) {
+    if (e->trims()) {
         if (sl.d_ends.n < g.cap) { BK_HIP(hipStreamSynchronize(e->stream)); BK_HIP(sl.d_ends.alloc(g.cap + g.cap / 4)); }
         ends = sl.d_ends.p;
     }
     { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream, q, ends); }
-    if (ends) trim_records(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, ends, g.cap, sl.d_nrec.p);
+    if (ends) { if (int rc = trim_records(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, ends, g.cap, sl.d_nrec.p); rc != BK_OK) return rc; }
     return push_device(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, g.cap, sl.d_nrec.p, total);   // (a batch holds fewer k-mers than bases)
 }
 
@@ -772,16 +795,18 @@ int bk_push_reads_ascii_qual_device(bk_engine* e, int mate, const void* d_bases,
     return push_ascii_device(e, mate, d_bases, d_quals, d_offsets, n_reads, total_bases, longest_read, (uint32_t)('!' + min_qual));
 }
 
-// the packed pushes: `ends` null (the plain calls: refused while primers are set, since those records would go untrimmed) or the
-// records' end flags (read only while primers are set)
-static int no_end_flags(const char* fn) {
+// the packed pushes: `ends` null (the plain calls: refused while primers or adapters are set, since those records would go
+// untrimmed) or the records' end flags (read only while primers or adapters are set)
+static int no_end_flags(const bk_engine* e, const char* fn) {
+    if (!e->primers) return fail(BK_ERR_STATE, "%s: adapters are set (bk_adapters_set) and these records carry no end flags: push them with %s_ends", fn, fn);
+    if (e->adapters) return fail(BK_ERR_STATE, "%s: primers and adapters are set (bk_primers_set, bk_adapters_set) and these records carry no end flags: push them with %s_ends", fn, fn);
     return fail(BK_ERR_STATE, "%s: primers are set (bk_primers_set) and these records carry no end flags: push them with %s_ends", fn, fn);
 }
 
 static int push_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends, uint64_t n) {
     if (int rc = packed_checks(e, mate, d_words, stride_words, d_lens, n); rc != kPush) return rc;
-    if (!e->primers) return push_device(e, mate, static_cast<const uint32_t*>(d_words), stride_words, static_cast<const uint16_t*>(d_lens), n);
-    if (!d_ends) return no_end_flags("bk_push_reads_packed_device");
+    if (!e->trims()) return push_device(e, mate, static_cast<const uint32_t*>(d_words), stride_words, static_cast<const uint16_t*>(d_lens), n);
+    if (!d_ends) return no_end_flags(e, "bk_push_reads_packed_device");
     // the caller's records are not the engine's to rewrite: they are trimmed in a copy (the buffers of bk_push_reads_ascii_device:
     // everything that uses them is ordered by the engine's stream)
     bk_engine::IngestSlot& sl = e->dev_ascii;
@@ -793,7 +818,7 @@ static int push_packed_device(bk_engine* e, int mate, const void* d_words, uint3
     }
     BK_HIP(hipMemcpyAsync(sl.d_words.p, d_words, nw * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
     BK_HIP(hipMemcpyAsync(sl.d_lens.p, d_lens, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToDevice, e->stream));
-    trim_records(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, static_cast<const uint8_t*>(d_ends), n);
+    if (int rc = trim_records(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, static_cast<const uint8_t*>(d_ends), n); rc != BK_OK) return rc;
     return push_device(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, n);
 }
 
@@ -803,14 +828,14 @@ int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uin
 
 int bk_push_reads_packed_ends_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends,
                                      uint64_t n) {
-    if (e && e->primers && !d_ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
+    if (e && e->trims() && !d_ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
     return push_packed_device(e, mate, d_words, stride_words, d_lens, d_ends, n);
 }
 
 static int push_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends, uint64_t n) {
     if (int rc = packed_checks(e, mate, words, stride_words, lens, n); rc != kPush) return rc;
-    if (e->primers && !ends) return no_end_flags("bk_push_reads_packed");
-    if (!e->primers) ends = nullptr;
+    if (e->trims() && !ends) return no_end_flags(e, "bk_push_reads_packed");
+    if (!e->trims()) ends = nullptr;
     const size_t nw = (size_t)n * stride_words;
     bk_engine::StageSlot& sl = e->stage[e->next_stage];
     e->next_stage ^= 1;
@@ -837,7 +862,7 @@ static int push_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t s
         BK_HIP(hipMemcpyAsync(sl.lens.p, sl.h + bytes_w, bytes_l, hipMemcpyHostToDevice, e->stream));
         if (ends) BK_HIP(hipMemcpyAsync(sl.ends.p, sl.h + bytes_w + bytes_l, bytes_e, hipMemcpyHostToDevice, e->stream));
     }
-    if (ends) trim_records(e, mate, sl.words.p, stride_words, sl.lens.p, sl.ends.p, n);
+    if (ends) { if (int rc = trim_records(e, mate, sl.words.p, stride_words, sl.lens.p, sl.ends.p, n); rc != BK_OK) return rc; }
     int rc = push_device(e, mate, sl.words.p, stride_words, sl.lens.p, n);
     if (rc != BK_OK) return rc;
     BK_HIP(hipEventRecord(sl.done, e->stream));
@@ -852,7 +877,7 @@ int bk_push_reads_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t
 
 int bk_push_reads_packed_ends(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends,
                               uint64_t n) {
-    if (e && e->primers && !ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
+    if (e && e->trims() && !ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
     return push_packed(e, mate, words, stride_words, lens, ends, n);
 }
 
@@ -1348,6 +1373,66 @@ int bk_primer_stats(bk_engine* e, int mate, uint64_t out[3]) {
     BK_HIP(hipMemcpyAsync(o, e->primers->stats.p + mate * 3, sizeof o, hipMemcpyDeviceToHost, e->stream));
     BK_HIP(hipStreamSynchronize(e->stream));
     for (int i = 0; i < 3; i++) out[i] = o[i];
+    return BK_OK;
+}
+
+// ---- 3' adapters (bk_adapters.hip) ----------------------------------------------------------------------------------
+int bk_adapters_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, uint32_t min_overlap, double max_error_rate) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_adapters_set comes between samples");
+    if (n > bk::kMaxAdapters) return fail(BK_ERR_INVALID, "%u adapters: at most %u", n, bk::kMaxAdapters);
+    if (n && (!seqs || !lens)) return fail(BK_ERR_INVALID, "null argument");
+    std::unique_ptr<Adapters> ad(new Adapters());
+    if (n) {
+        if (!(max_error_rate >= 0.0 && max_error_rate <= bk::kAdapterMaxErrorRate))
+            return fail(BK_ERR_INVALID, "max_error_rate must be between 0 and %g, got %g", bk::kAdapterMaxErrorRate, max_error_rate);
+        uint32_t shortest = bk::kAdapterMaxLen;
+        for (uint32_t a = 0; a < n; a++) {
+            const uint32_t L = lens[a];
+            if (L < bk::kAdapterMinLen || L > bk::kAdapterMaxLen)
+                return fail(BK_ERR_INVALID, "adapter %u: %u bases (an adapter has %u to %u)", a + 1, L, bk::kAdapterMinLen, bk::kAdapterMaxLen);
+            if (!seqs[a]) return fail(BK_ERR_INVALID, "adapter %u: null sequence", a + 1);
+            bk::AdapterEntry& t = ad->entry[a];
+            for (uint32_t i = 0; i < L; i++) {
+                const int c = bronko::acgt_code(seqs[a][i]);
+                if (c < 0) return fail(BK_ERR_INVALID, "adapter %u: symbol %u is not one of ACGT/acgt", a + 1, i + 1);
+                t.code[i >> 4] |= (uint32_t)c << (2 * (i & 15));
+                t.mask[i >> 4] |= 1u << (2 * (i & 15));
+            }
+            t.len = L;
+            t.allowed = (uint32_t)std::floor(max_error_rate * (double)L);
+            shortest = std::min(shortest, L);
+        }
+        if (min_overlap < bk::kAdapterMinOverlap || min_overlap > shortest)
+            return fail(BK_ERR_INVALID, "min_overlap must be between %u and the shortest adapter's %u bases, got %u", bk::kAdapterMinOverlap, shortest, min_overlap);
+        uint32_t prev = 0;   // floor(E * l), l = 1..64, as its steps (bk::AdapterArgs::allowed_steps)
+        for (uint32_t l = 1; l <= bk::kAdapterMaxLen; l++) {
+            const uint32_t al = (uint32_t)std::floor(max_error_rate * (double)l);
+            if (al > prev) ad->allowed_steps |= 1ull << (l - 1);
+            prev = al;
+        }
+        ad->n = n; ad->min_overlap = min_overlap;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
+    e->adapters.reset();
+    if (n == 0) return BK_OK;
+    BK_HIP(ad->stats.alloc(4));
+    BK_HIP(hipMemset(ad->stats.p, 0, 4 * sizeof(unsigned long long)));
+    e->adapters = std::move(ad);
+    return BK_OK;
+}
+
+int bk_adapter_stats(bk_engine* e, int mate, uint64_t out[2]) {
+    if (!e || !out) return fail(BK_ERR_INVALID, "null argument");
+    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
+    if (!e->adapters || !e->adapters->in_sample) return fail(BK_ERR_STATE, "no adapters were set for this sample (bk_adapters_set before bk_sample_begin)");
+    if (e->in_sample) return fail(BK_ERR_STATE, "the adapter counters are read after bk_sample_finalize");
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long o[2];
+    BK_HIP(hipMemcpyAsync(o, e->adapters->stats.p + mate * 2, sizeof o, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < 2; i++) out[i] = o[i];
     return BK_OK;
 }
 

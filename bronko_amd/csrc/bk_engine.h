@@ -155,6 +155,17 @@ struct Primers {
     bool in_sample = false;                 // set when the current / last sample began
 };
 
+// bk_adapters_set: the adapter table as the kernels take it (bk_adapters.hip), the per-record scratch and the sample's counters
+struct Adapters {
+    bk::AdapterEntry entry[bk::kMaxAdapters];
+    uint32_t n = 0;
+    uint32_t min_overlap = 0;
+    uint64_t allowed_steps = 0;             // bk::AdapterArgs::allowed_steps
+    DevBuf<uint32_t> cut;                   // [records of the largest batch so far] bk::kNoCut between launches
+    DevBuf<unsigned long long> stats;       // [2][2] per mate file: reads cut, bases removed (zeroed by bk_sample_begin)
+    bool in_sample = false;                 // set when the current / last sample began
+};
+
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
 // by an engine and its forks, freed with the last of them.
 struct IndexTables {
@@ -288,6 +299,8 @@ struct bk_engine {
     DevBuf<unsigned int> xchg_cnt;
     bool ktab_exchanged = false;            // bk_kmer_table_replace was called in this sample
     std::unique_ptr<Primers> primers;       // bk_primers_set (null: no primers, no launch, no end flags)
+    std::unique_ptr<Adapters> adapters;     // bk_adapters_set (null: no adapters, no launch; end flags only if primers are set)
+    bool trims() const { return primers || adapters; }   // the records' end flags are wanted
     std::unique_ptr<KmerDump> dump;         // bk_kmer_dump_enable (null: no table, no launch)
     // gathered votes (bk_gather.hip): this engine's voting pass is gather_votes_kernel (sparse planes of a many-genome index)
     bool gather_mode = false;
@@ -323,7 +336,7 @@ struct bk_engine {
     // bk_push_reads_packed: two staging slots, so that the copy of a batch overlaps the scan of the previous one
     struct StageSlot {
         DevBuf<uint32_t> words; DevBuf<uint16_t> lens;
-        DevBuf<uint8_t> ends;                       // bk_push_reads_packed_ends with primers set: the records' end flags
+        DevBuf<uint8_t> ends;                       // bk_push_reads_packed_ends with primers or adapters set: the records' end flags
         uint8_t* h = nullptr; size_t h_cap = 0;     // pinned host copy of the caller's batch (words, then lens, then end flags)
         hipEvent_t done = nullptr; bool busy = false;
     } stage[2];
@@ -340,7 +353,7 @@ struct bk_engine {
         DevBuf<uint32_t> d_work;           // pack_words_kernel's work list
         DevBuf<uint32_t> d_words;
         DevBuf<uint16_t> d_lens;
-        DevBuf<uint8_t> d_ends;            // primers set: the records' end flags (the *_ends_kernel variants of K0)
+        DevBuf<uint8_t> d_ends;            // primers or adapters set: the records' end flags (the *_ends_kernel variants of K0)
         hipEvent_t uploaded = nullptr, done = nullptr;
         bool busy = false;
     };

@@ -255,6 +255,40 @@ struct TrimArgs {
     unsigned long long* n_real;     // the sample's tally of records that hold a run: -= records left with fewer than k bases
 };
 void launch_primer_trim(const TrimArgs& a, int n_cus, hipStream_t stream);
+
+// ---- 3' adapter trimming (bk_adapters.hip) ----
+// (the limits of include/bronko_hip.h)
+constexpr uint32_t kAdapterMinLen = BK_ADAPTER_MIN_LEN, kAdapterMaxLen = BK_ADAPTER_MAX_LEN, kMaxAdapters = BK_MAX_ADAPTERS,
+                   kAdapterMinOverlap = BK_ADAPTER_MIN_OVERLAP;
+constexpr double kAdapterMaxErrorRate = BK_ADAPTER_MAX_ERROR_RATE;
+static_assert(kAdapterMaxLen == 64 && kMaxAdapters <= 8, "AdapterEntry holds 64 bases, AdapterArgs eight entries");
+constexpr uint32_t kNoCut = 0xFFFFFFFFu;   // cut[r]: no adapter found in record r
+// The adapter table travels as kernel arguments (it is the same for every lane: scalar registers, no LDS, no table in memory).
+struct AdapterEntry {
+    uint32_t code[4];               // the adapter's 2-bit codes at bases [0, len); unused bits 0
+    uint32_t mask[4];               // the even bits of bases [0, len)
+    uint32_t len;                   // 8..64
+    uint32_t allowed;               // floor(E * len): mismatches the whole adapter may have
+};
+struct AdapterArgs {
+    uint32_t* words;                // [n_records][stride_words], cut in place
+    uint16_t* lens;                 // [n_records]
+    const uint8_t* ends;            // [n_records] end flags: only records with kEndLast are searched
+    uint32_t* cut;                  // [n_records] scratch, kNoCut everywhere before and after: the leftmost match of each record
+    uint64_t n_records;
+    const unsigned long long* n_records_dev;   // null, or the device's count of record slots in use (K0)
+    uint32_t stride_words;
+    int32_t k;
+    uint32_t n_adapters;
+    uint32_t min_overlap;
+    // floor(E * l) for l = 1..64, as the host computed it in double: it starts at 0 and grows by 0 or 1 a step (E < 1), so it
+    // is held as its steps -- bit l - 1 set where allowed[l] = allowed[l - 1] + 1 -- and allowed[l] = popcount of the low l bits
+    uint64_t allowed_steps;
+    unsigned long long* stats;      // [2] += reads cut, bases removed
+    unsigned long long* n_real;     // the sample's tally of records that hold a run: -= records left with fewer than k bases
+    AdapterEntry adapters[kMaxAdapters];
+};
+void launch_adapter_trim(const AdapterArgs& a, int n_cus, hipStream_t stream);
 // votes[f] += number of the first records' middle k-mers that occur in genome file f (which genome does the sample look like?)
 void launch_pick_window(const ScanArgs& a, uint64_t n_probe, unsigned int* votes, const uint32_t* file_cell_lo, int forced, uint32_t* win,
                         hipStream_t stream);

@@ -223,6 +223,20 @@ class Engine:
         _check(self._L.bk_primer_stats(self.h, mate, out.ctypes.data), self._L)
         return out.tolist()
 
+    def adapters_set(self, adapters, min_overlap=5, max_error_rate=0.1):
+        """bk_adapters_set: 3' adapters (bytes, 5'->3' as they appear in a read) cut off every read pushed from now on; [] clears them."""
+        adapters = [bytes(a) for a in adapters]
+        bufs = [C.create_string_buffer(a, max(len(a), 1)) for a in adapters]
+        ptrs = (C.c_void_p * max(len(bufs), 1))(*[C.addressof(b) for b in bufs])
+        lens = np.array([len(a) for a in adapters] + [0], np.uint32)
+        _check(self._L.bk_adapters_set(self.h, C.addressof(ptrs), lens.ctypes.data, len(adapters), min_overlap, max_error_rate), self._L)
+
+    def adapter_stats(self, mate):
+        """bk_adapter_stats: [reads cut, bases removed] of the sample just finalized."""
+        out = np.zeros(2, np.uint64)
+        _check(self._L.bk_adapter_stats(self.h, mate, out.ctypes.data), self._L)
+        return out.tolist()
+
     def push_reads_ends(self, mate, words, lens, ends):
         """bk_push_reads_packed_ends: packed records with their end flags (pack_reads_ends)."""
         words = np.ascontiguousarray(words, np.uint32)

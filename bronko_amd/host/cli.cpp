@@ -102,6 +102,10 @@ struct Args {
     std::string primers;            // --primers: FASTA of amplicon primers trimmed from the read ends (empty: none)
     bool has_primers = false, has_primer_mismatches = false;
     long primer_mismatches = 1;     // --primer-mismatches: Hamming distance a primer match may have (0..3)
+    std::vector<std::string> adapters;   // --adapter: 3' adapters cut off the reads, preset names or sequences (empty: none)
+    bool has_adapter_min_overlap = false, has_adapter_error_rate = false;
+    long adapter_min_overlap = 5;   // --adapter-min-overlap: bases of an adapter's start that count as a match at the read's end
+    double adapter_error_rate = 0.1;   // --adapter-error-rate: mismatches allowed per compared base (0..0.3)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -118,14 +122,19 @@ struct Args {
           "            [--no-strand-balance-filter] [--balance-ratio F] [--n-per-strand N] [--strand_odds F]\n"
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
-          "            [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
           "                    are counted; 0..93, default 0 (off)\n"
           "  --primers FASTA   treat amplicon primers at the read ends as N: a primer (ACGT, 12..64 bases, at most 1024 of them) that\n"
           "                    lies whole at a read's 5' end, or whose reverse complement lies whole at its 3' end\n"
-          "  --primer-mismatches M  mismatches a primer match may have (no indels); 0..3, default 1\n", stderr);
+          "  --primer-mismatches M  mismatches a primer match may have (no indels); 0..3, default 1\n"
+          "  --adapter SEQ...  cut 3' sequencing adapters off the reads, before the primers: each SEQ is truseq (AGATCGGAAGAGC), nextera\n"
+          "                    (CTGTCTCTTATACACATCT) or a sequence (ACGT, 8..64 bases), at most 8; a read is truncated at the leftmost\n"
+          "                    place of its last run of valid letters where an adapter, or at the read's end its start, matches\n"
+          "  --adapter-min-overlap N  bases of an adapter's start that match at a read's end; 3..the shortest adapter, default 5\n"
+          "  --adapter-error-rate F   mismatches allowed per compared base (floor(F * length), no indels); 0..0.3, default 0.1\n", stderr);
     exit(code);
 }
 
@@ -223,6 +232,15 @@ Args parse_args(int argc, char** argv) {
             a.has_primer_mismatches = true;
             if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
         }
+        else if (opt == "--adapter") many(a.adapters);
+        else if (opt == "--adapter-min-overlap") {   // (any integer, any number here: what is out of range is refused by check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            a.adapter_min_overlap = strtol(v.c_str(), &end, 10);
+            a.has_adapter_min_overlap = true;
+            if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+        }
+        else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
     return a;
@@ -326,6 +344,41 @@ std::vector<std::string> read_primers(const char* T, const std::string& path) {
     return out;
 }
 
+// --adapter: preset names expanded, every sequence and both parameters checked against what bk_adapters_set takes
+std::vector<std::string> g_adapters;   // (set by check_call_args)
+uint32_t g_adapter_min_overlap = 5;
+double g_adapter_error_rate = 0.1;
+std::vector<std::string> expand_adapters(const char* T, const Args& a) {
+    constexpr size_t kMinLen = BK_ADAPTER_MIN_LEN, kMaxLen = BK_ADAPTER_MAX_LEN, kMaxAdapters = BK_MAX_ADAPTERS;   // (bk_adapters_set's limits)
+    constexpr long kMinOverlap = BK_ADAPTER_MIN_OVERLAP;
+    constexpr double kMaxErrorRate = BK_ADAPTER_MAX_ERROR_RATE;
+    std::vector<std::string> out;
+    if (a.adapters.size() > kMaxAdapters) die(T, "--adapter: " + std::to_string(a.adapters.size()) + " adapters, at most " + std::to_string(kMaxAdapters) + " are supported");
+    size_t shortest = kMaxLen;
+    for (size_t i = 0; i < a.adapters.size(); i++) {
+        std::string s = a.adapters[i];
+        const std::string where = "--adapter: adapter " + std::to_string(i + 1) + " (" + s + ")";
+        if (s == "truseq") s = "AGATCGGAAGAGC";
+        else if (s == "nextera") s = "CTGTCTCTTATACACATCT";
+        for (size_t j = 0; j < s.size(); j++)
+            if (!strchr("ACGTacgt", s[j]))
+                die(T, where + ": symbol '" + std::string(1, s[j]) + "' at position " + std::to_string(j + 1) + " is not one of ACGT (the presets are truseq and nextera; degenerate adapters are not supported)");
+        if (s.size() < kMinLen || s.size() > kMaxLen)
+            die(T, where + ": adapter of " + std::to_string(s.size()) + " bases, must be between " + std::to_string(kMinLen) + " and " + std::to_string(kMaxLen));
+        LOG_DEBUG(T, "adapter " + std::to_string(i + 1) + ": " + s);
+        shortest = std::min(shortest, s.size());
+        out.push_back(s);
+    }
+    if (a.adapter_min_overlap < kMinOverlap || (size_t)a.adapter_min_overlap > shortest)
+        die(T, "Adapter minimum overlap must be between " + std::to_string(kMinOverlap) + " and the shortest adapter's length (" + std::to_string(shortest) + "), got " + std::to_string(a.adapter_min_overlap));
+    if (!(a.adapter_error_rate >= 0.0 && a.adapter_error_rate <= kMaxErrorRate)) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "Adapter error rate must be between 0 and %g, got %g", kMaxErrorRate, a.adapter_error_rate);
+        die(T, buf);
+    }
+    return out;
+}
+
 void check_call_args(const Args& a) {   // call.rs:30-136
     const char* T = "bronko::call";
     if (a.kmer % 2 != 1 || a.kmer > 31 || a.kmer < 15) die(T, "Invalid kmer size, must be odd and between [15-31]");
@@ -353,6 +406,9 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.has_primer_mismatches && !a.has_primers) die(T, "--primer-mismatches needs --primers");
     if (a.primer_mismatches < 0 || a.primer_mismatches > 3) die(T, "Primer mismatches must be between 0 and 3, got " + std::to_string(a.primer_mismatches));
     if (a.has_primers) { g_primers = read_primers(T, a.primers); g_primer_mismatches = (int)a.primer_mismatches; }
+    if (a.has_adapter_min_overlap && a.adapters.empty()) die(T, "--adapter-min-overlap needs --adapter");
+    if (a.has_adapter_error_rate && a.adapters.empty()) die(T, "--adapter-error-rate needs --adapter");
+    if (!a.adapters.empty()) { g_adapters = expand_adapters(T, a); g_adapter_min_overlap = (uint32_t)a.adapter_min_overlap; g_adapter_error_rate = a.adapter_error_rate; }
 }
 
 struct Engine {
@@ -372,7 +428,7 @@ struct FastqBatch {
     std::string buf; std::vector<uint64_t> off{0};   // sequence lines back to back (the line loop: streams, one thread) ...
     std::string qual;                                // (--min-base-qual) ... and their quality lines, at the same offsets
     PackedBatch packed; bool is_packed = false;      // ... or 2-bit records, parsed and packed on several threads (fastq_pack.hpp;
-                                                     // --primers: with their end flags)
+                                                     // --primers, --adapter: with their end flags)
     bool last = false; std::string error;
     size_t bytes() const { return is_packed ? packed.bytes() : buf.size() + qual.size(); }
 };
@@ -463,7 +519,7 @@ void parse_fastq(const std::string& path, BatchQueue& out, unsigned inflate_thre
             // a few MB of text make a piece, pieces are gathered into batches of a quarter of a million records (a scan launch has
             // a fixed cost: small pushes are slow pushes)
             constexpr uint64_t kBatchRecords = 1u << 18;
-            FastqPacker in(path, g_kmer, inflate_threads, g_min_qual, !g_primers.empty());
+            FastqPacker in(path, g_kmer, inflate_threads, g_min_qual, !g_primers.empty() || !g_adapters.empty());
             PackedBatch b;
             cur.is_packed = true;
             while (in.next(b)) {
@@ -635,7 +691,7 @@ uint64_t push_fastqs(const std::vector<bk_engine*>& engs, const std::vector<std:
             FastqBatch b = queues[m].take();
             if (!b.error.empty() && error.empty()) error = b.error;
             if (error.empty() && b.is_packed) {
-                if (b.packed.n_records && !g_primers.empty())
+                if (b.packed.n_records && (!g_primers.empty() || !g_adapters.empty()))
                     hip_check(bk_push_reads_packed_ends(engs[n_batches++ % engs.size()], (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(),
                                                         b.packed.ends.data(), b.packed.n_records), "bk_push_reads_packed_ends");
                 else if (b.packed.n_records)
@@ -1016,6 +1072,26 @@ int run_call(const Args& a) {
                              std::to_string(sum[2]) + " bases masked in " + mates[m]);
         }
     };
+    // --adapter: the same for the adapters
+    auto set_adapters = [&](bk_engine* e) {
+        if (g_adapters.empty() || !e) return;
+        std::vector<const uint8_t*> seqs;
+        std::vector<uint32_t> lens;
+        for (const auto& p : g_adapters) { seqs.push_back(reinterpret_cast<const uint8_t*>(p.data())); lens.push_back((uint32_t)p.size()); }
+        hip_check(bk_adapters_set(e, seqs.data(), lens.data(), (uint32_t)seqs.size(), g_adapter_min_overlap, g_adapter_error_rate), "bk_adapters_set");
+    };
+    auto log_adapter_stats = [&](const std::vector<bk_engine*>& engs, const std::vector<std::string>& mates) {
+        if (g_adapters.empty() || g_level < 4) return;
+        for (size_t m = 0; m < mates.size(); m++) {
+            uint64_t sum[2] = {0, 0};
+            for (bk_engine* e : engs) {
+                uint64_t o[2];
+                hip_check(bk_adapter_stats(e, (int)m, o), "bk_adapter_stats");
+                for (int i = 0; i < 2; i++) sum[i] += o[i];
+            }
+            LOG_TRACE(T, "adapters: " + std::to_string(sum[0]) + " reads cut, " + std::to_string(sum[1]) + " bases removed in " + mates[m]);
+        }
+    };
     constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
     const int dump_threads = (int)std::max<size_t>(1, std::min<size_t>(16, (size_t)a.threads / std::max<size_t>(1, lanes.size())));
     auto complete = [&](bk_engine* e, const std::vector<std::string>& mates, size_t sample_id, bool finalized = false) {
@@ -1027,7 +1103,7 @@ int run_call(const Args& a) {
         // finalize, then reference selection + baseline noise + variant calls, all on the device and asynchronous
         // (bk_sample_call); the pileup arrays only travel when --pileup wants them written
         if (!finalized) hip_check(bk_sample_finalize(e, n_mates), "bk_sample_finalize");   // (a sharded sample: sharded_finalize has done it)
-        if (!finalized) log_primer_stats(std::vector<bk_engine*>{e}, mates);
+        if (!finalized) { log_adapter_stats(std::vector<bk_engine*>{e}, mates); log_primer_stats(std::vector<bk_engine*>{e}, mates); }
         bk_call_params dcp;
         bk_call_params_default(&dcp);
         dcp.k = cp.k; dcp.no_end_filter = cp.no_end_filter; dcp.no_strand_filter = cp.no_strand_filter;
@@ -1113,12 +1189,13 @@ int run_call(const Args& a) {
     };
 
     if (shard_mode) {
-        for (bk_engine* e : shards.engs) set_primers(e);
+        for (bk_engine* e : shards.engs) { set_adapters(e); set_primers(e); }
         for (size_t i = 0; i < samples.size(); i++) {
             const auto& mates = samples[i];
             LOG_INFO(T, mates.size() == 1 ? "Processing " + mates[0] : "Processing paired reads " + mates[0] + ", " + mates[1]);
             ingest(shards.engs, mates, i);
             sharded_finalize(shards, (int)mates.size(), cells4);
+            log_adapter_stats(shards.engs, mates);
             log_primer_stats(shards.engs, mates);
             complete(shards.engs[0], mates, i, true);
         }
@@ -1128,7 +1205,7 @@ int run_call(const Args& a) {
     for (size_t i = 0; i < samples.size() && !lanes.empty(); i++) lanes[i % lanes.size()].mine.push_back(i);
     auto run_lane = [&](Lane& ln) {
         if (ln.mine.size() > 1) hip_check(bk_engine_fork(ln.eng.e, &ln.fork.e), "bk_engine_fork");
-        for (bk_engine* e : {ln.eng.e, ln.fork.e}) set_primers(e);
+        for (bk_engine* e : {ln.eng.e, ln.fork.e}) { set_adapters(e); set_primers(e); }
         if (a.keep_kmer_info)   // (the table grows with the sample)
             for (bk_engine* e : {ln.eng.e, ln.fork.e})
                 if (e) hip_check(bk_kmer_dump_enable(e, kDumpTableLog2), "bk_kmer_dump_enable");

@@ -41,7 +41,7 @@ namespace bronko {
 struct PackedBatch {
     std::vector<uint32_t> words;   // [n_records][stride]
     std::vector<uint16_t> lens;    // [n_records]
-    std::vector<uint8_t> ends;     // [n_records] end flags (bk_push_reads_packed_ends), filled only for a reader asked for them (--primers)
+    std::vector<uint8_t> ends;     // [n_records] end flags (bk_push_reads_packed_ends), filled only for a reader asked for them (--primers, --adapter)
     uint32_t stride = 0;
     uint64_t n_records = 0, n_reads = 0;   // records packed; sequence lines seen (a read with an N is several records, a short one none)
     size_t bytes() const { return words.size() * 4 + lens.size() * 2 + ends.size(); }

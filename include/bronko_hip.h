@@ -284,8 +284,8 @@ int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* cou
 int bk_primers_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, int max_mismatches);
 /* Packed records with their end flags, one byte a record: bit 0 = the record's first base is its read's first letter, bit 1 =
  * its last base is its read's last letter (a chunk of a cut run carries neither); bk_pack_reads_flat_ends writes them.  With
- * primers set the flag-less bk_push_reads_packed / _device return BK_ERR_STATE (their records would go untrimmed); with none
- * set these behave as the plain calls and `ends` is not read.  The _device form trims a copy: the caller's records stay as
+ * primers or adapters set the flag-less bk_push_reads_packed / _device return BK_ERR_STATE (their records would go untrimmed);
+ * with neither set these behave as the plain calls and `ends` is not read.  The _device form trims a copy: the caller's records stay as
  * they are. */
 int bk_push_reads_packed_ends(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends,
                               uint64_t n_records);
@@ -296,6 +296,31 @@ int bk_push_reads_packed_ends_device(bk_engine* e, int mate, const void* d_words
  * of valid letters is shorter than k makes no record (it holds no k-mer, trimmed or not) and is not counted.  BK_ERR_STATE if
  * no primers were set when the sample began. */
 int bk_primer_stats(bk_engine* e, int mate, uint64_t out[3]);
+
+/* ---- 3' sequencing adapters (`bronko call --adapter`; additive, still v8) -----------------------------------------
+ * n adapters, each ACGT/acgt only, 8..64 bases, written 5'->3' as they appear in a read that runs through its insert; at most 8;
+ * min_overlap O: 3 .. the shortest adapter; max_error_rate E: 0 .. 0.3 (BK_ERR_INVALID on a violation, with the adapter or the
+ * parameter named).  n = 0 clears them.  Between samples only (BK_ERR_STATE inside one).  Per engine: forks set their own.
+ * While adapters are set, every read pushed is cut.  With R = the read's maximal suffix of valid letters (valid as for the
+ * primers), r its length and s1 its start: a position p, 0 <= p <= r - O, matches an adapter A of LA bases when, with
+ * l = min(LA, r - p), Hamming(R[p : p + l], A[0 : l]) <= floor(E * l) (case folded; the floor of the product in double): the
+ * whole adapter anywhere in R, or a prefix of at least O bases at R's end.  The read is truncated to s1 + p letters for the
+ * smallest matching p over all adapters.  Substitutions only, no indels; the leftmost match wins, not the best; nothing in
+ * front of R (an adapter before an N or a masked base) is found; a run so long that it is cut into several records is left as
+ * it is.  The cut is made after quality masking and before the primers, which see the truncated read.  Every result equals
+ * that of the same pushes, without adapters, of the truncated reads.
+ * The records' end flags are needed as for the primers: with adapters set the flag-less bk_push_reads_packed / _device return
+ * BK_ERR_STATE. */
+#define BK_ADAPTER_MIN_LEN 8
+#define BK_ADAPTER_MAX_LEN 64
+#define BK_MAX_ADAPTERS 8
+#define BK_ADAPTER_MIN_OVERLAP 3
+#define BK_ADAPTER_MAX_ERROR_RATE 0.3
+int bk_adapters_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, uint32_t min_overlap, double max_error_rate);
+/* After bk_sample_finalize / _finish, until the engine's next bk_sample_begin (synchronises): out = {reads cut, bases removed}
+ * of the mate file.  The counters are taken on the records: an R shorter than k makes no record (it holds no k-mer, cut or not)
+ * and is not counted.  BK_ERR_STATE if no adapters were set when the sample began. */
+int bk_adapter_stats(bk_engine* e, int mate, uint64_t out[2]);
 
 /* ---- after the pileup, on the device (optional) ----------------------------------------------
  * For the sample just finalized, asynchronously on the engine's stream:
