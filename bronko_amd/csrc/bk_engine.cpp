@@ -1,11 +1,11 @@
-// bk_engine.cpp -- host side of the C ABI declared in include/bronko_hip.h.
+// bk_engine.cpp -- host side of the C ABI declared in include/bronko_hip.h: the engine's life and the sample path.
 //
-// Owns the HBM buffers of a sample (counter planes, pileups) and sequences the kernels of bk_kernels.hip on one HIP stream; the
-// index tables an engine reads are built by bk_index_tables.cpp and shared with its forks.
+// Owns the HBM buffers of a sample (counter planes, pileups) and sequences the kernels of bk_kernels.hip on one HIP stream, from the
+// scan of a batch of records (push_device) to the calls; the index tables an engine reads are built by bk_index_tables.cpp and shared
+// with its forks; how a caller's reads become records (the bk_push_reads_* entry points, K0, the trimming stage) is bk_ingest.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -14,7 +14,6 @@
 #include <string>
 #include <vector>
 
-#include "../host/lcb.hpp"
 #include "bk_engine.h"
 
 thread_local std::string g_err;
@@ -58,8 +57,7 @@ static int alloc_sample_state(bk_engine* e) {
         BK_HIP(e->ktab.keys.alloc((size_t)1 << prm->kmer_table_log2));
         BK_HIP(e->ktab.cnt.alloc((size_t)1 << prm->kmer_table_log2));
         e->ktab.log2 = prm->kmer_table_log2;
-        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&e->ktab.h_fill), bk::ktab_fill_words() * sizeof(unsigned long long), hipHostMallocDefault));
-        BK_HIP(hipEventCreateWithFlags(&e->ktab.fill_ev, hipEventDisableTiming));
+        BK_HIP(e->ktab.h_fill.grow(bk::ktab_fill_words())); BK_HIP(e->ktab.fill_ev.create());
     }
     BK_HIP(e->ktab_out.alloc(8 + bk::ktab_fill_words()));
     // one row of per-genome tallies per finalize workgroup (8192 rows: 10 MB at 100 genomes); without it every workgroup adds its
@@ -226,11 +224,6 @@ void bk_engine_destroy(bk_engine* e) {
     (void)hipStreamSynchronize(e->stream);
     for (auto& s : e->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto ev : e->free_events) (void)hipEventDestroy(ev);
-    for (auto& sl : e->slots) {
-        if (sl.h_bases) (void)hipHostFree(sl.h_bases); if (sl.h_off) (void)hipHostFree(sl.h_off); if (sl.h_quals) (void)hipHostFree(sl.h_quals);
-        if (sl.uploaded) (void)hipEventDestroy(sl.uploaded); if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    for (auto& st : e->stage) { if (st.done) (void)hipEventDestroy(st.done); if (st.h) (void)hipHostFree(st.h); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
@@ -281,14 +274,9 @@ int bk_sample_begin(bk_engine* e) {
         BK_HIP(hipMemsetAsync(e->dump->out.p, 0, e->dump->out.n * sizeof(unsigned long long), e->stream));
         e->dump->upper[0] = e->dump->upper[1] = 0; e->dump->in_sample = true; e->dump->finalized_mates = 0;
     }
-    if (e->primers) {
-        BK_HIP(hipMemsetAsync(e->primers->stats.p, 0, e->primers->stats.n * sizeof(unsigned long long), e->stream));
-        e->primers->in_sample = true;
-    }
-    if (e->adapters) {
-        BK_HIP(hipMemsetAsync(e->adapters->stats.p, 0, e->adapters->stats.n * sizeof(unsigned long long), e->stream));
-        e->adapters->in_sample = true;
-    }
+    TrimStage* const trim_stages[] = {e->primers.get(), e->adapters.get()};
+    for (TrimStage* t : trim_stages)
+        if (t) { BK_HIP(hipMemsetAsync(t->stats.p, 0, t->stats.n * sizeof(unsigned long long), e->stream)); t->in_sample = true; }
     e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
@@ -358,7 +346,7 @@ static int ensure_table_room(bk_engine* e, GrowTable& t, unsigned long long* out
 }
 static int note_table_fill(bk_engine* e, GrowTable& t, const unsigned long long* out) {   // after a push: a fresh copy of the tallies
     if (!t.keys.p) return BK_OK;
-    BK_HIP(hipMemcpyAsync(t.h_fill, out + 8, bk::ktab_fill_words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipMemcpyAsync(t.h_fill.p, out + 8, bk::ktab_fill_words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
     BK_HIP(hipEventRecord(t.fill_ev, e->stream));
     t.fill_pending = true;
     return BK_OK;
@@ -368,12 +356,11 @@ static int note_ktab_fill(bk_engine* e) { return note_table_fill(e, e->ktab, e->
 
 // bk_kmer_dump_enable: every k-mer of the batch into the count table, on the engine stream behind the scan that read the same records
 // (a staging slot is reused only after the stream has passed both)
-static int dump_push(bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
-                     const unsigned long long* n_records_dev, uint64_t upper) {
+static int dump_push(bk_engine* e, int mate, const Records& r, uint64_t upper) {
     KmerDump& d = *e->dump;
     if (int rc = ensure_table_room(e, d.t, d.out.p, upper)) return rc;
     d.upper[mate] += upper;
-    bk::launch_kmer_dump_count(d_words, d_lens, n, n_records_dev, stride_words, e->ix->k, (uint32_t)mate, d.t.keys.p, d.t.cnt.p, d.t.log2, d.out.p + 4,
+    bk::launch_kmer_dump_count(r.words, r.lens, r.n, r.n_dev, r.stride_words, e->ix->k, (uint32_t)mate, d.t.keys.p, d.t.cnt.p, d.t.log2, d.out.p + 4,
                                e->ix->n_cus, e->stream);
     BK_HIP(hipGetLastError());
     return note_table_fill(e, d.t, d.out.p);
@@ -459,17 +446,16 @@ static int l2_stats_report(bk_engine*) { return BK_OK; }
 
 // The scan's arguments that every launch of a push shares.  Built for each push: a rehash of the statistics table
 // (ensure_table_room) moves ktab.keys and raises ktab.log2 in the middle of a sample.
-static bk::ScanArgs scan_args(const bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
-                              const unsigned long long* n_records_dev) {
+static bk::ScanArgs scan_args(const bk_engine* e, int mate, const Records& r) {
     const IndexTables& ix = *e->ix;
     const MatePlane& pl = e->mate[mate];
     bk::ScanArgs a{};
-    a.n_records_dev = n_records_dev; a.ixp = ix.d_view.p;
+    a.n_records_dev = r.n_dev; a.ixp = ix.d_view.p;
     a.k = ix.k; a.wstart = ix.wstart; a.W = ix.W; a.v_omin = ix.v_omin; a.v_span = ix.v_span; a.v_off = ix.v_off; a.total_cells = (uint32_t)ix.total_cells; a.n_u = ix.n_u;
     a.ref_words = ix.ref_words.p; a.cell_codes = ix.cell_codes.p; a.cell_has = ix.cell_has.p; a.cell_clean = ix.cell_clean.p; a.cell_clean3 = ix.cell_clean3.p; a.cell_yf = ix.cell_yf.p; a.cell_yr = ix.cell_yr.p; a.id_at = ix.id_at.p; a.cell_fast = ix.cell_fast.p; a.cell_nat = ix.cell_nat.p; a.cell_natrow = ix.cell_natrow.p; a.cell_blk = ix.cell_blk.p; a.seed_tab = ix.seed_tab.p; a.seed_log2 = ix.seed_log2;
     a.seed_tab2 = ix.seed_tab2.p; a.seed2_log2 = ix.seed2_log2; a.rc_words = ix.rc_words.p;
     a.n_direct = e->use_items && ix.n_files == 1 && ix.max_seqs_per_file == 1 && (uint64_t)ix.n_lds_bins >= ix.total_cells && !test_env("BK_NO_N_DIRECT");
-    a.words = d_words; a.lens = d_lens; a.n_records = n; a.stride_words = stride_words;
+    a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.stride_words = r.stride_words;
     a.counters = pl.counters.p; a.kmer_total = e->kstats.p + mate * 4 + 1;
     a.ablate = ix.ablate; a.slabs = e->slabs.p; a.n_lds_bins = ix.n_lds_bins; a.ref_in_lds = ix.ref_in_lds ? 1 : 0;
     a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2;
@@ -479,7 +465,7 @@ static bk::ScanArgs scan_args(const bk_engine* e, int mate, const uint32_t* d_wo
         a.touch_v = pl.touch_v.p; a.touch_b = pl.touch_b.p; a.touch_p = pl.touch_p.p; a.touch_e = pl.touch_e.p;
         a.rl_recip = ~0ull / (unsigned long long)(ix.v_span + 1) + 1ull;   // ceil(2^64 / row length): exact quotients for 32-bit counter indices
     }
-    a.dbg = e->dbg.p; a.l2_words = bk::scan_l2_words(stride_words, ix.k); a.l2_min_grid = (uint32_t)std::max(1, ix.n_cus / 2);
+    a.dbg = e->dbg.p; a.l2_words = bk::scan_l2_words(r.stride_words, ix.k); a.l2_min_grid = (uint32_t)std::max(1, ix.n_cus / 2);
     if (e->use_items) { a.ig = e->ig; a.items = e->items.p; a.tab = e->item_tab.p; a.gext = e->item_gext.p; a.ov = e->ov.p; a.ov_n = e->ov_n.p; a.ov_cap = (uint32_t)e->ov.n; }
     return a;
 }
@@ -575,16 +561,16 @@ static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32
     }
     return BK_OK;
 }
-static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t stride_words, const uint16_t* d_lens, uint64_t n,
-                       const unsigned long long* n_records_dev = nullptr, uint64_t kmers_upper = 0) {
+}  // extern "C" (bk_engine.h declares the next function for bk_ingest.cpp)
+int push_device(bk_engine* e, int mate, const Records& r) {
     MatePlane& pl = e->mate[mate];
     if (int rc = pl.zero_if_stale(e)) return rc;
-    const uint64_t upper = kmers_upper ? kmers_upper : n * (uint64_t)stride_words * 16;
+    const uint64_t n = r.n, upper = r.kmers_upper ? r.kmers_upper : n * (uint64_t)r.stride_words * 16;
     if (int rc = ensure_ktab_room(e, upper)) return rc;
-    if (e->dump) { if (int rc = dump_push(e, mate, d_words, stride_words, d_lens, n, n_records_dev, upper)) return rc; }
+    if (e->dump) { if (int rc = dump_push(e, mate, r, upper)) return rc; }
     pl.written();
     if (int rc = l2_stats_arm(e)) return rc;
-    bk::ScanArgs a = scan_args(e, mate, d_words, stride_words, d_lens, n, n_records_dev);
+    bk::ScanArgs a = scan_args(e, mate, r);
     if (e->ix->W <= 0) {
         // empty window: nothing can touch the index (map_kmers finds no bucket, call.rs:1291-1307); KMC's total k-mer count is all
         bk::launch_count_kmers(a, e->stream);
@@ -610,276 +596,10 @@ static int push_device(bk_engine* e, int mate, const uint32_t* d_words, uint32_t
         }
     }
     BK_HIP(hipGetLastError());
-    if (!n_records_dev) pl.pushed_records += n;
+    if (!r.n_dev) pl.pushed_records += n;
     return note_ktab_fill(e);
 }
-
-// The checks the four bk_push_reads_* entry points share, in this order (`batch_ok`: the batch's pointers and shape are valid;
-// `too_large`: it holds 2^32 bases or more).  kPush: push the batch; BK_OK: it is empty; else the error.
-static constexpr int kPush = 1;
-static int push_checks(bk_engine* e, int mate, uint64_t n, bool batch_ok, const char* bad_batch, bool too_large) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (!e->in_sample) return fail(BK_ERR_STATE, "bk_push_reads_* called before bk_sample_begin");
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (n == 0) return BK_OK;
-    if (!batch_ok) return fail(BK_ERR_INVALID, "%s", bad_batch);
-    if (too_large) return fail(BK_ERR_INVALID, "batch too large: push at most 2^32 bases per call");
-    BK_HIP(hipSetDevice(e->device));
-    return kPush;
-}
-static int packed_checks(bk_engine* e, int mate, const void* words, uint32_t stride_words, const void* lens, uint64_t n) {
-    return push_checks(e, mate, n, words && lens && stride_words != 0 && stride_words <= 4096, "bad record batch",
-                       stride_words != 0 && n > (1ull << 32) / ((uint64_t)stride_words * 16));
-}
-// ASCII reads: the packer's records hold up to 16 bases per word and at most 65535 bases (a longer run of bases is cut into records
-// that overlap by k - 1): words per record, and a bound on the records a batch becomes
-struct PackGeom {
-    uint32_t stride; uint64_t cap;
-    PackGeom(int k, uint64_t n_reads, uint64_t total, uint64_t longest)
-        : stride((uint32_t)std::min<uint64_t>((std::max<uint64_t>(longest, (uint64_t)k) + 15) / 16, 4095)),
-          cap(n_reads + total / (uint64_t)k + total / (std::min<uint64_t>((uint64_t)stride * 16, 65535) - (uint64_t)(k - 1)) + 16) {}
-};
-// bk_adapters_set, bk_primers_set: the adapters, then the primers, come off the records that touch a read end (adapter_find_kernel
-// and adapter_trim_kernel, primer_trim_kernel: in place), on the engine stream between the packer or the copy that made the records
-// and everything that reads them
-static int trim_records(bk_engine* e, int mate, uint32_t* d_words, uint32_t stride_words, uint16_t* d_lens, const uint8_t* d_ends, uint64_t n,
-                        const unsigned long long* n_records_dev = nullptr) {
-    if (e->adapters) {
-        Adapters& ad = *e->adapters;
-        if (ad.cut.n < n) {   // (the kernels leave kNoCut everywhere: filled once per allocation)
-            BK_HIP(hipStreamSynchronize(e->stream));
-            BK_HIP(ad.cut.alloc(n + n / 4));
-            BK_HIP(hipMemsetAsync(ad.cut.p, 0xFF, ad.cut.n * sizeof(uint32_t), e->stream));
-        }
-        bk_engine::Span sp(e, 2);
-        bk::AdapterArgs t{};
-        t.words = d_words; t.lens = d_lens; t.ends = d_ends; t.cut = ad.cut.p; t.n_records = n; t.n_records_dev = n_records_dev;
-        t.stride_words = stride_words; t.k = e->ix->k; t.n_adapters = ad.n; t.min_overlap = ad.min_overlap; t.allowed_steps = ad.allowed_steps;
-        t.stats = ad.stats.p + mate * 2; t.n_real = e->kstats.p + mate * 4 + 0;
-        std::copy(ad.entry, ad.entry + bk::kMaxAdapters, t.adapters);
-        bk::launch_adapter_trim(t, e->ix->n_cus, e->stream);
-    }
-    if (!e->primers) return BK_OK;
-    bk_engine::Span sp(e, 2);
-    bk::TrimArgs t{};
-    t.words = d_words; t.lens = d_lens; t.ends = d_ends; t.n_records = n; t.n_records_dev = n_records_dev; t.stride_words = stride_words;
-    t.k = e->ix->k; t.table = e->primers->table.p; t.n_primers = e->primers->n; t.max_mismatches = e->primers->max_mismatches;
-    t.stats = e->primers->stats.p + mate * 3; t.n_real = e->kstats.p + mate * 4 + 0;
-    bk::launch_primer_trim(t, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
-
-// the packer (records pushed: tallied on the device) into the slot's record buffers, then the push of those records
-// (q: the quality lines and threshold of a bk_push_reads_ascii_qual* batch, or null); with primers or adapters set the packer also
-// writes the records' end flags and the records are trimmed in between
-static int pack_and_push(bk_engine* e, int mate, bk_engine::IngestSlot& sl, const uint8_t* bases, uint32_t shift, const unsigned long long* offsets,
-                         uint64_t n_reads, uint64_t total, PackGeom g, const bk::QualArgs* q = nullptr) {
-    bk::PackArgs pa{};
-    pa.shift = shift; pa.bases = bases; pa.offsets = offsets; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = g.stride;
-    pa.words = sl.d_words.p; pa.lens = sl.d_lens.p; pa.cap = g.cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
-    uint8_t* ends = nullptr;
-    if (e->trims()) {
-        if (sl.d_ends.n < g.cap) { BK_HIP(hipStreamSynchronize(e->stream)); BK_HIP(sl.d_ends.alloc(g.cap + g.cap / 4)); }
-        ends = sl.d_ends.p;
-    }
-    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream, q, ends); }
-    if (ends) { if (int rc = trim_records(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, ends, g.cap, sl.d_nrec.p); rc != BK_OK) return rc; }
-    return push_device(e, mate, sl.d_words.p, g.stride, sl.d_lens.p, g.cap, sl.d_nrec.p, total);   // (a batch holds fewer k-mers than bases)
-}
-
-// --min-base-qual: a quality byte below '!' + min_qual (Phred+33) makes its base an N; 0 is off
-static constexpr int kMaxMinQual = 93;   // ('!' + 93 = '~', the last printable quality symbol)
-
-// bk_push_reads_ascii and bk_push_reads_ascii_qual (qual: null, or the quality lines at the same offsets; thr = '!' + min_qual)
-static int push_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint8_t* qual, const uint64_t* offsets, uint64_t n_reads, uint32_t thr) {
-    const bool too_large = buf && offsets && n_reads && offsets[n_reads] - offsets[0] >= (1ull << 32);
-    if (int rc = push_checks(e, mate, n_reads, buf && offsets, "bad read batch", too_large); rc != kPush) return rc;
-    const uint64_t base0 = offsets[0], total = offsets[n_reads] - base0;
-    if (!e->copy_stream) BK_HIP(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-    bk_engine::IngestSlot& sl = e->slots[e->next_slot];
-    e->next_slot = (e->next_slot + 1) % 3;
-    if (!sl.done) { BK_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)); BK_HIP(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming)); }
-    if (sl.busy) { BK_HIP(hipEventSynchronize(sl.done)); sl.busy = false; }   // slot still owned by an earlier batch
-
-    // staging copy (the caller's buffer is free as soon as we return) + longest read of the batch
-    if (sl.h_bases_cap < total + 1) {
-        if (sl.h_bases) BK_HIP(hipHostFree(sl.h_bases));
-        sl.h_bases_cap = total + total / 4 + 4096;
-        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_bases), sl.h_bases_cap, hipHostMallocDefault));
-    }
-    if (sl.h_off_cap < n_reads + 1) {
-        if (sl.h_off) BK_HIP(hipHostFree(sl.h_off));
-        sl.h_off_cap = n_reads + n_reads / 4 + 1024;
-        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_off), sl.h_off_cap * sizeof(unsigned long long), hipHostMallocDefault));
-    }
-    if (qual && sl.h_quals_cap < total + 1) {
-        if (sl.h_quals) BK_HIP(hipHostFree(sl.h_quals));
-        sl.h_quals_cap = total + total / 4 + 4096;
-        BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h_quals), sl.h_quals_cap, hipHostMallocDefault));
-    }
-    std::memcpy(sl.h_bases, buf + base0, total);
-    if (qual) std::memcpy(sl.h_quals, qual + base0, total);
-    uint64_t longest = 0;
-    for (uint64_t i = 0; i <= n_reads; i++) {
-        sl.h_off[i] = offsets[i] - base0;
-        if (i) longest = std::max(longest, offsets[i] - offsets[i - 1]);
-    }
-    const PackGeom g(e->ix->k, n_reads, total, longest);
-
-    if (sl.d_bases.n < total + 1) BK_HIP(sl.d_bases.alloc(total + total / 4 + 4096));
-    if (qual && sl.d_quals.n < total + 1) BK_HIP(sl.d_quals.alloc(total + total / 4 + 4096));
-    if (sl.d_off.n < n_reads + 1) BK_HIP(sl.d_off.alloc(n_reads + n_reads / 4 + 1024));
-    if (sl.d_words.n < g.cap * g.stride) BK_HIP(sl.d_words.alloc(g.cap * g.stride + g.cap * g.stride / 4));
-    if (sl.d_lens.n < g.cap) BK_HIP(sl.d_lens.alloc(g.cap + g.cap / 4));
-    if (!sl.d_nrec.p) BK_HIP(sl.d_nrec.alloc(4));
-    if (sl.d_work.n < n_reads) BK_HIP(sl.d_work.alloc(n_reads + n_reads / 4 + 1024));
-
-    BK_HIP(hipMemcpyAsync(sl.d_bases.p, sl.h_bases, total, hipMemcpyHostToDevice, e->copy_stream));
-    if (qual) BK_HIP(hipMemcpyAsync(sl.d_quals.p, sl.h_quals, total, hipMemcpyHostToDevice, e->copy_stream));
-    BK_HIP(hipMemcpyAsync(sl.d_off.p, sl.h_off, (n_reads + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, e->copy_stream));
-    BK_HIP(hipEventRecord(sl.uploaded, e->copy_stream));
-    BK_HIP(hipStreamWaitEvent(e->stream, sl.uploaded, 0));
-    const bk::QualArgs q{sl.d_quals.p, 0u, thr};
-    if (int rc = pack_and_push(e, mate, sl, sl.d_bases.p, 0, sl.d_off.p, n_reads, total, g, qual ? &q : nullptr)) return rc;
-    BK_HIP(hipEventRecord(sl.done, e->stream));
-    sl.busy = true;
-    return BK_OK;
-}
-
-int bk_push_reads_ascii(bk_engine* e, int mate, const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads) {
-    return push_ascii(e, mate, buf, nullptr, offsets, n_reads, 0u);
-}
-
-int bk_push_reads_ascii_qual(bk_engine* e, int mate, const uint8_t* buf, const uint8_t* qual, const uint64_t* offsets, uint64_t n_reads, int min_qual) {
-    if (min_qual < 0 || min_qual > kMaxMinQual) return fail(BK_ERR_INVALID, "min_qual must be between 0 and %d", kMaxMinQual);
-    if (min_qual == 0) return bk_push_reads_ascii(e, mate, buf, offsets, n_reads);
-    if (!qual && e && e->in_sample && mate >= 0 && mate <= 1 && n_reads) return fail(BK_ERR_INVALID, "bad read batch: no quality lines");
-    return push_ascii(e, mate, buf, qual, offsets, n_reads, (uint32_t)('!' + min_qual));
-}
-
-// sequence lines (d_bases) or quality lines (d_quals) from a pointer of any alignment: the packer stages them with 16-byte loads
-// from a 16-byte boundary, so the pointer is rounded down and the offsets carry the difference (a device allocation starts on a
-// 256-byte boundary, so the bytes in front belong to the same allocation)
-static uint32_t align_shift(const void* p) { return (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u); }
-
-static int push_ascii_device(bk_engine* e, int mate, const void* d_bases, const void* d_quals, const void* d_offsets, uint64_t n_reads,
-                             uint64_t total_bases, uint32_t longest_read, uint32_t thr) {
-    if (int rc = push_checks(e, mate, n_reads, d_bases && d_offsets, "bad read batch", total_bases >= (1ull << 32)); rc != kPush) return rc;
-    // (everything is ordered by the engine's stream: the records of the previous batch were consumed by its scan before this
-    // batch's packer starts, so one set of record buffers does)
-    bk_engine::IngestSlot& sl = e->dev_ascii;
-    const PackGeom g(e->ix->k, n_reads, total_bases, longest_read);
-    if (sl.d_words.n < g.cap * g.stride || sl.d_lens.n < g.cap || sl.d_work.n < n_reads) {
-        BK_HIP(hipStreamSynchronize(e->stream));
-        BK_HIP(sl.d_words.alloc(g.cap * g.stride + g.cap * g.stride / 4));
-        BK_HIP(sl.d_lens.alloc(g.cap + g.cap / 4));
-        BK_HIP(sl.d_work.alloc(n_reads + n_reads / 4 + 1024));
-    }
-    if (!sl.d_nrec.p) BK_HIP(sl.d_nrec.alloc(4));
-    const uint32_t shift = align_shift(d_bases);
-    const bk::QualArgs q{static_cast<const uint8_t*>(d_quals) - align_shift(d_quals), align_shift(d_quals), thr};
-    return pack_and_push(e, mate, sl, static_cast<const uint8_t*>(d_bases) - shift, shift, static_cast<const unsigned long long*>(d_offsets), n_reads,
-                         total_bases, g, d_quals ? &q : nullptr);
-}
-
-int bk_push_reads_ascii_device(bk_engine* e, int mate, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t total_bases,
-                               uint32_t longest_read) {
-    return push_ascii_device(e, mate, d_bases, nullptr, d_offsets, n_reads, total_bases, longest_read, 0u);
-}
-
-int bk_push_reads_ascii_qual_device(bk_engine* e, int mate, const void* d_bases, const void* d_quals, const void* d_offsets, uint64_t n_reads,
-                                    uint64_t total_bases, uint32_t longest_read, int min_qual) {
-    if (min_qual < 0 || min_qual > kMaxMinQual) return fail(BK_ERR_INVALID, "min_qual must be between 0 and %d", kMaxMinQual);
-    if (min_qual == 0) return bk_push_reads_ascii_device(e, mate, d_bases, d_offsets, n_reads, total_bases, longest_read);
-    if (!d_quals && e && e->in_sample && mate >= 0 && mate <= 1 && n_reads) return fail(BK_ERR_INVALID, "bad read batch: no quality lines");
-    return push_ascii_device(e, mate, d_bases, d_quals, d_offsets, n_reads, total_bases, longest_read, (uint32_t)('!' + min_qual));
-}
-
-// the packed pushes: `ends` null (the plain calls: refused while primers or adapters are set, since those records would go
-// untrimmed) or the records' end flags (read only while primers or adapters are set)
-static int no_end_flags(const bk_engine* e, const char* fn) {
-    if (!e->primers) return fail(BK_ERR_STATE, "%s: adapters are set (bk_adapters_set) and these records carry no end flags: push them with %s_ends", fn, fn);
-    if (e->adapters) return fail(BK_ERR_STATE, "%s: primers and adapters are set (bk_primers_set, bk_adapters_set) and these records carry no end flags: push them with %s_ends", fn, fn);
-    return fail(BK_ERR_STATE, "%s: primers are set (bk_primers_set) and these records carry no end flags: push them with %s_ends", fn, fn);
-}
-
-static int push_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends, uint64_t n) {
-    if (int rc = packed_checks(e, mate, d_words, stride_words, d_lens, n); rc != kPush) return rc;
-    if (!e->trims()) return push_device(e, mate, static_cast<const uint32_t*>(d_words), stride_words, static_cast<const uint16_t*>(d_lens), n);
-    if (!d_ends) return no_end_flags(e, "bk_push_reads_packed_device");
-    // the caller's records are not the engine's to rewrite: they are trimmed in a copy (the buffers of bk_push_reads_ascii_device:
-    // everything that uses them is ordered by the engine's stream)
-    bk_engine::IngestSlot& sl = e->dev_ascii;
-    const size_t nw = (size_t)n * stride_words;
-    if (sl.d_words.n < nw || sl.d_lens.n < n) {
-        BK_HIP(hipStreamSynchronize(e->stream));
-        if (sl.d_words.n < nw) BK_HIP(sl.d_words.alloc(nw + nw / 4));
-        if (sl.d_lens.n < n) BK_HIP(sl.d_lens.alloc(n + n / 4));
-    }
-    BK_HIP(hipMemcpyAsync(sl.d_words.p, d_words, nw * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream));
-    BK_HIP(hipMemcpyAsync(sl.d_lens.p, d_lens, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToDevice, e->stream));
-    if (int rc = trim_records(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, static_cast<const uint8_t*>(d_ends), n); rc != BK_OK) return rc;
-    return push_device(e, mate, sl.d_words.p, stride_words, sl.d_lens.p, n);
-}
-
-int bk_push_reads_packed_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, uint64_t n) {
-    return push_packed_device(e, mate, d_words, stride_words, d_lens, nullptr, n);
-}
-
-int bk_push_reads_packed_ends_device(bk_engine* e, int mate, const void* d_words, uint32_t stride_words, const void* d_lens, const void* d_ends,
-                                     uint64_t n) {
-    if (e && e->trims() && !d_ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
-    return push_packed_device(e, mate, d_words, stride_words, d_lens, d_ends, n);
-}
-
-static int push_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends, uint64_t n) {
-    if (int rc = packed_checks(e, mate, words, stride_words, lens, n); rc != kPush) return rc;
-    if (e->trims() && !ends) return no_end_flags(e, "bk_push_reads_packed");
-    if (!e->trims()) ends = nullptr;
-    const size_t nw = (size_t)n * stride_words;
-    bk_engine::StageSlot& sl = e->stage[e->next_stage];
-    e->next_stage ^= 1;
-    if (!sl.done) BK_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    if (sl.busy) { BK_HIP(hipEventSynchronize(sl.done)); sl.busy = false; }   // the scan that read this slot two pushes ago
-    if (sl.words.n < nw) BK_HIP(sl.words.alloc(nw + nw / 4));
-    if (sl.lens.n < n) BK_HIP(sl.lens.alloc(n + n / 4));
-    if (ends && sl.ends.n < n) BK_HIP(sl.ends.alloc(n + n / 4));
-    {
-        // the caller's buffer is free when this call returns: the batch is copied into the slot's pinned host buffer, from where
-        // it travels asynchronously (an asynchronous copy straight from pageable memory would still be reading the caller's pages)
-        const size_t bytes_w = nw * sizeof(uint32_t), bytes_l = (size_t)n * sizeof(uint16_t), bytes_e = ends ? (size_t)n : 0;
-        if (sl.h_cap < bytes_w + bytes_l + bytes_e) {
-            if (sl.h) BK_HIP(hipHostFree(sl.h));
-            sl.h = nullptr;
-            sl.h_cap = bytes_w + bytes_l + bytes_e + (bytes_w + bytes_l + bytes_e) / 4;
-            BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.h), sl.h_cap, hipHostMallocDefault));
-        }
-        std::memcpy(sl.h, words, bytes_w);
-        std::memcpy(sl.h + bytes_w, lens, bytes_l);
-        if (ends) std::memcpy(sl.h + bytes_w + bytes_l, ends, bytes_e);
-        bk_engine::Span sp(e, 2);
-        BK_HIP(hipMemcpyAsync(sl.words.p, sl.h, bytes_w, hipMemcpyHostToDevice, e->stream));
-        BK_HIP(hipMemcpyAsync(sl.lens.p, sl.h + bytes_w, bytes_l, hipMemcpyHostToDevice, e->stream));
-        if (ends) BK_HIP(hipMemcpyAsync(sl.ends.p, sl.h + bytes_w + bytes_l, bytes_e, hipMemcpyHostToDevice, e->stream));
-    }
-    if (ends) { if (int rc = trim_records(e, mate, sl.words.p, stride_words, sl.lens.p, sl.ends.p, n); rc != BK_OK) return rc; }
-    int rc = push_device(e, mate, sl.words.p, stride_words, sl.lens.p, n);
-    if (rc != BK_OK) return rc;
-    BK_HIP(hipEventRecord(sl.done, e->stream));
-    sl.busy = true;
-    if (test_env("BK_SYNC_PUSH")) BK_HIP(hipStreamSynchronize(e->stream));
-    return BK_OK;
-}
-
-int bk_push_reads_packed(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, uint64_t n) {
-    return push_packed(e, mate, words, stride_words, lens, nullptr, n);
-}
-
-int bk_push_reads_packed_ends(bk_engine* e, int mate, const uint32_t* words, uint32_t stride_words, const uint16_t* lens, const uint8_t* ends,
-                              uint64_t n) {
-    if (e && e->trims() && !ends && n) return fail(BK_ERR_INVALID, "bad record batch: no end flags");
-    return push_packed(e, mate, words, stride_words, lens, ends, n);
-}
+extern "C" {
 
 int bk_counters_device_ptr(bk_engine* e, int mate, void** d_ptr) {
     if (!e || !d_ptr || mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "bad argument");
@@ -1327,115 +1047,6 @@ int bk_sample_finish(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t* r
     return bk_sample_download(e, n_mates, fwd_depth, rev_depth, fwd_nk, rev_nk, stats, present, kmer_stats);
 }
 
-// ---- amplicon primers (bk_primers.hip) ----------------------------------------------------------------------------
-int bk_primers_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, int max_mismatches) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_primers_set comes between samples");
-    if (max_mismatches < 0 || max_mismatches > (int)bk::kMaxPrimerMismatches) return fail(BK_ERR_INVALID, "max_mismatches must be between 0 and %u", bk::kMaxPrimerMismatches);
-    if (n > bk::kMaxPrimers) return fail(BK_ERR_INVALID, "%u primers: at most %u", n, bk::kMaxPrimers);
-    if (n && (!seqs || !lens)) return fail(BK_ERR_INVALID, "null argument");
-    std::vector<uint32_t> tab((size_t)n * bk::kPrimerEntryWords, 0u);
-    for (uint32_t p = 0; p < n; p++) {
-        const uint32_t L = lens[p];
-        if (L < bk::kPrimerMinLen || L > bk::kPrimerMaxLen) return fail(BK_ERR_INVALID, "primer %u: %u bases (a primer has %u to %u)", p + 1, L, bk::kPrimerMinLen, bk::kPrimerMaxLen);
-        if (!seqs[p]) return fail(BK_ERR_INVALID, "primer %u: null sequence", p + 1);
-        uint32_t* t = tab.data() + (size_t)p * bk::kPrimerEntryWords;
-        for (uint32_t i = 0; i < L; i++) {
-            const int c = bronko::acgt_code(seqs[p][i]);
-            if (c < 0) return fail(BK_ERR_INVALID, "primer %u: symbol %u is not one of ACGT/acgt", p + 1, i + 1);
-            t[i >> 4] |= (uint32_t)c << (2 * (i & 15));
-            const uint32_t j = 64 - 1 - i;   // base i's complement, counted from the end of the 64-base window
-            t[4 + (j >> 4)] |= (uint32_t)(3 - c) << (2 * (j & 15));
-        }
-        t[8] = L;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still read the table being replaced)
-    e->primers.reset();
-    if (n == 0) return BK_OK;
-    std::unique_ptr<Primers> pr(new Primers());
-    BK_HIP(pr->table.alloc(tab.size()));
-    BK_HIP(hipMemcpy(pr->table.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    BK_HIP(pr->stats.alloc(6));
-    BK_HIP(hipMemset(pr->stats.p, 0, 6 * sizeof(unsigned long long)));
-    pr->n = n; pr->max_mismatches = (uint32_t)max_mismatches;
-    e->primers = std::move(pr);
-    return BK_OK;
-}
-
-int bk_primer_stats(bk_engine* e, int mate, uint64_t out[3]) {
-    if (!e || !out) return fail(BK_ERR_INVALID, "null argument");
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (!e->primers || !e->primers->in_sample) return fail(BK_ERR_STATE, "no primers were set for this sample (bk_primers_set before bk_sample_begin)");
-    if (e->in_sample) return fail(BK_ERR_STATE, "the primer counters are read after bk_sample_finalize");
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long o[3];
-    BK_HIP(hipMemcpyAsync(o, e->primers->stats.p + mate * 3, sizeof o, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < 3; i++) out[i] = o[i];
-    return BK_OK;
-}
-
-// ---- 3' adapters (bk_adapters.hip) ----------------------------------------------------------------------------------
-int bk_adapters_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, uint32_t min_overlap, double max_error_rate) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_adapters_set comes between samples");
-    if (n > bk::kMaxAdapters) return fail(BK_ERR_INVALID, "%u adapters: at most %u", n, bk::kMaxAdapters);
-    if (n && (!seqs || !lens)) return fail(BK_ERR_INVALID, "null argument");
-    std::unique_ptr<Adapters> ad(new Adapters());
-    if (n) {
-        if (!(max_error_rate >= 0.0 && max_error_rate <= bk::kAdapterMaxErrorRate))
-            return fail(BK_ERR_INVALID, "max_error_rate must be between 0 and %g, got %g", bk::kAdapterMaxErrorRate, max_error_rate);
-        uint32_t shortest = bk::kAdapterMaxLen;
-        for (uint32_t a = 0; a < n; a++) {
-            const uint32_t L = lens[a];
-            if (L < bk::kAdapterMinLen || L > bk::kAdapterMaxLen)
-                return fail(BK_ERR_INVALID, "adapter %u: %u bases (an adapter has %u to %u)", a + 1, L, bk::kAdapterMinLen, bk::kAdapterMaxLen);
-            if (!seqs[a]) return fail(BK_ERR_INVALID, "adapter %u: null sequence", a + 1);
-            bk::AdapterEntry& t = ad->entry[a];
-            for (uint32_t i = 0; i < L; i++) {
-                const int c = bronko::acgt_code(seqs[a][i]);
-                if (c < 0) return fail(BK_ERR_INVALID, "adapter %u: symbol %u is not one of ACGT/acgt", a + 1, i + 1);
-                t.code[i >> 4] |= (uint32_t)c << (2 * (i & 15));
-                t.mask[i >> 4] |= 1u << (2 * (i & 15));
-            }
-            t.len = L;
-            t.allowed = (uint32_t)std::floor(max_error_rate * (double)L);
-            shortest = std::min(shortest, L);
-        }
-        if (min_overlap < bk::kAdapterMinOverlap || min_overlap > shortest)
-            return fail(BK_ERR_INVALID, "min_overlap must be between %u and the shortest adapter's %u bases, got %u", bk::kAdapterMinOverlap, shortest, min_overlap);
-        uint32_t prev = 0;   // floor(E * l), l = 1..64, as its steps (bk::AdapterArgs::allowed_steps)
-        for (uint32_t l = 1; l <= bk::kAdapterMaxLen; l++) {
-            const uint32_t al = (uint32_t)std::floor(max_error_rate * (double)l);
-            if (al > prev) ad->allowed_steps |= 1ull << (l - 1);
-            prev = al;
-        }
-        ad->n = n; ad->min_overlap = min_overlap;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->adapters.reset();
-    if (n == 0) return BK_OK;
-    BK_HIP(ad->stats.alloc(4));
-    BK_HIP(hipMemset(ad->stats.p, 0, 4 * sizeof(unsigned long long)));
-    e->adapters = std::move(ad);
-    return BK_OK;
-}
-
-int bk_adapter_stats(bk_engine* e, int mate, uint64_t out[2]) {
-    if (!e || !out) return fail(BK_ERR_INVALID, "null argument");
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (!e->adapters || !e->adapters->in_sample) return fail(BK_ERR_STATE, "no adapters were set for this sample (bk_adapters_set before bk_sample_begin)");
-    if (e->in_sample) return fail(BK_ERR_STATE, "the adapter counters are read after bk_sample_finalize");
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long o[2];
-    BK_HIP(hipMemcpyAsync(o, e->adapters->stats.p + mate * 2, sizeof o, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < 2; i++) out[i] = o[i];
-    return BK_OK;
-}
-
 // ---- the sample's k-mer count table (bk_kmer_dump.hip) --------------------------------------------------------------
 int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
@@ -1449,8 +1060,7 @@ int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2) {
     BK_HIP(d->t.keys.alloc((size_t)1 << table_log2));
     BK_HIP(d->t.cnt.alloc((size_t)1 << table_log2));
     d->t.log2 = table_log2;
-    BK_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->t.h_fill), bk::ktab_fill_words() * sizeof(unsigned long long), hipHostMallocDefault));
-    BK_HIP(hipEventCreateWithFlags(&d->t.fill_ev, hipEventDisableTiming));
+    BK_HIP(d->t.h_fill.grow(bk::ktab_fill_words())); BK_HIP(d->t.fill_ev.create());
     BK_HIP(d->out.alloc(8 + bk::ktab_fill_words()));
     BK_HIP(hipMemset(d->out.p, 0, d->out.n * sizeof(unsigned long long)));
     e->dump = std::move(d);
@@ -1572,70 +1182,6 @@ int bk_sample_download_noise(bk_engine* e, double* out, uint64_t cap, uint64_t* 
     *n = hi - lo;
     if (out && cap) BK_HIP(hipMemcpy(out, e->call_noise.p + lo, (size_t)std::min<uint64_t>(cap, hi - lo) * sizeof(double), hipMemcpyDeviceToHost));
     return BK_OK;
-}
-
-// ---- K0 host packer ------------------------------------------------------------------------------------------
-namespace {
-struct Packer {
-    int k; uint32_t stride; uint32_t* words; uint16_t* lens; uint64_t cap; uint64_t n = 0;
-    uint8_t* ends = nullptr;   // bk_pack_reads_flat_ends: [cap] the records' end flags
-    void emit(const uint8_t* s, uint64_t len, uint8_t flags) {   // one record of <= 16*stride ACGT symbols
-        if (n < cap) {
-            uint32_t* w = words + n * stride;
-            std::memset(w, 0, (size_t)stride * 4);
-            for (uint64_t i = 0; i < len; i++) w[i >> 4] |= (uint32_t)bronko::acgt_code(s[i]) << (2 * (i & 15));
-            lens[n] = (uint16_t)len;
-            if (ends) ends[n] = flags;
-        }
-        n++;
-    }
-    void run(const uint8_t* s, uint64_t len, uint8_t flags) {    // one maximal ACGT run (flags: it starts / ends its read)
-        if (len < (uint64_t)k) return;
-        const uint64_t maxb = std::min<uint64_t>((uint64_t)stride * 16, 65535);
-        if (len > maxb) flags = 0;   // (cut into chunks: no chunk is flagged)
-        uint64_t pos = 0;
-        for (;;) {
-            const uint64_t take = std::min(maxb, len - pos);
-            emit(s + pos, take, flags);
-            if (pos + take >= len) break;
-            pos += take - (uint64_t)(k - 1);      // next chunk re-reads k-1 bases: no k-mer lost or doubled
-        }
-    }
-    void read(const uint8_t* s, uint64_t len) {
-        uint64_t start = 0;
-        for (uint64_t i = 0; i <= len; i++) {
-            if (i == len || bronko::acgt_code(s[i]) < 0) {
-                run(s + start, i - start, (uint8_t)((start == 0 ? bk::kEndFirst : 0u) | (i == len ? bk::kEndLast : 0u)));
-                start = i + 1;
-            }
-        }
-    }
-};
-}  // namespace
-
-uint64_t bk_pack_reads(const uint8_t* const* reads, const uint64_t* read_lens, uint64_t n_reads, int32_t k, uint32_t stride_words,
-                       uint32_t* out_words, uint16_t* out_lens, uint64_t cap_records) {
-    if (k < 1 || stride_words == 0 || (uint64_t)stride_words * 16 < (uint64_t)k) return 0;
-    Packer p{k, stride_words, out_words, out_lens, (out_words && out_lens) ? cap_records : 0};
-    for (uint64_t r = 0; r < n_reads; r++) p.read(reads[r], read_lens[r]);
-    return p.n;
-}
-
-uint64_t bk_pack_reads_flat(const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads, int32_t k, uint32_t stride_words,
-                            uint32_t* out_words, uint16_t* out_lens, uint64_t cap_records) {
-    if (k < 1 || stride_words == 0 || (uint64_t)stride_words * 16 < (uint64_t)k) return 0;
-    Packer p{k, stride_words, out_words, out_lens, (out_words && out_lens) ? cap_records : 0};
-    for (uint64_t r = 0; r < n_reads; r++) p.read(buf + offsets[r], offsets[r + 1] - offsets[r]);
-    return p.n;
-}
-
-uint64_t bk_pack_reads_flat_ends(const uint8_t* buf, const uint64_t* offsets, uint64_t n_reads, int32_t k, uint32_t stride_words,
-                                 uint32_t* out_words, uint16_t* out_lens, uint8_t* out_ends, uint64_t cap_records) {
-    if (k < 1 || stride_words == 0 || (uint64_t)stride_words * 16 < (uint64_t)k) return 0;
-    Packer p{k, stride_words, out_words, out_lens, (out_words && out_lens) ? cap_records : 0};
-    p.ends = out_ends;
-    for (uint64_t r = 0; r < n_reads; r++) p.read(buf + offsets[r], offsets[r + 1] - offsets[r]);
-    return p.n;
 }
 
 // ---- measurement ---------------------------------------------------------------------------------------------

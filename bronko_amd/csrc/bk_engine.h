@@ -1,5 +1,7 @@
-// bk_engine.h -- private to the host side of the engine (bk_engine.cpp, bk_index_tables.cpp): error reporting, device buffers,
-// host-thread helpers, the index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.
+// bk_engine.h -- private to the host side of the engine: error reporting, device and pinned buffers, host-thread helpers, the
+// index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
+// index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
+// packer) and bk_engine.cpp (the rest: the engine's life, the sample path from push_device on).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +55,61 @@ struct DevBuf {
     }
 };
 static_assert(!std::is_copy_constructible_v<DevBuf<int>> && !std::is_copy_assignable_v<DevBuf<int>>, "DevBuf owns its memory");
+// Room for `need` elements: a buffer that is too small is allocated again a quarter (+ `extra`) larger, its contents lost.  `drain`:
+// null when nothing in flight can still use the old memory (the caller has waited for it), else the stream to drain before it goes.
+template <typename T>
+hipError_t grow(DevBuf<T>& b, size_t need, size_t extra = 0, hipStream_t drain = nullptr) {
+    if (b.n >= need) return hipSuccess;
+    if (drain) { hipError_t e = hipStreamSynchronize(drain); if (e != hipSuccess) return e; }
+    return b.alloc(need + need / 4 + extra);
+}
+
+// A pinned host allocation and an event, each freed with its owner (move-only)
+template <typename T>
+struct PinnedBuf {
+    T* p = nullptr; size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t grow(size_t need, size_t extra = 0) {   // (like grow of a DevBuf)
+        if (n >= need) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; n = 0;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), (need + need / 4 + extra) * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess) n = need + need / 4 + extra;
+        return e;
+    }
+};
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t create() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }   // (first use)
+    operator hipEvent_t() const { return ev; }
+};
+
+// A batch of records on the device, as the scan and what runs beside it read them
+struct Records {
+    const uint32_t* words;                      // [n][stride_words] 2-bit bases, 16 a word
+    uint32_t stride_words;
+    const uint16_t* lens;                       // [n]
+    uint64_t n;                                 // records; with n_dev, the slots the batch can fill at most
+    const unsigned long long* n_dev = nullptr;  // null, or the device's count of the slots in use (K0)
+    uint64_t kmers_upper = 0;                   // a bound on the batch's k-mers (0: every base of every record)
+};
+// The device buffers that hold such a batch for the engine: a slot of the ASCII or the packed pushes, bk_engine::dev_ascii
+struct RecordBufs {
+    DevBuf<uint32_t> words; DevBuf<uint16_t> lens;
+    DevBuf<uint8_t> ends;                       // primers or adapters set: the records' end flags
+    hipError_t reserve(uint64_t n, uint32_t stride_words, hipStream_t drain) {   // (words and lengths; `drain` as for grow)
+        hipError_t e = grow(words, (size_t)n * stride_words, 0, drain);
+        return e != hipSuccess ? e : grow(lens, (size_t)n, 0, drain);
+    }
+    Records view(uint32_t stride_words, uint64_t n, const unsigned long long* n_dev = nullptr, uint64_t kmers_upper = 0) const {
+        return Records{words.p, stride_words, lens.p, n, n_dev, kmers_upper};
+    }
+};
 
 struct TimedSpan { hipEvent_t a, b; int kind; };
 
@@ -116,20 +173,16 @@ struct GrowTable {
     DevBuf<unsigned long long> keys;
     DevBuf<unsigned int> cnt;
     uint32_t log2 = 0;                      // current capacity (grows with the sample: ensure_table_room)
-    unsigned long long* h_fill = nullptr;   // pinned copy of the tallies, refreshed after every push
-    hipEvent_t fill_ev = nullptr;
+    PinnedBuf<unsigned long long> h_fill;   // pinned copy of the tallies, refreshed after every push
+    Event fill_ev;
     bool fill_pending = false;              // a copy of the tallies is in flight / unread
     uint64_t fill_known = 0, fill_unknown_upper = 0;   // keys in the table at the last reading; k-mers pushed since (upper bound on new keys)
     std::vector<std::pair<unsigned long long*, unsigned int*>> old;   // outgrown tables, freed at the next sample / destroy
     void read_fill() {   // (the copy of the tallies has arrived)
         fill_known = 0; fill_unknown_upper = 0; fill_pending = false;
-        for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) fill_known += h_fill[i];
+        for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) fill_known += h_fill.p[i];
     }
-    ~GrowTable() {
-        for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); }
-        if (h_fill) (void)hipHostFree(h_fill);
-        if (fill_ev) (void)hipEventDestroy(fill_ev);
-    }
+    ~GrowTable() { for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); } }
 };
 
 // bk_kmer_dump_enable: the sample's count table of every strand-specific k-mer (bk_kmer_dump.hip) and, per finalized mate file, its
@@ -146,24 +199,28 @@ struct KmerDump {
     int finalized_mates = 0;                // mate files the last finalize selected (0: none, or finalized by shards)
 };
 
-// bk_primers_set: the primer table (bk_primers.hip) and the sample's trim counters
-struct Primers {
+// What bk_primers_set and bk_adapters_set keep alike: the sample's counters and whether the stage was set when the sample began
+struct TrimStage {
+    const uint32_t n_stats;                 // counters per mate file
+    DevBuf<unsigned long long> stats;       // [2][n_stats] (zeroed by bk_sample_begin)
+    bool in_sample = false;                 // set when the current / last sample began
+    explicit TrimStage(uint32_t n_stats_) : n_stats(n_stats_) {}
+};
+// bk_primers_set: the primer table (bk_primers.hip); stats: reads trimmed at 5', at 3', bases masked
+struct Primers : TrimStage {
+    Primers() : TrimStage(3) {}
     DevBuf<uint32_t> table;                 // [n][bk::kPrimerEntryWords]
     uint32_t n = 0;
     uint32_t max_mismatches = 0;
-    DevBuf<unsigned long long> stats;       // [2][3] per mate file: reads trimmed at 5', at 3', bases masked (zeroed by bk_sample_begin)
-    bool in_sample = false;                 // set when the current / last sample began
 };
-
-// bk_adapters_set: the adapter table as the kernels take it (bk_adapters.hip), the per-record scratch and the sample's counters
-struct Adapters {
-    bk::AdapterEntry entry[bk::kMaxAdapters];
+// bk_adapters_set: the adapter table as the kernels take it (bk_adapters.hip) and the per-record scratch; stats: reads cut, bases removed
+struct Adapters : TrimStage {
+    Adapters() : TrimStage(2) {}
+    bk::AdapterEntry entry[bk::kMaxAdapters] = {};
     uint32_t n = 0;
     uint32_t min_overlap = 0;
     uint64_t allowed_steps = 0;             // bk::AdapterArgs::allowed_steps
     DevBuf<uint32_t> cut;                   // [records of the largest batch so far] bk::kNoCut between launches
-    DevBuf<unsigned long long> stats;       // [2][2] per mate file: reads cut, bases removed (zeroed by bk_sample_begin)
-    bool in_sample = false;                 // set when the current / last sample began
 };
 
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
@@ -335,30 +392,27 @@ struct bk_engine {
     DevBuf<unsigned long long> kstats;      // [2][4]
     // bk_push_reads_packed: two staging slots, so that the copy of a batch overlaps the scan of the previous one
     struct StageSlot {
-        DevBuf<uint32_t> words; DevBuf<uint16_t> lens;
-        DevBuf<uint8_t> ends;                       // bk_push_reads_packed_ends with primers or adapters set: the records' end flags
-        uint8_t* h = nullptr; size_t h_cap = 0;     // pinned host copy of the caller's batch (words, then lens, then end flags)
-        hipEvent_t done = nullptr; bool busy = false;
+        RecordBufs rec;
+        PinnedBuf<uint8_t> h;                   // pinned host copy of the caller's batch (words, then lens, then end flags)
+        Event done; bool busy = false;
     } stage[2];
     int next_stage = 0;
 
     // asynchronous ASCII ingest (bk_push_reads_ascii): pinned staging + device buffers per slot
     struct IngestSlot {
-        uint8_t* h_bases = nullptr; size_t h_bases_cap = 0;
-        unsigned long long* h_off = nullptr; size_t h_off_cap = 0;
-        DevBuf<uint8_t> d_bases;
-        uint8_t* h_quals = nullptr; size_t h_quals_cap = 0;   // bk_push_reads_ascii_qual: the quality lines (first use allocates)
-        DevBuf<uint8_t> d_quals;
+        PinnedBuf<uint8_t> h_bases, h_quals;    // (h_quals, d_quals: bk_push_reads_ascii_qual's quality lines; first use allocates)
+        PinnedBuf<unsigned long long> h_off;
+        DevBuf<uint8_t> d_bases, d_quals;
         DevBuf<unsigned long long> d_off, d_nrec;
-        DevBuf<uint32_t> d_work;           // pack_words_kernel's work list
-        DevBuf<uint32_t> d_words;
-        DevBuf<uint16_t> d_lens;
-        DevBuf<uint8_t> d_ends;            // primers or adapters set: the records' end flags (the *_ends_kernel variants of K0)
-        hipEvent_t uploaded = nullptr, done = nullptr;
+        DevBuf<uint32_t> d_work;               // pack_words_kernel's work list
+        RecordBufs rec;                        // what the packer writes (with primers or adapters set, the *_ends_kernel variants of K0)
+        Event uploaded, done;
         bool busy = false;
     };
     IngestSlot slots[3];
-    IngestSlot dev_ascii;                   // bk_push_reads_ascii_device: the packed records of the batch being scanned (device buffers only)
+    // the device pushes' records (device buffers only, ordered by the engine's stream): what the packer makes of a
+    // bk_push_reads_ascii*_device batch, and the copy of a bk_push_reads_packed_ends_device batch that is trimmed
+    IngestSlot dev_ascii;
     int next_slot = 0;
     hipStream_t copy_stream = nullptr;
 
@@ -398,5 +452,8 @@ struct bk_engine {
         }
     };
 };
+
+// The scan of a batch of records and all that follows it on the engine's stream (bk_engine.cpp); every push of bk_ingest.cpp ends here
+int push_device(bk_engine* e, int mate, const Records& r);
 
 #pragma GCC visibility pop

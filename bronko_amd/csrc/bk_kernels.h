@@ -236,7 +236,7 @@ void launch_pack_reads(const PackArgs& a, unsigned long long* tally, hipStream_t
 // A record's end flags: its first base is its read's first letter / its last base is its read's last letter (a chunk of a run
 // that was cut into several records carries neither).
 constexpr uint32_t kEndFirst = 1u, kEndLast = 2u;
-constexpr uint32_t kPrimerMinLen = 12, kPrimerMaxLen = 64, kMaxPrimers = 1024, kMaxPrimerMismatches = 3;
+constexpr uint32_t kPrimerMinLen = BK_PRIMER_MIN_LEN, kPrimerMaxLen = BK_PRIMER_MAX_LEN, kMaxPrimers = BK_MAX_PRIMERS, kMaxPrimerMismatches = BK_PRIMER_MAX_MISMATCHES;   // (the limits of include/bronko_hip.h)
 // A primer table entry: the primer's 2-bit codes at bases [0, len) of words 0..3, its reverse complement at positions
 // [64 - len, 64) of words 4..7 (so that it ends where a window of a record's last 64 bases ends), len in word 8; unused bits 0.
 constexpr uint32_t kPrimerEntryWords = 9;

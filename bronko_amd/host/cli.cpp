@@ -319,7 +319,7 @@ int run_build(const Args& a) {
 std::vector<std::string> g_primers;   // (set by check_call_args)
 int g_primer_mismatches = 1;
 std::vector<std::string> read_primers(const char* T, const std::string& path) {
-    constexpr size_t kMinLen = 12, kMaxLen = 64, kMaxPrimers = 1024;
+    constexpr size_t kMinLen = BK_PRIMER_MIN_LEN, kMaxLen = BK_PRIMER_MAX_LEN, kMaxPrimers = BK_MAX_PRIMERS;   // (bk_primers_set's limits)
     std::vector<std::string> out, names;
     try {
         GzLineReader in(path);
@@ -404,7 +404,8 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.first_pairs.size() != a.second_pairs.size()) die(T, "Number of paired end sequences do not match, exiting.");
     if (a.min_base_qual < 0 || a.min_base_qual > 93) die(T, "Minimum base quality must be between 0 and 93 (Phred+33), got " + std::to_string(a.min_base_qual));
     if (a.has_primer_mismatches && !a.has_primers) die(T, "--primer-mismatches needs --primers");
-    if (a.primer_mismatches < 0 || a.primer_mismatches > 3) die(T, "Primer mismatches must be between 0 and 3, got " + std::to_string(a.primer_mismatches));
+    if (a.primer_mismatches < 0 || a.primer_mismatches > BK_PRIMER_MAX_MISMATCHES)
+        die(T, "Primer mismatches must be between 0 and " + std::to_string(BK_PRIMER_MAX_MISMATCHES) + ", got " + std::to_string(a.primer_mismatches));
     if (a.has_primers) { g_primers = read_primers(T, a.primers); g_primer_mismatches = (int)a.primer_mismatches; }
     if (a.has_adapter_min_overlap && a.adapters.empty()) die(T, "--adapter-min-overlap needs --adapter");
     if (a.has_adapter_error_rate && a.adapters.empty()) die(T, "--adapter-error-rate needs --adapter");
@@ -690,19 +691,21 @@ uint64_t push_fastqs(const std::vector<bk_engine*>& engs, const std::vector<std:
             if (done[m]) continue;
             FastqBatch b = queues[m].take();
             if (!b.error.empty() && error.empty()) error = b.error;
+            // (a batch that is pushed goes to the next engine in turn)
+            const bool pushed = error.empty() && (b.is_packed ? b.packed.n_records != 0 : b.off.size() > 1);
+            bk_engine* const eng = pushed ? engs[n_batches++ % engs.size()] : nullptr;
             if (error.empty() && b.is_packed) {
-                if (b.packed.n_records && (!g_primers.empty() || !g_adapters.empty()))
-                    hip_check(bk_push_reads_packed_ends(engs[n_batches++ % engs.size()], (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(),
-                                                        b.packed.ends.data(), b.packed.n_records), "bk_push_reads_packed_ends");
-                else if (b.packed.n_records)
-                    hip_check(bk_push_reads_packed(engs[n_batches++ % engs.size()], (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(), b.packed.n_records), "bk_push_reads_packed");
+                if (pushed && (!g_primers.empty() || !g_adapters.empty()))
+                    hip_check(bk_push_reads_packed_ends(eng, (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(), b.packed.ends.data(), b.packed.n_records),
+                              "bk_push_reads_packed_ends");
+                else if (pushed)
+                    hip_check(bk_push_reads_packed(eng, (int)m, b.packed.words.data(), b.packed.stride, b.packed.lens.data(), b.packed.n_records), "bk_push_reads_packed");
                 n_reads += b.packed.n_reads;
-            } else if (error.empty() && b.off.size() > 1 && g_min_qual > 0) {
-                hip_check(bk_push_reads_ascii_qual(engs[n_batches++ % engs.size()], (int)m, reinterpret_cast<const uint8_t*>(b.buf.data()),
-                                                   reinterpret_cast<const uint8_t*>(b.qual.data()), b.off.data(), b.off.size() - 1, g_min_qual), "bk_push_reads_ascii_qual");
-                n_reads += b.off.size() - 1;
-            } else if (error.empty() && b.off.size() > 1) {
-                hip_check(bk_push_reads_ascii(engs[n_batches++ % engs.size()], (int)m, reinterpret_cast<const uint8_t*>(b.buf.data()), b.off.data(), b.off.size() - 1), "bk_push_reads_ascii");
+            } else if (pushed) {
+                const uint8_t* bases = reinterpret_cast<const uint8_t*>(b.buf.data());
+                if (g_min_qual > 0)
+                    hip_check(bk_push_reads_ascii_qual(eng, (int)m, bases, reinterpret_cast<const uint8_t*>(b.qual.data()), b.off.data(), b.off.size() - 1, g_min_qual), "bk_push_reads_ascii_qual");
+                else hip_check(bk_push_reads_ascii(eng, (int)m, bases, b.off.data(), b.off.size() - 1), "bk_push_reads_ascii");
                 n_reads += b.off.size() - 1;
             }
             if (b.last) { done[m] = true; left--; }
@@ -1051,46 +1054,39 @@ int run_call(const Args& a) {
         LOG_INFO(T, std::to_string(total_reads) + " reads counted from " + mates[0]);
         return total_reads;
     };
-    // --primers: every engine that takes reads trims them (bk_primers_set is per engine); under --verbose, what was trimmed per reads file
-    auto set_primers = [&](bk_engine* e) {
-        if (g_primers.empty() || !e) return;
+    // --adapter, --primers: every engine that takes reads trims them (bk_adapters_set, bk_primers_set are per engine); under
+    // --verbose, what was trimmed per reads file, summed over the sample's engines
+    auto set_seqs = [](const std::vector<std::string>& list, auto&& set) {   // set(seqs, lens, n): the bk_*_set call
         std::vector<const uint8_t*> seqs;
         std::vector<uint32_t> lens;
-        for (const auto& p : g_primers) { seqs.push_back(reinterpret_cast<const uint8_t*>(p.data())); lens.push_back((uint32_t)p.size()); }
-        hip_check(bk_primers_set(e, seqs.data(), lens.data(), (uint32_t)seqs.size(), g_primer_mismatches), "bk_primers_set");
+        for (const auto& p : list) { seqs.push_back(reinterpret_cast<const uint8_t*>(p.data())); lens.push_back((uint32_t)p.size()); }
+        if (!list.empty()) set(seqs.data(), lens.data(), (uint32_t)seqs.size());
     };
-    auto log_primer_stats = [&](const std::vector<bk_engine*>& engs, const std::vector<std::string>& mates) {
-        if (g_primers.empty() || g_level < 4) return;
+    auto set_trims = [&](bk_engine* e) {
+        if (!e) return;
+        set_seqs(g_adapters, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_adapters_set(e, q, l, n, g_adapter_min_overlap, g_adapter_error_rate), "bk_adapters_set"); });
+        set_seqs(g_primers, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_primers_set(e, q, l, n, g_primer_mismatches), "bk_primers_set"); });
+    };
+    // text(sum): the line's start; stats(e, mate, out): the bk_*_stats call, n counters a mate file
+    auto log_sums = [&](const std::vector<bk_engine*>& engs, const std::vector<std::string>& mates, int n, auto&& stats, const char* fn, auto&& text) {
         for (size_t m = 0; m < mates.size(); m++) {
             uint64_t sum[3] = {0, 0, 0};
             for (bk_engine* e : engs) {
-                uint64_t o[3];
-                hip_check(bk_primer_stats(e, (int)m, o), "bk_primer_stats");
-                for (int i = 0; i < 3; i++) sum[i] += o[i];
+                uint64_t o[3] = {0, 0, 0};
+                hip_check(stats(e, (int)m, o), fn);
+                for (int i = 0; i < n; i++) sum[i] += o[i];
             }
-            LOG_TRACE(T, "primers: " + std::to_string(sum[0]) + " reads trimmed at the 5' end, " + std::to_string(sum[1]) + " at the 3' end, " +
-                             std::to_string(sum[2]) + " bases masked in " + mates[m]);
+            LOG_TRACE(T, text(sum) + " in " + mates[m]);
         }
     };
-    // --adapter: the same for the adapters
-    auto set_adapters = [&](bk_engine* e) {
-        if (g_adapters.empty() || !e) return;
-        std::vector<const uint8_t*> seqs;
-        std::vector<uint32_t> lens;
-        for (const auto& p : g_adapters) { seqs.push_back(reinterpret_cast<const uint8_t*>(p.data())); lens.push_back((uint32_t)p.size()); }
-        hip_check(bk_adapters_set(e, seqs.data(), lens.data(), (uint32_t)seqs.size(), g_adapter_min_overlap, g_adapter_error_rate), "bk_adapters_set");
-    };
-    auto log_adapter_stats = [&](const std::vector<bk_engine*>& engs, const std::vector<std::string>& mates) {
-        if (g_adapters.empty() || g_level < 4) return;
-        for (size_t m = 0; m < mates.size(); m++) {
-            uint64_t sum[2] = {0, 0};
-            for (bk_engine* e : engs) {
-                uint64_t o[2];
-                hip_check(bk_adapter_stats(e, (int)m, o), "bk_adapter_stats");
-                for (int i = 0; i < 2; i++) sum[i] += o[i];
-            }
-            LOG_TRACE(T, "adapters: " + std::to_string(sum[0]) + " reads cut, " + std::to_string(sum[1]) + " bases removed in " + mates[m]);
-        }
+    auto log_trim_stats = [&](const std::vector<bk_engine*>& engs, const std::vector<std::string>& mates) {
+        if (g_level < 4) return;
+        if (!g_adapters.empty())
+            log_sums(engs, mates, 2, bk_adapter_stats, "bk_adapter_stats", [](const uint64_t* s) {
+                return "adapters: " + std::to_string(s[0]) + " reads cut, " + std::to_string(s[1]) + " bases removed"; });
+        if (!g_primers.empty())
+            log_sums(engs, mates, 3, bk_primer_stats, "bk_primer_stats", [](const uint64_t* s) {
+                return "primers: " + std::to_string(s[0]) + " reads trimmed at the 5' end, " + std::to_string(s[1]) + " at the 3' end, " + std::to_string(s[2]) + " bases masked"; });
     };
     constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
     const int dump_threads = (int)std::max<size_t>(1, std::min<size_t>(16, (size_t)a.threads / std::max<size_t>(1, lanes.size())));
@@ -1103,7 +1099,7 @@ int run_call(const Args& a) {
         // finalize, then reference selection + baseline noise + variant calls, all on the device and asynchronous
         // (bk_sample_call); the pileup arrays only travel when --pileup wants them written
         if (!finalized) hip_check(bk_sample_finalize(e, n_mates), "bk_sample_finalize");   // (a sharded sample: sharded_finalize has done it)
-        if (!finalized) { log_adapter_stats(std::vector<bk_engine*>{e}, mates); log_primer_stats(std::vector<bk_engine*>{e}, mates); }
+        if (!finalized) log_trim_stats(std::vector<bk_engine*>{e}, mates);
         bk_call_params dcp;
         bk_call_params_default(&dcp);
         dcp.k = cp.k; dcp.no_end_filter = cp.no_end_filter; dcp.no_strand_filter = cp.no_strand_filter;
@@ -1189,14 +1185,13 @@ int run_call(const Args& a) {
     };
 
     if (shard_mode) {
-        for (bk_engine* e : shards.engs) { set_adapters(e); set_primers(e); }
+        for (bk_engine* e : shards.engs) set_trims(e);
         for (size_t i = 0; i < samples.size(); i++) {
             const auto& mates = samples[i];
             LOG_INFO(T, mates.size() == 1 ? "Processing " + mates[0] : "Processing paired reads " + mates[0] + ", " + mates[1]);
             ingest(shards.engs, mates, i);
             sharded_finalize(shards, (int)mates.size(), cells4);
-            log_adapter_stats(shards.engs, mates);
-            log_primer_stats(shards.engs, mates);
+            log_trim_stats(shards.engs, mates);
             complete(shards.engs[0], mates, i, true);
         }
         for (auto c : shards.comms) nccl_check(ncclCommDestroy(c), "ncclCommDestroy");
@@ -1205,7 +1200,7 @@ int run_call(const Args& a) {
     for (size_t i = 0; i < samples.size() && !lanes.empty(); i++) lanes[i % lanes.size()].mine.push_back(i);
     auto run_lane = [&](Lane& ln) {
         if (ln.mine.size() > 1) hip_check(bk_engine_fork(ln.eng.e, &ln.fork.e), "bk_engine_fork");
-        for (bk_engine* e : {ln.eng.e, ln.fork.e}) { set_adapters(e); set_primers(e); }
+        for (bk_engine* e : {ln.eng.e, ln.fork.e}) set_trims(e);
         if (a.keep_kmer_info)   // (the table grows with the sample)
             for (bk_engine* e : {ln.eng.e, ln.fork.e})
                 if (e) hip_check(bk_kmer_dump_enable(e, kDumpTableLog2), "bk_kmer_dump_enable");

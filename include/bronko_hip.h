@@ -281,6 +281,10 @@ int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* cou
  * read is N.  Only whole primers anchored at a read end match: no indels, no internal or partial occurrences, and none at the
  * ends of a run so long that it is cut into several records.  Every result equals that of the same pushes, without primers, of
  * the reads with those letters replaced by N. */
+#define BK_PRIMER_MIN_LEN 12
+#define BK_PRIMER_MAX_LEN 64
+#define BK_MAX_PRIMERS 1024
+#define BK_PRIMER_MAX_MISMATCHES 3
 int bk_primers_set(bk_engine* e, const uint8_t* const* seqs, const uint32_t* lens, uint32_t n, int max_mismatches);
 /* Packed records with their end flags, one byte a record: bit 0 = the record's first base is its read's first letter, bit 1 =
  * its last base is its read's last letter (a chunk of a cut run carries neither); bk_pack_reads_flat_ends writes them.  With
