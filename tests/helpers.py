@@ -90,6 +90,37 @@ def assert_same_pileup(res, pile):
     assert np.array_equal(res.present, pile.present)
 
 
+def assert_same_calls(oracle, ix, eng, pile, best, op):
+    """What bk_sample_call left on the engine against the oracle's call_variants / baseline_noise of genome `best` on `pile` with the
+    oracle parameters `op`: the genome, the counts and the coverage summary, every record field by field -- integers and AF bit for
+    bit, SOR to 1e-12 relative and the same "%.3f" text -- and Noise.max of every position bit for bit.  Returns the number of records."""
+    recs, out, n, nmaj, nmin, breadth, depth = oracle.call_variants(ix, best, pile, op)
+    summ, drecs = eng.download_calls()
+    assert summ.file_id == best
+    assert (summ.n_records, summ.n_major, summ.n_minor) == (n, nmaj, nmin)
+    assert summ.covered / summ.positions == breadth
+    assert (summ.coverage / summ.covered if summ.covered else float("nan")) == depth or (summ.covered == 0 and np.isnan(depth))
+    assert len(drecs) == n
+    for d, o in zip(drecs, recs):
+        assert (d.seq_id, d.pos, d.ref_base, d.alt_base) == (o["seq_id"], o["pos"], o["ref_base"], o["alt_base"])
+        assert (d.fwd_ref, d.rev_ref, d.fwd_alt, d.rev_alt, d.depth) == (o["fwd_ref"], o["rev_ref"], o["fwd_alt"], o["rev_alt"], o["depth"])
+        assert d.af == o["af"]
+        assert abs(d.sor - o["sor"]) <= 1e-12 * max(1.0, abs(o["sor"]))
+        assert "%.3f" % d.sor == "%.3f" % o["sor"]
+    oracle.lib().orc_free(out)
+    # Noise.max of every position of the selected genome, bit for bit (every sequence of the genome is its own walk)
+    if best >= 0:
+        lo, ncell = ix.genome_cells(best)
+        want = []
+        for s_lo, s_n in ix.sequence_cells(best):
+            want.append(oracle.baseline_noise(pile.fwd_depth[s_lo * 4:(s_lo + s_n) * 4], pile.rev_depth[s_lo * 4:(s_lo + s_n) * 4])[0])
+        want = np.concatenate(want) if want else np.zeros(0)
+        got = eng.download_noise()
+        assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), \
+            "noise differs at %s" % np.nonzero(got.view(np.uint64) != want.view(np.uint64))[0][:5]
+    return n
+
+
 def hpv_reads(n, seed, read_len=150, err=0.005, with_n=False, ragged=False):
     g = synth.read_fasta_bytes(os.path.join(GOLDEN, "HPV16.fa"))
     gm, isnv = synth.sample_genome(g, seed)

@@ -3,7 +3,6 @@ host restatement of call.rs:422-502 / :799-967 / :969-1150: the same genome, the
 (one correctly rounded division), SOR to the last few ulps (the device's ln) -- and the same coverage summary."""
 import os
 
-import numpy as np
 import pytest
 
 from bronko_amd import synth
@@ -22,32 +21,8 @@ def _compare(oracle, ix, eng, mates, k, **overrides):
     for name, v in overrides.items():
         setattr(op, name, v)
         setattr(dp, name, v)
-    recs, out, n, nmaj, nmin, breadth, depth = oracle.call_variants(ix, best, pile, op)
     eng.sample_call(len(mates), dp)
-    summ, drecs = eng.download_calls()
-    assert summ.file_id == best
-    assert (summ.n_records, summ.n_major, summ.n_minor) == (n, nmaj, nmin)
-    assert summ.covered / summ.positions == breadth
-    assert (summ.coverage / summ.covered if summ.covered else float("nan")) == depth or (summ.covered == 0 and np.isnan(depth))
-    assert len(drecs) == n
-    for d, o in zip(drecs, recs):
-        assert (d.seq_id, d.pos, d.ref_base, d.alt_base) == (o["seq_id"], o["pos"], o["ref_base"], o["alt_base"])
-        assert (d.fwd_ref, d.rev_ref, d.fwd_alt, d.rev_alt, d.depth) == (o["fwd_ref"], o["rev_ref"], o["fwd_alt"], o["rev_alt"], o["depth"])
-        assert d.af == o["af"]
-        assert abs(d.sor - o["sor"]) <= 1e-12 * max(1.0, abs(o["sor"]))
-        assert "%.3f" % d.sor == "%.3f" % o["sor"]
-    oracle.lib().orc_free(out)
-    # Noise.max of every position of the selected genome, bit for bit (every sequence of the genome is its own walk)
-    if best >= 0:
-        lo, ncell = ix.genome_cells(best)
-        want = []
-        for s_lo, s_n in ix.sequence_cells(best):
-            want.append(oracle.baseline_noise(pile.fwd_depth[s_lo * 4:(s_lo + s_n) * 4], pile.rev_depth[s_lo * 4:(s_lo + s_n) * 4])[0])
-        want = np.concatenate(want) if want else np.zeros(0)
-        got = eng.download_noise()
-        assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), \
-            "noise differs at %s" % np.nonzero(got.view(np.uint64) != want.view(np.uint64))[0][:5]
-    return n
+    return helpers.assert_same_calls(oracle, ix, eng, pile, best, op)
 
 
 def test_hpv_single_end_calls(oracle, golden_dir):
