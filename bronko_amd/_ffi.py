@@ -45,6 +45,15 @@ class CallSummary(C.Structure):  # bk_call_summary
                 ("covered", C.c_uint64), ("positions", C.c_uint64), ("coverage", C.c_uint64)]
 
 
+class ConsensusParams(C.Structure):  # bk_consensus_params
+    _fields_ = [("min_depth", C.c_uint64), ("min_freq", C.c_double)]
+
+
+class ConsensusSummary(C.Structure):  # bk_consensus_summary
+    _fields_ = [("file_id", C.c_int32), ("pad", C.c_uint32), ("positions", C.c_uint64), ("called", C.c_uint64), ("ambiguous", C.c_uint64),
+                ("masked", C.c_uint64), ("substitutions", C.c_uint64)]
+
+
 class BuiltIndex(C.Structure):  # bk_built_index
     _fields_ = [("n_buckets", C.c_uint64), ("n_entries", C.c_uint64), ("bucket_ids", C.c_void_p), ("bucket_off", C.c_void_p),
                 ("entries", C.c_void_p)]
@@ -60,6 +69,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_adapters_set", "bk_adapter_stats",
            "bk_pileup_device_ptr", "bk_sample_download", "bk_sample_finish", "bk_pack_reads", "bk_pack_reads_flat",
            "bk_timing_enable", "bk_timing_read", "bk_call_params_default", "bk_sample_call", "bk_sample_download_calls", "bk_sample_download_noise",
+           "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -176,6 +186,11 @@ def load(testing=None):
     L.bk_sample_download_calls.argtypes = [vp, C.POINTER(CallSummary), vp, u64]
     L.bk_sample_download_noise.restype = C.c_int
     L.bk_sample_download_noise.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.bk_consensus_params_default.argtypes = [C.POINTER(ConsensusParams)]
+    L.bk_sample_consensus.restype = C.c_int
+    L.bk_sample_consensus.argtypes = [vp, C.POINTER(ConsensusParams)]
+    L.bk_sample_download_consensus.restype = C.c_int
+    L.bk_sample_download_consensus.argtypes = [vp, C.POINTER(ConsensusSummary), vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

@@ -2,6 +2,7 @@
 //   select_genome   pick_best_genome / _paired       /root/reference/src/call.rs:422-502
 //   noise           get_baseline_noise               call.rs:799-967
 //   call            call_variants                    call.rs:969-1150
+//   consensus       (bk_sample_consensus: not in the reference) one IUPAC letter per position of the selected genome
 // so that a host with many samples in flight never waits between a sample's reads and its variant records.
 //
 // Exactness.  Everything up to the decisions is IEEE double arithmetic in the reference's order: +, -, *, / and sqrt are
@@ -15,6 +16,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 
 #include "bk_device.h"
 #include "bk_kernels.h"
@@ -532,6 +534,84 @@ __global__ __launch_bounds__(256) void call_kernel(CallArgs a) {
         if (red[1]) atomicAdd(&a.out->coverage, red[1]);
         if (red[2]) atomicAdd(&a.out->positions, red[2]);
     }
+}
+
+// The consensus letter of every position of the selected genome (bk_sample_consensus), one thread per position.  The rule
+// (include/bronko_hip.h): below min_depth an N; else the bases in descending order of their counts are taken until their sum
+// reaches min_freq * depth, and every base that ties with the last one taken joins them.  Which bases those are needs no order
+// among equal counts: with `last` the count of the last base the walk takes, the set is {b : tot[b] >= last} -- a base before it
+// in the walk has at least that count, one behind it joins iff it has exactly that count.  So the counts are sorted without
+// their codes (the network of noise_maf_kernel), three compares find `last`, four more make the bit mask.  The product and the
+// compare are the rule's: one double multiplication, (double)cum >= it.  With min_freq <= 1 the walk ends before it reaches a
+// count of 0 (cum < min_freq * depth implies cum < depth), so `last` > 0.
+__device__ const char kConsensusLetter[17] = "-ACMGRSVTWYHKDBN";   // by bit mask A = 1, C = 2, G = 4, T = 8
+__global__ __launch_bounds__(256) void consensus_kernel(ConsensusArgs a) {
+    __shared__ unsigned int red[5];
+    if (threadIdx.x < 5) red[threadIdx.x] = 0;
+    __syncthreads();
+    const int file = a.out->file_id;
+    unsigned int tally[5] = {0, 0, 0, 0, 0};   // positions, called, ambiguous, masked, substitutions (constant indices only)
+    if (file >= 0) {
+        const uint64_t cell_lo = a.seq_cell[a.seq_first[file]];
+        const int sq_hi = a.seq_first[file] + a.n_seqs[file];
+        const uint64_t cell_hi = a.n_seqs[file] ? a.seq_cell[sq_hi - 1] + a.seq_len[sq_hi - 1] : cell_lo;
+        for (uint64_t cell = cell_lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; cell < cell_hi; cell += (uint64_t)gridDim.x * blockDim.x) {
+            const unsigned long long* fr = a.pileup + 0 * a.plane + cell * 4;
+            const unsigned long long* rr = a.pileup + 1 * a.plane + cell * 4;
+            const unsigned long long t0 = fr[0] + rr[0], t1 = fr[1] + rr[1], t2 = fr[2] + rr[2], t3 = fr[3] + rr[3];
+            const unsigned long long depth = t0 + t1 + t2 + t3;
+            tally[0] += 1;
+            char letter = 'N';
+            if (depth < a.prm.min_depth) {
+                tally[3] += 1;
+            } else {
+                unsigned long long c0 = t0, c1 = t1, c2 = t2, c3 = t3, t;   // descending (a sorting network; equal values are interchangeable)
+                if (c0 < c1) { t = c0; c0 = c1; c1 = t; }
+                if (c2 < c3) { t = c2; c2 = c3; c3 = t; }
+                if (c0 < c2) { t = c0; c0 = c2; c2 = t; }
+                if (c1 < c3) { t = c1; c1 = c3; c3 = t; }
+                if (c1 < c2) { t = c1; c1 = c2; c2 = t; }
+                const double need = a.prm.min_freq * (double)depth;
+                unsigned long long last = c0;
+                if (!((double)c0 >= need)) {
+                    last = c1;
+                    if (!((double)(c0 + c1) >= need)) {
+                        last = c2;
+                        if (!((double)(c0 + c1 + c2) >= need)) last = c3;
+                    }
+                }
+                const unsigned mask = (t0 >= last ? 1u : 0u) | (t1 >= last ? 2u : 0u) | (t2 >= last ? 4u : 0u) | (t3 >= last ? 8u : 0u);
+                letter = kConsensusLetter[mask];
+                if ((mask & (mask - 1u)) == 0u) {   // one base: called
+                    const unsigned ref = (a.ref_words[cell >> 4] >> (2 * (cell & 15))) & 3u;   // non-ACGT counts as A (lcb.rs:53)
+                    tally[1] += 1;
+                    tally[4] += mask != (1u << ref) ? 1u : 0u;
+                } else {
+                    tally[2] += 1;
+                }
+            }
+            a.letters[cell - cell_lo] = (uint8_t)letter;
+        }
+    }
+    // each tally: summed over the wave, one LDS atomic per wave, one device atomic per workgroup (as call_kernel adds `covered`)
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        unsigned int v = tally[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&red[q], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < 5 && red[threadIdx.x]) {
+        static_assert(offsetof(ConsensusSummaryDev, substitutions) == offsetof(ConsensusSummaryDev, positions) + 4 * sizeof(uint64_t), "five consecutive tallies");
+        atomicAdd(reinterpret_cast<unsigned long long*>(&a.summary->positions) + threadIdx.x, (unsigned long long)red[threadIdx.x]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.summary->file_id = file;
+}
+
+void launch_consensus(const ConsensusArgs& a, uint64_t max_file_cells, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((max_file_cells + 255) / 256);   // call_kernel's grid
+    hipLaunchKernelGGL(consensus_kernel, dim3(blocks ? (blocks > 4096u ? 4096u : blocks) : 1u), dim3(256), 0, stream, a);
 }
 
 void launch_select_genome(const CallArgs& a, hipStream_t stream) {

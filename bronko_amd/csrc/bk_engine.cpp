@@ -277,7 +277,7 @@ int bk_sample_begin(bk_engine* e) {
     TrimStage* const trim_stages[] = {e->primers.get(), e->adapters.get()};
     for (TrimStage* t : trim_stages)
         if (t) { BK_HIP(hipMemsetAsync(t->stats.p, 0, t->stats.n * sizeof(unsigned long long), e->stream)); t->in_sample = true; }
-    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0;
+    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0; e->called = false; e->cons_made = false;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
     for (MatePlane& p : e->mate) { if (int rc = p.begin_sample(e)) return rc; }
@@ -1148,6 +1148,7 @@ int bk_sample_call(bk_engine* e, int n_mates, const bk_call_params* p) {
     bk_engine::Span sp(e, 1);
     bk::launch_call(a, ix.max_seqs_per_file, ix.max_file_cells, e->stream);
     BK_HIP(hipGetLastError());
+    e->called = true; e->cons_made = false;   // (a consensus made before this call was of another selection)
     return BK_OK;
 }
 
@@ -1181,6 +1182,52 @@ int bk_sample_download_noise(bk_engine* e, double* out, uint64_t cap, uint64_t* 
     const uint64_t lo = e->ix->file_cell_lo[(size_t)summ.file_id], hi = summ.file_id + 1 < e->ix->n_files ? e->ix->file_cell_lo[(size_t)summ.file_id + 1] : e->ix->total_cells;
     *n = hi - lo;
     if (out && cap) BK_HIP(hipMemcpy(out, e->call_noise.p + lo, (size_t)std::min<uint64_t>(cap, hi - lo) * sizeof(double), hipMemcpyDeviceToHost));
+    return BK_OK;
+}
+
+// ---- per-sample consensus (consensus_kernel, bk_caller.hip) ------------------------------------------------------
+void bk_consensus_params_default(bk_consensus_params* p) {
+    if (!p) return;
+    p->min_depth = 10; p->min_freq = 0.5;
+}
+
+int bk_sample_consensus(bk_engine* e, const bk_consensus_params* p) {
+    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
+    if (p->min_depth < 1) return fail(BK_ERR_INVALID, "bk_sample_consensus: min_depth must be at least 1, got %llu", (unsigned long long)p->min_depth);
+    if (!(p->min_freq >= 0.0 && p->min_freq <= 1.0)) return fail(BK_ERR_INVALID, "bk_sample_consensus: min_freq must be between 0 and 1, got %g", p->min_freq);
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_consensus comes after bk_sample_finalize and bk_sample_call");
+    if (!e->called) return fail(BK_ERR_STATE, "bk_sample_consensus: bk_sample_call has not run for this sample");
+    const IndexTables& ix = *e->ix;
+    BK_HIP(hipSetDevice(e->device));
+    if (!e->cons_out.p) {
+        BK_HIP(e->cons_letters.alloc((size_t)ix.max_file_cells));
+        BK_HIP(e->cons_out.alloc(1));
+    }
+    bk::ConsensusArgs a{};
+    a.prm = *p;
+    a.seq_first = ix.seq_first.p; a.n_seqs = ix.n_seqs_d.p; a.seq_cell = ix.seq_cell.p; a.seq_len = ix.seq_len_d.p;
+    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words();
+    a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
+    a.out = e->call_out.p; a.letters = e->cons_letters.p; a.summary = e->cons_out.p;
+    bk_engine::Span sp(e, 1);
+    BK_HIP(hipMemsetAsync(e->cons_out.p, 0, sizeof(bk_consensus_summary), e->stream));
+    bk::launch_consensus(a, ix.max_file_cells, e->stream);
+    BK_HIP(hipGetLastError());
+    e->cons_made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, uint8_t* letters, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->cons_made) return fail(BK_ERR_STATE, "bk_sample_download_consensus comes after this sample's bk_sample_consensus");
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipMemcpyAsync(summary, e->cons_out.p, sizeof *summary, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->positions, cap), e->cons_letters.n);
+    if (n && letters) {
+        BK_HIP(hipMemcpyAsync(letters, e->cons_letters.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+        BK_HIP(hipStreamSynchronize(e->stream));
+    }
     return BK_OK;
 }
 

@@ -430,6 +430,11 @@ struct bk_engine {
     DevBuf<bk_call_record> call_records;
     DevBuf<bk_call_summary> call_out;
     DevBuf<bk_call_summary> sel_out;        // pileup_selected_only: the genome selected between the two finalize passes
+    bool called = false;                    // bk_sample_call ran for the current sample (call_out.p only says: for some sample)
+    // bk_sample_consensus (first use allocates): a letter per cell of the largest genome, the summary; made for the current sample
+    DevBuf<uint8_t> cons_letters;
+    DevBuf<bk_consensus_summary> cons_out;
+    bool cons_made = false;
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

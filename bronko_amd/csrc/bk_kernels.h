@@ -418,6 +418,23 @@ struct CallArgs {
 };
 void launch_call(const CallArgs& a, int max_seqs_per_file, uint64_t max_file_cells, hipStream_t stream);
 void launch_select_genome(const CallArgs& a, hipStream_t stream);   // the first kernel of launch_call alone: a.out->file_id
+// bk_sample_consensus: one letter per position of the genome bk_sample_call selected (consensus_kernel, bk_caller.hip)
+typedef bk_consensus_params ConsensusParamsDev;
+typedef bk_consensus_summary ConsensusSummaryDev;
+struct ConsensusArgs {
+    ConsensusParamsDev prm;
+    const int32_t* seq_first;            // the geometry CallArgs has
+    const int32_t* n_seqs;
+    const uint64_t* seq_cell;
+    const uint64_t* seq_len;
+    const uint32_t* ref_words;
+    const unsigned long long* pileup;    // the two depth planes are read
+    size_t plane;
+    const CallSummaryDev* out;           // bk_sample_call's: file_id
+    uint8_t* letters;                    // [cells of the selected genome] in (sequence, position) order
+    ConsensusSummaryDev* summary;        // tallies zeroed by the caller; the kernel writes file_id and adds
+};
+void launch_consensus(const ConsensusArgs& a, uint64_t max_file_cells, hipStream_t stream);
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

@@ -412,6 +412,28 @@ class Engine:
         _check(self._L.bk_sample_download_noise(self.h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), self._L)
         return out[:n.value]
 
+    def consensus_params(self, **kw):
+        """bk_consensus_params with the defaults (min_depth 10, min_freq 0.5); keyword overrides."""
+        p = _ffi.ConsensusParams()
+        self._L.bk_consensus_params_default(C.byref(p))
+        for name, v in kw.items():
+            setattr(p, name, v)
+        return p
+
+    def sample_consensus(self, params=None):
+        """One consensus letter per position of the genome sample_call selected, on the device (asynchronous)."""
+        _check(self._L.bk_sample_consensus(self.h, C.byref(params or self.consensus_params())), self._L)
+
+    def download_consensus(self, cap=None):
+        """(summary, letters as bytes) of sample_consensus: min(cap, summary.positions) letters, all of them by default."""
+        summ = _ffi.ConsensusSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_consensus(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many letters there are)
+            cap = int(summ.positions)
+        buf = np.zeros(max(1, cap), np.uint8)
+        _check(self._L.bk_sample_download_consensus(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, buf[:min(cap, int(summ.positions))].tobytes()
+
     def timing_enable(self, on=True):
         _check(self._L.bk_timing_enable(self.h, int(on)), self._L)
 

@@ -205,6 +205,58 @@ CallSummary call_variants(const Index& ix, int file_id, const Pileup& p, const C
     return out;
 }
 
+Consensus consensus(const Index& ix, int file_id, const Pileup& p, const ConsensusParams& prm) {
+    static const char kLetter[] = "-ACMGRSVTWYHKDBN";              // by bit mask A = 1, C = 2, G = 4, T = 8
+    Consensus out;
+    uint64_t cell = 0;
+    for (int f = 0; f < file_id; f++) cell += ix.genome_len(f);
+    for (const SeqMeta& sm : ix.files[file_id].sequences) {
+        for (uint64_t i = 0; i < sm.len; i++, cell++) {
+            const uint64_t* fd = p.fwd_depth.data() + cell * 4;
+            const uint64_t* rd = p.rev_depth.data() + cell * 4;
+            std::array<std::pair<uint64_t, unsigned>, 4> by;        // (count, base code)
+            uint64_t depth = 0;
+            for (unsigned b = 0; b < 4; b++) { by[b] = {fd[b] + rd[b], b}; depth += by[b].first; }
+            out.positions += 1;
+            if (depth < prm.min_depth) { out.letters.push_back('N'); out.masked += 1; continue; }
+            std::sort(by.begin(), by.end(), [](const auto& x, const auto& y) { return x.first != y.first ? x.first > y.first : x.second < y.second; });
+            const double need = prm.min_freq * (double)depth;
+            unsigned mask = 0;
+            uint64_t cum = 0;
+            size_t j = 0;
+            do {                                                    // at least one base; a count of 0 is never taken
+                mask |= 1u << by[j].second;
+                cum += by[j].first;
+                j++;
+            } while (j < 4 && by[j].first != 0 && !((double)cum >= need));
+            for (; j < 4 && by[j].first != 0 && by[j].first == by[j - 1].first; j++) mask |= 1u << by[j].second;   // ties with the last one taken
+            out.letters.push_back(kLetter[mask]);
+            if ((mask & (mask - 1)) == 0) {
+                out.called += 1;
+                if (mask != 1u << nt_to_bits(sm.seq[i])) out.substitutions += 1;   // non-ACGT counts as A
+            } else {
+                out.ambiguous += 1;
+            }
+        }
+    }
+    return out;
+}
+
+void write_consensus_fasta(const std::string& out_path, const std::string& stem, const Index& ix, int file_id, const uint8_t* letters, uint64_t n) {
+    if (n != ix.genome_len((size_t)file_id)) throw std::runtime_error("write_consensus_fasta: the letters are not the genome's length");
+    File f(out_path);
+    if (!f.fp) throw std::runtime_error("Failed to create consensus fasta file " + out_path);
+    uint64_t at = 0;
+    for (const SeqMeta& sm : ix.files[file_id].sequences) {
+        fprintf(f.fp, ">%s|%s\n", stem.c_str(), first_token(sm.name).c_str());
+        for (uint64_t i = 0; i < sm.len; i += 60) {
+            const size_t m = (size_t)std::min<uint64_t>(60, sm.len - i);
+            if (fwrite(letters + at + i, 1, m, f.fp) != m || fputc('\n', f.fp) == EOF) throw std::runtime_error("Failed to write consensus fasta file " + out_path);
+        }
+        at += sm.len;
+    }
+}
+
 std::string clean_sample_id(const std::string& path) {
     static const char* const kSuffixes[] = {".fastq.gz", ".fasta.gz", "fna.gz", "fnq.gz", ".fq.gz", ".fastq",
                                             ".fasta", ".fnq", ".fna", ".fa", ".fq"};

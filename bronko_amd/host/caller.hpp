@@ -56,6 +56,21 @@ std::vector<double> baseline_noise_max(const uint64_t* fwd4, const uint64_t* rev
 // call.rs:969-1150 over the sequences of `file_id` in metadata order.
 CallSummary call_variants(const Index& ix, int file_id, const Pileup& p, const CallParams& prm);
 
+// --consensus: the rule of include/bronko_hip.h (bk_sample_consensus) in plain C++, for the genome's positions in metadata order.
+// The product's letters come from the device (consensus_kernel); this is its twin for the tests that need no GPU.
+struct ConsensusParams {
+    uint64_t min_depth = 10;
+    double   min_freq = 0.5;
+};
+struct Consensus {
+    std::string letters;             // one per position of the genome, in (sequence, position) order
+    uint64_t positions = 0, called = 0, ambiguous = 0, masked = 0, substitutions = 0;
+};
+Consensus consensus(const Index& ix, int file_id, const Pileup& p, const ConsensusParams& prm);
+// OUT/<stem>.consensus.fa: one record per sequence of the genome, in metadata order; header ">" stem "|" the sequence-name
+// token of the VCF's CHROM column; the letters (`n` of them, genome_len(file_id)) in lines of 60
+void write_consensus_fasta(const std::string& out_path, const std::string& stem, const Index& ix, int file_id, const uint8_t* letters, uint64_t n);
+
 std::string clean_sample_id(const std::string& path);                               // util.rs:30-50
 void write_vcf(const std::string& out_path, const std::string& reads_path_as_given, const Index& ix, int file_id,
                const std::vector<VcfRecord>& recs);                                 // call.rs:735-774

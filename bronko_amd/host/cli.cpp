@@ -106,6 +106,10 @@ struct Args {
     bool has_adapter_min_overlap = false, has_adapter_error_rate = false;
     long adapter_min_overlap = 5;   // --adapter-min-overlap: bases of an adapter's start that count as a match at the read's end
     double adapter_error_rate = 0.1;   // --adapter-error-rate: mismatches allowed per compared base (0..0.3)
+    bool consensus = false;         // --consensus: <DIR>/<stem>.consensus.fa, one IUPAC letter per position of the selected genome
+    bool has_consensus_min_depth = false, has_consensus_min_freq = false;
+    long consensus_min_depth = 10;  // --consensus-min-depth: positions with less depth are N
+    double consensus_min_freq = 0.5;   // --consensus-min-freq: share of the depth the letter's bases must reach together (0..1)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -122,7 +126,8 @@ struct Args {
           "            [--no-strand-balance-filter] [--balance-ratio F] [--n-per-strand N] [--strand_odds F]\n"
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
-          "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
+          "            [--consensus-min-freq F] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -134,7 +139,12 @@ struct Args {
           "                    (CTGTCTCTTATACACATCT) or a sequence (ACGT, 8..64 bases), at most 8; a read is truncated at the leftmost\n"
           "                    place of its last run of valid letters where an adapter, or at the read's end its start, matches\n"
           "  --adapter-min-overlap N  bases of an adapter's start that match at a read's end; 3..the shortest adapter, default 5\n"
-          "  --adapter-error-rate F   mismatches allowed per compared base (floor(F * length), no indels); 0..0.3, default 0.1\n", stderr);
+          "  --adapter-error-rate F   mismatches allowed per compared base (floor(F * length), no indels); 0..0.3, default 0.1\n"
+          "  --consensus       write the sample's consensus of the selected genome to <DIR>/<stem>.consensus.fa: per position the most\n"
+          "                    frequent bases that together reach F of the depth (more than one: an IUPAC code), N below depth D; no\n"
+          "                    filters, no indels, the reference's length\n"
+          "  --consensus-min-depth D  depth below which a position is N; at least 1, default 10\n"
+          "  --consensus-min-freq F   share of a position's depth its letter's bases reach together; 0..1, default 0.5\n", stderr);
     exit(code);
 }
 
@@ -240,6 +250,16 @@ Args parse_args(int argc, char** argv) {
             a.has_adapter_min_overlap = true;
             if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
         }
+        else if (opt == "--consensus") a.consensus = true;
+        else if (opt == "--consensus-min-depth") {   // (any integer, any number here: what is out of range is refused by check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            a.consensus_min_depth = strtol(v.c_str(), &end, 10);
+            a.has_consensus_min_depth = true;
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+        }
+        else if (opt == "--consensus-min-freq") { a.consensus_min_freq = to_double(opt, one()); a.has_consensus_min_freq = true; }
         else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
@@ -410,6 +430,14 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.has_adapter_min_overlap && a.adapters.empty()) die(T, "--adapter-min-overlap needs --adapter");
     if (a.has_adapter_error_rate && a.adapters.empty()) die(T, "--adapter-error-rate needs --adapter");
     if (!a.adapters.empty()) { g_adapters = expand_adapters(T, a); g_adapter_min_overlap = (uint32_t)a.adapter_min_overlap; g_adapter_error_rate = a.adapter_error_rate; }
+    if (a.has_consensus_min_depth && !a.consensus) die(T, "--consensus-min-depth needs --consensus");
+    if (a.has_consensus_min_freq && !a.consensus) die(T, "--consensus-min-freq needs --consensus");
+    if (a.consensus_min_depth < 1) die(T, "Consensus minimum depth must be at least 1, got " + std::to_string(a.consensus_min_depth));
+    if (!(a.consensus_min_freq >= 0.0 && a.consensus_min_freq <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "Consensus minimum frequency must be between 0 and 1, got %g", a.consensus_min_freq);
+        die(T, buf);
+    }
 }
 
 struct Engine {
@@ -1107,6 +1135,12 @@ int run_call(const Args& a) {
         dcp.strand_odds_max = cp.strand_odds_max; dcp.variant_multiplier = cp.variant_multiplier; dcp.n_per_strand = cp.n_per_strand;
         dcp.min_depth = cp.min_depth; dcp.min_variant_depth = cp.min_variant_depth;
         hip_check(bk_sample_call(e, n_mates, &dcp), "bk_sample_call");
+        if (a.consensus) {   // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
+            bk_consensus_params ccp;
+            bk_consensus_params_default(&ccp);
+            ccp.min_depth = (uint64_t)a.consensus_min_depth; ccp.min_freq = a.consensus_min_freq;
+            hip_check(bk_sample_consensus(e, &ccp), "bk_sample_consensus");
+        }
         if (a.pileup) { p.fwd_depth.resize(cells4); p.rev_depth.resize(cells4); }
         hip_check(bk_sample_download(e, n_mates, a.pileup ? p.fwd_depth.data() : nullptr, a.pileup ? p.rev_depth.data() : nullptr, nullptr, nullptr,
                                      stats.data(), present.data(), kstats.data()), "bk_sample_download");
@@ -1128,6 +1162,12 @@ int run_call(const Args& a) {
         std::vector<bk_call_record> drecs((size_t)(3 * longest));
         bk_call_summary summ{};
         hip_check(bk_sample_download_calls(e, &summ, drecs.data(), drecs.size()), "bk_sample_download_calls");
+        bk_consensus_summary csumm{};
+        std::vector<uint8_t> letters;
+        if (a.consensus) {
+            letters.resize((size_t)longest);
+            hip_check(bk_sample_download_consensus(e, &csumm, letters.data(), letters.size()), "bk_sample_download_consensus");
+        }
         p.stats.assign(n_files * 3, 0);
         p.present.assign(n_files, 0);
         uint64_t kept = 0;   // KMC "No. of unique counted k-mers", summed over mate files (call.rs:336)
@@ -1179,6 +1219,12 @@ int run_call(const Args& a) {
             if (a.pileup) { LOG_INFO(T, "Writing output to pileup"); write_pileup_tsv(a.output + "/" + stem + ".tsv", ix, best, p); }
             LOG_INFO(T, "Writing output to VCF");
             write_vcf(a.output + "/" + stem + ".vcf", mates[0], ix, best, cs.records);
+            if (a.consensus) {
+                LOG_INFO(T, "Consensus of " + std::to_string(csumm.positions) + " positions: " + std::to_string(csumm.called) + " called (" +
+                                std::to_string(csumm.substitutions) + " substitutions), " + std::to_string(csumm.ambiguous) + " ambiguous, " +
+                                std::to_string(csumm.masked) + " masked");
+                write_consensus_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, letters.data(), csumm.positions);
+            }
         } catch (const std::exception& ex) { die(T, ex.what()); }
         overview[sample_id] = OverviewRow{mates[0], gname, cs.n_major, cs.n_minor, cs.breadth, cs.depth, n_perfect, n_variant, n_unmapped};
         if (a.alignment) all_calls[sample_id] = SampleCalls{mates[0], gname, cs.breadth, cs.records};

@@ -3,6 +3,7 @@
 // include/bronko_hip.h); errors are returned as NULL / non-zero with bh_last_error().
 #include <cstdio>
 #include <cstring>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -112,6 +113,30 @@ int bh_call_and_write(const void* h, int file_id, const uint64_t* fwd_depth, con
         if (cov) { cov[0] = cs.breadth; cov[1] = cs.depth; }
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// the host twin of bk_sample_consensus on the two depth arrays: letters[genome_len(file_id)], tallies = {positions, called,
+// ambiguous, masked, substitutions}
+int bh_consensus(const void* h, int file_id, const uint64_t* fwd_depth, const uint64_t* rev_depth, uint64_t min_depth, double min_freq,
+                 uint8_t* letters, uint64_t* tallies) {
+    try {
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        if (file_id < 0 || (size_t)file_id >= ix->files.size()) throw std::runtime_error("bh_consensus: no such genome file");
+        const size_t n = ix->total_cells() * 4;
+        bronko::Pileup p;
+        p.fwd_depth.assign(fwd_depth, fwd_depth + n); p.rev_depth.assign(rev_depth, rev_depth + n);
+        bronko::ConsensusParams c;
+        c.min_depth = min_depth; c.min_freq = min_freq;
+        const bronko::Consensus r = bronko::consensus(*ix, file_id, p, c);
+        std::memcpy(letters, r.letters.data(), r.letters.size());
+        tallies[0] = r.positions; tallies[1] = r.called; tallies[2] = r.ambiguous; tallies[3] = r.masked; tallies[4] = r.substitutions;
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_consensus_fasta(const void* h, int file_id, const char* path, const char* stem, const uint8_t* letters, uint64_t n) {
+    try { bronko::write_consensus_fasta(path, stem, *static_cast<const bronko::Index*>(h), file_id, letters, n); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
 int bh_write_kmer_counts(const char* path, int k, const uint64_t* kmers, const uint64_t* counts, uint64_t n, int threads) {

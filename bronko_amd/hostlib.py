@@ -150,6 +150,10 @@ def _caller_lib():
         L.bh_call_and_write.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(CallParams), C.c_char_p, C.c_char_p, C.c_char_p, vp, vp]
         L.bh_write_kmer_counts.restype = C.c_int
         L.bh_write_kmer_counts.argtypes = [C.c_char_p, C.c_int, vp, vp, C.c_uint64, C.c_int]
+        L.bh_consensus.restype = C.c_int
+        L.bh_consensus.argtypes = [vp, C.c_int, vp, vp, C.c_uint64, C.c_double, vp, vp]
+        L.bh_write_consensus_fasta.restype = C.c_int
+        L.bh_write_consensus_fasta.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, vp, C.c_uint64]
         L.bh_clean_sample_id.restype = None
         L.bh_clean_sample_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L._caller_ready = True
@@ -197,4 +201,26 @@ def write_kmer_counts(path, k, kmers, counts, threads=4):
     assert len(km) == len(ct)
     L = _caller_lib()
     if L.bh_write_kmer_counts(path.encode(), k, km.ctypes.data, ct.ctypes.data, len(km), threads) != 0:
+        raise RuntimeError("bronko host: " + L.bh_last_error().decode(errors="replace"))
+
+
+def consensus(ix, file_id, fwd_depth, rev_depth, min_depth=10, min_freq=0.5):
+    """The host twin of bk_sample_consensus (caller.cpp consensus) on the two depth arrays of all cells: (letters as bytes,
+    (positions, called, ambiguous, masked, substitutions))."""
+    fd = np.ascontiguousarray(fwd_depth, np.uint64)
+    rd = np.ascontiguousarray(rev_depth, np.uint64)
+    assert len(fd) == len(rd) == ix.total_cells * 4
+    letters = np.zeros(max(1, ix.genome_len(file_id)), np.uint8)
+    tallies = np.zeros(5, np.uint64)
+    L = _caller_lib()
+    if L.bh_consensus(ix.h, file_id, fd.ctypes.data, rd.ctypes.data, int(min_depth), float(min_freq), letters.ctypes.data, tallies.ctypes.data) != 0:
+        raise RuntimeError("bronko host: " + L.bh_last_error().decode(errors="replace"))
+    return letters[:int(tallies[0])].tobytes(), tuple(int(t) for t in tallies)
+
+
+def write_consensus_fasta(path, stem, ix, file_id, letters):
+    """The --consensus writer (caller.cpp write_consensus_fasta)."""
+    buf = np.frombuffer(bytes(letters), np.uint8)
+    L = _caller_lib()
+    if L.bh_write_consensus_fasta(ix.h, file_id, path.encode(), stem.encode(), buf.ctypes.data if len(buf) else None, len(buf)) != 0:
         raise RuntimeError("bronko host: " + L.bh_last_error().decode(errors="replace"))

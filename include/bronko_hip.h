@@ -372,6 +372,38 @@ int  bk_sample_download_calls(bk_engine* e, bk_call_summary* summary, bk_call_re
  * the number of positions through *n (0 when no genome was selected).  Synchronises. */
 int  bk_sample_download_noise(bk_engine* e, double* out, uint64_t cap, uint64_t* n);
 
+/* ---- per-sample consensus (`bronko call --consensus`; additive, still v8) -------------------------------------------------
+ * One letter per position of the genome bk_sample_call selected, made from the two depth planes where they are; only the
+ * letters travel.  For a position, tot[b] = forward + reverse depth of base b (A C G T), depth = their sum:
+ *   depth < min_depth                 N, the position is masked;
+ *   else                              the bases in descending order of tot (equal counts: ascending base code) are taken one by
+ *                                     one, their counts summed in cum, until (double)cum >= min_freq * (double)depth -- at least
+ *                                     one is taken --, then every further base whose count equals the last taken one's joins
+ *                                     them; a base with count 0 is never taken.  The set as a bit mask (A = 1, C = 2, G = 4,
+ *                                     T = 8) indexes "-ACMGRSVTWYHKDBN".
+ * A set of one base is called, a larger one ambiguous (all four print as N); a called base that differs from the reference code
+ * of the cell (a non-ACGT reference letter counts as A, as in call_variants) is a substitution.  Integer arithmetic but for the
+ * one product.  No end, strand or noise filter (the consensus is the pileup's majority, independent of the records), no indels:
+ * the letters have the reference's length, in (sequence, position) order.
+ * min_depth >= 1 and 0 <= min_freq <= 1 (BK_ERR_INVALID otherwise, the parameter named).
+ *   bk_sample_consensus            after the sample's bk_sample_call (BK_ERR_STATE before it, inside a sample, and after a later
+ *                                  bk_sample_begin); asynchronous on the engine's stream.  Its buffers -- a byte per cell of the
+ *                                  largest genome, and the summary -- are allocated at the engine's first call: an engine that never
+ *                                  asks allocates and launches nothing.  Per engine: forks own theirs.
+ *   bk_sample_download_consensus   synchronises; copies min(cap, positions) letters (letters may be NULL).  No genome selected:
+ *                                  file_id = -1, every tally 0, no letters. */
+typedef struct { uint64_t min_depth; double min_freq; } bk_consensus_params;
+typedef struct {
+    int32_t  file_id;               /* the genome bk_sample_call selected, -1 = none */
+    uint32_t pad;
+    uint64_t positions;             /* letters there are = positions of the genome = called + ambiguous + masked */
+    uint64_t called, ambiguous, masked;
+    uint64_t substitutions;         /* called positions whose base is not the reference's */
+} bk_consensus_summary;
+void bk_consensus_params_default(bk_consensus_params* p);   /* 10, 0.5 */
+int  bk_sample_consensus(bk_engine* e, const bk_consensus_params* p);
+int  bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, uint8_t* letters, uint64_t cap);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
