@@ -140,6 +140,25 @@ std::vector<double> baseline_noise_max(const uint64_t* fwd4, const uint64_t* rev
     return out;
 }
 
+double strand_odds(uint64_t fwd_ref, uint64_t rev_ref, uint64_t fwd_alt, uint64_t rev_alt, const CallParams& prm, bool* tested) {
+    if (tested) *tested = false;
+    double sor = prm.strand_odds_max + 1.0;
+    if (!prm.no_strand_filter) {                                        // call.rs:1059-1096
+        const double a = (double)fwd_ref + 1.0, b = (double)rev_ref + 1.0;
+        const double c = (double)fwd_alt + 1.0, d = (double)rev_alt + 1.0;
+        const double min_strand = std::fmin(a + c, b + d) / (a + b + c + d);
+        if (!prm.no_strand_balance_filter || min_strand >= prm.strand_balance_ratio) {
+            const double r = (a * d) / (b * c);
+            sor = std::log(r + 1.0 / r) + std::log(std::fmin(a, b) / std::fmax(a, b))
+                  - std::log(std::fmin(c, d) / std::fmax(c, d));
+            if (tested) *tested = true;
+        } else {
+            sor = -1.0;
+        }
+    }
+    return sor;
+}
+
 CallSummary call_variants(const Index& ix, int file_id, const Pileup& p, const CallParams& prm) {
     CallSummary out;
     uint64_t covered = 0, positions = 0, coverage = 0;
@@ -168,20 +187,11 @@ CallSummary call_variants(const Index& ix, int file_id, const Pileup& p, const C
             coverage += depth;
             for (unsigned alt = 0; alt < 4; alt++) {
                 if (alt == ref || tot[alt] == 0) continue;
-                double sor = prm.strand_odds_max + 1.0;
-                if (!prm.no_strand_filter) {                                        // call.rs:1059-1096
-                    const double a = (double)row[ref] + 1.0, b = (double)rrow[ref] + 1.0;
-                    const double c = (double)row[alt] + 1.0, d = (double)rrow[alt] + 1.0;
-                    const double min_strand = std::fmin(a + c, b + d) / (a + b + c + d);
-                    if (!prm.no_strand_balance_filter || min_strand >= prm.strand_balance_ratio) {
-                        const double r = (a * d) / (b * c);
-                        sor = std::log(r + 1.0 / r) + std::log(std::fmin(a, b) / std::fmax(a, b))
-                              - std::log(std::fmin(c, d) / std::fmax(c, d));
-                        if (sor > prm.strand_odds_max) continue;
-                        if (fk[i * 4 + alt] < prm.n_per_strand && rk[i * 4 + alt] < prm.n_per_strand) continue;
-                    } else {
-                        sor = -1.0;
-                    }
+                bool tested = false;
+                const double sor = strand_odds(row[ref], rrow[ref], row[alt], rrow[alt], prm, &tested);
+                if (tested) {
+                    if (sor > prm.strand_odds_max) continue;
+                    if (fk[i * 4 + alt] < prm.n_per_strand && rk[i * 4 + alt] < prm.n_per_strand) continue;
                 }
                 const double af = (double)tot[alt] / (double)depth;
                 const double y0 = prm.variant_multiplier;

@@ -53,6 +53,10 @@ int pick_best_genome(const Index& ix, const std::vector<uint64_t>& stats, const 
 // call.rs:799-967 -- only Noise.max is consumed downstream (call.rs:1107); returned per position.
 std::vector<double> baseline_noise_max(const uint64_t* fwd4, const uint64_t* rev4, uint64_t len);
 
+// The strand odds ratio of an alternative base as the VCF prints it (call.rs:1059-1096), from its DP4 counts: strand_odds_max + 1
+// without the strand filter, -1.0 where the strand balance filter lets the base through untested.  *tested: the ratio was computed.
+double strand_odds(uint64_t fwd_ref, uint64_t rev_ref, uint64_t fwd_alt, uint64_t rev_alt, const CallParams& prm, bool* tested = nullptr);
+
 // call.rs:969-1150 over the sequences of `file_id` in metadata order.
 CallSummary call_variants(const Index& ix, int file_id, const Pileup& p, const CallParams& prm);
 

@@ -1,0 +1,93 @@
+// cli.hpp -- what the three units of the `bronko` binary share: the logger, die, hip_check, the parsed arguments and the
+// settings of one `bronko call` (cli.cpp: arguments, checks, build, main; reads.cpp: FASTQ files -> engine; call_run.cpp: engines,
+// lanes and the per-sample code).
+#pragma once
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../include/bronko_hip.h"
+#include "caller.hpp"
+#include "index.hpp"
+
+namespace bronko {
+
+bool log_enabled(int lvl);   // 0 error, 1 warn, 2 info, 3 debug, 4 trace (simple_logger levels, call.rs:31-43)
+void logf(int lvl, const char* tag, const char* target, const std::string& msg);
+#define LOG_ERROR(t, m) logf(0, "ERROR", t, m)
+#define LOG_WARN(t, m) logf(1, "WARN", t, m)
+#define LOG_INFO(t, m) logf(2, "INFO", t, m)
+#define LOG_DEBUG(t, m) logf(3, "DEBUG", t, m)
+#define LOG_TRACE(t, m) logf(4, "TRACE", t, m)
+
+[[noreturn]] void die(const char* target, const std::string& msg);   // `error!(..); std::process::exit(1)`
+void hip_check(int rc, const char* what);                            // a bk_* status: dies with bk_last_error()
+
+// ---- argument parsing (clap derive surface of cli.rs) -------------------------------------------------------
+struct Args {
+    std::string mode;
+    std::vector<std::string> genomes, reads, first_pairs, second_pairs;
+    bool has_genomes = false;
+    std::string db;
+    bool has_db = false;
+    long kmer = 21;                 // consts.rs:3
+    long min_kmers = 3;             // consts.rs:5
+    bool use_full_kmer = false;
+    long n_fixed = 2;               // consts.rs:17
+    double min_af = 0.03;
+    bool no_end_filter = false, no_strand_filter = false, no_strand_balance_filter = false;
+    double balance_ratio = 0.1;
+    long n_per_strand = 2;
+    double strand_odds = 6.0;
+    long min_depth = 300;
+    long min_variant_depth = 3;
+    double noise_multiplier = 1.5;
+    long min_base_qual = 0;         // --min-base-qual: bases below this Phred+33 quality are N before k-mer counting (0: off)
+    std::string primers;            // --primers: FASTA of amplicon primers trimmed from the read ends (empty: none)
+    bool has_primers = false, has_primer_mismatches = false;
+    long primer_mismatches = 1;     // --primer-mismatches: Hamming distance a primer match may have (0..3)
+    std::vector<std::string> adapters;   // --adapter: 3' adapters cut off the reads, preset names or sequences (empty: none)
+    bool has_adapter_min_overlap = false, has_adapter_error_rate = false;
+    long adapter_min_overlap = 5;   // --adapter-min-overlap: bases of an adapter's start that count as a match at the read's end
+    double adapter_error_rate = 0.1;   // --adapter-error-rate: mismatches allowed per compared base (0..0.3)
+    bool consensus = false;         // --consensus: <DIR>/<stem>.consensus.fa, one IUPAC letter per position of the selected genome
+    bool has_consensus_min_depth = false, has_consensus_min_freq = false;
+    long consensus_min_depth = 10;  // --consensus-min-depth: positions with less depth are N
+    double consensus_min_freq = 0.5;   // --consensus-min-freq: share of the depth the letter's bases must reach together (0..1)
+    std::string output;             // default depends on the mode
+    bool pileup = false, alignment = false, keep_kmer_info = false;
+    long threads = 4;
+    bool debug = false, verbose = false;
+};
+
+// threads a FASTQ file's inflate may take (pargz.hpp): -t over the files that are open at the same time.  With many files open at
+// once the files are the parallelism: 16 lanes x 4 inflate threads measured slower than 16 x 1 -- 3.5 s against 2.8 s for
+// 32 x 1 M reads -- while 7 lanes x 9 threads, a hundred-genome index, gain 19.2 -> 13.8 s.
+inline unsigned inflate_threads(long threads, size_t open_files) {
+    if (const char* it = getenv("BRONKO_INFLATE_THREADS")) return (unsigned)std::max(1, atoi(it));
+    return open_files > 8 ? 1u : (unsigned)std::max<size_t>(1, std::min<size_t>(64, (size_t)threads / open_files));
+}
+
+// The settings of one `bronko call` that the reader threads and the per-sample code share: made once from the checked arguments
+// (make_call_config, cli.cpp) before the first reader thread starts, const from then on.
+struct CallConfig {
+    int k = 21;                             // (the records a reader thread packs drop runs shorter than k)
+    int min_qual = 0;                       // --min-base-qual: bases below '!' + min_qual are N
+    std::vector<std::string> primers;       // --primers: the file's records
+    int primer_mismatches = 1;
+    std::vector<std::string> adapters;      // --adapter: preset names expanded
+    uint32_t adapter_min_overlap = 5;
+    double adapter_error_rate = 0.1;
+    unsigned ahead_inflate_threads = 1;     // for the files that are read ahead of their turn: -t over the files ReadAhead has open at once
+    CallParams cp;                          // the printed strand odds (strand_odds, caller.hpp)
+    bk_call_params call;                    // bk_sample_call
+    bk_consensus_params consensus;          // bk_sample_consensus (--consensus)
+    // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
+    bool trims() const { return !primers.empty() || !adapters.empty(); }
+};
+
+Index build_index_any(const char* T, int k, const std::vector<std::string>& genomes, int threads);   // cli.cpp
+int call_samples(const Args& a, const CallConfig& cfg);                                                // call_run.cpp
+
+}  // namespace bronko

@@ -155,7 +155,7 @@ def test_call_alignment_mfa(oracle, golden_dir, tmp_path):
 
 def test_call_three_samples_overlapped(oracle, golden_dir, tmp_path):
     """Several samples in one run: sample i+1 is ingested into a forked engine while a worker thread completes sample i
-    (cli.cpp).  Every sample's VCF and pileup TSV must equal the oracle's, and bronko_overview.tsv keeps the input order."""
+    (call_run.cpp).  Every sample's VCF and pileup TSV must equal the oracle's, and bronko_overview.tsv keeps the input order."""
     g = synth.read_fasta_bytes(os.path.join(golden_dir, "HPV16.fa"))
     ix = oracle.Index.load(os.path.join(golden_dir, "hpv.bkdb"))
     paths, samples = [], []
@@ -219,7 +219,7 @@ def test_call_samples_dealt_to_several_lanes_on_the_one_gpu_of_the_box(oracle, g
 
 def test_call_one_sample_sharded_through_rccl(oracle, golden_dir, sars_paths, tmp_path):
     """BRONKO_SHARD=1: a sample's batches are dealt to one engine per GPU and the counter planes are reduce-scattered by RCCL from
-    inside the binary (cli.cpp sharded_finalize: the k-mer statistics tables' exchange, bk_shard_measure / _transport /
+    inside the binary (call_run.cpp sharded_finalize: the k-mer statistics tables' exchange, bk_shard_measure / _transport /
     ncclReduceScatter / _received per mate file, bk_sample_finalize_shard, three all-reduces, bk_sample_merge_shards).  On this
     box that is a communicator of ONE rank -- every collective still runs through the backend -- and the outputs must be the
     unsharded run's and the oracle's, byte for byte: a paired HPV16 sample, and a four-strain sample (every genome's rows: the
@@ -297,3 +297,54 @@ def test_call_reads_inflated_on_several_threads(golden_dir, tmp_path):
     assert outs[0].keys() == outs[1].keys() == outs[2].keys() and len(outs[0]) >= 3
     for f in outs[0]:
         assert outs[0][f] == outs[1][f] == outs[2][f], f
+
+
+def test_call_settings_reach_every_reader_path(golden_dir, tmp_path):
+    """The settings of a call (k, --min-base-qual, the adapters and with them whether a packed batch carries end flags) reach the
+    readers that are started ahead of a sample's turn and the ones its lane starts itself, on the line loop (one inflate thread:
+    text batches, the engine masks and cuts) and in the packer (several: 2-bit records with end flags).  Two paired samples of
+    2 x 2,000 reads, binned qualities with some below the threshold, a tenth of the reads running on into the TruSeq adapter;
+    `--pileup --consensus --keep-kmer-info --adapter truseq --min-base-qual 20` with -t 2 and -t 16, each with and without
+    BRONKO_NO_READ_AHEAD=1.  (-t 2 gives a lane's own readers one inflate thread but the two files read ahead two each, so a fifth
+    run, BRONKO_INFLATE_THREADS=1 with the files read ahead, puts the line loop behind ReadAhead too.)  Every output file is the
+    same in all runs, and the VCFs are those of a plain `--min-base-qual 20` call on the truncated files."""
+    from tests import adapter_ref
+    from tests.test_gpu_adapters import TRUSEQ, write_fastq_gz as write_fastq_qual_gz
+    g = synth.read_fasta_bytes(os.path.join(golden_dir, "HPV16.fa"))
+    orig, trunc = tmp_path / "orig", tmp_path / "trunc"
+    orig.mkdir()
+    trunc.mkdir()
+    for i in range(2):
+        gm, _ = synth.sample_genome(g, 60 + i, n_snp=5, n_isnv=0)
+        for m in range(2):
+            seed = 600 + 2 * i + m
+            reads = adapter_ref.library_reads(gm, [], [TRUSEQ], 2000, 150, seed, short=0.1)
+            x = np.random.default_rng(seed).random((len(reads), 150))   # binned qualities (tools/cli_end_to_end.py): ',' and '#' are below 20
+            quals = [row.tobytes() for row in np.where(x < 0.90, ord("F"), np.where(x < 0.96, ord(":"), np.where(x < 0.99, ord(","), ord("#")))).astype(np.uint8)]
+            cuts, _ = adapter_ref.cut_positions_all(reads, [TRUSEQ], 5, 0.1, quals, 20)
+            # (a tenth of the reads run on into the adapter; the masked bases leave few of them a whole adapter in their last run)
+            assert 0.05 <= (adapter_ref.cut_positions_all(reads, [TRUSEQ], 5, 0.1)[0] >= 0).mean() <= 0.2 and (cuts >= 0).sum() >= 5
+            name = "s%d_R%d.fastq.gz" % (i, m + 1)
+            write_fastq_qual_gz(str(orig / name), reads, quals, "ab"[m])
+            write_fastq_qual_gz(str(trunc / name), *adapter_ref.truncate(reads, quals, cuts), "ab"[m])
+
+    def call(d, flags, threads, env, out):
+        files = [[os.path.join(str(d), "s%d_R%d.fastq.gz" % (i, m)) for i in range(2)] for m in (1, 2)]
+        res = subprocess.run([BRONKO, "call", "-d", os.path.join(golden_dir, "hpv.bkdb"), "-1"] + files[0] + ["-2"] + files[1] + flags +
+                             ["--min-base-qual", "20", "-o", str(tmp_path / out), "-t", str(threads)], capture_output=True, text=True, env={**os.environ, **env})
+        assert res.returncode == 0, res.stdout + res.stderr
+        return {n: open(os.path.join(str(tmp_path / out), n), "rb").read() for n in sorted(os.listdir(str(tmp_path / out)))}
+    flags = ["--pileup", "--consensus", "--keep-kmer-info", "--adapter", "truseq"]
+    runs = [(t, env) for t in (2, 16) for env in ({}, {"BRONKO_NO_READ_AHEAD": "1"})] + [(2, {"BRONKO_INFLATE_THREADS": "1"})]
+    outs = [call(orig, flags, t, env, "out%d" % n) for n, (t, env) in enumerate(runs)]
+    want_names = ["s%d_R1%s" % (i, e) for i in range(2) for e in (".vcf", ".tsv", ".consensus.fa", "_counts.txt")] + ["s%d_R2_counts.txt" % i for i in range(2)]
+    assert sorted(outs[0]) == sorted(want_names + ["bronko_overview.tsv"])
+    for n, o in enumerate(outs[1:]):
+        assert sorted(o) == sorted(outs[0]), runs[n + 1]
+        for name in o:
+            assert o[name] == outs[0][name], (runs[n + 1], name)
+    want = call(trunc, [], 2, {}, "out_trunc")
+    for i in range(2):
+        name = "s%d_R1.vcf" % i
+        assert any(not ln.startswith(b"#") for ln in want[name].splitlines())   # (there are calls to compare)
+        assert outs[0][name].replace(str(orig).encode(), b"DIR") == want[name].replace(str(trunc).encode(), b"DIR"), name
