@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Randomised parity: small random indexes (repeats, reverse-complement repeats, homopolymers, several sequences and
 files, k from 11 to 31, window variants) and read sets (lengths 20..400, 0..12 % substitutions, indels, foreign reads,
-N symbols), HIP path vs oracle, ci = 1 so that every single k-mer occurrence shows.  Usage: fuzz_parity.py [iterations [seed0 [first iteration]]]"""
+N symbols), HIP path vs oracle, mostly ci = 1; one iteration in eight runs once more at one count level (ci = cx = c), where a k-mer
+counted one off shows even below another k-mer's maximum.  Usage: fuzz_parity.py [iterations [seed0 [first iteration]]]"""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bronko_amd import Params, pack_reads, _ffi
 _ffi.use_testing_library(True)   # BK_LDS_BINS / BK_REF_IN_LDS / BK_MAX_LAUNCH_RECORDS exist in the -DBK_TESTING build only
-from tests import helpers
+from tests import helpers, level_sweep
 from oracle import oracle as orc
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 100
@@ -37,6 +38,14 @@ def mutate(rng, g, n_sub):
     for p in rng.integers(0, len(g), n_sub):
         g[p] = B[(B.index(g[p]) + int(rng.integers(1, 4))) & 3]
     return bytes(g)
+
+def compare(res, pile, ix, sel_only, stats, what=""):
+    try:
+        level_sweep.assert_same_level(orc, ix, res, pile, sel_only)   # arrays (sel_only: the selected genome's rows, zeros elsewhere), stats, present, k-mer totals
+        if stats:
+            assert res.kmer_stats[:, 2:4].tolist() == pile.kmc_stats[:, 2:4].tolist(), ("kmc stats", res.kmer_stats, pile.kmc_stats)
+    except AssertionError as e:
+        raise AssertionError(what + str(e)) from None
 
 bad = 0
 t0 = time.time()
@@ -107,25 +116,27 @@ for it in range(first, first + iters):
     if rng.random() < 0.3:                                                              # the engine is left clean: a second sample gives the same
         res = helpers.hip_sample(eng, mates, k, batch=batch, ascii_path=ascii_path)
     pile = orc.sample_pileup(ix, mates, n_fixed=n_fixed, use_full_kmer=full, ci=int(prm.ci))
+    # one iteration in eight: one count level more.  A fork with ci = cx = c lets only the k-mers counted exactly c times vote, so
+    # a k-mer counted one off shows even where another k-mer's larger count hides it in the depths (tests/level_sweep.py).  These
+    # choices come from a generator of their own: the stream above is what it was, every recorded seed gives the same iteration
+    rng2 = np.random.default_rng([seed0, it])
+    level = None
+    if rng2.integers(0, 8) == 0:
+        values = np.unique(np.concatenate([orc.count_kmers(k, m, ci=1)[1] for m in mates]))
+        if len(values): level = int(rng2.choice(values))
     try:
-        if sel_only:
-            # statistics of every genome; rows of the selected genome only (the others stay zero)
-            assert np.array_equal(res.stats, pile.stats) and np.array_equal(res.present, pile.present), ("stats", res.stats.tolist(), pile.stats.tolist())
-            best = orc.pick_best_genome(ix, pile.stats.sum(axis=0), pile.present.max(axis=0))
-            lo, ncell = ix.genome_cells(best) if best >= 0 else (0, 0)
-            for name in ("fwd_depth", "rev_depth", "fwd_nk", "rev_nk"):
-                got, ref = getattr(res, name), getattr(pile, name)
-                assert np.array_equal(got[lo * 4:(lo + ncell) * 4], ref[lo * 4:(lo + ncell) * 4]), (name, "selected genome", best)
-                assert not got[:lo * 4].any() and not got[(lo + ncell) * 4:].any(), (name, "other genomes")
-        else:
-            helpers.assert_same_pileup(res, pile)
-        assert res.kmer_stats[:, 1].tolist() == pile.kmc_stats[:, 1].tolist(), ("total k-mers", res.kmer_stats[:, 1], pile.kmc_stats[:, 1])
-        if stats:
-            assert res.kmer_stats[:, 2:4].tolist() == pile.kmc_stats[:, 2:4].tolist(), ("kmc stats", res.kmer_stats, pile.kmc_stats)
+        compare(res, pile, ix, sel_only, stats)
+        if level is not None:
+            fork = eng.fork(Params(ci=level, cx=level, n_fixed=n_fixed, use_full_kmer=int(full), full_kmer_stats=stats, kmer_table_log2=21, pileup_selected_only=sel_only))
+            try:
+                res = helpers.hip_sample(fork, mates, k, batch=batch, ascii_path=ascii_path)
+            finally:
+                fork.close()
+            compare(res, orc.sample_pileup(ix, mates, n_fixed=n_fixed, use_full_kmer=full, ci=level, cx=level), ix, sel_only, stats, "level ci = cx = %d: " % level)
     except AssertionError as e:
         bad += 1
-        print("MISMATCH it=%d seed=%d k=%d n_fixed=%d full=%d files=%d reads=%d err=%.3f mates=%d batch=%s ascii=%d stats=%d sel_only=%d env=%s: %s" %
-              (it, seed0, k, n_fixed, full, len(files), len(reads), err, len(mates), batch, ascii_path, stats, sel_only,
+        print("MISMATCH it=%d seed=%d k=%d n_fixed=%d full=%d files=%d reads=%d err=%.3f mates=%d batch=%s ascii=%d stats=%d sel_only=%d level=%s env=%s: %s" %
+              (it, seed0, k, n_fixed, full, len(files), len(reads), err, len(mates), batch, ascii_path, stats, sel_only, level,
                {v: os.environ[v] for v in ("BK_LDS_BINS", "BK_REF_IN_LDS", "BK_MAX_LAUNCH_RECORDS", "BK_SPARSE_FINALIZE") if v in os.environ}, str(e)[:300]), flush=True)
     eng.close(); ix.close()
 print("%d iterations, %d mismatches, %.0f s" % (iters, bad, time.time() - t0))
