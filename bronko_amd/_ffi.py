@@ -54,6 +54,18 @@ class ConsensusSummary(C.Structure):  # bk_consensus_summary
                 ("masked", C.c_uint64), ("substitutions", C.c_uint64)]
 
 
+class Region(C.Structure):  # bk_region
+    _fields_ = [("file_id", C.c_int32), ("seq", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32)]
+
+
+class RegionDepth(C.Structure):  # bk_region_depth
+    _fields_ = [("sum", C.c_uint64), ("min", C.c_uint64), ("max", C.c_uint64), ("median", C.c_uint64), ("covered", C.c_uint64)]
+
+
+class RegionSummary(C.Structure):  # bk_region_summary
+    _fields_ = [("file_id", C.c_int32), ("n_regions", C.c_uint32), ("full", C.c_uint64), ("partial", C.c_uint64), ("empty", C.c_uint64)]
+
+
 class BuiltIndex(C.Structure):  # bk_built_index
     _fields_ = [("n_buckets", C.c_uint64), ("n_entries", C.c_uint64), ("bucket_ids", C.c_void_p), ("bucket_off", C.c_void_p),
                 ("entries", C.c_void_p)]
@@ -70,6 +82,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_pileup_device_ptr", "bk_sample_download", "bk_sample_finish", "bk_pack_reads", "bk_pack_reads_flat",
            "bk_timing_enable", "bk_timing_read", "bk_call_params_default", "bk_sample_call", "bk_sample_download_calls", "bk_sample_download_noise",
            "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
+           "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -191,6 +204,12 @@ def load(testing=None):
     L.bk_sample_consensus.argtypes = [vp, C.POINTER(ConsensusParams)]
     L.bk_sample_download_consensus.restype = C.c_int
     L.bk_sample_download_consensus.argtypes = [vp, C.POINTER(ConsensusSummary), vp, u64]
+    L.bk_regions_set.restype = C.c_int
+    L.bk_regions_set.argtypes = [vp, C.POINTER(Region), u64]
+    L.bk_sample_region_depths.restype = C.c_int
+    L.bk_sample_region_depths.argtypes = [vp, u64]
+    L.bk_sample_download_region_depths.restype = C.c_int
+    L.bk_sample_download_region_depths.argtypes = [vp, C.POINTER(RegionSummary), vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

@@ -277,7 +277,7 @@ int bk_sample_begin(bk_engine* e) {
     TrimStage* const trim_stages[] = {e->primers.get(), e->adapters.get()};
     for (TrimStage* t : trim_stages)
         if (t) { BK_HIP(hipMemsetAsync(t->stats.p, 0, t->stats.n * sizeof(unsigned long long), e->stream)); t->in_sample = true; }
-    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0; e->called = false; e->cons_made = false;
+    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0; e->called = false; e->cons_made = false; e->regions_made = false;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
     for (MatePlane& p : e->mate) { if (int rc = p.begin_sample(e)) return rc; }
@@ -1148,7 +1148,7 @@ int bk_sample_call(bk_engine* e, int n_mates, const bk_call_params* p) {
     bk_engine::Span sp(e, 1);
     bk::launch_call(a, ix.max_seqs_per_file, ix.max_file_cells, e->stream);
     BK_HIP(hipGetLastError());
-    e->called = true; e->cons_made = false;   // (a consensus made before this call was of another selection)
+    e->called = true; e->cons_made = false; e->regions_made = false;   // (a consensus or a region report made before this call was of another selection)
     return BK_OK;
 }
 
@@ -1226,6 +1226,81 @@ int bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, ui
     const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->positions, cap), e->cons_letters.n);
     if (n && letters) {
         BK_HIP(hipMemcpyAsync(letters, e->cons_letters.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+        BK_HIP(hipStreamSynchronize(e->stream));
+    }
+    return BK_OK;
+}
+
+// ---- per-region depth report (region_depth_kernel, bk_regions.hip) ------------------------------------------------
+int bk_regions_set(bk_engine* e, const bk_region* regions, uint64_t n) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_regions_set comes between samples");
+    if (n > BK_MAX_REGIONS) return fail(BK_ERR_INVALID, "%llu regions: at most %u", (unsigned long long)n, (unsigned)BK_MAX_REGIONS);
+    if (n && !regions) return fail(BK_ERR_INVALID, "null argument");
+    const IndexTables& ix = *e->ix;
+    std::vector<uint32_t> off((size_t)ix.n_files + 1, 0u);
+    for (uint64_t i = 0; i < n; i++) {
+        const bk_region& r = regions[i];
+        if (r.file_id < 0 || r.file_id >= ix.n_files) return fail(BK_ERR_INVALID, "region %llu: no genome file %d (the index has %d)", (unsigned long long)i, r.file_id, ix.n_files);
+        if ((int64_t)r.seq >= (int64_t)ix.h_n_seqs[(size_t)r.file_id])
+            return fail(BK_ERR_INVALID, "region %llu: no sequence %u in genome file %d (it has %d)", (unsigned long long)i, r.seq, r.file_id, ix.h_n_seqs[(size_t)r.file_id]);
+        const uint64_t len = ix.h_seq_len[(size_t)ix.h_seq_first[(size_t)r.file_id] + r.seq];
+        if (!(r.start < r.end && (uint64_t)r.end <= len))
+            return fail(BK_ERR_INVALID, "region %llu: [%u, %u) is not a range inside sequence %u of genome file %d (length %llu)", (unsigned long long)i, r.start, r.end,
+                        r.seq, r.file_id, (unsigned long long)len);
+        off[(size_t)r.file_id + 1] += 1;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernel may still use the table and the buffers being freed)
+    e->regions.reset();
+    e->regions_made = false;
+    if (n == 0) return BK_OK;
+    std::unique_ptr<Regions> rg(new Regions());
+    for (int f = 0; f < ix.n_files; f++) { rg->max_file_regions = std::max(rg->max_file_regions, off[(size_t)f + 1]); off[(size_t)f + 1] += off[(size_t)f]; }
+    std::vector<uint2> tab((size_t)n);
+    std::vector<uint32_t> at(off.begin(), off.end() - 1);   // grouped by file, the caller's order within a file
+    for (uint64_t i = 0; i < n; i++) {
+        const bk_region& r = regions[i];
+        const uint64_t cell = ix.h_seq_cell[(size_t)ix.h_seq_first[(size_t)r.file_id] + r.seq] + r.start;   // (below 2^32: build_index_tables)
+        tab[at[(size_t)r.file_id]++] = make_uint2((uint32_t)cell, r.end - r.start);
+    }
+    BK_HIP(rg->table.upload(tab)); BK_HIP(rg->file_off.upload(off));
+    BK_HIP(rg->rows.alloc(rg->max_file_regions)); BK_HIP(rg->out.alloc(1));
+    e->regions = std::move(rg);
+    return BK_OK;
+}
+
+int bk_sample_region_depths(bk_engine* e, uint64_t min_depth) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (min_depth < 1) return fail(BK_ERR_INVALID, "bk_sample_region_depths: min_depth must be at least 1, got 0");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_region_depths comes after bk_sample_finalize and bk_sample_call");
+    if (!e->called) return fail(BK_ERR_STATE, "bk_sample_region_depths: bk_sample_call has not run for this sample");
+    if (!e->regions) return fail(BK_ERR_STATE, "bk_sample_region_depths: no regions are set (bk_regions_set)");
+    const IndexTables& ix = *e->ix;
+    Regions& rg = *e->regions;
+    BK_HIP(hipSetDevice(e->device));
+    bk::RegionArgs a{};
+    a.min_depth = min_depth;
+    a.table = rg.table.p; a.file_off = rg.file_off.p;
+    a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
+    a.out = e->call_out.p; a.rows = rg.rows.p; a.summary = rg.out.p;
+    bk_engine::Span sp(e, 1);
+    BK_HIP(hipMemsetAsync(rg.out.p, 0, sizeof(bk_region_summary), e->stream));
+    bk::launch_region_depths(a, rg.max_file_regions, e->stream);
+    BK_HIP(hipGetLastError());
+    e->regions_made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_region_depths(bk_engine* e, bk_region_summary* summary, bk_region_depth* out, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->regions_made || !e->regions) return fail(BK_ERR_STATE, "bk_sample_download_region_depths comes after this sample's bk_sample_region_depths");
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipMemcpyAsync(summary, e->regions->out.p, sizeof *summary, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->n_regions, cap), e->regions->rows.n);
+    if (n && out) {
+        BK_HIP(hipMemcpyAsync(out, e->regions->rows.p, (size_t)n * sizeof(bk_region_depth), hipMemcpyDeviceToHost, e->stream));
         BK_HIP(hipStreamSynchronize(e->stream));
     }
     return BK_OK;

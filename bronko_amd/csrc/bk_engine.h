@@ -223,6 +223,15 @@ struct Adapters : TrimStage {
     DevBuf<uint32_t> cut;                   // [records of the largest batch so far] bk::kNoCut between launches
 };
 
+// bk_regions_set: the region table as region_depth_kernel takes it (bk_regions.hip) and the result buffers, allocated with it
+struct Regions {
+    DevBuf<uint2> table;                    // [n] {first cell, L}, grouped by genome file, the caller's order within a file
+    DevBuf<uint32_t> file_off;              // [n_files + 1]
+    DevBuf<bk_region_depth> rows;           // [max_file_regions]
+    DevBuf<bk_region_summary> out;
+    uint32_t max_file_regions = 0;          // regions of the genome file with the most: the kernel's grid
+};
+
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
 // by an engine and its forks, freed with the last of them.
 struct IndexTables {
@@ -272,6 +281,8 @@ struct IndexTables {
     // after the pileup (bk_sample_call): sequence geometry
     DevBuf<uint64_t> genome_len, seq_cell, seq_len_d;
     DevBuf<int32_t> seq_first, n_seqs_d;
+    std::vector<uint64_t> h_seq_cell, h_seq_len;   // host copies of seq_cell, seq_len_d, seq_first, n_seqs_d (bk_regions_set checks against them)
+    std::vector<int32_t> h_seq_first, h_n_seqs;
     int max_seqs_per_file = 0;
     uint64_t max_file_cells = 0;
     uint64_t max_file_cells_idx = 0;        // cells of the genome file with the most (pileup rows)
@@ -435,6 +446,8 @@ struct bk_engine {
     DevBuf<uint8_t> cons_letters;
     DevBuf<bk_consensus_summary> cons_out;
     bool cons_made = false;
+    std::unique_ptr<Regions> regions;       // bk_regions_set (null: no regions, no launch, no buffers)
+    bool regions_made = false;              // bk_sample_region_depths ran for the current sample and table
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

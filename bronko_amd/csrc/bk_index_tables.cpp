@@ -296,6 +296,7 @@ int IndexBuilder::sequence_geometry() {
         if (s_cell.empty()) { s_cell.push_back(0); s_len.push_back(0); }
         BK_HIP(tab.genome_len.upload(g_len)); BK_HIP(tab.seq_cell.upload(s_cell)); BK_HIP(tab.seq_len_d.upload(s_len));
         BK_HIP(tab.seq_first.upload(s_first)); BK_HIP(tab.n_seqs_d.upload(n_s));
+        tab.h_seq_cell = std::move(s_cell); tab.h_seq_len = std::move(s_len); tab.h_seq_first = std::move(s_first); tab.h_n_seqs = std::move(n_s);
     }
     return BK_OK;
 }

@@ -435,6 +435,21 @@ struct ConsensusArgs {
     ConsensusSummaryDev* summary;        // tallies zeroed by the caller; the kernel writes file_id and adds
 };
 void launch_consensus(const ConsensusArgs& a, uint64_t max_file_cells, hipStream_t stream);
+// bk_sample_region_depths: the depth numbers of every region of the genome bk_sample_call selected (region_depth_kernel, bk_regions.hip)
+typedef bk_region_depth RegionDepthDev;
+typedef bk_region_summary RegionSummaryDev;
+struct RegionArgs {
+    uint64_t min_depth;                  // covered: depth >= min_depth
+    const uint2* table;                  // [regions] {first cell, L}, grouped by genome file (bk_regions_set resolved and checked them)
+    const uint32_t* file_off;            // [n_files + 1] the file's slice of `table`
+    const unsigned long long* pileup;    // the two depth planes are read
+    size_t plane;
+    const CallSummaryDev* out;           // bk_sample_call's: file_id
+    RegionDepthDev* rows;                // [regions of the file with the most] row b: region b of the selected file's slice
+    RegionSummaryDev* summary;           // zeroed by the caller; the kernel writes file_id and n_regions and adds the tallies
+};
+constexpr uint32_t kRegionLdsDepths = 2048;   // a region of at most this many positions is staged in LDS once (16 KB)
+void launch_region_depths(const RegionArgs& a, uint32_t max_file_regions, hipStream_t stream);
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

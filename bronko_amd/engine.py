@@ -434,6 +434,25 @@ class Engine:
         _check(self._L.bk_sample_download_consensus(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, buf[:min(cap, int(summ.positions))].tobytes()
 
+    def regions_set(self, regions):
+        """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
+        arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])
+        _check(self._L.bk_regions_set(self.h, arr, len(regions)), self._L)
+
+    def sample_region_depths(self, min_depth=10):
+        """The depth numbers of every region of the genome sample_call selected, on the device (asynchronous)."""
+        _check(self._L.bk_sample_region_depths(self.h, int(min_depth)), self._L)
+
+    def download_region_depths(self, cap=None):
+        """(summary, rows) of sample_region_depths: min(cap, summary.n_regions) rows (sum, min, max, median, covered), all by default."""
+        summ = _ffi.RegionSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_region_depths(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.n_regions)
+        buf = np.zeros((max(1, cap), 5), np.uint64)
+        _check(self._L.bk_sample_download_region_depths(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, [tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.n_regions))]]
+
     def timing_enable(self, on=True):
         _check(self._L.bk_timing_enable(self.h, int(on)), self._L)
 

@@ -222,6 +222,8 @@ struct SampleData {
     std::vector<bk_call_record> recs;
     bk_consensus_summary csumm{};                         // --consensus
     std::vector<uint8_t> letters;
+    bk_region_summary rsumm{};                            // --regions, --region-window
+    std::vector<bk_region_depth> rrows;
 };
 
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
@@ -234,6 +236,9 @@ struct CallRun {
     Index ix;
     std::vector<OverviewRow> overview;               // by sample, in input order
     std::vector<SampleCalls> all_calls;              // --alignment
+    std::vector<Region> regions;                     // --regions / --region-window: resolved by open_index, every genome file's
+    std::vector<bk_region> region_table;             // ... as bk_regions_set takes them
+    size_t max_file_regions = 0;                     // regions of the genome file with the most
     int dump_threads = 1;                            // --keep-kmer-info: threads that format one sample's counts (set before the lanes start)
 
     // the samples, in input order; their files are read ahead from here on (ReadAhead): the index and the engine's tables take
@@ -264,6 +269,18 @@ struct CallRun {
         // (a few genomes: the engine's tables are made in a fraction of a second, the cores are the readers' from here on; with many
         // the readers stay few until the engines stand -- bk_engine_create runs on all cores for seconds)
         if (ahead && ix.files.size() <= 8) ahead->set_concurrency((unsigned)std::max<long>(2, a.threads / 2));
+        if (cfg.region_report()) resolve_regions();
+    }
+    // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
+    void resolve_regions() {
+        try { regions = cfg.region_window ? window_regions(ix, cfg.region_window) : resolve_bed(ix, cfg.bed, cfg.regions_path); }
+        catch (const std::exception& e) { die(T, e.what()); }
+        std::vector<size_t> per_file(ix.files.size(), 0);
+        for (const Region& r : regions) {
+            region_table.push_back(bk_region{r.file_id, r.seq, r.start, r.end});
+            max_file_regions = std::max(max_file_regions, ++per_file[(size_t)r.file_id]);
+        }
+        LOG_DEBUG(T, std::to_string(regions.size()) + " regions over " + std::to_string(ix.files.size()) + " genome file(s)");
     }
 
     void make_engine(int device, Engine& out, bool selected_only = true) const {
@@ -384,7 +401,8 @@ struct CallRun {
         LOG_INFO(T, std::to_string(total_reads) + " reads counted from " + mates[0]);
     }
 
-    // --adapter, --primers: every engine that takes reads trims them (bk_adapters_set, bk_primers_set are per engine); under
+    // --adapter, --primers: every engine that takes reads trims them (bk_adapters_set, bk_primers_set are per engine), and every engine
+    // that completes a sample holds the region table (bk_regions_set, per engine as well); under
     // --verbose, what was trimmed per reads file, summed over the sample's engines
     template <class Set>
     static void set_seqs(const std::vector<std::string>& list, Set&& set) {   // set(seqs, lens, n): the bk_*_set call
@@ -397,6 +415,7 @@ struct CallRun {
         if (!e) return;
         set_seqs(cfg.adapters, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_adapters_set(e, q, l, n, cfg.adapter_min_overlap, cfg.adapter_error_rate), "bk_adapters_set"); });
         set_seqs(cfg.primers, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_primers_set(e, q, l, n, cfg.primer_mismatches), "bk_primers_set"); });
+        if (!region_table.empty()) hip_check(bk_regions_set(e, region_table.data(), region_table.size()), "bk_regions_set");
     }
     // text(sum): the line's start; stats(e, mate, out): the bk_*_stats call, n counters a mate file
     template <class Stats, class Text>
@@ -430,6 +449,8 @@ struct CallRun {
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
         if (a.consensus) hip_check(bk_sample_consensus(e, &cfg.consensus), "bk_sample_consensus");
+        // likewise: a few numbers per region travel (bk_sample_download_region_depths below)
+        if (!region_table.empty()) hip_check(bk_sample_region_depths(e, cfg.region_min_depth), "bk_sample_region_depths");
     }
     void download_pileup(bk_engine* e, int n_mates, SampleData& d) const {
         const size_t n_files = ix.files.size(), cells4 = ix.total_cells() * 4;
@@ -460,6 +481,11 @@ struct CallRun {
         if (a.consensus) {
             d.letters.resize((size_t)longest);
             hip_check(bk_sample_download_consensus(e, &d.csumm, d.letters.data(), d.letters.size()), "bk_sample_download_consensus");
+        }
+        if (!region_table.empty()) {
+            d.rrows.resize(max_file_regions);
+            hip_check(bk_sample_download_region_depths(e, &d.rsumm, d.rrows.data(), d.rrows.size()), "bk_sample_download_region_depths");
+            d.rrows.resize(std::min<size_t>(d.rrows.size(), d.rsumm.n_regions));
         }
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
@@ -505,6 +531,13 @@ struct CallRun {
                                 std::to_string(c.substitutions) + " substitutions), " + std::to_string(c.ambiguous) + " ambiguous, " +
                                 std::to_string(c.masked) + " masked");
                 write_consensus_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, d.letters.data(), c.positions);
+            }
+            if (cfg.region_report()) {   // (a genome without a region: the two header lines)
+                LOG_INFO(T, "Depth of " + std::to_string(d.rsumm.n_regions) + " regions at minimum depth " + std::to_string(cfg.region_min_depth) + ": " +
+                                std::to_string(d.rsumm.full) + " full, " + std::to_string(d.rsumm.partial) + " partial, " + std::to_string(d.rsumm.empty) + " empty");
+                std::vector<RegionDepth> rows;
+                for (const bk_region_depth& r : d.rrows) { RegionDepth o; o.sum = r.sum; o.min = r.min; o.max = r.max; o.median = r.median; o.covered = r.covered; rows.push_back(o); }
+                write_regions_tsv(a.output + "/" + stem + ".regions.tsv", ix, best, regions, rows.data(), rows.size(), cfg.region_min_depth);
             }
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }

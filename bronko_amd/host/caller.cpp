@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "fastx.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -265,6 +266,135 @@ void write_consensus_fasta(const std::string& out_path, const std::string& stem,
         }
         at += sm.len;
     }
+}
+
+// ---- --regions / --region-window -------------------------------------------------------------------------------------------
+std::vector<BedLine> read_bed(const std::string& path) {
+    std::vector<BedLine> out;
+    GzLineReader in(path);
+    std::string line;
+    size_t no = 0;
+    // a column that is a number: digits only, below 2^63
+    auto number = [](const std::string& v, uint64_t* x) {
+        if (v.empty() || v.size() > 18) return false;
+        *x = 0;
+        for (char c : v) { if (c < '0' || c > '9') return false; *x = *x * 10 + (uint64_t)(c - '0'); }
+        return true;
+    };
+    while (in.next(line)) {
+        no++;
+        if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+        const std::string where = path + ": line " + std::to_string(no);
+        std::vector<std::string> col;
+        for (size_t a = 0; col.size() < 4;) {
+            const size_t b = line.find('\t', a);
+            col.push_back(line.substr(a, b == std::string::npos ? b : b - a));
+            if (b == std::string::npos) break;
+            a = b + 1;
+        }
+        if (col.size() < 3) throw std::runtime_error(where + ": " + std::to_string(col.size()) + " tab-separated column(s), a BED line has at least chrom, start and end");
+        BedLine r;
+        r.chrom = col[0]; r.line = no;
+        r.name = col.size() > 3 && !col[3].empty() ? col[3] : ".";
+        if (r.chrom.empty()) throw std::runtime_error(where + ": empty chrom column");
+        if (!number(col[1], &r.start)) throw std::runtime_error(where + ": start '" + col[1] + "' is not a non-negative integer");
+        if (!number(col[2], &r.end)) throw std::runtime_error(where + ": end '" + col[2] + "' is not a non-negative integer");
+        if (r.start >= r.end) throw std::runtime_error(where + ": start " + col[1] + " is not below end " + col[2] + " (BED ranges are half-open and not empty)");
+        if (out.size() == kMaxBedRegions) throw std::runtime_error(path + ": more than " + std::to_string(kMaxBedRegions) + " regions");
+        out.push_back(std::move(r));
+    }
+    return out;
+}
+
+std::vector<Region> resolve_bed(const Index& ix, const std::vector<BedLine>& bed, const std::string& path) {
+    std::map<std::string, std::vector<std::pair<int, uint32_t>>> where;   // CHROM token -> (file, sequence) in index order
+    for (size_t f = 0; f < ix.files.size(); f++)
+        for (size_t q = 0; q < ix.files[f].sequences.size(); q++) where[first_token(ix.files[f].sequences[q].name)].push_back({(int)f, (uint32_t)q});
+    std::vector<Region> out;
+    for (const BedLine& b : bed) {
+        const std::string at = path + ": line " + std::to_string(b.line);
+        const auto it = where.find(b.chrom);
+        if (it == where.end()) throw std::runtime_error(at + ": chrom '" + b.chrom + "' is no sequence of any genome");
+        for (const auto& fq : it->second) {
+            const SeqMeta& sm = ix.files[(size_t)fq.first].sequences[fq.second];
+            if (b.end > sm.len)
+                throw std::runtime_error(at + ": end " + std::to_string(b.end) + " lies beyond sequence '" + b.chrom + "' of " + ix.files[(size_t)fq.first].name +
+                                         " (length " + std::to_string(sm.len) + ")");
+            Region r;
+            r.file_id = fq.first; r.seq = fq.second; r.start = (uint32_t)b.start; r.end = (uint32_t)b.end; r.name = b.name;
+            out.push_back(std::move(r));
+        }
+        if (out.size() > kMaxRegions) throw std::runtime_error(path + ": more than " + std::to_string(kMaxRegions) + " regions over all genomes");
+    }
+    return out;
+}
+
+std::vector<Region> window_regions(const Index& ix, uint64_t window) {
+    if (window < 1) throw std::runtime_error("the region window must be at least 1");
+    uint64_t n = 0;
+    for (const FileMeta& fm : ix.files)
+        for (const SeqMeta& sm : fm.sequences) n += (sm.len + window - 1) / window;
+    if (n > kMaxRegions)
+        throw std::runtime_error("--region-window " + std::to_string(window) + " makes " + std::to_string(n) + " windows, at most " + std::to_string(kMaxRegions) +
+                                 " are supported: raise the window");
+    std::vector<Region> out;
+    out.reserve((size_t)n);
+    for (size_t f = 0; f < ix.files.size(); f++)
+        for (size_t q = 0; q < ix.files[f].sequences.size(); q++) {
+            const uint64_t len = ix.files[f].sequences[q].len;
+            for (uint64_t s = 0; s < len; s += window) {
+                Region r;
+                r.file_id = (int)f; r.seq = (uint32_t)q; r.start = (uint32_t)s; r.end = (uint32_t)std::min(s + window, len); r.name = ".";
+                out.push_back(std::move(r));
+            }
+        }
+    return out;
+}
+
+RegionReport region_depths(const Index& ix, int file_id, const Pileup& p, const std::vector<Region>& regions, uint64_t min_depth) {
+    RegionReport out;
+    if (file_id < 0) return out;
+    uint64_t file_cell = 0;
+    for (int f = 0; f < file_id; f++) file_cell += ix.genome_len((size_t)f);
+    for (const Region& r : regions) {
+        if (r.file_id != file_id) continue;
+        uint64_t cell = file_cell;
+        for (uint32_t q = 0; q < r.seq; q++) cell += ix.files[(size_t)file_id].sequences[q].len;
+        std::vector<uint64_t> d;
+        for (uint64_t i = r.start; i < r.end; i++) {
+            uint64_t depth = 0;
+            for (unsigned b = 0; b < 4; b++) depth += p.fwd_depth[(cell + i) * 4 + b] + p.rev_depth[(cell + i) * 4 + b];
+            d.push_back(depth);
+        }
+        const uint64_t L = d.size();
+        RegionDepth o;
+        for (uint64_t v : d) { o.sum += v; if (v >= min_depth) o.covered += 1; }
+        std::sort(d.begin(), d.end());
+        o.min = d.front(); o.max = d.back(); o.median = d[(size_t)((L - 1) / 2)];
+        out.rows.push_back(o);
+        if (o.covered == L) out.full += 1; else if (o.covered == 0) out.empty += 1; else out.partial += 1;
+    }
+    return out;
+}
+
+void write_regions_tsv(const std::string& out_path, const Index& ix, int file_id, const std::vector<Region>& regions,
+                       const RegionDepth* rows, uint64_t n_rows, uint64_t min_depth) {
+    File f(out_path);
+    if (!f.fp) throw std::runtime_error("Failed to create regions file " + out_path);
+    fprintf(f.fp, "##min_depth=%llu\nchrom\tstart\tend\tname\tlength\tmean\tmin\tmedian\tmax\tcovered\n", (unsigned long long)min_depth);
+    uint64_t at = 0;
+    for (const Region& r : regions) {
+        if (file_id < 0 || r.file_id != file_id) continue;
+        if (at == n_rows) throw std::runtime_error("write_regions_tsv: fewer rows than the genome has regions");
+        const RegionDepth& o = rows[at++];
+        const uint64_t L = (uint64_t)r.end - r.start;
+        const unsigned __int128 m = (unsigned __int128)o.sum * 100u / L;   // (100 * sum leaves u64 above 1.8e17)
+        fprintf(f.fp, "%s\t%u\t%u\t%s\t%llu\t%llu.%02u\t%llu\t%llu\t%llu\t%llu\n", first_token(ix.files[(size_t)file_id].sequences[r.seq].name).c_str(), r.start, r.end,
+                r.name.c_str(), (unsigned long long)L, (unsigned long long)(m / 100u), (unsigned)(m % 100u), (unsigned long long)o.min,
+                (unsigned long long)o.median, (unsigned long long)o.max, (unsigned long long)o.covered);
+    }
+    if (at != n_rows) throw std::runtime_error("write_regions_tsv: more rows than the genome has regions");
+    if (fflush(f.fp) != 0 || ferror(f.fp)) throw std::runtime_error("Failed to write regions file " + out_path);
 }
 
 std::string clean_sample_id(const std::string& path) {

@@ -75,6 +75,41 @@ Consensus consensus(const Index& ix, int file_id, const Pileup& p, const Consens
 // token of the VCF's CHROM column; the letters (`n` of them, genome_len(file_id)) in lines of 60
 void write_consensus_fasta(const std::string& out_path, const std::string& stem, const Index& ix, int file_id, const uint8_t* letters, uint64_t n);
 
+// --regions / --region-window: the rule of include/bronko_hip.h (bk_sample_region_depths) in plain C++.  The product's numbers
+// come from the device (region_depth_kernel); region_depths is its twin for the tests that need no GPU.
+struct BedLine {                     // one data line of a BED file: columns 1-3, column 4 or "."
+    std::string chrom, name;
+    uint64_t start = 0, end = 0;
+    size_t line = 0;                 // 1-based, as an editor counts
+};
+struct Region {                      // [start, end) of sequence `seq` (index within the file) of genome file `file_id`
+    int file_id = 0;
+    uint32_t seq = 0, start = 0, end = 0;
+    std::string name;                // "." when the BED gives none, and in window mode
+};
+struct RegionDepth { uint64_t sum = 0, min = 0, max = 0, median = 0, covered = 0; };
+struct RegionReport {
+    std::vector<RegionDepth> rows;   // the regions of the genome file, in the order given
+    uint64_t full = 0, partial = 0, empty = 0;
+};
+constexpr size_t kMaxBedRegions = 65536;          // data lines of a --regions file
+constexpr uint64_t kMaxRegions = 1ull << 22;      // BK_MAX_REGIONS: resolved regions, windows
+// The data lines of a BED file, plain or gzip: tab-separated chrom, 0-based start, end (exclusive), optional name; further columns
+// are ignored, blank lines and lines beginning '#', "track" or "browser" are skipped, a trailing CR is tolerated.  Throws with the
+// file and the line named: a missing column, a start or end that is no number, start >= end, more than kMaxBedRegions lines.
+std::vector<BedLine> read_bed(const std::string& path);
+// Each line's chrom against the CHROM token (as the VCF prints it) of every sequence of every genome file: one region per sequence
+// that carries the name, in the lines' order.  Throws (file and line named) for a name found in no file and an end beyond the sequence.
+std::vector<Region> resolve_bed(const Index& ix, const std::vector<BedLine>& bed, const std::string& path);
+// [iW, min((i + 1)W, len)) over every sequence of every genome file; throws above kMaxRegions windows (the message says to raise W)
+std::vector<Region> window_regions(const Index& ix, uint64_t window);
+// the numbers of the regions of `file_id` among `regions` (the others are passed over), literally: copy the depths, sort, index (L - 1) / 2
+RegionReport region_depths(const Index& ix, int file_id, const Pileup& p, const std::vector<Region>& regions, uint64_t min_depth);
+// OUT/<stem>.regions.tsv: "##min_depth=D", the header line, one line per region of `file_id` among `regions` (rows: theirs, in
+// order; file_id < 0: the two header lines).  The mean from integers: m = 100 * sum / L as m / 100 "." two digits of m % 100.
+void write_regions_tsv(const std::string& out_path, const Index& ix, int file_id, const std::vector<Region>& regions,
+                       const RegionDepth* rows, uint64_t n_rows, uint64_t min_depth);
+
 std::string clean_sample_id(const std::string& path);                               // util.rs:30-50
 void write_vcf(const std::string& out_path, const std::string& reads_path_as_given, const Index& ix, int file_id,
                const std::vector<VcfRecord>& recs);                                 // call.rs:735-774

@@ -71,7 +71,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
-          "            [--consensus-min-freq F] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [-t <THREADS>] [--debug]\n"
+          "            [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -88,7 +89,12 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    frequent bases that together reach F of the depth (more than one: an IUPAC code), N below depth D; no\n"
           "                    filters, no indels, the reference's length\n"
           "  --consensus-min-depth D  depth below which a position is N; at least 1, default 10\n"
-          "  --consensus-min-freq F   share of a position's depth its letter's bases reach together; 0..1, default 0.5\n", stderr);
+          "  --consensus-min-freq F   share of a position's depth its letter's bases reach together; 0..1, default 0.5\n"
+          "  --regions BED     write the depth of every region of the selected genome to <DIR>/<stem>.regions.tsv: length, mean, min,\n"
+          "                    median, max and the positions with depth >= D; BED (plain or gzip): chrom, 0-based start, end, optional\n"
+          "                    name, tab-separated, at most 65536 regions\n"
+          "  --region-window W the same for windows of W positions that tile every sequence (not with --regions); at least 1\n"
+          "  --region-min-depth D     depth from which a position counts as covered; at least 1, default 10\n", stderr);
     exit(code);
 }
 
@@ -204,6 +210,16 @@ Args parse_args(int argc, char** argv) {
             if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
         }
         else if (opt == "--consensus-min-freq") { a.consensus_min_freq = to_double(opt, one()); a.has_consensus_min_freq = true; }
+        else if (opt == "--regions") { a.regions = one(); a.has_regions = true; }
+        else if (opt == "--region-window" || opt == "--region-min-depth") {   // (any integer here: what is out of range is refused by check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--region-window") { a.region_window = x; a.has_region_window = true; }
+            else { a.region_min_depth = x; a.has_region_min_depth = true; }
+        }
         else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
@@ -379,9 +395,14 @@ void check_call_args(const Args& a) {   // call.rs:30-136
         snprintf(buf, sizeof buf, "Consensus minimum frequency must be between 0 and 1, got %g", a.consensus_min_freq);
         die(T, buf);
     }
+    if (a.has_regions && a.has_region_window) die(T, "--regions and --region-window cannot be given together");
+    if (a.has_region_min_depth && !a.has_regions && !a.has_region_window) die(T, "--region-min-depth needs --regions or --region-window");
+    if (a.has_regions && a.regions.empty()) die(T, "--regions needs a BED file");
+    if (a.has_region_window && a.region_window < 1) die(T, "Region window must be at least 1, got " + std::to_string(a.region_window));
+    if (a.region_min_depth < 1) die(T, "Region minimum depth must be at least 1, got " + std::to_string(a.region_min_depth));
 }
 
-// the checked arguments -> what the readers and the per-sample code work from; the primer file is read and the adapters are
+// the checked arguments -> what the readers and the per-sample code work from; the primer file and the regions file are read and the adapters are
 // expanded here, and every violation in them ends the run
 CallConfig make_call_config(const Args& a) {
     const char* T = "bronko::call";
@@ -406,6 +427,13 @@ CallConfig make_call_config(const Args& a) {
     d.min_depth = cp.min_depth; d.min_variant_depth = cp.min_variant_depth;
     bk_consensus_params_default(&c.consensus);
     c.consensus.min_depth = (uint64_t)a.consensus_min_depth; c.consensus.min_freq = a.consensus_min_freq;
+    if (a.has_regions) {   // (the chrom names meet the index's in call_samples, once its metadata is known)
+        try { c.bed = read_bed(a.regions); }
+        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the regions file"); }
+        c.regions_path = a.regions;
+    }
+    if (a.has_region_window) c.region_window = (uint64_t)a.region_window;
+    c.region_min_depth = (uint64_t)a.region_min_depth;
     return c;
 }
 

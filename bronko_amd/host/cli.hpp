@@ -55,6 +55,10 @@ struct Args {
     bool has_consensus_min_depth = false, has_consensus_min_freq = false;
     long consensus_min_depth = 10;  // --consensus-min-depth: positions with less depth are N
     double consensus_min_freq = 0.5;   // --consensus-min-freq: share of the depth the letter's bases must reach together (0..1)
+    std::string regions;            // --regions: BED file of the regions whose depths go to <DIR>/<stem>.regions.tsv (empty: none)
+    bool has_regions = false, has_region_window = false, has_region_min_depth = false;
+    long region_window = 0;         // --region-window: tile every sequence with windows of this many positions instead
+    long region_min_depth = 10;     // --region-min-depth: a position with at least this depth counts as covered
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -83,6 +87,12 @@ struct CallConfig {
     CallParams cp;                          // the printed strand odds (strand_odds, caller.hpp)
     bk_call_params call;                    // bk_sample_call
     bk_consensus_params consensus;          // bk_sample_consensus (--consensus)
+    // --regions: the file's data lines (resolved against the index once it is open, call_run.cpp); --region-window; neither: no report
+    std::string regions_path;
+    std::vector<BedLine> bed;
+    uint64_t region_window = 0;
+    uint64_t region_min_depth = 10;         // bk_sample_region_depths
+    bool region_report() const { return !regions_path.empty() || region_window > 0; }
     // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
     bool trims() const { return !primers.empty() || !adapters.empty(); }
 };

@@ -139,6 +139,79 @@ int bh_write_consensus_fasta(const void* h, int file_id, const char* path, const
     catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
+// ---- --regions / --region-window: regions travel as [n][4] u32 (file_id, seq, start, end), their names joined by '\n' ----------
+namespace {
+std::vector<bronko::Region> regions_of(const uint32_t* regs, const char* names, uint64_t n) {
+    std::vector<bronko::Region> out((size_t)n);
+    const char* at = names;
+    for (uint64_t i = 0; i < n; i++) {
+        out[i].file_id = (int)regs[i * 4]; out[i].seq = regs[i * 4 + 1]; out[i].start = regs[i * 4 + 2]; out[i].end = regs[i * 4 + 3];
+        out[i].name = ".";
+        if (at) {
+            const char* nl = strchr(at, '\n');
+            out[i].name = nl ? std::string(at, nl) : std::string(at);
+            at = nl ? nl + 1 : nullptr;
+        }
+    }
+    return out;
+}
+// *n regions, *names_len bytes of joined names; both written only where they fit cap / names_cap
+int regions_out(const std::vector<bronko::Region>& r, uint64_t cap, uint32_t* regs, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
+    std::string joined;
+    for (size_t i = 0; i < r.size(); i++) joined += (i ? "\n" : "") + r[i].name;
+    *n = r.size();
+    if (names_len) *names_len = joined.size() + 1;
+    if (regs && r.size() <= cap)
+        for (size_t i = 0; i < r.size(); i++) { regs[i * 4] = (uint32_t)r[i].file_id; regs[i * 4 + 1] = r[i].seq; regs[i * 4 + 2] = r[i].start; regs[i * 4 + 3] = r[i].end; }
+    if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
+    return 0;
+}
+}  // namespace
+
+// read_bed + resolve_bed of a --regions file against the index
+int bh_bed_regions(const void* h, const char* path, uint64_t cap, uint32_t* regs, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
+    try {
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        return regions_out(bronko::resolve_bed(*ix, bronko::read_bed(path), path), cap, regs, names, names_cap, n, names_len);
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_window_regions(const void* h, uint64_t window, uint64_t cap, uint32_t* regs, uint64_t* n) {
+    try { return regions_out(bronko::window_regions(*static_cast<const bronko::Index*>(h), window), cap, regs, nullptr, 0, n, nullptr); }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// the host twin of bk_sample_region_depths on the two depth arrays: rows[regions of file_id][5] = sum, min, max, median, covered;
+// tallies = {rows, full, partial, empty}
+int bh_region_depths(const void* h, int file_id, const uint64_t* fwd_depth, const uint64_t* rev_depth, const uint32_t* regs, uint64_t n, uint64_t min_depth,
+                     uint64_t* rows, uint64_t* tallies) {
+    try {
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        if (file_id >= (int)ix->files.size()) throw std::runtime_error("bh_region_depths: no such genome file");
+        const size_t cells4 = ix->total_cells() * 4;
+        bronko::Pileup p;
+        p.fwd_depth.assign(fwd_depth, fwd_depth + cells4); p.rev_depth.assign(rev_depth, rev_depth + cells4);
+        const bronko::RegionReport r = bronko::region_depths(*ix, file_id, p, regions_of(regs, nullptr, n), min_depth);
+        for (size_t i = 0; i < r.rows.size(); i++) {
+            const bronko::RegionDepth& o = r.rows[i];
+            const uint64_t v[5] = {o.sum, o.min, o.max, o.median, o.covered};
+            std::memcpy(rows + i * 5, v, sizeof v);
+        }
+        tallies[0] = r.rows.size(); tallies[1] = r.full; tallies[2] = r.partial; tallies[3] = r.empty;
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_regions_tsv(const void* h, int file_id, const char* path, const uint32_t* regs, const char* names, uint64_t n, const uint64_t* rows, uint64_t n_rows,
+                         uint64_t min_depth) {
+    try {
+        std::vector<bronko::RegionDepth> r((size_t)n_rows);
+        for (size_t i = 0; i < r.size(); i++) { r[i].sum = rows[i * 5]; r[i].min = rows[i * 5 + 1]; r[i].max = rows[i * 5 + 2]; r[i].median = rows[i * 5 + 3]; r[i].covered = rows[i * 5 + 4]; }
+        bronko::write_regions_tsv(path, *static_cast<const bronko::Index*>(h), file_id, regions_of(regs, names, n), r.data(), n_rows, min_depth);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
 int bh_write_kmer_counts(const char* path, int k, const uint64_t* kmers, const uint64_t* counts, uint64_t n, int threads) {
     try { bronko::write_kmer_counts(path, k, kmers, counts, n, threads); return 0; }
     catch (const std::exception& e) { g_err = e.what(); return -1; }

@@ -154,6 +154,15 @@ def _caller_lib():
         L.bh_consensus.argtypes = [vp, C.c_int, vp, vp, C.c_uint64, C.c_double, vp, vp]
         L.bh_write_consensus_fasta.restype = C.c_int
         L.bh_write_consensus_fasta.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, vp, C.c_uint64]
+        u64 = C.c_uint64
+        L.bh_bed_regions.restype = C.c_int
+        L.bh_bed_regions.argtypes = [vp, C.c_char_p, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bh_window_regions.restype = C.c_int
+        L.bh_window_regions.argtypes = [vp, u64, u64, vp, C.POINTER(u64)]
+        L.bh_region_depths.restype = C.c_int
+        L.bh_region_depths.argtypes = [vp, C.c_int, vp, vp, vp, u64, u64, vp, vp]
+        L.bh_write_regions_tsv.restype = C.c_int
+        L.bh_write_regions_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, C.c_char_p, u64, vp, u64, u64]
         L.bh_clean_sample_id.restype = None
         L.bh_clean_sample_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L._caller_ready = True
@@ -224,3 +233,64 @@ def write_consensus_fasta(path, stem, ix, file_id, letters):
     L = _caller_lib()
     if L.bh_write_consensus_fasta(ix.h, file_id, path.encode(), stem.encode(), buf.ctypes.data if len(buf) else None, len(buf)) != 0:
         raise RuntimeError("bronko host: " + L.bh_last_error().decode(errors="replace"))
+
+
+def _host_error(L):
+    return RuntimeError("bronko host: " + L.bh_last_error().decode(errors="replace"))
+
+
+def _region_array(regions):
+    """[(file_id, seq, start, end, ...)] -> [n][4] u32 as the bh_* region functions take them"""
+    return np.ascontiguousarray([tuple(r[:4]) for r in regions], np.uint32).reshape(len(regions), 4)
+
+
+def bed_regions(ix, path):
+    """A --regions BED file read and resolved against the index (caller.cpp read_bed, resolve_bed): [(file_id, seq, start, end, name)]
+    in the file's order; RuntimeError with the file and the line named for what the file or the index refuses."""
+    L = _caller_lib()
+    n, nl = C.c_uint64(), C.c_uint64()
+    if L.bh_bed_regions(ix.h, path.encode(), 0, None, None, 0, C.byref(n), C.byref(nl)) != 0:
+        raise _host_error(L)
+    regs = np.zeros((max(1, n.value), 4), np.uint32)
+    names = C.create_string_buffer(max(1, nl.value))
+    if L.bh_bed_regions(ix.h, path.encode(), n.value, regs.ctypes.data, names, nl.value, C.byref(n), C.byref(nl)) != 0:
+        raise _host_error(L)
+    nm = names.value.decode().split("\n") if n.value else []
+    return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), nm[i]) for i, r in enumerate(regs[:n.value])]
+
+
+def window_regions(ix, window):
+    """--region-window W: [iW, min((i + 1)W, len)) over every sequence of every genome file (caller.cpp window_regions), named '.'."""
+    L = _caller_lib()
+    n = C.c_uint64()
+    if L.bh_window_regions(ix.h, int(window), 0, None, C.byref(n)) != 0:
+        raise _host_error(L)
+    regs = np.zeros((max(1, n.value), 4), np.uint32)
+    if L.bh_window_regions(ix.h, int(window), n.value, regs.ctypes.data, C.byref(n)) != 0:
+        raise _host_error(L)
+    return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), ".") for r in regs[:n.value]]
+
+
+def region_depths(ix, file_id, fwd_depth, rev_depth, regions, min_depth=10):
+    """The host twin of bk_sample_region_depths (caller.cpp region_depths) on the two depth arrays of all cells: (rows, (full,
+    partial, empty)) with one (sum, min, max, median, covered) per region of `file_id` among `regions`, in order."""
+    fd = np.ascontiguousarray(fwd_depth, np.uint64)
+    rd = np.ascontiguousarray(rev_depth, np.uint64)
+    assert len(fd) == len(rd) == ix.total_cells * 4
+    regs = _region_array(regions)
+    rows = np.zeros((max(1, len(regions)), 5), np.uint64)
+    tallies = np.zeros(4, np.uint64)
+    L = _caller_lib()
+    if L.bh_region_depths(ix.h, file_id, fd.ctypes.data, rd.ctypes.data, regs.ctypes.data, len(regions), int(min_depth), rows.ctypes.data, tallies.ctypes.data) != 0:
+        raise _host_error(L)
+    return [tuple(int(v) for v in r) for r in rows[:int(tallies[0])]], tuple(int(t) for t in tallies[1:])
+
+
+def write_regions_tsv(path, ix, file_id, regions, rows, min_depth):
+    """The --regions writer (caller.cpp write_regions_tsv): regions as bed_regions gives them, rows of those of `file_id`."""
+    regs = _region_array(regions)
+    names = "\n".join(r[4] if len(r) > 4 else "." for r in regions).encode()
+    rw = np.ascontiguousarray(rows, np.uint64).reshape(len(rows), 5)
+    L = _caller_lib()
+    if L.bh_write_regions_tsv(ix.h, file_id, path.encode(), regs.ctypes.data, names, len(regions), rw.ctypes.data, len(rows), int(min_depth)) != 0:
+        raise _host_error(L)

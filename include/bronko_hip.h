@@ -404,6 +404,39 @@ void bk_consensus_params_default(bk_consensus_params* p);   /* 10, 0.5 */
 int  bk_sample_consensus(bk_engine* e, const bk_consensus_params* p);
 int  bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, uint8_t* letters, uint64_t cap);
 
+/* ---- per-region depth report (`bronko call --regions / --region-window`; additive, still v8) -------------------------------
+ * Which stretches of the selected genome dropped out, and how deep the rest is, from the two depth planes where they are; a few
+ * numbers per region travel.  The rule, all of it integer arithmetic:
+ *   depth[p]   of a position p of the selected genome = the sum over the four bases of forward + reverse depth (what the
+ *              consensus thresholds), in u64.
+ *   region     a half-open range [start, end) of one sequence (`seq`: its index within the genome file) of one genome file, with
+ *              0 <= start < end <= the sequence's length; L = end - start.  There is no cap on L.
+ *   per region sum     the sum of depth over the region, in u64
+ *              min, max
+ *              median  the element at index (L - 1) / 2 of the region's depths sorted ascending: the lower median (L = 2 gives
+ *                      the smaller value), exact over the whole u64 range
+ *              covered the number of positions with depth >= min_depth (min_depth >= 1)
+ *   mean       printed from integers only: m = (100 * sum) / L, written as m / 100, ".", two digits of m % 100
+ *   per sample n_regions = the selected genome file's regions; full: covered == L; empty: covered == 0; partial: the rest.
+ *   bk_regions_set                    validates every region against the index (file, sequence, bounds: BK_ERR_INVALID, the
+ *                                     message names the entry) and replaces the engine's table between samples (BK_ERR_STATE
+ *                                     inside one); n = 0 clears; at most BK_MAX_REGIONS.  The regions are kept grouped by genome
+ *                                     file, in the caller's order within a file.  The result buffers are allocated here: a sample
+ *                                     allocates nothing, an engine that never sets regions allocates and launches nothing.  Per
+ *                                     engine: forks set their own.
+ *   bk_sample_region_depths           after the sample's bk_sample_call (BK_ERR_STATE before it, inside a sample, after a later
+ *                                     bk_sample_begin, and with no regions set; BK_ERR_INVALID for min_depth == 0); asynchronous on
+ *                                     the engine's stream.
+ *   bk_sample_download_region_depths  synchronises; copies min(cap, n_regions) rows, in the order they were set (out may be
+ *                                     NULL).  No genome selected: file_id = -1, n_regions and every tally 0, no rows. */
+#define BK_MAX_REGIONS (1u << 22)
+typedef struct { int32_t file_id; uint32_t seq; uint32_t start, end; } bk_region;   /* seq: index within the file */
+typedef struct { uint64_t sum, min, max, median, covered; } bk_region_depth;
+typedef struct { int32_t file_id; uint32_t n_regions; uint64_t full, partial, empty; } bk_region_summary;
+int  bk_regions_set(bk_engine* e, const bk_region* regions, uint64_t n);
+int  bk_sample_region_depths(bk_engine* e, uint64_t min_depth);
+int  bk_sample_download_region_depths(bk_engine* e, bk_region_summary* summary, bk_region_depth* out, uint64_t cap);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
