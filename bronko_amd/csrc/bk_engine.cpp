@@ -519,7 +519,11 @@ static int make_l2_room(bk_engine* e, bk::ScanArgs& a, uint64_t l2_cap) {
 // The binned scan's items, bin by bin -> u64 plane (before Level 2 adds to it: a sample's first launch finds the V part all zero).
 // `wait_v`: the mate file's first launch, whose V items wait for the regional finalize (or for the next launch, which sends them to
 // the plane); Level 2 then notes the V rows it writes to.
-static int bin_items(bk_engine* e, bk::ScanArgs& a, int mate, uint32_t grid, bool wait_v) {
+// `ride`: Level 2 follows and counts the E bins inside its own launch (*ride: what launch_level2 is to be given) -- both only add
+// to the E counters with atomics and read only what the scan wrote, and nothing reads an E counter before the finalize.  Then
+// bin_count_kernel is launched over the V bins alone (its plain read-modify-write of the V part stays in front of Level 2), and
+// with waiting V items not at all.  E bin 0 zeroes the next launch's overflow count wherever the E bins run: once per scan launch.
+static int bin_items(bk_engine* e, bk::ScanArgs& a, int mate, uint32_t grid, bool wait_v, bk::BinArgs* ride) {
     const IndexTables& ix = *e->ix;
     MatePlane& pl = e->mate[mate];
     bk_engine::Span sp(e, 3);
@@ -532,7 +536,7 @@ static int bin_items(bk_engine* e, bk::ScanArgs& a, int mate, uint32_t grid, boo
     b.v_mode = ix.item_v_mode >= 0 ? ix.item_v_mode : (v_clean ? 2 : 1);
     if (const char* ba = test_env("BK_BIN_ABLATE")) b.ablate = atoi(ba);
     if (wait_v) {
-        e->pending.on = true; e->pending.mate = mate; e->pending.b = b;
+        e->pending.on = true; e->pending.mate = mate; e->pending.b = b;   // (the V bins' side of b: the same whoever counts the E bins)
         b.part = 1;
         a.touch_v = pl.fuse_touch.p; a.rl_recip = ~0ull / (unsigned long long)(ix.v_span + 1) + 1ull;
         pl.items_wait();
@@ -540,19 +544,26 @@ static int bin_items(bk_engine* e, bk::ScanArgs& a, int mate, uint32_t grid, boo
         pl.no_more_waiting();
         if (e->fuse_ok) a.touch_v = nullptr;   // (a push of several launches: set by the first)
     }
+    if (ride) {
+        *ride = b; ride->part = 1;
+        if (wait_v) return BK_OK;
+        b.part = 2;
+    }
     BK_HIP(bk::launch_bin_count(b, e->stream));
     return BK_OK;
 }
+// will level2_and_fold launch level2_kernel for this scan launch?  (Only then can the E bins ride in it.)
+static bool level2_runs(const bk_engine* e, const bk::ScanArgs& a) { return e->ix->ablate != 1 && e->ix->ablate != 4 && bk::level2_launches(a); }
 // Level 2 over the k-mers the scan left marked (it clears the marks it takes); behind the slab scan, its per-cell bin slabs -> u64 plane
-static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32_t grid) {
+static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32_t grid, const bk::BinArgs* ride) {
     const IndexTables& ix = *e->ix;
     bk_engine::Span sp(e, 3);
     if (int rc = l2_count_report(e, a)) return rc;
-    if (ix.ablate == 1 || ix.ablate == 4) {   // measurement aids: without Level 2
+    if (ix.ablate == 1 || ix.ablate == 4) {   // measurement aids: without Level 2 (and without a ride: push_device asked level2_runs)
         BK_HIP(hipMemsetAsync(e->n_bits.p, 0, (size_t)a.n_records * a.l2_words * sizeof(unsigned int), e->stream));
         BK_HIP(hipMemsetAsync(e->n_any.p, 0, e->n_any.n * sizeof(unsigned int), e->stream));
     }
-    else BK_HIP(bk::launch_level2(a, ix.n_cus, e->stream));
+    else BK_HIP(bk::launch_level2(a, ix.n_cus, e->stream, ride));
     if (!e->use_items) {
         bk::FoldArgs f{};
         f.slabs = e->slabs.p; f.n_slabs = grid; f.n_lds_bins = ix.n_lds_bins; f.id_at = ix.id_at.p; f.cell_codes = ix.cell_codes.p + bk::scan_ref_pad_words(); f.win_lo = a.win_lo; f.win_dev = a.win_dev; f.touch_e = a.touch_e;
@@ -591,8 +602,11 @@ int push_device(bk_engine* e, int mate, const Records& r) {
                 if (e->use_items) { a.ov_par = e->ov_par; BK_HIP(bk::launch_scan_items(a, grid, e->stream)); }
                 else BK_HIP(bk::launch_scan_count(a, grid, e->stream));
             }
-            if (e->use_items) { if (int rc = bin_items(e, a, mate, grid, wait_v)) return rc; }
-            if (int rc = level2_and_fold(e, a, mate, grid)) return rc;
+            // (the binned scan followed by a Level 2 launch: its E bins ride in that launch; BK_NO_E_RIDE, testing build: a launch of their own)
+            bk::BinArgs ride_b{};
+            const bool ride = e->use_items && level2_runs(e, a) && !test_env("BK_NO_E_RIDE");
+            if (e->use_items) { if (int rc = bin_items(e, a, mate, grid, wait_v, ride ? &ride_b : nullptr)) return rc; }
+            if (int rc = level2_and_fold(e, a, mate, grid, ride ? &ride_b : nullptr)) return rc;
         }
     }
     BK_HIP(hipGetLastError());

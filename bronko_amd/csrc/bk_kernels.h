@@ -305,7 +305,6 @@ int scan_bit_back_words();
 size_t scan_lds_budget();   // bytes available for histogram bins (4 B each) + the staged reference
 size_t scan_ref_lds_bytes(uint32_t total_cells);
 size_t scan_lds_bytes(uint32_t n_lds_bins, bool ref_in_lds, uint32_t total_cells);
-hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream);   // after launch_scan_count, same arguments
 hipError_t launch_scan_count(const ScanArgs& a, uint32_t grid, hipStream_t stream);
 void launch_fold(const FoldArgs& f, hipStream_t stream);
 // ---- the binned scan (bk_scan_items.hip) ----
@@ -328,7 +327,7 @@ struct BinArgs {
     uint32_t rl;                    // v_span + 1
     int v_mode;                     // how a V bin reaches the plane: 0 atomics, 1 plain read-modify-write, 2 plain stores (the V part is all zero)
     int part;                       // 0: every bin; 1: the E bins only (the V bins' items wait for the regional finalize, FinalizeArgs::f_items, or
-                                    // for a launch with part = 2); 2: the V bins only
+                                    // for a launch with part = 2); 2: the V bins only (also: the E bins ride in the Level 2 launch, launch_level2)
     int ablate;                     // measurement aid (-DBK_TESTING build only): 1 no items read, 2 nothing written to the plane, 3 no E atomics, 4 no V writes
 };
 // can this index take the binned scan (window of win_cells cells in LDS, dense planes)?  Fills g.
@@ -338,6 +337,11 @@ uint32_t items_max_grid(int n_cus);
 size_t items_lds_bytes(const ItemGeom& g, uint32_t win_cells);
 hipError_t launch_scan_items(const ScanArgs& a, uint32_t grid, hipStream_t stream);
 hipError_t launch_bin_count(const BinArgs& b, hipStream_t stream);
+// Level 2, after launch_scan_count / launch_scan_items with the same arguments.  ride: null, or the BinArgs of the launch_scan_items
+// it follows -- that launch's E bins are then counted by extra workgroups of level2_kernel's launch (both only add to the plane
+// with atomics and read only what the scan wrote), and launch_bin_count is wanted for its V bins at most (part = 2, in front of this).
+inline bool level2_launches(const ScanArgs& a) { return a.n_records != 0 && a.W > 0; }   // else launch_level2 launches nothing: no ride
+hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const BinArgs* ride = nullptr);
 void launch_ktab_stats(const unsigned long long* keys, const unsigned int* cnt, uint32_t log2n, unsigned long long ci,
                        unsigned long long cx, unsigned long long* out, hipStream_t stream);
 void launch_ktab_rehash(const unsigned long long* okeys, const unsigned int* ocnt, uint32_t olog2, unsigned long long* nkeys, unsigned int* ncnt,

@@ -26,6 +26,7 @@
 #include <utility>
 #include <vector>
 
+#include "bk_bin_count.h"
 #include "bk_device.h"
 #include "bk_kernels.h"
 #include "bk_scan_common.h"
@@ -1560,9 +1561,19 @@ __global__ __launch_bounds__(kL2Block) void nbatch_kernel(ScanArgs a) {
     }
 }
 
+// The ride (launch_level2): the grid is Level 2's own n_l2 workgroups and, behind them, one per E bin of the scan launch this one
+// follows -- those run bin_count_kernel's body on `ride` and leave.  Level 2's workgroups take their stride and their planned
+// share from n_l2, never from gridDim.x.
+static_assert(kL2Block == kBinBlock, "an E bin rides in a workgroup of level2_kernel");
+static_assert(kEBinAccWords * sizeof(unsigned int) <= (size_t)kL2Waves * kL2QueueCap * sizeof(unsigned long long), "the ride's accumulator lies in the slow-path queues");
+static_assert(sizeof(ScanArgs) + sizeof(uint32_t) + sizeof(BinArgs) + 16 <= 4096, "kernel arguments of level2_kernel");
 template <bool STATS, int KT, bool SPARSE>
-__global__ __launch_bounds__(kL2Block) void level2_kernel(ScanArgs a) {
+__global__ __launch_bounds__(kL2Block) void level2_kernel(ScanArgs a, uint32_t n_l2, BinArgs ride) {
     __shared__ unsigned long long queue_c[kL2Waves * kL2QueueCap];   // slow-path queue: canonical k-mer | orientation << 62 | stat_only << 63
+    if (blockIdx.x >= n_l2) {   // (wave-uniform, the whole workgroup) an E bin: its accumulator where Level 2's workgroups keep their slow-path queues
+        bin_count_body<true>(ride, blockIdx.x - n_l2, reinterpret_cast<unsigned int*>(queue_c));
+        return;
+    }
     __shared__ unsigned int rec_q[kL2Waves * kL2QueueCap];
     __shared__ unsigned long long kmer_q[kL2Waves * kL2KmerCap];     // record << 16 | k-mer index in the record
     const int lane = threadIdx.x & 63;
@@ -1887,7 +1898,7 @@ __global__ __launch_bounds__(kL2Block) void level2_kernel(ScanArgs a) {
     const uint64_t n_blk = (n_any + kAnyWords - 1) / kAnyWords;
 
     // (ScanArgs::l2_plan: with few records marked, few workgroups -- the others leave at once)
-    const uint32_t g_work = a.l2_plan ? min((uint32_t)gridDim.x, max(*a.l2_plan, 1u)) : (uint32_t)gridDim.x;
+    const uint32_t g_work = a.l2_plan ? min(n_l2, max(*a.l2_plan, 1u)) : n_l2;
     if (blockIdx.x >= g_work) return;
     for (uint64_t blk = (uint64_t)blockIdx.x * kL2Waves + wave; blk < n_blk; blk += (uint64_t)g_work * kL2Waves) {
         const uint64_t i = blk * kAnyWords + lane;
@@ -2061,11 +2072,11 @@ __global__ __launch_bounds__(1024) void l2_plan_kernel(const unsigned int* __res
     }
 }
 
-hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream) {
-    if (a.n_records == 0 || a.W <= 0) return hipSuccess;
+hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const BinArgs* ride) {
+    if (!level2_launches(a)) return ride ? hipErrorInvalidValue : hipSuccess;   // (a ride nobody carries: its E bins would never be counted)
     const bool stats = a.ktab_keys != nullptr;
-    void (*kern)(ScanArgs);
-    if (!a.n_direct) {   // the N runs first (they mark k-mers for the kernel below); ScanArgs::n_direct: the scan left none
+    if (!a.n_direct) {
+        void (*kern)(ScanArgs);   // the N runs first (they mark k-mers for the kernel below); ScanArgs::n_direct: the scan left none
 #define BK_PICKN(KT) (!a.touch_v ? (stats ? nbatch_kernel<true, KT, false> : nbatch_kernel<false, KT, false>) \
                                  : (stats ? nbatch_kernel<true, KT, true> : nbatch_kernel<false, KT, true>))
         kern = a.k == 21 ? BK_PICKN(21) : a.k == 31 ? BK_PICKN(31) : BK_PICKN(0);
@@ -2076,7 +2087,7 @@ hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream) {
     }
 #define BK_PICK(KT) (!a.touch_v ? (stats ? level2_kernel<true, KT, false> : level2_kernel<false, KT, false>) \
                                 : (stats ? level2_kernel<true, KT, true> : level2_kernel<false, KT, true>))
-    kern = a.k == 21 ? BK_PICK(21) : a.k == 31 ? BK_PICK(31) : BK_PICK(0);
+    void (*kern)(ScanArgs, uint32_t, BinArgs) = a.k == 21 ? BK_PICK(21) : a.k == 31 ? BK_PICK(31) : BK_PICK(0);
 #undef BK_PICK
     const uint64_t blks = (a.n_records + 32 * kAnyWords - 1) / (32 * kAnyWords);     // a wave takes kAnyWords words of l2_any at a time
     // One genome file: a thousandth of the k-mers are marked, and four thousand waves that find nothing to do still take their turn
@@ -2084,7 +2095,10 @@ hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream) {
     // waves; alone the kernel takes what it took).  Several files: the marks are Level 2's real work (config 3 lost 8 % that way).
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((blks + kL2Waves - 1) / kL2Waves, (uint64_t)n_cus * (a.n_files == 1 ? 2 : 8)));
     if (a.l2_plan) hipLaunchKernelGGL(l2_plan_kernel, dim3(1), dim3(1024), 0, stream, (const unsigned int*)a.l2_any, (a.n_records + 31) / 32, a.l2_plan, a.l2_min_grid);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kL2Block), 0, stream, a);
+    // the ride: the E bins of the scan launch this one follows, one workgroup each behind Level 2's own (none when that launch had no scan workgroup)
+    const BinArgs rb = ride ? *ride : BinArgs{};
+    const unsigned n_ride = ride && ride->n_wg ? ride->ig.n_ebins : 0u;
+    hipLaunchKernelGGL(kern, dim3(grid + n_ride), dim3(kL2Block), 0, stream, a, (uint32_t)grid, rb);
     return hipGetLastError();
 }
 
