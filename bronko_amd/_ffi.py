@@ -62,6 +62,19 @@ class RegionDepth(C.Structure):  # bk_region_depth
     _fields_ = [("sum", C.c_uint64), ("min", C.c_uint64), ("max", C.c_uint64), ("median", C.c_uint64), ("covered", C.c_uint64)]
 
 
+class IndelConfig(C.Structure):  # bk_indel_config
+    _fields_ = [("max_len", C.c_uint32), ("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
+class IndelParams(C.Structure):  # bk_indel_params
+    _fields_ = [("min_reads", C.c_uint64), ("min_af_ppm", C.c_uint32)]
+
+
+class IndelSummary(C.Structure):  # bk_indel_summary
+    _fields_ = [("records", C.c_uint64), ("anchored", C.c_uint64), ("ref_spanning", C.c_uint64), ("supporting", C.c_uint64),
+                ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
+
+
 class RegionSummary(C.Structure):  # bk_region_summary
     _fields_ = [("file_id", C.c_int32), ("n_regions", C.c_uint32), ("full", C.c_uint64), ("partial", C.c_uint64), ("empty", C.c_uint64)]
 
@@ -83,6 +96,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_timing_enable", "bk_timing_read", "bk_call_params_default", "bk_sample_call", "bk_sample_download_calls", "bk_sample_download_noise",
            "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
+           "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -210,6 +224,14 @@ def load(testing=None):
     L.bk_sample_region_depths.argtypes = [vp, u64]
     L.bk_sample_download_region_depths.restype = C.c_int
     L.bk_sample_download_region_depths.argtypes = [vp, C.POINTER(RegionSummary), vp, u64]
+    L.bk_indels_enable.restype = C.c_int
+    L.bk_indels_enable.argtypes = [vp, C.POINTER(IndelConfig)]
+    L.bk_sample_indels.restype = C.c_int
+    L.bk_sample_indels.argtypes = [vp, C.POINTER(IndelParams)]
+    L.bk_sample_download_indels.restype = C.c_int
+    L.bk_sample_download_indels.argtypes = [vp, C.POINTER(IndelSummary), vp, u64]
+    L.bk_sample_download_indel_span.restype = C.c_int
+    L.bk_sample_download_indel_span.argtypes = [vp, vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

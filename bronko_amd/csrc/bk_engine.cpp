@@ -274,6 +274,15 @@ int bk_sample_begin(bk_engine* e) {
         BK_HIP(hipMemsetAsync(e->dump->out.p, 0, e->dump->out.n * sizeof(unsigned long long), e->stream));
         e->dump->upper[0] = e->dump->upper[1] = 0; e->dump->in_sample = true; e->dump->finalized_mates = 0;
     }
+    if (e->indels) {   // an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
+        Indels& d = *e->indels;
+        BK_HIP(hipMemsetAsync(d.key0.p, 0xff, d.key0.n * sizeof(unsigned long long), e->stream));
+        BK_HIP(hipMemsetAsync(d.key1.p, 0xff, d.key1.n * sizeof(unsigned long long), e->stream));
+        BK_HIP(hipMemsetAsync(d.counts.p, 0, d.counts.n * sizeof(unsigned int), e->stream));
+        BK_HIP(hipMemsetAsync(d.span.p, 0, d.span.n * sizeof(unsigned int), e->stream));
+        BK_HIP(hipMemsetAsync(d.tallies.p, 0, d.tallies.n * sizeof(unsigned long long), e->stream));
+        d.in_sample = true; d.summed = false; d.made = false;
+    }
     TrimStage* const trim_stages[] = {e->primers.get(), e->adapters.get()};
     for (TrimStage* t : trim_stages)
         if (t) { BK_HIP(hipMemsetAsync(t->stats.p, 0, t->stats.n * sizeof(unsigned long long), e->stream)); t->in_sample = true; }
@@ -364,6 +373,32 @@ static int dump_push(bk_engine* e, int mate, const Records& r, uint64_t upper) {
                                e->ix->n_cus, e->stream);
     BK_HIP(hipGetLastError());
     return note_table_fill(e, d.t, d.out.p);
+}
+
+// bk_indels_enable: the records' anchors, spans and events (indel_scan_kernel), on the engine stream behind the scan of the same records
+static bk::IndelArgs indel_args(const bk_engine* e) {
+    const IndexTables& ix = *e->ix;
+    const Indels& d = *e->indels;
+    bk::IndelArgs a{};
+    a.kmer_pos = ix.kmer_pos.p; a.pilots = ix.pilots.p; a.m = ix.m; a.log2nb = ix.log2nb; a.log2p = ix.log2p; a.n_full = ix.n_full;
+    a.unique_bits = d.unique_bits.p;
+    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words(); a.rc_words = ix.rc_words.p + bk::scan_ref_pad_words();
+    a.total_cells = (uint32_t)ix.total_cells; a.k = ix.k;
+    a.seq_lo = d.seq_lo.p; a.n_seqs = (uint32_t)(d.seq_lo.n - 1);
+    a.nruns = d.nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
+    a.max_len = d.cfg.max_len; a.max_mismatches = d.cfg.max_mismatches;
+    a.key0 = d.key0.p; a.key1 = d.key1.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
+    a.span = d.span.p; a.tallies = d.tallies.p;
+    a.rows = d.rows.p; a.row_cap = d.rows.n;
+    return a;
+}
+static int indel_push(bk_engine* e, const Records& r) {
+    if (!e->indels->in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
+    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_indels_enable: a batch of 2^31 records or more");
+    bk::IndelArgs a = indel_args(e);
+    a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.n_records_dev = r.n_dev; a.stride_words = r.stride_words;
+    bk::launch_indel_scan(a, e->ix->n_cus, e->stream);
+    return BK_OK;
 }
 
 #ifdef BK_TESTING   // (the testing build's reports)
@@ -609,6 +644,7 @@ int push_device(bk_engine* e, int mate, const Records& r) {
             if (int rc = level2_and_fold(e, a, mate, grid, ride ? &ride_b : nullptr)) return rc;
         }
     }
+    if (e->indels) { if (int rc = indel_push(e, r)) return rc; }
     BK_HIP(hipGetLastError());
     if (!r.n_dev) pl.pushed_records += n;
     return note_ktab_fill(e);
@@ -1317,6 +1353,100 @@ int bk_sample_download_region_depths(bk_engine* e, bk_region_summary* summary, b
         BK_HIP(hipMemcpyAsync(out, e->regions->rows.p, (size_t)n * sizeof(bk_region_depth), hipMemcpyDeviceToHost, e->stream));
         BK_HIP(hipStreamSynchronize(e->stream));
     }
+    return BK_OK;
+}
+
+// ---- short insertions and deletions from the reads (bk_indels.hip) ------------------------------------------------
+int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_indels_enable comes between samples");
+    const IndexTables& ix = *e->ix;
+    if (cfg) {
+        if (cfg->max_len < 1 || cfg->max_len > BK_INDEL_MAX_LEN) return fail(BK_ERR_INVALID, "bk_indels_enable: max_len must be 1..%d, got %u", BK_INDEL_MAX_LEN, cfg->max_len);
+        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_indels_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
+        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_indels_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
+        if (ix.n_files != 1)
+            return fail(BK_ERR_INVALID, "bk_indels_enable: the index has %d genome files; indels are called against an index of one genome file", ix.n_files);
+        if (ix.W <= 0 || ix.n_full == 0) return fail(BK_ERR_INVALID, "bk_indels_enable: the index has no window of reference k-mers");
+        if (!ix.rc_words.p)   // (build_index_tables makes it with the binned scan's seed tables: fewer than 2^27 cells, at least k)
+            return fail(BK_ERR_UNSUPPORTED, "bk_indels_enable: the engine holds no reverse-complemented reference (it is made for a genome of k to 2^27 - 1 positions; this one has %llu)",
+                        (unsigned long long)ix.total_cells);
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
+    e->indels.reset();
+    if (!cfg) return BK_OK;
+    std::unique_ptr<Indels> d(new Indels());
+    d->cfg = *cfg;
+    {   // a histogram of the ids over the cells: one bit per id that starts at exactly one cell
+        std::vector<uint32_t> id_at((size_t)ix.total_cells);
+        BK_HIP(hipMemcpy(id_at.data(), ix.id_at.p, id_at.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> seen(ix.n_full, 0);
+        for (uint32_t id : id_at) if (id < ix.n_full && seen[id] < 2) seen[id]++;
+        std::vector<uint32_t> bits(((size_t)ix.n_full + 31) / 32, 0u);
+        for (uint32_t id = 0; id < ix.n_full; id++) if (seen[id] == 1) bits[id >> 5] |= 1u << (id & 31u);
+        BK_HIP(d->unique_bits.upload(bits));
+    }
+    std::vector<uint32_t> lo;
+    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) lo.push_back((uint32_t)ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q]);
+    lo.push_back((uint32_t)ix.total_cells);
+    if (lo.size() < 2) return fail(BK_ERR_INVALID, "bk_indels_enable: the genome file has no sequence");
+    BK_HIP(d->seq_lo.upload(lo));
+    BK_HIP(d->nruns.upload(ix.h_nonacgt));
+    const size_t slots = (size_t)1 << cfg->table_log2;
+    BK_HIP(d->key0.alloc(slots)); BK_HIP(d->key1.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
+    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
+    BK_HIP(d->tallies.alloc(8));
+    e->indels = std::move(d);
+    return BK_OK;
+}
+
+int bk_sample_indels(bk_engine* e, const bk_indel_params* p) {
+    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
+    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_indels: min_reads must be at least 1, got 0");
+    if (p->min_af_ppm > 1000000u) return fail(BK_ERR_INVALID, "bk_sample_indels: min_af_ppm must be 0..1000000, got %u", p->min_af_ppm);
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels comes after bk_sample_finalize");
+    if (!e->indels || !e->indels->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels: indels were not enabled for this sample (bk_indels_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_indels: bk_sample_finalize has not run for this sample");
+    Indels& d = *e->indels;
+    BK_HIP(hipSetDevice(e->device));
+    bk::IndelArgs a = indel_args(e);
+    a.min_reads = p->min_reads; a.min_af_ppm = p->min_af_ppm;
+    bk_engine::Span sp(e, 1);
+    if (!d.summed) { bk::launch_indel_span_prefix(a, e->stream); d.summed = true; }
+    BK_HIP(hipMemsetAsync(d.tallies.p + 5, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
+    bk::launch_indel_report(a, e->stream);
+    BK_HIP(hipGetLastError());
+    d.made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indels comes after this sample's bk_sample_indels");
+    Indels& d = *e->indels;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long t[8];
+    BK_HIP(hipMemcpyAsync(t, d.tallies.p, sizeof t, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    summary->records = t[0]; summary->anchored = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->discordant = t[4];
+    summary->candidates = t[5]; summary->reported = t[6]; summary->overflow = t[7] ? 1 : 0;
+    if (t[7]) return fail(BK_ERR_INVALID, "bk_sample_download_indels: more than 2^%u distinct candidate events: enable indels with a larger table_log2", d.cfg.table_log2);
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[6], cap), d.rows.n);
+    if (n && records) {
+        BK_HIP(hipMemcpyAsync(records, d.rows.p, (size_t)n * sizeof(bk_indel_record), hipMemcpyDeviceToHost, e->stream));
+        BK_HIP(hipStreamSynchronize(e->stream));
+    }
+    return BK_OK;
+}
+
+int bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap) {
+    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indel_span comes after this sample's bk_sample_indels");
+    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_indel_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipMemcpyAsync(span, e->indels->span.p, (size_t)e->ix->total_cells * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
     return BK_OK;
 }
 

@@ -232,6 +232,23 @@ struct Regions {
     uint32_t max_file_regions = 0;          // regions of the genome file with the most: the kernel's grid
 };
 
+// bk_indels_enable: what indel_scan_kernel reads beside the index tables (bk_indels.hip), the sample's event table, span array and
+// tallies, and the report's rows -- all allocated by the call
+struct Indels {
+    bk_indel_config cfg{};
+    DevBuf<uint32_t> unique_bits;           // one bit per reference k-mer id: it starts at exactly one cell (a histogram of id_at)
+    DevBuf<uint32_t> seq_lo;                // [sequences + 1] first cells, then total_cells
+    DevBuf<uint2> nruns;                    // IndexTables::h_nonacgt
+    DevBuf<unsigned long long> key0, key1;  // [2^table_log2] the event table's two key words (~0 = free)
+    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
+    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_indels
+    DevBuf<unsigned long long> tallies;     // [8] bk_kernels.h IndelArgs::tallies
+    DevBuf<bk_indel_record> rows;           // [2^table_log2]
+    bool in_sample = false;                 // enabled when the current / last sample began
+    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_indels ran)
+    bool made = false;                      // ... and the rows are this sample's
+};
+
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
 // by an engine and its forks, freed with the last of them.
 struct IndexTables {
@@ -283,6 +300,7 @@ struct IndexTables {
     DevBuf<int32_t> seq_first, n_seqs_d;
     std::vector<uint64_t> h_seq_cell, h_seq_len;   // host copies of seq_cell, seq_len_d, seq_first, n_seqs_d (bk_regions_set checks against them)
     std::vector<int32_t> h_seq_first, h_n_seqs;
+    std::vector<uint2> h_nonacgt;           // {first cell, end} of every run of reference letters that are not ACGT, ascending (bk_indels_enable)
     int max_seqs_per_file = 0;
     uint64_t max_file_cells = 0;
     uint64_t max_file_cells_idx = 0;        // cells of the genome file with the most (pileup rows)
@@ -448,6 +466,7 @@ struct bk_engine {
     bool cons_made = false;
     std::unique_ptr<Regions> regions;       // bk_regions_set (null: no regions, no launch, no buffers)
     bool regions_made = false;              // bk_sample_region_depths ran for the current sample and table
+    std::unique_ptr<Indels> indels;         // bk_indels_enable (null: no table, no launch, no buffers)
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

@@ -589,7 +589,15 @@ int IndexBuilder::reference_walk() {
             for (int sidx = 0; sidx < ix->n_seqs[f]; sidx++, sq++) {
                 const uint64_t len = ix->seq_lens[sq], c0 = cell_off[f][sidx];
                 const uint8_t* seq = ix->seqs[sq];
-                for (uint64_t i = 0; i < len; i++) h_refw[pad_w + ((c0 + i) >> 4)] |= (uint32_t)bronko::nt_to_bits(seq[i]) << (2 * ((c0 + i) & 15));
+                // (on the way: the runs of letters that are not ACGT, which this packing reads as A -- bk_indels_enable keeps records off them)
+                uint64_t run0 = len;   // first letter of the open run; len: none is open
+                for (uint64_t i = 0; i < len; i++) {
+                    h_refw[pad_w + ((c0 + i) >> 4)] |= (uint32_t)bronko::nt_to_bits(seq[i]) << (2 * ((c0 + i) & 15));
+                    const bool other = bronko::acgt_code(seq[i]) < 0;
+                    if (other && run0 == len) run0 = i;
+                    else if (!other && run0 != len) { tab.h_nonacgt.push_back(make_uint2((uint32_t)(c0 + run0), (uint32_t)(c0 + i))); run0 = len; }
+                }
+                if (run0 != len) tab.h_nonacgt.push_back(make_uint2((uint32_t)(c0 + run0), (uint32_t)(c0 + len)));
                 // long sequences in pieces (every piece re-reads the k - 1 bases before it)
                 for (uint64_t a = 0; a + k <= len; a += 8192) jobs.push_back(SeqJob{seq + a, std::min<uint64_t>(len - a, 8192 + (uint64_t)k - 1), c0 + a});
             }

@@ -454,6 +454,37 @@ struct RegionArgs {
 };
 constexpr uint32_t kRegionLdsDepths = 2048;   // a region of at most this many positions is staged in LDS once (16 KB)
 void launch_region_depths(const RegionArgs& a, uint32_t max_file_regions, hipStream_t stream);
+// bk_indels_enable: short insertions and deletions from the reads (bk_indels.hip; the rule: include/bronko_hip.h)
+typedef bk_indel_record IndelRecordDev;
+struct IndelArgs {
+    // a batch of records (Records of bk_engine.h): indel_scan_kernel
+    const uint32_t* words; const uint16_t* lens;
+    uint64_t n_records; const unsigned long long* n_records_dev;
+    uint32_t stride_words;
+    // the index: the perfect hash of the reference k-mers, one bit per id (it starts at one cell), both references past their padding
+    const KmerPos* kmer_pos; const uint16_t* pilots;
+    uint32_t m, log2nb, log2p, n_full;
+    const uint32_t* unique_bits;
+    const uint32_t* ref_words; const uint32_t* rc_words;
+    uint32_t total_cells; int32_t k;
+    const uint32_t* seq_lo;              // [n_seqs + 1] first cell of each sequence, then total_cells
+    uint32_t n_seqs;
+    const uint2* nruns;                  // [n_nruns] {first cell, end} of the runs of letters that are not ACGT, ascending
+    uint32_t n_nruns;
+    uint32_t max_len, max_mismatches;
+    // the sample: event table (two key words ~0 = free, {fwd, rev}), span, counters
+    unsigned long long* key0; unsigned long long* key1;
+    unsigned int* counts;                // [slots][2]
+    uint32_t log2n;
+    unsigned int* span;                  // [total_cells + 2]
+    unsigned long long* tallies;         // [8] records, anchored, ref_spanning, supporting, discordant, candidates, reported, overflow
+    // the report: indel_report_kernel
+    uint64_t min_reads; uint32_t min_af_ppm;
+    IndelRecordDev* rows; uint64_t row_cap;
+};
+void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream);
+void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream);   // span in place, once per sample
+void launch_indel_report(const IndelArgs& a, hipStream_t stream);
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

@@ -434,6 +434,36 @@ class Engine:
         _check(self._L.bk_sample_download_consensus(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, buf[:min(cap, int(summ.positions))].tobytes()
 
+    def indels_enable(self, max_len=32, max_mismatches=2, table_log2=16):
+        """bk_indels_enable: indel_scan_kernel runs behind every scan of the samples that begin from now on; max_len=None disables."""
+        cfg = None if max_len is None else C.byref(_ffi.IndelConfig(int(max_len), int(max_mismatches), int(table_log2)))
+        _check(self._L.bk_indels_enable(self.h, cfg), self._L)
+
+    def sample_indels(self, min_reads=5, min_af_ppm=30000):
+        """bk_sample_indels: the finalized sample's events that pass the thresholds, on the device (asynchronous)."""
+        _check(self._L.bk_sample_indels(self.h, C.byref(_ffi.IndelParams(int(min_reads), int(min_af_ppm)))), self._L)
+
+    def download_indels(self, cap=None):
+        """(summary, rows) of sample_indels: min(cap, summary.reported) rows (cell, len, fwd, rev, ref_span, seq) -- len > 0 a deletion,
+        < 0 an insertion --, all by default, sorted by (cell, kind, length, seq)."""
+        summ = _ffi.IndelSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_indels(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        dt = np.dtype([("cell", np.uint32), ("len", np.int32), ("fwd", np.uint32), ("rev", np.uint32), ("ref_span", np.uint32),
+                       ("pad", np.uint32), ("seq", np.uint64)])
+        buf = np.zeros(max(1, cap), dt)
+        _check(self._L.bk_sample_download_indels(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        rows = [(int(r["cell"]), int(r["len"]), int(r["fwd"]), int(r["rev"]), int(r["ref_span"]), int(r["seq"])) for r in buf[:min(cap, int(summ.reported))]]
+        rows.sort(key=lambda r: (r[0], 1 if r[1] < 0 else 0, abs(r[1]), r[5]))
+        return summ, rows
+
+    def download_indel_span(self):
+        """bk_sample_download_indel_span: the prefix-summed span array of all cells (after sample_indels)."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(self._L.bk_sample_download_indel_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def regions_set(self, regions):
         """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
         arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])

@@ -199,6 +199,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--keep-kmer-info: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.indels) {           // (likewise: a sample's events and span array are one engine's)
+        LOG_DEBUG(T, "--indels: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
     if (!shard_mode) shard_devices.clear();
     return shard_devices;
@@ -224,8 +228,11 @@ struct SampleData {
     std::vector<uint8_t> letters;
     bk_region_summary rsumm{};                            // --regions, --region-window
     std::vector<bk_region_depth> rrows;
+    bk_indel_summary isumm{};                             // --indels
+    std::vector<IndelEvent> indels;
 };
 
+constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
 struct CallRun {
@@ -270,6 +277,8 @@ struct CallRun {
         // the readers stay few until the engines stand -- bk_engine_create runs on all cores for seconds)
         if (ahead && ix.files.size() <= 8) ahead->set_concurrency((unsigned)std::max<long>(2, a.threads / 2));
         if (cfg.region_report()) resolve_regions();
+        if (cfg.indels && ix.files.size() != 1)   // (a k-mer's cell in the engine's table is its first among all files, not the selected genome's)
+            die(T, "--indels needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
     }
     // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
     void resolve_regions() {
@@ -416,6 +425,10 @@ struct CallRun {
         set_seqs(cfg.adapters, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_adapters_set(e, q, l, n, cfg.adapter_min_overlap, cfg.adapter_error_rate), "bk_adapters_set"); });
         set_seqs(cfg.primers, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_primers_set(e, q, l, n, cfg.primer_mismatches), "bk_primers_set"); });
         if (!region_table.empty()) hip_check(bk_regions_set(e, region_table.data(), region_table.size()), "bk_regions_set");
+        if (cfg.indels) {
+            const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
+            hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
+        }
     }
     // text(sum): the line's start; stats(e, mate, out): the bk_*_stats call, n counters a mate file
     template <class Stats, class Text>
@@ -446,6 +459,10 @@ struct CallRun {
         const int n_mates = (int)mates.size();
         if (!finalized) hip_check(bk_sample_finalize(e, n_mates), "bk_sample_finalize");   // (a sharded sample: sharded_finalize has done it)
         if (!finalized) log_trim_stats(std::vector<bk_engine*>{e}, mates);
+        if (cfg.indels) {   // (needs the finalize only: the events that pass the thresholds, a few rows travel)
+            const bk_indel_params ip{cfg.indel.min_reads, cfg.indel.min_af_ppm};
+            hip_check(bk_sample_indels(e, &ip), "bk_sample_indels");
+        }
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
         if (a.consensus) hip_check(bk_sample_consensus(e, &cfg.consensus), "bk_sample_consensus");
@@ -486,6 +503,12 @@ struct CallRun {
             d.rrows.resize(max_file_regions);
             hip_check(bk_sample_download_region_depths(e, &d.rsumm, d.rrows.data(), d.rrows.size()), "bk_sample_download_region_depths");
             d.rrows.resize(std::min<size_t>(d.rrows.size(), d.rsumm.n_regions));
+        }
+        if (cfg.indels) {
+            static_assert(sizeof(IndelEvent) == sizeof(bk_indel_record), "IndelEvent is bk_indel_record");
+            hip_check(bk_sample_download_indels(e, &d.isumm, nullptr, 0), "bk_sample_download_indels");
+            d.indels.resize((size_t)d.isumm.reported);
+            hip_check(bk_sample_download_indels(e, &d.isumm, reinterpret_cast<bk_indel_record*>(d.indels.data()), d.indels.size()), "bk_sample_download_indels");
         }
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
@@ -538,6 +561,13 @@ struct CallRun {
                 std::vector<RegionDepth> rows;
                 for (const bk_region_depth& r : d.rrows) { RegionDepth o; o.sum = r.sum; o.min = r.min; o.max = r.max; o.median = r.median; o.covered = r.covered; rows.push_back(o); }
                 write_regions_tsv(a.output + "/" + stem + ".regions.tsv", ix, best, regions, rows.data(), rows.size(), cfg.region_min_depth);
+            }
+            if (cfg.indels) {       // (a sample without events: the header alone)
+                const bk_indel_summary& s = d.isumm;
+                LOG_INFO(T, "Indels: " + std::to_string(s.anchored) + " of " + std::to_string(s.records) + " records anchored, " + std::to_string(s.ref_spanning) +
+                                " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.candidates) + " candidate events, " +
+                                std::to_string(s.reported) + " reported");
+                write_indels_vcf(a.output + "/" + stem + ".indels.vcf", mates[0], ix, best, d.indels, cfg.indel);
             }
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }

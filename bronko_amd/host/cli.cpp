@@ -6,6 +6,7 @@
 // Reference: /root/reference/src/main.rs:14-29 (banner, dispatch, elapsed), src/cli.rs:29-166 (flags),
 // src/consts.rs (defaults), src/build.rs:62-120 (build + its checks), src/call.rs:30-136 (call checks).
 #include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <mutex>
 #include <cstdio>
@@ -71,7 +72,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--min-depth N] [--min-variant-depth N] [--noise-multiplier F] [-o <DIR>] [--pileup]\n"
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
-          "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [-t <THREADS>] [--debug]\n"
+          "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
+          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [-t <THREADS>] [--debug]\n"
           "            [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
@@ -94,7 +96,14 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    median, max and the positions with depth >= D; BED (plain or gzip): chrom, 0-based start, end, optional\n"
           "                    name, tab-separated, at most 65536 regions\n"
           "  --region-window W the same for windows of W positions that tile every sequence (not with --regions); at least 1\n"
-          "  --region-min-depth D     depth from which a position counts as covered; at least 1, default 10\n", stderr);
+          "  --region-min-depth D     depth from which a position counts as covered; at least 1, default 10\n"
+          "  --indels          write short insertions and deletions to <DIR>/<stem>.indels.vcf (an index of one genome file): reads whose\n"
+          "                    two ends lie on diagonals of the reference L or fewer apart, left-normalised, with the reads that\n"
+          "                    support each (SF, SR), the reads that span it without an indel (RS) and AF = support / (support + RS)\n"
+          "  --indel-max-len L        longest insertion or deletion looked for; 1..32, default 32\n"
+          "  --indel-max-mismatches M substitutions a read may have beside its indel; 0..8, default 2\n"
+          "  --indel-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
+          "  --indel-min-af F         AF an event needs to be written; 0..1, default the value of --min-af\n", stderr);
     exit(code);
 }
 
@@ -220,6 +229,18 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--region-window") { a.region_window = x; a.has_region_window = true; }
             else { a.region_min_depth = x; a.has_region_min_depth = true; }
         }
+        else if (opt == "--indels") a.indels = true;
+        else if (opt == "--indel-max-len" || opt == "--indel-max-mismatches" || opt == "--indel-min-reads") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--indel-max-len") { a.indel_max_len = x; a.has_indel_max_len = true; }
+            else if (opt == "--indel-max-mismatches") { a.indel_max_mismatches = x; a.has_indel_max_mismatches = true; }
+            else { a.indel_min_reads = x; a.has_indel_min_reads = true; }
+        }
+        else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
         else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
@@ -400,6 +421,18 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.has_regions && a.regions.empty()) die(T, "--regions needs a BED file");
     if (a.has_region_window && a.region_window < 1) die(T, "Region window must be at least 1, got " + std::to_string(a.region_window));
     if (a.region_min_depth < 1) die(T, "Region minimum depth must be at least 1, got " + std::to_string(a.region_min_depth));
+    if (a.has_indel_max_len && !a.indels) die(T, "--indel-max-len needs --indels");
+    if (a.has_indel_max_mismatches && !a.indels) die(T, "--indel-max-mismatches needs --indels");
+    if (a.has_indel_min_reads && !a.indels) die(T, "--indel-min-reads needs --indels");
+    if (a.has_indel_min_af && !a.indels) die(T, "--indel-min-af needs --indels");
+    if (a.indel_max_len < 1 || a.indel_max_len > BK_INDEL_MAX_LEN) die(T, "--indel-max-len must be between 1 and " + std::to_string(BK_INDEL_MAX_LEN) + ", got " + std::to_string(a.indel_max_len));
+    if (a.indel_max_mismatches < 0 || a.indel_max_mismatches > 8) die(T, "--indel-max-mismatches must be between 0 and 8, got " + std::to_string(a.indel_max_mismatches));
+    if (a.indel_min_reads < 1) die(T, "--indel-min-reads must be at least 1, got " + std::to_string(a.indel_min_reads));
+    if (a.has_indel_min_af && !(a.indel_min_af >= 0.0 && a.indel_min_af <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "--indel-min-af must be between 0 and 1, got %g", a.indel_min_af);
+        die(T, buf);
+    }
 }
 
 // the checked arguments -> what the readers and the per-sample code work from; the primer file and the regions file are read and the adapters are
@@ -434,6 +467,10 @@ CallConfig make_call_config(const Args& a) {
     }
     if (a.has_region_window) c.region_window = (uint64_t)a.region_window;
     c.region_min_depth = (uint64_t)a.region_min_depth;
+    c.indels = a.indels;
+    c.indel.max_len = (uint32_t)a.indel_max_len; c.indel.max_mismatches = (uint32_t)a.indel_max_mismatches;
+    c.indel.min_reads = (uint64_t)a.indel_min_reads;
+    c.indel.min_af_ppm = (uint32_t)llround((a.has_indel_min_af ? a.indel_min_af : a.min_af) * 1e6);
     return c;
 }
 

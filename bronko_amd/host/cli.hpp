@@ -9,6 +9,7 @@
 
 #include "../../include/bronko_hip.h"
 #include "caller.hpp"
+#include "indels.hpp"
 #include "index.hpp"
 
 namespace bronko {
@@ -59,6 +60,12 @@ struct Args {
     bool has_regions = false, has_region_window = false, has_region_min_depth = false;
     long region_window = 0;         // --region-window: tile every sequence with windows of this many positions instead
     long region_min_depth = 10;     // --region-min-depth: a position with at least this depth counts as covered
+    bool indels = false;            // --indels: <DIR>/<stem>.indels.vcf, short insertions and deletions from the reads
+    bool has_indel_max_len = false, has_indel_max_mismatches = false, has_indel_min_reads = false, has_indel_min_af = false;
+    long indel_max_len = 32;        // --indel-max-len: longest insertion or deletion looked for (1..32)
+    long indel_max_mismatches = 2;  // --indel-max-mismatches: substitutions a record may have beside its indel (0..8)
+    long indel_min_reads = 5;       // --indel-min-reads: supporting records an event needs
+    double indel_min_af = 0.03;     // --indel-min-af: support / (support + reference-spanning records) an event needs (default: --min-af)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -92,6 +99,9 @@ struct CallConfig {
     std::vector<BedLine> bed;
     uint64_t region_window = 0;
     uint64_t region_min_depth = 10;         // bk_sample_region_depths
+    // --indels: bk_indels_enable / bk_sample_indels and the values the .indels.vcf header prints
+    bool indels = false;
+    IndelParams indel;
     bool region_report() const { return !regions_path.empty() || region_window > 0; }
     // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
     bool trims() const { return !primers.empty() || !adapters.empty(); }

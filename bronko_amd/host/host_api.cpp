@@ -1,6 +1,7 @@
 // host_api.cpp -- flat C entry points over the C++ host code (index build / .bkdb codec) so that the Python
 // test + bench harness can drive the same code the `bronko` binary runs.  Not the drop-in boundary (that is
 // include/bronko_hip.h); errors are returned as NULL / non-zero with bh_last_error().
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "caller.hpp"
+#include "indels.hpp"
 #include "index.hpp"
 
 namespace {
@@ -215,6 +217,41 @@ int bh_write_regions_tsv(const void* h, int file_id, const char* path, const uin
 int bh_write_kmer_counts(const char* path, int k, const uint64_t* kmers, const uint64_t* counts, uint64_t n, int threads) {
     try { bronko::write_kmer_counts(path, k, kmers, counts, n, threads); return 0; }
     catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --indels: the host twin of the engine's indel pass (indels.cpp) -------------------------------------------------
+// reads joined by '\n'; rows as bk_indel_record (= bronko::IndelEvent), at most cap written, *n their number; span: NULL or
+// [total_cells], prefix-summed; counters = {records, anchored, ref_spanning, supporting, discordant}
+int bh_indel_events(const void* h, int file_id, const char* reads, int max_len, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span,
+                    uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::IndelEvent) == 32, "IndelEvent is bk_indel_record");
+        std::vector<std::string> rd;
+        for (const char* at = reads; at && *at;) {
+            const char* nl = strchr(at, '\n');
+            rd.emplace_back(nl ? std::string(at, nl) : std::string(at));
+            at = nl ? nl + 1 : nullptr;
+        }
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const bronko::IndelResult r = bronko::indel_events(*ix, file_id, rd, max_len, max_mismatches);
+        *n = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::IndelEvent));
+        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+        if (counters) { counters[0] = r.n.records; counters[1] = r.n.anchored; counters[2] = r.n.ref_spanning; counters[3] = r.n.supporting; counters[4] = r.n.discordant; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_indels_vcf(const void* h, int file_id, const char* path, const char* reads_path, const void* rows, uint64_t n, uint32_t max_len,
+                        uint32_t max_mismatches, uint64_t min_reads, uint32_t min_af_ppm) {
+    try {
+        const auto* ev = static_cast<const bronko::IndelEvent*>(rows);
+        bronko::IndelParams p;
+        p.max_len = max_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_af_ppm = min_af_ppm;
+        bronko::write_indels_vcf(path, reads_path ? reads_path : "", *static_cast<const bronko::Index*>(h), file_id,
+                                 std::vector<bronko::IndelEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
 void bh_clean_sample_id(const char* path, char* buf, size_t n) {

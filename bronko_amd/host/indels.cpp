@@ -1,0 +1,238 @@
+// indels.cpp -- the host twin of bk_indels.hip and the .indels.vcf writer (indels.hpp).
+#include "indels.hpp"
+
+#include <algorithm>
+#include <cctype>
+#include <cstdio>
+#include <map>
+#include <stdexcept>
+#include <tuple>
+
+#include "lcb.hpp"
+
+namespace bronko {
+
+namespace {
+
+// One genome file as the rule sees it: its letters upper-cased, where its sequences start, its anchor k-mers
+struct IndelGenome {
+    int k = 0;
+    int64_t cell0 = 0;                               // first cell of the file among all cells of the index
+    std::string text;                                // the file's cells (upper-cased FASTA letters)
+    std::vector<int64_t> first;                      // first cell of each sequence, relative to cell0; one more entry: the end
+    struct Anchor { uint64_t kmer; uint32_t cell; bool rc; };
+    std::vector<Anchor> anchors;                     // canonical k-mers that start at exactly one cell, sorted
+
+    IndelGenome(const Index& ix, int file) : k(ix.k) {
+        if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("indel_events: no such genome file");
+        for (int f = 0; f < file; f++) cell0 += (int64_t)ix.genome_len((size_t)f);
+        std::vector<Anchor> all;
+        for (const SeqMeta& s : ix.files[(size_t)file].sequences) {
+            const int64_t c0 = (int64_t)text.size();
+            first.push_back(c0);
+            for (uint8_t c : s.seq) text.push_back((char)(c >= 'a' && c <= 'z' ? c - 32 : c));
+            // the genome's k-mers as the index reads them: every letter that is not ACGT stands for A (nt_to_bits)
+            for (uint64_t i = 0; i + (uint64_t)k <= s.seq.size(); i++) {
+                const Canon cn = canonical_kmer(s.seq.data() + i, k);
+                all.push_back(Anchor{cn.kmer, (uint32_t)(c0 + (int64_t)i), cn.rc});
+            }
+        }
+        first.push_back((int64_t)text.size());
+        std::sort(all.begin(), all.end(), [](const Anchor& x, const Anchor& y) { return x.kmer < y.kmer; });
+        for (size_t i = 0; i < all.size();) {
+            size_t j = i + 1;
+            while (j < all.size() && all[j].kmer == all[i].kmer) j++;
+            if (j == i + 1) anchors.push_back(all[i]);
+            i = j;
+        }
+    }
+    bool anchor(const char* kmer, uint32_t* cell, bool* against) const {
+        const Canon cn = canonical_kmer(reinterpret_cast<const uint8_t*>(kmer), k);
+        const auto it = std::lower_bound(anchors.begin(), anchors.end(), cn.kmer, [](const Anchor& a, uint64_t v) { return a.kmer < v; });
+        if (it == anchors.end() || it->kmer != cn.kmer) return false;
+        *cell = it->cell; *against = cn.rc != it->rc;
+        return true;
+    }
+    int seq_of(int64_t cell) const {
+        int s = 0;
+        while (s + 2 < (int)first.size() && first[(size_t)s + 1] <= cell) s++;
+        return s;
+    }
+};
+
+bool is_acgt(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
+char comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; }
+
+struct Tables {
+    std::map<std::tuple<uint32_t, int, int, uint64_t>, std::pair<uint32_t, uint32_t>> events;   // (cell, kind, length, seq) -> fwd, rev
+    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    IndelCounters n;
+};
+
+void add_record(const IndelGenome& g, const std::string& rec, int L, int M, Tables& t) {
+    const int k = g.k, n = (int)rec.size();
+    t.n.records++;
+    if (n < 2 * k) return;
+    int f_off = -1, b_off = -1;
+    uint32_t f_cell = 0, b_cell = 0;
+    bool f_ag = false, b_ag = false;
+    for (int o = 0; o <= 24 && o + k <= n; o += 8)
+        if (g.anchor(rec.data() + o, &f_cell, &f_ag)) { f_off = o; break; }
+    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
+        if (g.anchor(rec.data() + o, &b_cell, &b_ag)) { b_off = o; break; }
+    if (f_off < 0 || b_off < 0 || f_ag != b_ag) return;
+    const bool against = f_ag;
+    std::string r = rec;                             // r': the record along the reference
+    int64_t a, b, ca, cb;
+    if (against) {
+        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
+        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
+    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
+    if (a + k > b) return;
+    t.n.anchored++;
+    const int64_t dL = ca - a, dR = cb - b, delta = dR - dL;
+    if (delta > L || -delta > L) { t.n.discordant++; return; }
+    const int s = g.seq_of(ca);
+    if (g.seq_of(cb) != s) return;
+    const int64_t lo = std::min(dL, dR), hi = std::max(dL, dR) + n;
+    if (lo < g.first[(size_t)s] || hi > g.first[(size_t)s + 1]) return;
+    const std::string& ref = g.text;
+    for (int64_t c = lo; c < hi; c++) if (!is_acgt(ref[(size_t)c])) return;
+    auto mm = [&](int64_t j, int64_t d) { return r[(size_t)j] != ref[(size_t)(d + j)] ? 1 : 0; };
+    auto floor_of = [&](int64_t pos) {               // first cell of the stretch of ACGT letters of the sequence that holds pos - 1
+        int64_t f = pos - 1;
+        while (f - 1 >= g.first[(size_t)s] && is_acgt(ref[(size_t)(f - 1)])) f--;
+        return f;
+    };
+    if (delta == 0) {
+        int m = 0;
+        for (int64_t j = 0; j < n; j++) m += mm(j, dL);
+        if (m > M) { t.n.discordant++; return; }
+        t.n.ref_spanning++;
+        t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
+        return;
+    }
+    const int64_t I = delta < 0 ? -delta : 0, D = delta > 0 ? delta : 0;
+    const int64_t p0 = a + k, p1 = b - I;            // the breakpoint's range
+    if (p0 > p1) { t.n.discordant++; return; }
+    // m(p0), then one comparison exchanged per step
+    int64_t m = 0;
+    for (int64_t j = 0; j < p0; j++) m += mm(j, dL);
+    for (int64_t j = p0 + I; j < n; j++) m += mm(j, dR);
+    int64_t best = m, best_p = p0;
+    for (int64_t p = p0; p < p1; p++) {
+        m += mm(p, dL) - mm(p + I, dR);
+        if (m < best) { best = m; best_p = p + 1; }
+    }
+    if (best > M) { t.n.discordant++; return; }
+    int64_t pos = dL + best_p;
+    const int64_t F = floor_of(pos);
+    uint64_t seq = 0;
+    if (D) {
+        while (pos - 1 > F && ref[(size_t)(pos - 1)] == ref[(size_t)(pos + D - 1)]) pos--;
+    } else {
+        std::string S = r.substr((size_t)best_p, (size_t)I);
+        while (pos - 1 > F && ref[(size_t)(pos - 1)] == S.back()) { S.insert(S.begin(), S.back()); S.pop_back(); pos--; }
+        for (size_t i = 0; i < S.size(); i++) seq |= (uint64_t)nt_to_bits((uint8_t)S[i]) << (2 * i);
+    }
+    t.n.supporting++;
+    auto& e = t.events[std::make_tuple((uint32_t)(g.cell0 + pos), D ? 0 : 1, (int)(D ? D : I), seq)];
+    (against ? e.second : e.first)++;
+}
+
+}  // namespace
+
+bool indel_event_less(const IndelEvent& x, const IndelEvent& y) {
+    const int kx = x.len < 0, ky = y.len < 0;
+    const int32_t lx = x.len < 0 ? -x.len : x.len, ly = y.len < 0 ? -y.len : y.len;
+    return std::tie(x.cell, kx, lx, x.seq) < std::tie(y.cell, ky, ly, y.seq);
+}
+
+IndelResult indel_events(const Index& ix, int file, const std::vector<std::string>& reads, int max_len, int max_mismatches) {
+    if (max_len < 1 || max_len > kIndelMaxLen) throw std::runtime_error("indel_events: max_len must be 1..32");
+    if (max_mismatches < 0 || max_mismatches > kIndelMaxMismatches) throw std::runtime_error("indel_events: max_mismatches must be 0..8");
+    const IndelGenome g(ix, file);
+    Tables t;
+    t.span.assign(g.text.size() + 2, 0);
+    std::string run;
+    for (const std::string& read : reads) {
+        run.clear();
+        for (size_t i = 0; i <= read.size(); i++) {
+            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
+            if (is_acgt(c)) { run.push_back(c); continue; }
+            if ((int)run.size() >= g.k) add_record(g, run, max_len, max_mismatches, t);
+            run.clear();
+        }
+    }
+    IndelResult out;
+    out.n = t.n;
+    out.span.assign((size_t)ix.total_cells(), 0u);
+    int64_t acc = 0;
+    std::vector<uint32_t> sums(g.text.size());
+    for (size_t c = 0; c < g.text.size(); c++) { acc += t.span[c]; sums[c] = (uint32_t)acc; out.span[(size_t)g.cell0 + c] = (uint32_t)acc; }
+    for (const auto& kv : t.events) {
+        IndelEvent e;
+        e.cell = std::get<0>(kv.first);
+        e.len = std::get<1>(kv.first) == 0 ? std::get<2>(kv.first) : -std::get<2>(kv.first);
+        e.seq = std::get<3>(kv.first);
+        e.fwd = kv.second.first; e.rev = kv.second.second;
+        e.ref_span = sums[(size_t)(e.cell - g.cell0)];
+        out.events.push_back(e);
+    }
+    std::sort(out.events.begin(), out.events.end(), indel_event_less);
+    return out;
+}
+
+bool indel_reported(const IndelEvent& e, uint64_t min_reads, uint32_t min_af_ppm) {
+    const uint64_t support = (uint64_t)e.fwd + e.rev;
+    return support >= min_reads && support * 1000000ull >= (uint64_t)min_af_ppm * (support + e.ref_span);
+}
+
+void write_indels_vcf(const std::string& out_path, const std::string& reads_path, const Index& ix, int file, std::vector<IndelEvent> events,
+                      const IndelParams& p) {
+    if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("write_indels_vcf: no such genome file");
+    FILE* fp = fopen(out_path.c_str(), "w");
+    if (!fp) throw std::runtime_error("Failed to create indel vcf output file " + out_path);
+    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const FileMeta& fm = ix.files[(size_t)file];
+    auto chrom = [](const std::string& name) {       // the CHROM token as write_vcf prints it
+        size_t a = 0;
+        while (a < name.size() && isspace((unsigned char)name[a])) a++;
+        size_t b = a;
+        while (b < name.size() && !isspace((unsigned char)name[b])) b++;
+        return name.substr(a, b - a);
+    };
+    fprintf(fp, "##fileformat=VCFv4.5\n##source=bronko-v0.1.0\n##reference=file://%s\n", reads_path.c_str());
+    for (const auto& s : fm.sequences) fprintf(fp, "##contig=<ID=%s,length=%llu>\n", chrom(s.name).c_str(), (unsigned long long)s.len);
+    fputs("##INFO=<ID=TYPE,Number=1,Type=String,Description=\"DEL or INS\">\n"
+          "##INFO=<ID=LEN,Number=1,Type=Integer,Description=\"Bases deleted or inserted\">\n"
+          "##INFO=<ID=SF,Number=1,Type=Integer,Description=\"Supporting records along the reference\">\n"
+          "##INFO=<ID=SR,Number=1,Type=Integer,Description=\"Supporting records against the reference\">\n"
+          "##INFO=<ID=RS,Number=1,Type=Integer,Description=\"Records that span the site without an indel\">\n"
+          "##INFO=<ID=AF,Number=1,Type=Float,Description=\"(SF + SR) / (SF + SR + RS)\">\n", fp);
+    fprintf(fp, "##indel_max_len=%u\n##indel_max_mismatches=%u\n##indel_min_reads=%llu\n##indel_min_af=%u.%06u\n", p.max_len, p.max_mismatches,
+            (unsigned long long)p.min_reads, p.min_af_ppm / 1000000u, p.min_af_ppm % 1000000u);
+    fputs("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", fp);
+    uint64_t cell0 = 0;
+    for (int f = 0; f < file; f++) cell0 += ix.genome_len((size_t)f);
+    std::sort(events.begin(), events.end(), indel_event_less);
+    for (const IndelEvent& e : events) {
+        uint64_t at = cell0;
+        const SeqMeta* sm = nullptr;
+        for (const auto& s : fm.sequences) { if (e.cell >= at && e.cell < at + s.len) { sm = &s; break; } at += s.len; }
+        const uint64_t len = (uint64_t)(e.len < 0 ? -e.len : e.len);
+        if (!sm || e.cell == at || (e.len > 0 && e.cell + len > at + sm->len)) throw std::runtime_error("write_indels_vcf: an event outside the genome file's sequences");
+        auto up = [](uint8_t c) { return (char)(c >= 'a' && c <= 'z' ? c - 32 : c); };
+        const uint64_t i = e.cell - at;              // offset in the sequence; the base before the event is i - 1, 1-based position i
+        std::string ref_a(1, up(sm->seq[i - 1])), alt_a(ref_a);
+        if (e.len > 0) for (uint64_t j = 0; j < len; j++) ref_a.push_back(up(sm->seq[i + j]));
+        else for (uint64_t j = 0; j < len; j++) alt_a.push_back("ACGT"[(e.seq >> (2 * j)) & 3u]);
+        const uint64_t support = (uint64_t)e.fwd + e.rev, t = 10000ull * support / std::max<uint64_t>(1, support + e.ref_span);
+        fprintf(fp, "%s\t%llu\t.\t%s\t%s\t.\tPASS\tTYPE=%s;LEN=%llu;SF=%u;SR=%u;RS=%u;AF=%llu.%04llu\n", chrom(sm->name).c_str(), (unsigned long long)i,
+                ref_a.c_str(), alt_a.c_str(), e.len > 0 ? "DEL" : "INS", (unsigned long long)len, e.fwd, e.rev, e.ref_span,
+                (unsigned long long)(t / 10000), (unsigned long long)(t % 10000));
+    }
+    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write indel vcf file " + out_path);
+}
+
+}  // namespace bronko

@@ -294,3 +294,54 @@ def write_regions_tsv(path, ix, file_id, regions, rows, min_depth):
     L = _caller_lib()
     if L.bh_write_regions_tsv(ix.h, file_id, path.encode(), regs.ctypes.data, names, len(regions), rw.ctypes.data, len(rows), int(min_depth)) != 0:
         raise _host_error(L)
+
+
+# bk_indel_record (include/bronko_hip.h) == bronko::IndelEvent (indels.hpp)
+INDEL_DTYPE = np.dtype([("cell", np.uint32), ("len", np.int32), ("fwd", np.uint32), ("rev", np.uint32), ("ref_span", np.uint32),
+                        ("pad", np.uint32), ("seq", np.uint64)])
+
+
+def _indel_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_indels_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_indel_events.restype = C.c_int
+        L.bh_indel_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
+        L.bh_write_indels_vcf.restype = C.c_int
+        L.bh_write_indels_vcf.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, vp, u64, u32, u32, u64, u32]
+        L._indels_ready = True
+    return L
+
+
+def indel_rows(rec):
+    """A structured array of bk_indel_record as [(cell, len, fwd, rev, ref_span, seq)] sorted by (cell, kind, length, seq)."""
+    rows = [(int(r["cell"]), int(r["len"]), int(r["fwd"]), int(r["rev"]), int(r["ref_span"]), int(r["seq"])) for r in rec]
+    rows.sort(key=lambda r: (r[0], 1 if r[1] < 0 else 0, abs(r[1]), r[5]))
+    return rows
+
+
+def indel_events(ix, file_id, reads, max_len=32, max_mismatches=2):
+    """The host twin of the engine's indel pass (indels.cpp indel_events) over ASCII reads: (rows of the whole table as indel_rows
+    gives them, the prefix-summed span array of all cells, (records, anchored, ref_spanning, supporting, discordant))."""
+    L = _indel_lib()
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    span = np.zeros(max(1, ix.total_cells), np.uint32)
+    counters = np.zeros(5, np.uint64)
+    if L.bh_indel_events(ix.h, file_id, joined, int(max_len), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
+        raise _host_error(L)
+    rec = np.zeros(max(1, n.value), INDEL_DTYPE)
+    if L.bh_indel_events(ix.h, file_id, joined, int(max_len), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
+        raise _host_error(L)
+    return indel_rows(rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+
+
+def write_indels_vcf(path, ix, file_id, reads_path, rows, max_len=32, max_mismatches=2, min_reads=5, min_af_ppm=30000):
+    """The --indels writer (indels.cpp write_indels_vcf): rows as indel_rows gives them, already filtered."""
+    rec = np.zeros(max(1, len(rows)), INDEL_DTYPE)
+    for i, r in enumerate(rows):
+        rec[i] = (r[0], r[1], r[2], r[3], r[4], 0, r[5])
+    L = _indel_lib()
+    if L.bh_write_indels_vcf(ix.h, file_id, path.encode(), reads_path.encode(), rec.ctypes.data, len(rows), int(max_len), int(max_mismatches), int(min_reads),
+                             int(min_af_ppm)) != 0:
+        raise _host_error(L)

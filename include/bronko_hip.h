@@ -437,6 +437,69 @@ int  bk_regions_set(bk_engine* e, const bk_region* regions, uint64_t n);
 int  bk_sample_region_depths(bk_engine* e, uint64_t min_depth);
 int  bk_sample_download_region_depths(bk_engine* e, bk_region_summary* summary, bk_region_depth* out, uint64_t cap);
 
+/* ---- short insertions and deletions from the reads (`bronko call --indels`; additive, still v8) ----------------------------
+ * A k-mer that spans an indel is no reference k-mer and no neighbour of one: the pileup only sags there.  A read with one indel
+ * follows the reference on one diagonal up to the breakpoint and on another behind it; the difference of the two diagonals is
+ * the indel's signed length.  A pass of its own over each batch's records (indel_scan_kernel, behind the scan of the same
+ * records) finds the two diagonals from anchor k-mers.  The rule, all of it integer arithmetic:
+ *   unit       a record: a run of at least k valid letters as the packers make it, after the trimming stage -- what the scan
+ *              reads; a run that the trimming leaves with fewer than k letters is no record and is not counted.  n = its
+ *              length; a record of n < 2k is counted in `records` and otherwise ignored.  The index has exactly one genome file (any number of sequences).
+ *   anchor k-mer  a k-mer whose canonical form is a reference k-mer (id < n_full) that starts at exactly one cell of the genome,
+ *              counting both strands, the genome's k-mers read as the index reads them (a letter that is not ACGT stands for A).
+ *              It gives that cell and a strand: against the reference iff the read's k-mer and the cell's k-mer differ in whether
+ *              they were reverse-complemented to become canonical.
+ *   anchors    from the record's first base the k-mers at offsets 0, 8, 16, 24 are tried in that order (while offset + k <= n),
+ *              from its last base the offsets n - k, n - k - 8, n - k - 16, n - k - 24 (while >= 0); the first anchor k-mer from
+ *              each end is that end's anchor.  Both must exist and agree on the strand.  r' = the record oriented along the
+ *              reference (its reverse complement if the strand says so); a < b the anchors' offsets in r', c_a, c_b their cells.
+ *              a + k <= b, else the record is ignored.  Such a record is `anchored`.
+ *              dL = c_a - a, dR = c_b - b, delta = dR - dL.  Ignored: |delta| > max_len (counted `discordant`); the two anchors
+ *              in different sequences; the cells [min(dL, dR), max(dL, dR) + n) leave that sequence or hold a letter that is
+ *              not ACGT (these three are not counted).
+ *   delta = 0  m = Hamming(r', ref[dL, dL + n)).  m <= max_mismatches: the record is `ref_spanning` for the sites dL + a + k ..
+ *              dL + b: +1 at cell dL + a + k, -1 at cell dL + b + 1 of the per-cell difference array `span`.  Else `discordant`.
+ *   delta > 0  a deletion of D = delta.  For p in [a + k, b]: m(p) = #{j < p: r'[j] != ref[dL + j]} + #{j >= p: r'[j] !=
+ *              ref[dR + j]}; the smallest p that minimises m(p); m(p) > max_mismatches: `discordant`.  pos = dL + p.  F = the
+ *              first cell of the stretch of ACGT letters of the sequence that holds pos - 1.  While pos - 1 > F and ref[pos - 1]
+ *              = ref[pos + D - 1]: pos -= 1.  Event (pos, deletion, D).
+ *   delta < 0  an insertion of I = -delta.  a + k <= b - I, else `discordant`.  For p in [a + k, b - I]: m(p) = #{j < p: r'[j] !=
+ *              ref[dL + j]} + #{j >= p + I: r'[j] != ref[dR + j]}; smallest minimising p, `discordant` as above.  S = r'[p, p + I),
+ *              pos = dL + p, F as above.  While pos - 1 > F and ref[pos - 1] = the last base of S: rotate S right by one,
+ *              pos -= 1.  Event (pos, insertion, I, S); insertions at one place with different S are different events.
+ *   per event  `supporting` records per strand: fwd along the reference, rev against it.  Both mate files add into one table and
+ *              one span array.  ref_span = the prefix sum of span at pos; support = fwd + rev.  Reported iff support >= min_reads
+ *              and support * 1000000 >= min_af_ppm * (support + ref_span), in u64.
+ *   AF         printed from integers: t = 10000 * support / (support + ref_span), as t / 10000, ".", four digits of t % 10000.
+ *   bk_indels_enable           between samples (BK_ERR_STATE inside one); NULL disables and frees.  max_len 1..BK_INDEL_MAX_LEN,
+ *                              max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window (BK_ERR_INVALID
+ *                              otherwise).  The genome has k to 2^27 - 1 positions: only then does the engine hold the
+ *                              reverse-complemented reference that reads against the reference are compared with
+ *                              (BK_ERR_UNSUPPORTED otherwise, the message says so).  Allocates all the feature needs (the event table of 2^table_log2 slots, as many rows,
+ *                              span, one bit per reference k-mer: it starts at one cell) -- a sample allocates nothing; an engine
+ *                              that never enables it allocates and launches nothing.  Per engine: forks set their own.  A sample
+ *                              that began before the call has no events.
+ *   bk_sample_indels           after the sample's bk_sample_finalize (bk_sample_call is not needed): BK_ERR_STATE inside a sample,
+ *                              before any finalize, and when the feature was not enabled as the sample began; BK_ERR_INVALID for
+ *                              min_reads == 0 or min_af_ppm > 1000000.  Prefix-sums span, selects the rows; asynchronous on the
+ *                              engine's stream; may be repeated with other parameters.
+ *   bk_sample_download_indels  synchronises; copies min(cap, reported) rows in no particular order (records may be NULL).
+ *                              `candidates` = the distinct events of the sample.  A table that met more of them than it holds
+ *                              loses nothing silently: overflow = 1 in the summary and BK_ERR_INVALID ("more than 2^n distinct
+ *                              candidate events").
+ *   bk_sample_download_indel_span  the prefix-summed span array of all cells (cap >= bk_total_cells, BK_ERR_INVALID otherwise).
+ * bk_indel_record: cell = pos; len > 0 a deletion of len, < 0 an insertion of -len; seq = S, its base t at bits [2t, 2t + 2),
+ * A C G T = 0 1 2 3 (0 for a deletion). */
+#define BK_INDEL_MAX_LEN 32
+typedef struct { uint32_t max_len, max_mismatches, table_log2; } bk_indel_config;   /* table_log2 10..24 */
+typedef struct { uint64_t min_reads; uint32_t min_af_ppm; } bk_indel_params;
+typedef struct { uint32_t cell; int32_t len; uint32_t fwd, rev, ref_span, pad; uint64_t seq; } bk_indel_record;
+typedef struct { uint64_t records, anchored, ref_spanning, supporting, discordant, candidates, reported; int32_t overflow; } bk_indel_summary;
+int  bk_indels_enable(bk_engine* e, const bk_indel_config* cfg);
+int  bk_sample_indels(bk_engine* e, const bk_indel_params* p);
+int  bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap);
+int  bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
