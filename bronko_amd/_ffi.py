@@ -75,6 +75,15 @@ class IndelSummary(C.Structure):  # bk_indel_summary
                 ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class LinkConfig(C.Structure):  # bk_link_config
+    _fields_ = [("max_mismatches", C.c_uint32), ("initial_rows", C.c_uint64)]
+
+
+class LinkSummary(C.Structure):  # bk_link_summary
+    _fields_ = [("records", C.c_uint64), ("placed", C.c_uint64), ("unplaced", C.c_uint64), ("discordant", C.c_uint64), ("n_pairs", C.c_uint64),
+                ("n_sites", C.c_uint32), ("max_dist", C.c_uint32)]
+
+
 class RegionSummary(C.Structure):  # bk_region_summary
     _fields_ = [("file_id", C.c_int32), ("n_regions", C.c_uint32), ("full", C.c_uint64), ("partial", C.c_uint64), ("empty", C.c_uint64)]
 
@@ -97,6 +106,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
+           "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -232,6 +242,14 @@ def load(testing=None):
     L.bk_sample_download_indels.argtypes = [vp, C.POINTER(IndelSummary), vp, u64]
     L.bk_sample_download_indel_span.restype = C.c_int
     L.bk_sample_download_indel_span.argtypes = [vp, vp, u64]
+    L.bk_link_enable.restype = C.c_int
+    L.bk_link_enable.argtypes = [vp, C.POINTER(LinkConfig)]
+    L.bk_sample_linkage.restype = C.c_int
+    L.bk_sample_linkage.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.bk_sample_download_linkage.restype = C.c_int
+    L.bk_sample_download_linkage.argtypes = [vp, C.POINTER(LinkSummary), vp, u64]
+    L.bk_sample_download_link_rows.restype = C.c_int
+    L.bk_sample_download_link_rows.argtypes = [vp, vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

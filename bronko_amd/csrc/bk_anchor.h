@@ -1,0 +1,129 @@
+// bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip) and link_scan_kernel
+// (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+//
+// Every function is a template over the kernel's argument struct (IndelArgs, LinkArgs of bk_kernels.h); it reads the members both
+// have under the same names: the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb, log2p, n_full), one bit per id
+// that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the runs of letters that are
+// not ACGT (nruns, n_nruns) -- the engine's AnchorTables hold the last three.  Device code only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "bk_scan_common.h"
+
+namespace bk {
+
+__device__ __forceinline__ uint32_t sym_at(const uint32_t* __restrict__ w, uint32_t i) { return (w[i >> 4] >> (2u * (i & 15u))) & 3u; }
+// sixteen symbols from symbol `pos` on; word indices are clamped to last_word (a record's last word; ~0u for the references, which
+// are padded behind).  symbols_at / read_symbols_at of bk_scan_common.h cut the same window 32 symbols wide from three words; a step
+// here is sixteen bases, which two words hold, and the record's clamp and the references' lack of one share this one function.
+__device__ __forceinline__ uint32_t sym16_at(const uint32_t* __restrict__ w, uint32_t pos, uint32_t last_word) {
+    const uint32_t wi = pos >> 4;
+    return __builtin_amdgcn_alignbit(w[min(wi + 1u, last_word)], w[min(wi, last_word)], 2u * (pos & 15u));
+}
+// one bit (the low one of its pair) per base of [i, min(i + 16, hi)) at which record[i ..] and text[diag + i ..] differ
+__device__ __forceinline__ uint32_t mismatch_bits16(const uint32_t* __restrict__ w, uint32_t last_word, uint32_t i, uint32_t hi,
+                                                    const uint32_t* __restrict__ text, int64_t diag) {
+    uint32_t x = sym16_at(w, i, last_word) ^ sym16_at(text, (uint32_t)(diag + (int64_t)i), ~0u);
+    x = (x | (x >> 1)) & 0x55555555u;
+    const uint32_t c = hi - i;
+    if (c < 16u) x &= (1u << (2u * c)) - 1u;
+    return x;
+}
+// #{i in [lo, hi): record[i] != text[diag + i]}; gives up above `stop` (what it returns is then only known to be larger)
+__device__ __forceinline__ uint32_t mismatches(const uint32_t* __restrict__ w, uint32_t last_word, uint32_t lo, uint32_t hi,
+                                               const uint32_t* __restrict__ text, int64_t diag, uint32_t stop) {
+    uint32_t m = 0;
+    for (uint32_t i = lo; i < hi && m <= stop; i += 16u) m += (uint32_t)__popc(mismatch_bits16(w, last_word, i, hi, text, diag));
+    return m;
+}
+
+// the k-mer at offset o of a record as an anchor: its cell and strand.  o + k <= the record's length.
+template <class Args>
+__device__ __forceinline__ bool anchor_at(const Args& a, const uint32_t* __restrict__ w, uint32_t o, uint32_t* cell, bool* against) {
+    const uint32_t k = (uint32_t)a.k;
+    const uint32_t w0 = o >> 4, sh = 2u * (o & 15u), wl = (o + k - 1u) >> 4;
+    unsigned long long x = w[w0];
+    if (wl > w0) x |= (unsigned long long)w[w0 + 1] << 32;
+    x >>= sh;
+    if (wl > w0 + 1) x |= (unsigned long long)w[w0 + 2] << (64u - sh);   // (sh > 0 here, as in kmer_dump_count_kernel)
+    const unsigned long long kmask = (1ull << (2u * k)) - 1ull;
+    const unsigned long long fwd = rev2_64(x) >> (64u - 2u * k);          // base o leads (kmer_to_u64)
+    const unsigned long long rc = ~x & kmask;                             // its reverse complement: the complements, base o last
+    const bool read_rc = !(fwd < rc);
+    const unsigned long long canon = read_rc ? rc : fwd;
+    const uint32_t pilot = a.pilots[phf_bucket(canon, a.log2nb)];
+    const KmerPos kp = a.kmer_pos[phf_pos(canon, pilot, a.m, a.log2nb, a.log2p)];
+    if (kp.key != canon) return false;
+    const uint32_t id = kp.idflags & kIdMask;
+    if (id >= a.n_full || !((a.unique_bits[id >> 5] >> (id & 31u)) & 1u)) return false;
+    *cell = kp.refcell;
+    *against = read_rc != ((kp.idflags >> 31) != 0u);
+    return true;
+}
+
+template <class Args>
+__device__ __forceinline__ uint32_t seq_of(const Args& a, uint32_t cell) {
+    uint32_t lo = 0, hi = a.n_seqs;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.seq_lo[mid] <= cell) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the first of the runs of letters that are not ACGT (ascending, disjoint) that ends behind cell `lo`; n_nruns: none does
+template <class Args>
+__device__ __forceinline__ uint32_t first_run_behind(const Args& a, int32_t lo) {
+    uint32_t b = 0, e = a.n_nruns;
+    while (b < e) {
+        const uint32_t mid = (b + e) >> 1;
+        if ((int32_t)a.nruns[mid].y > lo) e = mid; else b = mid + 1u;
+    }
+    return b;
+}
+
+// A record's two anchors, oriented along the reference
+struct Anchors {
+    bool against;          // the record reads against the reference
+    int32_t pa, pb;        // the anchors' offsets a < b in r'
+    uint32_t ca, cb;       // their cells
+};
+// the first anchor k-mer from each end of a record of n >= 2k bases (offsets 0, 8, 16, 24 from either end), both on one strand,
+// a + k <= b
+template <class Args>
+__device__ __forceinline__ bool anchors_of(const Args& a, const uint32_t* __restrict__ w, int32_t n, Anchors& out) {
+    const int32_t k = a.k;
+    int32_t f_off = -1, b_off = -1;
+    uint32_t f_cell = 0, b_cell = 0;
+    bool f_ag = false, b_ag = false;
+    for (int32_t o = 0; o <= 24 && o + k <= n; o += 8)
+        if (anchor_at(a, w, (uint32_t)o, &f_cell, &f_ag)) { f_off = o; break; }
+    if (f_off < 0) return false;
+    for (int32_t o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
+        if (anchor_at(a, w, (uint32_t)o, &b_cell, &b_ag)) { b_off = o; break; }
+    if (b_off < 0 || f_ag != b_ag) return false;
+    out.against = f_ag;
+    out.pa = f_ag ? n - k - b_off : f_off; out.pb = f_ag ? n - k - f_off : b_off;   // offsets in r'
+    out.ca = f_ag ? b_cell : f_cell; out.cb = f_ag ? f_cell : b_cell;
+    return out.pa + k <= out.pb;
+}
+// both anchors in one sequence, the cells [lo, hi) inside it and holding ACGT only
+template <class Args>
+__device__ __forceinline__ bool cells_placed(const Args& a, uint32_t ca, uint32_t cb, int32_t lo, int32_t hi) {
+    const uint32_t s = seq_of(a, ca);
+    if (seq_of(a, cb) != s) return false;
+    if (lo < (int32_t)a.seq_lo[s] || hi > (int32_t)a.seq_lo[s + 1]) return false;
+    if (a.n_nruns) {
+        const uint32_t i = first_run_behind(a, lo);
+        if (i < a.n_nruns && (int32_t)a.nruns[i].x < hi) return false;
+    }
+    return true;
+}
+
+__device__ __forceinline__ uint32_t wave_total(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
+    return v;
+}
+
+}  // namespace bk

@@ -257,6 +257,20 @@ static int clear_table(bk_engine* e, GrowTable& t) {
     return BK_OK;
 }
 
+// the row stores that bk_link_enable's sample outgrew: each is freed once the stream has passed the copy out of it (`wait`: now)
+static int link_free_old(Linkage& d, bool wait) {
+    std::vector<std::pair<uint4*, Event>> keep;
+    hipError_t err = hipSuccess;
+    for (auto& o : d.old) {
+        if (wait && err == hipSuccess) err = hipEventSynchronize(o.second);
+        if (err == hipSuccess && (wait || hipEventQuery(o.second) == hipSuccess)) (void)hipFree(o.first);
+        else keep.emplace_back(o.first, std::move(o.second));
+    }
+    d.old.swap(keep);
+    BK_HIP(err);
+    return BK_OK;
+}
+
 int bk_sample_begin(bk_engine* e) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     BK_HIP(hipSetDevice(e->device));
@@ -282,6 +296,12 @@ int bk_sample_begin(bk_engine* e) {
         BK_HIP(hipMemsetAsync(d.span.p, 0, d.span.n * sizeof(unsigned int), e->stream));
         BK_HIP(hipMemsetAsync(d.tallies.p, 0, d.tallies.n * sizeof(unsigned long long), e->stream));
         d.in_sample = true; d.summed = false; d.made = false;
+    }
+    if (e->linkage) {  // an empty row store, zero tallies
+        Linkage& d = *e->linkage;
+        if (int rc = link_free_old(d, true)) return rc;
+        BK_HIP(hipMemsetAsync(d.tallies.p, 0, d.tallies.n * sizeof(unsigned long long), e->stream));
+        d.rows_upper = 0; d.in_sample = true; d.made = false; d.n_sites = 0; d.n_pairs = 0;
     }
     TrimStage* const trim_stages[] = {e->primers.get(), e->adapters.get()};
     for (TrimStage* t : trim_stages)
@@ -381,11 +401,11 @@ static bk::IndelArgs indel_args(const bk_engine* e) {
     const Indels& d = *e->indels;
     bk::IndelArgs a{};
     a.kmer_pos = ix.kmer_pos.p; a.pilots = ix.pilots.p; a.m = ix.m; a.log2nb = ix.log2nb; a.log2p = ix.log2p; a.n_full = ix.n_full;
-    a.unique_bits = d.unique_bits.p;
+    a.unique_bits = d.anchors->unique_bits.p;
     a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words(); a.rc_words = ix.rc_words.p + bk::scan_ref_pad_words();
     a.total_cells = (uint32_t)ix.total_cells; a.k = ix.k;
-    a.seq_lo = d.seq_lo.p; a.n_seqs = (uint32_t)(d.seq_lo.n - 1);
-    a.nruns = d.nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
+    a.seq_lo = d.anchors->seq_lo.p; a.n_seqs = (uint32_t)(d.anchors->seq_lo.n - 1);
+    a.nruns = d.anchors->nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
     a.max_len = d.cfg.max_len; a.max_mismatches = d.cfg.max_mismatches;
     a.key0 = d.key0.p; a.key1 = d.key1.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
     a.span = d.span.p; a.tallies = d.tallies.p;
@@ -398,6 +418,56 @@ static int indel_push(bk_engine* e, const Records& r) {
     bk::IndelArgs a = indel_args(e);
     a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.n_records_dev = r.n_dev; a.stride_words = r.stride_words;
     bk::launch_indel_scan(a, e->ix->n_cus, e->stream);
+    return BK_OK;
+}
+
+// bk_link_enable: a row per placed record (link_scan_kernel), on the engine stream behind the scan of the same records
+static bk::LinkArgs link_args(const bk_engine* e) {
+    const IndexTables& ix = *e->ix;
+    const Linkage& d = *e->linkage;
+    bk::LinkArgs a{};
+    a.kmer_pos = ix.kmer_pos.p; a.pilots = ix.pilots.p; a.m = ix.m; a.log2nb = ix.log2nb; a.log2p = ix.log2p; a.n_full = ix.n_full;
+    a.unique_bits = d.anchors->unique_bits.p;
+    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words(); a.rc_words = ix.rc_words.p + bk::scan_ref_pad_words();
+    a.total_cells = (uint32_t)ix.total_cells; a.k = ix.k;
+    a.seq_lo = d.anchors->seq_lo.p; a.n_seqs = (uint32_t)(d.anchors->seq_lo.n - 1);
+    a.nruns = d.anchors->nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
+    a.max_mismatches = d.cfg.max_mismatches;
+    a.rows = d.rows.p; a.row_cap = d.rows.n / 2;
+    a.tallies = d.tallies.p;
+    a.sites = d.sites.p; a.pair_lo = d.pair_lo.p; a.n_sites = d.n_sites; a.max_dist = d.max_dist; a.n_pairs = d.n_pairs;
+    a.counts = d.counts.p;
+    return a;
+}
+static int link_push(bk_engine* e, const Records& r) {
+    Linkage& d = *e->linkage;
+    if (!d.in_sample || r.n == 0) return BK_OK;      // (enabled after this sample began: it has no rows)
+    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_link_enable: a batch of 2^31 records or more");
+    const uint64_t need = d.rows_upper + r.n;       // (only the device knows how many of the records are placed: room for all of them)
+    if (need >= (1ull << 32)) return fail(BK_ERR_UNSUPPORTED, "bk_link_enable: a sample of 2^32 records or more (%llu)", (unsigned long long)need);
+    const uint64_t cap = d.rows.n / 2;
+    if (int rc = link_free_old(d, false)) return rc;
+    if (need > cap) {   // a larger store: allocate, copy behind the scans so far; the old one stays until the stream has passed the copy
+        const uint64_t ncap = std::min<uint64_t>(std::max<uint64_t>(need, 2 * cap), 1ull << 32);
+        uint4* np = nullptr;
+        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&np), (size_t)ncap * 2 * sizeof(uint4));
+        if (err != hipSuccess) return fail(BK_ERR_HIP, "bk_link_enable: no memory for a row store of %llu rows: %s", (unsigned long long)ncap, hipGetErrorString(err));
+        const uint64_t filled = std::min<uint64_t>(d.rows_upper, cap);
+        if (filled) {
+            const hipError_t ce = hipMemcpyAsync(np, d.rows.p, (size_t)filled * 2 * sizeof(uint4), hipMemcpyDeviceToDevice, e->stream);
+            if (ce != hipSuccess) { (void)hipFree(np); return fail(BK_ERR_HIP, "bk_link_enable: copying the row store failed: %s", hipGetErrorString(ce)); }
+        }
+        Event passed;                                // behind the copy: the old store is free once the stream is here
+        hipError_t ee = passed.create();
+        if (ee == hipSuccess) ee = hipEventRecord(passed, e->stream);
+        if (ee != hipSuccess) { (void)hipStreamSynchronize(e->stream); (void)hipFree(np); return fail(BK_ERR_HIP, "bk_link_enable: hipEventRecord failed: %s", hipGetErrorString(ee)); }
+        d.old.emplace_back(d.rows.p, std::move(passed));
+        d.rows.p = np; d.rows.n = (size_t)ncap * 2;
+    }
+    d.rows_upper = need;
+    bk::LinkArgs a = link_args(e);
+    a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.n_records_dev = r.n_dev; a.stride_words = r.stride_words;
+    bk::launch_link_scan(a, e->ix->n_cus, e->stream);
     return BK_OK;
 }
 
@@ -645,6 +715,7 @@ int push_device(bk_engine* e, int mate, const Records& r) {
         }
     }
     if (e->indels) { if (int rc = indel_push(e, r)) return rc; }
+    if (e->linkage) { if (int rc = link_push(e, r)) return rc; }
     BK_HIP(hipGetLastError());
     if (!r.n_dev) pl.pushed_records += n;
     return note_ktab_fill(e);
@@ -1356,6 +1427,39 @@ int bk_sample_download_region_depths(bk_engine* e, bk_region_summary* summary, b
     return BK_OK;
 }
 
+// ---- placing records by anchor k-mers: what bk_indels_enable and bk_link_enable ask of the index and build from it -----------------
+static int anchor_index_check(const IndexTables& ix, const char* who) {
+    if (ix.W <= 0 || ix.n_full == 0) return fail(BK_ERR_INVALID, "%s: the index has no window of reference k-mers", who);
+    if (!ix.rc_words.p)   // (build_index_tables makes it with the binned scan's seed tables: fewer than 2^27 cells, at least k)
+        return fail(BK_ERR_UNSUPPORTED, "%s: the engine holds no reverse-complemented reference (it is made for a genome of k to 2^27 - 1 positions; this one has %llu)",
+                    who, (unsigned long long)ix.total_cells);
+    return BK_OK;
+}
+// the engine's anchor tables: the ones the other feature holds, else built here
+static int anchor_tables(bk_engine* e, const char* who, std::shared_ptr<AnchorTables>& out) {
+    if ((out = e->anchors.lock())) return BK_OK;
+    const IndexTables& ix = *e->ix;
+    std::shared_ptr<AnchorTables> t(new AnchorTables());
+    {   // a histogram of the ids over the cells: one bit per id that starts at exactly one cell
+        std::vector<uint32_t> id_at((size_t)ix.total_cells);
+        BK_HIP(hipMemcpy(id_at.data(), ix.id_at.p, id_at.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> seen(ix.n_full, 0);
+        for (uint32_t id : id_at) if (id < ix.n_full && seen[id] < 2) seen[id]++;
+        std::vector<uint32_t> bits(((size_t)ix.n_full + 31) / 32, 0u);
+        for (uint32_t id = 0; id < ix.n_full; id++) if (seen[id] == 1) bits[id >> 5] |= 1u << (id & 31u);
+        BK_HIP(t->unique_bits.upload(bits));
+    }
+    std::vector<uint32_t> lo;
+    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) lo.push_back((uint32_t)ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q]);
+    lo.push_back((uint32_t)ix.total_cells);
+    if (lo.size() < 2) return fail(BK_ERR_INVALID, "%s: the genome file has no sequence", who);
+    BK_HIP(t->seq_lo.upload(lo));
+    BK_HIP(t->nruns.upload(ix.h_nonacgt));
+    e->anchors = t;
+    out = std::move(t);
+    return BK_OK;
+}
+
 // ---- short insertions and deletions from the reads (bk_indels.hip) ------------------------------------------------
 int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
@@ -1367,10 +1471,7 @@ int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
         if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_indels_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
         if (ix.n_files != 1)
             return fail(BK_ERR_INVALID, "bk_indels_enable: the index has %d genome files; indels are called against an index of one genome file", ix.n_files);
-        if (ix.W <= 0 || ix.n_full == 0) return fail(BK_ERR_INVALID, "bk_indels_enable: the index has no window of reference k-mers");
-        if (!ix.rc_words.p)   // (build_index_tables makes it with the binned scan's seed tables: fewer than 2^27 cells, at least k)
-            return fail(BK_ERR_UNSUPPORTED, "bk_indels_enable: the engine holds no reverse-complemented reference (it is made for a genome of k to 2^27 - 1 positions; this one has %llu)",
-                        (unsigned long long)ix.total_cells);
+        if (int rc = anchor_index_check(ix, "bk_indels_enable")) return rc;
     }
     BK_HIP(hipSetDevice(e->device));
     BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
@@ -1378,21 +1479,7 @@ int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
     if (!cfg) return BK_OK;
     std::unique_ptr<Indels> d(new Indels());
     d->cfg = *cfg;
-    {   // a histogram of the ids over the cells: one bit per id that starts at exactly one cell
-        std::vector<uint32_t> id_at((size_t)ix.total_cells);
-        BK_HIP(hipMemcpy(id_at.data(), ix.id_at.p, id_at.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        std::vector<uint8_t> seen(ix.n_full, 0);
-        for (uint32_t id : id_at) if (id < ix.n_full && seen[id] < 2) seen[id]++;
-        std::vector<uint32_t> bits(((size_t)ix.n_full + 31) / 32, 0u);
-        for (uint32_t id = 0; id < ix.n_full; id++) if (seen[id] == 1) bits[id >> 5] |= 1u << (id & 31u);
-        BK_HIP(d->unique_bits.upload(bits));
-    }
-    std::vector<uint32_t> lo;
-    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) lo.push_back((uint32_t)ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q]);
-    lo.push_back((uint32_t)ix.total_cells);
-    if (lo.size() < 2) return fail(BK_ERR_INVALID, "bk_indels_enable: the genome file has no sequence");
-    BK_HIP(d->seq_lo.upload(lo));
-    BK_HIP(d->nruns.upload(ix.h_nonacgt));
+    if (int rc = anchor_tables(e, "bk_indels_enable", d->anchors)) return rc;
     const size_t slots = (size_t)1 << cfg->table_log2;
     BK_HIP(d->key0.alloc(slots)); BK_HIP(d->key1.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
     BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
@@ -1447,6 +1534,128 @@ int bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap) {
     BK_HIP(hipSetDevice(e->device));
     BK_HIP(hipMemcpyAsync(span, e->indels->span.p, (size_t)e->ix->total_cells * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     BK_HIP(hipStreamSynchronize(e->stream));
+    return BK_OK;
+}
+
+// ---- which substitutions the same records carry (bk_linkage.hip) ----------------------------------------------------
+int bk_link_enable(bk_engine* e, const bk_link_config* cfg) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_link_enable comes between samples");
+    const IndexTables& ix = *e->ix;
+    if (cfg) {
+        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_link_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
+        if (cfg->initial_rows < 1 || cfg->initial_rows > (1ull << 32))
+            return fail(BK_ERR_INVALID, "bk_link_enable: initial_rows must be 1..2^32, got %llu", (unsigned long long)cfg->initial_rows);
+        if (ix.n_files != 1)
+            return fail(BK_ERR_INVALID, "bk_link_enable: the index has %d genome files; linkage is counted against an index of one genome file", ix.n_files);
+        if (int rc = anchor_index_check(ix, "bk_link_enable")) return rc;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
+    e->linkage.reset();
+    if (!cfg) return BK_OK;
+    std::unique_ptr<Linkage> d(new Linkage());
+    d->cfg = *cfg;
+    if (int rc = anchor_tables(e, "bk_link_enable", d->anchors)) return rc;
+    BK_HIP(d->rows.alloc((size_t)cfg->initial_rows * 2));
+    BK_HIP(d->tallies.alloc(4));
+    BK_HIP(hipMemsetAsync(d->tallies.p, 0, 4 * sizeof(unsigned long long), e->stream));
+    e->linkage = std::move(d);
+    return BK_OK;
+}
+
+int bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uint32_t max_dist) {
+    if (!e || (!cells && n_sites)) return fail(BK_ERR_INVALID, "null argument");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage comes after bk_sample_finalize");
+    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_linkage: bk_sample_finalize has not run for this sample");
+    if (n_sites > BK_LINK_MAX_SITES) return fail(BK_ERR_INVALID, "bk_sample_linkage: at most %d sites, got %u", BK_LINK_MAX_SITES, n_sites);
+    if (max_dist < 1 || max_dist > BK_LINK_MAX_DIST) return fail(BK_ERR_INVALID, "bk_sample_linkage: max_dist must be 1..%d, got %u", BK_LINK_MAX_DIST, max_dist);
+    const IndexTables& ix = *e->ix;
+    for (uint32_t i = 0; i < n_sites; i++) {
+        if (cells[i] >= ix.total_cells) return fail(BK_ERR_INVALID, "bk_sample_linkage: site %u is cell %u, the index has %llu", i, cells[i], (unsigned long long)ix.total_cells);
+        if (i && cells[i] <= cells[i - 1]) return fail(BK_ERR_INVALID, "bk_sample_linkage: the sites must be strictly ascending (site %u is cell %u behind cell %u)", i, cells[i], cells[i - 1]);
+    }
+    Linkage& d = *e->linkage;
+    // the pairs: i < j in one sequence, cell_j - cell_i <= max_dist -- for each i a stretch of j that starts at i + 1
+    std::vector<uint32_t> seq_end;               // end cell of every sequence of the genome file
+    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) seq_end.push_back((uint32_t)(ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q] + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q]));
+    std::vector<uint32_t> pair_lo(n_sites);
+    uint64_t n_pairs = 0;
+    for (uint32_t i = 0, j = 0, s = 0; i < n_sites; i++) {
+        while (s + 1 < seq_end.size() && cells[i] >= seq_end[s]) s++;
+        if (j < i + 1) j = i + 1;
+        while (j < n_sites && cells[j] < seq_end[s] && cells[j] - cells[i] <= max_dist) j++;   // (j never moves back: both bounds grow with i)
+        pair_lo[i] = (uint32_t)std::min<uint64_t>(n_pairs, 0xffffffffull);
+        n_pairs += j - (i + 1);
+    }
+    if (n_pairs > BK_LINK_MAX_PAIRS)
+        return fail(BK_ERR_INVALID, "bk_sample_linkage: %llu pairs of sites within %u cells, at most %u are counted", (unsigned long long)n_pairs, max_dist, BK_LINK_MAX_PAIRS);
+    BK_HIP(hipSetDevice(e->device));
+    // an earlier count may still read the sites, pair_lo, the counters and the pinned copies that are replaced here: wait for that
+    // launch alone -- nothing else of the stream's work is waited for
+    if (d.count_in_flight) { BK_HIP(hipEventSynchronize(d.counted)); d.count_in_flight = false; }
+    BK_HIP(d.h_sites.grow(std::max<size_t>(n_sites, 1))); BK_HIP(d.h_pair_lo.grow(std::max<size_t>(n_sites, 1)));
+    if (n_sites) { std::memcpy(d.h_sites.p, cells, n_sites * sizeof(uint32_t)); std::memcpy(d.h_pair_lo.p, pair_lo.data(), n_sites * sizeof(uint32_t)); }
+    d.n_sites = n_sites; d.max_dist = max_dist; d.n_pairs = n_pairs; d.made = false;
+    BK_HIP(grow(d.sites, n_sites)); BK_HIP(grow(d.pair_lo, n_sites)); BK_HIP(grow(d.counts, (size_t)n_pairs * 16));
+    bk_engine::Span sp(e, 1);
+    if (n_sites) {
+        BK_HIP(hipMemcpyAsync(d.sites.p, d.h_sites.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemcpyAsync(d.pair_lo.p, d.h_pair_lo.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    if (n_pairs) BK_HIP(hipMemsetAsync(d.counts.p, 0, (size_t)n_pairs * 16 * sizeof(unsigned int), e->stream));
+    bk::launch_link_count(link_args(e), d.rows_upper, ix.n_cus, e->stream);
+    BK_HIP(hipGetLastError());
+    BK_HIP(d.counted.create());
+    BK_HIP(hipEventRecord(d.counted, e->stream));
+    d.count_in_flight = true;
+    d.made = true;
+    return BK_OK;
+}
+
+static int link_finalized(bk_engine* e, const char* who) {
+    if (e->in_sample || !e->linkage || !e->linkage->in_sample || e->finalized_mates < 1)
+        return fail(BK_ERR_STATE, "%s comes after bk_sample_finalize of a sample that began with linkage enabled", who);
+    return BK_OK;
+}
+
+int bk_sample_download_linkage(bk_engine* e, bk_link_summary* summary, bk_link_pair* pairs, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_linkage")) return rc;
+    Linkage& d = *e->linkage;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long t[4];
+    BK_HIP(hipMemcpyAsync(t, d.tallies.p, sizeof t, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    summary->records = t[0]; summary->placed = t[1]; summary->unplaced = t[2]; summary->discordant = t[3];
+    summary->n_pairs = d.made ? d.n_pairs : 0; summary->n_sites = d.made ? d.n_sites : 0; summary->max_dist = d.made ? d.max_dist : 0;
+    const uint64_t n = std::min<uint64_t>(summary->n_pairs, cap);
+    if (!n || !pairs) return BK_OK;
+    std::vector<unsigned int> counts((size_t)n * 16);
+    BK_HIP(hipMemcpy(counts.data(), d.counts.p, counts.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < d.n_sites && at < n; i++) {
+        const uint64_t end = i + 1 < d.n_sites ? d.h_pair_lo.p[i + 1] : d.n_pairs;
+        for (uint64_t p = d.h_pair_lo.p[i]; p < end && at < n; p++, at++) {
+            pairs[at].site_a = d.h_sites.p[i]; pairs[at].site_b = d.h_sites.p[i + 1 + (size_t)(p - d.h_pair_lo.p[i])];
+            std::memcpy(pairs[at].count, counts.data() + (size_t)p * 16, 16 * sizeof(uint32_t));
+        }
+    }
+    return BK_OK;
+}
+
+int bk_sample_download_link_rows(bk_engine* e, bk_link_row* rows, uint64_t cap) {
+    static_assert(sizeof(bk_link_row) == 2 * sizeof(uint4), "a row is two 16-byte stores");
+    if (!e || (!rows && cap)) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_link_rows")) return rc;
+    Linkage& d = *e->linkage;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long placed = 0;
+    BK_HIP(hipMemcpyAsync(&placed, d.tallies.p + 1, sizeof placed, hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(placed, cap), d.rows.n / 2);
+    if (n) BK_HIP(hipMemcpy(rows, d.rows.p, (size_t)n * sizeof(bk_link_row), hipMemcpyDeviceToHost));
     return BK_OK;
 }
 

@@ -232,13 +232,39 @@ struct Regions {
     uint32_t max_file_regions = 0;          // regions of the genome file with the most: the kernel's grid
 };
 
+// What placing a record by two anchor k-mers reads beside the index tables (bk_anchor.h): built by the first of bk_indels_enable and
+// bk_link_enable, used by both, freed with the last of them
+struct AnchorTables {
+    DevBuf<uint32_t> unique_bits;           // one bit per reference k-mer id: it starts at exactly one cell (a histogram of id_at)
+    DevBuf<uint32_t> seq_lo;                // [sequences + 1] first cells, then total_cells
+    DevBuf<uint2> nruns;                    // IndexTables::h_nonacgt
+};
+
+// bk_link_enable: the sample's row store (one bk_link_row per placed record), its tallies, and what the last bk_sample_linkage made
+struct Linkage {
+    bk_link_config cfg{};
+    std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable
+    DevBuf<uint4> rows;                     // [2 * capacity in rows]
+    std::vector<std::pair<uint4*, Event>> old;   // outgrown stores with the event behind the copy out of them: freed once it has passed
+    uint64_t rows_upper = 0;                // a bound on the rows in the store: the records of every batch pushed (the count is the device's)
+    DevBuf<unsigned long long> tallies;     // [4] bk_kernels.h LinkArgs::tallies
+    DevBuf<uint32_t> sites, pair_lo;        // the last bk_sample_linkage's
+    DevBuf<unsigned int> counts;            // [pairs][16]
+    PinnedBuf<uint32_t> h_sites, h_pair_lo; // pinned host copies: the uploads are asynchronous, the download reads the enumeration
+    Event counted;                          // behind the last count's launch: the next bk_sample_linkage replaces what it reads
+    bool count_in_flight = false;
+    uint32_t n_sites = 0, max_dist = 0;
+    uint64_t n_pairs = 0;
+    bool in_sample = false;                 // enabled when the current / last sample began
+    bool made = false;                      // the counters are this sample's (bk_sample_linkage ran)
+    ~Linkage() { for (auto& o : old) (void)hipFree(o.first); }
+};
+
 // bk_indels_enable: what indel_scan_kernel reads beside the index tables (bk_indels.hip), the sample's event table, span array and
 // tallies, and the report's rows -- all allocated by the call
 struct Indels {
     bk_indel_config cfg{};
-    DevBuf<uint32_t> unique_bits;           // one bit per reference k-mer id: it starts at exactly one cell (a histogram of id_at)
-    DevBuf<uint32_t> seq_lo;                // [sequences + 1] first cells, then total_cells
-    DevBuf<uint2> nruns;                    // IndexTables::h_nonacgt
+    std::shared_ptr<AnchorTables> anchors;  // shared with bk_link_enable
     DevBuf<unsigned long long> key0, key1;  // [2^table_log2] the event table's two key words (~0 = free)
     DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
     DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_indels
@@ -467,6 +493,8 @@ struct bk_engine {
     std::unique_ptr<Regions> regions;       // bk_regions_set (null: no regions, no launch, no buffers)
     bool regions_made = false;              // bk_sample_region_depths ran for the current sample and table
     std::unique_ptr<Indels> indels;         // bk_indels_enable (null: no table, no launch, no buffers)
+    std::unique_ptr<Linkage> linkage;       // bk_link_enable (null: no row store, no launch, no buffers)
+    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while either feature holds them
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 
+#include "bk_anchor.h"
 #include "bk_scan_common.h"
 
 namespace bk {
@@ -31,70 +32,6 @@ constexpr int kPrefixBlock = 1024;
 constexpr unsigned long long kFreeWord = ~0ull;
 
 struct IndelTally { uint32_t records = 0, anchored = 0, spanning = 0, supporting = 0, discordant = 0; };
-
-__device__ __forceinline__ uint32_t sym_at(const uint32_t* __restrict__ w, uint32_t i) { return (w[i >> 4] >> (2u * (i & 15u))) & 3u; }
-// sixteen symbols from symbol `pos` on; word indices are clamped to last_word (a record's last word; ~0u for the references, which
-// are padded behind).  symbols_at / read_symbols_at of bk_scan_common.h cut the same window 32 symbols wide from three words; a step
-// here is sixteen bases, which two words hold, and the record's clamp and the references' lack of one share this one function.
-__device__ __forceinline__ uint32_t sym16_at(const uint32_t* __restrict__ w, uint32_t pos, uint32_t last_word) {
-    const uint32_t wi = pos >> 4;
-    return __builtin_amdgcn_alignbit(w[min(wi + 1u, last_word)], w[min(wi, last_word)], 2u * (pos & 15u));
-}
-// #{i in [lo, hi): record[i] != text[diag + i]}; gives up above `stop` (what it returns is then only known to be larger)
-__device__ __forceinline__ uint32_t mismatches(const uint32_t* __restrict__ w, uint32_t last_word, uint32_t lo, uint32_t hi,
-                                               const uint32_t* __restrict__ text, int64_t diag, uint32_t stop) {
-    uint32_t m = 0;
-    for (uint32_t i = lo; i < hi && m <= stop; i += 16u) {
-        uint32_t x = sym16_at(w, i, last_word) ^ sym16_at(text, (uint32_t)(diag + (int64_t)i), ~0u);
-        x = (x | (x >> 1)) & 0x55555555u;
-        const uint32_t c = hi - i;
-        if (c < 16u) x &= (1u << (2u * c)) - 1u;
-        m += (uint32_t)__popc(x);
-    }
-    return m;
-}
-
-// the k-mer at offset o of a record as an anchor: its cell and strand.  o + k <= the record's length.
-__device__ __forceinline__ bool anchor_at(const IndelArgs& a, const uint32_t* __restrict__ w, uint32_t o, uint32_t* cell, bool* against) {
-    const uint32_t k = (uint32_t)a.k;
-    const uint32_t w0 = o >> 4, sh = 2u * (o & 15u), wl = (o + k - 1u) >> 4;
-    unsigned long long x = w[w0];
-    if (wl > w0) x |= (unsigned long long)w[w0 + 1] << 32;
-    x >>= sh;
-    if (wl > w0 + 1) x |= (unsigned long long)w[w0 + 2] << (64u - sh);   // (sh > 0 here, as in kmer_dump_count_kernel)
-    const unsigned long long kmask = (1ull << (2u * k)) - 1ull;
-    const unsigned long long fwd = rev2_64(x) >> (64u - 2u * k);          // base o leads (kmer_to_u64)
-    const unsigned long long rc = ~x & kmask;                             // its reverse complement: the complements, base o last
-    const bool read_rc = !(fwd < rc);
-    const unsigned long long canon = read_rc ? rc : fwd;
-    const uint32_t pilot = a.pilots[phf_bucket(canon, a.log2nb)];
-    const KmerPos kp = a.kmer_pos[phf_pos(canon, pilot, a.m, a.log2nb, a.log2p)];
-    if (kp.key != canon) return false;
-    const uint32_t id = kp.idflags & kIdMask;
-    if (id >= a.n_full || !((a.unique_bits[id >> 5] >> (id & 31u)) & 1u)) return false;
-    *cell = kp.refcell;
-    *against = read_rc != ((kp.idflags >> 31) != 0u);
-    return true;
-}
-
-__device__ __forceinline__ uint32_t seq_of(const IndelArgs& a, uint32_t cell) {
-    uint32_t lo = 0, hi = a.n_seqs;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.seq_lo[mid] <= cell) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the first of the runs of letters that are not ACGT (ascending, disjoint) that ends behind cell `lo`; n_nruns: none does
-__device__ __forceinline__ uint32_t first_run_behind(const IndelArgs& a, int32_t lo) {
-    uint32_t b = 0, e = a.n_nruns;
-    while (b < e) {
-        const uint32_t mid = (b + e) >> 1;
-        if ((int32_t)a.nruns[mid].y > lo) e = mid; else b = mid + 1u;
-    }
-    return b;
-}
 
 __device__ __forceinline__ void event_insert(const IndelArgs& a, uint32_t cell, uint32_t kind, uint32_t len, unsigned long long s, bool against) {
     // {cell, kind, length, S}: S's first base rides in the first word, so that neither word can equal the free word
@@ -123,30 +60,14 @@ __device__ __forceinline__ bool indel_anchor(const IndelArgs& a, uint32_t r, Ind
     t.records++;
     if (n < 2 * k) return false;
     const uint32_t* __restrict__ w = a.words + (uint64_t)r * a.stride_words;
-    int32_t f_off = -1, b_off = -1;
-    uint32_t f_cell = 0, b_cell = 0;
-    bool f_ag = false, b_ag = false;
-    for (int32_t o = 0; o <= 24 && o + k <= n; o += 8)
-        if (anchor_at(a, w, (uint32_t)o, &f_cell, &f_ag)) { f_off = o; break; }
-    if (f_off < 0) return false;
-    for (int32_t o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (anchor_at(a, w, (uint32_t)o, &b_cell, &b_ag)) { b_off = o; break; }
-    if (b_off < 0 || f_ag != b_ag) return false;
-    const bool against = f_ag;
-    const int32_t pa = against ? n - k - b_off : f_off, pb = against ? n - k - f_off : b_off;   // offsets in r'
-    const uint32_t ca = against ? b_cell : f_cell, cb = against ? f_cell : b_cell;
-    if (pa + k > pb) return false;
+    Anchors an;
+    if (!anchors_of(a, w, n, an)) return false;
+    const bool against = an.against;
+    const int32_t pa = an.pa, pb = an.pb;
     t.anchored++;
-    const int32_t dL = (int32_t)ca - pa, dR = (int32_t)cb - pb, delta = dR - dL;
+    const int32_t dL = (int32_t)an.ca - pa, dR = (int32_t)an.cb - pb, delta = dR - dL;
     if (delta > (int32_t)a.max_len || -delta > (int32_t)a.max_len) { t.discordant++; return false; }
-    const uint32_t s = seq_of(a, ca);
-    if (seq_of(a, cb) != s) return false;
-    const int32_t lo = min(dL, dR), hi = max(dL, dR) + n;
-    if (lo < (int32_t)a.seq_lo[s] || hi > (int32_t)a.seq_lo[s + 1]) return false;
-    if (a.n_nruns) {
-        const uint32_t i = first_run_behind(a, lo);
-        if (i < a.n_nruns && (int32_t)a.nruns[i].x < hi) return false;
-    }
+    if (!cells_placed(a, an.ca, an.cb, min(dL, dR), max(dL, dR) + n)) return false;
     if (delta != 0) {
         work = make_uint4(r | (against ? 0x80000000u : 0u), (uint32_t)pa | ((uint32_t)pb << 16), (uint32_t)dL, (uint32_t)dR);
         return true;
@@ -210,12 +131,6 @@ __device__ __forceinline__ void indel_walk(const IndelArgs& a, const uint4 work,
     }
     t.supporting++;
     event_insert(a, (uint32_t)pos, D ? 0u : 1u, (uint32_t)(D ? D : I), s, against);
-}
-
-__device__ __forceinline__ uint32_t wave_total(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off);
-    return v;
 }
 
 __global__ __launch_bounds__(kIndelBlock) void indel_scan_kernel(IndelArgs a) {

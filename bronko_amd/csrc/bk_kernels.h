@@ -485,6 +485,36 @@ struct IndelArgs {
 void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream);
 void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_indel_report(const IndelArgs& a, hipStream_t stream);
+// bk_link_enable: which substitutions the same records carry (bk_linkage.hip; the rule: include/bronko_hip.h)
+struct LinkArgs {
+    // a batch of records (Records of bk_engine.h): link_scan_kernel
+    const uint32_t* words; const uint16_t* lens;
+    uint64_t n_records; const unsigned long long* n_records_dev;
+    uint32_t stride_words;
+    // the index and the anchor tables, as IndelArgs names them (bk_anchor.h reads both)
+    const KmerPos* kmer_pos; const uint16_t* pilots;
+    uint32_t m, log2nb, log2p, n_full;
+    const uint32_t* unique_bits;
+    const uint32_t* ref_words; const uint32_t* rc_words;
+    uint32_t total_cells; int32_t k;
+    const uint32_t* seq_lo;
+    uint32_t n_seqs;
+    const uint2* nruns;
+    uint32_t n_nruns;
+    uint32_t max_mismatches;
+    // the sample: its row store (a row is two uint4: bk_link_row) and tallies
+    uint4* rows; uint64_t row_cap;
+    unsigned long long* tallies;         // [4] records, placed (= the rows in the store), unplaced, discordant
+    // the count: link_count_kernel
+    const uint32_t* sites;               // [n_sites] cells, strictly ascending
+    const uint32_t* pair_lo;             // [n_sites] index of the pair (i, i + 1); the pair (i, j) is pair_lo[i] + (j - i - 1)
+    uint32_t n_sites, max_dist;
+    uint64_t n_pairs;
+    unsigned int* counts;                // [n_pairs][16] the record's base at A x its base at B
+};
+constexpr uint32_t kLinkLdsPairs = 512;  // a counter table of at most this many pairs is privatised in LDS (32 KiB a workgroup)
+void launch_link_scan(const LinkArgs& a, int n_cus, hipStream_t stream);
+void launch_link_count(const LinkArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

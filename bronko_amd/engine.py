@@ -464,6 +464,38 @@ class Engine:
         _check(self._L.bk_sample_download_indel_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
         return span[:self.total_cells]
 
+    def linkage_enable(self, max_mismatches=8, initial_rows=1 << 16):
+        """bk_link_enable: link_scan_kernel runs behind every scan of the samples that begin from now on and keeps a row per placed
+        record; max_mismatches=None disables."""
+        cfg = None if max_mismatches is None else C.byref(_ffi.LinkConfig(int(max_mismatches), int(initial_rows)))
+        _check(self._L.bk_link_enable(self.h, cfg), self._L)
+
+    def sample_linkage(self, cells, max_dist=1000):
+        """bk_sample_linkage: the 16 counters of every pair of the sites `cells` (strictly ascending) at most max_dist apart, counted
+        from the finalized sample's rows on the device (asynchronous)."""
+        arr = np.ascontiguousarray(np.asarray(cells, np.int64).astype(np.uint32))
+        _check(self._L.bk_sample_linkage(self.h, arr.ctypes.data_as(C.c_void_p), len(arr), int(max_dist)), self._L)
+
+    def download_linkage(self, cap=None):
+        """(summary, pairs) of sample_linkage: pairs = [(site_a, site_b, [16 counters: 4 * base at a + base at b])] in (i, j) order,
+        min(cap, summary.n_pairs) of them, all by default."""
+        summ = _ffi.LinkSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_linkage(self.h, C.byref(summ), None, 0), self._L)
+            cap = int(summ.n_pairs)
+        buf = np.zeros((max(1, cap), 18), np.uint32)
+        _check(self._L.bk_sample_download_linkage(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, [(int(r[0]), int(r[1]), [int(v) for v in r[2:]]) for r in buf[:min(cap, int(summ.n_pairs))]]
+
+    def download_link_rows(self, cap=None):
+        """bk_sample_download_link_rows: the finalized sample's row store as [(cell0, n, strand, ((offset, base), ...))], sorted."""
+        summ = _ffi.LinkSummary()
+        _check(self._L.bk_sample_download_linkage(self.h, C.byref(summ), None, 0), self._L)   # (how many rows the store holds)
+        cap = int(summ.placed) if cap is None else min(int(cap), int(summ.placed))
+        buf = np.zeros((max(1, cap), 32), np.uint8)
+        _check(self._L.bk_sample_download_link_rows(self.h, buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return link_rows(buf[:cap])
+
     def regions_set(self, regions):
         """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
         arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])
@@ -491,3 +523,18 @@ class Engine:
         n = (C.c_uint64 * 4)()
         _check(self._L.bk_timing_read(self.h, ms, n, int(reset)), self._L)
         return list(ms), list(n)
+
+
+def link_rows(raw):
+    """[n][32] bytes of bk_link_row as [(cell0, n, strand, ((offset, base), ...))], sorted.  A row that no placed record can have
+    left (n = 0, more than 8 mismatches, an entry behind n_mm that is not zero) raises ValueError."""
+    out = []
+    for i, r in enumerate(np.asarray(raw, np.uint8).reshape(-1, 32)):
+        b = r.tobytes()
+        n, n_mm = b[4] | (b[5] << 8), b[7]
+        if n == 0 or n_mm > 8 or any(b[8 + 3 * n_mm:]):
+            raise ValueError("row %d of the row store is no placed record's: %s" % (i, b.hex()))
+        mm = tuple((b[8 + 3 * t] | (b[9 + 3 * t] << 8), b[10 + 3 * t]) for t in range(n_mm))
+        out.append((int.from_bytes(b[:4], "little"), n, b[6], mm))
+    out.sort()
+    return out

@@ -203,6 +203,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--indels: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.linkage) {          // (likewise: a sample's row store is one engine's)
+        LOG_DEBUG(T, "--linkage: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
     if (!shard_mode) shard_devices.clear();
     return shard_devices;
@@ -230,8 +234,12 @@ struct SampleData {
     std::vector<bk_region_depth> rrows;
     bk_indel_summary isumm{};                             // --indels
     std::vector<IndelEvent> indels;
+    bk_link_summary lsumm{};                              // --linkage
+    std::vector<LinkSite> link_recs;
+    std::vector<LinkPair> link_pairs;
 };
 
+constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
 constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
@@ -279,6 +287,8 @@ struct CallRun {
         if (cfg.region_report()) resolve_regions();
         if (cfg.indels && ix.files.size() != 1)   // (a k-mer's cell in the engine's table is its first among all files, not the selected genome's)
             die(T, "--indels needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.linkage && ix.files.size() != 1)
+            die(T, "--linkage needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
     }
     // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
     void resolve_regions() {
@@ -429,6 +439,10 @@ struct CallRun {
             const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
             hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
         }
+        if (cfg.linkage) {
+            const bk_link_config lc{cfg.link.max_mismatches, kLinkInitialRows};
+            hip_check(bk_link_enable(e, &lc), "bk_link_enable");
+        }
     }
     // text(sum): the line's start; stats(e, mate, out): the bk_*_stats call, n counters a mate file
     template <class Stats, class Text>
@@ -510,6 +524,23 @@ struct CallRun {
             d.indels.resize((size_t)d.isumm.reported);
             hip_check(bk_sample_download_indels(e, &d.isumm, reinterpret_cast<bk_indel_record*>(d.indels.data()), d.indels.size()), "bk_sample_download_indels");
         }
+        if (cfg.linkage) {   // the sites are the sample's own VCF records: counted behind the calls, a few rows travel
+            static_assert(sizeof(LinkPair) == sizeof(bk_link_pair), "LinkPair is bk_link_pair");
+            const FileMeta& fm = ix.files[0];     // (one genome file: checked as the index was opened)
+            std::vector<uint64_t> seq_cell(fm.sequences.size(), 0);
+            for (size_t q = 1; q < fm.sequences.size(); q++) seq_cell[q] = seq_cell[q - 1] + fm.sequences[q - 1].len;
+            for (uint64_t i = 0; i < std::min<uint64_t>(d.summ.n_records, d.recs.size()); i++) {
+                const bk_call_record& r = d.recs[i];
+                LinkSite s;
+                s.cell = (uint32_t)(seq_cell[(size_t)r.seq_id] + r.pos - 1); s.ref_base = (uint8_t)r.ref_base; s.alt_base = (uint8_t)r.alt_base;
+                d.link_recs.push_back(s);
+            }
+            const std::vector<uint32_t> sites = link_sites(d.link_recs);
+            hip_check(bk_sample_linkage(e, sites.data(), (uint32_t)sites.size(), cfg.link.max_dist), "bk_sample_linkage");
+            hip_check(bk_sample_download_linkage(e, &d.lsumm, nullptr, 0), "bk_sample_download_linkage");
+            d.link_pairs.resize((size_t)d.lsumm.n_pairs);
+            hip_check(bk_sample_download_linkage(e, &d.lsumm, reinterpret_cast<bk_link_pair*>(d.link_pairs.data()), d.link_pairs.size()), "bk_sample_download_linkage");
+        }
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
     uint64_t merge_mates(const std::vector<std::string>& mates, SampleData& d) const {
@@ -568,6 +599,11 @@ struct CallRun {
                                 " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.candidates) + " candidate events, " +
                                 std::to_string(s.reported) + " reported");
                 write_indels_vcf(a.output + "/" + stem + ".indels.vcf", mates[0], ix, best, d.indels, cfg.indel);
+            }
+            if (cfg.linkage) {      // (a sample without such a pair: the header alone)
+                const uint64_t lines = write_linkage_tsv(a.output + "/" + stem + ".linkage.tsv", ix, best, d.link_recs, d.link_pairs, cfg.link);
+                LOG_INFO(T, "Linkage: " + std::to_string(d.lsumm.placed) + " of " + std::to_string(d.lsumm.records) + " records placed, " +
+                                std::to_string(d.lsumm.n_pairs) + " pairs counted, " + std::to_string(lines) + " lines written");
             }
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }

@@ -73,8 +73,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
-          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [-t <THREADS>] [--debug]\n"
-          "            [--verbose]\n\n"
+          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--linkage]\n"
+          "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -103,7 +103,12 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --indel-max-len L        longest insertion or deletion looked for; 1..32, default 32\n"
           "  --indel-max-mismatches M substitutions a read may have beside its indel; 0..8, default 2\n"
           "  --indel-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
-          "  --indel-min-af F         AF an event needs to be written; 0..1, default the value of --min-af\n", stderr);
+          "  --indel-min-af F         AF an event needs to be written; 0..1, default the value of --min-af\n"
+          "  --linkage         write to <DIR>/<stem>.linkage.tsv, per pair of the sample's substitutions (an index of one genome file), how\n"
+          "                    many of the reads that cover both positions carry neither, the first, the second or both\n"
+          "  --link-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8\n"
+          "  --link-max-dist D        positions a pair may be apart; 1..65519, default 1000\n"
+          "  --link-min-reads N       reads that cover both positions a pair needs to be written; at least 1, default 1\n", stderr);
     exit(code);
 }
 
@@ -239,6 +244,17 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--indel-max-len") { a.indel_max_len = x; a.has_indel_max_len = true; }
             else if (opt == "--indel-max-mismatches") { a.indel_max_mismatches = x; a.has_indel_max_mismatches = true; }
             else { a.indel_min_reads = x; a.has_indel_min_reads = true; }
+        }
+        else if (opt == "--linkage") a.linkage = true;
+        else if (opt == "--link-max-mismatches" || opt == "--link-max-dist" || opt == "--link-min-reads") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--link-max-mismatches") { a.link_max_mismatches = x; a.has_link_max_mismatches = true; }
+            else if (opt == "--link-max-dist") { a.link_max_dist = x; a.has_link_max_dist = true; }
+            else { a.link_min_reads = x; a.has_link_min_reads = true; }
         }
         else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
         else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
@@ -428,6 +444,12 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.indel_max_len < 1 || a.indel_max_len > BK_INDEL_MAX_LEN) die(T, "--indel-max-len must be between 1 and " + std::to_string(BK_INDEL_MAX_LEN) + ", got " + std::to_string(a.indel_max_len));
     if (a.indel_max_mismatches < 0 || a.indel_max_mismatches > 8) die(T, "--indel-max-mismatches must be between 0 and 8, got " + std::to_string(a.indel_max_mismatches));
     if (a.indel_min_reads < 1) die(T, "--indel-min-reads must be at least 1, got " + std::to_string(a.indel_min_reads));
+    if (a.has_link_max_mismatches && !a.linkage) die(T, "--link-max-mismatches needs --linkage");
+    if (a.has_link_max_dist && !a.linkage) die(T, "--link-max-dist needs --linkage");
+    if (a.has_link_min_reads && !a.linkage) die(T, "--link-min-reads needs --linkage");
+    if (a.link_max_mismatches < 0 || a.link_max_mismatches > kLinkMaxMismatches) die(T, "--link-max-mismatches must be between 0 and 8, got " + std::to_string(a.link_max_mismatches));
+    if (a.link_max_dist < 1 || a.link_max_dist > (long)kLinkMaxDist) die(T, "--link-max-dist must be between 1 and " + std::to_string(kLinkMaxDist) + ", got " + std::to_string(a.link_max_dist));
+    if (a.link_min_reads < 1) die(T, "--link-min-reads must be at least 1, got " + std::to_string(a.link_min_reads));
     if (a.has_indel_min_af && !(a.indel_min_af >= 0.0 && a.indel_min_af <= 1.0)) {
         char buf[128];
         snprintf(buf, sizeof buf, "--indel-min-af must be between 0 and 1, got %g", a.indel_min_af);
@@ -471,6 +493,8 @@ CallConfig make_call_config(const Args& a) {
     c.indel.max_len = (uint32_t)a.indel_max_len; c.indel.max_mismatches = (uint32_t)a.indel_max_mismatches;
     c.indel.min_reads = (uint64_t)a.indel_min_reads;
     c.indel.min_af_ppm = (uint32_t)llround((a.has_indel_min_af ? a.indel_min_af : a.min_af) * 1e6);
+    c.linkage = a.linkage;
+    c.link.max_mismatches = (uint32_t)a.link_max_mismatches; c.link.max_dist = (uint32_t)a.link_max_dist; c.link.min_reads = (uint64_t)a.link_min_reads;
     return c;
 }
 

@@ -10,6 +10,7 @@
 #include "../../include/bronko_hip.h"
 #include "caller.hpp"
 #include "indels.hpp"
+#include "linkage.hpp"
 #include "index.hpp"
 
 namespace bronko {
@@ -66,6 +67,11 @@ struct Args {
     long indel_max_mismatches = 2;  // --indel-max-mismatches: substitutions a record may have beside its indel (0..8)
     long indel_min_reads = 5;       // --indel-min-reads: supporting records an event needs
     double indel_min_af = 0.03;     // --indel-min-af: support / (support + reference-spanning records) an event needs (default: --min-af)
+    bool linkage = false;           // --linkage: <DIR>/<stem>.linkage.tsv, which of the sample's substitutions the same reads carry
+    bool has_link_max_mismatches = false, has_link_max_dist = false, has_link_min_reads = false;
+    long link_max_mismatches = 8;   // --link-max-mismatches: substitutions a placed record may have (0..8)
+    long link_max_dist = 1000;      // --link-max-dist: pairs of substitutions at most this far apart are counted (1..65519)
+    long link_min_reads = 1;        // --link-min-reads: records that cover both positions a pair needs to be written
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -102,6 +108,9 @@ struct CallConfig {
     // --indels: bk_indels_enable / bk_sample_indels and the values the .indels.vcf header prints
     bool indels = false;
     IndelParams indel;
+    // --linkage: bk_link_enable / bk_sample_linkage and the values the .linkage.tsv header prints
+    bool linkage = false;
+    LinkParams link;
     bool region_report() const { return !regions_path.empty() || region_window > 0; }
     // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
     bool trims() const { return !primers.empty() || !adapters.empty(); }

@@ -10,6 +10,7 @@
 
 #include "caller.hpp"
 #include "indels.hpp"
+#include "linkage.hpp"
 #include "index.hpp"
 
 namespace {
@@ -250,6 +251,55 @@ int bh_write_indels_vcf(const void* h, int file_id, const char* path, const char
         p.max_len = max_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_af_ppm = min_af_ppm;
         bronko::write_indels_vcf(path, reads_path ? reads_path : "", *static_cast<const bronko::Index*>(h), file_id,
                                  std::vector<bronko::IndelEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --linkage: the host twin of the engine's linkage passes (linkage.cpp) ---------------------------------------------
+static std::vector<std::string> split_lines(const char* reads) {
+    std::vector<std::string> rd;
+    for (const char* at = reads; at && *at;) {
+        const char* nl = strchr(at, '\n');
+        rd.emplace_back(nl ? std::string(at, nl) : std::string(at));
+        at = nl ? nl + 1 : nullptr;
+    }
+    return rd;
+}
+// reads joined by '\n'; rows as bk_link_row (= bronko::LinkRow), at most cap written, *n their number; counters = {records, placed,
+// unplaced, discordant}
+int bh_link_rows(const void* h, int file_id, const char* reads, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::LinkRow) == 32 && sizeof(bronko::LinkPair) == 72, "LinkRow is bk_link_row, LinkPair is bk_link_pair");
+        const bronko::LinkResult r = bronko::link_rows(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), max_mismatches);
+        *n = r.rows.size();
+        if (rows) std::memcpy(rows, r.rows.data(), (size_t)std::min<uint64_t>(cap, r.rows.size()) * sizeof(bronko::LinkRow));
+        if (counters) { counters[0] = r.n.records; counters[1] = r.n.placed; counters[2] = r.n.unplaced; counters[3] = r.n.discordant; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// pairs as bk_link_pair, at most cap written, *n their number
+int bh_link_count(const void* h, int file_id, const void* rows, uint64_t n_rows, const uint32_t* sites, uint64_t n_sites, uint32_t max_dist, uint64_t cap,
+                  void* pairs, uint64_t* n) {
+    try {
+        const auto* rw = static_cast<const bronko::LinkRow*>(rows);
+        const std::vector<bronko::LinkPair> r = bronko::link_count(*static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::LinkRow>(rw, rw + n_rows),
+                                                                   std::vector<uint32_t>(sites, sites + n_sites), max_dist);
+        *n = r.size();
+        if (pairs) std::memcpy(pairs, r.data(), (size_t)std::min<uint64_t>(cap, r.size()) * sizeof(bronko::LinkPair));
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// recs: n_recs x {cell, ref base, alt base} as three u32; returns the lines written through *lines
+int bh_write_linkage_tsv(const void* h, int file_id, const char* path, const uint32_t* recs, uint64_t n_recs, const void* pairs, uint64_t n_pairs,
+                         uint32_t max_mismatches, uint32_t max_dist, uint64_t min_reads, uint64_t* lines) {
+    try {
+        std::vector<bronko::LinkSite> rs((size_t)n_recs);
+        for (uint64_t i = 0; i < n_recs; i++) { rs[i].cell = recs[3 * i]; rs[i].ref_base = (uint8_t)recs[3 * i + 1]; rs[i].alt_base = (uint8_t)recs[3 * i + 2]; }
+        const auto* pr = static_cast<const bronko::LinkPair*>(pairs);
+        bronko::LinkParams p;
+        p.max_mismatches = max_mismatches; p.max_dist = max_dist; p.min_reads = min_reads;
+        const uint64_t w = bronko::write_linkage_tsv(path, *static_cast<const bronko::Index*>(h), file_id, rs, std::vector<bronko::LinkPair>(pr, pr + n_pairs), p);
+        if (lines) *lines = w;
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -8,60 +8,12 @@
 #include <stdexcept>
 #include <tuple>
 
+#include "anchor_genome.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
 
 namespace {
-
-// One genome file as the rule sees it: its letters upper-cased, where its sequences start, its anchor k-mers
-struct IndelGenome {
-    int k = 0;
-    int64_t cell0 = 0;                               // first cell of the file among all cells of the index
-    std::string text;                                // the file's cells (upper-cased FASTA letters)
-    std::vector<int64_t> first;                      // first cell of each sequence, relative to cell0; one more entry: the end
-    struct Anchor { uint64_t kmer; uint32_t cell; bool rc; };
-    std::vector<Anchor> anchors;                     // canonical k-mers that start at exactly one cell, sorted
-
-    IndelGenome(const Index& ix, int file) : k(ix.k) {
-        if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("indel_events: no such genome file");
-        for (int f = 0; f < file; f++) cell0 += (int64_t)ix.genome_len((size_t)f);
-        std::vector<Anchor> all;
-        for (const SeqMeta& s : ix.files[(size_t)file].sequences) {
-            const int64_t c0 = (int64_t)text.size();
-            first.push_back(c0);
-            for (uint8_t c : s.seq) text.push_back((char)(c >= 'a' && c <= 'z' ? c - 32 : c));
-            // the genome's k-mers as the index reads them: every letter that is not ACGT stands for A (nt_to_bits)
-            for (uint64_t i = 0; i + (uint64_t)k <= s.seq.size(); i++) {
-                const Canon cn = canonical_kmer(s.seq.data() + i, k);
-                all.push_back(Anchor{cn.kmer, (uint32_t)(c0 + (int64_t)i), cn.rc});
-            }
-        }
-        first.push_back((int64_t)text.size());
-        std::sort(all.begin(), all.end(), [](const Anchor& x, const Anchor& y) { return x.kmer < y.kmer; });
-        for (size_t i = 0; i < all.size();) {
-            size_t j = i + 1;
-            while (j < all.size() && all[j].kmer == all[i].kmer) j++;
-            if (j == i + 1) anchors.push_back(all[i]);
-            i = j;
-        }
-    }
-    bool anchor(const char* kmer, uint32_t* cell, bool* against) const {
-        const Canon cn = canonical_kmer(reinterpret_cast<const uint8_t*>(kmer), k);
-        const auto it = std::lower_bound(anchors.begin(), anchors.end(), cn.kmer, [](const Anchor& a, uint64_t v) { return a.kmer < v; });
-        if (it == anchors.end() || it->kmer != cn.kmer) return false;
-        *cell = it->cell; *against = cn.rc != it->rc;
-        return true;
-    }
-    int seq_of(int64_t cell) const {
-        int s = 0;
-        while (s + 2 < (int)first.size() && first[(size_t)s + 1] <= cell) s++;
-        return s;
-    }
-};
-
-bool is_acgt(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
-char comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; }
 
 struct Tables {
     std::map<std::tuple<uint32_t, int, int, uint64_t>, std::pair<uint32_t, uint32_t>> events;   // (cell, kind, length, seq) -> fwd, rev
@@ -69,7 +21,7 @@ struct Tables {
     IndelCounters n;
 };
 
-void add_record(const IndelGenome& g, const std::string& rec, int L, int M, Tables& t) {
+void add_record(const AnchorGenome& g, const std::string& rec, int L, int M, Tables& t) {
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
@@ -151,7 +103,7 @@ bool indel_event_less(const IndelEvent& x, const IndelEvent& y) {
 IndelResult indel_events(const Index& ix, int file, const std::vector<std::string>& reads, int max_len, int max_mismatches) {
     if (max_len < 1 || max_len > kIndelMaxLen) throw std::runtime_error("indel_events: max_len must be 1..32");
     if (max_mismatches < 0 || max_mismatches > kIndelMaxMismatches) throw std::runtime_error("indel_events: max_mismatches must be 0..8");
-    const IndelGenome g(ix, file);
+    const AnchorGenome g(ix, file);
     Tables t;
     t.span.assign(g.text.size() + 2, 0);
     std::string run;

@@ -345,3 +345,62 @@ def write_indels_vcf(path, ix, file_id, reads_path, rows, max_len=32, max_mismat
     if L.bh_write_indels_vcf(ix.h, file_id, path.encode(), reads_path.encode(), rec.ctypes.data, len(rows), int(max_len), int(max_mismatches), int(min_reads),
                              int(min_af_ppm)) != 0:
         raise _host_error(L)
+
+
+def _link_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_linkage_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_link_rows.restype = C.c_int
+        L.bh_link_rows.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, u64, vp, C.POINTER(u64), vp]
+        L.bh_link_count.restype = C.c_int
+        L.bh_link_count.argtypes = [vp, C.c_int, vp, u64, vp, u64, u32, u64, vp, C.POINTER(u64)]
+        L.bh_write_linkage_tsv.restype = C.c_int
+        L.bh_write_linkage_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, vp, u64, u32, u32, u64, C.POINTER(u64)]
+        L._linkage_ready = True
+    return L
+
+
+def link_rows(ix, file_id, reads, max_mismatches=8):
+    """The host twin of link_scan_kernel (linkage.cpp link_rows) over ASCII reads: (rows as [n][32] bytes of bk_link_row in the order
+    of the records, (records, placed, unplaced, discordant))."""
+    L = _link_lib()
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    counters = np.zeros(4, np.uint64)
+    if L.bh_link_rows(ix.h, file_id, joined, int(max_mismatches), 0, None, C.byref(n), None) != 0:
+        raise _host_error(L)
+    raw = np.zeros((max(1, n.value), 32), np.uint8)
+    if L.bh_link_rows(ix.h, file_id, joined, int(max_mismatches), n.value, raw.ctypes.data, C.byref(n), counters.ctypes.data) != 0:
+        raise _host_error(L)
+    return raw[:n.value], tuple(int(c) for c in counters)
+
+
+def link_count(ix, file_id, raw_rows, sites, max_dist=1000):
+    """The host twin of link_count_kernel (linkage.cpp link_count): [(site_a, site_b, [16 counters])] in (i, j) order."""
+    L = _link_lib()
+    raw = np.ascontiguousarray(np.asarray(raw_rows, np.uint8).reshape(-1, 32))
+    st = np.ascontiguousarray(np.asarray(sites, np.int64).astype(np.uint32))
+    n = C.c_uint64()
+    if L.bh_link_count(ix.h, file_id, raw.ctypes.data, len(raw), st.ctypes.data, len(st), int(max_dist), 0, None, C.byref(n)) != 0:
+        raise _host_error(L)
+    buf = np.zeros((max(1, n.value), 18), np.uint32)
+    if L.bh_link_count(ix.h, file_id, raw.ctypes.data, len(raw), st.ctypes.data, len(st), int(max_dist), n.value, buf.ctypes.data, C.byref(n)) != 0:
+        raise _host_error(L)
+    return [(int(r[0]), int(r[1]), [int(v) for v in r[2:]]) for r in buf[:n.value]]
+
+
+def write_linkage_tsv(path, ix, file_id, recs, pairs, max_mismatches=8, max_dist=1000, min_reads=1):
+    """The --linkage writer (linkage.cpp write_linkage_tsv): recs = [(cell, ref base, alt base)] with 2-bit bases, pairs as
+    link_count gives them; returns the lines written."""
+    L = _link_lib()
+    rc = np.ascontiguousarray(np.asarray(recs, np.int64).reshape(-1, 3).astype(np.uint32))
+    buf = np.zeros((max(1, len(pairs)), 18), np.uint32)
+    for i, (a, b, c) in enumerate(pairs):
+        buf[i, 0], buf[i, 1] = a, b
+        buf[i, 2:] = c
+    lines = C.c_uint64()
+    if L.bh_write_linkage_tsv(ix.h, file_id, path.encode(), rc.ctypes.data, len(rc), buf.ctypes.data, len(pairs), int(max_mismatches), int(max_dist),
+                              int(min_reads), C.byref(lines)) != 0:
+        raise _host_error(L)
+    return lines.value

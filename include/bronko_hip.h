@@ -500,6 +500,67 @@ int  bk_sample_indels(bk_engine* e, const bk_indel_params* p);
 int  bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap);
 int  bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap);
 
+/* ---- which substitutions the same reads carry (`bronko call --linkage`; additive, still v8) -------------------------------------
+ * The pileup says how often each substitution occurs, not whether two of them sit on the same molecules.  The reads say it: a pass
+ * of its own over each batch's records (link_scan_kernel, behind the scan of the same records) keeps, per record that can be placed
+ * on the reference, where it lies and where it differs; at the sample's end link_count_kernel counts, for a list of sites, the 4 x 4
+ * table of the records' bases at every pair of sites that one record covers.  The rule, all of it integer arithmetic:
+ *   unit       a record, as for bk_indels_enable: a run of at least k valid letters after the trimming stage, n its length.  The
+ *              index has exactly one genome file.
+ *   placed     bk_indels_enable's anchor rule unchanged: the k-mers at offsets 0, 8, 16, 24 from either end are tried, the first
+ *              anchor k-mer from each end is that end's anchor, both exist and agree on the strand; r' = the record oriented along
+ *              the reference, a < b the anchors' offsets in r', c_a, c_b their cells, a + k <= b; dL = c_a - a, dR = c_b - b.
+ *              dR = dL exactly; both anchors in one sequence; the cells [dL, dL + n) inside that sequence and holding ACGT only;
+ *              then m = Hamming(r', ref[dL, dL + n)) <= max_mismatches.  A record of n < 2k is never placed.
+ *   tallies    every record is counted in `records` and in exactly one of `placed`, `discordant` (every check but the last one
+ *              held: more than max_mismatches mismatches) and `unplaced` (all others: n < 2k, no two anchors on one strand with
+ *              a + k <= b, dR != dL, other sequences, out of bounds, a letter that is not ACGT).
+ *   row        a placed record leaves one bk_link_row in the sample's row store: cell0 = dL, n, strand (1: it reads against the
+ *              reference), n_mm = m, and its mismatches ascending by offset: mm[3 i ..] = the offset j from cell0 (16 bits, little
+ *              endian) and r'[j] (A C G T = 0 1 2 3); the entries from n_mm on are zero.
+ *   covers     a placed record covers every cell of [dL, dL + n) -- no margin at its ends --; its base at cell c is r'[c - dL]: the
+ *              reference's unless one of its mismatches sits there.
+ *   sites      a strictly ascending list of at most BK_LINK_MAX_SITES cells (each < bk_total_cells).
+ *   pairs      all i < j with both cells in one sequence and cell_j - cell_i <= max_dist, in (i, j) order; at most
+ *              BK_LINK_MAX_PAIRS of them.
+ *   counters   per pair, count[4 bA + bB] = the placed records of both mate files that cover both cells with base bA at cell_i
+ *              and bB at cell_j, u32.  A record on either strand counts alike; overlapping mates count twice.
+ *   bk_link_enable            between samples (BK_ERR_STATE inside one); NULL disables and frees.  max_mismatches 0..8,
+ *                             initial_rows >= 1 (the row store's first capacity; it doubles as the sample needs), an index of one
+ *                             genome file with a window (BK_ERR_INVALID otherwise) and a genome of k to 2^27 - 1 positions
+ *                             (BK_ERR_UNSUPPORTED otherwise, as bk_indels_enable).  Per engine: forks enable their own.  Works with
+ *                             and without bk_indels_enable; the two share their anchor tables.  A sample that began before the call
+ *                             has no rows.  An engine that never enables it allocates and launches nothing.
+ *   pushes                    before a batch is scanned the store has room for a row of every record of it; growing is an
+ *                             allocation and a device copy on the engine's stream, and an allocation that fails is the push's
+ *                             error, never a loss.  32 bytes per record pushed (room is made for every record, placed or not); a
+ *                             store that grows is held beside its successor until the stream has passed the copy, then freed.
+ *                             2^32 records or more in one sample are BK_ERR_UNSUPPORTED.  bk_sample_begin empties the store: an abandoned sample leaves nothing.
+ *   bk_sample_linkage         after the sample's bk_sample_finalize (BK_ERR_STATE inside a sample, before any finalize, and when
+ *                             the feature was not enabled as the sample began).  BK_ERR_INVALID: sites not strictly ascending or
+ *                             not below bk_total_cells, more than BK_LINK_MAX_SITES, max_dist outside 1..65519, more than
+ *                             BK_LINK_MAX_PAIRS pairs (the message names the count; the host enumerates, nothing is launched).
+ *                             Zeroes the counters and counts; asynchronous on the engine's stream: the sites are staged in
+ *                             pinned memory and uploaded on the stream, and the host waits for nothing but an earlier count
+ *                             whose buffers the call replaces.  May be repeated with other sites or another max_dist on the
+ *                             same sample.
+ *   bk_sample_download_linkage   after the sample's finalize; synchronises; the summary and min(cap, n_pairs) rows {site_a,
+ *                             site_b, count[16]} in (i, j) order (site_a, site_b are the cells; pairs may be NULL).  Before the
+ *                             sample's first bk_sample_linkage there are the tallies and no pairs.
+ *   bk_sample_download_link_rows the row store as it is, min(cap, placed) rows in no particular order, after the sample's
+ *                             finalize; synchronises. */
+#define BK_LINK_MAX_SITES 65536
+#define BK_LINK_MAX_PAIRS (1u << 20)
+#define BK_LINK_MAX_DIST 65519
+typedef struct { uint32_t max_mismatches; uint64_t initial_rows; } bk_link_config;
+typedef struct { uint32_t cell0; uint16_t n; uint8_t strand, n_mm; uint8_t mm[24]; } bk_link_row;   /* 32 bytes */
+typedef struct { uint32_t site_a, site_b; uint32_t count[16]; } bk_link_pair;
+typedef struct { uint64_t records, placed, unplaced, discordant, n_pairs; uint32_t n_sites, max_dist; } bk_link_summary;
+int  bk_link_enable(bk_engine* e, const bk_link_config* cfg);
+int  bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uint32_t max_dist);
+int  bk_sample_download_linkage(bk_engine* e, bk_link_summary* summary, bk_link_pair* pairs, uint64_t cap);
+int  bk_sample_download_link_rows(bk_engine* e, bk_link_row* rows, uint64_t cap);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
