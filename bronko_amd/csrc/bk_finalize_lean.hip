@@ -25,6 +25,13 @@ namespace bk {
 constexpr int kLeanVBlock = 1024;
 constexpr uint32_t kLeanVq = 64;       // row positions q of the V plane per workgroup (6 rows each)
 constexpr uint32_t kLeanWin = 256;     // pileup positions of its vote table: 64 + v_span reference k-mers' cells and k - 1 behind, with slack
+constexpr uint32_t kLeanMaxSpan = 32;  // v_span at most (finalize_lean_ok): at least two rows per wave
+constexpr uint32_t kLeanTouchWords = kLeanVq * kVRowsPerPos / 32;
+// LDS of one workgroup, static (the vote table, the tallies, the touch words; the compiler may pad a little) and dynamic: two
+// workgroups must fit a CU's 160 KB -- finalize_vbin_kernel is built for eight waves per SIMD, which is two of its workgroups
+constexpr size_t kLeanStaticLds = (2u * 8u * kLeanWin + 5u + kLeanTouchWords + 1u) * sizeof(unsigned int);
+constexpr size_t lean_dynamic_lds(uint32_t v_span) { return (size_t)kLeanVq * kVRowsPerPos * ((size_t)v_span + 1u) * sizeof(unsigned int); }
+static_assert(kLeanStaticLds + 64u + lean_dynamic_lds(kLeanMaxSpan) <= 80u * 1024u, "two finalize_vbin workgroups no longer fit one CU's LDS");
 
 // one vote into the dense table (or, out of its reach, straight to the pileup)
 __device__ __forceinline__ void lean_vote(unsigned int* cnt, unsigned int* mxv, uint32_t span, uint32_t p0, const FinalizeArgs& a, uint32_t cell,
@@ -63,11 +70,16 @@ __device__ __forceinline__ void lean_flush(const unsigned int* cnt, const unsign
 // adds the bin's items of every scan workgroup up in LDS, as bin_count_kernel does, and never stores them; a row that Level 2
 // wrote to meanwhile (f_touch: a bit per row) is read from the plane as well, zeroed, its bit cleared.  28 MB of stores, 27 MB of
 // loads and 25 MB of zeroing per 1 M-read sample of SARS-CoV-2 become 6 MB of item loads.
+//
+// Two workgroups per CU.  A workgroup puts four waves on each SIMD, a second one needs eight, and it was the scalar registers, not
+// the vector ones or the LDS, that allowed only seven: amdgpu_waves_per_eu holds the compiler to the 96 scalar registers that eight
+// waves leave each (tests/test_finalize_lean_resources.py pins what it reports).  The 467 workgroups of a SARS-CoV-2 sample are then
+// one round on 256 CUs instead of two (DESIGN section 4, K2 lean).
 template <bool FUSED>
-__global__ __launch_bounds__(kLeanVBlock) void finalize_vbin_kernel(FinalizeArgs a) {
+__global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void finalize_vbin_kernel(FinalizeArgs a) {
     __shared__ unsigned int cnt[8 * kLeanWin], mxv[8 * kLeanWin];
     __shared__ uint32_t lstats[3 + 2];
-    __shared__ unsigned int tmask[kLeanVq * kVRowsPerPos / 32 + 1];   // FUSED: the touch bits of the workgroup's 384 rows; [12]: all rows (the scan's item_direct wrote to the plane)
+    __shared__ unsigned int tmask[kLeanTouchWords + 1];   // FUSED: the touch bits of the workgroup's 384 rows; [12]: all rows (the scan's item_direct wrote to the plane)
     extern __shared__ __attribute__((aligned(16))) unsigned int acc[];   // FUSED: [384 * (v_span + 1)] the bin's counters (differences), from the items
     const IndexView& ix = a.ix;
     const int k = ix.k;
@@ -93,10 +105,10 @@ __global__ __launch_bounds__(kLeanVBlock) void finalize_vbin_kernel(FinalizeArgs
         uint4 v0 = make_uint4(0u, 0u, 0u, 0u);
         if (mine) { hdr0 = a.f_tab[(size_t)bin * G + wg0]; v0 = reinterpret_cast<const uint4*>(bin_items + (size_t)wg0 * cap)[un0]; }
         const unsigned long long ov_all = a.f_ov_n[a.f_ov_par];
-        if (threadIdx.x <= kLeanVq * kVRowsPerPos / 32) {
-            unsigned int* tw = a.f_touch + (size_t)blockIdx.x * (kLeanVq * kVRowsPerPos / 32) + threadIdx.x;
+        if (threadIdx.x <= kLeanTouchWords) {
+            unsigned int* tw = a.f_touch + (size_t)blockIdx.x * kLeanTouchWords + threadIdx.x;
             unsigned int m = 0u;
-            if (threadIdx.x < kLeanVq * kVRowsPerPos / 32) { m = *tw; if (m) *tw = 0u; }
+            if (threadIdx.x < kLeanTouchWords) { m = *tw; if (m) *tw = 0u; }
             else m = ov_all > (unsigned long long)a.f_ov_cap ? 1u : 0u;   // past the list's end the scan added to the plane itself: every row is read
             tmask[threadIdx.x] = m;
         }
@@ -160,7 +172,7 @@ __global__ __launch_bounds__(kLeanVBlock) void finalize_vbin_kernel(FinalizeArgs
             // the items' sum (a difference: sign-extended, the plane's arithmetic wraps modulo 2^64) + what Level 2 left in the plane
             const uint32_t gg = in_row ? g : 0u;
             n = in_row ? (unsigned long long)(long long)(int32_t)acc[gg * rl + oo] : 0ull;
-            if (in_row && (tmask[kLeanVq * kVRowsPerPos / 32] || ((tmask[gg >> 5] >> (gg & 31u)) & 1u))) {
+            if (in_row && (tmask[kLeanTouchWords] || ((tmask[gg >> 5] >> (gg & 31u)) & 1u))) {
                 const unsigned long long pv = vc[at];
                 if (pv) { n += pv; vc[at] = 0ull; }
             }
@@ -279,13 +291,13 @@ __global__ __launch_bounds__(kLeanVBlock) void finalize_vbin_kernel(FinalizeArgs
 
 bool finalize_lean_ok(const FinalizeArgs& a) {
     return !a.no_lean && a.lean_e_list && a.lean_n_list && !a.ix.slot_files && a.mode == 0 && !a.v_list && !a.p_list && !a.e_list && !a.ktab_keys && a.ix.n_prows == 0 && a.ix.n_u == a.ix.n_full &&
-           a.ix.n_full > 0 && a.ix.n_files == 1 && a.ix.dirty_ans && a.ix.W > 1 && a.ix.v_span > 0 && a.ix.v_span <= 32 && a.partials && a.cs < (1ull << 32) &&
+           a.ix.n_full > 0 && a.ix.n_files == 1 && a.ix.dirty_ans && a.ix.W > 1 && a.ix.v_span > 0 && a.ix.v_span <= (int)kLeanMaxSpan && a.partials && a.cs < (1ull << 32) &&
            a.elem_lo == 0 && a.elem_hi >= a.ix.v_off + v_plane_len(a.ix.n_full, a.ix.v_span, 0);
 }
 unsigned launch_finalize_lean_variant(const FinalizeArgs& a, hipStream_t stream) {
     const unsigned grid = (unsigned)((a.ix.n_full + (uint32_t)a.ix.v_span + kLeanVq - 1) / kLeanVq);
     if (a.f_items) {   // (the engine hands the items over only where a V bin is a workgroup's region: vq_log2 = 6, as many bins as workgroups)
-        const size_t lds = (size_t)kLeanVq * kVRowsPerPos * ((size_t)a.ix.v_span + 1u) * sizeof(unsigned int);
+        const size_t lds = lean_dynamic_lds((uint32_t)a.ix.v_span);   // (with kLeanStaticLds at most 80 KB, asserted above for every v_span finalize_lean_ok lets through)
         (void)raise_lds_limit(reinterpret_cast<const void*>(finalize_vbin_kernel<true>), lds + 20u * 1024u);
         hipLaunchKernelGGL(finalize_vbin_kernel<true>, dim3(grid), dim3(kLeanVBlock), lds, stream, a);
     } else {
