@@ -1,10 +1,9 @@
 // bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip) and link_scan_kernel
 // (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
 //
-// Every function is a template over the kernel's argument struct (IndelArgs, LinkArgs of bk_kernels.h); it reads the members both
-// have under the same names: the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb, log2p, n_full), one bit per id
-// that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the runs of letters that are
-// not ACGT (nruns, n_nruns) -- the engine's AnchorTables hold the last three.  Device code only.
+// What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
+// log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
+// runs of letters that are not ACGT (nruns, n_nruns) -- the engine's AnchorTables hold the last three.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,8 +37,7 @@ __device__ __forceinline__ uint32_t mismatches(const uint32_t* __restrict__ w, u
 }
 
 // the k-mer at offset o of a record as an anchor: its cell and strand.  o + k <= the record's length.
-template <class Args>
-__device__ __forceinline__ bool anchor_at(const Args& a, const uint32_t* __restrict__ w, uint32_t o, uint32_t* cell, bool* against) {
+__device__ __forceinline__ bool anchor_at(const AnchorIndex& a, const uint32_t* __restrict__ w, uint32_t o, uint32_t* cell, bool* against) {
     const uint32_t k = (uint32_t)a.k;
     const uint32_t w0 = o >> 4, sh = 2u * (o & 15u), wl = (o + k - 1u) >> 4;
     unsigned long long x = w[w0];
@@ -61,8 +59,7 @@ __device__ __forceinline__ bool anchor_at(const Args& a, const uint32_t* __restr
     return true;
 }
 
-template <class Args>
-__device__ __forceinline__ uint32_t seq_of(const Args& a, uint32_t cell) {
+__device__ __forceinline__ uint32_t seq_of(const AnchorIndex& a, uint32_t cell) {
     uint32_t lo = 0, hi = a.n_seqs;
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -72,8 +69,7 @@ __device__ __forceinline__ uint32_t seq_of(const Args& a, uint32_t cell) {
 }
 
 // the first of the runs of letters that are not ACGT (ascending, disjoint) that ends behind cell `lo`; n_nruns: none does
-template <class Args>
-__device__ __forceinline__ uint32_t first_run_behind(const Args& a, int32_t lo) {
+__device__ __forceinline__ uint32_t first_run_behind(const AnchorIndex& a, int32_t lo) {
     uint32_t b = 0, e = a.n_nruns;
     while (b < e) {
         const uint32_t mid = (b + e) >> 1;
@@ -90,8 +86,7 @@ struct Anchors {
 };
 // the first anchor k-mer from each end of a record of n >= 2k bases (offsets 0, 8, 16, 24 from either end), both on one strand,
 // a + k <= b
-template <class Args>
-__device__ __forceinline__ bool anchors_of(const Args& a, const uint32_t* __restrict__ w, int32_t n, Anchors& out) {
+__device__ __forceinline__ bool anchors_of(const AnchorIndex& a, const uint32_t* __restrict__ w, int32_t n, Anchors& out) {
     const int32_t k = a.k;
     int32_t f_off = -1, b_off = -1;
     uint32_t f_cell = 0, b_cell = 0;
@@ -108,8 +103,7 @@ __device__ __forceinline__ bool anchors_of(const Args& a, const uint32_t* __rest
     return out.pa + k <= out.pb;
 }
 // both anchors in one sequence, the cells [lo, hi) inside it and holding ACGT only
-template <class Args>
-__device__ __forceinline__ bool cells_placed(const Args& a, uint32_t ca, uint32_t cb, int32_t lo, int32_t hi) {
+__device__ __forceinline__ bool cells_placed(const AnchorIndex& a, uint32_t ca, uint32_t cb, int32_t lo, int32_t hi) {
     const uint32_t s = seq_of(a, ca);
     if (seq_of(a, cb) != s) return false;
     if (lo < (int32_t)a.seq_lo[s] || hi > (int32_t)a.seq_lo[s + 1]) return false;

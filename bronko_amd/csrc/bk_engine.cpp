@@ -1,8 +1,10 @@
 // bk_engine.cpp -- host side of the C ABI declared in include/bronko_hip.h: the engine's life and the sample path.
 //
 // Owns the HBM buffers of a sample (counter planes, pileups) and sequences the kernels of bk_kernels.hip on one HIP stream, from the
-// scan of a batch of records (push_device) to the calls; the index tables an engine reads are built by bk_index_tables.cpp and shared
-// with its forks; how a caller's reads become records (the bk_push_reads_* entry points, K0, the trimming stage) is bk_ingest.cpp.
+// scan of a batch of records (push_device) to the pileup's download; the index tables an engine reads are built by bk_index_tables.cpp
+// and shared with its forks; how a caller's reads become records (the bk_push_reads_* entry points, K0, the trimming stage) is
+// bk_ingest.cpp; the passes that ride behind every scan (k-mer dump, indels, linkage) are bk_riders.cpp, the reports made of the pileup
+// (calls, consensus, regions) bk_reports.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -245,29 +247,15 @@ uint64_t bk_counter_len(const bk_engine* e) { return e ? e->ix->plane_len : 0; }
 int bk_can_shard(const bk_engine* e) { return e && !e->sparse ? 1 : 0; }
 
 // a sample starts from an empty table (the capacity the last one grew to stays)
-static int clear_table(bk_engine* e, GrowTable& t) {
-    if (!t.old.empty()) {   // tables the previous sample outgrew
+int GrowTable::clear(bk_engine* e) {
+    if (!old.empty()) {   // tables the previous sample outgrew
         BK_HIP(hipStreamSynchronize(e->stream));
-        for (auto& o : t.old) { (void)hipFree(o.first); (void)hipFree(o.second); }
-        t.old.clear();
+        for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); }
+        old.clear();
     }
-    BK_HIP(hipMemsetAsync(t.keys.p, 0xff, t.keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(t.cnt.p, 0, t.cnt.n * sizeof(unsigned int), e->stream));
-    t.fill_known = 0; t.fill_unknown_upper = 0; t.fill_pending = false;
-    return BK_OK;
-}
-
-// the row stores that bk_link_enable's sample outgrew: each is freed once the stream has passed the copy out of it (`wait`: now)
-static int link_free_old(Linkage& d, bool wait) {
-    std::vector<std::pair<uint4*, Event>> keep;
-    hipError_t err = hipSuccess;
-    for (auto& o : d.old) {
-        if (wait && err == hipSuccess) err = hipEventSynchronize(o.second);
-        if (err == hipSuccess && (wait || hipEventQuery(o.second) == hipSuccess)) (void)hipFree(o.first);
-        else keep.emplace_back(o.first, std::move(o.second));
-    }
-    d.old.swap(keep);
-    BK_HIP(err);
+    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(cnt.p, 0, cnt.n * sizeof(unsigned int), e->stream));
+    fill_known = 0; fill_unknown_upper = 0; fill_pending = false;
     return BK_OK;
 }
 
@@ -282,30 +270,12 @@ int bk_sample_begin(bk_engine* e) {
     bk::launch_zero_small(e->stats.p, e->stats.n, e->kstats.p, e->kstats.n, e->ktab_out.p, e->ktab_out.n, e->present.p, e->present.n,
                           e->n_deferred.p, e->n_deferred.n, e->pileup.p, e->gather_mode ? 0 : e->pileup.n, e->stream);
     if (sel_rows) bk::launch_zero_genome_rows(e->pileup.p, (size_t)e->ix->total_cells * 4, e->ix->file_cell_lo_d.p, e->ix->n_files, (uint32_t)e->ix->total_cells, e->last_sel.p, e->stream);
-    if (e->ktab.keys.p) { if (int rc = clear_table(e, e->ktab)) return rc; }
-    if (e->dump) {
-        if (int rc = clear_table(e, e->dump->t)) return rc;
-        BK_HIP(hipMemsetAsync(e->dump->out.p, 0, e->dump->out.n * sizeof(unsigned long long), e->stream));
-        e->dump->upper[0] = e->dump->upper[1] = 0; e->dump->in_sample = true; e->dump->finalized_mates = 0;
-    }
-    if (e->indels) {   // an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
-        Indels& d = *e->indels;
-        BK_HIP(hipMemsetAsync(d.key0.p, 0xff, d.key0.n * sizeof(unsigned long long), e->stream));
-        BK_HIP(hipMemsetAsync(d.key1.p, 0xff, d.key1.n * sizeof(unsigned long long), e->stream));
-        BK_HIP(hipMemsetAsync(d.counts.p, 0, d.counts.n * sizeof(unsigned int), e->stream));
-        BK_HIP(hipMemsetAsync(d.span.p, 0, d.span.n * sizeof(unsigned int), e->stream));
-        BK_HIP(hipMemsetAsync(d.tallies.p, 0, d.tallies.n * sizeof(unsigned long long), e->stream));
-        d.in_sample = true; d.summed = false; d.made = false;
-    }
-    if (e->linkage) {  // an empty row store, zero tallies
-        Linkage& d = *e->linkage;
-        if (int rc = link_free_old(d, true)) return rc;
-        BK_HIP(hipMemsetAsync(d.tallies.p, 0, d.tallies.n * sizeof(unsigned long long), e->stream));
-        d.rows_upper = 0; d.in_sample = true; d.made = false; d.n_sites = 0; d.n_pairs = 0;
-    }
-    TrimStage* const trim_stages[] = {e->primers.get(), e->adapters.get()};
-    for (TrimStage* t : trim_stages)
-        if (t) { BK_HIP(hipMemsetAsync(t->stats.p, 0, t->stats.n * sizeof(unsigned long long), e->stream)); t->in_sample = true; }
+    if (e->ktab.keys.p) { if (int rc = e->ktab.clear(e)) return rc; }
+    if (e->dump) { if (int rc = e->dump->begin_sample(e)) return rc; }
+    if (e->indels) { if (int rc = e->indels->begin_sample(e)) return rc; }
+    if (e->linkage) { if (int rc = e->linkage->begin_sample(e)) return rc; }
+    if (e->primers) { if (int rc = e->primers->begin_sample(e)) return rc; }
+    if (e->adapters) { if (int rc = e->adapters->begin_sample(e)) return rc; }
     e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0; e->called = false; e->cons_made = false; e->regions_made = false;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
@@ -349,125 +319,35 @@ int MatePlane::zero_if_stale(bk_engine* e) {
 // batch of at most `upper` k-mers is pushed, the keys it holds (read back from the device tallies at out[8 ..] after every push;
 // the engine only waits for that reading when the bound says the batch might not fit) plus `upper` must fit, else the table is
 // rehashed into one four times larger.
-static int ensure_table_room(bk_engine* e, GrowTable& t, unsigned long long* out, uint64_t upper) {
-    if (!t.keys.p) return BK_OK;
-    const uint64_t cap = 1ull << t.log2;
-    if (t.fill_known + t.fill_unknown_upper + upper > cap / 2) {
-        if (t.fill_pending) { BK_HIP(hipEventSynchronize(t.fill_ev)); t.read_fill(); }
-        uint32_t nl = t.log2;
-        while (nl < 31 && t.fill_known + t.fill_unknown_upper + upper > (1ull << nl) / 2) nl += 2;
+int GrowTable::ensure_room(bk_engine* e, unsigned long long* out, uint64_t upper) {
+    if (!keys.p) return BK_OK;
+    const uint64_t cap = 1ull << log2;
+    if (fill_known + fill_unknown_upper + upper > cap / 2) {
+        if (fill_pending) { BK_HIP(hipEventSynchronize(fill_ev)); read_fill(); }
+        uint32_t nl = log2;
+        while (nl < 31 && fill_known + fill_unknown_upper + upper > (1ull << nl) / 2) nl += 2;
         if (nl > 31) nl = 31;
-        if (nl != t.log2) {
+        if (nl != log2) {
             unsigned long long* nk = nullptr; unsigned int* nc = nullptr;
             BK_HIP(hipMalloc(reinterpret_cast<void**>(&nk), ((size_t)1 << nl) * sizeof(unsigned long long)));
             BK_HIP(hipMalloc(reinterpret_cast<void**>(&nc), ((size_t)1 << nl) * sizeof(unsigned int)));
             BK_HIP(hipMemsetAsync(nk, 0xff, ((size_t)1 << nl) * sizeof(unsigned long long), e->stream));
             BK_HIP(hipMemsetAsync(nc, 0, ((size_t)1 << nl) * sizeof(unsigned int), e->stream));
-            bk::launch_ktab_rehash(t.keys.p, t.cnt.p, t.log2, nk, nc, nl, out + 4, e->stream);
-            t.old.emplace_back(t.keys.p, t.cnt.p);   // still read by the rehash in flight
-            t.keys.p = nk; t.keys.n = (size_t)1 << nl;
-            t.cnt.p = nc; t.cnt.n = (size_t)1 << nl;
-            t.log2 = nl;
+            bk::launch_ktab_rehash(keys.p, cnt.p, log2, nk, nc, nl, out + 4, e->stream);
+            old.emplace_back(keys.p, cnt.p);   // still read by the rehash in flight
+            keys.p = nk; keys.n = (size_t)1 << nl;
+            cnt.p = nc; cnt.n = (size_t)1 << nl;
+            log2 = nl;
         }
     }
-    t.fill_unknown_upper += upper;
+    fill_unknown_upper += upper;
     return BK_OK;
 }
-static int note_table_fill(bk_engine* e, GrowTable& t, const unsigned long long* out) {   // after a push: a fresh copy of the tallies
-    if (!t.keys.p) return BK_OK;
-    BK_HIP(hipMemcpyAsync(t.h_fill.p, out + 8, bk::ktab_fill_words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipEventRecord(t.fill_ev, e->stream));
-    t.fill_pending = true;
-    return BK_OK;
-}
-static int ensure_ktab_room(bk_engine* e, uint64_t upper) { return ensure_table_room(e, e->ktab, e->ktab_out.p, upper); }
-static int note_ktab_fill(bk_engine* e) { return note_table_fill(e, e->ktab, e->ktab_out.p); }
-
-// bk_kmer_dump_enable: every k-mer of the batch into the count table, on the engine stream behind the scan that read the same records
-// (a staging slot is reused only after the stream has passed both)
-static int dump_push(bk_engine* e, int mate, const Records& r, uint64_t upper) {
-    KmerDump& d = *e->dump;
-    if (int rc = ensure_table_room(e, d.t, d.out.p, upper)) return rc;
-    d.upper[mate] += upper;
-    bk::launch_kmer_dump_count(r.words, r.lens, r.n, r.n_dev, r.stride_words, e->ix->k, (uint32_t)mate, d.t.keys.p, d.t.cnt.p, d.t.log2, d.out.p + 4,
-                               e->ix->n_cus, e->stream);
-    BK_HIP(hipGetLastError());
-    return note_table_fill(e, d.t, d.out.p);
-}
-
-// bk_indels_enable: the records' anchors, spans and events (indel_scan_kernel), on the engine stream behind the scan of the same records
-static bk::IndelArgs indel_args(const bk_engine* e) {
-    const IndexTables& ix = *e->ix;
-    const Indels& d = *e->indels;
-    bk::IndelArgs a{};
-    a.kmer_pos = ix.kmer_pos.p; a.pilots = ix.pilots.p; a.m = ix.m; a.log2nb = ix.log2nb; a.log2p = ix.log2p; a.n_full = ix.n_full;
-    a.unique_bits = d.anchors->unique_bits.p;
-    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words(); a.rc_words = ix.rc_words.p + bk::scan_ref_pad_words();
-    a.total_cells = (uint32_t)ix.total_cells; a.k = ix.k;
-    a.seq_lo = d.anchors->seq_lo.p; a.n_seqs = (uint32_t)(d.anchors->seq_lo.n - 1);
-    a.nruns = d.anchors->nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
-    a.max_len = d.cfg.max_len; a.max_mismatches = d.cfg.max_mismatches;
-    a.key0 = d.key0.p; a.key1 = d.key1.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
-    a.span = d.span.p; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n;
-    return a;
-}
-static int indel_push(bk_engine* e, const Records& r) {
-    if (!e->indels->in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_indels_enable: a batch of 2^31 records or more");
-    bk::IndelArgs a = indel_args(e);
-    a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.n_records_dev = r.n_dev; a.stride_words = r.stride_words;
-    bk::launch_indel_scan(a, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
-
-// bk_link_enable: a row per placed record (link_scan_kernel), on the engine stream behind the scan of the same records
-static bk::LinkArgs link_args(const bk_engine* e) {
-    const IndexTables& ix = *e->ix;
-    const Linkage& d = *e->linkage;
-    bk::LinkArgs a{};
-    a.kmer_pos = ix.kmer_pos.p; a.pilots = ix.pilots.p; a.m = ix.m; a.log2nb = ix.log2nb; a.log2p = ix.log2p; a.n_full = ix.n_full;
-    a.unique_bits = d.anchors->unique_bits.p;
-    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words(); a.rc_words = ix.rc_words.p + bk::scan_ref_pad_words();
-    a.total_cells = (uint32_t)ix.total_cells; a.k = ix.k;
-    a.seq_lo = d.anchors->seq_lo.p; a.n_seqs = (uint32_t)(d.anchors->seq_lo.n - 1);
-    a.nruns = d.anchors->nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
-    a.max_mismatches = d.cfg.max_mismatches;
-    a.rows = d.rows.p; a.row_cap = d.rows.n / 2;
-    a.tallies = d.tallies.p;
-    a.sites = d.sites.p; a.pair_lo = d.pair_lo.p; a.n_sites = d.n_sites; a.max_dist = d.max_dist; a.n_pairs = d.n_pairs;
-    a.counts = d.counts.p;
-    return a;
-}
-static int link_push(bk_engine* e, const Records& r) {
-    Linkage& d = *e->linkage;
-    if (!d.in_sample || r.n == 0) return BK_OK;      // (enabled after this sample began: it has no rows)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_link_enable: a batch of 2^31 records or more");
-    const uint64_t need = d.rows_upper + r.n;       // (only the device knows how many of the records are placed: room for all of them)
-    if (need >= (1ull << 32)) return fail(BK_ERR_UNSUPPORTED, "bk_link_enable: a sample of 2^32 records or more (%llu)", (unsigned long long)need);
-    const uint64_t cap = d.rows.n / 2;
-    if (int rc = link_free_old(d, false)) return rc;
-    if (need > cap) {   // a larger store: allocate, copy behind the scans so far; the old one stays until the stream has passed the copy
-        const uint64_t ncap = std::min<uint64_t>(std::max<uint64_t>(need, 2 * cap), 1ull << 32);
-        uint4* np = nullptr;
-        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&np), (size_t)ncap * 2 * sizeof(uint4));
-        if (err != hipSuccess) return fail(BK_ERR_HIP, "bk_link_enable: no memory for a row store of %llu rows: %s", (unsigned long long)ncap, hipGetErrorString(err));
-        const uint64_t filled = std::min<uint64_t>(d.rows_upper, cap);
-        if (filled) {
-            const hipError_t ce = hipMemcpyAsync(np, d.rows.p, (size_t)filled * 2 * sizeof(uint4), hipMemcpyDeviceToDevice, e->stream);
-            if (ce != hipSuccess) { (void)hipFree(np); return fail(BK_ERR_HIP, "bk_link_enable: copying the row store failed: %s", hipGetErrorString(ce)); }
-        }
-        Event passed;                                // behind the copy: the old store is free once the stream is here
-        hipError_t ee = passed.create();
-        if (ee == hipSuccess) ee = hipEventRecord(passed, e->stream);
-        if (ee != hipSuccess) { (void)hipStreamSynchronize(e->stream); (void)hipFree(np); return fail(BK_ERR_HIP, "bk_link_enable: hipEventRecord failed: %s", hipGetErrorString(ee)); }
-        d.old.emplace_back(d.rows.p, std::move(passed));
-        d.rows.p = np; d.rows.n = (size_t)ncap * 2;
-    }
-    d.rows_upper = need;
-    bk::LinkArgs a = link_args(e);
-    a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.n_records_dev = r.n_dev; a.stride_words = r.stride_words;
-    bk::launch_link_scan(a, e->ix->n_cus, e->stream);
+int GrowTable::note_fill(bk_engine* e, const unsigned long long* out) {   // after a push: a fresh copy of the tallies
+    if (!keys.p) return BK_OK;
+    BK_HIP(hipMemcpyAsync(h_fill.p, out + 8, bk::ktab_fill_words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipEventRecord(fill_ev, e->stream));
+    fill_pending = true;
     return BK_OK;
 }
 
@@ -550,7 +430,7 @@ static int l2_stats_report(bk_engine*) { return BK_OK; }
 #endif
 
 // The scan's arguments that every launch of a push shares.  Built for each push: a rehash of the statistics table
-// (ensure_table_room) moves ktab.keys and raises ktab.log2 in the middle of a sample.
+// (GrowTable::ensure_room) moves ktab.keys and raises ktab.log2 in the middle of a sample.
 static bk::ScanArgs scan_args(const bk_engine* e, int mate, const Records& r) {
     const IndexTables& ix = *e->ix;
     const MatePlane& pl = e->mate[mate];
@@ -682,8 +562,8 @@ int push_device(bk_engine* e, int mate, const Records& r) {
     MatePlane& pl = e->mate[mate];
     if (int rc = pl.zero_if_stale(e)) return rc;
     const uint64_t n = r.n, upper = r.kmers_upper ? r.kmers_upper : n * (uint64_t)r.stride_words * 16;
-    if (int rc = ensure_ktab_room(e, upper)) return rc;
-    if (e->dump) { if (int rc = dump_push(e, mate, r, upper)) return rc; }
+    if (int rc = e->ktab.ensure_room(e, e->ktab_out.p, upper)) return rc;
+    if (e->dump) { if (int rc = e->dump->push(e, mate, r, upper)) return rc; }
     pl.written();
     if (int rc = l2_stats_arm(e)) return rc;
     bk::ScanArgs a = scan_args(e, mate, r);
@@ -714,11 +594,11 @@ int push_device(bk_engine* e, int mate, const Records& r) {
             if (int rc = level2_and_fold(e, a, mate, grid, ride ? &ride_b : nullptr)) return rc;
         }
     }
-    if (e->indels) { if (int rc = indel_push(e, r)) return rc; }
-    if (e->linkage) { if (int rc = link_push(e, r)) return rc; }
+    if (e->indels) { if (int rc = e->indels->push(e, r)) return rc; }
+    if (e->linkage) { if (int rc = e->linkage->push(e, r)) return rc; }
     BK_HIP(hipGetLastError());
     if (!r.n_dev) pl.pushed_records += n;
-    return note_ktab_fill(e);
+    return e->ktab.note_fill(e, e->ktab_out.p);
 }
 extern "C" {
 
@@ -885,51 +765,11 @@ static int finalize_part(bk_engine* e, int n_mates, uint64_t elem_lo, uint64_t e
     return l2_stats_report(e);
 }
 
-// bk_kmer_dump_enable, at the end of a whole-sample finalize (asynchronous, so that samples in flight never wait between their reads
-// and their results): per mate file, the entries with ci <= count <= cx as (k-mer, min(count, cs)), padded with ~0 keys up to a
-// bound on the mate file's distinct keys (the sort's length must be known on the host), sorted by k-mer -- the padding sorts last.
-static int dump_finalize(bk_engine* e, int n_mates) {
-    KmerDump& d = *e->dump;
-    if (!d.in_sample) return BK_OK;   // (enabled after this sample began: nothing was counted)
-    bk_engine::Span sp(e, 1);
-    // bounds on the keys in the table: the tallies of the last push when their copy has arrived (not waited for), else what the
-    // growth rule knows; the table's load stays below one half; and a mate file holds no more distinct k-mers than it was pushed
-    if (d.t.fill_pending && hipEventQuery(d.t.fill_ev) == hipSuccess) d.t.read_fill();
-    const uint64_t keys_upper = std::min<uint64_t>((1ull << d.t.log2) / 2, d.t.fill_known + d.t.fill_unknown_upper);
-    uint64_t bound[2] = {0, 0}, most = 1;
-    size_t tmp_bytes = 0;
-    for (int m = 0; m < n_mates; m++) {
-        bound[m] = std::max<uint64_t>(1, std::min<uint64_t>(keys_upper, d.upper[m]));
-        most = std::max(most, bound[m]);
-        size_t b = 0;
-        BK_HIP(bk::kmer_dump_sort(nullptr, b, d.sel_keys.p, d.keys[m].p, d.sel_cnt.p, d.cnt[m].p, bound[m], e->ix->k, e->stream));
-        tmp_bytes = std::max(tmp_bytes, b);
-    }
-    // every buffer is sized before the first launch (a buffer that grows is freed and allocated again)
-    if (d.sel_keys.n < most) { BK_HIP(d.sel_keys.alloc(most)); BK_HIP(d.sel_cnt.alloc(most)); }
-    for (int m = 0; m < n_mates; m++)
-        if (d.keys[m].n < bound[m]) { BK_HIP(d.keys[m].alloc(bound[m])); BK_HIP(d.cnt[m].alloc(bound[m])); }
-    if (d.sort_tmp.n < tmp_bytes) BK_HIP(d.sort_tmp.alloc(tmp_bytes));
-    for (int m = 0; m < n_mates; m++) {
-        BK_HIP(hipMemsetAsync(d.sel_keys.p, 0xff, bound[m] * sizeof(unsigned long long), e->stream));
-        bk::launch_kmer_dump_select(d.t.keys.p, d.t.cnt.p, d.t.log2, (uint32_t)m, e->params.ci, e->params.cs, e->params.cx, d.sel_keys.p, d.sel_cnt.p,
-                                    bound[m], d.out.p + 2 * m, e->stream);
-        size_t b = d.sort_tmp.n;
-        BK_HIP(bk::kmer_dump_sort(d.sort_tmp.p, b, d.sel_keys.p, d.keys[m].p, d.sel_cnt.p, d.cnt[m].p, bound[m], e->ix->k, e->stream));
-        d.n_sorted[m] = bound[m];
-    }
-    BK_HIP(hipGetLastError());
-    if (test_env("BK_DUMP_STATS"))   // measurement aid (testing build): the table's capacity and the sort's lengths
-        fprintf(stderr, "[bk] k-mer dump: table 2^%u slots, sorted %llu + %llu entries\n", d.t.log2, (unsigned long long)bound[0], (unsigned long long)bound[1]);
-    d.finalized_mates = n_mates;
-    return BK_OK;
-}
-
 int bk_sample_finalize(bk_engine* e, int n_mates) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     if (e->mate[0].reduced_shards > 1 || e->mate[1].reduced_shards > 1) return fail(BK_ERR_STATE, "this sample's planes went through bk_shard_transport: finalize it with bk_sample_finalize_shard");
     int rc = finalize_part(e, n_mates, 0, e->ix->plane_len);
-    if (rc == BK_OK && e->dump) rc = dump_finalize(e, n_mates);
+    if (rc == BK_OK && e->dump) rc = e->dump->finalize(e, n_mates);
     return rc;
 }
 
@@ -967,8 +807,7 @@ int bk_kmer_table_partition(bk_engine* e, int n_parts, void** d_keys, void** d_c
     BK_HIP(hipMemsetAsync(e->xchg_cursors.p, 0, bk::kMaxShards * sizeof(unsigned long long), e->stream));
     bk::launch_ktab_count_parts(e->ktab.keys.p, e->ktab.log2, (uint32_t)n_parts, e->xchg_cursors.p, e->stream);
     unsigned long long counts[bk::kMaxShards];
-    BK_HIP(hipMemcpyAsync(counts, e->xchg_cursors.p, (size_t)n_parts * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
+    if (int rc = download(e, counts, e->xchg_cursors.p, (size_t)n_parts)) return rc;
     unsigned long long first[bk::kMaxShards];
     part_off[0] = 0;
     for (int r = 0; r < n_parts; r++) { first[r] = part_off[r]; part_off[r + 1] = part_off[r] + counts[r]; }
@@ -996,12 +835,12 @@ int bk_kmer_table_replace(bk_engine* e, const void* d_keys, const void* d_counts
     BK_HIP(hipMemsetAsync(e->ktab_out.p + 8, 0, bk::ktab_fill_words() * sizeof(unsigned long long), e->stream));
     if (e->ktab.fill_pending) { BK_HIP(hipEventSynchronize(e->ktab.fill_ev)); e->ktab.fill_pending = false; }
     e->ktab.fill_known = 0; e->ktab.fill_unknown_upper = 0;
-    if (int rc = ensure_ktab_room(e, n)) return rc;
+    if (int rc = e->ktab.ensure_room(e, e->ktab_out.p, n)) return rc;
     bk::launch_ktab_import(static_cast<const unsigned long long*>(d_keys), static_cast<const unsigned int*>(d_counts), n, e->ktab.keys.p, e->ktab.cnt.p,
                            e->ktab.log2, e->ktab_out.p + 4, e->stream);
     BK_HIP(hipGetLastError());
     e->ktab_exchanged = true;
-    return note_ktab_fill(e);
+    return e->ktab.note_fill(e, e->ktab_out.p);
 }
 
 int bk_shard_sums_device_ptr(bk_engine* e, void** d_ptr, uint64_t* len) {
@@ -1166,497 +1005,6 @@ int bk_sample_finish(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t* r
     int rc = bk_sample_finalize(e, n_mates);
     if (rc != BK_OK) return rc;
     return bk_sample_download(e, n_mates, fwd_depth, rev_depth, fwd_nk, rev_nk, stats, present, kmer_stats);
-}
-
-// ---- the sample's k-mer count table (bk_kmer_dump.hip) --------------------------------------------------------------
-int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (table_log2 != 0 && (table_log2 < 10 || table_log2 > 31)) return fail(BK_ERR_INVALID, "table_log2 must be 0 or 10..31");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_kmer_dump_enable comes between samples");
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still read the table being replaced)
-    e->dump.reset();
-    if (table_log2 == 0) return BK_OK;
-    std::unique_ptr<KmerDump> d(new KmerDump());
-    BK_HIP(d->t.keys.alloc((size_t)1 << table_log2));
-    BK_HIP(d->t.cnt.alloc((size_t)1 << table_log2));
-    d->t.log2 = table_log2;
-    BK_HIP(d->t.h_fill.grow(bk::ktab_fill_words())); BK_HIP(d->t.fill_ev.create());
-    BK_HIP(d->out.alloc(8 + bk::ktab_fill_words()));
-    BK_HIP(hipMemset(d->out.p, 0, d->out.n * sizeof(unsigned long long)));
-    e->dump = std::move(d);
-    return BK_OK;
-}
-
-static int dump_results(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct) {
-    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
-    if (!e->dump || !e->dump->in_sample) return fail(BK_ERR_STATE, "the k-mer dump was not enabled for this sample (bk_kmer_dump_enable before bk_sample_begin)");
-    if (e->in_sample) return fail(BK_ERR_STATE, "the k-mer dump is read after bk_sample_finalize");
-    if (mate >= e->dump->finalized_mates)
-        return fail(BK_ERR_STATE, "mate file %d of this sample was not finalized by bk_sample_finalize (a sharded finalize keeps no k-mer dump)", mate);
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long o[8];
-    BK_HIP(hipMemcpyAsync(o, e->dump->out.p, sizeof o, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    if (o[4] || o[2 * mate] > e->dump->n_sorted[mate]) { *n_kept = *n_distinct = UINT64_MAX; return BK_OK; }   // (only a table that could not grow past 2^31 slots)
-    *n_kept = o[2 * mate];
-    *n_distinct = o[2 * mate + 1];
-    return BK_OK;
-}
-
-int bk_kmer_dump_size(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct) {
-    if (!e || !n_kept || !n_distinct) return fail(BK_ERR_INVALID, "null argument");
-    return dump_results(e, mate, n_kept, n_distinct);
-}
-
-int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* counts, uint64_t cap) {
-    if (!e || ((!kmers || !counts) && cap)) return fail(BK_ERR_INVALID, "null argument");
-    uint64_t kept = 0, distinct = 0;
-    if (int rc = dump_results(e, mate, &kept, &distinct)) return rc;
-    if (kept == UINT64_MAX) return fail(BK_ERR_RANGE, "the k-mer count table overflowed at 2^31 slots: no dump for this sample");
-    const uint64_t n = std::min(cap, kept);
-    if (!n) return BK_OK;
-    std::vector<unsigned int> c32(n);
-    BK_HIP(hipMemcpyAsync(kmers, e->dump->keys[mate].p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipMemcpyAsync(c32.data(), e->dump->cnt[mate].p, n * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    for (uint64_t i = 0; i < n; i++) counts[i] = c32[i];
-    return BK_OK;
-}
-
-// ---- after the pileup, on the device (bk_caller.hip) -----------------------------------------------------------
-void bk_call_params_default(bk_call_params* p) {
-    if (!p) return;
-    p->k = 21;                          // consts.rs:3
-    p->no_end_filter = 0; p->no_strand_filter = 0; p->no_strand_balance_filter = 0;
-    p->min_af = 0.03;                   // consts.rs:8
-    p->strand_balance_ratio = 0.1;      // consts.rs:10
-    p->strand_odds_max = 6.0;           // cli.rs --strand_odds
-    p->variant_multiplier = 1.5;        // consts.rs:15
-    p->n_per_strand = 2; p->min_depth = 300; p->min_variant_depth = 3;
-}
-
-int bk_sample_call(bk_engine* e, int n_mates, const bk_call_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    const IndexTables& ix = *e->ix;
-    if (n_mates < 1 || n_mates > 2) return fail(BK_ERR_INVALID, "n_mates must be 1 or 2");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_call comes after bk_sample_finalize");
-    if (e->finalized_mates == 0) return fail(BK_ERR_STATE, "bk_sample_call: no sample has been finalized on this engine");
-    if (e->finalized_mates != n_mates) return fail(BK_ERR_STATE, "bk_sample_call(n_mates = %d): the sample was finalized with %d mate file(s)", n_mates, e->finalized_mates);
-    BK_HIP(hipSetDevice(e->device));
-    const uint64_t cap = std::max<uint64_t>(3 * ix.max_file_cells, 1);   // at most three alternative bases per position
-    if (!e->call_out.p) {
-        BK_HIP(e->call_noise.alloc((size_t)ix.total_cells));
-        const size_t mc = std::max<uint64_t>(ix.max_file_cells, 1);
-        BK_HIP(e->noise_maf.alloc(mc * 3));
-        BK_HIP(e->noise_tbl.alloc((mc + 64 * (size_t)std::max(ix.max_seqs_per_file, 1) + 64) * 10));
-        BK_HIP(e->noise_state.alloc(mc));
-        BK_HIP(e->noise_sums.alloc(mc * 2));
-        BK_HIP(e->noise_cnt.alloc(mc));
-        BK_HIP(e->call_records.alloc((size_t)cap));
-        BK_HIP(e->call_out.alloc(1));
-    }
-    bk::CallArgs a{};
-    a.prm = *p;
-    a.n_files = ix.n_files; a.n_mates = n_mates;
-    a.stats = e->stats.p; a.present = e->present.p;
-    a.genome_len = ix.genome_len.p; a.seq_first = ix.seq_first.p; a.n_seqs = ix.n_seqs_d.p; a.seq_cell = ix.seq_cell.p; a.seq_len = ix.seq_len_d.p;
-    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words();
-    a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
-    a.noise = e->call_noise.p; a.records = e->call_records.p; a.record_cap = cap; a.out = e->call_out.p;
-    a.noise_maf = e->noise_maf.p; a.noise_tbl = e->noise_tbl.p; a.noise_sums = e->noise_sums.p; a.noise_cnt = e->noise_cnt.p; a.noise_state = e->noise_state.p;
-    if (const char* ns = test_env("BK_NOISE_SERIAL")) a.noise_serial = atoi(ns);
-    bk_engine::Span sp(e, 1);
-    bk::launch_call(a, ix.max_seqs_per_file, ix.max_file_cells, e->stream);
-    BK_HIP(hipGetLastError());
-    e->called = true; e->cons_made = false; e->regions_made = false;   // (a consensus or a region report made before this call was of another selection)
-    return BK_OK;
-}
-
-int bk_sample_download_calls(bk_engine* e, bk_call_summary* summary, bk_call_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->call_out.p) return fail(BK_ERR_STATE, "bk_sample_download_calls comes after bk_sample_call");
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipMemcpyAsync(summary, e->call_out.p, sizeof *summary, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->n_records, cap), e->call_records.n);
-    if (n && records) {
-        BK_HIP(hipMemcpy(records, e->call_records.p, (size_t)n * sizeof(bk_call_record), hipMemcpyDeviceToHost));
-        std::sort(records, records + n, [](const bk_call_record& x, const bk_call_record& y) {
-            if (x.seq_id != y.seq_id) return x.seq_id < y.seq_id;
-            if (x.pos != y.pos) return x.pos < y.pos;
-            return x.alt_base < y.alt_base;
-        });
-    }
-    return BK_OK;
-}
-
-int bk_sample_download_noise(bk_engine* e, double* out, uint64_t cap, uint64_t* n) {
-    if (!e || !n) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->call_out.p) return fail(BK_ERR_STATE, "bk_sample_download_noise comes after bk_sample_call");
-    BK_HIP(hipSetDevice(e->device));
-    bk_call_summary summ;
-    BK_HIP(hipMemcpyAsync(&summ, e->call_out.p, sizeof summ, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    *n = 0;
-    if (summ.file_id < 0 || summ.file_id >= e->ix->n_files) return BK_OK;
-    const uint64_t lo = e->ix->file_cell_lo[(size_t)summ.file_id], hi = summ.file_id + 1 < e->ix->n_files ? e->ix->file_cell_lo[(size_t)summ.file_id + 1] : e->ix->total_cells;
-    *n = hi - lo;
-    if (out && cap) BK_HIP(hipMemcpy(out, e->call_noise.p + lo, (size_t)std::min<uint64_t>(cap, hi - lo) * sizeof(double), hipMemcpyDeviceToHost));
-    return BK_OK;
-}
-
-// ---- per-sample consensus (consensus_kernel, bk_caller.hip) ------------------------------------------------------
-void bk_consensus_params_default(bk_consensus_params* p) {
-    if (!p) return;
-    p->min_depth = 10; p->min_freq = 0.5;
-}
-
-int bk_sample_consensus(bk_engine* e, const bk_consensus_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_depth < 1) return fail(BK_ERR_INVALID, "bk_sample_consensus: min_depth must be at least 1, got %llu", (unsigned long long)p->min_depth);
-    if (!(p->min_freq >= 0.0 && p->min_freq <= 1.0)) return fail(BK_ERR_INVALID, "bk_sample_consensus: min_freq must be between 0 and 1, got %g", p->min_freq);
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_consensus comes after bk_sample_finalize and bk_sample_call");
-    if (!e->called) return fail(BK_ERR_STATE, "bk_sample_consensus: bk_sample_call has not run for this sample");
-    const IndexTables& ix = *e->ix;
-    BK_HIP(hipSetDevice(e->device));
-    if (!e->cons_out.p) {
-        BK_HIP(e->cons_letters.alloc((size_t)ix.max_file_cells));
-        BK_HIP(e->cons_out.alloc(1));
-    }
-    bk::ConsensusArgs a{};
-    a.prm = *p;
-    a.seq_first = ix.seq_first.p; a.n_seqs = ix.n_seqs_d.p; a.seq_cell = ix.seq_cell.p; a.seq_len = ix.seq_len_d.p;
-    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words();
-    a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
-    a.out = e->call_out.p; a.letters = e->cons_letters.p; a.summary = e->cons_out.p;
-    bk_engine::Span sp(e, 1);
-    BK_HIP(hipMemsetAsync(e->cons_out.p, 0, sizeof(bk_consensus_summary), e->stream));
-    bk::launch_consensus(a, ix.max_file_cells, e->stream);
-    BK_HIP(hipGetLastError());
-    e->cons_made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, uint8_t* letters, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->cons_made) return fail(BK_ERR_STATE, "bk_sample_download_consensus comes after this sample's bk_sample_consensus");
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipMemcpyAsync(summary, e->cons_out.p, sizeof *summary, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->positions, cap), e->cons_letters.n);
-    if (n && letters) {
-        BK_HIP(hipMemcpyAsync(letters, e->cons_letters.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
-        BK_HIP(hipStreamSynchronize(e->stream));
-    }
-    return BK_OK;
-}
-
-// ---- per-region depth report (region_depth_kernel, bk_regions.hip) ------------------------------------------------
-int bk_regions_set(bk_engine* e, const bk_region* regions, uint64_t n) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_regions_set comes between samples");
-    if (n > BK_MAX_REGIONS) return fail(BK_ERR_INVALID, "%llu regions: at most %u", (unsigned long long)n, (unsigned)BK_MAX_REGIONS);
-    if (n && !regions) return fail(BK_ERR_INVALID, "null argument");
-    const IndexTables& ix = *e->ix;
-    std::vector<uint32_t> off((size_t)ix.n_files + 1, 0u);
-    for (uint64_t i = 0; i < n; i++) {
-        const bk_region& r = regions[i];
-        if (r.file_id < 0 || r.file_id >= ix.n_files) return fail(BK_ERR_INVALID, "region %llu: no genome file %d (the index has %d)", (unsigned long long)i, r.file_id, ix.n_files);
-        if ((int64_t)r.seq >= (int64_t)ix.h_n_seqs[(size_t)r.file_id])
-            return fail(BK_ERR_INVALID, "region %llu: no sequence %u in genome file %d (it has %d)", (unsigned long long)i, r.seq, r.file_id, ix.h_n_seqs[(size_t)r.file_id]);
-        const uint64_t len = ix.h_seq_len[(size_t)ix.h_seq_first[(size_t)r.file_id] + r.seq];
-        if (!(r.start < r.end && (uint64_t)r.end <= len))
-            return fail(BK_ERR_INVALID, "region %llu: [%u, %u) is not a range inside sequence %u of genome file %d (length %llu)", (unsigned long long)i, r.start, r.end,
-                        r.seq, r.file_id, (unsigned long long)len);
-        off[(size_t)r.file_id + 1] += 1;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernel may still use the table and the buffers being freed)
-    e->regions.reset();
-    e->regions_made = false;
-    if (n == 0) return BK_OK;
-    std::unique_ptr<Regions> rg(new Regions());
-    for (int f = 0; f < ix.n_files; f++) { rg->max_file_regions = std::max(rg->max_file_regions, off[(size_t)f + 1]); off[(size_t)f + 1] += off[(size_t)f]; }
-    std::vector<uint2> tab((size_t)n);
-    std::vector<uint32_t> at(off.begin(), off.end() - 1);   // grouped by file, the caller's order within a file
-    for (uint64_t i = 0; i < n; i++) {
-        const bk_region& r = regions[i];
-        const uint64_t cell = ix.h_seq_cell[(size_t)ix.h_seq_first[(size_t)r.file_id] + r.seq] + r.start;   // (below 2^32: build_index_tables)
-        tab[at[(size_t)r.file_id]++] = make_uint2((uint32_t)cell, r.end - r.start);
-    }
-    BK_HIP(rg->table.upload(tab)); BK_HIP(rg->file_off.upload(off));
-    BK_HIP(rg->rows.alloc(rg->max_file_regions)); BK_HIP(rg->out.alloc(1));
-    e->regions = std::move(rg);
-    return BK_OK;
-}
-
-int bk_sample_region_depths(bk_engine* e, uint64_t min_depth) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (min_depth < 1) return fail(BK_ERR_INVALID, "bk_sample_region_depths: min_depth must be at least 1, got 0");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_region_depths comes after bk_sample_finalize and bk_sample_call");
-    if (!e->called) return fail(BK_ERR_STATE, "bk_sample_region_depths: bk_sample_call has not run for this sample");
-    if (!e->regions) return fail(BK_ERR_STATE, "bk_sample_region_depths: no regions are set (bk_regions_set)");
-    const IndexTables& ix = *e->ix;
-    Regions& rg = *e->regions;
-    BK_HIP(hipSetDevice(e->device));
-    bk::RegionArgs a{};
-    a.min_depth = min_depth;
-    a.table = rg.table.p; a.file_off = rg.file_off.p;
-    a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
-    a.out = e->call_out.p; a.rows = rg.rows.p; a.summary = rg.out.p;
-    bk_engine::Span sp(e, 1);
-    BK_HIP(hipMemsetAsync(rg.out.p, 0, sizeof(bk_region_summary), e->stream));
-    bk::launch_region_depths(a, rg.max_file_regions, e->stream);
-    BK_HIP(hipGetLastError());
-    e->regions_made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_region_depths(bk_engine* e, bk_region_summary* summary, bk_region_depth* out, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->regions_made || !e->regions) return fail(BK_ERR_STATE, "bk_sample_download_region_depths comes after this sample's bk_sample_region_depths");
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipMemcpyAsync(summary, e->regions->out.p, sizeof *summary, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->n_regions, cap), e->regions->rows.n);
-    if (n && out) {
-        BK_HIP(hipMemcpyAsync(out, e->regions->rows.p, (size_t)n * sizeof(bk_region_depth), hipMemcpyDeviceToHost, e->stream));
-        BK_HIP(hipStreamSynchronize(e->stream));
-    }
-    return BK_OK;
-}
-
-// ---- placing records by anchor k-mers: what bk_indels_enable and bk_link_enable ask of the index and build from it -----------------
-static int anchor_index_check(const IndexTables& ix, const char* who) {
-    if (ix.W <= 0 || ix.n_full == 0) return fail(BK_ERR_INVALID, "%s: the index has no window of reference k-mers", who);
-    if (!ix.rc_words.p)   // (build_index_tables makes it with the binned scan's seed tables: fewer than 2^27 cells, at least k)
-        return fail(BK_ERR_UNSUPPORTED, "%s: the engine holds no reverse-complemented reference (it is made for a genome of k to 2^27 - 1 positions; this one has %llu)",
-                    who, (unsigned long long)ix.total_cells);
-    return BK_OK;
-}
-// the engine's anchor tables: the ones the other feature holds, else built here
-static int anchor_tables(bk_engine* e, const char* who, std::shared_ptr<AnchorTables>& out) {
-    if ((out = e->anchors.lock())) return BK_OK;
-    const IndexTables& ix = *e->ix;
-    std::shared_ptr<AnchorTables> t(new AnchorTables());
-    {   // a histogram of the ids over the cells: one bit per id that starts at exactly one cell
-        std::vector<uint32_t> id_at((size_t)ix.total_cells);
-        BK_HIP(hipMemcpy(id_at.data(), ix.id_at.p, id_at.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        std::vector<uint8_t> seen(ix.n_full, 0);
-        for (uint32_t id : id_at) if (id < ix.n_full && seen[id] < 2) seen[id]++;
-        std::vector<uint32_t> bits(((size_t)ix.n_full + 31) / 32, 0u);
-        for (uint32_t id = 0; id < ix.n_full; id++) if (seen[id] == 1) bits[id >> 5] |= 1u << (id & 31u);
-        BK_HIP(t->unique_bits.upload(bits));
-    }
-    std::vector<uint32_t> lo;
-    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) lo.push_back((uint32_t)ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q]);
-    lo.push_back((uint32_t)ix.total_cells);
-    if (lo.size() < 2) return fail(BK_ERR_INVALID, "%s: the genome file has no sequence", who);
-    BK_HIP(t->seq_lo.upload(lo));
-    BK_HIP(t->nruns.upload(ix.h_nonacgt));
-    e->anchors = t;
-    out = std::move(t);
-    return BK_OK;
-}
-
-// ---- short insertions and deletions from the reads (bk_indels.hip) ------------------------------------------------
-int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_indels_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->max_len < 1 || cfg->max_len > BK_INDEL_MAX_LEN) return fail(BK_ERR_INVALID, "bk_indels_enable: max_len must be 1..%d, got %u", BK_INDEL_MAX_LEN, cfg->max_len);
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_indels_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_indels_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_indels_enable: the index has %d genome files; indels are called against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_indels_enable")) return rc;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->indels.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Indels> d(new Indels());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_indels_enable", d->anchors)) return rc;
-    const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->key0.alloc(slots)); BK_HIP(d->key1.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
-    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(8));
-    e->indels = std::move(d);
-    return BK_OK;
-}
-
-int bk_sample_indels(bk_engine* e, const bk_indel_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_indels: min_reads must be at least 1, got 0");
-    if (p->min_af_ppm > 1000000u) return fail(BK_ERR_INVALID, "bk_sample_indels: min_af_ppm must be 0..1000000, got %u", p->min_af_ppm);
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels comes after bk_sample_finalize");
-    if (!e->indels || !e->indels->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels: indels were not enabled for this sample (bk_indels_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_indels: bk_sample_finalize has not run for this sample");
-    Indels& d = *e->indels;
-    BK_HIP(hipSetDevice(e->device));
-    bk::IndelArgs a = indel_args(e);
-    a.min_reads = p->min_reads; a.min_af_ppm = p->min_af_ppm;
-    bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_indel_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 5, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_indel_report(a, e->stream);
-    BK_HIP(hipGetLastError());
-    d.made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indels comes after this sample's bk_sample_indels");
-    Indels& d = *e->indels;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[8];
-    BK_HIP(hipMemcpyAsync(t, d.tallies.p, sizeof t, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    summary->records = t[0]; summary->anchored = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->discordant = t[4];
-    summary->candidates = t[5]; summary->reported = t[6]; summary->overflow = t[7] ? 1 : 0;
-    if (t[7]) return fail(BK_ERR_INVALID, "bk_sample_download_indels: more than 2^%u distinct candidate events: enable indels with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[6], cap), d.rows.n);
-    if (n && records) {
-        BK_HIP(hipMemcpyAsync(records, d.rows.p, (size_t)n * sizeof(bk_indel_record), hipMemcpyDeviceToHost, e->stream));
-        BK_HIP(hipStreamSynchronize(e->stream));
-    }
-    return BK_OK;
-}
-
-int bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap) {
-    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indel_span comes after this sample's bk_sample_indels");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_indel_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipMemcpyAsync(span, e->indels->span.p, (size_t)e->ix->total_cells * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    return BK_OK;
-}
-
-// ---- which substitutions the same records carry (bk_linkage.hip) ----------------------------------------------------
-int bk_link_enable(bk_engine* e, const bk_link_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_link_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_link_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->initial_rows < 1 || cfg->initial_rows > (1ull << 32))
-            return fail(BK_ERR_INVALID, "bk_link_enable: initial_rows must be 1..2^32, got %llu", (unsigned long long)cfg->initial_rows);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_link_enable: the index has %d genome files; linkage is counted against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_link_enable")) return rc;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->linkage.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Linkage> d(new Linkage());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_link_enable", d->anchors)) return rc;
-    BK_HIP(d->rows.alloc((size_t)cfg->initial_rows * 2));
-    BK_HIP(d->tallies.alloc(4));
-    BK_HIP(hipMemsetAsync(d->tallies.p, 0, 4 * sizeof(unsigned long long), e->stream));
-    e->linkage = std::move(d);
-    return BK_OK;
-}
-
-int bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uint32_t max_dist) {
-    if (!e || (!cells && n_sites)) return fail(BK_ERR_INVALID, "null argument");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage comes after bk_sample_finalize");
-    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_linkage: bk_sample_finalize has not run for this sample");
-    if (n_sites > BK_LINK_MAX_SITES) return fail(BK_ERR_INVALID, "bk_sample_linkage: at most %d sites, got %u", BK_LINK_MAX_SITES, n_sites);
-    if (max_dist < 1 || max_dist > BK_LINK_MAX_DIST) return fail(BK_ERR_INVALID, "bk_sample_linkage: max_dist must be 1..%d, got %u", BK_LINK_MAX_DIST, max_dist);
-    const IndexTables& ix = *e->ix;
-    for (uint32_t i = 0; i < n_sites; i++) {
-        if (cells[i] >= ix.total_cells) return fail(BK_ERR_INVALID, "bk_sample_linkage: site %u is cell %u, the index has %llu", i, cells[i], (unsigned long long)ix.total_cells);
-        if (i && cells[i] <= cells[i - 1]) return fail(BK_ERR_INVALID, "bk_sample_linkage: the sites must be strictly ascending (site %u is cell %u behind cell %u)", i, cells[i], cells[i - 1]);
-    }
-    Linkage& d = *e->linkage;
-    // the pairs: i < j in one sequence, cell_j - cell_i <= max_dist -- for each i a stretch of j that starts at i + 1
-    std::vector<uint32_t> seq_end;               // end cell of every sequence of the genome file
-    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) seq_end.push_back((uint32_t)(ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q] + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q]));
-    std::vector<uint32_t> pair_lo(n_sites);
-    uint64_t n_pairs = 0;
-    for (uint32_t i = 0, j = 0, s = 0; i < n_sites; i++) {
-        while (s + 1 < seq_end.size() && cells[i] >= seq_end[s]) s++;
-        if (j < i + 1) j = i + 1;
-        while (j < n_sites && cells[j] < seq_end[s] && cells[j] - cells[i] <= max_dist) j++;   // (j never moves back: both bounds grow with i)
-        pair_lo[i] = (uint32_t)std::min<uint64_t>(n_pairs, 0xffffffffull);
-        n_pairs += j - (i + 1);
-    }
-    if (n_pairs > BK_LINK_MAX_PAIRS)
-        return fail(BK_ERR_INVALID, "bk_sample_linkage: %llu pairs of sites within %u cells, at most %u are counted", (unsigned long long)n_pairs, max_dist, BK_LINK_MAX_PAIRS);
-    BK_HIP(hipSetDevice(e->device));
-    // an earlier count may still read the sites, pair_lo, the counters and the pinned copies that are replaced here: wait for that
-    // launch alone -- nothing else of the stream's work is waited for
-    if (d.count_in_flight) { BK_HIP(hipEventSynchronize(d.counted)); d.count_in_flight = false; }
-    BK_HIP(d.h_sites.grow(std::max<size_t>(n_sites, 1))); BK_HIP(d.h_pair_lo.grow(std::max<size_t>(n_sites, 1)));
-    if (n_sites) { std::memcpy(d.h_sites.p, cells, n_sites * sizeof(uint32_t)); std::memcpy(d.h_pair_lo.p, pair_lo.data(), n_sites * sizeof(uint32_t)); }
-    d.n_sites = n_sites; d.max_dist = max_dist; d.n_pairs = n_pairs; d.made = false;
-    BK_HIP(grow(d.sites, n_sites)); BK_HIP(grow(d.pair_lo, n_sites)); BK_HIP(grow(d.counts, (size_t)n_pairs * 16));
-    bk_engine::Span sp(e, 1);
-    if (n_sites) {
-        BK_HIP(hipMemcpyAsync(d.sites.p, d.h_sites.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        BK_HIP(hipMemcpyAsync(d.pair_lo.p, d.h_pair_lo.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    }
-    if (n_pairs) BK_HIP(hipMemsetAsync(d.counts.p, 0, (size_t)n_pairs * 16 * sizeof(unsigned int), e->stream));
-    bk::launch_link_count(link_args(e), d.rows_upper, ix.n_cus, e->stream);
-    BK_HIP(hipGetLastError());
-    BK_HIP(d.counted.create());
-    BK_HIP(hipEventRecord(d.counted, e->stream));
-    d.count_in_flight = true;
-    d.made = true;
-    return BK_OK;
-}
-
-static int link_finalized(bk_engine* e, const char* who) {
-    if (e->in_sample || !e->linkage || !e->linkage->in_sample || e->finalized_mates < 1)
-        return fail(BK_ERR_STATE, "%s comes after bk_sample_finalize of a sample that began with linkage enabled", who);
-    return BK_OK;
-}
-
-int bk_sample_download_linkage(bk_engine* e, bk_link_summary* summary, bk_link_pair* pairs, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (int rc = link_finalized(e, "bk_sample_download_linkage")) return rc;
-    Linkage& d = *e->linkage;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[4];
-    BK_HIP(hipMemcpyAsync(t, d.tallies.p, sizeof t, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    summary->records = t[0]; summary->placed = t[1]; summary->unplaced = t[2]; summary->discordant = t[3];
-    summary->n_pairs = d.made ? d.n_pairs : 0; summary->n_sites = d.made ? d.n_sites : 0; summary->max_dist = d.made ? d.max_dist : 0;
-    const uint64_t n = std::min<uint64_t>(summary->n_pairs, cap);
-    if (!n || !pairs) return BK_OK;
-    std::vector<unsigned int> counts((size_t)n * 16);
-    BK_HIP(hipMemcpy(counts.data(), d.counts.p, counts.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < d.n_sites && at < n; i++) {
-        const uint64_t end = i + 1 < d.n_sites ? d.h_pair_lo.p[i + 1] : d.n_pairs;
-        for (uint64_t p = d.h_pair_lo.p[i]; p < end && at < n; p++, at++) {
-            pairs[at].site_a = d.h_sites.p[i]; pairs[at].site_b = d.h_sites.p[i + 1 + (size_t)(p - d.h_pair_lo.p[i])];
-            std::memcpy(pairs[at].count, counts.data() + (size_t)p * 16, 16 * sizeof(uint32_t));
-        }
-    }
-    return BK_OK;
-}
-
-int bk_sample_download_link_rows(bk_engine* e, bk_link_row* rows, uint64_t cap) {
-    static_assert(sizeof(bk_link_row) == 2 * sizeof(uint4), "a row is two 16-byte stores");
-    if (!e || (!rows && cap)) return fail(BK_ERR_INVALID, "null argument");
-    if (int rc = link_finalized(e, "bk_sample_download_link_rows")) return rc;
-    Linkage& d = *e->linkage;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long placed = 0;
-    BK_HIP(hipMemcpyAsync(&placed, d.tallies.p + 1, sizeof placed, hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(placed, cap), d.rows.n / 2);
-    if (n) BK_HIP(hipMemcpy(rows, d.rows.p, (size_t)n * sizeof(bk_link_row), hipMemcpyDeviceToHost));
-    return BK_OK;
 }
 
 // ---- measurement ---------------------------------------------------------------------------------------------

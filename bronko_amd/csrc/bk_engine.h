@@ -1,7 +1,8 @@
 // bk_engine.h -- private to the host side of the engine: error reporting, device and pinned buffers, host-thread helpers, the
 // index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
-// packer) and bk_engine.cpp (the rest: the engine's life, the sample path from push_device on).
+// packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
+// ride behind every scan: the k-mer dump, indels, linkage) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,7 @@
 extern thread_local std::string g_err;   // bk_last_error
 
 int fail(int code, const char* fmt, ...);
+struct bk_engine;
 
 #define BK_HIP(expr)                                                                                  \
     do {                                                                                              \
@@ -167,12 +169,12 @@ struct PhaseClock {
 };
 
 // An open-addressing table of u64 keys (~0 = free) and u32 counts whose load stays below one half as a sample fills it
-// (ensure_table_room): full_kmer_stats' statistics table and the k-mer dump's count table (bk_kmer_dump_enable).  Its device-side
+// (ensure_room): full_kmer_stats' statistics table and the k-mer dump's count table (bk_kmer_dump_enable).  Its device-side
 // companion `out` holds the overflow flag at [4] and the tallies of new keys at [8 ..] (ktab_insert_key, kmer_dump_count_kernel).
 struct GrowTable {
     DevBuf<unsigned long long> keys;
     DevBuf<unsigned int> cnt;
-    uint32_t log2 = 0;                      // current capacity (grows with the sample: ensure_table_room)
+    uint32_t log2 = 0;                      // current capacity (grows with the sample: ensure_room)
     PinnedBuf<unsigned long long> h_fill;   // pinned copy of the tallies, refreshed after every push
     Event fill_ev;
     bool fill_pending = false;              // a copy of the tallies is in flight / unread
@@ -183,6 +185,10 @@ struct GrowTable {
         for (uint32_t i = 0; i < bk::ktab_fill_words(); i++) fill_known += h_fill.p[i];
     }
     ~GrowTable() { for (auto& o : old) { (void)hipFree(o.first); (void)hipFree(o.second); } }
+    // (bk_engine.cpp: on the engine's stream; `out` is the table's device-side companion)
+    int clear(bk_engine* e);                                                  // a sample starts from an empty table
+    int ensure_room(bk_engine* e, unsigned long long* out, uint64_t upper);   // before a batch of at most `upper` k-mers
+    int note_fill(bk_engine* e, const unsigned long long* out);               // after it: a fresh copy of the tallies
 };
 
 // bk_kmer_dump_enable: the sample's count table of every strand-specific k-mer (bk_kmer_dump.hip) and, per finalized mate file, its
@@ -197,6 +203,9 @@ struct KmerDump {
     uint64_t n_sorted[2] = {0, 0};          // length of the sorted arrays of the last finalize (selected entries, then padding)
     bool in_sample = false;                 // enabled when the current / last sample began
     int finalized_mates = 0;                // mate files the last finalize selected (0: none, or finalized by shards)
+    int begin_sample(bk_engine* e);         // (bk_riders.cpp: these three issue work on the engine's stream)
+    int push(bk_engine* e, int mate, const Records& r, uint64_t upper);   // in front of the scan of the same records
+    int finalize(bk_engine* e, int n_mates);                              // at the end of a whole-sample finalize
 };
 
 // What bk_primers_set and bk_adapters_set keep alike: the sample's counters and whether the stage was set when the sample began
@@ -205,6 +214,7 @@ struct TrimStage {
     DevBuf<unsigned long long> stats;       // [2][n_stats] (zeroed by bk_sample_begin)
     bool in_sample = false;                 // set when the current / last sample began
     explicit TrimStage(uint32_t n_stats_) : n_stats(n_stats_) {}
+    int begin_sample(bk_engine* e);         // (bk_ingest.cpp)
 };
 // bk_primers_set: the primer table (bk_primers.hip); stats: reads trimmed at 5', at 3', bases masked
 struct Primers : TrimStage {
@@ -258,6 +268,8 @@ struct Linkage {
     bool in_sample = false;                 // enabled when the current / last sample began
     bool made = false;                      // the counters are this sample's (bk_sample_linkage ran)
     ~Linkage() { for (auto& o : old) (void)hipFree(o.first); }
+    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
+    int push(bk_engine* e, const Records& r);   // behind the scan of the same records, and behind the indels' pass
 };
 
 // bk_indels_enable: what indel_scan_kernel reads beside the index tables (bk_indels.hip), the sample's event table, span array and
@@ -273,6 +285,8 @@ struct Indels {
     bool in_sample = false;                 // enabled when the current / last sample began
     bool summed = false;                    // span is prefix-summed (this sample's bk_sample_indels ran)
     bool made = false;                      // ... and the rows are this sample's
+    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
+    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
 };
 
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
@@ -520,5 +534,13 @@ struct bk_engine {
 
 // The scan of a batch of records and all that follows it on the engine's stream (bk_engine.cpp); every push of bk_ingest.cpp ends here
 int push_device(bk_engine* e, int mate, const Records& r);
+
+// `count` elements from the device to the host on the engine's stream, waited for
+template <class T>
+int download(bk_engine* e, T* host_dst, const void* dev_src, size_t count) {
+    BK_HIP(hipMemcpyAsync(host_dst, dev_src, count * sizeof(T), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    return BK_OK;
+}
 
 #pragma GCC visibility pop

@@ -55,26 +55,26 @@ __device__ __forceinline__ void event_insert(const IndelArgs& a, uint32_t cell, 
 // A record's anchors and all that needs no breakpoint.  Returns true with `work` filled for a record with delta != 0 that passed
 // the checks: {record | against << 31, a | b << 16, dL, dR}.
 __device__ __forceinline__ bool indel_anchor(const IndelArgs& a, uint32_t r, IndelTally& t, uint4& work) {
-    const int32_t k = a.k, n = (int32_t)a.lens[r];
+    const int32_t k = a.ix.k, n = (int32_t)a.rec.lens[r];
     if (n < k) return false;                          // (trimmed away: no record any more)
     t.records++;
     if (n < 2 * k) return false;
-    const uint32_t* __restrict__ w = a.words + (uint64_t)r * a.stride_words;
+    const uint32_t* __restrict__ w = a.rec.words + (uint64_t)r * a.rec.stride_words;
     Anchors an;
-    if (!anchors_of(a, w, n, an)) return false;
+    if (!anchors_of(a.ix, w, n, an)) return false;
     const bool against = an.against;
     const int32_t pa = an.pa, pb = an.pb;
     t.anchored++;
     const int32_t dL = (int32_t)an.ca - pa, dR = (int32_t)an.cb - pb, delta = dR - dL;
     if (delta > (int32_t)a.max_len || -delta > (int32_t)a.max_len) { t.discordant++; return false; }
-    if (!cells_placed(a, an.ca, an.cb, min(dL, dR), max(dL, dR) + n)) return false;
+    if (!cells_placed(a.ix, an.ca, an.cb, min(dL, dR), max(dL, dR) + n)) return false;
     if (delta != 0) {
         work = make_uint4(r | (against ? 0x80000000u : 0u), (uint32_t)pa | ((uint32_t)pb << 16), (uint32_t)dL, (uint32_t)dR);
         return true;
     }
     const uint32_t last_word = (uint32_t)(n - 1) >> 4;
-    const uint32_t m = against ? mismatches(w, last_word, 0u, (uint32_t)n, a.rc_words, (int64_t)a.total_cells - dL - n, a.max_mismatches)
-                               : mismatches(w, last_word, 0u, (uint32_t)n, a.ref_words, dL, a.max_mismatches);
+    const uint32_t m = against ? mismatches(w, last_word, 0u, (uint32_t)n, a.ix.rc_words, (int64_t)a.ix.total_cells - dL - n, a.max_mismatches)
+                               : mismatches(w, last_word, 0u, (uint32_t)n, a.ix.ref_words, dL, a.max_mismatches);
     if (m > a.max_mismatches) { t.discordant++; return false; }
     t.spanning++;
     atomicAdd(a.span + (dL + pa + k), 1u);
@@ -87,20 +87,20 @@ __device__ __forceinline__ void indel_walk(const IndelArgs& a, const uint4 work,
     const uint32_t r = work.x & 0x7fffffffu;
     const bool against = (work.x >> 31) != 0u;
     const int32_t pa = (int32_t)(work.y & 0xffffu), pb = (int32_t)(work.y >> 16), dL = (int32_t)work.z, dR = (int32_t)work.w;
-    const int32_t k = a.k, n = (int32_t)a.lens[r], delta = dR - dL;
+    const int32_t k = a.ix.k, n = (int32_t)a.rec.lens[r], delta = dR - dL;
     const int32_t I = delta < 0 ? -delta : 0, D = delta > 0 ? delta : 0;
-    const uint32_t* __restrict__ w = a.words + (uint64_t)r * a.stride_words;
+    const uint32_t* __restrict__ w = a.rec.words + (uint64_t)r * a.rec.stride_words;
     const uint32_t last_word = (uint32_t)(n - 1) >> 4;
     const int32_t p0 = pa + k, p1 = pb - I;
     if (p0 > p1) { t.discordant++; return; }
     // #{j in [j0, j1): r'[j] != ref[d + j]}: a record against the reference reads rc_words at the mirrored cells
     auto span_mm = [&](int32_t j0, int32_t j1, int32_t d) -> int32_t {
         if (j0 >= j1) return 0;
-        return (int32_t)(against ? mismatches(w, last_word, (uint32_t)(n - j1), (uint32_t)(n - j0), a.rc_words, (int64_t)a.total_cells - d - n, ~0u)
-                                 : mismatches(w, last_word, (uint32_t)j0, (uint32_t)j1, a.ref_words, d, ~0u));
+        return (int32_t)(against ? mismatches(w, last_word, (uint32_t)(n - j1), (uint32_t)(n - j0), a.ix.rc_words, (int64_t)a.ix.total_cells - d - n, ~0u)
+                                 : mismatches(w, last_word, (uint32_t)j0, (uint32_t)j1, a.ix.ref_words, d, ~0u));
     };
     auto rp = [&](int32_t j) -> uint32_t { return against ? 3u - sym_at(w, (uint32_t)(n - 1 - j)) : sym_at(w, (uint32_t)j); };   // r'[j]
-    auto mm = [&](int32_t j, int32_t d) -> int32_t { return rp(j) != sym_at(a.ref_words, (uint32_t)(d + j)) ? 1 : 0; };
+    auto mm = [&](int32_t j, int32_t d) -> int32_t { return rp(j) != sym_at(a.ix.ref_words, (uint32_t)(d + j)) ? 1 : 0; };
     int32_t m = span_mm(0, p0, dL) + span_mm(p0 + I, n, dR);
     int32_t best = m, best_p = p0;
     for (int32_t p = p0; p < p1; ++p) {
@@ -110,21 +110,21 @@ __device__ __forceinline__ void indel_walk(const IndelArgs& a, const uint4 work,
     if (best > (int32_t)a.max_mismatches) { t.discordant++; return; }
     int32_t pos = dL + best_p;
     // F: the first cell of the stretch of ACGT letters of the sequence that holds pos - 1 (the record's cells hold no other letter)
-    int32_t F = (int32_t)a.seq_lo[seq_of(a, (uint32_t)(dL + pa))];
+    int32_t F = (int32_t)a.ix.seq_lo[seq_of(a.ix, (uint32_t)(dL + pa))];
     const int32_t lo = min(dL, dR);
-    if (a.n_nruns) {   // (no run reaches into the record's cells: the runs in front of them are the ones that end at lo or before)
-        const uint32_t i = first_run_behind(a, lo);
-        if (i > 0u) F = max(F, (int32_t)a.nruns[i - 1u].y);
+    if (a.ix.n_nruns) {   // (no run reaches into the record's cells: the runs in front of them are the ones that end at lo or before)
+        const uint32_t i = first_run_behind(a.ix, lo);
+        if (i > 0u) F = max(F, (int32_t)a.ix.nruns[i - 1u].y);
     }
     unsigned long long s = 0ull;
     if (D) {
-        while (pos - 1 > F && sym_at(a.ref_words, (uint32_t)(pos - 1)) == sym_at(a.ref_words, (uint32_t)(pos + D - 1))) --pos;
+        while (pos - 1 > F && sym_at(a.ix.ref_words, (uint32_t)(pos - 1)) == sym_at(a.ix.ref_words, (uint32_t)(pos + D - 1))) --pos;
     } else {
         for (int32_t i = 0; i < I; ++i) s |= (unsigned long long)rp(best_p + i) << (2 * i);
         const unsigned long long smask = I == 32 ? ~0ull : (1ull << (2 * I)) - 1ull;
         while (pos - 1 > F) {
             const unsigned long long last = (s >> (2 * (I - 1))) & 3ull;
-            if ((unsigned long long)sym_at(a.ref_words, (uint32_t)(pos - 1)) != last) break;
+            if ((unsigned long long)sym_at(a.ix.ref_words, (uint32_t)(pos - 1)) != last) break;
             s = ((s << 2) | last) & smask;
             --pos;
         }
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kIndelBlock) void indel_scan_kernel(IndelArgs a) {
     __shared__ uint4 queue_s[kIndelBlock / 64][kIndelQueue];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4* const q = queue_s[wave];
-    const uint64_t n = a.n_records_dev ? std::min<uint64_t>(a.n_records, *a.n_records_dev) : a.n_records;
+    const uint64_t n = a.rec.n_records_dev ? std::min<uint64_t>(a.rec.n_records, *a.rec.n_records_dev) : a.rec.n_records;
     const uint64_t stride = (uint64_t)gridDim.x * kIndelBlock;
     IndelTally t;
     uint32_t qn = 0;                                  // records waiting in the wave's queue (the same in every lane)
@@ -229,14 +229,14 @@ __global__ __launch_bounds__(kIndelBlock) void indel_report_kernel(IndelArgs a) 
 }  // namespace
 
 void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream) {
-    if (a.n_records == 0) return;
-    const uint64_t blocks = (a.n_records + kIndelBlock - 1) / kIndelBlock;
+    if (a.rec.n_records == 0) return;
+    const uint64_t blocks = (a.rec.n_records + kIndelBlock - 1) / kIndelBlock;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
     hipLaunchKernelGGL(indel_scan_kernel, dim3(grid), dim3(kIndelBlock), 0, stream, a);
 }
 
 void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(indel_span_prefix_kernel, dim3(1), dim3(kPrefixBlock), 0, stream, a.span, a.total_cells + 2u);
+    hipLaunchKernelGGL(indel_span_prefix_kernel, dim3(1), dim3(kPrefixBlock), 0, stream, a.span, a.ix.total_cells + 2u);
 }
 
 void launch_indel_report(const IndelArgs& a, hipStream_t stream) {

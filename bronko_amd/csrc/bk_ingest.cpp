@@ -243,8 +243,12 @@ static int trim_stats(bk_engine* e, int mate, const TrimStage* t, const SeqKind&
     if (!t || !t->in_sample) return fail(BK_ERR_STATE, "no %ss were set for this sample (bk_%ss_set before bk_sample_begin)", kd.name, kd.name);
     if (e->in_sample) return fail(BK_ERR_STATE, "the %s counters are read after bk_sample_finalize", kd.name);
     BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipMemcpyAsync(out, t->stats.p + mate * t->n_stats, t->n_stats * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
+    return download(e, out, t->stats.p + mate * t->n_stats, t->n_stats);
+}
+// bk_sample_begin: zero counters
+int TrimStage::begin_sample(bk_engine* e) {
+    BK_HIP(hipMemsetAsync(stats.p, 0, stats.n * sizeof(unsigned long long), e->stream));
+    in_sample = true;
     return BK_OK;
 }
 

@@ -353,11 +353,31 @@ void launch_ktab_import(const unsigned long long* in_keys, const unsigned int* i
                         unsigned long long* overflow, hipStream_t stream);
 void launch_ktab_totals_to_kstats(unsigned long long* ktab_out, unsigned long long* kstats, int n_mates, hipStream_t stream);
 uint32_t ktab_fill_words();   // tallies of new keys behind the overflow word: ktab_out[8 ..]
+// What the kernels that ride behind a scan take of its batch and of the index (the k-mer dump, bk_indels.hip, bk_linkage.hip).
+// A batch of records (Records of bk_engine.h); n_records_dev: null, or the ASCII paths' record count, known on the device only
+struct RecordsView {
+    const uint32_t* words; const uint16_t* lens;
+    uint64_t n_records; const unsigned long long* n_records_dev;
+    uint32_t stride_words;
+};
+// Placing a record by two anchor k-mers (bk_anchor.h): the perfect hash of the reference k-mers, one bit per id (it starts at exactly
+// one cell), both references past their padding, and the genome file's geometry -- the engine's AnchorTables hold unique_bits, seq_lo
+// and nruns
+struct AnchorIndex {
+    const KmerPos* kmer_pos; const uint16_t* pilots;
+    uint32_t m, log2nb, log2p, n_full;
+    const uint32_t* unique_bits;
+    const uint32_t* ref_words; const uint32_t* rc_words;
+    uint32_t total_cells; int32_t k;
+    const uint32_t* seq_lo;              // [n_seqs + 1] first cell of each sequence, then total_cells
+    uint32_t n_seqs;
+    const uint2* nruns;                  // [n_nruns] {first cell, end} of the runs of letters that are not ACGT, ascending
+    uint32_t n_nruns;
+};
 // the sample's k-mer count table (bk_kmer_dump.hip; bk_kmer_dump_enable): count every k-mer of a batch of records (n_records_dev: the
 // ASCII paths' record count, known on the device only); per mate file, select ci <= count <= cx as (k-mer, min(count, cs)) into
 // out_* (at most cap; res[0] = kept, res[1] = distinct); sort the pairs by k-mer (rocprim; tmp == nullptr: tmp_bytes is sized)
-void launch_kmer_dump_count(const uint32_t* words, const uint16_t* lens, uint64_t n_records, const unsigned long long* n_records_dev,
-                            uint32_t stride_words, int k, uint32_t mate, unsigned long long* keys, unsigned int* cnt, uint32_t log2n,
+void launch_kmer_dump_count(const RecordsView& rec, int k, uint32_t mate, unsigned long long* keys, unsigned int* cnt, uint32_t log2n,
                             unsigned long long* overflow, int n_cus, hipStream_t stream);
 void launch_kmer_dump_select(const unsigned long long* keys, const unsigned int* cnt, uint32_t log2n, uint32_t mate, unsigned long long ci,
                              unsigned long long cs, unsigned long long cx, unsigned long long* out_keys, unsigned int* out_cnt, uint64_t cap,
@@ -457,20 +477,8 @@ void launch_region_depths(const RegionArgs& a, uint32_t max_file_regions, hipStr
 // bk_indels_enable: short insertions and deletions from the reads (bk_indels.hip; the rule: include/bronko_hip.h)
 typedef bk_indel_record IndelRecordDev;
 struct IndelArgs {
-    // a batch of records (Records of bk_engine.h): indel_scan_kernel
-    const uint32_t* words; const uint16_t* lens;
-    uint64_t n_records; const unsigned long long* n_records_dev;
-    uint32_t stride_words;
-    // the index: the perfect hash of the reference k-mers, one bit per id (it starts at one cell), both references past their padding
-    const KmerPos* kmer_pos; const uint16_t* pilots;
-    uint32_t m, log2nb, log2p, n_full;
-    const uint32_t* unique_bits;
-    const uint32_t* ref_words; const uint32_t* rc_words;
-    uint32_t total_cells; int32_t k;
-    const uint32_t* seq_lo;              // [n_seqs + 1] first cell of each sequence, then total_cells
-    uint32_t n_seqs;
-    const uint2* nruns;                  // [n_nruns] {first cell, end} of the runs of letters that are not ACGT, ascending
-    uint32_t n_nruns;
+    RecordsView rec;                     // indel_scan_kernel's batch
+    AnchorIndex ix;
     uint32_t max_len, max_mismatches;
     // the sample: event table (two key words ~0 = free, {fwd, rev}), span, counters
     unsigned long long* key0; unsigned long long* key1;
@@ -487,20 +495,8 @@ void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream);   // span
 void launch_indel_report(const IndelArgs& a, hipStream_t stream);
 // bk_link_enable: which substitutions the same records carry (bk_linkage.hip; the rule: include/bronko_hip.h)
 struct LinkArgs {
-    // a batch of records (Records of bk_engine.h): link_scan_kernel
-    const uint32_t* words; const uint16_t* lens;
-    uint64_t n_records; const unsigned long long* n_records_dev;
-    uint32_t stride_words;
-    // the index and the anchor tables, as IndelArgs names them (bk_anchor.h reads both)
-    const KmerPos* kmer_pos; const uint16_t* pilots;
-    uint32_t m, log2nb, log2p, n_full;
-    const uint32_t* unique_bits;
-    const uint32_t* ref_words; const uint32_t* rc_words;
-    uint32_t total_cells; int32_t k;
-    const uint32_t* seq_lo;
-    uint32_t n_seqs;
-    const uint2* nruns;
-    uint32_t n_nruns;
+    RecordsView rec;                     // link_scan_kernel's batch
+    AnchorIndex ix;
     uint32_t max_mismatches;
     // the sample: its row store (a row is two uint4: bk_link_row) and tallies
     uint4* rows; uint64_t row_cap;

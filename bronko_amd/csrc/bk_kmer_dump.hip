@@ -8,7 +8,7 @@
 //   kmer_dump_select_kernel  at finalize, per mate file: the entries with ci <= count <= cx, as (k-mer, min(count, cs)), one
 //                            append per wave; and the mate file's distinct k-mers;
 //   rocprim radix sort       the selected pairs by k-mer over bits [0, 2k): ascending lexicographic order (A < C < G < T).
-// The table grows like full_kmer_stats' table (bk_engine.cpp ensure_table_room, ktab_rehash_kernel): same slot hash.
+// The table grows like full_kmer_stats' table (GrowTable::ensure_room of bk_engine.cpp, ktab_rehash_kernel): same slot hash.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -151,14 +151,13 @@ __global__ __launch_bounds__(256) void kmer_dump_select_kernel(const unsigned lo
 
 }  // namespace
 
-void launch_kmer_dump_count(const uint32_t* words, const uint16_t* lens, uint64_t n_records, const unsigned long long* n_records_dev,
-                            uint32_t stride_words, int k, uint32_t mate, unsigned long long* keys, unsigned int* cnt, uint32_t log2n,
+void launch_kmer_dump_count(const RecordsView& rec, int k, uint32_t mate, unsigned long long* keys, unsigned int* cnt, uint32_t log2n,
                             unsigned long long* overflow, int n_cus, hipStream_t stream) {
-    if (n_records == 0 || stride_words * 16u < (uint32_t)k) return;   // (records too short to hold a k-mer)
-    const uint64_t tiles = (n_records + kDumpTile - 1) / kDumpTile;
+    if (rec.n_records == 0 || rec.stride_words * 16u < (uint32_t)k) return;   // (records too short to hold a k-mer)
+    const uint64_t tiles = (rec.n_records + kDumpTile - 1) / kDumpTile;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)n_cus * 8));
-    hipLaunchKernelGGL(kmer_dump_count_kernel, dim3(grid), dim3(256), 0, stream, words, lens, n_records, n_records_dev, stride_words, k, mate,
-                       keys, cnt, log2n, overflow);
+    hipLaunchKernelGGL(kmer_dump_count_kernel, dim3(grid), dim3(256), 0, stream, rec.words, rec.lens, rec.n_records, rec.n_records_dev,
+                       rec.stride_words, k, mate, keys, cnt, log2n, overflow);
 }
 
 void launch_kmer_dump_select(const unsigned long long* keys, const unsigned int* cnt, uint32_t log2n, uint32_t mate, unsigned long long ci,

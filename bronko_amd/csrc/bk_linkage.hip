@@ -2,7 +2,7 @@
 //
 // The rule is stated in include/bronko_hip.h and DESIGN.md section L; bronko_amd/host/linkage.cpp and tests/linkage_ref.py restate it.
 //   link_scan_kernel    behind the scan of the same records, a lane per record.  The anchors and the placement checks are
-//                       indel_scan_kernel's (bk_anchor.h); a record is placed only on one diagonal (delta = 0 exactly).  The
+//                       indel_scan_kernel's (bk_anchor.h, over LinkArgs::ix); a record is placed only on one diagonal (delta = 0 exactly).  The
 //                       sixteen-base XOR / fold / popcount pass keeps what indel_scan_kernel's delta = 0 branch throws away: the
 //                       set bits of the folded word are the mismatches' positions (ctz).  A record against the reference is
 //                       compared with rc_words at the mirrored cell; its position i is cell dL + n - 1 - i and its base there
@@ -31,19 +31,19 @@ struct LinkTally { uint32_t records = 0, unplaced = 0, discordant = 0; };
 
 // A record's row, or false with the tally that says why not.  lo / hi: the row's two halves.
 __device__ __forceinline__ bool link_place(const LinkArgs& a, uint32_t r, LinkTally& t, uint4& lo, uint4& hi) {
-    const int32_t k = a.k, n = (int32_t)a.lens[r];
+    const int32_t k = a.ix.k, n = (int32_t)a.rec.lens[r];
     if (n < k) return false;                          // (trimmed away: no record any more)
     t.records++;
     if (n < 2 * k) { t.unplaced++; return false; }
-    const uint32_t* __restrict__ w = a.words + (uint64_t)r * a.stride_words;
+    const uint32_t* __restrict__ w = a.rec.words + (uint64_t)r * a.rec.stride_words;
     Anchors an;
-    if (!anchors_of(a, w, n, an)) { t.unplaced++; return false; }
+    if (!anchors_of(a.ix, w, n, an)) { t.unplaced++; return false; }
     const int32_t dL = (int32_t)an.ca - an.pa, dR = (int32_t)an.cb - an.pb;
-    if (dL != dR || !cells_placed(a, an.ca, an.cb, dL, dL + n)) { t.unplaced++; return false; }
+    if (dL != dR || !cells_placed(a.ix, an.ca, an.cb, dL, dL + n)) { t.unplaced++; return false; }
     const bool against = an.against;
     const uint32_t last_word = (uint32_t)(n - 1) >> 4;
-    const uint32_t* __restrict__ text = against ? a.rc_words : a.ref_words;
-    const int64_t diag = against ? (int64_t)a.total_cells - dL - n : (int64_t)dL;
+    const uint32_t* __restrict__ text = against ? a.ix.rc_words : a.ix.ref_words;
+    const int64_t diag = against ? (int64_t)a.ix.total_cells - dL - n : (int64_t)dL;
     uint32_t e[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // the mismatches, ascending by offset: offset | base << 16 (static indices only)
     uint32_t m = 0;
     for (uint32_t i = 0; i < (uint32_t)n; i += 16u) {
@@ -77,7 +77,7 @@ __device__ __forceinline__ bool link_place(const LinkArgs& a, uint32_t r, LinkTa
 
 __global__ __launch_bounds__(kLinkBlock) void link_scan_kernel(LinkArgs a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t n = a.n_records_dev ? std::min<uint64_t>(a.n_records, *a.n_records_dev) : a.n_records;
+    const uint64_t n = a.rec.n_records_dev ? std::min<uint64_t>(a.rec.n_records, *a.rec.n_records_dev) : a.rec.n_records;
     const uint64_t stride = (uint64_t)gridDim.x * kLinkBlock;
     LinkTally t;
     for (uint64_t base = (uint64_t)blockIdx.x * kLinkBlock + wave * 64u; base < n; base += stride) {
@@ -133,10 +133,10 @@ __device__ __forceinline__ void link_count_rows(const LinkArgs& a, unsigned int*
             uint32_t cj = a.sites[j];
             if (cj >= end) break;                      // (the row's last site: no pair begins here or behind)
             if (cj - ci > a.max_dist) continue;
-            const uint32_t ba = row_base(e, n_mm, ci - cell0, sym_at(a.ref_words, ci));
+            const uint32_t ba = row_base(e, n_mm, ci - cell0, sym_at(a.ix.ref_words, ci));
             const uint64_t p0 = (uint64_t)a.pair_lo[i];
             for (;;) {
-                const uint32_t bb = row_base(e, n_mm, cj - cell0, sym_at(a.ref_words, cj));
+                const uint32_t bb = row_base(e, n_mm, cj - cell0, sym_at(a.ix.ref_words, cj));
                 const uint64_t at = (p0 + (j - i - 1u)) * 16u + ba * 4u + bb;
                 if (at < a.n_pairs * 16u) {            // (the host enumerated every pair that a row can cover)
                     if (kLds) atomicAdd(table + (uint32_t)at, 1u);
@@ -168,8 +168,8 @@ __global__ __launch_bounds__(kLinkBlock) void link_count_kernel(LinkArgs a) { li
 }  // namespace
 
 void launch_link_scan(const LinkArgs& a, int n_cus, hipStream_t stream) {
-    if (a.n_records == 0) return;
-    const uint64_t blocks = (a.n_records + kLinkBlock - 1) / kLinkBlock;
+    if (a.rec.n_records == 0) return;
+    const uint64_t blocks = (a.rec.n_records + kLinkBlock - 1) / kLinkBlock;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
     hipLaunchKernelGGL(link_scan_kernel, dim3(grid), dim3(kLinkBlock), 0, stream, a);
 }

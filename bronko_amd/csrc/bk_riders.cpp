@@ -1,0 +1,448 @@
+// bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
+// short insertions and deletions (bk_indels.hip) and linkage (bk_linkage.hip), with the anchor tables the last two share.
+// Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
+// push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
+// indels, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
+// by their declarations in bronko_hip.h).
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "bk_engine.h"
+
+static bk::RecordsView records_view(const Records& r) { return bk::RecordsView{r.words, r.lens, r.n, r.n_dev, r.stride_words}; }
+
+// ---- the sample's k-mer count table (bk_kmer_dump.hip) --------------------------------------------------------------
+int KmerDump::begin_sample(bk_engine* e) {
+    if (int rc = t.clear(e)) return rc;
+    BK_HIP(hipMemsetAsync(out.p, 0, out.n * sizeof(unsigned long long), e->stream));
+    upper[0] = upper[1] = 0; in_sample = true; finalized_mates = 0;
+    return BK_OK;
+}
+// bk_kmer_dump_enable: every k-mer of the batch into the count table, on the engine stream in front of the scan that reads the same records
+// (a staging slot is reused only after the stream has passed both)
+int KmerDump::push(bk_engine* e, int mate, const Records& r, uint64_t upper_new) {
+    if (int rc = t.ensure_room(e, out.p, upper_new)) return rc;
+    upper[mate] += upper_new;
+    bk::launch_kmer_dump_count(records_view(r), e->ix->k, (uint32_t)mate, t.keys.p, t.cnt.p, t.log2, out.p + 4, e->ix->n_cus, e->stream);
+    BK_HIP(hipGetLastError());
+    return t.note_fill(e, out.p);
+}
+// bk_kmer_dump_enable, at the end of a whole-sample finalize (asynchronous, so that samples in flight never wait between their reads
+// and their results): per mate file, the entries with ci <= count <= cx as (k-mer, min(count, cs)), padded with ~0 keys up to a
+// bound on the mate file's distinct keys (the sort's length must be known on the host), sorted by k-mer -- the padding sorts last.
+int KmerDump::finalize(bk_engine* e, int n_mates) {
+    if (!in_sample) return BK_OK;   // (enabled after this sample began: nothing was counted)
+    bk_engine::Span sp(e, 1);
+    // bounds on the keys in the table: the tallies of the last push when their copy has arrived (not waited for), else what the
+    // growth rule knows; the table's load stays below one half; and a mate file holds no more distinct k-mers than it was pushed
+    if (t.fill_pending && hipEventQuery(t.fill_ev) == hipSuccess) t.read_fill();
+    const uint64_t keys_upper = std::min<uint64_t>((1ull << t.log2) / 2, t.fill_known + t.fill_unknown_upper);
+    uint64_t bound[2] = {0, 0}, most = 1;
+    size_t tmp_bytes = 0;
+    for (int m = 0; m < n_mates; m++) {
+        bound[m] = std::max<uint64_t>(1, std::min<uint64_t>(keys_upper, upper[m]));
+        most = std::max(most, bound[m]);
+        size_t b = 0;
+        BK_HIP(bk::kmer_dump_sort(nullptr, b, sel_keys.p, keys[m].p, sel_cnt.p, cnt[m].p, bound[m], e->ix->k, e->stream));
+        tmp_bytes = std::max(tmp_bytes, b);
+    }
+    // every buffer is sized before the first launch (a buffer that grows is freed and allocated again)
+    if (sel_keys.n < most) { BK_HIP(sel_keys.alloc(most)); BK_HIP(sel_cnt.alloc(most)); }
+    for (int m = 0; m < n_mates; m++)
+        if (keys[m].n < bound[m]) { BK_HIP(keys[m].alloc(bound[m])); BK_HIP(cnt[m].alloc(bound[m])); }
+    if (sort_tmp.n < tmp_bytes) BK_HIP(sort_tmp.alloc(tmp_bytes));
+    for (int m = 0; m < n_mates; m++) {
+        BK_HIP(hipMemsetAsync(sel_keys.p, 0xff, bound[m] * sizeof(unsigned long long), e->stream));
+        bk::launch_kmer_dump_select(t.keys.p, t.cnt.p, t.log2, (uint32_t)m, e->params.ci, e->params.cs, e->params.cx, sel_keys.p, sel_cnt.p,
+                                    bound[m], out.p + 2 * m, e->stream);
+        size_t b = sort_tmp.n;
+        BK_HIP(bk::kmer_dump_sort(sort_tmp.p, b, sel_keys.p, keys[m].p, sel_cnt.p, cnt[m].p, bound[m], e->ix->k, e->stream));
+        n_sorted[m] = bound[m];
+    }
+    BK_HIP(hipGetLastError());
+    if (test_env("BK_DUMP_STATS"))   // measurement aid (testing build): the table's capacity and the sort's lengths
+        fprintf(stderr, "[bk] k-mer dump: table 2^%u slots, sorted %llu + %llu entries\n", t.log2, (unsigned long long)bound[0], (unsigned long long)bound[1]);
+    finalized_mates = n_mates;
+    return BK_OK;
+}
+
+int bk_kmer_dump_enable(bk_engine* e, uint32_t table_log2) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (table_log2 != 0 && (table_log2 < 10 || table_log2 > 31)) return fail(BK_ERR_INVALID, "table_log2 must be 0 or 10..31");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_kmer_dump_enable comes between samples");
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still read the table being replaced)
+    e->dump.reset();
+    if (table_log2 == 0) return BK_OK;
+    std::unique_ptr<KmerDump> d(new KmerDump());
+    BK_HIP(d->t.keys.alloc((size_t)1 << table_log2));
+    BK_HIP(d->t.cnt.alloc((size_t)1 << table_log2));
+    d->t.log2 = table_log2;
+    BK_HIP(d->t.h_fill.grow(bk::ktab_fill_words())); BK_HIP(d->t.fill_ev.create());
+    BK_HIP(d->out.alloc(8 + bk::ktab_fill_words()));
+    BK_HIP(hipMemset(d->out.p, 0, d->out.n * sizeof(unsigned long long)));
+    e->dump = std::move(d);
+    return BK_OK;
+}
+
+static int dump_results(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct) {
+    if (mate < 0 || mate > 1) return fail(BK_ERR_INVALID, "mate must be 0 or 1");
+    if (!e->dump || !e->dump->in_sample) return fail(BK_ERR_STATE, "the k-mer dump was not enabled for this sample (bk_kmer_dump_enable before bk_sample_begin)");
+    if (e->in_sample) return fail(BK_ERR_STATE, "the k-mer dump is read after bk_sample_finalize");
+    if (mate >= e->dump->finalized_mates)
+        return fail(BK_ERR_STATE, "mate file %d of this sample was not finalized by bk_sample_finalize (a sharded finalize keeps no k-mer dump)", mate);
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long o[8];
+    if (int rc = download(e, o, e->dump->out.p, 8)) return rc;
+    if (o[4] || o[2 * mate] > e->dump->n_sorted[mate]) { *n_kept = *n_distinct = UINT64_MAX; return BK_OK; }   // (only a table that could not grow past 2^31 slots)
+    *n_kept = o[2 * mate];
+    *n_distinct = o[2 * mate + 1];
+    return BK_OK;
+}
+
+int bk_kmer_dump_size(bk_engine* e, int mate, uint64_t* n_kept, uint64_t* n_distinct) {
+    if (!e || !n_kept || !n_distinct) return fail(BK_ERR_INVALID, "null argument");
+    return dump_results(e, mate, n_kept, n_distinct);
+}
+
+int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* counts, uint64_t cap) {
+    if (!e || ((!kmers || !counts) && cap)) return fail(BK_ERR_INVALID, "null argument");
+    uint64_t kept = 0, distinct = 0;
+    if (int rc = dump_results(e, mate, &kept, &distinct)) return rc;
+    if (kept == UINT64_MAX) return fail(BK_ERR_RANGE, "the k-mer count table overflowed at 2^31 slots: no dump for this sample");
+    const uint64_t n = std::min(cap, kept);
+    if (!n) return BK_OK;
+    std::vector<unsigned int> c32(n);
+    BK_HIP(hipMemcpyAsync(kmers, e->dump->keys[mate].p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    if (int rc = download(e, c32.data(), e->dump->cnt[mate].p, n)) return rc;
+    for (uint64_t i = 0; i < n; i++) counts[i] = c32[i];
+    return BK_OK;
+}
+
+// ---- placing records by anchor k-mers: what bk_indels_enable and bk_link_enable ask of the index and build from it -----------------
+static int anchor_index_check(const IndexTables& ix, const char* who) {
+    if (ix.W <= 0 || ix.n_full == 0) return fail(BK_ERR_INVALID, "%s: the index has no window of reference k-mers", who);
+    if (!ix.rc_words.p)   // (build_index_tables makes it with the binned scan's seed tables: fewer than 2^27 cells, at least k)
+        return fail(BK_ERR_UNSUPPORTED, "%s: the engine holds no reverse-complemented reference (it is made for a genome of k to 2^27 - 1 positions; this one has %llu)",
+                    who, (unsigned long long)ix.total_cells);
+    return BK_OK;
+}
+// the engine's anchor tables: the ones the other feature holds, else built here
+static int anchor_tables(bk_engine* e, const char* who, std::shared_ptr<AnchorTables>& out) {
+    if ((out = e->anchors.lock())) return BK_OK;
+    const IndexTables& ix = *e->ix;
+    std::shared_ptr<AnchorTables> t(new AnchorTables());
+    {   // a histogram of the ids over the cells: one bit per id that starts at exactly one cell
+        std::vector<uint32_t> id_at((size_t)ix.total_cells);
+        BK_HIP(hipMemcpy(id_at.data(), ix.id_at.p, id_at.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> seen(ix.n_full, 0);
+        for (uint32_t id : id_at) if (id < ix.n_full && seen[id] < 2) seen[id]++;
+        std::vector<uint32_t> bits(((size_t)ix.n_full + 31) / 32, 0u);
+        for (uint32_t id = 0; id < ix.n_full; id++) if (seen[id] == 1) bits[id >> 5] |= 1u << (id & 31u);
+        BK_HIP(t->unique_bits.upload(bits));
+    }
+    std::vector<uint32_t> lo;
+    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) lo.push_back((uint32_t)ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q]);
+    lo.push_back((uint32_t)ix.total_cells);
+    if (lo.size() < 2) return fail(BK_ERR_INVALID, "%s: the genome file has no sequence", who);
+    BK_HIP(t->seq_lo.upload(lo));
+    BK_HIP(t->nruns.upload(ix.h_nonacgt));
+    e->anchors = t;
+    out = std::move(t);
+    return BK_OK;
+}
+static bk::AnchorIndex anchor_index(const IndexTables& ix, const AnchorTables& t) {
+    bk::AnchorIndex a{};
+    a.kmer_pos = ix.kmer_pos.p; a.pilots = ix.pilots.p; a.m = ix.m; a.log2nb = ix.log2nb; a.log2p = ix.log2p; a.n_full = ix.n_full;
+    a.unique_bits = t.unique_bits.p;
+    a.ref_words = ix.ref_words.p + bk::scan_ref_pad_words(); a.rc_words = ix.rc_words.p + bk::scan_ref_pad_words();
+    a.total_cells = (uint32_t)ix.total_cells; a.k = ix.k;
+    a.seq_lo = t.seq_lo.p; a.n_seqs = (uint32_t)(t.seq_lo.n - 1);
+    a.nruns = t.nruns.p; a.n_nruns = (uint32_t)ix.h_nonacgt.size();
+    return a;
+}
+
+// ---- short insertions and deletions from the reads (bk_indels.hip) ------------------------------------------------
+// the sample starts from an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
+int Indels::begin_sample(bk_engine* e) {
+    BK_HIP(hipMemsetAsync(key0.p, 0xff, key0.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(key1.p, 0xff, key1.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
+    in_sample = true; summed = false; made = false;
+    return BK_OK;
+}
+// what every indel kernel is given (a.rec: the scan's batch)
+static bk::IndelArgs indel_args(const bk_engine* e) {
+    const Indels& d = *e->indels;
+    bk::IndelArgs a{};
+    a.ix = anchor_index(*e->ix, *d.anchors);
+    a.max_len = d.cfg.max_len; a.max_mismatches = d.cfg.max_mismatches;
+    a.key0 = d.key0.p; a.key1 = d.key1.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
+    a.span = d.span.p; a.tallies = d.tallies.p;
+    a.rows = d.rows.p; a.row_cap = d.rows.n;
+    return a;
+}
+// the records' anchors, spans and events (indel_scan_kernel), on the engine stream behind the scan of the same records
+int Indels::push(bk_engine* e, const Records& r) {
+    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
+    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_indels_enable: a batch of 2^31 records or more");
+    bk::IndelArgs a = indel_args(e); a.rec = records_view(r);
+    bk::launch_indel_scan(a, e->ix->n_cus, e->stream);
+    return BK_OK;
+}
+
+int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_indels_enable comes between samples");
+    const IndexTables& ix = *e->ix;
+    if (cfg) {
+        if (cfg->max_len < 1 || cfg->max_len > BK_INDEL_MAX_LEN) return fail(BK_ERR_INVALID, "bk_indels_enable: max_len must be 1..%d, got %u", BK_INDEL_MAX_LEN, cfg->max_len);
+        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_indels_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
+        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_indels_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
+        if (ix.n_files != 1)
+            return fail(BK_ERR_INVALID, "bk_indels_enable: the index has %d genome files; indels are called against an index of one genome file", ix.n_files);
+        if (int rc = anchor_index_check(ix, "bk_indels_enable")) return rc;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
+    e->indels.reset();
+    if (!cfg) return BK_OK;
+    std::unique_ptr<Indels> d(new Indels());
+    d->cfg = *cfg;
+    if (int rc = anchor_tables(e, "bk_indels_enable", d->anchors)) return rc;
+    const size_t slots = (size_t)1 << cfg->table_log2;
+    BK_HIP(d->key0.alloc(slots)); BK_HIP(d->key1.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
+    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
+    BK_HIP(d->tallies.alloc(8));
+    e->indels = std::move(d);
+    return BK_OK;
+}
+
+int bk_sample_indels(bk_engine* e, const bk_indel_params* p) {
+    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
+    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_indels: min_reads must be at least 1, got 0");
+    if (p->min_af_ppm > 1000000u) return fail(BK_ERR_INVALID, "bk_sample_indels: min_af_ppm must be 0..1000000, got %u", p->min_af_ppm);
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels comes after bk_sample_finalize");
+    if (!e->indels || !e->indels->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels: indels were not enabled for this sample (bk_indels_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_indels: bk_sample_finalize has not run for this sample");
+    Indels& d = *e->indels;
+    BK_HIP(hipSetDevice(e->device));
+    bk::IndelArgs a = indel_args(e);
+    a.min_reads = p->min_reads; a.min_af_ppm = p->min_af_ppm;
+    bk_engine::Span sp(e, 1);
+    if (!d.summed) { bk::launch_indel_span_prefix(a, e->stream); d.summed = true; }
+    BK_HIP(hipMemsetAsync(d.tallies.p + 5, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
+    bk::launch_indel_report(a, e->stream);
+    BK_HIP(hipGetLastError());
+    d.made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indels comes after this sample's bk_sample_indels");
+    Indels& d = *e->indels;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long t[8];
+    if (int rc = download(e, t, d.tallies.p, 8)) return rc;
+    summary->records = t[0]; summary->anchored = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->discordant = t[4];
+    summary->candidates = t[5]; summary->reported = t[6]; summary->overflow = t[7] ? 1 : 0;
+    if (t[7]) return fail(BK_ERR_INVALID, "bk_sample_download_indels: more than 2^%u distinct candidate events: enable indels with a larger table_log2", d.cfg.table_log2);
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[6], cap), d.rows.n);
+    if (n && records) return download(e, records, d.rows.p, (size_t)n);
+    return BK_OK;
+}
+
+int bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap) {
+    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indel_span comes after this sample's bk_sample_indels");
+    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_indel_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
+    BK_HIP(hipSetDevice(e->device));
+    return download(e, span, e->indels->span.p, (size_t)e->ix->total_cells);
+}
+
+// ---- which substitutions the same records carry (bk_linkage.hip) ----------------------------------------------------
+// the row stores that the sample outgrew: each is freed once the stream has passed the copy out of it (`wait`: now)
+static int link_free_old(Linkage& d, bool wait) {
+    std::vector<std::pair<uint4*, Event>> keep;
+    hipError_t err = hipSuccess;
+    for (auto& o : d.old) {
+        if (wait && err == hipSuccess) err = hipEventSynchronize(o.second);
+        if (err == hipSuccess && (wait || hipEventQuery(o.second) == hipSuccess)) (void)hipFree(o.first);
+        else keep.emplace_back(o.first, std::move(o.second));
+    }
+    d.old.swap(keep);
+    BK_HIP(err);
+    return BK_OK;
+}
+// the sample starts from an empty row store, zero tallies
+int Linkage::begin_sample(bk_engine* e) {
+    if (int rc = link_free_old(*this, true)) return rc;
+    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
+    rows_upper = 0; in_sample = true; made = false; n_sites = 0; n_pairs = 0;
+    return BK_OK;
+}
+// what both linkage kernels are given (a.rec: the scan's batch)
+static bk::LinkArgs link_args(const bk_engine* e) {
+    const Linkage& d = *e->linkage;
+    bk::LinkArgs a{};
+    a.ix = anchor_index(*e->ix, *d.anchors);
+    a.max_mismatches = d.cfg.max_mismatches; a.tallies = d.tallies.p;
+    a.rows = d.rows.p; a.row_cap = d.rows.n / 2;
+    a.sites = d.sites.p; a.pair_lo = d.pair_lo.p; a.n_sites = d.n_sites; a.max_dist = d.max_dist; a.n_pairs = d.n_pairs;
+    a.counts = d.counts.p;
+    return a;
+}
+// a row per placed record (link_scan_kernel), on the engine stream behind the scan of the same records
+int Linkage::push(bk_engine* e, const Records& r) {
+    if (!in_sample || r.n == 0) return BK_OK;      // (enabled after this sample began: it has no rows)
+    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_link_enable: a batch of 2^31 records or more");
+    const uint64_t need = rows_upper + r.n;       // (only the device knows how many of the records are placed: room for all of them)
+    if (need >= (1ull << 32)) return fail(BK_ERR_UNSUPPORTED, "bk_link_enable: a sample of 2^32 records or more (%llu)", (unsigned long long)need);
+    const uint64_t cap = rows.n / 2;
+    if (int rc = link_free_old(*this, false)) return rc;
+    if (need > cap) {   // a larger store: allocate, copy behind the scans so far; the old one stays until the stream has passed the copy
+        const uint64_t ncap = std::min<uint64_t>(std::max<uint64_t>(need, 2 * cap), 1ull << 32);
+        uint4* np = nullptr;
+        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&np), (size_t)ncap * 2 * sizeof(uint4));
+        if (err != hipSuccess) return fail(BK_ERR_HIP, "bk_link_enable: no memory for a row store of %llu rows: %s", (unsigned long long)ncap, hipGetErrorString(err));
+        const uint64_t filled = std::min<uint64_t>(rows_upper, cap);
+        if (filled) {
+            const hipError_t ce = hipMemcpyAsync(np, rows.p, (size_t)filled * 2 * sizeof(uint4), hipMemcpyDeviceToDevice, e->stream);
+            if (ce != hipSuccess) { (void)hipFree(np); return fail(BK_ERR_HIP, "bk_link_enable: copying the row store failed: %s", hipGetErrorString(ce)); }
+        }
+        Event passed;                                // behind the copy: the old store is free once the stream is here
+        hipError_t ee = passed.create();
+        if (ee == hipSuccess) ee = hipEventRecord(passed, e->stream);
+        if (ee != hipSuccess) { (void)hipStreamSynchronize(e->stream); (void)hipFree(np); return fail(BK_ERR_HIP, "bk_link_enable: hipEventRecord failed: %s", hipGetErrorString(ee)); }
+        old.emplace_back(rows.p, std::move(passed));
+        rows.p = np; rows.n = (size_t)ncap * 2;
+    }
+    rows_upper = need;
+    bk::LinkArgs a = link_args(e); a.rec = records_view(r);
+    bk::launch_link_scan(a, e->ix->n_cus, e->stream);
+    return BK_OK;
+}
+
+int bk_link_enable(bk_engine* e, const bk_link_config* cfg) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_link_enable comes between samples");
+    const IndexTables& ix = *e->ix;
+    if (cfg) {
+        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_link_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
+        if (cfg->initial_rows < 1 || cfg->initial_rows > (1ull << 32))
+            return fail(BK_ERR_INVALID, "bk_link_enable: initial_rows must be 1..2^32, got %llu", (unsigned long long)cfg->initial_rows);
+        if (ix.n_files != 1)
+            return fail(BK_ERR_INVALID, "bk_link_enable: the index has %d genome files; linkage is counted against an index of one genome file", ix.n_files);
+        if (int rc = anchor_index_check(ix, "bk_link_enable")) return rc;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
+    e->linkage.reset();
+    if (!cfg) return BK_OK;
+    std::unique_ptr<Linkage> d(new Linkage());
+    d->cfg = *cfg;
+    if (int rc = anchor_tables(e, "bk_link_enable", d->anchors)) return rc;
+    BK_HIP(d->rows.alloc((size_t)cfg->initial_rows * 2));
+    BK_HIP(d->tallies.alloc(4));
+    BK_HIP(hipMemsetAsync(d->tallies.p, 0, 4 * sizeof(unsigned long long), e->stream));
+    e->linkage = std::move(d);
+    return BK_OK;
+}
+
+int bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uint32_t max_dist) {
+    if (!e || (!cells && n_sites)) return fail(BK_ERR_INVALID, "null argument");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage comes after bk_sample_finalize");
+    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_linkage: bk_sample_finalize has not run for this sample");
+    if (n_sites > BK_LINK_MAX_SITES) return fail(BK_ERR_INVALID, "bk_sample_linkage: at most %d sites, got %u", BK_LINK_MAX_SITES, n_sites);
+    if (max_dist < 1 || max_dist > BK_LINK_MAX_DIST) return fail(BK_ERR_INVALID, "bk_sample_linkage: max_dist must be 1..%d, got %u", BK_LINK_MAX_DIST, max_dist);
+    const IndexTables& ix = *e->ix;
+    for (uint32_t i = 0; i < n_sites; i++) {
+        if (cells[i] >= ix.total_cells) return fail(BK_ERR_INVALID, "bk_sample_linkage: site %u is cell %u, the index has %llu", i, cells[i], (unsigned long long)ix.total_cells);
+        if (i && cells[i] <= cells[i - 1]) return fail(BK_ERR_INVALID, "bk_sample_linkage: the sites must be strictly ascending (site %u is cell %u behind cell %u)", i, cells[i], cells[i - 1]);
+    }
+    Linkage& d = *e->linkage;
+    // the pairs: i < j in one sequence, cell_j - cell_i <= max_dist -- for each i a stretch of j that starts at i + 1
+    std::vector<uint32_t> seq_end;               // end cell of every sequence of the genome file
+    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) seq_end.push_back((uint32_t)(ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q] + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q]));
+    std::vector<uint32_t> pair_lo(n_sites);
+    uint64_t n_pairs = 0;
+    for (uint32_t i = 0, j = 0, s = 0; i < n_sites; i++) {
+        while (s + 1 < seq_end.size() && cells[i] >= seq_end[s]) s++;
+        if (j < i + 1) j = i + 1;
+        while (j < n_sites && cells[j] < seq_end[s] && cells[j] - cells[i] <= max_dist) j++;   // (j never moves back: both bounds grow with i)
+        pair_lo[i] = (uint32_t)std::min<uint64_t>(n_pairs, 0xffffffffull);
+        n_pairs += j - (i + 1);
+    }
+    if (n_pairs > BK_LINK_MAX_PAIRS)
+        return fail(BK_ERR_INVALID, "bk_sample_linkage: %llu pairs of sites within %u cells, at most %u are counted", (unsigned long long)n_pairs, max_dist, BK_LINK_MAX_PAIRS);
+    BK_HIP(hipSetDevice(e->device));
+    // an earlier count may still read the sites, pair_lo, the counters and the pinned copies that are replaced here: wait for that
+    // launch alone -- nothing else of the stream's work is waited for
+    if (d.count_in_flight) { BK_HIP(hipEventSynchronize(d.counted)); d.count_in_flight = false; }
+    BK_HIP(d.h_sites.grow(std::max<size_t>(n_sites, 1))); BK_HIP(d.h_pair_lo.grow(std::max<size_t>(n_sites, 1)));
+    if (n_sites) { std::memcpy(d.h_sites.p, cells, n_sites * sizeof(uint32_t)); std::memcpy(d.h_pair_lo.p, pair_lo.data(), n_sites * sizeof(uint32_t)); }
+    d.n_sites = n_sites; d.max_dist = max_dist; d.n_pairs = n_pairs; d.made = false;
+    BK_HIP(grow(d.sites, n_sites)); BK_HIP(grow(d.pair_lo, n_sites)); BK_HIP(grow(d.counts, (size_t)n_pairs * 16));
+    bk_engine::Span sp(e, 1);
+    if (n_sites) {
+        BK_HIP(hipMemcpyAsync(d.sites.p, d.h_sites.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemcpyAsync(d.pair_lo.p, d.h_pair_lo.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    }
+    if (n_pairs) BK_HIP(hipMemsetAsync(d.counts.p, 0, (size_t)n_pairs * 16 * sizeof(unsigned int), e->stream));
+    bk::launch_link_count(link_args(e), d.rows_upper, ix.n_cus, e->stream);
+    BK_HIP(hipGetLastError());
+    BK_HIP(d.counted.create());
+    BK_HIP(hipEventRecord(d.counted, e->stream));
+    d.count_in_flight = true;
+    d.made = true;
+    return BK_OK;
+}
+
+static int link_finalized(bk_engine* e, const char* who) {
+    if (e->in_sample || !e->linkage || !e->linkage->in_sample || e->finalized_mates < 1)
+        return fail(BK_ERR_STATE, "%s comes after bk_sample_finalize of a sample that began with linkage enabled", who);
+    return BK_OK;
+}
+
+int bk_sample_download_linkage(bk_engine* e, bk_link_summary* summary, bk_link_pair* pairs, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_linkage")) return rc;
+    Linkage& d = *e->linkage;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long t[4];
+    if (int rc = download(e, t, d.tallies.p, 4)) return rc;
+    summary->records = t[0]; summary->placed = t[1]; summary->unplaced = t[2]; summary->discordant = t[3];
+    summary->n_pairs = d.made ? d.n_pairs : 0; summary->n_sites = d.made ? d.n_sites : 0; summary->max_dist = d.made ? d.max_dist : 0;
+    const uint64_t n = std::min<uint64_t>(summary->n_pairs, cap);
+    if (!n || !pairs) return BK_OK;
+    std::vector<unsigned int> counts((size_t)n * 16);
+    BK_HIP(hipMemcpy(counts.data(), d.counts.p, counts.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < d.n_sites && at < n; i++) {
+        const uint64_t end = i + 1 < d.n_sites ? d.h_pair_lo.p[i + 1] : d.n_pairs;
+        for (uint64_t p = d.h_pair_lo.p[i]; p < end && at < n; p++, at++) {
+            pairs[at].site_a = d.h_sites.p[i]; pairs[at].site_b = d.h_sites.p[i + 1 + (size_t)(p - d.h_pair_lo.p[i])];
+            std::memcpy(pairs[at].count, counts.data() + (size_t)p * 16, 16 * sizeof(uint32_t));
+        }
+    }
+    return BK_OK;
+}
+
+int bk_sample_download_link_rows(bk_engine* e, bk_link_row* rows, uint64_t cap) {
+    static_assert(sizeof(bk_link_row) == 2 * sizeof(uint4), "a row is two 16-byte stores");
+    if (!e || (!rows && cap)) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_link_rows")) return rc;
+    Linkage& d = *e->linkage;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long placed = 0;
+    if (int rc = download(e, &placed, d.tallies.p + 1, 1)) return rc;
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(placed, cap), d.rows.n / 2);
+    if (n) BK_HIP(hipMemcpy(rows, d.rows.p, (size_t)n * sizeof(bk_link_row), hipMemcpyDeviceToHost));
+    return BK_OK;
+}
