@@ -75,6 +75,10 @@ class IndelSummary(C.Structure):  # bk_indel_summary
                 ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class CodonSummary(C.Structure):  # bk_codon_summary
+    _fields_ = [("rows", C.c_uint64), ("n_codons", C.c_uint64), ("n_regions", C.c_uint32)]
+
+
 class LinkConfig(C.Structure):  # bk_link_config
     _fields_ = [("max_mismatches", C.c_uint32), ("initial_rows", C.c_uint64)]
 
@@ -107,6 +111,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
+           "bk_sample_codons", "bk_sample_download_codons",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -250,6 +255,10 @@ def load(testing=None):
     L.bk_sample_download_linkage.argtypes = [vp, C.POINTER(LinkSummary), vp, u64]
     L.bk_sample_download_link_rows.restype = C.c_int
     L.bk_sample_download_link_rows.argtypes = [vp, vp, u64]
+    L.bk_sample_codons.restype = C.c_int
+    L.bk_sample_codons.argtypes = [vp, vp, C.c_uint32]
+    L.bk_sample_download_codons.restype = C.c_int
+    L.bk_sample_download_codons.argtypes = [vp, C.POINTER(CodonSummary), vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

@@ -2,7 +2,7 @@
 // index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
 // packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
-// ride behind every scan: the k-mer dump, indels, linkage) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
+// ride behind every scan: the k-mer dump, indels, linkage and the codon count over linkage's rows) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -250,6 +250,21 @@ struct AnchorTables {
     DevBuf<uint2> nruns;                    // IndexTables::h_nonacgt
 };
 
+// bk_sample_codons: the region tables and the counters of the last call (bk_codons.hip).  Made by the first call, freed with the Linkage
+// whose row store it reads; its buffers grow and never shrink
+struct Codons {
+    DevBuf<uint4> sorted;                   // [regions] by first cell (bk_kernels.h CodonArgs::sorted)
+    DevBuf<uint2> regions;                  // [regions] the caller's order
+    DevBuf<unsigned int> cover_diff;        // [codons + 1]
+    DevBuf<unsigned int> counts;            // [codons][64]
+    PinnedBuf<uint4> h_sorted;              // pinned host copies: the uploads are asynchronous
+    PinnedBuf<uint2> h_regions;
+    Event counted;                          // behind the last count's kernels: the next bk_sample_codons replaces what they read
+    bool count_in_flight = false;
+    uint32_t n_regions = 0, n_codons = 0;
+    bool made = false;                      // the counters are this sample's (bk_sample_codons ran)
+};
+
 // bk_link_enable: the sample's row store (one bk_link_row per placed record), its tallies, and what the last bk_sample_linkage made
 struct Linkage {
     bk_link_config cfg{};
@@ -267,6 +282,7 @@ struct Linkage {
     uint64_t n_pairs = 0;
     bool in_sample = false;                 // enabled when the current / last sample began
     bool made = false;                      // the counters are this sample's (bk_sample_linkage ran)
+    std::unique_ptr<Codons> codons;         // bk_sample_codons (null: never called, no buffers)
     ~Linkage() { for (auto& o : old) (void)hipFree(o.first); }
     int begin_sample(bk_engine* e);         // (bk_riders.cpp)
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records, and behind the indels' pass

@@ -511,6 +511,21 @@ struct LinkArgs {
 constexpr uint32_t kLinkLdsPairs = 512;  // a counter table of at most this many pairs is privatised in LDS (32 KiB a workgroup)
 void launch_link_scan(const LinkArgs& a, int n_cus, hipStream_t stream);
 void launch_link_count(const LinkArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
+// bk_sample_codons: how many rows of bk_link_enable's store carry each of the 64 triplets at every codon of the caller's coding regions
+// (bk_codons.hip; the rule: include/bronko_hip.h)
+struct CodonArgs {
+    AnchorIndex ix;                      // ref_words only
+    const uint4* rows; uint64_t row_cap; // the sample's row store and its tallies: LinkArgs'
+    const unsigned long long* tallies;
+    const uint4* sorted;                 // [n_regions] by first cell: {cell0, n_codons, index of its first codon, max end cell of the regions up to here}
+    const uint2* regions;                // [n_regions] the caller's order: {cell0, index of its first codon}
+    uint32_t n_regions, n_codons;
+    unsigned int* cover_diff;            // [n_codons + 1] +1 at a row's first wholly covered codon of a region, -1 one behind its last
+    unsigned int* counts;                // [n_codons][64] the caller's codon numbering; triplet 16 b0 + 4 b1 + b2
+};
+constexpr uint32_t kCodonLdsCodons = 16384;   // a cover_diff of at most this many entries is privatised in LDS (64 KiB a workgroup)
+void launch_codon_count(const CodonArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
+void launch_codon_finish(const CodonArgs& a, hipStream_t stream);
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

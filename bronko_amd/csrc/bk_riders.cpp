@@ -1,5 +1,6 @@
 // bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
-// short insertions and deletions (bk_indels.hip) and linkage (bk_linkage.hip), with the anchor tables the last two share.
+// short insertions and deletions (bk_indels.hip) and linkage (bk_linkage.hip), with the anchor tables the last two share, and the codon
+// count that reads linkage's row store at the sample's end (bk_codons.hip).
 // Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
 // push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
 // indels, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
@@ -284,6 +285,7 @@ int Linkage::begin_sample(bk_engine* e) {
     if (int rc = link_free_old(*this, true)) return rc;
     BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
     rows_upper = 0; in_sample = true; made = false; n_sites = 0; n_pairs = 0;
+    if (codons) codons->made = false;
     return BK_OK;
 }
 // what both linkage kernels are given (a.rec: the scan's batch)
@@ -444,5 +446,95 @@ int bk_sample_download_link_rows(bk_engine* e, bk_link_row* rows, uint64_t cap) 
     if (int rc = download(e, &placed, d.tallies.p + 1, 1)) return rc;
     const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(placed, cap), d.rows.n / 2);
     if (n) BK_HIP(hipMemcpy(rows, d.rows.p, (size_t)n * sizeof(bk_link_row), hipMemcpyDeviceToHost));
+    return BK_OK;
+}
+
+// ---- the triplets the placed records carry at the codons of coding regions (bk_codons.hip) -----------------------------------------
+static bk::CodonArgs codon_args(const bk_engine* e) {
+    const Linkage& d = *e->linkage;
+    const Codons& c = *d.codons;
+    bk::CodonArgs a{};
+    a.ix = anchor_index(*e->ix, *d.anchors);
+    a.rows = d.rows.p; a.row_cap = d.rows.n / 2; a.tallies = d.tallies.p;
+    a.sorted = c.sorted.p; a.regions = c.regions.p; a.n_regions = c.n_regions; a.n_codons = c.n_codons;
+    a.cover_diff = c.cover_diff.p; a.counts = c.counts.p;
+    return a;
+}
+
+int bk_sample_codons(bk_engine* e, const bk_codon_region* regions, uint32_t n_regions) {
+    if (!e || (!regions && n_regions)) return fail(BK_ERR_INVALID, "null argument");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_codons comes after bk_sample_finalize");
+    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_codons: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_codons: bk_sample_finalize has not run for this sample");
+    if (n_regions > BK_CODON_MAX_REGIONS) return fail(BK_ERR_INVALID, "bk_sample_codons: at most %d regions, got %u", BK_CODON_MAX_REGIONS, n_regions);
+    const IndexTables& ix = *e->ix;
+    uint64_t n_codons = 0;
+    for (uint32_t i = 0; i < n_regions; i++) {
+        const uint64_t c0 = regions[i].cell0, end = c0 + 3ull * regions[i].n_codons;
+        if (regions[i].n_codons == 0) return fail(BK_ERR_INVALID, "bk_sample_codons: region %u has no codon", i);
+        if (end > ix.total_cells)
+            return fail(BK_ERR_INVALID, "bk_sample_codons: region %u ends at cell %llu, the index has %llu", i, (unsigned long long)end, (unsigned long long)ix.total_cells);
+        for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) {   // (one genome file: bk_link_enable)
+            const uint64_t lo = ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q], hi = lo + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q];
+            if (c0 >= lo && c0 < hi && end > hi)
+                return fail(BK_ERR_INVALID, "bk_sample_codons: region %u crosses a sequence border (cells %llu to %llu, its sequence ends at %llu)", i,
+                            (unsigned long long)c0, (unsigned long long)end, (unsigned long long)hi);
+        }
+        n_codons += regions[i].n_codons;
+    }
+    if (n_codons > BK_CODON_MAX_CODONS)
+        return fail(BK_ERR_INVALID, "bk_sample_codons: %llu codons in %u regions, at most %u are counted", (unsigned long long)n_codons, n_regions, BK_CODON_MAX_CODONS);
+    Linkage& d = *e->linkage;
+    if (!d.codons) d.codons.reset(new Codons());
+    Codons& c = *d.codons;
+    BK_HIP(hipSetDevice(e->device));
+    // an earlier count may still read the tables, the counters and the pinned copies that are replaced here: wait for it alone
+    if (c.count_in_flight) { BK_HIP(hipEventSynchronize(c.counted)); c.count_in_flight = false; }
+    c.made = false;
+    BK_HIP(c.h_sorted.grow(std::max<size_t>(n_regions, 1))); BK_HIP(c.h_regions.grow(std::max<size_t>(n_regions, 1)));
+    {   // the caller's order with each region's first codon; the same sorted by first cell, with the running maximum of the ends
+        std::vector<uint32_t> order(n_regions);
+        uint32_t base = 0;
+        for (uint32_t i = 0; i < n_regions; i++) { order[i] = i; c.h_regions.p[i] = make_uint2(regions[i].cell0, base); base += regions[i].n_codons; }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return regions[x].cell0 < regions[y].cell0; });
+        uint32_t reach = 0;
+        for (uint32_t i = 0; i < n_regions; i++) {
+            const bk_codon_region& r = regions[order[i]];
+            reach = std::max(reach, r.cell0 + 3u * r.n_codons);
+            c.h_sorted.p[i] = make_uint4(r.cell0, r.n_codons, c.h_regions.p[order[i]].y, reach);
+        }
+    }
+    c.n_regions = n_regions; c.n_codons = (uint32_t)n_codons;
+    BK_HIP(grow(c.sorted, n_regions)); BK_HIP(grow(c.regions, n_regions));
+    BK_HIP(grow(c.cover_diff, (size_t)n_codons + 1)); BK_HIP(grow(c.counts, (size_t)n_codons * 64));
+    bk_engine::Span sp(e, 1);
+    if (n_regions) {
+        BK_HIP(hipMemcpyAsync(c.sorted.p, c.h_sorted.p, n_regions * sizeof(uint4), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemcpyAsync(c.regions.p, c.h_regions.p, n_regions * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemsetAsync(c.cover_diff.p, 0, ((size_t)n_codons + 1) * sizeof(unsigned int), e->stream));
+        BK_HIP(hipMemsetAsync(c.counts.p, 0, (size_t)n_codons * 64 * sizeof(unsigned int), e->stream));
+    }
+    const bk::CodonArgs a = codon_args(e);
+    bk::launch_codon_count(a, d.rows_upper, ix.n_cus, e->stream);
+    bk::launch_codon_finish(a, e->stream);
+    BK_HIP(hipGetLastError());
+    BK_HIP(c.counted.create());
+    BK_HIP(hipEventRecord(c.counted, e->stream));
+    c.count_in_flight = true;
+    c.made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_codons(bk_engine* e, bk_codon_summary* summary, uint32_t* counts, uint64_t cap_codons) {
+    if (!e || (!summary && !counts) || (!counts && cap_codons)) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_codons")) return rc;
+    Linkage& d = *e->linkage;
+    const Codons* c = d.codons && d.codons->made ? d.codons.get() : nullptr;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long placed = 0;
+    if (int rc = download(e, &placed, d.tallies.p + 1, 1)) return rc;
+    if (summary) { summary->rows = placed; summary->n_codons = c ? c->n_codons : 0; summary->n_regions = c ? c->n_regions : 0; }
+    const uint64_t n = std::min<uint64_t>(c ? c->n_codons : 0, cap_codons);
+    if (n) BK_HIP(hipMemcpy(counts, c->counts.p, (size_t)n * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return BK_OK;
 }

@@ -496,6 +496,23 @@ class Engine:
         _check(self._L.bk_sample_download_link_rows(self.h, buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return link_rows(buf[:cap])
 
+    def sample_codons(self, regions):
+        """bk_sample_codons: for every codon of the regions [(cell0, n_codons), ...] (forward-strand cells, any order) the rows of the
+        finalized sample's store by the triplet they carry there, counted on the device (asynchronous); needs linkage_enable."""
+        arr = np.ascontiguousarray(np.asarray(regions, np.int64).reshape(-1, 2).astype(np.uint32))
+        _check(self._L.bk_sample_codons(self.h, arr.ctypes.data_as(C.c_void_p), len(arr)), self._L)
+
+    def download_codons(self, cap=None):
+        """(summary, counts) of sample_codons: counts[codon][16 b0 + 4 b1 + b2] as an (n, 64) uint32 array in the caller's codon
+        numbering, n = min(cap, summary.n_codons), all by default."""
+        summ = _ffi.CodonSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_codons(self.h, C.byref(summ), None, 0), self._L)
+            cap = int(summ.n_codons)
+        buf = np.zeros((max(1, cap), 64), np.uint32)
+        _check(self._L.bk_sample_download_codons(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, buf[:min(cap, int(summ.n_codons))]
+
     def regions_set(self, regions):
         """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
         arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])

@@ -207,6 +207,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--linkage: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.has_codons) {       // (likewise)
+        LOG_DEBUG(T, "--codons: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
     if (!shard_mode) shard_devices.clear();
     return shard_devices;
@@ -237,6 +241,8 @@ struct SampleData {
     bk_link_summary lsumm{};                              // --linkage
     std::vector<LinkSite> link_recs;
     std::vector<LinkPair> link_pairs;
+    bk_codon_summary csumm2{};                            // --codons
+    std::vector<uint32_t> codon_counts;
 };
 
 constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
@@ -254,6 +260,8 @@ struct CallRun {
     std::vector<Region> regions;                     // --regions / --region-window: resolved by open_index, every genome file's
     std::vector<bk_region> region_table;             // ... as bk_regions_set takes them
     size_t max_file_regions = 0;                     // regions of the genome file with the most
+    std::vector<CodonGene> genes;                    // --codons: resolved by open_index
+    std::vector<bk_codon_region> gene_table;         // ... as bk_sample_codons takes them
     int dump_threads = 1;                            // --keep-kmer-info: threads that format one sample's counts (set before the lanes start)
 
     // the samples, in input order; their files are read ahead from here on (ReadAhead): the index and the engine's tables take
@@ -289,6 +297,14 @@ struct CallRun {
             die(T, "--indels needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.linkage && ix.files.size() != 1)
             die(T, "--linkage needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.codons() && ix.files.size() != 1)
+            die(T, "--codons needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.codons()) {   // the BED lines against the CHROM tokens of the index.  Before any device is touched.
+            try { genes = resolve_codon_bed(ix, 0, cfg.codon_bed, cfg.codons_path); }
+            catch (const std::exception& e) { die(T, e.what()); }
+            for (const CodonGene& g : genes) gene_table.push_back(bk_codon_region{g.reg.cell0, g.reg.n_codons});
+            LOG_DEBUG(T, std::to_string(genes.size()) + " coding regions");
+        }
     }
     // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
     void resolve_regions() {
@@ -439,8 +455,8 @@ struct CallRun {
             const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
             hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
         }
-        if (cfg.linkage) {
-            const bk_link_config lc{cfg.link.max_mismatches, kLinkInitialRows};
+        if (cfg.row_store()) {   // (--codons reads --linkage's row store; alone it brings its own M, together the two are equal)
+            const bk_link_config lc{cfg.linkage ? cfg.link.max_mismatches : cfg.codon.max_mismatches, kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
         }
     }
@@ -541,6 +557,12 @@ struct CallRun {
             d.link_pairs.resize((size_t)d.lsumm.n_pairs);
             hip_check(bk_sample_download_linkage(e, &d.lsumm, reinterpret_cast<bk_link_pair*>(d.link_pairs.data()), d.link_pairs.size()), "bk_sample_download_linkage");
         }
+        if (cfg.codons()) {   // counted from the same rows, behind the calls: 256 bytes a codon travel
+            hip_check(bk_sample_codons(e, gene_table.data(), (uint32_t)gene_table.size()), "bk_sample_codons");
+            hip_check(bk_sample_download_codons(e, &d.csumm2, nullptr, 0), "bk_sample_download_codons");
+            d.codon_counts.resize((size_t)d.csumm2.n_codons * 64);
+            hip_check(bk_sample_download_codons(e, &d.csumm2, d.codon_counts.data(), d.csumm2.n_codons), "bk_sample_download_codons");
+        }
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
     uint64_t merge_mates(const std::vector<std::string>& mates, SampleData& d) const {
@@ -604,6 +626,11 @@ struct CallRun {
                 const uint64_t lines = write_linkage_tsv(a.output + "/" + stem + ".linkage.tsv", ix, best, d.link_recs, d.link_pairs, cfg.link);
                 LOG_INFO(T, "Linkage: " + std::to_string(d.lsumm.placed) + " of " + std::to_string(d.lsumm.records) + " records placed, " +
                                 std::to_string(d.lsumm.n_pairs) + " pairs counted, " + std::to_string(lines) + " lines written");
+            }
+            if (cfg.codons()) {     // (a sample without such a triplet: the header alone)
+                const uint64_t lines = write_codons_tsv(a.output + "/" + stem + ".codons.tsv", ix, best, genes, d.codon_counts, cfg.codon);
+                LOG_INFO(T, "Codons: " + std::to_string(d.csumm2.rows) + " placed records over " + std::to_string(d.csumm2.n_regions) + " regions, " +
+                                std::to_string(d.csumm2.n_codons) + " codons counted, " + std::to_string(lines) + " lines written");
             }
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }

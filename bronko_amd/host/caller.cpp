@@ -286,7 +286,7 @@ std::vector<BedLine> read_bed(const std::string& path) {
         if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
         const std::string where = path + ": line " + std::to_string(no);
         std::vector<std::string> col;
-        for (size_t a = 0; col.size() < 4;) {
+        for (size_t a = 0; col.size() < 6;) {
             const size_t b = line.find('\t', a);
             col.push_back(line.substr(a, b == std::string::npos ? b : b - a));
             if (b == std::string::npos) break;
@@ -296,6 +296,7 @@ std::vector<BedLine> read_bed(const std::string& path) {
         BedLine r;
         r.chrom = col[0]; r.line = no;
         r.name = col.size() > 3 && !col[3].empty() ? col[3] : ".";
+        if (col.size() > 5) r.strand = col[5];
         if (r.chrom.empty()) throw std::runtime_error(where + ": empty chrom column");
         if (!number(col[1], &r.start)) throw std::runtime_error(where + ": start '" + col[1] + "' is not a non-negative integer");
         if (!number(col[2], &r.end)) throw std::runtime_error(where + ": end '" + col[2] + "' is not a non-negative integer");

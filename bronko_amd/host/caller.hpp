@@ -79,6 +79,7 @@ void write_consensus_fasta(const std::string& out_path, const std::string& stem,
 // come from the device (region_depth_kernel); region_depths is its twin for the tests that need no GPU.
 struct BedLine {                     // one data line of a BED file: columns 1-3, column 4 or "."
     std::string chrom, name;
+    std::string strand;              // column 6 as the file gives it, "" when absent: read by --codons alone (codons.hpp)
     uint64_t start = 0, end = 0;
     size_t line = 0;                 // 1-based, as an editor counts
 };
@@ -94,7 +95,7 @@ struct RegionReport {
 };
 constexpr size_t kMaxBedRegions = 65536;          // data lines of a --regions file
 constexpr uint64_t kMaxRegions = 1ull << 22;      // BK_MAX_REGIONS: resolved regions, windows
-// The data lines of a BED file, plain or gzip: tab-separated chrom, 0-based start, end (exclusive), optional name; further columns
+// The data lines of a BED file, plain or gzip: tab-separated chrom, 0-based start, end (exclusive), optional name; column 6 is kept as it is and never looked at here, other columns
 // are ignored, blank lines and lines beginning '#', "track" or "browser" are skipped, a trailing CR is tolerated.  Throws with the
 // file and the line named: a missing column, a start or end that is no number, start >= end, more than kMaxBedRegions lines.
 std::vector<BedLine> read_bed(const std::string& path);

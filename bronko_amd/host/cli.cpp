@@ -74,7 +74,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--linkage]\n"
-          "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
+          "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -108,7 +109,13 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    many of the reads that cover both positions carry neither, the first, the second or both\n"
           "  --link-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8\n"
           "  --link-max-dist D        positions a pair may be apart; 1..65519, default 1000\n"
-          "  --link-min-reads N       reads that cover both positions a pair needs to be written; at least 1, default 1\n", stderr);
+          "  --link-min-reads N       reads that cover both positions a pair needs to be written; at least 1, default 1\n"
+          "  --codons BED      write to <DIR>/<stem>.codons.tsv, per codon of the coding regions of BED (an index of one genome file; chrom,\n"
+          "                    0-based start, end, name, score, strand; end - start a multiple of 3; at most 4096 regions, 262144 codons),\n"
+          "                    the triplets other than the reference's that whole reads carry there, translated, with count, cover and freq\n"
+          "  --codon-min-reads N      reads that carry a triplet for it to be written; at least 1, default 5\n"
+          "  --codon-min-freq F       count / cover a triplet needs to be written; 0..1, default the value of --min-af\n"
+          "  --codon-max-mismatches M substitutions a read may have to be counted; 0..8, default 8 (with --linkage: equal to its M)\n", stderr);
     exit(code);
 }
 
@@ -256,6 +263,17 @@ Args parse_args(int argc, char** argv) {
             else if (opt == "--link-max-dist") { a.link_max_dist = x; a.has_link_max_dist = true; }
             else { a.link_min_reads = x; a.has_link_min_reads = true; }
         }
+        else if (opt == "--codons") { a.codons = one(); a.has_codons = true; }
+        else if (opt == "--codon-min-reads" || opt == "--codon-max-mismatches") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--codon-min-reads") { a.codon_min_reads = x; a.has_codon_min_reads = true; }
+            else { a.codon_max_mismatches = x; a.has_codon_max_mismatches = true; }
+        }
+        else if (opt == "--codon-min-freq") { a.codon_min_freq = to_double(opt, one()); a.has_codon_min_freq = true; }
         else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
         else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
         else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
@@ -455,6 +473,20 @@ void check_call_args(const Args& a) {   // call.rs:30-136
         snprintf(buf, sizeof buf, "--indel-min-af must be between 0 and 1, got %g", a.indel_min_af);
         die(T, buf);
     }
+    if (a.has_codon_min_reads && !a.has_codons) die(T, "--codon-min-reads needs --codons");
+    if (a.has_codon_min_freq && !a.has_codons) die(T, "--codon-min-freq needs --codons");
+    if (a.has_codon_max_mismatches && !a.has_codons) die(T, "--codon-max-mismatches needs --codons");
+    if (a.has_codons && a.codons.empty()) die(T, "--codons needs a BED file");
+    if (a.codon_min_reads < 1) die(T, "--codon-min-reads must be at least 1, got " + std::to_string(a.codon_min_reads));
+    if (a.codon_max_mismatches < 0 || a.codon_max_mismatches > kLinkMaxMismatches) die(T, "--codon-max-mismatches must be between 0 and 8, got " + std::to_string(a.codon_max_mismatches));
+    if (a.has_codon_min_freq && !(a.codon_min_freq >= 0.0 && a.codon_min_freq <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "--codon-min-freq must be between 0 and 1, got %g", a.codon_min_freq);
+        die(T, buf);
+    }
+    if (a.has_codons && a.linkage && a.codon_max_mismatches != a.link_max_mismatches)   // (one row store, one M)
+        die(T, "--linkage and --codons count the same placed reads: --link-max-mismatches (" + std::to_string(a.link_max_mismatches) + ") and --codon-max-mismatches (" +
+                   std::to_string(a.codon_max_mismatches) + ") must be equal");
 }
 
 // the checked arguments -> what the readers and the per-sample code work from; the primer file and the regions file are read and the adapters are
@@ -495,6 +527,13 @@ CallConfig make_call_config(const Args& a) {
     c.indel.min_af_ppm = (uint32_t)llround((a.has_indel_min_af ? a.indel_min_af : a.min_af) * 1e6);
     c.linkage = a.linkage;
     c.link.max_mismatches = (uint32_t)a.link_max_mismatches; c.link.max_dist = (uint32_t)a.link_max_dist; c.link.min_reads = (uint64_t)a.link_min_reads;
+    if (a.has_codons) {   // (like the regions file: the chrom names meet the index's in call_samples)
+        try { c.codon_bed = read_codon_bed(a.codons); }
+        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the codons file"); }
+        c.codons_path = a.codons;
+    }
+    c.codon.max_mismatches = (uint32_t)a.codon_max_mismatches; c.codon.min_reads = (uint64_t)a.codon_min_reads;
+    c.codon.min_freq = a.has_codon_min_freq ? a.codon_min_freq : a.min_af;
     return c;
 }
 

@@ -9,6 +9,7 @@
 
 #include "../../include/bronko_hip.h"
 #include "caller.hpp"
+#include "codons.hpp"
 #include "indels.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
@@ -72,6 +73,11 @@ struct Args {
     long link_max_mismatches = 8;   // --link-max-mismatches: substitutions a placed record may have (0..8)
     long link_max_dist = 1000;      // --link-max-dist: pairs of substitutions at most this far apart are counted (1..65519)
     long link_min_reads = 1;        // --link-min-reads: records that cover both positions a pair needs to be written
+    std::string codons;             // --codons: BED file of the coding regions whose codons go to <DIR>/<stem>.codons.tsv (empty: none)
+    bool has_codons = false, has_codon_min_reads = false, has_codon_min_freq = false, has_codon_max_mismatches = false;
+    long codon_min_reads = 5;       // --codon-min-reads: records that carry a triplet for it to be written
+    double codon_min_freq = 0.03;   // --codon-min-freq: count / cover a triplet needs to be written (default: --min-af)
+    long codon_max_mismatches = 8;  // --codon-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with --linkage)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -111,6 +117,13 @@ struct CallConfig {
     // --linkage: bk_link_enable / bk_sample_linkage and the values the .linkage.tsv header prints
     bool linkage = false;
     LinkParams link;
+    // --codons: the file's lines (resolved against the index once it is open, call_run.cpp), bk_sample_codons and the values the
+    // .codons.tsv header prints; codon.max_mismatches is the row store's when --linkage is not given (equal to link's when it is)
+    std::string codons_path;
+    std::vector<BedLine> codon_bed;
+    CodonParams codon;
+    bool codons() const { return !codons_path.empty(); }
+    bool row_store() const { return linkage || codons(); }   // bk_link_enable
     bool region_report() const { return !regions_path.empty() || region_window > 0; }
     // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
     bool trims() const { return !primers.empty() || !adapters.empty(); }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "caller.hpp"
+#include "codons.hpp"
 #include "indels.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
@@ -303,6 +304,69 @@ int bh_write_linkage_tsv(const void* h, int file_id, const char* path, const uin
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+
+// ---- --codons: the host twin of the engine's codon count, the BED reader and the writer (codons.cpp) -----------------------------
+// regs: n_regions x {cell0, n_codons}; counts: [codons of all regions][64], the caller's room for them given as cap_codons
+int bh_codon_count(const void* h, int file_id, const void* rows, uint64_t n_rows, const uint32_t* regs, uint64_t n_regions, uint64_t cap_codons, uint32_t* counts,
+                   uint64_t* n_codons) {
+    try {
+        static_assert(sizeof(bronko::CodonRegion) == 8, "CodonRegion is bk_codon_region");
+        const auto* rw = static_cast<const bronko::LinkRow*>(rows);
+        std::vector<bronko::CodonRegion> rg((size_t)n_regions);
+        for (uint64_t i = 0; i < n_regions; i++) { rg[i].cell0 = regs[2 * i]; rg[i].n_codons = regs[2 * i + 1]; }
+        const std::vector<uint32_t> c = bronko::codon_count(*static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::LinkRow>(rw, rw + n_rows), rg);
+        if (n_codons) *n_codons = c.size() / 64;
+        if (counts) std::memcpy(counts, c.data(), (size_t)std::min<uint64_t>(cap_codons * 64, c.size()) * sizeof(uint32_t));
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// genes travel as [n][5] u32 (cell0, n_codons, seq, start, 1 for the '-' strand), their names joined by '\n'
+namespace {
+std::vector<bronko::CodonGene> genes_of(const uint32_t* genes, const char* names, uint64_t n) {
+    std::vector<bronko::CodonGene> out((size_t)n);
+    const char* at = names;
+    for (uint64_t i = 0; i < n; i++) {
+        out[i].reg.cell0 = genes[i * 5]; out[i].reg.n_codons = genes[i * 5 + 1]; out[i].seq = genes[i * 5 + 2]; out[i].start = genes[i * 5 + 3];
+        out[i].strand = genes[i * 5 + 4] ? '-' : '+';
+        out[i].name = ".";
+        if (at) {
+            const char* nl = strchr(at, '\n');
+            out[i].name = nl ? std::string(at, nl) : std::string(at);
+            at = nl ? nl + 1 : nullptr;
+        }
+    }
+    return out;
+}
+}  // namespace
+// read_codon_bed + resolve_codon_bed; *n genes, *names_len bytes of joined names, both written only where they fit cap / names_cap
+int bh_codon_bed(const void* h, int file_id, const char* path, uint64_t cap, uint32_t* genes, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
+    try {
+        const std::vector<bronko::CodonGene> r = bronko::resolve_codon_bed(*static_cast<const bronko::Index*>(h), file_id, bronko::read_codon_bed(path), path);
+        std::string joined;
+        for (size_t i = 0; i < r.size(); i++) joined += (i ? "\n" : "") + r[i].name;
+        *n = r.size();
+        if (names_len) *names_len = joined.size() + 1;
+        if (genes && r.size() <= cap)
+            for (size_t i = 0; i < r.size(); i++) {
+                genes[i * 5] = r[i].reg.cell0; genes[i * 5 + 1] = r[i].reg.n_codons; genes[i * 5 + 2] = r[i].seq; genes[i * 5 + 3] = r[i].start;
+                genes[i * 5 + 4] = r[i].strand == '-' ? 1u : 0u;
+            }
+        if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int bh_write_codons_tsv(const void* h, int file_id, const char* path, const uint32_t* genes, const char* names, uint64_t n, const uint32_t* counts, uint64_t n_codons,
+                        uint32_t max_mismatches, uint64_t min_reads, double min_freq, uint64_t* lines) {
+    try {
+        bronko::CodonParams p;
+        p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_freq = min_freq;
+        const uint64_t w = bronko::write_codons_tsv(path, *static_cast<const bronko::Index*>(h), file_id, genes_of(genes, names, n),
+                                                    std::vector<uint32_t>(counts, counts + n_codons * 64), p);
+        if (lines) *lines = w;
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int bh_translate(const char* triplet) { return bronko::translate(triplet); }
 
 void bh_clean_sample_id(const char* path, char* buf, size_t n) {
     const std::string s = bronko::clean_sample_id(path);

@@ -404,3 +404,68 @@ def write_linkage_tsv(path, ix, file_id, recs, pairs, max_mismatches=8, max_dist
                               int(min_reads), C.byref(lines)) != 0:
         raise _host_error(L)
     return lines.value
+
+
+# ---- --codons: the host twin of the engine's codon count, the BED reader and the writer (codons.cpp) ------------------------------
+def _codon_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_codons_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_codon_count.restype = C.c_int
+        L.bh_codon_count.argtypes = [vp, C.c_int, vp, u64, vp, u64, u64, vp, C.POINTER(u64)]
+        L.bh_codon_bed.restype = C.c_int
+        L.bh_codon_bed.argtypes = [vp, C.c_int, C.c_char_p, u64, vp, C.c_char_p, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bh_write_codons_tsv.restype = C.c_int
+        L.bh_write_codons_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, C.c_char_p, u64, vp, u64, u32, u64, C.c_double, C.POINTER(u64)]
+        L.bh_translate.restype = C.c_int
+        L.bh_translate.argtypes = [C.c_char_p]
+        L._codons_ready = True
+    return L
+
+
+def codon_count(ix, file_id, raw_rows, regions):
+    """The host twin of the codon kernels (codons.cpp codon_count): counts[codon][16 b0 + 4 b1 + b2] as an (n_codons, 64) uint32 array
+    for the regions [(cell0, n_codons), ...], their codons numbered in the order given; raw_rows as link_rows gives them."""
+    L = _codon_lib()
+    raw = np.ascontiguousarray(np.asarray(raw_rows, np.uint8).reshape(-1, 32))
+    rg = np.ascontiguousarray(np.asarray(regions, np.int64).reshape(-1, 2).astype(np.uint32))
+    n = int(rg[:, 1].sum())
+    out = np.zeros((max(1, n), 64), np.uint32)
+    got = C.c_uint64()
+    if L.bh_codon_count(ix.h, file_id, raw.ctypes.data, len(raw), rg.ctypes.data, len(rg), n, out.ctypes.data, C.byref(got)) != 0:
+        raise _host_error(L)
+    assert got.value == n
+    return out[:n]
+
+
+def codon_bed(ix, file_id, path):
+    """A --codons BED file read and resolved against genome file file_id (codons.cpp read_codon_bed, resolve_codon_bed):
+    [(cell0, n_codons, seq, start, strand, name)] in the file's order; RuntimeError with the file and the line named otherwise."""
+    L = _codon_lib()
+    n, nl = C.c_uint64(), C.c_uint64()
+    if L.bh_codon_bed(ix.h, file_id, path.encode(), 0, None, None, 0, C.byref(n), C.byref(nl)) != 0:
+        raise _host_error(L)
+    genes = np.zeros((max(1, n.value), 5), np.uint32)
+    names = C.create_string_buffer(max(1, nl.value))
+    if L.bh_codon_bed(ix.h, file_id, path.encode(), n.value, genes.ctypes.data, names, nl.value, C.byref(n), C.byref(nl)) != 0:
+        raise _host_error(L)
+    nm = names.value.decode().split("\n") if n.value else []
+    return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), "-" if r[4] else "+", nm[i]) for i, r in enumerate(genes[:n.value])]
+
+
+def write_codons_tsv(path, ix, file_id, genes, counts, max_mismatches=8, min_reads=5, min_freq=0.03):
+    """The --codons writer (codons.cpp write_codons_tsv): genes as codon_bed gives them, counts (n_codons, 64); returns the lines written."""
+    L = _codon_lib()
+    g = np.ascontiguousarray(np.array([[c0, nc, seq, start, 1 if strand == "-" else 0] for c0, nc, seq, start, strand, _ in genes], np.int64).reshape(-1, 5).astype(np.uint32))
+    names = "\n".join(name for *_, name in genes).encode()
+    cnt = np.ascontiguousarray(np.asarray(counts, np.uint32).reshape(-1, 64))
+    lines = C.c_uint64()
+    if L.bh_write_codons_tsv(ix.h, file_id, path.encode(), g.ctypes.data, names, len(genes), cnt.ctypes.data, len(cnt), int(max_mismatches), int(min_reads),
+                             float(min_freq), C.byref(lines)) != 0:
+        raise _host_error(L)
+    return lines.value
+
+
+def translate(triplet):
+    """The standard code of three letters ACGT (codons.cpp translate)."""
+    return chr(_codon_lib().bh_translate(triplet.encode()))

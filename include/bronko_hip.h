@@ -561,6 +561,44 @@ int  bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, ui
 int  bk_sample_download_linkage(bk_engine* e, bk_link_summary* summary, bk_link_pair* pairs, uint64_t cap);
 int  bk_sample_download_link_rows(bk_engine* e, bk_link_row* rows, uint64_t cap);
 
+/* ---- which triplets the reads carry at the codons of coding regions (`bronko call --codons`; additive, still v8) ------------------
+ * Two substitutions inside one codon give another amino acid together than either gives alone, so amino-acid changes cannot be read
+ * off the substitution calls; the rows of bk_link_enable's store can say it exactly.  A second consumer of that store: for every
+ * codon of every region the caller names, how many rows carry each of the 64 triplets.  The terms row, covers and base at a cell are
+ * those of bk_link_enable above: a placed record covers [cell0, cell0 + n), its base at cell c is its mismatch there, else the
+ * reference's; rows of both mate files count alike, overlapping mates count twice.  The rule, all of it integer arithmetic:
+ *   region     {cell0, n_codons}: the forward-strand cells [cell0, cell0 + 3 n_codons); n_codons >= 1, all cells inside one sequence and
+ *              below bk_total_cells.  Regions come in any order and may overlap, nest, repeat and lie in different frames.  At most
+ *              BK_CODON_MAX_REGIONS regions and BK_CODON_MAX_CODONS codons in total.
+ *   codon      the codons of all regions are numbered consecutively in the order the regions were given; codon i of a region is the
+ *              cells cell0 + 3 i .. cell0 + 3 i + 2.
+ *   counters   count[codon][16 b0 + 4 b1 + b2], u32 = the rows that cover all three cells of the codon and have the bases b0, b1, b2
+ *              (A C G T = 0 1 2 3) at them in ascending cell order.  A row that covers one or two cells of a codon counts nowhere for
+ *              that codon.  The device counts forward-strand triplets only: a gene's strand is the host's business.  A reference
+ *              cell that is not ACGT lies under no row: a codon that holds one has 64 zeros.
+ *   bk_sample_codons          the row store is bk_link_enable's, there is no enable call of its own.  After the sample's
+ *                             bk_sample_finalize (BK_ERR_STATE inside a sample, before any finalize, and when linkage was not
+ *                             enabled as the sample began).  BK_ERR_INVALID: a region of no codon, one that ends beyond
+ *                             bk_total_cells or crosses a sequence border (the message names the region's index), more than
+ *                             BK_CODON_MAX_REGIONS regions or BK_CODON_MAX_CODONS codons (it names the count); nothing is launched.
+ *                             n_regions = 0 is valid: an empty table.  Zeroes its buffers and counts (codon_count_kernel,
+ *                             codon_finish_kernel); asynchronous on the engine's stream: the regions are staged in pinned memory,
+ *                             and the host waits for nothing but an earlier count whose buffers the call replaces.  May be repeated
+ *                             with other regions on the same sample.  Independent of bk_sample_linkage: either order, neither
+ *                             disturbs the other's results.  Its buffers are made by the first call, grow and never shrink, and are
+ *                             freed with the row store; an engine that never calls it allocates and launches nothing; a fork has
+ *                             none of its parent's.
+ *   bk_sample_download_codons after the sample's finalize; synchronises; the summary (rows = the store's placed rows) and
+ *                             min(cap_codons, n_codons) counter rows of 64 in the caller's codon numbering.  counts may be NULL with
+ *                             cap_codons 0; both pointers NULL is BK_ERR_INVALID.  Before the sample's first bk_sample_codons there
+ *                             are the rows and no codons. */
+#define BK_CODON_MAX_REGIONS 4096
+#define BK_CODON_MAX_CODONS (1u << 18)
+typedef struct { uint32_t cell0, n_codons; } bk_codon_region;
+typedef struct { uint64_t rows, n_codons; uint32_t n_regions; } bk_codon_summary;   /* rows = the store's placed rows */
+int  bk_sample_codons(bk_engine* e, const bk_codon_region* regions, uint32_t n_regions);
+int  bk_sample_download_codons(bk_engine* e, bk_codon_summary* summary, uint32_t* counts /* [n_codons][64] */, uint64_t cap_codons);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
