@@ -79,6 +79,10 @@ class CodonSummary(C.Structure):  # bk_codon_summary
     _fields_ = [("rows", C.c_uint64), ("n_codons", C.c_uint64), ("n_regions", C.c_uint32)]
 
 
+class HapSummary(C.Structure):  # bk_hap_summary
+    _fields_ = [("rows", C.c_uint64), ("entries", C.c_uint64), ("dropped", C.c_uint64), ("n_regions", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
 class LinkConfig(C.Structure):  # bk_link_config
     _fields_ = [("max_mismatches", C.c_uint32), ("initial_rows", C.c_uint64)]
 
@@ -111,7 +115,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
-           "bk_sample_codons", "bk_sample_download_codons",
+           "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -259,6 +263,10 @@ def load(testing=None):
     L.bk_sample_codons.argtypes = [vp, vp, C.c_uint32]
     L.bk_sample_download_codons.restype = C.c_int
     L.bk_sample_download_codons.argtypes = [vp, C.POINTER(CodonSummary), vp, u64]
+    L.bk_sample_haplotypes.restype = C.c_int
+    L.bk_sample_haplotypes.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.bk_sample_download_haplotypes.restype = C.c_int
+    L.bk_sample_download_haplotypes.argtypes = [vp, C.POINTER(HapSummary), vp, vp, vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

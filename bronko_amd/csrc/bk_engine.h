@@ -2,7 +2,7 @@
 // index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
 // packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
-// ride behind every scan: the k-mer dump, indels, linkage and the codon count over linkage's rows) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
+// ride behind every scan: the k-mer dump, indels, linkage and the codon and haplotype counts over linkage's rows) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -265,6 +265,23 @@ struct Codons {
     bool made = false;                      // the counters are this sample's (bk_sample_codons ran)
 };
 
+// bk_sample_haplotypes: the region tables, the hot counters, the table of distinct haplotypes and the entry list of the last call
+// (bk_haplotypes.hip).  Made by the first call, freed with the Linkage whose row store it reads; its buffers grow and never shrink
+struct Haplotypes {
+    DevBuf<uint2> sorted;                   // [regions] by first cell (bk_kernels.h HapArgs::sorted)
+    DevBuf<uint2> regions;                  // [regions] the caller's order
+    DevBuf<unsigned int> hot;               // [regions][2] cover, ref_count
+    DevBuf<unsigned long long> owner;       // [2^table_log2]
+    DevBuf<unsigned int> count;             // [2^table_log2]
+    DevBuf<unsigned long long> tallies;     // [2] entries, dropped
+    DevBuf<bk_hap_entry> entries;           // [2^table_log2]
+    PinnedBuf<uint2> h_sorted, h_regions;   // pinned host copies: the uploads are asynchronous
+    Event counted;                          // behind the last count's kernels: the next bk_sample_haplotypes replaces what they read
+    bool count_in_flight = false;
+    uint32_t n_regions = 0, table_log2 = 0;
+    bool made = false;                      // the results are this sample's (bk_sample_haplotypes ran)
+};
+
 // bk_link_enable: the sample's row store (one bk_link_row per placed record), its tallies, and what the last bk_sample_linkage made
 struct Linkage {
     bk_link_config cfg{};
@@ -283,6 +300,7 @@ struct Linkage {
     bool in_sample = false;                 // enabled when the current / last sample began
     bool made = false;                      // the counters are this sample's (bk_sample_linkage ran)
     std::unique_ptr<Codons> codons;         // bk_sample_codons (null: never called, no buffers)
+    std::unique_ptr<Haplotypes> haps;       // bk_sample_haplotypes (likewise)
     ~Linkage() { for (auto& o : old) (void)hipFree(o.first); }
     int begin_sample(bk_engine* e);         // (bk_riders.cpp)
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records, and behind the indels' pass

@@ -526,6 +526,23 @@ struct CodonArgs {
 constexpr uint32_t kCodonLdsCodons = 16384;   // a cover_diff of at most this many entries is privatised in LDS (64 KiB a workgroup)
 void launch_codon_count(const CodonArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
 void launch_codon_finish(const CodonArgs& a, hipStream_t stream);
+// bk_sample_haplotypes: which lists of substitutions the rows of bk_link_enable's store carry across each of the caller's regions
+// (bk_haplotypes.hip; the rule: include/bronko_hip.h)
+typedef bk_hap_entry HapEntryDev;
+struct HapArgs {
+    const uint4* rows; uint64_t row_cap; // the sample's row store: LinkArgs'
+    const unsigned long long* placed;    // ... and the rows in it (LinkArgs::tallies + 1)
+    const uint2* sorted;                 // [n_regions] by first cell: {cell0, len | the caller's index << 16}
+    const uint2* regions;                // [n_regions] the caller's order: {cell0, len}
+    uint32_t n_regions, table_log2;
+    unsigned int* hot;                   // [n_regions][2] cover, ref_count
+    unsigned long long* owner;           // [2^table_log2] 0 = free, else ((row << 12) | region) + 1 of the row that claimed the slot
+    unsigned int* count;                 // [2^table_log2]
+    unsigned long long* tallies;         // [2] entries (hap_finish_kernel), dropped (hap_count_kernel)
+    HapEntryDev* entries; uint64_t entry_cap;
+};
+void launch_hap_count(const HapArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
+void launch_hap_finish(const HapArgs& a, hipStream_t stream);
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

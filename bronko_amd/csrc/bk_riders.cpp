@@ -1,6 +1,6 @@
 // bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
 // short insertions and deletions (bk_indels.hip) and linkage (bk_linkage.hip), with the anchor tables the last two share, and the codon
-// count that reads linkage's row store at the sample's end (bk_codons.hip).
+// and haplotype counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip).
 // Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
 // push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
 // indels, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
@@ -286,6 +286,7 @@ int Linkage::begin_sample(bk_engine* e) {
     BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
     rows_upper = 0; in_sample = true; made = false; n_sites = 0; n_pairs = 0;
     if (codons) codons->made = false;
+    if (haps) haps->made = false;
     return BK_OK;
 }
 // what both linkage kernels are given (a.rec: the scan's batch)
@@ -536,5 +537,123 @@ int bk_sample_download_codons(bk_engine* e, bk_codon_summary* summary, uint32_t*
     if (summary) { summary->rows = placed; summary->n_codons = c ? c->n_codons : 0; summary->n_regions = c ? c->n_regions : 0; }
     const uint64_t n = std::min<uint64_t>(c ? c->n_codons : 0, cap_codons);
     if (n) BK_HIP(hipMemcpy(counts, c->counts.p, (size_t)n * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BK_OK;
+}
+
+// ---- the lists of substitutions the placed records carry across whole regions (bk_haplotypes.hip) ----------------------------------
+static bk::HapArgs hap_args(const bk_engine* e) {
+    const Linkage& d = *e->linkage;
+    const Haplotypes& h = *d.haps;
+    bk::HapArgs a{};
+    a.rows = d.rows.p; a.row_cap = d.rows.n / 2; a.placed = d.tallies.p + 1;
+    a.sorted = h.sorted.p; a.regions = h.regions.p; a.n_regions = h.n_regions; a.table_log2 = h.table_log2;
+    a.hot = h.hot.p; a.owner = h.owner.p; a.count = h.count.p; a.tallies = h.tallies.p;
+    a.entries = h.entries.p; a.entry_cap = std::min<uint64_t>(h.entries.n, 1ull << h.table_log2);
+    return a;
+}
+
+int bk_sample_haplotypes(bk_engine* e, const bk_hap_region* regions, uint32_t n_regions, uint32_t table_log2) {
+    static_assert(sizeof(bk_hap_entry) == 40 && sizeof(bk_hap_region) == sizeof(uint2), "hap_finish_kernel writes an entry as ten words");
+    if (!e || (!regions && n_regions)) return fail(BK_ERR_INVALID, "null argument");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_haplotypes comes after bk_sample_finalize");
+    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_haplotypes: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_haplotypes: bk_sample_finalize has not run for this sample");
+    if (n_regions > BK_HAP_MAX_REGIONS) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: at most %d regions, got %u", BK_HAP_MAX_REGIONS, n_regions);
+    if (table_log2 < 10 || table_log2 > 24) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: table_log2 must be 10..24, got %u", table_log2);
+    if (const char* v = test_env("BK_HAP_TABLE_SHRINK"))   // testing build: 2^-v of the slots asked for, not below 2^10 -- a small sample fills a table
+        table_log2 -= std::min<uint32_t>(table_log2 - 10, (uint32_t)std::max(0, atoi(v)));
+    const IndexTables& ix = *e->ix;
+    for (uint32_t i = 0; i < n_regions; i++) {
+        const uint64_t c0 = regions[i].cell0, end = c0 + regions[i].len;
+        if (regions[i].len == 0) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u has no cell", i);
+        if (regions[i].len > BK_HAP_MAX_LEN) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u has %u cells, at most %d", i, regions[i].len, BK_HAP_MAX_LEN);
+        if (end > ix.total_cells)
+            return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u ends at cell %llu, the index has %llu", i, (unsigned long long)end, (unsigned long long)ix.total_cells);
+        for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) {   // (one genome file: bk_link_enable)
+            const uint64_t lo = ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q], hi = lo + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q];
+            if (c0 >= lo && c0 < hi && end > hi)
+                return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u crosses a sequence border (cells %llu to %llu, its sequence ends at %llu)", i,
+                            (unsigned long long)c0, (unsigned long long)end, (unsigned long long)hi);
+        }
+    }
+    Linkage& d = *e->linkage;
+    if (!d.haps) d.haps.reset(new Haplotypes());
+    Haplotypes& h = *d.haps;
+    BK_HIP(hipSetDevice(e->device));
+    // an earlier count may still read the tables, the counters and the pinned copies that are replaced here: wait for it alone
+    if (h.count_in_flight) { BK_HIP(hipEventSynchronize(h.counted)); h.count_in_flight = false; }
+    h.made = false;
+    BK_HIP(h.h_sorted.grow(std::max<size_t>(n_regions, 1))); BK_HIP(h.h_regions.grow(std::max<size_t>(n_regions, 1)));
+    {   // the caller's order; the same sorted by first cell, each with its index in the caller's order
+        std::vector<uint32_t> order(n_regions);
+        for (uint32_t i = 0; i < n_regions; i++) { order[i] = i; h.h_regions.p[i] = make_uint2(regions[i].cell0, regions[i].len); }
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return regions[x].cell0 < regions[y].cell0; });
+        for (uint32_t i = 0; i < n_regions; i++) h.h_sorted.p[i] = make_uint2(regions[order[i]].cell0, regions[order[i]].len | (order[i] << 16));
+    }
+    const size_t slots = (size_t)1 << table_log2;
+    h.n_regions = n_regions; h.table_log2 = table_log2;
+    BK_HIP(grow(h.sorted, n_regions)); BK_HIP(grow(h.regions, n_regions)); BK_HIP(grow(h.hot, (size_t)n_regions * 2));
+    if (h.owner.n < slots) { BK_HIP(h.owner.alloc(slots)); BK_HIP(h.count.alloc(slots)); BK_HIP(h.entries.alloc(slots)); }
+    if (!h.tallies.p) BK_HIP(h.tallies.alloc(2));
+    bk_engine::Span sp(e, 1);
+    BK_HIP(hipMemsetAsync(h.tallies.p, 0, 2 * sizeof(unsigned long long), e->stream));
+    if (n_regions) {
+        BK_HIP(hipMemcpyAsync(h.sorted.p, h.h_sorted.p, n_regions * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemcpyAsync(h.regions.p, h.h_regions.p, n_regions * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemsetAsync(h.hot.p, 0, (size_t)n_regions * 2 * sizeof(unsigned int), e->stream));
+        BK_HIP(hipMemsetAsync(h.owner.p, 0, slots * sizeof(unsigned long long), e->stream));
+        BK_HIP(hipMemsetAsync(h.count.p, 0, slots * sizeof(unsigned int), e->stream));
+    }
+    const bk::HapArgs a = hap_args(e);
+    bk::launch_hap_count(a, d.rows_upper, ix.n_cus, e->stream);
+    bk::launch_hap_finish(a, e->stream);
+    BK_HIP(hipGetLastError());
+    BK_HIP(h.counted.create());
+    BK_HIP(hipEventRecord(h.counted, e->stream));
+    h.count_in_flight = true;
+    h.made = true;
+    return BK_OK;
+}
+
+// by region, then by list as a sequence of (offset, base), a proper prefix first
+static bool hap_entry_less(const bk_hap_entry& x, const bk_hap_entry& y) {
+    if (x.region != y.region) return x.region < y.region;
+    for (uint32_t i = 0; i < std::min<uint32_t>(x.n_mm, y.n_mm); i++) {
+        const uint32_t ox = x.mm[3 * i] | (x.mm[3 * i + 1] << 8), oy = y.mm[3 * i] | (y.mm[3 * i + 1] << 8);
+        if (ox != oy) return ox < oy;
+        if (x.mm[3 * i + 2] != y.mm[3 * i + 2]) return x.mm[3 * i + 2] < y.mm[3 * i + 2];
+    }
+    return x.n_mm < y.n_mm;
+}
+
+int bk_sample_download_haplotypes(bk_engine* e, bk_hap_summary* summary, uint32_t* cover, uint32_t* ref_count, bk_hap_entry* entries, uint64_t cap) {
+    if (!e || !summary || (!entries && cap)) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_haplotypes")) return rc;
+    Linkage& d = *e->linkage;
+    const Haplotypes* h = d.haps && d.haps->made ? d.haps.get() : nullptr;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long placed = 0, t[2] = {0, 0};
+    if (int rc = download(e, &placed, d.tallies.p + 1, 1)) return rc;
+    if (h) { if (int rc = download(e, t, h->tallies.p, 2)) return rc; }
+    summary->rows = placed; summary->entries = t[0]; summary->dropped = t[1];
+    summary->n_regions = h ? h->n_regions : 0; summary->table_log2 = h ? h->table_log2 : 0;
+    if (!h) return BK_OK;
+    if (h->n_regions && (cover || ref_count)) {
+        std::vector<unsigned int> hot((size_t)h->n_regions * 2);
+        BK_HIP(hipMemcpy(hot.data(), h->hot.p, hot.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < h->n_regions; i++) {
+            if (cover) cover[i] = hot[2 * (size_t)i];
+            if (ref_count) ref_count[i] = hot[2 * (size_t)i + 1];
+        }
+    }
+    if (t[1])
+        return fail(BK_ERR_RANGE, "bk_sample_download_haplotypes: the table of 2^%u slots (table_log2 = %u) is full, %llu haplotype counts were dropped: call bk_sample_haplotypes again with a larger table_log2",
+                    h->table_log2, h->table_log2, (unsigned long long)t[1]);
+    const uint64_t have = std::min<uint64_t>(t[0], (uint64_t)1 << h->table_log2);
+    if (!have || !cap) return BK_OK;
+    std::vector<bk_hap_entry> all((size_t)have);
+    BK_HIP(hipMemcpy(all.data(), h->entries.p, all.size() * sizeof(bk_hap_entry), hipMemcpyDeviceToHost));
+    std::sort(all.begin(), all.end(), hap_entry_less);
+    std::memcpy(entries, all.data(), (size_t)std::min<uint64_t>(cap, have) * sizeof(bk_hap_entry));
     return BK_OK;
 }

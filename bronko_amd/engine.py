@@ -513,6 +513,35 @@ class Engine:
         _check(self._L.bk_sample_download_codons(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, buf[:min(cap, int(summ.n_codons))]
 
+    def sample_haplotypes(self, regions, table_log2=16):
+        """bk_sample_haplotypes: for every region [(cell0, len), ...] (forward-strand cells, any order) the rows of the finalized
+        sample's store that span it, by the list of substitutions they carry inside it, counted on the device (asynchronous) in a
+        table of 2^table_log2 slots; needs linkage_enable."""
+        arr = np.ascontiguousarray(np.asarray(regions, np.int64).reshape(-1, 2).astype(np.uint32))
+        _check(self._L.bk_sample_haplotypes(self.h, arr.ctypes.data_as(C.c_void_p), len(arr), int(table_log2)), self._L)
+
+    def download_haplotypes(self, cap=None):
+        """(summary, cover, ref_count, entries) of sample_haplotypes: cover and ref_count as uint32 arrays in the regions' order,
+        entries [(region, count, ((offset, base), ...))] in the defined order, min(cap, summary.entries) of them, all by default.
+        A table that dropped counts raises BronkoError (status -6) with .hap = (summary, cover, ref_count): those stay exact."""
+        summ = _ffi.HapSummary()
+        rc = self._L.bk_sample_download_haplotypes(self.h, C.byref(summ), None, None, None, 0)   # (sizes; -6 still fills the summary)
+        if rc != -6:
+            _check(rc, self._L)
+        n = int(summ.n_regions)
+        cover, ref = np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.uint32)
+        cap = int(summ.entries) if cap is None else int(cap)
+        buf = np.zeros((max(1, cap), 40), np.uint8)
+        rc = self._L.bk_sample_download_haplotypes(self.h, C.byref(summ), cover.ctypes.data_as(C.c_void_p), ref.ctypes.data_as(C.c_void_p),
+                                                   buf.ctypes.data_as(C.c_void_p), cap)
+        if rc != 0:
+            try:
+                _check(rc, self._L)
+            except BronkoError as err:
+                err.hap = (summ, cover[:n], ref[:n])
+                raise
+        return summ, cover[:n], ref[:n], hap_entries(buf[:min(cap, int(summ.entries))])
+
     def regions_set(self, regions):
         """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
         arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])
@@ -540,6 +569,20 @@ class Engine:
         n = (C.c_uint64 * 4)()
         _check(self._L.bk_timing_read(self.h, ms, n, int(reset)), self._L)
         return list(ms), list(n)
+
+
+def hap_entries(raw):
+    """[n][40] bytes of bk_hap_entry as [(region, count, ((offset, base), ...))], in the order given.  An entry that the device cannot
+    have written (no or more than 8 substitutions, a pad byte or an entry behind n_mm that is not zero) raises ValueError."""
+    out = []
+    for i, r in enumerate(np.asarray(raw, np.uint8).reshape(-1, 40)):
+        b = r.tobytes()
+        n_mm = b[8]
+        if n_mm < 1 or n_mm > 8 or any(b[9:16]) or any(b[16 + 3 * n_mm:]):
+            raise ValueError("entry %d of the haplotype list is no haplotype: %s" % (i, b.hex()))
+        mm = tuple((b[16 + 3 * t] | (b[17 + 3 * t] << 8), b[18 + 3 * t]) for t in range(n_mm))
+        out.append((int.from_bytes(b[:4], "little"), int.from_bytes(b[4:8], "little"), mm))
+    return out
 
 
 def link_rows(raw):

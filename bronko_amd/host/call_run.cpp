@@ -211,6 +211,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--codons: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.haps()) {           // (likewise)
+        LOG_DEBUG(T, "--haplotypes: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
     if (!shard_mode) shard_devices.clear();
     return shard_devices;
@@ -243,8 +247,11 @@ struct SampleData {
     std::vector<LinkPair> link_pairs;
     bk_codon_summary csumm2{};                            // --codons
     std::vector<uint32_t> codon_counts;
+    bk_hap_summary hsumm{};                               // --haplotypes
+    HapTable hap_table;
 };
 
+constexpr uint32_t kHapTableLog2 = 16, kHapTableLog2Max = 24;   // --haplotypes: the table's first size (768 KB + 2.5 MB of entries); four times as many slots after each that was full
 constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
 constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
@@ -262,6 +269,8 @@ struct CallRun {
     size_t max_file_regions = 0;                     // regions of the genome file with the most
     std::vector<CodonGene> genes;                    // --codons: resolved by open_index
     std::vector<bk_codon_region> gene_table;         // ... as bk_sample_codons takes them
+    std::vector<HapWindow> hap_wins;                 // --haplotypes / --hap-window: resolved by open_index
+    std::vector<bk_hap_region> hap_regs;             // ... as bk_sample_haplotypes takes them
     int dump_threads = 1;                            // --keep-kmer-info: threads that format one sample's counts (set before the lanes start)
 
     // the samples, in input order; their files are read ahead from here on (ReadAhead): the index and the engine's tables take
@@ -304,6 +313,14 @@ struct CallRun {
             catch (const std::exception& e) { die(T, e.what()); }
             for (const CodonGene& g : genes) gene_table.push_back(bk_codon_region{g.reg.cell0, g.reg.n_codons});
             LOG_DEBUG(T, std::to_string(genes.size()) + " coding regions");
+        }
+        if (cfg.haps() && ix.files.size() != 1)
+            die(T, "--haplotypes needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.haps()) {     // the BED lines against the CHROM tokens of the index, or the tiling.  Before any device is touched.
+            try { hap_wins = cfg.hap_window ? hap_windows(ix, 0, cfg.hap_window, cfg.hap_step) : resolve_hap_bed(ix, 0, cfg.hap_bed, cfg.haps_path); }
+            catch (const std::exception& e) { die(T, e.what()); }
+            for (const HapWindow& w : hap_wins) hap_regs.push_back(bk_hap_region{w.reg.cell0, w.reg.len});
+            LOG_DEBUG(T, std::to_string(hap_wins.size()) + " haplotype regions");
         }
     }
     // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
@@ -455,8 +472,8 @@ struct CallRun {
             const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
             hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
         }
-        if (cfg.row_store()) {   // (--codons reads --linkage's row store; alone it brings its own M, together the two are equal)
-            const bk_link_config lc{cfg.linkage ? cfg.link.max_mismatches : cfg.codon.max_mismatches, kLinkInitialRows};
+        if (cfg.row_store()) {   // (--codons and --haplotypes read --linkage's row store; alone each brings its own M, together they are equal)
+            const bk_link_config lc{cfg.row_store_mismatches(), kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
         }
     }
@@ -563,6 +580,24 @@ struct CallRun {
             d.codon_counts.resize((size_t)d.csumm2.n_codons * 64);
             hip_check(bk_sample_download_codons(e, &d.csumm2, d.codon_counts.data(), d.csumm2.n_codons), "bk_sample_download_codons");
         }
+        if (cfg.haps()) {     // likewise; a table that was full: the same rows again into one of four times the slots
+            d.hap_table.cover.assign(hap_regs.size(), 0u); d.hap_table.ref_count.assign(hap_regs.size(), 0u);
+            for (uint32_t log2 = kHapTableLog2;; log2 += 2) {
+                hip_check(bk_sample_haplotypes(e, hap_regs.data(), (uint32_t)hap_regs.size(), log2), "bk_sample_haplotypes");
+                const int rc = bk_sample_download_haplotypes(e, &d.hsumm, d.hap_table.cover.data(), d.hap_table.ref_count.data(), nullptr, 0);
+                if (rc == BK_ERR_RANGE && log2 + 2 <= kHapTableLog2Max) {
+                    LOG_INFO(T, "Haplotypes: a table of 2^" + std::to_string(d.hsumm.table_log2) + " slots was full (" + std::to_string(d.hsumm.dropped) +
+                                    " counts dropped), counting again with four times as many");
+                    continue;
+                }
+                hip_check(rc, "bk_sample_download_haplotypes");
+                break;
+            }
+            static_assert(sizeof(HapEntry) == sizeof(bk_hap_entry), "HapEntry is bk_hap_entry");
+            d.hap_table.entries.resize((size_t)d.hsumm.entries);
+            hip_check(bk_sample_download_haplotypes(e, &d.hsumm, nullptr, nullptr, reinterpret_cast<bk_hap_entry*>(d.hap_table.entries.data()), d.hap_table.entries.size()),
+                      "bk_sample_download_haplotypes");
+        }
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
     uint64_t merge_mates(const std::vector<std::string>& mates, SampleData& d) const {
@@ -631,6 +666,12 @@ struct CallRun {
                 const uint64_t lines = write_codons_tsv(a.output + "/" + stem + ".codons.tsv", ix, best, genes, d.codon_counts, cfg.codon);
                 LOG_INFO(T, "Codons: " + std::to_string(d.csumm2.rows) + " placed records over " + std::to_string(d.csumm2.n_regions) + " regions, " +
                                 std::to_string(d.csumm2.n_codons) + " codons counted, " + std::to_string(lines) + " lines written");
+            }
+            if (cfg.haps()) {       // (a sample without such a haplotype: the header alone)
+                const HapStats hs = write_haplotypes_tsv(a.output + "/" + stem + ".haplotypes.tsv", ix, best, hap_wins, d.hap_table, cfg.hap);
+                LOG_INFO(T, "Haplotypes: " + std::to_string(d.hsumm.rows) + " placed records over " + std::to_string(d.hsumm.n_regions) + " regions, " +
+                                std::to_string(hs.no_cover) + " without cover, " + std::to_string(hs.distinct) + " distinct haplotypes, " + std::to_string(hs.lines) +
+                                " lines written, table of 2^" + std::to_string(d.hsumm.table_log2) + " slots");
             }
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }

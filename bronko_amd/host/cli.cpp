@@ -75,7 +75,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
-          "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
+          "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -115,7 +116,15 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    the triplets other than the reference's that whole reads carry there, translated, with count, cover and freq\n"
           "  --codon-min-reads N      reads that carry a triplet for it to be written; at least 1, default 5\n"
           "  --codon-min-freq F       count / cover a triplet needs to be written; 0..1, default the value of --min-af\n"
-          "  --codon-max-mismatches M substitutions a read may have to be counted; 0..8, default 8 (with --linkage: equal to its M)\n", stderr);
+          "  --codon-max-mismatches M substitutions a read may have to be counted; 0..8, default 8 (with --linkage: equal to its M)\n"
+          "  --haplotypes BED  write to <DIR>/<stem>.haplotypes.tsv, per region of BED (an index of one genome file; chrom, 0-based start, end,\n"
+          "                    name; at most 4096 regions of at most 65520 positions), the combinations of substitutions that single reads\n"
+          "                    carry across the whole region, the reference's included, ranked by count, with cover and freq\n"
+          "  --hap-window W    the same for windows of W positions every S positions of every sequence (not with --haplotypes); 1..65520\n"
+          "  --hap-step S      positions from one window's start to the next; at least 1, default W\n"
+          "  --hap-min-reads N        reads that carry a haplotype for it to be written; at least 1, default 5\n"
+          "  --hap-min-freq F         count / cover a haplotype needs to be written; 0..1, default the value of --min-af\n"
+          "  --hap-max-mismatches M   substitutions a read may have to be counted; 0..8, default 8 (with --linkage or --codons: equal to their M)\n", stderr);
     exit(code);
 }
 
@@ -273,6 +282,19 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--codon-min-reads") { a.codon_min_reads = x; a.has_codon_min_reads = true; }
             else { a.codon_max_mismatches = x; a.has_codon_max_mismatches = true; }
         }
+        else if (opt == "--haplotypes") { a.haplotypes = one(); a.has_haplotypes = true; }
+        else if (opt == "--hap-window" || opt == "--hap-step" || opt == "--hap-min-reads" || opt == "--hap-max-mismatches") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--hap-window") { a.hap_window = x; a.has_hap_window = true; }
+            else if (opt == "--hap-step") { a.hap_step = x; a.has_hap_step = true; }
+            else if (opt == "--hap-min-reads") { a.hap_min_reads = x; a.has_hap_min_reads = true; }
+            else { a.hap_max_mismatches = x; a.has_hap_max_mismatches = true; }
+        }
+        else if (opt == "--hap-min-freq") { a.hap_min_freq = to_double(opt, one()); a.has_hap_min_freq = true; }
         else if (opt == "--codon-min-freq") { a.codon_min_freq = to_double(opt, one()); a.has_codon_min_freq = true; }
         else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
         else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
@@ -487,6 +509,27 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.has_codons && a.linkage && a.codon_max_mismatches != a.link_max_mismatches)   // (one row store, one M)
         die(T, "--linkage and --codons count the same placed reads: --link-max-mismatches (" + std::to_string(a.link_max_mismatches) + ") and --codon-max-mismatches (" +
                    std::to_string(a.codon_max_mismatches) + ") must be equal");
+    if (a.has_haplotypes && a.has_hap_window) die(T, "--haplotypes and --hap-window cannot be given together");
+    if (a.has_hap_step && !a.has_hap_window) die(T, "--hap-step needs --hap-window");
+    if (a.has_hap_min_reads && !a.haps()) die(T, "--hap-min-reads needs --haplotypes or --hap-window");
+    if (a.has_hap_min_freq && !a.haps()) die(T, "--hap-min-freq needs --haplotypes or --hap-window");
+    if (a.has_hap_max_mismatches && !a.haps()) die(T, "--hap-max-mismatches needs --haplotypes or --hap-window");
+    if (a.has_haplotypes && a.haplotypes.empty()) die(T, "--haplotypes needs a BED file");
+    if (a.has_hap_window && (a.hap_window < 1 || a.hap_window > (long)kHapMaxLen)) die(T, "--hap-window must be between 1 and 65520, got " + std::to_string(a.hap_window));
+    if (a.has_hap_step && a.hap_step < 1) die(T, "--hap-step must be at least 1, got " + std::to_string(a.hap_step));
+    if (a.hap_min_reads < 1) die(T, "--hap-min-reads must be at least 1, got " + std::to_string(a.hap_min_reads));
+    if (a.hap_max_mismatches < 0 || a.hap_max_mismatches > kLinkMaxMismatches) die(T, "--hap-max-mismatches must be between 0 and 8, got " + std::to_string(a.hap_max_mismatches));
+    if (a.has_hap_min_freq && !(a.hap_min_freq >= 0.0 && a.hap_min_freq <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "--hap-min-freq must be between 0 and 1, got %g", a.hap_min_freq);
+        die(T, buf);
+    }
+    if (a.haps() && a.linkage && a.hap_max_mismatches != a.link_max_mismatches)   // (one row store, one M)
+        die(T, "--linkage and --haplotypes count the same placed reads: --link-max-mismatches (" + std::to_string(a.link_max_mismatches) + ") and --hap-max-mismatches (" +
+                   std::to_string(a.hap_max_mismatches) + ") must be equal");
+    if (a.haps() && a.has_codons && a.hap_max_mismatches != a.codon_max_mismatches)
+        die(T, "--codons and --haplotypes count the same placed reads: --codon-max-mismatches (" + std::to_string(a.codon_max_mismatches) + ") and --hap-max-mismatches (" +
+                   std::to_string(a.hap_max_mismatches) + ") must be equal");
 }
 
 // the checked arguments -> what the readers and the per-sample code work from; the primer file and the regions file are read and the adapters are
@@ -534,6 +577,14 @@ CallConfig make_call_config(const Args& a) {
     }
     c.codon.max_mismatches = (uint32_t)a.codon_max_mismatches; c.codon.min_reads = (uint64_t)a.codon_min_reads;
     c.codon.min_freq = a.has_codon_min_freq ? a.codon_min_freq : a.min_af;
+    if (a.has_haplotypes) {   // (likewise)
+        try { c.hap_bed = read_hap_bed(a.haplotypes); }
+        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the haplotypes file"); }
+        c.haps_path = a.haplotypes;
+    }
+    if (a.has_hap_window) { c.hap_window = (uint64_t)a.hap_window; c.hap_step = (uint64_t)(a.has_hap_step ? a.hap_step : a.hap_window); }
+    c.hap.max_mismatches = (uint32_t)a.hap_max_mismatches; c.hap.min_reads = (uint64_t)a.hap_min_reads;
+    c.hap.min_freq = a.has_hap_min_freq ? a.hap_min_freq : a.min_af;
     return c;
 }
 

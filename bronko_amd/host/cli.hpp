@@ -10,6 +10,7 @@
 #include "../../include/bronko_hip.h"
 #include "caller.hpp"
 #include "codons.hpp"
+#include "haplotypes.hpp"
 #include "indels.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
@@ -78,6 +79,14 @@ struct Args {
     long codon_min_reads = 5;       // --codon-min-reads: records that carry a triplet for it to be written
     double codon_min_freq = 0.03;   // --codon-min-freq: count / cover a triplet needs to be written (default: --min-af)
     long codon_max_mismatches = 8;  // --codon-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with --linkage)
+    std::string haplotypes;         // --haplotypes: BED file of the regions whose read haplotypes go to <DIR>/<stem>.haplotypes.tsv (empty: none)
+    bool has_haplotypes = false, has_hap_window = false, has_hap_step = false, has_hap_min_reads = false, has_hap_min_freq = false, has_hap_max_mismatches = false;
+    long hap_window = 0;            // --hap-window: tile every sequence with windows of this many positions instead (1..65520)
+    long hap_step = 0;              // --hap-step: positions from one window's start to the next (default: the window)
+    long hap_min_reads = 5;         // --hap-min-reads: records that carry a haplotype for it to be written
+    double hap_min_freq = 0.03;     // --hap-min-freq: count / cover a haplotype needs to be written (default: --min-af)
+    long hap_max_mismatches = 8;    // --hap-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with --linkage and --codons)
+    bool haps() const { return has_haplotypes || has_hap_window; }
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -123,7 +132,16 @@ struct CallConfig {
     std::vector<BedLine> codon_bed;
     CodonParams codon;
     bool codons() const { return !codons_path.empty(); }
-    bool row_store() const { return linkage || codons(); }   // bk_link_enable
+    // --haplotypes / --hap-window: the file's lines or the tiling (resolved against the index once it is open, call_run.cpp),
+    // bk_sample_haplotypes and the values the .haplotypes.tsv header prints; hap.max_mismatches is the row store's when neither
+    // --linkage nor --codons is given (equal to theirs when one is)
+    std::string haps_path;
+    std::vector<BedLine> hap_bed;
+    uint64_t hap_window = 0, hap_step = 0;
+    HapParams hap;
+    bool haps() const { return !haps_path.empty() || hap_window > 0; }
+    bool row_store() const { return linkage || codons() || haps(); }   // bk_link_enable
+    uint32_t row_store_mismatches() const { return linkage ? link.max_mismatches : codons() ? codon.max_mismatches : hap.max_mismatches; }
     bool region_report() const { return !regions_path.empty() || region_window > 0; }
     // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
     bool trims() const { return !primers.empty() || !adapters.empty(); }

@@ -10,6 +10,7 @@
 
 #include "caller.hpp"
 #include "codons.hpp"
+#include "haplotypes.hpp"
 #include "indels.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
@@ -367,6 +368,74 @@ int bh_write_codons_tsv(const void* h, int file_id, const char* path, const uint
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 int bh_translate(const char* triplet) { return bronko::translate(triplet); }
+
+// ---- --haplotypes: the host twin of the engine's haplotype count, the regions and the writer (haplotypes.cpp) --------------------
+// regs: n_regions x {cell0, len}; cover, ref_count: [n_regions]; entries: 40 bytes each (bk_hap_entry), written only where they fit cap
+int bh_hap_count(const void* h, int file_id, const void* rows, uint64_t n_rows, const uint32_t* regs, uint64_t n_regions, uint32_t* cover, uint32_t* ref_count,
+                 uint64_t cap, void* entries, uint64_t* n_entries) {
+    try {
+        const auto* rw = static_cast<const bronko::LinkRow*>(rows);
+        std::vector<bronko::HapRegion> rg((size_t)n_regions);
+        for (uint64_t i = 0; i < n_regions; i++) { rg[i].cell0 = regs[2 * i]; rg[i].len = regs[2 * i + 1]; }
+        const bronko::HapTable t = bronko::hap_count(*static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::LinkRow>(rw, rw + n_rows), rg);
+        if (n_entries) *n_entries = t.entries.size();
+        if (cover && n_regions) std::memcpy(cover, t.cover.data(), (size_t)n_regions * sizeof(uint32_t));
+        if (ref_count && n_regions) std::memcpy(ref_count, t.ref_count.data(), (size_t)n_regions * sizeof(uint32_t));
+        if (entries && t.entries.size() <= cap && !t.entries.empty()) std::memcpy(entries, t.entries.data(), t.entries.size() * sizeof(bronko::HapEntry));
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// windows travel as [n][4] u32 (cell0, len, seq, start), their names joined by '\n'
+namespace {
+std::vector<bronko::HapWindow> windows_of(const uint32_t* wins, const char* names, uint64_t n) {
+    std::vector<bronko::HapWindow> out((size_t)n);
+    const char* at = names;
+    for (uint64_t i = 0; i < n; i++) {
+        out[i].reg.cell0 = wins[i * 4]; out[i].reg.len = wins[i * 4 + 1]; out[i].seq = wins[i * 4 + 2]; out[i].start = wins[i * 4 + 3];
+        out[i].name = ".";
+        if (at) {
+            const char* nl = strchr(at, '\n');
+            out[i].name = nl ? std::string(at, nl) : std::string(at);
+            at = nl ? nl + 1 : nullptr;
+        }
+    }
+    return out;
+}
+int windows_out(const std::vector<bronko::HapWindow>& r, uint64_t cap, uint32_t* wins, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
+    std::string joined;
+    for (size_t i = 0; i < r.size(); i++) joined += (i ? "\n" : "") + r[i].name;
+    *n = r.size();
+    if (names_len) *names_len = joined.size() + 1;
+    if (wins && r.size() <= cap)
+        for (size_t i = 0; i < r.size(); i++) { wins[i * 4] = r[i].reg.cell0; wins[i * 4 + 1] = r[i].reg.len; wins[i * 4 + 2] = r[i].seq; wins[i * 4 + 3] = r[i].start; }
+    if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
+    return 0;
+}
+}  // namespace
+// read_hap_bed + resolve_hap_bed (path) or hap_windows (path null); *n windows, *names_len bytes of joined names, both written only where they fit
+int bh_hap_regions(const void* h, int file_id, const char* path, uint64_t window, uint64_t step, uint64_t cap, uint32_t* wins, char* names, uint64_t names_cap, uint64_t* n,
+                   uint64_t* names_len) {
+    try {
+        const bronko::Index& ix = *static_cast<const bronko::Index*>(h);
+        return windows_out(path ? bronko::resolve_hap_bed(ix, file_id, bronko::read_hap_bed(path), path) : bronko::hap_windows(ix, file_id, window, step), cap, wins, names,
+                           names_cap, n, names_len);
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// stats: lines written, regions without cover, distinct haplotypes
+int bh_write_haplotypes_tsv(const void* h, int file_id, const char* path, const uint32_t* wins, const char* names, uint64_t n, const uint32_t* cover,
+                            const uint32_t* ref_count, const void* entries, uint64_t n_entries, uint32_t max_mismatches, uint64_t min_reads, double min_freq, uint64_t* stats) {
+    try {
+        bronko::HapParams p;
+        p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_freq = min_freq;
+        bronko::HapTable t;
+        t.cover.assign(cover, cover + n); t.ref_count.assign(ref_count, ref_count + n);
+        const auto* en = static_cast<const bronko::HapEntry*>(entries);
+        t.entries.assign(en, en + n_entries);
+        const bronko::HapStats st = bronko::write_haplotypes_tsv(path, *static_cast<const bronko::Index*>(h), file_id, windows_of(wins, names, n), t, p);
+        if (stats) { stats[0] = st.lines; stats[1] = st.no_cover; stats[2] = st.distinct; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
 
 void bh_clean_sample_id(const char* path, char* buf, size_t n) {
     const std::string s = bronko::clean_sample_id(path);

@@ -469,3 +469,80 @@ def write_codons_tsv(path, ix, file_id, genes, counts, max_mismatches=8, min_rea
 def translate(triplet):
     """The standard code of three letters ACGT (codons.cpp translate)."""
     return chr(_codon_lib().bh_translate(triplet.encode()))
+
+
+# ---- --haplotypes: the host twin of the engine's haplotype count, the regions and the writer (haplotypes.cpp) ---------------------
+def _hap_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_haps_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_hap_count.restype = C.c_int
+        L.bh_hap_count.argtypes = [vp, C.c_int, vp, u64, vp, u64, vp, vp, u64, vp, C.POINTER(u64)]
+        L.bh_hap_regions.restype = C.c_int
+        L.bh_hap_regions.argtypes = [vp, C.c_int, C.c_char_p, u64, u64, u64, vp, C.c_char_p, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bh_write_haplotypes_tsv.restype = C.c_int
+        L.bh_write_haplotypes_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, C.c_char_p, u64, vp, vp, vp, u64, u32, u64, C.c_double, vp]
+        L._haps_ready = True
+    return L
+
+
+def _hap_entry_bytes(entries):
+    """[(region, count, ((offset, base), ...))] as [n][40] bytes of bk_hap_entry"""
+    out = np.zeros((max(1, len(entries)), 40), np.uint8)
+    for i, (region, count, mm) in enumerate(entries):
+        out[i, :4] = np.frombuffer(int(region).to_bytes(4, "little"), np.uint8)
+        out[i, 4:8] = np.frombuffer(int(count).to_bytes(4, "little"), np.uint8)
+        out[i, 8] = len(mm)
+        for t, (off, b) in enumerate(mm):
+            out[i, 16 + 3 * t:19 + 3 * t] = (off & 0xff, off >> 8, b)
+    return out
+
+
+def hap_count(ix, file_id, raw_rows, regions):
+    """The host twin of the haplotype kernels (haplotypes.cpp hap_count) for the regions [(cell0, len), ...]: (cover, ref_count,
+    entries) -- two uint32 arrays in the regions' order and [(region, count, ((offset, base), ...))] by region, then by list;
+    raw_rows as link_rows gives them."""
+    from .engine import hap_entries
+    L = _hap_lib()
+    raw = np.ascontiguousarray(np.asarray(raw_rows, np.uint8).reshape(-1, 32))
+    rg = np.ascontiguousarray(np.asarray(regions, np.int64).reshape(-1, 2).astype(np.uint32))
+    cover, ref = np.zeros(max(1, len(rg)), np.uint32), np.zeros(max(1, len(rg)), np.uint32)
+    got = C.c_uint64()
+    if L.bh_hap_count(ix.h, file_id, raw.ctypes.data, len(raw), rg.ctypes.data, len(rg), None, None, 0, None, C.byref(got)) != 0:
+        raise _host_error(L)
+    buf = np.zeros((max(1, got.value), 40), np.uint8)
+    if L.bh_hap_count(ix.h, file_id, raw.ctypes.data, len(raw), rg.ctypes.data, len(rg), cover.ctypes.data, ref.ctypes.data, got.value, buf.ctypes.data, C.byref(got)) != 0:
+        raise _host_error(L)
+    return cover[:len(rg)], ref[:len(rg)], hap_entries(buf[:got.value])
+
+
+def hap_regions(ix, file_id, path=None, window=0, step=0):
+    """The regions of a --haplotypes BED file (haplotypes.cpp read_hap_bed, resolve_hap_bed) or, with path None, the --hap-window
+    tiling (hap_windows) of genome file file_id: [(cell0, len, seq, start, name)] in order; RuntimeError otherwise."""
+    L = _hap_lib()
+    n, nl = C.c_uint64(), C.c_uint64()
+    pth = path.encode() if path is not None else None
+    if L.bh_hap_regions(ix.h, file_id, pth, int(window), int(step), 0, None, None, 0, C.byref(n), C.byref(nl)) != 0:
+        raise _host_error(L)
+    wins = np.zeros((max(1, n.value), 4), np.uint32)
+    names = C.create_string_buffer(max(1, nl.value))
+    if L.bh_hap_regions(ix.h, file_id, pth, int(window), int(step), n.value, wins.ctypes.data, names, nl.value, C.byref(n), C.byref(nl)) != 0:
+        raise _host_error(L)
+    nm = names.value.decode().split("\n") if n.value else []
+    return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), nm[i]) for i, r in enumerate(wins[:n.value])]
+
+
+def write_haplotypes_tsv(path, ix, file_id, windows, cover, ref_count, entries, max_mismatches=8, min_reads=5, min_freq=0.03):
+    """The --haplotypes writer (haplotypes.cpp write_haplotypes_tsv): windows as hap_regions gives them, the table as hap_count or
+    Engine.download_haplotypes gives it; returns (lines written, regions without cover, distinct haplotypes)."""
+    L = _hap_lib()
+    w = np.ascontiguousarray(np.array([[c0, ln, seq, start] for c0, ln, seq, start, _ in windows], np.int64).reshape(-1, 4).astype(np.uint32))
+    names = "\n".join(name for *_, name in windows).encode()
+    cv = np.ascontiguousarray(np.resize(np.asarray(cover, np.uint32), max(1, len(windows))))
+    rf = np.ascontiguousarray(np.resize(np.asarray(ref_count, np.uint32), max(1, len(windows))))
+    en = _hap_entry_bytes(entries)
+    stats = (C.c_uint64 * 3)()
+    if L.bh_write_haplotypes_tsv(ix.h, file_id, path.encode(), w.ctypes.data, names, len(windows), cv.ctypes.data, rf.ctypes.data, en.ctypes.data, len(entries),
+                                 int(max_mismatches), int(min_reads), float(min_freq), stats) != 0:
+        raise _host_error(L)
+    return tuple(int(v) for v in stats)

@@ -599,6 +599,59 @@ typedef struct { uint64_t rows, n_codons; uint32_t n_regions; } bk_codon_summary
 int  bk_sample_codons(bk_engine* e, const bk_codon_region* regions, uint32_t n_regions);
 int  bk_sample_download_codons(bk_engine* e, bk_codon_summary* summary, uint32_t* counts /* [n_codons][64] */, uint64_t cap_codons);
 
+/* ---- which haplotypes the reads carry across a region (`bronko call --haplotypes`; additive, still v8) ---------------------------
+ * Given an amplicon, an epitope or a drug-resistance stretch: which combinations of substitutions do single reads carry across all of
+ * it, and how often?  Pair tables cannot be folded into that answer; the rows of bk_link_enable's store hold it exactly.  A third
+ * consumer of that store, and the first whose result size depends on the data: a table of the distinct haplotypes, not a dense
+ * counter array.  The terms row, placed, covers and base at a cell are those of bk_link_enable above; rows of both mate files count
+ * alike, overlapping mates count twice.  The rule, all of it integer arithmetic:
+ *   region     {cell0, len}: the forward-strand cells [cell0, cell0 + len); len is 1..65520; all cells inside one sequence of the
+ *              genome file and below bk_total_cells.  At most BK_HAP_MAX_REGIONS regions, in any order; they may overlap, nest and
+ *              repeat -- two equal regions are two regions with equal results.
+ *   spans      a row spans a region when row.cell0 <= cell0 and cell0 + len <= row.cell0 + row.n.  A row that covers only part of a
+ *              region counts nowhere for that region.
+ *   haplotype  of a spanning row in a region: the ascending list of (cell - cell0, base) over the row's substitutions whose cell
+ *              lies in the region, 0 to 8 entries.  The empty list is the reference haplotype.  Substitutions outside the region do
+ *              not belong to it, and neither does the row's strand: two rows that agree inside the region are one haplotype.
+ *   results    per region: cover = the spanning rows; ref_count = the spanning rows whose list is empty; one count for each distinct
+ *              non-empty list; cover = ref_count + the sum of the counts.  A reference cell that is not ACGT lies under no row: a
+ *              region that holds one has cover 0.
+ *   entry      bk_hap_entry: the region's index in the caller's order, the count, n_mm and the list in bk_link_row's packing --
+ *              mm[3 i ..] = the offset from the region's first cell (16 bits, little endian) and the base (A C G T = 0 1 2 3); the
+ *              entries from n_mm on and pad are zero.
+ *   bk_sample_haplotypes      the row store is bk_link_enable's, there is no enable call of its own.  After the sample's
+ *                             bk_sample_finalize (BK_ERR_STATE inside a sample, before any finalize, and when linkage was not
+ *                             enabled as the sample began).  BK_ERR_INVALID: a region with len 0 or above 65520, one that ends beyond
+ *                             bk_total_cells or crosses a sequence border (the message names the region's index), more than
+ *                             BK_HAP_MAX_REGIONS regions (it names the count), table_log2 outside 10..24; nothing is launched.
+ *                             n_regions = 0 is valid: no results.  The distinct non-empty haplotypes of all regions share one
+ *                             open-addressing table of 2^table_log2 slots (12 bytes a slot, and room for an entry of 40 bytes per
+ *                             slot); it stores no key -- a slot names the first row that claimed it -- and no lane of the kernel waits
+ *                             for another.  Zeroes its buffers and counts (hap_count_kernel, hap_finish_kernel); asynchronous on the
+ *                             engine's stream: the regions are staged in pinned memory, and the host waits for nothing but an earlier
+ *                             count whose buffers the call replaces.  May be repeated on the same sample with other regions or a
+ *                             larger table: the rows stay.  Independent of bk_sample_linkage and bk_sample_codons: any order, none
+ *                             disturbs another's results.  Its buffers are made by the first call, grow and never shrink, and are
+ *                             freed with the row store; an engine that never calls it allocates and launches nothing; a fork has
+ *                             none of its parent's.
+ *   bk_sample_download_haplotypes  after the sample's finalize; synchronises.  The summary (rows = the store's placed rows, entries =
+ *                             the distinct non-empty haplotypes in the table, dropped = the (row, region) that found no slot) and
+ *                             cover / ref_count of every region in the caller's order are always exact.  dropped > 0: the summary,
+ *                             cover and ref_count are filled, no entry is copied and the call returns BK_ERR_RANGE; the message names
+ *                             table_log2 and the count -- call bk_sample_haplotypes again with a larger table.  Otherwise
+ *                             min(cap, entries) entries in a defined order: by region, then by list compared as a sequence of
+ *                             (offset, base), a proper prefix first (the host sorts: the device's append order is not defined).
+ *                             cover, ref_count and entries may be NULL (entries with cap 0); summary may not.  Before the sample's
+ *                             first bk_sample_haplotypes there are the rows and no regions. */
+#define BK_HAP_MAX_REGIONS 4096
+#define BK_HAP_MAX_LEN 65520
+typedef struct { uint32_t cell0, len; } bk_hap_region;
+typedef struct { uint32_t region, count; uint8_t n_mm, pad[7]; uint8_t mm[24]; } bk_hap_entry;      /* 40 bytes */
+typedef struct { uint64_t rows, entries, dropped; uint32_t n_regions, table_log2; } bk_hap_summary;
+int  bk_sample_haplotypes(bk_engine* e, const bk_hap_region* regions, uint32_t n_regions, uint32_t table_log2 /* 10..24 */);
+int  bk_sample_download_haplotypes(bk_engine* e, bk_hap_summary* summary, uint32_t* cover, uint32_t* ref_count /* [n_regions] each */,
+                                   bk_hap_entry* entries, uint64_t cap);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
