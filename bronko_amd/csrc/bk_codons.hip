@@ -3,7 +3,7 @@
 //
 // The rule is stated in include/bronko_hip.h and DESIGN.md section T; bronko_amd/host/codons.cpp and tests/codons_ref.py restate it.
 // The rows are bk_link_enable's (bk_linkage.hip): this file only reads the store.
-//   codon_count_kernel   a lane per row (two 16-byte loads, unpacked as link_count_rows does).  A row covers some fifty codons of every
+//   codon_count_kernel   a lane per row (two 16-byte loads, unpacked by bk_link_row.h).  A row covers some fifty codons of every
 //                        region it overlaps and differs from the reference in at most eight cells, so it does not touch fifty
 //                        counters: per region it adds +1 / -1 to a cover difference array (at its first wholly covered codon and one
 //                        behind its last), and only for a codon that holds one of its mismatches it forms its triplet and adds 1 to
@@ -30,28 +30,14 @@ namespace {
 
 constexpr int kCodonBlock = 256;
 
-// the row's base at offset `off` from its first cell: one of its mismatches, else the reference's (bk_linkage.hip's row_base)
-__device__ __forceinline__ uint32_t codon_row_base(const uint32_t (&e)[8], uint32_t n_mm, uint32_t off, uint32_t ref_base) {
-    uint32_t b = ref_base;
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-        if ((uint32_t)s < n_mm && (e[s] & 0xffffu) == off) b = (e[s] >> 16) & 3u;
-    return b;
-}
-
 template <bool kLds>
 __device__ __forceinline__ void codon_count_rows(const CodonArgs& a, unsigned int* __restrict__ diff) {
-    const uint64_t n_rows = std::min<uint64_t>(a.tallies[1], a.row_cap);
+    const uint64_t n_rows = a.store.rows_in_store();
     for (uint64_t r = (uint64_t)blockIdx.x * kCodonBlock + threadIdx.x; r < n_rows; r += (uint64_t)gridDim.x * kCodonBlock) {
-        const uint4 lo = a.rows[2u * r], hi = a.rows[2u * r + 1u];
-        const uint32_t cell0 = lo.x, end = lo.x + (lo.y & 0xffffu), n_mm = min(lo.y >> 24, 8u);
-        const uint32_t e[8] = {lo.z & 0xffffffu, (lo.z >> 24) | ((lo.w & 0xffffu) << 8), (lo.w >> 16) | ((hi.x & 0xffu) << 16), hi.x >> 8,
-                               hi.y & 0xffffffu, (hi.y >> 24) | ((hi.z & 0xffffu) << 8), (hi.z >> 16) | ((hi.w & 0xffu) << 16), hi.w >> 8};
-        uint32_t s0 = 0, s1 = a.n_regions;             // the regions that start before the row's end
-        while (s0 < s1) {
-            const uint32_t mid = (s0 + s1) >> 1;
-            if (a.sorted[mid].x < end) s0 = mid + 1u; else s1 = mid;
-        }
+        const RowRegs row = a.store.load(r);
+        const uint32_t cell0 = row.cell0, end = row.end, n_mm = row.n_mm;
+        const uint32_t (&e)[8] = row.e;
+        const uint32_t s0 = first_not_below(0u, a.n_regions, end, [&](uint32_t i) { return a.sorted[i].x; });   // the regions that start before the row's end
         for (uint32_t i = s0; i-- > 0u;) {
             const uint4 reg = a.sorted[i];
             if (reg.w <= cell0) break;                 // (no region up to here reaches the row)
@@ -73,7 +59,7 @@ __device__ __forceinline__ void codon_count_rows(const CodonArgs& a, unsigned in
                 if (s > 0 && cell0 + (e[s > 0 ? s - 1 : 0] & 0xffffu) >= first) continue;   // (the codon's first mismatch adds for all of them)
                 uint32_t trip = 0;
 #pragma unroll
-                for (uint32_t t = 0; t < 3u; ++t) trip = trip * 4u + codon_row_base(e, n_mm, first + t - cell0, sym_at(a.ix.ref_words, first + t));
+                for (uint32_t t = 0; t < 3u; ++t) trip = trip * 4u + row_base(row, first + t - cell0, sym_at(a.ref_words, first + t));
                 atomicAdd(a.counts + (uint64_t)(base + j) * 64u + trip, 1u);
             }
         }
@@ -83,14 +69,9 @@ __device__ __forceinline__ void codon_count_rows(const CodonArgs& a, unsigned in
 __global__ __launch_bounds__(kCodonBlock) void codon_count_lds_kernel(CodonArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned int diff_s[];
     const uint32_t n = a.n_codons + 1u;               // at most kCodonLdsCodons
-    for (uint32_t i = threadIdx.x; i < n; i += kCodonBlock) diff_s[i] = 0u;
-    __syncthreads();
+    lds_table_zero<kCodonBlock>(diff_s, n);
     codon_count_rows<true>(a, diff_s);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += kCodonBlock) {
-        const unsigned int v = diff_s[i];
-        if (v) atomicAdd(a.cover_diff + i, v);
-    }
+    lds_table_add_to<kCodonBlock>(diff_s, n, a.cover_diff);
 }
 
 __global__ __launch_bounds__(kCodonBlock) void codon_count_kernel(CodonArgs a) { codon_count_rows<false>(a, nullptr); }
@@ -128,8 +109,8 @@ __global__ __launch_bounds__(kCodonBlock) void codon_finish_kernel(CodonArgs a) 
         }
         const uint2 reg = a.regions[r0];
         const uint32_t cell = reg.x + 3u * (cd - reg.y);
-        if (cell + 2u >= a.ix.total_cells) continue;   // (the host refused a region beyond the cells)
-        const uint32_t trip = sym_at(a.ix.ref_words, cell) * 16u + sym_at(a.ix.ref_words, cell + 1u) * 4u + sym_at(a.ix.ref_words, cell + 2u);
+        if (cell + 2u >= a.total_cells) continue;   // (the host refused a region beyond the cells)
+        const uint32_t trip = sym_at(a.ref_words, cell) * 16u + sym_at(a.ref_words, cell + 1u) * 4u + sym_at(a.ref_words, cell + 2u);
         a.counts[(uint64_t)cd * 64u + trip] = cover_s[j] - sum;
     }
 }
@@ -138,13 +119,10 @@ __global__ __launch_bounds__(kCodonBlock) void codon_finish_kernel(CodonArgs a) 
 
 void launch_codon_count(const CodonArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream) {
     if (a.n_codons == 0 || rows_upper == 0) return;
-    const uint64_t blocks = (rows_upper + kCodonBlock - 1) / kCodonBlock;
     if (a.n_codons + 1u <= kCodonLdsCodons) {         // (up to 64 KiB of LDS a workgroup: two fit a CU)
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 2));
-        hipLaunchKernelGGL(codon_count_lds_kernel, dim3(grid), dim3(kCodonBlock), (size_t)(a.n_codons + 1u) * sizeof(unsigned int), stream, a);
+        hipLaunchKernelGGL(codon_count_lds_kernel, dim3(row_grid(rows_upper, kCodonBlock, n_cus, 2)), dim3(kCodonBlock), (size_t)(a.n_codons + 1u) * sizeof(unsigned int), stream, a);
     } else {
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
-        hipLaunchKernelGGL(codon_count_kernel, dim3(grid), dim3(kCodonBlock), 0, stream, a);
+        hipLaunchKernelGGL(codon_count_kernel, dim3(row_grid(rows_upper, kCodonBlock, n_cus, 8)), dim3(kCodonBlock), 0, stream, a);
     }
 }
 

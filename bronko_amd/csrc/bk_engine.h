@@ -250,24 +250,32 @@ struct AnchorTables {
     DevBuf<uint2> nruns;                    // IndexTables::h_nonacgt
 };
 
+// One count over the sample's row store at a time -- what bk_sample_linkage (Linkage), bk_sample_codons (Codons) and
+// bk_sample_haplotypes (Haplotypes) keep alike.  A call replaces the tables, counters and pinned copies that the last call's kernels may
+// still read, so it first waits for them, and for them alone; it ends by recording `counted` behind its own launches.
+struct StoreCount {
+    Event counted;                          // behind the last count's launches
+    bool count_in_flight = false;
+    bool made = false;                      // the results are this sample's (cleared by Linkage::begin_sample and while a call replaces them)
+    int wait_last();                        // (bk_riders.cpp) nothing else of the stream's work is waited for; the results are void from here on
+    int record(hipStream_t stream);         // behind this count's launches: the results are this sample's
+};
+
 // bk_sample_codons: the region tables and the counters of the last call (bk_codons.hip).  Made by the first call, freed with the Linkage
 // whose row store it reads; its buffers grow and never shrink
-struct Codons {
+struct Codons : StoreCount {
     DevBuf<uint4> sorted;                   // [regions] by first cell (bk_kernels.h CodonArgs::sorted)
     DevBuf<uint2> regions;                  // [regions] the caller's order
     DevBuf<unsigned int> cover_diff;        // [codons + 1]
     DevBuf<unsigned int> counts;            // [codons][64]
     PinnedBuf<uint4> h_sorted;              // pinned host copies: the uploads are asynchronous
     PinnedBuf<uint2> h_regions;
-    Event counted;                          // behind the last count's kernels: the next bk_sample_codons replaces what they read
-    bool count_in_flight = false;
     uint32_t n_regions = 0, n_codons = 0;
-    bool made = false;                      // the counters are this sample's (bk_sample_codons ran)
 };
 
 // bk_sample_haplotypes: the region tables, the hot counters, the table of distinct haplotypes and the entry list of the last call
 // (bk_haplotypes.hip).  Made by the first call, freed with the Linkage whose row store it reads; its buffers grow and never shrink
-struct Haplotypes {
+struct Haplotypes : StoreCount {
     DevBuf<uint2> sorted;                   // [regions] by first cell (bk_kernels.h HapArgs::sorted)
     DevBuf<uint2> regions;                  // [regions] the caller's order
     DevBuf<unsigned int> hot;               // [regions][2] cover, ref_count
@@ -276,29 +284,24 @@ struct Haplotypes {
     DevBuf<unsigned long long> tallies;     // [2] entries, dropped
     DevBuf<bk_hap_entry> entries;           // [2^table_log2]
     PinnedBuf<uint2> h_sorted, h_regions;   // pinned host copies: the uploads are asynchronous
-    Event counted;                          // behind the last count's kernels: the next bk_sample_haplotypes replaces what they read
-    bool count_in_flight = false;
     uint32_t n_regions = 0, table_log2 = 0;
-    bool made = false;                      // the results are this sample's (bk_sample_haplotypes ran)
 };
 
 // bk_link_enable: the sample's row store (one bk_link_row per placed record), its tallies, and what the last bk_sample_linkage made
-struct Linkage {
+// (the StoreCount it is itself)
+struct Linkage : StoreCount {
     bk_link_config cfg{};
     std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable
     DevBuf<uint4> rows;                     // [2 * capacity in rows]
     std::vector<std::pair<uint4*, Event>> old;   // outgrown stores with the event behind the copy out of them: freed once it has passed
     uint64_t rows_upper = 0;                // a bound on the rows in the store: the records of every batch pushed (the count is the device's)
-    DevBuf<unsigned long long> tallies;     // [4] bk_kernels.h LinkArgs::tallies
+    DevBuf<unsigned long long> tallies;     // [4] bk_kernels.h LinkArgs::tallies; [1] is the store's count of rows (RowStoreView::placed)
     DevBuf<uint32_t> sites, pair_lo;        // the last bk_sample_linkage's
     DevBuf<unsigned int> counts;            // [pairs][16]
     PinnedBuf<uint32_t> h_sites, h_pair_lo; // pinned host copies: the uploads are asynchronous, the download reads the enumeration
-    Event counted;                          // behind the last count's launch: the next bk_sample_linkage replaces what it reads
-    bool count_in_flight = false;
     uint32_t n_sites = 0, max_dist = 0;
     uint64_t n_pairs = 0;
     bool in_sample = false;                 // enabled when the current / last sample began
-    bool made = false;                      // the counters are this sample's (bk_sample_linkage ran)
     std::unique_ptr<Codons> codons;         // bk_sample_codons (null: never called, no buffers)
     std::unique_ptr<Haplotypes> haps;       // bk_sample_haplotypes (likewise)
     ~Linkage() { for (auto& o : old) (void)hipFree(o.first); }

@@ -3,7 +3,7 @@
 //
 // The rule is stated in include/bronko_hip.h and DESIGN.md section H; bronko_amd/host/haplotypes.cpp and tests/haplotypes_ref.py restate
 // it.  The rows are bk_link_enable's (bk_linkage.hip): this file only reads the store.
-//   hap_count_kernel    a lane per row (two 16-byte loads, unpacked as link_count_rows does).  Two binary searches over the regions
+//   hap_count_kernel    a lane per row (two 16-byte loads, unpacked by bk_link_row.h).  Two binary searches over the regions
 //                       sorted by first cell give those that begin under the row; of them the ones that end at or before the row's
 //                       end are spanned.  Nearly every (row, region) is the reference haplotype and amplicon reads share their first
 //                       cell by the thousand, so cover and ref_count are privatised in LDS (8 bytes a region, at most 32 KiB;
@@ -33,12 +33,9 @@ constexpr int kHapFinishSlots = 4;             // groups of 64 slots a wave of h
 constexpr uint32_t kHapNone = 0xffffffffu;   // no entry: its cell lies behind every region
 
 // the row's mismatches as cell | base << 28 (a cell is below 2^27), kHapNone from n_mm on
-__device__ __forceinline__ void hap_unpack(const uint4 lo, const uint4 hi, uint32_t (&q)[8]) {
-    const uint32_t cell0 = lo.x, n_mm = min(lo.y >> 24, 8u);
-    const uint32_t e[8] = {lo.z & 0xffffffu, (lo.z >> 24) | ((lo.w & 0xffffu) << 8), (lo.w >> 16) | ((hi.x & 0xffu) << 16), hi.x >> 8,
-                           hi.y & 0xffffffu, (hi.y >> 24) | ((hi.z & 0xffffu) << 8), (hi.z >> 16) | ((hi.w & 0xffu) << 16), hi.w >> 8};
+__device__ __forceinline__ void hap_cells(const RowRegs& row, uint32_t (&q)[8]) {
 #pragma unroll
-    for (int s = 0; s < 8; ++s) q[s] = (uint32_t)s < n_mm ? (cell0 + (e[s] & 0xffffu)) | (((e[s] >> 16) & 3u) << 28) : kHapNone;
+    for (int s = 0; s < 8; ++s) q[s] = (uint32_t)s < row.n_mm ? (row.cell0 + (row.e[s] & 0xffffu)) | (((row.e[s] >> 16) & 3u) << 28) : kHapNone;
 }
 
 // the list of a row inside the cells [c0, c1): the entries in front of c0 shifted out (they are ascending, so those inside are one
@@ -77,9 +74,9 @@ __device__ __forceinline__ void hap_insert(const HapArgs& a, uint64_t row, uint3
         bool same = o == mine;
         if (!same && (uint32_t)((o - 1ull) & 0xfffull) == region) {   // the owner's row: written by an earlier launch
             const uint64_t r2 = (o - 1ull) >> 12;
-            if (r2 < a.row_cap) {
+            if (r2 < a.store.cap) {
                 uint32_t q2[8], l2[8];
-                hap_unpack(a.rows[2u * r2], a.rows[2u * r2 + 1u], q2);
+                hap_cells(a.store.load(r2), q2);
                 hap_list(q2, c0, c1, l2);
                 same = true;
 #pragma unroll
@@ -95,24 +92,16 @@ __device__ __forceinline__ void hap_insert(const HapArgs& a, uint64_t row, uint3
 __global__ __launch_bounds__(kHapBlock) void hap_count_kernel(HapArgs a) {
     extern __shared__ unsigned int hot_s[];            // [n_regions][2] cover, ref_count
     const uint32_t n_hot = 2u * a.n_regions;           // at most 2 * BK_HAP_MAX_REGIONS: 32 KiB
-    for (uint32_t i = threadIdx.x; i < n_hot; i += kHapBlock) hot_s[i] = 0u;
-    __syncthreads();
-    const uint64_t n_rows = std::min<uint64_t>(a.placed[0], a.row_cap);
+    lds_table_zero<kHapBlock>(hot_s, n_hot);
+    const uint64_t n_rows = a.store.rows_in_store();
     for (uint64_t r = (uint64_t)blockIdx.x * kHapBlock + threadIdx.x; r < n_rows; r += (uint64_t)gridDim.x * kHapBlock) {
-        const uint4 lo = a.rows[2u * r], hi = a.rows[2u * r + 1u];
-        const uint32_t cell0 = lo.x, end = lo.x + (lo.y & 0xffffu);
+        const RowRegs row = a.store.load(r);
+        const uint32_t cell0 = row.cell0, end = row.end;
         uint32_t q[8];
-        hap_unpack(lo, hi, q);
-        uint32_t s0 = 0, s1 = a.n_regions;             // the first region that begins at or behind cell0
-        while (s0 < s1) {
-            const uint32_t mid = (s0 + s1) >> 1;
-            if (a.sorted[mid].x < cell0) s0 = mid + 1u; else s1 = mid;
-        }
-        uint32_t t0 = s0, t1 = a.n_regions;            // ... and the first that begins at or behind the row's end
-        while (t0 < t1) {
-            const uint32_t mid = (t0 + t1) >> 1;
-            if (a.sorted[mid].x < end) t0 = mid + 1u; else t1 = mid;
-        }
+        hap_cells(row, q);
+        const auto first_cell = [&](uint32_t i) { return a.sorted[i].x; };
+        const uint32_t s0 = first_not_below(0u, a.n_regions, cell0, first_cell);   // the first region that begins at or behind cell0
+        const uint32_t t0 = first_not_below(s0, a.n_regions, end, first_cell);     // ... and the first that begins at or behind the row's end
         for (uint32_t i = s0; i < t0; ++i) {
             const uint2 reg = a.sorted[i];
             const uint32_t c0 = reg.x, c1 = reg.x + (reg.y & 0xffffu), region = reg.y >> 16;
@@ -127,11 +116,7 @@ __global__ __launch_bounds__(kHapBlock) void hap_count_kernel(HapArgs a) {
             hap_insert(a, r, region, c0, c1, l);
         }
     }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n_hot; i += kHapBlock) {
-        const unsigned int v = hot_s[i];
-        if (v) atomicAdd(a.hot + i, v);
-    }
+    lds_table_add_to<kHapBlock>(hot_s, n_hot, a.hot);
 }
 
 __global__ __launch_bounds__(kHapBlock) void hap_finish_kernel(HapArgs a) {
@@ -145,7 +130,7 @@ __global__ __launch_bounds__(kHapBlock) void hap_finish_kernel(HapArgs a) {
         for (int j = 0; j < kHapFinishSlots; ++j) o[j] = a.owner[base + 64u * j + lane];
 #pragma unroll
         for (int j = 0; j < kHapFinishSlots; ++j) {
-            const bool there = o[j] != 0ull && ((o[j] - 1ull) >> 12) < a.row_cap && (uint32_t)((o[j] - 1ull) & 0xfffull) < a.n_regions;
+            const bool there = o[j] != 0ull && ((o[j] - 1ull) >> 12) < a.store.cap && (uint32_t)((o[j] - 1ull) & 0xfffull) < a.n_regions;
             if (!there) o[j] = 0ull;
             m[j] = __ballot(there);
             total += (uint32_t)__popcll(m[j]);
@@ -163,17 +148,18 @@ __global__ __launch_bounds__(kHapBlock) void hap_finish_kernel(HapArgs a) {
             const uint32_t region = (uint32_t)((o[j] - 1ull) & 0xfffull);
             const uint2 reg = a.regions[region];
             uint32_t q[8], l[8];
-            hap_unpack(a.rows[2u * row], a.rows[2u * row + 1u], q);
+            hap_cells(a.store.load(row), q);
             const uint32_t n = hap_list(q, reg.x, reg.x + reg.y, l);
-            uint32_t e[8];                              // offset from the region's first cell | base << 16, zero from n on: the row's packing
+            uint32_t e[8], mm[6];                       // offset from the region's first cell | base << 16, zero from n on: the row's packing
 #pragma unroll
             for (int s = 0; s < 8; ++s) e[s] = (uint32_t)s < n ? ((l[s] & 0x0fffffffu) - reg.x) | ((l[s] >> 28) << 16) : 0u;
+            row_mm_words(e, mm);
             uint2* __restrict__ w = reinterpret_cast<uint2*>(a.entries + out);   // bk_hap_entry: five pairs of words
             w[0] = make_uint2(region, a.count[base + 64u * j + lane]);
             w[1] = make_uint2(n, 0u);
-            w[2] = make_uint2(e[0] | (e[1] << 24), (e[1] >> 8) | (e[2] << 16));
-            w[3] = make_uint2((e[2] >> 16) | (e[3] << 8), e[4] | (e[5] << 24));
-            w[4] = make_uint2((e[5] >> 8) | (e[6] << 16), (e[6] >> 16) | (e[7] << 8));
+            w[2] = make_uint2(mm[0], mm[1]);
+            w[3] = make_uint2(mm[2], mm[3]);
+            w[4] = make_uint2(mm[4], mm[5]);
         }
     }
 }
@@ -182,9 +168,7 @@ __global__ __launch_bounds__(kHapBlock) void hap_finish_kernel(HapArgs a) {
 
 void launch_hap_count(const HapArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream) {
     if (a.n_regions == 0 || rows_upper == 0) return;
-    const uint64_t blocks = (rows_upper + kHapBlock - 1) / kHapBlock;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 2));
-    hipLaunchKernelGGL(hap_count_kernel, dim3(grid), dim3(kHapBlock), (size_t)a.n_regions * 2u * sizeof(unsigned int), stream, a);
+    hipLaunchKernelGGL(hap_count_kernel, dim3(row_grid(rows_upper, kHapBlock, n_cus, 2)), dim3(kHapBlock), (size_t)a.n_regions * 2u * sizeof(unsigned int), stream, a);
 }
 
 void launch_hap_finish(const HapArgs& a, hipStream_t stream) {

@@ -4,6 +4,7 @@
 
 #include "../../include/bronko_hip.h"
 #include "bk_device.h"
+#include "bk_link_row.h"
 
 namespace bk {
 
@@ -498,9 +499,9 @@ struct LinkArgs {
     RecordsView rec;                     // link_scan_kernel's batch
     AnchorIndex ix;
     uint32_t max_mismatches;
-    // the sample: its row store (a row is two uint4: bk_link_row) and tallies
-    uint4* rows; uint64_t row_cap;
-    unsigned long long* tallies;         // [4] records, placed (= the rows in the store), unplaced, discordant
+    // the sample: its row store (bk_link_row.h) and tallies
+    RowStoreView store;
+    unsigned long long* tallies;         // [4] records, placed (= the rows in the store: store.placed), unplaced, discordant
     // the count: link_count_kernel
     const uint32_t* sites;               // [n_sites] cells, strictly ascending
     const uint32_t* pair_lo;             // [n_sites] index of the pair (i, i + 1); the pair (i, j) is pair_lo[i] + (j - i - 1)
@@ -514,9 +515,9 @@ void launch_link_count(const LinkArgs& a, uint64_t rows_upper, int n_cus, hipStr
 // bk_sample_codons: how many rows of bk_link_enable's store carry each of the 64 triplets at every codon of the caller's coding regions
 // (bk_codons.hip; the rule: include/bronko_hip.h)
 struct CodonArgs {
-    AnchorIndex ix;                      // ref_words only
-    const uint4* rows; uint64_t row_cap; // the sample's row store and its tallies: LinkArgs'
-    const unsigned long long* tallies;
+    const uint32_t* ref_words;           // AnchorIndex's
+    uint32_t total_cells;
+    RowStoreView store;                  // the sample's row store: LinkArgs'
     const uint4* sorted;                 // [n_regions] by first cell: {cell0, n_codons, index of its first codon, max end cell of the regions up to here}
     const uint2* regions;                // [n_regions] the caller's order: {cell0, index of its first codon}
     uint32_t n_regions, n_codons;
@@ -530,8 +531,7 @@ void launch_codon_finish(const CodonArgs& a, hipStream_t stream);
 // (bk_haplotypes.hip; the rule: include/bronko_hip.h)
 typedef bk_hap_entry HapEntryDev;
 struct HapArgs {
-    const uint4* rows; uint64_t row_cap; // the sample's row store: LinkArgs'
-    const unsigned long long* placed;    // ... and the rows in it (LinkArgs::tallies + 1)
+    RowStoreView store;                  // the sample's row store: LinkArgs'
     const uint2* sorted;                 // [n_regions] by first cell: {cell0, len | the caller's index << 16}
     const uint2* regions;                // [n_regions] the caller's order: {cell0, len}
     uint32_t n_regions, table_log2;

@@ -7,9 +7,9 @@
 //                       set bits of the folded word are the mismatches' positions (ctz).  A record against the reference is
 //                       compared with rc_words at the mirrored cell; its position i is cell dL + n - 1 - i and its base there
 //                       the complement -- nothing is reverse-complemented in memory.  A placed record leaves one row of 32 bytes
-//                       (bk_link_row) in the sample's row store: one returning add per wave (ballot + mbcnt), two 16-byte stores
-//                       per row.  The sample's tallies: one add per wave and tally.
-//   link_count_kernel   at the sample's end, given the sites: a lane per row (two 16-byte loads) binary-searches the first site
+//                       (bk_link_row, packed by bk_link_row.h) in the sample's row store: one returning add per wave (ballot +
+//                       mbcnt), two 16-byte stores per row.  The sample's tallies: one add per wave and tally.
+//   link_count_kernel   at the sample's end, given the sites: a lane per row (bk_link_row.h) binary-searches the first site
 //                       at or behind the row's first cell, walks the sites the row covers and adds 1 to count[bA][bB] of every
 //                       pair of them within max_dist.  A counter table of at most kLinkLdsPairs pairs is privatised in LDS
 //                       (zeroed, LDS atomics, one global add per non-zero counter behind a barrier); a larger one takes global
@@ -44,7 +44,8 @@ __device__ __forceinline__ bool link_place(const LinkArgs& a, uint32_t r, LinkTa
     const uint32_t last_word = (uint32_t)(n - 1) >> 4;
     const uint32_t* __restrict__ text = against ? a.ix.rc_words : a.ix.ref_words;
     const int64_t diag = against ? (int64_t)a.ix.total_cells - dL - n : (int64_t)dL;
-    uint32_t e[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // the mismatches, ascending by offset: offset | base << 16 (static indices only)
+    RowRegs row{};                                    // e: the mismatches, ascending by offset (static indices only)
+    uint32_t (&e)[8] = row.e;
     uint32_t m = 0;
     for (uint32_t i = 0; i < (uint32_t)n; i += 16u) {
         uint32_t x = mismatch_bits16(w, last_word, i, (uint32_t)n, text, diag);
@@ -70,8 +71,8 @@ __device__ __forceinline__ bool link_place(const LinkArgs& a, uint32_t r, LinkTa
         }
     }
     if (m > a.max_mismatches) { t.discordant++; return false; }
-    lo = make_uint4((uint32_t)dL, (uint32_t)n | (against ? 1u << 16 : 0u) | (m << 24), e[0] | (e[1] << 24), (e[1] >> 8) | (e[2] << 16));
-    hi = make_uint4((e[2] >> 16) | (e[3] << 8), e[4] | (e[5] << 24), (e[5] >> 8) | (e[6] << 16), (e[6] >> 16) | (e[7] << 8));
+    row.cell0 = (uint32_t)dL; row.end = (uint32_t)(dL + n); row.strand = against ? 1u : 0u; row.n_mm = m;
+    row_pack(row, lo, hi);
     return true;
 }
 
@@ -88,11 +89,11 @@ __global__ __launch_bounds__(kLinkBlock) void link_scan_kernel(LinkArgs a) {
         if (mask == 0ull) continue;
         const uint32_t cnt = (uint32_t)__popcll(mask);
         unsigned long long at = 0ull;
-        if (lane == 0) at = atomicAdd(a.tallies + 1, (unsigned long long)cnt);
+        if (lane == 0) at = atomicAdd(a.store.placed, (unsigned long long)cnt);
         at = __shfl(at, 0);
         if (row) {
             const uint64_t o = at + lane_prefix(mask);
-            if (o < a.row_cap) { a.rows[2u * o] = lo; a.rows[2u * o + 1u] = hi; }   // (the engine made room for every record of the batch)
+            if (o < a.store.cap) a.store.store(o, lo, hi);   // (the engine made room for every record of the batch)
         }
     }
     const uint32_t sums[3] = {wave_total(t.records), wave_total(t.unplaced), wave_total(t.discordant)};
@@ -103,28 +104,13 @@ __global__ __launch_bounds__(kLinkBlock) void link_scan_kernel(LinkArgs a) {
     }
 }
 
-// the row's base at offset `off` from its first cell: one of its mismatches, else the reference's
-__device__ __forceinline__ uint32_t row_base(const uint32_t (&e)[8], uint32_t n_mm, uint32_t off, uint32_t ref_base) {
-    uint32_t b = ref_base;
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-        if ((uint32_t)s < n_mm && (e[s] & 0xffffu) == off) b = (e[s] >> 16) & 3u;
-    return b;
-}
-
 template <bool kLds>
 __device__ __forceinline__ void link_count_rows(const LinkArgs& a, unsigned int* __restrict__ table) {
-    const uint64_t n_rows = std::min<uint64_t>(a.tallies[1], a.row_cap);
+    const uint64_t n_rows = a.store.rows_in_store();
     for (uint64_t r = (uint64_t)blockIdx.x * kLinkBlock + threadIdx.x; r < n_rows; r += (uint64_t)gridDim.x * kLinkBlock) {
-        const uint4 lo = a.rows[2u * r], hi = a.rows[2u * r + 1u];
-        const uint32_t cell0 = lo.x, end = lo.x + (lo.y & 0xffffu), n_mm = min(lo.y >> 24, 8u);
-        const uint32_t e[8] = {lo.z & 0xffffffu, (lo.z >> 24) | ((lo.w & 0xffffu) << 8), (lo.w >> 16) | ((hi.x & 0xffu) << 16), hi.x >> 8,
-                               hi.y & 0xffffffu, (hi.y >> 24) | ((hi.z & 0xffffu) << 8), (hi.z >> 16) | ((hi.w & 0xffu) << 16), hi.w >> 8};
-        uint32_t s0 = 0, s1 = a.n_sites;               // the first site at or behind cell0
-        while (s0 < s1) {
-            const uint32_t mid = (s0 + s1) >> 1;
-            if (a.sites[mid] < cell0) s0 = mid + 1u; else s1 = mid;
-        }
+        const RowRegs row = a.store.load(r);
+        const uint32_t cell0 = row.cell0, end = row.end;
+        const uint32_t s0 = first_not_below(0u, a.n_sites, cell0, [&](uint32_t i) { return a.sites[i]; });   // the first site at or behind cell0
         for (uint32_t i = s0; i < a.n_sites; ++i) {
             const uint32_t ci = a.sites[i];
             if (ci >= end) break;
@@ -133,10 +119,10 @@ __device__ __forceinline__ void link_count_rows(const LinkArgs& a, unsigned int*
             uint32_t cj = a.sites[j];
             if (cj >= end) break;                      // (the row's last site: no pair begins here or behind)
             if (cj - ci > a.max_dist) continue;
-            const uint32_t ba = row_base(e, n_mm, ci - cell0, sym_at(a.ix.ref_words, ci));
+            const uint32_t ba = row_base(row, ci - cell0, sym_at(a.ix.ref_words, ci));
             const uint64_t p0 = (uint64_t)a.pair_lo[i];
             for (;;) {
-                const uint32_t bb = row_base(e, n_mm, cj - cell0, sym_at(a.ix.ref_words, cj));
+                const uint32_t bb = row_base(row, cj - cell0, sym_at(a.ix.ref_words, cj));
                 const uint64_t at = (p0 + (j - i - 1u)) * 16u + ba * 4u + bb;
                 if (at < a.n_pairs * 16u) {            // (the host enumerated every pair that a row can cover)
                     if (kLds) atomicAdd(table + (uint32_t)at, 1u);
@@ -153,14 +139,9 @@ __device__ __forceinline__ void link_count_rows(const LinkArgs& a, unsigned int*
 __global__ __launch_bounds__(kLinkBlock) void link_count_lds_kernel(LinkArgs a) {
     extern __shared__ unsigned int table_s[];
     const uint32_t n_counters = (uint32_t)a.n_pairs * 16u;   // at most kLinkLdsPairs * 16
-    for (uint32_t i = threadIdx.x; i < n_counters; i += kLinkBlock) table_s[i] = 0u;
-    __syncthreads();
+    lds_table_zero<kLinkBlock>(table_s, n_counters);
     link_count_rows<true>(a, table_s);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n_counters; i += kLinkBlock) {
-        const unsigned int v = table_s[i];
-        if (v) atomicAdd(a.counts + i, v);
-    }
+    lds_table_add_to<kLinkBlock>(table_s, n_counters, a.counts);
 }
 
 __global__ __launch_bounds__(kLinkBlock) void link_count_kernel(LinkArgs a) { link_count_rows<false>(a, nullptr); }
@@ -169,15 +150,12 @@ __global__ __launch_bounds__(kLinkBlock) void link_count_kernel(LinkArgs a) { li
 
 void launch_link_scan(const LinkArgs& a, int n_cus, hipStream_t stream) {
     if (a.rec.n_records == 0) return;
-    const uint64_t blocks = (a.rec.n_records + kLinkBlock - 1) / kLinkBlock;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
-    hipLaunchKernelGGL(link_scan_kernel, dim3(grid), dim3(kLinkBlock), 0, stream, a);
+    hipLaunchKernelGGL(link_scan_kernel, dim3(row_grid(a.rec.n_records, kLinkBlock, n_cus, 8)), dim3(kLinkBlock), 0, stream, a);
 }
 
 void launch_link_count(const LinkArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream) {
     if (a.n_pairs == 0 || rows_upper == 0) return;
-    const uint64_t blocks = (rows_upper + kLinkBlock - 1) / kLinkBlock;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
+    const unsigned grid = row_grid(rows_upper, kLinkBlock, n_cus, 8);
     if (a.n_pairs <= kLinkLdsPairs)
         hipLaunchKernelGGL(link_count_lds_kernel, dim3(grid), dim3(kLinkBlock), (size_t)a.n_pairs * 16u * sizeof(unsigned int), stream, a);
     else

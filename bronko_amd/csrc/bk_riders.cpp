@@ -1,6 +1,8 @@
 // bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
 // short insertions and deletions (bk_indels.hip) and linkage (bk_linkage.hip), with the anchor tables the last two share, and the codon
-// and haplotype counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip).
+// and haplotype counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip).  The three counts over the
+// store (bk_sample_linkage, bk_sample_codons, bk_sample_haplotypes) share one lifecycle, StoreCount of bk_engine.h, and the helpers in
+// front of them here: what they ask of the engine's state, of a region's cells, and how their tables reach the device.
 // Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
 // push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
 // indels, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
@@ -130,6 +132,11 @@ static int anchor_index_check(const IndexTables& ix, const char* who) {
                     who, (unsigned long long)ix.total_cells);
     return BK_OK;
 }
+// the sequences of the one genome file these features take (n_files == 1): how many, and sequence q's cells {first, end}
+static size_t n_seqs(const IndexTables& ix) { return (size_t)ix.h_n_seqs[0]; }
+static std::pair<uint64_t, uint64_t> seq_cells(const IndexTables& ix, size_t q) {
+    return {ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q], ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q] + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q]};
+}
 // the engine's anchor tables: the ones the other feature holds, else built here
 static int anchor_tables(bk_engine* e, const char* who, std::shared_ptr<AnchorTables>& out) {
     if ((out = e->anchors.lock())) return BK_OK;
@@ -145,7 +152,7 @@ static int anchor_tables(bk_engine* e, const char* who, std::shared_ptr<AnchorTa
         BK_HIP(t->unique_bits.upload(bits));
     }
     std::vector<uint32_t> lo;
-    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) lo.push_back((uint32_t)ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q]);
+    for (size_t q = 0; q < n_seqs(ix); q++) lo.push_back((uint32_t)seq_cells(ix, q).first);
     lo.push_back((uint32_t)ix.total_cells);
     if (lo.size() < 2) return fail(BK_ERR_INVALID, "%s: the genome file has no sequence", who);
     BK_HIP(t->seq_lo.upload(lo));
@@ -284,18 +291,72 @@ static int link_free_old(Linkage& d, bool wait) {
 int Linkage::begin_sample(bk_engine* e) {
     if (int rc = link_free_old(*this, true)) return rc;
     BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
-    rows_upper = 0; in_sample = true; made = false; n_sites = 0; n_pairs = 0;
-    if (codons) codons->made = false;
-    if (haps) haps->made = false;
+    rows_upper = 0; in_sample = true; n_sites = 0; n_pairs = 0;
+    for (StoreCount* c : {(StoreCount*)this, (StoreCount*)codons.get(), (StoreCount*)haps.get()}) if (c) c->made = false;
     return BK_OK;
 }
+// the sample's row store as the kernels take it (bk_link_row.h)
+static bk::RowStoreView store_view(const Linkage& d) { return bk::RowStoreView{d.rows.p, d.rows.n / 2, d.tallies.p + 1}; }
+
+// ---- a count over the row store: what bk_sample_linkage, bk_sample_codons and bk_sample_haplotypes share ---------------------------
+int StoreCount::wait_last() {
+    if (count_in_flight) { BK_HIP(hipEventSynchronize(counted)); count_in_flight = false; }
+    made = false;
+    return BK_OK;
+}
+int StoreCount::record(hipStream_t stream) {
+    BK_HIP(hipGetLastError());
+    BK_HIP(counted.create());
+    BK_HIP(hipEventRecord(counted, stream));
+    count_in_flight = made = true;
+    return BK_OK;
+}
+// what each of the three asks before it looks at its items (sites or regions)
+static int store_count_ready(const bk_engine* e, const void* items, uint32_t n_items, const char* who) {
+    if (!e || (!items && n_items)) return fail(BK_ERR_INVALID, "null argument");
+    if (e->in_sample) return fail(BK_ERR_STATE, "%s comes after bk_sample_finalize", who);
+    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "%s: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)", who);
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "%s: bk_sample_finalize has not run for this sample", who);
+    return BK_OK;
+}
+// region i of `who`, the cells [c0, end): inside the index's cells and inside one sequence
+static int region_cells_check(const IndexTables& ix, const char* who, uint32_t i, uint64_t c0, uint64_t end) {
+    if (end > ix.total_cells)
+        return fail(BK_ERR_INVALID, "%s: region %u ends at cell %llu, the index has %llu", who, i, (unsigned long long)end, (unsigned long long)ix.total_cells);
+    for (size_t q = 0; q < n_seqs(ix); q++) {
+        const auto sq = seq_cells(ix, q);
+        if (c0 >= sq.first && c0 < sq.second && end > sq.second)
+            return fail(BK_ERR_INVALID, "%s: region %u crosses a sequence border (cells %llu to %llu, its sequence ends at %llu)", who, i, (unsigned long long)c0,
+                        (unsigned long long)end, (unsigned long long)sq.second);
+    }
+    return BK_OK;
+}
+// the regions' indices ordered by first cell, the caller's order among equals
+template <typename R>
+static std::vector<uint32_t> by_first_cell(const R* regions, uint32_t n) {
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return regions[x].cell0 < regions[y].cell0; });
+    return order;
+}
+// n elements to the device behind the stream's work, through a pinned copy (the copy is asynchronous; wait_last has made both buffers
+// free).  A call uploads its tables before it grows its counters: device memory is allocated in the order it always was, and where
+// a counter table lands has moved codon_count_kernel's time by several per cent.
+template <typename T>
+static int upload(PinnedBuf<T>& h, DevBuf<T>& d, const T* src, size_t n, hipStream_t stream) {
+    BK_HIP(h.grow(std::max<size_t>(n, 1)));
+    BK_HIP(grow(d, n));
+    if (n) { std::memcpy(h.p, src, n * sizeof(T)); BK_HIP(hipMemcpyAsync(d.p, h.p, n * sizeof(T), hipMemcpyHostToDevice, stream)); }
+    return BK_OK;
+}
+
 // what both linkage kernels are given (a.rec: the scan's batch)
 static bk::LinkArgs link_args(const bk_engine* e) {
     const Linkage& d = *e->linkage;
     bk::LinkArgs a{};
     a.ix = anchor_index(*e->ix, *d.anchors);
     a.max_mismatches = d.cfg.max_mismatches; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n / 2;
+    a.store = store_view(d);
     a.sites = d.sites.p; a.pair_lo = d.pair_lo.p; a.n_sites = d.n_sites; a.max_dist = d.max_dist; a.n_pairs = d.n_pairs;
     a.counts = d.counts.p;
     return a;
@@ -358,10 +419,7 @@ int bk_link_enable(bk_engine* e, const bk_link_config* cfg) {
 }
 
 int bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uint32_t max_dist) {
-    if (!e || (!cells && n_sites)) return fail(BK_ERR_INVALID, "null argument");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage comes after bk_sample_finalize");
-    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_linkage: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_linkage: bk_sample_finalize has not run for this sample");
+    if (int rc = store_count_ready(e, cells, n_sites, "bk_sample_linkage")) return rc;
     if (n_sites > BK_LINK_MAX_SITES) return fail(BK_ERR_INVALID, "bk_sample_linkage: at most %d sites, got %u", BK_LINK_MAX_SITES, n_sites);
     if (max_dist < 1 || max_dist > BK_LINK_MAX_DIST) return fail(BK_ERR_INVALID, "bk_sample_linkage: max_dist must be 1..%d, got %u", BK_LINK_MAX_DIST, max_dist);
     const IndexTables& ix = *e->ix;
@@ -372,7 +430,7 @@ int bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uin
     Linkage& d = *e->linkage;
     // the pairs: i < j in one sequence, cell_j - cell_i <= max_dist -- for each i a stretch of j that starts at i + 1
     std::vector<uint32_t> seq_end;               // end cell of every sequence of the genome file
-    for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) seq_end.push_back((uint32_t)(ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q] + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q]));
+    for (size_t q = 0; q < n_seqs(ix); q++) seq_end.push_back((uint32_t)seq_cells(ix, q).second);
     std::vector<uint32_t> pair_lo(n_sites);
     uint64_t n_pairs = 0;
     for (uint32_t i = 0, j = 0, s = 0; i < n_sites; i++) {
@@ -385,26 +443,15 @@ int bk_sample_linkage(bk_engine* e, const uint32_t* cells, uint32_t n_sites, uin
     if (n_pairs > BK_LINK_MAX_PAIRS)
         return fail(BK_ERR_INVALID, "bk_sample_linkage: %llu pairs of sites within %u cells, at most %u are counted", (unsigned long long)n_pairs, max_dist, BK_LINK_MAX_PAIRS);
     BK_HIP(hipSetDevice(e->device));
-    // an earlier count may still read the sites, pair_lo, the counters and the pinned copies that are replaced here: wait for that
-    // launch alone -- nothing else of the stream's work is waited for
-    if (d.count_in_flight) { BK_HIP(hipEventSynchronize(d.counted)); d.count_in_flight = false; }
-    BK_HIP(d.h_sites.grow(std::max<size_t>(n_sites, 1))); BK_HIP(d.h_pair_lo.grow(std::max<size_t>(n_sites, 1)));
-    if (n_sites) { std::memcpy(d.h_sites.p, cells, n_sites * sizeof(uint32_t)); std::memcpy(d.h_pair_lo.p, pair_lo.data(), n_sites * sizeof(uint32_t)); }
-    d.n_sites = n_sites; d.max_dist = max_dist; d.n_pairs = n_pairs; d.made = false;
-    BK_HIP(grow(d.sites, n_sites)); BK_HIP(grow(d.pair_lo, n_sites)); BK_HIP(grow(d.counts, (size_t)n_pairs * 16));
+    if (int rc = d.wait_last()) return rc;         // (the sites, pair_lo, the counters and the pinned copies are replaced here)
+    d.n_sites = n_sites; d.max_dist = max_dist; d.n_pairs = n_pairs;
     bk_engine::Span sp(e, 1);
-    if (n_sites) {
-        BK_HIP(hipMemcpyAsync(d.sites.p, d.h_sites.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-        BK_HIP(hipMemcpyAsync(d.pair_lo.p, d.h_pair_lo.p, n_sites * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    }
+    if (int rc = upload(d.h_sites, d.sites, cells, n_sites, e->stream)) return rc;
+    if (int rc = upload(d.h_pair_lo, d.pair_lo, pair_lo.data(), n_sites, e->stream)) return rc;
+    BK_HIP(grow(d.counts, (size_t)n_pairs * 16));
     if (n_pairs) BK_HIP(hipMemsetAsync(d.counts.p, 0, (size_t)n_pairs * 16 * sizeof(unsigned int), e->stream));
     bk::launch_link_count(link_args(e), d.rows_upper, ix.n_cus, e->stream);
-    BK_HIP(hipGetLastError());
-    BK_HIP(d.counted.create());
-    BK_HIP(hipEventRecord(d.counted, e->stream));
-    d.count_in_flight = true;
-    d.made = true;
-    return BK_OK;
+    return d.record(e->stream);
 }
 
 static int link_finalized(bk_engine* e, const char* who) {
@@ -455,32 +502,21 @@ static bk::CodonArgs codon_args(const bk_engine* e) {
     const Linkage& d = *e->linkage;
     const Codons& c = *d.codons;
     bk::CodonArgs a{};
-    a.ix = anchor_index(*e->ix, *d.anchors);
-    a.rows = d.rows.p; a.row_cap = d.rows.n / 2; a.tallies = d.tallies.p;
+    a.store = store_view(d);
+    a.ref_words = e->ix->ref_words.p + bk::scan_ref_pad_words(); a.total_cells = (uint32_t)e->ix->total_cells;   // (anchor_index's)
     a.sorted = c.sorted.p; a.regions = c.regions.p; a.n_regions = c.n_regions; a.n_codons = c.n_codons;
     a.cover_diff = c.cover_diff.p; a.counts = c.counts.p;
     return a;
 }
 
 int bk_sample_codons(bk_engine* e, const bk_codon_region* regions, uint32_t n_regions) {
-    if (!e || (!regions && n_regions)) return fail(BK_ERR_INVALID, "null argument");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_codons comes after bk_sample_finalize");
-    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_codons: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_codons: bk_sample_finalize has not run for this sample");
+    if (int rc = store_count_ready(e, regions, n_regions, "bk_sample_codons")) return rc;
     if (n_regions > BK_CODON_MAX_REGIONS) return fail(BK_ERR_INVALID, "bk_sample_codons: at most %d regions, got %u", BK_CODON_MAX_REGIONS, n_regions);
     const IndexTables& ix = *e->ix;
     uint64_t n_codons = 0;
     for (uint32_t i = 0; i < n_regions; i++) {
-        const uint64_t c0 = regions[i].cell0, end = c0 + 3ull * regions[i].n_codons;
         if (regions[i].n_codons == 0) return fail(BK_ERR_INVALID, "bk_sample_codons: region %u has no codon", i);
-        if (end > ix.total_cells)
-            return fail(BK_ERR_INVALID, "bk_sample_codons: region %u ends at cell %llu, the index has %llu", i, (unsigned long long)end, (unsigned long long)ix.total_cells);
-        for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) {   // (one genome file: bk_link_enable)
-            const uint64_t lo = ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q], hi = lo + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q];
-            if (c0 >= lo && c0 < hi && end > hi)
-                return fail(BK_ERR_INVALID, "bk_sample_codons: region %u crosses a sequence border (cells %llu to %llu, its sequence ends at %llu)", i,
-                            (unsigned long long)c0, (unsigned long long)end, (unsigned long long)hi);
-        }
+        if (int rc = region_cells_check(ix, "bk_sample_codons", i, regions[i].cell0, regions[i].cell0 + 3ull * regions[i].n_codons)) return rc;
         n_codons += regions[i].n_codons;
     }
     if (n_codons > BK_CODON_MAX_CODONS)
@@ -489,41 +525,31 @@ int bk_sample_codons(bk_engine* e, const bk_codon_region* regions, uint32_t n_re
     if (!d.codons) d.codons.reset(new Codons());
     Codons& c = *d.codons;
     BK_HIP(hipSetDevice(e->device));
-    // an earlier count may still read the tables, the counters and the pinned copies that are replaced here: wait for it alone
-    if (c.count_in_flight) { BK_HIP(hipEventSynchronize(c.counted)); c.count_in_flight = false; }
-    c.made = false;
-    BK_HIP(c.h_sorted.grow(std::max<size_t>(n_regions, 1))); BK_HIP(c.h_regions.grow(std::max<size_t>(n_regions, 1)));
-    {   // the caller's order with each region's first codon; the same sorted by first cell, with the running maximum of the ends
-        std::vector<uint32_t> order(n_regions);
-        uint32_t base = 0;
-        for (uint32_t i = 0; i < n_regions; i++) { order[i] = i; c.h_regions.p[i] = make_uint2(regions[i].cell0, base); base += regions[i].n_codons; }
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return regions[x].cell0 < regions[y].cell0; });
-        uint32_t reach = 0;
-        for (uint32_t i = 0; i < n_regions; i++) {
-            const bk_codon_region& r = regions[order[i]];
-            reach = std::max(reach, r.cell0 + 3u * r.n_codons);
-            c.h_sorted.p[i] = make_uint4(r.cell0, r.n_codons, c.h_regions.p[order[i]].y, reach);
-        }
+    if (int rc = c.wait_last()) return rc;         // (the tables, the counters and the pinned copies are replaced here)
+    // the caller's order with each region's first codon; the same sorted by first cell, with the running maximum of the ends
+    std::vector<uint2> in_order(n_regions);
+    std::vector<uint4> sorted(n_regions);
+    uint32_t base = 0, reach = 0;
+    for (uint32_t i = 0; i < n_regions; i++) { in_order[i] = make_uint2(regions[i].cell0, base); base += regions[i].n_codons; }
+    const std::vector<uint32_t> order = by_first_cell(regions, n_regions);
+    for (uint32_t i = 0; i < n_regions; i++) {
+        const bk_codon_region& r = regions[order[i]];
+        reach = std::max(reach, r.cell0 + 3u * r.n_codons);
+        sorted[i] = make_uint4(r.cell0, r.n_codons, in_order[order[i]].y, reach);
     }
     c.n_regions = n_regions; c.n_codons = (uint32_t)n_codons;
-    BK_HIP(grow(c.sorted, n_regions)); BK_HIP(grow(c.regions, n_regions));
-    BK_HIP(grow(c.cover_diff, (size_t)n_codons + 1)); BK_HIP(grow(c.counts, (size_t)n_codons * 64));
     bk_engine::Span sp(e, 1);
+    if (int rc = upload(c.h_sorted, c.sorted, sorted.data(), n_regions, e->stream)) return rc;
+    if (int rc = upload(c.h_regions, c.regions, in_order.data(), n_regions, e->stream)) return rc;
+    BK_HIP(grow(c.cover_diff, (size_t)n_codons + 1)); BK_HIP(grow(c.counts, (size_t)n_codons * 64));
     if (n_regions) {
-        BK_HIP(hipMemcpyAsync(c.sorted.p, c.h_sorted.p, n_regions * sizeof(uint4), hipMemcpyHostToDevice, e->stream));
-        BK_HIP(hipMemcpyAsync(c.regions.p, c.h_regions.p, n_regions * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
         BK_HIP(hipMemsetAsync(c.cover_diff.p, 0, ((size_t)n_codons + 1) * sizeof(unsigned int), e->stream));
         BK_HIP(hipMemsetAsync(c.counts.p, 0, (size_t)n_codons * 64 * sizeof(unsigned int), e->stream));
     }
     const bk::CodonArgs a = codon_args(e);
     bk::launch_codon_count(a, d.rows_upper, ix.n_cus, e->stream);
     bk::launch_codon_finish(a, e->stream);
-    BK_HIP(hipGetLastError());
-    BK_HIP(c.counted.create());
-    BK_HIP(hipEventRecord(c.counted, e->stream));
-    c.count_in_flight = true;
-    c.made = true;
-    return BK_OK;
+    return c.record(e->stream);
 }
 
 int bk_sample_download_codons(bk_engine* e, bk_codon_summary* summary, uint32_t* counts, uint64_t cap_codons) {
@@ -545,7 +571,7 @@ static bk::HapArgs hap_args(const bk_engine* e) {
     const Linkage& d = *e->linkage;
     const Haplotypes& h = *d.haps;
     bk::HapArgs a{};
-    a.rows = d.rows.p; a.row_cap = d.rows.n / 2; a.placed = d.tallies.p + 1;
+    a.store = store_view(d);
     a.sorted = h.sorted.p; a.regions = h.regions.p; a.n_regions = h.n_regions; a.table_log2 = h.table_log2;
     a.hot = h.hot.p; a.owner = h.owner.p; a.count = h.count.p; a.tallies = h.tallies.p;
     a.entries = h.entries.p; a.entry_cap = std::min<uint64_t>(h.entries.n, 1ull << h.table_log2);
@@ -554,52 +580,36 @@ static bk::HapArgs hap_args(const bk_engine* e) {
 
 int bk_sample_haplotypes(bk_engine* e, const bk_hap_region* regions, uint32_t n_regions, uint32_t table_log2) {
     static_assert(sizeof(bk_hap_entry) == 40 && sizeof(bk_hap_region) == sizeof(uint2), "hap_finish_kernel writes an entry as ten words");
-    if (!e || (!regions && n_regions)) return fail(BK_ERR_INVALID, "null argument");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_haplotypes comes after bk_sample_finalize");
-    if (!e->linkage || !e->linkage->in_sample) return fail(BK_ERR_STATE, "bk_sample_haplotypes: linkage was not enabled for this sample (bk_link_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_haplotypes: bk_sample_finalize has not run for this sample");
+    if (int rc = store_count_ready(e, regions, n_regions, "bk_sample_haplotypes")) return rc;
     if (n_regions > BK_HAP_MAX_REGIONS) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: at most %d regions, got %u", BK_HAP_MAX_REGIONS, n_regions);
     if (table_log2 < 10 || table_log2 > 24) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: table_log2 must be 10..24, got %u", table_log2);
     if (const char* v = test_env("BK_HAP_TABLE_SHRINK"))   // testing build: 2^-v of the slots asked for, not below 2^10 -- a small sample fills a table
         table_log2 -= std::min<uint32_t>(table_log2 - 10, (uint32_t)std::max(0, atoi(v)));
     const IndexTables& ix = *e->ix;
     for (uint32_t i = 0; i < n_regions; i++) {
-        const uint64_t c0 = regions[i].cell0, end = c0 + regions[i].len;
         if (regions[i].len == 0) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u has no cell", i);
         if (regions[i].len > BK_HAP_MAX_LEN) return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u has %u cells, at most %d", i, regions[i].len, BK_HAP_MAX_LEN);
-        if (end > ix.total_cells)
-            return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u ends at cell %llu, the index has %llu", i, (unsigned long long)end, (unsigned long long)ix.total_cells);
-        for (size_t q = 0; q < (size_t)ix.h_n_seqs[0]; q++) {   // (one genome file: bk_link_enable)
-            const uint64_t lo = ix.h_seq_cell[(size_t)ix.h_seq_first[0] + q], hi = lo + ix.h_seq_len[(size_t)ix.h_seq_first[0] + q];
-            if (c0 >= lo && c0 < hi && end > hi)
-                return fail(BK_ERR_INVALID, "bk_sample_haplotypes: region %u crosses a sequence border (cells %llu to %llu, its sequence ends at %llu)", i,
-                            (unsigned long long)c0, (unsigned long long)end, (unsigned long long)hi);
-        }
+        if (int rc = region_cells_check(ix, "bk_sample_haplotypes", i, regions[i].cell0, (uint64_t)regions[i].cell0 + regions[i].len)) return rc;
     }
     Linkage& d = *e->linkage;
     if (!d.haps) d.haps.reset(new Haplotypes());
     Haplotypes& h = *d.haps;
     BK_HIP(hipSetDevice(e->device));
-    // an earlier count may still read the tables, the counters and the pinned copies that are replaced here: wait for it alone
-    if (h.count_in_flight) { BK_HIP(hipEventSynchronize(h.counted)); h.count_in_flight = false; }
-    h.made = false;
-    BK_HIP(h.h_sorted.grow(std::max<size_t>(n_regions, 1))); BK_HIP(h.h_regions.grow(std::max<size_t>(n_regions, 1)));
-    {   // the caller's order; the same sorted by first cell, each with its index in the caller's order
-        std::vector<uint32_t> order(n_regions);
-        for (uint32_t i = 0; i < n_regions; i++) { order[i] = i; h.h_regions.p[i] = make_uint2(regions[i].cell0, regions[i].len); }
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return regions[x].cell0 < regions[y].cell0; });
-        for (uint32_t i = 0; i < n_regions; i++) h.h_sorted.p[i] = make_uint2(regions[order[i]].cell0, regions[order[i]].len | (order[i] << 16));
-    }
+    if (int rc = h.wait_last()) return rc;         // (the tables, the counters and the pinned copies are replaced here)
+    // the caller's order (a bk_hap_region is the uint2 {cell0, len}); the same sorted by first cell, each with its index in the caller's order
+    const std::vector<uint32_t> order = by_first_cell(regions, n_regions);
+    std::vector<uint2> sorted(n_regions);
+    for (uint32_t i = 0; i < n_regions; i++) sorted[i] = make_uint2(regions[order[i]].cell0, regions[order[i]].len | (order[i] << 16));
     const size_t slots = (size_t)1 << table_log2;
     h.n_regions = n_regions; h.table_log2 = table_log2;
-    BK_HIP(grow(h.sorted, n_regions)); BK_HIP(grow(h.regions, n_regions)); BK_HIP(grow(h.hot, (size_t)n_regions * 2));
+    bk_engine::Span sp(e, 1);
+    if (int rc = upload(h.h_sorted, h.sorted, sorted.data(), n_regions, e->stream)) return rc;
+    if (int rc = upload(h.h_regions, h.regions, reinterpret_cast<const uint2*>(regions), n_regions, e->stream)) return rc;
+    BK_HIP(grow(h.hot, (size_t)n_regions * 2));
     if (h.owner.n < slots) { BK_HIP(h.owner.alloc(slots)); BK_HIP(h.count.alloc(slots)); BK_HIP(h.entries.alloc(slots)); }
     if (!h.tallies.p) BK_HIP(h.tallies.alloc(2));
-    bk_engine::Span sp(e, 1);
     BK_HIP(hipMemsetAsync(h.tallies.p, 0, 2 * sizeof(unsigned long long), e->stream));
     if (n_regions) {
-        BK_HIP(hipMemcpyAsync(h.sorted.p, h.h_sorted.p, n_regions * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
-        BK_HIP(hipMemcpyAsync(h.regions.p, h.h_regions.p, n_regions * sizeof(uint2), hipMemcpyHostToDevice, e->stream));
         BK_HIP(hipMemsetAsync(h.hot.p, 0, (size_t)n_regions * 2 * sizeof(unsigned int), e->stream));
         BK_HIP(hipMemsetAsync(h.owner.p, 0, slots * sizeof(unsigned long long), e->stream));
         BK_HIP(hipMemsetAsync(h.count.p, 0, slots * sizeof(unsigned int), e->stream));
@@ -607,21 +617,15 @@ int bk_sample_haplotypes(bk_engine* e, const bk_hap_region* regions, uint32_t n_
     const bk::HapArgs a = hap_args(e);
     bk::launch_hap_count(a, d.rows_upper, ix.n_cus, e->stream);
     bk::launch_hap_finish(a, e->stream);
-    BK_HIP(hipGetLastError());
-    BK_HIP(h.counted.create());
-    BK_HIP(hipEventRecord(h.counted, e->stream));
-    h.count_in_flight = true;
-    h.made = true;
-    return BK_OK;
+    return h.record(e->stream);
 }
 
 // by region, then by list as a sequence of (offset, base), a proper prefix first
 static bool hap_entry_less(const bk_hap_entry& x, const bk_hap_entry& y) {
     if (x.region != y.region) return x.region < y.region;
     for (uint32_t i = 0; i < std::min<uint32_t>(x.n_mm, y.n_mm); i++) {
-        const uint32_t ox = x.mm[3 * i] | (x.mm[3 * i + 1] << 8), oy = y.mm[3 * i] | (y.mm[3 * i + 1] << 8);
-        if (ox != oy) return ox < oy;
-        if (x.mm[3 * i + 2] != y.mm[3 * i + 2]) return x.mm[3 * i + 2] < y.mm[3 * i + 2];
+        if (bk::mm_offset(x.mm, i) != bk::mm_offset(y.mm, i)) return bk::mm_offset(x.mm, i) < bk::mm_offset(y.mm, i);
+        if (bk::mm_base(x.mm, i) != bk::mm_base(y.mm, i)) return bk::mm_base(x.mm, i) < bk::mm_base(y.mm, i);
     }
     return x.n_mm < y.n_mm;
 }

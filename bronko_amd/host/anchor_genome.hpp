@@ -7,35 +7,25 @@
 #include <string>
 #include <vector>
 
-#include "index.hpp"
+#include "file_cells.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
 
-// One genome file as the rule sees it: its letters upper-cased, where its sequences start, its anchor k-mers
-struct AnchorGenome {
+// One genome file as the rule sees it: its cells and where its sequences start (FileCells), its anchor k-mers
+struct AnchorGenome : FileCells {
     int k = 0;
-    int64_t cell0 = 0;                               // first cell of the file among all cells of the index
-    std::string text;                                // the file's cells (upper-cased FASTA letters)
-    std::vector<int64_t> first;                      // first cell of each sequence, relative to cell0; one more entry: the end
     struct Anchor { uint64_t kmer; uint32_t cell; bool rc; };
     std::vector<Anchor> anchors;                     // canonical k-mers that start at exactly one cell, sorted
 
-    AnchorGenome(const Index& ix, int file) : k(ix.k) {
-        if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("no such genome file");
-        for (int f = 0; f < file; f++) cell0 += (int64_t)ix.genome_len((size_t)f);
+    AnchorGenome(const Index& ix, int file) : FileCells(ix, file), k(ix.k) {
         std::vector<Anchor> all;
-        for (const SeqMeta& s : ix.files[(size_t)file].sequences) {
-            const int64_t c0 = (int64_t)text.size();
-            first.push_back(c0);
-            for (uint8_t c : s.seq) text.push_back((char)(c >= 'a' && c <= 'z' ? c - 32 : c));
-            // the genome's k-mers as the index reads them: every letter that is not ACGT stands for A (nt_to_bits)
-            for (uint64_t i = 0; i + (uint64_t)k <= s.seq.size(); i++) {
-                const Canon cn = canonical_kmer(s.seq.data() + i, k);
-                all.push_back(Anchor{cn.kmer, (uint32_t)(c0 + (int64_t)i), cn.rc});
+        const std::vector<SeqMeta>& seqs = ix.files[(size_t)file].sequences;
+        for (size_t q = 0; q < seqs.size(); q++)    // the genome's k-mers as the index reads them: every letter that is not ACGT stands for A (nt_to_bits)
+            for (uint64_t i = 0; i + (uint64_t)k <= seqs[q].seq.size(); i++) {
+                const Canon cn = canonical_kmer(seqs[q].seq.data() + i, k);
+                all.push_back(Anchor{cn.kmer, (uint32_t)(first[q] + (int64_t)i), cn.rc});
             }
-        }
-        first.push_back((int64_t)text.size());
         std::sort(all.begin(), all.end(), [](const Anchor& x, const Anchor& y) { return x.kmer < y.kmer; });
         for (size_t i = 0; i < all.size();) {
             size_t j = i + 1;

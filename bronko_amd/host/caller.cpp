@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "fastx.hpp"
+#include "file_cells.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -30,14 +31,6 @@ double thompson_tau(uint64_t n) {
     const double t = (n <= 300) ? kTCrit[n - 3] : NAN;
     const double dn = (double)n;
     return (t * (dn - 1.0)) / (std::sqrt(dn) * std::sqrt(dn - 2.0 + t * t));   // call.rs:926
-}
-
-std::string first_token(const std::string& s) {
-    size_t a = 0;
-    while (a < s.size() && isspace((unsigned char)s[a])) a++;
-    size_t b = a;
-    while (b < s.size() && !isspace((unsigned char)s[b])) b++;
-    return s.substr(a, b - a);
 }
 
 char base_char(unsigned b) { return b < 4 ? "ACGT"[b] : 'N'; }   // lcb.rs:57-65
@@ -259,7 +252,7 @@ void write_consensus_fasta(const std::string& out_path, const std::string& stem,
     if (!f.fp) throw std::runtime_error("Failed to create consensus fasta file " + out_path);
     uint64_t at = 0;
     for (const SeqMeta& sm : ix.files[file_id].sequences) {
-        fprintf(f.fp, ">%s|%s\n", stem.c_str(), first_token(sm.name).c_str());
+        fprintf(f.fp, ">%s|%s\n", stem.c_str(), chrom_of(sm.name).c_str());
         for (uint64_t i = 0; i < sm.len; i += 60) {
             const size_t m = (size_t)std::min<uint64_t>(60, sm.len - i);
             if (fwrite(letters + at + i, 1, m, f.fp) != m || fputc('\n', f.fp) == EOF) throw std::runtime_error("Failed to write consensus fasta file " + out_path);
@@ -310,7 +303,7 @@ std::vector<BedLine> read_bed(const std::string& path) {
 std::vector<Region> resolve_bed(const Index& ix, const std::vector<BedLine>& bed, const std::string& path) {
     std::map<std::string, std::vector<std::pair<int, uint32_t>>> where;   // CHROM token -> (file, sequence) in index order
     for (size_t f = 0; f < ix.files.size(); f++)
-        for (size_t q = 0; q < ix.files[f].sequences.size(); q++) where[first_token(ix.files[f].sequences[q].name)].push_back({(int)f, (uint32_t)q});
+        for (size_t q = 0; q < ix.files[f].sequences.size(); q++) where[chrom_of(ix.files[f].sequences[q].name)].push_back({(int)f, (uint32_t)q});
     std::vector<Region> out;
     for (const BedLine& b : bed) {
         const std::string at = path + ": line " + std::to_string(b.line);
@@ -390,7 +383,7 @@ void write_regions_tsv(const std::string& out_path, const Index& ix, int file_id
         const RegionDepth& o = rows[at++];
         const uint64_t L = (uint64_t)r.end - r.start;
         const unsigned __int128 m = (unsigned __int128)o.sum * 100u / L;   // (100 * sum leaves u64 above 1.8e17)
-        fprintf(f.fp, "%s\t%u\t%u\t%s\t%llu\t%llu.%02u\t%llu\t%llu\t%llu\t%llu\n", first_token(ix.files[(size_t)file_id].sequences[r.seq].name).c_str(), r.start, r.end,
+        fprintf(f.fp, "%s\t%u\t%u\t%s\t%llu\t%llu.%02u\t%llu\t%llu\t%llu\t%llu\n", chrom_of(ix.files[(size_t)file_id].sequences[r.seq].name).c_str(), r.start, r.end,
                 r.name.c_str(), (unsigned long long)L, (unsigned long long)(m / 100u), (unsigned)(m % 100u), (unsigned long long)o.min,
                 (unsigned long long)o.median, (unsigned long long)o.max, (unsigned long long)o.covered);
     }
@@ -465,7 +458,7 @@ void write_vcf(const std::string& out_path, const std::string& reads_path, const
     const FileMeta& fm = ix.files[file_id];
     fprintf(f.fp, "##fileformat=VCFv4.5\n##source=bronko-v0.1.0\n##reference=file://%s\n", reads_path.c_str());
     for (const auto& s : fm.sequences)
-        fprintf(f.fp, "##contig=<ID=%s,length=%llu>\n", first_token(s.name).c_str(), (unsigned long long)s.len);
+        fprintf(f.fp, "##contig=<ID=%s,length=%llu>\n", chrom_of(s.name).c_str(), (unsigned long long)s.len);
     fputs("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Total Depth\">\n"
           "##INFO=<ID=AF,Number=1,Type=Float,Description=\"Allele Frequency\">\n"
           "##INFO=<ID=DP4,Number=4,Type=Integer,Description=\"Fwd_ref,Rev_ref,Fwd_alt,Rev_alt\">\n"
@@ -473,7 +466,7 @@ void write_vcf(const std::string& out_path, const std::string& reads_path, const
           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n", f.fp);
     for (const VcfRecord& v : recs)
         fprintf(f.fp, "%s\t%llu\t.\t%c\t%c\t.\tPASS\tDP=%llu;AF=%s;DP4=%llu,%llu,%llu,%llu;SOR=%s\n",
-                first_token(fm.sequences[v.seq_id].name).c_str(), (unsigned long long)v.pos, base_char(v.ref_base),
+                chrom_of(fm.sequences[v.seq_id].name).c_str(), (unsigned long long)v.pos, base_char(v.ref_base),
                 base_char(v.alt_base), (unsigned long long)v.depth, fixed(v.af, 3).c_str(), (unsigned long long)v.fwd_ref,
                 (unsigned long long)v.rev_ref, (unsigned long long)v.fwd_alt, (unsigned long long)v.rev_alt, fixed(v.sor, 3).c_str());
 }

@@ -1,31 +1,15 @@
 // codons.cpp -- the host twin of bk_codons.hip, the --codons BED reader, the translation and the .codons.tsv writer (codons.hpp).
 #include "codons.hpp"
 
-#include <cctype>
 #include <cstdio>
 #include <stdexcept>
 
+#include "file_cells.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
 
 namespace {
-
-// one genome file's cells: its letters upper-cased, where its sequences start (relative to the file's first cell), one more entry: the end
-struct FileCells {
-    uint64_t cell0 = 0;
-    std::string text;
-    std::vector<uint64_t> first;
-    FileCells(const Index& ix, int file) {
-        if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("no such genome file");
-        for (int f = 0; f < file; f++) cell0 += ix.genome_len((size_t)f);
-        for (const SeqMeta& s : ix.files[(size_t)file].sequences) {
-            first.push_back(text.size());
-            for (uint8_t c : s.seq) text.push_back((char)toupper(c));
-        }
-        first.push_back(text.size());
-    }
-};
 
 void check_regions(const FileCells& g, const std::vector<CodonRegion>& regions) {
     if (regions.size() > kCodonMaxRegions) throw std::runtime_error("codon_count: at most 4096 regions, got " + std::to_string(regions.size()));
@@ -34,21 +18,10 @@ void check_regions(const FileCells& g, const std::vector<CodonRegion>& regions) 
         const CodonRegion& r = regions[i];
         const std::string who = "codon_count: region " + std::to_string(i);
         if (r.n_codons == 0) throw std::runtime_error(who + " has no codon");
-        const uint64_t lo = r.cell0, hi = lo + 3ull * r.n_codons;
-        if (lo < g.cell0 || hi > g.cell0 + g.text.size()) throw std::runtime_error(who + " lies outside the genome file");
-        for (size_t s = 0; s + 1 < g.first.size(); s++)
-            if (lo - g.cell0 >= g.first[s] && lo - g.cell0 < g.first[s + 1] && hi - g.cell0 > g.first[s + 1]) throw std::runtime_error(who + " crosses a sequence border");
+        g.check_region(who, r.cell0, r.cell0 + 3ull * r.n_codons);
         total += r.n_codons;
     }
     if (total > kCodonMaxCodons) throw std::runtime_error("codon_count: " + std::to_string(total) + " codons, at most 262144 are counted");
-}
-
-std::string chrom_of(const std::string& name) {       // the CHROM token as write_vcf prints it
-    size_t a = 0;
-    while (a < name.size() && isspace((unsigned char)name[a])) a++;
-    size_t b = a;
-    while (b < name.size() && !isspace((unsigned char)name[b])) b++;
-    return name.substr(a, b - a);
 }
 
 char complement(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N'; }
@@ -62,11 +35,7 @@ std::vector<uint32_t> codon_count(const Index& ix, int file, const std::vector<L
     for (const CodonRegion& r : regions) total += r.n_codons;
     std::vector<uint32_t> count(total * 64, 0u);
     for (const LinkRow& row : rows) {
-        auto base_at = [&](uint32_t cell) -> uint32_t {
-            for (int t = 0; t < row.n_mm; t++)
-                if ((uint32_t)(row.mm[3 * t] | (row.mm[3 * t + 1] << 8)) == cell - row.cell0) return row.mm[3 * t + 2];
-            return nt_to_bits((uint8_t)g.text[(size_t)(cell - g.cell0)]);
-        };
+        auto base_at = [&](uint32_t cell) { return row_base(row, cell, nt_to_bits((uint8_t)g.text[(size_t)(cell - g.cell0)])); };
         size_t codon = 0;
         for (const CodonRegion& r : regions)
             for (uint32_t i = 0; i < r.n_codons; i++, codon++) {

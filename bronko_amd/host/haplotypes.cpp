@@ -2,31 +2,16 @@
 #include "haplotypes.hpp"
 
 #include <algorithm>
-#include <cctype>
 #include <cstdio>
 #include <map>
 #include <stdexcept>
 #include <utility>
 
+#include "file_cells.hpp"
+
 namespace bronko {
 
 namespace {
-
-// one genome file's cells: its letters upper-cased, where its sequences start (relative to the file's first cell), one more entry: the end
-struct FileCells {
-    uint64_t cell0 = 0;
-    std::string text;
-    std::vector<uint64_t> first;
-    FileCells(const Index& ix, int file) {
-        if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("no such genome file");
-        for (int f = 0; f < file; f++) cell0 += ix.genome_len((size_t)f);
-        for (const SeqMeta& s : ix.files[(size_t)file].sequences) {
-            first.push_back(text.size());
-            for (uint8_t c : s.seq) text.push_back((char)toupper(c));
-        }
-        first.push_back(text.size());
-    }
-};
 
 void check_regions(const FileCells& g, const std::vector<HapRegion>& regions) {
     if (regions.size() > kHapMaxRegions) throw std::runtime_error("hap_count: at most 4096 regions, got " + std::to_string(regions.size()));
@@ -35,26 +20,15 @@ void check_regions(const FileCells& g, const std::vector<HapRegion>& regions) {
         const std::string who = "hap_count: region " + std::to_string(i);
         if (r.len == 0) throw std::runtime_error(who + " has no cell");
         if (r.len > kHapMaxLen) throw std::runtime_error(who + " has " + std::to_string(r.len) + " cells, at most 65520");
-        const uint64_t lo = r.cell0, hi = lo + r.len;
-        if (lo < g.cell0 || hi > g.cell0 + g.text.size()) throw std::runtime_error(who + " lies outside the genome file");
-        for (size_t s = 0; s + 1 < g.first.size(); s++)
-            if (lo - g.cell0 >= g.first[s] && lo - g.cell0 < g.first[s + 1] && hi - g.cell0 > g.first[s + 1]) throw std::runtime_error(who + " crosses a sequence border");
+        g.check_region(who, r.cell0, (uint64_t)r.cell0 + r.len);
     }
-}
-
-std::string chrom_of(const std::string& name) {       // the CHROM token as write_vcf prints it
-    size_t a = 0;
-    while (a < name.size() && isspace((unsigned char)name[a])) a++;
-    size_t b = a;
-    while (b < name.size() && !isspace((unsigned char)name[b])) b++;
-    return name.substr(a, b - a);
 }
 
 typedef std::vector<std::pair<uint32_t, uint8_t>> HapList;   // (offset, base): vectors compare as the order asks, a proper prefix first
 
 HapList list_of(const HapEntry& e) {
     HapList l;
-    for (int t = 0; t < e.n_mm; t++) l.emplace_back((uint32_t)(e.mm[3 * t] | (e.mm[3 * t + 1] << 8)), e.mm[3 * t + 2]);
+    for (int t = 0; t < e.n_mm; t++) l.emplace_back(mm_offset(e.mm, t), (uint8_t)mm_base(e.mm, t));
     return l;
 }
 
@@ -73,8 +47,8 @@ HapTable hap_count(const Index& ix, int file, const std::vector<LinkRow>& rows, 
             t.cover[i]++;
             HapList l;
             for (int s = 0; s < row.n_mm; s++) {
-                const uint64_t cell = (uint64_t)row.cell0 + (uint32_t)(row.mm[3 * s] | (row.mm[3 * s + 1] << 8));
-                if (cell >= c0 && cell < c1) l.emplace_back((uint32_t)(cell - c0), row.mm[3 * s + 2]);
+                const uint64_t cell = (uint64_t)row.cell0 + mm_offset(row.mm, s);
+                if (cell >= c0 && cell < c1) l.emplace_back((uint32_t)(cell - c0), (uint8_t)mm_base(row.mm, s));
             }
             if (l.empty()) t.ref_count[i]++; else seen[l]++;
         }

@@ -17,7 +17,47 @@
 
 namespace {
 thread_local std::string g_err;
+
+// reads joined by '\n'
+std::vector<std::string> split_lines(const char* reads) {
+    std::vector<std::string> rd;
+    for (const char* at = reads; at && *at;) {
+        const char* nl = strchr(at, '\n');
+        rd.emplace_back(nl ? std::string(at, nl) : std::string(at));
+        at = nl ? nl + 1 : nullptr;
+    }
+    return rd;
 }
+// tables of named things (--codons' genes, --haplotypes' windows) cross this boundary as n rows of W u32 and their names joined by '\n'
+// in: get(item, row) reads a row; a missing name is "."
+template <int W, class T, class F>
+std::vector<T> named_rows_in(const uint32_t* rows, const char* names, uint64_t n, F get) {
+    std::vector<T> out((size_t)n);
+    const char* at = names;
+    for (uint64_t i = 0; i < n; i++) {
+        get(out[i], rows + i * W);
+        out[i].name = ".";
+        if (at) {
+            const char* nl = strchr(at, '\n');
+            out[i].name = nl ? std::string(at, nl) : std::string(at);
+            at = nl ? nl + 1 : nullptr;
+        }
+    }
+    return out;
+}
+// out: put(item, row) writes a row; *n items, *names_len bytes of joined names, both written only where they fit cap / names_cap
+template <int W, class T, class F>
+int named_rows_out(const std::vector<T>& r, F put, uint64_t cap, uint32_t* rows, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
+    std::string joined;
+    for (size_t i = 0; i < r.size(); i++) joined += (i ? "\n" : "") + r[i].name;
+    *n = r.size();
+    if (names_len) *names_len = joined.size() + 1;
+    if (rows && r.size() <= cap)
+        for (size_t i = 0; i < r.size(); i++) put(r[i], rows + i * W);
+    if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
+    return 0;
+}
+}  // namespace
 
 extern "C" {
 
@@ -229,14 +269,8 @@ int bh_indel_events(const void* h, int file_id, const char* reads, int max_len, 
                     uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::IndelEvent) == 32, "IndelEvent is bk_indel_record");
-        std::vector<std::string> rd;
-        for (const char* at = reads; at && *at;) {
-            const char* nl = strchr(at, '\n');
-            rd.emplace_back(nl ? std::string(at, nl) : std::string(at));
-            at = nl ? nl + 1 : nullptr;
-        }
         const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::IndelResult r = bronko::indel_events(*ix, file_id, rd, max_len, max_mismatches);
+        const bronko::IndelResult r = bronko::indel_events(*ix, file_id, split_lines(reads), max_len, max_mismatches);
         *n = r.events.size();
         if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::IndelEvent));
         if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
@@ -258,15 +292,6 @@ int bh_write_indels_vcf(const void* h, int file_id, const char* path, const char
 }
 
 // ---- --linkage: the host twin of the engine's linkage passes (linkage.cpp) ---------------------------------------------
-static std::vector<std::string> split_lines(const char* reads) {
-    std::vector<std::string> rd;
-    for (const char* at = reads; at && *at;) {
-        const char* nl = strchr(at, '\n');
-        rd.emplace_back(nl ? std::string(at, nl) : std::string(at));
-        at = nl ? nl + 1 : nullptr;
-    }
-    return rd;
-}
 // reads joined by '\n'; rows as bk_link_row (= bronko::LinkRow), at most cap written, *n their number; counters = {records, placed,
 // unplaced, discordant}
 int bh_link_rows(const void* h, int file_id, const char* reads, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint64_t* counters) {
@@ -324,36 +349,17 @@ int bh_codon_count(const void* h, int file_id, const void* rows, uint64_t n_rows
 // genes travel as [n][5] u32 (cell0, n_codons, seq, start, 1 for the '-' strand), their names joined by '\n'
 namespace {
 std::vector<bronko::CodonGene> genes_of(const uint32_t* genes, const char* names, uint64_t n) {
-    std::vector<bronko::CodonGene> out((size_t)n);
-    const char* at = names;
-    for (uint64_t i = 0; i < n; i++) {
-        out[i].reg.cell0 = genes[i * 5]; out[i].reg.n_codons = genes[i * 5 + 1]; out[i].seq = genes[i * 5 + 2]; out[i].start = genes[i * 5 + 3];
-        out[i].strand = genes[i * 5 + 4] ? '-' : '+';
-        out[i].name = ".";
-        if (at) {
-            const char* nl = strchr(at, '\n');
-            out[i].name = nl ? std::string(at, nl) : std::string(at);
-            at = nl ? nl + 1 : nullptr;
-        }
-    }
-    return out;
+    return named_rows_in<5, bronko::CodonGene>(genes, names, n, [](bronko::CodonGene& g, const uint32_t* w) {
+        g.reg.cell0 = w[0]; g.reg.n_codons = w[1]; g.seq = w[2]; g.start = w[3]; g.strand = w[4] ? '-' : '+';
+    });
 }
 }  // namespace
 // read_codon_bed + resolve_codon_bed; *n genes, *names_len bytes of joined names, both written only where they fit cap / names_cap
 int bh_codon_bed(const void* h, int file_id, const char* path, uint64_t cap, uint32_t* genes, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
     try {
-        const std::vector<bronko::CodonGene> r = bronko::resolve_codon_bed(*static_cast<const bronko::Index*>(h), file_id, bronko::read_codon_bed(path), path);
-        std::string joined;
-        for (size_t i = 0; i < r.size(); i++) joined += (i ? "\n" : "") + r[i].name;
-        *n = r.size();
-        if (names_len) *names_len = joined.size() + 1;
-        if (genes && r.size() <= cap)
-            for (size_t i = 0; i < r.size(); i++) {
-                genes[i * 5] = r[i].reg.cell0; genes[i * 5 + 1] = r[i].reg.n_codons; genes[i * 5 + 2] = r[i].seq; genes[i * 5 + 3] = r[i].start;
-                genes[i * 5 + 4] = r[i].strand == '-' ? 1u : 0u;
-            }
-        if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
-        return 0;
+        return named_rows_out<5>(bronko::resolve_codon_bed(*static_cast<const bronko::Index*>(h), file_id, bronko::read_codon_bed(path), path),
+                                 [](const bronko::CodonGene& g, uint32_t* w) { w[0] = g.reg.cell0; w[1] = g.reg.n_codons; w[2] = g.seq; w[3] = g.start; w[4] = g.strand == '-' ? 1u : 0u; },
+                                 cap, genes, names, names_cap, n, names_len);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 int bh_write_codons_tsv(const void* h, int file_id, const char* path, const uint32_t* genes, const char* names, uint64_t n, const uint32_t* counts, uint64_t n_codons,
@@ -388,28 +394,11 @@ int bh_hap_count(const void* h, int file_id, const void* rows, uint64_t n_rows, 
 // windows travel as [n][4] u32 (cell0, len, seq, start), their names joined by '\n'
 namespace {
 std::vector<bronko::HapWindow> windows_of(const uint32_t* wins, const char* names, uint64_t n) {
-    std::vector<bronko::HapWindow> out((size_t)n);
-    const char* at = names;
-    for (uint64_t i = 0; i < n; i++) {
-        out[i].reg.cell0 = wins[i * 4]; out[i].reg.len = wins[i * 4 + 1]; out[i].seq = wins[i * 4 + 2]; out[i].start = wins[i * 4 + 3];
-        out[i].name = ".";
-        if (at) {
-            const char* nl = strchr(at, '\n');
-            out[i].name = nl ? std::string(at, nl) : std::string(at);
-            at = nl ? nl + 1 : nullptr;
-        }
-    }
-    return out;
+    return named_rows_in<4, bronko::HapWindow>(wins, names, n, [](bronko::HapWindow& x, const uint32_t* w) { x.reg.cell0 = w[0]; x.reg.len = w[1]; x.seq = w[2]; x.start = w[3]; });
 }
 int windows_out(const std::vector<bronko::HapWindow>& r, uint64_t cap, uint32_t* wins, char* names, uint64_t names_cap, uint64_t* n, uint64_t* names_len) {
-    std::string joined;
-    for (size_t i = 0; i < r.size(); i++) joined += (i ? "\n" : "") + r[i].name;
-    *n = r.size();
-    if (names_len) *names_len = joined.size() + 1;
-    if (wins && r.size() <= cap)
-        for (size_t i = 0; i < r.size(); i++) { wins[i * 4] = r[i].reg.cell0; wins[i * 4 + 1] = r[i].reg.len; wins[i * 4 + 2] = r[i].seq; wins[i * 4 + 3] = r[i].start; }
-    if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
-    return 0;
+    return named_rows_out<4>(r, [](const bronko::HapWindow& x, uint32_t* w) { w[0] = x.reg.cell0; w[1] = x.reg.len; w[2] = x.seq; w[3] = x.start; }, cap, wins, names, names_cap,
+                             n, names_len);
 }
 }  // namespace
 // read_hap_bed + resolve_hap_bed (path) or hap_windows (path null); *n windows, *names_len bytes of joined names, both written only where they fit

@@ -2,7 +2,6 @@
 #include "indels.hpp"
 
 #include <algorithm>
-#include <cctype>
 #include <cstdio>
 #include <map>
 #include <stdexcept>
@@ -147,15 +146,8 @@ void write_indels_vcf(const std::string& out_path, const std::string& reads_path
     if (!fp) throw std::runtime_error("Failed to create indel vcf output file " + out_path);
     struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
     const FileMeta& fm = ix.files[(size_t)file];
-    auto chrom = [](const std::string& name) {       // the CHROM token as write_vcf prints it
-        size_t a = 0;
-        while (a < name.size() && isspace((unsigned char)name[a])) a++;
-        size_t b = a;
-        while (b < name.size() && !isspace((unsigned char)name[b])) b++;
-        return name.substr(a, b - a);
-    };
     fprintf(fp, "##fileformat=VCFv4.5\n##source=bronko-v0.1.0\n##reference=file://%s\n", reads_path.c_str());
-    for (const auto& s : fm.sequences) fprintf(fp, "##contig=<ID=%s,length=%llu>\n", chrom(s.name).c_str(), (unsigned long long)s.len);
+    for (const auto& s : fm.sequences) fprintf(fp, "##contig=<ID=%s,length=%llu>\n", chrom_of(s.name).c_str(), (unsigned long long)s.len);
     fputs("##INFO=<ID=TYPE,Number=1,Type=String,Description=\"DEL or INS\">\n"
           "##INFO=<ID=LEN,Number=1,Type=Integer,Description=\"Bases deleted or inserted\">\n"
           "##INFO=<ID=SF,Number=1,Type=Integer,Description=\"Supporting records along the reference\">\n"
@@ -180,7 +172,7 @@ void write_indels_vcf(const std::string& out_path, const std::string& reads_path
         if (e.len > 0) for (uint64_t j = 0; j < len; j++) ref_a.push_back(up(sm->seq[i + j]));
         else for (uint64_t j = 0; j < len; j++) alt_a.push_back("ACGT"[(e.seq >> (2 * j)) & 3u]);
         const uint64_t support = (uint64_t)e.fwd + e.rev, t = 10000ull * support / std::max<uint64_t>(1, support + e.ref_span);
-        fprintf(fp, "%s\t%llu\t.\t%s\t%s\t.\tPASS\tTYPE=%s;LEN=%llu;SF=%u;SR=%u;RS=%u;AF=%llu.%04llu\n", chrom(sm->name).c_str(), (unsigned long long)i,
+        fprintf(fp, "%s\t%llu\t.\t%s\t%s\t.\tPASS\tTYPE=%s;LEN=%llu;SF=%u;SR=%u;RS=%u;AF=%llu.%04llu\n", chrom_of(sm->name).c_str(), (unsigned long long)i,
                 ref_a.c_str(), alt_a.c_str(), e.len > 0 ? "DEL" : "INS", (unsigned long long)len, e.fwd, e.rev, e.ref_span,
                 (unsigned long long)(t / 10000), (unsigned long long)(t % 10000));
     }

@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "fastx.hpp"
+#include "file_cells.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -47,14 +48,6 @@ std::string path_file_stem(const std::string& path) {   // Path::file_stem (buil
     const size_t dot = base.find_last_of('.');
     if (dot != std::string::npos && dot != 0) base.resize(dot);
     return base;
-}
-
-std::string first_token(const std::string& h) {          // split_whitespace().next() (build.rs:178-182)
-    size_t a = 0;
-    while (a < h.size() && isspace((unsigned char)h[a])) a++;
-    size_t b = a;
-    while (b < h.size() && !isspace((unsigned char)h[b])) b++;
-    return h.substr(a, b - a);
 }
 
 struct Pair { uint64_t id; BucketInfo e; };
@@ -133,7 +126,7 @@ std::vector<FileMeta> read_genomes(const std::vector<std::string>& genomes) {
         files[f].name = path_file_stem(genomes[f]);
         for (auto& r : recs) {
             SeqMeta sm;
-            sm.name = first_token(r.header);
+            sm.name = chrom_of(r.header);                  // split_whitespace().next() (build.rs:178-182)
             sm.len = r.seq.size();
             sm.seq = std::move(r.seq);
             files[f].sequences.push_back(std::move(sm));

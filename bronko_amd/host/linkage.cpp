@@ -2,7 +2,6 @@
 #include "linkage.hpp"
 
 #include <algorithm>
-#include <cctype>
 #include <cstdio>
 #include <map>
 #include <stdexcept>
@@ -52,14 +51,6 @@ void place_record(const AnchorGenome& g, const std::string& rec, int M, LinkResu
     out.rows.push_back(row);
 }
 
-std::string chrom_of(const std::string& name) {       // the CHROM token as write_vcf prints it
-    size_t a = 0;
-    while (a < name.size() && isspace((unsigned char)name[a])) a++;
-    size_t b = a;
-    while (b < name.size() && !isspace((unsigned char)name[b])) b++;
-    return name.substr(a, b - a);
-}
-
 }  // namespace
 
 LinkResult link_rows(const Index& ix, int file, const std::vector<std::string>& reads, int max_mismatches) {
@@ -99,11 +90,7 @@ std::vector<LinkPair> link_count(const Index& ix, int file, const std::vector<Li
         }
     }
     for (const LinkRow& row : rows) {
-        auto base_at = [&](uint32_t cell) -> uint32_t {
-            for (int t = 0; t < row.n_mm; t++)
-                if ((uint32_t)(row.mm[3 * t] | (row.mm[3 * t + 1] << 8)) == cell - row.cell0) return row.mm[3 * t + 2];
-            return nt_to_bits((uint8_t)g.text[(size_t)((int64_t)cell - g.cell0)]);
-        };
+        auto base_at = [&](uint32_t cell) { return row_base(row, cell, nt_to_bits((uint8_t)g.text[(size_t)((int64_t)cell - g.cell0)])); };
         const size_t s0 = (size_t)(std::lower_bound(sites.begin(), sites.end(), row.cell0) - sites.begin());
         const uint32_t end = row.cell0 + row.n;
         for (size_t i = s0; i < sites.size() && sites[i] < end; i++)

@@ -22,6 +22,15 @@ struct LinkRow {
     uint8_t strand = 0, n_mm = 0;
     uint8_t mm[24] = {};
 };
+// mismatch t of a row's mm (or of a HapEntry's, whose offsets are from its region's first cell)
+inline uint32_t mm_offset(const uint8_t* mm, int t) { return (uint32_t)mm[3 * t] | ((uint32_t)mm[3 * t + 1] << 8); }
+inline uint32_t mm_base(const uint8_t* mm, int t) { return mm[3 * t + 2]; }
+// the row's base at `cell`: one of its mismatches, else `ref_base` (the reference's there)
+inline uint32_t row_base(const LinkRow& row, uint32_t cell, uint32_t ref_base) {
+    for (int t = 0; t < row.n_mm; t++)
+        if (mm_offset(row.mm, t) == cell - row.cell0) return mm_base(row.mm, t);
+    return ref_base;
+}
 // bk_link_pair: count[4 bA + bB]
 struct LinkPair {
     uint32_t site_a = 0, site_b = 0;

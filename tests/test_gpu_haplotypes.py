@@ -196,6 +196,32 @@ def test_linkage_codons_and_haplotypes_on_one_sample(world, order):
         eng.sample_haplotypes(p.regs_a, 10)                                            # ... and again: the others' counters stay
 
 
+def test_eight_mismatches_on_both_strands_through_every_reader_of_the_store(world):
+    """A row's codec at its limits: a record along and one against the reference, each with all eight mismatch slots in use (the second
+    found from its last cell down, each put in front), the first and the last of them on the first and last cell of a region.  The rows
+    are downloaded, then linkage, codons and haplotypes are counted on that one sample: everything equal to the restatements."""
+    p, eng = world.p, world.eng
+    start, offs = haplotype_cases.HOT_START, [40 + 9 * t for t in range(8)]
+    fwd = indel_cases.mut_read(p.g.text, start, 150, subs=tuple(offs))
+    reads = [fwd, indels_ref.revcomp(indel_cases.mut_read(p.g.text, start + 3, 150, subs=tuple(o - 3 for o in offs[:4]) + tuple(o - 1 for o in offs[4:])))]
+    rows, t = linkage_ref.link_rows(p.g, reads, 8)
+    assert t["placed"] == 2 and sorted(r[2] for r in rows) == [0, 1] and all(len(r[3]) == 8 for r in rows), (t, rows)
+    first, last = start + offs[0], start + offs[-1] + 2                                # the first mismatch of both rows, the last of the second
+    assert all(r[0] + r[3][0][0] == first for r in rows) and max(r[0] + r[3][-1][0] for r in rows) == last
+    _sample(eng, reads)
+    assert eng.download_link_rows() == rows
+    sites = sorted({r[0] + o for r in rows for o, _ in r[3]} | {first - 1, last + 1})
+    eng.sample_linkage(sites, 1000)
+    summ, pairs = eng.download_linkage()
+    assert pairs == linkage_ref.link_count(p.g, rows, sites, 1000) and (summ.placed, summ.discordant) == (2, 0)
+    regs = [(first - f, (last - first + f) // 3 + 1) for f in range(3)]               # the three frames: each holds the first and the last mismatch
+    eng.sample_codons(regs)
+    assert np.array_equal(eng.download_codons()[1], codons_ref.codon_count(p.g, rows, regs))
+    hregs = [(first, last + 1 - first), (first + 1, last - 1 - first), (first, offs[-1] - offs[0] + 1), (start, 150)]
+    cover, ref, entries = _check(eng, 2, hregs, haplotypes_ref.hap_count(p.g, rows, hregs), what="eight on both strands")
+    assert list(cover) == [2, 2, 2, 1] and list(ref) == [0, 0, 0, 0] and sorted(len(h) for r, _, h in entries if r == 0) == [8, 8]
+
+
 def test_an_engine_its_fork_and_a_store_that_grew(world):
     p = world.p
     fork = world.eng.fork()
