@@ -487,14 +487,15 @@ class Engine:
         _check(self._L.bk_sample_download_linkage(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, [(int(r[0]), int(r[1]), [int(v) for v in r[2:]]) for r in buf[:min(cap, int(summ.n_pairs))]]
 
-    def download_link_rows(self, cap=None):
-        """bk_sample_download_link_rows: the finalized sample's row store as [(cell0, n, strand, ((offset, base), ...))], sorted."""
+    def download_link_rows(self, cap=None, raw=False):
+        """bk_sample_download_link_rows: the finalized sample's row store as [(cell0, n, strand, ((offset, base), ...))], sorted.
+        raw=True: the rows as they lie in the store, an (n, 32) uint8 array of bk_link_row, not decoded and not sorted."""
         summ = _ffi.LinkSummary()
         _check(self._L.bk_sample_download_linkage(self.h, C.byref(summ), None, 0), self._L)   # (how many rows the store holds)
         cap = int(summ.placed) if cap is None else min(int(cap), int(summ.placed))
         buf = np.zeros((max(1, cap), 32), np.uint8)
         _check(self._L.bk_sample_download_link_rows(self.h, buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        return link_rows(buf[:cap])
+        return buf[:cap] if raw else link_rows(buf[:cap])
 
     def sample_codons(self, regions):
         """bk_sample_codons: for every codon of the regions [(cell0, n_codons), ...] (forward-strand cells, any order) the rows of the
