@@ -83,6 +83,14 @@ class HapSummary(C.Structure):  # bk_hap_summary
     _fields_ = [("rows", C.c_uint64), ("entries", C.c_uint64), ("dropped", C.c_uint64), ("n_regions", C.c_uint32), ("table_log2", C.c_uint32)]
 
 
+class ReadPileupCell(C.Structure):  # bk_read_pileup_cell
+    _fields_ = [("fwd", C.c_uint32 * 4), ("rev", C.c_uint32 * 4), ("near", C.c_uint32 * 4)]
+
+
+class ReadPileupSummary(C.Structure):  # bk_read_pileup_summary
+    _fields_ = [("rows", C.c_uint64), ("n_cells", C.c_uint64), ("end_dist", C.c_uint32), ("pad", C.c_uint32), ("covered", C.c_uint64), ("bases", C.c_uint64)]
+
+
 class LinkConfig(C.Structure):  # bk_link_config
     _fields_ = [("max_mismatches", C.c_uint32), ("initial_rows", C.c_uint64)]
 
@@ -116,6 +124,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
+           "bk_sample_read_pileup", "bk_sample_download_read_pileup",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -267,6 +276,10 @@ def load(testing=None):
     L.bk_sample_haplotypes.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.bk_sample_download_haplotypes.restype = C.c_int
     L.bk_sample_download_haplotypes.argtypes = [vp, C.POINTER(HapSummary), vp, vp, vp, u64]
+    L.bk_sample_read_pileup.restype = C.c_int
+    L.bk_sample_read_pileup.argtypes = [vp, C.c_uint32]
+    L.bk_sample_download_read_pileup.restype = C.c_int
+    L.bk_sample_download_read_pileup.argtypes = [vp, C.POINTER(ReadPileupSummary), vp, u64]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

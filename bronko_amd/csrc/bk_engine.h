@@ -2,7 +2,7 @@
 // index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
 // packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
-// ride behind every scan: the k-mer dump, indels, linkage and the codon and haplotype counts over linkage's rows) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
+// ride behind every scan: the k-mer dump, indels, linkage and the codon, haplotype and read-pileup counts over linkage's rows) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -250,8 +250,8 @@ struct AnchorTables {
     DevBuf<uint2> nruns;                    // IndexTables::h_nonacgt
 };
 
-// One count over the sample's row store at a time -- what bk_sample_linkage (Linkage), bk_sample_codons (Codons) and
-// bk_sample_haplotypes (Haplotypes) keep alike.  A call replaces the tables, counters and pinned copies that the last call's kernels may
+// One count over the sample's row store at a time -- what bk_sample_linkage (Linkage), bk_sample_codons (Codons),
+// bk_sample_haplotypes (Haplotypes) and bk_sample_read_pileup (ReadPileup) keep alike.  A call replaces the tables, counters and pinned copies that the last call's kernels may
 // still read, so it first waits for them, and for them alone; it ends by recording `counted` behind its own launches.
 struct StoreCount {
     Event counted;                          // behind the last count's launches
@@ -287,6 +287,15 @@ struct Haplotypes : StoreCount {
     uint32_t n_regions = 0, table_log2 = 0;
 };
 
+// bk_sample_read_pileup: the work arrays and the cells of the last call (bk_read_pileup.hip).  Made by the first call for the index's
+// cells, freed with the Linkage whose row store it reads
+struct ReadPileup : StoreCount {
+    DevBuf<unsigned int> work;              // [15 cells + 3] ReadPileupArgs::diff, mm, mm_near in this order: zeroed by one memset
+    DevBuf<bk_read_pileup_cell> cells;      // [cells]
+    DevBuf<unsigned long long> tallies;     // [2] covered, bases
+    uint32_t end_dist = 0;
+};
+
 // bk_link_enable: the sample's row store (one bk_link_row per placed record), its tallies, and what the last bk_sample_linkage made
 // (the StoreCount it is itself)
 struct Linkage : StoreCount {
@@ -304,6 +313,7 @@ struct Linkage : StoreCount {
     bool in_sample = false;                 // enabled when the current / last sample began
     std::unique_ptr<Codons> codons;         // bk_sample_codons (null: never called, no buffers)
     std::unique_ptr<Haplotypes> haps;       // bk_sample_haplotypes (likewise)
+    std::unique_ptr<ReadPileup> read_pileup;   // bk_sample_read_pileup (likewise)
     ~Linkage() { for (auto& o : old) (void)hipFree(o.first); }
     int begin_sample(bk_engine* e);         // (bk_riders.cpp)
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records, and behind the indels' pass

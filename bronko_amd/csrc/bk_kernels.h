@@ -543,6 +543,22 @@ struct HapArgs {
 };
 void launch_hap_count(const HapArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
 void launch_hap_finish(const HapArgs& a, hipStream_t stream);
+// bk_sample_read_pileup: per cell, the rows of bk_link_enable's store that cover it by the base they carry there, by strand and near
+// their ends (bk_read_pileup.hip; the rule: include/bronko_hip.h)
+typedef bk_read_pileup_cell ReadPileupCellDev;
+struct ReadPileupArgs {
+    const uint32_t* ref_words;           // AnchorIndex's
+    uint32_t total_cells;
+    uint32_t end_dist;                   // E: 0..255
+    RowStoreView store;                  // the sample's row store: LinkArgs'
+    unsigned int* diff;                  // [3][total_cells + 1] difference arrays: cover of strand 0, of strand 1, near-end cover
+    unsigned int* mm;                    // [total_cells][4][2] substitutions by cell, base, strand
+    unsigned int* mm_near;               // [total_cells][4] ... of them the ones near an end of their row
+    ReadPileupCellDev* cells;            // [total_cells] the result
+    unsigned long long* tallies;         // [2] covered, bases (read_pileup_finish_kernel writes both)
+};
+void launch_read_pileup_count(const ReadPileupArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
+void launch_read_pileup_finish(const ReadPileupArgs& a, hipStream_t stream);
 size_t finalize_lds_bytes(int n_files);
 size_t finalize_partial_rows();
 void launch_prefix_rows(unsigned long long* counters, const IndexView& ix, const unsigned int* v_list, const unsigned int* n_list, unsigned int* row_bits, hipStream_t stream);   // bk_gather.hip

@@ -1,8 +1,9 @@
 // bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
 // short insertions and deletions (bk_indels.hip) and linkage (bk_linkage.hip), with the anchor tables the last two share, and the codon
-// and haplotype counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip).  The three counts over the
-// store (bk_sample_linkage, bk_sample_codons, bk_sample_haplotypes) share one lifecycle, StoreCount of bk_engine.h, and the helpers in
-// front of them here: what they ask of the engine's state, of a region's cells, and how their tables reach the device.
+// haplotype and read-pileup counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip,
+// bk_read_pileup.hip).  The four counts over the store (bk_sample_linkage, bk_sample_codons, bk_sample_haplotypes, bk_sample_read_pileup)
+// share one lifecycle, StoreCount of bk_engine.h, and the helpers in front of them here: what they ask of the engine's state, of a
+// region's cells, and how their tables reach the device.
 // Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
 // push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
 // indels, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
@@ -292,13 +293,13 @@ int Linkage::begin_sample(bk_engine* e) {
     if (int rc = link_free_old(*this, true)) return rc;
     BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
     rows_upper = 0; in_sample = true; n_sites = 0; n_pairs = 0;
-    for (StoreCount* c : {(StoreCount*)this, (StoreCount*)codons.get(), (StoreCount*)haps.get()}) if (c) c->made = false;
+    for (StoreCount* c : {(StoreCount*)this, (StoreCount*)codons.get(), (StoreCount*)haps.get(), (StoreCount*)read_pileup.get()}) if (c) c->made = false;
     return BK_OK;
 }
 // the sample's row store as the kernels take it (bk_link_row.h)
 static bk::RowStoreView store_view(const Linkage& d) { return bk::RowStoreView{d.rows.p, d.rows.n / 2, d.tallies.p + 1}; }
 
-// ---- a count over the row store: what bk_sample_linkage, bk_sample_codons and bk_sample_haplotypes share ---------------------------
+// ---- a count over the row store: what bk_sample_linkage, bk_sample_codons, bk_sample_haplotypes and bk_sample_read_pileup share ----
 int StoreCount::wait_last() {
     if (count_in_flight) { BK_HIP(hipEventSynchronize(counted)); count_in_flight = false; }
     made = false;
@@ -311,7 +312,7 @@ int StoreCount::record(hipStream_t stream) {
     count_in_flight = made = true;
     return BK_OK;
 }
-// what each of the three asks before it looks at its items (sites or regions)
+// what each of them asks before it looks at its items (sites or regions; the read pileup has none)
 static int store_count_ready(const bk_engine* e, const void* items, uint32_t n_items, const char* who) {
     if (!e || (!items && n_items)) return fail(BK_ERR_INVALID, "null argument");
     if (e->in_sample) return fail(BK_ERR_STATE, "%s comes after bk_sample_finalize", who);
@@ -659,5 +660,61 @@ int bk_sample_download_haplotypes(bk_engine* e, bk_hap_summary* summary, uint32_
     BK_HIP(hipMemcpy(all.data(), h->entries.p, all.size() * sizeof(bk_hap_entry), hipMemcpyDeviceToHost));
     std::sort(all.begin(), all.end(), hap_entry_less);
     std::memcpy(entries, all.data(), (size_t)std::min<uint64_t>(cap, have) * sizeof(bk_hap_entry));
+    return BK_OK;
+}
+
+// ---- the bases the placed records carry at every cell, by strand and near their ends (bk_read_pileup.hip) --------------------------
+static bk::ReadPileupArgs read_pileup_args(const bk_engine* e) {
+    const Linkage& d = *e->linkage;
+    const ReadPileup& p = *d.read_pileup;
+    const size_t n = (size_t)e->ix->total_cells;
+    bk::ReadPileupArgs a{};
+    a.store = store_view(d);
+    a.ref_words = e->ix->ref_words.p + bk::scan_ref_pad_words(); a.total_cells = (uint32_t)n;   // (anchor_index's)
+    a.end_dist = p.end_dist;
+    a.mm = p.work.p; a.mm_near = p.work.p + 8 * n; a.diff = p.work.p + 12 * n;   // (the two that are read 16 bytes at a time come first)
+    a.cells = p.cells.p; a.tallies = p.tallies.p;
+    return a;
+}
+
+int bk_sample_read_pileup(bk_engine* e, uint32_t end_dist) {
+    static_assert(sizeof(bk_read_pileup_cell) == 3 * sizeof(uint4), "read_pileup_finish_kernel writes a cell as three 16-byte stores");
+    if (int rc = store_count_ready(e, nullptr, 0, "bk_sample_read_pileup")) return rc;
+    if (end_dist > BK_READ_PILEUP_MAX_END) return fail(BK_ERR_INVALID, "bk_sample_read_pileup: end_dist must be 0..%d, got %u", BK_READ_PILEUP_MAX_END, end_dist);
+    const IndexTables& ix = *e->ix;
+    if (ix.total_cells > BK_READ_PILEUP_MAX_CELLS)
+        return fail(BK_ERR_UNSUPPORTED, "bk_sample_read_pileup: the index has %llu cells, the read pileup is made for at most %u", (unsigned long long)ix.total_cells,
+                    BK_READ_PILEUP_MAX_CELLS);
+    Linkage& d = *e->linkage;
+    if (!d.read_pileup) d.read_pileup.reset(new ReadPileup());
+    ReadPileup& p = *d.read_pileup;
+    BK_HIP(hipSetDevice(e->device));
+    if (int rc = p.wait_last()) return rc;         // (the work arrays and the cells are replaced here)
+    const size_t n = (size_t)ix.total_cells, words = 15 * n + 3;
+    if (p.work.n < words) { BK_HIP(p.work.alloc(words)); BK_HIP(p.cells.alloc(std::max<size_t>(n, 1))); BK_HIP(p.tallies.alloc(2)); }
+    p.end_dist = end_dist;
+    bk_engine::Span sp(e, 1);
+    BK_HIP(hipMemsetAsync(p.work.p, 0, words * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(p.tallies.p, 0, 2 * sizeof(unsigned long long), e->stream));
+    const bk::ReadPileupArgs a = read_pileup_args(e);
+    bk::launch_read_pileup_count(a, d.rows_upper, ix.n_cus, e->stream);
+    bk::launch_read_pileup_finish(a, e->stream);
+    return p.record(e->stream);
+}
+
+int bk_sample_download_read_pileup(bk_engine* e, bk_read_pileup_summary* summary, bk_read_pileup_cell* cells, uint64_t cap_cells) {
+    if (!e || !summary || (!cells && cap_cells)) return fail(BK_ERR_INVALID, "null argument");
+    if (int rc = link_finalized(e, "bk_sample_download_read_pileup")) return rc;
+    Linkage& d = *e->linkage;
+    if (!d.read_pileup || !d.read_pileup->made) return fail(BK_ERR_STATE, "bk_sample_download_read_pileup comes after this sample's bk_sample_read_pileup");
+    const ReadPileup& p = *d.read_pileup;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long placed = 0, t[2] = {0, 0};
+    if (int rc = download(e, &placed, d.tallies.p + 1, 1)) return rc;
+    if (int rc = download(e, t, p.tallies.p, 2)) return rc;
+    summary->rows = placed; summary->n_cells = e->ix->total_cells; summary->end_dist = p.end_dist; summary->pad = 0;
+    summary->covered = t[0]; summary->bases = t[1];
+    const uint64_t n = std::min<uint64_t>(e->ix->total_cells, cap_cells);
+    if (n) BK_HIP(hipMemcpy(cells, p.cells.p, (size_t)n * sizeof(bk_read_pileup_cell), hipMemcpyDeviceToHost));
     return BK_OK;
 }

@@ -543,6 +543,22 @@ class Engine:
                 raise
         return summ, cover[:n], ref[:n], hap_entries(buf[:min(cap, int(summ.entries))])
 
+    def sample_read_pileup(self, end_dist=10):
+        """bk_sample_read_pileup: per cell the rows of the finalized sample's store that cover it, by the base they carry there, by
+        strand and near their ends (within end_dist positions of one), counted on the device (asynchronous); needs linkage_enable."""
+        _check(self._L.bk_sample_read_pileup(self.h, int(end_dist)), self._L)
+
+    def download_read_pileup(self, cap=None):
+        """(summary, cells) of sample_read_pileup: cells as an (n, 12) uint32 array -- fwd[ACGT], rev[ACGT], near[ACGT] per cell --,
+        n = min(cap, summary.n_cells), all by default."""
+        summ = _ffi.ReadPileupSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_read_pileup(self.h, C.byref(summ), None, 0), self._L)
+            cap = int(summ.n_cells)
+        buf = np.zeros((max(1, cap), 12), np.uint32)
+        _check(self._L.bk_sample_download_read_pileup(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, buf[:min(cap, int(summ.n_cells))]
+
     def regions_set(self, regions):
         """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
         arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])

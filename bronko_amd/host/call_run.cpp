@@ -215,6 +215,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--haplotypes: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.read_pileup) {      // (likewise)
+        LOG_DEBUG(T, "--read-pileup: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
     if (!shard_mode) shard_devices.clear();
     return shard_devices;
@@ -249,6 +253,8 @@ struct SampleData {
     std::vector<uint32_t> codon_counts;
     bk_hap_summary hsumm{};                               // --haplotypes
     HapTable hap_table;
+    bk_read_pileup_summary psumm{};                       // --read-pileup
+    std::vector<ReadPileupCell> read_cells;
 };
 
 constexpr uint32_t kHapTableLog2 = 16, kHapTableLog2Max = 24;   // --haplotypes: the table's first size (768 KB + 2.5 MB of entries); four times as many slots after each that was full
@@ -322,6 +328,8 @@ struct CallRun {
             for (const HapWindow& w : hap_wins) hap_regs.push_back(bk_hap_region{w.reg.cell0, w.reg.len});
             LOG_DEBUG(T, std::to_string(hap_wins.size()) + " haplotype regions");
         }
+        if (cfg.read_pileup && ix.files.size() != 1)
+            die(T, "--read-pileup needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
     }
     // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
     void resolve_regions() {
@@ -472,7 +480,7 @@ struct CallRun {
             const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
             hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
         }
-        if (cfg.row_store()) {   // (--codons and --haplotypes read --linkage's row store; alone each brings its own M, together they are equal)
+        if (cfg.row_store()) {   // (--codons, --haplotypes and --read-pileup read --linkage's row store; alone each brings its own M, together they are equal)
             const bk_link_config lc{cfg.row_store_mismatches(), kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
         }
@@ -598,6 +606,12 @@ struct CallRun {
             hip_check(bk_sample_download_haplotypes(e, &d.hsumm, nullptr, nullptr, reinterpret_cast<bk_hap_entry*>(d.hap_table.entries.data()), d.hap_table.entries.size()),
                       "bk_sample_download_haplotypes");
         }
+        if (cfg.read_pileup) {   // likewise: 48 bytes a position travel
+            static_assert(sizeof(ReadPileupCell) == sizeof(bk_read_pileup_cell), "ReadPileupCell is bk_read_pileup_cell");
+            hip_check(bk_sample_read_pileup(e, cfg.read_pile.end_dist), "bk_sample_read_pileup");
+            d.read_cells.resize((size_t)ix.genome_len(0));
+            hip_check(bk_sample_download_read_pileup(e, &d.psumm, reinterpret_cast<bk_read_pileup_cell*>(d.read_cells.data()), d.read_cells.size()), "bk_sample_download_read_pileup");
+        }
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
     uint64_t merge_mates(const std::vector<std::string>& mates, SampleData& d) const {
@@ -672,6 +686,11 @@ struct CallRun {
                 LOG_INFO(T, "Haplotypes: " + std::to_string(d.hsumm.rows) + " placed records over " + std::to_string(d.hsumm.n_regions) + " regions, " +
                                 std::to_string(hs.no_cover) + " without cover, " + std::to_string(hs.distinct) + " distinct haplotypes, " + std::to_string(hs.lines) +
                                 " lines written, table of 2^" + std::to_string(d.hsumm.table_log2) + " slots");
+            }
+            if (cfg.read_pileup) {
+                write_read_pileup_tsv(a.output + "/" + stem + ".read_pileup.tsv", ix, best, d.read_cells, cfg.read_pile);
+                LOG_INFO(T, "Read pileup: " + std::to_string(d.psumm.rows) + " placed records, " + std::to_string(d.psumm.covered) + " of " + std::to_string(d.psumm.n_cells) +
+                                " positions covered, " + std::to_string(d.psumm.bases) + " bases, near an end within " + std::to_string(d.psumm.end_dist));
             }
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }

@@ -76,7 +76,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
-          "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
+          "            [--read-pileup-max-mismatches M] [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -124,7 +125,13 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --hap-step S      positions from one window's start to the next; at least 1, default W\n"
           "  --hap-min-reads N        reads that carry a haplotype for it to be written; at least 1, default 5\n"
           "  --hap-min-freq F         count / cover a haplotype needs to be written; 0..1, default the value of --min-af\n"
-          "  --hap-max-mismatches M   substitutions a read may have to be counted; 0..8, default 8 (with --linkage or --codons: equal to their M)\n", stderr);
+          "  --hap-max-mismatches M   substitutions a read may have to be counted; 0..8, default 8 (with --linkage or --codons: equal to their M)\n"
+          "  --read-pileup     write to <DIR>/<stem>.read_pileup.tsv, per position of every sequence (an index of one genome file), how many\n"
+          "                    whole reads carry A, C, G and T there on the forward and on the reverse strand -- the columns of --pileup --\n"
+          "                    and how many of them within E positions of a read's end (near_A .. near_T)\n"
+          "  --read-pileup-end E      positions from a read's end up to which a base counts as near it; 0..255, default 10\n"
+          "  --read-pileup-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8 (with --linkage, --codons or\n"
+          "                    --haplotypes: equal to their M)\n", stderr);
     exit(code);
 }
 
@@ -293,6 +300,16 @@ Args parse_args(int argc, char** argv) {
             else if (opt == "--hap-step") { a.hap_step = x; a.has_hap_step = true; }
             else if (opt == "--hap-min-reads") { a.hap_min_reads = x; a.has_hap_min_reads = true; }
             else { a.hap_max_mismatches = x; a.has_hap_max_mismatches = true; }
+        }
+        else if (opt == "--read-pileup") a.read_pileup = true;
+        else if (opt == "--read-pileup-end" || opt == "--read-pileup-max-mismatches") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--read-pileup-end") { a.read_pileup_end = x; a.has_read_pileup_end = true; }
+            else { a.read_pileup_max_mismatches = x; a.has_read_pileup_max_mismatches = true; }
         }
         else if (opt == "--hap-min-freq") { a.hap_min_freq = to_double(opt, one()); a.has_hap_min_freq = true; }
         else if (opt == "--codon-min-freq") { a.codon_min_freq = to_double(opt, one()); a.has_codon_min_freq = true; }
@@ -530,6 +547,18 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.haps() && a.has_codons && a.hap_max_mismatches != a.codon_max_mismatches)
         die(T, "--codons and --haplotypes count the same placed reads: --codon-max-mismatches (" + std::to_string(a.codon_max_mismatches) + ") and --hap-max-mismatches (" +
                    std::to_string(a.hap_max_mismatches) + ") must be equal");
+    if (a.has_read_pileup_end && !a.read_pileup) die(T, "--read-pileup-end needs --read-pileup");
+    if (a.has_read_pileup_max_mismatches && !a.read_pileup) die(T, "--read-pileup-max-mismatches needs --read-pileup");
+    if (a.read_pileup_end < 0 || a.read_pileup_end > (long)kReadPileupMaxEnd) die(T, "--read-pileup-end must be between 0 and 255, got " + std::to_string(a.read_pileup_end));
+    if (a.read_pileup_max_mismatches < 0 || a.read_pileup_max_mismatches > kLinkMaxMismatches)
+        die(T, "--read-pileup-max-mismatches must be between 0 and 8, got " + std::to_string(a.read_pileup_max_mismatches));
+    struct { bool on; const char* flag; const char* opt; long m; } const others[] = {{a.linkage, "--linkage", "--link-max-mismatches", a.link_max_mismatches},
+                                                                                     {a.has_codons, "--codons", "--codon-max-mismatches", a.codon_max_mismatches},
+                                                                                     {a.haps(), "--haplotypes", "--hap-max-mismatches", a.hap_max_mismatches}};
+    for (const auto& o : others)   // (one row store, one M)
+        if (a.read_pileup && o.on && o.m != a.read_pileup_max_mismatches)
+            die(T, std::string(o.flag) + " and --read-pileup count the same placed reads: " + o.opt + " (" + std::to_string(o.m) + ") and --read-pileup-max-mismatches (" +
+                       std::to_string(a.read_pileup_max_mismatches) + ") must be equal");
 }
 
 // the checked arguments -> what the readers and the per-sample code work from; the primer file and the regions file are read and the adapters are
@@ -585,6 +614,8 @@ CallConfig make_call_config(const Args& a) {
     if (a.has_hap_window) { c.hap_window = (uint64_t)a.hap_window; c.hap_step = (uint64_t)(a.has_hap_step ? a.hap_step : a.hap_window); }
     c.hap.max_mismatches = (uint32_t)a.hap_max_mismatches; c.hap.min_reads = (uint64_t)a.hap_min_reads;
     c.hap.min_freq = a.has_hap_min_freq ? a.hap_min_freq : a.min_af;
+    c.read_pileup = a.read_pileup;
+    c.read_pile.max_mismatches = (uint32_t)a.read_pileup_max_mismatches; c.read_pile.end_dist = (uint32_t)a.read_pileup_end;
     return c;
 }
 

@@ -14,6 +14,7 @@
 #include "indels.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
+#include "read_pileup.hpp"
 
 namespace bronko {
 
@@ -87,6 +88,10 @@ struct Args {
     double hap_min_freq = 0.03;     // --hap-min-freq: count / cover a haplotype needs to be written (default: --min-af)
     long hap_max_mismatches = 8;    // --hap-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with --linkage and --codons)
     bool haps() const { return has_haplotypes || has_hap_window; }
+    bool read_pileup = false;       // --read-pileup: <DIR>/<stem>.read_pileup.tsv, per position the bases the placed reads carry, by strand and near their ends
+    bool has_read_pileup_end = false, has_read_pileup_max_mismatches = false;
+    long read_pileup_end = 10;      // --read-pileup-end: a base within this many positions of a read's end counts as near it (0..255)
+    long read_pileup_max_mismatches = 8;   // --read-pileup-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with the other three)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -140,8 +145,14 @@ struct CallConfig {
     uint64_t hap_window = 0, hap_step = 0;
     HapParams hap;
     bool haps() const { return !haps_path.empty() || hap_window > 0; }
-    bool row_store() const { return linkage || codons() || haps(); }   // bk_link_enable
-    uint32_t row_store_mismatches() const { return linkage ? link.max_mismatches : codons() ? codon.max_mismatches : hap.max_mismatches; }
+    // --read-pileup: bk_sample_read_pileup and the values the .read_pileup.tsv header prints; read_pile.max_mismatches is the row
+    // store's when none of the other three is given (equal to theirs when one is)
+    bool read_pileup = false;
+    ReadPileupParams read_pile;
+    bool row_store() const { return linkage || codons() || haps() || read_pileup; }   // bk_link_enable
+    uint32_t row_store_mismatches() const {
+        return linkage ? link.max_mismatches : codons() ? codon.max_mismatches : haps() ? hap.max_mismatches : read_pile.max_mismatches;
+    }
     bool region_report() const { return !regions_path.empty() || region_window > 0; }
     // reads are trimmed on the engine: a packed batch carries end flags and goes to bk_push_reads_packed_ends
     bool trims() const { return !primers.empty() || !adapters.empty(); }

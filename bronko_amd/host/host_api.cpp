@@ -14,6 +14,7 @@
 #include "indels.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
+#include "read_pileup.hpp"
 
 namespace {
 thread_local std::string g_err;
@@ -422,6 +423,30 @@ int bh_write_haplotypes_tsv(const void* h, int file_id, const char* path, const 
         t.entries.assign(en, en + n_entries);
         const bronko::HapStats st = bronko::write_haplotypes_tsv(path, *static_cast<const bronko::Index*>(h), file_id, windows_of(wins, names, n), t, p);
         if (stats) { stats[0] = st.lines; stats[1] = st.no_cover; stats[2] = st.distinct; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --read-pileup: the host twin of the engine's read pileup and the writer (read_pileup.cpp) ------------------------------------
+// cells: 48 bytes each (bk_read_pileup_cell), one per position of the genome file, written only where they fit cap; *n_cells: how many
+int bh_read_pileup_count(const void* h, int file_id, const void* rows, uint64_t n_rows, uint32_t end_dist, uint64_t cap, void* cells, uint64_t* n_cells) {
+    try {
+        const auto* rw = static_cast<const bronko::LinkRow*>(rows);
+        const std::vector<bronko::ReadPileupCell> c =
+            bronko::read_pileup_count(*static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::LinkRow>(rw, rw + n_rows), end_dist);
+        if (n_cells) *n_cells = c.size();
+        if (cells && c.size() <= cap && !c.empty()) std::memcpy(cells, c.data(), c.size() * sizeof(bronko::ReadPileupCell));
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// stats: cells with at least one row, the sum of all fwd and rev counters
+int bh_write_read_pileup_tsv(const void* h, int file_id, const char* path, const void* cells, uint64_t n_cells, uint32_t max_mismatches, uint32_t end_dist, uint64_t* stats) {
+    try {
+        bronko::ReadPileupParams p;
+        p.max_mismatches = max_mismatches; p.end_dist = end_dist;
+        const auto* c = static_cast<const bronko::ReadPileupCell*>(cells);
+        const bronko::ReadPileupStats st = bronko::write_read_pileup_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::ReadPileupCell>(c, c + n_cells), p);
+        if (stats) { stats[0] = st.covered; stats[1] = st.bases; }
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -546,3 +546,41 @@ def write_haplotypes_tsv(path, ix, file_id, windows, cover, ref_count, entries, 
                                  int(max_mismatches), int(min_reads), float(min_freq), stats) != 0:
         raise _host_error(L)
     return tuple(int(v) for v in stats)
+
+
+# ---- --read-pileup: the host twin of the engine's read pileup and the writer (read_pileup.cpp) ------------------------------------
+def _read_pileup_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_read_pileup_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_read_pileup_count.restype = C.c_int
+        L.bh_read_pileup_count.argtypes = [vp, C.c_int, vp, u64, u32, u64, vp, C.POINTER(u64)]
+        L.bh_write_read_pileup_tsv.restype = C.c_int
+        L.bh_write_read_pileup_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, vp]
+        L._read_pileup_ready = True
+    return L
+
+
+def read_pileup_count(ix, file_id, raw_rows, end_dist=10):
+    """The host twin of the read-pileup kernels (read_pileup.cpp read_pileup_count): an (n_cells, 12) uint32 array, per position of
+    genome file file_id fwd[ACGT], rev[ACGT], near[ACGT]; raw_rows as link_rows gives them."""
+    L = _read_pileup_lib()
+    raw = np.ascontiguousarray(np.asarray(raw_rows, np.uint8).reshape(-1, 32))
+    n = C.c_uint64()
+    if L.bh_read_pileup_count(ix.h, file_id, raw.ctypes.data, len(raw), int(end_dist), 0, None, C.byref(n)) != 0:
+        raise _host_error(L)
+    out = np.zeros((max(1, n.value), 12), np.uint32)
+    if L.bh_read_pileup_count(ix.h, file_id, raw.ctypes.data, len(raw), int(end_dist), n.value, out.ctypes.data, C.byref(n)) != 0:
+        raise _host_error(L)
+    return out[:n.value]
+
+
+def write_read_pileup_tsv(path, ix, file_id, cells, max_mismatches=8, end_dist=10):
+    """The --read-pileup writer (read_pileup.cpp write_read_pileup_tsv): cells (n_cells, 12) as read_pileup_count or
+    Engine.download_read_pileup gives them; returns (positions covered, bases)."""
+    L = _read_pileup_lib()
+    c = np.ascontiguousarray(np.asarray(cells, np.uint32).reshape(-1, 12))
+    stats = (C.c_uint64 * 2)()
+    if L.bh_write_read_pileup_tsv(ix.h, file_id, path.encode(), c.ctypes.data, len(c), int(max_mismatches), int(end_dist), stats) != 0:
+        raise _host_error(L)
+    return tuple(int(v) for v in stats)

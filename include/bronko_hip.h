@@ -652,6 +652,47 @@ int  bk_sample_haplotypes(bk_engine* e, const bk_hap_region* regions, uint32_t n
 int  bk_sample_download_haplotypes(bk_engine* e, bk_hap_summary* summary, uint32_t* cover, uint32_t* ref_count /* [n_regions] each */,
                                    bk_hap_entry* entries, uint64_t cap);
 
+/* ---- the pileup of whole reads: per position, which base the placed reads carry, by strand (`bronko call --read-pileup`; additive,
+ * still v8) ---------------------------------------------------------------------------------------------------------------------------
+ * The k-mer pileup's depth is approximate; the codon and haplotype tables count placed reads, but only inside their regions.  This is
+ * the plain pileup those rest on: how many rows lie over a cell, which base each carries there, on which strand, and how many of them
+ * have the cell within a few positions of one of their ends.  A fourth consumer of bk_link_enable's row store.  The terms row, placed
+ * and strand are those of bk_link_enable above; rows of both mate files count alike, overlapping mates count twice.  The rule, all
+ * of it integer arithmetic:
+ *   covers     a row covers the cells [c0, end), c0 = its cell0, end = c0 + n.
+ *   base       at a cell c of that range the row's base is its substitution at offset c - c0 if it has one, else the reference's
+ *              base at c; bases are in the reference's orientation, as in the rows (A C G T = 0 1 2 3).  Placement guarantees that
+ *              the reference's letter under a row is one of ACGT.
+ *   near       for the end distance E (0..255) the row is near an end at c when min(c - c0, end - 1 - c) < E.  With n <= 2 E that is
+ *              every cell of the row, with E = 0 none.
+ *   counters   per cell of the genome file one bk_read_pileup_cell of twelve u32: fwd[b] / rev[b] = the rows of strand 0 / 1 that
+ *              cover the cell and carry base b there; near[b] = the rows of either strand that carry b there and are near an end.
+ *              A sample has fewer than 2^32 rows: nothing overflows.  A cell whose reference letter is not ACGT has twelve zeros.
+ *   summary    rows = the store's placed rows; n_cells; end_dist = E; covered = the cells with at least one row; bases = the sum of
+ *              all fwd and rev counters, which equals the sum of the rows' lengths.
+ *   bk_sample_read_pileup     the row store is bk_link_enable's, there is no enable call of its own.  After the sample's
+ *                             bk_sample_finalize (BK_ERR_STATE inside a sample, before any finalize, and when linkage was not
+ *                             enabled as the sample began).  BK_ERR_INVALID: end_dist above 255.  BK_ERR_UNSUPPORTED: an index of
+ *                             more than BK_READ_PILEUP_MAX_CELLS cells (the message names both numbers): the work arrays are 15 words
+ *                             a cell and the result 12.  Nothing is launched in either case.  A row costs O(1 + n_mm) adds, not n:
+ *                             read_pileup_count_kernel adds +1 / -1 to per-strand and near-end difference arrays and 1 per
+ *                             substitution, equal destinations of a wave merged into one add; read_pileup_finish_kernel prefix-sums
+ *                             the difference arrays over all cells and writes the cells.  Asynchronous on the engine's stream; the
+ *                             host waits for nothing but an earlier count whose buffers the call replaces.  May be repeated on the
+ *                             same sample with another E.  Independent of bk_sample_linkage, bk_sample_codons and
+ *                             bk_sample_haplotypes: any order, none disturbs another's results.  Its buffers are made by the first
+ *                             call and are freed with the row store; an engine that never calls it allocates and launches nothing; a
+ *                             fork has none of its parent's.
+ *   bk_sample_download_read_pileup  after this sample's bk_sample_read_pileup (BK_ERR_STATE before it); synchronises; the summary
+ *                             and min(cap_cells, n_cells) cells from cell 0 on.  cells may be NULL with cap_cells 0; summary may
+ *                             not. */
+#define BK_READ_PILEUP_MAX_CELLS (1u << 22)
+#define BK_READ_PILEUP_MAX_END 255
+typedef struct { uint32_t fwd[4], rev[4], near[4]; } bk_read_pileup_cell;                          /* 48 bytes */
+typedef struct { uint64_t rows, n_cells; uint32_t end_dist, pad; uint64_t covered, bases; } bk_read_pileup_summary;
+int  bk_sample_read_pileup(bk_engine* e, uint32_t end_dist /* 0..255 */);
+int  bk_sample_download_read_pileup(bk_engine* e, bk_read_pileup_summary* summary, bk_read_pileup_cell* cells, uint64_t cap_cells);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
