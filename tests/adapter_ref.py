@@ -108,6 +108,32 @@ def hamming_at_cut(read, cut, s1, adapters, E):
     return out
 
 
+def masked(reads, quals, min_qual):
+    """the reads with every base whose quality is below min_qual written as N (min_qual 0: as they are)"""
+    if not min_qual:
+        return reads
+    out = []
+    for r, ql in zip(reads, quals):
+        a = np.frombuffer(r, np.uint8).copy()
+        a[np.frombuffer(ql, np.uint8) < 33 + min_qual] = ord("N")
+        out.append(a.tobytes())
+    return out
+
+
+def seen_reads(reads, quals, adapters, O, E, k, min_qual, primers=None, m=1):
+    """(the reads every result is defined by, adapter counters, primer counters or None, the share of reads cut): truncate, then mask,
+    then substitute"""
+    cuts, s1 = cut_positions_all(reads, adapters, O, E, quals, min_qual)
+    trunc, tq = truncate(reads, quals, cuts)
+    want = masked(trunc, tq, min_qual)
+    pcounts = None
+    if primers:
+        p5, p3, e0, ps1 = primer_ref.trim_lengths_all(trunc, primers, m, tq, min_qual)
+        want = primer_ref.substitute(want, p5, p3, e0)
+        pcounts = primer_ref.record_counts(trunc, p5, p3, e0, ps1, k)
+    return want, record_counts(reads, cuts, s1, k), pcounts, (cuts >= 0).mean()
+
+
 # ---- reads ------------------------------------------------------------------------------------------------------------------------
 def _tail(rng, n, poly_g):
     return b"G" * n if poly_g else np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n)].tobytes()

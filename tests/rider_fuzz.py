@@ -1,10 +1,14 @@
-"""Random cases for the passes that ride on a sample's records: --indels, --linkage, --codons, --haplotypes and the row store they share.
+"""Random cases for the passes that ride on a sample's records: --indels, --linkage, --codons, --haplotypes, --read-pileup and the row store
+they share, with and without --adapter, --primers and --min-base-qual in front of them.
 
 make_case(seed, iteration) draws one case -- k, a genome, reads, every parameter, the sites and regions, how the sample is pushed --
-from numpy's generator seeded with (seed, iteration) and nothing else.  expected(case) is what the restatements (tests/indels_ref.py,
-linkage_ref.py, codons_ref.py, haplotypes_ref.py) make of it; nothing of the product is asked.  check_host holds the host twins
-(bronko_amd.hostlib) against that, check_engine the engine.  tally() counts what a run of cases has exercised, for the conditions of
-tests/test_rider_fuzz_cpu.py.  tests/test_gpu_rider_fuzz.py and tools/fuzz_riders.py run the same cases.
+from numpy's generator seeded with (seed, iteration), and the read pileup's end distance and place among the other counts from a
+second one seeded with (seed, iteration, 1); nothing else goes in.  make_case(seed, iteration, trim=True) is the same base case with
+adapters and primers drawn from the second generator and reads that carry them.  expected(case) is what the restatements
+(tests/indels_ref.py, linkage_ref.py, codons_ref.py, haplotypes_ref.py, read_pileup_ref.py; adapter_ref.py and primer_ref.py for the
+reads as the rule sees them) make of it; nothing of the product is asked.  check_host holds the host twins (bronko_amd.hostlib) against
+that, check_engine the engine.  tally() counts what a run of cases has exercised, for the conditions of tests/test_rider_fuzz_cpu.py.
+tests/test_gpu_rider_fuzz.py and tools/fuzz_riders.py run the same cases.
 
 The generator itself is plain Python and numpy; the product is imported by the two check functions only.
 """
@@ -14,7 +18,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from tests import codons_ref, haplotypes_ref, indels_ref, linkage_ref
+from tests import adapter_ref, codons_ref, haplotypes_ref, indels_ref, linkage_ref, read_pileup_ref
 
 B = "ACGT"
 KS = (11, 15, 19, 21, 21, 25, 31, 31)            # 21 and 31 twice as likely
@@ -24,6 +28,9 @@ MIN_QUAL = 20
 LDS_PAIRS = 512                                  # kLinkLdsPairs: a counter table of more pairs takes the global path
 SEED = 20261                                     # the suite's seed
 BLOCK, BLOCKS = 30, 4                            # the suite's iterations: BLOCKS blocks of BLOCK
+TRIM_BLOCKS = 2                                  # ... and TRIM_BLOCKS blocks of BLOCK with adapters and primers set
+MERGE_ROUNDS = 4                                 # kMergeRounds: a wave merges at most so many groups of equal adds
+FINISH_BLOCK = 1024                              # kPileFinishBlock: a genome of fewer cells leaves finish threads without a cell
 
 
 def rand_seq(rng, n: int) -> str:
@@ -79,6 +86,22 @@ class Case:
     rc_repeat: bool
     n_run: tuple | None              # (first cell, length)
     first: list = field(default_factory=list)
+    # drawn from the second generator, (seed, it, 1): the read pileup's first end distance, where among the other counts it is taken
+    # (0 before linkage, 1 between codons and haplotypes, 2 last), which row and which d make the second end distance, what is
+    # downloaded once more at the end
+    pile_end: int = 10
+    pile_at: int = 2
+    pile_row: float = 0.0
+    pile_d: int = 0
+    recheck: str = "pairs"
+    # a trimmed case: the adapters and primers the engine is given (the reads carry them)
+    trim: bool = False
+    adapters: list = field(default_factory=list)
+    min_overlap: int = 5
+    max_error_rate: float = 0.1
+    primers: list = field(default_factory=list)
+    primer_m: int = 1
+    _seen: tuple | None = None
 
     def files(self):
         return [("fuzz", [(name, s.encode()) for name, s in zip(self.names, self.seqs)])]
@@ -86,24 +109,43 @@ class Case:
     def genome(self) -> indels_ref.Genome:
         return indels_ref.Genome(list(self.names), list(self.seqs), self.k)
 
+    def mates(self) -> list:
+        n = len(self.reads)
+        return [(0, n)] if self.n_mates == 1 else [(0, n // 2), (n // 2, n)]
+
+    def _see(self) -> tuple:
+        if self._seen is None:
+            min_qual = MIN_QUAL if self.push == "ascii_qual" else 0
+            if not self.trim:
+                self._seen = ([r.decode() for r in adapter_ref.masked(self.reads, self.quals, min_qual)], None)
+            else:                                                  # truncate, then mask, then substitute; the counters are a mate's
+                seen, counts = [], []
+                for lo, hi in self.mates():
+                    want, ac, pc, _ = adapter_ref.seen_reads(self.reads[lo:hi], self.quals[lo:hi], self.adapters, self.min_overlap, self.max_error_rate, self.k,
+                                                             min_qual, self.primers, self.primer_m)
+                    seen += [r.decode() for r in want]
+                    counts.append((ac, pc))
+                self._seen = (seen, counts)
+        return self._seen
+
     def reads_seen(self) -> list:
-        """The reads as the rule sees them: under ascii_qual a base whose quality is below MIN_QUAL is an N"""
-        if self.push != "ascii_qual":
-            return [r.decode() for r in self.reads]
-        out = []
-        for r, q in zip(self.reads, self.quals):
-            a = np.frombuffer(r, np.uint8).copy()
-            a[np.frombuffer(q, np.uint8) < 33 + MIN_QUAL] = ord("N")
-            out.append(a.tobytes().decode())
-        return out
+        """The reads as the rule sees them: under ascii_qual a base whose quality is below MIN_QUAL is an N; in a trimmed case cut at
+        the adapter first and with the primers' letters written as N last (adapter_ref.seen_reads)"""
+        return self._see()[0]
+
+    def trim_counts(self):
+        """[(bk_adapter_stats, bk_primer_stats) per mate] of a trimmed case, None of another"""
+        return self._see()[1]
 
     def describe(self) -> str:
         return ("seed=%d it=%d k=%d seqs=%s n_run=%s rc_repeat=%d reads=%d kinds=%s link_M=%d indel_L=%d indel_M=%d min_reads=%d ppm=%d initial_rows=%d "
-                "table_log2=%d sites=%d max_dist=%d codon_regions=%d hap_regions=%d push=%s batch=%s mates=%d twice=%d linkage_first=%d" %
+                "table_log2=%d sites=%d max_dist=%d codon_regions=%d hap_regions=%d push=%s batch=%s mates=%d twice=%d linkage_first=%d "
+                "pile_end=%d pile_at=%d pile_row=%.4f pile_d=%d recheck=%s trim=%d adapters=%s O=%d E=%g primers=%s m=%d" %
                 (self.seed, self.it, self.k, [len(s) for s in self.seqs], self.n_run, self.rc_repeat, len(self.reads),
                  ",".join("%s:%d" % kv for kv in sorted(self.kinds.items())), self.link_M, self.indel_L, self.indel_M, self.min_reads, self.min_af_ppm,
                  self.initial_rows, self.table_log2, len(self.sites), self.max_dist, len(self.codon_regions), len(self.hap_regions), self.push, self.batch,
-                 self.n_mates, self.twice, self.linkage_first))
+                 self.n_mates, self.twice, self.linkage_first, self.pile_end, self.pile_at, self.pile_row, self.pile_d, self.recheck, self.trim,
+                 [len(a) for a in self.adapters], self.min_overlap, self.max_error_rate, [len(p) for p in self.primers], self.primer_m))
 
 
 def _cut(rng, text: str, k: int) -> list:
@@ -162,8 +204,68 @@ def _regions(rng, seqs, first, n_run, spans, limits: tuple, per: int, n_max: int
     return out
 
 
-def make_case(seed: int, it: int) -> Case | None:
-    """Case `it` of `seed`, or None where no sequence holds a k-mer (no index is built of those)."""
+def _errors(rng, letters: list, positions) -> None:
+    for p in positions:
+        if letters[p] in B:
+            letters[p] = B[(B.index(letters[p]) + int(rng.integers(1, 4))) & 3]
+
+
+def _trim(rng, case: Case, src: str) -> None:
+    """Adapters and primers for the case, and reads that carry them.  One to three adapters of the two presets and a random 12 to
+    30-mer; one to six primers of 18 to 30 bases cut from either strand of the genome, clear of the N run; only what bk_adapters_set
+    and bk_primers_set accept.  About 20 % of the reads are drawn again to begin at a primer and about 10 % to end at the reverse
+    complement of one, with up to primer_m + 1 errors in it; then about 30 % of the reads of more than 50 bases run into an adapter
+    with up to two errors and a tail -- at a drawn position, or right behind the reverse-complemented primer."""
+    n = len(src)
+    pool = [adapter_ref.PRESETS["truseq"], adapter_ref.PRESETS["nextera"], rand_seq(rng, int(rng.integers(12, 31))).encode()]
+    case.adapters = [pool[int(i)] for i in rng.permutation(3)[:int(rng.integers(1, 4))]]
+    case.min_overlap = int(rng.choice([3, 5, 12]))
+    case.max_error_rate = float(rng.choice([0.0, 0.1, 0.2]))
+    case.primer_m = int(rng.choice([0, 1, 2]))
+    sites = []                                                     # (first cell, length, whether the primer is the reverse strand's)
+    for _ in range(int(rng.integers(1, 7))):
+        L = int(rng.integers(18, 31))
+        before = 0 if case.n_run is None else max(0, case.n_run[0] - L + 1)          # starts that end in front of the N run
+        after = n - L + 1 if case.n_run is None else max(0, n - L + 1 - (case.n_run[0] + case.n_run[1]))
+        a = int(rng.integers(0, before + after))
+        if a >= before and case.n_run is not None:
+            a = a - before + case.n_run[0] + case.n_run[1]
+        sites.append((a, L, bool(rng.random() < 0.5)))
+    case.primers = [(indels_ref.revcomp(src[a:a + L]) if rev else src[a:a + L]).encode() for a, L, rev in sites]
+    for i in range(len(case.reads)):
+        r, u, kind = case.reads[i].decode(), rng.random(), None
+        if u < 0.3:
+            a, L, rev = sites[int(rng.integers(0, len(sites)))]
+            ln = max(len(r), L)
+            s = list(indels_ref.revcomp(src[max(0, a + L - ln):a + L]) if rev else src[a:a + ln])   # begins with the primer
+            _errors(rng, s, rng.choice(L, size=int(rng.integers(0, case.primer_m + 2)), replace=False))
+            if rng.random() < 0.5:
+                _errors(rng, s, [p for p in np.nonzero(rng.random(len(s)) < 0.01)[0] if p >= L])
+            r, kind = "".join(s), "at_primer"
+            if u >= 0.2:
+                r, kind = indels_ref.revcomp(r), "to_primer"
+        if len(r) > 50 and rng.random() < 0.3:
+            A = list(case.adapters[int(rng.integers(0, len(case.adapters)))].decode())
+            _errors(rng, A, rng.choice(len(A), size=int(rng.integers(0, 3)), replace=False))
+            tail = "G" * len(r) if rng.random() < 0.5 else rand_seq(rng, len(r))
+            if kind == "to_primer" and rng.random() < 0.5:         # a short amplicon read through: primer, adapter, tail
+                r = r + "".join(A) + tail[:int(rng.integers(0, 21))]
+            else:
+                r = (r[:int(rng.integers(0, len(r) + 1))] + "".join(A) + tail)[:len(r)]
+            kind = (kind + "+adapter") if kind else "adapter"
+        if kind is not None:
+            qv = rng.integers(30, 41, len(r))
+            qv[rng.random(len(r)) < 0.01] = 7
+            case.reads[i], case.quals[i] = r.encode(), (qv + 33).astype(np.uint8).tobytes()
+            case.kinds[kind] = case.kinds.get(kind, 0) + 1
+    case.trim = True
+
+
+def make_case(seed: int, it: int, trim: bool = False) -> Case | None:
+    """Case `it` of `seed`, or None where no sequence holds a k-mer (no index is built of those).  What the first generator draws is
+    the case as it was before the read pileup and the trimming joined: everything of those comes from a second generator, so that an
+    iteration's genome, reads and parameters stay what they were.  With `trim` the second generator also draws adapters and primers
+    and rewrites some of the reads to carry them (_trim)."""
     rng = np.random.default_rng([seed, it])
     k = int(rng.choice(KS))
     text, rc_repeat = make_genome(rng, int(rng.integers(300, 6001)))
@@ -254,6 +356,14 @@ def make_case(seed: int, it: int) -> Case | None:
                 push=PUSHES[int(rng.integers(0, len(PUSHES)))], batch=int(rng.integers(1, 501)) if rng.random() < 0.4 else None,
                 n_mates=2 if rng.random() < 0.3 and len(reads) > 1 else 1, twice=bool(rng.random() < 0.3), linkage_first=bool(rng.random() < 0.2),
                 rc_repeat=rc_repeat, n_run=n_run, first=first)
+    rng2 = np.random.default_rng([seed, it, 1])
+    case.pile_end = int((0, 1, 10, k, 80, 128, 255)[int(rng2.integers(0, 7))])
+    case.pile_at = int(rng2.integers(0, 3))
+    case.pile_row = float(rng2.random())
+    case.pile_d = int(rng2.integers(-1, 2))
+    case.recheck = ("pairs", "codons")[int(rng2.integers(0, 2))]
+    if trim:
+        _trim(rng2, case, src)
     return case
 
 
@@ -266,6 +376,10 @@ class Expected:
     pairs: list
     codons: np.ndarray
     hap: tuple                       # (cover, ref_count, entries)
+    ends: tuple = ()                 # the two end distances of the read pileup: the drawn one, and about half the length of a drawn row
+    pile: dict = field(default_factory=dict)          # {E: the (cells, 12) counters}
+    pile_summary: dict = field(default_factory=dict)  # {E: (covered, bases)}
+    trim_counts: list | None = None  # [(adapter counters, primer counters) per mate] of a trimmed case
 
 
 def expected(case: Case) -> Expected:
@@ -277,7 +391,18 @@ def expected(case: Case) -> Expected:
         case.table_log2 += 1
     rows, t = linkage_ref.link_rows(g, seen, case.link_M)
     pairs = linkage_ref.link_count(g, rows, case.sites, case.max_dist)
-    return Expected(g, ind, rows, t, pairs, codons_ref.codon_count(g, rows, case.codon_regions), haplotypes_ref.hap_count(g, rows, case.hap_regions))
+    exp = Expected(g, ind, rows, t, pairs, codons_ref.codon_count(g, rows, case.codon_regions), haplotypes_ref.hap_count(g, rows, case.hap_regions))
+    # the second end distance puts a row at n = 2E - 1, 2E or 2E + 1: the count kernel takes its two ways apart at n <= 2E
+    second = case.pile_end
+    if rows:
+        second = min(read_pileup_ref.MAX_END, (rows[int(case.pile_row * len(rows))][1] + case.pile_d) // 2)
+    exp.ends = (case.pile_end, second)
+    for E in exp.ends:
+        if E not in exp.pile:
+            exp.pile[E] = read_pileup_ref.read_pileup(g, rows, E)
+            exp.pile_summary[E] = read_pileup_ref.summary(exp.pile[E], rows)
+    exp.trim_counts = case.trim_counts()
+    return exp
 
 
 def tally(case: Case, exp: Expected, into: dict) -> dict:
@@ -319,6 +444,39 @@ def tally(case: Case, exp: Expected, into: dict) -> dict:
     add("hap_cover", sum(exp.hap[0]))
     add("hap_cover_with_a_list", sum(exp.hap[0]) - sum(exp.hap[1]))
     add("pair_counts", sum(sum(c) for _, _, c in exp.pairs))
+    # the read pileup, per end distance the case counts at
+    for E in exp.ends:
+        add("pile_rows_whole", sum(1 for r in exp.rows if r[1] <= 2 * E))
+        add("pile_rows_split", sum(1 for r in exp.rows if r[1] > 2 * E))
+        add("pile_rows_at_2e", sum(1 for r in exp.rows if 2 * E - 1 <= r[1] <= 2 * E + 1))
+        add("pile_subs_near", sum(1 for r in exp.rows for off, _ in r[3] if min(off, r[1] - 1 - off) < E))
+        add("pile_subs_far", sum(1 for r in exp.rows for off, _ in r[3] if min(off, r[1] - 1 - off) >= E))
+        add("pile_near_counts", int(exp.pile[E][:, 8:].sum()))
+    add("it_pile_end_0", 0 in exp.ends)
+    add("it_pile_end_255", 255 in exp.ends)
+    add("it_pile_at_%d" % case.pile_at)
+    add("it_under_1024_cells", exp.g.cells < FINISH_BLOCK)
+    # 64-row chunks of the restatement's sorted rows in which more than MERGE_ROUNDS groups of two or more rows share (strand, cell0):
+    # a wave of those runs out of merge rounds.  The store's order on the device need not be the restatement's, so this is an
+    # indication and no guarantee; tests/test_gpu_read_pileup_waves.py fixes the composition of a wave.
+    for at in range(0, len(exp.rows), 64):
+        groups = {}
+        for r in exp.rows[at:at + 64]:
+            groups[(r[2], r[0])] = groups.get((r[2], r[0]), 0) + 1
+        add("pile_waves")
+        add("pile_waves_over_4_groups", sum(1 for v in groups.values() if v > 1) > MERGE_ROUNDS)
+    if case.trim:
+        records = lambda reads: sum(len(indels_ref.records_of(r, case.k)) for r in reads)
+        for (lo, hi), (ac, pc) in zip(case.mates(), exp.trim_counts):
+            add("trim_reads_cut", ac[0])
+            add("trim_bases_removed", ac[1])
+            add("trim_5", pc[0])
+            add("trim_3", pc[1])
+            add("trim_bases_masked", pc[2])
+        # a read that held a record and holds none as the rule sees it: emptied, or shortened below k
+        min_qual = MIN_QUAL if case.push == "ascii_qual" else 0
+        plain = [r.decode() for r in adapter_ref.masked(case.reads, case.quals, min_qual)]
+        add("trim_reads_emptied", sum(1 for a, b in zip(plain, case.reads_seen()) if records([a]) > 0 and records([b]) == 0))
     return into
 
 
@@ -339,8 +497,12 @@ def _span(exp):
     return np.array(exp.indels.span_sums()[:exp.g.cells], np.int64).astype(np.uint32)
 
 
+def _pile_differs(got, want):
+    return np.argwhere(np.asarray(got) != want)[:5].tolist()
+
+
 def check_host(case: Case, exp: Expected) -> None:
-    """The host twins on the case against the restatements; AssertionError names what differs"""
+    """The host twins on the case (on the reads as the rule sees them) against the restatements; AssertionError names what differs"""
     from bronko_amd import hostlib
     from bronko_amd.engine import link_rows as decode_rows
     ix = hostlib.HostIndex.build_mem(case.k, case.files())
@@ -364,6 +526,9 @@ def check_host(case: Case, exp: Expected) -> None:
         cover, ref, entries = hostlib.hap_count(ix, 0, raw, case.hap_regions)
         assert (list(cover), list(ref)) == (exp.hap[0], exp.hap[1]), "haplotype cover / ref_count"
         assert entries == exp.hap[2], ("haplotype entries",) + _differ(entries, exp.hap[2])
+        for E in exp.ends:
+            got = hostlib.read_pileup_count(ix, 0, raw, E)
+            assert got.shape == exp.pile[E].shape and np.array_equal(got, exp.pile[E]), ("read pileup", E, _pile_differs(got, exp.pile[E]))
     finally:
         ix.close()
 
@@ -371,10 +536,10 @@ def check_host(case: Case, exp: Expected) -> None:
 def _push(eng, case: Case, mate: int, a: int, b: int, keep: list) -> None:
     from bronko_amd import pack_reads, pack_reads_ends
     reads = case.reads[a:b]
-    if case.push == "packed":
+    if case.push == "packed" and not case.trim:                     # (the push without end flags is refused once primers are set)
         w, l = pack_reads(reads, case.k)
         eng.push_reads(mate, w, l)
-    elif case.push == "packed_ends":
+    elif case.push in ("packed", "packed_ends"):
         w, l, e = pack_reads_ends(reads, case.k)
         eng.push_reads_ends(mate, w, l, e)
     elif case.push == "ascii":
@@ -395,19 +560,31 @@ def _push(eng, case: Case, mate: int, a: int, b: int, keep: list) -> None:
 
 def _sample(eng, case: Case) -> None:
     eng.sample_begin()
-    n = len(case.reads)
-    mates = [(0, n)] if case.n_mates == 1 else [(0, n // 2), (n // 2, n)]
     keep = []
-    for m, (lo, hi) in enumerate(mates):
+    for m, (lo, hi) in enumerate(case.mates()):
         step = case.batch or max(1, hi - lo)
         for a in range(lo, hi, step):
             _push(eng, case, m, a, min(hi, a + step), keep)
     eng.sample_finalize(case.n_mates)
 
 
+def _check_pile(eng, exp: Expected, E: int, what: str) -> None:
+    """One read-pileup count of the finalized sample at end distance E: every counter of every cell and every field of the summary"""
+    eng.sample_read_pileup(E)
+    summ, cells = eng.download_read_pileup()
+    want = exp.pile[E]
+    assert cells.shape == want.shape and np.array_equal(cells, want), ("read pileup " + what, E, _pile_differs(cells, want))
+    got = (summ.rows, summ.n_cells, summ.end_dist, summ.covered, summ.bases)
+    assert got == (exp.tallies["placed"], exp.g.cells, E) + exp.pile_summary[E], ("read pileup summary " + what, E, got, exp.pile_summary[E])
+
+
 def _check_sample(eng, case: Case, exp: Expected) -> None:
     from bronko_amd import BronkoError
     g, c = exp.g, exp.indels.counters
+    if case.trim:
+        for m, (ac, pc) in enumerate(exp.trim_counts):
+            got = (eng.adapter_stats(m), eng.primer_stats(m))
+            assert got == (ac, pc), ("trimming counters of mate %d" % m, got, (ac, pc))
     # indels: the reported records at the drawn thresholds, the whole table, the span, the summary
     eng.sample_indels(case.min_reads, case.min_af_ppm)
     summ, rows = eng.download_indels()
@@ -425,6 +602,8 @@ def _check_sample(eng, case: Case, exp: Expected) -> None:
     # linkage: the rows, the tallies, every pair
     got = eng.download_link_rows()
     assert got == exp.rows, ("rows", len(got), len(exp.rows)) + _differ(got, exp.rows)
+    if case.pile_at == 0:
+        _check_pile(eng, exp, exp.ends[0], "before linkage")
     eng.sample_linkage(case.sites, case.max_dist)
     summ, pairs = eng.download_linkage()
     t = exp.tallies
@@ -436,6 +615,8 @@ def _check_sample(eng, case: Case, exp: Expected) -> None:
     summ, counts = eng.download_codons()
     assert (summ.rows, summ.n_codons, summ.n_regions) == (t["placed"], len(exp.codons), len(case.codon_regions)), "codon summary"
     assert np.array_equal(counts, exp.codons), ("codons", np.argwhere(counts != exp.codons)[:5].tolist())
+    if case.pile_at == 1:
+        _check_pile(eng, exp, exp.ends[0], "between codons and haplotypes")
     # haplotypes: a table of 2^10 slots; where it cannot hold every haplotype the hot counters stay exact, and 2^16 slots hold all
     cover, ref, entries = exp.hap
     log2 = 10
@@ -456,6 +637,16 @@ def _check_sample(eng, case: Case, exp: Expected) -> None:
         ("haplotype summary", summ.rows, summ.dropped, summ.entries, len(entries))
     assert (list(cv), list(rf)) == (cover, ref), "haplotype cover / ref_count"
     assert got == entries, ("haplotype entries",) + _differ(got, entries)
+    # the read pileup where it was not counted yet, then at the second end distance; a count in between left its neighbours' results alone
+    if case.pile_at == 2:
+        _check_pile(eng, exp, exp.ends[0], "last")
+    _check_pile(eng, exp, exp.ends[1], "at the second end distance")
+    if case.recheck == "codons" and case.codon_regions:
+        counts = eng.download_codons()[1]
+        assert np.array_equal(counts, exp.codons), ("codons after the read pileup", np.argwhere(counts != exp.codons)[:5].tolist())
+    else:
+        pairs = eng.download_linkage()[1]
+        assert pairs == exp.pairs, ("pairs after the read pileup", [x for x in zip(pairs, exp.pairs) if x[0] != x[1]][:2])
 
 
 def check_engine(case: Case, exp: Expected) -> None:
@@ -468,6 +659,9 @@ def check_engine(case: Case, exp: Expected) -> None:
         enable = [lambda: eng.indels_enable(case.indel_L, case.indel_M, case.table_log2), lambda: eng.linkage_enable(case.link_M, case.initial_rows)]
         for fn in (enable[::-1] if case.linkage_first else enable):
             fn()
+        if case.trim:
+            eng.adapters_set(case.adapters, case.min_overlap, case.max_error_rate)
+            eng.primers_set(case.primers, case.primer_m)
         for _ in range(2 if case.twice else 1):
             _sample(eng, case)
             _check_sample(eng, case, exp)
@@ -477,11 +671,12 @@ def check_engine(case: Case, exp: Expected) -> None:
         ix.close()
 
 
-def run(seed: int, first: int, count: int, check, verbose: bool = False, out=print) -> tuple:
-    """Cases first .. first + count - 1 of `seed` through `check` (check_host or check_engine): (cases run, [(case's line, message)])"""
+def run(seed: int, first: int, count: int, check, verbose: bool = False, out=print, trim: bool = False) -> tuple:
+    """Cases first .. first + count - 1 of `seed`, trimmed ones with `trim`, through `check` (check_host or check_engine): (cases run,
+    [(case's line, message)])"""
     ran, bad = 0, []
     for it in range(first, first + count):
-        case = make_case(seed, it)
+        case = make_case(seed, it, trim)
         if case is None:
             continue
         exp = expected(case)

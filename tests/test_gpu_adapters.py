@@ -14,6 +14,7 @@ from bronko_amd import pack_reads, pack_reads_ends, synth
 from bronko_amd.engine import BronkoError
 
 from tests import adapter_ref, helpers, primer_ref
+from tests.adapter_ref import seen_reads as expected
 
 pytestmark = pytest.mark.gpu
 
@@ -48,30 +49,6 @@ def dataset(genome, seed, adapters, O, E, n=3000):
     reads += adapter_ref.library_reads(gm, amps, adapters, n // 8, 32, seed + 2) + adapter_ref.library_reads(gm, amps, adapters, n // 8, 300, seed + 3)
     reads += [r for r, _ in adapter_ref.edge_reads(genome, adapters, O, E, 150, seed + 4)]
     return reads, primers
-
-
-def masked(reads, quals, min_qual):
-    if not min_qual:
-        return reads
-    out = []
-    for r, ql in zip(reads, quals):
-        a = np.frombuffer(r, np.uint8).copy()
-        a[np.frombuffer(ql, np.uint8) < 33 + min_qual] = ord("N")
-        out.append(a.tobytes())
-    return out
-
-
-def expected(reads, quals, adapters, O, E, k, min_qual, primers=None, m=1):
-    """(the reads every result is defined by, adapter counters, primer counters or None): truncate, then mask, then substitute"""
-    cuts, s1 = adapter_ref.cut_positions_all(reads, adapters, O, E, quals, min_qual)
-    trunc, tq = adapter_ref.truncate(reads, quals, cuts)
-    want = masked(trunc, tq, min_qual)
-    pcounts = None
-    if primers:
-        p5, p3, e0, ps1 = primer_ref.trim_lengths_all(trunc, primers, m, tq, min_qual)
-        want = primer_ref.substitute(want, p5, p3, e0)
-        pcounts = primer_ref.record_counts(trunc, p5, p3, e0, ps1, k)
-    return want, adapter_ref.record_counts(reads, cuts, s1, k), pcounts, (cuts >= 0).mean()
 
 
 def check(eng, res, pile, ref, ref_dump, counts, pcounts):

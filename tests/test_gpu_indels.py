@@ -238,7 +238,7 @@ def test_enable_disable_enable_and_an_abandoned_sample(world):
 
 
 def test_with_primers_and_adapters_set(world):
-    from tests.test_gpu_adapters import expected
+    from tests.adapter_ref import seen_reads as expected
     rng = np.random.default_rng(5)
     reads = []
     for i, r in enumerate(_b(world.reads[:1200])):               # a third of the reads run into the adapter and a tail

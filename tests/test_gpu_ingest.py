@@ -11,7 +11,8 @@ import pytest
 from bronko_amd import pack_reads_ends, synth
 
 from tests import adapter_ref, helpers, primer_ref
-from tests.test_gpu_adapters import TRUSEQ, expected, quals_for
+from tests.adapter_ref import seen_reads as expected
+from tests.test_gpu_adapters import TRUSEQ, quals_for
 
 pytestmark = pytest.mark.gpu
 
