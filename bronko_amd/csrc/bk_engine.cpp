@@ -418,6 +418,7 @@ static int l2_stats_report(bk_engine* e) {
     }
     fprintf(stderr, "[bk] scan: %llu mismatches counted, %llu items processed, %llu E gaps before a mismatch, %llu behind the last\n", h[23], h[24], h[25], h[26]);
     fprintf(stderr, "[bk] scan N batches: %llu with %llu pieces (%.1f per batch), %llu of them forced by a tile's end\n", h[20], h[21], h[20] ? (double)h[21] / (double)h[20] : 0.0, h[22]);
+    fprintf(stderr, "[bk] level 2 discovery: %llu records newly marked by the scan, %llu records queued, g_work %llu\n", h[27], h[28], h[29]);
     fprintf(stderr, "[bk] scan marked: no-diagonal %llu, dirty-head %llu, clean-head %llu, pairs %llu | level 2: k-mers %llu in %llu chunks, simple %llu, dead %llu, "
             "dirty answers %llu (one difference but id unknown: %llu), neither half present %llu, slow %llu (diffs 0/1/2/3+ with a diagonal: %llu/%llu/%llu/%llu) -> member %llu, neighbour %llu, nothing %llu\n",
             h[0], h[1], h[2], h[3], h[4], h[11], h[5], h[6], h[16], h[17], h[18], h[7], h[12], h[13], h[14], h[15], h[8], h[9], h[10]);
@@ -451,6 +452,7 @@ static bk::ScanArgs scan_args(const bk_engine* e, int mate, const Records& r) {
         a.rl_recip = ~0ull / (unsigned long long)(ix.v_span + 1) + 1ull;   // ceil(2^64 / row length): exact quotients for 32-bit counter indices
     }
     a.dbg = e->dbg.p; a.l2_words = bk::scan_l2_words(r.stride_words, ix.k); a.l2_min_grid = (uint32_t)std::max(1, ix.n_cus / 2);
+    if (const char* mg = test_env("BK_L2_MIN_GRID")) a.l2_min_grid = (uint32_t)std::max(1, atoi(mg));   // testing aid: a plan so small that a wave of level2_kernel goes round several times
     if (e->use_items) { a.ig = e->ig; a.items = e->items.p; a.tab = e->item_tab.p; a.gext = e->item_gext.p; a.ov = e->ov.p; a.ov_n = e->ov_n.p; a.ov_cap = (uint32_t)e->ov.n; }
     return a;
 }

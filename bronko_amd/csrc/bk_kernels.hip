@@ -1326,7 +1326,7 @@ constexpr int kL2Block = 256;
 constexpr int kL2Waves = kL2Block / 64;
 constexpr int kL2QueueCap = 128;            // record / slow queues: a batch is taken at 64 pending, a round adds <= 64
 constexpr int kL2KmerCap = 256;             // k-mer queue
-constexpr int kAnyWords = 8;                // words of l2_any a wave takes at a time (256 records)
+constexpr int kAnyWords = 8;                // words of n_any a wave of nbatch_kernel takes at a time (256 records); of l2_any a wave of level2_kernel takes no fewer
 constexpr int kNbBlocksPerWave = 4;        // blocks of 256 records a wave of nbatch_kernel takes when there are enough of them
 template <bool STATS, int KT, bool SPARSE>
 __global__ __launch_bounds__(kL2Block) void nbatch_kernel(ScanArgs a) {
@@ -1567,8 +1567,9 @@ __global__ __launch_bounds__(kL2Block) void nbatch_kernel(ScanArgs a) {
 static_assert(kL2Block == kBinBlock, "an E bin rides in a workgroup of level2_kernel");
 static_assert(kEBinAccWords * sizeof(unsigned int) <= (size_t)kL2Waves * kL2QueueCap * sizeof(unsigned long long), "the ride's accumulator lies in the slow-path queues");
 static_assert(sizeof(ScanArgs) + sizeof(uint32_t) + sizeof(BinArgs) + 16 <= 4096, "kernel arguments of level2_kernel");
+// (four waves per SIMD asked for: left to itself the compiler takes 132 VGPRs for the statistics instantiations -- three waves)
 template <bool STATS, int KT, bool SPARSE>
-__global__ __launch_bounds__(kL2Block) void level2_kernel(ScanArgs a, uint32_t n_l2, BinArgs ride) {
+__global__ __launch_bounds__(kL2Block) __attribute__((amdgpu_waves_per_eu(4))) void level2_kernel(ScanArgs a, uint32_t n_l2, BinArgs ride) {
     __shared__ unsigned long long queue_c[kL2Waves * kL2QueueCap];   // slow-path queue: canonical k-mer | orientation << 62 | stat_only << 63
     if (blockIdx.x >= n_l2) {   // (wave-uniform, the whole workgroup) an E bin: its accumulator where Level 2's workgroups keep their slow-path queues
         bin_count_body<true>(ride, blockIdx.x - n_l2, reinterpret_cast<unsigned int*>(queue_c));
@@ -1895,28 +1896,47 @@ __global__ __launch_bounds__(kL2Block) void level2_kernel(ScanArgs a, uint32_t n
     };
 
     const uint64_t n_any = (n_records + 31) / 32;                    // words of l2_any / n_any
-    const uint64_t n_blk = (n_any + kAnyWords - 1) / kAnyWords;
 
     // (ScanArgs::l2_plan: with few records marked, few workgroups -- the others leave at once)
     const uint32_t g_work = a.l2_plan ? min(n_l2, max(*a.l2_plan, 1u)) : n_l2;
+#ifdef BK_TESTING
+    if (a.dbg && blockIdx.x == 0 && threadIdx.x == 0) a.dbg[29] = g_work;
+#endif
     if (blockIdx.x >= g_work) return;
-    for (uint64_t blk = (uint64_t)blockIdx.x * kL2Waves + wave; blk < n_blk; blk += (uint64_t)g_work * kL2Waves) {
-        const uint64_t i = blk * kAnyWords + lane;
-        const uint32_t anyw = (lane < kAnyWords && i < n_any) ? a.l2_any[i] : 0u;
-        if (anyw) a.l2_any[i] = 0u;     // taken: l2_any and l2_bits are all zero again when this kernel ends
-        if (!__ballot(anyw != 0u)) continue;
-#pragma unroll
-        for (int j = 0; j < kAnyWords / 2; ++j) {   // record 64 j + lane of the block: bit (lane & 31) of word 2 j + (lane >> 5)
-            const uint32_t wv = (uint32_t)__shfl((int)anyw, 2 * j + (lane >> 5));
+    // Discovery, one trip to memory per wave where the launch allows: the working waves share the words of l2_any in stretches of
+    // m consecutive words, one word per lane and one load per stretch (at least kAnyWords words -- the distribution is as fine as
+    // a launch with a block of kAnyWords per wave or less ever had it --, at most a word per lane; a launch with more stretches than
+    // waves goes round, the next stretch asked for before this one is walked).  A stretch is walked in steps of 64 records -- two
+    // words: record 64 j + lane of the stretch is bit (lane & 31) of word 2 j + (lane >> 5) --, the steps whose words are both
+    // empty not at all: records reach the queue in rising order.
+    const uint32_t n_waves = g_work * kL2Waves;
+    const uint32_t n_anyw = (uint32_t)n_any;   // (a launch has fewer than 2^32 records: everything below fits 32 bits)
+    const uint32_t m = min(64u, max((uint32_t)kAnyWords, (n_anyw + n_waves - 1u) / n_waves));   // (wave-uniform)
+    const uint32_t n_trips = (n_anyw + m - 1u) / m;
+    auto any_words = [&](uint32_t trip) __attribute__((always_inline)) -> uint32_t {
+        const uint32_t i = trip * m + (uint32_t)lane;
+        return (trip < n_trips && (uint32_t)lane < m && i < n_anyw) ? a.l2_any[i] : 0u;
+    };
+    uint32_t trip = blockIdx.x * kL2Waves + (uint32_t)wave;
+    uint32_t anyw = any_words(trip);
+    while (trip < n_trips) {
+        const uint32_t trip_next = trip + n_waves;
+        const uint32_t anyw_next = any_words(trip_next);
+        if (anyw) a.l2_any[trip * m + (uint32_t)lane] = 0u;     // taken: l2_any and l2_bits are all zero again when this kernel ends
+        unsigned long long nz = __ballot(anyw != 0u);           // the stretch's words that hold a mark (lanes at m and beyond: none)
+        while (nz) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(nz) >> 1;
+            nz &= ~(3ull << (2u * j));
+            const uint32_t wv = (uint32_t)__shfl((int)anyw, (int)(2u * j) + (lane >> 5));
             const bool marked = (wv >> (lane & 31)) & 1u;
-            const unsigned long long hm = __ballot(marked);
-            if (hm) {
-                if (marked) rq[qr + lane_prefix(hm)] = (uint32_t)(blk * (kAnyWords * 32) + 64u * (uint32_t)j + (uint32_t)lane);
-                qr += (uint32_t)__popcll(hm);
-                __builtin_amdgcn_wave_barrier();
-                if (qr >= 64u) take_records();
-            }
+            const unsigned long long hm = __ballot(marked);     // (not zero: one of the step's two words is not)
+            if (marked) rq[qr + lane_prefix(hm)] = trip * m * 32u + 64u * j + (uint32_t)lane;
+            qr += (uint32_t)__popcll(hm);
+            BK_DBG(a, 28, lane == 0, __popcll(hm));
+            __builtin_amdgcn_wave_barrier();
+            if (qr >= 64u) take_records();
         }
+        trip = trip_next; anyw = anyw_next;
     }
     while (qr) take_records();
     while (qk) take_kmers();
@@ -2089,7 +2109,7 @@ hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const
                                 : (stats ? level2_kernel<true, KT, true> : level2_kernel<false, KT, true>))
     void (*kern)(ScanArgs, uint32_t, BinArgs) = a.k == 21 ? BK_PICK(21) : a.k == 31 ? BK_PICK(31) : BK_PICK(0);
 #undef BK_PICK
-    const uint64_t blks = (a.n_records + 32 * kAnyWords - 1) / (32 * kAnyWords);     // a wave takes kAnyWords words of l2_any at a time
+    const uint64_t blks = (a.n_records + 32 * kAnyWords - 1) / (32 * kAnyWords);     // a wave takes at least kAnyWords words of l2_any at a time
     // One genome file: a thousandth of the k-mers are marked, and four thousand waves that find nothing to do still take their turn
     // on the CUs the sibling samples' kernels are waiting for (three samples in flight: 10.5 -> 10.8 G reads/s with a quarter of the
     // waves; alone the kernel takes what it took).  Several files: the marks are Level 2's real work (config 3 lost 8 % that way).

@@ -13,7 +13,9 @@ namespace bk {
 #define BK_ABLATE(a, x) ((a).ablate == (x))
 // BK_L2_STATS tallies (ScanArgs::dbg): k-mers marked by the scan [0] without a diagonal, [1] at a dirty / id-breaking head,
 // [2] mismatch-free head, [3] close pairs; Level 2: [4] k-mers looked at, [5] single-k-mer S runs, [6] dropped as dead,
-// [7] queued for the slow pipeline, [8] ... reference k-mers after all, [9] ... a neighbour found, [10] ... nothing; [11] chunks
+// [7] queued for the slow pipeline, [8] ... reference k-mers after all, [9] ... a neighbour found, [10] ... nothing; [11] chunks;
+// Level 2's discovery: [27] records the binned scan marked for the first time, [28] records level2_kernel's discovery queued (equal
+// where nbatch_kernel marks none), [29] the workgroups of the last level2_kernel launch that worked (ScanArgs::l2_plan)
 #define BK_DBG(a, idx, pred, cnt) do { if ((a).dbg && (pred)) atomicAdd((a).dbg + (idx), (unsigned long long)(cnt)); } while (0)
 // ... and behind the 32 tallies, per workgroup of scan_items_kernel: [32 + 4 b] clock at its start, [+ 1] after the reference is
 // staged, [+ 2] after its last tile, [+ 3] at its end (wall_clock64: 100 MHz)

@@ -250,6 +250,10 @@ __global__ __launch_bounds__(kItemBlock) void scan_items_kernel(ScanArgs a) {
         if (!on) return;
         const ColdArgs c = cold();
         unsigned int* row = c->l2_bits + (size_t)rec * c->l2_words;
+#ifdef BK_TESTING   // (BK_L2_STATS counts the records marked for the first time: what level2_kernel's discovery must find)
+        if (c->dbg) { const uint32_t rbit = 1u << (rec & 31u); BK_DBG(*c, 27, !(atomicOr(c->l2_any + (rec >> 5), rbit) & rbit), 1); }
+        else
+#endif
         atomicOr(c->l2_any + (rec >> 5), 1u << (rec & 31u));
         c->l2_diag[rec] = make_uint2((uint32_t)dgm, flm);
         uint32_t w = sk >> 5, bit = sk & 31u, left = n;
