@@ -75,6 +75,19 @@ class IndelSummary(C.Structure):  # bk_indel_summary
                 ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class JunctionConfig(C.Structure):  # bk_junction_config
+    _fields_ = [("min_len", C.c_uint32), ("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
+class JunctionParams(C.Structure):  # bk_junction_params
+    _fields_ = [("min_reads", C.c_uint64)]
+
+
+class JunctionSummary(C.Structure):  # bk_junction_summary
+    _fields_ = [("records", C.c_uint64), ("anchored", C.c_uint64), ("ref_spanning", C.c_uint64), ("supporting", C.c_uint64), ("short_", C.c_uint64),
+                ("backward", C.c_uint64), ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
+
+
 class CodonSummary(C.Structure):  # bk_codon_summary
     _fields_ = [("rows", C.c_uint64), ("n_codons", C.c_uint64), ("n_regions", C.c_uint32)]
 
@@ -122,6 +135,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
+           "bk_junctions_enable", "bk_sample_junctions", "bk_sample_download_junctions", "bk_sample_download_junction_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
            "bk_sample_read_pileup", "bk_sample_download_read_pileup",
@@ -260,6 +274,14 @@ def load(testing=None):
     L.bk_sample_download_indels.argtypes = [vp, C.POINTER(IndelSummary), vp, u64]
     L.bk_sample_download_indel_span.restype = C.c_int
     L.bk_sample_download_indel_span.argtypes = [vp, vp, u64]
+    L.bk_junctions_enable.restype = C.c_int
+    L.bk_junctions_enable.argtypes = [vp, C.POINTER(JunctionConfig)]
+    L.bk_sample_junctions.restype = C.c_int
+    L.bk_sample_junctions.argtypes = [vp, C.POINTER(JunctionParams)]
+    L.bk_sample_download_junctions.restype = C.c_int
+    L.bk_sample_download_junctions.argtypes = [vp, C.POINTER(JunctionSummary), vp, u64]
+    L.bk_sample_download_junction_span.restype = C.c_int
+    L.bk_sample_download_junction_span.argtypes = [vp, vp, u64]
     L.bk_link_enable.restype = C.c_int
     L.bk_link_enable.argtypes = [vp, C.POINTER(LinkConfig)]
     L.bk_sample_linkage.restype = C.c_int

@@ -1,5 +1,5 @@
-// bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip) and link_scan_kernel
-// (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+// bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip), junction_scan_kernel
+// (bk_junctions.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
 //
 // What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
 // log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
@@ -112,6 +112,56 @@ __device__ __forceinline__ bool cells_placed(const AnchorIndex& a, uint32_t ca, 
         if (i < a.n_nruns && (int32_t)a.nruns[i].x < hi) return false;
     }
     return true;
+}
+
+// A record as the breakpoint walks of indel_scan_kernel and junction_scan_kernel read it: r', the record along the reference.  One
+// against the reference reads rc_words at the mirrored cells, so no record is reverse-complemented.
+struct OrientedRecord {
+    const AnchorIndex& ix;
+    const uint32_t* __restrict__ w;
+    int32_t n;
+    uint32_t last_word;
+    bool against;
+    // #{j in [j0, j1): r'[j] != ref[d + j]}
+    __device__ __forceinline__ int32_t span_mm(int32_t j0, int32_t j1, int32_t d) const {
+        if (j0 >= j1) return 0;
+        return (int32_t)(against ? mismatches(w, last_word, (uint32_t)(n - j1), (uint32_t)(n - j0), ix.rc_words, (int64_t)ix.total_cells - d - n, ~0u)
+                                 : mismatches(w, last_word, (uint32_t)j0, (uint32_t)j1, ix.ref_words, d, ~0u));
+    }
+    __device__ __forceinline__ uint32_t at(int32_t j) const { return against ? 3u - sym_at(w, (uint32_t)(n - 1 - j)) : sym_at(w, (uint32_t)j); }   // r'[j]
+    __device__ __forceinline__ int32_t mm(int32_t j, int32_t d) const { return at(j) != sym_at(ix.ref_words, (uint32_t)(d + j)) ? 1 : 0; }
+};
+// F of the normalisation: the first cell of the stretch of ACGT letters of the sequence (the one that holds `cell`) in front of the
+// record's cells, which begin at `lo` and hold no other letter: the runs in front of them are the ones that end at lo or before
+__device__ __forceinline__ int32_t acgt_floor(const AnchorIndex& a, uint32_t cell, int32_t lo) {
+    int32_t F = (int32_t)a.seq_lo[seq_of(a, cell)];
+    if (a.n_nruns) {
+        const uint32_t i = first_run_behind(a, lo);
+        if (i > 0u) F = max(F, (int32_t)a.nruns[i - 1u].y);
+    }
+    return F;
+}
+
+constexpr int kSpanPrefixBlock = 1024;
+// span[0 .. n) prefix-summed in place by one workgroup of kSpanPrefixBlock threads (u32 arithmetic wraps: a -1 that precedes its +1
+// in memory order still cancels): a thread sums its stretch, the stretches' sums are scanned through LDS, the thread writes its stretch.
+__device__ __forceinline__ void span_prefix_block(unsigned int* __restrict__ span, uint32_t n) {
+    __shared__ unsigned int part_s[2][kSpanPrefixBlock];
+    const uint32_t per = (n + kSpanPrefixBlock - 1) / kSpanPrefixBlock;
+    const uint32_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
+    unsigned int sum = 0u;
+    for (uint32_t i = lo; i < hi; ++i) sum += span[i];
+    part_s[0][threadIdx.x] = sum;
+    __syncthreads();
+    int cur = 0;
+    for (uint32_t off = 1; off < (uint32_t)kSpanPrefixBlock; off <<= 1) {   // inclusive scan of the stretches' sums
+        const unsigned int v = part_s[cur][threadIdx.x] + (threadIdx.x >= off ? part_s[cur][threadIdx.x - off] : 0u);
+        part_s[cur ^ 1][threadIdx.x] = v;
+        __syncthreads();
+        cur ^= 1;
+    }
+    unsigned int acc = part_s[cur][threadIdx.x] - sum;   // what precedes this thread's stretch
+    for (uint32_t i = lo; i < hi; ++i) { acc += span[i]; span[i] = acc; }
 }
 
 __device__ __forceinline__ uint32_t wave_total(uint32_t v) {

@@ -242,8 +242,8 @@ struct Regions {
     uint32_t max_file_regions = 0;          // regions of the genome file with the most: the kernel's grid
 };
 
-// What placing a record by two anchor k-mers reads beside the index tables (bk_anchor.h): built by the first of bk_indels_enable and
-// bk_link_enable, used by both, freed with the last of them
+// What placing a record by two anchor k-mers reads beside the index tables (bk_anchor.h): built by the first of bk_indels_enable,
+// bk_junctions_enable and bk_link_enable, used by all of them, freed with the last
 struct AnchorTables {
     DevBuf<uint32_t> unique_bits;           // one bit per reference k-mer id: it starts at exactly one cell (a histogram of id_at)
     DevBuf<uint32_t> seq_lo;                // [sequences + 1] first cells, then total_cells
@@ -331,6 +331,22 @@ struct Indels {
     DevBuf<bk_indel_record> rows;           // [2^table_log2]
     bool in_sample = false;                 // enabled when the current / last sample began
     bool summed = false;                    // span is prefix-summed (this sample's bk_sample_indels ran)
+    bool made = false;                      // ... and the rows are this sample's
+    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
+    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+};
+
+// bk_junctions_enable: the same for junction_scan_kernel (bk_junctions.hip) -- its own event table, span array, tallies and rows
+struct Junctions {
+    bk_junction_config cfg{};
+    std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable and bk_link_enable
+    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word pos | D << 32 (~0 = free)
+    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
+    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_junctions
+    DevBuf<unsigned long long> tallies;     // [10] bk_kernels.h JunctionArgs::tallies
+    DevBuf<bk_junction_record> rows;        // [2^table_log2]
+    bool in_sample = false;                 // enabled when the current / last sample began
+    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_junctions ran)
     bool made = false;                      // ... and the rows are this sample's
     int begin_sample(bk_engine* e);         // (bk_riders.cpp)
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records
@@ -554,8 +570,9 @@ struct bk_engine {
     std::unique_ptr<Regions> regions;       // bk_regions_set (null: no regions, no launch, no buffers)
     bool regions_made = false;              // bk_sample_region_depths ran for the current sample and table
     std::unique_ptr<Indels> indels;         // bk_indels_enable (null: no table, no launch, no buffers)
+    std::unique_ptr<Junctions> junctions;   // bk_junctions_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Linkage> linkage;       // bk_link_enable (null: no row store, no launch, no buffers)
-    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while either feature holds them
+    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the three features holds them
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

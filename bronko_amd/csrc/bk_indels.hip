@@ -28,7 +28,6 @@ namespace {
 
 constexpr int kIndelBlock = 256;
 constexpr uint32_t kIndelQueue = 128;      // entries of a wave's queue: fewer than 64 wait when up to 64 more arrive
-constexpr int kPrefixBlock = 1024;
 constexpr unsigned long long kFreeWord = ~0ull;
 
 struct IndelTally { uint32_t records = 0, anchored = 0, spanning = 0, supporting = 0, discordant = 0; };
@@ -93,34 +92,22 @@ __device__ __forceinline__ void indel_walk(const IndelArgs& a, const uint4 work,
     const uint32_t last_word = (uint32_t)(n - 1) >> 4;
     const int32_t p0 = pa + k, p1 = pb - I;
     if (p0 > p1) { t.discordant++; return; }
-    // #{j in [j0, j1): r'[j] != ref[d + j]}: a record against the reference reads rc_words at the mirrored cells
-    auto span_mm = [&](int32_t j0, int32_t j1, int32_t d) -> int32_t {
-        if (j0 >= j1) return 0;
-        return (int32_t)(against ? mismatches(w, last_word, (uint32_t)(n - j1), (uint32_t)(n - j0), a.ix.rc_words, (int64_t)a.ix.total_cells - d - n, ~0u)
-                                 : mismatches(w, last_word, (uint32_t)j0, (uint32_t)j1, a.ix.ref_words, d, ~0u));
-    };
-    auto rp = [&](int32_t j) -> uint32_t { return against ? 3u - sym_at(w, (uint32_t)(n - 1 - j)) : sym_at(w, (uint32_t)j); };   // r'[j]
-    auto mm = [&](int32_t j, int32_t d) -> int32_t { return rp(j) != sym_at(a.ix.ref_words, (uint32_t)(d + j)) ? 1 : 0; };
-    int32_t m = span_mm(0, p0, dL) + span_mm(p0 + I, n, dR);
+    const OrientedRecord rec{a.ix, w, n, last_word, against};
+    int32_t m = rec.span_mm(0, p0, dL) + rec.span_mm(p0 + I, n, dR);
     int32_t best = m, best_p = p0;
     for (int32_t p = p0; p < p1; ++p) {
-        m += mm(p, dL) - mm(p + I, dR);
+        m += rec.mm(p, dL) - rec.mm(p + I, dR);
         if (m < best) { best = m; best_p = p + 1; }
     }
     if (best > (int32_t)a.max_mismatches) { t.discordant++; return; }
     int32_t pos = dL + best_p;
     // F: the first cell of the stretch of ACGT letters of the sequence that holds pos - 1 (the record's cells hold no other letter)
-    int32_t F = (int32_t)a.ix.seq_lo[seq_of(a.ix, (uint32_t)(dL + pa))];
-    const int32_t lo = min(dL, dR);
-    if (a.ix.n_nruns) {   // (no run reaches into the record's cells: the runs in front of them are the ones that end at lo or before)
-        const uint32_t i = first_run_behind(a.ix, lo);
-        if (i > 0u) F = max(F, (int32_t)a.ix.nruns[i - 1u].y);
-    }
+    const int32_t F = acgt_floor(a.ix, (uint32_t)(dL + pa), min(dL, dR));
     unsigned long long s = 0ull;
     if (D) {
         while (pos - 1 > F && sym_at(a.ix.ref_words, (uint32_t)(pos - 1)) == sym_at(a.ix.ref_words, (uint32_t)(pos + D - 1))) --pos;
     } else {
-        for (int32_t i = 0; i < I; ++i) s |= (unsigned long long)rp(best_p + i) << (2 * i);
+        for (int32_t i = 0; i < I; ++i) s |= (unsigned long long)rec.at(best_p + i) << (2 * i);
         const unsigned long long smask = I == 32 ? ~0ull : (1ull << (2 * I)) - 1ull;
         while (pos - 1 > F) {
             const unsigned long long last = (s >> (2 * (I - 1))) & 3ull;
@@ -168,26 +155,8 @@ __global__ __launch_bounds__(kIndelBlock) void indel_scan_kernel(IndelArgs a) {
     }
 }
 
-// span[0 .. n) prefix-summed in place (u32 arithmetic wraps: a -1 that precedes its +1 in memory order still cancels).  One workgroup:
-// a thread sums its stretch, the stretches' sums are scanned through LDS, the thread writes its stretch.
-__global__ __launch_bounds__(kPrefixBlock) void indel_span_prefix_kernel(unsigned int* __restrict__ span, uint32_t n) {
-    __shared__ unsigned int part_s[2][kPrefixBlock];
-    const uint32_t per = (n + kPrefixBlock - 1) / kPrefixBlock;
-    const uint32_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
-    unsigned int sum = 0u;
-    for (uint32_t i = lo; i < hi; ++i) sum += span[i];
-    part_s[0][threadIdx.x] = sum;
-    __syncthreads();
-    int cur = 0;
-    for (uint32_t off = 1; off < (uint32_t)kPrefixBlock; off <<= 1) {   // inclusive scan of the stretches' sums
-        const unsigned int v = part_s[cur][threadIdx.x] + (threadIdx.x >= off ? part_s[cur][threadIdx.x - off] : 0u);
-        part_s[cur ^ 1][threadIdx.x] = v;
-        __syncthreads();
-        cur ^= 1;
-    }
-    unsigned int acc = part_s[cur][threadIdx.x] - sum;   // what precedes this thread's stretch
-    for (uint32_t i = lo; i < hi; ++i) { acc += span[i]; span[i] = acc; }
-}
+// span[0 .. n) prefix-summed in place by one workgroup (span_prefix_block, bk_anchor.h)
+__global__ __launch_bounds__(kSpanPrefixBlock) void indel_span_prefix_kernel(unsigned int* __restrict__ span, uint32_t n) { span_prefix_block(span, n); }
 
 __global__ __launch_bounds__(kIndelBlock) void indel_report_kernel(IndelArgs a) {
     const uint64_t n_slots = 1ull << a.log2n;
@@ -236,7 +205,7 @@ void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream) {
 }
 
 void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(indel_span_prefix_kernel, dim3(1), dim3(kPrefixBlock), 0, stream, a.span, a.ix.total_cells + 2u);
+    hipLaunchKernelGGL(indel_span_prefix_kernel, dim3(1), dim3(kSpanPrefixBlock), 0, stream, a.span, a.ix.total_cells + 2u);
 }
 
 void launch_indel_report(const IndelArgs& a, hipStream_t stream) {

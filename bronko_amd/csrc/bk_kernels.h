@@ -494,6 +494,26 @@ struct IndelArgs {
 void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream);
 void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_indel_report(const IndelArgs& a, hipStream_t stream);
+// bk_junctions_enable: long deletions and subgenomic-RNA junctions from the reads (bk_junctions.hip; the rule: include/bronko_hip.h,
+// DESIGN.md section J)
+typedef bk_junction_record JunctionRecordDev;
+struct JunctionArgs {
+    RecordsView rec;                     // junction_scan_kernel's batch
+    AnchorIndex ix;
+    uint32_t min_len, max_mismatches;
+    // the sample: event table (one key word pos | D << 32, ~0 = free, {fwd, rev}), span, counters
+    unsigned long long* keys;
+    unsigned int* counts;                // [slots][2]
+    uint32_t log2n;
+    unsigned int* span;                  // [total_cells + 2]
+    unsigned long long* tallies;         // [10] records, anchored, ref_spanning, supporting, short, backward, discordant, candidates, reported, overflow
+    // the report: junction_report_kernel
+    uint64_t min_reads;
+    JunctionRecordDev* rows; uint64_t row_cap;
+};
+void launch_junction_scan(const JunctionArgs& a, int n_cus, hipStream_t stream);
+void launch_junction_span_prefix(const JunctionArgs& a, hipStream_t stream);   // span in place, once per sample
+void launch_junction_report(const JunctionArgs& a, hipStream_t stream);
 // bk_link_enable: which substitutions the same records carry (bk_linkage.hip; the rule: include/bronko_hip.h)
 struct LinkArgs {
     RecordsView rec;                     // link_scan_kernel's batch

@@ -464,6 +464,32 @@ class Engine:
         _check(self._L.bk_sample_download_indel_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
         return span[:self.total_cells]
 
+    def junctions_enable(self, min_len=33, max_mismatches=2, table_log2=16):
+        """bk_junctions_enable: junction_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
+        cfg = None if min_len is None else C.byref(_ffi.JunctionConfig(int(min_len), int(max_mismatches), int(table_log2)))
+        _check(self._L.bk_junctions_enable(self.h, cfg), self._L)
+
+    def sample_junctions(self, min_reads=5):
+        """bk_sample_junctions: the finalized sample's junctions with at least min_reads reads, on the device (asynchronous)."""
+        _check(self._L.bk_sample_junctions(self.h, C.byref(_ffi.JunctionParams(int(min_reads)))), self._L)
+
+    def download_junctions(self, cap=None):
+        """(summary, rows) of sample_junctions: min(cap, summary.reported) rows (cell, len, fwd, rev, span_donor, span_acceptor), all by
+        default, sorted by (cell, len)."""
+        summ = _ffi.JunctionSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_junctions(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        buf = np.zeros((max(1, cap), 6), np.uint32)
+        _check(self._L.bk_sample_download_junctions(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+
+    def download_junction_span(self):
+        """bk_sample_download_junction_span: the prefix-summed span array of all cells (after sample_junctions)."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(self._L.bk_sample_download_junction_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def linkage_enable(self, max_mismatches=8, initial_rows=1 << 16):
         """bk_link_enable: link_scan_kernel runs behind every scan of the samples that begin from now on and keeps a row per placed
         record; max_mismatches=None disables."""

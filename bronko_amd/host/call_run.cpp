@@ -203,6 +203,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--indels: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.junctions) {        // (likewise)
+        LOG_DEBUG(T, "--junctions: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     if (shard_mode && a.linkage) {          // (likewise: a sample's row store is one engine's)
         LOG_DEBUG(T, "--linkage: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
@@ -246,6 +250,8 @@ struct SampleData {
     std::vector<bk_region_depth> rrows;
     bk_indel_summary isumm{};                             // --indels
     std::vector<IndelEvent> indels;
+    bk_junction_summary jsumm{};                          // --junctions
+    std::vector<JunctionEvent> junctions;
     bk_link_summary lsumm{};                              // --linkage
     std::vector<LinkSite> link_recs;
     std::vector<LinkPair> link_pairs;
@@ -260,6 +266,7 @@ struct SampleData {
 constexpr uint32_t kHapTableLog2 = 16, kHapTableLog2Max = 24;   // --haplotypes: the table's first size (768 KB + 2.5 MB of entries); four times as many slots after each that was full
 constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
 constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
+constexpr uint32_t kJunctionTableLog2 = 18;   // --junctions: likewise
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
 struct CallRun {
@@ -310,6 +317,8 @@ struct CallRun {
         if (cfg.region_report()) resolve_regions();
         if (cfg.indels && ix.files.size() != 1)   // (a k-mer's cell in the engine's table is its first among all files, not the selected genome's)
             die(T, "--indels needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.junctions && ix.files.size() != 1)
+            die(T, "--junctions needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.linkage && ix.files.size() != 1)
             die(T, "--linkage needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.codons() && ix.files.size() != 1)
@@ -480,6 +489,10 @@ struct CallRun {
             const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
             hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
         }
+        if (cfg.junctions) {
+            const bk_junction_config jc{cfg.junction.min_len, cfg.junction.max_mismatches, kJunctionTableLog2};
+            hip_check(bk_junctions_enable(e, &jc), "bk_junctions_enable");
+        }
         if (cfg.row_store()) {   // (--codons, --haplotypes and --read-pileup read --linkage's row store; alone each brings its own M, together they are equal)
             const bk_link_config lc{cfg.row_store_mismatches(), kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
@@ -517,6 +530,10 @@ struct CallRun {
         if (cfg.indels) {   // (needs the finalize only: the events that pass the thresholds, a few rows travel)
             const bk_indel_params ip{cfg.indel.min_reads, cfg.indel.min_af_ppm};
             hip_check(bk_sample_indels(e, &ip), "bk_sample_indels");
+        }
+        if (cfg.junctions) {   // (likewise)
+            const bk_junction_params jp{cfg.junction.min_reads};
+            hip_check(bk_sample_junctions(e, &jp), "bk_sample_junctions");
         }
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
@@ -564,6 +581,12 @@ struct CallRun {
             hip_check(bk_sample_download_indels(e, &d.isumm, nullptr, 0), "bk_sample_download_indels");
             d.indels.resize((size_t)d.isumm.reported);
             hip_check(bk_sample_download_indels(e, &d.isumm, reinterpret_cast<bk_indel_record*>(d.indels.data()), d.indels.size()), "bk_sample_download_indels");
+        }
+        if (cfg.junctions) {
+            static_assert(sizeof(JunctionEvent) == sizeof(bk_junction_record), "JunctionEvent is bk_junction_record");
+            hip_check(bk_sample_download_junctions(e, &d.jsumm, nullptr, 0), "bk_sample_download_junctions");
+            d.junctions.resize((size_t)d.jsumm.reported);
+            hip_check(bk_sample_download_junctions(e, &d.jsumm, reinterpret_cast<bk_junction_record*>(d.junctions.data()), d.junctions.size()), "bk_sample_download_junctions");
         }
         if (cfg.linkage) {   // the sites are the sample's own VCF records: counted behind the calls, a few rows travel
             static_assert(sizeof(LinkPair) == sizeof(bk_link_pair), "LinkPair is bk_link_pair");
@@ -670,6 +693,14 @@ struct CallRun {
                                 " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.candidates) + " candidate events, " +
                                 std::to_string(s.reported) + " reported");
                 write_indels_vcf(a.output + "/" + stem + ".indels.vcf", mates[0], ix, best, d.indels, cfg.indel);
+            }
+            if (cfg.junctions) {    // (a sample without events: the headers alone)
+                const bk_junction_summary& s = d.jsumm;
+                LOG_INFO(T, "Junctions: " + std::to_string(s.anchored) + " of " + std::to_string(s.records) + " records anchored, " + std::to_string(s.ref_spanning) +
+                                " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.short_) + " short, " +
+                                std::to_string(s.backward) + " backward, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) +
+                                " candidate junctions, " + std::to_string(s.reported) + " reported");
+                write_junctions_tsv(a.output + "/" + stem + ".junctions.tsv", ix, best, d.junctions, cfg.junction);
             }
             if (cfg.linkage) {      // (a sample without such a pair: the header alone)
                 const uint64_t lines = write_linkage_tsv(a.output + "/" + stem + ".linkage.tsv", ix, best, d.link_recs, d.link_pairs, cfg.link);

@@ -73,7 +73,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
-          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--linkage]\n"
+          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--junctions]\n"
+          "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
           "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
@@ -107,6 +108,13 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --indel-max-mismatches M substitutions a read may have beside its indel; 0..8, default 2\n"
           "  --indel-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
           "  --indel-min-af F         AF an event needs to be written; 0..1, default the value of --min-af\n"
+          "  --junctions       write long deletions and subgenomic-RNA junctions to <DIR>/<stem>.junctions.tsv (an index of one genome\n"
+          "                    file): reads whose two ends lie on diagonals of the reference L or more apart, forward on one strand of\n"
+          "                    one sequence, left-normalised, with the reads that support each, the reads that span its donor and\n"
+          "                    acceptor side unbroken, freq = reads / (reads + span_donor) and the microhomology of its flanks\n"
+          "  --junction-min-len L        shortest jump counted; at least 1, default 33 (where --indels ends)\n"
+          "  --junction-max-mismatches M substitutions a read may have beside its junction; 0..8, default 2\n"
+          "  --junction-min-reads N      supporting reads a junction needs to be written; at least 1, default 5\n"
           "  --linkage         write to <DIR>/<stem>.linkage.tsv, per pair of the sample's substitutions (an index of one genome file), how\n"
           "                    many of the reads that cover both positions carry neither, the first, the second or both\n"
           "  --link-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8\n"
@@ -267,6 +275,17 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--indel-max-len") { a.indel_max_len = x; a.has_indel_max_len = true; }
             else if (opt == "--indel-max-mismatches") { a.indel_max_mismatches = x; a.has_indel_max_mismatches = true; }
             else { a.indel_min_reads = x; a.has_indel_min_reads = true; }
+        }
+        else if (opt == "--junctions") a.junctions = true;
+        else if (opt == "--junction-min-len" || opt == "--junction-max-mismatches" || opt == "--junction-min-reads") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--junction-min-len") { a.junction_min_len = x; a.has_junction_min_len = true; }
+            else if (opt == "--junction-max-mismatches") { a.junction_max_mismatches = x; a.has_junction_max_mismatches = true; }
+            else { a.junction_min_reads = x; a.has_junction_min_reads = true; }
         }
         else if (opt == "--linkage") a.linkage = true;
         else if (opt == "--link-max-mismatches" || opt == "--link-max-dist" || opt == "--link-min-reads") {   // (any integer here: check_call_args)
@@ -501,6 +520,12 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.indel_max_len < 1 || a.indel_max_len > BK_INDEL_MAX_LEN) die(T, "--indel-max-len must be between 1 and " + std::to_string(BK_INDEL_MAX_LEN) + ", got " + std::to_string(a.indel_max_len));
     if (a.indel_max_mismatches < 0 || a.indel_max_mismatches > 8) die(T, "--indel-max-mismatches must be between 0 and 8, got " + std::to_string(a.indel_max_mismatches));
     if (a.indel_min_reads < 1) die(T, "--indel-min-reads must be at least 1, got " + std::to_string(a.indel_min_reads));
+    if (a.has_junction_min_len && !a.junctions) die(T, "--junction-min-len needs --junctions");
+    if (a.has_junction_max_mismatches && !a.junctions) die(T, "--junction-max-mismatches needs --junctions");
+    if (a.has_junction_min_reads && !a.junctions) die(T, "--junction-min-reads needs --junctions");
+    if (a.junction_min_len < 1 || a.junction_min_len > (long)kJunctionMaxLen) die(T, "--junction-min-len must be between 1 and " + std::to_string(kJunctionMaxLen) + ", got " + std::to_string(a.junction_min_len));
+    if (a.junction_max_mismatches < 0 || a.junction_max_mismatches > kJunctionMaxMismatches) die(T, "--junction-max-mismatches must be between 0 and 8, got " + std::to_string(a.junction_max_mismatches));
+    if (a.junction_min_reads < 1) die(T, "--junction-min-reads must be at least 1, got " + std::to_string(a.junction_min_reads));
     if (a.has_link_max_mismatches && !a.linkage) die(T, "--link-max-mismatches needs --linkage");
     if (a.has_link_max_dist && !a.linkage) die(T, "--link-max-dist needs --linkage");
     if (a.has_link_min_reads && !a.linkage) die(T, "--link-min-reads needs --linkage");
@@ -593,6 +618,9 @@ CallConfig make_call_config(const Args& a) {
     }
     if (a.has_region_window) c.region_window = (uint64_t)a.region_window;
     c.region_min_depth = (uint64_t)a.region_min_depth;
+    c.junctions = a.junctions;
+    c.junction.min_len = (uint32_t)a.junction_min_len; c.junction.max_mismatches = (uint32_t)a.junction_max_mismatches;
+    c.junction.min_reads = (uint64_t)a.junction_min_reads;
     c.indels = a.indels;
     c.indel.max_len = (uint32_t)a.indel_max_len; c.indel.max_mismatches = (uint32_t)a.indel_max_mismatches;
     c.indel.min_reads = (uint64_t)a.indel_min_reads;

@@ -12,6 +12,7 @@
 #include "codons.hpp"
 #include "haplotypes.hpp"
 #include "indels.hpp"
+#include "junctions.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
 #include "read_pileup.hpp"
@@ -70,6 +71,11 @@ struct Args {
     long indel_max_mismatches = 2;  // --indel-max-mismatches: substitutions a record may have beside its indel (0..8)
     long indel_min_reads = 5;       // --indel-min-reads: supporting records an event needs
     double indel_min_af = 0.03;     // --indel-min-af: support / (support + reference-spanning records) an event needs (default: --min-af)
+    bool junctions = false;         // --junctions: <DIR>/<stem>.junctions.tsv, long deletions and subgenomic-RNA junctions from the reads
+    bool has_junction_min_len = false, has_junction_max_mismatches = false, has_junction_min_reads = false;
+    long junction_min_len = 33;     // --junction-min-len: shortest jump counted as a junction (with 33 it begins where --indels ends)
+    long junction_max_mismatches = 2;   // --junction-max-mismatches: substitutions a record may have beside its junction (0..8)
+    long junction_min_reads = 5;    // --junction-min-reads: supporting records a junction needs
     bool linkage = false;           // --linkage: <DIR>/<stem>.linkage.tsv, which of the sample's substitutions the same reads carry
     bool has_link_max_mismatches = false, has_link_max_dist = false, has_link_min_reads = false;
     long link_max_mismatches = 8;   // --link-max-mismatches: substitutions a placed record may have (0..8)
@@ -128,6 +134,9 @@ struct CallConfig {
     // --indels: bk_indels_enable / bk_sample_indels and the values the .indels.vcf header prints
     bool indels = false;
     IndelParams indel;
+    // --junctions: bk_junctions_enable / bk_sample_junctions and the values the .junctions.tsv header prints
+    bool junctions = false;
+    JunctionParams junction;
     // --linkage: bk_link_enable / bk_sample_linkage and the values the .linkage.tsv header prints
     bool linkage = false;
     LinkParams link;

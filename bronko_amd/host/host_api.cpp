@@ -12,6 +12,7 @@
 #include "codons.hpp"
 #include "haplotypes.hpp"
 #include "indels.hpp"
+#include "junctions.hpp"
 #include "linkage.hpp"
 #include "index.hpp"
 #include "read_pileup.hpp"
@@ -288,6 +289,36 @@ int bh_write_indels_vcf(const void* h, int file_id, const char* path, const char
         p.max_len = max_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_af_ppm = min_af_ppm;
         bronko::write_indels_vcf(path, reads_path ? reads_path : "", *static_cast<const bronko::Index*>(h), file_id,
                                  std::vector<bronko::IndelEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --junctions: the host twin of the engine's junction pass (junctions.cpp) ----------------------------------------
+// reads joined by '\n'; rows as bk_junction_record (= bronko::JunctionEvent), at most cap written, *n their number; span: NULL or
+// [total_cells], prefix-summed; counters = {records, anchored, ref_spanning, supporting, short, backward, discordant}
+int bh_junction_events(const void* h, int file_id, const char* reads, uint32_t min_len, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span,
+                       uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::JunctionEvent) == 24, "JunctionEvent is bk_junction_record");
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const bronko::JunctionResult r = bronko::junction_events(*ix, file_id, split_lines(reads), min_len, max_mismatches);
+        *n = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::JunctionEvent));
+        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+        if (counters) {
+            const uint64_t c[7] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.backward, r.n.discordant};
+            std::memcpy(counters, c, sizeof c);
+        }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_junctions_tsv(const void* h, int file_id, const char* path, const void* rows, uint64_t n, uint32_t min_len, uint32_t max_mismatches, uint64_t min_reads) {
+    try {
+        const auto* ev = static_cast<const bronko::JunctionEvent*>(rows);
+        bronko::JunctionParams p;
+        p.min_len = min_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads;
+        bronko::write_junctions_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::JunctionEvent>(ev, ev + n), p);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -347,6 +347,45 @@ def write_indels_vcf(path, ix, file_id, reads_path, rows, max_len=32, max_mismat
         raise _host_error(L)
 
 
+def _junction_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_junctions_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_junction_events.restype = C.c_int
+        L.bh_junction_events.argtypes = [vp, C.c_int, C.c_char_p, u32, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
+        L.bh_write_junctions_tsv.restype = C.c_int
+        L.bh_write_junctions_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, u64]
+        L._junctions_ready = True
+    return L
+
+
+def junction_events(ix, file_id, reads, min_len=33, max_mismatches=2):
+    """The host twin of the engine's junction pass (junctions.cpp junction_events) over ASCII reads: (rows of the whole table as
+    bk_junction_record (cell, len, fwd, rev, span_donor, span_acceptor) sorted by (cell, len), the prefix-summed span array of all
+    cells, (records, anchored, ref_spanning, supporting, short, backward, discordant))."""
+    L = _junction_lib()
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    span = np.zeros(max(1, ix.total_cells), np.uint32)
+    counters = np.zeros(7, np.uint64)
+    if L.bh_junction_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
+        raise _host_error(L)
+    rec = np.zeros((max(1, n.value), 6), np.uint32)
+    if L.bh_junction_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
+        raise _host_error(L)
+    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+
+
+def write_junctions_tsv(path, ix, file_id, rows, min_len=33, max_mismatches=2, min_reads=5):
+    """The --junctions writer (junctions.cpp write_junctions_tsv): rows as junction_events gives them, already filtered."""
+    rec = np.zeros((max(1, len(rows)), 6), np.uint32)
+    for i, r in enumerate(rows):
+        rec[i] = r
+    L = _junction_lib()
+    if L.bh_write_junctions_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(min_len), int(max_mismatches), int(min_reads)) != 0:
+        raise _host_error(L)
+
+
 def _link_lib():
     L = _caller_lib()
     if not hasattr(L, "_linkage_ready"):

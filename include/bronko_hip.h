@@ -500,6 +500,53 @@ int  bk_sample_indels(bk_engine* e, const bk_indel_params* p);
 int  bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap);
 int  bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap);
 
+/* ---- long deletions and subgenomic-RNA junctions from the reads (`bronko call --junctions`; additive, still v8) ---------------
+ * A read whose two ends lie on diagonals more than BK_INDEL_MAX_LEN apart is `discordant` to bk_indels_enable and dropped there.
+ * Such reads are the leader-body junctions of subgenomic RNAs, the internal deletions of defective genomes, any long deletion.
+ * A pass of its own over each batch's records (junction_scan_kernel, behind the scan of the same records) counts them.  The rule,
+ * all of it integer arithmetic, in bk_indels_enable's terms:
+ *   unit, anchor k-mer, anchors, r', a, b, c_a, c_b, dL, dR, delta   exactly as under bk_indels_enable: a record of n < 2k is
+ *              counted in `records` and otherwise ignored; a record with both anchors on one strand and a + k <= b is `anchored`.
+ *   ignored    without a tally, before anything else is asked of delta: the two anchors in different sequences; the cells
+ *              [min(dL, dR), max(dL, dR) + n) leave that sequence or hold a letter that is not ACGT (so a junction across a run
+ *              of N of the reference is not found).
+ *   delta = 0  m = Hamming(r', ref[dL, dL + n)).  m <= max_mismatches: the record is `ref_spanning` for the sites dL + a + k ..
+ *              dL + b: +1 at cell dL + a + k, -1 at cell dL + b + 1 of the pass's own difference array `span` (not
+ *              bk_indels_enable's: either feature works without the other).  Else `discordant`.
+ *   0 < |delta| < min_len   counted `short`, nothing else: bk_indels_enable reports those.
+ *   delta <= -min_len       counted `backward`, nothing else (duplications and copy-backs are not looked for).
+ *   delta >= min_len        a junction of D = delta.  For p in [a + k, b]: m(p) = #{j < p: r'[j] != ref[dL + j]} + #{j >= p: r'[j]
+ *              != ref[dR + j]}; the smallest p that minimises m(p); m(p) > max_mismatches: `discordant`.  pos = dL + p, F as in
+ *              the indel rule.  While pos - 1 > F and ref[pos - 1] = ref[pos + D - 1]: pos -= 1.  Event (pos, D): the cells
+ *              [pos, pos + D) are left out.  The record is `supporting`: fwd along the reference, rev against it.
+ *   per event  reads = fwd + rev; span_donor = the prefix sum of span at pos, span_acceptor = at pos + D.  Reported iff reads >=
+ *              min_reads.  Both mate files add into one table and one span array.
+ *   bk_junctions_enable        as bk_indels_enable: between samples (BK_ERR_STATE inside one); NULL disables and frees.  min_len
+ *                              1..2^27 - 1, max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window
+ *                              (BK_ERR_INVALID otherwise) and a genome of k to 2^27 - 1 positions (BK_ERR_UNSUPPORTED otherwise).
+ *                              Allocates all the feature needs (the event table of 2^table_log2 slots, as many rows, span; the
+ *                              anchor tables are shared with bk_indels_enable and bk_link_enable); an engine that never enables it
+ *                              allocates and launches nothing.  Per engine: forks set their own.  A sample that began before the
+ *                              call has no events.
+ *   bk_sample_junctions        after the sample's bk_sample_finalize: BK_ERR_STATE inside a sample, before any finalize, and when
+ *                              the feature was not enabled as the sample began; BK_ERR_INVALID for min_reads == 0.  Prefix-sums
+ *                              span, selects the rows; asynchronous on the engine's stream; may be repeated with other parameters.
+ *   bk_sample_download_junctions   synchronises; copies min(cap, reported) rows in no particular order (records may be NULL).
+ *                              `candidates` = the distinct events of the sample.  A table that met more of them than it holds
+ *                              loses nothing silently: overflow = 1 in the summary and BK_ERR_INVALID ("more than 2^n distinct
+ *                              candidate junctions").
+ *   bk_sample_download_junction_span   the prefix-summed span array of all cells (cap >= bk_total_cells, BK_ERR_INVALID otherwise).
+ * bk_junction_record: cell = pos, the first cell left out; len = D; the read continues at cell pos + D. */
+#define BK_JUNCTION_MAX_LEN 134217727u   /* 2^27 - 1 */
+typedef struct { uint32_t min_len, max_mismatches, table_log2; } bk_junction_config;   /* table_log2 10..24 */
+typedef struct { uint64_t min_reads; } bk_junction_params;
+typedef struct { uint32_t cell, len, fwd, rev, span_donor, span_acceptor; } bk_junction_record;
+typedef struct { uint64_t records, anchored, ref_spanning, supporting, short_, backward, discordant, candidates, reported; int32_t overflow; } bk_junction_summary;
+int  bk_junctions_enable(bk_engine* e, const bk_junction_config* cfg);
+int  bk_sample_junctions(bk_engine* e, const bk_junction_params* p);
+int  bk_sample_download_junctions(bk_engine* e, bk_junction_summary* summary, bk_junction_record* records, uint64_t cap);
+int  bk_sample_download_junction_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
 /* ---- which substitutions the same reads carry (`bronko call --linkage`; additive, still v8) -------------------------------------
  * The pileup says how often each substitution occurs, not whether two of them sit on the same molecules.  The reads say it: a pass
  * of its own over each batch's records (link_scan_kernel, behind the scan of the same records) keeps, per record that can be placed
