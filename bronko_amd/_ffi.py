@@ -88,6 +88,19 @@ class JunctionSummary(C.Structure):  # bk_junction_summary
                 ("backward", C.c_uint64), ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class CopybackConfig(C.Structure):  # bk_copyback_config
+    _fields_ = [("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
+class CopybackParams(C.Structure):  # bk_copyback_params
+    _fields_ = [("min_reads", C.c_uint64), ("min_dist", C.c_uint32)]
+
+
+class CopybackSummary(C.Structure):  # bk_copyback_summary
+    _fields_ = [("records", C.c_uint64), ("same_strand", C.c_uint64), ("ref_spanning", C.c_uint64), ("switched", C.c_uint64), ("supporting", C.c_uint64),
+                ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
+
+
 class CodonSummary(C.Structure):  # bk_codon_summary
     _fields_ = [("rows", C.c_uint64), ("n_codons", C.c_uint64), ("n_regions", C.c_uint32)]
 
@@ -136,6 +149,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_junctions_enable", "bk_sample_junctions", "bk_sample_download_junctions", "bk_sample_download_junction_span",
+           "bk_copybacks_enable", "bk_sample_copybacks", "bk_sample_download_copybacks", "bk_sample_download_copyback_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
            "bk_sample_read_pileup", "bk_sample_download_read_pileup",
@@ -282,6 +296,14 @@ def load(testing=None):
     L.bk_sample_download_junctions.argtypes = [vp, C.POINTER(JunctionSummary), vp, u64]
     L.bk_sample_download_junction_span.restype = C.c_int
     L.bk_sample_download_junction_span.argtypes = [vp, vp, u64]
+    L.bk_copybacks_enable.restype = C.c_int
+    L.bk_copybacks_enable.argtypes = [vp, C.POINTER(CopybackConfig)]
+    L.bk_sample_copybacks.restype = C.c_int
+    L.bk_sample_copybacks.argtypes = [vp, C.POINTER(CopybackParams)]
+    L.bk_sample_download_copybacks.restype = C.c_int
+    L.bk_sample_download_copybacks.argtypes = [vp, C.POINTER(CopybackSummary), vp, u64]
+    L.bk_sample_download_copyback_span.restype = C.c_int
+    L.bk_sample_download_copyback_span.argtypes = [vp, vp, u64]
     L.bk_link_enable.restype = C.c_int
     L.bk_link_enable.argtypes = [vp, C.POINTER(LinkConfig)]
     L.bk_sample_linkage.restype = C.c_int

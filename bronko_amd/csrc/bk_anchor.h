@@ -1,5 +1,5 @@
 // bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip), junction_scan_kernel
-// (bk_junctions.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+// (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
 //
 // What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
 // log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
@@ -84,23 +84,36 @@ struct Anchors {
     int32_t pa, pb;        // the anchors' offsets a < b in r'
     uint32_t ca, cb;       // their cells
 };
-// the first anchor k-mer from each end of a record of n >= 2k bases (offsets 0, 8, 16, 24 from either end), both on one strand,
-// a + k <= b
-__device__ __forceinline__ bool anchors_of(const AnchorIndex& a, const uint32_t* __restrict__ w, int32_t n, Anchors& out) {
+// A record's two end anchors as they are found, the record as packed (copyback_scan_kernel needs them on either strand)
+struct EndAnchors {
+    int32_t f_off, b_off;  // the front and the back anchor's offsets in the record
+    uint32_t f_cell, b_cell;   // the first cells of their reference k-mers
+    bool f_ag, b_ag;       // each: against the reference
+};
+// the first anchor k-mer from each end of a record of n >= 2k bases (offsets 0, 8, 16, 24 from either end)
+__device__ __forceinline__ bool end_anchors(const AnchorIndex& a, const uint32_t* __restrict__ w, int32_t n, EndAnchors& e) {
     const int32_t k = a.k;
-    int32_t f_off = -1, b_off = -1;
-    uint32_t f_cell = 0, b_cell = 0;
-    bool f_ag = false, b_ag = false;
+    e.f_off = -1; e.b_off = -1;
+    e.f_cell = 0; e.b_cell = 0;
+    e.f_ag = false; e.b_ag = false;
     for (int32_t o = 0; o <= 24 && o + k <= n; o += 8)
-        if (anchor_at(a, w, (uint32_t)o, &f_cell, &f_ag)) { f_off = o; break; }
-    if (f_off < 0) return false;
+        if (anchor_at(a, w, (uint32_t)o, &e.f_cell, &e.f_ag)) { e.f_off = o; break; }
+    if (e.f_off < 0) return false;
     for (int32_t o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (anchor_at(a, w, (uint32_t)o, &b_cell, &b_ag)) { b_off = o; break; }
-    if (b_off < 0 || f_ag != b_ag) return false;
-    out.against = f_ag;
-    out.pa = f_ag ? n - k - b_off : f_off; out.pb = f_ag ? n - k - f_off : b_off;   // offsets in r'
-    out.ca = f_ag ? b_cell : f_cell; out.cb = f_ag ? f_cell : b_cell;
+        if (anchor_at(a, w, (uint32_t)o, &e.b_cell, &e.b_ag)) { e.b_off = o; break; }
+    return e.b_off >= 0;
+}
+// the two end anchors on one strand, oriented along the reference: a + k <= b
+__device__ __forceinline__ bool anchors_of(const EndAnchors& e, int32_t k, int32_t n, Anchors& out) {
+    if (e.f_ag != e.b_ag) return false;
+    out.against = e.f_ag;
+    out.pa = e.f_ag ? n - k - e.b_off : e.f_off; out.pb = e.f_ag ? n - k - e.f_off : e.b_off;   // offsets in r'
+    out.ca = e.f_ag ? e.b_cell : e.f_cell; out.cb = e.f_ag ? e.f_cell : e.b_cell;
     return out.pa + k <= out.pb;
+}
+__device__ __forceinline__ bool anchors_of(const AnchorIndex& a, const uint32_t* __restrict__ w, int32_t n, Anchors& out) {
+    EndAnchors e;
+    return end_anchors(a, w, n, e) && anchors_of(e, a.k, n, out);
 }
 // both anchors in one sequence, the cells [lo, hi) inside it and holding ACGT only
 __device__ __forceinline__ bool cells_placed(const AnchorIndex& a, uint32_t ca, uint32_t cb, int32_t lo, int32_t hi) {

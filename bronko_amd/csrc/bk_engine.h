@@ -243,7 +243,7 @@ struct Regions {
 };
 
 // What placing a record by two anchor k-mers reads beside the index tables (bk_anchor.h): built by the first of bk_indels_enable,
-// bk_junctions_enable and bk_link_enable, used by all of them, freed with the last
+// bk_junctions_enable, bk_copybacks_enable and bk_link_enable, used by all of them, freed with the last
 struct AnchorTables {
     DevBuf<uint32_t> unique_bits;           // one bit per reference k-mer id: it starts at exactly one cell (a histogram of id_at)
     DevBuf<uint32_t> seq_lo;                // [sequences + 1] first cells, then total_cells
@@ -347,6 +347,22 @@ struct Junctions {
     DevBuf<bk_junction_record> rows;        // [2^table_log2]
     bool in_sample = false;                 // enabled when the current / last sample began
     bool summed = false;                    // span is prefix-summed (this sample's bk_sample_junctions ran)
+    bool made = false;                      // ... and the rows are this sample's
+    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
+    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+};
+
+// bk_copybacks_enable: the same for copyback_scan_kernel (bk_copybacks.hip) -- its own event table, span array, tallies and rows
+struct Copybacks {
+    bk_copyback_config cfg{};
+    std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable, bk_junctions_enable and bk_link_enable
+    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word lo | kind << 31 | hi << 32 (~0 = free)
+    DevBuf<unsigned int> counts;            // [2^table_log2][2] lo_first, hi_first
+    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_copybacks
+    DevBuf<unsigned long long> tallies;     // [9] bk_kernels.h CopybackArgs::tallies
+    DevBuf<bk_copyback_record> rows;        // [2^table_log2]
+    bool in_sample = false;                 // enabled when the current / last sample began
+    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_copybacks ran)
     bool made = false;                      // ... and the rows are this sample's
     int begin_sample(bk_engine* e);         // (bk_riders.cpp)
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records
@@ -571,8 +587,9 @@ struct bk_engine {
     bool regions_made = false;              // bk_sample_region_depths ran for the current sample and table
     std::unique_ptr<Indels> indels;         // bk_indels_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Junctions> junctions;   // bk_junctions_enable (null: no table, no launch, no buffers)
+    std::unique_ptr<Copybacks> copybacks;   // bk_copybacks_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Linkage> linkage;       // bk_link_enable (null: no row store, no launch, no buffers)
-    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the three features holds them
+    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the four features holds them
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

@@ -514,6 +514,26 @@ struct JunctionArgs {
 void launch_junction_scan(const JunctionArgs& a, int n_cus, hipStream_t stream);
 void launch_junction_span_prefix(const JunctionArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_junction_report(const JunctionArgs& a, hipStream_t stream);
+// bk_copybacks_enable: strand-switch (copy-back, snap-back) junctions from the reads (bk_copybacks.hip; the rule: include/bronko_hip.h,
+// DESIGN.md section B)
+typedef bk_copyback_record CopybackRecordDev;
+struct CopybackArgs {
+    RecordsView rec;                     // copyback_scan_kernel's batch
+    AnchorIndex ix;
+    uint32_t max_mismatches;
+    // the sample: event table (one key word lo | kind << 31 | hi << 32, ~0 = free, {lo_first, hi_first}), span, counters
+    unsigned long long* keys;
+    unsigned int* counts;                // [slots][2]
+    uint32_t log2n;
+    unsigned int* span;                  // [total_cells + 2]
+    unsigned long long* tallies;         // [9] records, same_strand, ref_spanning, switched, supporting, discordant, candidates, reported, overflow
+    // the report: copyback_report_kernel
+    uint64_t min_reads; uint32_t min_dist;
+    CopybackRecordDev* rows; uint64_t row_cap;
+};
+void launch_copyback_scan(const CopybackArgs& a, int n_cus, hipStream_t stream);
+void launch_copyback_span_prefix(const CopybackArgs& a, hipStream_t stream);   // span in place, once per sample
+void launch_copyback_report(const CopybackArgs& a, hipStream_t stream);
 // bk_link_enable: which substitutions the same records carry (bk_linkage.hip; the rule: include/bronko_hip.h)
 struct LinkArgs {
     RecordsView rec;                     // link_scan_kernel's batch

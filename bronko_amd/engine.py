@@ -490,6 +490,34 @@ class Engine:
         _check(self._L.bk_sample_download_junction_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
         return span[:self.total_cells]
 
+    def copybacks_enable(self, max_mismatches=2, table_log2=16):
+        """bk_copybacks_enable: copyback_scan_kernel runs behind every scan of the samples that begin from now on; max_mismatches=None
+        disables."""
+        cfg = None if max_mismatches is None else C.byref(_ffi.CopybackConfig(int(max_mismatches), int(table_log2)))
+        _check(self._L.bk_copybacks_enable(self.h, cfg), self._L)
+
+    def sample_copybacks(self, min_reads=5, min_dist=0):
+        """bk_sample_copybacks: the finalized sample's copy-backs with at least min_reads reads and hi - lo >= min_dist, on the device
+        (asynchronous)."""
+        _check(self._L.bk_sample_copybacks(self.h, C.byref(_ffi.CopybackParams(int(min_reads), int(min_dist)))), self._L)
+
+    def download_copybacks(self, cap=None):
+        """(summary, rows) of sample_copybacks: min(cap, summary.reported) rows (lo, hi, kind, lo_first, hi_first, span_lo, span_hi, 0),
+        all by default, sorted."""
+        summ = _ffi.CopybackSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_copybacks(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        buf = np.zeros((max(1, cap), 8), np.uint32)
+        _check(self._L.bk_sample_download_copybacks(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+
+    def download_copyback_span(self):
+        """bk_sample_download_copyback_span: the prefix-summed span array of all cells (after sample_copybacks)."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(self._L.bk_sample_download_copyback_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def linkage_enable(self, max_mismatches=8, initial_rows=1 << 16):
         """bk_link_enable: link_scan_kernel runs behind every scan of the samples that begin from now on and keeps a row per placed
         record; max_mismatches=None disables."""

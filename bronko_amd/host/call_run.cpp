@@ -207,6 +207,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--junctions: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.copybacks) {        // (likewise)
+        LOG_DEBUG(T, "--copybacks: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     if (shard_mode && a.linkage) {          // (likewise: a sample's row store is one engine's)
         LOG_DEBUG(T, "--linkage: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
@@ -252,6 +256,8 @@ struct SampleData {
     std::vector<IndelEvent> indels;
     bk_junction_summary jsumm{};                          // --junctions
     std::vector<JunctionEvent> junctions;
+    bk_copyback_summary cbsumm{};                         // --copybacks
+    std::vector<CopybackEvent> copybacks;
     bk_link_summary lsumm{};                              // --linkage
     std::vector<LinkSite> link_recs;
     std::vector<LinkPair> link_pairs;
@@ -267,6 +273,7 @@ constexpr uint32_t kHapTableLog2 = 16, kHapTableLog2Max = 24;   // --haplotypes:
 constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
 constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
 constexpr uint32_t kJunctionTableLog2 = 18;   // --junctions: likewise
+constexpr uint32_t kCopybackTableLog2 = 18;   // --copybacks: likewise
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
 struct CallRun {
@@ -319,6 +326,8 @@ struct CallRun {
             die(T, "--indels needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.junctions && ix.files.size() != 1)
             die(T, "--junctions needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.copybacks && ix.files.size() != 1)
+            die(T, "--copybacks needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.linkage && ix.files.size() != 1)
             die(T, "--linkage needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.codons() && ix.files.size() != 1)
@@ -493,6 +502,10 @@ struct CallRun {
             const bk_junction_config jc{cfg.junction.min_len, cfg.junction.max_mismatches, kJunctionTableLog2};
             hip_check(bk_junctions_enable(e, &jc), "bk_junctions_enable");
         }
+        if (cfg.copybacks) {
+            const bk_copyback_config cc{cfg.copyback.max_mismatches, kCopybackTableLog2};
+            hip_check(bk_copybacks_enable(e, &cc), "bk_copybacks_enable");
+        }
         if (cfg.row_store()) {   // (--codons, --haplotypes and --read-pileup read --linkage's row store; alone each brings its own M, together they are equal)
             const bk_link_config lc{cfg.row_store_mismatches(), kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
@@ -534,6 +547,10 @@ struct CallRun {
         if (cfg.junctions) {   // (likewise)
             const bk_junction_params jp{cfg.junction.min_reads};
             hip_check(bk_sample_junctions(e, &jp), "bk_sample_junctions");
+        }
+        if (cfg.copybacks) {   // (likewise)
+            const bk_copyback_params cp{cfg.copyback.min_reads, cfg.copyback.min_dist};
+            hip_check(bk_sample_copybacks(e, &cp), "bk_sample_copybacks");
         }
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
@@ -587,6 +604,12 @@ struct CallRun {
             hip_check(bk_sample_download_junctions(e, &d.jsumm, nullptr, 0), "bk_sample_download_junctions");
             d.junctions.resize((size_t)d.jsumm.reported);
             hip_check(bk_sample_download_junctions(e, &d.jsumm, reinterpret_cast<bk_junction_record*>(d.junctions.data()), d.junctions.size()), "bk_sample_download_junctions");
+        }
+        if (cfg.copybacks) {
+            static_assert(sizeof(CopybackEvent) == sizeof(bk_copyback_record), "CopybackEvent is bk_copyback_record");
+            hip_check(bk_sample_download_copybacks(e, &d.cbsumm, nullptr, 0), "bk_sample_download_copybacks");
+            d.copybacks.resize((size_t)d.cbsumm.reported);
+            hip_check(bk_sample_download_copybacks(e, &d.cbsumm, reinterpret_cast<bk_copyback_record*>(d.copybacks.data()), d.copybacks.size()), "bk_sample_download_copybacks");
         }
         if (cfg.linkage) {   // the sites are the sample's own VCF records: counted behind the calls, a few rows travel
             static_assert(sizeof(LinkPair) == sizeof(bk_link_pair), "LinkPair is bk_link_pair");
@@ -701,6 +724,14 @@ struct CallRun {
                                 std::to_string(s.backward) + " backward, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) +
                                 " candidate junctions, " + std::to_string(s.reported) + " reported");
                 write_junctions_tsv(a.output + "/" + stem + ".junctions.tsv", ix, best, d.junctions, cfg.junction);
+            }
+            if (cfg.copybacks) {    // (a sample without events: the headers alone)
+                const bk_copyback_summary& s = d.cbsumm;
+                LOG_INFO(T, "Copy-backs: " + std::to_string(s.records) + " records, " + std::to_string(s.same_strand) + " on one strand, " +
+                                std::to_string(s.ref_spanning) + " reference-spanning, " + std::to_string(s.switched) + " switched, " + std::to_string(s.supporting) +
+                                " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate copy-backs, " +
+                                std::to_string(s.reported) + " reported");
+                write_copybacks_tsv(a.output + "/" + stem + ".copybacks.tsv", ix, best, d.copybacks, cfg.copyback);
             }
             if (cfg.linkage) {      // (a sample without such a pair: the header alone)
                 const uint64_t lines = write_linkage_tsv(a.output + "/" + stem + ".linkage.tsv", ix, best, d.link_recs, d.link_pairs, cfg.link);

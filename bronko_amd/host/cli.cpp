@@ -74,7 +74,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--junctions]\n"
-          "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--linkage]\n"
+          "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--copybacks]\n"
+          "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
           "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
@@ -115,6 +116,14 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --junction-min-len L        shortest jump counted; at least 1, default 33 (where --indels ends)\n"
           "  --junction-max-mismatches M substitutions a read may have beside its junction; 0..8, default 2\n"
           "  --junction-min-reads N      supporting reads a junction needs to be written; at least 1, default 5\n"
+          "  --copybacks       write strand-switch (copy-back, snap-back) junctions to <DIR>/<stem>.copybacks.tsv (an index of one genome\n"
+          "                    file): reads whose front lies on one strand of a sequence and whose back on the other, by kind (H: both\n"
+          "                    arms below the turn, T: both above) and the two cells of the turn, normalised, with the reads that\n"
+          "                    support each, the reads that span either cell unbroken, freq = reads / (reads + the larger span) and\n"
+          "                    the homology of the turn\n"
+          "  --copyback-max-mismatches M substitutions a read may have beside its turn; 0..8, default 2\n"
+          "  --copyback-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
+          "  --copyback-min-dist D       cells the two breakpoints must lie apart; at least 0, default 0 (hairpins too)\n"
           "  --linkage         write to <DIR>/<stem>.linkage.tsv, per pair of the sample's substitutions (an index of one genome file), how\n"
           "                    many of the reads that cover both positions carry neither, the first, the second or both\n"
           "  --link-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8\n"
@@ -286,6 +295,17 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--junction-min-len") { a.junction_min_len = x; a.has_junction_min_len = true; }
             else if (opt == "--junction-max-mismatches") { a.junction_max_mismatches = x; a.has_junction_max_mismatches = true; }
             else { a.junction_min_reads = x; a.has_junction_min_reads = true; }
+        }
+        else if (opt == "--copybacks") a.copybacks = true;
+        else if (opt == "--copyback-max-mismatches" || opt == "--copyback-min-reads" || opt == "--copyback-min-dist") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--copyback-max-mismatches") { a.copyback_max_mismatches = x; a.has_copyback_max_mismatches = true; }
+            else if (opt == "--copyback-min-reads") { a.copyback_min_reads = x; a.has_copyback_min_reads = true; }
+            else { a.copyback_min_dist = x; a.has_copyback_min_dist = true; }
         }
         else if (opt == "--linkage") a.linkage = true;
         else if (opt == "--link-max-mismatches" || opt == "--link-max-dist" || opt == "--link-min-reads") {   // (any integer here: check_call_args)
@@ -526,6 +546,12 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.junction_min_len < 1 || a.junction_min_len > (long)kJunctionMaxLen) die(T, "--junction-min-len must be between 1 and " + std::to_string(kJunctionMaxLen) + ", got " + std::to_string(a.junction_min_len));
     if (a.junction_max_mismatches < 0 || a.junction_max_mismatches > kJunctionMaxMismatches) die(T, "--junction-max-mismatches must be between 0 and 8, got " + std::to_string(a.junction_max_mismatches));
     if (a.junction_min_reads < 1) die(T, "--junction-min-reads must be at least 1, got " + std::to_string(a.junction_min_reads));
+    if (a.has_copyback_max_mismatches && !a.copybacks) die(T, "--copyback-max-mismatches needs --copybacks");
+    if (a.has_copyback_min_reads && !a.copybacks) die(T, "--copyback-min-reads needs --copybacks");
+    if (a.has_copyback_min_dist && !a.copybacks) die(T, "--copyback-min-dist needs --copybacks");
+    if (a.copyback_max_mismatches < 0 || a.copyback_max_mismatches > kCopybackMaxMismatches) die(T, "--copyback-max-mismatches must be between 0 and 8, got " + std::to_string(a.copyback_max_mismatches));
+    if (a.copyback_min_reads < 1) die(T, "--copyback-min-reads must be at least 1, got " + std::to_string(a.copyback_min_reads));
+    if (a.copyback_min_dist < 0 || a.copyback_min_dist > 0xffffffffl) die(T, "--copyback-min-dist must be between 0 and 4294967295, got " + std::to_string(a.copyback_min_dist));
     if (a.has_link_max_mismatches && !a.linkage) die(T, "--link-max-mismatches needs --linkage");
     if (a.has_link_max_dist && !a.linkage) die(T, "--link-max-dist needs --linkage");
     if (a.has_link_min_reads && !a.linkage) die(T, "--link-min-reads needs --linkage");
@@ -618,6 +644,9 @@ CallConfig make_call_config(const Args& a) {
     }
     if (a.has_region_window) c.region_window = (uint64_t)a.region_window;
     c.region_min_depth = (uint64_t)a.region_min_depth;
+    c.copybacks = a.copybacks;
+    c.copyback.max_mismatches = (uint32_t)a.copyback_max_mismatches; c.copyback.min_reads = (uint64_t)a.copyback_min_reads;
+    c.copyback.min_dist = (uint32_t)a.copyback_min_dist;
     c.junctions = a.junctions;
     c.junction.min_len = (uint32_t)a.junction_min_len; c.junction.max_mismatches = (uint32_t)a.junction_max_mismatches;
     c.junction.min_reads = (uint64_t)a.junction_min_reads;

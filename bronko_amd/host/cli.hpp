@@ -10,6 +10,7 @@
 #include "../../include/bronko_hip.h"
 #include "caller.hpp"
 #include "codons.hpp"
+#include "copybacks.hpp"
 #include "haplotypes.hpp"
 #include "indels.hpp"
 #include "junctions.hpp"
@@ -76,6 +77,11 @@ struct Args {
     long junction_min_len = 33;     // --junction-min-len: shortest jump counted as a junction (with 33 it begins where --indels ends)
     long junction_max_mismatches = 2;   // --junction-max-mismatches: substitutions a record may have beside its junction (0..8)
     long junction_min_reads = 5;    // --junction-min-reads: supporting records a junction needs
+    bool copybacks = false;         // --copybacks: <DIR>/<stem>.copybacks.tsv, strand-switch (copy-back, snap-back) junctions from the reads
+    bool has_copyback_max_mismatches = false, has_copyback_min_reads = false, has_copyback_min_dist = false;
+    long copyback_max_mismatches = 2;   // --copyback-max-mismatches: substitutions a record may have beside its turn (0..8)
+    long copyback_min_reads = 5;    // --copyback-min-reads: supporting records an event needs
+    long copyback_min_dist = 0;     // --copyback-min-dist: cells an event's two breakpoints must lie apart
     bool linkage = false;           // --linkage: <DIR>/<stem>.linkage.tsv, which of the sample's substitutions the same reads carry
     bool has_link_max_mismatches = false, has_link_max_dist = false, has_link_min_reads = false;
     long link_max_mismatches = 8;   // --link-max-mismatches: substitutions a placed record may have (0..8)
@@ -137,6 +143,9 @@ struct CallConfig {
     // --junctions: bk_junctions_enable / bk_sample_junctions and the values the .junctions.tsv header prints
     bool junctions = false;
     JunctionParams junction;
+    // --copybacks: bk_copybacks_enable / bk_sample_copybacks and the values the .copybacks.tsv header prints
+    bool copybacks = false;
+    CopybackParams copyback;
     // --linkage: bk_link_enable / bk_sample_linkage and the values the .linkage.tsv header prints
     bool linkage = false;
     LinkParams link;

@@ -10,6 +10,7 @@
 
 #include "caller.hpp"
 #include "codons.hpp"
+#include "copybacks.hpp"
 #include "haplotypes.hpp"
 #include "indels.hpp"
 #include "junctions.hpp"
@@ -319,6 +320,35 @@ int bh_write_junctions_tsv(const void* h, int file_id, const char* path, const v
         bronko::JunctionParams p;
         p.min_len = min_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads;
         bronko::write_junctions_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::JunctionEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --copybacks: the host twin of the engine's copy-back pass (copybacks.cpp) ------------------------------------------
+// reads joined by '\n'; rows as bk_copyback_record (= bronko::CopybackEvent), at most cap written, *n their number; span: NULL or
+// [total_cells], prefix-summed; counters = {records, same_strand, ref_spanning, switched, supporting, discordant}
+int bh_copyback_events(const void* h, int file_id, const char* reads, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span, uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::CopybackEvent) == 32, "CopybackEvent is bk_copyback_record");
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const bronko::CopybackResult r = bronko::copyback_events(*ix, file_id, split_lines(reads), max_mismatches);
+        *n = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::CopybackEvent));
+        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+        if (counters) {
+            const uint64_t c[6] = {r.n.records, r.n.same_strand, r.n.ref_spanning, r.n.switched, r.n.supporting, r.n.discordant};
+            std::memcpy(counters, c, sizeof c);
+        }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_copybacks_tsv(const void* h, int file_id, const char* path, const void* rows, uint64_t n, uint32_t max_mismatches, uint64_t min_reads, uint32_t min_dist) {
+    try {
+        const auto* ev = static_cast<const bronko::CopybackEvent*>(rows);
+        bronko::CopybackParams p;
+        p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_dist = min_dist;
+        bronko::write_copybacks_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::CopybackEvent>(ev, ev + n), p);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -514,7 +514,7 @@ int  bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap);
  *              dL + b: +1 at cell dL + a + k, -1 at cell dL + b + 1 of the pass's own difference array `span` (not
  *              bk_indels_enable's: either feature works without the other).  Else `discordant`.
  *   0 < |delta| < min_len   counted `short`, nothing else: bk_indels_enable reports those.
- *   delta <= -min_len       counted `backward`, nothing else (duplications and copy-backs are not looked for).
+ *   delta <= -min_len       counted `backward`, nothing else (duplications are not looked for; copy-backs: bk_copybacks_enable).
  *   delta >= min_len        a junction of D = delta.  For p in [a + k, b]: m(p) = #{j < p: r'[j] != ref[dL + j]} + #{j >= p: r'[j]
  *              != ref[dR + j]}; the smallest p that minimises m(p); m(p) > max_mismatches: `discordant`.  pos = dL + p, F as in
  *              the indel rule.  While pos - 1 > F and ref[pos - 1] = ref[pos + D - 1]: pos -= 1.  Event (pos, D): the cells
@@ -546,6 +546,66 @@ int  bk_junctions_enable(bk_engine* e, const bk_junction_config* cfg);
 int  bk_sample_junctions(bk_engine* e, const bk_junction_params* p);
 int  bk_sample_download_junctions(bk_engine* e, bk_junction_summary* summary, bk_junction_record* records, uint64_t cap);
 int  bk_sample_download_junction_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
+/* ---- strand-switch (copy-back, snap-back) junctions from the reads (`bronko call --copybacks`; additive, still v8) ---------------
+ * bk_indels_enable and bk_junctions_enable follow a read on one strand of the reference; a read whose front anchor lies on one strand
+ * and whose back anchor on the other is not even `anchored` there.  Those reads are the copy-back and snap-back defective genomes
+ * (the polymerase leaves its template and copies the nascent strand back) and the hairpin artefacts of library preparation.  A pass
+ * of its own over each batch's records (copyback_scan_kernel, behind the scan of the same records) counts them.  The rule, all of it
+ * integer arithmetic, in bk_indels_enable's terms:
+ *   unit, anchor k-mer, the offsets tried from each end   exactly as under bk_indels_enable: a record of n < 2k is counted in
+ *              `records` and otherwise ignored.  The record `rec` is taken as packed, not re-oriented: its front anchor is (f, c_f,
+ *              s_f), its back anchor (g, c_g, s_g); c the first cell of the reference k-mer, s "against the reference".  comp is the
+ *              complement.
+ *   s_f == s_g     only what the span needs, exactly as under bk_junctions_enable: r', a, b, dL, dR and the `ignored` conditions are
+ *              that rule's.  A record with a + k <= b is `same_strand`; with delta = 0 and at most max_mismatches mismatches it is
+ *              `ref_spanning`: +1 at cell dL + a + k, -1 at cell dL + b + 1 of this pass's own difference array `span`.  Any other
+ *              same-strand record leaves no trace.
+ *   s_f != s_g and f + k <= g   the record is `switched`.
+ *              kind H (front along, back against): A(j) = c_f - f + j, the base expected at j is ref[A(j)]; B(j) = c_g + k - 1 + g
+ *              - j, the base expected is comp(ref[B(j)]).  The read runs up the reference to a cell and comes back down from
+ *              another: both arms lie at and below their breakpoints.
+ *              kind T (front against, back along): A(j) = c_f + k - 1 + f - j, expected comp(ref[A(j)]); B(j) = c_g - g + j,
+ *              expected ref[B(j)].  Both arms lie at and above their breakpoints.
+ *   ignored    a switched record, without a further tally: c_f and c_g in different sequences; a cell A(j), 0 <= j < g, or a cell
+ *              B(j), f + k <= j < n, leaves that sequence or holds a letter that is not ACGT.  (The arms' own ranges, not the whole
+ *              record's: a copy-back whose arms end at the last cell of a sequence is found.)
+ *   breakpoint for p in [f + k, g]: m(p) = #{j < p: rec[j] != arm A's base} + #{j >= p: rec[j] != arm B's base}; x(p) = A(p - 1),
+ *              y(p) = B(p).  The p that minimises (m(p), min(x(p), y(p)), p) -- the middle term makes a read and its reverse
+ *              complement choose the same pair of cells.  m > max_mismatches: `discordant`.  Else `supporting`, and `lo_first` if
+ *              x <= y at that p, else `hi_first`.
+ *   normalised the pairs (x + t, y - t) that the reference cannot tell apart form a run t0 <= 0 <= t1.  H: the step from (x, y) to
+ *              (x + 1, y - 1) is allowed iff ref[x + 1] = comp(ref[y]); T: iff comp(ref[x]) = ref[y - 1]; the step down is the same
+ *              condition at the lower pair; both cells of every pair stay inside the sequence and hold ACGT.  Of the two extreme
+ *              pairs the one whose smaller cell is smaller (on a tie both are the same two cells); lo = its smaller, hi = its
+ *              larger cell.  Event (kind, lo, hi); homology = t1 - t0 (the writer computes it from the reference).
+ *   per event  reads = lo_first + hi_first.  With S the prefix sum of span: kind H span_lo = S[lo + 1], span_hi = S[hi + 1]; kind T
+ *              span_lo = S[lo], span_hi = S[hi].  Reported iff reads >= min_reads and hi - lo >= min_dist.  Both mate files add
+ *              into one table and one span array.  Same-strand backward jumps stay a tally of bk_junctions_enable.
+ *   bk_copybacks_enable        as bk_junctions_enable: between samples (BK_ERR_STATE inside one); NULL disables and frees.
+ *                              max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window (BK_ERR_INVALID
+ *                              otherwise) and a genome of k to 2^27 - 1 positions (BK_ERR_UNSUPPORTED otherwise).  Allocates all the
+ *                              feature needs (the event table of 2^table_log2 slots, as many rows, span; the anchor tables are shared
+ *                              with bk_indels_enable, bk_junctions_enable and bk_link_enable); an engine that never enables it
+ *                              allocates and launches nothing.  Per engine: forks set their own.  A sample that began before the
+ *                              call has no events.
+ *   bk_sample_copybacks        after the sample's bk_sample_finalize: BK_ERR_STATE inside a sample, before any finalize, and when
+ *                              the feature was not enabled as the sample began; BK_ERR_INVALID for min_reads == 0.  Prefix-sums
+ *                              span, selects the rows; asynchronous on the engine's stream; may be repeated with other parameters.
+ *   bk_sample_download_copybacks   synchronises; copies min(cap, reported) rows in no particular order (records may be NULL).
+ *                              `candidates` = the distinct events of the sample.  A table that met more of them than it holds
+ *                              loses nothing silently: overflow = 1 in the summary and BK_ERR_INVALID ("more than 2^n distinct
+ *                              candidate copy-backs").
+ *   bk_sample_download_copyback_span   the prefix-summed span array of all cells (cap >= bk_total_cells, BK_ERR_INVALID otherwise).
+ * bk_copyback_record: kind 0 = H, 1 = T; the read turns between the cells lo <= hi (hi = lo: a hairpin). */
+typedef struct { uint32_t max_mismatches, table_log2; } bk_copyback_config;   /* 0..8, 10..24 */
+typedef struct { uint64_t min_reads; uint32_t min_dist; } bk_copyback_params;
+typedef struct { uint32_t lo, hi, kind, lo_first, hi_first, span_lo, span_hi, pad; } bk_copyback_record;
+typedef struct { uint64_t records, same_strand, ref_spanning, switched, supporting, discordant, candidates, reported; int32_t overflow; } bk_copyback_summary;
+int  bk_copybacks_enable(bk_engine* e, const bk_copyback_config* cfg);
+int  bk_sample_copybacks(bk_engine* e, const bk_copyback_params* p);
+int  bk_sample_download_copybacks(bk_engine* e, bk_copyback_summary* summary, bk_copyback_record* records, uint64_t cap);
+int  bk_sample_download_copyback_span(bk_engine* e, uint32_t* span, uint64_t cap);
 
 /* ---- which substitutions the same reads carry (`bronko call --linkage`; additive, still v8) -------------------------------------
  * The pileup says how often each substitution occurs, not whether two of them sit on the same molecules.  The reads say it: a pass
