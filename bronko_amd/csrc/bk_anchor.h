@@ -1,5 +1,6 @@
 // bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip), junction_scan_kernel
-// (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+// (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip), duplication_scan_kernel (bk_duplications.hip) and link_scan_kernel
+// (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
 //
 // What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
 // log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
@@ -115,16 +116,19 @@ __device__ __forceinline__ bool anchors_of(const AnchorIndex& a, const uint32_t*
     EndAnchors e;
     return end_anchors(a, w, n, e) && anchors_of(e, a.k, n, out);
 }
-// both anchors in one sequence, the cells [lo, hi) inside it and holding ACGT only
-__device__ __forceinline__ bool cells_placed(const AnchorIndex& a, uint32_t ca, uint32_t cb, int32_t lo, int32_t hi) {
-    const uint32_t s = seq_of(a, ca);
-    if (seq_of(a, cb) != s) return false;
+// the cells [lo, hi) inside sequence s and holding ACGT only
+__device__ __forceinline__ bool arm_placed(const AnchorIndex& a, uint32_t s, int32_t lo, int32_t hi) {
     if (lo < (int32_t)a.seq_lo[s] || hi > (int32_t)a.seq_lo[s + 1]) return false;
     if (a.n_nruns) {
         const uint32_t i = first_run_behind(a, lo);
         if (i < a.n_nruns && (int32_t)a.nruns[i].x < hi) return false;
     }
     return true;
+}
+// both anchors in one sequence, the cells [lo, hi) inside it and holding ACGT only
+__device__ __forceinline__ bool cells_placed(const AnchorIndex& a, uint32_t ca, uint32_t cb, int32_t lo, int32_t hi) {
+    const uint32_t s = seq_of(a, ca);
+    return seq_of(a, cb) == s && arm_placed(a, s, lo, hi);
 }
 
 // A record as the breakpoint walks of indel_scan_kernel and junction_scan_kernel read it: r', the record along the reference.  One
@@ -144,15 +148,50 @@ struct OrientedRecord {
     __device__ __forceinline__ uint32_t at(int32_t j) const { return against ? 3u - sym_at(w, (uint32_t)(n - 1 - j)) : sym_at(w, (uint32_t)j); }   // r'[j]
     __device__ __forceinline__ int32_t mm(int32_t j, int32_t d) const { return at(j) != sym_at(ix.ref_words, (uint32_t)(d + j)) ? 1 : 0; }
 };
-// F of the normalisation: the first cell of the stretch of ACGT letters of the sequence (the one that holds `cell`) in front of the
-// record's cells, which begin at `lo` and hold no other letter: the runs in front of them are the ones that end at lo or before
-__device__ __forceinline__ int32_t acgt_floor(const AnchorIndex& a, uint32_t cell, int32_t lo) {
-    int32_t F = (int32_t)a.seq_lo[seq_of(a, cell)];
+// F of the normalisation: the first cell of the stretch of ACGT letters of sequence s in front of cells that begin at `lo` and hold
+// no other letter: the runs in front of them are the ones that end at lo or before
+__device__ __forceinline__ int32_t acgt_floor_in(const AnchorIndex& a, uint32_t s, int32_t lo) {
+    int32_t F = (int32_t)a.seq_lo[s];
     if (a.n_nruns) {
         const uint32_t i = first_run_behind(a, lo);
         if (i > 0u) F = max(F, (int32_t)a.nruns[i - 1u].y);
     }
     return F;
+}
+// ... of the sequence that holds `cell`
+__device__ __forceinline__ int32_t acgt_floor(const AnchorIndex& a, uint32_t cell, int32_t lo) { return acgt_floor_in(a, seq_of(a, cell), lo); }
+
+// The breakpoint of a record whose front lies on diagonal dL and whose back on dR (junction_scan_kernel: dR > dL; duplication_scan_kernel:
+// dR < dL): m(p) = #{j < p: r'[j] != ref[dL + j]} + #{j >= p: r'[j] != ref[dR + j]} for p in [p0, p1], p0 <= p1.  Returns the least
+// m(p), best_p the smallest p that has it.  Incremental: moving p by one exchanges one comparison on dR for one on dL.  The cells read
+// are [dL, dL + p1) and [dR + p0, dR + n).
+__device__ __forceinline__ int32_t breakpoint_walk(const OrientedRecord& rec, int32_t p0, int32_t p1, int32_t dL, int32_t dR, int32_t& best_p) {
+    int32_t m = rec.span_mm(0, p0, dL) + rec.span_mm(p0, rec.n, dR);
+    int32_t best = m;
+    best_p = p0;
+    for (int32_t p = p0; p < p1; ++p) {
+        m += rec.mm(p, dL) - rec.mm(p, dR);
+        if (m < best) { best = m; best_p = p + 1; }
+    }
+    return best;
+}
+
+// The event tables of junction_scan_kernel and duplication_scan_kernel: open addressing, the key one word, cell | len << 32 (both
+// below 2^27: never the free word), claimed with one CAS; two counters a slot, along and against the reference.  A table whose every
+// slot is another event's raises *overflow: the sample's result is an error.
+constexpr unsigned long long kEventFreeWord = ~0ull;
+__device__ __forceinline__ void event_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ counts, uint32_t log2n,
+                                             unsigned long long* __restrict__ overflow, uint32_t cell, uint32_t len, bool against) {
+    const unsigned long long key = (unsigned long long)cell | ((unsigned long long)len << 32);
+    const uint64_t mask = (1ull << log2n) - 1ull;
+    uint64_t h = (key * 0x9E3779B97F4A7C15ull) >> (64u - log2n);
+    for (uint64_t probes = 0; probes <= mask; ++probes) {
+        unsigned long long c = __hip_atomic_load(keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c == kEventFreeWord) { c = atomicCAS(keys + h, kEventFreeWord, key); if (c == kEventFreeWord) c = key; }
+        if (c == key) { atomicAdd(counts + 2u * h + (against ? 1u : 0u), 1u); return; }
+        h = (h + 1) & mask;
+    }
+    atomicExch(overflow, 1ull);
 }
 
 constexpr int kSpanPrefixBlock = 1024;

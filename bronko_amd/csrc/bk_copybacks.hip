@@ -46,15 +46,6 @@ __device__ __forceinline__ void event_insert(const CopybackArgs& a, uint32_t lo,
     atomicExch(a.tallies + kOverflow, 1ull);   // every slot is another event's: the sample's result is an error
 }
 
-// the cells [lo, hi) inside sequence s and holding ACGT only
-__device__ __forceinline__ bool arm_placed(const AnchorIndex& a, uint32_t s, int32_t lo, int32_t hi) {
-    if (lo < (int32_t)a.seq_lo[s] || hi > (int32_t)a.seq_lo[s + 1]) return false;
-    if (a.n_nruns) {
-        const uint32_t i = first_run_behind(a, lo);
-        if (i < a.n_nruns && (int32_t)a.nruns[i].x < hi) return false;
-    }
-    return true;
-}
 // the stretch [lo, hi) of ACGT letters of sequence s around `cell`, which holds one
 __device__ __forceinline__ void acgt_stretch(const AnchorIndex& a, uint32_t s, int32_t cell, int32_t& lo, int32_t& hi) {
     lo = (int32_t)a.seq_lo[s]; hi = (int32_t)a.seq_lo[s + 1];

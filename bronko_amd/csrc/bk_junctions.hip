@@ -5,10 +5,8 @@
 //                                the anchors through bk_anchor.h, delta = 0 inline (the Hamming pass with an early exit, two atomics
 //                                on `span`), `short` and `backward` a tally each.  A forward jump of min_len or more is rare: those
 //                                records are gathered in a queue of the wave (LDS, filled through a ballot) and walked a lane each
-//                                once 64 wait.  The walk is incremental: moving p by one exchanges one comparison on dL for one on dR.
-//                                Events go to an open-addressing table whose key is one word, pos | D << 32 (both below 2^27: never
-//                                the free word), claimed with one CAS.  A full table raises the overflow word.  The sample's
-//                                tallies: one add per wave and tally.
+//                                once 64 wait.  The walk (breakpoint_walk) and the event table (event_insert, key pos | D << 32) are
+//                                bk_anchor.h's, shared with duplication_scan_kernel.  The sample's tallies: one add per wave and tally.
 //   junction_span_prefix_kernel  at the sample's end: `span` prefix-summed in place by one workgroup.
 //   junction_report_kernel       the table's events with enough reads, appended with one returning add per wave.
 // Vector stores and atomics only.
@@ -24,25 +22,11 @@ namespace {
 
 constexpr int kJunctionBlock = 256;
 constexpr uint32_t kJunctionQueue = 128;   // entries of a wave's queue: fewer than 64 wait when up to 64 more arrive
-constexpr unsigned long long kFreeWord = ~0ull;
 constexpr int kScanTallies = 7;            // records, anchored, ref_spanning, supporting, short, backward, discordant
 constexpr int kCandidates = 7, kReported = 8, kOverflow = 9;   // JunctionArgs::tallies behind them
 
 struct JunctionTally { uint32_t v[kScanTallies] = {0, 0, 0, 0, 0, 0, 0}; };
 enum { T_RECORDS, T_ANCHORED, T_SPANNING, T_SUPPORTING, T_SHORT, T_BACKWARD, T_DISCORDANT };
-
-__device__ __forceinline__ void event_insert(const JunctionArgs& a, uint32_t cell, uint32_t len, bool against) {
-    const unsigned long long key = (unsigned long long)cell | ((unsigned long long)len << 32);
-    const uint64_t mask = (1ull << a.log2n) - 1ull;
-    uint64_t h = (key * 0x9E3779B97F4A7C15ull) >> (64u - a.log2n);
-    for (uint64_t probes = 0; probes <= mask; ++probes) {
-        unsigned long long c = __hip_atomic_load(a.keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (c == kFreeWord) { c = atomicCAS(a.keys + h, kFreeWord, key); if (c == kFreeWord) c = key; }
-        if (c == key) { atomicAdd(a.counts + 2u * h + (against ? 1u : 0u), 1u); return; }
-        h = (h + 1) & mask;
-    }
-    atomicExch(a.tallies + kOverflow, 1ull);   // every slot is another event's: the sample's result is an error
-}
 
 // A record's anchors and all that needs no breakpoint.  Returns true with `work` filled for a record with delta >= min_len that
 // passed the checks: {record | against << 31, a | b << 16, dL, dR}.
@@ -83,21 +67,16 @@ __device__ __forceinline__ void junction_walk(const JunctionArgs& a, const uint4
     const int32_t k = a.ix.k, n = (int32_t)a.rec.lens[r], D = dR - dL;
     const uint32_t* __restrict__ w = a.rec.words + (uint64_t)r * a.rec.stride_words;
     const uint32_t last_word = (uint32_t)(n - 1) >> 4;
-    const int32_t p0 = pa + k, p1 = pb;               // (p0 <= p1: anchors_of)
     const OrientedRecord rec{a.ix, w, n, last_word, against};
-    int32_t m = rec.span_mm(0, p0, dL) + rec.span_mm(p0, n, dR);
-    int32_t best = m, best_p = p0;
-    for (int32_t p = p0; p < p1; ++p) {
-        m += rec.mm(p, dL) - rec.mm(p, dR);
-        if (m < best) { best = m; best_p = p + 1; }
-    }
+    int32_t best_p;
+    const int32_t best = breakpoint_walk(rec, pa + k, pb, dL, dR, best_p);   // (pa + k <= pb: anchors_of)
     if (best > (int32_t)a.max_mismatches) { t.v[T_DISCORDANT]++; return; }
     int32_t pos = dL + best_p;
     // F: the first cell of the stretch of ACGT letters of the sequence that holds pos - 1 (the record's cells [dL, dR + n) hold no other letter)
     const int32_t F = acgt_floor(a.ix, (uint32_t)(dL + pa), dL);
     while (pos - 1 > F && sym_at(a.ix.ref_words, (uint32_t)(pos - 1)) == sym_at(a.ix.ref_words, (uint32_t)(pos + D - 1))) --pos;
     t.v[T_SUPPORTING]++;
-    event_insert(a, (uint32_t)pos, (uint32_t)D, against);
+    event_insert(a.keys, a.counts, a.log2n, a.tallies + kOverflow, (uint32_t)pos, (uint32_t)D, against);
 }
 
 __global__ __launch_bounds__(kJunctionBlock) void junction_scan_kernel(JunctionArgs a) {
@@ -146,7 +125,7 @@ __global__ __launch_bounds__(kJunctionBlock) void junction_report_kernel(Junctio
         JunctionRecordDev row{};
         if (i < n_slots) {
             const unsigned long long key = a.keys[i];
-            there = key != kFreeWord;
+            there = key != kEventFreeWord;
             if (there) {
                 row.cell = (uint32_t)key; row.len = (uint32_t)(key >> 32);
                 row.fwd = a.counts[2u * i]; row.rev = a.counts[2u * i + 1u];

@@ -534,6 +534,26 @@ struct CopybackArgs {
 void launch_copyback_scan(const CopybackArgs& a, int n_cus, hipStream_t stream);
 void launch_copyback_span_prefix(const CopybackArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_copyback_report(const CopybackArgs& a, hipStream_t stream);
+// bk_duplications_enable: tandem duplications and circular-origin reads (bk_duplications.hip; the rule: include/bronko_hip.h,
+// DESIGN.md section V)
+typedef bk_duplication_record DuplicationRecordDev;
+struct DuplicationArgs {
+    RecordsView rec;                     // duplication_scan_kernel's batch
+    AnchorIndex ix;
+    uint32_t min_len, max_mismatches;
+    // the sample: event table (one key word pos | E << 32, ~0 = free, {fwd, rev}), span, counters
+    unsigned long long* keys;
+    unsigned int* counts;                // [slots][2]
+    uint32_t log2n;
+    unsigned int* span;                  // [total_cells + 2]
+    unsigned long long* tallies;         // [10] records, anchored, ref_spanning, supporting, short, forward, discordant, candidates, reported, overflow
+    // the report: duplication_report_kernel
+    uint64_t min_reads;
+    DuplicationRecordDev* rows; uint64_t row_cap;
+};
+void launch_duplication_scan(const DuplicationArgs& a, int n_cus, hipStream_t stream);
+void launch_duplication_span_prefix(const DuplicationArgs& a, hipStream_t stream);   // span in place, once per sample
+void launch_duplication_report(const DuplicationArgs& a, hipStream_t stream);
 // bk_link_enable: which substitutions the same records carry (bk_linkage.hip; the rule: include/bronko_hip.h)
 struct LinkArgs {
     RecordsView rec;                     // link_scan_kernel's batch
@@ -584,7 +604,7 @@ struct HapArgs {
 void launch_hap_count(const HapArgs& a, uint64_t rows_upper, int n_cus, hipStream_t stream);   // rows_upper: a bound on the rows (the grid)
 void launch_hap_finish(const HapArgs& a, hipStream_t stream);
 // bk_sample_read_pileup: per cell, the rows of bk_link_enable's store that cover it by the base they carry there, by strand and near
-// their ends (bk_read_pileup.hip; the rule: include/bronko_hip.h, DESIGN.md section U)
+// their ends (bk_read_pileup.hip; the rule: include/bronko_hip.h, DESIGN.md section V)
 typedef bk_read_pileup_cell ReadPileupCellDev;
 struct ReadPileupArgs {
     const uint32_t* ref_words;           // AnchorIndex's

@@ -518,6 +518,32 @@ class Engine:
         _check(self._L.bk_sample_download_copyback_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
         return span[:self.total_cells]
 
+    def duplications_enable(self, min_len=33, max_mismatches=2, table_log2=16):
+        """bk_duplications_enable: duplication_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
+        cfg = None if min_len is None else C.byref(_ffi.DuplicationConfig(int(min_len), int(max_mismatches), int(table_log2)))
+        _check(self._L.bk_duplications_enable(self.h, cfg), self._L)
+
+    def sample_duplications(self, min_reads=5):
+        """bk_sample_duplications: the finalized sample's duplications with at least min_reads reads, on the device (asynchronous)."""
+        _check(self._L.bk_sample_duplications(self.h, C.byref(_ffi.DuplicationParams(int(min_reads)))), self._L)
+
+    def download_duplications(self, cap=None):
+        """(summary, rows) of sample_duplications: min(cap, summary.reported) rows (cell, len, fwd, rev, span_start, span_end), all by
+        default, sorted by (cell, len)."""
+        summ = _ffi.DuplicationSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_duplications(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        buf = np.zeros((max(1, cap), 6), np.uint32)
+        _check(self._L.bk_sample_download_duplications(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+
+    def download_duplication_span(self):
+        """bk_sample_download_duplication_span: the prefix-summed span array of all cells (after sample_duplications)."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(self._L.bk_sample_download_duplication_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def linkage_enable(self, max_mismatches=8, initial_rows=1 << 16):
         """bk_link_enable: link_scan_kernel runs behind every scan of the samples that begin from now on and keeps a row per placed
         record; max_mismatches=None disables."""

@@ -211,6 +211,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--copybacks: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.duplications) {     // (likewise)
+        LOG_DEBUG(T, "--duplications: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     if (shard_mode && a.linkage) {          // (likewise: a sample's row store is one engine's)
         LOG_DEBUG(T, "--linkage: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
@@ -258,6 +262,8 @@ struct SampleData {
     std::vector<JunctionEvent> junctions;
     bk_copyback_summary cbsumm{};                         // --copybacks
     std::vector<CopybackEvent> copybacks;
+    bk_duplication_summary dpsumm{};                      // --duplications
+    std::vector<DuplicationEvent> duplications;
     bk_link_summary lsumm{};                              // --linkage
     std::vector<LinkSite> link_recs;
     std::vector<LinkPair> link_pairs;
@@ -274,6 +280,7 @@ constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity
 constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
 constexpr uint32_t kJunctionTableLog2 = 18;   // --junctions: likewise
 constexpr uint32_t kCopybackTableLog2 = 18;   // --copybacks: likewise
+constexpr uint32_t kDuplicationTableLog2 = 18;   // --duplications: likewise
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
 struct CallRun {
@@ -328,6 +335,8 @@ struct CallRun {
             die(T, "--junctions needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.copybacks && ix.files.size() != 1)
             die(T, "--copybacks needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.duplications && ix.files.size() != 1)
+            die(T, "--duplications needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.linkage && ix.files.size() != 1)
             die(T, "--linkage needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.codons() && ix.files.size() != 1)
@@ -506,6 +515,10 @@ struct CallRun {
             const bk_copyback_config cc{cfg.copyback.max_mismatches, kCopybackTableLog2};
             hip_check(bk_copybacks_enable(e, &cc), "bk_copybacks_enable");
         }
+        if (cfg.duplications) {
+            const bk_duplication_config dc{cfg.duplication.min_len, cfg.duplication.max_mismatches, kDuplicationTableLog2};
+            hip_check(bk_duplications_enable(e, &dc), "bk_duplications_enable");
+        }
         if (cfg.row_store()) {   // (--codons, --haplotypes and --read-pileup read --linkage's row store; alone each brings its own M, together they are equal)
             const bk_link_config lc{cfg.row_store_mismatches(), kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
@@ -551,6 +564,10 @@ struct CallRun {
         if (cfg.copybacks) {   // (likewise)
             const bk_copyback_params cp{cfg.copyback.min_reads, cfg.copyback.min_dist};
             hip_check(bk_sample_copybacks(e, &cp), "bk_sample_copybacks");
+        }
+        if (cfg.duplications) {   // (likewise)
+            const bk_duplication_params dp{cfg.duplication.min_reads};
+            hip_check(bk_sample_duplications(e, &dp), "bk_sample_duplications");
         }
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
@@ -610,6 +627,12 @@ struct CallRun {
             hip_check(bk_sample_download_copybacks(e, &d.cbsumm, nullptr, 0), "bk_sample_download_copybacks");
             d.copybacks.resize((size_t)d.cbsumm.reported);
             hip_check(bk_sample_download_copybacks(e, &d.cbsumm, reinterpret_cast<bk_copyback_record*>(d.copybacks.data()), d.copybacks.size()), "bk_sample_download_copybacks");
+        }
+        if (cfg.duplications) {
+            static_assert(sizeof(DuplicationEvent) == sizeof(bk_duplication_record), "DuplicationEvent is bk_duplication_record");
+            hip_check(bk_sample_download_duplications(e, &d.dpsumm, nullptr, 0), "bk_sample_download_duplications");
+            d.duplications.resize((size_t)d.dpsumm.reported);
+            hip_check(bk_sample_download_duplications(e, &d.dpsumm, reinterpret_cast<bk_duplication_record*>(d.duplications.data()), d.duplications.size()), "bk_sample_download_duplications");
         }
         if (cfg.linkage) {   // the sites are the sample's own VCF records: counted behind the calls, a few rows travel
             static_assert(sizeof(LinkPair) == sizeof(bk_link_pair), "LinkPair is bk_link_pair");
@@ -732,6 +755,14 @@ struct CallRun {
                                 " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate copy-backs, " +
                                 std::to_string(s.reported) + " reported");
                 write_copybacks_tsv(a.output + "/" + stem + ".copybacks.tsv", ix, best, d.copybacks, cfg.copyback);
+            }
+            if (cfg.duplications) {    // (a sample without events: the headers alone)
+                const bk_duplication_summary& s = d.dpsumm;
+                LOG_INFO(T, "Duplications: " + std::to_string(s.anchored) + " of " + std::to_string(s.records) + " records anchored, " + std::to_string(s.ref_spanning) +
+                                " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.short_) + " short, " +
+                                std::to_string(s.forward) + " forward, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) +
+                                " candidate duplications, " + std::to_string(s.reported) + " reported");
+                write_duplications_tsv(a.output + "/" + stem + ".duplications.tsv", ix, best, d.duplications, cfg.duplication);
             }
             if (cfg.linkage) {      // (a sample without such a pair: the header alone)
                 const uint64_t lines = write_linkage_tsv(a.output + "/" + stem + ".linkage.tsv", ix, best, d.link_recs, d.link_pairs, cfg.link);

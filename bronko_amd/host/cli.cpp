@@ -75,7 +75,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--junctions]\n"
           "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--copybacks]\n"
-          "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--linkage]\n"
+          "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--duplications]\n"
+          "            [--duplication-min-len L] [--duplication-max-mismatches M] [--duplication-min-reads N] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
           "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
@@ -124,6 +125,15 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --copyback-max-mismatches M substitutions a read may have beside its turn; 0..8, default 2\n"
           "  --copyback-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
           "  --copyback-min-dist D       cells the two breakpoints must lie apart; at least 0, default 0 (hairpins too)\n"
+          "  --duplications    write tandem duplications and the reads across the origin of a circular genome to\n"
+          "                    <DIR>/<stem>.duplications.tsv (an index of one genome file): reads whose two ends lie on diagonals of the\n"
+          "                    reference L or more apart, backward on one strand of one sequence, counted on the GPU; per event the\n"
+          "                    first and last duplicated base, reads per strand, reads that span either end unbroken, freq = reads /\n"
+          "                    (reads + max(span_start, span_end)), the homology behind it, whole = 1 when the whole sequence is\n"
+          "                    duplicated: the read crosses the origin\n"
+          "  --duplication-min-len L        shortest jump counted; at least 1, default 33 (where --indels ends)\n"
+          "  --duplication-max-mismatches M substitutions a read may have beside its junction; 0..8, default 2\n"
+          "  --duplication-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
           "  --linkage         write to <DIR>/<stem>.linkage.tsv, per pair of the sample's substitutions (an index of one genome file), how\n"
           "                    many of the reads that cover both positions carry neither, the first, the second or both\n"
           "  --link-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8\n"
@@ -306,6 +316,17 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--copyback-max-mismatches") { a.copyback_max_mismatches = x; a.has_copyback_max_mismatches = true; }
             else if (opt == "--copyback-min-reads") { a.copyback_min_reads = x; a.has_copyback_min_reads = true; }
             else { a.copyback_min_dist = x; a.has_copyback_min_dist = true; }
+        }
+        else if (opt == "--duplications") a.duplications = true;
+        else if (opt == "--duplication-min-len" || opt == "--duplication-max-mismatches" || opt == "--duplication-min-reads") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--duplication-min-len") { a.duplication_min_len = x; a.has_duplication_min_len = true; }
+            else if (opt == "--duplication-max-mismatches") { a.duplication_max_mismatches = x; a.has_duplication_max_mismatches = true; }
+            else { a.duplication_min_reads = x; a.has_duplication_min_reads = true; }
         }
         else if (opt == "--linkage") a.linkage = true;
         else if (opt == "--link-max-mismatches" || opt == "--link-max-dist" || opt == "--link-min-reads") {   // (any integer here: check_call_args)
@@ -552,6 +573,12 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.copyback_max_mismatches < 0 || a.copyback_max_mismatches > kCopybackMaxMismatches) die(T, "--copyback-max-mismatches must be between 0 and 8, got " + std::to_string(a.copyback_max_mismatches));
     if (a.copyback_min_reads < 1) die(T, "--copyback-min-reads must be at least 1, got " + std::to_string(a.copyback_min_reads));
     if (a.copyback_min_dist < 0 || a.copyback_min_dist > 0xffffffffl) die(T, "--copyback-min-dist must be between 0 and 4294967295, got " + std::to_string(a.copyback_min_dist));
+    if (a.has_duplication_min_len && !a.duplications) die(T, "--duplication-min-len needs --duplications");
+    if (a.has_duplication_max_mismatches && !a.duplications) die(T, "--duplication-max-mismatches needs --duplications");
+    if (a.has_duplication_min_reads && !a.duplications) die(T, "--duplication-min-reads needs --duplications");
+    if (a.duplication_min_len < 1 || a.duplication_min_len > (long)kDuplicationMaxLen) die(T, "--duplication-min-len must be between 1 and " + std::to_string(kDuplicationMaxLen) + ", got " + std::to_string(a.duplication_min_len));
+    if (a.duplication_max_mismatches < 0 || a.duplication_max_mismatches > kDuplicationMaxMismatches) die(T, "--duplication-max-mismatches must be between 0 and 8, got " + std::to_string(a.duplication_max_mismatches));
+    if (a.duplication_min_reads < 1) die(T, "--duplication-min-reads must be at least 1, got " + std::to_string(a.duplication_min_reads));
     if (a.has_link_max_mismatches && !a.linkage) die(T, "--link-max-mismatches needs --linkage");
     if (a.has_link_max_dist && !a.linkage) die(T, "--link-max-dist needs --linkage");
     if (a.has_link_min_reads && !a.linkage) die(T, "--link-min-reads needs --linkage");
@@ -647,6 +674,9 @@ CallConfig make_call_config(const Args& a) {
     c.copybacks = a.copybacks;
     c.copyback.max_mismatches = (uint32_t)a.copyback_max_mismatches; c.copyback.min_reads = (uint64_t)a.copyback_min_reads;
     c.copyback.min_dist = (uint32_t)a.copyback_min_dist;
+    c.duplications = a.duplications;
+    c.duplication.min_len = (uint32_t)a.duplication_min_len; c.duplication.max_mismatches = (uint32_t)a.duplication_max_mismatches;
+    c.duplication.min_reads = (uint64_t)a.duplication_min_reads;
     c.junctions = a.junctions;
     c.junction.min_len = (uint32_t)a.junction_min_len; c.junction.max_mismatches = (uint32_t)a.junction_max_mismatches;
     c.junction.min_reads = (uint64_t)a.junction_min_reads;

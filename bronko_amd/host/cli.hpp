@@ -11,6 +11,7 @@
 #include "caller.hpp"
 #include "codons.hpp"
 #include "copybacks.hpp"
+#include "duplications.hpp"
 #include "haplotypes.hpp"
 #include "indels.hpp"
 #include "junctions.hpp"
@@ -82,6 +83,11 @@ struct Args {
     long copyback_max_mismatches = 2;   // --copyback-max-mismatches: substitutions a record may have beside its turn (0..8)
     long copyback_min_reads = 5;    // --copyback-min-reads: supporting records an event needs
     long copyback_min_dist = 0;     // --copyback-min-dist: cells an event's two breakpoints must lie apart
+    bool duplications = false;      // --duplications: <DIR>/<stem>.duplications.tsv, tandem duplications and circular-origin reads
+    bool has_duplication_min_len = false, has_duplication_max_mismatches = false, has_duplication_min_reads = false;
+    long duplication_min_len = 33;  // --duplication-min-len: shortest backward jump counted (with 33 it begins where --indels ends)
+    long duplication_max_mismatches = 2;   // --duplication-max-mismatches: substitutions a record may have beside its junction (0..8)
+    long duplication_min_reads = 5; // --duplication-min-reads: supporting records an event needs
     bool linkage = false;           // --linkage: <DIR>/<stem>.linkage.tsv, which of the sample's substitutions the same reads carry
     bool has_link_max_mismatches = false, has_link_max_dist = false, has_link_min_reads = false;
     long link_max_mismatches = 8;   // --link-max-mismatches: substitutions a placed record may have (0..8)
@@ -146,6 +152,9 @@ struct CallConfig {
     // --copybacks: bk_copybacks_enable / bk_sample_copybacks and the values the .copybacks.tsv header prints
     bool copybacks = false;
     CopybackParams copyback;
+    // --duplications: bk_duplications_enable / bk_sample_duplications and the values the .duplications.tsv header prints
+    bool duplications = false;
+    DuplicationParams duplication;
     // --linkage: bk_link_enable / bk_sample_linkage and the values the .linkage.tsv header prints
     bool linkage = false;
     LinkParams link;

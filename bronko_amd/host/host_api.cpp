@@ -11,6 +11,7 @@
 #include "caller.hpp"
 #include "codons.hpp"
 #include "copybacks.hpp"
+#include "duplications.hpp"
 #include "haplotypes.hpp"
 #include "indels.hpp"
 #include "junctions.hpp"
@@ -349,6 +350,36 @@ int bh_write_copybacks_tsv(const void* h, int file_id, const char* path, const v
         bronko::CopybackParams p;
         p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_dist = min_dist;
         bronko::write_copybacks_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::CopybackEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --duplications: the host twin of the engine's duplication pass (duplications.cpp) ------------------------------------
+// reads joined by '\n'; rows as bk_duplication_record (= bronko::DuplicationEvent), at most cap written, *n their number; span: NULL or
+// [total_cells], prefix-summed; counters = {records, anchored, ref_spanning, supporting, short, forward, discordant}
+int bh_duplication_events(const void* h, int file_id, const char* reads, uint32_t min_len, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span,
+                       uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::DuplicationEvent) == 24, "DuplicationEvent is bk_duplication_record");
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const bronko::DuplicationResult r = bronko::duplication_events(*ix, file_id, split_lines(reads), min_len, max_mismatches);
+        *n = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::DuplicationEvent));
+        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+        if (counters) {
+            const uint64_t c[7] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.forward, r.n.discordant};
+            std::memcpy(counters, c, sizeof c);
+        }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_duplications_tsv(const void* h, int file_id, const char* path, const void* rows, uint64_t n, uint32_t min_len, uint32_t max_mismatches, uint64_t min_reads) {
+    try {
+        const auto* ev = static_cast<const bronko::DuplicationEvent*>(rows);
+        bronko::DuplicationParams p;
+        p.min_len = min_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads;
+        bronko::write_duplications_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::DuplicationEvent>(ev, ev + n), p);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

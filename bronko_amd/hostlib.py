@@ -425,6 +425,45 @@ def write_copybacks_tsv(path, ix, file_id, rows, max_mismatches=2, min_reads=5, 
         raise _host_error(L)
 
 
+def _duplication_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_duplications_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_duplication_events.restype = C.c_int
+        L.bh_duplication_events.argtypes = [vp, C.c_int, C.c_char_p, u32, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
+        L.bh_write_duplications_tsv.restype = C.c_int
+        L.bh_write_duplications_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, u64]
+        L._duplications_ready = True
+    return L
+
+
+def duplication_events(ix, file_id, reads, min_len=33, max_mismatches=2):
+    """The host twin of the engine's duplication pass (duplications.cpp duplication_events) over ASCII reads: (rows of the whole table as
+    bk_duplication_record (cell, len, fwd, rev, span_start, span_end) sorted by (cell, len), the prefix-summed span array of all
+    cells, (records, anchored, ref_spanning, supporting, short, forward, discordant))."""
+    L = _duplication_lib()
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    span = np.zeros(max(1, ix.total_cells), np.uint32)
+    counters = np.zeros(7, np.uint64)
+    if L.bh_duplication_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
+        raise _host_error(L)
+    rec = np.zeros((max(1, n.value), 6), np.uint32)
+    if L.bh_duplication_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
+        raise _host_error(L)
+    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+
+
+def write_duplications_tsv(path, ix, file_id, rows, min_len=33, max_mismatches=2, min_reads=5):
+    """The --duplications writer (duplications.cpp write_duplications_tsv): rows as duplication_events gives them, already filtered."""
+    rec = np.zeros((max(1, len(rows)), 6), np.uint32)
+    for i, r in enumerate(rows):
+        rec[i] = r
+    L = _duplication_lib()
+    if L.bh_write_duplications_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(min_len), int(max_mismatches), int(min_reads)) != 0:
+        raise _host_error(L)
+
+
 def _link_lib():
     L = _caller_lib()
     if not hasattr(L, "_linkage_ready"):

@@ -514,7 +514,7 @@ int  bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap);
  *              dL + b: +1 at cell dL + a + k, -1 at cell dL + b + 1 of the pass's own difference array `span` (not
  *              bk_indels_enable's: either feature works without the other).  Else `discordant`.
  *   0 < |delta| < min_len   counted `short`, nothing else: bk_indels_enable reports those.
- *   delta <= -min_len       counted `backward`, nothing else (duplications are not looked for; copy-backs: bk_copybacks_enable).
+ *   delta <= -min_len       counted `backward`, nothing else (duplications: bk_duplications_enable; copy-backs: bk_copybacks_enable).
  *   delta >= min_len        a junction of D = delta.  For p in [a + k, b]: m(p) = #{j < p: r'[j] != ref[dL + j]} + #{j >= p: r'[j]
  *              != ref[dR + j]}; the smallest p that minimises m(p); m(p) > max_mismatches: `discordant`.  pos = dL + p, F as in
  *              the indel rule.  While pos - 1 > F and ref[pos - 1] = ref[pos + D - 1]: pos -= 1.  Event (pos, D): the cells
@@ -581,7 +581,7 @@ int  bk_sample_download_junction_span(bk_engine* e, uint32_t* span, uint64_t cap
  *              larger cell.  Event (kind, lo, hi); homology = t1 - t0 (the writer computes it from the reference).
  *   per event  reads = lo_first + hi_first.  With S the prefix sum of span: kind H span_lo = S[lo + 1], span_hi = S[hi + 1]; kind T
  *              span_lo = S[lo], span_hi = S[hi].  Reported iff reads >= min_reads and hi - lo >= min_dist.  Both mate files add
- *              into one table and one span array.  Same-strand backward jumps stay a tally of bk_junctions_enable.
+ *              into one table and one span array.  Same-strand backward jumps: bk_duplications_enable.
  *   bk_copybacks_enable        as bk_junctions_enable: between samples (BK_ERR_STATE inside one); NULL disables and frees.
  *                              max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window (BK_ERR_INVALID
  *                              otherwise) and a genome of k to 2^27 - 1 positions (BK_ERR_UNSUPPORTED otherwise).  Allocates all the
@@ -606,6 +606,63 @@ int  bk_copybacks_enable(bk_engine* e, const bk_copyback_config* cfg);
 int  bk_sample_copybacks(bk_engine* e, const bk_copyback_params* p);
 int  bk_sample_download_copybacks(bk_engine* e, bk_copyback_summary* summary, bk_copyback_record* records, uint64_t cap);
 int  bk_sample_download_copyback_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
+/* ---- tandem duplications and circular-origin reads (`bronko call --duplications`; additive, still v8) ----------------------------
+ * The one case of a record placed by its two end anchors that the passes above leave: both anchors on one strand, the back one on a
+ * diagonal behind the front one's.  bk_junctions_enable counts it `backward` and drops it.  Such a read crosses the junction between
+ * the two copies of a tandem duplication (it need not hold a whole copy), or the linearisation point of a circular genome: it runs
+ * to the last cell of the sequence and goes on at the first, a backward jump of the sequence's length.  A pass of its own over each
+ * batch's records (duplication_scan_kernel, behind the scan of the same records) counts them.  The rule, all of it integer
+ * arithmetic, in bk_indels_enable's terms:
+ *   unit, anchor k-mer, anchors, r', a, b, c_a, c_b, dL, dR, delta   exactly as under bk_indels_enable: a record of n < 2k is
+ *              counted in `records` and otherwise ignored; a record with both anchors on one strand and a + k <= b is `anchored`.
+ *   ignored    without a tally, before anything is asked of delta: the two anchors in different sequences.  [lo, hi) are the cells
+ *              of the anchors' sequence.
+ *   delta = 0  as under bk_junctions_enable: the cells [dL, dL + n) lie in [lo, hi) and hold ACGT only, else the record is ignored.
+ *              m = Hamming(r', ref[dL, dL + n)).  m <= max_mismatches: the record is `ref_spanning`: +1 at cell dL + a + k, -1 at
+ *              cell dL + b + 1 of this pass's own difference array `span`.  Else `discordant`.
+ *   delta > 0  counted `forward`, nothing else (bk_indels_enable and bk_junctions_enable report those).
+ *   -min_len < delta < 0   counted `short`, nothing else.
+ *   delta <= -min_len   a backward jump of E = -delta.  Ignored without a tally unless lo <= dL and dR + n <= hi.  The breakpoint's
+ *              range is clipped to the sequence: p0 = max(a + k, lo - dR), p1 = min(b, hi - dL); p0 > p1: ignored.  The two arms'
+ *              cells [dL, dL + p1) and [dR + p0, dR + n) hold ACGT only, else the record is ignored.  (This is the difference from
+ *              bk_junctions_enable: the left arm may run to the last cell of the sequence and the right arm may begin at its
+ *              first; a virtual overhang beyond either is never read.)  For p in [p0, p1]: m(p) = #{j < p: r'[j] != ref[dL + j]}
+ *              + #{j >= p: r'[j] != ref[dR + j]}; the smallest p that minimises m(p); m(p) > max_mismatches: `discordant`.
+ *              pos = dL + p: the read leaves the reference behind cell pos - 1 and goes on at cell pos - E; the cells
+ *              [pos - E, pos) are read twice.
+ *   normalised with two floors: F_L = the first cell of the stretch of ACGT letters of the sequence that holds pos - 1, F_R = the
+ *              first cell of the stretch that holds pos - E.  While pos - 1 > F_L and pos - E - 1 >= F_R and ref[pos - 1] =
+ *              ref[pos - E - 1]: pos -= 1.  Event (pos, E).  The record is `supporting`: fwd along the reference, rev against it.
+ *   per event  reads = fwd + rev; span_start = the prefix sum of span at pos - E, span_end = at pos.  Reported iff reads >=
+ *              min_reads.  Both mate files add into one table and one span array.
+ *   key        pos | E << 32, both below 2^27, so never the free word; pos = hi is a legal key and a legal index of span, which has
+ *              total_cells + 2 entries.
+ *   bk_duplications_enable     as bk_junctions_enable: between samples (BK_ERR_STATE inside one); NULL disables and frees.  min_len
+ *                              1..2^27 - 1, max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window
+ *                              (BK_ERR_INVALID otherwise) and a genome of k to 2^27 - 1 positions (BK_ERR_UNSUPPORTED otherwise).
+ *                              Allocates all the feature needs (the event table of 2^table_log2 slots, as many rows, span; the
+ *                              anchor tables are shared with bk_indels_enable, bk_junctions_enable, bk_copybacks_enable and
+ *                              bk_link_enable); an engine that never enables it allocates and launches nothing.  Per engine: forks
+ *                              set their own.  A sample that began before the call has no events.
+ *   bk_sample_duplications     after the sample's bk_sample_finalize: BK_ERR_STATE inside a sample, before any finalize, and when
+ *                              the feature was not enabled as the sample began; BK_ERR_INVALID for min_reads == 0.  Prefix-sums
+ *                              span, selects the rows; asynchronous on the engine's stream; may be repeated with other parameters.
+ *   bk_sample_download_duplications   synchronises; copies min(cap, reported) rows in no particular order (records may be NULL).
+ *                              `candidates` = the distinct events of the sample.  A table that met more of them than it holds
+ *                              loses nothing silently: overflow = 1 in the summary and BK_ERR_INVALID ("more than 2^n distinct
+ *                              candidate duplications").
+ *   bk_sample_download_duplication_span   the prefix-summed span array of all cells (cap >= bk_total_cells, BK_ERR_INVALID otherwise).
+ * bk_duplication_record: cell = pos, the cell behind the last one read twice; len = E; the cells [pos - E, pos) are read twice. */
+#define BK_DUPLICATION_MAX_LEN 134217727u   /* 2^27 - 1 */
+typedef struct { uint32_t min_len, max_mismatches, table_log2; } bk_duplication_config;   /* table_log2 10..24 */
+typedef struct { uint64_t min_reads; } bk_duplication_params;
+typedef struct { uint32_t cell, len, fwd, rev, span_start, span_end; } bk_duplication_record;
+typedef struct { uint64_t records, anchored, ref_spanning, supporting, short_, forward, discordant, candidates, reported; int32_t overflow; } bk_duplication_summary;
+int  bk_duplications_enable(bk_engine* e, const bk_duplication_config* cfg);
+int  bk_sample_duplications(bk_engine* e, const bk_duplication_params* p);
+int  bk_sample_download_duplications(bk_engine* e, bk_duplication_summary* summary, bk_duplication_record* records, uint64_t cap);
+int  bk_sample_download_duplication_span(bk_engine* e, uint32_t* span, uint64_t cap);
 
 /* ---- which substitutions the same reads carry (`bronko call --linkage`; additive, still v8) -------------------------------------
  * The pileup says how often each substitution occurs, not whether two of them sit on the same molecules.  The reads say it: a pass
