@@ -101,6 +101,19 @@ class CopybackSummary(C.Structure):  # bk_copyback_summary
                 ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class ChimeraConfig(C.Structure):  # bk_chimera_config
+    _fields_ = [("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
+class ChimeraParams(C.Structure):  # bk_chimera_params
+    _fields_ = [("min_reads", C.c_uint64)]
+
+
+class ChimeraSummary(C.Structure):  # bk_chimera_summary
+    _fields_ = [("records", C.c_uint64), ("same_strand", C.c_uint64), ("ref_spanning", C.c_uint64), ("crossed", C.c_uint64), ("supporting", C.c_uint64),
+                ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
+
+
 class DuplicationConfig(C.Structure):  # bk_duplication_config
     _fields_ = [("min_len", C.c_uint32), ("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -163,6 +176,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_junctions_enable", "bk_sample_junctions", "bk_sample_download_junctions", "bk_sample_download_junction_span",
            "bk_copybacks_enable", "bk_sample_copybacks", "bk_sample_download_copybacks", "bk_sample_download_copyback_span",
+           "bk_chimeras_enable", "bk_sample_chimeras", "bk_sample_download_chimeras", "bk_sample_download_chimera_span",
            "bk_duplications_enable", "bk_sample_duplications", "bk_sample_download_duplications", "bk_sample_download_duplication_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
@@ -318,6 +332,14 @@ def load(testing=None):
     L.bk_sample_download_copybacks.argtypes = [vp, C.POINTER(CopybackSummary), vp, u64]
     L.bk_sample_download_copyback_span.restype = C.c_int
     L.bk_sample_download_copyback_span.argtypes = [vp, vp, u64]
+    L.bk_chimeras_enable.restype = C.c_int
+    L.bk_chimeras_enable.argtypes = [vp, C.POINTER(ChimeraConfig)]
+    L.bk_sample_chimeras.restype = C.c_int
+    L.bk_sample_chimeras.argtypes = [vp, C.POINTER(ChimeraParams)]
+    L.bk_sample_download_chimeras.restype = C.c_int
+    L.bk_sample_download_chimeras.argtypes = [vp, C.POINTER(ChimeraSummary), vp, u64]
+    L.bk_sample_download_chimera_span.restype = C.c_int
+    L.bk_sample_download_chimera_span.argtypes = [vp, vp, u64]
     L.bk_duplications_enable.restype = C.c_int
     L.bk_duplications_enable.argtypes = [vp, C.POINTER(DuplicationConfig)]
     L.bk_sample_duplications.restype = C.c_int

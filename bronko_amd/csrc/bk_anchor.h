@@ -1,6 +1,6 @@
 // bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip), junction_scan_kernel
-// (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip), duplication_scan_kernel (bk_duplications.hip) and link_scan_kernel
-// (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+// (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip), duplication_scan_kernel (bk_duplications.hip), chimera_scan_kernel
+// (bk_chimeras.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
 //
 // What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
 // log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
@@ -160,6 +160,15 @@ __device__ __forceinline__ int32_t acgt_floor_in(const AnchorIndex& a, uint32_t 
 }
 // ... of the sequence that holds `cell`
 __device__ __forceinline__ int32_t acgt_floor(const AnchorIndex& a, uint32_t cell, int32_t lo) { return acgt_floor_in(a, seq_of(a, cell), lo); }
+// the stretch [lo, hi) of ACGT letters of sequence s around `cell`, which holds one
+__device__ __forceinline__ void acgt_stretch(const AnchorIndex& a, uint32_t s, int32_t cell, int32_t& lo, int32_t& hi) {
+    lo = (int32_t)a.seq_lo[s]; hi = (int32_t)a.seq_lo[s + 1];
+    if (a.n_nruns) {
+        const uint32_t i = first_run_behind(a, cell);   // (it ends behind the cell and does not hold it: it begins behind it)
+        if (i < a.n_nruns) hi = min(hi, (int32_t)a.nruns[i].x);
+        if (i > 0u) lo = max(lo, (int32_t)a.nruns[i - 1u].y);
+    }
+}
 
 // The breakpoint of a record whose front lies on diagonal dL and whose back on dR (junction_scan_kernel: dR > dL; duplication_scan_kernel:
 // dR < dL): m(p) = #{j < p: r'[j] != ref[dL + j]} + #{j >= p: r'[j] != ref[dR + j]} for p in [p0, p1], p0 <= p1.  Returns the least

@@ -46,16 +46,6 @@ __device__ __forceinline__ void event_insert(const CopybackArgs& a, uint32_t lo,
     atomicExch(a.tallies + kOverflow, 1ull);   // every slot is another event's: the sample's result is an error
 }
 
-// the stretch [lo, hi) of ACGT letters of sequence s around `cell`, which holds one
-__device__ __forceinline__ void acgt_stretch(const AnchorIndex& a, uint32_t s, int32_t cell, int32_t& lo, int32_t& hi) {
-    lo = (int32_t)a.seq_lo[s]; hi = (int32_t)a.seq_lo[s + 1];
-    if (a.n_nruns) {
-        const uint32_t i = first_run_behind(a, cell);   // (it ends behind the cell and does not hold it: it begins behind it)
-        if (i < a.n_nruns) hi = min(hi, (int32_t)a.nruns[i].x);
-        if (i > 0u) lo = max(lo, (int32_t)a.nruns[i - 1u].y);
-    }
-}
-
 // A record's end anchors and all that needs no breakpoint.  Returns true with `work` filled for a switched record:
 // {record | kind << 31, f | g << 16, c_f, c_g}.
 __device__ __forceinline__ bool copyback_anchor(const CopybackArgs& a, uint32_t r, CopybackTally& t, uint4& work) {

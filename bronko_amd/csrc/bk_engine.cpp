@@ -275,6 +275,7 @@ int bk_sample_begin(bk_engine* e) {
     if (e->indels) { if (int rc = e->indels->begin_sample(e)) return rc; }
     if (e->junctions) { if (int rc = e->junctions->begin_sample(e)) return rc; }
     if (e->copybacks) { if (int rc = e->copybacks->begin_sample(e)) return rc; }
+    if (e->chimeras) { if (int rc = e->chimeras->begin_sample(e)) return rc; }
     if (e->duplications) { if (int rc = e->duplications->begin_sample(e)) return rc; }
     if (e->linkage) { if (int rc = e->linkage->begin_sample(e)) return rc; }
     if (e->primers) { if (int rc = e->primers->begin_sample(e)) return rc; }
@@ -602,6 +603,7 @@ int push_device(bk_engine* e, int mate, const Records& r) {
     if (e->indels) { if (int rc = e->indels->push(e, r)) return rc; }
     if (e->junctions) { if (int rc = e->junctions->push(e, r)) return rc; }
     if (e->copybacks) { if (int rc = e->copybacks->push(e, r)) return rc; }
+    if (e->chimeras) { if (int rc = e->chimeras->push(e, r)) return rc; }
     if (e->duplications) { if (int rc = e->duplications->push(e, r)) return rc; }
     if (e->linkage) { if (int rc = e->linkage->push(e, r)) return rc; }
     BK_HIP(hipGetLastError());

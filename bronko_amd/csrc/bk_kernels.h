@@ -534,6 +534,26 @@ struct CopybackArgs {
 void launch_copyback_scan(const CopybackArgs& a, int n_cus, hipStream_t stream);
 void launch_copyback_span_prefix(const CopybackArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_copyback_report(const CopybackArgs& a, hipStream_t stream);
+// bk_chimeras_enable: junctions between two sequences of the genome file from the reads (bk_chimeras.hip; the rule: include/bronko_hip.h,
+// DESIGN.md section X)
+typedef bk_chimera_record ChimeraRecordDev;
+struct ChimeraArgs {
+    RecordsView rec;                     // chimera_scan_kernel's batch
+    AnchorIndex ix;
+    uint32_t max_mismatches;
+    // the sample: event table (one key word lo | sides << 28 | hi << 32, ~0 = free, {lo_first, hi_first}), span, counters
+    unsigned long long* keys;
+    unsigned int* counts;                // [slots][2]
+    uint32_t log2n;
+    unsigned int* span;                  // [total_cells + 2]
+    unsigned long long* tallies;         // [9] records, same_strand, ref_spanning, crossed, supporting, discordant, candidates, reported, overflow
+    // the report: chimera_report_kernel
+    uint64_t min_reads;
+    ChimeraRecordDev* rows; uint64_t row_cap;
+};
+void launch_chimera_scan(const ChimeraArgs& a, int n_cus, hipStream_t stream);
+void launch_chimera_span_prefix(const ChimeraArgs& a, hipStream_t stream);   // span in place, once per sample
+void launch_chimera_report(const ChimeraArgs& a, hipStream_t stream);
 // bk_duplications_enable: tandem duplications and circular-origin reads (bk_duplications.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section V)
 typedef bk_duplication_record DuplicationRecordDev;

@@ -518,6 +518,34 @@ class Engine:
         _check(self._L.bk_sample_download_copyback_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
         return span[:self.total_cells]
 
+    def chimeras_enable(self, max_mismatches=2, table_log2=16):
+        """bk_chimeras_enable: chimera_scan_kernel runs behind every scan of the samples that begin from now on; max_mismatches=None
+        disables."""
+        cfg = None if max_mismatches is None else C.byref(_ffi.ChimeraConfig(int(max_mismatches), int(table_log2)))
+        _check(self._L.bk_chimeras_enable(self.h, cfg), self._L)
+
+    def sample_chimeras(self, min_reads=5):
+        """bk_sample_chimeras: the finalized sample's junctions between two sequences with at least min_reads reads, on the device
+        (asynchronous)."""
+        _check(self._L.bk_sample_chimeras(self.h, C.byref(_ffi.ChimeraParams(int(min_reads)))), self._L)
+
+    def download_chimeras(self, cap=None):
+        """(summary, rows) of sample_chimeras: min(cap, summary.reported) rows (lo, hi, sides, lo_first, hi_first, span_lo, span_hi, 0),
+        all by default, sorted."""
+        summ = _ffi.ChimeraSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_chimeras(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        buf = np.zeros((max(1, cap), 8), np.uint32)
+        _check(self._L.bk_sample_download_chimeras(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+
+    def download_chimera_span(self):
+        """bk_sample_download_chimera_span: the prefix-summed span array of all cells (after sample_chimeras)."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(self._L.bk_sample_download_chimera_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def duplications_enable(self, min_len=33, max_mismatches=2, table_log2=16):
         """bk_duplications_enable: duplication_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
         cfg = None if min_len is None else C.byref(_ffi.DuplicationConfig(int(min_len), int(max_mismatches), int(table_log2)))

@@ -211,6 +211,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--copybacks: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.chimeras) {         // (likewise)
+        LOG_DEBUG(T, "--chimeras: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     if (shard_mode && a.duplications) {     // (likewise)
         LOG_DEBUG(T, "--duplications: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
@@ -262,6 +266,8 @@ struct SampleData {
     std::vector<JunctionEvent> junctions;
     bk_copyback_summary cbsumm{};                         // --copybacks
     std::vector<CopybackEvent> copybacks;
+    bk_chimera_summary chsumm{};                          // --chimeras
+    std::vector<ChimeraEvent> chimeras;
     bk_duplication_summary dpsumm{};                      // --duplications
     std::vector<DuplicationEvent> duplications;
     bk_link_summary lsumm{};                              // --linkage
@@ -280,6 +286,7 @@ constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity
 constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
 constexpr uint32_t kJunctionTableLog2 = 18;   // --junctions: likewise
 constexpr uint32_t kCopybackTableLog2 = 18;   // --copybacks: likewise
+constexpr uint32_t kChimeraTableLog2 = 18;    // --chimeras: likewise
 constexpr uint32_t kDuplicationTableLog2 = 18;   // --duplications: likewise
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
@@ -335,6 +342,8 @@ struct CallRun {
             die(T, "--junctions needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.copybacks && ix.files.size() != 1)
             die(T, "--copybacks needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.chimeras && ix.files.size() != 1)
+            die(T, "--chimeras needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.duplications && ix.files.size() != 1)
             die(T, "--duplications needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.linkage && ix.files.size() != 1)
@@ -515,6 +524,10 @@ struct CallRun {
             const bk_copyback_config cc{cfg.copyback.max_mismatches, kCopybackTableLog2};
             hip_check(bk_copybacks_enable(e, &cc), "bk_copybacks_enable");
         }
+        if (cfg.chimeras) {
+            const bk_chimera_config xc{cfg.chimera.max_mismatches, kChimeraTableLog2};
+            hip_check(bk_chimeras_enable(e, &xc), "bk_chimeras_enable");
+        }
         if (cfg.duplications) {
             const bk_duplication_config dc{cfg.duplication.min_len, cfg.duplication.max_mismatches, kDuplicationTableLog2};
             hip_check(bk_duplications_enable(e, &dc), "bk_duplications_enable");
@@ -564,6 +577,10 @@ struct CallRun {
         if (cfg.copybacks) {   // (likewise)
             const bk_copyback_params cp{cfg.copyback.min_reads, cfg.copyback.min_dist};
             hip_check(bk_sample_copybacks(e, &cp), "bk_sample_copybacks");
+        }
+        if (cfg.chimeras) {   // (likewise)
+            const bk_chimera_params xp{cfg.chimera.min_reads};
+            hip_check(bk_sample_chimeras(e, &xp), "bk_sample_chimeras");
         }
         if (cfg.duplications) {   // (likewise)
             const bk_duplication_params dp{cfg.duplication.min_reads};
@@ -627,6 +644,12 @@ struct CallRun {
             hip_check(bk_sample_download_copybacks(e, &d.cbsumm, nullptr, 0), "bk_sample_download_copybacks");
             d.copybacks.resize((size_t)d.cbsumm.reported);
             hip_check(bk_sample_download_copybacks(e, &d.cbsumm, reinterpret_cast<bk_copyback_record*>(d.copybacks.data()), d.copybacks.size()), "bk_sample_download_copybacks");
+        }
+        if (cfg.chimeras) {
+            static_assert(sizeof(ChimeraEvent) == sizeof(bk_chimera_record), "ChimeraEvent is bk_chimera_record");
+            hip_check(bk_sample_download_chimeras(e, &d.chsumm, nullptr, 0), "bk_sample_download_chimeras");
+            d.chimeras.resize((size_t)d.chsumm.reported);
+            hip_check(bk_sample_download_chimeras(e, &d.chsumm, reinterpret_cast<bk_chimera_record*>(d.chimeras.data()), d.chimeras.size()), "bk_sample_download_chimeras");
         }
         if (cfg.duplications) {
             static_assert(sizeof(DuplicationEvent) == sizeof(bk_duplication_record), "DuplicationEvent is bk_duplication_record");
@@ -755,6 +778,14 @@ struct CallRun {
                                 " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate copy-backs, " +
                                 std::to_string(s.reported) + " reported");
                 write_copybacks_tsv(a.output + "/" + stem + ".copybacks.tsv", ix, best, d.copybacks, cfg.copyback);
+            }
+            if (cfg.chimeras) {        // (a sample without events, a genome file of one sequence: the headers alone)
+                const bk_chimera_summary& s = d.chsumm;
+                LOG_INFO(T, "Chimeras: " + std::to_string(s.records) + " records, " + std::to_string(s.same_strand) + " on one strand of one sequence, " +
+                                std::to_string(s.ref_spanning) + " reference-spanning, " + std::to_string(s.crossed) + " crossed, " + std::to_string(s.supporting) +
+                                " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate chimeras, " +
+                                std::to_string(s.reported) + " reported");
+                write_chimeras_tsv(a.output + "/" + stem + ".chimeras.tsv", ix, best, d.chimeras, cfg.chimera, s.supporting, s.ref_spanning);
             }
             if (cfg.duplications) {    // (a sample without events: the headers alone)
                 const bk_duplication_summary& s = d.dpsumm;

@@ -75,7 +75,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--junctions]\n"
           "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--copybacks]\n"
-          "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--duplications]\n"
+          "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--chimeras]\n"
+          "            [--chimera-max-mismatches M] [--chimera-min-reads N] [--duplications]\n"
           "            [--duplication-min-len L] [--duplication-max-mismatches M] [--duplication-min-reads N] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
@@ -125,6 +126,14 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --copyback-max-mismatches M substitutions a read may have beside its turn; 0..8, default 2\n"
           "  --copyback-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
           "  --copyback-min-dist D       cells the two breakpoints must lie apart; at least 0, default 0 (hairpins too)\n"
+          "  --chimeras        write junctions between two sequences of the genome file to <DIR>/<stem>.chimeras.tsv (an index of one\n"
+          "                    genome file): reads whose front lies in one sequence and whose back in another -- segment junctions,\n"
+          "                    virus and spike-in, template-switch artefacts --, by the two cells of the junction and the side of each\n"
+          "                    the read holds (L: the cells below it, R: above), normalised, with the reads that support each, the\n"
+          "                    reads that span either cell unbroken, freq = reads / (reads + the larger span) and the homology of the\n"
+          "                    junction; the header gives the sample's supporting and spanning reads\n"
+          "  --chimera-max-mismatches M  substitutions a read may have beside its junction; 0..8, default 2\n"
+          "  --chimera-min-reads N       supporting reads an event needs to be written; at least 1, default 5\n"
           "  --duplications    write tandem duplications and the reads across the origin of a circular genome to\n"
           "                    <DIR>/<stem>.duplications.tsv (an index of one genome file): reads whose two ends lie on diagonals of the\n"
           "                    reference L or more apart, backward on one strand of one sequence, counted on the GPU; per event the\n"
@@ -316,6 +325,16 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--copyback-max-mismatches") { a.copyback_max_mismatches = x; a.has_copyback_max_mismatches = true; }
             else if (opt == "--copyback-min-reads") { a.copyback_min_reads = x; a.has_copyback_min_reads = true; }
             else { a.copyback_min_dist = x; a.has_copyback_min_dist = true; }
+        }
+        else if (opt == "--chimeras") a.chimeras = true;
+        else if (opt == "--chimera-max-mismatches" || opt == "--chimera-min-reads") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--chimera-max-mismatches") { a.chimera_max_mismatches = x; a.has_chimera_max_mismatches = true; }
+            else { a.chimera_min_reads = x; a.has_chimera_min_reads = true; }
         }
         else if (opt == "--duplications") a.duplications = true;
         else if (opt == "--duplication-min-len" || opt == "--duplication-max-mismatches" || opt == "--duplication-min-reads") {   // (any integer here: check_call_args)
@@ -573,6 +592,10 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.copyback_max_mismatches < 0 || a.copyback_max_mismatches > kCopybackMaxMismatches) die(T, "--copyback-max-mismatches must be between 0 and 8, got " + std::to_string(a.copyback_max_mismatches));
     if (a.copyback_min_reads < 1) die(T, "--copyback-min-reads must be at least 1, got " + std::to_string(a.copyback_min_reads));
     if (a.copyback_min_dist < 0 || a.copyback_min_dist > 0xffffffffl) die(T, "--copyback-min-dist must be between 0 and 4294967295, got " + std::to_string(a.copyback_min_dist));
+    if (a.has_chimera_max_mismatches && !a.chimeras) die(T, "--chimera-max-mismatches needs --chimeras");
+    if (a.has_chimera_min_reads && !a.chimeras) die(T, "--chimera-min-reads needs --chimeras");
+    if (a.chimera_max_mismatches < 0 || a.chimera_max_mismatches > kChimeraMaxMismatches) die(T, "--chimera-max-mismatches must be between 0 and 8, got " + std::to_string(a.chimera_max_mismatches));
+    if (a.chimera_min_reads < 1) die(T, "--chimera-min-reads must be at least 1, got " + std::to_string(a.chimera_min_reads));
     if (a.has_duplication_min_len && !a.duplications) die(T, "--duplication-min-len needs --duplications");
     if (a.has_duplication_max_mismatches && !a.duplications) die(T, "--duplication-max-mismatches needs --duplications");
     if (a.has_duplication_min_reads && !a.duplications) die(T, "--duplication-min-reads needs --duplications");
@@ -674,6 +697,8 @@ CallConfig make_call_config(const Args& a) {
     c.copybacks = a.copybacks;
     c.copyback.max_mismatches = (uint32_t)a.copyback_max_mismatches; c.copyback.min_reads = (uint64_t)a.copyback_min_reads;
     c.copyback.min_dist = (uint32_t)a.copyback_min_dist;
+    c.chimeras = a.chimeras;
+    c.chimera.max_mismatches = (uint32_t)a.chimera_max_mismatches; c.chimera.min_reads = (uint64_t)a.chimera_min_reads;
     c.duplications = a.duplications;
     c.duplication.min_len = (uint32_t)a.duplication_min_len; c.duplication.max_mismatches = (uint32_t)a.duplication_max_mismatches;
     c.duplication.min_reads = (uint64_t)a.duplication_min_reads;

@@ -9,6 +9,7 @@
 
 #include "../../include/bronko_hip.h"
 #include "caller.hpp"
+#include "chimeras.hpp"
 #include "codons.hpp"
 #include "copybacks.hpp"
 #include "duplications.hpp"
@@ -83,6 +84,10 @@ struct Args {
     long copyback_max_mismatches = 2;   // --copyback-max-mismatches: substitutions a record may have beside its turn (0..8)
     long copyback_min_reads = 5;    // --copyback-min-reads: supporting records an event needs
     long copyback_min_dist = 0;     // --copyback-min-dist: cells an event's two breakpoints must lie apart
+    bool chimeras = false;          // --chimeras: <DIR>/<stem>.chimeras.tsv, junctions between two sequences of the genome file from the reads
+    bool has_chimera_max_mismatches = false, has_chimera_min_reads = false;
+    long chimera_max_mismatches = 2;    // --chimera-max-mismatches: substitutions a record may have beside its junction (0..8)
+    long chimera_min_reads = 5;     // --chimera-min-reads: supporting records an event needs
     bool duplications = false;      // --duplications: <DIR>/<stem>.duplications.tsv, tandem duplications and circular-origin reads
     bool has_duplication_min_len = false, has_duplication_max_mismatches = false, has_duplication_min_reads = false;
     long duplication_min_len = 33;  // --duplication-min-len: shortest backward jump counted (with 33 it begins where --indels ends)
@@ -152,6 +157,9 @@ struct CallConfig {
     // --copybacks: bk_copybacks_enable / bk_sample_copybacks and the values the .copybacks.tsv header prints
     bool copybacks = false;
     CopybackParams copyback;
+    // --chimeras: bk_chimeras_enable / bk_sample_chimeras and the values the .chimeras.tsv header prints
+    bool chimeras = false;
+    ChimeraParams chimera;
     // --duplications: bk_duplications_enable / bk_sample_duplications and the values the .duplications.tsv header prints
     bool duplications = false;
     DuplicationParams duplication;

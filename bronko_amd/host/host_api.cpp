@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "caller.hpp"
+#include "chimeras.hpp"
 #include "codons.hpp"
 #include "copybacks.hpp"
 #include "duplications.hpp"
@@ -350,6 +351,36 @@ int bh_write_copybacks_tsv(const void* h, int file_id, const char* path, const v
         bronko::CopybackParams p;
         p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_dist = min_dist;
         bronko::write_copybacks_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::CopybackEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --chimeras: the host twin of the engine's chimera pass (chimeras.cpp) ------------------------------------------------
+// reads joined by '\n'; rows as bk_chimera_record (= bronko::ChimeraEvent), at most cap written, *n their number; span: NULL or
+// [total_cells], prefix-summed; counters = {records, same_strand, ref_spanning, crossed, supporting, discordant}
+int bh_chimera_events(const void* h, int file_id, const char* reads, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span, uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::ChimeraEvent) == 32, "ChimeraEvent is bk_chimera_record");
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const bronko::ChimeraResult r = bronko::chimera_events(*ix, file_id, split_lines(reads), max_mismatches);
+        *n = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::ChimeraEvent));
+        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+        if (counters) {
+            const uint64_t c[6] = {r.n.records, r.n.same_strand, r.n.ref_spanning, r.n.crossed, r.n.supporting, r.n.discordant};
+            std::memcpy(counters, c, sizeof c);
+        }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_chimeras_tsv(const void* h, int file_id, const char* path, const void* rows, uint64_t n, uint32_t max_mismatches, uint64_t min_reads, uint64_t supporting,
+                          uint64_t ref_spanning) {
+    try {
+        const auto* ev = static_cast<const bronko::ChimeraEvent*>(rows);
+        bronko::ChimeraParams p;
+        p.max_mismatches = max_mismatches; p.min_reads = min_reads;
+        bronko::write_chimeras_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::ChimeraEvent>(ev, ev + n), p, supporting, ref_spanning);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -425,6 +425,46 @@ def write_copybacks_tsv(path, ix, file_id, rows, max_mismatches=2, min_reads=5, 
         raise _host_error(L)
 
 
+def _chimera_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_chimeras_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_chimera_events.restype = C.c_int
+        L.bh_chimera_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
+        L.bh_write_chimeras_tsv.restype = C.c_int
+        L.bh_write_chimeras_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u64, u64, u64]
+        L._chimeras_ready = True
+    return L
+
+
+def chimera_events(ix, file_id, reads, max_mismatches=2):
+    """The host twin of the engine's chimera pass (chimeras.cpp chimera_events) over ASCII reads: (rows of the whole table as
+    bk_chimera_record (lo, hi, sides, lo_first, hi_first, span_lo, span_hi, 0) sorted, the prefix-summed span array of all cells,
+    (records, same_strand, ref_spanning, crossed, supporting, discordant))."""
+    L = _chimera_lib()
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    span = np.zeros(max(1, ix.total_cells), np.uint32)
+    counters = np.zeros(6, np.uint64)
+    if L.bh_chimera_events(ix.h, file_id, joined, int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
+        raise _host_error(L)
+    rec = np.zeros((max(1, n.value), 8), np.uint32)
+    if L.bh_chimera_events(ix.h, file_id, joined, int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
+        raise _host_error(L)
+    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+
+
+def write_chimeras_tsv(path, ix, file_id, rows, max_mismatches=2, min_reads=5, supporting=0, ref_spanning=0):
+    """The --chimeras writer (chimeras.cpp write_chimeras_tsv): rows as chimera_events gives them, already filtered, and the sample's
+    two tallies that the header prints."""
+    rec = np.zeros((max(1, len(rows)), 8), np.uint32)
+    for i, r in enumerate(rows):
+        rec[i] = r
+    L = _chimera_lib()
+    if L.bh_write_chimeras_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(max_mismatches), int(min_reads), int(supporting), int(ref_spanning)) != 0:
+        raise _host_error(L)
+
+
 def _duplication_lib():
     L = _caller_lib()
     if not hasattr(L, "_duplications_ready"):

@@ -607,6 +607,72 @@ int  bk_sample_copybacks(bk_engine* e, const bk_copyback_params* p);
 int  bk_sample_download_copybacks(bk_engine* e, bk_copyback_summary* summary, bk_copyback_record* records, uint64_t cap);
 int  bk_sample_download_copyback_span(bk_engine* e, uint32_t* span, uint64_t cap);
 
+/* ---- junctions between two sequences of the genome file (`bronko call --chimeras`; additive, still v8) ----------------------------
+ * bk_indels_enable, bk_junctions_enable, bk_copybacks_enable and bk_duplications_enable each ignore, without a tally, a record whose
+ * two anchors lie in different sequences.  Those reads are the inter-segment junctions of segmented viruses, whose segments are the
+ * sequences of one genome file, the reads that join virus and spike-in, and the template-switch chimeras of reverse transcription,
+ * PCR and library preparation, whose rate is a quality figure of the run.  A pass of its own over each batch's records
+ * (chimera_scan_kernel, behind the scan of the same records) counts them.  The rule, all of it integer arithmetic, in the terms of
+ * bk_indels_enable and bk_copybacks_enable:
+ *   unit, anchor k-mer, the offsets tried from each end   exactly as under bk_indels_enable: a record of n < 2k is counted in
+ *              `records` and otherwise ignored.  The record `rec` is taken as packed, as bk_copybacks_enable takes it: its front
+ *              anchor is (f, c_f, s_f), its back anchor (g, c_g, s_g); c the first cell of the reference k-mer, s "against the
+ *              reference".  comp is the complement.  An anchor k-mer starts at exactly one cell of the whole genome file, so
+ *              the k-mers of termini that the segments share make no anchors.  X = seq(c_f), Y = seq(c_g).
+ *   X == Y     only what the span needs, exactly bk_copybacks_enable's `s_f == s_g` rule: a record with both anchors on one strand
+ *              and a + k <= b is `same_strand`; with delta = 0, the cells [dL, dL + n) inside the sequence and ACGT only, and at
+ *              most max_mismatches mismatches it is `ref_spanning`: +1 at cell dL + a + k, -1 at cell dL + b + 1 of this pass's
+ *              own difference array `span`.  Every other record of one sequence leaves no trace here.
+ *   X != Y and f + k <= g   the record is `crossed`, whatever the two strands are.
+ *              arm A, offsets j < p: front along (s_f = 0): A(j) = c_f - f + j, the base expected at j is ref[A(j)], dA = +1;
+ *              front against: A(j) = c_f + k - 1 + f - j, expected comp(ref[A(j)]), dA = -1.
+ *              arm B, offsets j >= p: back along (s_g = 0): B(j) = c_g - g + j, expected ref[B(j)], dB = +1; back against:
+ *              B(j) = c_g + k - 1 + g - j, expected comp(ref[B(j)]), dB = -1.
+ *   ignored    a crossed record, without a further tally: a cell A(j), 0 <= j < g, leaves X or holds a letter that is not ACGT; a
+ *              cell B(j), f + k <= j < n, leaves Y or holds one.  (The arms' own ranges: an arm may end at the last or begin at
+ *              the first cell of its sequence.  The cells of two neighbouring sequences are neighbours in the index; each arm is
+ *              held to its own sequence, so no arm walks from one into the next.)
+ *   breakpoint for p in [f + k, g]: m(p) = #{j < p: rec[j] != arm A's base} + #{j >= p: rec[j] != arm B's base}; x(p) = A(p - 1),
+ *              y(p) = B(p).  The p that minimises (m(p), min(x(p), y(p))) -- X and Y share no cell, so the second term is x
+ *              throughout or y throughout, strictly monotonic in p: no further tie; and it makes a read and its reverse
+ *              complement choose the same two cells.  m > max_mismatches: `discordant`.  Else `supporting`.
+ *   normalised the pairs (x + dA t, y + dB t) that the reference cannot tell apart form a run t0 <= 0 <= t1.  The step from t to
+ *              t + 1 is allowed iff the base arm A expects at cell x + dA (t + 1) equals the base arm B expects at cell y + dB t;
+ *              the step down is the same condition at the lower pair; both cells of every pair stay inside their own sequence and
+ *              hold ACGT.  Of the two extreme pairs the one whose smaller cell is smaller; lo < hi its two cells.  Each cell has a
+ *              side: L, the read holds that cell and the cells below it (arm A along, arm B against); R, the read holds that cell
+ *              and the cells above it (arm A against, arm B along).  Event (lo, side_lo, hi, side_hi): the same two cells with
+ *              other sides are other events.  homology = t1 - t0 (the writer computes it from the reference).
+ *   per event  `lo_first` counts the supporting records whose arm A lies at lo, `hi_first` the others: a read and its reverse
+ *              complement count on opposite sides.  reads = lo_first + hi_first.  With S the prefix sum of span: a cell c with
+ *              side L has span S[c + 1], with side R S[c] (span has total_cells + 2 entries).  Reported iff reads >= min_reads.
+ *              Both mate files add into one table and one span array.  Key: lo | sides << 28 | hi << 32 (both cells below 2^27:
+ *              never the free word).
+ *   bk_chimeras_enable         as bk_copybacks_enable: between samples (BK_ERR_STATE inside one); NULL disables and frees.
+ *                              max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window (BK_ERR_INVALID
+ *                              otherwise) and a genome of k to 2^27 - 1 positions (BK_ERR_UNSUPPORTED otherwise).  Allocates all the
+ *                              feature needs (the event table of 2^table_log2 slots, as many rows, span; the anchor tables are shared
+ *                              with the other anchor passes and bk_link_enable); an engine that never enables it allocates and
+ *                              launches nothing.  Per engine: forks set their own.  A sample that began before the call has no
+ *                              events.  A genome file of one sequence is no error: no record is crossed.
+ *   bk_sample_chimeras         after the sample's bk_sample_finalize: BK_ERR_STATE inside a sample, before any finalize, and when
+ *                              the feature was not enabled as the sample began; BK_ERR_INVALID for min_reads == 0.  Prefix-sums
+ *                              span, selects the rows; asynchronous on the engine's stream; may be repeated with other parameters.
+ *   bk_sample_download_chimeras    synchronises; copies min(cap, reported) rows in no particular order (records may be NULL).
+ *                              `candidates` = the distinct events of the sample.  A table that met more of them than it holds
+ *                              loses nothing silently: overflow = 1 in the summary and BK_ERR_INVALID ("more than 2^n distinct
+ *                              candidate chimeras").
+ *   bk_sample_download_chimera_span    the prefix-summed span array of all cells (cap >= bk_total_cells, BK_ERR_INVALID otherwise).
+ * bk_chimera_record: sides bit 0 the side of lo, bit 1 the side of hi, 1 = R. */
+typedef struct { uint32_t max_mismatches, table_log2; } bk_chimera_config;   /* 0..8, 10..24 */
+typedef struct { uint64_t min_reads; } bk_chimera_params;
+typedef struct { uint32_t lo, hi, sides, lo_first, hi_first, span_lo, span_hi, pad; } bk_chimera_record;
+typedef struct { uint64_t records, same_strand, ref_spanning, crossed, supporting, discordant, candidates, reported; int32_t overflow; } bk_chimera_summary;
+int  bk_chimeras_enable(bk_engine* e, const bk_chimera_config* cfg);
+int  bk_sample_chimeras(bk_engine* e, const bk_chimera_params* p);
+int  bk_sample_download_chimeras(bk_engine* e, bk_chimera_summary* summary, bk_chimera_record* records, uint64_t cap);
+int  bk_sample_download_chimera_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
 /* ---- tandem duplications and circular-origin reads (`bronko call --duplications`; additive, still v8) ----------------------------
  * The one case of a record placed by its two end anchors that the passes above leave: both anchors on one strand, the back one on a
  * diagonal behind the front one's.  bk_junctions_enable counts it `backward` and drops it.  Such a read crosses the junction between
