@@ -114,6 +114,20 @@ class ChimeraSummary(C.Structure):  # bk_chimera_summary
                 ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class BreakendConfig(C.Structure):  # bk_breakend_config
+    _fields_ = [("min_clip", C.c_uint32), ("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
+
+
+class BreakendParams(C.Structure):  # bk_breakend_params
+    _fields_ = [("min_reads", C.c_uint64)]
+
+
+class BreakendSummary(C.Structure):  # bk_breakend_summary
+    _fields_ = [("records", C.c_uint64), ("one_anchor", C.c_uint64), ("ref_spanning", C.c_uint64), ("supporting", C.c_uint64), ("short_", C.c_uint64),
+                ("through", C.c_uint64), ("discordant", C.c_uint64), ("unplaced", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64),
+                ("overflow", C.c_int32)]
+
+
 class DuplicationConfig(C.Structure):  # bk_duplication_config
     _fields_ = [("min_len", C.c_uint32), ("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -177,6 +191,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_junctions_enable", "bk_sample_junctions", "bk_sample_download_junctions", "bk_sample_download_junction_span",
            "bk_copybacks_enable", "bk_sample_copybacks", "bk_sample_download_copybacks", "bk_sample_download_copyback_span",
            "bk_chimeras_enable", "bk_sample_chimeras", "bk_sample_download_chimeras", "bk_sample_download_chimera_span",
+           "bk_breakends_enable", "bk_sample_breakends", "bk_sample_download_breakends", "bk_sample_download_breakend_span",
            "bk_duplications_enable", "bk_sample_duplications", "bk_sample_download_duplications", "bk_sample_download_duplication_span",
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
@@ -340,6 +355,14 @@ def load(testing=None):
     L.bk_sample_download_chimeras.argtypes = [vp, C.POINTER(ChimeraSummary), vp, u64]
     L.bk_sample_download_chimera_span.restype = C.c_int
     L.bk_sample_download_chimera_span.argtypes = [vp, vp, u64]
+    L.bk_breakends_enable.restype = C.c_int
+    L.bk_breakends_enable.argtypes = [vp, C.POINTER(BreakendConfig)]
+    L.bk_sample_breakends.restype = C.c_int
+    L.bk_sample_breakends.argtypes = [vp, C.POINTER(BreakendParams)]
+    L.bk_sample_download_breakends.restype = C.c_int
+    L.bk_sample_download_breakends.argtypes = [vp, C.POINTER(BreakendSummary), vp, u64]
+    L.bk_sample_download_breakend_span.restype = C.c_int
+    L.bk_sample_download_breakend_span.argtypes = [vp, vp, u64]
     L.bk_duplications_enable.restype = C.c_int
     L.bk_duplications_enable.argtypes = [vp, C.POINTER(DuplicationConfig)]
     L.bk_sample_duplications.restype = C.c_int

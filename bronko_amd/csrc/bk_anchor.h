@@ -1,6 +1,6 @@
 // bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip), junction_scan_kernel
 // (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip), duplication_scan_kernel (bk_duplications.hip), chimera_scan_kernel
-// (bk_chimeras.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+// (bk_chimeras.hip), breakend_scan_kernel (bk_breakends.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
 //
 // What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
 // log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
@@ -104,6 +104,20 @@ __device__ __forceinline__ bool end_anchors(const AnchorIndex& a, const uint32_t
         if (anchor_at(a, w, (uint32_t)o, &e.b_cell, &e.b_ag)) { e.b_off = o; break; }
     return e.b_off >= 0;
 }
+// ... both ends searched whatever the other gave (breakend_scan_kernel, bk_breakends.hip: the record with exactly one end anchored).
+// Returns the ends that have an anchor: bit 0 the front, bit 1 the back; an end without one keeps its offset -1.  With both it fills
+// `e` exactly as end_anchors does.
+__device__ __forceinline__ uint32_t end_anchors_both(const AnchorIndex& a, const uint32_t* __restrict__ w, int32_t n, EndAnchors& e) {
+    const int32_t k = a.k;
+    e.f_off = -1; e.b_off = -1;
+    e.f_cell = 0; e.b_cell = 0;
+    e.f_ag = false; e.b_ag = false;
+    for (int32_t o = 0; o <= 24 && o + k <= n; o += 8)
+        if (anchor_at(a, w, (uint32_t)o, &e.f_cell, &e.f_ag)) { e.f_off = o; break; }
+    for (int32_t o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
+        if (anchor_at(a, w, (uint32_t)o, &e.b_cell, &e.b_ag)) { e.b_off = o; break; }
+    return (e.f_off >= 0 ? 1u : 0u) | (e.b_off >= 0 ? 2u : 0u);
+}
 // the two end anchors on one strand, oriented along the reference: a + k <= b
 __device__ __forceinline__ bool anchors_of(const EndAnchors& e, int32_t k, int32_t n, Anchors& out) {
     if (e.f_ag != e.b_ag) return false;
@@ -185,7 +199,8 @@ __device__ __forceinline__ int32_t breakpoint_walk(const OrientedRecord& rec, in
     return best;
 }
 
-// The event tables of junction_scan_kernel and duplication_scan_kernel: open addressing, the key one word, cell | len << 32 (both
+// The event tables of junction_scan_kernel, duplication_scan_kernel and breakend_scan_kernel (whose `len` is a tag of 32 bits under a
+// cell below 2^28): open addressing, the key one word, cell | len << 32 (both
 // below 2^27: never the free word), claimed with one CAS; two counters a slot, along and against the reference.  A table whose every
 // slot is another event's raises *overflow: the sample's result is an error.
 constexpr unsigned long long kEventFreeWord = ~0ull;

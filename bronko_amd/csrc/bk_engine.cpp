@@ -276,6 +276,7 @@ int bk_sample_begin(bk_engine* e) {
     if (e->junctions) { if (int rc = e->junctions->begin_sample(e)) return rc; }
     if (e->copybacks) { if (int rc = e->copybacks->begin_sample(e)) return rc; }
     if (e->chimeras) { if (int rc = e->chimeras->begin_sample(e)) return rc; }
+    if (e->breakends) { if (int rc = e->breakends->begin_sample(e)) return rc; }
     if (e->duplications) { if (int rc = e->duplications->begin_sample(e)) return rc; }
     if (e->linkage) { if (int rc = e->linkage->begin_sample(e)) return rc; }
     if (e->primers) { if (int rc = e->primers->begin_sample(e)) return rc; }
@@ -604,6 +605,7 @@ int push_device(bk_engine* e, int mate, const Records& r) {
     if (e->junctions) { if (int rc = e->junctions->push(e, r)) return rc; }
     if (e->copybacks) { if (int rc = e->copybacks->push(e, r)) return rc; }
     if (e->chimeras) { if (int rc = e->chimeras->push(e, r)) return rc; }
+    if (e->breakends) { if (int rc = e->breakends->push(e, r)) return rc; }
     if (e->duplications) { if (int rc = e->duplications->push(e, r)) return rc; }
     if (e->linkage) { if (int rc = e->linkage->push(e, r)) return rc; }
     BK_HIP(hipGetLastError());

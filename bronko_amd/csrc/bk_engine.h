@@ -243,7 +243,7 @@ struct Regions {
 };
 
 // What placing a record by two anchor k-mers reads beside the index tables (bk_anchor.h): built by the first of bk_indels_enable,
-// bk_junctions_enable, bk_copybacks_enable, bk_chimeras_enable, bk_duplications_enable and bk_link_enable, used by all of them, freed
+// bk_junctions_enable, bk_copybacks_enable, bk_chimeras_enable, bk_breakends_enable, bk_duplications_enable and bk_link_enable, used by all of them, freed
 // with the last
 struct AnchorTables {
     DevBuf<uint32_t> unique_bits;           // one bit per reference k-mer id: it starts at exactly one cell (a histogram of id_at)
@@ -380,6 +380,24 @@ struct Chimeras {
     DevBuf<bk_chimera_record> rows;         // [2^table_log2]
     bool in_sample = false;                 // enabled when the current / last sample began
     bool summed = false;                    // span is prefix-summed (this sample's bk_sample_chimeras ran)
+    bool made = false;                      // ... and the rows are this sample's
+    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
+    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+};
+
+// bk_breakends_enable: the same for breakend_scan_kernel (bk_breakends.hip) -- its own event table, (cell, side) array, span array,
+// tallies and rows
+struct Breakends {
+    bk_breakend_config cfg{};
+    std::shared_ptr<AnchorTables> anchors;  // shared with the other anchor passes and bk_link_enable
+    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word cell | side << 27 | tag << 32 (~0 = free)
+    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
+    DevBuf<unsigned int> site;              // [total_cells][2] the supporting records of every (cell, side), over every tag
+    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_breakends
+    DevBuf<unsigned long long> tallies;     // [11] bk_kernels.h BreakendArgs::tallies
+    DevBuf<bk_breakend_record> rows;        // [2^table_log2]
+    bool in_sample = false;                 // enabled when the current / last sample began
+    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_breakends ran)
     bool made = false;                      // ... and the rows are this sample's
     int begin_sample(bk_engine* e);         // (bk_riders.cpp)
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records
@@ -622,9 +640,10 @@ struct bk_engine {
     std::unique_ptr<Junctions> junctions;   // bk_junctions_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Copybacks> copybacks;   // bk_copybacks_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Chimeras> chimeras;     // bk_chimeras_enable (null: no table, no launch, no buffers)
+    std::unique_ptr<Breakends> breakends;   // bk_breakends_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Duplications> duplications;   // bk_duplications_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Linkage> linkage;       // bk_link_enable (null: no row store, no launch, no buffers)
-    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the six features holds them
+    std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the seven features holds them
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

@@ -554,6 +554,28 @@ struct ChimeraArgs {
 void launch_chimera_scan(const ChimeraArgs& a, int n_cus, hipStream_t stream);
 void launch_chimera_span_prefix(const ChimeraArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_chimera_report(const ChimeraArgs& a, hipStream_t stream);
+// bk_breakends_enable: reads that leave the reference -- records with an anchor at one end only (bk_breakends.hip; the rule:
+// include/bronko_hip.h)
+typedef bk_breakend_record BreakendRecordDev;
+struct BreakendArgs {
+    RecordsView rec;                     // breakend_scan_kernel's batch
+    AnchorIndex ix;
+    uint32_t min_clip, max_mismatches;
+    // the sample: event table (one key word cell | side << 27 | tag << 32, ~0 = free, {fwd, rev}), the supporting reads of every
+    // (cell, side), span, counters
+    unsigned long long* keys;
+    unsigned int* counts;                // [slots][2]
+    uint32_t log2n;
+    unsigned int* site;                  // [total_cells][2] L, R
+    unsigned int* span;                  // [total_cells + 2]
+    unsigned long long* tallies;         // [11] records, one_anchor, ref_spanning, supporting, short, through, discordant, unplaced, candidates, reported, overflow
+    // the report: breakend_report_kernel
+    uint64_t min_reads;
+    BreakendRecordDev* rows; uint64_t row_cap;
+};
+void launch_breakend_scan(const BreakendArgs& a, int n_cus, hipStream_t stream);
+void launch_breakend_span_prefix(const BreakendArgs& a, hipStream_t stream);   // span in place, once per sample
+void launch_breakend_report(const BreakendArgs& a, hipStream_t stream);
 // bk_duplications_enable: tandem duplications and circular-origin reads (bk_duplications.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section V)
 typedef bk_duplication_record DuplicationRecordDev;

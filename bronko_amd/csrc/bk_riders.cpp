@@ -1,13 +1,13 @@
 // bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
 // short insertions and deletions (bk_indels.hip), junctions (bk_junctions.hip), copy-backs (bk_copybacks.hip), chimeras
-// (bk_chimeras.hip), duplications (bk_duplications.hip) and linkage (bk_linkage.hip), with the anchor tables the last six share, and the codon
+// (bk_chimeras.hip), breakends (bk_breakends.hip), duplications (bk_duplications.hip) and linkage (bk_linkage.hip), with the anchor tables the last seven share, and the codon
 // haplotype and read-pileup counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip,
 // bk_read_pileup.hip).  The four counts over the store (bk_sample_linkage, bk_sample_codons, bk_sample_haplotypes, bk_sample_read_pileup)
 // share one lifecycle, StoreCount of bk_engine.h, and the helpers in front of them here: what they ask of the engine's state, of a
 // region's cells, and how their tables reach the device.
 // Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
 // push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
-// indels, junctions, copy-backs, chimeras, duplications, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
+// indels, junctions, copy-backs, chimeras, breakends, duplications, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
 // by their declarations in bronko_hip.h).
 #include <algorithm>
 #include <cstring>
@@ -126,7 +126,7 @@ int bk_kmer_dump_download(bk_engine* e, int mate, uint64_t* kmers, uint64_t* cou
     return BK_OK;
 }
 
-// ---- placing records by anchor k-mers: what bk_indels_enable, bk_junctions_enable, bk_copybacks_enable, bk_chimeras_enable, bk_duplications_enable and bk_link_enable ask of the index and build from it -----------------
+// ---- placing records by anchor k-mers: what bk_indels_enable, bk_junctions_enable, bk_copybacks_enable, bk_chimeras_enable, bk_breakends_enable, bk_duplications_enable and bk_link_enable ask of the index and build from it -----------------
 static int anchor_index_check(const IndexTables& ix, const char* who) {
     if (ix.W <= 0 || ix.n_full == 0) return fail(BK_ERR_INVALID, "%s: the index has no window of reference k-mers", who);
     if (!ix.rc_words.p)   // (build_index_tables makes it with the binned scan's seed tables: fewer than 2^27 cells, at least k)
@@ -571,6 +571,109 @@ int bk_sample_download_chimera_span(bk_engine* e, uint32_t* span, uint64_t cap) 
     if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_chimera_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
     BK_HIP(hipSetDevice(e->device));
     return download(e, span, e->chimeras->span.p, (size_t)e->ix->total_cells);
+}
+
+// ---- reads that leave the reference: records with an anchor at one end only (bk_breakends.hip) ------------------------
+// the sample starts from an empty table, zero (cell, side) and span arrays, zero tallies (an abandoned sample leaves nothing behind)
+int Breakends::begin_sample(bk_engine* e) {
+    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(site.p, 0, site.n * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
+    in_sample = true; summed = false; made = false;
+    return BK_OK;
+}
+// what every breakend kernel is given (a.rec: the scan's batch)
+static bk::BreakendArgs breakend_args(const bk_engine* e) {
+    const Breakends& d = *e->breakends;
+    bk::BreakendArgs a{};
+    a.ix = anchor_index(*e->ix, *d.anchors);
+    a.min_clip = d.cfg.min_clip; a.max_mismatches = d.cfg.max_mismatches;
+    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
+    a.site = d.site.p; a.span = d.span.p; a.tallies = d.tallies.p;
+    a.rows = d.rows.p; a.row_cap = d.rows.n;
+    return a;
+}
+// the records' anchors, spans and events (breakend_scan_kernel), on the engine stream behind the scan of the same records
+int Breakends::push(bk_engine* e, const Records& r) {
+    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
+    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_breakends_enable: a batch of 2^31 records or more");
+    bk::BreakendArgs a = breakend_args(e); a.rec = records_view(r);
+    bk::launch_breakend_scan(a, e->ix->n_cus, e->stream);
+    return BK_OK;
+}
+
+int bk_breakends_enable(bk_engine* e, const bk_breakend_config* cfg) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_breakends_enable comes between samples");
+    const IndexTables& ix = *e->ix;
+    if (cfg) {
+        if (cfg->min_clip < 16 || cfg->min_clip > 65519) return fail(BK_ERR_INVALID, "bk_breakends_enable: min_clip must be 16..65519, got %u", cfg->min_clip);
+        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_breakends_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
+        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_breakends_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
+        if (ix.n_files != 1)
+            return fail(BK_ERR_INVALID, "bk_breakends_enable: the index has %d genome files; breakends are counted against an index of one genome file", ix.n_files);
+        if (int rc = anchor_index_check(ix, "bk_breakends_enable")) return rc;
+    }
+    BK_HIP(hipSetDevice(e->device));
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
+    e->breakends.reset();
+    if (!cfg) return BK_OK;
+    std::unique_ptr<Breakends> d(new Breakends());
+    d->cfg = *cfg;
+    if (int rc = anchor_tables(e, "bk_breakends_enable", d->anchors)) return rc;
+    const size_t slots = (size_t)1 << cfg->table_log2;
+    BK_HIP(d->keys.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
+    BK_HIP(d->site.alloc(2 * (size_t)ix.total_cells));
+    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
+    BK_HIP(d->tallies.alloc(11));
+    e->breakends = std::move(d);
+    return BK_OK;
+}
+
+int bk_sample_breakends(bk_engine* e, const bk_breakend_params* p) {
+    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
+    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_breakends: min_reads must be at least 1, got 0");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_breakends comes after bk_sample_finalize");
+    if (!e->breakends || !e->breakends->in_sample)
+        return fail(BK_ERR_STATE, "bk_sample_breakends: breakends were not enabled for this sample (bk_breakends_enable before bk_sample_begin)");
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_breakends: bk_sample_finalize has not run for this sample");
+    Breakends& d = *e->breakends;
+    BK_HIP(hipSetDevice(e->device));
+    bk::BreakendArgs a = breakend_args(e);
+    a.min_reads = p->min_reads;
+    bk_engine::Span sp(e, 1);
+    if (!d.summed) { bk::launch_breakend_span_prefix(a, e->stream); d.summed = true; }
+    BK_HIP(hipMemsetAsync(d.tallies.p + 8, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
+    bk::launch_breakend_report(a, e->stream);
+    BK_HIP(hipGetLastError());
+    d.made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_breakends(bk_engine* e, bk_breakend_summary* summary, bk_breakend_record* records, uint64_t cap) {
+    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->breakends || !e->breakends->made) return fail(BK_ERR_STATE, "bk_sample_download_breakends comes after this sample's bk_sample_breakends");
+    Breakends& d = *e->breakends;
+    BK_HIP(hipSetDevice(e->device));
+    unsigned long long t[11];
+    if (int rc = download(e, t, d.tallies.p, 11)) return rc;
+    summary->records = t[0]; summary->one_anchor = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->short_ = t[4];
+    summary->through = t[5]; summary->discordant = t[6]; summary->unplaced = t[7]; summary->candidates = t[8]; summary->reported = t[9];
+    summary->overflow = t[10] ? 1 : 0;
+    if (t[10]) return fail(BK_ERR_INVALID, "bk_sample_download_breakends: more than 2^%u distinct candidate breakends: enable breakends with a larger table_log2", d.cfg.table_log2);
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[9], cap), d.rows.n);
+    if (n && records) return download(e, records, d.rows.p, (size_t)n);
+    return BK_OK;
+}
+
+int bk_sample_download_breakend_span(bk_engine* e, uint32_t* span, uint64_t cap) {
+    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->breakends || !e->breakends->made) return fail(BK_ERR_STATE, "bk_sample_download_breakend_span comes after this sample's bk_sample_breakends");
+    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_breakend_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
+    BK_HIP(hipSetDevice(e->device));
+    return download(e, span, e->breakends->span.p, (size_t)e->ix->total_cells);
 }
 
 // ---- tandem duplications and circular-origin reads (bk_duplications.hip) ---------------------------------------------

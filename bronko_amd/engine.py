@@ -546,6 +546,33 @@ class Engine:
         _check(self._L.bk_sample_download_chimera_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
         return span[:self.total_cells]
 
+    def breakends_enable(self, min_clip=20, max_mismatches=2, table_log2=16):
+        """bk_breakends_enable: breakend_scan_kernel runs behind every scan of the samples that begin from now on; min_clip=None
+        disables."""
+        cfg = None if min_clip is None else C.byref(_ffi.BreakendConfig(int(min_clip), int(max_mismatches), int(table_log2)))
+        _check(self._L.bk_breakends_enable(self.h, cfg), self._L)
+
+    def sample_breakends(self, min_reads=5):
+        """bk_sample_breakends: the finalized sample's breakends with at least min_reads reads, on the device (asynchronous)."""
+        _check(self._L.bk_sample_breakends(self.h, C.byref(_ffi.BreakendParams(int(min_reads)))), self._L)
+
+    def download_breakends(self, cap=None):
+        """(summary, rows) of sample_breakends: min(cap, summary.reported) rows (cell, tag, side, fwd, rev, site_reads, span, 0), all by
+        default, sorted."""
+        summ = _ffi.BreakendSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_breakends(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        buf = np.zeros((max(1, cap), 8), np.uint32)
+        _check(self._L.bk_sample_download_breakends(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+
+    def download_breakend_span(self):
+        """bk_sample_download_breakend_span: the prefix-summed span array of all cells (after sample_breakends)."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(self._L.bk_sample_download_breakend_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def duplications_enable(self, min_len=33, max_mismatches=2, table_log2=16):
         """bk_duplications_enable: duplication_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
         cfg = None if min_len is None else C.byref(_ffi.DuplicationConfig(int(min_len), int(max_mismatches), int(table_log2)))

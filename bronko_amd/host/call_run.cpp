@@ -215,6 +215,10 @@ std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, siz
         LOG_DEBUG(T, "--chimeras: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
+    if (shard_mode && a.breakends) {        // (likewise)
+        LOG_DEBUG(T, "--breakends: samples are not sharded over GPUs, each sample's reads go to one GPU");
+        shard_mode = false;
+    }
     if (shard_mode && a.duplications) {     // (likewise)
         LOG_DEBUG(T, "--duplications: samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
@@ -268,6 +272,8 @@ struct SampleData {
     std::vector<CopybackEvent> copybacks;
     bk_chimera_summary chsumm{};                          // --chimeras
     std::vector<ChimeraEvent> chimeras;
+    bk_breakend_summary besumm{};                         // --breakends
+    std::vector<BreakendEvent> breakends;
     bk_duplication_summary dpsumm{};                      // --duplications
     std::vector<DuplicationEvent> duplications;
     bk_link_summary lsumm{};                              // --linkage
@@ -287,6 +293,7 @@ constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's even
 constexpr uint32_t kJunctionTableLog2 = 18;   // --junctions: likewise
 constexpr uint32_t kCopybackTableLog2 = 18;   // --copybacks: likewise
 constexpr uint32_t kChimeraTableLog2 = 18;    // --chimeras: likewise
+constexpr uint32_t kBreakendTableLog2 = 18;   // --breakends: likewise
 constexpr uint32_t kDuplicationTableLog2 = 18;   // --duplications: likewise
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
@@ -344,6 +351,8 @@ struct CallRun {
             die(T, "--copybacks needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.chimeras && ix.files.size() != 1)
             die(T, "--chimeras needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        if (cfg.breakends && ix.files.size() != 1)
+            die(T, "--breakends needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.duplications && ix.files.size() != 1)
             die(T, "--duplications needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.linkage && ix.files.size() != 1)
@@ -528,6 +537,10 @@ struct CallRun {
             const bk_chimera_config xc{cfg.chimera.max_mismatches, kChimeraTableLog2};
             hip_check(bk_chimeras_enable(e, &xc), "bk_chimeras_enable");
         }
+        if (cfg.breakends) {
+            const bk_breakend_config bc{cfg.breakend.min_clip, cfg.breakend.max_mismatches, kBreakendTableLog2};
+            hip_check(bk_breakends_enable(e, &bc), "bk_breakends_enable");
+        }
         if (cfg.duplications) {
             const bk_duplication_config dc{cfg.duplication.min_len, cfg.duplication.max_mismatches, kDuplicationTableLog2};
             hip_check(bk_duplications_enable(e, &dc), "bk_duplications_enable");
@@ -581,6 +594,10 @@ struct CallRun {
         if (cfg.chimeras) {   // (likewise)
             const bk_chimera_params xp{cfg.chimera.min_reads};
             hip_check(bk_sample_chimeras(e, &xp), "bk_sample_chimeras");
+        }
+        if (cfg.breakends) {   // (likewise)
+            const bk_breakend_params bp{cfg.breakend.min_reads};
+            hip_check(bk_sample_breakends(e, &bp), "bk_sample_breakends");
         }
         if (cfg.duplications) {   // (likewise)
             const bk_duplication_params dp{cfg.duplication.min_reads};
@@ -650,6 +667,12 @@ struct CallRun {
             hip_check(bk_sample_download_chimeras(e, &d.chsumm, nullptr, 0), "bk_sample_download_chimeras");
             d.chimeras.resize((size_t)d.chsumm.reported);
             hip_check(bk_sample_download_chimeras(e, &d.chsumm, reinterpret_cast<bk_chimera_record*>(d.chimeras.data()), d.chimeras.size()), "bk_sample_download_chimeras");
+        }
+        if (cfg.breakends) {
+            static_assert(sizeof(BreakendEvent) == sizeof(bk_breakend_record), "BreakendEvent is bk_breakend_record");
+            hip_check(bk_sample_download_breakends(e, &d.besumm, nullptr, 0), "bk_sample_download_breakends");
+            d.breakends.resize((size_t)d.besumm.reported);
+            hip_check(bk_sample_download_breakends(e, &d.besumm, reinterpret_cast<bk_breakend_record*>(d.breakends.data()), d.breakends.size()), "bk_sample_download_breakends");
         }
         if (cfg.duplications) {
             static_assert(sizeof(DuplicationEvent) == sizeof(bk_duplication_record), "DuplicationEvent is bk_duplication_record");
@@ -786,6 +809,17 @@ struct CallRun {
                                 " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate chimeras, " +
                                 std::to_string(s.reported) + " reported");
                 write_chimeras_tsv(a.output + "/" + stem + ".chimeras.tsv", ix, best, d.chimeras, cfg.chimera, s.supporting, s.ref_spanning);
+            }
+            if (cfg.breakends) {       // (a sample without events: the headers alone)
+                const bk_breakend_summary& s = d.besumm;
+                LOG_INFO(T, "Breakends: " + std::to_string(s.records) + " records, " + std::to_string(s.one_anchor) + " with one anchor, " +
+                                std::to_string(s.ref_spanning) + " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.short_) +
+                                " short, " + std::to_string(s.through) + " through, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.unplaced) +
+                                " unplaced, " + std::to_string(s.candidates) + " candidate breakends, " + std::to_string(s.reported) + " reported");
+                BreakendTallies bt;
+                bt.records = s.records; bt.one_anchor = s.one_anchor; bt.ref_spanning = s.ref_spanning; bt.supporting = s.supporting; bt.short_ = s.short_;
+                bt.through = s.through; bt.discordant = s.discordant; bt.unplaced = s.unplaced; bt.candidates = s.candidates; bt.reported = s.reported;
+                write_breakends_tsv(a.output + "/" + stem + ".breakends.tsv", ix, best, d.breakends, cfg.breakend, bt);
             }
             if (cfg.duplications) {    // (a sample without events: the headers alone)
                 const bk_duplication_summary& s = d.dpsumm;

@@ -76,7 +76,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--junctions]\n"
           "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--copybacks]\n"
           "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--chimeras]\n"
-          "            [--chimera-max-mismatches M] [--chimera-min-reads N] [--duplications]\n"
+          "            [--chimera-max-mismatches M] [--chimera-min-reads N] [--breakends] [--breakend-min-clip C]\n"
+          "            [--breakend-max-mismatches M] [--breakend-min-reads N] [--duplications]\n"
           "            [--duplication-min-len L] [--duplication-max-mismatches M] [--duplication-min-reads N] [--linkage]\n"
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
@@ -134,6 +135,15 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    junction; the header gives the sample's supporting and spanning reads\n"
           "  --chimera-max-mismatches M  substitutions a read may have beside its junction; 0..8, default 2\n"
           "  --chimera-min-reads N       supporting reads an event needs to be written; at least 1, default 5\n"
+          "  --breakends       write the places where reads leave the reference to <DIR>/<stem>.breakends.tsv (an index of one genome\n"
+          "                    file): reads with an anchor at one end only -- integration junctions, junctions too near a read end for\n"
+          "                    the other reports, reads over the first or last base of a sequence, long insertions, untrimmed adapters --,\n"
+          "                    by the last reference base held, the side the read holds (L: the cells below it, R: above) and the 16\n"
+          "                    clipped bases next to it, with the reads per strand, the reads of the site over all tags, the reads that\n"
+          "                    span the site unbroken and freq = reads / (reads + span); the header gives the sample's tallies\n"
+          "  --breakend-min-clip C        clipped bases a read needs to support an event; 16..65519, default 20\n"
+          "  --breakend-max-mismatches M  substitutions the held part of a read may have; 0..8, default 2\n"
+          "  --breakend-min-reads N       supporting reads an event needs to be written; at least 1, default 5\n"
           "  --duplications    write tandem duplications and the reads across the origin of a circular genome to\n"
           "                    <DIR>/<stem>.duplications.tsv (an index of one genome file): reads whose two ends lie on diagonals of the\n"
           "                    reference L or more apart, backward on one strand of one sequence, counted on the GPU; per event the\n"
@@ -335,6 +345,17 @@ Args parse_args(int argc, char** argv) {
             if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
             if (opt == "--chimera-max-mismatches") { a.chimera_max_mismatches = x; a.has_chimera_max_mismatches = true; }
             else { a.chimera_min_reads = x; a.has_chimera_min_reads = true; }
+        }
+        else if (opt == "--breakends") a.breakends = true;
+        else if (opt == "--breakend-min-clip" || opt == "--breakend-max-mismatches" || opt == "--breakend-min-reads") {   // (any integer here: check_call_args)
+            const std::string v = one();
+            char* end = nullptr;
+            errno = 0;
+            const long x = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            if (opt == "--breakend-min-clip") { a.breakend_min_clip = x; a.has_breakend_min_clip = true; }
+            else if (opt == "--breakend-max-mismatches") { a.breakend_max_mismatches = x; a.has_breakend_max_mismatches = true; }
+            else { a.breakend_min_reads = x; a.has_breakend_min_reads = true; }
         }
         else if (opt == "--duplications") a.duplications = true;
         else if (opt == "--duplication-min-len" || opt == "--duplication-max-mismatches" || opt == "--duplication-min-reads") {   // (any integer here: check_call_args)
@@ -596,6 +617,12 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.has_chimera_min_reads && !a.chimeras) die(T, "--chimera-min-reads needs --chimeras");
     if (a.chimera_max_mismatches < 0 || a.chimera_max_mismatches > kChimeraMaxMismatches) die(T, "--chimera-max-mismatches must be between 0 and 8, got " + std::to_string(a.chimera_max_mismatches));
     if (a.chimera_min_reads < 1) die(T, "--chimera-min-reads must be at least 1, got " + std::to_string(a.chimera_min_reads));
+    if (a.has_breakend_min_clip && !a.breakends) die(T, "--breakend-min-clip needs --breakends");
+    if (a.has_breakend_max_mismatches && !a.breakends) die(T, "--breakend-max-mismatches needs --breakends");
+    if (a.has_breakend_min_reads && !a.breakends) die(T, "--breakend-min-reads needs --breakends");
+    if (a.breakend_min_clip < kBreakendMinClipLo || a.breakend_min_clip > kBreakendMinClipHi) die(T, "--breakend-min-clip must be between 16 and 65519, got " + std::to_string(a.breakend_min_clip));
+    if (a.breakend_max_mismatches < 0 || a.breakend_max_mismatches > kBreakendMaxMismatches) die(T, "--breakend-max-mismatches must be between 0 and 8, got " + std::to_string(a.breakend_max_mismatches));
+    if (a.breakend_min_reads < 1) die(T, "--breakend-min-reads must be at least 1, got " + std::to_string(a.breakend_min_reads));
     if (a.has_duplication_min_len && !a.duplications) die(T, "--duplication-min-len needs --duplications");
     if (a.has_duplication_max_mismatches && !a.duplications) die(T, "--duplication-max-mismatches needs --duplications");
     if (a.has_duplication_min_reads && !a.duplications) die(T, "--duplication-min-reads needs --duplications");
@@ -699,6 +726,9 @@ CallConfig make_call_config(const Args& a) {
     c.copyback.min_dist = (uint32_t)a.copyback_min_dist;
     c.chimeras = a.chimeras;
     c.chimera.max_mismatches = (uint32_t)a.chimera_max_mismatches; c.chimera.min_reads = (uint64_t)a.chimera_min_reads;
+    c.breakends = a.breakends;
+    c.breakend.min_clip = (uint32_t)a.breakend_min_clip; c.breakend.max_mismatches = (uint32_t)a.breakend_max_mismatches;
+    c.breakend.min_reads = (uint64_t)a.breakend_min_reads;
     c.duplications = a.duplications;
     c.duplication.min_len = (uint32_t)a.duplication_min_len; c.duplication.max_mismatches = (uint32_t)a.duplication_max_mismatches;
     c.duplication.min_reads = (uint64_t)a.duplication_min_reads;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/bronko_hip.h"
+#include "breakends.hpp"
 #include "caller.hpp"
 #include "chimeras.hpp"
 #include "codons.hpp"
@@ -88,6 +89,11 @@ struct Args {
     bool has_chimera_max_mismatches = false, has_chimera_min_reads = false;
     long chimera_max_mismatches = 2;    // --chimera-max-mismatches: substitutions a record may have beside its junction (0..8)
     long chimera_min_reads = 5;     // --chimera-min-reads: supporting records an event needs
+    bool breakends = false;         // --breakends: <DIR>/<stem>.breakends.tsv, reads that leave the reference (an anchor at one end only)
+    bool has_breakend_min_clip = false, has_breakend_max_mismatches = false, has_breakend_min_reads = false;
+    long breakend_min_clip = 20;    // --breakend-min-clip: clipped bases a record needs to support an event (16..65519)
+    long breakend_max_mismatches = 2;   // --breakend-max-mismatches: substitutions the held part of a record may have (0..8)
+    long breakend_min_reads = 5;    // --breakend-min-reads: supporting records an event needs
     bool duplications = false;      // --duplications: <DIR>/<stem>.duplications.tsv, tandem duplications and circular-origin reads
     bool has_duplication_min_len = false, has_duplication_max_mismatches = false, has_duplication_min_reads = false;
     long duplication_min_len = 33;  // --duplication-min-len: shortest backward jump counted (with 33 it begins where --indels ends)
@@ -160,6 +166,9 @@ struct CallConfig {
     // --chimeras: bk_chimeras_enable / bk_sample_chimeras and the values the .chimeras.tsv header prints
     bool chimeras = false;
     ChimeraParams chimera;
+    // --breakends: bk_breakends_enable / bk_sample_breakends and the values the .breakends.tsv header prints
+    bool breakends = false;
+    BreakendParams breakend;
     // --duplications: bk_duplications_enable / bk_sample_duplications and the values the .duplications.tsv header prints
     bool duplications = false;
     DuplicationParams duplication;

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "breakends.hpp"
 #include "caller.hpp"
 #include "chimeras.hpp"
 #include "codons.hpp"
@@ -381,6 +382,41 @@ int bh_write_chimeras_tsv(const void* h, int file_id, const char* path, const vo
         bronko::ChimeraParams p;
         p.max_mismatches = max_mismatches; p.min_reads = min_reads;
         bronko::write_chimeras_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::ChimeraEvent>(ev, ev + n), p, supporting, ref_spanning);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --breakends: the host twin of the engine's breakend pass (breakends.cpp) ----------------------------------------------
+// reads joined by '\n'; rows as bk_breakend_record (= bronko::BreakendEvent), at most cap written, *n their number; span: NULL or
+// [total_cells], prefix-summed; counters = {records, one_anchor, ref_spanning, supporting, short, through, discordant, unplaced}
+int bh_breakend_events(const void* h, int file_id, const char* reads, int min_clip, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span,
+                       uint64_t* counters) {
+    try {
+        static_assert(sizeof(bronko::BreakendEvent) == 32, "BreakendEvent is bk_breakend_record");
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const bronko::BreakendResult r = bronko::breakend_events(*ix, file_id, split_lines(reads), min_clip, max_mismatches);
+        *n = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::BreakendEvent));
+        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+        if (counters) {
+            const uint64_t c[8] = {r.n.records, r.n.one_anchor, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.through, r.n.discordant, r.n.unplaced};
+            std::memcpy(counters, c, sizeof c);
+        }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// tallies: the ten of the ##breakend_tallies line, in bk_breakend_summary's order
+int bh_write_breakends_tsv(const void* h, int file_id, const char* path, const void* rows, uint64_t n, uint32_t min_clip, uint32_t max_mismatches, uint64_t min_reads,
+                           const uint64_t* tallies) {
+    try {
+        const auto* ev = static_cast<const bronko::BreakendEvent*>(rows);
+        bronko::BreakendParams p;
+        p.min_clip = min_clip; p.max_mismatches = max_mismatches; p.min_reads = min_reads;
+        bronko::BreakendTallies t;
+        t.records = tallies[0]; t.one_anchor = tallies[1]; t.ref_spanning = tallies[2]; t.supporting = tallies[3]; t.short_ = tallies[4];
+        t.through = tallies[5]; t.discordant = tallies[6]; t.unplaced = tallies[7]; t.candidates = tallies[8]; t.reported = tallies[9];
+        bronko::write_breakends_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::BreakendEvent>(ev, ev + n), p, t);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -465,6 +465,48 @@ def write_chimeras_tsv(path, ix, file_id, rows, max_mismatches=2, min_reads=5, s
         raise _host_error(L)
 
 
+def _breakend_lib():
+    L = _caller_lib()
+    if not hasattr(L, "_breakends_ready"):
+        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+        L.bh_breakend_events.restype = C.c_int
+        L.bh_breakend_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
+        L.bh_write_breakends_tsv.restype = C.c_int
+        L.bh_write_breakends_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, u64, vp]
+        L._breakends_ready = True
+    return L
+
+
+def breakend_events(ix, file_id, reads, min_clip=20, max_mismatches=2):
+    """The host twin of the engine's breakend pass (breakends.cpp breakend_events) over ASCII reads: (rows of the whole table as
+    bk_breakend_record (cell, tag, side, fwd, rev, site_reads, span, 0) sorted, the prefix-summed span array of all cells,
+    (records, one_anchor, ref_spanning, supporting, short, through, discordant, unplaced))."""
+    L = _breakend_lib()
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    span = np.zeros(max(1, ix.total_cells), np.uint32)
+    counters = np.zeros(8, np.uint64)
+    if L.bh_breakend_events(ix.h, file_id, joined, int(min_clip), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
+        raise _host_error(L)
+    rec = np.zeros((max(1, n.value), 8), np.uint32)
+    if L.bh_breakend_events(ix.h, file_id, joined, int(min_clip), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
+        raise _host_error(L)
+    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+
+
+def write_breakends_tsv(path, ix, file_id, rows, min_clip=20, max_mismatches=2, min_reads=5, tallies=(0,) * 10):
+    """The --breakends writer (breakends.cpp write_breakends_tsv): rows as breakend_events gives them, already filtered, and the
+    sample's ten tallies (bk_breakend_summary's, without overflow) that the header prints."""
+    rec = np.zeros((max(1, len(rows)), 8), np.uint32)
+    for i, r in enumerate(rows):
+        rec[i] = r
+    t = np.array([int(v) for v in tallies], np.uint64)
+    assert t.shape == (10,)
+    L = _breakend_lib()
+    if L.bh_write_breakends_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(min_clip), int(max_mismatches), int(min_reads), t.ctypes.data) != 0:
+        raise _host_error(L)
+
+
 def _duplication_lib():
     L = _caller_lib()
     if not hasattr(L, "_duplications_ready"):

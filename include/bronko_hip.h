@@ -673,6 +673,71 @@ int  bk_sample_chimeras(bk_engine* e, const bk_chimera_params* p);
 int  bk_sample_download_chimeras(bk_engine* e, bk_chimera_summary* summary, bk_chimera_record* records, uint64_t cap);
 int  bk_sample_download_chimera_span(bk_engine* e, uint32_t* span, uint64_t cap);
 
+/* ---- reads that leave the reference: records with an anchor at one end only (`bronko call --breakends`; additive, still v8) -------
+ * Every pass above places a record by its two end anchors and drops, without a tally, the record of which only one end has an anchor.
+ * Those are the reads that run from the virus into host DNA at an integration site, the reads with a junction inside the blind margin
+ * of k + 24 bases of the other passes, the reads that run over the first or last base of a sequence, long insertions of novel sequence
+ * and untrimmed adapter read-through.  A pass of its own over each batch's records (breakend_scan_kernel, behind the scan of the same
+ * records) counts them.  The rule, all of it integer arithmetic, in the terms of bk_indels_enable:
+ *   unit, anchor k-mer, the offsets tried from each end, r'   exactly as under bk_indels_enable: a record of n < 2k is counted in
+ *              `records` and otherwise ignored.  Both ends are searched, whatever the other end gave.
+ *   two anchors    only what the span needs, exactly bk_junctions_enable's: both anchors on one strand with a + k <= b, in one sequence,
+ *              the cells [min(dL, dR), max(dL, dR) + n) inside it and ACGT only, delta = 0 and at most max_mismatches mismatches:
+ *              `ref_spanning`, +1 at cell dL + a + k, -1 at cell dL + b + 1 of this pass's own difference array `span`.  Every other
+ *              record of two anchors leaves no trace here; one of none leaves none either.
+ *   one_anchor     exactly one end has an anchor.  Oriented along the reference the anchor lies at offset a of r' at cell c; d = c - a.
+ *              s = seq(c); [lo, hi) is the stretch of ACGT letters of s around c.  side = L when the anchor is the left one of r'
+ *              (the front anchor of a record along the reference, the back anchor of one against it): the read holds a cell and the
+ *              cells below it and leaves the reference above it; else R, the mirror case.
+ *   unplaced       the anchor's cells [c, c + k) do not lie in [lo, hi) (an index k-mer reads every other letter as A, so an anchor
+ *              may lie over one); or side L and d < lo; or side R and d + n > hi: the end that is held runs off its stretch.
+ *   extension      a match scores +1, a mismatch -BK_BREAKEND_MISMATCH_PENALTY (4).
+ *              side L: P = min(n, hi - d); for p in [a + k, P]: S(p) = (p - a - k) - 5 #{j in [a + k, p): r'[j] != ref[d + j]};
+ *              p* = the smallest p with the largest S.  side R: Q = max(0, lo - d); for q in [Q, a]: S(q) = (a - q) -
+ *              5 #{j in [q, a): r'[j] != ref[d + j]}; q* = the largest q with the largest S.  A mismatch followed by four matches
+ *              is not crossed, one followed by five is.  The walk never leaves [lo, hi): it enters no run of other letters and not
+ *              the neighbouring sequence, whose cells are the next cells of the index.  Foreign bases that happen to continue the
+ *              reference are held: the breakpoint lies as far from the anchor as the reference allows.
+ *   held part      side L: r'[0, p*); side R: r'[q*, n).  m = its Hamming distance to ref on diagonal d (the mismatches in front of
+ *              an anchor found at the second to fourth offset count).  m > max_mismatches: `discordant`.
+ *   clip           n - p* (L), q* (R).  0: `through` -- the far end merely failed to anchor.  Below min_clip: `short`.  Else
+ *              `supporting`.  Every one_anchor record is in exactly one of unplaced, discordant, through, short, supporting, asked
+ *              in that order.
+ *   event          (cell, side, tag): cell = d + p* - 1 (L), d + q* (R), the last reference base held; tag = the 16 clipped bases
+ *              next to the breakpoint as they lie in r': r'[p*, p* + 16) (L), r'[q* - 16, q*) (R), base t at bits [2t, 2t + 2),
+ *              A C G T = 0 1 2 3 (min_clip >= 16: a tag always exists).  Two tags at one cell are two events.
+ *   per event      `fwd` / `rev` count the supporting records along / against the reference: a read and its reverse complement give
+ *              the same event on opposite counters.  `site_reads`: the supporting records of (cell, side) over every tag, from an
+ *              array of its own, so that events below min_reads still count.  With S the prefix sum of span: side L has span
+ *              S[cell + 1], side R S[cell] (span has total_cells + 2 entries); 0 at a terminus by construction.  Reported iff
+ *              fwd + rev >= min_reads.  Both mate files add into one table.  Key: cell | side << 27 | tag << 32 (a cell is below
+ *              2^27: never the free word).
+ *   bk_breakends_enable        as bk_junctions_enable: between samples (BK_ERR_STATE inside one); NULL disables and frees.
+ *                              min_clip 16..65519, max_mismatches 0..8, table_log2 10..24, an index of one genome file with a window
+ *                              (BK_ERR_INVALID otherwise) and a genome of k to 2^27 - 1 positions (BK_ERR_UNSUPPORTED otherwise).
+ *                              Allocates all the feature needs (the event table of 2^table_log2 slots, as many rows, the (cell, side)
+ *                              array, span; the anchor tables are shared with the other anchor passes and bk_link_enable); an engine
+ *                              that never enables it allocates and launches nothing.  Per engine: forks set their own.  A sample
+ *                              that began before the call has no events.
+ *   bk_sample_breakends        after the sample's bk_sample_finalize: BK_ERR_STATE inside a sample, before any finalize, and when
+ *                              the feature was not enabled as the sample began; BK_ERR_INVALID for min_reads == 0.  Prefix-sums
+ *                              span, selects the rows; asynchronous on the engine's stream; may be repeated with other parameters.
+ *   bk_sample_download_breakends   synchronises; copies min(cap, reported) rows in no particular order (records may be NULL).
+ *                              `candidates` = the distinct events of the sample.  A table that met more of them than it holds
+ *                              loses nothing silently: overflow = 1 in the summary and BK_ERR_INVALID ("more than 2^n distinct
+ *                              candidate breakends").
+ *   bk_sample_download_breakend_span   the prefix-summed span array of all cells (cap >= bk_total_cells, BK_ERR_INVALID otherwise).
+ * bk_breakend_record: side 0 = L, 1 = R. */
+#define BK_BREAKEND_MISMATCH_PENALTY 4
+typedef struct { uint32_t min_clip, max_mismatches, table_log2; } bk_breakend_config;   /* 16..65519, 0..8, 10..24 */
+typedef struct { uint64_t min_reads; } bk_breakend_params;
+typedef struct { uint32_t cell, tag, side, fwd, rev, site_reads, span, pad; } bk_breakend_record;
+typedef struct { uint64_t records, one_anchor, ref_spanning, supporting, short_, through, discordant, unplaced, candidates, reported; int32_t overflow; } bk_breakend_summary;
+int  bk_breakends_enable(bk_engine* e, const bk_breakend_config* cfg);
+int  bk_sample_breakends(bk_engine* e, const bk_breakend_params* p);
+int  bk_sample_download_breakends(bk_engine* e, bk_breakend_summary* summary, bk_breakend_record* records, uint64_t cap);
+int  bk_sample_download_breakend_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
 /* ---- tandem duplications and circular-origin reads (`bronko call --duplications`; additive, still v8) ----------------------------
  * The one case of a record placed by its two end anchors that the passes above leave: both anchors on one strand, the back one on a
  * diagonal behind the front one's.  bk_junctions_enable counts it `backward` and drops it.  Such a read crosses the junction between
