@@ -1,6 +1,7 @@
-// bk_anchor.h -- placing a record on the reference by two anchor k-mers: what indel_scan_kernel (bk_indels.hip), junction_scan_kernel
-// (bk_junctions.hip), copyback_scan_kernel (bk_copybacks.hip), duplication_scan_kernel (bk_duplications.hip), chimera_scan_kernel
-// (bk_chimeras.hip), breakend_scan_kernel (bk_breakends.hip) and link_scan_kernel (bk_linkage.hip) share.  The rule is DESIGN.md section I's, stated in include/bronko_hip.h (bk_indels_enable).
+// bk_anchor.h -- placing a record on the reference by two anchor k-mers: the arithmetic that the six event passes (bk_event_pass.h,
+// which holds the shape they share) and link_scan_kernel (bk_linkage.hip) share -- anchors, placement, the oriented record and its
+// breakpoint walk, the one-word event table, the prefix sum of a span array.  The rule is DESIGN.md section I's, stated in
+// include/bronko_hip.h (bk_indels_enable).
 //
 // What is read of the index is an AnchorIndex (bk_kernels.h): the perfect hash of the reference k-mers (kmer_pos, pilots, m, log2nb,
 // log2p, n_full), one bit per id that starts at exactly one cell (unique_bits), k, the sequences' first cells (seq_lo, n_seqs) and the
@@ -199,10 +200,15 @@ __device__ __forceinline__ int32_t breakpoint_walk(const OrientedRecord& rec, in
     return best;
 }
 
-// The event tables of junction_scan_kernel, duplication_scan_kernel and breakend_scan_kernel (whose `len` is a tag of 32 bits under a
-// cell below 2^28): open addressing, the key one word, cell | len << 32 (both
-// below 2^27: never the free word), claimed with one CAS; two counters a slot, along and against the reference.  A table whose every
-// slot is another event's raises *overflow: the sample's result is an error.
+// The event table of every event pass but the indels' (two key words: bk_indels.hip): open addressing, the key one word,
+// cell | len << 32, claimed with one CAS; two counters a slot, chosen by `against`.  The layouts it serves, none of which can be
+// the free word (a cell is below 2^27):
+//   junction_walk     pos | D << 32                          {fwd, rev}
+//   duplication_walk  pos | E << 32                          {fwd, rev}
+//   copyback_walk     lo | kind << 31 | hi << 32             {lo_first, hi_first}
+//   chimera_walk      lo | sides << 28 | hi << 32            {lo_first, hi_first}
+//   breakend_walk     cell | side << 27 | tag << 32          {fwd, rev}   (`len` is a tag of 32 bits: the low word below 2^28 keeps the key off the free word)
+// A table whose every slot is another event's raises *overflow: the sample's result is an error.
 constexpr unsigned long long kEventFreeWord = ~0ull;
 __device__ __forceinline__ void event_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ counts, uint32_t log2n,
                                              unsigned long long* __restrict__ overflow, uint32_t cell, uint32_t len, bool against) {

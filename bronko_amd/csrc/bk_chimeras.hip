@@ -1,36 +1,22 @@
 // bk_chimeras.hip -- junctions between two sequences of the genome file from the reads (bk_chimeras_enable; `bronko call --chimeras`).
 //
 // The rule is stated in include/bronko_hip.h and DESIGN.md section X; bronko_amd/host/chimeras.cpp and tests/chimeras_ref.py restate it.
-//   chimera_scan_kernel         behind the scan of the same records, a lane per record, shaped as copyback_scan_kernel (bk_copybacks.hip):
-//                               both ends' anchors through bk_anchor.h (end_anchors) and the sequence of each.  In one sequence and on
-//                               one strand: delta = 0 inline (the Hamming pass with an early exit, two atomics on `span`), nothing
-//                               else.  In two sequences with f + k <= g the record is rare: those are gathered in a queue of the
-//                               wave (LDS, filled through a ballot) and walked a lane each once 64 wait.  An arm that runs down the
-//                               reference is a plain diagonal of rc_words, so mismatches / sym_at of bk_anchor.h serve all four
-//                               orientations; each arm is held to its own sequence.  The walk is incremental: moving p by one
-//                               exchanges one comparison on arm A for one on arm B; the best p by (m, min(x, y)); then the two slide
-//                               loops, each cell inside its own sequence's stretch of ACGT.  Events go to bk_anchor.h's one-word
-//                               table, the key lo | sides << 28 | hi << 32 (both cells below 2^27: never the free word), the two
-//                               counters of a slot lo_first and hi_first.  The sample's tallies: one add per wave and tally.
-//   chimera_span_prefix_kernel  at the sample's end: `span` prefix-summed in place by one workgroup.
-//   chimera_report_kernel       the table's events with enough reads, appended with one returning add per wave.
+// An event pass (bk_event_pass.h: the scan's queue loop, the span of a record on one diagonal, the report's append); its own are
+//   chimera_anchor  both ends' anchors through bk_anchor.h (end_anchors) and the sequence of each.  In one sequence and on one strand:
+//                   the record on one diagonal, nothing else.  In two sequences with f + k <= g it is the rare record that is walked.
+//   chimera_walk    an arm that runs down the reference is a plain diagonal of rc_words, so mismatches / sym_at of bk_anchor.h serve
+//                   all four orientations; each arm is held to its own sequence.  Incremental: moving p by one exchanges one
+//                   comparison on arm A for one on arm B; the best p by (m, min(x, y)); then the two slide loops, each cell inside
+//                   its own sequence's stretch of ACGT.  The event goes to bk_anchor.h's one-word table (event_insert), the key
+//                   lo | sides << 28 | hi << 32, the two counters of a slot lo_first and hi_first.
+//   chimera_decode  a slot as a row: the events with enough reads pass.
 // Vector stores and atomics only.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "bk_anchor.h"
-#include "bk_scan_common.h"
+#include "bk_event_pass.h"
 
 namespace bk {
 namespace {
 
-constexpr int kChimeraBlock = 256;
-constexpr uint32_t kChimeraQueue = 128;    // entries of a wave's queue: fewer than 64 wait when up to 64 more arrive
-constexpr int kScanTallies = 6;            // records, same_strand, ref_spanning, crossed, supporting, discordant
-constexpr int kCandidates = 6, kReported = 7, kOverflow = 8;   // ChimeraArgs::tallies behind them
-
-struct ChimeraTally { uint32_t v[kScanTallies] = {0, 0, 0, 0, 0, 0}; };
+typedef EventTally<ChimeraArgs::kScanTallies> ChimeraTally;
 enum { T_RECORDS, T_SAME_STRAND, T_SPANNING, T_CROSSED, T_SUPPORTING, T_DISCORDANT };
 
 // A record's end anchors and all that needs no breakpoint.  Returns true with `work` filled for a crossed record:
@@ -56,13 +42,7 @@ __device__ __forceinline__ bool chimera_anchor(const ChimeraArgs& a, uint32_t r,
     const int32_t dL = (int32_t)an.ca - an.pa, dR = (int32_t)an.cb - an.pb;
     if (!arm_placed(a.ix, s, min(dL, dR), max(dL, dR) + n)) return false;
     if (dL != dR) return false;
-    const uint32_t last_word = (uint32_t)(n - 1) >> 4;
-    const uint32_t m = an.against ? mismatches(w, last_word, 0u, (uint32_t)n, a.ix.rc_words, (int64_t)a.ix.total_cells - dL - n, a.max_mismatches)
-                                  : mismatches(w, last_word, 0u, (uint32_t)n, a.ix.ref_words, dL, a.max_mismatches);
-    if (m > a.max_mismatches) return false;
-    t.v[T_SPANNING]++;
-    atomicAdd(a.span + (dL + an.pa + k), 1u);
-    atomicAdd(a.span + (dL + an.pb + 1), 0xffffffffu);
+    if (ref_span_count(a.ix, w, n, an, dL, a.max_mismatches, a.span)) t.v[T_SPANNING]++;
     return false;
 }
 
@@ -124,95 +104,26 @@ __device__ __forceinline__ void chimera_walk(const ChimeraArgs& a, const uint4 w
     const uint32_t side_x = a_ag ? 1u : 0u, side_y = b_ag ? 0u : 1u;   // 1 = R: the read holds the cell and the cells above it
     const uint32_t lo = (uint32_t)(a_low ? ex : ey), hi = (uint32_t)(a_low ? ey : ex);
     const uint32_t sides = a_low ? side_x | (side_y << 1) : side_y | (side_x << 1);
-    event_insert(a.keys, a.counts, a.log2n, a.tallies + kOverflow, lo | (sides << 28), hi, !a_low);
+    event_insert(a.keys, a.counts, a.log2n, a.tallies + ChimeraArgs::kOverflow, lo | (sides << 28), hi, !a_low);
 }
 
-__global__ __launch_bounds__(kChimeraBlock) void chimera_scan_kernel(ChimeraArgs a) {
-    __shared__ uint4 queue_s[kChimeraBlock / 64][kChimeraQueue];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint4* const q = queue_s[wave];
-    const uint64_t n = a.rec.n_records_dev ? std::min<uint64_t>(a.rec.n_records, *a.rec.n_records_dev) : a.rec.n_records;
-    const uint64_t stride = (uint64_t)gridDim.x * kChimeraBlock;
-    ChimeraTally t;
-    uint32_t qn = 0;                                  // records waiting in the wave's queue (the same in every lane)
-    for (uint64_t base = (uint64_t)blockIdx.x * kChimeraBlock + wave * 64u; base < n; base += stride) {
-        const uint64_t r = base + lane;
-        uint4 work = make_uint4(0u, 0u, 0u, 0u);
-        const bool slow = r < n && chimera_anchor(a, (uint32_t)r, t, work);
-        const unsigned long long mask = __ballot(slow);
-        if (mask == 0ull) continue;
-        if (slow) q[qn + lane_prefix(mask)] = work;   // (qn < 64 here and at most 64 arrive: below kChimeraQueue)
-        qn += (uint32_t)__popcll(mask);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the queue is the wave's own: its lanes' stores before its lanes' loads)
-        __builtin_amdgcn_wave_barrier();
-        if (qn >= 64u) {
-            qn -= 64u;
-            work = q[qn + lane];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            chimera_walk(a, work, t);
-        }
-    }
-    if (lane < qn) chimera_walk(a, q[lane], t);
-#pragma unroll
-    for (int i = 0; i < kScanTallies; ++i) {
-        const uint32_t sum = wave_total(t.v[i]);
-        if (lane == 0 && sum) atomicAdd(a.tallies + i, (unsigned long long)sum);
-    }
+__device__ __forceinline__ bool chimera_decode(const ChimeraArgs& a, uint64_t i, ChimeraRecordDev& row, bool& pass) {
+    const unsigned long long key = a.keys[i];
+    if (key == kEventFreeWord) return false;
+    row.lo = (uint32_t)key & 0x07ffffffu; row.hi = (uint32_t)(key >> 32); row.sides = ((uint32_t)key >> 28) & 3u;
+    row.lo_first = a.counts[2u * i]; row.hi_first = a.counts[2u * i + 1u];
+    // side L: the records that hold the cell and the one above it; (hi + 1 <= total_cells: span holds total_cells + 2)
+    row.span_lo = a.span[row.lo + ((row.sides & 1u) ? 0u : 1u)]; row.span_hi = a.span[row.hi + ((row.sides & 2u) ? 0u : 1u)];
+    pass = (unsigned long long)row.lo_first + row.hi_first >= a.min_reads;
+    return true;
 }
 
-// span[0 .. n) prefix-summed in place by one workgroup (span_prefix_block, bk_anchor.h)
-__global__ __launch_bounds__(kSpanPrefixBlock) void chimera_span_prefix_kernel(unsigned int* __restrict__ span, uint32_t n) { span_prefix_block(span, n); }
-
-__global__ __launch_bounds__(kChimeraBlock) void chimera_report_kernel(ChimeraArgs a) {
-    const uint64_t n_slots = 1ull << a.log2n;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t base = (uint64_t)blockIdx.x * kChimeraBlock + (threadIdx.x & ~63u); base < n_slots; base += (uint64_t)gridDim.x * kChimeraBlock) {
-        const uint64_t i = base + lane;
-        bool there = false, pass = false;
-        ChimeraRecordDev row{};
-        if (i < n_slots) {
-            const unsigned long long key = a.keys[i];
-            there = key != kEventFreeWord;
-            if (there) {
-                row.lo = (uint32_t)key & 0x07ffffffu; row.hi = (uint32_t)(key >> 32); row.sides = ((uint32_t)key >> 28) & 3u;
-                row.lo_first = a.counts[2u * i]; row.hi_first = a.counts[2u * i + 1u];
-                // side L: the records that hold the cell and the one above it; (hi + 1 <= total_cells: span holds total_cells + 2)
-                row.span_lo = a.span[row.lo + ((row.sides & 1u) ? 0u : 1u)]; row.span_hi = a.span[row.hi + ((row.sides & 2u) ? 0u : 1u)];
-                pass = (unsigned long long)row.lo_first + row.hi_first >= a.min_reads;
-            }
-        }
-        const unsigned long long m_there = __ballot(there), m_pass = __ballot(pass);
-        if (m_there == 0ull) continue;
-        unsigned long long at = 0ull;
-        if (lane == 0) {
-            atomicAdd(a.tallies + kCandidates, (unsigned long long)__popcll(m_there));
-            if (m_pass) at = atomicAdd(a.tallies + kReported, (unsigned long long)__popcll(m_pass));
-        }
-        at = __shfl(at, 0);
-        if (pass) {
-            const uint64_t o = at + lane_prefix(m_pass);
-            if (o < a.row_cap) a.rows[o] = row;
-        }
-    }
-}
+__global__ __launch_bounds__(kEventBlock) void chimera_scan_kernel(ChimeraArgs a) { event_scan<ChimeraArgs, chimera_anchor, chimera_walk>(a); }
+__global__ __launch_bounds__(kEventBlock) void chimera_report_kernel(ChimeraArgs a) { event_report<ChimeraArgs, ChimeraRecordDev, chimera_decode>(a); }
 
 }  // namespace
 
-void launch_chimera_scan(const ChimeraArgs& a, int n_cus, hipStream_t stream) {
-    if (a.rec.n_records == 0) return;
-    const uint64_t blocks = (a.rec.n_records + kChimeraBlock - 1) / kChimeraBlock;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
-    hipLaunchKernelGGL(chimera_scan_kernel, dim3(grid), dim3(kChimeraBlock), 0, stream, a);
-}
-
-void launch_chimera_span_prefix(const ChimeraArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(chimera_span_prefix_kernel, dim3(1), dim3(kSpanPrefixBlock), 0, stream, a.span, a.ix.total_cells + 2u);
-}
-
-void launch_chimera_report(const ChimeraArgs& a, hipStream_t stream) {
-    const uint64_t blocks = ((1ull << a.log2n) + kChimeraBlock - 1) / kChimeraBlock;
-    hipLaunchKernelGGL(chimera_report_kernel, dim3((unsigned)std::min<uint64_t>(blocks, 2048)), dim3(kChimeraBlock), 0, stream, a);
-}
+void launch_chimera_scan(const ChimeraArgs& a, int n_cus, hipStream_t stream) { launch_event_scan(chimera_scan_kernel, a, n_cus, stream); }
+void launch_chimera_report(const ChimeraArgs& a, hipStream_t stream) { launch_event_report(chimera_report_kernel, a, stream); }
 
 }  // namespace bk

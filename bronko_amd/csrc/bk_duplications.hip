@@ -1,34 +1,22 @@
 // bk_duplications.hip -- tandem duplications and the origin of a circular genome from the reads (bk_duplications_enable; `bronko call --duplications`).
 //
 // The rule is stated in include/bronko_hip.h and DESIGN.md section V; bronko_amd/host/duplications.cpp and tests/duplications_ref.py restate it.
-//   duplication_scan_kernel         behind the scan of the same records, a lane per record, shaped as junction_scan_kernel (bk_junctions.hip):
-//                                   the anchors through bk_anchor.h, delta = 0 inline (the Hamming pass with an early exit, two atomics
-//                                   on `span`), `forward` and `short` a tally each.  A backward jump of min_len or more is rare: those
-//                                   records are gathered in a queue of the wave (LDS, filled through a ballot) and walked a lane each
-//                                   once 64 wait.  What differs from the junction is asked before the queue: each arm against the
-//                                   sequence's borders and the runs of other letters on its own, and the breakpoint's range clipped to
-//                                   the sequence, so that an arm may end at the sequence's last cell or begin at its first.  The walk
-//                                   (breakpoint_walk) and the event table (event_insert, key pos | E << 32) are bk_anchor.h's, shared
-//                                   with junction_scan_kernel.  The sample's tallies: one add per wave and tally.
-//   duplication_span_prefix_kernel  at the sample's end: `span` prefix-summed in place by one workgroup.
-//   duplication_report_kernel       the table's events with enough reads, appended with one returning add per wave.
+// An event pass (bk_event_pass.h: the scan's queue loop, the span of a record on one diagonal, the report's append); its own are
+//   duplication_anchor  the anchors through bk_anchor.h; delta = 0 is the record on one diagonal, `forward` and `short` a tally each;
+//                       a backward jump of min_len or more is the rare record that is walked.  What differs from the junction is
+//                       asked here, before the queue: each arm against the sequence's borders and the runs of other letters on its
+//                       own, and the breakpoint's range clipped to the sequence, so that an arm may end at the sequence's last cell
+//                       or begin at its first.
+//   duplication_walk    the breakpoint (breakpoint_walk), the event slid down between its two floors, the table (event_insert, key
+//                       pos | E << 32): bk_anchor.h's, shared with junction_walk.
+//   duplication_decode  a slot as a row: the events with enough reads pass.
 // Vector stores and atomics only.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "bk_anchor.h"
-#include "bk_scan_common.h"
+#include "bk_event_pass.h"
 
 namespace bk {
 namespace {
 
-constexpr int kDuplicationBlock = 256;
-constexpr uint32_t kDuplicationQueue = 128;   // entries of a wave's queue: fewer than 64 wait when up to 64 more arrive
-constexpr int kScanTallies = 7;               // records, anchored, ref_spanning, supporting, short, forward, discordant
-constexpr int kCandidates = 7, kReported = 8, kOverflow = 9;   // DuplicationArgs::tallies behind them
-
-struct DuplicationTally { uint32_t v[kScanTallies] = {0, 0, 0, 0, 0, 0, 0}; };
+typedef EventTally<DuplicationArgs::kScanTallies> DuplicationTally;
 enum { T_RECORDS, T_ANCHORED, T_SPANNING, T_SUPPORTING, T_SHORT, T_FORWARD, T_DISCORDANT };
 
 // A record's anchors and all that needs no breakpoint.  Returns true with `work` filled for a record with delta <= -min_len that
@@ -49,13 +37,7 @@ __device__ __forceinline__ bool duplication_anchor(const DuplicationArgs& a, uin
     if (seq_of(a.ix, an.cb) != s) return false;
     if (delta == 0) {
         if (!arm_placed(a.ix, s, dL, dL + n)) return false;
-        const uint32_t last_word = (uint32_t)(n - 1) >> 4;
-        const uint32_t m = against ? mismatches(w, last_word, 0u, (uint32_t)n, a.ix.rc_words, (int64_t)a.ix.total_cells - dL - n, a.max_mismatches)
-                                   : mismatches(w, last_word, 0u, (uint32_t)n, a.ix.ref_words, dL, a.max_mismatches);
-        if (m > a.max_mismatches) { t.v[T_DISCORDANT]++; return false; }
-        t.v[T_SPANNING]++;
-        atomicAdd(a.span + (dL + pa + k), 1u);
-        atomicAdd(a.span + (dL + pb + 1), 0xffffffffu);
+        if (ref_span_count(a.ix, w, n, an, dL, a.max_mismatches, a.span)) t.v[T_SPANNING]++; else t.v[T_DISCORDANT]++;
         return false;
     }
     if (delta > 0) { t.v[T_FORWARD]++; return false; }
@@ -90,95 +72,26 @@ __device__ __forceinline__ void duplication_walk(const DuplicationArgs& a, const
     const int32_t FL = acgt_floor_in(a.ix, s, dL), FR = acgt_floor_in(a.ix, s, dR + p0);
     while (pos - 1 > FL && pos - E - 1 >= FR && sym_at(a.ix.ref_words, (uint32_t)(pos - 1)) == sym_at(a.ix.ref_words, (uint32_t)(pos - E - 1))) --pos;
     t.v[T_SUPPORTING]++;
-    event_insert(a.keys, a.counts, a.log2n, a.tallies + kOverflow, (uint32_t)pos, (uint32_t)E, against);
+    event_insert(a.keys, a.counts, a.log2n, a.tallies + DuplicationArgs::kOverflow, (uint32_t)pos, (uint32_t)E, against);
 }
 
-__global__ __launch_bounds__(kDuplicationBlock) void duplication_scan_kernel(DuplicationArgs a) {
-    __shared__ uint4 queue_s[kDuplicationBlock / 64][kDuplicationQueue];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint4* const q = queue_s[wave];
-    const uint64_t n = a.rec.n_records_dev ? std::min<uint64_t>(a.rec.n_records, *a.rec.n_records_dev) : a.rec.n_records;
-    const uint64_t stride = (uint64_t)gridDim.x * kDuplicationBlock;
-    DuplicationTally t;
-    uint32_t qn = 0;                                  // records waiting in the wave's queue (the same in every lane)
-    for (uint64_t base = (uint64_t)blockIdx.x * kDuplicationBlock + wave * 64u; base < n; base += stride) {
-        const uint64_t r = base + lane;
-        uint4 work = make_uint4(0u, 0u, 0u, 0u);
-        const bool slow = r < n && duplication_anchor(a, (uint32_t)r, t, work);
-        const unsigned long long mask = __ballot(slow);
-        if (mask == 0ull) continue;
-        if (slow) q[qn + lane_prefix(mask)] = work;   // (qn < 64 here and at most 64 arrive: below kDuplicationQueue)
-        qn += (uint32_t)__popcll(mask);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the queue is the wave's own: its lanes' stores before its lanes' loads)
-        __builtin_amdgcn_wave_barrier();
-        if (qn >= 64u) {
-            qn -= 64u;
-            work = q[qn + lane];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            duplication_walk(a, work, t);
-        }
-    }
-    if (lane < qn) duplication_walk(a, q[lane], t);
-#pragma unroll
-    for (int i = 0; i < kScanTallies; ++i) {
-        const uint32_t sum = wave_total(t.v[i]);
-        if (lane == 0 && sum) atomicAdd(a.tallies + i, (unsigned long long)sum);
-    }
+__device__ __forceinline__ bool duplication_decode(const DuplicationArgs& a, uint64_t i, DuplicationRecordDev& row, bool& pass) {
+    const unsigned long long key = a.keys[i];
+    if (key == kEventFreeWord) return false;
+    row.cell = (uint32_t)key; row.len = (uint32_t)(key >> 32);
+    row.fwd = a.counts[2u * i]; row.rev = a.counts[2u * i + 1u];
+    // (lo <= pos - E and pos <= hi <= total_cells: both are entries of span)
+    row.span_start = a.span[row.cell - row.len]; row.span_end = a.span[row.cell];
+    pass = (unsigned long long)row.fwd + row.rev >= a.min_reads;
+    return true;
 }
 
-// span[0 .. n) prefix-summed in place by one workgroup (span_prefix_block, bk_anchor.h)
-__global__ __launch_bounds__(kSpanPrefixBlock) void duplication_span_prefix_kernel(unsigned int* __restrict__ span, uint32_t n) { span_prefix_block(span, n); }
-
-__global__ __launch_bounds__(kDuplicationBlock) void duplication_report_kernel(DuplicationArgs a) {
-    const uint64_t n_slots = 1ull << a.log2n;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t base = (uint64_t)blockIdx.x * kDuplicationBlock + (threadIdx.x & ~63u); base < n_slots; base += (uint64_t)gridDim.x * kDuplicationBlock) {
-        const uint64_t i = base + lane;
-        bool there = false, pass = false;
-        DuplicationRecordDev row{};
-        if (i < n_slots) {
-            const unsigned long long key = a.keys[i];
-            there = key != kEventFreeWord;
-            if (there) {
-                row.cell = (uint32_t)key; row.len = (uint32_t)(key >> 32);
-                row.fwd = a.counts[2u * i]; row.rev = a.counts[2u * i + 1u];
-                // (lo <= pos - E and pos <= hi <= total_cells: both are entries of span)
-                row.span_start = a.span[row.cell - row.len]; row.span_end = a.span[row.cell];
-                pass = (unsigned long long)row.fwd + row.rev >= a.min_reads;
-            }
-        }
-        const unsigned long long m_there = __ballot(there), m_pass = __ballot(pass);
-        if (m_there == 0ull) continue;
-        unsigned long long at = 0ull;
-        if (lane == 0) {
-            atomicAdd(a.tallies + kCandidates, (unsigned long long)__popcll(m_there));
-            if (m_pass) at = atomicAdd(a.tallies + kReported, (unsigned long long)__popcll(m_pass));
-        }
-        at = __shfl(at, 0);
-        if (pass) {
-            const uint64_t o = at + lane_prefix(m_pass);
-            if (o < a.row_cap) a.rows[o] = row;
-        }
-    }
-}
+__global__ __launch_bounds__(kEventBlock) void duplication_scan_kernel(DuplicationArgs a) { event_scan<DuplicationArgs, duplication_anchor, duplication_walk>(a); }
+__global__ __launch_bounds__(kEventBlock) void duplication_report_kernel(DuplicationArgs a) { event_report<DuplicationArgs, DuplicationRecordDev, duplication_decode>(a); }
 
 }  // namespace
 
-void launch_duplication_scan(const DuplicationArgs& a, int n_cus, hipStream_t stream) {
-    if (a.rec.n_records == 0) return;
-    const uint64_t blocks = (a.rec.n_records + kDuplicationBlock - 1) / kDuplicationBlock;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
-    hipLaunchKernelGGL(duplication_scan_kernel, dim3(grid), dim3(kDuplicationBlock), 0, stream, a);
-}
-
-void launch_duplication_span_prefix(const DuplicationArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(duplication_span_prefix_kernel, dim3(1), dim3(kSpanPrefixBlock), 0, stream, a.span, a.ix.total_cells + 2u);
-}
-
-void launch_duplication_report(const DuplicationArgs& a, hipStream_t stream) {
-    const uint64_t blocks = ((1ull << a.log2n) + kDuplicationBlock - 1) / kDuplicationBlock;
-    hipLaunchKernelGGL(duplication_report_kernel, dim3((unsigned)std::min<uint64_t>(blocks, 2048)), dim3(kDuplicationBlock), 0, stream, a);
-}
+void launch_duplication_scan(const DuplicationArgs& a, int n_cus, hipStream_t stream) { launch_event_scan(duplication_scan_kernel, a, n_cus, stream); }
+void launch_duplication_report(const DuplicationArgs& a, hipStream_t stream) { launch_event_report(duplication_report_kernel, a, stream); }
 
 }  // namespace bk

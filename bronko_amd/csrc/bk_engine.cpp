@@ -272,12 +272,7 @@ int bk_sample_begin(bk_engine* e) {
     if (sel_rows) bk::launch_zero_genome_rows(e->pileup.p, (size_t)e->ix->total_cells * 4, e->ix->file_cell_lo_d.p, e->ix->n_files, (uint32_t)e->ix->total_cells, e->last_sel.p, e->stream);
     if (e->ktab.keys.p) { if (int rc = e->ktab.clear(e)) return rc; }
     if (e->dump) { if (int rc = e->dump->begin_sample(e)) return rc; }
-    if (e->indels) { if (int rc = e->indels->begin_sample(e)) return rc; }
-    if (e->junctions) { if (int rc = e->junctions->begin_sample(e)) return rc; }
-    if (e->copybacks) { if (int rc = e->copybacks->begin_sample(e)) return rc; }
-    if (e->chimeras) { if (int rc = e->chimeras->begin_sample(e)) return rc; }
-    if (e->breakends) { if (int rc = e->breakends->begin_sample(e)) return rc; }
-    if (e->duplications) { if (int rc = e->duplications->begin_sample(e)) return rc; }
+    for (EventPass* p : e->event_passes()) if (p) { if (int rc = p->begin_sample(e)) return rc; }
     if (e->linkage) { if (int rc = e->linkage->begin_sample(e)) return rc; }
     if (e->primers) { if (int rc = e->primers->begin_sample(e)) return rc; }
     if (e->adapters) { if (int rc = e->adapters->begin_sample(e)) return rc; }
@@ -601,12 +596,7 @@ int push_device(bk_engine* e, int mate, const Records& r) {
             if (int rc = level2_and_fold(e, a, mate, grid, ride ? &ride_b : nullptr)) return rc;
         }
     }
-    if (e->indels) { if (int rc = e->indels->push(e, r)) return rc; }
-    if (e->junctions) { if (int rc = e->junctions->push(e, r)) return rc; }
-    if (e->copybacks) { if (int rc = e->copybacks->push(e, r)) return rc; }
-    if (e->chimeras) { if (int rc = e->chimeras->push(e, r)) return rc; }
-    if (e->breakends) { if (int rc = e->breakends->push(e, r)) return rc; }
-    if (e->duplications) { if (int rc = e->duplications->push(e, r)) return rc; }
+    for (EventPass* p : e->event_passes()) if (p) { if (int rc = p->push(e, r)) return rc; }
     if (e->linkage) { if (int rc = e->linkage->push(e, r)) return rc; }
     BK_HIP(hipGetLastError());
     if (!r.n_dev) pl.pushed_records += n;

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -320,104 +321,44 @@ struct Linkage : StoreCount {
     int push(bk_engine* e, const Records& r);   // behind the scan of the same records, and behind the indels' pass
 };
 
-// bk_indels_enable: what indel_scan_kernel reads beside the index tables (bk_indels.hip), the sample's event table, span array and
-// tallies, and the report's rows -- all allocated by the call
-struct Indels {
-    bk_indel_config cfg{};
-    std::shared_ptr<AnchorTables> anchors;  // shared with bk_link_enable
-    DevBuf<unsigned long long> key0, key1;  // [2^table_log2] the event table's two key words (~0 = free)
-    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
-    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_indels
-    DevBuf<unsigned long long> tallies;     // [8] bk_kernels.h IndelArgs::tallies
-    DevBuf<bk_indel_record> rows;           // [2^table_log2]
+// An event pass of the engine (device side: bk_event_pass.h): what bk_indels_enable, bk_junctions_enable, bk_copybacks_enable,
+// bk_chimeras_enable, bk_breakends_enable and bk_duplications_enable each allocate alike -- the sample's event table, span array and
+// tallies -- and the sample's lifecycle (bk_riders.cpp: enable, begin_sample, push, report, download written once over these)
+struct EventPass {
+    std::shared_ptr<AnchorTables> anchors;  // shared with the other event passes and bk_link_enable
+    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word (~0 = free; its layouts: event_insert, bk_anchor.h)
+    DevBuf<unsigned int> counts;            // [2^table_log2][2] the two counters of a slot
+    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_x
+    DevBuf<unsigned long long> tallies;     // [Args::kTallies] bk_kernels.h
+    uint32_t table_log2 = 0;
     bool in_sample = false;                 // enabled when the current / last sample began
-    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_indels ran)
+    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_x ran)
     bool made = false;                      // ... and the rows are this sample's
-    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
-    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+    virtual ~EventPass() = default;
+    int begin_sample(bk_engine* e);         // an empty table, a zero span array, zero tallies
+    virtual int push(bk_engine* e, const Records& r) = 0;   // x_scan_kernel behind the scan of the same records
+    virtual int clear_table(bk_engine* e);  // the part of begin_sample a pass with more than keys and counts adds to
 };
-
-// bk_junctions_enable: the same for junction_scan_kernel (bk_junctions.hip) -- its own event table, span array, tallies and rows
-struct Junctions {
-    bk_junction_config cfg{};
-    std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable and bk_link_enable
-    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word pos | D << 32 (~0 = free)
-    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
-    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_junctions
-    DevBuf<unsigned long long> tallies;     // [10] bk_kernels.h JunctionArgs::tallies
-    DevBuf<bk_junction_record> rows;        // [2^table_log2]
-    bool in_sample = false;                 // enabled when the current / last sample began
-    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_junctions ran)
-    bool made = false;                      // ... and the rows are this sample's
-    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
-    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+// ... with what is typed by the pass: its configuration and the report's rows [2^table_log2]
+template <class Cfg, class Row>
+struct EventPassOf : EventPass {
+    Cfg cfg{};
+    DevBuf<Row> rows;
 };
-
-// bk_copybacks_enable: the same for copyback_scan_kernel (bk_copybacks.hip) -- its own event table, span array, tallies and rows
-struct Copybacks {
-    bk_copyback_config cfg{};
-    std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable, bk_junctions_enable and bk_link_enable
-    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word lo | kind << 31 | hi << 32 (~0 = free)
-    DevBuf<unsigned int> counts;            // [2^table_log2][2] lo_first, hi_first
-    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_copybacks
-    DevBuf<unsigned long long> tallies;     // [9] bk_kernels.h CopybackArgs::tallies
-    DevBuf<bk_copyback_record> rows;        // [2^table_log2]
-    bool in_sample = false;                 // enabled when the current / last sample began
-    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_copybacks ran)
-    bool made = false;                      // ... and the rows are this sample's
-    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
-    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+struct Indels : EventPassOf<bk_indel_config, bk_indel_record> {
+    DevBuf<unsigned long long> key0, key1;  // [2^table_log2] the event table's two key words, in place of `keys`
+    int push(bk_engine* e, const Records& r) override;
+    int clear_table(bk_engine* e) override;
 };
-
-// bk_chimeras_enable: the same for chimera_scan_kernel (bk_chimeras.hip) -- its own event table, span array, tallies and rows
-struct Chimeras {
-    bk_chimera_config cfg{};
-    std::shared_ptr<AnchorTables> anchors;  // shared with the other four anchor passes and bk_link_enable
-    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word lo | sides << 28 | hi << 32 (~0 = free)
-    DevBuf<unsigned int> counts;            // [2^table_log2][2] lo_first, hi_first
-    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_chimeras
-    DevBuf<unsigned long long> tallies;     // [9] bk_kernels.h ChimeraArgs::tallies
-    DevBuf<bk_chimera_record> rows;         // [2^table_log2]
-    bool in_sample = false;                 // enabled when the current / last sample began
-    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_chimeras ran)
-    bool made = false;                      // ... and the rows are this sample's
-    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
-    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
-};
-
-// bk_breakends_enable: the same for breakend_scan_kernel (bk_breakends.hip) -- its own event table, (cell, side) array, span array,
-// tallies and rows
-struct Breakends {
-    bk_breakend_config cfg{};
-    std::shared_ptr<AnchorTables> anchors;  // shared with the other anchor passes and bk_link_enable
-    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word cell | side << 27 | tag << 32 (~0 = free)
-    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
+struct Junctions : EventPassOf<bk_junction_config, bk_junction_record> { int push(bk_engine* e, const Records& r) override; };
+struct Copybacks : EventPassOf<bk_copyback_config, bk_copyback_record> { int push(bk_engine* e, const Records& r) override; };
+struct Chimeras : EventPassOf<bk_chimera_config, bk_chimera_record> { int push(bk_engine* e, const Records& r) override; };
+struct Breakends : EventPassOf<bk_breakend_config, bk_breakend_record> {
     DevBuf<unsigned int> site;              // [total_cells][2] the supporting records of every (cell, side), over every tag
-    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_breakends
-    DevBuf<unsigned long long> tallies;     // [11] bk_kernels.h BreakendArgs::tallies
-    DevBuf<bk_breakend_record> rows;        // [2^table_log2]
-    bool in_sample = false;                 // enabled when the current / last sample began
-    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_breakends ran)
-    bool made = false;                      // ... and the rows are this sample's
-    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
-    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
+    int push(bk_engine* e, const Records& r) override;
+    int clear_table(bk_engine* e) override;
 };
-
-// bk_duplications_enable: the same for duplication_scan_kernel (bk_duplications.hip) -- its own event table, span array, tallies and rows
-struct Duplications {
-    bk_duplication_config cfg{};
-    std::shared_ptr<AnchorTables> anchors;  // shared with bk_indels_enable, bk_junctions_enable, bk_copybacks_enable and bk_link_enable
-    DevBuf<unsigned long long> keys;        // [2^table_log2] the event table's key word pos | E << 32 (~0 = free)
-    DevBuf<unsigned int> counts;            // [2^table_log2][2] fwd, rev
-    DevBuf<unsigned int> span;              // [total_cells + 2] difference array; prefix-summed by the sample's first bk_sample_duplications
-    DevBuf<unsigned long long> tallies;     // [10] bk_kernels.h DuplicationArgs::tallies
-    DevBuf<bk_duplication_record> rows;     // [2^table_log2]
-    bool in_sample = false;                 // enabled when the current / last sample began
-    bool summed = false;                    // span is prefix-summed (this sample's bk_sample_duplications ran)
-    bool made = false;                      // ... and the rows are this sample's
-    int begin_sample(bk_engine* e);         // (bk_riders.cpp)
-    int push(bk_engine* e, const Records& r);   // behind the scan of the same records
-};
+struct Duplications : EventPassOf<bk_duplication_config, bk_duplication_record> { int push(bk_engine* e, const Records& r) override; };
 
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
 // by an engine and its forks, freed with the last of them.
@@ -642,6 +583,8 @@ struct bk_engine {
     std::unique_ptr<Chimeras> chimeras;     // bk_chimeras_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Breakends> breakends;   // bk_breakends_enable (null: no table, no launch, no buffers)
     std::unique_ptr<Duplications> duplications;   // bk_duplications_enable (null: no table, no launch, no buffers)
+    // the six event passes in the order they begin a sample and ride behind a scan (null: not enabled)
+    std::array<EventPass*, 6> event_passes() const { return {indels.get(), junctions.get(), copybacks.get(), chimeras.get(), breakends.get(), duplications.get()}; }
     std::unique_ptr<Linkage> linkage;       // bk_link_enable (null: no row store, no launch, no buffers)
     std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the seven features holds them
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2

@@ -1,31 +1,19 @@
 // bk_junctions.hip -- long deletions and subgenomic-RNA junctions from the reads (bk_junctions_enable; `bronko call --junctions`).
 //
 // The rule is stated in include/bronko_hip.h and DESIGN.md section J; bronko_amd/host/junctions.cpp and tests/junctions_ref.py restate it.
-//   junction_scan_kernel         behind the scan of the same records, a lane per record, shaped as indel_scan_kernel (bk_indels.hip):
-//                                the anchors through bk_anchor.h, delta = 0 inline (the Hamming pass with an early exit, two atomics
-//                                on `span`), `short` and `backward` a tally each.  A forward jump of min_len or more is rare: those
-//                                records are gathered in a queue of the wave (LDS, filled through a ballot) and walked a lane each
-//                                once 64 wait.  The walk (breakpoint_walk) and the event table (event_insert, key pos | D << 32) are
-//                                bk_anchor.h's, shared with duplication_scan_kernel.  The sample's tallies: one add per wave and tally.
-//   junction_span_prefix_kernel  at the sample's end: `span` prefix-summed in place by one workgroup.
-//   junction_report_kernel       the table's events with enough reads, appended with one returning add per wave.
+// An event pass (bk_event_pass.h: the scan's queue loop, the span of a record on one diagonal, the report's append); its own are
+//   junction_anchor  the anchors through bk_anchor.h; delta = 0 is the record on one diagonal, `short` and `backward` a tally each;
+//                    a forward jump of min_len or more is the rare record that is walked.
+//   junction_walk    the breakpoint (breakpoint_walk), the event slid down to its first cell, the table (event_insert, key
+//                    pos | D << 32): bk_anchor.h's, shared with duplication_walk.
+//   junction_decode  a slot as a row: the events with enough reads pass.
 // Vector stores and atomics only.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "bk_anchor.h"
-#include "bk_scan_common.h"
+#include "bk_event_pass.h"
 
 namespace bk {
 namespace {
 
-constexpr int kJunctionBlock = 256;
-constexpr uint32_t kJunctionQueue = 128;   // entries of a wave's queue: fewer than 64 wait when up to 64 more arrive
-constexpr int kScanTallies = 7;            // records, anchored, ref_spanning, supporting, short, backward, discordant
-constexpr int kCandidates = 7, kReported = 8, kOverflow = 9;   // JunctionArgs::tallies behind them
-
-struct JunctionTally { uint32_t v[kScanTallies] = {0, 0, 0, 0, 0, 0, 0}; };
+typedef EventTally<JunctionArgs::kScanTallies> JunctionTally;
 enum { T_RECORDS, T_ANCHORED, T_SPANNING, T_SUPPORTING, T_SHORT, T_BACKWARD, T_DISCORDANT };
 
 // A record's anchors and all that needs no breakpoint.  Returns true with `work` filled for a record with delta >= min_len that
@@ -44,13 +32,7 @@ __device__ __forceinline__ bool junction_anchor(const JunctionArgs& a, uint32_t 
     const int32_t dL = (int32_t)an.ca - pa, dR = (int32_t)an.cb - pb, delta = dR - dL;
     if (!cells_placed(a.ix, an.ca, an.cb, min(dL, dR), max(dL, dR) + n)) return false;
     if (delta == 0) {
-        const uint32_t last_word = (uint32_t)(n - 1) >> 4;
-        const uint32_t m = against ? mismatches(w, last_word, 0u, (uint32_t)n, a.ix.rc_words, (int64_t)a.ix.total_cells - dL - n, a.max_mismatches)
-                                   : mismatches(w, last_word, 0u, (uint32_t)n, a.ix.ref_words, dL, a.max_mismatches);
-        if (m > a.max_mismatches) { t.v[T_DISCORDANT]++; return false; }
-        t.v[T_SPANNING]++;
-        atomicAdd(a.span + (dL + pa + k), 1u);
-        atomicAdd(a.span + (dL + pb + 1), 0xffffffffu);
+        if (ref_span_count(a.ix, w, n, an, dL, a.max_mismatches, a.span)) t.v[T_SPANNING]++; else t.v[T_DISCORDANT]++;
         return false;
     }
     if (delta < (int32_t)a.min_len && -delta < (int32_t)a.min_len) { t.v[T_SHORT]++; return false; }
@@ -76,94 +58,25 @@ __device__ __forceinline__ void junction_walk(const JunctionArgs& a, const uint4
     const int32_t F = acgt_floor(a.ix, (uint32_t)(dL + pa), dL);
     while (pos - 1 > F && sym_at(a.ix.ref_words, (uint32_t)(pos - 1)) == sym_at(a.ix.ref_words, (uint32_t)(pos + D - 1))) --pos;
     t.v[T_SUPPORTING]++;
-    event_insert(a.keys, a.counts, a.log2n, a.tallies + kOverflow, (uint32_t)pos, (uint32_t)D, against);
+    event_insert(a.keys, a.counts, a.log2n, a.tallies + JunctionArgs::kOverflow, (uint32_t)pos, (uint32_t)D, against);
 }
 
-__global__ __launch_bounds__(kJunctionBlock) void junction_scan_kernel(JunctionArgs a) {
-    __shared__ uint4 queue_s[kJunctionBlock / 64][kJunctionQueue];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint4* const q = queue_s[wave];
-    const uint64_t n = a.rec.n_records_dev ? std::min<uint64_t>(a.rec.n_records, *a.rec.n_records_dev) : a.rec.n_records;
-    const uint64_t stride = (uint64_t)gridDim.x * kJunctionBlock;
-    JunctionTally t;
-    uint32_t qn = 0;                                  // records waiting in the wave's queue (the same in every lane)
-    for (uint64_t base = (uint64_t)blockIdx.x * kJunctionBlock + wave * 64u; base < n; base += stride) {
-        const uint64_t r = base + lane;
-        uint4 work = make_uint4(0u, 0u, 0u, 0u);
-        const bool slow = r < n && junction_anchor(a, (uint32_t)r, t, work);
-        const unsigned long long mask = __ballot(slow);
-        if (mask == 0ull) continue;
-        if (slow) q[qn + lane_prefix(mask)] = work;   // (qn < 64 here and at most 64 arrive: below kJunctionQueue)
-        qn += (uint32_t)__popcll(mask);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the queue is the wave's own: its lanes' stores before its lanes' loads)
-        __builtin_amdgcn_wave_barrier();
-        if (qn >= 64u) {
-            qn -= 64u;
-            work = q[qn + lane];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            junction_walk(a, work, t);
-        }
-    }
-    if (lane < qn) junction_walk(a, q[lane], t);
-#pragma unroll
-    for (int i = 0; i < kScanTallies; ++i) {
-        const uint32_t sum = wave_total(t.v[i]);
-        if (lane == 0 && sum) atomicAdd(a.tallies + i, (unsigned long long)sum);
-    }
+__device__ __forceinline__ bool junction_decode(const JunctionArgs& a, uint64_t i, JunctionRecordDev& row, bool& pass) {
+    const unsigned long long key = a.keys[i];
+    if (key == kEventFreeWord) return false;
+    row.cell = (uint32_t)key; row.len = (uint32_t)(key >> 32);
+    row.fwd = a.counts[2u * i]; row.rev = a.counts[2u * i + 1u];
+    row.span_donor = a.span[row.cell]; row.span_acceptor = a.span[row.cell + row.len];   // (pos + D lies inside the record's cells)
+    pass = (unsigned long long)row.fwd + row.rev >= a.min_reads;
+    return true;
 }
 
-// span[0 .. n) prefix-summed in place by one workgroup (span_prefix_block, bk_anchor.h)
-__global__ __launch_bounds__(kSpanPrefixBlock) void junction_span_prefix_kernel(unsigned int* __restrict__ span, uint32_t n) { span_prefix_block(span, n); }
-
-__global__ __launch_bounds__(kJunctionBlock) void junction_report_kernel(JunctionArgs a) {
-    const uint64_t n_slots = 1ull << a.log2n;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t base = (uint64_t)blockIdx.x * kJunctionBlock + (threadIdx.x & ~63u); base < n_slots; base += (uint64_t)gridDim.x * kJunctionBlock) {
-        const uint64_t i = base + lane;
-        bool there = false, pass = false;
-        JunctionRecordDev row{};
-        if (i < n_slots) {
-            const unsigned long long key = a.keys[i];
-            there = key != kEventFreeWord;
-            if (there) {
-                row.cell = (uint32_t)key; row.len = (uint32_t)(key >> 32);
-                row.fwd = a.counts[2u * i]; row.rev = a.counts[2u * i + 1u];
-                row.span_donor = a.span[row.cell]; row.span_acceptor = a.span[row.cell + row.len];   // (pos + D lies inside the record's cells)
-                pass = (unsigned long long)row.fwd + row.rev >= a.min_reads;
-            }
-        }
-        const unsigned long long m_there = __ballot(there), m_pass = __ballot(pass);
-        if (m_there == 0ull) continue;
-        unsigned long long at = 0ull;
-        if (lane == 0) {
-            atomicAdd(a.tallies + kCandidates, (unsigned long long)__popcll(m_there));
-            if (m_pass) at = atomicAdd(a.tallies + kReported, (unsigned long long)__popcll(m_pass));
-        }
-        at = __shfl(at, 0);
-        if (pass) {
-            const uint64_t o = at + lane_prefix(m_pass);
-            if (o < a.row_cap) a.rows[o] = row;
-        }
-    }
-}
+__global__ __launch_bounds__(kEventBlock) void junction_scan_kernel(JunctionArgs a) { event_scan<JunctionArgs, junction_anchor, junction_walk>(a); }
+__global__ __launch_bounds__(kEventBlock) void junction_report_kernel(JunctionArgs a) { event_report<JunctionArgs, JunctionRecordDev, junction_decode>(a); }
 
 }  // namespace
 
-void launch_junction_scan(const JunctionArgs& a, int n_cus, hipStream_t stream) {
-    if (a.rec.n_records == 0) return;
-    const uint64_t blocks = (a.rec.n_records + kJunctionBlock - 1) / kJunctionBlock;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cus * 8));
-    hipLaunchKernelGGL(junction_scan_kernel, dim3(grid), dim3(kJunctionBlock), 0, stream, a);
-}
-
-void launch_junction_span_prefix(const JunctionArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(junction_span_prefix_kernel, dim3(1), dim3(kSpanPrefixBlock), 0, stream, a.span, a.ix.total_cells + 2u);
-}
-
-void launch_junction_report(const JunctionArgs& a, hipStream_t stream) {
-    const uint64_t blocks = ((1ull << a.log2n) + kJunctionBlock - 1) / kJunctionBlock;
-    hipLaunchKernelGGL(junction_report_kernel, dim3((unsigned)std::min<uint64_t>(blocks, 2048)), dim3(kJunctionBlock), 0, stream, a);
-}
+void launch_junction_scan(const JunctionArgs& a, int n_cus, hipStream_t stream) { launch_event_scan(junction_scan_kernel, a, n_cus, stream); }
+void launch_junction_report(const JunctionArgs& a, hipStream_t stream) { launch_event_report(junction_report_kernel, a, stream); }
 
 }  // namespace bk

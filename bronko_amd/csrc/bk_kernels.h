@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "../../include/bronko_hip.h"
 #include "bk_device.h"
 #include "bk_link_row.h"
@@ -475,126 +477,96 @@ struct RegionArgs {
 };
 constexpr uint32_t kRegionLdsDepths = 2048;   // a region of at most this many positions is staged in LDS once (16 KB)
 void launch_region_depths(const RegionArgs& a, uint32_t max_file_regions, hipStream_t stream);
-// bk_indels_enable: short insertions and deletions from the reads (bk_indels.hip; the rule: include/bronko_hip.h, DESIGN.md section I)
-typedef bk_indel_record IndelRecordDev;
-struct IndelArgs {
-    RecordsView rec;                     // indel_scan_kernel's batch
+// The event passes (bk_event_pass.h): what the six passes below are given alike.  `tallies` holds the pass's kScanTallies scan
+// tallies, then candidates, reported, overflow (Args::kCandidates, kReported, kOverflow; kTallies words in all).  The members a scan
+// kernel reads lie in the order its arguments have always had: these kernels sit at the SGPR limit, and another order of the
+// argument block is another register allocation (profiles/README.md, the event pass).  So the word in front of max_mismatches is
+// the pass's length limit under the pass's own name -- the indels' max_len, the junctions' and duplications' min_len, the
+// breakends' min_clip; copy-backs and chimeras have none and leave it zero.  For the same reason what a pass adds to the sample's
+// arrays (`more`: the breakends' site array; an empty struct, which lies in log2n's padding, for the others) keeps its place in
+// front of span.
+struct NoSampleArrays {};
+template <class SampleArrays = NoSampleArrays>
+struct EventPassArgsOf {
+    RecordsView rec;                     // x_scan_kernel's batch
     AnchorIndex ix;
-    uint32_t max_len, max_mismatches;
-    // the sample: event table (two key words ~0 = free, {fwd, rev}), span, counters
-    unsigned long long* key0; unsigned long long* key1;
+    union { uint32_t max_len, min_len, min_clip; };
+    uint32_t max_mismatches;
+    // the sample: event table (one key word, ~0 = free; two counters a slot), span, counters
+    unsigned long long* keys;
     unsigned int* counts;                // [slots][2]
     uint32_t log2n;
+    SampleArrays more;
     unsigned int* span;                  // [total_cells + 2]
-    unsigned long long* tallies;         // [8] records, anchored, ref_spanning, supporting, discordant, candidates, reported, overflow
-    // the report: indel_report_kernel
-    uint64_t min_reads; uint32_t min_af_ppm;
-    IndelRecordDev* rows; uint64_t row_cap;
+    unsigned long long* tallies;         // [kTallies]
+    // the report: x_report_kernel
+    uint64_t min_reads, row_cap;
+};
+typedef EventPassArgsOf<> EventPassArgs;
+struct BreakendSite { unsigned int* site; };   // [total_cells][2] L, R: the supporting reads of every (cell, side)
+typedef EventPassArgsOf<BreakendSite> BreakendPassArgs;
+// (the order above, held: the limit's word directly in front of max_mismatches, span behind log2n's word, behind `site` where there is one)
+static_assert(offsetof(EventPassArgs, max_mismatches) == offsetof(EventPassArgs, min_len) + 4 && offsetof(EventPassArgs, keys) == offsetof(EventPassArgs, min_len) + 8 &&
+              offsetof(EventPassArgs, span) == offsetof(EventPassArgs, log2n) + 8 && offsetof(EventPassArgs, tallies) == offsetof(EventPassArgs, log2n) + 16,
+              "EventPassArgs: the scan kernels' argument order");
+static_assert(offsetof(BreakendPassArgs, more) == offsetof(BreakendPassArgs, log2n) + 8 && offsetof(BreakendPassArgs, span) == offsetof(BreakendPassArgs, log2n) + 16,
+              "BreakendArgs: site in front of span");
+void launch_span_prefix(unsigned int* span, uint32_t n, hipStream_t stream);   // span[0 .. n) in place, once per sample (bk_event_pass.hip)
+// bk_indels_enable: short insertions and deletions from the reads (bk_indels.hip; the rule: include/bronko_hip.h, DESIGN.md section I)
+typedef bk_indel_record IndelRecordDev;
+struct IndelArgs : EventPassArgs {       // (`keys` is not used: the table's key is two words, {fwd, rev})
+    enum { kScanTallies = 5, kCandidates = 5, kReported, kOverflow, kTallies };   // records, anchored, ref_spanning, supporting, discordant
+    uint32_t min_af_ppm;
+    unsigned long long* key0; unsigned long long* key1;
+    IndelRecordDev* rows;
 };
 void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream);
-void launch_indel_span_prefix(const IndelArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_indel_report(const IndelArgs& a, hipStream_t stream);
 // bk_junctions_enable: long deletions and subgenomic-RNA junctions from the reads (bk_junctions.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section J)
 typedef bk_junction_record JunctionRecordDev;
-struct JunctionArgs {
-    RecordsView rec;                     // junction_scan_kernel's batch
-    AnchorIndex ix;
-    uint32_t min_len, max_mismatches;
-    // the sample: event table (one key word pos | D << 32, ~0 = free, {fwd, rev}), span, counters
-    unsigned long long* keys;
-    unsigned int* counts;                // [slots][2]
-    uint32_t log2n;
-    unsigned int* span;                  // [total_cells + 2]
-    unsigned long long* tallies;         // [10] records, anchored, ref_spanning, supporting, short, backward, discordant, candidates, reported, overflow
-    // the report: junction_report_kernel
-    uint64_t min_reads;
-    JunctionRecordDev* rows; uint64_t row_cap;
+struct JunctionArgs : EventPassArgs {    // key pos | D << 32, {fwd, rev}
+    enum { kScanTallies = 7, kCandidates = 7, kReported, kOverflow, kTallies };   // records, anchored, ref_spanning, supporting, short, backward, discordant
+    JunctionRecordDev* rows;
 };
 void launch_junction_scan(const JunctionArgs& a, int n_cus, hipStream_t stream);
-void launch_junction_span_prefix(const JunctionArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_junction_report(const JunctionArgs& a, hipStream_t stream);
 // bk_copybacks_enable: strand-switch (copy-back, snap-back) junctions from the reads (bk_copybacks.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section B)
 typedef bk_copyback_record CopybackRecordDev;
-struct CopybackArgs {
-    RecordsView rec;                     // copyback_scan_kernel's batch
-    AnchorIndex ix;
-    uint32_t max_mismatches;
-    // the sample: event table (one key word lo | kind << 31 | hi << 32, ~0 = free, {lo_first, hi_first}), span, counters
-    unsigned long long* keys;
-    unsigned int* counts;                // [slots][2]
-    uint32_t log2n;
-    unsigned int* span;                  // [total_cells + 2]
-    unsigned long long* tallies;         // [9] records, same_strand, ref_spanning, switched, supporting, discordant, candidates, reported, overflow
-    // the report: copyback_report_kernel
-    uint64_t min_reads; uint32_t min_dist;
-    CopybackRecordDev* rows; uint64_t row_cap;
+struct CopybackArgs : EventPassArgs {    // key lo | kind << 31 | hi << 32, {lo_first, hi_first}
+    enum { kScanTallies = 6, kCandidates = 6, kReported, kOverflow, kTallies };   // records, same_strand, ref_spanning, switched, supporting, discordant
+    uint32_t min_dist;
+    CopybackRecordDev* rows;
 };
 void launch_copyback_scan(const CopybackArgs& a, int n_cus, hipStream_t stream);
-void launch_copyback_span_prefix(const CopybackArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_copyback_report(const CopybackArgs& a, hipStream_t stream);
 // bk_chimeras_enable: junctions between two sequences of the genome file from the reads (bk_chimeras.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section X)
 typedef bk_chimera_record ChimeraRecordDev;
-struct ChimeraArgs {
-    RecordsView rec;                     // chimera_scan_kernel's batch
-    AnchorIndex ix;
-    uint32_t max_mismatches;
-    // the sample: event table (one key word lo | sides << 28 | hi << 32, ~0 = free, {lo_first, hi_first}), span, counters
-    unsigned long long* keys;
-    unsigned int* counts;                // [slots][2]
-    uint32_t log2n;
-    unsigned int* span;                  // [total_cells + 2]
-    unsigned long long* tallies;         // [9] records, same_strand, ref_spanning, crossed, supporting, discordant, candidates, reported, overflow
-    // the report: chimera_report_kernel
-    uint64_t min_reads;
-    ChimeraRecordDev* rows; uint64_t row_cap;
+struct ChimeraArgs : EventPassArgs {     // key lo | sides << 28 | hi << 32, {lo_first, hi_first}
+    enum { kScanTallies = 6, kCandidates = 6, kReported, kOverflow, kTallies };   // records, same_strand, ref_spanning, crossed, supporting, discordant
+    ChimeraRecordDev* rows;
 };
 void launch_chimera_scan(const ChimeraArgs& a, int n_cus, hipStream_t stream);
-void launch_chimera_span_prefix(const ChimeraArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_chimera_report(const ChimeraArgs& a, hipStream_t stream);
 // bk_breakends_enable: reads that leave the reference -- records with an anchor at one end only (bk_breakends.hip; the rule:
 // include/bronko_hip.h)
 typedef bk_breakend_record BreakendRecordDev;
-struct BreakendArgs {
-    RecordsView rec;                     // breakend_scan_kernel's batch
-    AnchorIndex ix;
-    uint32_t min_clip, max_mismatches;
-    // the sample: event table (one key word cell | side << 27 | tag << 32, ~0 = free, {fwd, rev}), the supporting reads of every
-    // (cell, side), span, counters
-    unsigned long long* keys;
-    unsigned int* counts;                // [slots][2]
-    uint32_t log2n;
-    unsigned int* site;                  // [total_cells][2] L, R
-    unsigned int* span;                  // [total_cells + 2]
-    unsigned long long* tallies;         // [11] records, one_anchor, ref_spanning, supporting, short, through, discordant, unplaced, candidates, reported, overflow
-    // the report: breakend_report_kernel
-    uint64_t min_reads;
-    BreakendRecordDev* rows; uint64_t row_cap;
+struct BreakendArgs : BreakendPassArgs {    // key cell | side << 27 | tag << 32, {fwd, rev}
+    enum { kScanTallies = 8, kCandidates = 8, kReported, kOverflow, kTallies };   // records, one_anchor, ref_spanning, supporting, short, through, discordant, unplaced
+    BreakendRecordDev* rows;
 };
 void launch_breakend_scan(const BreakendArgs& a, int n_cus, hipStream_t stream);
-void launch_breakend_span_prefix(const BreakendArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_breakend_report(const BreakendArgs& a, hipStream_t stream);
 // bk_duplications_enable: tandem duplications and circular-origin reads (bk_duplications.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section V)
 typedef bk_duplication_record DuplicationRecordDev;
-struct DuplicationArgs {
-    RecordsView rec;                     // duplication_scan_kernel's batch
-    AnchorIndex ix;
-    uint32_t min_len, max_mismatches;
-    // the sample: event table (one key word pos | E << 32, ~0 = free, {fwd, rev}), span, counters
-    unsigned long long* keys;
-    unsigned int* counts;                // [slots][2]
-    uint32_t log2n;
-    unsigned int* span;                  // [total_cells + 2]
-    unsigned long long* tallies;         // [10] records, anchored, ref_spanning, supporting, short, forward, discordant, candidates, reported, overflow
-    // the report: duplication_report_kernel
-    uint64_t min_reads;
-    DuplicationRecordDev* rows; uint64_t row_cap;
+struct DuplicationArgs : EventPassArgs { // key pos | E << 32, {fwd, rev}
+    enum { kScanTallies = 7, kCandidates = 7, kReported, kOverflow, kTallies };   // records, anchored, ref_spanning, supporting, short, forward, discordant
+    DuplicationRecordDev* rows;
 };
 void launch_duplication_scan(const DuplicationArgs& a, int n_cus, hipStream_t stream);
-void launch_duplication_span_prefix(const DuplicationArgs& a, hipStream_t stream);   // span in place, once per sample
 void launch_duplication_report(const DuplicationArgs& a, hipStream_t stream);
 // bk_link_enable: which substitutions the same records carry (bk_linkage.hip; the rule: include/bronko_hip.h)
 struct LinkArgs {

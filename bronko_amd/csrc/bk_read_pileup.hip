@@ -13,7 +13,7 @@
 //                              merged first: a ballot on the leader's index, one add of the popcount, at most kMergeRounds rounds and
 //                              none after a round in which the leader stood alone; what is left takes single adds.  No LDS: the indices
 //                              range over fifteen words a cell of a genome of up to 2^22 cells, which no dense table in LDS holds.
-//   read_pileup_finish_kernel  one workgroup, as indel_span_prefix_kernel: a thread sums its stretch of the three difference arrays,
+//   read_pileup_finish_kernel  one workgroup, as span_prefix_kernel (bk_event_pass.hip): a thread sums its stretch of the three difference arrays,
 //                              the stretches' sums are scanned through LDS, the thread walks its stretch again and writes per cell one
 //                              bk_read_pileup_cell (three 16-byte stores): a base other than the reference's takes its mm counts, the
 //                              reference's base cover - sum mm per strand and near_cover - sum mm_near.  A cell whose reference letter

@@ -1,14 +1,14 @@
 // bk_riders.cpp -- the passes that ride behind every scan of a sample, each owning its part of it: the k-mer dump (bk_kmer_dump.hip),
-// short insertions and deletions (bk_indels.hip), junctions (bk_junctions.hip), copy-backs (bk_copybacks.hip), chimeras
-// (bk_chimeras.hip), breakends (bk_breakends.hip), duplications (bk_duplications.hip) and linkage (bk_linkage.hip), with the anchor tables the last seven share, and the codon
-// haplotype and read-pileup counts that read linkage's row store at the sample's end (bk_codons.hip, bk_haplotypes.hip,
-// bk_read_pileup.hip).  The four counts over the store (bk_sample_linkage, bk_sample_codons, bk_sample_haplotypes, bk_sample_read_pileup)
-// share one lifecycle, StoreCount of bk_engine.h, and the helpers in front of them here: what they ask of the engine's state, of a
-// region's cells, and how their tables reach the device.
+// the six event passes (bk_event_pass.h: indels, junctions, copy-backs, chimeras, breakends, duplications) and linkage
+// (bk_linkage.hip), with the anchor tables the last seven share, and the codon, haplotype and read-pileup counts that read linkage's
+// row store at the sample's end (bk_codons.hip, bk_haplotypes.hip, bk_read_pileup.hip).  The event passes share one lifecycle,
+// EventPass of bk_engine.h, written once here over a description of each pass.  The four counts over the store (bk_sample_linkage,
+// bk_sample_codons, bk_sample_haplotypes, bk_sample_read_pileup) share another, StoreCount of bk_engine.h, and the helpers in front
+// of them here: what they ask of the engine's state, of a region's cells, and how their tables reach the device.
 // Each is a struct of bk_engine.h, null in the engine until its bk_*_enable: begin_sample empties what the sample fills (bk_sample_begin),
 // push launches its kernel on the engine's stream next to the scan of the same records (push_device: the dump in front of the scan,
-// indels, junctions, copy-backs, chimeras, breakends, duplications, then linkage behind it); the dump's finalize ends bk_sample_finalize.  With each, its entry points of the C ABI (extern "C"
-// by their declarations in bronko_hip.h).
+// the event passes in the order of bk_engine::event_passes, then linkage behind it); the dump's finalize ends bk_sample_finalize.
+// With each, its entry points of the C ABI (extern "C" by their declarations in bronko_hip.h).
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -174,607 +174,366 @@ static bk::AnchorIndex anchor_index(const IndexTables& ix, const AnchorTables& t
     return a;
 }
 
-// ---- short insertions and deletions from the reads (bk_indels.hip) ------------------------------------------------
+// ---- the event passes: indels, junctions, copy-backs, chimeras, breakends, duplications (bk_event_pass.h) ------------------------
+// One lifecycle, written once over a pass's description P: enable (checks, sync, reset, allocation), begin_sample, push (x_scan_kernel),
+// report (span prefix once per sample, x_report_kernel), download, span download.  A description names the pass's types, its slot
+// in the engine, its launches, its texts, and the hooks below where it has more than the common part.
 // the sample starts from an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
-int Indels::begin_sample(bk_engine* e) {
+int EventPass::clear_table(bk_engine* e) {
+    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
+    return BK_OK;
+}
+int Indels::clear_table(bk_engine* e) {
     BK_HIP(hipMemsetAsync(key0.p, 0xff, key0.n * sizeof(unsigned long long), e->stream));
     BK_HIP(hipMemsetAsync(key1.p, 0xff, key1.n * sizeof(unsigned long long), e->stream));
     BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
-    in_sample = true; summed = false; made = false;
     return BK_OK;
 }
-// what every indel kernel is given (a.rec: the scan's batch)
-static bk::IndelArgs indel_args(const bk_engine* e) {
-    const Indels& d = *e->indels;
-    bk::IndelArgs a{};
-    a.ix = anchor_index(*e->ix, *d.anchors);
-    a.max_len = d.cfg.max_len; a.max_mismatches = d.cfg.max_mismatches;
-    a.key0 = d.key0.p; a.key1 = d.key1.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
-    a.span = d.span.p; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n;
-    return a;
-}
-// the records' anchors, spans and events (indel_scan_kernel), on the engine stream behind the scan of the same records
-int Indels::push(bk_engine* e, const Records& r) {
-    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_indels_enable: a batch of 2^31 records or more");
-    bk::IndelArgs a = indel_args(e); a.rec = records_view(r);
-    bk::launch_indel_scan(a, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
-
-int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_indels_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->max_len < 1 || cfg->max_len > BK_INDEL_MAX_LEN) return fail(BK_ERR_INVALID, "bk_indels_enable: max_len must be 1..%d, got %u", BK_INDEL_MAX_LEN, cfg->max_len);
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_indels_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_indels_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_indels_enable: the index has %d genome files; indels are called against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_indels_enable")) return rc;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->indels.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Indels> d(new Indels());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_indels_enable", d->anchors)) return rc;
-    const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->key0.alloc(slots)); BK_HIP(d->key1.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
-    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(8));
-    e->indels = std::move(d);
-    return BK_OK;
-}
-
-int bk_sample_indels(bk_engine* e, const bk_indel_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_indels: min_reads must be at least 1, got 0");
-    if (p->min_af_ppm > 1000000u) return fail(BK_ERR_INVALID, "bk_sample_indels: min_af_ppm must be 0..1000000, got %u", p->min_af_ppm);
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels comes after bk_sample_finalize");
-    if (!e->indels || !e->indels->in_sample) return fail(BK_ERR_STATE, "bk_sample_indels: indels were not enabled for this sample (bk_indels_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_indels: bk_sample_finalize has not run for this sample");
-    Indels& d = *e->indels;
-    BK_HIP(hipSetDevice(e->device));
-    bk::IndelArgs a = indel_args(e);
-    a.min_reads = p->min_reads; a.min_af_ppm = p->min_af_ppm;
-    bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_indel_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 5, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_indel_report(a, e->stream);
-    BK_HIP(hipGetLastError());
-    d.made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indels comes after this sample's bk_sample_indels");
-    Indels& d = *e->indels;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[8];
-    if (int rc = download(e, t, d.tallies.p, 8)) return rc;
-    summary->records = t[0]; summary->anchored = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->discordant = t[4];
-    summary->candidates = t[5]; summary->reported = t[6]; summary->overflow = t[7] ? 1 : 0;
-    if (t[7]) return fail(BK_ERR_INVALID, "bk_sample_download_indels: more than 2^%u distinct candidate events: enable indels with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[6], cap), d.rows.n);
-    if (n && records) return download(e, records, d.rows.p, (size_t)n);
-    return BK_OK;
-}
-
-int bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap) {
-    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->indels || !e->indels->made) return fail(BK_ERR_STATE, "bk_sample_download_indel_span comes after this sample's bk_sample_indels");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_indel_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
-    BK_HIP(hipSetDevice(e->device));
-    return download(e, span, e->indels->span.p, (size_t)e->ix->total_cells);
-}
-
-// ---- long deletions and subgenomic-RNA junctions from the reads (bk_junctions.hip) ------------------------------------
-// the sample starts from an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
-int Junctions::begin_sample(bk_engine* e) {
-    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
-    in_sample = true; summed = false; made = false;
-    return BK_OK;
-}
-// what every junction kernel is given (a.rec: the scan's batch)
-static bk::JunctionArgs junction_args(const bk_engine* e) {
-    const Junctions& d = *e->junctions;
-    bk::JunctionArgs a{};
-    a.ix = anchor_index(*e->ix, *d.anchors);
-    a.min_len = d.cfg.min_len; a.max_mismatches = d.cfg.max_mismatches;
-    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
-    a.span = d.span.p; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n;
-    return a;
-}
-// the records' anchors, spans and events (junction_scan_kernel), on the engine stream behind the scan of the same records
-int Junctions::push(bk_engine* e, const Records& r) {
-    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_junctions_enable: a batch of 2^31 records or more");
-    bk::JunctionArgs a = junction_args(e); a.rec = records_view(r);
-    bk::launch_junction_scan(a, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
-
-int bk_junctions_enable(bk_engine* e, const bk_junction_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_junctions_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->min_len < 1 || cfg->min_len > BK_JUNCTION_MAX_LEN) return fail(BK_ERR_INVALID, "bk_junctions_enable: min_len must be 1..%u, got %u", BK_JUNCTION_MAX_LEN, cfg->min_len);
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_junctions_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_junctions_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_junctions_enable: the index has %d genome files; junctions are counted against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_junctions_enable")) return rc;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->junctions.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Junctions> d(new Junctions());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_junctions_enable", d->anchors)) return rc;
-    const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->keys.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
-    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(10));
-    e->junctions = std::move(d);
-    return BK_OK;
-}
-
-int bk_sample_junctions(bk_engine* e, const bk_junction_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_junctions: min_reads must be at least 1, got 0");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_junctions comes after bk_sample_finalize");
-    if (!e->junctions || !e->junctions->in_sample)
-        return fail(BK_ERR_STATE, "bk_sample_junctions: junctions were not enabled for this sample (bk_junctions_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_junctions: bk_sample_finalize has not run for this sample");
-    Junctions& d = *e->junctions;
-    BK_HIP(hipSetDevice(e->device));
-    bk::JunctionArgs a = junction_args(e);
-    a.min_reads = p->min_reads;
-    bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_junction_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 7, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_junction_report(a, e->stream);
-    BK_HIP(hipGetLastError());
-    d.made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_junctions(bk_engine* e, bk_junction_summary* summary, bk_junction_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->junctions || !e->junctions->made) return fail(BK_ERR_STATE, "bk_sample_download_junctions comes after this sample's bk_sample_junctions");
-    Junctions& d = *e->junctions;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[10];
-    if (int rc = download(e, t, d.tallies.p, 10)) return rc;
-    summary->records = t[0]; summary->anchored = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->short_ = t[4];
-    summary->backward = t[5]; summary->discordant = t[6]; summary->candidates = t[7]; summary->reported = t[8]; summary->overflow = t[9] ? 1 : 0;
-    if (t[9]) return fail(BK_ERR_INVALID, "bk_sample_download_junctions: more than 2^%u distinct candidate junctions: enable junctions with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[8], cap), d.rows.n);
-    if (n && records) return download(e, records, d.rows.p, (size_t)n);
-    return BK_OK;
-}
-
-int bk_sample_download_junction_span(bk_engine* e, uint32_t* span, uint64_t cap) {
-    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->junctions || !e->junctions->made) return fail(BK_ERR_STATE, "bk_sample_download_junction_span comes after this sample's bk_sample_junctions");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_junction_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
-    BK_HIP(hipSetDevice(e->device));
-    return download(e, span, e->junctions->span.p, (size_t)e->ix->total_cells);
-}
-
-// ---- strand-switch (copy-back) junctions from the reads (bk_copybacks.hip) --------------------------------------------
-// the sample starts from an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
-int Copybacks::begin_sample(bk_engine* e) {
-    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
-    in_sample = true; summed = false; made = false;
-    return BK_OK;
-}
-// what every copy-back kernel is given (a.rec: the scan's batch)
-static bk::CopybackArgs copyback_args(const bk_engine* e) {
-    const Copybacks& d = *e->copybacks;
-    bk::CopybackArgs a{};
-    a.ix = anchor_index(*e->ix, *d.anchors);
-    a.max_mismatches = d.cfg.max_mismatches;
-    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
-    a.span = d.span.p; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n;
-    return a;
-}
-// the records' anchors, spans and events (copyback_scan_kernel), on the engine stream behind the scan of the same records
-int Copybacks::push(bk_engine* e, const Records& r) {
-    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_copybacks_enable: a batch of 2^31 records or more");
-    bk::CopybackArgs a = copyback_args(e); a.rec = records_view(r);
-    bk::launch_copyback_scan(a, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
-
-int bk_copybacks_enable(bk_engine* e, const bk_copyback_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_copybacks_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_copybacks_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_copybacks_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_copybacks_enable: the index has %d genome files; copy-backs are counted against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_copybacks_enable")) return rc;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->copybacks.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Copybacks> d(new Copybacks());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_copybacks_enable", d->anchors)) return rc;
-    const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->keys.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
-    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(9));
-    e->copybacks = std::move(d);
-    return BK_OK;
-}
-
-int bk_sample_copybacks(bk_engine* e, const bk_copyback_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_copybacks: min_reads must be at least 1, got 0");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_copybacks comes after bk_sample_finalize");
-    if (!e->copybacks || !e->copybacks->in_sample)
-        return fail(BK_ERR_STATE, "bk_sample_copybacks: copy-backs were not enabled for this sample (bk_copybacks_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_copybacks: bk_sample_finalize has not run for this sample");
-    Copybacks& d = *e->copybacks;
-    BK_HIP(hipSetDevice(e->device));
-    bk::CopybackArgs a = copyback_args(e);
-    a.min_reads = p->min_reads; a.min_dist = p->min_dist;
-    bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_copyback_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 6, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_copyback_report(a, e->stream);
-    BK_HIP(hipGetLastError());
-    d.made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_copybacks(bk_engine* e, bk_copyback_summary* summary, bk_copyback_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->copybacks || !e->copybacks->made) return fail(BK_ERR_STATE, "bk_sample_download_copybacks comes after this sample's bk_sample_copybacks");
-    Copybacks& d = *e->copybacks;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[9];
-    if (int rc = download(e, t, d.tallies.p, 9)) return rc;
-    summary->records = t[0]; summary->same_strand = t[1]; summary->ref_spanning = t[2]; summary->switched = t[3]; summary->supporting = t[4];
-    summary->discordant = t[5]; summary->candidates = t[6]; summary->reported = t[7]; summary->overflow = t[8] ? 1 : 0;
-    if (t[8]) return fail(BK_ERR_INVALID, "bk_sample_download_copybacks: more than 2^%u distinct candidate copy-backs: enable copy-backs with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[7], cap), d.rows.n);
-    if (n && records) return download(e, records, d.rows.p, (size_t)n);
-    return BK_OK;
-}
-
-int bk_sample_download_copyback_span(bk_engine* e, uint32_t* span, uint64_t cap) {
-    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->copybacks || !e->copybacks->made) return fail(BK_ERR_STATE, "bk_sample_download_copyback_span comes after this sample's bk_sample_copybacks");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_copyback_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
-    BK_HIP(hipSetDevice(e->device));
-    return download(e, span, e->copybacks->span.p, (size_t)e->ix->total_cells);
-}
-
-// ---- junctions between two sequences of the genome file from the reads (bk_chimeras.hip) ------------------------------
-// the sample starts from an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
-int Chimeras::begin_sample(bk_engine* e) {
-    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
-    in_sample = true; summed = false; made = false;
-    return BK_OK;
-}
-// what every chimera kernel is given (a.rec: the scan's batch)
-static bk::ChimeraArgs chimera_args(const bk_engine* e) {
-    const Chimeras& d = *e->chimeras;
-    bk::ChimeraArgs a{};
-    a.ix = anchor_index(*e->ix, *d.anchors);
-    a.max_mismatches = d.cfg.max_mismatches;
-    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
-    a.span = d.span.p; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n;
-    return a;
-}
-// the records' anchors, spans and events (chimera_scan_kernel), on the engine stream behind the scan of the same records
-int Chimeras::push(bk_engine* e, const Records& r) {
-    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_chimeras_enable: a batch of 2^31 records or more");
-    bk::ChimeraArgs a = chimera_args(e); a.rec = records_view(r);
-    bk::launch_chimera_scan(a, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
-
-int bk_chimeras_enable(bk_engine* e, const bk_chimera_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_chimeras_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_chimeras_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_chimeras_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_chimeras_enable: the index has %d genome files; chimeras are counted between the sequences of an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_chimeras_enable")) return rc;
-    }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->chimeras.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Chimeras> d(new Chimeras());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_chimeras_enable", d->anchors)) return rc;
-    const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->keys.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
-    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(9));
-    e->chimeras = std::move(d);
-    return BK_OK;
-}
-
-int bk_sample_chimeras(bk_engine* e, const bk_chimera_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_chimeras: min_reads must be at least 1, got 0");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_chimeras comes after bk_sample_finalize");
-    if (!e->chimeras || !e->chimeras->in_sample)
-        return fail(BK_ERR_STATE, "bk_sample_chimeras: chimeras were not enabled for this sample (bk_chimeras_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_chimeras: bk_sample_finalize has not run for this sample");
-    Chimeras& d = *e->chimeras;
-    BK_HIP(hipSetDevice(e->device));
-    bk::ChimeraArgs a = chimera_args(e);
-    a.min_reads = p->min_reads;
-    bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_chimera_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 6, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_chimera_report(a, e->stream);
-    BK_HIP(hipGetLastError());
-    d.made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_chimeras(bk_engine* e, bk_chimera_summary* summary, bk_chimera_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->chimeras || !e->chimeras->made) return fail(BK_ERR_STATE, "bk_sample_download_chimeras comes after this sample's bk_sample_chimeras");
-    Chimeras& d = *e->chimeras;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[9];
-    if (int rc = download(e, t, d.tallies.p, 9)) return rc;
-    summary->records = t[0]; summary->same_strand = t[1]; summary->ref_spanning = t[2]; summary->crossed = t[3]; summary->supporting = t[4];
-    summary->discordant = t[5]; summary->candidates = t[6]; summary->reported = t[7]; summary->overflow = t[8] ? 1 : 0;
-    if (t[8]) return fail(BK_ERR_INVALID, "bk_sample_download_chimeras: more than 2^%u distinct candidate chimeras: enable chimeras with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[7], cap), d.rows.n);
-    if (n && records) return download(e, records, d.rows.p, (size_t)n);
-    return BK_OK;
-}
-
-int bk_sample_download_chimera_span(bk_engine* e, uint32_t* span, uint64_t cap) {
-    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->chimeras || !e->chimeras->made) return fail(BK_ERR_STATE, "bk_sample_download_chimera_span comes after this sample's bk_sample_chimeras");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_chimera_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
-    BK_HIP(hipSetDevice(e->device));
-    return download(e, span, e->chimeras->span.p, (size_t)e->ix->total_cells);
-}
-
-// ---- reads that leave the reference: records with an anchor at one end only (bk_breakends.hip) ------------------------
-// the sample starts from an empty table, zero (cell, side) and span arrays, zero tallies (an abandoned sample leaves nothing behind)
-int Breakends::begin_sample(bk_engine* e) {
-    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
+int Breakends::clear_table(bk_engine* e) {
+    if (int rc = EventPass::clear_table(e)) return rc;
     BK_HIP(hipMemsetAsync(site.p, 0, site.n * sizeof(unsigned int), e->stream));
+    return BK_OK;
+}
+int EventPass::begin_sample(bk_engine* e) {
+    if (int rc = clear_table(e)) return rc;
     BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
     BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
     in_sample = true; summed = false; made = false;
     return BK_OK;
 }
-// what every breakend kernel is given (a.rec: the scan's batch)
-static bk::BreakendArgs breakend_args(const bk_engine* e) {
-    const Breakends& d = *e->breakends;
-    bk::BreakendArgs a{};
-    a.ix = anchor_index(*e->ix, *d.anchors);
-    a.min_clip = d.cfg.min_clip; a.max_mismatches = d.cfg.max_mismatches;
-    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
-    a.site = d.site.p; a.span = d.span.p; a.tallies = d.tallies.p;
-    a.rows = d.rows.p; a.row_cap = d.rows.n;
-    return a;
-}
-// the records' anchors, spans and events (breakend_scan_kernel), on the engine stream behind the scan of the same records
-int Breakends::push(bk_engine* e, const Records& r) {
-    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_breakends_enable: a batch of 2^31 records or more");
-    bk::BreakendArgs a = breakend_args(e); a.rec = records_view(r);
-    bk::launch_breakend_scan(a, e->ix->n_cus, e->stream);
-    return BK_OK;
-}
 
-int bk_breakends_enable(bk_engine* e, const bk_breakend_config* cfg) {
-    if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_breakends_enable comes between samples");
-    const IndexTables& ix = *e->ix;
-    if (cfg) {
-        if (cfg->min_clip < 16 || cfg->min_clip > 65519) return fail(BK_ERR_INVALID, "bk_breakends_enable: min_clip must be 16..65519, got %u", cfg->min_clip);
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_breakends_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_breakends_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_breakends_enable: the index has %d genome files; breakends are counted against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_breakends_enable")) return rc;
+// What bk_last_error says of a pass, each text whole: the nouns and the entry points' names follow no one pattern.  A text reaches
+// fail() as a runtime format, so the compiler does not check it against its arguments: each field has one call site below, which
+// passes exactly the conversions noted here, cast to their types there.
+struct PassText {
+    const char* enable;          // the entry point that enables it (the `who` of the anchor tables' texts)
+    const char* between;         // bk_x_enable inside a sample
+    const char* mismatches;      // (%u) cfg->max_mismatches
+    const char* table;           // (%u) cfg->table_log2
+    const char* one_file;        // (%d) the index's genome files
+    const char* batch;           // push: 2^31 records
+    const char* min_reads;       // bk_sample_x: min_reads 0
+    const char* in_sample;       // ... inside a sample
+    const char* not_enabled;     // ... not enabled when the sample began
+    const char* not_finalized;   // ... before bk_sample_finalize
+    const char* download_early;  // bk_sample_download_x before bk_sample_x
+    const char* overflow;        // (%u) a full table
+    const char* span_early;      // bk_sample_download_x_span before bk_sample_x
+    const char* span_room;       // (%llu, %llu) cap, the index's cells
+};
+// the hooks of a pass with nothing to add
+struct PassDefaults {
+    template <class Cfg> static int check(const Cfg&) { return BK_OK; }             // the cfg checks in front of max_mismatches
+    template <class Params> static int check_params(const Params&) { return BK_OK; }   // the params checks behind min_reads
+    template <class Args, class State> static void extras(Args&, const State&) {}   // the args beside the common part
+    template <class Args, class Params> static void params(Args&, const Params&) {} // the report's thresholds beside min_reads
+    template <class State> static int alloc_table(State* d, size_t slots) { BK_HIP(d->keys.alloc(slots)); return BK_OK; }
+    template <class State> static int alloc_extras(State*, const IndexTables&) { return BK_OK; }   // between rows and span
+};
+
+struct IndelPass : PassDefaults {
+    typedef Indels State; typedef bk::IndelArgs Args; typedef bk_indel_config Cfg; typedef bk_indel_params Params;
+    typedef bk_indel_summary Summary; typedef bk_indel_record Record;
+    static std::unique_ptr<State>& slot(bk_engine* e) { return e->indels; }
+    static constexpr auto scan = bk::launch_indel_scan; static constexpr auto report = bk::launch_indel_report;
+    static constexpr PassText text = {
+        "bk_indels_enable",
+        "bk_indels_enable comes between samples",
+        "bk_indels_enable: max_mismatches must be 0..8, got %u",
+        "bk_indels_enable: table_log2 must be 10..24, got %u",
+        "bk_indels_enable: the index has %d genome files; indels are called against an index of one genome file",
+        "bk_indels_enable: a batch of 2^31 records or more",
+        "bk_sample_indels: min_reads must be at least 1, got 0",
+        "bk_sample_indels comes after bk_sample_finalize",
+        "bk_sample_indels: indels were not enabled for this sample (bk_indels_enable before bk_sample_begin)",
+        "bk_sample_indels: bk_sample_finalize has not run for this sample",
+        "bk_sample_download_indels comes after this sample's bk_sample_indels",
+        "bk_sample_download_indels: more than 2^%u distinct candidate events: enable indels with a larger table_log2",
+        "bk_sample_download_indel_span comes after this sample's bk_sample_indels",
+        "bk_sample_download_indel_span: room for %llu cells, the index has %llu"};
+    static int check(const Cfg& c) {
+        if (c.max_len < 1 || c.max_len > BK_INDEL_MAX_LEN) return fail(BK_ERR_INVALID, "bk_indels_enable: max_len must be 1..%d, got %u", BK_INDEL_MAX_LEN, c.max_len);
+        return BK_OK;
     }
-    BK_HIP(hipSetDevice(e->device));
-    BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->breakends.reset();
-    if (!cfg) return BK_OK;
-    std::unique_ptr<Breakends> d(new Breakends());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_breakends_enable", d->anchors)) return rc;
-    const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->keys.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
-    BK_HIP(d->site.alloc(2 * (size_t)ix.total_cells));
-    BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(11));
-    e->breakends = std::move(d);
-    return BK_OK;
-}
+    static int check_params(const Params& p) {
+        if (p.min_af_ppm > 1000000u) return fail(BK_ERR_INVALID, "bk_sample_indels: min_af_ppm must be 0..1000000, got %u", p.min_af_ppm);
+        return BK_OK;
+    }
+    static void extras(Args& a, const State& d) { a.max_len = d.cfg.max_len; a.key0 = d.key0.p; a.key1 = d.key1.p; }
+    static void params(Args& a, const Params& p) { a.min_af_ppm = p.min_af_ppm; }
+    static int alloc_table(State* d, size_t slots) { BK_HIP(d->key0.alloc(slots)); BK_HIP(d->key1.alloc(slots)); return BK_OK; }
+    static void summary(Summary& s, const unsigned long long* t) {
+        s.records = t[0]; s.anchored = t[1]; s.ref_spanning = t[2]; s.supporting = t[3]; s.discordant = t[4];
+    }
+};
+struct JunctionPass : PassDefaults {
+    typedef Junctions State; typedef bk::JunctionArgs Args; typedef bk_junction_config Cfg; typedef bk_junction_params Params;
+    typedef bk_junction_summary Summary; typedef bk_junction_record Record;
+    static std::unique_ptr<State>& slot(bk_engine* e) { return e->junctions; }
+    static constexpr auto scan = bk::launch_junction_scan; static constexpr auto report = bk::launch_junction_report;
+    static constexpr PassText text = {
+        "bk_junctions_enable",
+        "bk_junctions_enable comes between samples",
+        "bk_junctions_enable: max_mismatches must be 0..8, got %u",
+        "bk_junctions_enable: table_log2 must be 10..24, got %u",
+        "bk_junctions_enable: the index has %d genome files; junctions are counted against an index of one genome file",
+        "bk_junctions_enable: a batch of 2^31 records or more",
+        "bk_sample_junctions: min_reads must be at least 1, got 0",
+        "bk_sample_junctions comes after bk_sample_finalize",
+        "bk_sample_junctions: junctions were not enabled for this sample (bk_junctions_enable before bk_sample_begin)",
+        "bk_sample_junctions: bk_sample_finalize has not run for this sample",
+        "bk_sample_download_junctions comes after this sample's bk_sample_junctions",
+        "bk_sample_download_junctions: more than 2^%u distinct candidate junctions: enable junctions with a larger table_log2",
+        "bk_sample_download_junction_span comes after this sample's bk_sample_junctions",
+        "bk_sample_download_junction_span: room for %llu cells, the index has %llu"};
+    static int check(const Cfg& c) {
+        if (c.min_len < 1 || c.min_len > BK_JUNCTION_MAX_LEN) return fail(BK_ERR_INVALID, "bk_junctions_enable: min_len must be 1..%u, got %u", BK_JUNCTION_MAX_LEN, c.min_len);
+        return BK_OK;
+    }
+    static void extras(Args& a, const State& d) { a.min_len = d.cfg.min_len; }
+    static void summary(Summary& s, const unsigned long long* t) {
+        s.records = t[0]; s.anchored = t[1]; s.ref_spanning = t[2]; s.supporting = t[3]; s.short_ = t[4]; s.backward = t[5]; s.discordant = t[6];
+    }
+};
+struct CopybackPass : PassDefaults {
+    typedef Copybacks State; typedef bk::CopybackArgs Args; typedef bk_copyback_config Cfg; typedef bk_copyback_params Params;
+    typedef bk_copyback_summary Summary; typedef bk_copyback_record Record;
+    static std::unique_ptr<State>& slot(bk_engine* e) { return e->copybacks; }
+    static constexpr auto scan = bk::launch_copyback_scan; static constexpr auto report = bk::launch_copyback_report;
+    static constexpr PassText text = {
+        "bk_copybacks_enable",
+        "bk_copybacks_enable comes between samples",
+        "bk_copybacks_enable: max_mismatches must be 0..8, got %u",
+        "bk_copybacks_enable: table_log2 must be 10..24, got %u",
+        "bk_copybacks_enable: the index has %d genome files; copy-backs are counted against an index of one genome file",
+        "bk_copybacks_enable: a batch of 2^31 records or more",
+        "bk_sample_copybacks: min_reads must be at least 1, got 0",
+        "bk_sample_copybacks comes after bk_sample_finalize",
+        "bk_sample_copybacks: copy-backs were not enabled for this sample (bk_copybacks_enable before bk_sample_begin)",
+        "bk_sample_copybacks: bk_sample_finalize has not run for this sample",
+        "bk_sample_download_copybacks comes after this sample's bk_sample_copybacks",
+        "bk_sample_download_copybacks: more than 2^%u distinct candidate copy-backs: enable copy-backs with a larger table_log2",
+        "bk_sample_download_copyback_span comes after this sample's bk_sample_copybacks",
+        "bk_sample_download_copyback_span: room for %llu cells, the index has %llu"};
+    static void params(Args& a, const Params& p) { a.min_dist = p.min_dist; }
+    static void summary(Summary& s, const unsigned long long* t) {
+        s.records = t[0]; s.same_strand = t[1]; s.ref_spanning = t[2]; s.switched = t[3]; s.supporting = t[4]; s.discordant = t[5];
+    }
+};
+struct ChimeraPass : PassDefaults {
+    typedef Chimeras State; typedef bk::ChimeraArgs Args; typedef bk_chimera_config Cfg; typedef bk_chimera_params Params;
+    typedef bk_chimera_summary Summary; typedef bk_chimera_record Record;
+    static std::unique_ptr<State>& slot(bk_engine* e) { return e->chimeras; }
+    static constexpr auto scan = bk::launch_chimera_scan; static constexpr auto report = bk::launch_chimera_report;
+    static constexpr PassText text = {
+        "bk_chimeras_enable",
+        "bk_chimeras_enable comes between samples",
+        "bk_chimeras_enable: max_mismatches must be 0..8, got %u",
+        "bk_chimeras_enable: table_log2 must be 10..24, got %u",
+        "bk_chimeras_enable: the index has %d genome files; chimeras are counted between the sequences of an index of one genome file",
+        "bk_chimeras_enable: a batch of 2^31 records or more",
+        "bk_sample_chimeras: min_reads must be at least 1, got 0",
+        "bk_sample_chimeras comes after bk_sample_finalize",
+        "bk_sample_chimeras: chimeras were not enabled for this sample (bk_chimeras_enable before bk_sample_begin)",
+        "bk_sample_chimeras: bk_sample_finalize has not run for this sample",
+        "bk_sample_download_chimeras comes after this sample's bk_sample_chimeras",
+        "bk_sample_download_chimeras: more than 2^%u distinct candidate chimeras: enable chimeras with a larger table_log2",
+        "bk_sample_download_chimera_span comes after this sample's bk_sample_chimeras",
+        "bk_sample_download_chimera_span: room for %llu cells, the index has %llu"};
+    static void summary(Summary& s, const unsigned long long* t) {
+        s.records = t[0]; s.same_strand = t[1]; s.ref_spanning = t[2]; s.crossed = t[3]; s.supporting = t[4]; s.discordant = t[5];
+    }
+};
+struct BreakendPass : PassDefaults {
+    typedef Breakends State; typedef bk::BreakendArgs Args; typedef bk_breakend_config Cfg; typedef bk_breakend_params Params;
+    typedef bk_breakend_summary Summary; typedef bk_breakend_record Record;
+    static std::unique_ptr<State>& slot(bk_engine* e) { return e->breakends; }
+    static constexpr auto scan = bk::launch_breakend_scan; static constexpr auto report = bk::launch_breakend_report;
+    static constexpr PassText text = {
+        "bk_breakends_enable",
+        "bk_breakends_enable comes between samples",
+        "bk_breakends_enable: max_mismatches must be 0..8, got %u",
+        "bk_breakends_enable: table_log2 must be 10..24, got %u",
+        "bk_breakends_enable: the index has %d genome files; breakends are counted against an index of one genome file",
+        "bk_breakends_enable: a batch of 2^31 records or more",
+        "bk_sample_breakends: min_reads must be at least 1, got 0",
+        "bk_sample_breakends comes after bk_sample_finalize",
+        "bk_sample_breakends: breakends were not enabled for this sample (bk_breakends_enable before bk_sample_begin)",
+        "bk_sample_breakends: bk_sample_finalize has not run for this sample",
+        "bk_sample_download_breakends comes after this sample's bk_sample_breakends",
+        "bk_sample_download_breakends: more than 2^%u distinct candidate breakends: enable breakends with a larger table_log2",
+        "bk_sample_download_breakend_span comes after this sample's bk_sample_breakends",
+        "bk_sample_download_breakend_span: room for %llu cells, the index has %llu"};
+    static int check(const Cfg& c) {
+        if (c.min_clip < 16 || c.min_clip > 65519) return fail(BK_ERR_INVALID, "bk_breakends_enable: min_clip must be 16..65519, got %u", c.min_clip);
+        return BK_OK;
+    }
+    static void extras(Args& a, const State& d) { a.min_clip = d.cfg.min_clip; a.more.site = d.site.p; }
+    static int alloc_extras(State* d, const IndexTables& ix) { BK_HIP(d->site.alloc(2 * (size_t)ix.total_cells)); return BK_OK; }
+    static void summary(Summary& s, const unsigned long long* t) {
+        s.records = t[0]; s.one_anchor = t[1]; s.ref_spanning = t[2]; s.supporting = t[3]; s.short_ = t[4]; s.through = t[5]; s.discordant = t[6];
+        s.unplaced = t[7];
+    }
+};
+struct DuplicationPass : PassDefaults {
+    typedef Duplications State; typedef bk::DuplicationArgs Args; typedef bk_duplication_config Cfg; typedef bk_duplication_params Params;
+    typedef bk_duplication_summary Summary; typedef bk_duplication_record Record;
+    static std::unique_ptr<State>& slot(bk_engine* e) { return e->duplications; }
+    static constexpr auto scan = bk::launch_duplication_scan; static constexpr auto report = bk::launch_duplication_report;
+    static constexpr PassText text = {
+        "bk_duplications_enable",
+        "bk_duplications_enable comes between samples",
+        "bk_duplications_enable: max_mismatches must be 0..8, got %u",
+        "bk_duplications_enable: table_log2 must be 10..24, got %u",
+        "bk_duplications_enable: the index has %d genome files; duplications are counted against an index of one genome file",
+        "bk_duplications_enable: a batch of 2^31 records or more",
+        "bk_sample_duplications: min_reads must be at least 1, got 0",
+        "bk_sample_duplications comes after bk_sample_finalize",
+        "bk_sample_duplications: duplications were not enabled for this sample (bk_duplications_enable before bk_sample_begin)",
+        "bk_sample_duplications: bk_sample_finalize has not run for this sample",
+        "bk_sample_download_duplications comes after this sample's bk_sample_duplications",
+        "bk_sample_download_duplications: more than 2^%u distinct candidate duplications: enable duplications with a larger table_log2",
+        "bk_sample_download_duplication_span comes after this sample's bk_sample_duplications",
+        "bk_sample_download_duplication_span: room for %llu cells, the index has %llu"};
+    static int check(const Cfg& c) {
+        if (c.min_len < 1 || c.min_len > BK_DUPLICATION_MAX_LEN) return fail(BK_ERR_INVALID, "bk_duplications_enable: min_len must be 1..%u, got %u", BK_DUPLICATION_MAX_LEN, c.min_len);
+        return BK_OK;
+    }
+    static void extras(Args& a, const State& d) { a.min_len = d.cfg.min_len; }
+    static void summary(Summary& s, const unsigned long long* t) {
+        s.records = t[0]; s.anchored = t[1]; s.ref_spanning = t[2]; s.supporting = t[3]; s.short_ = t[4]; s.forward = t[5]; s.discordant = t[6];
+    }
+};
 
-int bk_sample_breakends(bk_engine* e, const bk_breakend_params* p) {
-    if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_breakends: min_reads must be at least 1, got 0");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_breakends comes after bk_sample_finalize");
-    if (!e->breakends || !e->breakends->in_sample)
-        return fail(BK_ERR_STATE, "bk_sample_breakends: breakends were not enabled for this sample (bk_breakends_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_breakends: bk_sample_finalize has not run for this sample");
-    Breakends& d = *e->breakends;
-    BK_HIP(hipSetDevice(e->device));
-    bk::BreakendArgs a = breakend_args(e);
-    a.min_reads = p->min_reads;
-    bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_breakend_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 8, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_breakend_report(a, e->stream);
-    BK_HIP(hipGetLastError());
-    d.made = true;
-    return BK_OK;
-}
-
-int bk_sample_download_breakends(bk_engine* e, bk_breakend_summary* summary, bk_breakend_record* records, uint64_t cap) {
-    if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->breakends || !e->breakends->made) return fail(BK_ERR_STATE, "bk_sample_download_breakends comes after this sample's bk_sample_breakends");
-    Breakends& d = *e->breakends;
-    BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[11];
-    if (int rc = download(e, t, d.tallies.p, 11)) return rc;
-    summary->records = t[0]; summary->one_anchor = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->short_ = t[4];
-    summary->through = t[5]; summary->discordant = t[6]; summary->unplaced = t[7]; summary->candidates = t[8]; summary->reported = t[9];
-    summary->overflow = t[10] ? 1 : 0;
-    if (t[10]) return fail(BK_ERR_INVALID, "bk_sample_download_breakends: more than 2^%u distinct candidate breakends: enable breakends with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[9], cap), d.rows.n);
-    if (n && records) return download(e, records, d.rows.p, (size_t)n);
-    return BK_OK;
-}
-
-int bk_sample_download_breakend_span(bk_engine* e, uint32_t* span, uint64_t cap) {
-    if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->breakends || !e->breakends->made) return fail(BK_ERR_STATE, "bk_sample_download_breakend_span comes after this sample's bk_sample_breakends");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_breakend_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
-    BK_HIP(hipSetDevice(e->device));
-    return download(e, span, e->breakends->span.p, (size_t)e->ix->total_cells);
-}
-
-// ---- tandem duplications and circular-origin reads (bk_duplications.hip) ---------------------------------------------
-// the sample starts from an empty table, a zero span array, zero tallies (an abandoned sample leaves nothing behind)
-int Duplications::begin_sample(bk_engine* e) {
-    BK_HIP(hipMemsetAsync(keys.p, 0xff, keys.n * sizeof(unsigned long long), e->stream));
-    BK_HIP(hipMemsetAsync(counts.p, 0, counts.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(span.p, 0, span.n * sizeof(unsigned int), e->stream));
-    BK_HIP(hipMemsetAsync(tallies.p, 0, tallies.n * sizeof(unsigned long long), e->stream));
-    in_sample = true; summed = false; made = false;
-    return BK_OK;
-}
-// what every duplication kernel is given (a.rec: the scan's batch)
-static bk::DuplicationArgs duplication_args(const bk_engine* e) {
-    const Duplications& d = *e->duplications;
-    bk::DuplicationArgs a{};
+// what every kernel of the pass is given (a.rec: the scan's batch)
+template <class P> static typename P::Args pass_args(bk_engine* e) {
+    const typename P::State& d = *P::slot(e);
+    typename P::Args a{};
     a.ix = anchor_index(*e->ix, *d.anchors);
-    a.min_len = d.cfg.min_len; a.max_mismatches = d.cfg.max_mismatches;
-    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.cfg.table_log2;
+    a.max_mismatches = d.cfg.max_mismatches;
+    a.keys = d.keys.p; a.counts = d.counts.p; a.log2n = d.table_log2;
     a.span = d.span.p; a.tallies = d.tallies.p;
     a.rows = d.rows.p; a.row_cap = d.rows.n;
+    P::extras(a, d);
     return a;
 }
-// the records' anchors, spans and events (duplication_scan_kernel), on the engine stream behind the scan of the same records
-int Duplications::push(bk_engine* e, const Records& r) {
-    if (!in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
-    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, "bk_duplications_enable: a batch of 2^31 records or more");
-    bk::DuplicationArgs a = duplication_args(e); a.rec = records_view(r);
-    bk::launch_duplication_scan(a, e->ix->n_cus, e->stream);
+// the records' anchors, spans and events (x_scan_kernel), on the engine stream behind the scan of the same records
+template <class P> static int pass_push(bk_engine* e, const Records& r) {
+    if (!P::slot(e)->in_sample || r.n == 0) return BK_OK;   // (enabled after this sample began: it has no events)
+    if (r.n >= (1ull << 31)) return fail(BK_ERR_UNSUPPORTED, P::text.batch);
+    typename P::Args a = pass_args<P>(e); a.rec = records_view(r);
+    P::scan(a, e->ix->n_cus, e->stream);
     return BK_OK;
 }
+int Indels::push(bk_engine* e, const Records& r) { return pass_push<IndelPass>(e, r); }
+int Junctions::push(bk_engine* e, const Records& r) { return pass_push<JunctionPass>(e, r); }
+int Copybacks::push(bk_engine* e, const Records& r) { return pass_push<CopybackPass>(e, r); }
+int Chimeras::push(bk_engine* e, const Records& r) { return pass_push<ChimeraPass>(e, r); }
+int Breakends::push(bk_engine* e, const Records& r) { return pass_push<BreakendPass>(e, r); }
+int Duplications::push(bk_engine* e, const Records& r) { return pass_push<DuplicationPass>(e, r); }
 
-int bk_duplications_enable(bk_engine* e, const bk_duplication_config* cfg) {
+template <class P> static int pass_enable(bk_engine* e, const typename P::Cfg* cfg) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_duplications_enable comes between samples");
+    if (e->in_sample) return fail(BK_ERR_STATE, P::text.between);
     const IndexTables& ix = *e->ix;
     if (cfg) {
-        if (cfg->min_len < 1 || cfg->min_len > BK_DUPLICATION_MAX_LEN) return fail(BK_ERR_INVALID, "bk_duplications_enable: min_len must be 1..%u, got %u", BK_DUPLICATION_MAX_LEN, cfg->min_len);
-        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, "bk_duplications_enable: max_mismatches must be 0..8, got %u", cfg->max_mismatches);
-        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, "bk_duplications_enable: table_log2 must be 10..24, got %u", cfg->table_log2);
-        if (ix.n_files != 1)
-            return fail(BK_ERR_INVALID, "bk_duplications_enable: the index has %d genome files; duplications are counted against an index of one genome file", ix.n_files);
-        if (int rc = anchor_index_check(ix, "bk_duplications_enable")) return rc;
+        if (int rc = P::check(*cfg)) return rc;
+        if (cfg->max_mismatches > 8) return fail(BK_ERR_INVALID, P::text.mismatches, (unsigned)cfg->max_mismatches);
+        if (cfg->table_log2 < 10 || cfg->table_log2 > 24) return fail(BK_ERR_INVALID, P::text.table, (unsigned)cfg->table_log2);
+        if (ix.n_files != 1) return fail(BK_ERR_INVALID, P::text.one_file, (int)ix.n_files);
+        if (int rc = anchor_index_check(ix, P::text.enable)) return rc;
     }
     BK_HIP(hipSetDevice(e->device));
     BK_HIP(hipStreamSynchronize(e->stream));   // (the last sample's kernels may still use the buffers being freed)
-    e->duplications.reset();
+    P::slot(e).reset();
     if (!cfg) return BK_OK;
-    std::unique_ptr<Duplications> d(new Duplications());
-    d->cfg = *cfg;
-    if (int rc = anchor_tables(e, "bk_duplications_enable", d->anchors)) return rc;
+    std::unique_ptr<typename P::State> d(new typename P::State());
+    d->cfg = *cfg; d->table_log2 = cfg->table_log2;
+    if (int rc = anchor_tables(e, P::text.enable, d->anchors)) return rc;
     const size_t slots = (size_t)1 << cfg->table_log2;
-    BK_HIP(d->keys.alloc(slots)); BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
+    if (int rc = P::alloc_table(d.get(), slots)) return rc;
+    BK_HIP(d->counts.alloc(2 * slots)); BK_HIP(d->rows.alloc(slots));
+    if (int rc = P::alloc_extras(d.get(), ix)) return rc;
     BK_HIP(d->span.alloc((size_t)ix.total_cells + 2));
-    BK_HIP(d->tallies.alloc(10));
-    e->duplications = std::move(d);
+    BK_HIP(d->tallies.alloc(P::Args::kTallies));
+    P::slot(e) = std::move(d);
     return BK_OK;
 }
 
-int bk_sample_duplications(bk_engine* e, const bk_duplication_params* p) {
+template <class P> static int pass_report(bk_engine* e, const typename P::Params* p) {
     if (!e || !p) return fail(BK_ERR_INVALID, "null argument");
-    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_duplications: min_reads must be at least 1, got 0");
-    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_duplications comes after bk_sample_finalize");
-    if (!e->duplications || !e->duplications->in_sample)
-        return fail(BK_ERR_STATE, "bk_sample_duplications: duplications were not enabled for this sample (bk_duplications_enable before bk_sample_begin)");
-    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, "bk_sample_duplications: bk_sample_finalize has not run for this sample");
-    Duplications& d = *e->duplications;
+    if (p->min_reads < 1) return fail(BK_ERR_INVALID, P::text.min_reads);
+    if (int rc = P::check_params(*p)) return rc;
+    if (e->in_sample) return fail(BK_ERR_STATE, P::text.in_sample);
+    if (!P::slot(e) || !P::slot(e)->in_sample) return fail(BK_ERR_STATE, P::text.not_enabled);
+    if (e->finalized_mates < 1) return fail(BK_ERR_STATE, P::text.not_finalized);
+    typename P::State& d = *P::slot(e);
     BK_HIP(hipSetDevice(e->device));
-    bk::DuplicationArgs a = duplication_args(e);
-    a.min_reads = p->min_reads;
+    typename P::Args a = pass_args<P>(e);
+    a.min_reads = p->min_reads; P::params(a, *p);
     bk_engine::Span sp(e, 1);
-    if (!d.summed) { bk::launch_duplication_span_prefix(a, e->stream); d.summed = true; }
-    BK_HIP(hipMemsetAsync(d.tallies.p + 7, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
-    bk::launch_duplication_report(a, e->stream);
+    if (!d.summed) { bk::launch_span_prefix(a.span, a.ix.total_cells + 2u, e->stream); d.summed = true; }
+    BK_HIP(hipMemsetAsync(d.tallies.p + P::Args::kCandidates, 0, 2 * sizeof(unsigned long long), e->stream));   // candidates, reported
+    P::report(a, e->stream);
     BK_HIP(hipGetLastError());
     d.made = true;
     return BK_OK;
 }
 
-int bk_sample_download_duplications(bk_engine* e, bk_duplication_summary* summary, bk_duplication_record* records, uint64_t cap) {
+template <class P> static int pass_download(bk_engine* e, typename P::Summary* summary, typename P::Record* records, uint64_t cap) {
+    typedef typename P::Args A;
     if (!e || !summary) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->duplications || !e->duplications->made) return fail(BK_ERR_STATE, "bk_sample_download_duplications comes after this sample's bk_sample_duplications");
-    Duplications& d = *e->duplications;
+    if (!P::slot(e) || !P::slot(e)->made) return fail(BK_ERR_STATE, P::text.download_early);
+    typename P::State& d = *P::slot(e);
     BK_HIP(hipSetDevice(e->device));
-    unsigned long long t[10];
-    if (int rc = download(e, t, d.tallies.p, 10)) return rc;
-    summary->records = t[0]; summary->anchored = t[1]; summary->ref_spanning = t[2]; summary->supporting = t[3]; summary->short_ = t[4];
-    summary->forward = t[5]; summary->discordant = t[6]; summary->candidates = t[7]; summary->reported = t[8]; summary->overflow = t[9] ? 1 : 0;
-    if (t[9]) return fail(BK_ERR_INVALID, "bk_sample_download_duplications: more than 2^%u distinct candidate duplications: enable duplications with a larger table_log2", d.cfg.table_log2);
-    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[8], cap), d.rows.n);
+    unsigned long long t[A::kTallies];
+    if (int rc = download(e, t, d.tallies.p, A::kTallies)) return rc;
+    P::summary(*summary, t);
+    summary->candidates = t[A::kCandidates]; summary->reported = t[A::kReported]; summary->overflow = t[A::kOverflow] ? 1 : 0;
+    if (t[A::kOverflow]) return fail(BK_ERR_INVALID, P::text.overflow, (unsigned)d.table_log2);
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(t[A::kReported], cap), d.rows.n);
     if (n && records) return download(e, records, d.rows.p, (size_t)n);
     return BK_OK;
 }
 
-int bk_sample_download_duplication_span(bk_engine* e, uint32_t* span, uint64_t cap) {
+template <class P> static int pass_download_span(bk_engine* e, uint32_t* span, uint64_t cap) {
     if (!e || !span) return fail(BK_ERR_INVALID, "null argument");
-    if (!e->duplications || !e->duplications->made) return fail(BK_ERR_STATE, "bk_sample_download_duplication_span comes after this sample's bk_sample_duplications");
-    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, "bk_sample_download_duplication_span: room for %llu cells, the index has %llu", (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
+    if (!P::slot(e) || !P::slot(e)->made) return fail(BK_ERR_STATE, P::text.span_early);
+    if (cap < e->ix->total_cells) return fail(BK_ERR_INVALID, P::text.span_room, (unsigned long long)cap, (unsigned long long)e->ix->total_cells);
     BK_HIP(hipSetDevice(e->device));
-    return download(e, span, e->duplications->span.p, (size_t)e->ix->total_cells);
+    return download(e, span, P::slot(e)->span.p, (size_t)e->ix->total_cells);
 }
+
+int bk_indels_enable(bk_engine* e, const bk_indel_config* cfg) { return pass_enable<IndelPass>(e, cfg); }
+int bk_sample_indels(bk_engine* e, const bk_indel_params* p) { return pass_report<IndelPass>(e, p); }
+int bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap) { return pass_download<IndelPass>(e, summary, records, cap); }
+int bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap) { return pass_download_span<IndelPass>(e, span, cap); }
+
+int bk_junctions_enable(bk_engine* e, const bk_junction_config* cfg) { return pass_enable<JunctionPass>(e, cfg); }
+int bk_sample_junctions(bk_engine* e, const bk_junction_params* p) { return pass_report<JunctionPass>(e, p); }
+int bk_sample_download_junctions(bk_engine* e, bk_junction_summary* summary, bk_junction_record* records, uint64_t cap) { return pass_download<JunctionPass>(e, summary, records, cap); }
+int bk_sample_download_junction_span(bk_engine* e, uint32_t* span, uint64_t cap) { return pass_download_span<JunctionPass>(e, span, cap); }
+
+int bk_copybacks_enable(bk_engine* e, const bk_copyback_config* cfg) { return pass_enable<CopybackPass>(e, cfg); }
+int bk_sample_copybacks(bk_engine* e, const bk_copyback_params* p) { return pass_report<CopybackPass>(e, p); }
+int bk_sample_download_copybacks(bk_engine* e, bk_copyback_summary* summary, bk_copyback_record* records, uint64_t cap) { return pass_download<CopybackPass>(e, summary, records, cap); }
+int bk_sample_download_copyback_span(bk_engine* e, uint32_t* span, uint64_t cap) { return pass_download_span<CopybackPass>(e, span, cap); }
+
+int bk_chimeras_enable(bk_engine* e, const bk_chimera_config* cfg) { return pass_enable<ChimeraPass>(e, cfg); }
+int bk_sample_chimeras(bk_engine* e, const bk_chimera_params* p) { return pass_report<ChimeraPass>(e, p); }
+int bk_sample_download_chimeras(bk_engine* e, bk_chimera_summary* summary, bk_chimera_record* records, uint64_t cap) { return pass_download<ChimeraPass>(e, summary, records, cap); }
+int bk_sample_download_chimera_span(bk_engine* e, uint32_t* span, uint64_t cap) { return pass_download_span<ChimeraPass>(e, span, cap); }
+
+int bk_breakends_enable(bk_engine* e, const bk_breakend_config* cfg) { return pass_enable<BreakendPass>(e, cfg); }
+int bk_sample_breakends(bk_engine* e, const bk_breakend_params* p) { return pass_report<BreakendPass>(e, p); }
+int bk_sample_download_breakends(bk_engine* e, bk_breakend_summary* summary, bk_breakend_record* records, uint64_t cap) { return pass_download<BreakendPass>(e, summary, records, cap); }
+int bk_sample_download_breakend_span(bk_engine* e, uint32_t* span, uint64_t cap) { return pass_download_span<BreakendPass>(e, span, cap); }
+
+int bk_duplications_enable(bk_engine* e, const bk_duplication_config* cfg) { return pass_enable<DuplicationPass>(e, cfg); }
+int bk_sample_duplications(bk_engine* e, const bk_duplication_params* p) { return pass_report<DuplicationPass>(e, p); }
+int bk_sample_download_duplications(bk_engine* e, bk_duplication_summary* summary, bk_duplication_record* records, uint64_t cap) { return pass_download<DuplicationPass>(e, summary, records, cap); }
+int bk_sample_download_duplication_span(bk_engine* e, uint32_t* span, uint64_t cap) { return pass_download_span<DuplicationPass>(e, span, cap); }
 
 // ---- which substitutions the same records carry (bk_linkage.hip) ----------------------------------------------------
 // the row stores that the sample outgrew: each is freed once the stream has passed the copy out of it (`wait`: now)

@@ -434,6 +434,22 @@ class Engine:
         _check(self._L.bk_sample_download_consensus(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, buf[:min(cap, int(summ.positions))].tobytes()
 
+    def _download_events(self, download, summ, cap, dtype, columns=None):
+        """What the six download_x of the event passes do alike: (summary, min(cap, summary.reported) rows of `dtype`, `columns` wide) --
+        all rows when cap is None, by asking for the summary first."""
+        if cap is None:
+            _check(download(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.reported)
+        buf = np.zeros(max(1, cap) if columns is None else (max(1, cap), columns), dtype)
+        _check(download(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, buf[:min(cap, int(summ.reported))]
+
+    def _download_event_span(self, download):
+        """... and the six download_x_span: the prefix-summed span array of all cells."""
+        span = np.zeros(max(1, self.total_cells), np.uint32)
+        _check(download(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
+        return span[:self.total_cells]
+
     def indels_enable(self, max_len=32, max_mismatches=2, table_log2=16):
         """bk_indels_enable: indel_scan_kernel runs behind every scan of the samples that begin from now on; max_len=None disables."""
         cfg = None if max_len is None else C.byref(_ffi.IndelConfig(int(max_len), int(max_mismatches), int(table_log2)))
@@ -446,23 +462,16 @@ class Engine:
     def download_indels(self, cap=None):
         """(summary, rows) of sample_indels: min(cap, summary.reported) rows (cell, len, fwd, rev, ref_span, seq) -- len > 0 a deletion,
         < 0 an insertion --, all by default, sorted by (cell, kind, length, seq)."""
-        summ = _ffi.IndelSummary()
-        if cap is None:
-            _check(self._L.bk_sample_download_indels(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
-            cap = int(summ.reported)
         dt = np.dtype([("cell", np.uint32), ("len", np.int32), ("fwd", np.uint32), ("rev", np.uint32), ("ref_span", np.uint32),
                        ("pad", np.uint32), ("seq", np.uint64)])
-        buf = np.zeros(max(1, cap), dt)
-        _check(self._L.bk_sample_download_indels(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        rows = [(int(r["cell"]), int(r["len"]), int(r["fwd"]), int(r["rev"]), int(r["ref_span"]), int(r["seq"])) for r in buf[:min(cap, int(summ.reported))]]
+        summ, buf = self._download_events(self._L.bk_sample_download_indels, _ffi.IndelSummary(), cap, dt)
+        rows = [(int(r["cell"]), int(r["len"]), int(r["fwd"]), int(r["rev"]), int(r["ref_span"]), int(r["seq"])) for r in buf]
         rows.sort(key=lambda r: (r[0], 1 if r[1] < 0 else 0, abs(r[1]), r[5]))
         return summ, rows
 
     def download_indel_span(self):
         """bk_sample_download_indel_span: the prefix-summed span array of all cells (after sample_indels)."""
-        span = np.zeros(max(1, self.total_cells), np.uint32)
-        _check(self._L.bk_sample_download_indel_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
-        return span[:self.total_cells]
+        return self._download_event_span(self._L.bk_sample_download_indel_span)
 
     def junctions_enable(self, min_len=33, max_mismatches=2, table_log2=16):
         """bk_junctions_enable: junction_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
@@ -476,19 +485,12 @@ class Engine:
     def download_junctions(self, cap=None):
         """(summary, rows) of sample_junctions: min(cap, summary.reported) rows (cell, len, fwd, rev, span_donor, span_acceptor), all by
         default, sorted by (cell, len)."""
-        summ = _ffi.JunctionSummary()
-        if cap is None:
-            _check(self._L.bk_sample_download_junctions(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
-            cap = int(summ.reported)
-        buf = np.zeros((max(1, cap), 6), np.uint32)
-        _check(self._L.bk_sample_download_junctions(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+        summ, buf = self._download_events(self._L.bk_sample_download_junctions, _ffi.JunctionSummary(), cap, np.uint32, 6)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf)
 
     def download_junction_span(self):
         """bk_sample_download_junction_span: the prefix-summed span array of all cells (after sample_junctions)."""
-        span = np.zeros(max(1, self.total_cells), np.uint32)
-        _check(self._L.bk_sample_download_junction_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
-        return span[:self.total_cells]
+        return self._download_event_span(self._L.bk_sample_download_junction_span)
 
     def copybacks_enable(self, max_mismatches=2, table_log2=16):
         """bk_copybacks_enable: copyback_scan_kernel runs behind every scan of the samples that begin from now on; max_mismatches=None
@@ -504,19 +506,12 @@ class Engine:
     def download_copybacks(self, cap=None):
         """(summary, rows) of sample_copybacks: min(cap, summary.reported) rows (lo, hi, kind, lo_first, hi_first, span_lo, span_hi, 0),
         all by default, sorted."""
-        summ = _ffi.CopybackSummary()
-        if cap is None:
-            _check(self._L.bk_sample_download_copybacks(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
-            cap = int(summ.reported)
-        buf = np.zeros((max(1, cap), 8), np.uint32)
-        _check(self._L.bk_sample_download_copybacks(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+        summ, buf = self._download_events(self._L.bk_sample_download_copybacks, _ffi.CopybackSummary(), cap, np.uint32, 8)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf)
 
     def download_copyback_span(self):
         """bk_sample_download_copyback_span: the prefix-summed span array of all cells (after sample_copybacks)."""
-        span = np.zeros(max(1, self.total_cells), np.uint32)
-        _check(self._L.bk_sample_download_copyback_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
-        return span[:self.total_cells]
+        return self._download_event_span(self._L.bk_sample_download_copyback_span)
 
     def chimeras_enable(self, max_mismatches=2, table_log2=16):
         """bk_chimeras_enable: chimera_scan_kernel runs behind every scan of the samples that begin from now on; max_mismatches=None
@@ -532,19 +527,12 @@ class Engine:
     def download_chimeras(self, cap=None):
         """(summary, rows) of sample_chimeras: min(cap, summary.reported) rows (lo, hi, sides, lo_first, hi_first, span_lo, span_hi, 0),
         all by default, sorted."""
-        summ = _ffi.ChimeraSummary()
-        if cap is None:
-            _check(self._L.bk_sample_download_chimeras(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
-            cap = int(summ.reported)
-        buf = np.zeros((max(1, cap), 8), np.uint32)
-        _check(self._L.bk_sample_download_chimeras(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+        summ, buf = self._download_events(self._L.bk_sample_download_chimeras, _ffi.ChimeraSummary(), cap, np.uint32, 8)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf)
 
     def download_chimera_span(self):
         """bk_sample_download_chimera_span: the prefix-summed span array of all cells (after sample_chimeras)."""
-        span = np.zeros(max(1, self.total_cells), np.uint32)
-        _check(self._L.bk_sample_download_chimera_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
-        return span[:self.total_cells]
+        return self._download_event_span(self._L.bk_sample_download_chimera_span)
 
     def breakends_enable(self, min_clip=20, max_mismatches=2, table_log2=16):
         """bk_breakends_enable: breakend_scan_kernel runs behind every scan of the samples that begin from now on; min_clip=None
@@ -559,19 +547,12 @@ class Engine:
     def download_breakends(self, cap=None):
         """(summary, rows) of sample_breakends: min(cap, summary.reported) rows (cell, tag, side, fwd, rev, site_reads, span, 0), all by
         default, sorted."""
-        summ = _ffi.BreakendSummary()
-        if cap is None:
-            _check(self._L.bk_sample_download_breakends(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
-            cap = int(summ.reported)
-        buf = np.zeros((max(1, cap), 8), np.uint32)
-        _check(self._L.bk_sample_download_breakends(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+        summ, buf = self._download_events(self._L.bk_sample_download_breakends, _ffi.BreakendSummary(), cap, np.uint32, 8)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf)
 
     def download_breakend_span(self):
         """bk_sample_download_breakend_span: the prefix-summed span array of all cells (after sample_breakends)."""
-        span = np.zeros(max(1, self.total_cells), np.uint32)
-        _check(self._L.bk_sample_download_breakend_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
-        return span[:self.total_cells]
+        return self._download_event_span(self._L.bk_sample_download_breakend_span)
 
     def duplications_enable(self, min_len=33, max_mismatches=2, table_log2=16):
         """bk_duplications_enable: duplication_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
@@ -585,19 +566,12 @@ class Engine:
     def download_duplications(self, cap=None):
         """(summary, rows) of sample_duplications: min(cap, summary.reported) rows (cell, len, fwd, rev, span_start, span_end), all by
         default, sorted by (cell, len)."""
-        summ = _ffi.DuplicationSummary()
-        if cap is None:
-            _check(self._L.bk_sample_download_duplications(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
-            cap = int(summ.reported)
-        buf = np.zeros((max(1, cap), 6), np.uint32)
-        _check(self._L.bk_sample_download_duplications(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
-        return summ, sorted(tuple(int(v) for v in r) for r in buf[:min(cap, int(summ.reported))])
+        summ, buf = self._download_events(self._L.bk_sample_download_duplications, _ffi.DuplicationSummary(), cap, np.uint32, 6)
+        return summ, sorted(tuple(int(v) for v in r) for r in buf)
 
     def download_duplication_span(self):
         """bk_sample_download_duplication_span: the prefix-summed span array of all cells (after sample_duplications)."""
-        span = np.zeros(max(1, self.total_cells), np.uint32)
-        _check(self._L.bk_sample_download_duplication_span(self.h, span.ctypes.data_as(C.c_void_p), self.total_cells), self._L)
-        return span[:self.total_cells]
+        return self._download_event_span(self._L.bk_sample_download_duplication_span)
 
     def linkage_enable(self, max_mismatches=8, initial_rows=1 << 16):
         """bk_link_enable: link_scan_kernel runs behind every scan of the samples that begin from now on and keeps a row per placed
