@@ -8,7 +8,7 @@
 #include <tuple>
 
 #include "../../include/bronko_hip.h"
-#include "anchor_genome.hpp"
+#include "event_twin.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -18,41 +18,12 @@ namespace {
 struct Tables {
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::pair<uint32_t, uint32_t>> events;   // (cell, side, tag) -> fwd, rev
     std::map<std::pair<uint32_t, uint32_t>, uint32_t> site;                                     // (cell, side) -> supporting records
-    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    SpanCount span;
     BreakendCounters n;
+    explicit Tables(const FileCells& g) : span(g) {}
 };
 
 int code_of(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3; }
-
-std::string along_reference(const std::string& rec, bool against) {
-    if (!against) return rec;
-    std::string r(rec.size(), 'A');
-    for (size_t j = 0; j < rec.size(); j++) r[j] = comp(rec[rec.size() - 1 - j]);
-    return r;
-}
-
-// both ends anchored: what the span needs, as junctions.cpp has it
-void two_anchors(const AnchorGenome& g, const std::string& rec, int f_off, uint32_t f_cell, bool f_ag, int b_off, uint32_t b_cell, bool b_ag, int M, Tables& t) {
-    const int k = g.k, n = (int)rec.size();
-    if (f_ag != b_ag) return;
-    const std::string r = along_reference(rec, f_ag);
-    int64_t a, b, ca, cb;
-    if (f_ag) { a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell; }
-    else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
-    if (a + k > b) return;
-    const size_t s = (size_t)g.seq_of(ca);
-    if ((size_t)g.seq_of(cb) != s) return;
-    const int64_t dL = ca - a, dR = cb - b;
-    const int64_t lo = std::min(dL, dR), hi = std::max(dL, dR) + n;
-    if (lo < g.first[s] || hi > g.first[s + 1]) return;
-    for (int64_t c = lo; c < hi; c++) if (!is_acgt(g.text[(size_t)c])) return;
-    if (dL != dR) return;
-    int m = 0;
-    for (int64_t j = 0; j < n; j++) m += r[(size_t)j] != g.text[(size_t)(dL + j)] ? 1 : 0;
-    if (m > M) return;
-    t.n.ref_spanning++;
-    t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
-}
 
 void one_anchor(const AnchorGenome& g, const std::string& rec, bool front, int off, uint32_t cell, bool against, int C, int M, Tables& t) {
     const int64_t k = g.k, n = (int64_t)rec.size();
@@ -97,15 +68,17 @@ void add_record(const AnchorGenome& g, const std::string& rec, int C, int M, Tab
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
-    int f = -1, b = -1;
-    uint32_t cf = 0, cb = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &cf, &f_ag)) { f = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &cb, &b_ag)) { b = o; break; }
+    const EndAnchors ends = end_anchors(g, rec);
+    const int f = ends.f_off, b = ends.b_off;
+    const uint32_t cf = ends.f_cell, cb = ends.b_cell;
+    const bool f_ag = ends.f_ag, b_ag = ends.b_ag;
     if (f < 0 && b < 0) return;
-    if (f >= 0 && b >= 0) { two_anchors(g, rec, f, cf, f_ag, b, cb, b_ag, M, t); return; }
+    if (ends.both()) {                               // both ends anchored: on one strand, what the span needs
+        if (f_ag != b_ag) return;
+        const Oriented o = orient(rec, k, ends);
+        if (o.a + k <= o.b && t.span.place(g, o, M) == Placed::spanning) t.n.ref_spanning++;
+        return;
+    }
     if (f >= 0) one_anchor(g, rec, true, f, cf, f_ag, C, M, t);
     else one_anchor(g, rec, false, b, cb, b_ag, C, M, t);
 }
@@ -122,27 +95,11 @@ BreakendResult breakend_events(const Index& ix, int file, const std::vector<std:
     if (max_mismatches < 0 || max_mismatches > kBreakendMaxMismatches) throw std::runtime_error("breakend_events: max_mismatches must be 0..8");
     if (min_clip < kBreakendMinClipLo || min_clip > kBreakendMinClipHi) throw std::runtime_error("breakend_events: min_clip must be 16..65519");
     const AnchorGenome g(ix, file);
-    Tables t;
-    t.span.assign(g.text.size() + 2, 0);
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) add_record(g, run, min_clip, max_mismatches, t);
-            run.clear();
-        }
-    }
+    Tables t(g);
+    for_each_record(reads, g.k, [&](const std::string& rec) { add_record(g, rec, min_clip, max_mismatches, t); });
     BreakendResult out;
     out.n = t.n;
-    out.span.assign((size_t)ix.total_cells(), 0u);
-    int64_t acc = 0;
-    std::vector<uint32_t> sums(g.text.size() + 1);
-    for (size_t c = 0; c <= g.text.size(); c++) {
-        acc += t.span[c]; sums[c] = (uint32_t)acc;
-        if (c < g.text.size()) out.span[(size_t)g.cell0 + c] = (uint32_t)acc;
-    }
+    const std::vector<uint32_t> sums = t.span.sums(ix, g, &out.span);
     for (const auto& kv : t.events) {               // (the map's order is (cell, side, tag))
         BreakendEvent e;
         std::tie(e.cell, e.side, e.tag) = kv.first;
@@ -157,9 +114,7 @@ BreakendResult breakend_events(const Index& ix, int file, const std::vector<std:
 void write_breakends_tsv(const std::string& out_path, const Index& ix, int file, std::vector<BreakendEvent> events, const BreakendParams& p,
                          const BreakendTallies& t) {
     const FileCells g(ix, file);
-    FILE* fp = fopen(out_path.c_str(), "w");
-    if (!fp) throw std::runtime_error("Failed to create breakends output file " + out_path);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const OutFile fp("breakends", out_path);
     fprintf(fp, "##breakend_min_clip=%u\n##breakend_max_mismatches=%u\n##breakend_min_reads=%llu\n", p.min_clip, p.max_mismatches, (unsigned long long)p.min_reads);
     fprintf(fp, "##breakend_tallies=records:%llu,one_anchor:%llu,ref_spanning:%llu,supporting:%llu,short:%llu,through:%llu,discordant:%llu,unplaced:%llu,candidates:%llu,reported:%llu\n",
             (unsigned long long)t.records, (unsigned long long)t.one_anchor, (unsigned long long)t.ref_spanning, (unsigned long long)t.supporting,
@@ -173,16 +128,13 @@ void write_breakends_tsv(const std::string& out_path, const Index& ix, int file,
     for (const BreakendEvent& e : events) {
         const int64_t c = (int64_t)e.cell - g.cell0;
         if (c < 0 || c >= (int64_t)g.text.size() || e.side > 1 || !is_acgt(g.text[(size_t)c])) throw std::runtime_error("write_breakends_tsv: an event outside the genome file's sequences");
-        size_t s = 0;
-        while (s + 2 < g.first.size() && g.first[s + 1] <= c) s++;
+        const size_t s = (size_t)g.seq_of(c);
         const bool terminus = e.side ? c == g.first[s] : c == g.first[s + 1] - 1;
         const uint64_t reads = (uint64_t)e.fwd + e.rev;
-        const uint64_t f = 10000ull * reads / std::max<uint64_t>(1, reads + e.span);
-        fprintf(fp, "%s\t%lld\t%c\t%u\t%u\t%llu\t%u\t%u\t%llu.%04llu\t%d\t%s\n", chrom_of(fm.sequences[s].name).c_str(), (long long)(c - g.first[s] + 1), e.side ? 'R' : 'L',
-                e.fwd, e.rev, (unsigned long long)reads, e.site_reads, e.span, (unsigned long long)(f / 10000), (unsigned long long)(f % 10000), terminus ? 1 : 0,
-                tag_letters(e.tag).c_str());
+        fprintf(fp, "%s\t%lld\t%c\t%u\t%u\t%llu\t%u\t%u\t%s\t%d\t%s\n", chrom_of(fm.sequences[s].name).c_str(), (long long)(c - g.first[s] + 1), e.side ? 'R' : 'L',
+                e.fwd, e.rev, (unsigned long long)reads, e.site_reads, e.span, freq_text(reads, e.span).c_str(), terminus ? 1 : 0, tag_letters(e.tag).c_str());
     }
-    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write breakends file " + out_path);
+    fp.finish();
 }
 
 }  // namespace bronko

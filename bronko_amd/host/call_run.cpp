@@ -297,6 +297,16 @@ constexpr uint32_t kBreakendTableLog2 = 18;   // --breakends: likewise
 constexpr uint32_t kDuplicationTableLog2 = 18;   // --duplications: likewise
 constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
 
+// One table of a sample's rows: a first download for the summary, of which `count` is the rows' number, then that many rows.  Row is
+// the host's struct for the engine's record Rec
+template <class Summ, class Rec, class Row>
+void download_rows(bk_engine* e, int (*download)(bk_engine*, Summ*, Rec*, uint64_t), const char* name, Summ& summ, const uint64_t& count, std::vector<Row>& rows) {
+    static_assert(sizeof(Row) == sizeof(Rec), "the host's struct is the engine's record");
+    hip_check(download(e, &summ, nullptr, 0), name);
+    rows.resize((size_t)count);
+    hip_check(download(e, &summ, reinterpret_cast<Rec*>(rows.data()), rows.size()), name);
+}
+
 struct CallRun {
     const Args& a;
     const CallConfig& cfg;
@@ -343,22 +353,13 @@ struct CallRun {
         // the readers stay few until the engines stand -- bk_engine_create runs on all cores for seconds)
         if (ahead && ix.files.size() <= 8) ahead->set_concurrency((unsigned)std::max<long>(2, a.threads / 2));
         if (cfg.region_report()) resolve_regions();
-        if (cfg.indels && ix.files.size() != 1)   // (a k-mer's cell in the engine's table is its first among all files, not the selected genome's)
-            die(T, "--indels needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.junctions && ix.files.size() != 1)
-            die(T, "--junctions needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.copybacks && ix.files.size() != 1)
-            die(T, "--copybacks needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.chimeras && ix.files.size() != 1)
-            die(T, "--chimeras needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.breakends && ix.files.size() != 1)
-            die(T, "--breakends needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.duplications && ix.files.size() != 1)
-            die(T, "--duplications needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.linkage && ix.files.size() != 1)
-            die(T, "--linkage needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.codons() && ix.files.size() != 1)
-            die(T, "--codons needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        // (a k-mer's cell in the engine's table is its first among all files, not the selected genome's)
+        const std::pair<bool, const char*> one_file[] = {{cfg.indels, "--indels"}, {cfg.junctions, "--junctions"}, {cfg.copybacks, "--copybacks"},
+                                                         {cfg.chimeras, "--chimeras"}, {cfg.breakends, "--breakends"}, {cfg.duplications, "--duplications"},
+                                                         {cfg.linkage, "--linkage"}, {cfg.codons(), "--codons"}};
+        for (const auto& flag : one_file)
+            if (flag.first && ix.files.size() != 1)
+                die(T, std::string(flag.second) + " needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
         if (cfg.codons()) {   // the BED lines against the CHROM tokens of the index.  Before any device is touched.
             try { genes = resolve_codon_bed(ix, 0, cfg.codon_bed, cfg.codons_path); }
             catch (const std::exception& e) { die(T, e.what()); }
@@ -644,44 +645,13 @@ struct CallRun {
             hip_check(bk_sample_download_region_depths(e, &d.rsumm, d.rrows.data(), d.rrows.size()), "bk_sample_download_region_depths");
             d.rrows.resize(std::min<size_t>(d.rrows.size(), d.rsumm.n_regions));
         }
-        if (cfg.indels) {
-            static_assert(sizeof(IndelEvent) == sizeof(bk_indel_record), "IndelEvent is bk_indel_record");
-            hip_check(bk_sample_download_indels(e, &d.isumm, nullptr, 0), "bk_sample_download_indels");
-            d.indels.resize((size_t)d.isumm.reported);
-            hip_check(bk_sample_download_indels(e, &d.isumm, reinterpret_cast<bk_indel_record*>(d.indels.data()), d.indels.size()), "bk_sample_download_indels");
-        }
-        if (cfg.junctions) {
-            static_assert(sizeof(JunctionEvent) == sizeof(bk_junction_record), "JunctionEvent is bk_junction_record");
-            hip_check(bk_sample_download_junctions(e, &d.jsumm, nullptr, 0), "bk_sample_download_junctions");
-            d.junctions.resize((size_t)d.jsumm.reported);
-            hip_check(bk_sample_download_junctions(e, &d.jsumm, reinterpret_cast<bk_junction_record*>(d.junctions.data()), d.junctions.size()), "bk_sample_download_junctions");
-        }
-        if (cfg.copybacks) {
-            static_assert(sizeof(CopybackEvent) == sizeof(bk_copyback_record), "CopybackEvent is bk_copyback_record");
-            hip_check(bk_sample_download_copybacks(e, &d.cbsumm, nullptr, 0), "bk_sample_download_copybacks");
-            d.copybacks.resize((size_t)d.cbsumm.reported);
-            hip_check(bk_sample_download_copybacks(e, &d.cbsumm, reinterpret_cast<bk_copyback_record*>(d.copybacks.data()), d.copybacks.size()), "bk_sample_download_copybacks");
-        }
-        if (cfg.chimeras) {
-            static_assert(sizeof(ChimeraEvent) == sizeof(bk_chimera_record), "ChimeraEvent is bk_chimera_record");
-            hip_check(bk_sample_download_chimeras(e, &d.chsumm, nullptr, 0), "bk_sample_download_chimeras");
-            d.chimeras.resize((size_t)d.chsumm.reported);
-            hip_check(bk_sample_download_chimeras(e, &d.chsumm, reinterpret_cast<bk_chimera_record*>(d.chimeras.data()), d.chimeras.size()), "bk_sample_download_chimeras");
-        }
-        if (cfg.breakends) {
-            static_assert(sizeof(BreakendEvent) == sizeof(bk_breakend_record), "BreakendEvent is bk_breakend_record");
-            hip_check(bk_sample_download_breakends(e, &d.besumm, nullptr, 0), "bk_sample_download_breakends");
-            d.breakends.resize((size_t)d.besumm.reported);
-            hip_check(bk_sample_download_breakends(e, &d.besumm, reinterpret_cast<bk_breakend_record*>(d.breakends.data()), d.breakends.size()), "bk_sample_download_breakends");
-        }
-        if (cfg.duplications) {
-            static_assert(sizeof(DuplicationEvent) == sizeof(bk_duplication_record), "DuplicationEvent is bk_duplication_record");
-            hip_check(bk_sample_download_duplications(e, &d.dpsumm, nullptr, 0), "bk_sample_download_duplications");
-            d.duplications.resize((size_t)d.dpsumm.reported);
-            hip_check(bk_sample_download_duplications(e, &d.dpsumm, reinterpret_cast<bk_duplication_record*>(d.duplications.data()), d.duplications.size()), "bk_sample_download_duplications");
-        }
+        if (cfg.indels) download_rows(e, bk_sample_download_indels, "bk_sample_download_indels", d.isumm, d.isumm.reported, d.indels);
+        if (cfg.junctions) download_rows(e, bk_sample_download_junctions, "bk_sample_download_junctions", d.jsumm, d.jsumm.reported, d.junctions);
+        if (cfg.copybacks) download_rows(e, bk_sample_download_copybacks, "bk_sample_download_copybacks", d.cbsumm, d.cbsumm.reported, d.copybacks);
+        if (cfg.chimeras) download_rows(e, bk_sample_download_chimeras, "bk_sample_download_chimeras", d.chsumm, d.chsumm.reported, d.chimeras);
+        if (cfg.breakends) download_rows(e, bk_sample_download_breakends, "bk_sample_download_breakends", d.besumm, d.besumm.reported, d.breakends);
+        if (cfg.duplications) download_rows(e, bk_sample_download_duplications, "bk_sample_download_duplications", d.dpsumm, d.dpsumm.reported, d.duplications);
         if (cfg.linkage) {   // the sites are the sample's own VCF records: counted behind the calls, a few rows travel
-            static_assert(sizeof(LinkPair) == sizeof(bk_link_pair), "LinkPair is bk_link_pair");
             const FileMeta& fm = ix.files[0];     // (one genome file: checked as the index was opened)
             std::vector<uint64_t> seq_cell(fm.sequences.size(), 0);
             for (size_t q = 1; q < fm.sequences.size(); q++) seq_cell[q] = seq_cell[q - 1] + fm.sequences[q - 1].len;
@@ -693,9 +663,7 @@ struct CallRun {
             }
             const std::vector<uint32_t> sites = link_sites(d.link_recs);
             hip_check(bk_sample_linkage(e, sites.data(), (uint32_t)sites.size(), cfg.link.max_dist), "bk_sample_linkage");
-            hip_check(bk_sample_download_linkage(e, &d.lsumm, nullptr, 0), "bk_sample_download_linkage");
-            d.link_pairs.resize((size_t)d.lsumm.n_pairs);
-            hip_check(bk_sample_download_linkage(e, &d.lsumm, reinterpret_cast<bk_link_pair*>(d.link_pairs.data()), d.link_pairs.size()), "bk_sample_download_linkage");
+            download_rows(e, bk_sample_download_linkage, "bk_sample_download_linkage", d.lsumm, d.lsumm.n_pairs, d.link_pairs);
         }
         if (cfg.codons()) {   // counted from the same rows, behind the calls: 256 bytes a codon travel
             hip_check(bk_sample_codons(e, gene_table.data(), (uint32_t)gene_table.size()), "bk_sample_codons");

@@ -7,7 +7,7 @@
 #include <stdexcept>
 #include <tuple>
 
-#include "anchor_genome.hpp"
+#include "event_twin.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -16,8 +16,9 @@ namespace {
 
 struct Tables {
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::pair<uint32_t, uint32_t>> events;   // (lo, hi, sides) -> lo_first, hi_first
-    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    SpanCount span;
     ChimeraCounters n;
+    explicit Tables(const FileCells& g) : span(g) {}
 };
 
 // One arm: the cell of offset j is c0 + d * j, in sequence s; along the reference (d = +1) the read shows the cell's letter, against
@@ -43,44 +44,22 @@ void slide_run(const Arm& a, const Arm& b, int64_t x, int64_t y, int64_t* t0, in
     while (a.holds(x + a.d * (*t0 - 1)) && b.holds(y + b.d * (*t0 - 1)) && up(*t0 - 1)) --*t0;
 }
 
-// both anchors in one sequence and on one strand: what the span needs, as copybacks.cpp has it
-void one_sequence(const AnchorGenome& g, size_t s, const std::string& rec, int f_off, uint32_t f_cell, int b_off, uint32_t b_cell, bool against, int M, Tables& t) {
-    const int k = g.k, n = (int)rec.size();
-    std::string r = rec;                             // r': the record along the reference
-    int64_t a, b, ca, cb;
-    if (against) {
-        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
-        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
-    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
-    if (a + k > b) return;
-    t.n.same_strand++;
-    const int64_t dL = ca - a, dR = cb - b;
-    const int64_t lo = std::min(dL, dR), hi = std::max(dL, dR) + n;
-    if (lo < g.first[s] || hi > g.first[s + 1]) return;
-    for (int64_t c = lo; c < hi; c++) if (!is_acgt(g.text[(size_t)c])) return;
-    if (dL != dR) return;
-    int m = 0;
-    for (int64_t j = 0; j < n; j++) m += r[(size_t)j] != g.text[(size_t)(dL + j)] ? 1 : 0;
-    if (m > M) return;
-    t.n.ref_spanning++;
-    t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
-}
-
 void add_record(const AnchorGenome& g, const std::string& rec, int M, Tables& t) {
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
-    int f = -1, b = -1;
-    uint32_t cf = 0, cg = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &cf, &f_ag)) { f = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &cg, &b_ag)) { b = o; break; }
+    const EndAnchors ends = end_anchors(g, rec);
+    const int f = ends.f_off, b = ends.b_off;
+    const uint32_t cf = ends.f_cell, cg = ends.b_cell;
+    const bool f_ag = ends.f_ag, b_ag = ends.b_ag;
     if (f < 0 || b < 0) return;
     const size_t sx = (size_t)g.seq_of(cf), sy = (size_t)g.seq_of(cg);
-    if (sx == sy) {
-        if (f_ag == b_ag) one_sequence(g, sx, rec, f, cf, b, cg, f_ag, M, t);
+    if (sx == sy) {                                  // both anchors in one sequence: on one strand, what the span needs
+        if (f_ag != b_ag) return;
+        const Oriented o = orient(rec, k, ends);
+        if (o.a + k > o.b) return;
+        t.n.same_strand++;
+        if (t.span.place(g, o, M) == Placed::spanning) t.n.ref_spanning++;
         return;
     }
     if (f + k > b) return;
@@ -125,27 +104,11 @@ void add_record(const AnchorGenome& g, const std::string& rec, int M, Tables& t)
 ChimeraResult chimera_events(const Index& ix, int file, const std::vector<std::string>& reads, int max_mismatches) {
     if (max_mismatches < 0 || max_mismatches > kChimeraMaxMismatches) throw std::runtime_error("chimera_events: max_mismatches must be 0..8");
     const AnchorGenome g(ix, file);
-    Tables t;
-    t.span.assign(g.text.size() + 2, 0);
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) add_record(g, run, max_mismatches, t);
-            run.clear();
-        }
-    }
+    Tables t(g);
+    for_each_record(reads, g.k, [&](const std::string& rec) { add_record(g, rec, max_mismatches, t); });
     ChimeraResult out;
     out.n = t.n;
-    out.span.assign((size_t)ix.total_cells(), 0u);
-    int64_t acc = 0;
-    std::vector<uint32_t> sums(g.text.size() + 1);
-    for (size_t c = 0; c <= g.text.size(); c++) {
-        acc += t.span[c]; sums[c] = (uint32_t)acc;
-        if (c < g.text.size()) out.span[(size_t)g.cell0 + c] = (uint32_t)acc;
-    }
+    const std::vector<uint32_t> sums = t.span.sums(ix, g, &out.span);
     for (const auto& kv : t.events) {               // (the map's order is (lo, hi, sides))
         ChimeraEvent e;
         std::tie(e.lo, e.hi, e.sides) = kv.first;
@@ -159,21 +122,18 @@ ChimeraResult chimera_events(const Index& ix, int file, const std::vector<std::s
 void write_chimeras_tsv(const std::string& out_path, const Index& ix, int file, std::vector<ChimeraEvent> events, const ChimeraParams& p,
                         uint64_t supporting, uint64_t ref_spanning) {
     const FileCells g(ix, file);
-    FILE* fp = fopen(out_path.c_str(), "w");
-    if (!fp) throw std::runtime_error("Failed to create chimeras output file " + out_path);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const OutFile fp("chimeras", out_path);
     fprintf(fp, "##chimera_max_mismatches=%u\n##chimera_min_reads=%llu\n##chimera_supporting=%llu\n##chimera_ref_spanning=%llu\n", p.max_mismatches,
             (unsigned long long)p.min_reads, (unsigned long long)supporting, (unsigned long long)ref_spanning);
     fputs("chrom_lo\tpos_lo\tside_lo\tchrom_hi\tpos_hi\tside_hi\tlo_first\thi_first\treads\tspan_lo\tspan_hi\tfreq\thomology\n", fp);
     std::sort(events.begin(), events.end(), [](const ChimeraEvent& x, const ChimeraEvent& y) {
         return std::make_tuple(x.lo, x.sides & 1u, x.hi, x.sides >> 1) < std::make_tuple(y.lo, y.sides & 1u, y.hi, y.sides >> 1);
     });
-    auto seq_of = [&](int64_t c) { size_t s = 0; while (s + 2 < g.first.size() && g.first[s + 1] <= c) s++; return s; };
     const FileMeta& fm = ix.files[(size_t)file];
     for (const ChimeraEvent& e : events) {
         const int64_t lo = (int64_t)e.lo - g.cell0, hi = (int64_t)e.hi - g.cell0;
         if (lo < 0 || hi <= lo || hi >= (int64_t)g.text.size() || e.sides > 3) throw std::runtime_error("write_chimeras_tsv: an event outside the genome file's sequences");
-        const size_t sx = seq_of(lo), sy = seq_of(hi);
+        const size_t sx = (size_t)g.seq_of(lo), sy = (size_t)g.seq_of(hi);
         if (sx == sy || !is_acgt(g.text[(size_t)lo]) || !is_acgt(g.text[(size_t)hi]))
             throw std::runtime_error("write_chimeras_tsv: an event that does not join two sequences of the genome file");
         // the arm at lo taken as arm A: side L runs up to its cell, side R down to it; the arm at hi as arm B: side R goes on upward
@@ -181,12 +141,11 @@ void write_chimeras_tsv(const std::string& out_path, const Index& ix, int file, 
         int64_t t0, t1;
         slide_run(A, B, lo, hi, &t0, &t1);
         const uint64_t reads = (uint64_t)e.lo_first + e.hi_first;
-        const uint64_t t = 10000ull * reads / std::max<uint64_t>(1, reads + std::max(e.span_lo, e.span_hi));
-        fprintf(fp, "%s\t%lld\t%c\t%s\t%lld\t%c\t%u\t%u\t%llu\t%u\t%u\t%llu.%04llu\t%lld\n", chrom_of(fm.sequences[sx].name).c_str(), (long long)(lo - g.first[sx] + 1),
+        fprintf(fp, "%s\t%lld\t%c\t%s\t%lld\t%c\t%u\t%u\t%llu\t%u\t%u\t%s\t%lld\n", chrom_of(fm.sequences[sx].name).c_str(), (long long)(lo - g.first[sx] + 1),
                 (e.sides & 1u) ? 'R' : 'L', chrom_of(fm.sequences[sy].name).c_str(), (long long)(hi - g.first[sy] + 1), (e.sides & 2u) ? 'R' : 'L', e.lo_first,
-                e.hi_first, (unsigned long long)reads, e.span_lo, e.span_hi, (unsigned long long)(t / 10000), (unsigned long long)(t % 10000), (long long)(t1 - t0));
+                e.hi_first, (unsigned long long)reads, e.span_lo, e.span_hi, freq_text(reads, std::max(e.span_lo, e.span_hi)).c_str(), (long long)(t1 - t0));
     }
-    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write chimeras file " + out_path);
+    fp.finish();
 }
 
 }  // namespace bronko

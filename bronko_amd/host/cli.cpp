@@ -187,6 +187,14 @@ long to_long(const std::string& opt, const std::string& v) {
     if (v.empty() || *end || x < 0) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
     return x;
 }
+// any integer that fits a long: what is out of an option's range is refused by check_call_args
+long any_long(const std::string& opt, const std::string& v) {
+    char* end = nullptr;
+    errno = 0;
+    const long x = strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+    return x;
+}
 double to_double(const std::string& opt, const std::string& v) {
     char* end = nullptr;
     const double x = strtod(v.c_str(), &end);
@@ -284,118 +292,71 @@ Args parse_args(int argc, char** argv) {
             if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
         }
         else if (opt == "--consensus") a.consensus = true;
-        else if (opt == "--consensus-min-depth") {   // (any integer, any number here: what is out of range is refused by check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            a.consensus_min_depth = strtol(v.c_str(), &end, 10);
-            a.has_consensus_min_depth = true;
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
-        }
+        else if (opt == "--consensus-min-depth") { a.consensus_min_depth = any_long(opt, one()); a.has_consensus_min_depth = true; }   // (check_call_args)
         else if (opt == "--consensus-min-freq") { a.consensus_min_freq = to_double(opt, one()); a.has_consensus_min_freq = true; }
         else if (opt == "--regions") { a.regions = one(); a.has_regions = true; }
         else if (opt == "--region-window" || opt == "--region-min-depth") {   // (any integer here: what is out of range is refused by check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--region-window") { a.region_window = x; a.has_region_window = true; }
             else { a.region_min_depth = x; a.has_region_min_depth = true; }
         }
         else if (opt == "--indels") a.indels = true;
         else if (opt == "--indel-max-len" || opt == "--indel-max-mismatches" || opt == "--indel-min-reads") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--indel-max-len") { a.indel_max_len = x; a.has_indel_max_len = true; }
             else if (opt == "--indel-max-mismatches") { a.indel_max_mismatches = x; a.has_indel_max_mismatches = true; }
             else { a.indel_min_reads = x; a.has_indel_min_reads = true; }
         }
         else if (opt == "--junctions") a.junctions = true;
         else if (opt == "--junction-min-len" || opt == "--junction-max-mismatches" || opt == "--junction-min-reads") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--junction-min-len") { a.junction_min_len = x; a.has_junction_min_len = true; }
             else if (opt == "--junction-max-mismatches") { a.junction_max_mismatches = x; a.has_junction_max_mismatches = true; }
             else { a.junction_min_reads = x; a.has_junction_min_reads = true; }
         }
         else if (opt == "--copybacks") a.copybacks = true;
         else if (opt == "--copyback-max-mismatches" || opt == "--copyback-min-reads" || opt == "--copyback-min-dist") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--copyback-max-mismatches") { a.copyback_max_mismatches = x; a.has_copyback_max_mismatches = true; }
             else if (opt == "--copyback-min-reads") { a.copyback_min_reads = x; a.has_copyback_min_reads = true; }
             else { a.copyback_min_dist = x; a.has_copyback_min_dist = true; }
         }
         else if (opt == "--chimeras") a.chimeras = true;
         else if (opt == "--chimera-max-mismatches" || opt == "--chimera-min-reads") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--chimera-max-mismatches") { a.chimera_max_mismatches = x; a.has_chimera_max_mismatches = true; }
             else { a.chimera_min_reads = x; a.has_chimera_min_reads = true; }
         }
         else if (opt == "--breakends") a.breakends = true;
         else if (opt == "--breakend-min-clip" || opt == "--breakend-max-mismatches" || opt == "--breakend-min-reads") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--breakend-min-clip") { a.breakend_min_clip = x; a.has_breakend_min_clip = true; }
             else if (opt == "--breakend-max-mismatches") { a.breakend_max_mismatches = x; a.has_breakend_max_mismatches = true; }
             else { a.breakend_min_reads = x; a.has_breakend_min_reads = true; }
         }
         else if (opt == "--duplications") a.duplications = true;
         else if (opt == "--duplication-min-len" || opt == "--duplication-max-mismatches" || opt == "--duplication-min-reads") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--duplication-min-len") { a.duplication_min_len = x; a.has_duplication_min_len = true; }
             else if (opt == "--duplication-max-mismatches") { a.duplication_max_mismatches = x; a.has_duplication_max_mismatches = true; }
             else { a.duplication_min_reads = x; a.has_duplication_min_reads = true; }
         }
         else if (opt == "--linkage") a.linkage = true;
         else if (opt == "--link-max-mismatches" || opt == "--link-max-dist" || opt == "--link-min-reads") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--link-max-mismatches") { a.link_max_mismatches = x; a.has_link_max_mismatches = true; }
             else if (opt == "--link-max-dist") { a.link_max_dist = x; a.has_link_max_dist = true; }
             else { a.link_min_reads = x; a.has_link_min_reads = true; }
         }
         else if (opt == "--codons") { a.codons = one(); a.has_codons = true; }
         else if (opt == "--codon-min-reads" || opt == "--codon-max-mismatches") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--codon-min-reads") { a.codon_min_reads = x; a.has_codon_min_reads = true; }
             else { a.codon_max_mismatches = x; a.has_codon_max_mismatches = true; }
         }
         else if (opt == "--haplotypes") { a.haplotypes = one(); a.has_haplotypes = true; }
         else if (opt == "--hap-window" || opt == "--hap-step" || opt == "--hap-min-reads" || opt == "--hap-max-mismatches") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--hap-window") { a.hap_window = x; a.has_hap_window = true; }
             else if (opt == "--hap-step") { a.hap_step = x; a.has_hap_step = true; }
             else if (opt == "--hap-min-reads") { a.hap_min_reads = x; a.has_hap_min_reads = true; }
@@ -403,11 +364,7 @@ Args parse_args(int argc, char** argv) {
         }
         else if (opt == "--read-pileup") a.read_pileup = true;
         else if (opt == "--read-pileup-end" || opt == "--read-pileup-max-mismatches") {   // (any integer here: check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            errno = 0;
-            const long x = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+            const long x = any_long(opt, one());
             if (opt == "--read-pileup-end") { a.read_pileup_end = x; a.has_read_pileup_end = true; }
             else { a.read_pileup_max_mismatches = x; a.has_read_pileup_max_mismatches = true; }
         }

@@ -7,7 +7,7 @@
 #include <stdexcept>
 #include <tuple>
 
-#include "anchor_genome.hpp"
+#include "event_twin.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -16,8 +16,9 @@ namespace {
 
 struct Tables {
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::pair<uint32_t, uint32_t>> events;   // (lo, hi, kind) -> lo_first, hi_first
-    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    SpanCount span;
     CopybackCounters n;
+    explicit Tables(const FileCells& g) : span(g) {}
 };
 
 // the pairs (x + t, y - t), t0 <= t <= t1, that the reference cannot tell from (x, y): both cells of each inside sequence s and ACGT
@@ -34,44 +35,22 @@ void slide_run(const FileCells& g, size_t s, int kind, int64_t x, int64_t y, int
     while (ok(x + *t0 - 1) && ok(y - *t0 + 1) && up(x + *t0 - 1, y - *t0 + 1)) --*t0;
 }
 
-// both anchors on one strand: what the span needs, as junctions.cpp has it
-void same_strand(const AnchorGenome& g, const std::string& rec, int f_off, uint32_t f_cell, int b_off, uint32_t b_cell, bool against, int M, Tables& t) {
-    const int k = g.k, n = (int)rec.size();
-    std::string r = rec;                             // r': the record along the reference
-    int64_t a, b, ca, cb;
-    if (against) {
-        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
-        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
-    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
-    if (a + k > b) return;
-    t.n.same_strand++;
-    const int64_t dL = ca - a, dR = cb - b;
-    const int s = g.seq_of(ca);
-    if (g.seq_of(cb) != s) return;
-    const int64_t lo = std::min(dL, dR), hi = std::max(dL, dR) + n;
-    if (lo < g.first[(size_t)s] || hi > g.first[(size_t)s + 1]) return;
-    for (int64_t c = lo; c < hi; c++) if (!is_acgt(g.text[(size_t)c])) return;
-    if (dL != dR) return;
-    int m = 0;
-    for (int64_t j = 0; j < n; j++) m += r[(size_t)j] != g.text[(size_t)(dL + j)] ? 1 : 0;
-    if (m > M) return;
-    t.n.ref_spanning++;
-    t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
-}
-
 void add_record(const AnchorGenome& g, const std::string& rec, int M, Tables& t) {
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
-    int f = -1, b = -1;
-    uint32_t cf = 0, cg = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &cf, &f_ag)) { f = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &cg, &b_ag)) { b = o; break; }
+    const EndAnchors ends = end_anchors(g, rec);
+    const int f = ends.f_off, b = ends.b_off;
+    const uint32_t cf = ends.f_cell, cg = ends.b_cell;
+    const bool f_ag = ends.f_ag, b_ag = ends.b_ag;
     if (f < 0 || b < 0) return;
-    if (f_ag == b_ag) { same_strand(g, rec, f, cf, b, cg, f_ag, M, t); return; }
+    if (f_ag == b_ag) {                              // both anchors on one strand: what the span needs
+        const Oriented o = orient(rec, k, ends);
+        if (o.a + k > o.b) return;
+        t.n.same_strand++;
+        if (t.span.place(g, o, M) == Placed::spanning) t.n.ref_spanning++;
+        return;
+    }
     if (f + k > b) return;
     t.n.switched++;
     const int kind = f_ag ? 1 : 0;                   // H: front along, back against; T: front against, back along
@@ -115,27 +94,11 @@ void add_record(const AnchorGenome& g, const std::string& rec, int M, Tables& t)
 CopybackResult copyback_events(const Index& ix, int file, const std::vector<std::string>& reads, int max_mismatches) {
     if (max_mismatches < 0 || max_mismatches > kCopybackMaxMismatches) throw std::runtime_error("copyback_events: max_mismatches must be 0..8");
     const AnchorGenome g(ix, file);
-    Tables t;
-    t.span.assign(g.text.size() + 2, 0);
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) add_record(g, run, max_mismatches, t);
-            run.clear();
-        }
-    }
+    Tables t(g);
+    for_each_record(reads, g.k, [&](const std::string& rec) { add_record(g, rec, max_mismatches, t); });
     CopybackResult out;
     out.n = t.n;
-    out.span.assign((size_t)ix.total_cells(), 0u);
-    int64_t acc = 0;
-    std::vector<uint32_t> sums(g.text.size() + 1);
-    for (size_t c = 0; c <= g.text.size(); c++) {
-        acc += t.span[c]; sums[c] = (uint32_t)acc;
-        if (c < g.text.size()) out.span[(size_t)g.cell0 + c] = (uint32_t)acc;
-    }
+    const std::vector<uint32_t> sums = t.span.sums(ix, g, &out.span);
     for (const auto& kv : t.events) {               // (the map's order is (lo, hi, kind))
         CopybackEvent e;
         std::tie(e.lo, e.hi, e.kind) = kv.first;
@@ -149,32 +112,28 @@ CopybackResult copyback_events(const Index& ix, int file, const std::vector<std:
 
 void write_copybacks_tsv(const std::string& out_path, const Index& ix, int file, std::vector<CopybackEvent> events, const CopybackParams& p) {
     const FileCells g(ix, file);
-    FILE* fp = fopen(out_path.c_str(), "w");
-    if (!fp) throw std::runtime_error("Failed to create copybacks output file " + out_path);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const OutFile fp("copybacks", out_path);
     fprintf(fp, "##copyback_max_mismatches=%u\n##copyback_min_reads=%llu\n##copyback_min_dist=%u\n", p.max_mismatches, (unsigned long long)p.min_reads, p.min_dist);
     fputs("chrom\tkind\tlo\thi\tdistance\tlo_first\thi_first\treads\tspan_lo\tspan_hi\tfreq\thomology\n", fp);
     // (one sequence holds both cells, and the sequences' cells ascend: ordered by sequence, kind, lo, hi)
-    auto seq_of = [&](int64_t c) { size_t s = 0; while (s + 2 < g.first.size() && g.first[s + 1] <= c) s++; return s; };
     std::sort(events.begin(), events.end(), [&](const CopybackEvent& x, const CopybackEvent& y) {
-        return std::make_tuple(seq_of((int64_t)x.lo - g.cell0), x.kind, x.lo, x.hi) < std::make_tuple(seq_of((int64_t)y.lo - g.cell0), y.kind, y.lo, y.hi);
+        return std::make_tuple(g.seq_of((int64_t)x.lo - g.cell0), x.kind, x.lo, x.hi) < std::make_tuple(g.seq_of((int64_t)y.lo - g.cell0), y.kind, y.lo, y.hi);
     });
     const FileMeta& fm = ix.files[(size_t)file];
     for (const CopybackEvent& e : events) {
         const int64_t lo = (int64_t)e.lo - g.cell0, hi = (int64_t)e.hi - g.cell0;
         if (lo < 0 || hi < lo || hi >= (int64_t)g.text.size() || e.kind > 1) throw std::runtime_error("write_copybacks_tsv: an event outside the genome file's sequences");
-        const size_t s = seq_of(lo);
+        const size_t s = (size_t)g.seq_of(lo);
         if (hi >= g.first[s + 1] || !is_acgt(g.text[(size_t)lo]) || !is_acgt(g.text[(size_t)hi]))
             throw std::runtime_error("write_copybacks_tsv: an event outside the genome file's sequences");
         int64_t t0, t1;
         slide_run(g, s, (int)e.kind, lo, hi, &t0, &t1);
         const uint64_t reads = (uint64_t)e.lo_first + e.hi_first;
-        const uint64_t t = 10000ull * reads / std::max<uint64_t>(1, reads + std::max(e.span_lo, e.span_hi));
-        fprintf(fp, "%s\t%c\t%lld\t%lld\t%lld\t%u\t%u\t%llu\t%u\t%u\t%llu.%04llu\t%lld\n", chrom_of(fm.sequences[s].name).c_str(), e.kind == 0 ? 'H' : 'T',
+        fprintf(fp, "%s\t%c\t%lld\t%lld\t%lld\t%u\t%u\t%llu\t%u\t%u\t%s\t%lld\n", chrom_of(fm.sequences[s].name).c_str(), e.kind == 0 ? 'H' : 'T',
                 (long long)(lo - g.first[s] + 1), (long long)(hi - g.first[s] + 1), (long long)(hi - lo), e.lo_first, e.hi_first, (unsigned long long)reads,
-                e.span_lo, e.span_hi, (unsigned long long)(t / 10000), (unsigned long long)(t % 10000), (long long)(t1 - t0));
+                e.span_lo, e.span_hi, freq_text(reads, std::max(e.span_lo, e.span_hi)).c_str(), (long long)(t1 - t0));
     }
-    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write copybacks file " + out_path);
+    fp.finish();
 }
 
 }  // namespace bronko

@@ -7,7 +7,7 @@
 #include <stdexcept>
 #include <tuple>
 
-#include "anchor_genome.hpp"
+#include "event_twin.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -16,47 +16,34 @@ namespace {
 
 struct Tables {
     std::map<std::pair<uint32_t, uint32_t>, std::pair<uint32_t, uint32_t>> events;   // (cell, E) -> fwd, rev
-    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    SpanCount span;
     DuplicationCounters n;
+    explicit Tables(const FileCells& g) : span(g) {}
 };
 
 void add_record(const AnchorGenome& g, const std::string& rec, int64_t L, int M, Tables& t) {
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
-    int f_off = -1, b_off = -1;
-    uint32_t f_cell = 0, b_cell = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &f_cell, &f_ag)) { f_off = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &b_cell, &b_ag)) { b_off = o; break; }
-    if (f_off < 0 || b_off < 0 || f_ag != b_ag) return;
-    const bool against = f_ag;
-    std::string r = rec;                             // r': the record along the reference
-    int64_t a, b, ca, cb;
-    if (against) {
-        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
-        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
-    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
+    const EndAnchors ends = end_anchors(g, rec);
+    if (!ends.both() || ends.f_ag != ends.b_ag) return;
+    const Oriented o = orient(rec, k, ends);
+    const std::string& r = o.r;
+    const int64_t a = o.a, b = o.b;
     if (a + k > b) return;
     t.n.anchored++;
-    const int64_t dL = ca - a, dR = cb - b, delta = dR - dL;
-    const int s = g.seq_of(ca);
-    if (g.seq_of(cb) != s) return;
+    switch (t.span.place(g, o, M)) {
+        case Placed::outside: return;
+        case Placed::discordant: t.n.discordant++; return;
+        case Placed::spanning: t.n.ref_spanning++; return;
+        case Placed::shifted: break;
+    }
+    const int64_t dL = o.ca - a, dR = o.cb - b, delta = dR - dL;
+    const int s = g.seq_of(o.ca);
     const int64_t lo = g.first[(size_t)s], hi = g.first[(size_t)s + 1];
     const std::string& ref = g.text;
     auto acgt = [&](int64_t c0, int64_t c1) { for (int64_t c = c0; c < c1; c++) if (!is_acgt(ref[(size_t)c])) return false; return true; };
     auto mm = [&](int64_t j, int64_t d) { return r[(size_t)j] != ref[(size_t)(d + j)] ? 1 : 0; };
-    if (delta == 0) {
-        if (dL < lo || dL + n > hi || !acgt(dL, dL + n)) return;
-        int m = 0;
-        for (int64_t j = 0; j < n; j++) m += mm(j, dL);
-        if (m > M) { t.n.discordant++; return; }
-        t.n.ref_spanning++;
-        t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
-        return;
-    }
     if (delta > 0) { t.n.forward++; return; }
     if (-delta < L) { t.n.short_++; return; }
     const int64_t E = -delta;
@@ -81,7 +68,7 @@ void add_record(const AnchorGenome& g, const std::string& rec, int64_t L, int M,
     while (pos - 1 > FL && pos - E - 1 >= FR && ref[(size_t)(pos - 1)] == ref[(size_t)(pos - E - 1)]) pos--;
     t.n.supporting++;
     auto& e = t.events[std::make_pair((uint32_t)(g.cell0 + pos), (uint32_t)E)];
-    (against ? e.second : e.first)++;
+    (o.against ? e.second : e.first)++;
 }
 
 }  // namespace
@@ -90,27 +77,11 @@ DuplicationResult duplication_events(const Index& ix, int file, const std::vecto
     if (min_len < 1 || min_len > kDuplicationMaxLen) throw std::runtime_error("duplication_events: min_len must be 1..2^27 - 1");
     if (max_mismatches < 0 || max_mismatches > kDuplicationMaxMismatches) throw std::runtime_error("duplication_events: max_mismatches must be 0..8");
     const AnchorGenome g(ix, file);
-    Tables t;
-    t.span.assign(g.text.size() + 2, 0);
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) add_record(g, run, (int64_t)min_len, max_mismatches, t);
-            run.clear();
-        }
-    }
+    Tables t(g);
+    for_each_record(reads, g.k, [&](const std::string& rec) { add_record(g, rec, (int64_t)min_len, max_mismatches, t); });
     DuplicationResult out;
     out.n = t.n;
-    out.span.assign((size_t)ix.total_cells(), 0u);
-    int64_t acc = 0;
-    std::vector<uint32_t> sums(g.text.size() + 1);   // (an event's cell may be the end of the file's last sequence)
-    for (size_t c = 0; c <= g.text.size(); c++) {
-        acc += t.span[c]; sums[c] = (uint32_t)acc;
-        if (c < g.text.size()) out.span[(size_t)g.cell0 + c] = (uint32_t)acc;
-    }
+    const std::vector<uint32_t> sums = t.span.sums(ix, g, &out.span);
     for (const auto& kv : t.events) {               // (the map's order is (cell, len))
         DuplicationEvent e;
         e.cell = kv.first.first; e.len = kv.first.second;
@@ -123,9 +94,7 @@ DuplicationResult duplication_events(const Index& ix, int file, const std::vecto
 
 void write_duplications_tsv(const std::string& out_path, const Index& ix, int file, std::vector<DuplicationEvent> events, const DuplicationParams& p) {
     const FileCells g(ix, file);
-    FILE* fp = fopen(out_path.c_str(), "w");
-    if (!fp) throw std::runtime_error("Failed to create duplications output file " + out_path);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const OutFile fp("duplications", out_path);
     fprintf(fp, "##duplication_min_len=%u\n##duplication_max_mismatches=%u\n##duplication_min_reads=%llu\n", p.min_len, p.max_mismatches, (unsigned long long)p.min_reads);
     fputs("chrom\tstart\tend\tlength\tfwd\trev\treads\tspan_start\tspan_end\tfreq\thomology\twhole\n", fp);
     // by sequence, start, end: start = cell - len ascends with the sequence, end with the cell
@@ -135,20 +104,18 @@ void write_duplications_tsv(const std::string& out_path, const Index& ix, int fi
     const FileMeta& fm = ix.files[(size_t)file];
     for (const DuplicationEvent& e : events) {
         const int64_t pos = (int64_t)e.cell - g.cell0, E = e.len;
-        size_t s = 0;                                // the sequence of the first duplicated cell (pos itself may be the next one's first)
-        while (s + 2 < g.first.size() && g.first[s + 1] <= pos - E) s++;
+        const size_t s = (size_t)g.seq_of(pos - E);  // the sequence of the first duplicated cell (pos itself may be the next one's first)
         const int64_t lo = g.first[s], hi = g.first[s + 1];
         if (E < 1 || pos - E < lo || pos > hi) throw std::runtime_error("write_duplications_tsv: an event outside the genome file's sequences");
         int64_t h = 0;                               // how far the event could slide to the right
         while (h < E && pos + h < hi && is_acgt(g.text[(size_t)(pos + h)]) && is_acgt(g.text[(size_t)(pos - E + h)]) &&
                g.text[(size_t)(pos + h)] == g.text[(size_t)(pos - E + h)]) h++;
         const uint64_t reads = (uint64_t)e.fwd + e.rev;
-        const uint64_t t = 10000ull * reads / std::max<uint64_t>(1, reads + std::max(e.span_start, e.span_end));
-        fprintf(fp, "%s\t%lld\t%lld\t%u\t%u\t%u\t%llu\t%u\t%u\t%llu.%04llu\t%lld\t%d\n", chrom_of(fm.sequences[s].name).c_str(), (long long)(pos - E - lo + 1),
-                (long long)(pos - lo), e.len, e.fwd, e.rev, (unsigned long long)reads, e.span_start, e.span_end, (unsigned long long)(t / 10000),
-                (unsigned long long)(t % 10000), (long long)h, E == hi - lo ? 1 : 0);
+        fprintf(fp, "%s\t%lld\t%lld\t%u\t%u\t%u\t%llu\t%u\t%u\t%s\t%lld\t%d\n", chrom_of(fm.sequences[s].name).c_str(), (long long)(pos - E - lo + 1),
+                (long long)(pos - lo), e.len, e.fwd, e.rev, (unsigned long long)reads, e.span_start, e.span_end,
+                freq_text(reads, std::max(e.span_start, e.span_end)).c_str(), (long long)h, E == hi - lo ? 1 : 0);
     }
-    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write duplications file " + out_path);
+    fp.finish();
 }
 
 }  // namespace bronko

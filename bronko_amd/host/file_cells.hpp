@@ -1,6 +1,7 @@
-// file_cells.hpp -- one genome file of the index as the host twins of the engine's row-store passes see it (linkage.cpp, codons.cpp,
-// haplotypes.cpp, and through AnchorGenome indels.cpp): its cells, where its sequences start, the CHROM token of a sequence name, and
-// whether a region of cells lies in the file and inside one sequence.
+// file_cells.hpp -- one genome file of the index as the host twins and the report writers see it: its cells, where its sequences start
+// and which of them holds a cell, the CHROM token of a sequence name, and whether a region of cells lies in the file and inside one
+// sequence.  Used by the row-store passes (linkage.cpp, codons.cpp, haplotypes.cpp, read_pileup.cpp), by the writers of the six event
+// passes, and through AnchorGenome (anchor_genome.hpp) by every twin that places records.
 #pragma once
 #include <cctype>
 #include <cstdint>
@@ -25,6 +26,12 @@ struct FileCells {
             for (uint8_t c : s.seq) text.push_back((char)(c >= 'a' && c <= 'z' ? c - 32 : c));
         }
         first.push_back((int64_t)text.size());
+    }
+    // the sequence that holds a cell (relative to cell0); the last one for every cell behind it
+    int seq_of(int64_t cell) const {
+        int s = 0;
+        while (s + 2 < (int)first.size() && first[(size_t)s + 1] <= cell) s++;
+        return s;
     }
     // the cells [lo, hi) of the index (lo < hi) lie in the file and in one sequence; `who` begins the message
     void check_region(const std::string& who, uint64_t lo, uint64_t hi) const {

@@ -63,6 +63,15 @@ int named_rows_out(const std::vector<T>& r, F put, uint64_t cap, uint32_t* rows,
     if (names && joined.size() + 1 <= names_cap) std::memcpy(names, joined.c_str(), joined.size() + 1);
     return 0;
 }
+// what every bh_*_events hands back: *n rows of which at most cap are written, the span of all cells, the counters in the order given
+template <class Result, size_t N>
+int events_out(const Result& r, const uint64_t (&c)[N], uint64_t cap, void* rows, uint64_t* n, uint32_t* span, uint64_t* counters) {
+    *n = r.events.size();
+    if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof r.events[0]);
+    if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
+    if (counters) std::memcpy(counters, c, sizeof c);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -275,13 +284,9 @@ int bh_indel_events(const void* h, int file_id, const char* reads, int max_len, 
                     uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::IndelEvent) == 32, "IndelEvent is bk_indel_record");
-        const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::IndelResult r = bronko::indel_events(*ix, file_id, split_lines(reads), max_len, max_mismatches);
-        *n = r.events.size();
-        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::IndelEvent));
-        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
-        if (counters) { counters[0] = r.n.records; counters[1] = r.n.anchored; counters[2] = r.n.ref_spanning; counters[3] = r.n.supporting; counters[4] = r.n.discordant; }
-        return 0;
+        const bronko::IndelResult r = bronko::indel_events(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), max_len, max_mismatches);
+        const uint64_t c[5] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.discordant};
+        return events_out(r, c, cap, rows, n, span, counters);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
@@ -304,16 +309,9 @@ int bh_junction_events(const void* h, int file_id, const char* reads, uint32_t m
                        uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::JunctionEvent) == 24, "JunctionEvent is bk_junction_record");
-        const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::JunctionResult r = bronko::junction_events(*ix, file_id, split_lines(reads), min_len, max_mismatches);
-        *n = r.events.size();
-        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::JunctionEvent));
-        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
-        if (counters) {
-            const uint64_t c[7] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.backward, r.n.discordant};
-            std::memcpy(counters, c, sizeof c);
-        }
-        return 0;
+        const bronko::JunctionResult r = bronko::junction_events(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), min_len, max_mismatches);
+        const uint64_t c[7] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.backward, r.n.discordant};
+        return events_out(r, c, cap, rows, n, span, counters);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
@@ -333,16 +331,9 @@ int bh_write_junctions_tsv(const void* h, int file_id, const char* path, const v
 int bh_copyback_events(const void* h, int file_id, const char* reads, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span, uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::CopybackEvent) == 32, "CopybackEvent is bk_copyback_record");
-        const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::CopybackResult r = bronko::copyback_events(*ix, file_id, split_lines(reads), max_mismatches);
-        *n = r.events.size();
-        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::CopybackEvent));
-        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
-        if (counters) {
-            const uint64_t c[6] = {r.n.records, r.n.same_strand, r.n.ref_spanning, r.n.switched, r.n.supporting, r.n.discordant};
-            std::memcpy(counters, c, sizeof c);
-        }
-        return 0;
+        const bronko::CopybackResult r = bronko::copyback_events(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), max_mismatches);
+        const uint64_t c[6] = {r.n.records, r.n.same_strand, r.n.ref_spanning, r.n.switched, r.n.supporting, r.n.discordant};
+        return events_out(r, c, cap, rows, n, span, counters);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
@@ -362,16 +353,9 @@ int bh_write_copybacks_tsv(const void* h, int file_id, const char* path, const v
 int bh_chimera_events(const void* h, int file_id, const char* reads, int max_mismatches, uint64_t cap, void* rows, uint64_t* n, uint32_t* span, uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::ChimeraEvent) == 32, "ChimeraEvent is bk_chimera_record");
-        const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::ChimeraResult r = bronko::chimera_events(*ix, file_id, split_lines(reads), max_mismatches);
-        *n = r.events.size();
-        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::ChimeraEvent));
-        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
-        if (counters) {
-            const uint64_t c[6] = {r.n.records, r.n.same_strand, r.n.ref_spanning, r.n.crossed, r.n.supporting, r.n.discordant};
-            std::memcpy(counters, c, sizeof c);
-        }
-        return 0;
+        const bronko::ChimeraResult r = bronko::chimera_events(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), max_mismatches);
+        const uint64_t c[6] = {r.n.records, r.n.same_strand, r.n.ref_spanning, r.n.crossed, r.n.supporting, r.n.discordant};
+        return events_out(r, c, cap, rows, n, span, counters);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
@@ -393,16 +377,9 @@ int bh_breakend_events(const void* h, int file_id, const char* reads, int min_cl
                        uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::BreakendEvent) == 32, "BreakendEvent is bk_breakend_record");
-        const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::BreakendResult r = bronko::breakend_events(*ix, file_id, split_lines(reads), min_clip, max_mismatches);
-        *n = r.events.size();
-        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::BreakendEvent));
-        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
-        if (counters) {
-            const uint64_t c[8] = {r.n.records, r.n.one_anchor, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.through, r.n.discordant, r.n.unplaced};
-            std::memcpy(counters, c, sizeof c);
-        }
-        return 0;
+        const bronko::BreakendResult r = bronko::breakend_events(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), min_clip, max_mismatches);
+        const uint64_t c[8] = {r.n.records, r.n.one_anchor, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.through, r.n.discordant, r.n.unplaced};
+        return events_out(r, c, cap, rows, n, span, counters);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
@@ -428,16 +405,9 @@ int bh_duplication_events(const void* h, int file_id, const char* reads, uint32_
                        uint64_t* counters) {
     try {
         static_assert(sizeof(bronko::DuplicationEvent) == 24, "DuplicationEvent is bk_duplication_record");
-        const auto* ix = static_cast<const bronko::Index*>(h);
-        const bronko::DuplicationResult r = bronko::duplication_events(*ix, file_id, split_lines(reads), min_len, max_mismatches);
-        *n = r.events.size();
-        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::DuplicationEvent));
-        if (span) std::memcpy(span, r.span.data(), r.span.size() * sizeof(uint32_t));
-        if (counters) {
-            const uint64_t c[7] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.forward, r.n.discordant};
-            std::memcpy(counters, c, sizeof c);
-        }
-        return 0;
+        const bronko::DuplicationResult r = bronko::duplication_events(*static_cast<const bronko::Index*>(h), file_id, split_lines(reads), min_len, max_mismatches);
+        const uint64_t c[7] = {r.n.records, r.n.anchored, r.n.ref_spanning, r.n.supporting, r.n.short_, r.n.forward, r.n.discordant};
+        return events_out(r, c, cap, rows, n, span, counters);
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 

@@ -7,7 +7,7 @@
 #include <stdexcept>
 #include <tuple>
 
-#include "anchor_genome.hpp"
+#include "event_twin.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -16,53 +16,39 @@ namespace {
 
 struct Tables {
     std::map<std::tuple<uint32_t, int, int, uint64_t>, std::pair<uint32_t, uint32_t>> events;   // (cell, kind, length, seq) -> fwd, rev
-    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    SpanCount span;
     IndelCounters n;
+    explicit Tables(const FileCells& g) : span(g) {}
 };
 
 void add_record(const AnchorGenome& g, const std::string& rec, int L, int M, Tables& t) {
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
-    int f_off = -1, b_off = -1;
-    uint32_t f_cell = 0, b_cell = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &f_cell, &f_ag)) { f_off = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &b_cell, &b_ag)) { b_off = o; break; }
-    if (f_off < 0 || b_off < 0 || f_ag != b_ag) return;
-    const bool against = f_ag;
-    std::string r = rec;                             // r': the record along the reference
-    int64_t a, b, ca, cb;
-    if (against) {
-        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
-        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
-    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
+    const EndAnchors ends = end_anchors(g, rec);
+    if (!ends.both() || ends.f_ag != ends.b_ag) return;
+    const Oriented o = orient(rec, k, ends);
+    const std::string& r = o.r;
+    const int64_t a = o.a, b = o.b;
     if (a + k > b) return;
     t.n.anchored++;
-    const int64_t dL = ca - a, dR = cb - b, delta = dR - dL;
+    const int64_t dL = o.ca - a, dR = o.cb - b, delta = dR - dL;
     if (delta > L || -delta > L) { t.n.discordant++; return; }
-    const int s = g.seq_of(ca);
-    if (g.seq_of(cb) != s) return;
-    const int64_t lo = std::min(dL, dR), hi = std::max(dL, dR) + n;
-    if (lo < g.first[(size_t)s] || hi > g.first[(size_t)s + 1]) return;
+    switch (t.span.place(g, o, M)) {
+        case Placed::outside: return;
+        case Placed::discordant: t.n.discordant++; return;
+        case Placed::spanning: t.n.ref_spanning++; return;
+        case Placed::shifted: break;
+    }
+    const int s = g.seq_of(o.ca);
+    if (!g.holds_acgt((size_t)s, std::min(dL, dR), std::max(dL, dR) + n)) return;
     const std::string& ref = g.text;
-    for (int64_t c = lo; c < hi; c++) if (!is_acgt(ref[(size_t)c])) return;
     auto mm = [&](int64_t j, int64_t d) { return r[(size_t)j] != ref[(size_t)(d + j)] ? 1 : 0; };
     auto floor_of = [&](int64_t pos) {               // first cell of the stretch of ACGT letters of the sequence that holds pos - 1
         int64_t f = pos - 1;
         while (f - 1 >= g.first[(size_t)s] && is_acgt(ref[(size_t)(f - 1)])) f--;
         return f;
     };
-    if (delta == 0) {
-        int m = 0;
-        for (int64_t j = 0; j < n; j++) m += mm(j, dL);
-        if (m > M) { t.n.discordant++; return; }
-        t.n.ref_spanning++;
-        t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
-        return;
-    }
     const int64_t I = delta < 0 ? -delta : 0, D = delta > 0 ? delta : 0;
     const int64_t p0 = a + k, p1 = b - I;            // the breakpoint's range
     if (p0 > p1) { t.n.discordant++; return; }
@@ -88,7 +74,7 @@ void add_record(const AnchorGenome& g, const std::string& rec, int L, int M, Tab
     }
     t.n.supporting++;
     auto& e = t.events[std::make_tuple((uint32_t)(g.cell0 + pos), D ? 0 : 1, (int)(D ? D : I), seq)];
-    (against ? e.second : e.first)++;
+    (o.against ? e.second : e.first)++;
 }
 
 }  // namespace
@@ -103,24 +89,11 @@ IndelResult indel_events(const Index& ix, int file, const std::vector<std::strin
     if (max_len < 1 || max_len > kIndelMaxLen) throw std::runtime_error("indel_events: max_len must be 1..32");
     if (max_mismatches < 0 || max_mismatches > kIndelMaxMismatches) throw std::runtime_error("indel_events: max_mismatches must be 0..8");
     const AnchorGenome g(ix, file);
-    Tables t;
-    t.span.assign(g.text.size() + 2, 0);
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) add_record(g, run, max_len, max_mismatches, t);
-            run.clear();
-        }
-    }
+    Tables t(g);
+    for_each_record(reads, g.k, [&](const std::string& rec) { add_record(g, rec, max_len, max_mismatches, t); });
     IndelResult out;
     out.n = t.n;
-    out.span.assign((size_t)ix.total_cells(), 0u);
-    int64_t acc = 0;
-    std::vector<uint32_t> sums(g.text.size());
-    for (size_t c = 0; c < g.text.size(); c++) { acc += t.span[c]; sums[c] = (uint32_t)acc; out.span[(size_t)g.cell0 + c] = (uint32_t)acc; }
+    const std::vector<uint32_t> sums = t.span.sums(ix, g, &out.span);
     for (const auto& kv : t.events) {
         IndelEvent e;
         e.cell = std::get<0>(kv.first);
@@ -142,9 +115,7 @@ bool indel_reported(const IndelEvent& e, uint64_t min_reads, uint32_t min_af_ppm
 void write_indels_vcf(const std::string& out_path, const std::string& reads_path, const Index& ix, int file, std::vector<IndelEvent> events,
                       const IndelParams& p) {
     if (file < 0 || (size_t)file >= ix.files.size()) throw std::runtime_error("write_indels_vcf: no such genome file");
-    FILE* fp = fopen(out_path.c_str(), "w");
-    if (!fp) throw std::runtime_error("Failed to create indel vcf output file " + out_path);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const OutFile fp("indel vcf", out_path);
     const FileMeta& fm = ix.files[(size_t)file];
     fprintf(fp, "##fileformat=VCFv4.5\n##source=bronko-v0.1.0\n##reference=file://%s\n", reads_path.c_str());
     for (const auto& s : fm.sequences) fprintf(fp, "##contig=<ID=%s,length=%llu>\n", chrom_of(s.name).c_str(), (unsigned long long)s.len);
@@ -171,12 +142,11 @@ void write_indels_vcf(const std::string& out_path, const std::string& reads_path
         std::string ref_a(1, up(sm->seq[i - 1])), alt_a(ref_a);
         if (e.len > 0) for (uint64_t j = 0; j < len; j++) ref_a.push_back(up(sm->seq[i + j]));
         else for (uint64_t j = 0; j < len; j++) alt_a.push_back("ACGT"[(e.seq >> (2 * j)) & 3u]);
-        const uint64_t support = (uint64_t)e.fwd + e.rev, t = 10000ull * support / std::max<uint64_t>(1, support + e.ref_span);
-        fprintf(fp, "%s\t%llu\t.\t%s\t%s\t.\tPASS\tTYPE=%s;LEN=%llu;SF=%u;SR=%u;RS=%u;AF=%llu.%04llu\n", chrom_of(sm->name).c_str(), (unsigned long long)i,
+        fprintf(fp, "%s\t%llu\t.\t%s\t%s\t.\tPASS\tTYPE=%s;LEN=%llu;SF=%u;SR=%u;RS=%u;AF=%s\n", chrom_of(sm->name).c_str(), (unsigned long long)i,
                 ref_a.c_str(), alt_a.c_str(), e.len > 0 ? "DEL" : "INS", (unsigned long long)len, e.fwd, e.rev, e.ref_span,
-                (unsigned long long)(t / 10000), (unsigned long long)(t % 10000));
+                freq_text((uint64_t)e.fwd + e.rev, e.ref_span).c_str());
     }
-    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write indel vcf file " + out_path);
+    fp.finish();
 }
 
 }  // namespace bronko

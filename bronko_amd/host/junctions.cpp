@@ -7,7 +7,7 @@
 #include <stdexcept>
 #include <tuple>
 
-#include "anchor_genome.hpp"
+#include "event_twin.hpp"
 #include "lcb.hpp"
 
 namespace bronko {
@@ -16,47 +16,33 @@ namespace {
 
 struct Tables {
     std::map<std::pair<uint32_t, uint32_t>, std::pair<uint32_t, uint32_t>> events;   // (cell, D) -> fwd, rev
-    std::vector<int64_t> span;                       // difference array over the file's cells (+ 2)
+    SpanCount span;
     JunctionCounters n;
+    explicit Tables(const FileCells& g) : span(g) {}
 };
 
 void add_record(const AnchorGenome& g, const std::string& rec, int64_t L, int M, Tables& t) {
     const int k = g.k, n = (int)rec.size();
     t.n.records++;
     if (n < 2 * k) return;
-    int f_off = -1, b_off = -1;
-    uint32_t f_cell = 0, b_cell = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &f_cell, &f_ag)) { f_off = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &b_cell, &b_ag)) { b_off = o; break; }
-    if (f_off < 0 || b_off < 0 || f_ag != b_ag) return;
-    const bool against = f_ag;
-    std::string r = rec;                             // r': the record along the reference
-    int64_t a, b, ca, cb;
-    if (against) {
-        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
-        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
-    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
+    const EndAnchors ends = end_anchors(g, rec);
+    if (!ends.both() || ends.f_ag != ends.b_ag) return;
+    const Oriented o = orient(rec, k, ends);
+    const std::string& r = o.r;
+    const int64_t a = o.a, b = o.b;
     if (a + k > b) return;
     t.n.anchored++;
-    const int64_t dL = ca - a, dR = cb - b, delta = dR - dL;
-    const int s = g.seq_of(ca);
-    if (g.seq_of(cb) != s) return;
-    const int64_t lo = std::min(dL, dR), hi = std::max(dL, dR) + n;
-    if (lo < g.first[(size_t)s] || hi > g.first[(size_t)s + 1]) return;
-    const std::string& ref = g.text;
-    for (int64_t c = lo; c < hi; c++) if (!is_acgt(ref[(size_t)c])) return;
-    auto mm = [&](int64_t j, int64_t d) { return r[(size_t)j] != ref[(size_t)(d + j)] ? 1 : 0; };
-    if (delta == 0) {
-        int m = 0;
-        for (int64_t j = 0; j < n; j++) m += mm(j, dL);
-        if (m > M) { t.n.discordant++; return; }
-        t.n.ref_spanning++;
-        t.span[(size_t)(dL + a + k)] += 1; t.span[(size_t)(dL + b + 1)] -= 1;
-        return;
+    switch (t.span.place(g, o, M)) {
+        case Placed::outside: return;
+        case Placed::discordant: t.n.discordant++; return;
+        case Placed::spanning: t.n.ref_spanning++; return;
+        case Placed::shifted: break;
     }
+    const int64_t dL = o.ca - a, dR = o.cb - b, delta = dR - dL;
+    const int s = g.seq_of(o.ca);
+    if (!g.holds_acgt((size_t)s, std::min(dL, dR), std::max(dL, dR) + n)) return;
+    const std::string& ref = g.text;
+    auto mm = [&](int64_t j, int64_t d) { return r[(size_t)j] != ref[(size_t)(d + j)] ? 1 : 0; };
     if (delta < L && -delta < L) { t.n.short_++; return; }
     if (delta < 0) { t.n.backward++; return; }
     const int64_t D = delta, p0 = a + k, p1 = b;     // the breakpoint's range
@@ -76,7 +62,7 @@ void add_record(const AnchorGenome& g, const std::string& rec, int64_t L, int M,
     while (pos - 1 > F && ref[(size_t)(pos - 1)] == ref[(size_t)(pos + D - 1)]) pos--;
     t.n.supporting++;
     auto& e = t.events[std::make_pair((uint32_t)(g.cell0 + pos), (uint32_t)D)];
-    (against ? e.second : e.first)++;
+    (o.against ? e.second : e.first)++;
 }
 
 }  // namespace
@@ -85,24 +71,11 @@ JunctionResult junction_events(const Index& ix, int file, const std::vector<std:
     if (min_len < 1 || min_len > kJunctionMaxLen) throw std::runtime_error("junction_events: min_len must be 1..2^27 - 1");
     if (max_mismatches < 0 || max_mismatches > kJunctionMaxMismatches) throw std::runtime_error("junction_events: max_mismatches must be 0..8");
     const AnchorGenome g(ix, file);
-    Tables t;
-    t.span.assign(g.text.size() + 2, 0);
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) add_record(g, run, (int64_t)min_len, max_mismatches, t);
-            run.clear();
-        }
-    }
+    Tables t(g);
+    for_each_record(reads, g.k, [&](const std::string& rec) { add_record(g, rec, (int64_t)min_len, max_mismatches, t); });
     JunctionResult out;
     out.n = t.n;
-    out.span.assign((size_t)ix.total_cells(), 0u);
-    int64_t acc = 0;
-    std::vector<uint32_t> sums(g.text.size());
-    for (size_t c = 0; c < g.text.size(); c++) { acc += t.span[c]; sums[c] = (uint32_t)acc; out.span[(size_t)g.cell0 + c] = (uint32_t)acc; }
+    const std::vector<uint32_t> sums = t.span.sums(ix, g, &out.span);
     for (const auto& kv : t.events) {               // (the map's order is (cell, len))
         JunctionEvent e;
         e.cell = kv.first.first; e.len = kv.first.second;
@@ -115,27 +88,23 @@ JunctionResult junction_events(const Index& ix, int file, const std::vector<std:
 
 void write_junctions_tsv(const std::string& out_path, const Index& ix, int file, std::vector<JunctionEvent> events, const JunctionParams& p) {
     const FileCells g(ix, file);
-    FILE* fp = fopen(out_path.c_str(), "w");
-    if (!fp) throw std::runtime_error("Failed to create junctions output file " + out_path);
-    struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{fp};
+    const OutFile fp("junctions", out_path);
     fprintf(fp, "##junction_min_len=%u\n##junction_max_mismatches=%u\n##junction_min_reads=%llu\n", p.min_len, p.max_mismatches, (unsigned long long)p.min_reads);
     fputs("chrom\tdonor\tacceptor\tlength\tfwd\trev\treads\tspan_donor\tspan_acceptor\tfreq\thomology\n", fp);
     std::sort(events.begin(), events.end(), [](const JunctionEvent& x, const JunctionEvent& y) { return std::tie(x.cell, x.len) < std::tie(y.cell, y.len); });
     const FileMeta& fm = ix.files[(size_t)file];
     for (const JunctionEvent& e : events) {
         const int64_t pos = (int64_t)e.cell - g.cell0, D = e.len;
-        size_t s = 0;
-        while (s + 2 < g.first.size() && g.first[s + 1] <= pos) s++;
+        const size_t s = (size_t)g.seq_of(pos);
         if (pos <= g.first[s] || pos + D >= g.first[s + 1]) throw std::runtime_error("write_junctions_tsv: an event outside the genome file's sequences");
         int64_t h = 0;                               // how far the junction could slide to the right
         while (h < D && pos + D + h < g.first[s + 1] && is_acgt(g.text[(size_t)(pos + h)]) && g.text[(size_t)(pos + h)] == g.text[(size_t)(pos + D + h)]) h++;
         const uint64_t reads = (uint64_t)e.fwd + e.rev, donor = (uint64_t)(pos - g.first[s]);
-        const uint64_t t = 10000ull * reads / std::max<uint64_t>(1, reads + e.span_donor);
-        fprintf(fp, "%s\t%llu\t%llu\t%u\t%u\t%u\t%llu\t%u\t%u\t%llu.%04llu\t%lld\n", chrom_of(fm.sequences[s].name).c_str(), (unsigned long long)donor,
+        fprintf(fp, "%s\t%llu\t%llu\t%u\t%u\t%u\t%llu\t%u\t%u\t%s\t%lld\n", chrom_of(fm.sequences[s].name).c_str(), (unsigned long long)donor,
                 (unsigned long long)(donor + (uint64_t)D + 1), e.len, e.fwd, e.rev, (unsigned long long)reads, e.span_donor, e.span_acceptor,
-                (unsigned long long)(t / 10000), (unsigned long long)(t % 10000), (long long)h);
+                freq_text(reads, e.span_donor).c_str(), (long long)h);
     }
-    if (fflush(fp) != 0 || ferror(fp)) throw std::runtime_error("Failed to write junctions file " + out_path);
+    fp.finish();
 }
 
 }  // namespace bronko

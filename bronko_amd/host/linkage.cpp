@@ -18,21 +18,12 @@ void place_record(const AnchorGenome& g, const std::string& rec, int M, LinkResu
     const int k = g.k, n = (int)rec.size();
     out.n.records++;
     if (n < 2 * k || n > 65535) { out.n.unplaced++; return; }
-    int f_off = -1, b_off = -1;
-    uint32_t f_cell = 0, b_cell = 0;
-    bool f_ag = false, b_ag = false;
-    for (int o = 0; o <= 24 && o + k <= n; o += 8)
-        if (g.anchor(rec.data() + o, &f_cell, &f_ag)) { f_off = o; break; }
-    for (int o = n - k; o >= n - k - 24 && o >= 0; o -= 8)
-        if (g.anchor(rec.data() + o, &b_cell, &b_ag)) { b_off = o; break; }
-    if (f_off < 0 || b_off < 0 || f_ag != b_ag) { out.n.unplaced++; return; }
-    const bool against = f_ag;
-    std::string r = rec;                             // r': the record along the reference
-    int64_t a, b, ca, cb;
-    if (against) {
-        for (int j = 0; j < n; j++) r[(size_t)j] = comp(rec[(size_t)(n - 1 - j)]);
-        a = n - k - b_off; ca = b_cell; b = n - k - f_off; cb = f_cell;
-    } else { a = f_off; ca = f_cell; b = b_off; cb = b_cell; }
+    const EndAnchors ends = end_anchors(g, rec);
+    if (!ends.both() || ends.f_ag != ends.b_ag) { out.n.unplaced++; return; }
+    const Oriented o = orient(rec, k, ends);
+    const bool against = o.against;
+    const std::string& r = o.r;
+    const int64_t a = o.a, b = o.b, ca = o.ca, cb = o.cb;
     const int64_t dL = ca - a, dR = cb - b;
     const int s = g.seq_of(ca);
     bool ok = a + k <= b && dL == dR && g.seq_of(cb) == s && dL >= g.first[(size_t)s] && dL + n <= g.first[(size_t)s + 1];
@@ -57,16 +48,7 @@ LinkResult link_rows(const Index& ix, int file, const std::vector<std::string>& 
     if (max_mismatches < 0 || max_mismatches > kLinkMaxMismatches) throw std::runtime_error("link_rows: max_mismatches must be 0..8");
     const AnchorGenome g(ix, file);
     LinkResult out;
-    std::string run;
-    for (const std::string& read : reads) {
-        run.clear();
-        for (size_t i = 0; i <= read.size(); i++) {
-            const char c = i < read.size() ? (char)(read[i] >= 'a' && read[i] <= 'z' ? read[i] - 32 : read[i]) : 'N';
-            if (is_acgt(c)) { run.push_back(c); continue; }
-            if ((int)run.size() >= g.k) place_record(g, run, max_mismatches, out);
-            run.clear();
-        }
-    }
+    for_each_record(reads, g.k, [&](const std::string& rec) { place_record(g, rec, max_mismatches, out); });
     return out;
 }
 

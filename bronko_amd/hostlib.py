@@ -301,16 +301,52 @@ INDEL_DTYPE = np.dtype([("cell", np.uint32), ("len", np.int32), ("fwd", np.uint3
                         ("pad", np.uint32), ("seq", np.uint64)])
 
 
-def _indel_lib():
+_VP, _U64, _U32 = C.c_void_p, C.c_uint64, C.c_uint32
+_EVENTS_TAIL = [_U64, _VP, C.POINTER(_U64), _VP, _VP]      # what every bh_*_events ends with: cap, rows, n, span, counters
+
+
+def _bound(ready, signatures):
+    """The library with the argtypes of the bh_* functions of `signatures` ({name: argtypes}, each returning int) set, once."""
     L = _caller_lib()
-    if not hasattr(L, "_indels_ready"):
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.bh_indel_events.restype = C.c_int
-        L.bh_indel_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
-        L.bh_write_indels_vcf.restype = C.c_int
-        L.bh_write_indels_vcf.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, vp, u64, u32, u32, u64, u32]
-        L._indels_ready = True
+    if not hasattr(L, ready):
+        for name, argtypes in signatures.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = C.c_int, argtypes
+        setattr(L, ready, True)
     return L
+
+
+def _events(fn, ix, file_id, reads, params, shape, dtype, n_counters):
+    """The two calls of a bh_*_events over ASCII reads, the first for the table's size: (its records as an array of `dtype` with
+    `shape` per record, the prefix-summed span array of all cells, the counters)."""
+    joined = "\n".join(reads).encode()
+    n = C.c_uint64()
+    span = np.zeros(max(1, ix.total_cells), np.uint32)
+    counters = np.zeros(n_counters, np.uint64)
+    if fn(ix.h, file_id, joined, *params, 0, None, C.byref(n), None, None) != 0:
+        raise _host_error(load())
+    rec = np.zeros((max(1, n.value),) + shape, dtype)
+    if fn(ix.h, file_id, joined, *params, n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
+        raise _host_error(load())
+    return rec[:n.value], span[:ix.total_cells], tuple(int(c) for c in counters)
+
+
+def _u32_rows(rec):
+    """[n][width] u32 as sorted tuples of int"""
+    return sorted(tuple(int(v) for v in r) for r in rec)
+
+
+def _u32_records(rows, width):
+    """rows of `width` numbers each as the [n][width] u32 that a bh_write_* takes (one zero record for none)"""
+    rec = np.zeros((max(1, len(rows)), width), np.uint32)
+    for i, r in enumerate(rows):
+        rec[i] = r
+    return rec
+
+
+def _indel_lib():
+    return _bound("_indels_ready", {"bh_indel_events": [_VP, C.c_int, C.c_char_p, C.c_int, C.c_int] + _EVENTS_TAIL,
+                                    "bh_write_indels_vcf": [_VP, C.c_int, C.c_char_p, C.c_char_p, _VP, _U64, _U32, _U32, _U64, _U32]})
 
 
 def indel_rows(rec):
@@ -323,17 +359,8 @@ def indel_rows(rec):
 def indel_events(ix, file_id, reads, max_len=32, max_mismatches=2):
     """The host twin of the engine's indel pass (indels.cpp indel_events) over ASCII reads: (rows of the whole table as indel_rows
     gives them, the prefix-summed span array of all cells, (records, anchored, ref_spanning, supporting, discordant))."""
-    L = _indel_lib()
-    joined = "\n".join(reads).encode()
-    n = C.c_uint64()
-    span = np.zeros(max(1, ix.total_cells), np.uint32)
-    counters = np.zeros(5, np.uint64)
-    if L.bh_indel_events(ix.h, file_id, joined, int(max_len), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
-        raise _host_error(L)
-    rec = np.zeros(max(1, n.value), INDEL_DTYPE)
-    if L.bh_indel_events(ix.h, file_id, joined, int(max_len), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
-        raise _host_error(L)
-    return indel_rows(rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+    rec, span, counters = _events(_indel_lib().bh_indel_events, ix, file_id, reads, (int(max_len), int(max_mismatches)), (), INDEL_DTYPE, 5)
+    return indel_rows(rec), span, counters
 
 
 def write_indels_vcf(path, ix, file_id, reads_path, rows, max_len=32, max_mismatches=2, min_reads=5, min_af_ppm=30000):
@@ -348,158 +375,86 @@ def write_indels_vcf(path, ix, file_id, reads_path, rows, max_len=32, max_mismat
 
 
 def _junction_lib():
-    L = _caller_lib()
-    if not hasattr(L, "_junctions_ready"):
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.bh_junction_events.restype = C.c_int
-        L.bh_junction_events.argtypes = [vp, C.c_int, C.c_char_p, u32, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
-        L.bh_write_junctions_tsv.restype = C.c_int
-        L.bh_write_junctions_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, u64]
-        L._junctions_ready = True
-    return L
+    return _bound("_junctions_ready", {"bh_junction_events": [_VP, C.c_int, C.c_char_p, _U32, C.c_int] + _EVENTS_TAIL,
+                                       "bh_write_junctions_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U32, _U32, _U64]})
 
 
 def junction_events(ix, file_id, reads, min_len=33, max_mismatches=2):
     """The host twin of the engine's junction pass (junctions.cpp junction_events) over ASCII reads: (rows of the whole table as
     bk_junction_record (cell, len, fwd, rev, span_donor, span_acceptor) sorted by (cell, len), the prefix-summed span array of all
     cells, (records, anchored, ref_spanning, supporting, short, backward, discordant))."""
-    L = _junction_lib()
-    joined = "\n".join(reads).encode()
-    n = C.c_uint64()
-    span = np.zeros(max(1, ix.total_cells), np.uint32)
-    counters = np.zeros(7, np.uint64)
-    if L.bh_junction_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
-        raise _host_error(L)
-    rec = np.zeros((max(1, n.value), 6), np.uint32)
-    if L.bh_junction_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
-        raise _host_error(L)
-    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+    rec, span, counters = _events(_junction_lib().bh_junction_events, ix, file_id, reads, (int(min_len), int(max_mismatches)), (6,), np.uint32, 7)
+    return _u32_rows(rec), span, counters
 
 
 def write_junctions_tsv(path, ix, file_id, rows, min_len=33, max_mismatches=2, min_reads=5):
     """The --junctions writer (junctions.cpp write_junctions_tsv): rows as junction_events gives them, already filtered."""
-    rec = np.zeros((max(1, len(rows)), 6), np.uint32)
-    for i, r in enumerate(rows):
-        rec[i] = r
+    rec = _u32_records(rows, 6)
     L = _junction_lib()
     if L.bh_write_junctions_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(min_len), int(max_mismatches), int(min_reads)) != 0:
         raise _host_error(L)
 
 
 def _copyback_lib():
-    L = _caller_lib()
-    if not hasattr(L, "_copybacks_ready"):
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.bh_copyback_events.restype = C.c_int
-        L.bh_copyback_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
-        L.bh_write_copybacks_tsv.restype = C.c_int
-        L.bh_write_copybacks_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u64, u32]
-        L._copybacks_ready = True
-    return L
+    return _bound("_copybacks_ready", {"bh_copyback_events": [_VP, C.c_int, C.c_char_p, C.c_int] + _EVENTS_TAIL,
+                                       "bh_write_copybacks_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U32, _U64, _U32]})
 
 
 def copyback_events(ix, file_id, reads, max_mismatches=2):
     """The host twin of the engine's copy-back pass (copybacks.cpp copyback_events) over ASCII reads: (rows of the whole table as
     bk_copyback_record (lo, hi, kind, lo_first, hi_first, span_lo, span_hi, 0) sorted, the prefix-summed span array of all cells,
     (records, same_strand, ref_spanning, switched, supporting, discordant))."""
-    L = _copyback_lib()
-    joined = "\n".join(reads).encode()
-    n = C.c_uint64()
-    span = np.zeros(max(1, ix.total_cells), np.uint32)
-    counters = np.zeros(6, np.uint64)
-    if L.bh_copyback_events(ix.h, file_id, joined, int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
-        raise _host_error(L)
-    rec = np.zeros((max(1, n.value), 8), np.uint32)
-    if L.bh_copyback_events(ix.h, file_id, joined, int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
-        raise _host_error(L)
-    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+    rec, span, counters = _events(_copyback_lib().bh_copyback_events, ix, file_id, reads, (int(max_mismatches),), (8,), np.uint32, 6)
+    return _u32_rows(rec), span, counters
 
 
 def write_copybacks_tsv(path, ix, file_id, rows, max_mismatches=2, min_reads=5, min_dist=0):
     """The --copybacks writer (copybacks.cpp write_copybacks_tsv): rows as copyback_events gives them, already filtered."""
-    rec = np.zeros((max(1, len(rows)), 8), np.uint32)
-    for i, r in enumerate(rows):
-        rec[i] = r
+    rec = _u32_records(rows, 8)
     L = _copyback_lib()
     if L.bh_write_copybacks_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(max_mismatches), int(min_reads), int(min_dist)) != 0:
         raise _host_error(L)
 
 
 def _chimera_lib():
-    L = _caller_lib()
-    if not hasattr(L, "_chimeras_ready"):
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.bh_chimera_events.restype = C.c_int
-        L.bh_chimera_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
-        L.bh_write_chimeras_tsv.restype = C.c_int
-        L.bh_write_chimeras_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u64, u64, u64]
-        L._chimeras_ready = True
-    return L
+    return _bound("_chimeras_ready", {"bh_chimera_events": [_VP, C.c_int, C.c_char_p, C.c_int] + _EVENTS_TAIL,
+                                      "bh_write_chimeras_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U32, _U64, _U64, _U64]})
 
 
 def chimera_events(ix, file_id, reads, max_mismatches=2):
     """The host twin of the engine's chimera pass (chimeras.cpp chimera_events) over ASCII reads: (rows of the whole table as
     bk_chimera_record (lo, hi, sides, lo_first, hi_first, span_lo, span_hi, 0) sorted, the prefix-summed span array of all cells,
     (records, same_strand, ref_spanning, crossed, supporting, discordant))."""
-    L = _chimera_lib()
-    joined = "\n".join(reads).encode()
-    n = C.c_uint64()
-    span = np.zeros(max(1, ix.total_cells), np.uint32)
-    counters = np.zeros(6, np.uint64)
-    if L.bh_chimera_events(ix.h, file_id, joined, int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
-        raise _host_error(L)
-    rec = np.zeros((max(1, n.value), 8), np.uint32)
-    if L.bh_chimera_events(ix.h, file_id, joined, int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
-        raise _host_error(L)
-    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+    rec, span, counters = _events(_chimera_lib().bh_chimera_events, ix, file_id, reads, (int(max_mismatches),), (8,), np.uint32, 6)
+    return _u32_rows(rec), span, counters
 
 
 def write_chimeras_tsv(path, ix, file_id, rows, max_mismatches=2, min_reads=5, supporting=0, ref_spanning=0):
     """The --chimeras writer (chimeras.cpp write_chimeras_tsv): rows as chimera_events gives them, already filtered, and the sample's
     two tallies that the header prints."""
-    rec = np.zeros((max(1, len(rows)), 8), np.uint32)
-    for i, r in enumerate(rows):
-        rec[i] = r
+    rec = _u32_records(rows, 8)
     L = _chimera_lib()
     if L.bh_write_chimeras_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(max_mismatches), int(min_reads), int(supporting), int(ref_spanning)) != 0:
         raise _host_error(L)
 
 
 def _breakend_lib():
-    L = _caller_lib()
-    if not hasattr(L, "_breakends_ready"):
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.bh_breakend_events.restype = C.c_int
-        L.bh_breakend_events.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
-        L.bh_write_breakends_tsv.restype = C.c_int
-        L.bh_write_breakends_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, u64, vp]
-        L._breakends_ready = True
-    return L
+    return _bound("_breakends_ready", {"bh_breakend_events": [_VP, C.c_int, C.c_char_p, C.c_int, C.c_int] + _EVENTS_TAIL,
+                                       "bh_write_breakends_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U32, _U32, _U64, _VP]})
 
 
 def breakend_events(ix, file_id, reads, min_clip=20, max_mismatches=2):
     """The host twin of the engine's breakend pass (breakends.cpp breakend_events) over ASCII reads: (rows of the whole table as
     bk_breakend_record (cell, tag, side, fwd, rev, site_reads, span, 0) sorted, the prefix-summed span array of all cells,
     (records, one_anchor, ref_spanning, supporting, short, through, discordant, unplaced))."""
-    L = _breakend_lib()
-    joined = "\n".join(reads).encode()
-    n = C.c_uint64()
-    span = np.zeros(max(1, ix.total_cells), np.uint32)
-    counters = np.zeros(8, np.uint64)
-    if L.bh_breakend_events(ix.h, file_id, joined, int(min_clip), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
-        raise _host_error(L)
-    rec = np.zeros((max(1, n.value), 8), np.uint32)
-    if L.bh_breakend_events(ix.h, file_id, joined, int(min_clip), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
-        raise _host_error(L)
-    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+    rec, span, counters = _events(_breakend_lib().bh_breakend_events, ix, file_id, reads, (int(min_clip), int(max_mismatches)), (8,), np.uint32, 8)
+    return _u32_rows(rec), span, counters
 
 
 def write_breakends_tsv(path, ix, file_id, rows, min_clip=20, max_mismatches=2, min_reads=5, tallies=(0,) * 10):
     """The --breakends writer (breakends.cpp write_breakends_tsv): rows as breakend_events gives them, already filtered, and the
     sample's ten tallies (bk_breakend_summary's, without overflow) that the header prints."""
-    rec = np.zeros((max(1, len(rows)), 8), np.uint32)
-    for i, r in enumerate(rows):
-        rec[i] = r
+    rec = _u32_records(rows, 8)
     t = np.array([int(v) for v in tallies], np.uint64)
     assert t.shape == (10,)
     L = _breakend_lib()
@@ -508,39 +463,21 @@ def write_breakends_tsv(path, ix, file_id, rows, min_clip=20, max_mismatches=2, 
 
 
 def _duplication_lib():
-    L = _caller_lib()
-    if not hasattr(L, "_duplications_ready"):
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.bh_duplication_events.restype = C.c_int
-        L.bh_duplication_events.argtypes = [vp, C.c_int, C.c_char_p, u32, C.c_int, u64, vp, C.POINTER(u64), vp, vp]
-        L.bh_write_duplications_tsv.restype = C.c_int
-        L.bh_write_duplications_tsv.argtypes = [vp, C.c_int, C.c_char_p, vp, u64, u32, u32, u64]
-        L._duplications_ready = True
-    return L
+    return _bound("_duplications_ready", {"bh_duplication_events": [_VP, C.c_int, C.c_char_p, _U32, C.c_int] + _EVENTS_TAIL,
+                                          "bh_write_duplications_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U32, _U32, _U64]})
 
 
 def duplication_events(ix, file_id, reads, min_len=33, max_mismatches=2):
     """The host twin of the engine's duplication pass (duplications.cpp duplication_events) over ASCII reads: (rows of the whole table as
     bk_duplication_record (cell, len, fwd, rev, span_start, span_end) sorted by (cell, len), the prefix-summed span array of all
     cells, (records, anchored, ref_spanning, supporting, short, forward, discordant))."""
-    L = _duplication_lib()
-    joined = "\n".join(reads).encode()
-    n = C.c_uint64()
-    span = np.zeros(max(1, ix.total_cells), np.uint32)
-    counters = np.zeros(7, np.uint64)
-    if L.bh_duplication_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), 0, None, C.byref(n), None, None) != 0:
-        raise _host_error(L)
-    rec = np.zeros((max(1, n.value), 6), np.uint32)
-    if L.bh_duplication_events(ix.h, file_id, joined, int(min_len), int(max_mismatches), n.value, rec.ctypes.data, C.byref(n), span.ctypes.data, counters.ctypes.data) != 0:
-        raise _host_error(L)
-    return sorted(tuple(int(v) for v in r) for r in rec[:n.value]), span[:ix.total_cells], tuple(int(c) for c in counters)
+    rec, span, counters = _events(_duplication_lib().bh_duplication_events, ix, file_id, reads, (int(min_len), int(max_mismatches)), (6,), np.uint32, 7)
+    return _u32_rows(rec), span, counters
 
 
 def write_duplications_tsv(path, ix, file_id, rows, min_len=33, max_mismatches=2, min_reads=5):
     """The --duplications writer (duplications.cpp write_duplications_tsv): rows as duplication_events gives them, already filtered."""
-    rec = np.zeros((max(1, len(rows)), 6), np.uint32)
-    for i, r in enumerate(rows):
-        rec[i] = r
+    rec = _u32_records(rows, 6)
     L = _duplication_lib()
     if L.bh_write_duplications_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(min_len), int(max_mismatches), int(min_reads)) != 0:
         raise _host_error(L)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Build tools/breakends_sanitize.cpp with AddressSanitizer and UBSan and run it over the crafted records of tests/breakend_cases.py
-(k = 21 and 31), on the CPU.  Nothing of it is loaded into Python: the program is a child process with its own main."""
+(k = 21 and 31), on the CPU; after the breakend twin the program runs the twins of the other five event passes over the same records.
+Nothing of it is loaded into Python: the program is a child process with its own main."""
 import os
 import subprocess
 import sys
