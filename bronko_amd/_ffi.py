@@ -75,6 +75,12 @@ class IndelSummary(C.Structure):  # bk_indel_summary
                 ("discordant", C.c_uint64), ("candidates", C.c_uint64), ("reported", C.c_uint64), ("overflow", C.c_int32)]
 
 
+class ConsensusIndelSummary(C.Structure):  # bk_consensus_indel_summary
+    _fields_ = [("candidates", C.c_uint64), ("accepted", C.c_uint64), ("applied", C.c_uint64), ("contested", C.c_uint64), ("deletions", C.c_uint64),
+                ("insertions", C.c_uint64), ("deleted_bases", C.c_uint64), ("inserted_bases", C.c_uint64), ("frameshifts", C.c_uint64),
+                ("file_id", C.c_int32), ("overflow", C.c_int32)]
+
+
 class JunctionConfig(C.Structure):  # bk_junction_config
     _fields_ = [("min_len", C.c_uint32), ("max_mismatches", C.c_uint32), ("table_log2", C.c_uint32)]
 
@@ -188,6 +194,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
+           "bk_sample_consensus_indels", "bk_sample_download_consensus_indels",
            "bk_junctions_enable", "bk_sample_junctions", "bk_sample_download_junctions", "bk_sample_download_junction_span",
            "bk_copybacks_enable", "bk_sample_copybacks", "bk_sample_download_copybacks", "bk_sample_download_copyback_span",
            "bk_chimeras_enable", "bk_sample_chimeras", "bk_sample_download_chimeras", "bk_sample_download_chimera_span",
@@ -331,6 +338,10 @@ def load(testing=None):
     L.bk_sample_download_indels.argtypes = [vp, C.POINTER(IndelSummary), vp, u64]
     L.bk_sample_download_indel_span.restype = C.c_int
     L.bk_sample_download_indel_span.argtypes = [vp, vp, u64]
+    L.bk_sample_consensus_indels.restype = C.c_int
+    L.bk_sample_consensus_indels.argtypes = [vp]
+    L.bk_sample_download_consensus_indels.restype = C.c_int
+    L.bk_sample_download_consensus_indels.argtypes = [vp, C.POINTER(ConsensusIndelSummary), vp, u64]
     L.bk_junctions_enable.restype = C.c_int
     L.bk_junctions_enable.argtypes = [vp, C.POINTER(JunctionConfig)]
     L.bk_sample_junctions.restype = C.c_int

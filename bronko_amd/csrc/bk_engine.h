@@ -575,6 +575,13 @@ struct bk_engine {
     DevBuf<uint8_t> cons_letters;
     DevBuf<bk_consensus_summary> cons_out;
     bool cons_made = false;
+    bk_consensus_params cons_prm{};         // ... with these parameters
+    // bk_sample_consensus_indels (first use allocates): best and ties of every boundary, the accepted events, the summary; made of the
+    // current sample's letters as they are (a later bk_sample_consensus or bk_sample_call clears it)
+    DevBuf<unsigned int> ci_bounds;         // [2][total_cells + 1] ConsensusIndelArgs::best, ties in this order: zeroed by one memset
+    DevBuf<bk_consensus_indel_record> ci_rows;   // [BK_CONSENSUS_INDEL_MAX]
+    DevBuf<bk_consensus_indel_summary> ci_out;
+    bool ci_made = false;
     std::unique_ptr<Regions> regions;       // bk_regions_set (null: no regions, no launch, no buffers)
     bool regions_made = false;              // bk_sample_region_depths ran for the current sample and table
     std::unique_ptr<Indels> indels;         // bk_indels_enable (null: no table, no launch, no buffers)

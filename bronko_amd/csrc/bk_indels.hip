@@ -10,9 +10,10 @@
 //   indel_walk    incremental: moving p by one exchanges one comparison on dL for one on dR.  Events go to an open-addressing
 //                 table of its own: two key words, each claimed with a CAS; a slot matches iff both words are this event's, so the
 //                 loser of the second CAS probes on.  A full table raises the overflow word.
-//   indel_decode  a slot as a row, there once both key words are written: the events that pass the thresholds.
+//   indel_decode  a slot as a row (its key words: bk_indel_slot.h), there once both are written: the events that pass the thresholds.
 // Vector stores and atomics only.
 #include "bk_event_pass.h"
+#include "bk_indel_slot.h"
 
 namespace bk {
 namespace {
@@ -103,12 +104,11 @@ __device__ __forceinline__ void indel_walk(const IndelArgs& a, const uint4 work,
 }
 
 __device__ __forceinline__ bool indel_decode(const IndelArgs& a, uint64_t i, IndelRecordDev& row, bool& pass) {
-    const unsigned long long k0 = a.key0[i], k1 = a.key1[i];
-    if (k0 == kEventFreeWord || k1 == kEventFreeWord) return false;
-    row.cell = (uint32_t)k0;
-    const uint32_t kind = (uint32_t)(k0 >> 32) & 1u, len = ((uint32_t)(k0 >> 33) & 31u) + 1u;
-    row.len = kind ? -(int32_t)len : (int32_t)len;
-    row.seq = (k1 << 2) | ((k0 >> 38) & 3ull);
+    IndelSlot s;
+    if (!indel_slot_decode(a.key0[i], a.key1[i], s)) return false;
+    row.cell = s.cell;
+    row.len = s.kind ? -(int32_t)s.len : (int32_t)s.len;
+    row.seq = s.seq;
     row.fwd = a.counts[2u * i]; row.rev = a.counts[2u * i + 1u];
     row.ref_span = a.span[row.cell];
     row.pad = 0u;

@@ -522,6 +522,30 @@ struct IndelArgs : EventPassArgs {       // (`keys` is not used: the table's key
 };
 void launch_indel_scan(const IndelArgs& a, int n_cus, hipStream_t stream);
 void launch_indel_report(const IndelArgs& a, hipStream_t stream);
+// bk_sample_consensus_indels: the sample's indel events applied to its consensus letters (bk_consensus_indels.hip; the rule:
+// include/bronko_hip.h, DESIGN.md section CI).  Three passes over the indels' table, which none of them writes
+typedef bk_consensus_indel_record ConsensusIndelRecordDev;
+typedef bk_consensus_indel_summary ConsensusIndelSummaryDev;
+struct ConsensusIndelArgs {
+    ConsensusParamsDev prm;              // of the sample's last bk_sample_consensus
+    const unsigned long long* key0;      // the indels' event table (IndelArgs)
+    const unsigned long long* key1;
+    const unsigned int* counts;
+    uint32_t log2n;
+    uint32_t total_cells;
+    const unsigned int* span;            // prefix-summed (bk_sample_indels)
+    const unsigned long long* table_overflow;   // the indels' overflow tally: a full table makes this result an error too
+    const CallSummaryDev* out;           // bk_sample_call's: file_id
+    const int32_t* seq_first;            // where the selected genome's letters begin (ConsensusArgs)
+    const uint64_t* seq_cell;
+    unsigned int* best;                  // [total_cells + 1] per boundary: the largest s of an accepted event; zeroed by the caller
+    unsigned int* ties;                  // [total_cells + 1] ... and how many accepted events have it; zeroed by the caller
+    uint8_t* letters;                    // the consensus letters (ConsensusArgs::letters): '-' is stored at the applied deletions
+    uint64_t n_letters;                  // the room of `letters`
+    ConsensusIndelRecordDev* rows;       // [BK_CONSENSUS_INDEL_MAX] the accepted events, in no order
+    ConsensusIndelSummaryDev* summary;   // zeroed by the caller; the last pass writes file_id and adds the tallies
+};
+void launch_consensus_indels(const ConsensusIndelArgs& a, hipStream_t stream);
 // bk_junctions_enable: long deletions and subgenomic-RNA junctions from the reads (bk_junctions.hip; the rule: include/bronko_hip.h,
 // DESIGN.md section J)
 typedef bk_junction_record JunctionRecordDev;

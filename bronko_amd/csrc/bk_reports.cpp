@@ -1,6 +1,6 @@
 // bk_reports.cpp -- the reports made of a finalized sample's pileup on the device, and their downloads: the calls and the noise
-// (bk_sample_call, bk_caller.hip), the consensus (consensus_kernel, bk_caller.hip) and the per-region depths (bk_regions.hip).  Their
-// buffers and the flags that say whose sample a result is (called, cons_made, regions_made) are bk_engine's (bk_engine.h).  The entry
+// (bk_sample_call, bk_caller.hip), the consensus (consensus_kernel, bk_caller.hip) with the sample's indels applied to it (bk_consensus_indels.hip) and the per-region depths (bk_regions.hip).  Their
+// buffers and the flags that say whose sample a result is (called, cons_made, ci_made, regions_made) are bk_engine's (bk_engine.h).  The entry
 // points are extern "C" by their declarations in bronko_hip.h.
 #include <algorithm>
 #include <cstdlib>
@@ -54,7 +54,7 @@ int bk_sample_call(bk_engine* e, int n_mates, const bk_call_params* p) {
     bk_engine::Span sp(e, 1);
     bk::launch_call(a, ix.max_seqs_per_file, ix.max_file_cells, e->stream);
     BK_HIP(hipGetLastError());
-    e->called = true; e->cons_made = false; e->regions_made = false;   // (a consensus or a region report made before this call was of another selection)
+    e->called = true; e->cons_made = false; e->ci_made = false; e->regions_made = false;   // (a consensus or a region report made before this call was of another selection)
     return BK_OK;
 }
 
@@ -117,7 +117,8 @@ int bk_sample_consensus(bk_engine* e, const bk_consensus_params* p) {
     BK_HIP(hipMemsetAsync(e->cons_out.p, 0, sizeof(bk_consensus_summary), e->stream));
     bk::launch_consensus(a, ix.max_file_cells, e->stream);
     BK_HIP(hipGetLastError());
-    e->cons_made = true;
+    e->cons_made = true; e->cons_prm = *p;
+    e->ci_made = false;                     // (fresh letters: the indels are not in them)
     return BK_OK;
 }
 
@@ -128,6 +129,54 @@ int bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, ui
     if (int rc = download(e, summary, e->cons_out.p, 1)) return rc;
     const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->positions, cap), e->cons_letters.n);
     if (n && letters) return download(e, letters, e->cons_letters.p, (size_t)n);
+    return BK_OK;
+}
+
+// ---- the sample's indels applied to its consensus (bk_consensus_indels.hip) --------------------------------------------
+int bk_sample_consensus_indels(bk_engine* e) {
+    if (!e) return fail(BK_ERR_INVALID, "null engine");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_consensus_indels comes after bk_sample_finalize, bk_sample_consensus and bk_sample_indels");
+    if (!e->indels || !e->indels->in_sample)
+        return fail(BK_ERR_STATE, "bk_sample_consensus_indels: indels were not enabled for this sample (bk_indels_enable before bk_sample_begin)");
+    if (!e->cons_made) return fail(BK_ERR_STATE, "bk_sample_consensus_indels: bk_sample_consensus has not run for this sample");
+    if (!e->indels->made) return fail(BK_ERR_STATE, "bk_sample_consensus_indels: bk_sample_indels has not run for this sample");
+    const IndexTables& ix = *e->ix;
+    const Indels& d = *e->indels;
+    BK_HIP(hipSetDevice(e->device));
+    const size_t bounds = (size_t)ix.total_cells + 1;
+    if (!e->ci_out.p) {
+        BK_HIP(e->ci_bounds.alloc(2 * bounds));
+        BK_HIP(e->ci_rows.alloc(BK_CONSENSUS_INDEL_MAX));
+        BK_HIP(e->ci_out.alloc(1));
+    }
+    bk::ConsensusIndelArgs a{};
+    a.prm = e->cons_prm;
+    a.key0 = d.key0.p; a.key1 = d.key1.p; a.counts = d.counts.p; a.log2n = d.table_log2;
+    a.total_cells = (uint32_t)ix.total_cells;   // (below 2^27: bk_indels_enable)
+    a.span = d.span.p; a.table_overflow = d.tallies.p + bk::IndelArgs::kOverflow;
+    a.out = e->call_out.p; a.seq_first = ix.seq_first.p; a.seq_cell = ix.seq_cell.p;
+    a.best = e->ci_bounds.p; a.ties = e->ci_bounds.p + bounds;
+    a.letters = e->cons_letters.p; a.n_letters = e->cons_letters.n;
+    a.rows = e->ci_rows.p; a.summary = e->ci_out.p;
+    bk_engine::Span sp(e, 1);
+    BK_HIP(hipMemsetAsync(e->ci_bounds.p, 0, 2 * bounds * sizeof(unsigned int), e->stream));
+    BK_HIP(hipMemsetAsync(e->ci_out.p, 0, sizeof(bk_consensus_indel_summary), e->stream));
+    bk::launch_consensus_indels(a, e->stream);
+    BK_HIP(hipGetLastError());
+    e->ci_made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_consensus_indels(bk_engine* e, bk_consensus_indel_summary* s, bk_consensus_indel_record* rows, uint64_t cap) {
+    if (!e || !s) return fail(BK_ERR_INVALID, "null argument");
+    if (!e->ci_made) return fail(BK_ERR_STATE, "bk_sample_download_consensus_indels comes after this sample's bk_sample_consensus_indels");
+    BK_HIP(hipSetDevice(e->device));
+    if (int rc = download(e, s, e->ci_out.p, 1)) return rc;
+    if (s->overflow)
+        return fail(BK_ERR_INVALID, "bk_sample_download_consensus_indels: more than %d accepted events, or a full indel event table (bk_sample_download_indels tells)",
+                    BK_CONSENSUS_INDEL_MAX);
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(s->accepted, cap), e->ci_rows.n);
+    if (n && rows) return download(e, rows, e->ci_rows.p, (size_t)n);
     return BK_OK;
 }
 

@@ -473,6 +473,26 @@ class Engine:
         """bk_sample_download_indel_span: the prefix-summed span array of all cells (after sample_indels)."""
         return self._download_event_span(self._L.bk_sample_download_indel_span)
 
+    def sample_consensus_indels(self):
+        """bk_sample_consensus_indels: the sample's indel events applied to its consensus letters at the last sample_consensus's
+        parameters, on the device (asynchronous); after sample_consensus and sample_indels."""
+        _check(self._L.bk_sample_consensus_indels(self.h), self._L)
+
+    def download_consensus_indels(self, cap=None):
+        """(summary, rows) of sample_consensus_indels: min(cap, summary.accepted) rows (cell, len, support, ref_span, seq, applied) --
+        len > 0 a deletion, < 0 an insertion --, all by default, sorted by (cell, kind, length, seq)."""
+        dt = np.dtype([("cell", np.uint32), ("len", np.int32), ("support", np.uint32), ("ref_span", np.uint32), ("seq", np.uint64),
+                       ("applied", np.uint32), ("pad", np.uint32)])
+        summ = _ffi.ConsensusIndelSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_consensus_indels(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many rows there are)
+            cap = int(summ.accepted)
+        buf = np.zeros(max(1, cap), dt)
+        _check(self._L.bk_sample_download_consensus_indels(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        rows = [(int(r["cell"]), int(r["len"]), int(r["support"]), int(r["ref_span"]), int(r["seq"]), int(r["applied"])) for r in buf[:min(cap, int(summ.accepted))]]
+        rows.sort(key=lambda r: (r[0], 1 if r[1] < 0 else 0, abs(r[1]), r[4]))
+        return summ, rows
+
     def junctions_enable(self, min_len=33, max_mismatches=2, table_log2=16):
         """bk_junctions_enable: junction_scan_kernel runs behind every scan of the samples that begin from now on; min_len=None disables."""
         cfg = None if min_len is None else C.byref(_ffi.JunctionConfig(int(min_len), int(max_mismatches), int(table_log2)))

@@ -266,6 +266,8 @@ struct SampleData {
     std::vector<bk_region_depth> rrows;
     bk_indel_summary isumm{};                             // --indels
     std::vector<IndelEvent> indels;
+    bk_consensus_indel_summary cisumm{};                  // --consensus-indels
+    std::vector<ConsensusIndel> cons_indels;
     bk_junction_summary jsumm{};                          // --junctions
     std::vector<JunctionEvent> junctions;
     bk_copyback_summary cbsumm{};                         // --copybacks
@@ -607,6 +609,8 @@ struct CallRun {
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
         if (a.consensus) hip_check(bk_sample_consensus(e, &cfg.consensus), "bk_sample_consensus");
+        // ... and the indels join the letters where both lie: the few accepted events travel (bk_sample_download_consensus_indels below)
+        if (a.consensus_indels) hip_check(bk_sample_consensus_indels(e), "bk_sample_consensus_indels");
         // likewise: a few numbers per region travel (bk_sample_download_region_depths below)
         if (!region_table.empty()) hip_check(bk_sample_region_depths(e, cfg.region_min_depth), "bk_sample_region_depths");
     }
@@ -646,6 +650,8 @@ struct CallRun {
             d.rrows.resize(std::min<size_t>(d.rrows.size(), d.rsumm.n_regions));
         }
         if (cfg.indels) download_rows(e, bk_sample_download_indels, "bk_sample_download_indels", d.isumm, d.isumm.reported, d.indels);
+        if (a.consensus_indels)
+            download_rows(e, bk_sample_download_consensus_indels, "bk_sample_download_consensus_indels", d.cisumm, d.cisumm.accepted, d.cons_indels);
         if (cfg.junctions) download_rows(e, bk_sample_download_junctions, "bk_sample_download_junctions", d.jsumm, d.jsumm.reported, d.junctions);
         if (cfg.copybacks) download_rows(e, bk_sample_download_copybacks, "bk_sample_download_copybacks", d.cbsumm, d.cbsumm.reported, d.copybacks);
         if (cfg.chimeras) download_rows(e, bk_sample_download_chimeras, "bk_sample_download_chimeras", d.chsumm, d.chsumm.reported, d.chimeras);
@@ -738,7 +744,16 @@ struct CallRun {
                 LOG_INFO(T, "Consensus of " + std::to_string(c.positions) + " positions: " + std::to_string(c.called) + " called (" +
                                 std::to_string(c.substitutions) + " substitutions), " + std::to_string(c.ambiguous) + " ambiguous, " +
                                 std::to_string(c.masked) + " masked");
-                write_consensus_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, d.letters.data(), c.positions);
+                if (!a.consensus_indels) write_consensus_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, d.letters.data(), c.positions);
+            }
+            if (a.consensus_indels) {   // (the letters came with '-' at the applied deletions; a sample without accepted events: the header lines alone)
+                const bk_consensus_indel_summary& s = d.cisumm;
+                LOG_INFO(T, "Consensus indels: " + std::to_string(s.accepted) + " of " + std::to_string(s.candidates) + " candidate events accepted, " +
+                                std::to_string(s.applied) + " applied (" + std::to_string(s.deletions) + " deletions of " + std::to_string(s.deleted_bases) + " bases, " +
+                                std::to_string(s.insertions) + " insertions of " + std::to_string(s.inserted_bases) + " bases, " + std::to_string(s.frameshifts) +
+                                " frameshifts), " + std::to_string(s.contested) + " contested");
+                write_consensus_indels_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, d.letters.data(), d.csumm.positions, d.cons_indels);
+                write_consensus_indels_tsv(a.output + "/" + stem + ".consensus_indels.tsv", ix, best, d.cons_indels, cfg.consensus.min_depth, cfg.consensus.min_freq);
             }
             if (cfg.region_report()) {   // (a genome without a region: the two header lines)
                 LOG_INFO(T, "Depth of " + std::to_string(d.rsumm.n_regions) + " regions at minimum depth " + std::to_string(cfg.region_min_depth) + ": " +

@@ -73,7 +73,7 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--alignment] [--keep-kmer-info] [--min-base-qual Q] [--primers FASTA] [--primer-mismatches M]\n"
           "            [--adapter SEQ...] [--adapter-min-overlap N] [--adapter-error-rate F] [--consensus] [--consensus-min-depth D]\n"
           "            [--consensus-min-freq F] [--regions BED | --region-window W] [--region-min-depth D] [--indels]\n"
-          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--junctions]\n"
+          "            [--indel-max-len L] [--indel-max-mismatches M] [--indel-min-reads N] [--indel-min-af F] [--consensus-indels] [--junctions]\n"
           "            [--junction-min-len L] [--junction-max-mismatches M] [--junction-min-reads N] [--copybacks]\n"
           "            [--copyback-max-mismatches M] [--copyback-min-reads N] [--copyback-min-dist D] [--chimeras]\n"
           "            [--chimera-max-mismatches M] [--chimera-min-reads N] [--breakends] [--breakend-min-clip C]\n"
@@ -97,7 +97,7 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --adapter-error-rate F   mismatches allowed per compared base (floor(F * length), no indels); 0..0.3, default 0.1\n"
           "  --consensus       write the sample's consensus of the selected genome to <DIR>/<stem>.consensus.fa: per position the most\n"
           "                    frequent bases that together reach F of the depth (more than one: an IUPAC code), N below depth D; no\n"
-          "                    filters, no indels, the reference's length\n"
+          "                    filters, the reference's length; no indels unless --consensus-indels applies the sample's\n"
           "  --consensus-min-depth D  depth below which a position is N; at least 1, default 10\n"
           "  --consensus-min-freq F   share of a position's depth its letter's bases reach together; 0..1, default 0.5\n"
           "  --regions BED     write the depth of every region of the selected genome to <DIR>/<stem>.regions.tsv: length, mean, min,\n"
@@ -112,6 +112,10 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "  --indel-max-mismatches M substitutions a read may have beside its indel; 0..8, default 2\n"
           "  --indel-min-reads N      supporting reads an event needs to be written; at least 1, default 5\n"
           "  --indel-min-af F         AF an event needs to be written; 0..1, default the value of --min-af\n"
+          "  --consensus-indels  apply the sample's indels to its consensus (needs --consensus and --indels): an event whose reads s and\n"
+          "                    reference-spanning reads r give s + r >= D and s >= F (s + r) is accepted, and applied unless a stronger or\n"
+          "                    equal accepted event touches it; <DIR>/<stem>.consensus.fa then leaves the deleted letters out and holds the\n"
+          "                    inserted ones, <DIR>/<stem>.consensus_indels.tsv lists every accepted event\n"
           "  --junctions       write long deletions and subgenomic-RNA junctions to <DIR>/<stem>.junctions.tsv (an index of one genome\n"
           "                    file): reads whose two ends lie on diagonals of the reference L or more apart, forward on one strand of\n"
           "                    one sequence, left-normalised, with the reads that support each, the reads that span its donor and\n"
@@ -301,6 +305,7 @@ Args parse_args(int argc, char** argv) {
             else { a.region_min_depth = x; a.has_region_min_depth = true; }
         }
         else if (opt == "--indels") a.indels = true;
+        else if (opt == "--consensus-indels") a.consensus_indels = true;
         else if (opt == "--indel-max-len" || opt == "--indel-max-mismatches" || opt == "--indel-min-reads") {   // (any integer here: check_call_args)
             const long x = any_long(opt, one());
             if (opt == "--indel-max-len") { a.indel_max_len = x; a.has_indel_max_len = true; }
@@ -558,6 +563,8 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (a.indel_max_len < 1 || a.indel_max_len > BK_INDEL_MAX_LEN) die(T, "--indel-max-len must be between 1 and " + std::to_string(BK_INDEL_MAX_LEN) + ", got " + std::to_string(a.indel_max_len));
     if (a.indel_max_mismatches < 0 || a.indel_max_mismatches > 8) die(T, "--indel-max-mismatches must be between 0 and 8, got " + std::to_string(a.indel_max_mismatches));
     if (a.indel_min_reads < 1) die(T, "--indel-min-reads must be at least 1, got " + std::to_string(a.indel_min_reads));
+    if (a.consensus_indels && !a.consensus) die(T, "--consensus-indels needs --consensus");
+    if (a.consensus_indels && !a.indels) die(T, "--consensus-indels needs --indels");
     if (a.has_junction_min_len && !a.junctions) die(T, "--junction-min-len needs --junctions");
     if (a.has_junction_max_mismatches && !a.junctions) die(T, "--junction-max-mismatches needs --junctions");
     if (a.has_junction_min_reads && !a.junctions) die(T, "--junction-min-reads needs --junctions");

@@ -15,6 +15,7 @@
 #include "copybacks.hpp"
 #include "duplications.hpp"
 #include "haplotypes.hpp"
+#include "consensus_indels.hpp"
 #include "indels.hpp"
 #include "junctions.hpp"
 #include "linkage.hpp"
@@ -75,6 +76,7 @@ struct Args {
     long indel_max_mismatches = 2;  // --indel-max-mismatches: substitutions a record may have beside its indel (0..8)
     long indel_min_reads = 5;       // --indel-min-reads: supporting records an event needs
     double indel_min_af = 0.03;     // --indel-min-af: support / (support + reference-spanning records) an event needs (default: --min-af)
+    bool consensus_indels = false;  // --consensus-indels: the sample's indels in <DIR>/<stem>.consensus.fa, <DIR>/<stem>.consensus_indels.tsv (needs --consensus and --indels)
     bool junctions = false;         // --junctions: <DIR>/<stem>.junctions.tsv, long deletions and subgenomic-RNA junctions from the reads
     bool has_junction_min_len = false, has_junction_max_mismatches = false, has_junction_min_reads = false;
     long junction_min_len = 33;     // --junction-min-len: shortest jump counted as a junction (with 33 it begins where --indels ends)

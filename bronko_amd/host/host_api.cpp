@@ -15,6 +15,7 @@
 #include "copybacks.hpp"
 #include "duplications.hpp"
 #include "haplotypes.hpp"
+#include "consensus_indels.hpp"
 #include "indels.hpp"
 #include "junctions.hpp"
 #include "linkage.hpp"
@@ -298,6 +299,47 @@ int bh_write_indels_vcf(const void* h, int file_id, const char* path, const char
         p.max_len = max_len; p.max_mismatches = max_mismatches; p.min_reads = min_reads; p.min_af_ppm = min_af_ppm;
         bronko::write_indels_vcf(path, reads_path ? reads_path : "", *static_cast<const bronko::Index*>(h), file_id,
                                  std::vector<bronko::IndelEvent>(ev, ev + n), p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --consensus-indels: the host twin of bk_sample_consensus_indels (consensus_indels.cpp) --------------------------
+// events as bk_indel_record (n of them: the whole table), span[total_cells] prefix-summed, letters[n_letters] of the genome file:
+// '-' is stored at the applied deletions; rows as bk_consensus_indel_record (= bronko::ConsensusIndel), sorted, at most cap
+// written, *n_rows their number; tallies = {candidates, accepted, applied, contested, deletions, insertions, deleted_bases,
+// inserted_bases, frameshifts}
+int bh_consensus_indels(const void* h, int file_id, const void* events, uint64_t n, const uint32_t* span, uint64_t min_depth, double min_freq, uint8_t* letters,
+                        uint64_t n_letters, uint64_t cap, void* rows, uint64_t* n_rows, uint64_t* tallies) {
+    try {
+        static_assert(sizeof(bronko::ConsensusIndel) == 32, "ConsensusIndel is bk_consensus_indel_record");
+        const auto* ix = static_cast<const bronko::Index*>(h);
+        const auto* ev = static_cast<const bronko::IndelEvent*>(events);
+        const bronko::ConsensusIndels r = bronko::consensus_indels(*ix, file_id, std::vector<bronko::IndelEvent>(ev, ev + n),
+                                                                   std::vector<uint32_t>(span, span + ix->total_cells()), min_depth, min_freq, letters, n_letters);
+        *n_rows = r.events.size();
+        if (rows) std::memcpy(rows, r.events.data(), (size_t)std::min<uint64_t>(cap, r.events.size()) * sizeof(bronko::ConsensusIndel));
+        if (tallies) {
+            const uint64_t t[9] = {r.n.candidates, r.n.accepted, r.n.applied, r.n.contested, r.n.deletions, r.n.insertions, r.n.deleted_bases, r.n.inserted_bases,
+                                   r.n.frameshifts};
+            std::memcpy(tallies, t, sizeof t);
+        }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_consensus_indels_fasta(const void* h, int file_id, const char* path, const char* stem, const uint8_t* letters, uint64_t n, const void* rows,
+                                    uint64_t n_rows) {
+    try {
+        const auto* ev = static_cast<const bronko::ConsensusIndel*>(rows);
+        bronko::write_consensus_indels_fasta(path, stem, *static_cast<const bronko::Index*>(h), file_id, letters, n, std::vector<bronko::ConsensusIndel>(ev, ev + n_rows));
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+int bh_write_consensus_indels_tsv(const void* h, int file_id, const char* path, const void* rows, uint64_t n_rows, uint64_t min_depth, double min_freq) {
+    try {
+        const auto* ev = static_cast<const bronko::ConsensusIndel*>(rows);
+        bronko::write_consensus_indels_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::ConsensusIndel>(ev, ev + n_rows), min_depth, min_freq);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -374,6 +374,66 @@ def write_indels_vcf(path, ix, file_id, reads_path, rows, max_len=32, max_mismat
         raise _host_error(L)
 
 
+# bk_consensus_indel_record (include/bronko_hip.h) == bronko::ConsensusIndel (consensus_indels.hpp)
+CONSENSUS_INDEL_DTYPE = np.dtype([("cell", np.uint32), ("len", np.int32), ("support", np.uint32), ("ref_span", np.uint32), ("seq", np.uint64),
+                                  ("applied", np.uint32), ("pad", np.uint32)])
+CONSENSUS_INDEL_TALLIES = ("candidates", "accepted", "applied", "contested", "deletions", "insertions", "deleted_bases", "inserted_bases", "frameshifts")
+
+
+def _consensus_indel_lib():
+    return _bound("_consensus_indels_ready", {
+        "bh_consensus_indels": [_VP, C.c_int, _VP, _U64, _VP, _U64, C.c_double, _VP, _U64, _U64, _VP, C.POINTER(_U64), _VP],
+        "bh_write_consensus_indels_fasta": [_VP, C.c_int, C.c_char_p, C.c_char_p, _VP, _U64, _VP, _U64],
+        "bh_write_consensus_indels_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U64, C.c_double]})
+
+
+def _consensus_indel_records(rows):
+    """[(cell, len, support, ref_span, seq, applied)] as the array of bk_consensus_indel_record a bh_* takes (one zero record for none)"""
+    rec = np.zeros(max(1, len(rows)), CONSENSUS_INDEL_DTYPE)
+    for i, r in enumerate(rows):
+        rec[i] = (r[0], r[1], r[2], r[3], r[4], r[5], 0)
+    return rec
+
+
+def consensus_indels(ix, file_id, events, span, letters, min_depth=10, min_freq=0.5):
+    """The host twin of bk_sample_consensus_indels (consensus_indels.cpp): `events` as indel_rows gives the whole table, `span` the
+    prefix-summed span array of all cells, `letters` the genome file's consensus letters.  Returns (the accepted events as
+    [(cell, len, support, ref_span, seq, applied)] sorted by (cell, kind, length, seq), the tallies by name, the letters with '-' at
+    the applied deletions)."""
+    ev = np.zeros(max(1, len(events)), INDEL_DTYPE)
+    for i, r in enumerate(events):
+        ev[i] = (r[0], r[1], r[2], r[3], r[4], 0, r[5])
+    sp = np.ascontiguousarray(span, np.uint32)
+    assert len(sp) >= ix.total_cells
+    out = np.frombuffer(bytes(letters), np.uint8).copy()
+    rec = np.zeros(max(1, len(events)), CONSENSUS_INDEL_DTYPE)
+    n, tallies = C.c_uint64(), np.zeros(len(CONSENSUS_INDEL_TALLIES), np.uint64)
+    L = _consensus_indel_lib()
+    if L.bh_consensus_indels(ix.h, file_id, ev.ctypes.data, len(events), sp.ctypes.data, int(min_depth), float(min_freq), out.ctypes.data if len(out) else None,
+                             len(out), len(rec), rec.ctypes.data, C.byref(n), tallies.ctypes.data) != 0:
+        raise _host_error(L)
+    rows = [(int(r["cell"]), int(r["len"]), int(r["support"]), int(r["ref_span"]), int(r["seq"]), int(r["applied"])) for r in rec[:n.value]]
+    return rows, dict(zip(CONSENSUS_INDEL_TALLIES, (int(t) for t in tallies))), out.tobytes()
+
+
+def write_consensus_indels_fasta(path, stem, ix, file_id, letters, rows):
+    """The --consensus-indels FASTA writer (consensus_indels.cpp write_consensus_indels_fasta): the letters with '-' at the applied
+    deletions, rows as consensus_indels gives them."""
+    buf = np.frombuffer(bytes(letters), np.uint8)
+    rec = _consensus_indel_records(rows)
+    L = _consensus_indel_lib()
+    if L.bh_write_consensus_indels_fasta(ix.h, file_id, path.encode(), stem.encode(), buf.ctypes.data if len(buf) else None, len(buf), rec.ctypes.data, len(rows)) != 0:
+        raise _host_error(L)
+
+
+def write_consensus_indels_tsv(path, ix, file_id, rows, min_depth=10, min_freq=0.5):
+    """The --consensus-indels table writer (consensus_indels.cpp write_consensus_indels_tsv)."""
+    rec = _consensus_indel_records(rows)
+    L = _consensus_indel_lib()
+    if L.bh_write_consensus_indels_tsv(ix.h, file_id, path.encode(), rec.ctypes.data, len(rows), int(min_depth), float(min_freq)) != 0:
+        raise _host_error(L)
+
+
 def _junction_lib():
     return _bound("_junctions_ready", {"bh_junction_events": [_VP, C.c_int, C.c_char_p, _U32, C.c_int] + _EVENTS_TAIL,
                                        "bh_write_junctions_tsv": [_VP, C.c_int, C.c_char_p, _VP, _U64, _U32, _U32, _U64]})

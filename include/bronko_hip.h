@@ -383,8 +383,9 @@ int  bk_sample_download_noise(bk_engine* e, double* out, uint64_t cap, uint64_t*
  *                                     T = 8) indexes "-ACMGRSVTWYHKDBN".
  * A set of one base is called, a larger one ambiguous (all four print as N); a called base that differs from the reference code
  * of the cell (a non-ACGT reference letter counts as A, as in call_variants) is a substitution.  Integer arithmetic but for the
- * one product.  No end, strand or noise filter (the consensus is the pileup's majority, independent of the records), no indels:
- * the letters have the reference's length, in (sequence, position) order.
+ * one product.  No end, strand or noise filter (the consensus is the pileup's majority, independent of the records), no indels here
+ * (bk_sample_consensus_indels applies the sample's to these letters): the letters have the reference's length, in (sequence,
+ * position) order.
  * min_depth >= 1 and 0 <= min_freq <= 1 (BK_ERR_INVALID otherwise, the parameter named).
  *   bk_sample_consensus            after the sample's bk_sample_call (BK_ERR_STATE before it, inside a sample, and after a later
  *                                  bk_sample_begin); asynchronous on the engine's stream.  Its buffers -- a byte per cell of the
@@ -499,6 +500,49 @@ int  bk_indels_enable(bk_engine* e, const bk_indel_config* cfg);
 int  bk_sample_indels(bk_engine* e, const bk_indel_params* p);
 int  bk_sample_download_indels(bk_engine* e, bk_indel_summary* summary, bk_indel_record* records, uint64_t cap);
 int  bk_sample_download_indel_span(bk_engine* e, uint32_t* span, uint64_t cap);
+
+/* ---- the sample's indels applied to its consensus (`bronko call --consensus-indels`; additive, still v8) ---------------------
+ * bk_sample_consensus writes one letter per reference position and bk_sample_indels finds the sample's insertions and deletions;
+ * this step joins the two where both lie: it selects the events that reach the consensus thresholds, resolves those that
+ * collide, marks the deleted letters and hands the few accepted events to the host, whose writer drops the deleted letters and
+ * splices in the inserted ones.  The rule, all of it integer arithmetic but for one product:
+ *   inputs     the sample's consensus letters with D = min_depth and F = min_freq of its last bk_sample_consensus; the sample's
+ *              whole indel event table -- every candidate, whatever bk_sample_indels' min_reads and min_af_ppm select --; the
+ *              prefix-summed span array bk_sample_indels made.
+ *   per event  (cell c; a deletion of len, or an insertion of len with sequence S, exactly as bk_indel_record gives them)
+ *              s = fwd + rev, r = span[c], n = s + r, in u64.
+ *   accepted   iff n >= D and (double)s >= F * (double)n: the compare the consensus makes for a base.
+ *   boundaries boundary b lies in front of cell b.  A deletion occupies the boundaries c .. c + len inclusive, an insertion the
+ *              boundary c.  So two adjacent deletions collide, an insertion at either edge of a deletion collides with it, and
+ *              two insertions at one cell collide.
+ *   applied    iff on every boundary it occupies its s is strictly greater than the s of every other accepted event on that
+ *              boundary.  An accepted event that is not applied is `contested`.  Equal support on a shared boundary contests both;
+ *              there is one round only: an event that loses to a neighbour stays contested even when that neighbour lost too.
+ *              Nothing depends on slot order, table size or launch order.
+ *   effect     the letter of every cell [c, c + len) of an applied deletion becomes '-' (applied deletions share no boundary);
+ *              an applied insertion puts S, upper-case ACGT along the reference, in front of cell c.
+ *   tallies    candidates: the table's events; accepted = applied + contested; deletions, insertions: the applied events by
+ *              kind; deleted_bases, inserted_bases: their lengths summed; frameshifts: applied events with len % 3 != 0.
+ *   cap        at most BK_CONSENSUS_INDEL_MAX accepted events travel.  More: overflow = 1 in the summary and the download fails
+ *              with BK_ERR_INVALID, as a full event table does (and a full event table fails this download too).
+ *   bk_sample_consensus_indels           after this sample's bk_sample_consensus and bk_sample_indels: BK_ERR_STATE inside a
+ *                                        sample, before either call, and when indels were not enabled as the sample began, each
+ *                                        with its own message.  Asynchronous on the engine's stream.  Its buffers -- two words per
+ *                                        boundary, BK_CONSENSUS_INDEL_MAX rows, the summary -- are allocated at the engine's first
+ *                                        call and zeroed on the stream at every call: an engine that never asks allocates and
+ *                                        launches nothing.  Per engine: forks own theirs.  A later bk_sample_consensus writes fresh
+ *                                        letters and makes the step due again, so it may be repeated with other parameters.
+ *                                        After it bk_sample_download_consensus returns the letters with '-' at the applied
+ *                                        deletions; bk_consensus_summary's five tallies stay those of the unedited letters.
+ *   bk_sample_download_consensus_indels  synchronises; copies min(cap, accepted) rows in no particular order (rows may be NULL).
+ *                                        No genome selected: file_id = -1, every tally 0, no rows.
+ * bk_consensus_indel_record: cell, len and seq as in bk_indel_record; support = s, ref_span = r; applied = 1 or 0 (contested). */
+#define BK_CONSENSUS_INDEL_MAX 65536
+typedef struct { uint32_t cell; int32_t len; uint32_t support, ref_span; uint64_t seq; uint32_t applied, pad; } bk_consensus_indel_record;
+typedef struct { uint64_t candidates, accepted, applied, contested, deletions, insertions, deleted_bases, inserted_bases, frameshifts;
+                 int32_t file_id, overflow; } bk_consensus_indel_summary;
+int  bk_sample_consensus_indels(bk_engine* e);
+int  bk_sample_download_consensus_indels(bk_engine* e, bk_consensus_indel_summary* s, bk_consensus_indel_record* rows, uint64_t cap);
 
 /* ---- long deletions and subgenomic-RNA junctions from the reads (`bronko call --junctions`; additive, still v8) ---------------
  * A read whose two ends lie on diagonals more than BK_INDEL_MAX_LEN apart is `discordant` to bk_indels_enable and dropped there.
