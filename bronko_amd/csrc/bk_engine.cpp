@@ -75,7 +75,6 @@ static int alloc_sample_state(bk_engine* e) {
         BK_HIP(e->deferred_n.alloc(e->deferred.n));
         for (MatePlane& p : e->mate) BK_HIP(hipMemset(p.counters.p, 0, std::max<size_t>(p.counters.n, 1) * sizeof(unsigned long long)));
     }
-    if (ix.n_files == 1 && !e->sparse && ix.n_full > 0) { BK_HIP(e->lean_e_list.alloc((size_t)ix.n_full)); BK_HIP(e->lean_n_list.alloc(8)); BK_HIP(hipMemset(e->lean_n_list.p, 0, 8 * sizeof(unsigned int))); }
     BK_HIP(e->pileup.alloc(ix.total_cells * 4 * 4));
     e->gather_mode = ix.gather_ok && e->sparse && ix.cell_file.p && ix.dirty_ans.p && ix.W > 1 && ix.file_cell_lo_d.p && !test_env("BK_NO_GATHER");
     if (e->gather_mode) {
@@ -126,7 +125,7 @@ static int alloc_sample_state(bk_engine* e) {
     // planes, no statistics table, no pseudo k-mers, an answer table; FinalizeArgs are checked again at finalize), a V bin is the 64
     // row positions of one of its workgroups, and Level 2 is the only other writer of the V part (ScanArgs::n_direct: no nbatch_kernel)
     e->fuse_ok = e->use_items && ix.n_files == 1 && ix.max_seqs_per_file == 1 && (uint64_t)ix.n_lds_bins >= ix.total_cells && !e->ktab.keys.p && ix.n_prows == 0 &&
-                 ix.n_u == ix.n_full && ix.n_full > 0 && ix.dirty_ans.p && ix.W > 1 && ix.v_span > 0 && ix.v_span <= 32 && e->fin_partials.p && e->lean_e_list.p &&
+                 ix.n_u == ix.n_full && ix.n_full > 0 && ix.dirty_ans.p && ix.W > 1 && ix.v_span > 0 && ix.v_span <= 32 && e->fin_partials.p &&
                  prm->cs < (1ull << 32) && e->ig.vq_log2 == 6 && !test_env("BK_NO_LEAN_FINALIZE") && !test_env("BK_NO_FUSE") && !test_env("BK_NO_N_DIRECT");
     if (e->fuse_ok)
         for (MatePlane& p : e->mate) { BK_HIP(p.fuse_touch.alloc(((size_t)ix.n_full + (size_t)ix.v_span + 63) / 64 * 12 + 16)); BK_HIP(hipMemset(p.fuse_touch.p, 0, p.fuse_touch.n * sizeof(unsigned int))); }
@@ -404,7 +403,7 @@ static int l2_stats_report(bk_engine* e) {
         if (test_env("BK_L2_STATS")[0] == '2')
             for (int b = 0; b < n_wg; b++) fprintf(stderr, "[bk]   wg %d: %.1f %.1f %.1f %.1f\n", b, (clk[4 * b] - t0) * 0.01, (clk[4 * b + 1] - t0) * 0.01, (clk[4 * b + 2] - t0) * 0.01, (clk[4 * b + 3] - t0) * 0.01);
     }
-    fprintf(stderr, "[bk] finalize: %u + %u k-mers deferred to the general kernel\n", nd[0], nd[1]);
+    fprintf(stderr, "[bk] finalize: %u + %u k-mers deferred (items the regional finalize settles in place, or the general kernel's list)\n", nd[0], nd[1]);
     if (e->gather_mode) {
         unsigned int ah[2] = {0u, 0u};
         BK_HIP(hipMemcpy(ah, e->n_alias_hits.p, sizeof ah, hipMemcpyDeviceToHost));
@@ -671,7 +670,8 @@ static bk::FinalizeArgs finalize_args(const bk_engine* e, const FinalizeCall& c,
     // the reduce kernel of the mate file's last statistics pass (it runs behind K2e, the E part's only reader in that pass;
     // a second, votes-only pass reads it again: then clean_planes' memset does it)
     const bool ride = c.clean_dense && !c.two_pass && e->fin_partials.p && pl.used;
-    a.no_lean = test_env("BK_NO_LEAN_FINALIZE") != nullptr; a.lean_e_list = e->lean_e_list.p; a.lean_n_list = e->lean_n_list.p;
+    a.no_lean = test_env("BK_NO_LEAN_FINALIZE") != nullptr; a.lean_list_cap = bk::kLeanListCap;
+    if (const char* lc = test_env("BK_LEAN_LIST_CAP")) a.lean_list_cap = (uint32_t)std::max(1, std::min((int)bk::kLeanListCap, atoi(lc)));   // testing aid: a list that a small reference fills
     a.zero_e = ride ? pl.counters.p : nullptr; a.zero_e_n = ride ? (size_t)std::min<uint64_t>(ix.v_off, ix.plane_len) : 0;
     return a;
 }

@@ -517,7 +517,6 @@ struct bk_engine {
     DevBuf<unsigned int> ov;
     DevBuf<unsigned long long> ov_n;
     uint32_t ov_par = 0;                    // parity of the next scan_items launch (which of the two overflow counts it appends to)
-    DevBuf<unsigned int> lean_e_list, lean_n_list;   // bk_finalize_lean.hip: the reference k-mers finalize_ecell_kernel leaves to finalize_exact_kernel
     bool fuse_ok = false;                   // the index, planes and parameters admit the fuse (MatePlane; alloc_sample_state)
     struct PendingItems { bool on = false; int mate = 0; bk::BinArgs b{}; } pending;
     DevBuf<unsigned int> n_bits, n_any;     // scan -> Level 2: one bit per k-mer of each record of a launch / per record (bk_kernels.h ScanArgs): the N runs; all zero between launches

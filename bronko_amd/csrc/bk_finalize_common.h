@@ -8,6 +8,19 @@
 
 namespace bk {
 
+// The window bucket (slot) of a masked k-mer in one window sub-table, or -1.
+__device__ __forceinline__ int probe_table(const TableSlot* __restrict__ sub, uint32_t log2s, uint64_t key) {
+    const uint32_t smask = (1u << log2s) - 1u;
+    uint32_t h = hash_key(key, log2s);
+    for (;;) {
+        const uint4 e = *reinterpret_cast<const uint4*>(sub + h);  // one dwordx4 load per probe
+        const uint64_t kk = (uint64_t)e.x | ((uint64_t)e.y << 32);
+        if (kk == key) return (int)e.z;
+        if (kk == kEmptyKey) return -1;
+        h = (h + 1) & smask;
+    }
+}
+
 // The vote of call.rs:1327-1384 for one BucketInfo.
 __device__ __forceinline__ void vote(const FinalizeArgs& a, const DevEntry& e, uint64_t c, uint32_t isrc, int k, unsigned long long v) {
     if (a.mode == 1 || (a.mode == 2 && (int)e.file != a.sel_file)) return;   // statistics pass / votes for the selected genome only

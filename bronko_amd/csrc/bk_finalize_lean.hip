@@ -8,11 +8,13 @@
 // bytes and not instructions.  Here a pileup cell receives one pair of global atomics per workgroup that reaches it (~1.5 per
 // cell) and a workgroup synchronises twice in all.
 //
-// What these kernels do not settle themselves goes where the general path takes it: a V k-mer whose reference neighbour is not
-// "simple" (repeats) or whose answer was not worked out, or that touches several buckets, is appended to the deferred list of
-// finalize_general_kernel (K2b), exactly as K2a defers its multi-bucket k-mers; a reference k-mer that is not simple walks its
-// buckets' BucketInfos here, vote by vote.  launch_finalize (bk_kernels.hip) decides: one genome file, statistics and votes in
-// one pass over whole dense planes, no k-mer statistics table, no pseudo k-mers, an answer table, W > 1, cs < 2^32.
+// What is not "one BucketInfo, known from the record" -- a V k-mer whose reference neighbour is not "simple" (repeats) or whose
+// answer was not worked out, or that touches several buckets; a reference k-mer that is not simple -- is an ITEM: the lane that
+// finds it puts it on the workgroup's own list in LDS, and behind the row loop and the K2e part the workgroup's waves take the
+// list's items in turn, one wave per item, and walk the item's buckets (lean_settle: finalize_general_kernel's walk for one
+// genome file).  A few dozen items per sample; nothing is handed to another workgroup or another launch.  launch_finalize
+// (bk_kernels.hip) decides: one genome file, statistics and votes in one pass over whole dense planes, no k-mer statistics
+// table, no pseudo k-mers, an answer table, W > 1, cs < 2^32.
 #include <hip/hip_runtime.h>
 
 #include "bk_device.h"
@@ -27,14 +29,24 @@ constexpr uint32_t kLeanVq = 64;       // row positions q of the V plane per wor
 constexpr uint32_t kLeanWin = 256;     // pileup positions of its vote table: 64 + v_span reference k-mers' cells and k - 1 behind, with slack
 constexpr uint32_t kLeanMaxSpan = 32;  // v_span at most (finalize_lean_ok): at least two rows per wave
 constexpr uint32_t kLeanTouchWords = kLeanVq * kVRowsPerPos / 32;
-// LDS of one workgroup, static (the vote table, the tallies, the touch words; the compiler may pad a little) and dynamic: two
+// LDS of one workgroup, static (the vote table, the tallies, the touch words, the item list; the compiler may pad a little) and dynamic: two
 // workgroups must fit a CU's 160 KB -- finalize_vbin_kernel is built for eight waves per SIMD, which is two of its workgroups
-constexpr size_t kLeanStaticLds = (2u * 8u * kLeanWin + 5u + kLeanTouchWords + 1u) * sizeof(unsigned int);
+constexpr size_t kLeanStaticLds = (2u * 8u * kLeanWin + 6u + kLeanTouchWords + 1u + 4u * kLeanListCap) * sizeof(unsigned int);
 constexpr size_t lean_dynamic_lds(uint32_t v_span) { return (size_t)kLeanVq * kVRowsPerPos * ((size_t)v_span + 1u) * sizeof(unsigned int); }
 static_assert(kLeanStaticLds + 64u + lean_dynamic_lds(kLeanMaxSpan) <= 80u * 1024u, "two finalize_vbin workgroups no longer fit one CU's LDS");
 
+typedef const __attribute__((address_space(4))) FinalizeArgs* LeanColdArgs;   // the kernel's arguments where they lie (the kernel-argument segment)
+// What only the items read (the window's tables, the entry lists, the list's own counters) is read from there where it is used, through a
+// pointer the compiler cannot see through, as the binned scan reads its rare paths' arguments: held in scalar registers through the row
+// loop it would cost the kernel its eight waves per SIMD.
+__device__ __forceinline__ LeanColdArgs lean_cold_args() {
+    LeanColdArgs p = (LeanColdArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
 // one vote into the dense table (or, out of its reach, straight to the pileup)
-__device__ __forceinline__ void lean_vote(unsigned int* cnt, unsigned int* mxv, uint32_t span, uint32_t p0, const FinalizeArgs& a, uint32_t cell,
+template <typename Args>
+__device__ __forceinline__ void lean_vote(unsigned int* cnt, unsigned int* mxv, uint32_t span, uint32_t p0, const Args& a, uint32_t cell,
                                           uint32_t idx, bool canonical, uint64_t c, uint32_t isrc, int k, uint32_t v) {
     uint32_t bit_idx;
     bool forward;
@@ -47,8 +59,8 @@ __device__ __forceinline__ void lean_vote(unsigned int* cnt, unsigned int* mxv, 
         __hip_atomic_fetch_max(mxv + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     } else {
         const size_t pc = (size_t)cell * 4 + bit_idx;
-        atomicAdd(a.pileup + (forward ? 2 : 3) * a.plane + pc, 1ull);
-        atomicMax(a.pileup + (forward ? 0 : 1) * a.plane + pc, (unsigned long long)v);
+        atomicAdd(a->pileup + (forward ? 2 : 3) * a->plane + pc, 1ull);
+        atomicMax(a->pileup + (forward ? 0 : 1) * a->plane + pc, (unsigned long long)v);
     }
 }
 // the table -> pileup: one pair of global atomics per cell that received a vote
@@ -60,6 +72,44 @@ __device__ __forceinline__ void lean_flush(const unsigned int* cnt, const unsign
         const size_t pc = ((size_t)p0 + pos) * 4 + (row & 3u);
         atomicAdd(a.pileup + (row < 4u ? 2 : 3) * a.plane + pc, (unsigned long long)nv);   // #kmers
         atomicMax(a.pileup + (row < 4u ? 0 : 1) * a.plane + pc, (unsigned long long)mxv[i]);   // depth
+    }
+}
+
+// One item -- k-mer c read in orientation isrc (meta bit 0), reported count v -- settled by one wave, all 64 lanes of it:
+// wave_item of finalize_general_kernel for ONE genome file.  Lane t < W finds the bucket at window position t (a V item probes
+// the window's sub-table; an E item, meta bit 1, is reference k-mer meta >> 2 and owns its buckets: slot_of); the buckets found
+// are walked one after the other, their BucketInfos spread over the lanes, a vote each.  With one file the per-genome hit table
+// of call.rs:1316-1318 is one number, the wave's sum: perfect iff it equals W, else a variant if there is any, and unique iff
+// perfect (call.rs:1390-1418).
+__device__ __forceinline__ void lean_settle(unsigned int* cnt, unsigned int* mxv, uint32_t* lstats, uint32_t p0, uint64_t c, uint32_t meta, uint32_t v) {
+    const LeanColdArgs a = lean_cold_args();
+    const auto& ix = a->ix;
+    const int k = ix.k;
+    const uint32_t lane = threadIdx.x & 63u, isrc = meta & 1u;
+    int s = -1;
+    if (lane < (uint32_t)ix.W) {
+        if (meta & 2u) {
+            s = (int)ix.slot_of[(size_t)(meta >> 2) * (uint32_t)ix.W + lane];
+        } else {
+            const int sh = 2 * (k - 1 - (ix.wstart + (int)lane));
+            s = probe_table(ix.table + ((size_t)lane << ix.log2s), ix.log2s, c & ~(3ull << sh));
+        }
+    }
+    unsigned int hits = 0;
+    for (unsigned long long bm = __ballot(s >= 0); bm; bm &= bm - 1ull) {
+        const int sb = __shfl(s, __builtin_ctzll(bm));
+        const uint32_t off = ix.ent_off[sb], len = ix.ent_len[sb];
+        for (uint32_t q = lane; q < len; q += 64u) {
+            const DevEntry e = ix.entries[off + q];
+            hits += 1u;
+            lean_vote(cnt, mxv, kLeanWin, p0, a, e.cell, e.idx, e.canonical != 0, c, isrc, k, v);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) hits += (unsigned int)__shfl_xor((int)hits, off);
+    if (lane == 0 && hits) {
+        if (hits == (unsigned int)ix.W) { atomicAdd(&lstats[0], 1u); atomicAdd(&lstats[2], 1u); }
+        else atomicAdd(&lstats[1], 1u);
     }
 }
 
@@ -78,7 +128,8 @@ __device__ __forceinline__ void lean_flush(const unsigned int* cnt, const unsign
 template <bool FUSED>
 __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void finalize_vbin_kernel(FinalizeArgs a) {
     __shared__ unsigned int cnt[8 * kLeanWin], mxv[8 * kLeanWin];
-    __shared__ uint32_t lstats[3 + 2];
+    __shared__ uint32_t lstats[3 + 2 + 1];                 // [5]: items put on the list (those that found it full included)
+    __shared__ uint4 wlist[kLeanListCap];                  // the workgroup's items: {k-mer, isrc | E item << 1 | id << 2, reported count}
     __shared__ unsigned int tmask[kLeanTouchWords + 1];   // FUSED: the touch bits of the workgroup's 384 rows; [12]: all rows (the scan's item_direct wrote to the plane)
     extern __shared__ __attribute__((aligned(16))) unsigned int acc[];   // FUSED: [384 * (v_span + 1)] the bin's counters (differences), from the items
     const IndexView& ix = a.ix;
@@ -90,7 +141,7 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
     const uint32_t id_lo = min(q0 >= span - 1u ? q0 - (span - 1u) : 0u, ix.n_full - 1u);
     const uint32_t p0 = ix.id_rec[id_lo].cell;
     for (uint32_t i = threadIdx.x; i < 8u * kLeanWin; i += kLeanVBlock) { cnt[i] = 0u; mxv[i] = 0u; }
-    if (threadIdx.x < 5) lstats[threadIdx.x] = 0u;
+    if (threadIdx.x < 6) lstats[threadIdx.x] = 0u;
     if constexpr (FUSED) {
         const uint32_t n_eb = a.f_ig.n_ebins, n_bins = n_eb + a.f_ig.n_vbins, bin = n_eb + blockIdx.x, cap = a.f_ig.cap_v, G = a.f_ig.grid_max;
         const uint32_t upb = cap / 8u;                                     // 16-byte units per bucket
@@ -162,6 +213,31 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
     const uint32_t grp = lane64 / lpr, oo = lane64 - grp * lpr;
     const bool lane_on = grp < gpw;
     unsigned int kept = 0, distinct = 0, variant = 0;
+#ifdef BK_TESTING
+    const uint32_t list_cap = lean_cold_args()->lean_list_cap;   // (BK_LEAN_LIST_CAP: a list that a test-sized reference fills)
+#else
+    constexpr uint32_t list_cap = kLeanListCap;
+#endif
+    // The lanes of a wave that have an item put them on the list together: one LDS atomic per wave and append (n_deferred only
+    // counts the sample's items: BK_L2_STATS).  Those that find the list full are settled by the wave on the spot, one after the
+    // other (the loop is wave-uniform): a full list loses nothing and nobody has to size it.
+    auto list_items = [&](bool has, uint64_t c, uint32_t meta, uint32_t v) __attribute__((always_inline)) {
+        const unsigned long long dm = __ballot(has);
+        if (!dm) return;
+        const int lead = __builtin_ctzll(dm);
+        unsigned int base = 0;
+        if (lane64 == (uint32_t)lead) {
+            base = __hip_atomic_fetch_add(&lstats[5], (unsigned int)__popcll(dm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            atomicAdd(lean_cold_args()->n_deferred, (unsigned int)__popcll(dm));
+        }
+        base = (unsigned int)__shfl((int)base, lead);
+        const unsigned int slot = base + (unsigned int)__popcll(dm & ((1ull << lane64) - 1ull));
+        if (has && slot < list_cap) wlist[slot] = make_uint4((uint32_t)c, (uint32_t)(c >> 32), meta, v);
+        for (unsigned long long om = __ballot(has && slot >= list_cap); om; om &= om - 1ull) {
+            const int l = __builtin_ctzll(om);
+            lean_settle(cnt, mxv, lstats, p0, __shfl(c, l), (uint32_t)__shfl((int)meta, l), (uint32_t)__shfl((int)v, l));
+        }
+    };
     for (uint32_t g0 = 0; g0 < kLeanVq * kVRowsPerPos; g0 += (kLeanVBlock / 64) * gpw) {   // (wave-uniform)
         const uint32_t g = g0 + wave * gpw + grp;                 // this lane's row among the workgroup's 384
         const uint32_t q = q0 + g / kVRowsPerPos, r6 = g % kVRowsPerPos;
@@ -217,7 +293,7 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
         if (act) { distinct += 1; if (n < a.ci || n > a.cx) act = false; else kept += 1; }   // kmc -ci / -cx act on the true count
         const uint32_t v = (uint32_t)(n > a.cs ? a.cs : n);      // kmc -cs: reported count saturates (cs < 2^32 here)
         // its one bucket is the reference k-mer's own at j unless another reference k-mer is near (dirty: the answer table knows
-        // whether it then touches a second bucket); everything that is not "one BucketInfo, known from the record" goes to K2b
+        // whether it then touches a second bucket); everything that is not "one BucketInfo, known from the record" is an item
         bool defer = false;
         if (act) {
             bool plain = (ambp & kIdSimple) != 0u;
@@ -227,22 +303,10 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
             }
             if (!plain) { defer = true; act = false; }
         }
-        {   // the wave's deferred k-mers are appended together: one returning atomic on the list's counter per wave
-            const unsigned long long dm = __ballot(defer);
-            if (dm) {
-                unsigned int base = 0;
-                if (lane64 == (uint32_t)__builtin_ctzll(dm)) base = atomicAdd(a.n_deferred, (unsigned int)__popcll(dm));
-                base = (unsigned int)__shfl((int)base, __builtin_ctzll(dm));
-                if (defer) {
-                    const unsigned int slot = base + (unsigned int)__popcll(dm & ((1ull << lane64) - 1ull));
-                    a.deferred[slot] = (uint32_t)at;
-                    if (a.deferred_n) a.deferred_n[slot] = n;
-                }
-            }
-        }
         // the vote: BucketInfo {cell = first cell + j, idx = j, canonical = rcid} (IdRec "simple"); one hit in the genome: "variant" (W > 1)
-        if (act) lean_vote(cnt, mxv, kLeanWin, p0, a, idr.z + (uint32_t)j, (uint32_t)j, rcid != 0u, c, isrc, k, v);
+        if (act) lean_vote(cnt, mxv, kLeanWin, p0, &a, idr.z + (uint32_t)j, (uint32_t)j, rcid != 0u, c, isrc, k, v);
         variant += act ? 1u : 0u;
+        list_items(defer, c, isrc, v);   // (last in the pass: nothing of the row lives across it; -ci / -cx are applied, the reported count is all that is left of n)
     }
 #pragma unroll
     for (int off = 32; off; off >>= 1) variant += (unsigned int)__shfl_xor((int)variant, off);
@@ -254,16 +318,20 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
         const uint32_t W = (uint32_t)ix.W;
         const uint32_t sub = threadIdx.x & 15u, id = q0 + (threadIdx.x >> 4);
         unsigned int perfect = 0;
+        unsigned long long n0 = 0ull, n1 = 0ull;
+        uint64_t km = 0ull;
+        bool listed = false;
         if (id < ix.n_full) {
             const uint4 idr = *reinterpret_cast<const uint4*>(ix.id_rec + id);
-            const unsigned long long n0 = a.counters[2 * (size_t)id], n1 = a.counters[2 * (size_t)id + 1];
+            n0 = a.counters[2 * (size_t)id]; n1 = a.counters[2 * (size_t)id + 1];
+            // (this workgroup is the only reader of the id's two counters: it leaves them zeroed behind the sample)
+            if (unsigned long long* const ze = lean_cold_args()->zero_e; ze && sub < 2u && (sub ? n1 : n0)) ze[2 * (size_t)id + sub] = 0ull;
+            km = (uint64_t)idr.x | ((uint64_t)idr.y << 32);
             if (!(idr.w & kIdSimple)) {
                 // Repeats: its buckets hold several BucketInfos each -- a walk of dependent loads that one thread would take a
-                // hundred microseconds over while the others wait.  Listed instead; finalize_exact_kernel maps the list (votes and
-                // statistics), a thread per (counter, bucket), as it maps the touched k-mers of a large index.
-                if (sub == 0u && (n0 | n1)) a.lean_e_list[atomicAdd(a.lean_n_list + 2, 1u)] = id;
+                // hundred microseconds over while the others wait.  Items instead, one per counter (below).
+                listed = sub == 0u && (n0 | n1) != 0ull;
             } else {
-                const uint64_t km = (uint64_t)idr.x | ((uint64_t)idr.y << 32);
                 const uint32_t rcid = (idr.w >> 1) & 1u;
 #pragma unroll
                 for (uint32_t isrc = 0; isrc < 2u; ++isrc) {
@@ -275,9 +343,18 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
                     // each of its W buckets holds its own single occurrence: {cell + j, idx = j, canonical = rcid}
                     for (uint32_t t = sub; t < W; t += 16u) {
                         const uint32_t j = (uint32_t)ix.wstart + t;
-                        lean_vote(cnt, mxv, kLeanWin, p0, a, idr.z + j, j, rcid != 0u, km, isrc, k, v);
+                        lean_vote(cnt, mxv, kLeanWin, p0, &a, idr.z + j, j, rcid != 0u, km, isrc, k, v);
                     }
                 }
+            }
+        }
+        if (__ballot(listed)) {   // (wave-uniform) the listed k-mers' counters that pass -ci / -cx: their statistics here, their votes as items
+#pragma unroll 1
+            for (uint32_t isrc = 0; isrc < 2u; ++isrc) {
+                const unsigned long long n = isrc ? n1 : n0;
+                bool item = listed && n != 0ull;
+                if (item) { distinct += 1; if (n < a.ci || n > a.cx) item = false; else kept += 1; }   // kmc -ci / -cx act on the true count
+                list_items(item, km, isrc | 2u | (id << 2), (uint32_t)(n > a.cs ? a.cs : n));             // kmc -cs: reported count saturates
             }
         }
 #pragma unroll
@@ -285,12 +362,20 @@ __global__ __launch_bounds__(kLeanVBlock) __attribute__((amdgpu_waves_per_eu(8, 
         if (lane64 == 0 && perfect) { atomicAdd(&lstats[0], perfect); atomicAdd(&lstats[2], perfect); }
     }
     __syncthreads();
+    // ---- the list: sixteen waves, an item each in turn (nobody appends any more: the count is the same for every wave)
+    if (const uint32_t n_list = min(lstats[5], list_cap)) {
+        for (uint32_t i = wave; i < n_list; i += kLeanVBlock / 64) {
+            const uint4 it = wlist[i];
+            lean_settle(cnt, mxv, lstats, p0, (uint64_t)it.x | ((uint64_t)it.y << 32), it.z, it.w);
+        }
+        __syncthreads();
+    }
     lean_flush(cnt, mxv, kLeanWin, p0, a);
     finalize_epilogue(a, lstats, kept, distinct, lstats + 3, (int)blockIdx.x);
 }
 
 bool finalize_lean_ok(const FinalizeArgs& a) {
-    return !a.no_lean && a.lean_e_list && a.lean_n_list && !a.ix.slot_files && a.mode == 0 && !a.v_list && !a.p_list && !a.e_list && !a.ktab_keys && a.ix.n_prows == 0 && a.ix.n_u == a.ix.n_full &&
+    return !a.no_lean && !a.ix.slot_files && a.mode == 0 && !a.v_list && !a.p_list && !a.e_list && !a.ktab_keys && a.ix.n_prows == 0 && a.ix.n_u == a.ix.n_full &&
            a.ix.n_full > 0 && a.ix.n_files == 1 && a.ix.dirty_ans && a.ix.W > 1 && a.ix.v_span > 0 && a.ix.v_span <= (int)kLeanMaxSpan && a.partials && a.cs < (1ull << 32) &&
            a.elem_lo == 0 && a.elem_hi >= a.ix.v_off + v_plane_len(a.ix.n_full, a.ix.v_span, 0);
 }

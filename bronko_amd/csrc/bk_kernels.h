@@ -40,6 +40,10 @@ struct ItemGeom {
 constexpr uint32_t kEBinLog2 = 7;   // E bins of 128 cells
 constexpr uint32_t kERunMax = 255;  // cells one E item covers at most
 constexpr uint32_t kEBinSpan = (1u << kEBinLog2) + kERunMax;   // cells an E bin's items reach from its first: 383 (the difference array has one more)
+// finalize_vbin_kernel's list of items in LDS (bk_finalize_lean.hip): 16-byte entries.  A region whose 64 reference k-mers are all repeats
+// lists 128 E items and as many V items as its reads' errors give it; a sample of the benchmark has 57-76 items over all 467 regions.  4 KB
+// of the 14 KB that two workgroups per CU leave at the longest rows; an item that finds it full is settled where it was found.
+constexpr uint32_t kLeanListCap = 256;
 constexpr uint32_t kItemGCap = 256;   // slots of a (scan workgroup, bin)'s extension in device memory (ScanArgs::gext): what its LDS bucket has no room for
 
 struct ScanArgs {
@@ -164,13 +168,10 @@ struct FinalizeArgs {
     int mode;
     const int* sel;
     int sel_file;                   // = *sel, read by each kernel of the second pass
-    unsigned int* lean_e_list;      // bk_finalize_lean.hip: [n_full] the reference k-mers finalize_ecell_kernel leaves to finalize_exact_kernel (repeats), and
-    unsigned int* lean_n_list;      //   [8] their number at [2] (the layout of n_list); null: no regional kernels
-    int no_lean;                    // testing aid (BK_NO_LEAN_FINALIZE): the general K2a / K2e even where the regional kernels of bk_finalize_lean.hip apply
-    const unsigned int* tail_e_list;   // set by launch_finalize for finalize_general_kernel: the regional finalize's lean_e_list / lean_n_list, whose
-    const unsigned int* tail_n_list;   //   k-mers' E counters it maps behind its deferred k-mers (null otherwise)
-    unsigned long long* zero_e;     // launch_finalize's last kernel also zeroes zero_e[0, zero_e_n): the plane's E part behind the sample (or null)
-    size_t zero_e_n;
+    int no_lean;                    // testing aid (BK_NO_LEAN_FINALIZE): the general K2a / K2e even where the regional kernel of bk_finalize_lean.hip applies
+    uint32_t lean_list_cap;         // testing aid (-DBK_TESTING build only, BK_LEAN_LIST_CAP): entries of finalize_vbin_kernel's item list, 1 ... kLeanListCap
+    unsigned long long* zero_e;     // the plane's E part behind the sample, zero_e[0, zero_e_n), is left zeroed (or null): by launch_finalize's last kernel,
+    size_t zero_e_n;                //   or, in the regional finalize, counter by counter by the workgroup that read it
     // The regional finalize fed from the scan's V items (a mate file whose reads were one launch: the V part of its plane is never
     // written).  A V bin of the binned scan is the 64 row positions one finalize_vbin workgroup owns: the workgroup adds the bin's
     // items up in LDS -- what bin_count_kernel does before it stores the bin -- and takes its counts from there.  What Level 2 added

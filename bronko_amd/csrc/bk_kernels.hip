@@ -35,18 +35,6 @@
 namespace bk {
 
 
-__device__ __forceinline__ int probe_table(const TableSlot* __restrict__ sub, uint32_t log2s, uint64_t key) {
-    const uint32_t smask = (1u << log2s) - 1u;
-    uint32_t h = hash_key(key, log2s);
-    for (;;) {
-        const uint4 e = *reinterpret_cast<const uint4*>(sub + h);  // one dwordx4 load per probe
-        const uint64_t kk = (uint64_t)e.x | ((uint64_t)e.y << 32);
-        if (kk == key) return (int)e.z;
-        if (kk == kEmptyKey) return -1;
-        h = (h + 1) & smask;
-    }
-}
-
 // If a and b differ in exactly one base, return its position counted from the left (0..k-1), else -1.
 __device__ __forceinline__ int single_diff_pos(uint64_t a, uint64_t b, int k) {
     const uint64_t x = a ^ b;
@@ -2201,10 +2189,9 @@ __device__ __forceinline__ void tally_files(const uint4& fb, uint32_t* lstats, u
 __global__ __launch_bounds__(256) void finalize_reduce_kernel(FinalizeArgs a, int n_rows, unsigned long long* zero_p, size_t zero_n) {
     __shared__ unsigned long long wave_sums[4];
     const int n3 = a.ix.n_files * 3, cols = n3 + 2;
-    // (the last kernel of a sample's last pass also zeroes the E part of the plane behind the sample: dense planes, see K2a's clear_v)
+    // (the last kernel of a sample's last pass also zeroes the E part of the plane behind the sample: dense planes, see K2a's clear_v;
+    // not behind the regional finalize, whose workgroups zero the E counters they read)
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < zero_n; i += (size_t)gridDim.x * 256) zero_p[i] = 0ull;
-    // (... and empties the regional finalize's list of reference k-mers that are not simple for the next pass: its readers are done)
-    if (a.lean_n_list && blockIdx.x == 0 && threadIdx.x < 8) a.lean_n_list[threadIdx.x] = 0u;
     const int col = blockIdx.x;   // one workgroup per column, rows strided over its threads
     unsigned long long s = 0;
     for (int r = threadIdx.x; r < n_rows; r += 256) s += a.partials[(size_t)r * cols + col];
@@ -3013,7 +3000,6 @@ __global__ __launch_bounds__(64) void finalize_general_kernel(FinalizeArgs a) {
 
     const int k = ix.k;
     const size_t S = (size_t)1 << ix.log2s;
-    const uint64_t n_e = e_plane_len(ix.n_u);
     const uint64_t n_items = *a.n_deferred;   // the E counters are mapped by K2e
 
     if (a.mode == 2) {
@@ -3049,41 +3035,19 @@ __global__ __launch_bounds__(64) void finalize_general_kernel(FinalizeArgs a) {
         }
         return;
     }
-    // (the regional finalize's list of reference k-mers that are not simple -- repeats: a few dozen -- rides with this kernel: two
-    // items per listed k-mer behind the deferred ones, its two E counters; a launch of finalize_exact_kernel for them was 14 us)
-    const uint64_t n_tail = (a.tail_e_list && a.mode == 0) ? 2ull * a.tail_n_list[2] : 0ull;
-    unsigned int tail_kept = 0, tail_distinct = 0;
     auto wave_item = [&](uint64_t item) {
         {
-            uint64_t ci, c;
+            uint64_t c;
             unsigned long long v;
             uint32_t isrc, p_, t_;
-            if (item < n_items) {
-                ci = n_e + a.deferred[item];                      // a V counter (n_e: the offset that tells it from an E counter below)
-                v_kmer_of_counter(ix, a.deferred_n ? nullptr : a.counters + ix.v_off, ci - n_e, p_, t_, c, isrc, v);
-                if (a.deferred_n) v = a.deferred_n[item];         // (K2a may have zeroed the row since)
-            } else {
-                const uint64_t e = item - n_items;
-                const uint32_t id = a.tail_e_list[e >> 1];
-                isrc = (uint32_t)e & 1u;
-                ci = 2ull * id + isrc;                            // an E counter: the reference k-mer itself, read in orientation isrc
-                v = a.counters[ci];
-                const uint4 idr = *reinterpret_cast<const uint4*>(ix.id_rec + id);
-                c = (uint64_t)idr.x | ((uint64_t)idr.y << 32);
-                if (lane == 0) tail_distinct += v != 0;
-                if (v == 0 || v < a.ci || v > a.cx) return;       // kmc -ci / -cx act on the true count (wave-uniform)
-                if (lane == 0) tail_kept += 1;
-            }
+            v_kmer_of_counter(ix, a.deferred_n ? nullptr : a.counters + ix.v_off, a.deferred[item], p_, t_, c, isrc, v);
+            if (a.deferred_n) v = a.deferred_n[item];             // (K2a may have zeroed the row since)
             v = v > a.cs ? a.cs : v;                              // kmc -cs: reported count saturates
 
             int s = -1;   // lane t: the k-mer's bucket at window position t, if the index has it
             if (lane < ix.W) {
-                if (ci < n_e) {
-                    s = (int)ix.slot_of[(size_t)(ci >> 1) * ix.W + lane];   // a reference k-mer owns all its buckets
-                } else {
-                    const int sh = 2 * (k - 1 - (ix.wstart + lane));
-                    s = probe_table(ix.table + (size_t)lane * S, ix.log2s, c & ~(3ull << sh));
-                }
+                const int sh = 2 * (k - 1 - (ix.wstart + lane));
+                s = probe_table(ix.table + (size_t)lane * S, ix.log2s, c & ~(3ull << sh));
             }
             // the buckets found, one after the other; the BucketInfos of a bucket (one per genome that has the k-mer: up to
             // hundreds) spread over the lanes
@@ -3163,11 +3127,11 @@ __global__ __launch_bounds__(64) void finalize_general_kernel(FinalizeArgs a) {
     } else
     // deferred items all passed the thresholds in K2a; one item per wave at a time, dealt round-robin so that a few
     // thousand items spread over the whole grid
-    for (uint64_t item = blockIdx.x; item < n_items + n_tail; item += gridDim.x) wave_item(item);
+    for (uint64_t item = blockIdx.x; item < n_items; item += gridDim.x) wave_item(item);
     __syncthreads();
     if (lane == 0) { ntouched[0] = 0; ntouched[1] = 0; }
     __syncthreads();
-    if (do_stats) finalize_epilogue(a, lstats, tail_kept, tail_distinct, ntouched, a.row_general + (int)blockIdx.x);
+    if (do_stats) finalize_epilogue(a, lstats, 0u, 0u, ntouched, a.row_general + (int)blockIdx.x);
 }
 
 // Sparse finalize: the set bits of a touch bitmap -> a list of indices (order is irrelevant); every word read is cleared, so the
@@ -3262,7 +3226,7 @@ static unsigned finalize_general_blocks(const FinalizeArgs& a) {
     return (unsigned)std::min<size_t>(a.ix.n_files >= 8 ? kFinGeneralBlocks : kFinGeneralBlocks / 32, 256 * std::max<size_t>(1, (160u * 1024u) / finalize_lds_bytes(a.ix.n_files)));
 }
 bool finalize_runs_by_region(const FinalizeArgs& a) {
-    return finalize_lean_ok(a) && (uint64_t)(a.ix.n_full + (uint32_t)a.ix.v_span) / 64 + (uint64_t)a.ix.total_cells / 256 + 2 + 64 + finalize_general_blocks(a) <= finalize_partial_rows();
+    return finalize_lean_ok(a) && (uint64_t)(a.ix.n_full + (uint32_t)a.ix.v_span) / 64 + 1 <= finalize_partial_rows();   // (a row of partials per workgroup)
 }
 void launch_finalize(const FinalizeArgs& a0, hipStream_t stream) {
     if (a0.ix.W <= 0) return;
@@ -3292,15 +3256,15 @@ void launch_finalize(const FinalizeArgs& a0, hipStream_t stream) {
         if (a.alias_hits) launch_alias_votes(a, stream);
         return;
     }
-    unsigned b_v = b_var, b_e = 0;
-    const bool lean = finalize_runs_by_region(a);
-    if (lean) {
-        // one genome file, dense planes: K2a and K2e by region of the reference (bk_finalize_lean.hip)
-        b_v = launch_finalize_lean_variant(a, stream);   // (V rows and the E counters of the same region)
-        // ... and the reference k-mers it listed (repeats: not "simple") go with K2b's deferred k-mers
-        a.tail_e_list = a.lean_e_list; a.tail_n_list = a.lean_n_list;
-        b_e = 0;
-    } else {
+    if (finalize_runs_by_region(a)) {
+        // one genome file, dense planes: K2a, K2e and K2b by region of the reference (bk_finalize_lean.hip) -- the V rows, the E counters
+        // of the same region, and what either finds that is not simple, settled by the workgroup that found it; the E counters zeroed
+        // by their readers.  The reduce only adds the workgroups' rows up.
+        const unsigned b_lean = launch_finalize_lean_variant(a, stream);
+        hipLaunchKernelGGL(finalize_reduce_kernel, dim3((unsigned)(a.ix.n_files * 3 + 2)), dim3(256), 0, stream, a, (int)b_lean, (unsigned long long*)nullptr, (size_t)0);
+        return;
+    }
+    const unsigned b_v = b_var;
     if (a.ix.slot_files) hipLaunchKernelGGL(finalize_variant_kernel<true>, dim3(b_var), dim3(256), lds_votes, stream, a);
     else hipLaunchKernelGGL(finalize_variant_kernel<false>, dim3(b_var), dim3(256), lds_votes, stream, a);
     // K2e
@@ -3312,8 +3276,7 @@ void launch_finalize(const FinalizeArgs& a0, hipStream_t stream) {
     else if (a.mode == 0 && a.e_list && a.file_cell_lo && a.ix.id_own_files && a.ix.cell_file && a.ix.estat_files && a.ix.id_rest_off && a.ix.total_cells)   // (finalize_exact_kernel: own_all)
         hipLaunchKernelGGL(finalize_exact_own_kernel, dim3((a.ix.total_cells + kOwnCells - 1) / kOwnCells), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(finalize_exact_kernel, dim3(b_ex), dim3(256), lds_votes, stream, a);
-    b_e = b_ex;
-    }
+    const unsigned b_e = b_ex;
     // K2b (deferred k-mers only; the kernel reads their number on the device)
     a.row_general = (int)(b_v + b_e);
     hipLaunchKernelGGL(finalize_general_kernel, dim3(b_gen), dim3(64), lds, stream, a);
