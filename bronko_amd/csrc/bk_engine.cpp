@@ -94,7 +94,7 @@ static int alloc_sample_state(bk_engine* e) {
     BK_HIP(e->present.alloc((size_t)2 * ix.n_files));
     if (prm->pileup_selected_only != 0 && ix.n_files > 1) BK_HIP(e->sel_out.alloc(1));   // (the genome selected between the two finalize passes)
     BK_HIP(e->l2_plan.alloc(4));
-    BK_HIP(e->kstats.alloc(8));
+    BK_HIP(e->kstats.alloc(16));   // two sets, by sample parity (bk_engine::kstats_cur)
     // the scan: binned (items) when the planes are dense, the window's reference is staged in LDS and the bins are few enough;
     // else the whole-window difference array of scan_count_kernel with its slabs
     e->use_items = !e->sparse && ix.ref_in_lds && ix.W > 0 && ix.n_lds_bins > 0 && !test_env("BK_NO_ITEMS") && ix.seed_tab2.p && ix.rc_words.p &&
@@ -258,6 +258,29 @@ int GrowTable::clear(bk_engine* e) {
     return BK_OK;
 }
 
+// may this engine's samples leave their zeroing to the Level 2 launch (bk_sample_begin)?  BK_NO_ZERO_RIDE (testing build): never
+static bool zero_ride_ok(const bk_engine* e) {
+    const bool sel_rows = e->gather_mode && e->params.pileup_selected_only != 0 && e->ix->n_files > 1;
+    return !e->ktab.keys.p && !sel_rows && !test_env("BK_NO_ZERO_RIDE");
+}
+// what the zero ride zeroes: the sample's outputs and the kstats set of the next sample
+static bk::ZeroRide zero_ride_args(const bk_engine* e) {
+    bk::ZeroRide z{};
+    z.big = e->pileup.p; z.n_big = e->gather_mode ? 0 : e->pileup.n;
+    z.a = e->stats.p; z.n_a = (uint32_t)e->stats.n; z.b = e->kstats_other(); z.n_b = 8;
+    z.c = e->present.p; z.n_c = (uint32_t)e->present.n; z.d = e->n_deferred.p; z.n_d = (uint32_t)e->n_deferred.n;
+    return z;
+}
+// A sample whose zeros are still owed and that is about to need them (its finalize; it had no Level 2 launch to carry them): the
+// launch bk_sample_begin left out, over the same buffers as the ride.
+static void pay_owed_zeros(bk_engine* e) {
+    if (!e->zero_owed) return;
+    bk_engine::Span sp(e, 2);
+    const bk::ZeroRide z = zero_ride_args(e);
+    bk::launch_zero_small(z.a, z.n_a, z.b, z.n_b, nullptr, 0, z.c, z.n_c, z.d, z.n_d, z.big, z.n_big, e->stream);
+    e->zero_owed = false; e->next_clean = true;
+}
+
 int bk_sample_begin(bk_engine* e) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     BK_HIP(hipSetDevice(e->device));
@@ -266,8 +289,18 @@ int bk_sample_begin(bk_engine* e) {
     // gathered votes (bk_gather.hip) store the rows they own: every genome's rows -- nothing to zero; the selected genome's -- the rows
     // the previous sample wrote are all that is not zero
     const bool sel_rows = e->gather_mode && e->params.pileup_selected_only != 0 && e->ix->n_files > 1;
-    bk::launch_zero_small(e->stats.p, e->stats.n, e->kstats.p, e->kstats.n, e->ktab_out.p, e->ktab_out.n, e->present.p, e->present.n,
-                          e->n_deferred.p, e->n_deferred.n, e->pileup.p, e->gather_mode ? 0 : e->pileup.n, e->stream);
+    // The zero ride.  Nothing reads or writes the pileup, stats, present or n_deferred between here and the sample's finalize, so
+    // they are zeroed by workgroups of the sample's first Level 2 launch (push_device; pay_owed_zeros for a sample that has none) and
+    // not by a launch of their own.  The four words of kstats that the pushes add to must be clean NOW: that launch zeroed them a
+    // sample ahead, in the set of the other parity.  Without the statistics table (ktab_out is its results) and the gathered votes'
+    // row zeroing; the first sample of an engine, and one behind a sample that never paid, zero everything here as ever.
+    if (zero_ride_ok(e) && e->next_clean) {
+        e->kstats_par ^= 1; e->zero_owed = true; e->next_clean = false;
+    } else {
+        bk::launch_zero_small(e->stats.p, e->stats.n, e->kstats.p, e->kstats.n, e->ktab_out.p, e->ktab_out.n, e->present.p, e->present.n,
+                              e->n_deferred.p, e->n_deferred.n, e->pileup.p, e->gather_mode ? 0 : e->pileup.n, e->stream);   // (both sets of kstats)
+        e->zero_owed = false; e->next_clean = true;
+    }
     if (sel_rows) bk::launch_zero_genome_rows(e->pileup.p, (size_t)e->ix->total_cells * 4, e->ix->file_cell_lo_d.p, e->ix->n_files, (uint32_t)e->ix->total_cells, e->last_sel.p, e->stream);
     if (e->ktab.keys.p) { if (int rc = e->ktab.clear(e)) return rc; }
     if (e->dump) { if (int rc = e->dump->begin_sample(e)) return rc; }
@@ -441,7 +474,7 @@ static bk::ScanArgs scan_args(const bk_engine* e, int mate, const Records& r) {
     a.seed_tab2 = ix.seed_tab2.p; a.seed2_log2 = ix.seed2_log2; a.rc_words = ix.rc_words.p;
     a.n_direct = e->use_items && ix.n_files == 1 && ix.max_seqs_per_file == 1 && (uint64_t)ix.n_lds_bins >= ix.total_cells && !test_env("BK_NO_N_DIRECT");
     a.words = r.words; a.lens = r.lens; a.n_records = r.n; a.stride_words = r.stride_words;
-    a.counters = pl.counters.p; a.kmer_total = e->kstats.p + mate * 4 + 1;
+    a.counters = pl.counters.p; a.kmer_total = e->kstats_cur() + mate * 4 + 1;
     a.ablate = ix.ablate; a.slabs = e->slabs.p; a.n_lds_bins = ix.n_lds_bins; a.ref_in_lds = ix.ref_in_lds ? 1 : 0;
     a.ktab_keys = e->ktab.keys.p; a.ktab_cnt = e->ktab.cnt.p; a.ktab_log2 = e->ktab.log2;
     a.ktab_overflow = e->ktab_out.p + 4; a.mate = (uint32_t)mate;
@@ -541,7 +574,7 @@ static int bin_items(bk_engine* e, bk::ScanArgs& a, int mate, uint32_t grid, boo
 // will level2_and_fold launch level2_kernel for this scan launch?  (Only then can the E bins ride in it.)
 static bool level2_runs(const bk_engine* e, const bk::ScanArgs& a) { return e->ix->ablate != 1 && e->ix->ablate != 4 && bk::level2_launches(a); }
 // Level 2 over the k-mers the scan left marked (it clears the marks it takes); behind the slab scan, its per-cell bin slabs -> u64 plane
-static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32_t grid, const bk::BinArgs* ride) {
+static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32_t grid, const bk::BinArgs* ride, const bk::ZeroRide* zero) {
     const IndexTables& ix = *e->ix;
     bk_engine::Span sp(e, 3);
     if (int rc = l2_count_report(e, a)) return rc;
@@ -549,7 +582,7 @@ static int level2_and_fold(bk_engine* e, const bk::ScanArgs& a, int mate, uint32
         BK_HIP(hipMemsetAsync(e->n_bits.p, 0, (size_t)a.n_records * a.l2_words * sizeof(unsigned int), e->stream));
         BK_HIP(hipMemsetAsync(e->n_any.p, 0, e->n_any.n * sizeof(unsigned int), e->stream));
     }
-    else BK_HIP(bk::launch_level2(a, ix.n_cus, e->stream, ride));
+    else BK_HIP(bk::launch_level2(a, ix.n_cus, e->stream, ride, zero));
     if (!e->use_items) {
         bk::FoldArgs f{};
         f.slabs = e->slabs.p; f.n_slabs = grid; f.n_lds_bins = ix.n_lds_bins; f.id_at = ix.id_at.p; f.cell_codes = ix.cell_codes.p + bk::scan_ref_pad_words(); f.win_lo = a.win_lo; f.win_dev = a.win_dev; f.touch_e = a.touch_e;
@@ -592,7 +625,11 @@ int push_device(bk_engine* e, int mate, const Records& r) {
             bk::BinArgs ride_b{};
             const bool ride = e->use_items && level2_runs(e, a) && !test_env("BK_NO_E_RIDE");
             if (e->use_items) { if (int rc = bin_items(e, a, mate, grid, wait_v, ride ? &ride_b : nullptr)) return rc; }
-            if (int rc = level2_and_fold(e, a, mate, grid, ride ? &ride_b : nullptr)) return rc;
+            // (the sample's first Level 2 launch: the zeros bk_sample_begin left owing ride in it too; later launches carry none)
+            const bool zride = e->zero_owed && level2_runs(e, a);
+            const bk::ZeroRide zero_b = zride ? zero_ride_args(e) : bk::ZeroRide{};
+            if (int rc = level2_and_fold(e, a, mate, grid, ride ? &ride_b : nullptr, zride ? &zero_b : nullptr)) return rc;
+            if (zride) { e->zero_owed = false; e->next_clean = true; }
         }
     }
     for (EventPass* p : e->event_passes()) if (p) { if (int rc = p->push(e, r)) return rc; }
@@ -650,7 +687,7 @@ static bk::FinalizeArgs finalize_args(const bk_engine* e, const FinalizeCall& c,
     // (a part that came through bk_shard_received lives in its own buffer: element i of the plane is reduced[i - elem_lo])
     a.counters = pl.reduced_shards > 0 ? pl.reduced.p - c.elem_lo : pl.counters.p;
     a.elem_lo = c.elem_lo; a.elem_hi = c.elem_hi; a.ci = e->params.ci; a.cs = e->params.cs; a.cx = e->params.cx; a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
-    a.stats = e->stats.p + (size_t)m * ix.n_files * 3; a.present = e->present.p + (size_t)m * ix.n_files; a.kept_total = e->kstats.p + m * 4 + 3; a.distinct_total = e->kstats.p + m * 4 + 2;
+    a.stats = e->stats.p + (size_t)m * ix.n_files * 3; a.present = e->present.p + (size_t)m * ix.n_files; a.kept_total = e->kstats_cur() + m * 4 + 3; a.distinct_total = e->kstats_cur() + m * 4 + 2;
     a.partials = e->fin_partials.p; a.n_deferred = e->n_deferred.p + m;
     a.deferred = e->deferred.p + (c.two_pass ? (size_t)m * (e->deferred.n / 2) : 0);   // (kept from the first pass to the second)
     a.file_cell_lo = ix.file_cell_lo_d.p; a.max_file_cells = (uint32_t)ix.max_file_cells_idx;
@@ -702,6 +739,7 @@ static int finalize_part(bk_engine* e, int n_mates, uint64_t elem_lo, uint64_t e
     if (!e->in_sample) return fail(BK_ERR_STATE, "bk_sample_finalize called before bk_sample_begin");
     if (n_mates < 1 || n_mates > 2) return fail(BK_ERR_INVALID, "n_mates must be 1 or 2");
     BK_HIP(hipSetDevice(e->device));
+    pay_owed_zeros(e);   // (a sample without a Level 2 launch)
     const bool whole = elem_lo == 0 && elem_hi == ix.plane_len;
     const bool via_reduced = e->mate[0].reduced_shards > 0 || e->mate[1].reduced_shards > 0;   // (the planes themselves are not what is mapped: they are zeroed at the next push)
     // bk_params.pileup_selected_only (several genome files): first the statistics of every genome without a single vote, then the
@@ -789,12 +827,12 @@ int bk_sample_finalize_shard(bk_engine* e, int n_mates, int shard, int n_shards)
                         e->mate[m].reduced_shard, e->mate[m].reduced_shards);
     int rc = finalize_part(e, n_mates, part * shard, part * (shard + 1));
     if (rc != BK_OK) return rc;
-    if (e->ktab.keys.p) bk::launch_ktab_totals_to_kstats(e->ktab_out.p, e->kstats.p, n_mates, e->stream);   // (the ranks' totals add up)
+    if (e->ktab.keys.p) bk::launch_ktab_totals_to_kstats(e->ktab_out.p, e->kstats_cur(), n_mates, e->stream);   // (the ranks' totals add up)
     for (int m = 0; m < n_mates; m++) {   // the records this rank pushed join the device tally, so that the sum over ranks is the sample's
-        if (e->mate[m].pushed_records) bk::launch_add_const_u64(e->kstats.p + m * 4 + 0, e->mate[m].pushed_records, e->stream);
+        if (e->mate[m].pushed_records) bk::launch_add_const_u64(e->kstats_cur() + m * 4 + 0, e->mate[m].pushed_records, e->stream);
         e->mate[m].pushed_records = 0;
     }
-    bk::launch_pack_sums(e->shard_sums.p, e->stats.p, e->present.p, e->kstats.p, e->ix->n_files, e->xport_flag.p, e->stream);
+    bk::launch_pack_sums(e->shard_sums.p, e->stats.p, e->present.p, e->kstats_cur(), e->ix->n_files, e->xport_flag.p, e->stream);
     BK_HIP(hipGetLastError());
     return BK_OK;
 }
@@ -855,7 +893,8 @@ int bk_shard_sums_device_ptr(bk_engine* e, void** d_ptr, uint64_t* len) {
 int bk_sample_merge_shards(bk_engine* e) {
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     BK_HIP(hipSetDevice(e->device));
-    bk::launch_unpack_sums(e->shard_sums.p, e->stats.p, e->present.p, e->kstats.p, e->ix->n_files, e->xport_flag.p, e->stream);
+    pay_owed_zeros(e);
+    bk::launch_unpack_sums(e->shard_sums.p, e->stats.p, e->present.p, e->kstats_cur(), e->ix->n_files, e->xport_flag.p, e->stream);
     BK_HIP(hipGetLastError());
     return BK_OK;
 }
@@ -962,6 +1001,7 @@ int bk_sample_download(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t*
     if (!e) return fail(BK_ERR_INVALID, "null engine");
     if (n_mates < 1 || n_mates > 2) return fail(BK_ERR_INVALID, "n_mates must be 1 or 2");
     BK_HIP(hipSetDevice(e->device));
+    pay_owed_zeros(e);   // (a sample begun and not finalized reads zero, as ever)
     const size_t plane = (size_t)e->ix->total_cells * 4;
     uint64_t* dst[4] = {fwd_depth, rev_depth, fwd_nk, rev_nk};
     {
@@ -970,7 +1010,7 @@ int bk_sample_download(bk_engine* e, int n_mates, uint64_t* fwd_depth, uint64_t*
             if (dst[i] && plane) BK_HIP(hipMemcpyAsync(dst[i], e->pileup.p + (size_t)i * plane, plane * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
         if (stats) BK_HIP(hipMemcpyAsync(stats, e->stats.p, (size_t)n_mates * e->ix->n_files * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
         if (present) BK_HIP(hipMemcpyAsync(present, e->present.p, (size_t)n_mates * e->ix->n_files, hipMemcpyDeviceToHost, e->stream));
-        if (kmer_stats) BK_HIP(hipMemcpyAsync(kmer_stats, e->kstats.p, (size_t)n_mates * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+        if (kmer_stats) BK_HIP(hipMemcpyAsync(kmer_stats, e->kstats_cur(), (size_t)n_mates * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     }
     unsigned long long kt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (kmer_stats) BK_HIP(hipMemcpyAsync(kt, e->ktab_out.p, sizeof kt, hipMemcpyDeviceToHost, e->stream));

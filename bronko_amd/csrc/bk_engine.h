@@ -528,7 +528,15 @@ struct bk_engine {
     DevBuf<unsigned long long> pileup;      // 4 planes
     DevBuf<unsigned long long> stats;       // [2][n_files][3]
     DevBuf<unsigned char> present;          // [2][n_files]
-    DevBuf<unsigned long long> kstats;      // [2][4]
+    DevBuf<unsigned long long> kstats;      // [2 sets][2][4]: a sample uses the set of its parity (kstats_cur), so that the set of the next
+                                            // sample can be zeroed while this one is being counted
+    int kstats_par = 0;                     // the current sample's set
+    unsigned long long* kstats_cur() const { return kstats.p + kstats_par * 8; }
+    unsigned long long* kstats_other() const { return kstats.p + (kstats_par ^ 1) * 8; }
+    // The zero ride (bk_engine.cpp, bk_sample_begin): a sample's outputs are zeroed by workgroups of its first Level 2 launch, not by
+    // a launch of their own.
+    bool zero_owed = false;                 // this sample's pileup, stats, present and n_deferred are not zeroed yet
+    bool next_clean = false;                // the other set of kstats is known to be zero
     // bk_push_reads_packed: two staging slots, so that the copy of a batch overlaps the scan of the previous one
     struct StageSlot {
         RecordBufs rec;

@@ -64,7 +64,7 @@ static int trim_records(bk_engine* e, int mate, RecordBufs& b, const Records& r,
         bk::AdapterArgs t{};
         t.words = b.words.p; t.lens = b.lens.p; t.ends = ends; t.cut = ad.cut.p; t.n_records = r.n; t.n_records_dev = r.n_dev;
         t.stride_words = r.stride_words; t.k = e->ix->k; t.n_adapters = ad.n; t.min_overlap = ad.min_overlap; t.allowed_steps = ad.allowed_steps;
-        t.stats = ad.stats.p + mate * 2; t.n_real = e->kstats.p + mate * 4 + 0;
+        t.stats = ad.stats.p + mate * 2; t.n_real = e->kstats_cur() + mate * 4 + 0;
         std::copy(ad.entry, ad.entry + bk::kMaxAdapters, t.adapters);
         bk::launch_adapter_trim(t, e->ix->n_cus, e->stream);
     }
@@ -73,7 +73,7 @@ static int trim_records(bk_engine* e, int mate, RecordBufs& b, const Records& r,
     bk::TrimArgs t{};
     t.words = b.words.p; t.lens = b.lens.p; t.ends = ends; t.n_records = r.n; t.n_records_dev = r.n_dev; t.stride_words = r.stride_words;
     t.k = e->ix->k; t.table = e->primers->table.p; t.n_primers = e->primers->n; t.max_mismatches = e->primers->max_mismatches;
-    t.stats = e->primers->stats.p + mate * 3; t.n_real = e->kstats.p + mate * 4 + 0;
+    t.stats = e->primers->stats.p + mate * 3; t.n_real = e->kstats_cur() + mate * 4 + 0;
     bk::launch_primer_trim(t, e->ix->n_cus, e->stream);
     return BK_OK;
 }
@@ -90,7 +90,7 @@ static int pack_and_push(bk_engine* e, int mate, bk_engine::IngestSlot& sl, cons
     bk::PackArgs pa{};
     pa.shift = shift; pa.bases = bases; pa.offsets = offsets; pa.n_reads = n_reads; pa.k = e->ix->k; pa.stride_words = g.stride;
     pa.words = sl.rec.words.p; pa.lens = sl.rec.lens.p; pa.cap = g.cap; pa.n_records = sl.d_nrec.p; pa.work = sl.d_work.p;
-    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats.p + mate * 4 + 0, e->stream, q, ends); }
+    { bk_engine::Span sp(e, 2); bk::launch_pack_reads(pa, e->kstats_cur() + mate * 4 + 0, e->stream, q, ends); }
     if (ends) { if (int rc = trim_records(e, mate, sl.rec, r, ends)) return rc; }
     return push_device(e, mate, r);
 }

@@ -344,8 +344,17 @@ hipError_t launch_bin_count(const BinArgs& b, hipStream_t stream);
 // Level 2, after launch_scan_count / launch_scan_items with the same arguments.  ride: null, or the BinArgs of the launch_scan_items
 // it follows -- that launch's E bins are then counted by extra workgroups of level2_kernel's launch (both only add to the plane
 // with atomics and read only what the scan wrote), and launch_bin_count is wanted for its V bins at most (part = 2, in front of this).
+// zero: null, or what further workgroups of that launch zero (the engine's zero ride: a sample's outputs, which nothing reads or
+// writes before its finalize, and the kstats set of the next sample) -- what launch_zero_small would have been given.
+struct ZeroRide {
+    unsigned long long* big; uint64_t n_big;      // 16-byte stores, shared by the ride's workgroups (the pileup arrays)
+    unsigned long long* a; unsigned long long* b; // the small buffers: the ride's first workgroup
+    unsigned char* c; unsigned int* d;
+    uint32_t n_a, n_b, n_c, n_d;
+    uint32_t first, n_wg;                         // (launch_level2 fills these) the ride's first workgroup in the grid, and how many
+};
 inline bool level2_launches(const ScanArgs& a) { return a.n_records != 0 && a.W > 0; }   // else launch_level2 launches nothing: no ride
-hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const BinArgs* ride = nullptr);
+hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const BinArgs* ride = nullptr, const ZeroRide* zero = nullptr);
 void launch_ktab_stats(const unsigned long long* keys, const unsigned int* cnt, uint32_t log2n, unsigned long long ci,
                        unsigned long long cx, unsigned long long* out, hipStream_t stream);
 void launch_ktab_rehash(const unsigned long long* okeys, const unsigned int* ocnt, uint32_t olog2, unsigned long long* nkeys, unsigned int* ncnt,

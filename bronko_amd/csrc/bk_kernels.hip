@@ -1554,12 +1554,30 @@ __global__ __launch_bounds__(kL2Block) void nbatch_kernel(ScanArgs a) {
 // share from n_l2, never from gridDim.x.
 static_assert(kL2Block == kBinBlock, "an E bin rides in a workgroup of level2_kernel");
 static_assert(kEBinAccWords * sizeof(unsigned int) <= (size_t)kL2Waves * kL2QueueCap * sizeof(unsigned long long), "the ride's accumulator lies in the slow-path queues");
-static_assert(sizeof(ScanArgs) + sizeof(uint32_t) + sizeof(BinArgs) + 16 <= 4096, "kernel arguments of level2_kernel");
+// The zero ride: behind the E bins, z.n_wg workgroups that zero what a sample's finalize starts from (ZeroRide) and leave.  Nothing
+// in this launch -- Level 2, the E bins, the N batches before it -- reads or writes any of it.
+static_assert(sizeof(ScanArgs) + sizeof(uint32_t) + sizeof(BinArgs) + sizeof(ZeroRide) + 16 <= 4096, "kernel arguments of level2_kernel");
+constexpr uint32_t kZeroRidePerThread = 2;   // 16-byte stores a thread of the ride makes, where the grid is not capped
+constexpr uint32_t kZeroRideMaxWgs = 256;
+__device__ __forceinline__ void zero_ride_body(const ZeroRide& z, const uint32_t wg) {
+    if (wg == 0) {
+        for (uint32_t i = threadIdx.x; i < z.n_a; i += kL2Block) z.a[i] = 0ull;
+        for (uint32_t i = threadIdx.x; i < z.n_b; i += kL2Block) z.b[i] = 0ull;
+        for (uint32_t i = threadIdx.x; i < z.n_c; i += kL2Block) z.c[i] = 0;
+        for (uint32_t i = threadIdx.x; i < z.n_d; i += kL2Block) z.d[i] = 0u;
+        if (threadIdx.x == 0 && (z.n_big & 1)) z.big[z.n_big - 1] = 0ull;
+    }
+    ulonglong2* const big2 = reinterpret_cast<ulonglong2*>(z.big);   // (device allocations are aligned far beyond 16 bytes)
+    const uint64_t n2 = z.n_big / 2, step = (uint64_t)z.n_wg * kL2Block;
+    for (uint64_t i = (uint64_t)wg * kL2Block + threadIdx.x; i < n2; i += step) big2[i] = make_ulonglong2(0ull, 0ull);
+}
 // (four waves per SIMD asked for: left to itself the compiler takes 132 VGPRs for the statistics instantiations -- three waves)
 template <bool STATS, int KT, bool SPARSE>
-__global__ __launch_bounds__(kL2Block) __attribute__((amdgpu_waves_per_eu(4))) void level2_kernel(ScanArgs a, uint32_t n_l2, BinArgs ride) {
+__global__ __launch_bounds__(kL2Block) __attribute__((amdgpu_waves_per_eu(4))) void level2_kernel(ScanArgs a, uint32_t n_l2, BinArgs ride, ZeroRide z) {
     __shared__ unsigned long long queue_c[kL2Waves * kL2QueueCap];   // slow-path queue: canonical k-mer | orientation << 62 | stat_only << 63
-    if (blockIdx.x >= n_l2) {   // (wave-uniform, the whole workgroup) an E bin: its accumulator where Level 2's workgroups keep their slow-path queues
+    if (blockIdx.x >= n_l2) {   // (wave-uniform, the whole workgroup) a rider
+        if (blockIdx.x >= z.first) { zero_ride_body(z, blockIdx.x - z.first); return; }
+        // an E bin: its accumulator where Level 2's workgroups keep their slow-path queues
         bin_count_body<true>(ride, blockIdx.x - n_l2, reinterpret_cast<unsigned int*>(queue_c));
         return;
     }
@@ -2080,8 +2098,8 @@ __global__ __launch_bounds__(1024) void l2_plan_kernel(const unsigned int* __res
     }
 }
 
-hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const BinArgs* ride) {
-    if (!level2_launches(a)) return ride ? hipErrorInvalidValue : hipSuccess;   // (a ride nobody carries: its E bins would never be counted)
+hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const BinArgs* ride, const ZeroRide* zero) {
+    if (!level2_launches(a)) return ride || zero ? hipErrorInvalidValue : hipSuccess;   // (a ride nobody carries: its E bins would never be counted)
     const bool stats = a.ktab_keys != nullptr;
     if (!a.n_direct) {
         void (*kern)(ScanArgs);   // the N runs first (they mark k-mers for the kernel below); ScanArgs::n_direct: the scan left none
@@ -2095,7 +2113,7 @@ hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const
     }
 #define BK_PICK(KT) (!a.touch_v ? (stats ? level2_kernel<true, KT, false> : level2_kernel<false, KT, false>) \
                                 : (stats ? level2_kernel<true, KT, true> : level2_kernel<false, KT, true>))
-    void (*kern)(ScanArgs, uint32_t, BinArgs) = a.k == 21 ? BK_PICK(21) : a.k == 31 ? BK_PICK(31) : BK_PICK(0);
+    void (*kern)(ScanArgs, uint32_t, BinArgs, ZeroRide) = a.k == 21 ? BK_PICK(21) : a.k == 31 ? BK_PICK(31) : BK_PICK(0);
 #undef BK_PICK
     const uint64_t blks = (a.n_records + 32 * kAnyWords - 1) / (32 * kAnyWords);     // a wave takes at least kAnyWords words of l2_any at a time
     // One genome file: a thousandth of the k-mers are marked, and four thousand waves that find nothing to do still take their turn
@@ -2106,7 +2124,11 @@ hipError_t launch_level2(const ScanArgs& a, int n_cus, hipStream_t stream, const
     // the ride: the E bins of the scan launch this one follows, one workgroup each behind Level 2's own (none when that launch had no scan workgroup)
     const BinArgs rb = ride ? *ride : BinArgs{};
     const unsigned n_ride = ride && ride->n_wg ? ride->ig.n_ebins : 0u;
-    hipLaunchKernelGGL(kern, dim3(grid + n_ride), dim3(kL2Block), 0, stream, a, (uint32_t)grid, rb);
+    // the zero ride behind them: a workgroup per kZeroRidePerThread 16-byte stores a thread (at least one: the small buffers)
+    ZeroRide zr = zero ? *zero : ZeroRide{};
+    zr.n_wg = zero ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((zr.n_big / 2 + kL2Block * kZeroRidePerThread - 1) / (kL2Block * kZeroRidePerThread), kZeroRideMaxWgs)) : 0u;
+    zr.first = zero ? grid + n_ride : 0xffffffffu;
+    hipLaunchKernelGGL(kern, dim3(grid + n_ride + zr.n_wg), dim3(kL2Block), 0, stream, a, (uint32_t)grid, rb, zr);
     return hipGetLastError();
 }
 

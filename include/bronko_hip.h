@@ -241,7 +241,10 @@ int bk_transport_overflow(bk_engine* e, int* overflowed);
 int bk_kmer_table_partition(bk_engine* e, int n_parts, void** d_keys, void** d_counts, uint64_t* part_off /* [n_parts + 1] */);
 int bk_kmer_table_replace(bk_engine* e, const void* d_keys, const void* d_counts, uint64_t n);
 /* Device pointers of the finalized arrays: 4 planes (fwd depth, rev depth, fwd #kmers, rev #kmers) of
- * total_cells*4 u64 each, contiguous, in (file, seq, pos, base) order. */
+ * total_cells*4 u64 each, contiguous, in (file, seq, pos, base) order.  The pointer is the engine's for its lifetime; what it
+ * points at holds a finalized sample until the next bk_sample_begin on this engine.  The arrays are zeroed for the next sample
+ * on the engine's stream by bk_sample_begin or, where that launch can be saved, by the sample's first push (inside its Level 2
+ * launch) or its finalize: between bk_sample_begin and bk_sample_finalize their contents are unspecified. */
 int bk_pileup_device_ptr(bk_engine* e, void** d_ptr);
 /* Synchronises and copies results to host memory.  Any pointer may be NULL (skipped).
  *   fwd_depth/rev_depth/fwd_nk/rev_nk : total_cells*4 u64 each    (OutputData.counts, call.rs:1235-1239)
