@@ -1114,7 +1114,14 @@ int IndexBuilder::perfect_hash_and_uploads() {
     BK_HIP(tab.id_at.upload(h_id_at));
     pc.lap("  tables of U filled, uploaded");
     tab.file_cell_lo.assign((size_t)ix->n_files, 0u);
-    for (int f = 0; f < ix->n_files; f++) tab.file_cell_lo[f] = ix->n_seqs[f] ? (uint32_t)cell_off[f][0] : (uint32_t)cells;
+    // (a file without sequences starts where the next file does, so that [file_cell_lo[f], file_cell_lo[f + 1]) is file f's cells
+    // for every f: with `cells` in its place a file in front of it took every later file's cells as its own, and its own range
+    // came out negative -- seed_tables() then looked for a power of two above 2^64 - n and never returned)
+    uint64_t next_lo = cells;
+    for (int f = ix->n_files - 1; f >= 0; f--) {
+        if (ix->n_seqs[f]) next_lo = cell_off[f][0];
+        tab.file_cell_lo[f] = (uint32_t)next_lo;
+    }
     return BK_OK;
 }
 

@@ -96,12 +96,16 @@ class HostIndex:
             self.h = None
 
     def bucket_ids(self):
+        if not self.n_buckets:   # (an index of no k-mer at all: the empty vector's data() may be null)
+            return np.zeros(0, np.uint64)
         return np.ctypeslib.as_array(load().bh_index_bucket_ids(self.h), shape=(self.n_buckets,)).copy()
 
     def bucket_off(self):
         return np.ctypeslib.as_array(load().bh_index_bucket_off(self.h), shape=(self.n_buckets + 1,)).copy()
 
     def entries(self):
+        if not self.n_entries:
+            return np.zeros(0, BUCKET_INFO_DTYPE)
         raw = np.ctypeslib.as_array(load().bh_index_entries(self.h), shape=(max(self.n_entries, 1) * 12,))
         return raw[: self.n_entries * 12].copy().view(BUCKET_INFO_DTYPE)
 

@@ -224,12 +224,16 @@ class Index:
 
     # flattened views (copies)
     def bucket_ids(self):
+        if not self.n_buckets:   # (an index of no k-mer at all)
+            return np.zeros(0, np.uint64)
         return np.ctypeslib.as_array(lib().orc_index_bucket_ids(self.h), shape=(self.n_buckets,)).copy()
 
     def bucket_off(self):
         return np.ctypeslib.as_array(lib().orc_index_bucket_off(self.h), shape=(self.n_buckets + 1,)).copy()
 
     def entries(self):
+        if not self.n_entries:
+            return np.zeros(0, BUCKET_INFO_DTYPE)
         p = lib().orc_index_entries(self.h)
         raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.n_entries * 12,)).copy()
         # padding bytes (offsets 3, 10, 11) are zeroed by the oracle
