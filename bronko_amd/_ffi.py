@@ -203,6 +203,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
            "bk_sample_read_pileup", "bk_sample_download_read_pileup",
+           "bk_cohort_set", "bk_cohort_distances", "bk_cohort_clear",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -402,6 +403,12 @@ def load(testing=None):
     L.bk_sample_read_pileup.argtypes = [vp, C.c_uint32]
     L.bk_sample_download_read_pileup.restype = C.c_int
     L.bk_sample_download_read_pileup.argtypes = [vp, C.POINTER(ReadPileupSummary), vp, u64]
+    L.bk_cohort_set.restype = C.c_int
+    L.bk_cohort_set.argtypes = [vp, vp, u64, u64]
+    L.bk_cohort_distances.restype = C.c_int
+    L.bk_cohort_distances.argtypes = [vp, u64, u64, vp, vp]
+    L.bk_cohort_clear.restype = C.c_int
+    L.bk_cohort_clear.argtypes = [vp]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

@@ -2,7 +2,8 @@
 // index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
 // packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
-// ride behind every scan: the k-mer dump, indels, linkage and the codon, haplotype and read-pileup counts over linkage's rows) and bk_reports.cpp (the reports made of a pileup: calls, consensus, regions).
+// ride behind every scan: the k-mer dump, indels, linkage and the codon, haplotype and read-pileup counts over linkage's rows), bk_reports.cpp (the reports made of a pileup: calls, consensus, regions)
+// and bk_cohort.hip (the distances of a cohort of consensus sequences).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -360,6 +361,16 @@ struct Breakends : EventPassOf<bk_breakend_config, bk_breakend_record> {
 };
 struct Duplications : EventPassOf<bk_duplication_config, bk_duplication_record> { int push(bk_engine* e, const Records& r) override; };
 
+// bk_cohort_set: the cohort's bit planes and the output block of the last bk_cohort_distances (bk_cohort.hip).  No part of a sample:
+// bk_sample_begin and what follows it never look at it
+struct Cohort {
+    uint64_t n = 0, positions = 0;          // samples, letters of each
+    uint64_t W = 0;                         // words of a plane: ceil(positions / 64)
+    uint64_t n_stride = 0;                  // n rounded up to 64, plus 64: the padding samples are all zero
+    DevBuf<unsigned long long> planes;      // [3][W][n_stride] valid, b0, b1
+    DevBuf<unsigned int> out;               // [2][rows of the largest block so far][n] diff, compared
+};
+
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared
 // by an engine and its forks, freed with the last of them.
 struct IndexTables {
@@ -601,6 +612,7 @@ struct bk_engine {
     std::array<EventPass*, 6> event_passes() const { return {indels.get(), junctions.get(), copybacks.get(), chimeras.get(), breakends.get(), duplications.get()}; }
     std::unique_ptr<Linkage> linkage;       // bk_link_enable (null: no row store, no launch, no buffers)
     std::weak_ptr<AnchorTables> anchors;    // the anchor tables while any of the seven features holds them
+    std::unique_ptr<Cohort> cohort;         // bk_cohort_set (null: no cohort, no launch, no buffers)
     DevBuf<unsigned long long> dbg;   // BK_L2_STATS (testing build): tallies of what the scan leaves to Level 2
     bool timing = false;
     unsigned timing_kinds = 0xfu, timing_every = 1, timing_seen[4] = {0, 0, 0, 0};

@@ -688,6 +688,31 @@ class Engine:
         _check(self._L.bk_sample_download_read_pileup(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, buf[:min(cap, int(summ.n_cells))]
 
+    def cohort_set(self, letters):
+        """bk_cohort_set: the consensus letters of a cohort, an (n_samples, positions) uint8 array, uploaded and packed into bit
+        planes on the device; replaces an earlier cohort.  Between samples only."""
+        a = np.ascontiguousarray(letters, np.uint8)
+        if a.ndim != 2:
+            raise ValueError("cohort_set takes a 2-d array: a row of letters per sample")
+        _check(self._L.bk_cohort_set(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]), self._L)
+        self._cohort_n = int(a.shape[0])
+
+    def cohort_distances(self, row0=0, n_rows=None):
+        """bk_cohort_distances: (diff, compared) of the rows [row0, row0 + n_rows) against every sample of the cohort, two
+        (n_rows, n_samples) uint32 arrays; all rows from row0 on by default."""
+        n = int(getattr(self, "_cohort_n", 0))
+        if n_rows is None:
+            n_rows = max(0, n - int(row0))
+        diff = np.zeros((max(1, int(n_rows)), max(1, n)), np.uint32)
+        compared = np.zeros_like(diff)
+        _check(self._L.bk_cohort_distances(self.h, int(row0), int(n_rows), diff.ctypes.data_as(C.c_void_p), compared.ctypes.data_as(C.c_void_p)), self._L)
+        return diff[:int(n_rows), :n], compared[:int(n_rows), :n]
+
+    def cohort_clear(self):
+        """bk_cohort_clear: frees the cohort's device memory (fine without a cohort)."""
+        _check(self._L.bk_cohort_clear(self.h), self._L)
+        self._cohort_n = 0
+
     def regions_set(self, regions):
         """bk_regions_set: the regions [(file_id, seq, start, end), ...] whose depths sample_region_depths reports; [] clears them."""
         arr = (_ffi.Region * max(1, len(regions)))(*[_ffi.Region(*(int(v) for v in r[:4])) for r in regions])

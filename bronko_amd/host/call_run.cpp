@@ -317,6 +317,8 @@ struct CallRun {
     Index ix;
     std::vector<OverviewRow> overview;               // by sample, in input order
     std::vector<SampleCalls> all_calls;              // --alignment
+    std::vector<std::vector<uint8_t>> cohort_letters;   // --distances: by sample, its consensus letters (n x positions bytes of host memory in all)
+    std::vector<int> cohort_genome;                  // ... and the genome file it selected (-1: none)
     std::vector<Region> regions;                     // --regions / --region-window: resolved by open_index, every genome file's
     std::vector<bk_region> region_table;             // ... as bk_regions_set takes them
     size_t max_file_regions = 0;                     // regions of the genome file with the most
@@ -333,6 +335,7 @@ struct CallRun {
         for (size_t i = 0; i < a.first_pairs.size(); i++) samples.push_back({a.first_pairs[i], a.second_pairs[i]});
         overview.resize(samples.size());
         if (a.alignment) all_calls.resize(samples.size());
+        if (a.distances) { cohort_letters.resize(samples.size()); cohort_genome.assign(samples.size(), -1); }
         if (!getenv("BRONKO_NO_READ_AHEAD")) {
             const uint64_t ram = (uint64_t)sysconf(_SC_PHYS_PAGES) * (uint64_t)sysconf(_SC_PAGE_SIZE);
             ahead.reset(new ReadAhead(samples, cfg, (unsigned)std::max<long>(2, a.threads / 8), std::min<uint64_t>(ram / 4, 32ull << 30)));
@@ -862,6 +865,70 @@ struct CallRun {
         write_outputs(mates, best, d, cs);
         overview[sample_id] = OverviewRow{mates[0], gname, cs.n_major, cs.n_minor, cs.breadth, cs.depth, n_perfect, n_variant, n_unmapped};
         if (a.alignment) all_calls[sample_id] = SampleCalls{mates[0], gname, cs.breadth, cs.records};
+        if (a.distances) {   // (the letters as they were written: with '-' at the deletions --consensus-indels applied)
+            cohort_letters[sample_id].assign(d.letters.begin(), d.letters.begin() + (ptrdiff_t)std::min<uint64_t>(d.csumm.positions, d.letters.size()));
+            cohort_genome[sample_id] = best;
+        }
+    }
+
+    // ---- --distances: the samples' consensus letters compared pair by pair, per selected genome, on one engine that is still alive ----
+    void write_distances(bk_engine* e) {
+        constexpr uint64_t kBlockBytes = 256ull << 20;   // a block's two host buffers together
+        for (size_t i = 0; i < samples.size(); i++)
+            if (cohort_genome[i] < 0) LOG_INFO(T, "Distances: " + clean_sample_id(samples[i][0]) + " selected no genome and is left out");
+        for (size_t g = 0; g < ix.files.size(); g++) {
+            std::vector<size_t> group;
+            for (size_t i = 0; i < samples.size(); i++)
+                if (cohort_genome[i] == (int)g) group.push_back(i);
+            if (group.empty()) continue;
+            const std::string& gname = ix.files[g].name;
+            if (group.size() < 2) { LOG_INFO(T, "Skipping distances for " + gname + " (1 sample selected it, at least 2 are compared)"); continue; }
+            const auto t0 = std::chrono::steady_clock::now();
+            const uint64_t n = group.size(), positions = ix.genome_len(g);
+            std::vector<std::string> names;
+            std::vector<uint8_t> letters((size_t)(n * positions));
+            for (size_t r = 0; r < n; r++) {
+                names.push_back(clean_sample_id(samples[group[r]][0]));
+                std::vector<uint8_t>& l = cohort_letters[group[r]];
+                if (l.size() != positions) die(T, "Distances: the consensus of " + names.back() + " is not as long as " + gname);
+                std::copy(l.begin(), l.end(), letters.begin() + (ptrdiff_t)(r * positions));
+                std::vector<uint8_t>().swap(l);   // (a sample's letters are held once)
+            }
+            hip_check(bk_cohort_set(e, letters.data(), n, positions), "bk_cohort_set");
+            std::vector<uint8_t>().swap(letters);
+            const uint64_t block_rows = std::max<uint64_t>(1, std::min<uint64_t>(n, kBlockBytes / (8 * n)));
+            std::vector<uint32_t> diff((size_t)(block_rows * n)), compared((size_t)(block_rows * n));
+            uint64_t max_diff = 0, empty_pairs = 0;
+            CohortClusters cl;
+            try {
+                CohortMatrixWriter wd(a.output + "/" + gname + ".distances.tsv", names), wc(a.output + "/" + gname + ".compared.tsv", names);
+                CohortClusterer clusterer(n, positions, (uint64_t)a.clusters, a.cluster_min_breadth);
+                for (uint64_t row0 = 0; row0 < n; row0 += block_rows) {
+                    const uint64_t rows = std::min(block_rows, n - row0);
+                    hip_check(bk_cohort_distances(e, row0, rows, diff.data(), compared.data()), "bk_cohort_distances");
+                    wd.add_rows(row0, rows, diff.data());
+                    wc.add_rows(row0, rows, compared.data());
+                    if (a.has_clusters) clusterer.add_rows(row0, rows, diff.data(), compared.data());
+                    for (uint64_t r = 0; r < rows; r++)
+                        for (uint64_t j = row0 + r + 1; j < n; j++) {   // (each pair once)
+                            max_diff = std::max<uint64_t>(max_diff, diff[r * n + j]);
+                            empty_pairs += compared[r * n + j] == 0;
+                        }
+                }
+                wd.close(); wc.close();
+                if (a.has_clusters) {
+                    cl = clusterer.finish();
+                    write_cohort_clusters_tsv(a.output + "/" + gname + ".clusters.tsv", names, cl, (uint64_t)a.clusters, a.cluster_min_breadth);
+                }
+            } catch (const std::exception& ex) { die(T, ex.what()); }
+            char secs[32];
+            snprintf(secs, sizeof secs, "%.3f", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            LOG_INFO(T, "Distances for " + gname + ": " + std::to_string(n) + " samples, largest distance " + std::to_string(max_diff) + ", " +
+                            std::to_string(empty_pairs) + " pairs with nothing compared" +
+                            (a.has_clusters ? ", " + std::to_string(cl.n_clusters) + " clusters, the largest of " + std::to_string(cl.largest) + " samples" : std::string()) +
+                            " (" + secs + " s)");
+        }
+        hip_check(bk_cohort_clear(e), "bk_cohort_clear");
     }
 
     // ---- the samples ---------------------------------------------------------------------------------------------------------------
@@ -941,8 +1008,13 @@ int call_samples(const Args& a, const CallConfig& cfg) {
     if (run.ahead) run.ahead->set_concurrency((unsigned)std::max<long>(2, a.threads / 2));   // (the engines are made: the cores are the readers')
     run.dump_threads = (int)std::max<size_t>(1, std::min<size_t>(16, (size_t)a.threads / std::max<size_t>(1, lanes.size())));
 
-    if (!shards.engs.empty()) { run.run_sharded_samples(shards, inflate); shard_engines.clear(); }
+    if (!shards.engs.empty()) {
+        run.run_sharded_samples(shards, inflate);
+        if (a.distances) run.write_distances(shards.engs[0]);   // (the cohort step takes one engine that is still alive: the first shard's ...)
+        shard_engines.clear();
+    }
     run.run_lanes(lanes, inflate);
+    if (a.distances && !lanes.empty()) run.write_distances(lanes[0].eng.e);   // (... or the first lane's)
     release_lanes(lanes);
     run.write_run_outputs();
     LOG_INFO(T, "");

@@ -82,7 +82,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--link-max-mismatches M] [--link-max-dist D] [--link-min-reads N] [--codons BED]\n"
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
           "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
-          "            [--read-pileup-max-mismatches M] [-t <THREADS>] [--debug] [--verbose]\n\n"
+          "            [--read-pileup-max-mismatches M] [--distances] [--clusters T] [--cluster-min-breadth B]\n"
+          "            [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
           "  --min-base-qual Q treat every base whose quality is below Q (Phred+33: quality byte < '!' + Q) as N before k-mers\n"
@@ -181,7 +182,14 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    and how many of them within E positions of a read's end (near_A .. near_T)\n"
           "  --read-pileup-end E      positions from a read's end up to which a base counts as near it; 0..255, default 10\n"
           "  --read-pileup-max-mismatches M  substitutions a read may have to be counted; 0..8, default 8 (with --linkage, --codons or\n"
-          "                    --haplotypes: equal to their M)\n", stderr);
+          "                    --haplotypes: equal to their M)\n"
+          "  --distances       compare the consensus letters of all samples that selected the same genome, pair by pair (needs --consensus):\n"
+          "                    <DIR>/<genome>.distances.tsv holds per pair the positions at which both letters are one of ACGT and differ,\n"
+          "                    <DIR>/<genome>.compared.tsv the positions at which both are one of ACGT; N, '-', ambiguity codes and inserted\n"
+          "                    bases are not compared; a genome that fewer than two samples selected gets no files\n"
+          "  --clusters T      write single-linkage clusters to <DIR>/<genome>.clusters.tsv (needs --distances): two samples are linked when\n"
+          "                    they differ at T positions or fewer and compared at least B of the genome's positions; at least 0\n"
+          "  --cluster-min-breadth B  share of the genome's positions a pair must have compared to be linked; 0..1, default 0.9\n", stderr);
     exit(code);
 }
 
@@ -373,6 +381,9 @@ Args parse_args(int argc, char** argv) {
             if (opt == "--read-pileup-end") { a.read_pileup_end = x; a.has_read_pileup_end = true; }
             else { a.read_pileup_max_mismatches = x; a.has_read_pileup_max_mismatches = true; }
         }
+        else if (opt == "--distances") a.distances = true;
+        else if (opt == "--clusters") { a.clusters = any_long(opt, one()); a.has_clusters = true; }   // (any integer here: check_call_args)
+        else if (opt == "--cluster-min-breadth") { a.cluster_min_breadth = to_double(opt, one()); a.has_cluster_min_breadth = true; }
         else if (opt == "--hap-min-freq") { a.hap_min_freq = to_double(opt, one()); a.has_hap_min_freq = true; }
         else if (opt == "--codon-min-freq") { a.codon_min_freq = to_double(opt, one()); a.has_codon_min_freq = true; }
         else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
@@ -651,6 +662,15 @@ void check_call_args(const Args& a) {   // call.rs:30-136
         if (a.read_pileup && o.on && o.m != a.read_pileup_max_mismatches)
             die(T, std::string(o.flag) + " and --read-pileup count the same placed reads: " + o.opt + " (" + std::to_string(o.m) + ") and --read-pileup-max-mismatches (" +
                        std::to_string(a.read_pileup_max_mismatches) + ") must be equal");
+    if (a.distances && !a.consensus) die(T, "--distances needs --consensus");
+    if (a.has_clusters && !a.distances) die(T, "--clusters needs --distances");
+    if (a.has_cluster_min_breadth && !a.has_clusters) die(T, "--cluster-min-breadth needs --clusters");
+    if (a.clusters < 0) die(T, "--clusters must be at least 0, got " + std::to_string(a.clusters));
+    if (!(a.cluster_min_breadth >= 0.0 && a.cluster_min_breadth <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "--cluster-min-breadth must be between 0 and 1, got %g", a.cluster_min_breadth);
+        die(T, buf);
+    }
 }
 
 // the checked arguments -> what the readers and the per-sample code work from; the primer file and the regions file are read and the adapters are

@@ -12,6 +12,7 @@
 #include "caller.hpp"
 #include "chimeras.hpp"
 #include "codons.hpp"
+#include "cohort.hpp"
 #include "copybacks.hpp"
 #include "duplications.hpp"
 #include "haplotypes.hpp"
@@ -123,6 +124,10 @@ struct Args {
     bool has_read_pileup_end = false, has_read_pileup_max_mismatches = false;
     long read_pileup_end = 10;      // --read-pileup-end: a base within this many positions of a read's end counts as near it (0..255)
     long read_pileup_max_mismatches = 8;   // --read-pileup-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with the other three)
+    bool distances = false;         // --distances: <DIR>/<genome>.distances.tsv and .compared.tsv, the samples' pairwise consensus distances (needs --consensus)
+    bool has_clusters = false, has_cluster_min_breadth = false;
+    long clusters = 0;              // --clusters T: <DIR>/<genome>.clusters.tsv, single-linkage clusters of the samples at most T apart (needs --distances)
+    double cluster_min_breadth = 0.9;   // --cluster-min-breadth B: share of the genome's positions a pair must have compared to be linked (0..1)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;

@@ -12,6 +12,7 @@
 #include "caller.hpp"
 #include "chimeras.hpp"
 #include "codons.hpp"
+#include "cohort.hpp"
 #include "copybacks.hpp"
 #include "duplications.hpp"
 #include "haplotypes.hpp"
@@ -618,6 +619,47 @@ int bh_write_read_pileup_tsv(const void* h, int file_id, const char* path, const
         const auto* c = static_cast<const bronko::ReadPileupCell*>(cells);
         const bronko::ReadPileupStats st = bronko::write_read_pileup_tsv(path, *static_cast<const bronko::Index*>(h), file_id, std::vector<bronko::ReadPileupCell>(c, c + n_cells), p);
         if (stats) { stats[0] = st.covered; stats[1] = st.bases; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- --distances: the host twin of the engine's cohort kernels, the clusterer and the three writers (cohort.cpp) ---------------------
+// letters: n rows of `positions` bytes; diff, compared: [n_rows][n] each, either may be null
+int bh_cohort_distances(const uint8_t* letters, uint64_t n, uint64_t positions, uint64_t row0, uint64_t n_rows, uint32_t* diff, uint32_t* compared, uint32_t threads) {
+    try {
+        if (!letters) throw std::runtime_error("bh_cohort_distances: letters is null");
+        bronko::cohort_distances_host(letters, n, positions, row0, n_rows, diff, compared, threads);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// the matrices go to the clusterer in blocks of block_rows rows (0: all at once); cluster, size: [n]; stats: clusters, the largest's size
+int bh_cohort_clusters(uint64_t n, uint64_t positions, const uint32_t* diff, const uint32_t* compared, uint64_t threshold, double min_breadth, uint64_t block_rows,
+                       uint32_t* cluster, uint32_t* size, uint32_t* stats) {
+    try {
+        bronko::CohortClusterer cl(n, positions, threshold, min_breadth);
+        const uint64_t step = block_rows ? block_rows : std::max<uint64_t>(n, 1);
+        for (uint64_t r = 0; r < n; r += step) cl.add_rows(r, std::min(step, n - r), diff + r * n, compared + r * n);
+        const bronko::CohortClusters c = cl.finish();
+        for (uint64_t i = 0; i < n; i++) { cluster[i] = c.cluster[i]; size[i] = c.size[i]; }
+        if (stats) { stats[0] = c.n_clusters; stats[1] = c.largest; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// names: the samples' names joined by '\n'
+int bh_write_cohort_distances_tsv(const char* path, const char* names, const uint32_t* diff) {
+    try { bronko::write_cohort_distances_tsv(path, split_lines(names), diff); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int bh_write_cohort_compared_tsv(const char* path, const char* names, const uint32_t* compared) {
+    try { bronko::write_cohort_compared_tsv(path, split_lines(names), compared); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int bh_write_cohort_clusters_tsv(const char* path, const char* names, const uint32_t* cluster, const uint32_t* size, uint64_t threshold, double min_breadth) {
+    try {
+        const std::vector<std::string> nm = split_lines(names);
+        bronko::CohortClusters c;
+        c.cluster.assign(cluster, cluster + nm.size()); c.size.assign(size, size + nm.size());
+        bronko::write_cohort_clusters_tsv(path, nm, c, threshold, min_breadth);
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -784,3 +784,62 @@ def write_read_pileup_tsv(path, ix, file_id, cells, max_mismatches=8, end_dist=1
     if L.bh_write_read_pileup_tsv(ix.h, file_id, path.encode(), c.ctypes.data, len(c), int(max_mismatches), int(end_dist), stats) != 0:
         raise _host_error(L)
     return tuple(int(v) for v in stats)
+
+
+# ---- --distances: the host twin of the engine's cohort kernels, the clusterer and the three writers (cohort.cpp) ---------------------
+def _cohort_lib():
+    vp, u64, u32 = _VP, _U64, _U32
+    return _bound("_cohort_ready", {
+        "bh_cohort_distances": [vp, u64, u64, u64, u64, vp, vp, u32],
+        "bh_cohort_clusters": [u64, u64, vp, vp, u64, C.c_double, u64, vp, vp, vp],
+        "bh_write_cohort_distances_tsv": [C.c_char_p, C.c_char_p, vp],
+        "bh_write_cohort_compared_tsv": [C.c_char_p, C.c_char_p, vp],
+        "bh_write_cohort_clusters_tsv": [C.c_char_p, C.c_char_p, vp, vp, u64, C.c_double]})
+
+
+def cohort_distances(letters, row0=0, n_rows=None, threads=4):
+    """The host twin of the cohort kernels (cohort.cpp cohort_distances_host): (diff, compared) of the rows [row0, row0 + n_rows) of an
+    (n_samples, positions) uint8 array of letters against all of its rows, two (n_rows, n_samples) uint32 arrays."""
+    L = _cohort_lib()
+    a = np.ascontiguousarray(letters, np.uint8)
+    n, positions = a.shape
+    n_rows = n - row0 if n_rows is None else n_rows
+    diff = np.zeros((max(1, n_rows), max(1, n)), np.uint32)
+    compared = np.zeros_like(diff)
+    if L.bh_cohort_distances(a.ctypes.data, n, positions, int(row0), int(n_rows), diff.ctypes.data, compared.ctypes.data, int(threads)) != 0:
+        raise _host_error(L)
+    return diff[:n_rows, :n], compared[:n_rows, :n]
+
+
+def cohort_clusters(diff, compared, positions, threshold, min_breadth=0.9, block_rows=0):
+    """The --clusters clusterer (cohort.cpp CohortClusterer) fed the two (n, n) matrices in blocks of block_rows rows (0: at once):
+    (cluster numbers, cluster sizes, number of clusters, size of the largest)."""
+    L = _cohort_lib()
+    d = np.ascontiguousarray(diff, np.uint32)
+    c = np.ascontiguousarray(compared, np.uint32)
+    n = d.shape[0]
+    cluster = np.zeros(max(1, n), np.uint32)
+    size = np.zeros(max(1, n), np.uint32)
+    stats = np.zeros(2, np.uint32)
+    if L.bh_cohort_clusters(n, int(positions), d.ctypes.data, c.ctypes.data, int(threshold), float(min_breadth), int(block_rows),
+                            cluster.ctypes.data, size.ctypes.data, stats.ctypes.data) != 0:
+        raise _host_error(L)
+    return cluster[:n], size[:n], int(stats[0]), int(stats[1])
+
+
+def write_cohort_matrix_tsv(path, names, matrix, compared=False):
+    """The --distances writers (cohort.cpp): OUT/<genome>.distances.tsv, or .compared.tsv with compared=True, of an (n, n) matrix."""
+    L = _cohort_lib()
+    m = np.ascontiguousarray(matrix, np.uint32)
+    fn = L.bh_write_cohort_compared_tsv if compared else L.bh_write_cohort_distances_tsv
+    if fn(path.encode(), "\n".join(names).encode(), m.ctypes.data) != 0:
+        raise _host_error(L)
+
+
+def write_cohort_clusters_tsv(path, names, cluster, size, threshold, min_breadth=0.9):
+    """The --clusters writer (cohort.cpp write_cohort_clusters_tsv)."""
+    L = _cohort_lib()
+    cl = np.ascontiguousarray(cluster, np.uint32)
+    sz = np.ascontiguousarray(size, np.uint32)
+    if L.bh_write_cohort_clusters_tsv(path.encode(), "\n".join(names).encode(), cl.ctypes.data, sz.ctypes.data, int(threshold), float(min_breadth)) != 0:
+        raise _host_error(L)

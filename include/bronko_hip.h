@@ -1035,6 +1035,32 @@ typedef struct { uint64_t rows, n_cells; uint32_t end_dist, pad; uint64_t covere
 int  bk_sample_read_pileup(bk_engine* e, uint32_t end_dist /* 0..255 */);
 int  bk_sample_download_read_pileup(bk_engine* e, bk_read_pileup_summary* summary, bk_read_pileup_cell* cells, uint64_t cap_cells);
 
+/* ---- pairwise distances of a cohort (`bronko call --distances`; additive, still v8) ----------------------------------------------
+ * The consensus letters of many samples of one genome, compared pair by pair on the device.  No part of a sample: the three calls
+ * come between samples (BK_ERR_STATE inside one) and touch nothing a sample reads or writes.  The rule, all of it integer arithmetic:
+ *   input      n rows of `positions` bytes, row-major: the letters bk_sample_download_consensus returns (under
+ *              bk_sample_consensus_indels with '-' at the applied deletions; inserted bases are not among them).
+ *   base       a byte is a base iff it is exactly 'A', 'C', 'G' or 'T'.  Every other byte -- N, '-', the IUPAC ambiguity codes, lower
+ *              case, anything else -- is not comparable.
+ *   compared   compared[i][j] = the positions at which both letters are bases; diff[i][j] = those of them at which the two differ.
+ *              Both u32, both symmetric; diff[i][i] = 0, compared[i][i] = the bases of sample i; a pair that shares no base has 0 / 0.
+ *   bk_cohort_set        uploads the letters (host memory), packs them into three bit planes per sample (cohort_pack_kernel,
+ *                        bk_cohort.hip) and keeps the planes: 24 bytes per 64 positions and sample.  Replaces an earlier cohort, of which
+ *                        nothing stays (a call refused for its arguments or its state leaves the earlier cohort as it was; one that
+ *                        fails later leaves none).  Synchronises: the letters may go when it returns.  BK_ERR_INVALID,
+ *                        with the parameter named: a null pointer, n_samples = 0 or above BK_COHORT_MAX_SAMPLES, positions = 0 or
+ *                        >= 2^32.  Per engine: a fork has none of its parent's.  An engine that never calls it allocates and launches
+ *                        nothing.
+ *   bk_cohort_distances  rows [row0, row0 + n_rows) against all n_samples columns (cohort_pairs_kernel); synchronises and copies
+ *                        n_rows x n_samples values, row-major, into each output that is not NULL.  BK_ERR_STATE without a cohort;
+ *                        BK_ERR_INVALID for n_rows = 0 and for a block that reaches beyond the cohort.  The device's output buffer grows
+ *                        to the largest block asked for: a caller bounds its memory, and the device's, by the block it asks for.
+ *   bk_cohort_clear      frees the cohort's device memory; BK_OK also without one. */
+#define BK_COHORT_MAX_SAMPLES (1u << 20)
+int  bk_cohort_set(bk_engine* e, const uint8_t* letters, uint64_t n_samples, uint64_t positions);
+int  bk_cohort_distances(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* diff, uint32_t* compared);
+int  bk_cohort_clear(bk_engine* e);
+
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
  * (bucket id, BucketInfo) pairs in generation order, a stable device radix sort groups them by bucket id (inside a bucket the
