@@ -176,6 +176,14 @@ class RegionSummary(C.Structure):  # bk_region_summary
     _fields_ = [("file_id", C.c_int32), ("n_regions", C.c_uint32), ("full", C.c_uint64), ("partial", C.c_uint64), ("empty", C.c_uint64)]
 
 
+class MstEdge(C.Structure):  # bk_mst_edge
+    _fields_ = [("lo", C.c_uint32), ("hi", C.c_uint32), ("diff", C.c_uint32), ("compared", C.c_uint32)]
+
+
+class MstNearest(C.Structure):  # bk_mst_nearest
+    _fields_ = [("sample", C.c_uint32), ("diff", C.c_uint32), ("compared", C.c_uint32)]
+
+
 class BuiltIndex(C.Structure):  # bk_built_index
     _fields_ = [("n_buckets", C.c_uint64), ("n_entries", C.c_uint64), ("bucket_ids", C.c_void_p), ("bucket_off", C.c_void_p),
                 ("entries", C.c_void_p)]
@@ -203,7 +211,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
            "bk_sample_read_pileup", "bk_sample_download_read_pileup",
-           "bk_cohort_set", "bk_cohort_distances", "bk_cohort_clear",
+           "bk_cohort_set", "bk_cohort_distances", "bk_cohort_clear", "bk_cohort_mst",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -409,6 +417,8 @@ def load(testing=None):
     L.bk_cohort_distances.argtypes = [vp, u64, u64, vp, vp]
     L.bk_cohort_clear.restype = C.c_int
     L.bk_cohort_clear.argtypes = [vp]
+    L.bk_cohort_mst.restype = C.c_int
+    L.bk_cohort_mst.argtypes = [vp, C.c_uint32, C.POINTER(MstEdge), u64, C.POINTER(u64), C.POINTER(MstNearest), C.POINTER(C.c_uint32)]
     L.bk_build_index.restype = C.c_int
     L.bk_build_index.argtypes = [i32, i32, vp, vp, vp, i32, C.POINTER(BuiltIndex)]
     L.bk_built_index_free.argtypes = [C.POINTER(BuiltIndex)]

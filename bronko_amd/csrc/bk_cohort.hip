@@ -21,11 +21,20 @@
 //                         The grid is tiles x position slices: with few samples the tiles alone do not fill the device, so the words are
 //                         cut into slices and every workgroup adds its partial sums to the output block, which is zeroed on the stream
 //                         before the launch, with one atomicAdd per pair and counter (none for a zero).  Integer sums: exact in any order.
+// bk_cohort_mst (`--mst`) finds the cohort's minimum spanning forest by Boruvka rounds over the same row blocks (rule: bronko_hip.h,
+// DESIGN.md section Y; bronko_amd/host/cohort.cpp and tests/mst_ref.py find the same forest by Prim and by Kruskal):
+//   cohort_row_best_kernel   a workgroup of four waves per row of the block the pairs kernel left: lanes stride the columns (coalesced
+//                            loads of diff, compared and label), keep the least diff << 32 | j over the admissible columns of another
+//                            component and that pair's compared; a wave reduction (__shfl_xor on the key's halves), the four waves
+//                            meet in LDS, lane 0 stores.  The loop's bound is n.
+//   cohort_comp_diff_kernel, cohort_comp_pair_kernel   a lane per row: atomicMin of the row's diff at its label, then, among the rows
+//                            that have that diff, atomicMin of lo << 32 | hi: the component's least edge under (diff, lo, hi).
 // Vector stores and atomics only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 #include "bk_engine.h"
 
@@ -125,6 +134,79 @@ __global__ __launch_bounds__(kCohortBlock) void cohort_pairs_kernel(PairsArgs a)
     }
 }
 
+// ---- bk_cohort_mst ------------------------------------------------------------------------------------------------------------------
+constexpr unsigned long long kNoKey = ~0ull;
+
+struct RowBestArgs {
+    const unsigned int* diff;               // [n_rows][n] the block cohort_pairs_kernel left
+    const unsigned int* compared;           // [n_rows][n]
+    const unsigned int* label;              // [n]
+    uint64_t n, row0, n_rows;
+    uint32_t need;                          // compared a pair must reach: max(1, min_compared)
+    unsigned long long* row_key;            // [n]
+    unsigned int* row_cmp;                  // [n]
+};
+
+// the lesser key of two lanes, 32 bits at a time, and the compared that goes with it
+__device__ __forceinline__ void wave_min_key(unsigned long long& key, unsigned int& cmp) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned int lo = (unsigned int)__shfl_xor((int)(unsigned int)key, m, 64), hi = (unsigned int)__shfl_xor((int)(unsigned int)(key >> 32), m, 64);
+        const unsigned int oc = (unsigned int)__shfl_xor((int)cmp, m, 64);
+        const unsigned long long other = (unsigned long long)hi << 32 | lo;
+        if (other < key) { key = other; cmp = oc; }   // (keys of different lanes differ in j, or both are kNoKey)
+    }
+}
+
+__global__ __launch_bounds__(kCohortBlock) void cohort_row_best_kernel(RowBestArgs a) {
+    __shared__ unsigned long long s_key[kCohortBlock / 64];
+    __shared__ unsigned int s_cmp[kCohortBlock / 64];
+    const uint64_t r = blockIdx.x;                                // (the grid is n_rows workgroups: r < n_rows)
+    const uint64_t i = a.row0 + r;
+    const unsigned int mine = a.label[i];
+    const unsigned int* __restrict__ drow = a.diff + (size_t)r * a.n;
+    const unsigned int* __restrict__ crow = a.compared + (size_t)r * a.n;
+    unsigned long long key = kNoKey;
+    unsigned int cmp = 0;
+    for (uint64_t j = threadIdx.x; j < a.n; j += kCohortBlock) {   // (ascending j: the first of equal diffs stays)
+        const unsigned int c = crow[j], d = drow[j], l = a.label[j];
+        const unsigned long long k = (unsigned long long)d << 32 | (unsigned long long)j;
+        if (l != mine && c >= a.need && k < key) { key = k; cmp = c; }
+    }
+    wave_min_key(key, cmp);
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) { s_key[wave] = key; s_cmp[wave] = cmp; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < kCohortBlock / 64; w++)
+            if (s_key[w] < key) { key = s_key[w]; cmp = s_cmp[w]; }
+        a.row_key[i] = key; a.row_cmp[i] = cmp;
+    }
+}
+
+// every component's least edge under (diff, lo, hi) from its rows' bests, in two passes over the n rows: the least diff, then the
+// least lo << 32 | hi among the rows that have it
+__global__ __launch_bounds__(kCohortBlock) void cohort_comp_diff_kernel(const unsigned long long* __restrict__ row_key, const unsigned int* __restrict__ label, uint64_t n,
+                                                                        unsigned int* __restrict__ comp_diff) {
+    const uint64_t i = (uint64_t)blockIdx.x * kCohortBlock + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = row_key[i];
+    if (key != kNoKey) atomicMin(comp_diff + label[i], (unsigned int)(key >> 32));
+}
+
+__global__ __launch_bounds__(kCohortBlock) void cohort_comp_pair_kernel(const unsigned long long* __restrict__ row_key, const unsigned int* __restrict__ label, uint64_t n,
+                                                                        const unsigned int* __restrict__ comp_diff, unsigned long long* __restrict__ comp_pair) {
+    const uint64_t i = (uint64_t)blockIdx.x * kCohortBlock + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = row_key[i];
+    if (key == kNoKey) return;
+    const unsigned int l = label[i];
+    if ((unsigned int)(key >> 32) != comp_diff[l]) return;
+    const unsigned long long j = key & 0xffffffffull;
+    atomicMin(comp_pair + l, i < j ? (unsigned long long)i << 32 | j : j << 32 | (unsigned long long)i);
+}
+
 }  // namespace
 }  // namespace bk
 
@@ -170,6 +252,8 @@ int bk_cohort_set(bk_engine* e, const uint8_t* letters, uint64_t n_samples, uint
     return BK_OK;
 }
 
+static int launch_pairs(bk_engine* e, Cohort& c, const char* who, uint64_t row0, uint64_t n_rows);
+
 int bk_cohort_distances(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* diff, uint32_t* compared) {
     if (!e) return fail(BK_ERR_INVALID, "bk_cohort_distances: e is null");
     if (e->in_sample) return fail(BK_ERR_STATE, "bk_cohort_distances inside a sample: it comes before bk_sample_begin or after the sample's downloads");
@@ -179,13 +263,24 @@ int bk_cohort_distances(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* 
     if (row0 >= c.n || n_rows > c.n - row0)
         return fail(BK_ERR_INVALID, "bk_cohort_distances: row0 = %llu, n_rows = %llu lie beyond the cohort's %llu samples", (unsigned long long)row0, (unsigned long long)n_rows, (unsigned long long)c.n);
     BK_HIP(hipSetDevice(e->device));
+    if (int rc = launch_pairs(e, c, "bk_cohort_distances", row0, n_rows)) return rc;
+    const size_t block = (size_t)n_rows * c.n;
+    if (diff) BK_HIP(hipMemcpyAsync(diff, c.out.p, block * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    if (compared) BK_HIP(hipMemcpyAsync(compared, c.out.p + block, block * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
+    return BK_OK;
+}
+
+// diff and compared of the rows [row0, row0 + n_rows) against all columns into c.out, [2][n_rows][n], on the engine's stream: the
+// zeroing and cohort_pairs_kernel.  The rows lie inside the cohort (the callers' check).
+static int launch_pairs(bk_engine* e, Cohort& c, const char* who, uint64_t row0, uint64_t n_rows) {
     const size_t block = (size_t)n_rows * c.n;
     BK_HIP(grow(c.out, 2 * block, 0, e->stream));
     bk::PairsArgs a{};
     a.planes = c.planes.p; a.n = c.n; a.n_stride = c.n_stride; a.W = c.W; a.row0 = row0; a.n_rows = n_rows;
     a.n_col_tiles = (uint32_t)((c.n + bk::kTile - 1) / bk::kTile);
     const uint64_t n_row_tiles = (n_rows + bk::kTile - 1) / bk::kTile, tiles = n_row_tiles * a.n_col_tiles;
-    if (tiles > 0x7fffffffull) return fail(BK_ERR_INVALID, "bk_cohort_distances: n_rows = %llu is too many rows for one block of %llu columns", (unsigned long long)n_rows, (unsigned long long)c.n);
+    if (tiles > 0x7fffffffull) return fail(BK_ERR_INVALID, "%s: n_rows = %llu is too many rows for one block of %llu columns", who, (unsigned long long)n_rows, (unsigned long long)c.n);
     uint64_t slice_words, chunk = bk::kChunk;
     const char* forced = test_env("BK_COHORT_SLICE_WORDS");   // (testing build: small inputs cross slice and chunk borders)
     if (forced && atoi(forced) >= 1) {
@@ -203,8 +298,101 @@ int bk_cohort_distances(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* 
     const dim3 grid((unsigned)tiles, (unsigned)((c.W + slice_words - 1) / slice_words));
     hipLaunchKernelGGL(bk::cohort_pairs_kernel, grid, dim3(bk::kCohortBlock), 0, e->stream, a);
     BK_HIP(hipGetLastError());
-    if (diff) BK_HIP(hipMemcpyAsync(diff, a.diff, block * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
-    if (compared) BK_HIP(hipMemcpyAsync(compared, a.compared, block * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
-    BK_HIP(hipStreamSynchronize(e->stream));
+    return BK_OK;
+}
+
+// Boruvka by row blocks (the rule: include/bronko_hip.h).  Per round: for every block of rows the pairs kernel and the row-best kernel
+// over the block where it lies, then every component's least edge from the rows' bests (two launches over the n rows); the O(n)
+// component bests come down, the host merges them (a union-find whose root is the component's first sample) and the new labels go up.
+// Launch order on the engine's stream and the one synchronise per round carry every dependence.
+int bk_cohort_mst(bk_engine* e, uint32_t min_compared, bk_mst_edge* edges, uint64_t cap_edges, uint64_t* n_edges, bk_mst_nearest* nearest, uint32_t* rounds) {
+    if (!e) return fail(BK_ERR_INVALID, "bk_cohort_mst: e is null");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_cohort_mst inside a sample: it comes before bk_sample_begin or after the sample's downloads");
+    if (!e->cohort) return fail(BK_ERR_STATE, "bk_cohort_mst comes after bk_cohort_set");
+    Cohort& c = *e->cohort;
+    const uint64_t n = c.n;
+    if (!edges) return fail(BK_ERR_INVALID, "bk_cohort_mst: edges is null");
+    if (!n_edges) return fail(BK_ERR_INVALID, "bk_cohort_mst: n_edges is null");
+    if (cap_edges < n - 1) return fail(BK_ERR_INVALID, "bk_cohort_mst: cap_edges = %llu is less than the %llu edges a cohort of %llu samples may have", (unsigned long long)cap_edges, (unsigned long long)(n - 1), (unsigned long long)n);
+    *n_edges = 0;
+    if (rounds) *rounds = 0;
+    if (nearest)
+        for (uint64_t i = 0; i < n; i++) nearest[i] = bk_mst_nearest{0xffffffffu, 0, 0};
+    if (n == 1) return BK_OK;
+    BK_HIP(hipSetDevice(e->device));
+    if (c.mst_label.n < n) {
+        BK_HIP(c.mst_label.alloc((size_t)n)); BK_HIP(c.mst_row_key.alloc((size_t)n)); BK_HIP(c.mst_row_cmp.alloc((size_t)n));
+        BK_HIP(c.mst_comp_diff.alloc((size_t)n)); BK_HIP(c.mst_comp_pair.alloc((size_t)n));
+    }
+    // a block's two u32 arrays together stay under 256 MB, as the blocks of `bronko call --distances` do
+    uint64_t block_rows = std::max<uint64_t>(1, std::min<uint64_t>(n, (256ull << 20) / (8 * n)));
+    const char* forced = test_env("BK_COHORT_MST_BLOCK_ROWS");   // (testing build: small cohorts cross block borders)
+    if (forced && atoi(forced) >= 1) block_rows = std::min<uint64_t>(n, (uint64_t)atoi(forced));
+    uint32_t max_passes = 1;                                     // ceil(log2 n) + 1
+    while ((1ull << (max_passes - 1)) < n) max_passes++;
+
+    std::vector<uint32_t> parent((size_t)n), label((size_t)n), comp_diff((size_t)n), row_cmp((size_t)n);
+    std::vector<unsigned long long> comp_pair((size_t)n), row_key;
+    for (uint64_t i = 0; i < n; i++) parent[i] = (uint32_t)i;
+    auto find = [&parent](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    const unsigned n_groups = (unsigned)((n + bk::kCohortBlock - 1) / bk::kCohortBlock);
+    uint64_t n_found = 0, components = n;
+    uint32_t n_rounds = 0;
+    bool done = false;
+    for (uint32_t pass = 0; pass < max_passes && !done; pass++) {
+        for (uint64_t i = 0; i < n; i++) label[i] = find((uint32_t)i);
+        BK_HIP(hipMemcpyAsync(c.mst_label.p, label.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+        BK_HIP(hipMemsetAsync(c.mst_comp_diff.p, 0xff, (size_t)n * sizeof(unsigned int), e->stream));
+        BK_HIP(hipMemsetAsync(c.mst_comp_pair.p, 0xff, (size_t)n * sizeof(unsigned long long), e->stream));
+        for (uint64_t row0 = 0; row0 < n; row0 += block_rows) {
+            const uint64_t rows = std::min(block_rows, n - row0);
+            if (int rc = launch_pairs(e, c, "bk_cohort_mst", row0, rows)) return rc;
+            bk::RowBestArgs a{};
+            a.diff = c.out.p; a.compared = c.out.p + (size_t)rows * n; a.label = c.mst_label.p;
+            a.n = n; a.row0 = row0; a.n_rows = rows; a.need = std::max<uint32_t>(1, min_compared);
+            a.row_key = c.mst_row_key.p; a.row_cmp = c.mst_row_cmp.p;
+            hipLaunchKernelGGL(bk::cohort_row_best_kernel, dim3((unsigned)rows), dim3(bk::kCohortBlock), 0, e->stream, a);
+            BK_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(bk::cohort_comp_diff_kernel, dim3(n_groups), dim3(bk::kCohortBlock), 0, e->stream, c.mst_row_key.p, c.mst_label.p, n, c.mst_comp_diff.p);
+        BK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(bk::cohort_comp_pair_kernel, dim3(n_groups), dim3(bk::kCohortBlock), 0, e->stream, c.mst_row_key.p, c.mst_label.p, n, c.mst_comp_diff.p, c.mst_comp_pair.p);
+        BK_HIP(hipGetLastError());
+        BK_HIP(hipMemcpyAsync(comp_diff.data(), c.mst_comp_diff.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        BK_HIP(hipMemcpyAsync(comp_pair.data(), c.mst_comp_pair.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        BK_HIP(hipMemcpyAsync(row_cmp.data(), c.mst_row_cmp.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        if (pass == 0 && nearest) {                              // (with label[i] = i a row's best is its nearest)
+            row_key.resize((size_t)n);
+            BK_HIP(hipMemcpyAsync(row_key.data(), c.mst_row_key.p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+        }
+        BK_HIP(hipStreamSynchronize(e->stream));
+        if (pass == 0 && nearest)
+            for (uint64_t i = 0; i < n; i++)
+                if (row_key[i] != ~0ull) nearest[i] = bk_mst_nearest{(uint32_t)(row_key[i] & 0xffffffffull), (uint32_t)(row_key[i] >> 32), row_cmp[i]};
+        uint64_t added = 0;
+        for (uint64_t l = 0; l < n; l++) {                       // (label: the components' bests, of this round's labels)
+            if (label[l] != l || comp_pair[l] == ~0ull) continue;
+            const uint32_t lo = (uint32_t)(comp_pair[l] >> 32), hi = (uint32_t)(comp_pair[l] & 0xffffffffull);
+            if (lo >= hi || hi >= n || (label[lo] == l) == (label[hi] == l)) return fail(BK_ERR_INTERNAL, "bk_cohort_mst: a component's best edge does not leave it");
+            const uint32_t ra = find(lo), rb = find(hi);
+            if (ra == rb) continue;                              // (the edge was picked from both sides: it counts once)
+            if (n_found >= n - 1) return fail(BK_ERR_INTERNAL, "bk_cohort_mst: more than n - 1 edges");
+            parent[std::max(ra, rb)] = std::min(ra, rb);
+            edges[n_found++] = bk_mst_edge{lo, hi, comp_diff[l], row_cmp[label[lo] == l ? lo : hi]};
+            added++;
+        }
+        components -= added;
+        if (added) n_rounds++;
+        done = added == 0 || components == 1;
+    }
+    if (!done) return fail(BK_ERR_INTERNAL, "bk_cohort_mst: no end after ceil(log2 n) + 1 = %u rounds", max_passes);
+    std::sort(edges, edges + n_found, [](const bk_mst_edge& x, const bk_mst_edge& y) {
+        return x.diff != y.diff ? x.diff < y.diff : x.lo != y.lo ? x.lo < y.lo : x.hi < y.hi;
+    });
+    *n_edges = n_found;
+    if (rounds) *rounds = n_rounds;
     return BK_OK;
 }

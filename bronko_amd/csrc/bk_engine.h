@@ -3,7 +3,7 @@
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
 // packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
 // ride behind every scan: the k-mer dump, indels, linkage and the codon, haplotype and read-pileup counts over linkage's rows), bk_reports.cpp (the reports made of a pileup: calls, consensus, regions)
-// and bk_cohort.hip (the distances of a cohort of consensus sequences).
+// and bk_cohort.hip (the distances of a cohort of consensus sequences and its minimum spanning forest).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -369,6 +369,12 @@ struct Cohort {
     uint64_t n_stride = 0;                  // n rounded up to 64, plus 64: the padding samples are all zero
     DevBuf<unsigned long long> planes;      // [3][W][n_stride] valid, b0, b1
     DevBuf<unsigned int> out;               // [2][rows of the largest block so far][n] diff, compared
+    // bk_cohort_mst (allocated by its first call on this cohort; empty before)
+    DevBuf<unsigned int> mst_label;         // [n] a sample's component, named by the component's first sample
+    DevBuf<unsigned long long> mst_row_key; // [n] per row the least diff << 32 | j over the admissible columns of another component (~0: none)
+    DevBuf<unsigned int> mst_row_cmp;       // [n] ... and that pair's compared
+    DevBuf<unsigned int> mst_comp_diff;     // [n] per label the least diff of its rows' bests (~0: none)
+    DevBuf<unsigned long long> mst_comp_pair;   // [n] per label the least lo << 32 | hi among its rows' bests of that diff (~0: none)
 };
 
 // What bk_engine_create derives from the index and the table-shaping parameters (bk_index_tables.cpp): immutable once built, shared

@@ -708,6 +708,22 @@ class Engine:
         _check(self._L.bk_cohort_distances(self.h, int(row0), int(n_rows), diff.ctypes.data_as(C.c_void_p), compared.ctypes.data_as(C.c_void_p)), self._L)
         return diff[:int(n_rows), :n], compared[:int(n_rows), :n]
 
+    def cohort_mst(self, min_compared=0, nearest=True, rounds=True):
+        """bk_cohort_mst: the minimum spanning forest of the cohort under the edge order (diff, lo, hi) over the pairs that compared
+        at least max(1, min_compared) positions: (edges, nearest, rounds) -- edges an (E, 4) uint32 array of lo, hi, diff, compared,
+        ascending in the edge order; nearest an (n, 3) uint32 array of sample (0xffffffff: none), diff, compared; rounds the Boruvka
+        rounds that added an edge.  nearest=False / rounds=False pass NULL and return None there."""
+        n = int(getattr(self, "_cohort_n", 0))
+        cap = max(1, n)
+        edges = np.zeros((cap, 4), np.uint32)
+        near = np.zeros((cap, 3), np.uint32) if nearest else None
+        n_edges = C.c_uint64(0)
+        n_rounds = C.c_uint32(0)
+        _check(self._L.bk_cohort_mst(self.h, int(min_compared), edges.ctypes.data_as(C.POINTER(_ffi.MstEdge)), cap, C.byref(n_edges),
+                                     near.ctypes.data_as(C.POINTER(_ffi.MstNearest)) if nearest else None,
+                                     C.byref(n_rounds) if rounds else None), self._L)
+        return edges[:int(n_edges.value)], (near[:n] if nearest else None), (int(n_rounds.value) if rounds else None)
+
     def cohort_clear(self):
         """bk_cohort_clear: frees the cohort's device memory (fine without a cohort)."""
         _check(self._L.bk_cohort_clear(self.h), self._L)

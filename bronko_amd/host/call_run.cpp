@@ -871,6 +871,32 @@ struct CallRun {
         }
     }
 
+    // ---- --mst: the minimum spanning forest of the cohort the engine holds, found on the device; OUT/<genome>.mst.tsv ----
+    void write_forest(bk_engine* e, const std::string& gname, const std::vector<std::string>& names, uint64_t positions) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint64_t n = names.size();
+        const uint32_t min_compared = cohort_min_compared(a.mst_min_breadth, positions);
+        std::vector<bk_mst_edge> edges((size_t)(n - 1));
+        std::vector<bk_mst_nearest> nearest((size_t)n);
+        uint64_t n_edges = 0;
+        uint32_t rounds = 0;
+        hip_check(bk_cohort_mst(e, min_compared, edges.data(), edges.size(), &n_edges, nearest.data(), &rounds), "bk_cohort_mst");
+        CohortForest f;
+        try {
+            std::vector<CohortMstEdge> ev;
+            std::vector<CohortMstNearest> nr;
+            for (uint64_t k = 0; k < n_edges; k++) ev.push_back(CohortMstEdge{edges[k].lo, edges[k].hi, edges[k].diff, edges[k].compared});
+            for (const auto& x : nearest) nr.push_back(CohortMstNearest{x.sample, x.diff, x.compared});
+            f = root_forest(n, ev);
+            write_cohort_mst_tsv(a.output + "/" + gname + ".mst.tsv", names, f, nr, a.mst_min_breadth, min_compared);
+        } catch (const std::exception& ex) { die(T, ex.what()); }
+        char secs[32];
+        snprintf(secs, sizeof secs, "%.3f", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        LOG_INFO(T, "Forest for " + gname + ": " + std::to_string(n) + " samples, " + std::to_string(n_edges) + " edges, " + std::to_string(f.n_components) +
+                        " components, the largest of " + std::to_string(f.largest) + " samples, longest edge " + std::to_string(f.longest) + ", " +
+                        std::to_string(rounds) + " rounds (" + secs + " s)");
+    }
+
     // ---- --distances: the samples' consensus letters compared pair by pair, per selected genome, on one engine that is still alive ----
     void write_distances(bk_engine* e) {
         constexpr uint64_t kBlockBytes = 256ull << 20;   // a block's two host buffers together
@@ -927,6 +953,7 @@ struct CallRun {
                             std::to_string(empty_pairs) + " pairs with nothing compared" +
                             (a.has_clusters ? ", " + std::to_string(cl.n_clusters) + " clusters, the largest of " + std::to_string(cl.largest) + " samples" : std::string()) +
                             " (" + secs + " s)");
+            if (a.mst) write_forest(e, gname, names, positions);   // (the cohort is still set)
         }
         hip_check(bk_cohort_clear(e), "bk_cohort_clear");
     }

@@ -83,6 +83,7 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
           "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
           "            [--read-pileup-max-mismatches M] [--distances] [--clusters T] [--cluster-min-breadth B]\n"
+          "            [--mst] [--mst-min-breadth B]\n"
           "            [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
@@ -189,7 +190,12 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    bases are not compared; a genome that fewer than two samples selected gets no files\n"
           "  --clusters T      write single-linkage clusters to <DIR>/<genome>.clusters.tsv (needs --distances): two samples are linked when\n"
           "                    they differ at T positions or fewer and compared at least B of the genome's positions; at least 0\n"
-          "  --cluster-min-breadth B  share of the genome's positions a pair must have compared to be linked; 0..1, default 0.9\n", stderr);
+          "  --cluster-min-breadth B  share of the genome's positions a pair must have compared to be linked; 0..1, default 0.9\n"
+          "  --mst             write the minimum spanning forest of the distances to <DIR>/<genome>.mst.tsv (needs --distances): per sample its\n"
+          "                    parent towards its component's first sample, that edge's distance and compared positions, its component and\n"
+          "                    its nearest neighbour; a pair is an edge only if it compared at least one position and at least B of the\n"
+          "                    genome's; equally distant candidates are chosen by sample order; a forest of consensus distances, not a phylogeny\n"
+          "  --mst-min-breadth B  share of the genome's positions a pair must have compared to be an edge; 0..1, default 0.9\n", stderr);
     exit(code);
 }
 
@@ -384,6 +390,8 @@ Args parse_args(int argc, char** argv) {
         else if (opt == "--distances") a.distances = true;
         else if (opt == "--clusters") { a.clusters = any_long(opt, one()); a.has_clusters = true; }   // (any integer here: check_call_args)
         else if (opt == "--cluster-min-breadth") { a.cluster_min_breadth = to_double(opt, one()); a.has_cluster_min_breadth = true; }
+        else if (opt == "--mst") a.mst = true;
+        else if (opt == "--mst-min-breadth") { a.mst_min_breadth = to_double(opt, one()); a.has_mst_min_breadth = true; }
         else if (opt == "--hap-min-freq") { a.hap_min_freq = to_double(opt, one()); a.has_hap_min_freq = true; }
         else if (opt == "--codon-min-freq") { a.codon_min_freq = to_double(opt, one()); a.has_codon_min_freq = true; }
         else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
@@ -669,6 +677,13 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     if (!(a.cluster_min_breadth >= 0.0 && a.cluster_min_breadth <= 1.0)) {
         char buf[128];
         snprintf(buf, sizeof buf, "--cluster-min-breadth must be between 0 and 1, got %g", a.cluster_min_breadth);
+        die(T, buf);
+    }
+    if (a.mst && !a.distances) die(T, "--mst needs --distances");
+    if (a.has_mst_min_breadth && !a.mst) die(T, "--mst-min-breadth needs --mst");
+    if (!(a.mst_min_breadth >= 0.0 && a.mst_min_breadth <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "--mst-min-breadth must be between 0 and 1, got %g", a.mst_min_breadth);
         die(T, buf);
     }
 }

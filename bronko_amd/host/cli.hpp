@@ -128,6 +128,9 @@ struct Args {
     bool has_clusters = false, has_cluster_min_breadth = false;
     long clusters = 0;              // --clusters T: <DIR>/<genome>.clusters.tsv, single-linkage clusters of the samples at most T apart (needs --distances)
     double cluster_min_breadth = 0.9;   // --cluster-min-breadth B: share of the genome's positions a pair must have compared to be linked (0..1)
+    bool mst = false;               // --mst: <DIR>/<genome>.mst.tsv, the minimum spanning forest of the samples' distances (needs --distances)
+    bool has_mst_min_breadth = false;
+    double mst_min_breadth = 0.9;   // --mst-min-breadth B: share of the genome's positions a pair must have compared to be an edge (0..1)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;

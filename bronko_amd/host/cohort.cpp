@@ -3,7 +3,11 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
+#include <condition_variable>
 #include <cstring>
+#include <functional>
+#include <mutex>
 #include <numeric>
 #include <stdexcept>
 #include <thread>
@@ -25,14 +29,66 @@ void over_threads(uint64_t n, unsigned threads, F fn) {
     for (auto& t : th) t.join();
 }
 
-// one row against the columns [0, n): the hardware's population count where the target has one
+// The same split of [0, n) run again and again on threads that stay: a step of cohort_mst_host is one row, too short to start
+// threads for.  run(fn) returns when fn(begin, end) has returned for every part; the caller's thread takes the first part.
+class RangePool {
+public:
+    RangePool(uint64_t n, unsigned threads) {
+        const unsigned nt = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::max(1u, threads), n));
+        const uint64_t per = nt ? (n + nt - 1) / nt : 0;
+        for (unsigned i = 0; i < nt; i++) {
+            const uint64_t b = std::min(n, i * per), e = std::min(n, b + per);
+            if (i == 0) { b0_ = b; e0_ = e; }
+            else if (b < e) workers_.emplace_back([this, b, e] { work(b, e); });
+        }
+    }
+    ~RangePool() {
+        { std::lock_guard<std::mutex> g(m_); stop_ = true; }
+        start_.notify_all();
+        for (auto& t : workers_) t.join();
+    }
+    RangePool(const RangePool&) = delete;
+    RangePool& operator=(const RangePool&) = delete;
+    void run(const std::function<void(uint64_t, uint64_t)>& fn) {
+        { std::lock_guard<std::mutex> g(m_); fn_ = &fn; pending_ = workers_.size(); generation_++; }
+        start_.notify_all();
+        if (b0_ < e0_) fn(b0_, e0_);
+        std::unique_lock<std::mutex> g(m_);
+        done_.wait(g, [this] { return pending_ == 0; });
+    }
+private:
+    void work(uint64_t b, uint64_t e) {
+        uint64_t seen = 0;
+        for (;;) {
+            const std::function<void(uint64_t, uint64_t)>* fn;
+            {
+                std::unique_lock<std::mutex> g(m_);
+                start_.wait(g, [&] { return stop_ || generation_ != seen; });
+                if (stop_) return;
+                seen = generation_; fn = fn_;
+            }
+            (*fn)(b, e);
+            { std::lock_guard<std::mutex> g(m_); pending_--; }
+            done_.notify_one();
+        }
+    }
+    std::vector<std::thread> workers_;
+    std::mutex m_;
+    std::condition_variable start_, done_;
+    const std::function<void(uint64_t, uint64_t)>* fn_ = nullptr;
+    uint64_t generation_ = 0, b0_ = 0, e0_ = 0;
+    size_t pending_ = 0;
+    bool stop_ = false;
+};
+
+// one row against the columns [j0, j1): the hardware's population count where the target has one
 #if defined(__x86_64__)
 __attribute__((target("popcnt")))
 #endif
-void row_against_all(const CohortPlanes& p, uint64_t i, uint32_t* diff, uint32_t* compared) {
+void row_against_columns(const CohortPlanes& p, uint64_t i, uint64_t j0, uint64_t j1, uint32_t* diff, uint32_t* compared) {
     const uint64_t W = p.W;
     const uint64_t *vi = p.valid.data() + i * W, *b0i = p.b0.data() + i * W, *b1i = p.b1.data() + i * W;
-    for (uint64_t j = 0; j < p.n; j++) {
+    for (uint64_t j = j0; j < j1; j++) {
         const uint64_t *vj = p.valid.data() + j * W, *b0j = p.b0.data() + j * W, *b1j = p.b1.data() + j * W;
         uint64_t cmp = 0, dif = 0;
         for (uint64_t w = 0; w < W; w++) {
@@ -45,6 +101,7 @@ void row_against_all(const CohortPlanes& p, uint64_t i, uint32_t* diff, uint32_t
         if (diff) diff[j] = (uint32_t)dif;
     }
 }
+void row_against_all(const CohortPlanes& p, uint64_t i, uint32_t* diff, uint32_t* compared) { row_against_columns(p, i, 0, p.n, diff, compared); }
 
 }  // namespace
 
@@ -120,6 +177,114 @@ CohortClusters CohortClusterer::finish() {
         c.largest = std::max(c.largest, count[r]);
     }
     return c;
+}
+
+// ---- the minimum spanning forest --------------------------------------------------------------------------------------------------
+uint32_t cohort_min_compared(double min_breadth, uint64_t positions) {
+    const double need = min_breadth * (double)positions;
+    if (!(need > 0.0)) return 0;
+    if (need >= 4294967295.0) return 0xffffffffu;
+    return (uint32_t)std::ceil(need);       // (an integer below 2^32 is exact as a double: (double)c >= need iff c >= ceil(need))
+}
+
+CohortMst cohort_mst_host(const CohortPlanes& p, uint32_t min_compared, unsigned threads) {
+    const uint64_t n = p.n;
+    const uint32_t need = std::max<uint32_t>(1, min_compared);
+    CohortMst m;
+    m.nearest.assign((size_t)n, CohortMstNearest{kCohortNone, 0, 0});
+    std::vector<uint32_t> diff((size_t)n), cmp((size_t)n);
+    // per sample outside the tree its least edge into the tree, under (diff, lo, hi); lo = kCohortNone: none yet
+    std::vector<CohortMstEdge> best((size_t)n, CohortMstEdge{kCohortNone, kCohortNone, 0, 0});
+    std::vector<uint8_t> in_tree((size_t)n, 0);
+    auto less = [](const CohortMstEdge& x, const CohortMstEdge& y) {
+        return x.diff != y.diff ? x.diff < y.diff : x.lo != y.lo ? x.lo < y.lo : x.hi < y.hi;
+    };
+    RangePool pool(n, threads);             // (the columns of a row, split once)
+    uint64_t u = 0;
+    const std::function<void(uint64_t, uint64_t)> row = [&](uint64_t j0, uint64_t j1) { row_against_columns(p, u, j0, j1, diff.data(), cmp.data()); };
+    for (uint64_t first = 0; first < n; first++) {
+        if (in_tree[first]) continue;
+        u = first;                 // (a component's tree grows from its first sample)
+        for (;;) {
+            in_tree[u] = 1;
+            pool.run(row);
+            for (uint64_t j = 0; j < n; j++) {
+                if (j == u || cmp[j] < need) continue;
+                CohortMstNearest& nr = m.nearest[u];
+                if (nr.sample == kCohortNone || diff[j] < nr.diff) nr = CohortMstNearest{(uint32_t)j, diff[j], cmp[j]};   // (ascending j: the first of equals stays)
+                if (in_tree[j]) continue;
+                const CohortMstEdge e{(uint32_t)std::min(u, j), (uint32_t)std::max(u, j), diff[j], cmp[j]};
+                if (best[j].lo == kCohortNone || less(e, best[j])) best[j] = e;
+            }
+            uint64_t next = n;
+            for (uint64_t j = 0; j < n; j++)
+                if (!in_tree[j] && best[j].lo != kCohortNone && (next == n || less(best[j], best[next]))) next = j;
+            if (next == n) break;           // (nothing admissible leaves the tree: the component is whole)
+            m.edges.push_back(best[next]);
+            u = next;
+        }
+    }
+    std::sort(m.edges.begin(), m.edges.end(), less);
+    return m;
+}
+
+CohortForest root_forest(uint64_t n, const std::vector<CohortMstEdge>& edges) {
+    CohortForest f;
+    f.parent.assign((size_t)n, kCohortNone); f.diff.assign((size_t)n, 0); f.compared.assign((size_t)n, 0);
+    f.component.assign((size_t)n, 0); f.size.assign((size_t)n, 0);
+    std::vector<uint32_t> start((size_t)n + 1, 0), adj(2 * edges.size());   // the neighbours of a sample: the edges' indices
+    for (const auto& e : edges) {
+        if (e.lo >= e.hi || e.hi >= n) throw std::runtime_error("root_forest: an edge's samples must be lo < hi < n");
+        start[e.lo + 1]++; start[e.hi + 1]++;
+        f.longest = std::max(f.longest, e.diff);
+    }
+    for (uint64_t i = 0; i < n; i++) start[i + 1] += start[i];
+    std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+    for (size_t k = 0; k < edges.size(); k++) { adj[fill[edges[k].lo]++] = (uint32_t)k; adj[fill[edges[k].hi]++] = (uint32_t)k; }
+    std::vector<uint32_t> todo, members;
+    for (uint64_t root = 0; root < n; root++) {
+        if (f.component[root]) continue;    // (in input order: an unreached sample is its component's smallest)
+        const uint32_t number = ++f.n_components;
+        f.component[root] = number;
+        todo.assign(1, (uint32_t)root); members.clear();
+        while (!todo.empty()) {
+            const uint32_t i = todo.back();
+            todo.pop_back();
+            members.push_back(i);
+            for (uint32_t k = start[i]; k < start[i + 1]; k++) {
+                const CohortMstEdge& e = edges[adj[k]];
+                const uint32_t j = e.lo == i ? e.hi : e.lo;
+                if (j == f.parent[i]) continue;
+                if (f.component[j]) throw std::runtime_error("root_forest: the edges hold a cycle");
+                f.component[j] = number; f.parent[j] = i; f.diff[j] = e.diff; f.compared[j] = e.compared;
+                todo.push_back(j);
+            }
+        }
+        for (uint32_t i : members) f.size[i] = (uint32_t)members.size();
+        f.largest = std::max<uint32_t>(f.largest, (uint32_t)members.size());
+    }
+    return f;
+}
+
+void write_cohort_mst_tsv(const std::string& path, const std::vector<std::string>& names, const CohortForest& f, const std::vector<CohortMstNearest>& nearest,
+                          double min_breadth, uint32_t min_compared) {
+    const size_t n = names.size();
+    if (f.parent.size() != n || f.diff.size() != n || f.compared.size() != n || f.component.size() != n || f.size.size() != n || nearest.size() != n)
+        throw std::runtime_error("write_cohort_mst_tsv: one line per sample");
+    FILE* file = fopen(path.c_str(), "wb");
+    if (!file) throw std::runtime_error(std::string(strerror(errno)) + " | Failed to create spanning forest file " + path);
+    fprintf(file, "##mst_min_breadth=%g\n##mst_min_compared=%u\nsample\tparent\tdiff\tcompared\tcomponent\tsize\tnearest\tnearest_diff\tnearest_compared\n", min_breadth, min_compared);
+    for (size_t i = 0; i < n; i++) {
+        fprintf(file, "%s\t", names[i].c_str());
+        if (f.parent[i] == kCohortNone) fputs(".\t.\t.", file);
+        else if (f.parent[i] < n) fprintf(file, "%s\t%u\t%u", names[f.parent[i]].c_str(), f.diff[i], f.compared[i]);
+        else { fclose(file); throw std::runtime_error("write_cohort_mst_tsv: a parent beyond the samples"); }
+        fprintf(file, "\t%u\t%u\t", f.component[i], f.size[i]);
+        if (nearest[i].sample == kCohortNone) fputs(".\t.\t.\n", file);
+        else if (nearest[i].sample < n) fprintf(file, "%s\t%u\t%u\n", names[nearest[i].sample].c_str(), nearest[i].diff, nearest[i].compared);
+        else { fclose(file); throw std::runtime_error("write_cohort_mst_tsv: a nearest neighbour beyond the samples"); }
+    }
+    if (fclose(file) != 0) throw std::runtime_error(std::string(strerror(errno)) + " | Failed to write " + path);
 }
 
 // ---- writers --------------------------------------------------------------------------------------------------------------------

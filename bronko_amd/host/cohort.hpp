@@ -1,7 +1,9 @@
 // cohort.hpp -- --distances: the host twin of the engine's cohort kernels (bk_cohort.hip), the single-linkage clusterer and the writers
 // of OUT/<genome>.distances.tsv, .compared.tsv and .clusters.tsv.  The rule is stated in include/bronko_hip.h (bk_cohort_set) and
 // DESIGN.md section W; tests/cohort_ref.py restates it.  The `bronko` binary never computes distances here: the twin is the tests'
-// and the measurements' yardstick, the clusterer and the writers are the product's.
+// and the measurements' yardstick, the clusterer and the writers are the product's.  --mst: the twin of bk_cohort_mst (the same
+// split: the twin is a yardstick), the rooting of a forest's edges and the writer of OUT/<genome>.mst.tsv (DESIGN.md section Y;
+// tests/mst_ref.py restates the rule).
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -63,5 +65,34 @@ void write_cohort_distances_tsv(const std::string& path, const std::vector<std::
 void write_cohort_compared_tsv(const std::string& path, const std::vector<std::string>& names, const uint32_t* compared);    // [n][n]
 // OUT/<genome>.clusters.tsv: "##cluster_threshold=T", "##cluster_min_breadth=B" (%g), "sample<TAB>cluster<TAB>size", a line per sample in input order
 void write_cohort_clusters_tsv(const std::string& path, const std::vector<std::string>& names, const CohortClusters& c, uint64_t threshold, double min_breadth);
+
+// --mst --mst-min-breadth B: the cohort's minimum spanning forest (the rule: include/bronko_hip.h, bk_cohort_mst).  A pair i < j is
+// admissible iff compared >= 1 and compared >= min_compared; edges are ordered by (diff, i, j); the forest is the unique minimum
+// spanning forest of the admissible graph under that order; nearest[i] is the admissible j != i with the least (diff, j).
+constexpr uint32_t kCohortNone = 0xffffffffu;
+struct CohortMstEdge { uint32_t lo, hi, diff, compared; };          // lo < hi
+struct CohortMstNearest { uint32_t sample, diff, compared; };       // sample = kCohortNone: none
+struct CohortMst {
+    std::vector<CohortMstEdge> edges;       // ascending in the edge order
+    std::vector<CohortMstNearest> nearest;  // per sample
+};
+// the smallest integer c with (double)c >= min_breadth * (double)positions: the compare --clusters makes, as a count
+uint32_t cohort_min_compared(double min_breadth, uint64_t positions);
+// The twin of bk_cohort_mst, by another algorithm: Prim per component from the component's first sample, one row of the distances at
+// a time, always the least edge that leaves the tree under (diff, lo, hi).  O(n^2 W) time, O(n) memory.
+CohortMst cohort_mst_host(const CohortPlanes& p, uint32_t min_compared, unsigned threads);
+// The forest rooted: a component's root is its smallest sample, every other sample's parent is its neighbour on the path to the root;
+// components are numbered from 1 in the order of their first sample, as clusters are.
+struct CohortForest {
+    std::vector<uint32_t> parent, diff, compared;   // per sample: its parent (kCohortNone: a root) and the edge to it
+    std::vector<uint32_t> component, size;          // per sample: its component's number and size
+    uint32_t n_components = 0, largest = 0, longest = 0;   // longest: the largest diff of an edge
+};
+CohortForest root_forest(uint64_t n, const std::vector<CohortMstEdge>& edges);
+// OUT/<genome>.mst.tsv: "##mst_min_breadth=B" (%g), "##mst_min_compared=C", "sample parent diff compared component size nearest
+// nearest_diff nearest_compared" (tab-separated), a line per sample in input order; "." for a root's parent, diff and compared and
+// for the three nearest columns of a sample without a nearest neighbour
+void write_cohort_mst_tsv(const std::string& path, const std::vector<std::string>& names, const CohortForest& f, const std::vector<CohortMstNearest>& nearest,
+                          double min_breadth, uint32_t min_compared);
 
 }  // namespace bronko

@@ -654,6 +654,42 @@ int bh_write_cohort_compared_tsv(const char* path, const char* names, const uint
     try { bronko::write_cohort_compared_tsv(path, split_lines(names), compared); return 0; }
     catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
+// --mst: the twin of bk_cohort_mst (Prim), the rooting and the writer.  edges: [n - 1][4] lo, hi, diff, compared; nearest: [n][3] sample,
+// diff, compared; either may be null
+uint32_t bh_cohort_min_compared(double min_breadth, uint64_t positions) { return bronko::cohort_min_compared(min_breadth, positions); }
+int bh_cohort_mst(const uint8_t* letters, uint64_t n, uint64_t positions, uint32_t min_compared, uint32_t threads, uint32_t* edges, uint64_t* n_edges, uint32_t* nearest) {
+    try {
+        if (!letters || !n_edges) throw std::runtime_error("bh_cohort_mst: letters or n_edges is null");
+        const bronko::CohortMst m = bronko::cohort_mst_host(bronko::cohort_pack_host(letters, n, positions, threads), min_compared, threads);
+        *n_edges = m.edges.size();
+        for (size_t k = 0; edges && k < m.edges.size(); k++) { edges[4 * k] = m.edges[k].lo; edges[4 * k + 1] = m.edges[k].hi; edges[4 * k + 2] = m.edges[k].diff; edges[4 * k + 3] = m.edges[k].compared; }
+        for (size_t i = 0; nearest && i < m.nearest.size(); i++) { nearest[3 * i] = m.nearest[i].sample; nearest[3 * i + 1] = m.nearest[i].diff; nearest[3 * i + 2] = m.nearest[i].compared; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+static std::vector<bronko::CohortMstEdge> mst_edges_of(const uint32_t* edges, uint64_t n_edges) {
+    std::vector<bronko::CohortMstEdge> ev((size_t)n_edges);
+    for (size_t k = 0; k < ev.size(); k++) ev[k] = bronko::CohortMstEdge{edges[4 * k], edges[4 * k + 1], edges[4 * k + 2], edges[4 * k + 3]};
+    return ev;
+}
+// parent, diff, compared, component, size: [n]; stats: components, the largest's size, the longest edge
+int bh_cohort_root_forest(uint64_t n, const uint32_t* edges, uint64_t n_edges, uint32_t* parent, uint32_t* diff, uint32_t* compared, uint32_t* component, uint32_t* size, uint32_t* stats) {
+    try {
+        const bronko::CohortForest f = bronko::root_forest(n, mst_edges_of(edges, n_edges));
+        for (uint64_t i = 0; i < n; i++) { parent[i] = f.parent[i]; diff[i] = f.diff[i]; compared[i] = f.compared[i]; component[i] = f.component[i]; size[i] = f.size[i]; }
+        if (stats) { stats[0] = f.n_components; stats[1] = f.largest; stats[2] = f.longest; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int bh_write_cohort_mst_tsv(const char* path, const char* names, const uint32_t* edges, uint64_t n_edges, const uint32_t* nearest, double min_breadth, uint32_t min_compared) {
+    try {
+        const std::vector<std::string> nm = split_lines(names);
+        std::vector<bronko::CohortMstNearest> nr(nm.size());
+        for (size_t i = 0; i < nr.size(); i++) nr[i] = bronko::CohortMstNearest{nearest[3 * i], nearest[3 * i + 1], nearest[3 * i + 2]};
+        bronko::write_cohort_mst_tsv(path, nm, bronko::root_forest(nm.size(), mst_edges_of(edges, n_edges)), nr, min_breadth, min_compared);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
 int bh_write_cohort_clusters_tsv(const char* path, const char* names, const uint32_t* cluster, const uint32_t* size, uint64_t threshold, double min_breadth) {
     try {
         const std::vector<std::string> nm = split_lines(names);

@@ -794,7 +794,56 @@ def _cohort_lib():
         "bh_cohort_clusters": [u64, u64, vp, vp, u64, C.c_double, u64, vp, vp, vp],
         "bh_write_cohort_distances_tsv": [C.c_char_p, C.c_char_p, vp],
         "bh_write_cohort_compared_tsv": [C.c_char_p, C.c_char_p, vp],
-        "bh_write_cohort_clusters_tsv": [C.c_char_p, C.c_char_p, vp, vp, u64, C.c_double]})
+        "bh_write_cohort_clusters_tsv": [C.c_char_p, C.c_char_p, vp, vp, u64, C.c_double],
+        "bh_cohort_min_compared": [C.c_double, u64],
+        "bh_cohort_mst": [vp, u64, u64, u32, u32, vp, vp, vp],
+        "bh_cohort_root_forest": [u64, vp, u64, vp, vp, vp, vp, vp, vp],
+        "bh_write_cohort_mst_tsv": [C.c_char_p, C.c_char_p, vp, u64, vp, C.c_double, u32]})
+
+
+def cohort_min_compared(min_breadth, positions):
+    """The smallest integer c with float(c) >= min_breadth * float(positions) (cohort.cpp cohort_min_compared): --mst-min-breadth as a count."""
+    L = _cohort_lib()
+    L.bh_cohort_min_compared.restype = C.c_uint32
+    return int(L.bh_cohort_min_compared(float(min_breadth), int(positions)))
+
+
+def cohort_mst(letters, min_compared=0, threads=4):
+    """The host twin of bk_cohort_mst (cohort.cpp cohort_mst_host: Prim per component): (edges, nearest) of an (n_samples, positions)
+    uint8 array of letters -- an (E, 4) uint32 array of lo, hi, diff, compared, ascending in the edge order, and an (n, 3) uint32
+    array of sample (0xffffffff: none), diff, compared."""
+    L = _cohort_lib()
+    a = np.ascontiguousarray(letters, np.uint8)
+    n, positions = a.shape
+    edges = np.zeros((max(1, n), 4), np.uint32)
+    nearest = np.zeros((max(1, n), 3), np.uint32)
+    n_edges = C.c_uint64(0)
+    if L.bh_cohort_mst(a.ctypes.data, n, positions, int(min_compared), int(threads), edges.ctypes.data, C.addressof(n_edges), nearest.ctypes.data) != 0:
+        raise _host_error(L)
+    return edges[:int(n_edges.value)], nearest[:n]
+
+
+def cohort_root_forest(n, edges):
+    """cohort.cpp root_forest: (parent, diff, compared, component, size, n_components, largest, longest) of a forest's (E, 4) edges; a
+    root's parent is 0xffffffff."""
+    L = _cohort_lib()
+    e = np.ascontiguousarray(edges, np.uint32).reshape(-1, 4)
+    out = [np.zeros(max(1, n), np.uint32) for _ in range(5)]
+    stats = np.zeros(3, np.uint32)
+    if L.bh_cohort_root_forest(int(n), e.ctypes.data, len(e), *[o.ctypes.data for o in out], stats.ctypes.data) != 0:
+        raise _host_error(L)
+    return tuple(o[:n] for o in out) + tuple(int(v) for v in stats)
+
+
+def write_cohort_mst_tsv(path, names, edges, nearest, min_breadth, min_compared):
+    """The --mst writer (cohort.cpp root_forest and write_cohort_mst_tsv): OUT/<genome>.mst.tsv of a forest's edges and the nearest neighbours."""
+    L = _cohort_lib()
+    e = np.ascontiguousarray(edges, np.uint32).reshape(-1, 4)
+    nr = np.ascontiguousarray(nearest, np.uint32).reshape(-1, 3)
+    if len(nr) != len(names):
+        raise ValueError("write_cohort_mst_tsv: one nearest neighbour per sample")
+    if L.bh_write_cohort_mst_tsv(path.encode(), "\n".join(names).encode(), e.ctypes.data, len(e), nr.ctypes.data, float(min_breadth), int(min_compared)) != 0:
+        raise _host_error(L)
 
 
 def cohort_distances(letters, row0=0, n_rows=None, threads=4):

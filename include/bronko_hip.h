@@ -39,7 +39,8 @@ typedef enum {
     BK_ERR_HIP = -3,       /* a HIP runtime call failed                    */
     BK_ERR_UNSUPPORTED = -4,
     BK_ERR_STATE = -5,     /* call order violated (e.g. push before begin) */
-    BK_ERR_RANGE = -6      /* a counter did not fit the width its plane was exchanged at (bk_shard_transport) */
+    BK_ERR_RANGE = -6,     /* a counter did not fit the width its plane was exchanged at (bk_shard_transport) */
+    BK_ERR_INTERNAL = -7   /* an invariant of the library did not hold (bk_cohort_mst past its round bound); additive, still v8 */
 } bk_status;
 
 /* build.rs:52-60  `#[repr(C)] struct BucketInfo` -- same field order, same layout (12 bytes) */
@@ -1060,6 +1061,35 @@ int  bk_sample_download_read_pileup(bk_engine* e, bk_read_pileup_summary* summar
 int  bk_cohort_set(bk_engine* e, const uint8_t* letters, uint64_t n_samples, uint64_t positions);
 int  bk_cohort_distances(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* diff, uint32_t* compared);
 int  bk_cohort_clear(bk_engine* e);
+
+/* ---- the cohort's minimum spanning forest (`bronko call --distances --mst`; additive, still v8) ------------------------------------
+ * Who is next to whom: the minimum spanning forest of the cohort bk_cohort_set holds, found on the device by Boruvka rounds over
+ * row blocks; nothing of size n^2 leaves the device or is ever held.  The rule, all of it integer arithmetic, over diff[i][j] and
+ * compared[i][j] as defined above and one parameter min_compared (u32):
+ *   admissible  a pair {i, j}, i < j, is admissible iff compared[i][j] >= 1 and compared[i][j] >= min_compared.  The >= 1 is on
+ *               purpose: a pair that shares no base is never "0 apart", even with min_compared = 0.
+ *   edge order  edges are ordered by (diff, i, j), lexicographically: a strict total order, there are no ties.
+ *   forest      the minimum spanning forest of the admissible graph under that order: the set Kruskal's algorithm keeps when it takes
+ *               the admissible edges in ascending order and skips any edge whose ends are already connected.  It is unique, whatever
+ *               algorithm finds it.
+ *   nearest     nearest[i] is the admissible j != i with the least (diff[i][j], j), or none (sample = 0xffffffff, diff = compared = 0).
+ *   rounds      the number of Boruvka rounds in which at least one edge was added: in a round every component picks its least
+ *               outgoing admissible edge under the edge order and all picked edges are merged.  Deterministic given the order; at
+ *               most ceil(log2 n) + 1.
+ *   bk_cohort_mst  between samples only (BK_ERR_STATE inside one); BK_ERR_STATE without a cohort.  Writes the forest's edges, ascending
+ *               in the edge order, lo < hi, and their number to *n_edges; nearest (n entries) and rounds where they are not NULL.
+ *               BK_ERR_INVALID, with the parameter named: a null edges or n_edges; cap_edges < n - 1 (nothing is written).  n = 1
+ *               gives 0 edges and 0 rounds.  Per round and block of rows (sized so that the block's two u32 arrays stay under
+ *               256 MB): cohort_pairs_kernel into the cohort's output block, cohort_row_best_kernel over the block where it lies
+ *               (per row the least diff << 32 | j over the admissible columns of another component), then two O(n) launches for
+ *               every component's least edge; the host merges the O(n) component bests (a union-find) and uploads the new labels.
+ *               One synchronise per round.  The cohort stays as it was: bk_cohort_distances afterwards gives the same blocks.
+ *               Its buffers (28 bytes per sample) are allocated by the first call and freed with the cohort: an engine that never
+ *               calls it allocates and launches nothing. */
+typedef struct { uint32_t lo, hi, diff, compared; } bk_mst_edge;        /* lo < hi */
+typedef struct { uint32_t sample, diff, compared; } bk_mst_nearest;     /* sample = 0xffffffff: none */
+int  bk_cohort_mst(bk_engine* e, uint32_t min_compared, bk_mst_edge* edges, uint64_t cap_edges, uint64_t* n_edges,
+                   bk_mst_nearest* nearest /* [n_samples] or NULL */, uint32_t* rounds /* or NULL */);
 
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k
