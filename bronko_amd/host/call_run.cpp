@@ -1,11 +1,13 @@
 // call_run.cpp -- one `bronko call` behind its checked arguments: the index, the engines on the GPUs, the lanes that whole samples
 // are dealt to (or one sample over several GPUs), and the per-sample code (reference: src/call.rs:151-402, per-sample orchestration).
 // The k-mer counting + map_kmers stages of the per-sample loop run on the GPU through the C ABI of include/bronko_hip.h; everything
-// else here is host code.
+// else here is host code.  A per-sample report is one unit here: the six anchor passes a description each, over which
+// every stage of a sample is one template; the other seven a group of functions each (resolve, launch, download, write-and-log).
 #include <cerrno>
 #include <cstring>
 #include <stdexcept>
 #include <thread>
+#include <tuple>
 
 #include <sys/stat.h>
 #include <unistd.h>
@@ -190,53 +192,17 @@ std::vector<int> devices_from_env() {
 // the counter planes are reduce-scattered by RCCL (sharded_finalize above).  BRONKO_SHARD=1 / 0 forces / forbids it (1 with a single
 // GPU runs every collective on a communicator of one rank).  The shard count is a power of two (it divides 64).
 // Returns the GPUs a sample is sharded over; none: whole samples go to lanes.
-std::vector<int> plan_shards(const Args& a, const std::vector<int>& devices, size_t n_samples) {
+std::vector<const char*> one_file_reports(const CallConfig& cfg);   // (below, with the report units)
+std::vector<int> plan_shards(const Args& a, const CallConfig& cfg, const std::vector<int>& devices, size_t n_samples) {
     std::vector<int> shard_devices;
     for (int d : devices) if (std::find(shard_devices.begin(), shard_devices.end(), d) == shard_devices.end()) shard_devices.push_back(d);
     bool shard_mode = shard_devices.size() >= 2 && n_samples < shard_devices.size();
     if (const char* sh = getenv("BRONKO_SHARD")) shard_mode = atoi(sh) != 0;
-    if (shard_mode && a.keep_kmer_info) {   // (the k-mer counts of a sample are one engine's: whole samples go to the GPUs in turn)
-        LOG_DEBUG(T, "--keep-kmer-info: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.indels) {           // (likewise: a sample's events and span array are one engine's)
-        LOG_DEBUG(T, "--indels: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.junctions) {        // (likewise)
-        LOG_DEBUG(T, "--junctions: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.copybacks) {        // (likewise)
-        LOG_DEBUG(T, "--copybacks: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.chimeras) {         // (likewise)
-        LOG_DEBUG(T, "--chimeras: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.breakends) {        // (likewise)
-        LOG_DEBUG(T, "--breakends: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.duplications) {     // (likewise)
-        LOG_DEBUG(T, "--duplications: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.linkage) {          // (likewise: a sample's row store is one engine's)
-        LOG_DEBUG(T, "--linkage: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.has_codons) {       // (likewise)
-        LOG_DEBUG(T, "--codons: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.haps()) {           // (likewise)
-        LOG_DEBUG(T, "--haplotypes: samples are not sharded over GPUs, each sample's reads go to one GPU");
-        shard_mode = false;
-    }
-    if (shard_mode && a.read_pileup) {      // (likewise)
-        LOG_DEBUG(T, "--read-pileup: samples are not sharded over GPUs, each sample's reads go to one GPU");
+    // (the k-mer counts of a sample are one engine's, and so are its events, span arrays and row store: whole samples go to the GPUs in turn)
+    std::vector<const char*> whole = one_file_reports(cfg);
+    if (a.keep_kmer_info) whole.insert(whole.begin(), "--keep-kmer-info");
+    if (shard_mode && !whole.empty()) {
+        LOG_DEBUG(T, std::string(whole[0]) + ": samples are not sharded over GPUs, each sample's reads go to one GPU");
         shard_mode = false;
     }
     { size_t S = 1; while (S * 2 <= std::min<size_t>(shard_devices.size(), 64)) S *= 2; shard_devices.resize(S); }
@@ -252,7 +218,130 @@ void release_lanes(std::vector<Lane>& lanes) {
     for (auto& t : th) t.join();
 }
 
-// ---- the run ---------------------------------------------------------------------------------------------------------------------
+// ---- the per-sample report units ---------------------------------------------------------------------------------------------------
+// One table of a sample's rows as a report brings it back from the device: its summary and its rows, in the host's struct
+template <class Summ, class Row>
+struct Rows { Summ summ{}; std::vector<Row> rows; };
+
+// ... by a first download for the summary, of which `count` is the rows' number, then that many rows.  Row is the host's struct for
+// the engine's record Rec
+template <class Summ, class Rec, class Row>
+void download_rows(bk_engine* e, int (*download)(bk_engine*, Summ*, Rec*, uint64_t), const char* name, Rows<Summ, Row>& t, const uint64_t& count) {
+    static_assert(sizeof(Row) == sizeof(Rec), "the host's struct is the engine's record");
+    hip_check(download(e, &t.summ, nullptr, 0), name);
+    t.rows.resize((size_t)count);
+    hip_check(download(e, &t.summ, reinterpret_cast<Rec*>(t.rows.data()), t.rows.size()), name);
+}
+
+constexpr uint32_t kHapTableLog2 = 16, kHapTableLog2Max = 24;   // --haplotypes: the table's first size (768 KB + 2.5 MB of entries); four times as many slots after each that was full
+constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
+constexpr uint32_t kEventTableLog2 = 18;  // the anchor passes: slots of an engine's event table (a sample with more distinct candidate events is an error)
+constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
+
+// The six anchor passes, one description each (the engine's side of them: bk_riders.cpp): the pass's C types and the host's row, its
+// three entry points with their names for hip_check, its switch, config and params out of CallConfig, its option (an index of one
+// genome file; no sharding), its file's suffix, its log sentence and its writer.  The stages of CallRun are one template each over these.
+#define BK_PASS(noun, Row_, switch_, enable_, report_, download_)                                                                                      \
+    using Config = bk_##noun##_config; using Params = bk_##noun##_params; using Summary = bk_##noun##_summary; using Row = Row_;                   \
+    static constexpr auto enable = enable_, report = report_; static constexpr auto download = download_;                                       \
+    static constexpr const char *enable_name = #enable_, *report_name = #report_, *download_name = #download_;                                     \
+    static bool on(const CallConfig& c) { return c.switch_; }
+inline std::string num(uint64_t x) { return std::to_string(x); }
+struct IndelPass {
+    BK_PASS(indel, IndelEvent, indels, bk_indels_enable, bk_sample_indels, bk_sample_download_indels);
+    static constexpr const char *option = "--indels", *suffix = ".indels.vcf";
+    static Config config(const CallConfig& c) { return {c.indel.max_len, c.indel.max_mismatches, kEventTableLog2}; }
+    static Params params(const CallConfig& c) { return {c.indel.min_reads, c.indel.min_af_ppm}; }
+    static std::string sentence(const Summary& s) {
+        return "Indels: " + num(s.anchored) + " of " + num(s.records) + " records anchored, " + num(s.ref_spanning) + " reference-spanning, " + num(s.supporting) +
+               " supporting, " + num(s.candidates) + " candidate events, " + num(s.reported) + " reported";
+    }
+    static void write(const std::string& path, const std::string& reads, const Index& ix, int best, const Rows<Summary, Row>& t, const CallConfig& c) { write_indels_vcf(path, reads, ix, best, t.rows, c.indel); }
+};
+struct JunctionPass {
+    BK_PASS(junction, JunctionEvent, junctions, bk_junctions_enable, bk_sample_junctions, bk_sample_download_junctions);
+    static constexpr const char *option = "--junctions", *suffix = ".junctions.tsv";
+    static Config config(const CallConfig& c) { return {c.junction.min_len, c.junction.max_mismatches, kEventTableLog2}; }
+    static Params params(const CallConfig& c) { return {c.junction.min_reads}; }
+    static std::string sentence(const Summary& s) {
+        return "Junctions: " + num(s.anchored) + " of " + num(s.records) + " records anchored, " + num(s.ref_spanning) + " reference-spanning, " + num(s.supporting) +
+               " supporting, " + num(s.short_) + " short, " + num(s.backward) + " backward, " + num(s.discordant) + " discordant, " + num(s.candidates) +
+               " candidate junctions, " + num(s.reported) + " reported";
+    }
+    static void write(const std::string& path, const std::string&, const Index& ix, int best, const Rows<Summary, Row>& t, const CallConfig& c) { write_junctions_tsv(path, ix, best, t.rows, c.junction); }
+};
+struct CopybackPass {
+    BK_PASS(copyback, CopybackEvent, copybacks, bk_copybacks_enable, bk_sample_copybacks, bk_sample_download_copybacks);
+    static constexpr const char *option = "--copybacks", *suffix = ".copybacks.tsv";
+    static Config config(const CallConfig& c) { return {c.copyback.max_mismatches, kEventTableLog2}; }
+    static Params params(const CallConfig& c) { return {c.copyback.min_reads, c.copyback.min_dist}; }
+    static std::string sentence(const Summary& s) {
+        return "Copy-backs: " + num(s.records) + " records, " + num(s.same_strand) + " on one strand, " + num(s.ref_spanning) + " reference-spanning, " + num(s.switched) +
+               " switched, " + num(s.supporting) + " supporting, " + num(s.discordant) + " discordant, " + num(s.candidates) + " candidate copy-backs, " + num(s.reported) +
+               " reported";
+    }
+    static void write(const std::string& path, const std::string&, const Index& ix, int best, const Rows<Summary, Row>& t, const CallConfig& c) { write_copybacks_tsv(path, ix, best, t.rows, c.copyback); }
+};
+struct ChimeraPass {   // (a genome file of one sequence: the headers alone)
+    BK_PASS(chimera, ChimeraEvent, chimeras, bk_chimeras_enable, bk_sample_chimeras, bk_sample_download_chimeras);
+    static constexpr const char *option = "--chimeras", *suffix = ".chimeras.tsv";
+    static Config config(const CallConfig& c) { return {c.chimera.max_mismatches, kEventTableLog2}; }
+    static Params params(const CallConfig& c) { return {c.chimera.min_reads}; }
+    static std::string sentence(const Summary& s) {
+        return "Chimeras: " + num(s.records) + " records, " + num(s.same_strand) + " on one strand of one sequence, " + num(s.ref_spanning) + " reference-spanning, " +
+               num(s.crossed) + " crossed, " + num(s.supporting) + " supporting, " + num(s.discordant) + " discordant, " + num(s.candidates) + " candidate chimeras, " +
+               num(s.reported) + " reported";
+    }
+    static void write(const std::string& path, const std::string&, const Index& ix, int best, const Rows<Summary, Row>& t, const CallConfig& c) { write_chimeras_tsv(path, ix, best, t.rows, c.chimera, t.summ.supporting, t.summ.ref_spanning); }
+};
+struct BreakendPass {
+    BK_PASS(breakend, BreakendEvent, breakends, bk_breakends_enable, bk_sample_breakends, bk_sample_download_breakends);
+    static constexpr const char *option = "--breakends", *suffix = ".breakends.tsv";
+    static Config config(const CallConfig& c) { return {c.breakend.min_clip, c.breakend.max_mismatches, kEventTableLog2}; }
+    static Params params(const CallConfig& c) { return {c.breakend.min_reads}; }
+    static std::string sentence(const Summary& s) {
+        return "Breakends: " + num(s.records) + " records, " + num(s.one_anchor) + " with one anchor, " + num(s.ref_spanning) + " reference-spanning, " + num(s.supporting) +
+               " supporting, " + num(s.short_) + " short, " + num(s.through) + " through, " + num(s.discordant) + " discordant, " + num(s.unplaced) + " unplaced, " +
+               num(s.candidates) + " candidate breakends, " + num(s.reported) + " reported";
+    }
+    static void write(const std::string& path, const std::string&, const Index& ix, int best, const Rows<Summary, Row>& t, const CallConfig& c) {
+        const Summary& s = t.summ;
+        BreakendTallies bt;
+        bt.records = s.records; bt.one_anchor = s.one_anchor; bt.ref_spanning = s.ref_spanning; bt.supporting = s.supporting; bt.short_ = s.short_;
+        bt.through = s.through; bt.discordant = s.discordant; bt.unplaced = s.unplaced; bt.candidates = s.candidates; bt.reported = s.reported;
+        write_breakends_tsv(path, ix, best, t.rows, c.breakend, bt);
+    }
+};
+struct DuplicationPass {
+    BK_PASS(duplication, DuplicationEvent, duplications, bk_duplications_enable, bk_sample_duplications, bk_sample_download_duplications);
+    static constexpr const char *option = "--duplications", *suffix = ".duplications.tsv";
+    static Config config(const CallConfig& c) { return {c.duplication.min_len, c.duplication.max_mismatches, kEventTableLog2}; }
+    static Params params(const CallConfig& c) { return {c.duplication.min_reads}; }
+    static std::string sentence(const Summary& s) {
+        return "Duplications: " + num(s.anchored) + " of " + num(s.records) + " records anchored, " + num(s.ref_spanning) + " reference-spanning, " + num(s.supporting) +
+               " supporting, " + num(s.short_) + " short, " + num(s.forward) + " forward, " + num(s.discordant) + " discordant, " + num(s.candidates) +
+               " candidate duplications, " + num(s.reported) + " reported";
+    }
+    static void write(const std::string& path, const std::string&, const Index& ix, int best, const Rows<Summary, Row>& t, const CallConfig& c) { write_duplications_tsv(path, ix, best, t.rows, c.duplication); }
+};
+using AnchorPasses = std::tuple<IndelPass, JunctionPass, CopybackPass, ChimeraPass, BreakendPass, DuplicationPass>;   // as they launch and are written
+template <class F>
+void each_anchor_pass(F&& f) { std::apply([&](auto... p) { (f(p), ...); }, AnchorPasses{}); }   // f(P{}) for every pass P, in that order
+template <class P> using PassRows = Rows<typename P::Summary, typename P::Row>;
+template <class... P> std::tuple<PassRows<P>...> rows_of(std::tuple<P...>);
+
+// the reports that count a sample's reads against the cells of one genome file (a k-mer's cell in the engine's table is its first among
+// all files, not the selected genome's), on the one engine that holds their tables: the options that are on, in the order they are named
+std::vector<const char*> one_file_reports(const CallConfig& cfg) {
+    std::vector<const char*> on;
+    each_anchor_pass([&](auto p) { if (p.on(cfg)) on.push_back(p.option); });
+    if (cfg.linkage) on.push_back("--linkage");
+    if (cfg.codons()) on.push_back("--codons");
+    if (cfg.haps()) on.push_back("--haplotypes");
+    if (cfg.read_pileup) on.push_back("--read-pileup");
+    return on;
+}
+
 // what a sample's completion brings back from the device
 struct SampleData {
     Pileup p;                                             // depth planes under --pileup; stats and present summed over the mates
@@ -260,54 +349,17 @@ struct SampleData {
     std::vector<uint8_t> present;
     bk_call_summary summ{};
     std::vector<bk_call_record> recs;
-    bk_consensus_summary csumm{};                         // --consensus
-    std::vector<uint8_t> letters;
-    bk_region_summary rsumm{};                            // --regions, --region-window
-    std::vector<bk_region_depth> rrows;
-    bk_indel_summary isumm{};                             // --indels
-    std::vector<IndelEvent> indels;
-    bk_consensus_indel_summary cisumm{};                  // --consensus-indels
-    std::vector<ConsensusIndel> cons_indels;
-    bk_junction_summary jsumm{};                          // --junctions
-    std::vector<JunctionEvent> junctions;
-    bk_copyback_summary cbsumm{};                         // --copybacks
-    std::vector<CopybackEvent> copybacks;
-    bk_chimera_summary chsumm{};                          // --chimeras
-    std::vector<ChimeraEvent> chimeras;
-    bk_breakend_summary besumm{};                         // --breakends
-    std::vector<BreakendEvent> breakends;
-    bk_duplication_summary dpsumm{};                      // --duplications
-    std::vector<DuplicationEvent> duplications;
-    bk_link_summary lsumm{};                              // --linkage
-    std::vector<LinkSite> link_recs;
-    std::vector<LinkPair> link_pairs;
-    bk_codon_summary csumm2{};                            // --codons
-    std::vector<uint32_t> codon_counts;
-    bk_hap_summary hsumm{};                               // --haplotypes
+    Rows<bk_consensus_summary, uint8_t> consensus;        // --consensus: the letters
+    Rows<bk_consensus_indel_summary, ConsensusIndel> cons_indels;   // --consensus-indels
+    Rows<bk_region_summary, bk_region_depth> regions;     // --regions, --region-window
+    decltype(rows_of(AnchorPasses{})) events;             // the anchor passes: a PassRows<P> each
+    Rows<bk_link_summary, LinkPair> linkage;              // --linkage
+    std::vector<LinkSite> link_sites;                     // ... and the sample's VCF records its pairs are of
+    Rows<bk_codon_summary, uint32_t> codons;              // --codons: 64 counts a codon
+    bk_hap_summary hap_summ{};                            // --haplotypes
     HapTable hap_table;
-    bk_read_pileup_summary psumm{};                       // --read-pileup
-    std::vector<ReadPileupCell> read_cells;
+    Rows<bk_read_pileup_summary, ReadPileupCell> read_pileup;   // --read-pileup
 };
-
-constexpr uint32_t kHapTableLog2 = 16, kHapTableLog2Max = 24;   // --haplotypes: the table's first size (768 KB + 2.5 MB of entries); four times as many slots after each that was full
-constexpr uint64_t kLinkInitialRows = 1ull << 20;   // --linkage: first capacity of an engine's row store (32 MB; it doubles as a sample needs)
-constexpr uint32_t kIndelTableLog2 = 18;  // --indels: slots of an engine's event table (a sample with more distinct candidate events is an error)
-constexpr uint32_t kJunctionTableLog2 = 18;   // --junctions: likewise
-constexpr uint32_t kCopybackTableLog2 = 18;   // --copybacks: likewise
-constexpr uint32_t kChimeraTableLog2 = 18;    // --chimeras: likewise
-constexpr uint32_t kBreakendTableLog2 = 18;   // --breakends: likewise
-constexpr uint32_t kDuplicationTableLog2 = 18;   // --duplications: likewise
-constexpr uint32_t kDumpTableLog2 = 24;   // --keep-kmer-info: first capacity of an engine's k-mer count table
-
-// One table of a sample's rows: a first download for the summary, of which `count` is the rows' number, then that many rows.  Row is
-// the host's struct for the engine's record Rec
-template <class Summ, class Rec, class Row>
-void download_rows(bk_engine* e, int (*download)(bk_engine*, Summ*, Rec*, uint64_t), const char* name, Summ& summ, const uint64_t& count, std::vector<Row>& rows) {
-    static_assert(sizeof(Row) == sizeof(Rec), "the host's struct is the engine's record");
-    hip_check(download(e, &summ, nullptr, 0), name);
-    rows.resize((size_t)count);
-    hip_check(download(e, &summ, reinterpret_cast<Rec*>(rows.data()), rows.size()), name);
-}
 
 struct CallRun {
     const Args& a;
@@ -319,13 +371,6 @@ struct CallRun {
     std::vector<SampleCalls> all_calls;              // --alignment
     std::vector<std::vector<uint8_t>> cohort_letters;   // --distances: by sample, its consensus letters (n x positions bytes of host memory in all)
     std::vector<int> cohort_genome;                  // ... and the genome file it selected (-1: none)
-    std::vector<Region> regions;                     // --regions / --region-window: resolved by open_index, every genome file's
-    std::vector<bk_region> region_table;             // ... as bk_regions_set takes them
-    size_t max_file_regions = 0;                     // regions of the genome file with the most
-    std::vector<CodonGene> genes;                    // --codons: resolved by open_index
-    std::vector<bk_codon_region> gene_table;         // ... as bk_sample_codons takes them
-    std::vector<HapWindow> hap_wins;                 // --haplotypes / --hap-window: resolved by open_index
-    std::vector<bk_hap_region> hap_regs;             // ... as bk_sample_haplotypes takes them
     int dump_threads = 1;                            // --keep-kmer-info: threads that format one sample's counts (set before the lanes start)
 
     // the samples, in input order; their files are read ahead from here on (ReadAhead): the index and the engine's tables take
@@ -343,7 +388,7 @@ struct CallRun {
     }
 
     void open_index() {
-        if (a.has_genomes) {                                            // call.rs:170-178
+        if (a.has_genomes()) {                                            // call.rs:170-178
             LOG_INFO(T, "Creating bronko index from provided reference genomes");
             try { ix = build_index_any(T, (int)a.kmer, a.genomes, (int)a.threads); }
             catch (const std::exception& e) { die(T, std::string(e.what()) + " | Reference failed to build"); }
@@ -357,41 +402,172 @@ struct CallRun {
         // (a few genomes: the engine's tables are made in a fraction of a second, the cores are the readers' from here on; with many
         // the readers stay few until the engines stand -- bk_engine_create runs on all cores for seconds)
         if (ahead && ix.files.size() <= 8) ahead->set_concurrency((unsigned)std::max<long>(2, a.threads / 2));
-        if (cfg.region_report()) resolve_regions();
-        // (a k-mer's cell in the engine's table is its first among all files, not the selected genome's)
-        const std::pair<bool, const char*> one_file[] = {{cfg.indels, "--indels"}, {cfg.junctions, "--junctions"}, {cfg.copybacks, "--copybacks"},
-                                                         {cfg.chimeras, "--chimeras"}, {cfg.breakends, "--breakends"}, {cfg.duplications, "--duplications"},
-                                                         {cfg.linkage, "--linkage"}, {cfg.codons(), "--codons"}};
-        for (const auto& flag : one_file)
-            if (flag.first && ix.files.size() != 1)
-                die(T, std::string(flag.second) + " needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.codons()) {   // the BED lines against the CHROM tokens of the index.  Before any device is touched.
-            try { genes = resolve_codon_bed(ix, 0, cfg.codon_bed, cfg.codons_path); }
-            catch (const std::exception& e) { die(T, e.what()); }
-            for (const CodonGene& g : genes) gene_table.push_back(bk_codon_region{g.reg.cell0, g.reg.n_codons});
-            LOG_DEBUG(T, std::to_string(genes.size()) + " coding regions");
-        }
-        if (cfg.haps() && ix.files.size() != 1)
-            die(T, "--haplotypes needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
-        if (cfg.haps()) {     // the BED lines against the CHROM tokens of the index, or the tiling.  Before any device is touched.
-            try { hap_wins = cfg.hap_window ? hap_windows(ix, 0, cfg.hap_window, cfg.hap_step) : resolve_hap_bed(ix, 0, cfg.hap_bed, cfg.haps_path); }
-            catch (const std::exception& e) { die(T, e.what()); }
-            for (const HapWindow& w : hap_wins) hap_regs.push_back(bk_hap_region{w.reg.cell0, w.reg.len});
-            LOG_DEBUG(T, std::to_string(hap_wins.size()) + " haplotype regions");
-        }
-        if (cfg.read_pileup && ix.files.size() != 1)
-            die(T, "--read-pileup needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        regions_resolve();   // every report's BED lines meet the CHROM tokens of the index here, before any device is touched
+        for (const char* opt : one_file_reports(cfg))
+            if (ix.files.size() != 1) die(T, std::string(opt) + " needs an index of one genome file, this one has " + std::to_string(ix.files.size()));
+        codons_resolve();
+        haps_resolve();
     }
-    // --regions: the BED lines against the CHROM tokens of the index; --region-window: the tiling.  Before any device is touched.
-    void resolve_regions() {
+
+    // ---- the other seven reports, a group of functions each: what open_index resolves for it, its launch, its download and its
+    // write-and-log, side by side.  The stages below call them in a fixed order; `base` is <DIR>/<stem>, `best` the selected genome file.
+    // --consensus: on the device, behind the calls; only the letters travel
+    void consensus_launch(bk_engine* e) const { if (a.consensus) hip_check(bk_sample_consensus(e, &cfg.consensus), "bk_sample_consensus"); }
+    void consensus_download(bk_engine* e, uint64_t longest, SampleData& d) const {
+        if (!a.consensus) return;
+        d.consensus.rows.resize((size_t)longest);
+        hip_check(bk_sample_download_consensus(e, &d.consensus.summ, d.consensus.rows.data(), d.consensus.rows.size()), "bk_sample_download_consensus");
+    }
+    void consensus_write(const std::string& base, const std::string& stem, int best, const SampleData& d) const {
+        if (!a.consensus) return;
+        const bk_consensus_summary& c = d.consensus.summ;
+        LOG_INFO(T, "Consensus of " + num(c.positions) + " positions: " + num(c.called) + " called (" + num(c.substitutions) + " substitutions), " + num(c.ambiguous) +
+                        " ambiguous, " + num(c.masked) + " masked");
+        if (!a.consensus_indels) write_consensus_fasta(base + ".consensus.fa", stem, ix, best, d.consensus.rows.data(), c.positions);
+    }
+    // --consensus-indels: the indels join the letters where both lie; the few accepted events travel
+    void consensus_indels_launch(bk_engine* e) const { if (a.consensus_indels) hip_check(bk_sample_consensus_indels(e), "bk_sample_consensus_indels"); }
+    void consensus_indels_download(bk_engine* e, SampleData& d) const {
+        if (a.consensus_indels) download_rows(e, bk_sample_download_consensus_indels, "bk_sample_download_consensus_indels", d.cons_indels, d.cons_indels.summ.accepted);
+    }
+    // (the letters came with '-' at the applied deletions; a sample without accepted events: the header lines alone)
+    void consensus_indels_write(const std::string& base, const std::string& stem, int best, const SampleData& d) const {
+        if (!a.consensus_indels) return;
+        const bk_consensus_indel_summary& s = d.cons_indels.summ;
+        LOG_INFO(T, "Consensus indels: " + num(s.accepted) + " of " + num(s.candidates) + " candidate events accepted, " + num(s.applied) + " applied (" + num(s.deletions) +
+                        " deletions of " + num(s.deleted_bases) + " bases, " + num(s.insertions) + " insertions of " + num(s.inserted_bases) + " bases, " +
+                        num(s.frameshifts) + " frameshifts), " + num(s.contested) + " contested");
+        write_consensus_indels_fasta(base + ".consensus.fa", stem, ix, best, d.consensus.rows.data(), d.consensus.summ.positions, d.cons_indels.rows);
+        write_consensus_indels_tsv(base + ".consensus_indels.tsv", ix, best, d.cons_indels.rows, cfg.consensus.min_depth, cfg.consensus.min_freq);
+    }
+    // --regions: the BED lines against the index; --region-window: the tiling; a few numbers per region travel
+    std::vector<Region> regions;         // every genome file's
+    std::vector<bk_region> region_table;         // ... as bk_regions_set takes them (every engine that completes a sample holds them)
+    size_t max_file_regions = 0;          // regions of the genome file with the most
+    void regions_resolve() {
+        if (!cfg.region_report()) return;
         try { regions = cfg.region_window ? window_regions(ix, cfg.region_window) : resolve_bed(ix, cfg.bed, cfg.regions_path); }
         catch (const std::exception& e) { die(T, e.what()); }
         std::vector<size_t> per_file(ix.files.size(), 0);
-        for (const Region& r : regions) {
-            region_table.push_back(bk_region{r.file_id, r.seq, r.start, r.end});
-            max_file_regions = std::max(max_file_regions, ++per_file[(size_t)r.file_id]);
+        for (const Region& g : regions) {
+            region_table.push_back(bk_region{g.file_id, g.seq, g.start, g.end});
+            max_file_regions = std::max(max_file_regions, ++per_file[(size_t)g.file_id]);
         }
-        LOG_DEBUG(T, std::to_string(regions.size()) + " regions over " + std::to_string(ix.files.size()) + " genome file(s)");
+        LOG_DEBUG(T, num(regions.size()) + " regions over " + num(ix.files.size()) + " genome file(s)");
+    }
+    void regions_set(bk_engine* e) const { if (!region_table.empty()) hip_check(bk_regions_set(e, region_table.data(), region_table.size()), "bk_regions_set"); }
+    void regions_launch(bk_engine* e) const { if (!region_table.empty()) hip_check(bk_sample_region_depths(e, cfg.region_min_depth), "bk_sample_region_depths"); }
+    void regions_download(bk_engine* e, SampleData& d) const {
+        if (region_table.empty()) return;
+        d.regions.rows.resize(max_file_regions);
+        hip_check(bk_sample_download_region_depths(e, &d.regions.summ, d.regions.rows.data(), d.regions.rows.size()), "bk_sample_download_region_depths");
+        d.regions.rows.resize(std::min<size_t>(d.regions.rows.size(), d.regions.summ.n_regions));
+    }
+    void regions_write(const std::string& base, int best, const SampleData& d) const {   // (a genome without a region: the two header lines)
+        if (!cfg.region_report()) return;
+        const bk_region_summary& s = d.regions.summ;
+        LOG_INFO(T, "Depth of " + num(s.n_regions) + " regions at minimum depth " + num(cfg.region_min_depth) + ": " + num(s.full) + " full, " + num(s.partial) +
+                        " partial, " + num(s.empty) + " empty");
+        std::vector<RegionDepth> rows;
+        for (const bk_region_depth& g : d.regions.rows) { RegionDepth o; o.sum = g.sum; o.min = g.min; o.max = g.max; o.median = g.median; o.covered = g.covered; rows.push_back(o); }
+        write_regions_tsv(base + ".regions.tsv", ix, best, regions, rows.data(), rows.size(), cfg.region_min_depth);
+    }
+    // --linkage: the sites are the sample's own VCF records, so it is counted once the calls are down; a few rows travel
+    void linkage_count(bk_engine* e, SampleData& d) const {
+        if (!cfg.linkage) return;
+        const FileMeta& fm = ix.files[0];     // (one genome file: checked as the index was opened)
+        std::vector<uint64_t> seq_cell(fm.sequences.size(), 0);
+        for (size_t q = 1; q < fm.sequences.size(); q++) seq_cell[q] = seq_cell[q - 1] + fm.sequences[q - 1].len;
+        for (uint64_t i = 0; i < std::min<uint64_t>(d.summ.n_records, d.recs.size()); i++) {
+            const bk_call_record& c = d.recs[i];
+            LinkSite s;
+            s.cell = (uint32_t)(seq_cell[(size_t)c.seq_id] + c.pos - 1); s.ref_base = (uint8_t)c.ref_base; s.alt_base = (uint8_t)c.alt_base;
+            d.link_sites.push_back(s);
+        }
+        const std::vector<uint32_t> sites = link_sites(d.link_sites);
+        hip_check(bk_sample_linkage(e, sites.data(), (uint32_t)sites.size(), cfg.link.max_dist), "bk_sample_linkage");
+        download_rows(e, bk_sample_download_linkage, "bk_sample_download_linkage", d.linkage, d.linkage.summ.n_pairs);
+    }
+    void linkage_write(const std::string& base, int best, const SampleData& d) const {   // (a sample without such a pair: the header alone)
+        if (!cfg.linkage) return;
+        const uint64_t lines = write_linkage_tsv(base + ".linkage.tsv", ix, best, d.link_sites, d.linkage.rows, cfg.link);
+        LOG_INFO(T, "Linkage: " + num(d.linkage.summ.placed) + " of " + num(d.linkage.summ.records) + " records placed, " + num(d.linkage.summ.n_pairs) +
+                        " pairs counted, " + num(lines) + " lines written");
+    }
+    // --codons: counted from the same rows, behind the calls; 256 bytes a codon travel
+    std::vector<CodonGene> genes;             // the BED lines against the index
+    std::vector<bk_codon_region> gene_table;       // ... as bk_sample_codons takes them
+    void codons_resolve() {
+        if (!cfg.codons()) return;
+        try { genes = resolve_codon_bed(ix, 0, cfg.codon_bed, cfg.codons_path); }
+        catch (const std::exception& e) { die(T, e.what()); }
+        for (const CodonGene& g : genes) gene_table.push_back(bk_codon_region{g.reg.cell0, g.reg.n_codons});
+        LOG_DEBUG(T, num(genes.size()) + " coding regions");
+    }
+    void codons_count(bk_engine* e, SampleData& d) const {
+        if (!cfg.codons()) return;
+        bk_codon_summary& s = d.codons.summ;
+        hip_check(bk_sample_codons(e, gene_table.data(), (uint32_t)gene_table.size()), "bk_sample_codons");
+        hip_check(bk_sample_download_codons(e, &s, nullptr, 0), "bk_sample_download_codons");
+        d.codons.rows.resize((size_t)s.n_codons * 64);
+        hip_check(bk_sample_download_codons(e, &s, d.codons.rows.data(), s.n_codons), "bk_sample_download_codons");
+    }
+    void codons_write(const std::string& base, int best, const SampleData& d) const {   // (a sample without such a triplet: the header alone)
+        if (!cfg.codons()) return;
+        const uint64_t lines = write_codons_tsv(base + ".codons.tsv", ix, best, genes, d.codons.rows, cfg.codon);
+        LOG_INFO(T, "Codons: " + num(d.codons.summ.rows) + " placed records over " + num(d.codons.summ.n_regions) + " regions, " + num(d.codons.summ.n_codons) +
+                        " codons counted, " + num(lines) + " lines written");
+    }
+    // --haplotypes / --hap-window: likewise; a table that was full: the same rows again into one of four times the slots
+    std::vector<HapWindow> hap_wins;              // the BED lines against the index, or the tiling
+    std::vector<bk_hap_region> hap_regs;          // ... as bk_sample_haplotypes takes them
+    void haps_resolve() {
+        if (!cfg.haps()) return;
+        try { hap_wins = cfg.hap_window ? hap_windows(ix, 0, cfg.hap_window, cfg.hap_step) : resolve_hap_bed(ix, 0, cfg.hap_bed, cfg.haps_path); }
+        catch (const std::exception& e) { die(T, e.what()); }
+        for (const HapWindow& w : hap_wins) hap_regs.push_back(bk_hap_region{w.reg.cell0, w.reg.len});
+        LOG_DEBUG(T, num(hap_wins.size()) + " haplotype regions");
+    }
+    void haps_count(bk_engine* e, SampleData& d) const {
+        if (!cfg.haps()) return;
+        bk_hap_summary& s = d.hap_summ;
+        d.hap_table.cover.assign(hap_regs.size(), 0u); d.hap_table.ref_count.assign(hap_regs.size(), 0u);
+        for (uint32_t log2 = kHapTableLog2;; log2 += 2) {
+            hip_check(bk_sample_haplotypes(e, hap_regs.data(), (uint32_t)hap_regs.size(), log2), "bk_sample_haplotypes");
+            const int rc = bk_sample_download_haplotypes(e, &s, d.hap_table.cover.data(), d.hap_table.ref_count.data(), nullptr, 0);
+            if (rc == BK_ERR_RANGE && log2 + 2 <= kHapTableLog2Max) {
+                LOG_INFO(T, "Haplotypes: a table of 2^" + num(s.table_log2) + " slots was full (" + num(s.dropped) + " counts dropped), counting again with four times as many");
+                continue;
+            }
+            hip_check(rc, "bk_sample_download_haplotypes");
+            break;
+        }
+        static_assert(sizeof(HapEntry) == sizeof(bk_hap_entry), "HapEntry is bk_hap_entry");
+        d.hap_table.entries.resize((size_t)s.entries);
+        hip_check(bk_sample_download_haplotypes(e, &s, nullptr, nullptr, reinterpret_cast<bk_hap_entry*>(d.hap_table.entries.data()), d.hap_table.entries.size()),
+                  "bk_sample_download_haplotypes");
+    }
+    void haps_write(const std::string& base, int best, const SampleData& d) const {   // (a sample without such a haplotype: the header alone)
+        if (!cfg.haps()) return;
+        const HapStats hs = write_haplotypes_tsv(base + ".haplotypes.tsv", ix, best, hap_wins, d.hap_table, cfg.hap);
+        LOG_INFO(T, "Haplotypes: " + num(d.hap_summ.rows) + " placed records over " + num(d.hap_summ.n_regions) + " regions, " + num(hs.no_cover) + " without cover, " +
+                        num(hs.distinct) + " distinct haplotypes, " + num(hs.lines) + " lines written, table of 2^" + num(d.hap_summ.table_log2) + " slots");
+    }
+    // --read-pileup: likewise; 48 bytes a position travel
+    void read_pileup_count(bk_engine* e, SampleData& d) const {
+        if (!cfg.read_pileup) return;
+        static_assert(sizeof(ReadPileupCell) == sizeof(bk_read_pileup_cell), "ReadPileupCell is bk_read_pileup_cell");
+        hip_check(bk_sample_read_pileup(e, cfg.read_pile.end_dist), "bk_sample_read_pileup");
+        d.read_pileup.rows.resize((size_t)ix.genome_len(0));
+        hip_check(bk_sample_download_read_pileup(e, &d.read_pileup.summ, reinterpret_cast<bk_read_pileup_cell*>(d.read_pileup.rows.data()), d.read_pileup.rows.size()),
+                  "bk_sample_download_read_pileup");
+    }
+    void read_pileup_write(const std::string& base, int best, const SampleData& d) const {
+        if (!cfg.read_pileup) return;
+        const bk_read_pileup_summary& s = d.read_pileup.summ;
+        write_read_pileup_tsv(base + ".read_pileup.tsv", ix, best, d.read_pileup.rows, cfg.read_pile);
+        LOG_INFO(T, "Read pileup: " + num(s.rows) + " placed records, " + num(s.covered) + " of " + num(s.n_cells) + " positions covered, " + num(s.bases) +
+                        " bases, near an end within " + num(s.end_dist));
     }
 
     void make_engine(int device, Engine& out, bool selected_only = true) const {
@@ -526,31 +702,12 @@ struct CallRun {
         if (!e) return;
         set_seqs(cfg.adapters, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_adapters_set(e, q, l, n, cfg.adapter_min_overlap, cfg.adapter_error_rate), "bk_adapters_set"); });
         set_seqs(cfg.primers, [&](const uint8_t* const* q, const uint32_t* l, uint32_t n) { hip_check(bk_primers_set(e, q, l, n, cfg.primer_mismatches), "bk_primers_set"); });
-        if (!region_table.empty()) hip_check(bk_regions_set(e, region_table.data(), region_table.size()), "bk_regions_set");
-        if (cfg.indels) {
-            const bk_indel_config ic{cfg.indel.max_len, cfg.indel.max_mismatches, kIndelTableLog2};
-            hip_check(bk_indels_enable(e, &ic), "bk_indels_enable");
-        }
-        if (cfg.junctions) {
-            const bk_junction_config jc{cfg.junction.min_len, cfg.junction.max_mismatches, kJunctionTableLog2};
-            hip_check(bk_junctions_enable(e, &jc), "bk_junctions_enable");
-        }
-        if (cfg.copybacks) {
-            const bk_copyback_config cc{cfg.copyback.max_mismatches, kCopybackTableLog2};
-            hip_check(bk_copybacks_enable(e, &cc), "bk_copybacks_enable");
-        }
-        if (cfg.chimeras) {
-            const bk_chimera_config xc{cfg.chimera.max_mismatches, kChimeraTableLog2};
-            hip_check(bk_chimeras_enable(e, &xc), "bk_chimeras_enable");
-        }
-        if (cfg.breakends) {
-            const bk_breakend_config bc{cfg.breakend.min_clip, cfg.breakend.max_mismatches, kBreakendTableLog2};
-            hip_check(bk_breakends_enable(e, &bc), "bk_breakends_enable");
-        }
-        if (cfg.duplications) {
-            const bk_duplication_config dc{cfg.duplication.min_len, cfg.duplication.max_mismatches, kDuplicationTableLog2};
-            hip_check(bk_duplications_enable(e, &dc), "bk_duplications_enable");
-        }
+        regions_set(e);
+        each_anchor_pass([&](auto p) {
+            if (!p.on(cfg)) return;
+            const auto c = p.config(cfg);
+            hip_check(p.enable(e, &c), p.enable_name);
+        });
         if (cfg.row_store()) {   // (--codons, --haplotypes and --read-pileup read --linkage's row store; alone each brings its own M, together they are equal)
             const bk_link_config lc{cfg.row_store_mismatches(), kLinkInitialRows};
             hip_check(bk_link_enable(e, &lc), "bk_link_enable");
@@ -585,37 +742,15 @@ struct CallRun {
         const int n_mates = (int)mates.size();
         if (!finalized) hip_check(bk_sample_finalize(e, n_mates), "bk_sample_finalize");   // (a sharded sample: sharded_finalize has done it)
         if (!finalized) log_trim_stats(std::vector<bk_engine*>{e}, mates);
-        if (cfg.indels) {   // (needs the finalize only: the events that pass the thresholds, a few rows travel)
-            const bk_indel_params ip{cfg.indel.min_reads, cfg.indel.min_af_ppm};
-            hip_check(bk_sample_indels(e, &ip), "bk_sample_indels");
-        }
-        if (cfg.junctions) {   // (likewise)
-            const bk_junction_params jp{cfg.junction.min_reads};
-            hip_check(bk_sample_junctions(e, &jp), "bk_sample_junctions");
-        }
-        if (cfg.copybacks) {   // (likewise)
-            const bk_copyback_params cp{cfg.copyback.min_reads, cfg.copyback.min_dist};
-            hip_check(bk_sample_copybacks(e, &cp), "bk_sample_copybacks");
-        }
-        if (cfg.chimeras) {   // (likewise)
-            const bk_chimera_params xp{cfg.chimera.min_reads};
-            hip_check(bk_sample_chimeras(e, &xp), "bk_sample_chimeras");
-        }
-        if (cfg.breakends) {   // (likewise)
-            const bk_breakend_params bp{cfg.breakend.min_reads};
-            hip_check(bk_sample_breakends(e, &bp), "bk_sample_breakends");
-        }
-        if (cfg.duplications) {   // (likewise)
-            const bk_duplication_params dp{cfg.duplication.min_reads};
-            hip_check(bk_sample_duplications(e, &dp), "bk_sample_duplications");
-        }
+        each_anchor_pass([&](auto p) {   // (they need the finalize only: the events that pass the thresholds, a few rows travel)
+            if (!p.on(cfg)) return;
+            const auto q = p.params(cfg);
+            hip_check(p.report(e, &q), p.report_name);
+        });
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
-        // on the device, behind the calls: only the letters travel (bk_sample_download_consensus below)
-        if (a.consensus) hip_check(bk_sample_consensus(e, &cfg.consensus), "bk_sample_consensus");
-        // ... and the indels join the letters where both lie: the few accepted events travel (bk_sample_download_consensus_indels below)
-        if (a.consensus_indels) hip_check(bk_sample_consensus_indels(e), "bk_sample_consensus_indels");
-        // likewise: a few numbers per region travel (bk_sample_download_region_depths below)
-        if (!region_table.empty()) hip_check(bk_sample_region_depths(e, cfg.region_min_depth), "bk_sample_region_depths");
+        consensus_launch(e);        // behind the calls, in this order
+        consensus_indels_launch(e);
+        regions_launch(e);
     }
     void download_pileup(bk_engine* e, int n_mates, SampleData& d) const {
         const size_t n_files = ix.files.size(), cells4 = ix.total_cells() * 4;
@@ -643,67 +778,18 @@ struct CallRun {
         for (size_t f = 0; f < ix.files.size(); f++) longest = std::max<uint64_t>(longest, ix.genome_len(f));
         d.recs.resize((size_t)(3 * longest));
         hip_check(bk_sample_download_calls(e, &d.summ, d.recs.data(), d.recs.size()), "bk_sample_download_calls");
-        if (a.consensus) {
-            d.letters.resize((size_t)longest);
-            hip_check(bk_sample_download_consensus(e, &d.csumm, d.letters.data(), d.letters.size()), "bk_sample_download_consensus");
-        }
-        if (!region_table.empty()) {
-            d.rrows.resize(max_file_regions);
-            hip_check(bk_sample_download_region_depths(e, &d.rsumm, d.rrows.data(), d.rrows.size()), "bk_sample_download_region_depths");
-            d.rrows.resize(std::min<size_t>(d.rrows.size(), d.rsumm.n_regions));
-        }
-        if (cfg.indels) download_rows(e, bk_sample_download_indels, "bk_sample_download_indels", d.isumm, d.isumm.reported, d.indels);
-        if (a.consensus_indels)
-            download_rows(e, bk_sample_download_consensus_indels, "bk_sample_download_consensus_indels", d.cisumm, d.cisumm.accepted, d.cons_indels);
-        if (cfg.junctions) download_rows(e, bk_sample_download_junctions, "bk_sample_download_junctions", d.jsumm, d.jsumm.reported, d.junctions);
-        if (cfg.copybacks) download_rows(e, bk_sample_download_copybacks, "bk_sample_download_copybacks", d.cbsumm, d.cbsumm.reported, d.copybacks);
-        if (cfg.chimeras) download_rows(e, bk_sample_download_chimeras, "bk_sample_download_chimeras", d.chsumm, d.chsumm.reported, d.chimeras);
-        if (cfg.breakends) download_rows(e, bk_sample_download_breakends, "bk_sample_download_breakends", d.besumm, d.besumm.reported, d.breakends);
-        if (cfg.duplications) download_rows(e, bk_sample_download_duplications, "bk_sample_download_duplications", d.dpsumm, d.dpsumm.reported, d.duplications);
-        if (cfg.linkage) {   // the sites are the sample's own VCF records: counted behind the calls, a few rows travel
-            const FileMeta& fm = ix.files[0];     // (one genome file: checked as the index was opened)
-            std::vector<uint64_t> seq_cell(fm.sequences.size(), 0);
-            for (size_t q = 1; q < fm.sequences.size(); q++) seq_cell[q] = seq_cell[q - 1] + fm.sequences[q - 1].len;
-            for (uint64_t i = 0; i < std::min<uint64_t>(d.summ.n_records, d.recs.size()); i++) {
-                const bk_call_record& r = d.recs[i];
-                LinkSite s;
-                s.cell = (uint32_t)(seq_cell[(size_t)r.seq_id] + r.pos - 1); s.ref_base = (uint8_t)r.ref_base; s.alt_base = (uint8_t)r.alt_base;
-                d.link_recs.push_back(s);
-            }
-            const std::vector<uint32_t> sites = link_sites(d.link_recs);
-            hip_check(bk_sample_linkage(e, sites.data(), (uint32_t)sites.size(), cfg.link.max_dist), "bk_sample_linkage");
-            download_rows(e, bk_sample_download_linkage, "bk_sample_download_linkage", d.lsumm, d.lsumm.n_pairs, d.link_pairs);
-        }
-        if (cfg.codons()) {   // counted from the same rows, behind the calls: 256 bytes a codon travel
-            hip_check(bk_sample_codons(e, gene_table.data(), (uint32_t)gene_table.size()), "bk_sample_codons");
-            hip_check(bk_sample_download_codons(e, &d.csumm2, nullptr, 0), "bk_sample_download_codons");
-            d.codon_counts.resize((size_t)d.csumm2.n_codons * 64);
-            hip_check(bk_sample_download_codons(e, &d.csumm2, d.codon_counts.data(), d.csumm2.n_codons), "bk_sample_download_codons");
-        }
-        if (cfg.haps()) {     // likewise; a table that was full: the same rows again into one of four times the slots
-            d.hap_table.cover.assign(hap_regs.size(), 0u); d.hap_table.ref_count.assign(hap_regs.size(), 0u);
-            for (uint32_t log2 = kHapTableLog2;; log2 += 2) {
-                hip_check(bk_sample_haplotypes(e, hap_regs.data(), (uint32_t)hap_regs.size(), log2), "bk_sample_haplotypes");
-                const int rc = bk_sample_download_haplotypes(e, &d.hsumm, d.hap_table.cover.data(), d.hap_table.ref_count.data(), nullptr, 0);
-                if (rc == BK_ERR_RANGE && log2 + 2 <= kHapTableLog2Max) {
-                    LOG_INFO(T, "Haplotypes: a table of 2^" + std::to_string(d.hsumm.table_log2) + " slots was full (" + std::to_string(d.hsumm.dropped) +
-                                    " counts dropped), counting again with four times as many");
-                    continue;
-                }
-                hip_check(rc, "bk_sample_download_haplotypes");
-                break;
-            }
-            static_assert(sizeof(HapEntry) == sizeof(bk_hap_entry), "HapEntry is bk_hap_entry");
-            d.hap_table.entries.resize((size_t)d.hsumm.entries);
-            hip_check(bk_sample_download_haplotypes(e, &d.hsumm, nullptr, nullptr, reinterpret_cast<bk_hap_entry*>(d.hap_table.entries.data()), d.hap_table.entries.size()),
-                      "bk_sample_download_haplotypes");
-        }
-        if (cfg.read_pileup) {   // likewise: 48 bytes a position travel
-            static_assert(sizeof(ReadPileupCell) == sizeof(bk_read_pileup_cell), "ReadPileupCell is bk_read_pileup_cell");
-            hip_check(bk_sample_read_pileup(e, cfg.read_pile.end_dist), "bk_sample_read_pileup");
-            d.read_cells.resize((size_t)ix.genome_len(0));
-            hip_check(bk_sample_download_read_pileup(e, &d.psumm, reinterpret_cast<bk_read_pileup_cell*>(d.read_cells.data()), d.read_cells.size()), "bk_sample_download_read_pileup");
-        }
+        consensus_download(e, longest, d);
+        consensus_indels_download(e, d);
+        regions_download(e, d);
+        each_anchor_pass([&](auto p) {
+            using P = decltype(p);
+            PassRows<P>& t = std::get<PassRows<P>>(d.events);
+            if (p.on(cfg)) download_rows(e, p.download, p.download_name, t, t.summ.reported);
+        });
+        linkage_count(e, d);        // the readers of the row store, behind the calls: each launches and downloads here
+        codons_count(e, d);
+        haps_count(e, d);
+        read_pileup_count(e, d);
     }
     // the mates' statistics summed into d.p; returns KMC's "No. of unique counted k-mers", summed over mate files (call.rs:336)
     uint64_t merge_mates(const std::vector<std::string>& mates, SampleData& d) const {
@@ -737,105 +823,25 @@ struct CallRun {
         return cs;
     }
     void write_outputs(const std::vector<std::string>& mates, int best, const SampleData& d, const CallSummary& cs) const {
-        const std::string stem = clean_sample_id(mates[0]);
+        const std::string stem = clean_sample_id(mates[0]), base = a.output + "/" + stem;
         try {
-            if (a.pileup) { LOG_INFO(T, "Writing output to pileup"); write_pileup_tsv(a.output + "/" + stem + ".tsv", ix, best, d.p); }
+            if (a.pileup) { LOG_INFO(T, "Writing output to pileup"); write_pileup_tsv(base + ".tsv", ix, best, d.p); }
             LOG_INFO(T, "Writing output to VCF");
-            write_vcf(a.output + "/" + stem + ".vcf", mates[0], ix, best, cs.records);
-            if (a.consensus) {
-                const bk_consensus_summary& c = d.csumm;
-                LOG_INFO(T, "Consensus of " + std::to_string(c.positions) + " positions: " + std::to_string(c.called) + " called (" +
-                                std::to_string(c.substitutions) + " substitutions), " + std::to_string(c.ambiguous) + " ambiguous, " +
-                                std::to_string(c.masked) + " masked");
-                if (!a.consensus_indels) write_consensus_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, d.letters.data(), c.positions);
-            }
-            if (a.consensus_indels) {   // (the letters came with '-' at the applied deletions; a sample without accepted events: the header lines alone)
-                const bk_consensus_indel_summary& s = d.cisumm;
-                LOG_INFO(T, "Consensus indels: " + std::to_string(s.accepted) + " of " + std::to_string(s.candidates) + " candidate events accepted, " +
-                                std::to_string(s.applied) + " applied (" + std::to_string(s.deletions) + " deletions of " + std::to_string(s.deleted_bases) + " bases, " +
-                                std::to_string(s.insertions) + " insertions of " + std::to_string(s.inserted_bases) + " bases, " + std::to_string(s.frameshifts) +
-                                " frameshifts), " + std::to_string(s.contested) + " contested");
-                write_consensus_indels_fasta(a.output + "/" + stem + ".consensus.fa", stem, ix, best, d.letters.data(), d.csumm.positions, d.cons_indels);
-                write_consensus_indels_tsv(a.output + "/" + stem + ".consensus_indels.tsv", ix, best, d.cons_indels, cfg.consensus.min_depth, cfg.consensus.min_freq);
-            }
-            if (cfg.region_report()) {   // (a genome without a region: the two header lines)
-                LOG_INFO(T, "Depth of " + std::to_string(d.rsumm.n_regions) + " regions at minimum depth " + std::to_string(cfg.region_min_depth) + ": " +
-                                std::to_string(d.rsumm.full) + " full, " + std::to_string(d.rsumm.partial) + " partial, " + std::to_string(d.rsumm.empty) + " empty");
-                std::vector<RegionDepth> rows;
-                for (const bk_region_depth& r : d.rrows) { RegionDepth o; o.sum = r.sum; o.min = r.min; o.max = r.max; o.median = r.median; o.covered = r.covered; rows.push_back(o); }
-                write_regions_tsv(a.output + "/" + stem + ".regions.tsv", ix, best, regions, rows.data(), rows.size(), cfg.region_min_depth);
-            }
-            if (cfg.indels) {       // (a sample without events: the header alone)
-                const bk_indel_summary& s = d.isumm;
-                LOG_INFO(T, "Indels: " + std::to_string(s.anchored) + " of " + std::to_string(s.records) + " records anchored, " + std::to_string(s.ref_spanning) +
-                                " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.candidates) + " candidate events, " +
-                                std::to_string(s.reported) + " reported");
-                write_indels_vcf(a.output + "/" + stem + ".indels.vcf", mates[0], ix, best, d.indels, cfg.indel);
-            }
-            if (cfg.junctions) {    // (a sample without events: the headers alone)
-                const bk_junction_summary& s = d.jsumm;
-                LOG_INFO(T, "Junctions: " + std::to_string(s.anchored) + " of " + std::to_string(s.records) + " records anchored, " + std::to_string(s.ref_spanning) +
-                                " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.short_) + " short, " +
-                                std::to_string(s.backward) + " backward, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) +
-                                " candidate junctions, " + std::to_string(s.reported) + " reported");
-                write_junctions_tsv(a.output + "/" + stem + ".junctions.tsv", ix, best, d.junctions, cfg.junction);
-            }
-            if (cfg.copybacks) {    // (a sample without events: the headers alone)
-                const bk_copyback_summary& s = d.cbsumm;
-                LOG_INFO(T, "Copy-backs: " + std::to_string(s.records) + " records, " + std::to_string(s.same_strand) + " on one strand, " +
-                                std::to_string(s.ref_spanning) + " reference-spanning, " + std::to_string(s.switched) + " switched, " + std::to_string(s.supporting) +
-                                " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate copy-backs, " +
-                                std::to_string(s.reported) + " reported");
-                write_copybacks_tsv(a.output + "/" + stem + ".copybacks.tsv", ix, best, d.copybacks, cfg.copyback);
-            }
-            if (cfg.chimeras) {        // (a sample without events, a genome file of one sequence: the headers alone)
-                const bk_chimera_summary& s = d.chsumm;
-                LOG_INFO(T, "Chimeras: " + std::to_string(s.records) + " records, " + std::to_string(s.same_strand) + " on one strand of one sequence, " +
-                                std::to_string(s.ref_spanning) + " reference-spanning, " + std::to_string(s.crossed) + " crossed, " + std::to_string(s.supporting) +
-                                " supporting, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) + " candidate chimeras, " +
-                                std::to_string(s.reported) + " reported");
-                write_chimeras_tsv(a.output + "/" + stem + ".chimeras.tsv", ix, best, d.chimeras, cfg.chimera, s.supporting, s.ref_spanning);
-            }
-            if (cfg.breakends) {       // (a sample without events: the headers alone)
-                const bk_breakend_summary& s = d.besumm;
-                LOG_INFO(T, "Breakends: " + std::to_string(s.records) + " records, " + std::to_string(s.one_anchor) + " with one anchor, " +
-                                std::to_string(s.ref_spanning) + " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.short_) +
-                                " short, " + std::to_string(s.through) + " through, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.unplaced) +
-                                " unplaced, " + std::to_string(s.candidates) + " candidate breakends, " + std::to_string(s.reported) + " reported");
-                BreakendTallies bt;
-                bt.records = s.records; bt.one_anchor = s.one_anchor; bt.ref_spanning = s.ref_spanning; bt.supporting = s.supporting; bt.short_ = s.short_;
-                bt.through = s.through; bt.discordant = s.discordant; bt.unplaced = s.unplaced; bt.candidates = s.candidates; bt.reported = s.reported;
-                write_breakends_tsv(a.output + "/" + stem + ".breakends.tsv", ix, best, d.breakends, cfg.breakend, bt);
-            }
-            if (cfg.duplications) {    // (a sample without events: the headers alone)
-                const bk_duplication_summary& s = d.dpsumm;
-                LOG_INFO(T, "Duplications: " + std::to_string(s.anchored) + " of " + std::to_string(s.records) + " records anchored, " + std::to_string(s.ref_spanning) +
-                                " reference-spanning, " + std::to_string(s.supporting) + " supporting, " + std::to_string(s.short_) + " short, " +
-                                std::to_string(s.forward) + " forward, " + std::to_string(s.discordant) + " discordant, " + std::to_string(s.candidates) +
-                                " candidate duplications, " + std::to_string(s.reported) + " reported");
-                write_duplications_tsv(a.output + "/" + stem + ".duplications.tsv", ix, best, d.duplications, cfg.duplication);
-            }
-            if (cfg.linkage) {      // (a sample without such a pair: the header alone)
-                const uint64_t lines = write_linkage_tsv(a.output + "/" + stem + ".linkage.tsv", ix, best, d.link_recs, d.link_pairs, cfg.link);
-                LOG_INFO(T, "Linkage: " + std::to_string(d.lsumm.placed) + " of " + std::to_string(d.lsumm.records) + " records placed, " +
-                                std::to_string(d.lsumm.n_pairs) + " pairs counted, " + std::to_string(lines) + " lines written");
-            }
-            if (cfg.codons()) {     // (a sample without such a triplet: the header alone)
-                const uint64_t lines = write_codons_tsv(a.output + "/" + stem + ".codons.tsv", ix, best, genes, d.codon_counts, cfg.codon);
-                LOG_INFO(T, "Codons: " + std::to_string(d.csumm2.rows) + " placed records over " + std::to_string(d.csumm2.n_regions) + " regions, " +
-                                std::to_string(d.csumm2.n_codons) + " codons counted, " + std::to_string(lines) + " lines written");
-            }
-            if (cfg.haps()) {       // (a sample without such a haplotype: the header alone)
-                const HapStats hs = write_haplotypes_tsv(a.output + "/" + stem + ".haplotypes.tsv", ix, best, hap_wins, d.hap_table, cfg.hap);
-                LOG_INFO(T, "Haplotypes: " + std::to_string(d.hsumm.rows) + " placed records over " + std::to_string(d.hsumm.n_regions) + " regions, " +
-                                std::to_string(hs.no_cover) + " without cover, " + std::to_string(hs.distinct) + " distinct haplotypes, " + std::to_string(hs.lines) +
-                                " lines written, table of 2^" + std::to_string(d.hsumm.table_log2) + " slots");
-            }
-            if (cfg.read_pileup) {
-                write_read_pileup_tsv(a.output + "/" + stem + ".read_pileup.tsv", ix, best, d.read_cells, cfg.read_pile);
-                LOG_INFO(T, "Read pileup: " + std::to_string(d.psumm.rows) + " placed records, " + std::to_string(d.psumm.covered) + " of " + std::to_string(d.psumm.n_cells) +
-                                " positions covered, " + std::to_string(d.psumm.bases) + " bases, near an end within " + std::to_string(d.psumm.end_dist));
-            }
+            write_vcf(base + ".vcf", mates[0], ix, best, cs.records);
+            consensus_write(base, stem, best, d);
+            consensus_indels_write(base, stem, best, d);
+            regions_write(base, best, d);
+            each_anchor_pass([&](auto p) {   // (a sample without events: the headers alone)
+                using P = decltype(p);
+                if (!p.on(cfg)) return;
+                const PassRows<P>& t = std::get<PassRows<P>>(d.events);
+                LOG_INFO(T, p.sentence(t.summ));
+                p.write(base + p.suffix, mates[0], ix, best, t, cfg);
+            });
+            linkage_write(base, best, d);
+            codons_write(base, best, d);
+            haps_write(base, best, d);
+            read_pileup_write(base, best, d);
         } catch (const std::exception& ex) { die(T, ex.what()); }
     }
 
@@ -866,7 +872,7 @@ struct CallRun {
         overview[sample_id] = OverviewRow{mates[0], gname, cs.n_major, cs.n_minor, cs.breadth, cs.depth, n_perfect, n_variant, n_unmapped};
         if (a.alignment) all_calls[sample_id] = SampleCalls{mates[0], gname, cs.breadth, cs.records};
         if (a.distances) {   // (the letters as they were written: with '-' at the deletions --consensus-indels applied)
-            cohort_letters[sample_id].assign(d.letters.begin(), d.letters.begin() + (ptrdiff_t)std::min<uint64_t>(d.csumm.positions, d.letters.size()));
+            cohort_letters[sample_id].assign(d.consensus.rows.begin(), d.consensus.rows.begin() + (ptrdiff_t)std::min<uint64_t>(d.consensus.summ.positions, d.consensus.rows.size()));
             cohort_genome[sample_id] = best;
         }
     }
@@ -934,7 +940,7 @@ struct CallRun {
                     hip_check(bk_cohort_distances(e, row0, rows, diff.data(), compared.data()), "bk_cohort_distances");
                     wd.add_rows(row0, rows, diff.data());
                     wc.add_rows(row0, rows, compared.data());
-                    if (a.has_clusters) clusterer.add_rows(row0, rows, diff.data(), compared.data());
+                    if (a.has_clusters()) clusterer.add_rows(row0, rows, diff.data(), compared.data());
                     for (uint64_t r = 0; r < rows; r++)
                         for (uint64_t j = row0 + r + 1; j < n; j++) {   // (each pair once)
                             max_diff = std::max<uint64_t>(max_diff, diff[r * n + j]);
@@ -942,7 +948,7 @@ struct CallRun {
                         }
                 }
                 wd.close(); wc.close();
-                if (a.has_clusters) {
+                if (a.has_clusters()) {
                     cl = clusterer.finish();
                     write_cohort_clusters_tsv(a.output + "/" + gname + ".clusters.tsv", names, cl, (uint64_t)a.clusters, a.cluster_min_breadth);
                 }
@@ -951,7 +957,7 @@ struct CallRun {
             snprintf(secs, sizeof secs, "%.3f", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
             LOG_INFO(T, "Distances for " + gname + ": " + std::to_string(n) + " samples, largest distance " + std::to_string(max_diff) + ", " +
                             std::to_string(empty_pairs) + " pairs with nothing compared" +
-                            (a.has_clusters ? ", " + std::to_string(cl.n_clusters) + " clusters, the largest of " + std::to_string(cl.largest) + " samples" : std::string()) +
+                            (a.has_clusters() ? ", " + std::to_string(cl.n_clusters) + " clusters, the largest of " + std::to_string(cl.largest) + " samples" : std::string()) +
                             " (" + secs + " s)");
             if (a.mst) write_forest(e, gname, names, positions);   // (the cohort is still set)
         }
@@ -1020,7 +1026,7 @@ int call_samples(const Args& a, const CallConfig& cfg) {
 
     std::vector<int> devices = devices_from_env();
     const size_t n_samples = std::max<size_t>(run.samples.size(), 1);
-    const std::vector<int> shard_devices = plan_shards(a, devices, run.samples.size());
+    const std::vector<int> shard_devices = plan_shards(a, cfg, devices, run.samples.size());
     if (devices.size() > n_samples) devices.resize(n_samples);   // no more lanes than samples
     ShardGroup shards;
     std::vector<Engine> shard_engines;

@@ -1,7 +1,8 @@
 // cli.cpp -- the `bronko` command line: `bronko build` and `bronko call` with the reference's flag names,
-// defaults, validations, exit codes and output files (drop-in surface).  Here: the logger, the arguments and
-// their checks, `bronko build` and main; `bronko call` goes on in reads.cpp (FASTQ files -> engine) and call_run.cpp (engines,
-// lanes, the per-sample code), cli.hpp is what the three share.
+// defaults, validations, exit codes and output files (drop-in surface).  Here: the logger, the option table
+// (every option once: parse_args looks an argument up in it), the ordered rules of `bronko call`'s arguments (check_call_args walks
+// them), `bronko build` and main; `bronko call` goes on in reads.cpp (FASTQ files -> engine) and call_run.cpp (engines, lanes, the
+// per-sample report units), cli.hpp is what the three share.  DESIGN.md §O.
 //
 // Reference: /root/reference/src/main.rs:14-29 (banner, dispatch, elapsed), src/cli.rs:29-166 (flags),
 // src/consts.rs (defaults), src/build.rs:62-120 (build + its checks), src/call.rs:30-136 (call checks).
@@ -199,25 +200,141 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
     exit(code);
 }
 
-long to_long(const std::string& opt, const std::string& v) {
-    char* end = nullptr;
-    const long x = strtol(v.c_str(), &end, 10);
-    if (v.empty() || *end || x < 0) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
-    return x;
+[[noreturn]] void invalid_value(const std::string& opt, const std::string& v) {
+    fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str());
+    exit(2);
 }
-// any integer that fits a long: what is out of an option's range is refused by check_call_args
-long any_long(const std::string& opt, const std::string& v) {
+// any: any integer that fits a long (what is out of an option's range is refused by check_call_args); else: none below 0
+long to_long(const std::string& opt, const std::string& v, bool any) {
     char* end = nullptr;
     errno = 0;
     const long x = strtol(v.c_str(), &end, 10);
-    if (v.empty() || *end || errno == ERANGE) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+    if (v.empty() || *end || (any ? errno == ERANGE : x < 0)) invalid_value(opt, v);
     return x;
 }
 double to_double(const std::string& opt, const std::string& v) {
     char* end = nullptr;
     const double x = strtod(v.c_str(), &end);
-    if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+    if (v.empty() || *end) invalid_value(opt, v);
     return x;
+}
+
+// ---- the option table: every option of `bronko build` and `bronko call`, once ------------------------------------------------------
+// A row: the option's long name (its only name where it has no other), its short form, its kind -- a switch, a non-negative
+// integer, any integer (to_long), a real, one text, one or more texts --, the field of Args its value goes to, and whether
+// `bronko build` takes it too.  That an option was given is recorded for every row: Args::given_rows, a bit per row.
+enum Kind { kSwitch, kNat, kInt, kReal, kText, kTexts };
+struct Opt {
+    const char* name;
+    Kind kind;
+    bool Args::*b = nullptr;
+    long Args::*l = nullptr;
+    double Args::*d = nullptr;
+    std::string Args::*s = nullptr;
+    std::vector<std::string> Args::*v = nullptr;
+    const char* alias = nullptr;
+    bool build = false;
+    Opt(const char* n, bool Args::*p) : name(n), kind(kSwitch), b(p) {}
+    Opt(const char* n, Kind k, long Args::*p) : name(n), kind(k), l(p) {}
+    Opt(const char* n, double Args::*p) : name(n), kind(kReal), d(p) {}
+    Opt(const char* n, std::string Args::*p) : name(n), kind(kText), s(p) {}
+    Opt(const char* n, std::vector<std::string> Args::*p) : name(n), kind(kTexts), v(p) {}
+    Opt shortened(const char* a) const { Opt o = *this; o.alias = a; return o; }
+    Opt in_build() const { Opt o = *this; o.build = true; return o; }
+};
+const Opt kOpts[] = {
+    Opt("--genomes", &Args::genomes).shortened("-g").in_build(),
+    Opt("--kmer-size", kNat, &Args::kmer).shortened("-k").in_build(),
+    Opt("--output", &Args::output).shortened("-o").in_build(),
+    Opt("--threads", kNat, &Args::threads).shortened("-t").in_build(),
+    Opt("--debug", &Args::debug).in_build(),
+    Opt("--verbose", &Args::verbose).in_build(),
+    Opt("--db", &Args::db).shortened("-d"),
+    Opt("--reads", &Args::reads).shortened("-r"),
+    Opt("--first-pairs", &Args::first_pairs).shortened("-1"),
+    Opt("--second-pairs", &Args::second_pairs).shortened("-2"),
+    Opt("--min-kmers", kNat, &Args::min_kmers),
+    Opt("--use-full-kmer", &Args::use_full_kmer),
+    Opt("--n-fixed", kNat, &Args::n_fixed),
+    Opt("--min-af", &Args::min_af),
+    Opt("--no-end-filter", &Args::no_end_filter),
+    Opt("--no-strand-filter", &Args::no_strand_filter),
+    Opt("--no-strand-balance-filter", &Args::no_strand_balance_filter),
+    Opt("--balance-ratio", &Args::balance_ratio),
+    Opt("--n-per-strand", kNat, &Args::n_per_strand),
+    Opt("--strand_odds", &Args::strand_odds),
+    Opt("--min-depth", kNat, &Args::min_depth),
+    Opt("--min-variant-depth", kNat, &Args::min_variant_depth),
+    Opt("--noise-multiplier", &Args::noise_multiplier),
+    Opt("--pileup", &Args::pileup),
+    Opt("--alignment", &Args::alignment),
+    Opt("--keep-kmer-info", &Args::keep_kmer_info),
+    Opt("--min-base-qual", kInt, &Args::min_base_qual),
+    Opt("--primers", &Args::primers),
+    Opt("--primer-mismatches", kInt, &Args::primer_mismatches),
+    Opt("--adapter", &Args::adapters),
+    Opt("--adapter-min-overlap", kInt, &Args::adapter_min_overlap),
+    Opt("--adapter-error-rate", &Args::adapter_error_rate),
+    Opt("--consensus", &Args::consensus),
+    Opt("--consensus-min-depth", kInt, &Args::consensus_min_depth),
+    Opt("--consensus-min-freq", &Args::consensus_min_freq),
+    Opt("--regions", &Args::regions),
+    Opt("--region-window", kInt, &Args::region_window),
+    Opt("--region-min-depth", kInt, &Args::region_min_depth),
+    Opt("--indels", &Args::indels),
+    Opt("--indel-max-len", kInt, &Args::indel_max_len),
+    Opt("--indel-max-mismatches", kInt, &Args::indel_max_mismatches),
+    Opt("--indel-min-reads", kInt, &Args::indel_min_reads),
+    Opt("--indel-min-af", &Args::indel_min_af),
+    Opt("--consensus-indels", &Args::consensus_indels),
+    Opt("--junctions", &Args::junctions),
+    Opt("--junction-min-len", kInt, &Args::junction_min_len),
+    Opt("--junction-max-mismatches", kInt, &Args::junction_max_mismatches),
+    Opt("--junction-min-reads", kInt, &Args::junction_min_reads),
+    Opt("--copybacks", &Args::copybacks),
+    Opt("--copyback-max-mismatches", kInt, &Args::copyback_max_mismatches),
+    Opt("--copyback-min-reads", kInt, &Args::copyback_min_reads),
+    Opt("--copyback-min-dist", kInt, &Args::copyback_min_dist),
+    Opt("--chimeras", &Args::chimeras),
+    Opt("--chimera-max-mismatches", kInt, &Args::chimera_max_mismatches),
+    Opt("--chimera-min-reads", kInt, &Args::chimera_min_reads),
+    Opt("--breakends", &Args::breakends),
+    Opt("--breakend-min-clip", kInt, &Args::breakend_min_clip),
+    Opt("--breakend-max-mismatches", kInt, &Args::breakend_max_mismatches),
+    Opt("--breakend-min-reads", kInt, &Args::breakend_min_reads),
+    Opt("--duplications", &Args::duplications),
+    Opt("--duplication-min-len", kInt, &Args::duplication_min_len),
+    Opt("--duplication-max-mismatches", kInt, &Args::duplication_max_mismatches),
+    Opt("--duplication-min-reads", kInt, &Args::duplication_min_reads),
+    Opt("--linkage", &Args::linkage),
+    Opt("--link-max-mismatches", kInt, &Args::link_max_mismatches),
+    Opt("--link-max-dist", kInt, &Args::link_max_dist),
+    Opt("--link-min-reads", kInt, &Args::link_min_reads),
+    Opt("--codons", &Args::codons),
+    Opt("--codon-min-reads", kInt, &Args::codon_min_reads),
+    Opt("--codon-min-freq", &Args::codon_min_freq),
+    Opt("--codon-max-mismatches", kInt, &Args::codon_max_mismatches),
+    Opt("--haplotypes", &Args::haplotypes),
+    Opt("--hap-window", kInt, &Args::hap_window),
+    Opt("--hap-step", kInt, &Args::hap_step),
+    Opt("--hap-min-reads", kInt, &Args::hap_min_reads),
+    Opt("--hap-min-freq", &Args::hap_min_freq),
+    Opt("--hap-max-mismatches", kInt, &Args::hap_max_mismatches),
+    Opt("--read-pileup", &Args::read_pileup),
+    Opt("--read-pileup-end", kInt, &Args::read_pileup_end),
+    Opt("--read-pileup-max-mismatches", kInt, &Args::read_pileup_max_mismatches),
+    Opt("--distances", &Args::distances),
+    Opt("--clusters", kInt, &Args::clusters),
+    Opt("--cluster-min-breadth", &Args::cluster_min_breadth),
+    Opt("--mst", &Args::mst),
+    Opt("--mst-min-breadth", &Args::mst_min_breadth),
+};
+static_assert(sizeof kOpts / sizeof kOpts[0] <= 128, "Args::given_rows has a bit per row");
+
+const Opt* find_opt(const std::string& name) {   // by either name; nullptr: no such option
+    for (const Opt& o : kOpts)
+        if (name == o.name || (o.alias && name == o.alias)) return &o;
+    return nullptr;
 }
 
 Args parse_args(int argc, char** argv) {
@@ -234,7 +351,6 @@ Args parse_args(int argc, char** argv) {
     std::vector<std::string> tok;
     for (int i = 2; i < argc; i++) tok.push_back(argv[i]);
     size_t i = 0;
-    auto is_flag = [](const std::string& s) { return s.size() >= 2 && s[0] == '-' && !(isdigit((unsigned char)s[1]) && s.size() > 2 && s[1] != '1' && s[1] != '2'); };
     while (i < tok.size()) {
         std::string opt = tok[i++], inline_val;
         bool has_inline = false;
@@ -259,144 +375,16 @@ Args parse_args(int argc, char** argv) {
             while (i < tok.size() && !(tok[i].size() >= 2 && tok[i][0] == '-')) dst.push_back(tok[i++]);
             if (!has_inline && dst.size() == before) { fprintf(stderr, "error: a value is required for '%s'\n", opt.c_str()); exit(2); }
         };
-        (void)is_flag;
-        if (opt == "-g" || opt == "--genomes") { many(a.genomes); a.has_genomes = true; }
-        else if (opt == "-k" || opt == "--kmer-size") a.kmer = to_long(opt, one());
-        else if (opt == "-o" || opt == "--output") a.output = one();
-        else if (opt == "-t" || opt == "--threads") a.threads = to_long(opt, one());
-        else if (opt == "--debug") a.debug = true;
-        else if (opt == "--verbose") a.verbose = true;
-        else if (!call) { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
-        else if (opt == "-d" || opt == "--db") { a.db = one(); a.has_db = true; }
-        else if (opt == "-r" || opt == "--reads") many(a.reads);
-        else if (opt == "-1" || opt == "--first-pairs") many(a.first_pairs);
-        else if (opt == "-2" || opt == "--second-pairs") many(a.second_pairs);
-        else if (opt == "--min-kmers") a.min_kmers = to_long(opt, one());
-        else if (opt == "--use-full-kmer") a.use_full_kmer = true;
-        else if (opt == "--n-fixed") a.n_fixed = to_long(opt, one());
-        else if (opt == "--min-af") a.min_af = to_double(opt, one());
-        else if (opt == "--no-end-filter") a.no_end_filter = true;
-        else if (opt == "--no-strand-filter") a.no_strand_filter = true;
-        else if (opt == "--no-strand-balance-filter") a.no_strand_balance_filter = true;
-        else if (opt == "--balance-ratio") a.balance_ratio = to_double(opt, one());
-        else if (opt == "--n-per-strand") a.n_per_strand = to_long(opt, one());
-        else if (opt == "--strand_odds") a.strand_odds = to_double(opt, one());
-        else if (opt == "--min-depth") a.min_depth = to_long(opt, one());
-        else if (opt == "--min-variant-depth") a.min_variant_depth = to_long(opt, one());
-        else if (opt == "--noise-multiplier") a.noise_multiplier = to_double(opt, one());
-        else if (opt == "--pileup") a.pileup = true;
-        else if (opt == "--alignment") a.alignment = true;
-        else if (opt == "--keep-kmer-info") a.keep_kmer_info = true;
-        else if (opt == "--min-base-qual") {   // (any integer here: a value outside 0..93 is refused by check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            a.min_base_qual = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
+        const Opt* o = find_opt(opt);
+        if (!o || (!call && !o->build)) { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
+        a.given_rows.set((size_t)(o - kOpts));
+        switch (o->kind) {
+            case kSwitch: a.*o->b = true; break;
+            case kNat: case kInt: a.*o->l = to_long(opt, one(), o->kind == kInt); break;
+            case kReal: a.*o->d = to_double(opt, one()); break;
+            case kText: a.*o->s = one(); break;
+            case kTexts: many(a.*o->v); break;
         }
-        else if (opt == "--primers") { a.primers = one(); a.has_primers = true; }
-        else if (opt == "--primer-mismatches") {   // (any integer here: a value outside 0..3 is refused by check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            a.primer_mismatches = strtol(v.c_str(), &end, 10);
-            a.has_primer_mismatches = true;
-            if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
-        }
-        else if (opt == "--adapter") many(a.adapters);
-        else if (opt == "--adapter-min-overlap") {   // (any integer, any number here: what is out of range is refused by check_call_args)
-            const std::string v = one();
-            char* end = nullptr;
-            a.adapter_min_overlap = strtol(v.c_str(), &end, 10);
-            a.has_adapter_min_overlap = true;
-            if (v.empty() || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), opt.c_str()); exit(2); }
-        }
-        else if (opt == "--consensus") a.consensus = true;
-        else if (opt == "--consensus-min-depth") { a.consensus_min_depth = any_long(opt, one()); a.has_consensus_min_depth = true; }   // (check_call_args)
-        else if (opt == "--consensus-min-freq") { a.consensus_min_freq = to_double(opt, one()); a.has_consensus_min_freq = true; }
-        else if (opt == "--regions") { a.regions = one(); a.has_regions = true; }
-        else if (opt == "--region-window" || opt == "--region-min-depth") {   // (any integer here: what is out of range is refused by check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--region-window") { a.region_window = x; a.has_region_window = true; }
-            else { a.region_min_depth = x; a.has_region_min_depth = true; }
-        }
-        else if (opt == "--indels") a.indels = true;
-        else if (opt == "--consensus-indels") a.consensus_indels = true;
-        else if (opt == "--indel-max-len" || opt == "--indel-max-mismatches" || opt == "--indel-min-reads") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--indel-max-len") { a.indel_max_len = x; a.has_indel_max_len = true; }
-            else if (opt == "--indel-max-mismatches") { a.indel_max_mismatches = x; a.has_indel_max_mismatches = true; }
-            else { a.indel_min_reads = x; a.has_indel_min_reads = true; }
-        }
-        else if (opt == "--junctions") a.junctions = true;
-        else if (opt == "--junction-min-len" || opt == "--junction-max-mismatches" || opt == "--junction-min-reads") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--junction-min-len") { a.junction_min_len = x; a.has_junction_min_len = true; }
-            else if (opt == "--junction-max-mismatches") { a.junction_max_mismatches = x; a.has_junction_max_mismatches = true; }
-            else { a.junction_min_reads = x; a.has_junction_min_reads = true; }
-        }
-        else if (opt == "--copybacks") a.copybacks = true;
-        else if (opt == "--copyback-max-mismatches" || opt == "--copyback-min-reads" || opt == "--copyback-min-dist") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--copyback-max-mismatches") { a.copyback_max_mismatches = x; a.has_copyback_max_mismatches = true; }
-            else if (opt == "--copyback-min-reads") { a.copyback_min_reads = x; a.has_copyback_min_reads = true; }
-            else { a.copyback_min_dist = x; a.has_copyback_min_dist = true; }
-        }
-        else if (opt == "--chimeras") a.chimeras = true;
-        else if (opt == "--chimera-max-mismatches" || opt == "--chimera-min-reads") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--chimera-max-mismatches") { a.chimera_max_mismatches = x; a.has_chimera_max_mismatches = true; }
-            else { a.chimera_min_reads = x; a.has_chimera_min_reads = true; }
-        }
-        else if (opt == "--breakends") a.breakends = true;
-        else if (opt == "--breakend-min-clip" || opt == "--breakend-max-mismatches" || opt == "--breakend-min-reads") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--breakend-min-clip") { a.breakend_min_clip = x; a.has_breakend_min_clip = true; }
-            else if (opt == "--breakend-max-mismatches") { a.breakend_max_mismatches = x; a.has_breakend_max_mismatches = true; }
-            else { a.breakend_min_reads = x; a.has_breakend_min_reads = true; }
-        }
-        else if (opt == "--duplications") a.duplications = true;
-        else if (opt == "--duplication-min-len" || opt == "--duplication-max-mismatches" || opt == "--duplication-min-reads") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--duplication-min-len") { a.duplication_min_len = x; a.has_duplication_min_len = true; }
-            else if (opt == "--duplication-max-mismatches") { a.duplication_max_mismatches = x; a.has_duplication_max_mismatches = true; }
-            else { a.duplication_min_reads = x; a.has_duplication_min_reads = true; }
-        }
-        else if (opt == "--linkage") a.linkage = true;
-        else if (opt == "--link-max-mismatches" || opt == "--link-max-dist" || opt == "--link-min-reads") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--link-max-mismatches") { a.link_max_mismatches = x; a.has_link_max_mismatches = true; }
-            else if (opt == "--link-max-dist") { a.link_max_dist = x; a.has_link_max_dist = true; }
-            else { a.link_min_reads = x; a.has_link_min_reads = true; }
-        }
-        else if (opt == "--codons") { a.codons = one(); a.has_codons = true; }
-        else if (opt == "--codon-min-reads" || opt == "--codon-max-mismatches") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--codon-min-reads") { a.codon_min_reads = x; a.has_codon_min_reads = true; }
-            else { a.codon_max_mismatches = x; a.has_codon_max_mismatches = true; }
-        }
-        else if (opt == "--haplotypes") { a.haplotypes = one(); a.has_haplotypes = true; }
-        else if (opt == "--hap-window" || opt == "--hap-step" || opt == "--hap-min-reads" || opt == "--hap-max-mismatches") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--hap-window") { a.hap_window = x; a.has_hap_window = true; }
-            else if (opt == "--hap-step") { a.hap_step = x; a.has_hap_step = true; }
-            else if (opt == "--hap-min-reads") { a.hap_min_reads = x; a.has_hap_min_reads = true; }
-            else { a.hap_max_mismatches = x; a.has_hap_max_mismatches = true; }
-        }
-        else if (opt == "--read-pileup") a.read_pileup = true;
-        else if (opt == "--read-pileup-end" || opt == "--read-pileup-max-mismatches") {   // (any integer here: check_call_args)
-            const long x = any_long(opt, one());
-            if (opt == "--read-pileup-end") { a.read_pileup_end = x; a.has_read_pileup_end = true; }
-            else { a.read_pileup_max_mismatches = x; a.has_read_pileup_max_mismatches = true; }
-        }
-        else if (opt == "--distances") a.distances = true;
-        else if (opt == "--clusters") { a.clusters = any_long(opt, one()); a.has_clusters = true; }   // (any integer here: check_call_args)
-        else if (opt == "--cluster-min-breadth") { a.cluster_min_breadth = to_double(opt, one()); a.has_cluster_min_breadth = true; }
-        else if (opt == "--mst") a.mst = true;
-        else if (opt == "--mst-min-breadth") { a.mst_min_breadth = to_double(opt, one()); a.has_mst_min_breadth = true; }
-        else if (opt == "--hap-min-freq") { a.hap_min_freq = to_double(opt, one()); a.has_hap_min_freq = true; }
-        else if (opt == "--codon-min-freq") { a.codon_min_freq = to_double(opt, one()); a.has_codon_min_freq = true; }
-        else if (opt == "--indel-min-af") { a.indel_min_af = to_double(opt, one()); a.has_indel_min_af = true; }
-        else if (opt == "--adapter-error-rate") { a.adapter_error_rate = to_double(opt, one()); a.has_adapter_error_rate = true; }
-        else { fprintf(stderr, "error: unexpected argument '%s' found\n", opt.c_str()); exit(2); }
     }
     return a;
 }
@@ -413,6 +401,12 @@ void check_common(const Args& a, const char* target) {
 }
 
 }  // namespace
+
+bool Args::given(const char* name) const {
+    const Opt* o = find_opt(name);
+    if (!o) die("bronko", std::string("no option ") + name + " in the option table");
+    return given_rows.test((size_t)(o - kOpts));
+}
 
 // ---- bronko build (build.rs:102-120) ------------------------------------------------------------------------
 // build_indexes (build.rs:145-231): on the GPU when one is visible (bk_build_index: one thread per k-mer, stable device sort), on
@@ -533,13 +527,43 @@ std::vector<std::string> expand_adapters(const char* T, const Args& a) {
     return out;
 }
 
-void check_call_args(const Args& a) {   // call.rs:30-136
-    const char* T = "bronko::call";
+// ---- the rules of `bronko call`'s arguments (call.rs:30-136 and every report's own), one ordered list -----------------------------------
+// A rule is a "needs" rule -- the option, what must hold when it was given, the text behind "needs" --, a "range" rule -- the
+// option whose value is meant, its bounds, whether it holds only when the option was given, the sentence's subject where that is not
+// the option's name -- or a check written by hand.  check_call_args walks the list; the first violation ends the run, so the
+// order is part of the surface.
+using Pred = bool (*)(const Args&);
+struct Rule {
+    const char* opt = nullptr;
+    Pred ok = nullptr;                     // needs
+    const char* text = nullptr;            // needs: what follows "needs"; range: the subject (nullptr: opt)
+    long lo = 0, hi = 0;                   // range
+    bool no_hi = false, if_given = false;
+    const char* after = "";                // range: what follows the bounds
+    void (*by_hand)(const Args&) = nullptr;
+    Rule when_given() const { Rule r = *this; r.if_given = true; return r; }
+};
+Rule needs(const char* opt, Pred ok, const char* what) { Rule r; r.opt = opt; r.ok = ok; r.text = what; return r; }
+Rule range(const char* opt, long lo, long hi, const char* subject = nullptr, const char* after = "") {
+    Rule r; r.opt = opt; r.lo = lo; r.hi = hi; r.text = subject; r.after = after; return r;
+}
+Rule at_least(const char* opt, long lo, const char* subject = nullptr) { Rule r; r.opt = opt; r.lo = lo; r.no_hi = true; r.text = subject; return r; }
+Rule by_hand(void (*f)(const Args&)) { Rule r; r.by_hand = f; return r; }
+
+const char* const TC = "bronko::call";
+template <bool Args::*sw> bool on(const Args& a) { return a.*sw; }
+template <std::string Args::*s> bool filled(const Args& a) { return !(a.*s).empty(); }
+template <bool (Args::*f)() const> bool is(const Args& a) { return (a.*f)(); }
+bool with_adapters(const Args& a) { return !a.adapters.empty(); }
+bool with_regions(const Args& a) { return a.has_regions() || a.has_region_window(); }
+
+void reference_checks(const Args& a) {   // call.rs:30-136, its warnings and errors as they are
+    const char* T = TC;
     if (a.kmer % 2 != 1 || a.kmer > 31 || a.kmer < 15) die(T, "Invalid kmer size, must be odd and between [15-31]");
     for (const auto& f : a.reads)
         if (!check_fastq(f)) die(T, f + " does not appear to be a fastq file (must be .fq(.gz)/.fastq(.gz)/.fnq(.gz))");
-    if (a.has_genomes && a.has_db) die(T, "Please provide either a db or the genomes you would like to index, not both.");
-    if (!a.has_genomes && !a.has_db) die(T, "Please provide either a db or the genomes you would like to index.");
+    if (a.has_genomes() && a.has_db()) die(T, "Please provide either a db or the genomes you would like to index, not both.");
+    if (!a.has_genomes() && !a.has_db()) die(T, "Please provide either a db or the genomes you would like to index.");
     for (const auto& g : a.genomes)
         if (!check_fasta(g)) die(T, g + " does not appear to be a fasta file (must be .fa(.gz)/.fasta(.gz)/.fna(.gz))");
     check_common(a, T);
@@ -556,135 +580,118 @@ void check_call_args(const Args& a) {   // call.rs:30-136
     else if (a.noise_multiplier > 2.0) LOG_WARN(T, "Strand balance ratio is set above 2, may experience a drop in recall (we recommend ~1.5)");
     else if (a.noise_multiplier == 1.0) LOG_WARN(T, "Noise multiplier for variant detection set to 1.0, all variants will pass this filter");
     if (a.first_pairs.size() != a.second_pairs.size()) die(T, "Number of paired end sequences do not match, exiting.");
-    if (a.min_base_qual < 0 || a.min_base_qual > 93) die(T, "Minimum base quality must be between 0 and 93 (Phred+33), got " + std::to_string(a.min_base_qual));
-    if (a.has_primer_mismatches && !a.has_primers) die(T, "--primer-mismatches needs --primers");
-    if (a.primer_mismatches < 0 || a.primer_mismatches > BK_PRIMER_MAX_MISMATCHES)
-        die(T, "Primer mismatches must be between 0 and " + std::to_string(BK_PRIMER_MAX_MISMATCHES) + ", got " + std::to_string(a.primer_mismatches));
-    if (a.has_adapter_min_overlap && a.adapters.empty()) die(T, "--adapter-min-overlap needs --adapter");
-    if (a.has_adapter_error_rate && a.adapters.empty()) die(T, "--adapter-error-rate needs --adapter");
-    if (a.has_consensus_min_depth && !a.consensus) die(T, "--consensus-min-depth needs --consensus");
-    if (a.has_consensus_min_freq && !a.consensus) die(T, "--consensus-min-freq needs --consensus");
-    if (a.consensus_min_depth < 1) die(T, "Consensus minimum depth must be at least 1, got " + std::to_string(a.consensus_min_depth));
-    if (!(a.consensus_min_freq >= 0.0 && a.consensus_min_freq <= 1.0)) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "Consensus minimum frequency must be between 0 and 1, got %g", a.consensus_min_freq);
-        die(T, buf);
-    }
-    if (a.has_regions && a.has_region_window) die(T, "--regions and --region-window cannot be given together");
-    if (a.has_region_min_depth && !a.has_regions && !a.has_region_window) die(T, "--region-min-depth needs --regions or --region-window");
-    if (a.has_regions && a.regions.empty()) die(T, "--regions needs a BED file");
-    if (a.has_region_window && a.region_window < 1) die(T, "Region window must be at least 1, got " + std::to_string(a.region_window));
-    if (a.region_min_depth < 1) die(T, "Region minimum depth must be at least 1, got " + std::to_string(a.region_min_depth));
-    if (a.has_indel_max_len && !a.indels) die(T, "--indel-max-len needs --indels");
-    if (a.has_indel_max_mismatches && !a.indels) die(T, "--indel-max-mismatches needs --indels");
-    if (a.has_indel_min_reads && !a.indels) die(T, "--indel-min-reads needs --indels");
-    if (a.has_indel_min_af && !a.indels) die(T, "--indel-min-af needs --indels");
-    if (a.indel_max_len < 1 || a.indel_max_len > BK_INDEL_MAX_LEN) die(T, "--indel-max-len must be between 1 and " + std::to_string(BK_INDEL_MAX_LEN) + ", got " + std::to_string(a.indel_max_len));
-    if (a.indel_max_mismatches < 0 || a.indel_max_mismatches > 8) die(T, "--indel-max-mismatches must be between 0 and 8, got " + std::to_string(a.indel_max_mismatches));
-    if (a.indel_min_reads < 1) die(T, "--indel-min-reads must be at least 1, got " + std::to_string(a.indel_min_reads));
-    if (a.consensus_indels && !a.consensus) die(T, "--consensus-indels needs --consensus");
-    if (a.consensus_indels && !a.indels) die(T, "--consensus-indels needs --indels");
-    if (a.has_junction_min_len && !a.junctions) die(T, "--junction-min-len needs --junctions");
-    if (a.has_junction_max_mismatches && !a.junctions) die(T, "--junction-max-mismatches needs --junctions");
-    if (a.has_junction_min_reads && !a.junctions) die(T, "--junction-min-reads needs --junctions");
-    if (a.junction_min_len < 1 || a.junction_min_len > (long)kJunctionMaxLen) die(T, "--junction-min-len must be between 1 and " + std::to_string(kJunctionMaxLen) + ", got " + std::to_string(a.junction_min_len));
-    if (a.junction_max_mismatches < 0 || a.junction_max_mismatches > kJunctionMaxMismatches) die(T, "--junction-max-mismatches must be between 0 and 8, got " + std::to_string(a.junction_max_mismatches));
-    if (a.junction_min_reads < 1) die(T, "--junction-min-reads must be at least 1, got " + std::to_string(a.junction_min_reads));
-    if (a.has_copyback_max_mismatches && !a.copybacks) die(T, "--copyback-max-mismatches needs --copybacks");
-    if (a.has_copyback_min_reads && !a.copybacks) die(T, "--copyback-min-reads needs --copybacks");
-    if (a.has_copyback_min_dist && !a.copybacks) die(T, "--copyback-min-dist needs --copybacks");
-    if (a.copyback_max_mismatches < 0 || a.copyback_max_mismatches > kCopybackMaxMismatches) die(T, "--copyback-max-mismatches must be between 0 and 8, got " + std::to_string(a.copyback_max_mismatches));
-    if (a.copyback_min_reads < 1) die(T, "--copyback-min-reads must be at least 1, got " + std::to_string(a.copyback_min_reads));
-    if (a.copyback_min_dist < 0 || a.copyback_min_dist > 0xffffffffl) die(T, "--copyback-min-dist must be between 0 and 4294967295, got " + std::to_string(a.copyback_min_dist));
-    if (a.has_chimera_max_mismatches && !a.chimeras) die(T, "--chimera-max-mismatches needs --chimeras");
-    if (a.has_chimera_min_reads && !a.chimeras) die(T, "--chimera-min-reads needs --chimeras");
-    if (a.chimera_max_mismatches < 0 || a.chimera_max_mismatches > kChimeraMaxMismatches) die(T, "--chimera-max-mismatches must be between 0 and 8, got " + std::to_string(a.chimera_max_mismatches));
-    if (a.chimera_min_reads < 1) die(T, "--chimera-min-reads must be at least 1, got " + std::to_string(a.chimera_min_reads));
-    if (a.has_breakend_min_clip && !a.breakends) die(T, "--breakend-min-clip needs --breakends");
-    if (a.has_breakend_max_mismatches && !a.breakends) die(T, "--breakend-max-mismatches needs --breakends");
-    if (a.has_breakend_min_reads && !a.breakends) die(T, "--breakend-min-reads needs --breakends");
-    if (a.breakend_min_clip < kBreakendMinClipLo || a.breakend_min_clip > kBreakendMinClipHi) die(T, "--breakend-min-clip must be between 16 and 65519, got " + std::to_string(a.breakend_min_clip));
-    if (a.breakend_max_mismatches < 0 || a.breakend_max_mismatches > kBreakendMaxMismatches) die(T, "--breakend-max-mismatches must be between 0 and 8, got " + std::to_string(a.breakend_max_mismatches));
-    if (a.breakend_min_reads < 1) die(T, "--breakend-min-reads must be at least 1, got " + std::to_string(a.breakend_min_reads));
-    if (a.has_duplication_min_len && !a.duplications) die(T, "--duplication-min-len needs --duplications");
-    if (a.has_duplication_max_mismatches && !a.duplications) die(T, "--duplication-max-mismatches needs --duplications");
-    if (a.has_duplication_min_reads && !a.duplications) die(T, "--duplication-min-reads needs --duplications");
-    if (a.duplication_min_len < 1 || a.duplication_min_len > (long)kDuplicationMaxLen) die(T, "--duplication-min-len must be between 1 and " + std::to_string(kDuplicationMaxLen) + ", got " + std::to_string(a.duplication_min_len));
-    if (a.duplication_max_mismatches < 0 || a.duplication_max_mismatches > kDuplicationMaxMismatches) die(T, "--duplication-max-mismatches must be between 0 and 8, got " + std::to_string(a.duplication_max_mismatches));
-    if (a.duplication_min_reads < 1) die(T, "--duplication-min-reads must be at least 1, got " + std::to_string(a.duplication_min_reads));
-    if (a.has_link_max_mismatches && !a.linkage) die(T, "--link-max-mismatches needs --linkage");
-    if (a.has_link_max_dist && !a.linkage) die(T, "--link-max-dist needs --linkage");
-    if (a.has_link_min_reads && !a.linkage) die(T, "--link-min-reads needs --linkage");
-    if (a.link_max_mismatches < 0 || a.link_max_mismatches > kLinkMaxMismatches) die(T, "--link-max-mismatches must be between 0 and 8, got " + std::to_string(a.link_max_mismatches));
-    if (a.link_max_dist < 1 || a.link_max_dist > (long)kLinkMaxDist) die(T, "--link-max-dist must be between 1 and " + std::to_string(kLinkMaxDist) + ", got " + std::to_string(a.link_max_dist));
-    if (a.link_min_reads < 1) die(T, "--link-min-reads must be at least 1, got " + std::to_string(a.link_min_reads));
-    if (a.has_indel_min_af && !(a.indel_min_af >= 0.0 && a.indel_min_af <= 1.0)) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "--indel-min-af must be between 0 and 1, got %g", a.indel_min_af);
-        die(T, buf);
-    }
-    if (a.has_codon_min_reads && !a.has_codons) die(T, "--codon-min-reads needs --codons");
-    if (a.has_codon_min_freq && !a.has_codons) die(T, "--codon-min-freq needs --codons");
-    if (a.has_codon_max_mismatches && !a.has_codons) die(T, "--codon-max-mismatches needs --codons");
-    if (a.has_codons && a.codons.empty()) die(T, "--codons needs a BED file");
-    if (a.codon_min_reads < 1) die(T, "--codon-min-reads must be at least 1, got " + std::to_string(a.codon_min_reads));
-    if (a.codon_max_mismatches < 0 || a.codon_max_mismatches > kLinkMaxMismatches) die(T, "--codon-max-mismatches must be between 0 and 8, got " + std::to_string(a.codon_max_mismatches));
-    if (a.has_codon_min_freq && !(a.codon_min_freq >= 0.0 && a.codon_min_freq <= 1.0)) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "--codon-min-freq must be between 0 and 1, got %g", a.codon_min_freq);
-        die(T, buf);
-    }
-    if (a.has_codons && a.linkage && a.codon_max_mismatches != a.link_max_mismatches)   // (one row store, one M)
-        die(T, "--linkage and --codons count the same placed reads: --link-max-mismatches (" + std::to_string(a.link_max_mismatches) + ") and --codon-max-mismatches (" +
-                   std::to_string(a.codon_max_mismatches) + ") must be equal");
-    if (a.has_haplotypes && a.has_hap_window) die(T, "--haplotypes and --hap-window cannot be given together");
-    if (a.has_hap_step && !a.has_hap_window) die(T, "--hap-step needs --hap-window");
-    if (a.has_hap_min_reads && !a.haps()) die(T, "--hap-min-reads needs --haplotypes or --hap-window");
-    if (a.has_hap_min_freq && !a.haps()) die(T, "--hap-min-freq needs --haplotypes or --hap-window");
-    if (a.has_hap_max_mismatches && !a.haps()) die(T, "--hap-max-mismatches needs --haplotypes or --hap-window");
-    if (a.has_haplotypes && a.haplotypes.empty()) die(T, "--haplotypes needs a BED file");
-    if (a.has_hap_window && (a.hap_window < 1 || a.hap_window > (long)kHapMaxLen)) die(T, "--hap-window must be between 1 and 65520, got " + std::to_string(a.hap_window));
-    if (a.has_hap_step && a.hap_step < 1) die(T, "--hap-step must be at least 1, got " + std::to_string(a.hap_step));
-    if (a.hap_min_reads < 1) die(T, "--hap-min-reads must be at least 1, got " + std::to_string(a.hap_min_reads));
-    if (a.hap_max_mismatches < 0 || a.hap_max_mismatches > kLinkMaxMismatches) die(T, "--hap-max-mismatches must be between 0 and 8, got " + std::to_string(a.hap_max_mismatches));
-    if (a.has_hap_min_freq && !(a.hap_min_freq >= 0.0 && a.hap_min_freq <= 1.0)) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "--hap-min-freq must be between 0 and 1, got %g", a.hap_min_freq);
-        die(T, buf);
-    }
-    if (a.haps() && a.linkage && a.hap_max_mismatches != a.link_max_mismatches)   // (one row store, one M)
-        die(T, "--linkage and --haplotypes count the same placed reads: --link-max-mismatches (" + std::to_string(a.link_max_mismatches) + ") and --hap-max-mismatches (" +
-                   std::to_string(a.hap_max_mismatches) + ") must be equal");
-    if (a.haps() && a.has_codons && a.hap_max_mismatches != a.codon_max_mismatches)
-        die(T, "--codons and --haplotypes count the same placed reads: --codon-max-mismatches (" + std::to_string(a.codon_max_mismatches) + ") and --hap-max-mismatches (" +
-                   std::to_string(a.hap_max_mismatches) + ") must be equal");
-    if (a.has_read_pileup_end && !a.read_pileup) die(T, "--read-pileup-end needs --read-pileup");
-    if (a.has_read_pileup_max_mismatches && !a.read_pileup) die(T, "--read-pileup-max-mismatches needs --read-pileup");
-    if (a.read_pileup_end < 0 || a.read_pileup_end > (long)kReadPileupMaxEnd) die(T, "--read-pileup-end must be between 0 and 255, got " + std::to_string(a.read_pileup_end));
-    if (a.read_pileup_max_mismatches < 0 || a.read_pileup_max_mismatches > kLinkMaxMismatches)
-        die(T, "--read-pileup-max-mismatches must be between 0 and 8, got " + std::to_string(a.read_pileup_max_mismatches));
-    struct { bool on; const char* flag; const char* opt; long m; } const others[] = {{a.linkage, "--linkage", "--link-max-mismatches", a.link_max_mismatches},
-                                                                                     {a.has_codons, "--codons", "--codon-max-mismatches", a.codon_max_mismatches},
-                                                                                     {a.haps(), "--haplotypes", "--hap-max-mismatches", a.hap_max_mismatches}};
-    for (const auto& o : others)   // (one row store, one M)
-        if (a.read_pileup && o.on && o.m != a.read_pileup_max_mismatches)
-            die(T, std::string(o.flag) + " and --read-pileup count the same placed reads: " + o.opt + " (" + std::to_string(o.m) + ") and --read-pileup-max-mismatches (" +
-                       std::to_string(a.read_pileup_max_mismatches) + ") must be equal");
-    if (a.distances && !a.consensus) die(T, "--distances needs --consensus");
-    if (a.has_clusters && !a.distances) die(T, "--clusters needs --distances");
-    if (a.has_cluster_min_breadth && !a.has_clusters) die(T, "--cluster-min-breadth needs --clusters");
-    if (a.clusters < 0) die(T, "--clusters must be at least 0, got " + std::to_string(a.clusters));
-    if (!(a.cluster_min_breadth >= 0.0 && a.cluster_min_breadth <= 1.0)) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "--cluster-min-breadth must be between 0 and 1, got %g", a.cluster_min_breadth);
-        die(T, buf);
-    }
-    if (a.mst && !a.distances) die(T, "--mst needs --distances");
-    if (a.has_mst_min_breadth && !a.mst) die(T, "--mst-min-breadth needs --mst");
-    if (!(a.mst_min_breadth >= 0.0 && a.mst_min_breadth <= 1.0)) {
-        char buf[128];
-        snprintf(buf, sizeof buf, "--mst-min-breadth must be between 0 and 1, got %g", a.mst_min_breadth);
-        die(T, buf);
+}
+void regions_or_window(const Args& a) { if (a.has_regions() && a.has_region_window()) die(TC, "--regions and --region-window cannot be given together"); }
+void haplotypes_or_window(const Args& a) { if (a.has_haplotypes() && a.has_hap_window()) die(TC, "--haplotypes and --hap-window cannot be given together"); }
+// one row store, one M: the N-th of its four readers against the ones before it
+template <int N>
+void one_m(const Args& a) {
+    const struct { bool on; const char* flag; const char* opt; long m; } r[] = {
+        {a.linkage, "--linkage", "--link-max-mismatches", a.link_max_mismatches},
+        {a.has_codons(), "--codons", "--codon-max-mismatches", a.codon_max_mismatches},
+        {a.haps(), "--haplotypes", "--hap-max-mismatches", a.hap_max_mismatches},
+        {a.read_pileup, "--read-pileup", "--read-pileup-max-mismatches", a.read_pileup_max_mismatches}};
+    for (int i = 0; i < N; i++)
+        if (r[N].on && r[i].on && r[i].m != r[N].m)
+            die(TC, std::string(r[i].flag) + " and " + r[N].flag + " count the same placed reads: " + r[i].opt + " (" + std::to_string(r[i].m) + ") and " + r[N].opt + " (" +
+                        std::to_string(r[N].m) + ") must be equal");
+}
+
+const Rule kRules[] = {
+    by_hand(reference_checks),
+    range("--min-base-qual", 0, 93, "Minimum base quality", " (Phred+33)"),
+    needs("--primer-mismatches", is<&Args::has_primers>, "--primers"),
+    range("--primer-mismatches", 0, BK_PRIMER_MAX_MISMATCHES, "Primer mismatches"),
+    needs("--adapter-min-overlap --adapter-error-rate", with_adapters, "--adapter"),
+    needs("--consensus-min-depth --consensus-min-freq", on<&Args::consensus>, "--consensus"),
+    at_least("--consensus-min-depth", 1, "Consensus minimum depth"),
+    range("--consensus-min-freq", 0, 1, "Consensus minimum frequency"),
+    by_hand(regions_or_window),
+    needs("--region-min-depth", with_regions, "--regions or --region-window"),
+    needs("--regions", filled<&Args::regions>, "a BED file"),
+    at_least("--region-window", 1, "Region window").when_given(),
+    at_least("--region-min-depth", 1, "Region minimum depth"),
+    needs("--indel-max-len --indel-max-mismatches --indel-min-reads --indel-min-af", on<&Args::indels>, "--indels"),
+    range("--indel-max-len", 1, BK_INDEL_MAX_LEN),
+    range("--indel-max-mismatches", 0, kIndelMaxMismatches),
+    at_least("--indel-min-reads", 1),
+    needs("--consensus-indels", on<&Args::consensus>, "--consensus"),
+    needs("--consensus-indels", on<&Args::indels>, "--indels"),
+    needs("--junction-min-len --junction-max-mismatches --junction-min-reads", on<&Args::junctions>, "--junctions"),
+    range("--junction-min-len", 1, (long)kJunctionMaxLen),
+    range("--junction-max-mismatches", 0, kJunctionMaxMismatches),
+    at_least("--junction-min-reads", 1),
+    needs("--copyback-max-mismatches --copyback-min-reads --copyback-min-dist", on<&Args::copybacks>, "--copybacks"),
+    range("--copyback-max-mismatches", 0, kCopybackMaxMismatches),
+    at_least("--copyback-min-reads", 1),
+    range("--copyback-min-dist", 0, 0xffffffffl),
+    needs("--chimera-max-mismatches --chimera-min-reads", on<&Args::chimeras>, "--chimeras"),
+    range("--chimera-max-mismatches", 0, kChimeraMaxMismatches),
+    at_least("--chimera-min-reads", 1),
+    needs("--breakend-min-clip --breakend-max-mismatches --breakend-min-reads", on<&Args::breakends>, "--breakends"),
+    range("--breakend-min-clip", kBreakendMinClipLo, kBreakendMinClipHi),
+    range("--breakend-max-mismatches", 0, kBreakendMaxMismatches),
+    at_least("--breakend-min-reads", 1),
+    needs("--duplication-min-len --duplication-max-mismatches --duplication-min-reads", on<&Args::duplications>, "--duplications"),
+    range("--duplication-min-len", 1, (long)kDuplicationMaxLen),
+    range("--duplication-max-mismatches", 0, kDuplicationMaxMismatches),
+    at_least("--duplication-min-reads", 1),
+    needs("--link-max-mismatches --link-max-dist --link-min-reads", on<&Args::linkage>, "--linkage"),
+    range("--link-max-mismatches", 0, kLinkMaxMismatches),
+    range("--link-max-dist", 1, (long)kLinkMaxDist),
+    at_least("--link-min-reads", 1),
+    range("--indel-min-af", 0, 1).when_given(),   // (behind the --link-* rules, where it has always stood)
+    needs("--codon-min-reads --codon-min-freq --codon-max-mismatches", is<&Args::has_codons>, "--codons"),
+    needs("--codons", filled<&Args::codons>, "a BED file"),
+    at_least("--codon-min-reads", 1),
+    range("--codon-max-mismatches", 0, kLinkMaxMismatches),
+    range("--codon-min-freq", 0, 1).when_given(),
+    by_hand(one_m<1>),
+    by_hand(haplotypes_or_window),
+    needs("--hap-step", is<&Args::has_hap_window>, "--hap-window"),
+    needs("--hap-min-reads --hap-min-freq --hap-max-mismatches", is<&Args::haps>, "--haplotypes or --hap-window"),
+    needs("--haplotypes", filled<&Args::haplotypes>, "a BED file"),
+    range("--hap-window", 1, (long)kHapMaxLen).when_given(),
+    at_least("--hap-step", 1).when_given(),
+    at_least("--hap-min-reads", 1),
+    range("--hap-max-mismatches", 0, kLinkMaxMismatches),
+    range("--hap-min-freq", 0, 1).when_given(),
+    by_hand(one_m<2>),
+    needs("--read-pileup-end --read-pileup-max-mismatches", on<&Args::read_pileup>, "--read-pileup"),
+    range("--read-pileup-end", 0, (long)kReadPileupMaxEnd),
+    range("--read-pileup-max-mismatches", 0, kLinkMaxMismatches),
+    by_hand(one_m<3>),
+    needs("--distances", on<&Args::consensus>, "--consensus"),
+    needs("--clusters", on<&Args::distances>, "--distances"),
+    needs("--cluster-min-breadth", is<&Args::has_clusters>, "--clusters"),
+    at_least("--clusters", 0),
+    range("--cluster-min-breadth", 0, 1),
+    needs("--mst", on<&Args::distances>, "--distances"),
+    needs("--mst-min-breadth", on<&Args::mst>, "--mst"),
+    range("--mst-min-breadth", 0, 1),
+};
+
+void check_call_args(const Args& a) {
+    for (const Rule& r : kRules) {
+        if (r.by_hand) { r.by_hand(a); continue; }
+        if (r.ok) {   // (opt: one option or several, blank-separated, in the order they are checked)
+            for (const char *p = r.opt, *q; *p; p = *q ? q + 1 : q) {
+                q = strchr(p, ' ') ? strchr(p, ' ') : p + strlen(p);
+                const std::string opt(p, q);
+                if (a.given(opt.c_str()) && !r.ok(a)) die(TC, opt + " needs " + r.text);
+            }
+            continue;
+        }
+        if (r.if_given && !a.given(r.opt)) continue;
+        const Opt& o = *find_opt(r.opt);   // an integer or a real; a real out of range includes one that is no number
+        const long n = o.l ? a.*o.l : 0;
+        const double x = o.d ? a.*o.d : 0.0;
+        if (o.l ? n >= r.lo && (r.no_hi || n <= r.hi) : x >= (double)r.lo && (r.no_hi || x <= (double)r.hi)) continue;
+        char got[64];
+        snprintf(got, sizeof got, "%g", x);
+        die(TC, std::string(r.text ? r.text : r.opt) + " must be " +
+                    (r.no_hi ? "at least " + std::to_string(r.lo) : "between " + std::to_string(r.lo) + " and " + std::to_string(r.hi)) + r.after + ", got " +
+                    (o.l ? std::to_string(n) : std::string(got)));
     }
 }
 
@@ -695,7 +702,7 @@ CallConfig make_call_config(const Args& a) {
     CallConfig c;
     c.k = (int)a.kmer;
     c.min_qual = (int)a.min_base_qual;
-    if (a.has_primers) { c.primers = read_primers(T, a.primers); c.primer_mismatches = (int)a.primer_mismatches; }
+    if (a.has_primers()) { c.primers = read_primers(T, a.primers); c.primer_mismatches = (int)a.primer_mismatches; }
     if (!a.adapters.empty()) { c.adapters = expand_adapters(T, a); c.adapter_min_overlap = (uint32_t)a.adapter_min_overlap; c.adapter_error_rate = a.adapter_error_rate; }
     // inflate threads per file (pargz.hpp) for what is read ahead: -t over the files that will be open at once
     const size_t files = (a.reads.size() + a.first_pairs.size()) * (a.first_pairs.empty() ? 1 : 2);
@@ -713,50 +720,31 @@ CallConfig make_call_config(const Args& a) {
     d.min_depth = cp.min_depth; d.min_variant_depth = cp.min_variant_depth;
     bk_consensus_params_default(&c.consensus);
     c.consensus.min_depth = (uint64_t)a.consensus_min_depth; c.consensus.min_freq = a.consensus_min_freq;
-    if (a.has_regions) {   // (the chrom names meet the index's in call_samples, once its metadata is known)
-        try { c.bed = read_bed(a.regions); }
-        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the regions file"); }
-        c.regions_path = a.regions;
-    }
-    if (a.has_region_window) c.region_window = (uint64_t)a.region_window;
+    // (the chrom names of the three BED files meet the index's in call_samples, once its metadata is known)
+    auto bed_file = [&](bool given, const std::string& path, std::vector<BedLine> (*read)(const std::string&), const char* what, std::vector<BedLine>& lines, std::string& kept) {
+        if (!given) return;
+        try { lines = read(path); }
+        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the " + what + " file"); }
+        kept = path;
+    };
+    bed_file(a.has_regions(), a.regions, read_bed, "regions", c.bed, c.regions_path);
+    if (a.has_region_window()) c.region_window = (uint64_t)a.region_window;
     c.region_min_depth = (uint64_t)a.region_min_depth;
-    c.copybacks = a.copybacks;
-    c.copyback.max_mismatches = (uint32_t)a.copyback_max_mismatches; c.copyback.min_reads = (uint64_t)a.copyback_min_reads;
-    c.copyback.min_dist = (uint32_t)a.copyback_min_dist;
-    c.chimeras = a.chimeras;
-    c.chimera.max_mismatches = (uint32_t)a.chimera_max_mismatches; c.chimera.min_reads = (uint64_t)a.chimera_min_reads;
-    c.breakends = a.breakends;
-    c.breakend.min_clip = (uint32_t)a.breakend_min_clip; c.breakend.max_mismatches = (uint32_t)a.breakend_max_mismatches;
-    c.breakend.min_reads = (uint64_t)a.breakend_min_reads;
-    c.duplications = a.duplications;
-    c.duplication.min_len = (uint32_t)a.duplication_min_len; c.duplication.max_mismatches = (uint32_t)a.duplication_max_mismatches;
-    c.duplication.min_reads = (uint64_t)a.duplication_min_reads;
-    c.junctions = a.junctions;
-    c.junction.min_len = (uint32_t)a.junction_min_len; c.junction.max_mismatches = (uint32_t)a.junction_max_mismatches;
-    c.junction.min_reads = (uint64_t)a.junction_min_reads;
+    // a report's switch and its params, in the order of the fields of its params struct
+    c.copybacks = a.copybacks; c.copyback = {(uint32_t)a.copyback_max_mismatches, (uint64_t)a.copyback_min_reads, (uint32_t)a.copyback_min_dist};
+    c.chimeras = a.chimeras; c.chimera = {(uint32_t)a.chimera_max_mismatches, (uint64_t)a.chimera_min_reads};
+    c.breakends = a.breakends; c.breakend = {(uint32_t)a.breakend_min_clip, (uint32_t)a.breakend_max_mismatches, (uint64_t)a.breakend_min_reads};
+    c.duplications = a.duplications; c.duplication = {(uint32_t)a.duplication_min_len, (uint32_t)a.duplication_max_mismatches, (uint64_t)a.duplication_min_reads};
+    c.junctions = a.junctions; c.junction = {(uint32_t)a.junction_min_len, (uint32_t)a.junction_max_mismatches, (uint64_t)a.junction_min_reads};
     c.indels = a.indels;
-    c.indel.max_len = (uint32_t)a.indel_max_len; c.indel.max_mismatches = (uint32_t)a.indel_max_mismatches;
-    c.indel.min_reads = (uint64_t)a.indel_min_reads;
-    c.indel.min_af_ppm = (uint32_t)llround((a.has_indel_min_af ? a.indel_min_af : a.min_af) * 1e6);
-    c.linkage = a.linkage;
-    c.link.max_mismatches = (uint32_t)a.link_max_mismatches; c.link.max_dist = (uint32_t)a.link_max_dist; c.link.min_reads = (uint64_t)a.link_min_reads;
-    if (a.has_codons) {   // (like the regions file: the chrom names meet the index's in call_samples)
-        try { c.codon_bed = read_codon_bed(a.codons); }
-        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the codons file"); }
-        c.codons_path = a.codons;
-    }
-    c.codon.max_mismatches = (uint32_t)a.codon_max_mismatches; c.codon.min_reads = (uint64_t)a.codon_min_reads;
-    c.codon.min_freq = a.has_codon_min_freq ? a.codon_min_freq : a.min_af;
-    if (a.has_haplotypes) {   // (likewise)
-        try { c.hap_bed = read_hap_bed(a.haplotypes); }
-        catch (const std::exception& e) { die(T, std::string(e.what()) + " | Unable to read the haplotypes file"); }
-        c.haps_path = a.haplotypes;
-    }
-    if (a.has_hap_window) { c.hap_window = (uint64_t)a.hap_window; c.hap_step = (uint64_t)(a.has_hap_step ? a.hap_step : a.hap_window); }
-    c.hap.max_mismatches = (uint32_t)a.hap_max_mismatches; c.hap.min_reads = (uint64_t)a.hap_min_reads;
-    c.hap.min_freq = a.has_hap_min_freq ? a.hap_min_freq : a.min_af;
-    c.read_pileup = a.read_pileup;
-    c.read_pile.max_mismatches = (uint32_t)a.read_pileup_max_mismatches; c.read_pile.end_dist = (uint32_t)a.read_pileup_end;
+    c.indel = {(uint32_t)a.indel_max_len, (uint32_t)a.indel_max_mismatches, (uint64_t)a.indel_min_reads, (uint32_t)llround((a.given("--indel-min-af") ? a.indel_min_af : a.min_af) * 1e6)};
+    c.linkage = a.linkage; c.link = {(uint32_t)a.link_max_mismatches, (uint32_t)a.link_max_dist, (uint64_t)a.link_min_reads};
+    bed_file(a.has_codons(), a.codons, read_codon_bed, "codons", c.codon_bed, c.codons_path);
+    c.codon = {(uint32_t)a.codon_max_mismatches, (uint64_t)a.codon_min_reads, a.given("--codon-min-freq") ? a.codon_min_freq : a.min_af};
+    bed_file(a.has_haplotypes(), a.haplotypes, read_hap_bed, "haplotypes", c.hap_bed, c.haps_path);
+    if (a.has_hap_window()) { c.hap_window = (uint64_t)a.hap_window; c.hap_step = (uint64_t)(a.given("--hap-step") ? a.hap_step : a.hap_window); }
+    c.hap = {(uint32_t)a.hap_max_mismatches, (uint64_t)a.hap_min_reads, a.given("--hap-min-freq") ? a.hap_min_freq : a.min_af};
+    c.read_pileup = a.read_pileup; c.read_pile = {(uint32_t)a.read_pileup_max_mismatches, (uint32_t)a.read_pileup_end};
     return c;
 }
 

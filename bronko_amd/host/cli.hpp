@@ -1,8 +1,9 @@
-// cli.hpp -- what the three units of the `bronko` binary share: the logger, die, hip_check, the parsed arguments and the
-// settings of one `bronko call` (cli.cpp: arguments, checks, build, main; reads.cpp: FASTQ files -> engine; call_run.cpp: engines,
-// lanes and the per-sample code).
+// cli.hpp -- what the three units of the `bronko` binary share: the logger, die, hip_check, the parsed arguments (a field per
+// option, one record of the options given) and the settings of one `bronko call` (cli.cpp: the option table, the rules, build, main;
+// reads.cpp: FASTQ files -> engine; call_run.cpp: engines, lanes and the per-sample report units).
 #pragma once
 #include <algorithm>
+#include <bitset>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -37,12 +38,23 @@ void logf(int lvl, const char* tag, const char* target, const std::string& msg);
 void hip_check(int rc, const char* what);                            // a bk_* status: dies with bk_last_error()
 
 // ---- argument parsing (clap derive surface of cli.rs) -------------------------------------------------------
+// One field per option that takes a value or is a switch; which options were given at all is one record, a bit per row of the option
+// table (cli.cpp), read by the option's long name.
 struct Args {
     std::string mode;
+    std::bitset<128> given_rows;
+    bool given(const char* name) const;   // cli.cpp; name: the option's long name, as the table has it
+    bool has_genomes() const { return given("--genomes"); }
+    bool has_db() const { return given("--db"); }
+    bool has_primers() const { return given("--primers"); }
+    bool has_regions() const { return given("--regions"); }
+    bool has_region_window() const { return given("--region-window"); }
+    bool has_codons() const { return given("--codons"); }
+    bool has_haplotypes() const { return given("--haplotypes"); }
+    bool has_hap_window() const { return given("--hap-window"); }
+    bool has_clusters() const { return given("--clusters"); }
     std::vector<std::string> genomes, reads, first_pairs, second_pairs;
-    bool has_genomes = false;
     std::string db;
-    bool has_db = false;
     long kmer = 21;                 // consts.rs:3
     long min_kmers = 3;             // consts.rs:5
     bool use_full_kmer = false;
@@ -57,79 +69,63 @@ struct Args {
     double noise_multiplier = 1.5;
     long min_base_qual = 0;         // --min-base-qual: bases below this Phred+33 quality are N before k-mer counting (0: off)
     std::string primers;            // --primers: FASTA of amplicon primers trimmed from the read ends (empty: none)
-    bool has_primers = false, has_primer_mismatches = false;
     long primer_mismatches = 1;     // --primer-mismatches: Hamming distance a primer match may have (0..3)
     std::vector<std::string> adapters;   // --adapter: 3' adapters cut off the reads, preset names or sequences (empty: none)
-    bool has_adapter_min_overlap = false, has_adapter_error_rate = false;
     long adapter_min_overlap = 5;   // --adapter-min-overlap: bases of an adapter's start that count as a match at the read's end
     double adapter_error_rate = 0.1;   // --adapter-error-rate: mismatches allowed per compared base (0..0.3)
     bool consensus = false;         // --consensus: <DIR>/<stem>.consensus.fa, one IUPAC letter per position of the selected genome
-    bool has_consensus_min_depth = false, has_consensus_min_freq = false;
     long consensus_min_depth = 10;  // --consensus-min-depth: positions with less depth are N
     double consensus_min_freq = 0.5;   // --consensus-min-freq: share of the depth the letter's bases must reach together (0..1)
     std::string regions;            // --regions: BED file of the regions whose depths go to <DIR>/<stem>.regions.tsv (empty: none)
-    bool has_regions = false, has_region_window = false, has_region_min_depth = false;
     long region_window = 0;         // --region-window: tile every sequence with windows of this many positions instead
     long region_min_depth = 10;     // --region-min-depth: a position with at least this depth counts as covered
     bool indels = false;            // --indels: <DIR>/<stem>.indels.vcf, short insertions and deletions from the reads
-    bool has_indel_max_len = false, has_indel_max_mismatches = false, has_indel_min_reads = false, has_indel_min_af = false;
     long indel_max_len = 32;        // --indel-max-len: longest insertion or deletion looked for (1..32)
     long indel_max_mismatches = 2;  // --indel-max-mismatches: substitutions a record may have beside its indel (0..8)
     long indel_min_reads = 5;       // --indel-min-reads: supporting records an event needs
     double indel_min_af = 0.03;     // --indel-min-af: support / (support + reference-spanning records) an event needs (default: --min-af)
     bool consensus_indels = false;  // --consensus-indels: the sample's indels in <DIR>/<stem>.consensus.fa, <DIR>/<stem>.consensus_indels.tsv (needs --consensus and --indels)
     bool junctions = false;         // --junctions: <DIR>/<stem>.junctions.tsv, long deletions and subgenomic-RNA junctions from the reads
-    bool has_junction_min_len = false, has_junction_max_mismatches = false, has_junction_min_reads = false;
     long junction_min_len = 33;     // --junction-min-len: shortest jump counted as a junction (with 33 it begins where --indels ends)
     long junction_max_mismatches = 2;   // --junction-max-mismatches: substitutions a record may have beside its junction (0..8)
     long junction_min_reads = 5;    // --junction-min-reads: supporting records a junction needs
     bool copybacks = false;         // --copybacks: <DIR>/<stem>.copybacks.tsv, strand-switch (copy-back, snap-back) junctions from the reads
-    bool has_copyback_max_mismatches = false, has_copyback_min_reads = false, has_copyback_min_dist = false;
     long copyback_max_mismatches = 2;   // --copyback-max-mismatches: substitutions a record may have beside its turn (0..8)
     long copyback_min_reads = 5;    // --copyback-min-reads: supporting records an event needs
     long copyback_min_dist = 0;     // --copyback-min-dist: cells an event's two breakpoints must lie apart
     bool chimeras = false;          // --chimeras: <DIR>/<stem>.chimeras.tsv, junctions between two sequences of the genome file from the reads
-    bool has_chimera_max_mismatches = false, has_chimera_min_reads = false;
     long chimera_max_mismatches = 2;    // --chimera-max-mismatches: substitutions a record may have beside its junction (0..8)
     long chimera_min_reads = 5;     // --chimera-min-reads: supporting records an event needs
     bool breakends = false;         // --breakends: <DIR>/<stem>.breakends.tsv, reads that leave the reference (an anchor at one end only)
-    bool has_breakend_min_clip = false, has_breakend_max_mismatches = false, has_breakend_min_reads = false;
     long breakend_min_clip = 20;    // --breakend-min-clip: clipped bases a record needs to support an event (16..65519)
     long breakend_max_mismatches = 2;   // --breakend-max-mismatches: substitutions the held part of a record may have (0..8)
     long breakend_min_reads = 5;    // --breakend-min-reads: supporting records an event needs
     bool duplications = false;      // --duplications: <DIR>/<stem>.duplications.tsv, tandem duplications and circular-origin reads
-    bool has_duplication_min_len = false, has_duplication_max_mismatches = false, has_duplication_min_reads = false;
     long duplication_min_len = 33;  // --duplication-min-len: shortest backward jump counted (with 33 it begins where --indels ends)
     long duplication_max_mismatches = 2;   // --duplication-max-mismatches: substitutions a record may have beside its junction (0..8)
     long duplication_min_reads = 5; // --duplication-min-reads: supporting records an event needs
     bool linkage = false;           // --linkage: <DIR>/<stem>.linkage.tsv, which of the sample's substitutions the same reads carry
-    bool has_link_max_mismatches = false, has_link_max_dist = false, has_link_min_reads = false;
     long link_max_mismatches = 8;   // --link-max-mismatches: substitutions a placed record may have (0..8)
     long link_max_dist = 1000;      // --link-max-dist: pairs of substitutions at most this far apart are counted (1..65519)
     long link_min_reads = 1;        // --link-min-reads: records that cover both positions a pair needs to be written
     std::string codons;             // --codons: BED file of the coding regions whose codons go to <DIR>/<stem>.codons.tsv (empty: none)
-    bool has_codons = false, has_codon_min_reads = false, has_codon_min_freq = false, has_codon_max_mismatches = false;
     long codon_min_reads = 5;       // --codon-min-reads: records that carry a triplet for it to be written
     double codon_min_freq = 0.03;   // --codon-min-freq: count / cover a triplet needs to be written (default: --min-af)
     long codon_max_mismatches = 8;  // --codon-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with --linkage)
     std::string haplotypes;         // --haplotypes: BED file of the regions whose read haplotypes go to <DIR>/<stem>.haplotypes.tsv (empty: none)
-    bool has_haplotypes = false, has_hap_window = false, has_hap_step = false, has_hap_min_reads = false, has_hap_min_freq = false, has_hap_max_mismatches = false;
     long hap_window = 0;            // --hap-window: tile every sequence with windows of this many positions instead (1..65520)
     long hap_step = 0;              // --hap-step: positions from one window's start to the next (default: the window)
     long hap_min_reads = 5;         // --hap-min-reads: records that carry a haplotype for it to be written
     double hap_min_freq = 0.03;     // --hap-min-freq: count / cover a haplotype needs to be written (default: --min-af)
     long hap_max_mismatches = 8;    // --hap-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with --linkage and --codons)
-    bool haps() const { return has_haplotypes || has_hap_window; }
+    bool haps() const { return has_haplotypes() || has_hap_window(); }
     bool read_pileup = false;       // --read-pileup: <DIR>/<stem>.read_pileup.tsv, per position the bases the placed reads carry, by strand and near their ends
-    bool has_read_pileup_end = false, has_read_pileup_max_mismatches = false;
     long read_pileup_end = 10;      // --read-pileup-end: a base within this many positions of a read's end counts as near it (0..255)
     long read_pileup_max_mismatches = 8;   // --read-pileup-max-mismatches: substitutions a placed record may have (0..8; the row store's, shared with the other three)
     bool distances = false;         // --distances: <DIR>/<genome>.distances.tsv and .compared.tsv, the samples' pairwise consensus distances (needs --consensus)
-    bool has_clusters = false, has_cluster_min_breadth = false;
     long clusters = 0;              // --clusters T: <DIR>/<genome>.clusters.tsv, single-linkage clusters of the samples at most T apart (needs --distances)
     double cluster_min_breadth = 0.9;   // --cluster-min-breadth B: share of the genome's positions a pair must have compared to be linked (0..1)
     bool mst = false;               // --mst: <DIR>/<genome>.mst.tsv, the minimum spanning forest of the samples' distances (needs --distances)
-    bool has_mst_min_breadth = false;
     double mst_min_breadth = 0.9;   // --mst-min-breadth B: share of the genome's positions a pair must have compared to be an edge (0..1)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
