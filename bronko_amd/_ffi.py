@@ -54,6 +54,14 @@ class ConsensusSummary(C.Structure):  # bk_consensus_summary
                 ("masked", C.c_uint64), ("substitutions", C.c_uint64)]
 
 
+class MinorParams(C.Structure):  # bk_minor_params
+    _fields_ = [("min_reads", C.c_uint64), ("min_freq", C.c_double)]
+
+
+class MinorSummary(C.Structure):  # bk_minor_summary
+    _fields_ = [("file_id", C.c_int32), ("pad", C.c_uint32), ("positions", C.c_uint64), ("mixed", C.c_uint64), ("present", C.c_uint64)]
+
+
 class Region(C.Structure):  # bk_region
     _fields_ = [("file_id", C.c_int32), ("seq", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32)]
 
@@ -200,6 +208,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_pileup_device_ptr", "bk_sample_download", "bk_sample_finish", "bk_pack_reads", "bk_pack_reads_flat",
            "bk_timing_enable", "bk_timing_read", "bk_call_params_default", "bk_sample_call", "bk_sample_download_calls", "bk_sample_download_noise",
            "bk_consensus_params_default", "bk_sample_consensus", "bk_sample_download_consensus",
+           "bk_minor_params_default", "bk_sample_minor_alleles", "bk_sample_download_minor_alleles",
            "bk_regions_set", "bk_sample_region_depths", "bk_sample_download_region_depths",
            "bk_indels_enable", "bk_sample_indels", "bk_sample_download_indels", "bk_sample_download_indel_span",
            "bk_sample_consensus_indels", "bk_sample_download_consensus_indels",
@@ -211,7 +220,7 @@ SYMBOLS = ["bk_abi_version", "bk_device_count", "bk_device_memory", "bk_last_err
            "bk_link_enable", "bk_sample_linkage", "bk_sample_download_linkage", "bk_sample_download_link_rows",
            "bk_sample_codons", "bk_sample_download_codons", "bk_sample_haplotypes", "bk_sample_download_haplotypes",
            "bk_sample_read_pileup", "bk_sample_download_read_pileup",
-           "bk_cohort_set", "bk_cohort_distances", "bk_cohort_clear", "bk_cohort_mst",
+           "bk_cohort_set", "bk_cohort_distances", "bk_cohort_clear", "bk_cohort_mst", "bk_cohort_set_minor", "bk_cohort_explained",
            "bk_build_index", "bk_built_index_free", "bk_build_last_error"]
 
 _libs = {}
@@ -347,6 +356,11 @@ def load(testing=None):
     L.bk_sample_download_indels.argtypes = [vp, C.POINTER(IndelSummary), vp, u64]
     L.bk_sample_download_indel_span.restype = C.c_int
     L.bk_sample_download_indel_span.argtypes = [vp, vp, u64]
+    L.bk_minor_params_default.argtypes = [C.POINTER(MinorParams)]
+    L.bk_sample_minor_alleles.restype = C.c_int
+    L.bk_sample_minor_alleles.argtypes = [vp, C.POINTER(MinorParams)]
+    L.bk_sample_download_minor_alleles.restype = C.c_int
+    L.bk_sample_download_minor_alleles.argtypes = [vp, C.POINTER(MinorSummary), vp, u64]
     L.bk_sample_consensus_indels.restype = C.c_int
     L.bk_sample_consensus_indels.argtypes = [vp]
     L.bk_sample_download_consensus_indels.restype = C.c_int
@@ -417,6 +431,10 @@ def load(testing=None):
     L.bk_cohort_distances.argtypes = [vp, u64, u64, vp, vp]
     L.bk_cohort_clear.restype = C.c_int
     L.bk_cohort_clear.argtypes = [vp]
+    L.bk_cohort_set_minor.restype = C.c_int
+    L.bk_cohort_set_minor.argtypes = [vp, vp, u64, u64]
+    L.bk_cohort_explained.restype = C.c_int
+    L.bk_cohort_explained.argtypes = [vp, u64, u64, vp, vp]
     L.bk_cohort_mst.restype = C.c_int
     L.bk_cohort_mst.argtypes = [vp, C.c_uint32, C.POINTER(MstEdge), u64, C.POINTER(u64), C.POINTER(MstNearest), C.POINTER(C.c_uint32)]
     L.bk_build_index.restype = C.c_int

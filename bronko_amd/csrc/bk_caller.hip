@@ -3,6 +3,7 @@
 //   noise           get_baseline_noise               call.rs:799-967
 //   call            call_variants                    call.rs:969-1150
 //   consensus       (bk_sample_consensus: not in the reference) one IUPAC letter per position of the selected genome
+//   minor alleles   (bk_sample_minor_alleles: not in the reference) which bases are present at every position of it
 // so that a host with many samples in flight never waits between a sample's reads and its variant records.
 //
 // Exactness.  Everything up to the decisions is IEEE double arithmetic in the reference's order: +, -, *, / and sqrt are
@@ -612,6 +613,52 @@ __global__ __launch_bounds__(256) void consensus_kernel(ConsensusArgs a) {
 void launch_consensus(const ConsensusArgs& a, uint64_t max_file_cells, hipStream_t stream) {
     const unsigned blocks = (unsigned)((max_file_cells + 255) / 256);   // call_kernel's grid
     hipLaunchKernelGGL(consensus_kernel, dim3(blocks ? (blocks > 4096u ? 4096u : blocks) : 1u), dim3(256), 0, stream, a);
+}
+
+// The present mask of every position of the selected genome (bk_sample_minor_alleles), one thread per position: consensus_kernel's
+// grid, walk over the cells and tally reduction.  The rule (include/bronko_hip.h): bit b iff tot[b] >= min_reads and
+// (double)tot[b] >= min_freq * (double)depth -- one double multiplication per position, four compares with it.
+__global__ __launch_bounds__(256) void minor_alleles_kernel(MinorArgs a) {
+    __shared__ unsigned int red[3];
+    if (threadIdx.x < 3) red[threadIdx.x] = 0;
+    __syncthreads();
+    const int file = a.out->file_id;
+    unsigned int tally[3] = {0, 0, 0};   // positions, mixed, present (constant indices only)
+    if (file >= 0) {
+        const uint64_t cell_lo = a.seq_cell[a.seq_first[file]];
+        const int sq_hi = a.seq_first[file] + a.n_seqs[file];
+        const uint64_t cell_hi = a.n_seqs[file] ? a.seq_cell[sq_hi - 1] + a.seq_len[sq_hi - 1] : cell_lo;
+        for (uint64_t cell = cell_lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; cell < cell_hi; cell += (uint64_t)gridDim.x * blockDim.x) {
+            const unsigned long long* fr = a.pileup + 0 * a.plane + cell * 4;
+            const unsigned long long* rr = a.pileup + 1 * a.plane + cell * 4;
+            const unsigned long long t0 = fr[0] + rr[0], t1 = fr[1] + rr[1], t2 = fr[2] + rr[2], t3 = fr[3] + rr[3];
+            const double need = a.prm.min_freq * (double)(t0 + t1 + t2 + t3);
+            const unsigned mask = (t0 >= a.prm.min_reads && (double)t0 >= need ? 1u : 0u) | (t1 >= a.prm.min_reads && (double)t1 >= need ? 2u : 0u) |
+                                  (t2 >= a.prm.min_reads && (double)t2 >= need ? 4u : 0u) | (t3 >= a.prm.min_reads && (double)t3 >= need ? 8u : 0u);
+            tally[0] += 1;
+            tally[1] += (mask & (mask - 1u)) != 0u ? 1u : 0u;
+            tally[2] += (unsigned int)__popc(mask);
+            a.masks[cell - cell_lo] = (uint8_t)mask;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        unsigned int v = tally[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&red[q], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && red[threadIdx.x]) {
+        static_assert(offsetof(MinorSummaryDev, present) == offsetof(MinorSummaryDev, positions) + 2 * sizeof(uint64_t), "three consecutive tallies");
+        atomicAdd(reinterpret_cast<unsigned long long*>(&a.summary->positions) + threadIdx.x, (unsigned long long)red[threadIdx.x]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.summary->file_id = file;
+}
+
+void launch_minor_alleles(const MinorArgs& a, uint64_t max_file_cells, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((max_file_cells + 255) / 256);   // consensus_kernel's grid
+    hipLaunchKernelGGL(minor_alleles_kernel, dim3(blocks ? (blocks > 4096u ? 4096u : blocks) : 1u), dim3(256), 0, stream, a);
 }
 
 void launch_select_genome(const CallArgs& a, hipStream_t stream) {

@@ -29,6 +29,23 @@
 //                            meet in LDS, lane 0 stores.  The loop's bound is n.
 //   cohort_comp_diff_kernel, cohort_comp_pair_kernel   a lane per row: atomicMin of the row's diff at its label, then, among the rows
 //                            that have that diff, atomicMin of lo << 32 | hi: the component's least edge under (diff, lo, hi).
+// bk_cohort_set_minor and bk_cohort_explained (`--contamination`) count, per ordered pair, the positions at which the column's consensus
+// base is a minor allele of the row (rule: bronko_hip.h; bronko_amd/host/cohort.cpp and tests/contamination_ref.py
+// restate it):
+//   cohort_minor_pack_kernel   present masks -> four minor planes per sample, M_X = "X is present, the consensus is a base and not X",
+//                              laid out like the letters' planes, [4][W][n_stride].  The wave and lane of cohort_pack_kernel; a lane
+//                              takes its bit of the sample's valid, b0 and b1 words, which are there, clears its consensus base from the
+//                              mask's low four bits, four ballots, lane 0 stores the four words and adds the popcount of their OR to
+//                              the sample's minor_sites (one atomicAdd per word and sample that has any).
+//   cohort_explained_kernel    the tile and slice geometry of cohort_pairs_kernel: 64 rows x 64 columns over a slice of words, a lane
+//                              holds 4 x 4 pairs interleaved by 16 (16 counters).  The row side stages M_A..M_T as they lie; the column
+//                              side stages the one-hot planes C_X = "the consensus is X", made of valid, b0 and b1 while staging:
+//                              32 KB of LDS per chunk of 8 words, word-major and read exactly as the pairs kernel reads its image (no
+//                              bank conflict).  Per pair and word explained += popcount((M_A & C_A) | (M_C & C_C) | (M_G & C_G) |
+//                              (M_T & C_T)): the four terms are disjoint (C is one-hot), M_X & C_X says "the column's base X is present
+//                              in the row and the row's consensus is another base" -- both are bases and differ.  Not symmetric, so
+//                              the two sides hold different planes; partial sums go to the zeroed block with one atomicAdd per
+//                              non-zero pair.
 // Vector stores and atomics only.
 #include <hip/hip_runtime.h>
 
@@ -59,6 +76,33 @@ __global__ __launch_bounds__(kCohortBlock) void cohort_pack_kernel(const uint8_t
         if (lane == 0 && w < W) {
             const size_t at = (size_t)w * n_stride + (size_t)(s0 + s), plane = (size_t)W * n_stride;
             planes[at] = v; planes[plane + at] = b0; planes[2 * plane + at] = b1;
+        }
+    }
+}
+
+// masks -> the minor planes, and minor_sites (zeroed by the caller)
+__global__ __launch_bounds__(kCohortBlock) void cohort_minor_pack_kernel(const uint8_t* __restrict__ masks, uint64_t s0, uint64_t ns, uint64_t positions, uint64_t W,
+                                                                         uint64_t n_stride, const unsigned long long* __restrict__ planes,
+                                                                         unsigned long long* __restrict__ minor, unsigned int* __restrict__ minor_sites) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t w = (uint64_t)blockIdx.x * (kCohortBlock / 64) + (threadIdx.x >> 6);   // (wave-uniform)
+    const uint64_t pos = w * 64 + lane;
+    const bool in = w < W && pos < positions;
+    const size_t plane = (size_t)W * n_stride;
+    for (uint64_t s = blockIdx.y; s < ns; s += gridDim.y) {
+        unsigned m = 0;
+        if (in) {
+            const size_t at = (size_t)w * n_stride + (size_t)(s0 + s);
+            const unsigned long long v = planes[at], b0 = planes[plane + at], b1 = planes[2 * plane + at];   // (one address a wave: a broadcast)
+            const unsigned code = (unsigned)((b0 >> lane) & 1ull) | (unsigned)((b1 >> lane) & 1ull) << 1;
+            if ((v >> lane) & 1ull) m = (unsigned)masks[s * positions + pos] & 15u & ~(1u << code);
+        }
+        const unsigned long long ma = __ballot(m & 1u), mc = __ballot(m & 2u), mg = __ballot(m & 4u), mt = __ballot(m & 8u);
+        if (lane == 0 && w < W) {
+            const size_t at = (size_t)w * n_stride + (size_t)(s0 + s);
+            minor[at] = ma; minor[plane + at] = mc; minor[2 * plane + at] = mg; minor[3 * plane + at] = mt;
+            const unsigned int sites = (unsigned int)__popcll(ma | mc | mg | mt);
+            if (sites) atomicAdd(minor_sites + (s0 + s), sites);
         }
     }
 }
@@ -130,6 +174,80 @@ __global__ __launch_bounds__(kCohortBlock) void cohort_pairs_kernel(PairsArgs a)
             const size_t at = (size_t)(row - a.row0) * a.n + col;
             if (cmp[i][j]) atomicAdd(a.compared + at, cmp[i][j]);
             if (dif[i][j]) atomicAdd(a.diff + at, dif[i][j]);
+        }
+    }
+}
+
+struct ExplainedArgs {
+    const unsigned long long* planes;       // [3][W][n_stride] the columns' letters
+    const unsigned long long* minor;        // [4][W][n_stride] the rows' minor planes
+    uint64_t n, n_stride, W;
+    uint64_t row0, n_rows;
+    uint32_t n_col_tiles;
+    uint32_t slice_words, chunk;            // as PairsArgs
+    unsigned int* explained;                // [n_rows][n]
+};
+
+__global__ __launch_bounds__(kCohortBlock) void cohort_explained_kernel(ExplainedArgs a) {
+    __shared__ unsigned long long lds[4 * kChunk * 2 * kTile];   // [A C G T][word of the chunk][rows 0..63: M_X | columns 0..63: C_X]
+    const uint32_t t = threadIdx.x, tx = t & 15u, ty = t >> 4;
+    const uint32_t ct = blockIdx.x % a.n_col_tiles, rt = blockIdx.x / a.n_col_tiles;
+    const uint64_t row_base = a.row0 + (uint64_t)rt * kTile, col_base = (uint64_t)ct * kTile;   // (both + 63 < n_stride)
+    const uint64_t w_lo = (uint64_t)blockIdx.y * a.slice_words, w_hi = std::min<uint64_t>(a.W, w_lo + a.slice_words);
+    const size_t plane = (size_t)a.W * a.n_stride;
+
+    unsigned int ex[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) ex[i][j] = 0;
+
+    for (uint64_t w0 = w_lo; w0 < w_hi; w0 += a.chunk) {
+        const uint32_t L = (uint32_t)std::min<uint64_t>(a.chunk, w_hi - w0);
+        __syncthreads();   // (the previous step's reads are done)
+        for (uint32_t idx = t; idx < L * 2 * kTile; idx += kCohortBlock) {   // (side is wave-uniform: 64 consecutive idx share it)
+            const uint32_t s = idx & 63u, side = (idx >> 6) & 1u, w = idx >> 7;
+            unsigned long long x[4];
+            if (side) {
+                const size_t at = (size_t)(w0 + w) * a.n_stride + col_base + s;
+                const unsigned long long v = a.planes[at], b0 = a.planes[plane + at], b1 = a.planes[2 * plane + at];
+                x[0] = v & ~b0 & ~b1; x[1] = v & b0 & ~b1; x[2] = v & ~b0 & b1; x[3] = v & b0 & b1;
+            } else {
+                const size_t at = (size_t)(w0 + w) * a.n_stride + row_base + s;
+#pragma unroll
+                for (int p = 0; p < 4; p++) x[p] = a.minor[p * plane + at];
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) lds[p * kChunk * 2 * kTile + idx] = x[p];
+        }
+        __syncthreads();
+        for (uint32_t w = 0; w < L; w++) {
+            const unsigned long long* q = lds + w * 2 * kTile;
+            unsigned long long r[4][4], c[4][4];   // [A C G T][i or j]
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    r[p][i] = q[p * kChunk * 2 * kTile + ty + 16 * i];
+                    c[p][i] = q[p * kChunk * 2 * kTile + kTile + tx + 16 * i];
+                }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    ex[i][j] += (unsigned int)__popcll((r[0][i] & c[0][j]) | (r[1][i] & c[1][j]) | (r[2][i] & c[2][j]) | (r[3][i] & c[3][j]));
+        }
+    }
+
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint64_t row = row_base + ty + 16 * i;
+        if (row >= a.row0 + a.n_rows) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint64_t col = col_base + tx + 16 * j;
+            if (col >= a.n) continue;
+            if (ex[i][j]) atomicAdd(a.explained + (size_t)(row - a.row0) * a.n + col, ex[i][j]);
         }
     }
 }
@@ -271,17 +389,10 @@ int bk_cohort_distances(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* 
     return BK_OK;
 }
 
-// diff and compared of the rows [row0, row0 + n_rows) against all columns into c.out, [2][n_rows][n], on the engine's stream: the
-// zeroing and cohort_pairs_kernel.  The rows lie inside the cohort (the callers' check).
-static int launch_pairs(bk_engine* e, Cohort& c, const char* who, uint64_t row0, uint64_t n_rows) {
-    const size_t block = (size_t)n_rows * c.n;
-    BK_HIP(grow(c.out, 2 * block, 0, e->stream));
-    bk::PairsArgs a{};
-    a.planes = c.planes.p; a.n = c.n; a.n_stride = c.n_stride; a.W = c.W; a.row0 = row0; a.n_rows = n_rows;
-    a.n_col_tiles = (uint32_t)((c.n + bk::kTile - 1) / bk::kTile);
-    const uint64_t n_row_tiles = (n_rows + bk::kTile - 1) / bk::kTile, tiles = n_row_tiles * a.n_col_tiles;
-    if (tiles > 0x7fffffffull) return fail(BK_ERR_INVALID, "%s: n_rows = %llu is too many rows for one block of %llu columns", who, (unsigned long long)n_rows, (unsigned long long)c.n);
-    uint64_t slice_words, chunk = bk::kChunk;
+// The words of a slice and the words staged per step for a launch of `tiles` tiles (the pairs kernel's and the explained kernel's):
+// slices are cut until tiles x slices reaches kTargetGroups
+static void cut_slices(const Cohort& c, uint64_t tiles, uint64_t& slice_words, uint64_t& chunk) {
+    chunk = bk::kChunk;
     const char* forced = test_env("BK_COHORT_SLICE_WORDS");   // (testing build: small inputs cross slice and chunk borders)
     if (forced && atoi(forced) >= 1) {
         slice_words = (uint64_t)atoi(forced);
@@ -292,6 +403,20 @@ static int launch_pairs(bk_engine* e, Cohort& c, const char* who, uint64_t row0,
         slice_words = (chunks + want - 1) / want * bk::kChunk;
     }
     slice_words = std::max<uint64_t>(slice_words, (c.W + 65534) / 65535);   // (the grid's y)
+}
+
+// diff and compared of the rows [row0, row0 + n_rows) against all columns into c.out, [2][n_rows][n], on the engine's stream: the
+// zeroing and cohort_pairs_kernel.  The rows lie inside the cohort (the callers' check).
+static int launch_pairs(bk_engine* e, Cohort& c, const char* who, uint64_t row0, uint64_t n_rows) {
+    const size_t block = (size_t)n_rows * c.n;
+    BK_HIP(grow(c.out, 2 * block, 0, e->stream));
+    bk::PairsArgs a{};
+    a.planes = c.planes.p; a.n = c.n; a.n_stride = c.n_stride; a.W = c.W; a.row0 = row0; a.n_rows = n_rows;
+    a.n_col_tiles = (uint32_t)((c.n + bk::kTile - 1) / bk::kTile);
+    const uint64_t n_row_tiles = (n_rows + bk::kTile - 1) / bk::kTile, tiles = n_row_tiles * a.n_col_tiles;
+    if (tiles > 0x7fffffffull) return fail(BK_ERR_INVALID, "%s: n_rows = %llu is too many rows for one block of %llu columns", who, (unsigned long long)n_rows, (unsigned long long)c.n);
+    uint64_t slice_words, chunk;
+    cut_slices(c, tiles, slice_words, chunk);
     a.slice_words = (uint32_t)slice_words; a.chunk = (uint32_t)chunk;
     a.diff = c.out.p; a.compared = c.out.p + block;
     BK_HIP(hipMemsetAsync(c.out.p, 0, 2 * block * sizeof(unsigned int), e->stream));
@@ -394,5 +519,72 @@ int bk_cohort_mst(bk_engine* e, uint32_t min_compared, bk_mst_edge* edges, uint6
     });
     *n_edges = n_found;
     if (rounds) *rounds = n_rounds;
+    return BK_OK;
+}
+
+// ---- bk_cohort_set_minor, bk_cohort_explained -------------------------------------------------------------------------------------
+int bk_cohort_set_minor(bk_engine* e, const uint8_t* masks, uint64_t n_samples, uint64_t positions) {
+    if (!e) return fail(BK_ERR_INVALID, "bk_cohort_set_minor: e is null");
+    if (!masks) return fail(BK_ERR_INVALID, "bk_cohort_set_minor: masks is null");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_cohort_set_minor inside a sample: it comes before bk_sample_begin or after the sample's downloads");
+    if (!e->cohort) return fail(BK_ERR_STATE, "bk_cohort_set_minor comes after bk_cohort_set");
+    Cohort& c = *e->cohort;
+    if (n_samples != c.n) return fail(BK_ERR_INVALID, "bk_cohort_set_minor: n_samples = %llu, the cohort has %llu", (unsigned long long)n_samples, (unsigned long long)c.n);
+    if (positions != c.positions) return fail(BK_ERR_INVALID, "bk_cohort_set_minor: positions = %llu, the cohort has %llu", (unsigned long long)positions, (unsigned long long)c.positions);
+    BK_HIP(hipSetDevice(e->device));
+    const size_t words = (size_t)4 * c.W * c.n_stride;
+    DevBuf<unsigned long long> minor;       // (the cohort's own only once they are whole)
+    DevBuf<unsigned int> sites;
+    BK_HIP(minor.alloc(words));
+    BK_HIP(sites.alloc((size_t)c.n));
+    BK_HIP(hipMemsetAsync(minor.p, 0, words * sizeof(unsigned long long), e->stream));
+    BK_HIP(hipMemsetAsync(sites.p, 0, (size_t)c.n * sizeof(unsigned int), e->stream));
+    // the masks pass through a device buffer of at most 256 MB, a batch of whole samples at a time, as bk_cohort_set's letters do
+    const uint64_t batch = std::max<uint64_t>(1, std::min<uint64_t>(c.n, (256ull << 20) / positions));
+    DevBuf<uint8_t> d_masks;
+    BK_HIP(d_masks.alloc((size_t)(batch * positions)));
+    for (uint64_t s0 = 0; s0 < c.n; s0 += batch) {
+        const uint64_t ns = std::min<uint64_t>(batch, c.n - s0);
+        BK_HIP(hipMemcpyAsync(d_masks.p, masks + s0 * positions, (size_t)(ns * positions), hipMemcpyHostToDevice, e->stream));
+        const dim3 grid((unsigned)((c.W + 3) / 4), (unsigned)std::min<uint64_t>(ns, 65535));
+        hipLaunchKernelGGL(bk::cohort_minor_pack_kernel, grid, dim3(bk::kCohortBlock), 0, e->stream, d_masks.p, s0, ns, positions, c.W, c.n_stride, c.planes.p, minor.p, sites.p);
+        BK_HIP(hipGetLastError());
+    }
+    BK_HIP(hipStreamSynchronize(e->stream));   // (the caller's masks and d_masks are free again)
+    std::swap(c.minor.p, minor.p); std::swap(c.minor.n, minor.n);   // (planes of an earlier call go with the locals)
+    std::swap(c.minor_sites.p, sites.p); std::swap(c.minor_sites.n, sites.n);
+    return BK_OK;
+}
+
+int bk_cohort_explained(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* explained, uint32_t* minor_sites) {
+    if (!e) return fail(BK_ERR_INVALID, "bk_cohort_explained: e is null");
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_cohort_explained inside a sample: it comes before bk_sample_begin or after the sample's downloads");
+    if (!e->cohort) return fail(BK_ERR_STATE, "bk_cohort_explained comes after bk_cohort_set and bk_cohort_set_minor");
+    Cohort& c = *e->cohort;
+    if (!c.minor.p) return fail(BK_ERR_STATE, "bk_cohort_explained comes after bk_cohort_set_minor");
+    if (n_rows == 0) return fail(BK_ERR_INVALID, "bk_cohort_explained: n_rows must be at least 1");
+    if (row0 >= c.n || n_rows > c.n - row0)
+        return fail(BK_ERR_INVALID, "bk_cohort_explained: row0 = %llu, n_rows = %llu lie beyond the cohort's %llu samples", (unsigned long long)row0, (unsigned long long)n_rows, (unsigned long long)c.n);
+    BK_HIP(hipSetDevice(e->device));
+    if (explained) {
+        const size_t block = (size_t)n_rows * c.n;
+        BK_HIP(grow(c.ex_out, block, 0, e->stream));
+        bk::ExplainedArgs a{};
+        a.planes = c.planes.p; a.minor = c.minor.p; a.n = c.n; a.n_stride = c.n_stride; a.W = c.W; a.row0 = row0; a.n_rows = n_rows;
+        a.n_col_tiles = (uint32_t)((c.n + bk::kTile - 1) / bk::kTile);
+        const uint64_t n_row_tiles = (n_rows + bk::kTile - 1) / bk::kTile, tiles = n_row_tiles * a.n_col_tiles;
+        if (tiles > 0x7fffffffull) return fail(BK_ERR_INVALID, "bk_cohort_explained: n_rows = %llu is too many rows for one block of %llu columns", (unsigned long long)n_rows, (unsigned long long)c.n);
+        uint64_t slice_words, chunk;
+        cut_slices(c, tiles, slice_words, chunk);
+        a.slice_words = (uint32_t)slice_words; a.chunk = (uint32_t)chunk;
+        a.explained = c.ex_out.p;
+        BK_HIP(hipMemsetAsync(c.ex_out.p, 0, block * sizeof(unsigned int), e->stream));
+        const dim3 grid((unsigned)tiles, (unsigned)((c.W + slice_words - 1) / slice_words));
+        hipLaunchKernelGGL(bk::cohort_explained_kernel, grid, dim3(bk::kCohortBlock), 0, e->stream, a);
+        BK_HIP(hipGetLastError());
+        BK_HIP(hipMemcpyAsync(explained, c.ex_out.p, block * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    }
+    if (minor_sites) BK_HIP(hipMemcpyAsync(minor_sites, c.minor_sites.p + row0, (size_t)n_rows * sizeof(unsigned int), hipMemcpyDeviceToHost, e->stream));
+    BK_HIP(hipStreamSynchronize(e->stream));
     return BK_OK;
 }

@@ -308,7 +308,7 @@ int bk_sample_begin(bk_engine* e) {
     if (e->linkage) { if (int rc = e->linkage->begin_sample(e)) return rc; }
     if (e->primers) { if (int rc = e->primers->begin_sample(e)) return rc; }
     if (e->adapters) { if (int rc = e->adapters->begin_sample(e)) return rc; }
-    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0; e->called = false; e->cons_made = false; e->ci_made = false; e->regions_made = false;
+    e->ktab_exchanged = false; e->in_sample = true; e->finalized_mates = 0; e->called = false; e->cons_made = false; e->minor_made = false; e->ci_made = false; e->regions_made = false;
     // items of a sample that was begun and never finalized are nobody's any more; neither are the rows Level 2 noted for them
     e->pending.on = false;
     for (MatePlane& p : e->mate) { if (int rc = p.begin_sample(e)) return rc; }

@@ -2,8 +2,8 @@
 // index tables that bk_engine_create builds and its forks share, and struct bk_engine itself.  Included by bk_index_tables.cpp (the
 // index tables), bk_ingest.cpp (reads -> records ready to scan: the bk_push_reads_* entry points, K0, the trimming stage, the host
 // packer), bk_engine.cpp (the engine's life, the sample path from push_device to bk_sample_download), bk_riders.cpp (the passes that
-// ride behind every scan: the k-mer dump, indels, linkage and the codon, haplotype and read-pileup counts over linkage's rows), bk_reports.cpp (the reports made of a pileup: calls, consensus, regions)
-// and bk_cohort.hip (the distances of a cohort of consensus sequences and its minimum spanning forest).
+// ride behind every scan: the k-mer dump, indels, linkage and the codon, haplotype and read-pileup counts over linkage's rows), bk_reports.cpp (the reports made of a pileup: calls, consensus, minor alleles, regions)
+// and bk_cohort.hip (the distances of a cohort of consensus sequences, its minimum spanning forest and the alleles its samples carry of each other).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -361,7 +361,7 @@ struct Breakends : EventPassOf<bk_breakend_config, bk_breakend_record> {
 };
 struct Duplications : EventPassOf<bk_duplication_config, bk_duplication_record> { int push(bk_engine* e, const Records& r) override; };
 
-// bk_cohort_set: the cohort's bit planes and the output block of the last bk_cohort_distances (bk_cohort.hip).  No part of a sample:
+// bk_cohort_set: the cohort's bit planes, the output block of the last bk_cohort_distances and what bk_cohort_set_minor adds (bk_cohort.hip).  No part of a sample:
 // bk_sample_begin and what follows it never look at it
 struct Cohort {
     uint64_t n = 0, positions = 0;          // samples, letters of each
@@ -369,6 +369,10 @@ struct Cohort {
     uint64_t n_stride = 0;                  // n rounded up to 64, plus 64: the padding samples are all zero
     DevBuf<unsigned long long> planes;      // [3][W][n_stride] valid, b0, b1
     DevBuf<unsigned int> out;               // [2][rows of the largest block so far][n] diff, compared
+    // bk_cohort_set_minor (empty before it: no minor planes)
+    DevBuf<unsigned long long> minor;       // [4][W][n_stride] M_A, M_C, M_G, M_T: X is present, the consensus is a base and not X
+    DevBuf<unsigned int> minor_sites;       // [n] positions with any of the four
+    DevBuf<unsigned int> ex_out;            // [rows of the largest block so far][n] explained (bk_cohort_explained's own block)
     // bk_cohort_mst (allocated by its first call on this cohort; empty before)
     DevBuf<unsigned int> mst_label;         // [n] a sample's component, named by the component's first sample
     DevBuf<unsigned long long> mst_row_key; // [n] per row the least diff << 32 | j over the admissible columns of another component (~0: none)
@@ -600,6 +604,10 @@ struct bk_engine {
     DevBuf<bk_consensus_summary> cons_out;
     bool cons_made = false;
     bk_consensus_params cons_prm{};         // ... with these parameters
+    // bk_sample_minor_alleles (first use allocates): a present mask per cell of the largest genome, the summary; made for the current sample
+    DevBuf<uint8_t> minor_masks;
+    DevBuf<bk_minor_summary> minor_out;
+    bool minor_made = false;
     // bk_sample_consensus_indels (first use allocates): best and ties of every boundary, the accepted events, the summary; made of the
     // current sample's letters as they are (a later bk_sample_consensus or bk_sample_call clears it)
     DevBuf<unsigned int> ci_bounds;         // [2][total_cells + 1] ConsensusIndelArgs::best, ties in this order: zeroed by one memset

@@ -472,6 +472,22 @@ struct ConsensusArgs {
     ConsensusSummaryDev* summary;        // tallies zeroed by the caller; the kernel writes file_id and adds
 };
 void launch_consensus(const ConsensusArgs& a, uint64_t max_file_cells, hipStream_t stream);
+// bk_sample_minor_alleles: the present mask of every position of the genome bk_sample_call selected (minor_alleles_kernel, bk_caller.hip)
+typedef bk_minor_params MinorParamsDev;
+typedef bk_minor_summary MinorSummaryDev;
+struct MinorArgs {
+    MinorParamsDev prm;
+    const int32_t* seq_first;            // the geometry CallArgs has
+    const int32_t* n_seqs;
+    const uint64_t* seq_cell;
+    const uint64_t* seq_len;
+    const unsigned long long* pileup;    // the two depth planes are read
+    size_t plane;
+    const CallSummaryDev* out;           // bk_sample_call's: file_id
+    uint8_t* masks;                      // [cells of the selected genome] in (sequence, position) order
+    MinorSummaryDev* summary;            // tallies zeroed by the caller; the kernel writes file_id and adds
+};
+void launch_minor_alleles(const MinorArgs& a, uint64_t max_file_cells, hipStream_t stream);
 // bk_sample_region_depths: the depth numbers of every region of the genome bk_sample_call selected (region_depth_kernel, bk_regions.hip)
 typedef bk_region_depth RegionDepthDev;
 typedef bk_region_summary RegionSummaryDev;

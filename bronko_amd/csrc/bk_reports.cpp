@@ -1,6 +1,6 @@
 // bk_reports.cpp -- the reports made of a finalized sample's pileup on the device, and their downloads: the calls and the noise
 // (bk_sample_call, bk_caller.hip), the consensus (consensus_kernel, bk_caller.hip) with the sample's indels applied to it (bk_consensus_indels.hip) and the per-region depths (bk_regions.hip).  Their
-// buffers and the flags that say whose sample a result is (called, cons_made, ci_made, regions_made) are bk_engine's (bk_engine.h).  The entry
+// buffers and the flags that say whose sample a result is (called, cons_made, minor_made, ci_made, regions_made) are bk_engine's (bk_engine.h).  The entry
 // points are extern "C" by their declarations in bronko_hip.h.
 #include <algorithm>
 #include <cstdlib>
@@ -54,7 +54,7 @@ int bk_sample_call(bk_engine* e, int n_mates, const bk_call_params* p) {
     bk_engine::Span sp(e, 1);
     bk::launch_call(a, ix.max_seqs_per_file, ix.max_file_cells, e->stream);
     BK_HIP(hipGetLastError());
-    e->called = true; e->cons_made = false; e->ci_made = false; e->regions_made = false;   // (a consensus or a region report made before this call was of another selection)
+    e->called = true; e->cons_made = false; e->minor_made = false; e->ci_made = false; e->regions_made = false;   // (a consensus or a region report made before this call was of another selection)
     return BK_OK;
 }
 
@@ -129,6 +129,49 @@ int bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, ui
     if (int rc = download(e, summary, e->cons_out.p, 1)) return rc;
     const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->positions, cap), e->cons_letters.n);
     if (n && letters) return download(e, letters, e->cons_letters.p, (size_t)n);
+    return BK_OK;
+}
+
+// ---- per-sample minor alleles (minor_alleles_kernel, bk_caller.hip) -----------------------------------------------
+void bk_minor_params_default(bk_minor_params* p) {
+    if (!p) return;
+    p->min_reads = 10; p->min_freq = 0.03;
+}
+
+int bk_sample_minor_alleles(bk_engine* e, const bk_minor_params* p) {
+    if (!e) return fail(BK_ERR_INVALID, "bk_sample_minor_alleles: e is null");
+    if (!p) return fail(BK_ERR_INVALID, "bk_sample_minor_alleles: p is null");
+    if (p->min_reads < 1) return fail(BK_ERR_INVALID, "bk_sample_minor_alleles: min_reads must be at least 1, got %llu", (unsigned long long)p->min_reads);
+    if (!(p->min_freq >= 0.0 && p->min_freq <= 1.0)) return fail(BK_ERR_INVALID, "bk_sample_minor_alleles: min_freq must be between 0 and 1, got %g", p->min_freq);
+    if (e->in_sample) return fail(BK_ERR_STATE, "bk_sample_minor_alleles comes after bk_sample_finalize and bk_sample_call");
+    if (!e->called) return fail(BK_ERR_STATE, "bk_sample_minor_alleles: bk_sample_call has not run for this sample");
+    const IndexTables& ix = *e->ix;
+    BK_HIP(hipSetDevice(e->device));
+    if (!e->minor_out.p) {
+        BK_HIP(e->minor_masks.alloc((size_t)ix.max_file_cells));
+        BK_HIP(e->minor_out.alloc(1));
+    }
+    bk::MinorArgs a{};
+    a.prm = *p;
+    a.seq_first = ix.seq_first.p; a.n_seqs = ix.n_seqs_d.p; a.seq_cell = ix.seq_cell.p; a.seq_len = ix.seq_len_d.p;
+    a.pileup = e->pileup.p; a.plane = (size_t)ix.total_cells * 4;
+    a.out = e->call_out.p; a.masks = e->minor_masks.p; a.summary = e->minor_out.p;
+    bk_engine::Span sp(e, 1);
+    BK_HIP(hipMemsetAsync(e->minor_out.p, 0, sizeof(bk_minor_summary), e->stream));
+    bk::launch_minor_alleles(a, ix.max_file_cells, e->stream);
+    BK_HIP(hipGetLastError());
+    e->minor_made = true;
+    return BK_OK;
+}
+
+int bk_sample_download_minor_alleles(bk_engine* e, bk_minor_summary* summary, uint8_t* masks, uint64_t cap) {
+    if (!e) return fail(BK_ERR_INVALID, "bk_sample_download_minor_alleles: e is null");
+    if (!summary) return fail(BK_ERR_INVALID, "bk_sample_download_minor_alleles: summary is null");
+    if (!e->minor_made) return fail(BK_ERR_STATE, "bk_sample_download_minor_alleles comes after this sample's bk_sample_minor_alleles");
+    BK_HIP(hipSetDevice(e->device));
+    if (int rc = download(e, summary, e->minor_out.p, 1)) return rc;
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(summary->positions, cap), e->minor_masks.n);
+    if (n && masks) return download(e, masks, e->minor_masks.p, (size_t)n);
     return BK_OK;
 }
 

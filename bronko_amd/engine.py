@@ -434,6 +434,28 @@ class Engine:
         _check(self._L.bk_sample_download_consensus(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
         return summ, buf[:min(cap, int(summ.positions))].tobytes()
 
+    def minor_params(self, **kw):
+        """bk_minor_params with the defaults (min_reads 10, min_freq 0.03); keyword overrides."""
+        p = _ffi.MinorParams()
+        self._L.bk_minor_params_default(C.byref(p))
+        for name, v in kw.items():
+            setattr(p, name, v)
+        return p
+
+    def sample_minor_alleles(self, params=None):
+        """The present mask of every position of the genome sample_call selected, on the device (asynchronous)."""
+        _check(self._L.bk_sample_minor_alleles(self.h, C.byref(params or self.minor_params())), self._L)
+
+    def download_minor_alleles(self, cap=None):
+        """(summary, masks as a uint8 array) of sample_minor_alleles: min(cap, summary.positions) bytes, all of them by default."""
+        summ = _ffi.MinorSummary()
+        if cap is None:
+            _check(self._L.bk_sample_download_minor_alleles(self.h, C.byref(summ), None, 0), self._L)   # (the summary first: how many bytes there are)
+            cap = int(summ.positions)
+        buf = np.zeros(max(1, cap), np.uint8)
+        _check(self._L.bk_sample_download_minor_alleles(self.h, C.byref(summ), buf.ctypes.data_as(C.c_void_p), cap), self._L)
+        return summ, buf[:min(cap, int(summ.positions))]
+
     def _download_events(self, download, summ, cap, dtype, columns=None):
         """What the six download_x of the event passes do alike: (summary, min(cap, summary.reported) rows of `dtype`, `columns` wide) --
         all rows when cap is None, by asking for the summary first."""
@@ -723,6 +745,25 @@ class Engine:
                                      near.ctypes.data_as(C.POINTER(_ffi.MstNearest)) if nearest else None,
                                      C.byref(n_rounds) if rounds else None), self._L)
         return edges[:int(n_edges.value)], (near[:n] if nearest else None), (int(n_rounds.value) if rounds else None)
+
+    def cohort_set_minor(self, masks):
+        """bk_cohort_set_minor: the present masks of the cohort's samples, an (n_samples, positions) uint8 array shaped like the
+        letters of cohort_set, uploaded and packed into four minor planes per sample; a later cohort_set drops them."""
+        a = np.ascontiguousarray(masks, np.uint8)
+        if a.ndim != 2:
+            raise ValueError("cohort_set_minor takes a 2-d array: a row of masks per sample")
+        _check(self._L.bk_cohort_set_minor(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1]), self._L)
+
+    def cohort_explained(self, row0=0, n_rows=None):
+        """bk_cohort_explained: (explained, minor_sites) of the rows [row0, row0 + n_rows) -- the recipients -- against every sample of
+        the cohort, an (n_rows, n_samples) and an (n_rows,) uint32 array; all rows from row0 on by default."""
+        n = int(getattr(self, "_cohort_n", 0))
+        if n_rows is None:
+            n_rows = max(0, n - int(row0))
+        explained = np.zeros((max(1, int(n_rows)), max(1, n)), np.uint32)
+        sites = np.zeros(max(1, int(n_rows)), np.uint32)
+        _check(self._L.bk_cohort_explained(self.h, int(row0), int(n_rows), explained.ctypes.data_as(C.c_void_p), sites.ctypes.data_as(C.c_void_p)), self._L)
+        return explained[:int(n_rows), :n], sites[:int(n_rows)]
 
     def cohort_clear(self):
         """bk_cohort_clear: frees the cohort's device memory (fine without a cohort)."""

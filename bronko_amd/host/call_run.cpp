@@ -351,6 +351,7 @@ struct SampleData {
     std::vector<bk_call_record> recs;
     Rows<bk_consensus_summary, uint8_t> consensus;        // --consensus: the letters
     Rows<bk_consensus_indel_summary, ConsensusIndel> cons_indels;   // --consensus-indels
+    Rows<bk_minor_summary, uint8_t> minor;                // --contamination: the present masks
     Rows<bk_region_summary, bk_region_depth> regions;     // --regions, --region-window
     decltype(rows_of(AnchorPasses{})) events;             // the anchor passes: a PassRows<P> each
     Rows<bk_link_summary, LinkPair> linkage;              // --linkage
@@ -371,6 +372,7 @@ struct CallRun {
     std::vector<SampleCalls> all_calls;              // --alignment
     std::vector<std::vector<uint8_t>> cohort_letters;   // --distances: by sample, its consensus letters (n x positions bytes of host memory in all)
     std::vector<int> cohort_genome;                  // ... and the genome file it selected (-1: none)
+    std::vector<std::vector<uint8_t>> cohort_masks;  // --contamination: by sample, its present masks (n x positions more bytes)
     int dump_threads = 1;                            // --keep-kmer-info: threads that format one sample's counts (set before the lanes start)
 
     // the samples, in input order; their files are read ahead from here on (ReadAhead): the index and the engine's tables take
@@ -381,6 +383,7 @@ struct CallRun {
         overview.resize(samples.size());
         if (a.alignment) all_calls.resize(samples.size());
         if (a.distances) { cohort_letters.resize(samples.size()); cohort_genome.assign(samples.size(), -1); }
+        if (a.contamination) cohort_masks.resize(samples.size());
         if (!getenv("BRONKO_NO_READ_AHEAD")) {
             const uint64_t ram = (uint64_t)sysconf(_SC_PHYS_PAGES) * (uint64_t)sysconf(_SC_PAGE_SIZE);
             ahead.reset(new ReadAhead(samples, cfg, (unsigned)std::max<long>(2, a.threads / 8), std::min<uint64_t>(ram / 4, 32ull << 30)));
@@ -424,6 +427,16 @@ struct CallRun {
         LOG_INFO(T, "Consensus of " + num(c.positions) + " positions: " + num(c.called) + " called (" + num(c.substitutions) + " substitutions), " + num(c.ambiguous) +
                         " ambiguous, " + num(c.masked) + " masked");
         if (!a.consensus_indels) write_consensus_fasta(base + ".consensus.fa", stem, ix, best, d.consensus.rows.data(), c.positions);
+    }
+    // --contamination: the present masks, on the device, behind the consensus; only the bytes travel
+    void minor_launch(bk_engine* e) const { if (a.contamination) hip_check(bk_sample_minor_alleles(e, &cfg.minor), "bk_sample_minor_alleles"); }
+    void minor_download(bk_engine* e, uint64_t longest, SampleData& d) const {
+        if (!a.contamination) return;
+        d.minor.rows.resize((size_t)longest);
+        hip_check(bk_sample_download_minor_alleles(e, &d.minor.summ, d.minor.rows.data(), d.minor.rows.size()), "bk_sample_download_minor_alleles");
+    }
+    void minor_log(const SampleData& d) const {
+        if (a.contamination) LOG_INFO(T, "Minor alleles: " + num(d.minor.summ.mixed) + " mixed positions, " + num(d.minor.summ.present) + " bases present");
     }
     // --consensus-indels: the indels join the letters where both lie; the few accepted events travel
     void consensus_indels_launch(bk_engine* e) const { if (a.consensus_indels) hip_check(bk_sample_consensus_indels(e), "bk_sample_consensus_indels"); }
@@ -749,6 +762,7 @@ struct CallRun {
         });
         hip_check(bk_sample_call(e, n_mates, &cfg.call), "bk_sample_call");
         consensus_launch(e);        // behind the calls, in this order
+        minor_launch(e);
         consensus_indels_launch(e);
         regions_launch(e);
     }
@@ -779,6 +793,7 @@ struct CallRun {
         d.recs.resize((size_t)(3 * longest));
         hip_check(bk_sample_download_calls(e, &d.summ, d.recs.data(), d.recs.size()), "bk_sample_download_calls");
         consensus_download(e, longest, d);
+        minor_download(e, longest, d);
         consensus_indels_download(e, d);
         regions_download(e, d);
         each_anchor_pass([&](auto p) {
@@ -829,6 +844,7 @@ struct CallRun {
             LOG_INFO(T, "Writing output to VCF");
             write_vcf(base + ".vcf", mates[0], ix, best, cs.records);
             consensus_write(base, stem, best, d);
+            minor_log(d);
             consensus_indels_write(base, stem, best, d);
             regions_write(base, best, d);
             each_anchor_pass([&](auto p) {   // (a sample without events: the headers alone)
@@ -875,6 +891,7 @@ struct CallRun {
             cohort_letters[sample_id].assign(d.consensus.rows.begin(), d.consensus.rows.begin() + (ptrdiff_t)std::min<uint64_t>(d.consensus.summ.positions, d.consensus.rows.size()));
             cohort_genome[sample_id] = best;
         }
+        if (a.contamination) cohort_masks[sample_id].assign(d.minor.rows.begin(), d.minor.rows.begin() + (ptrdiff_t)std::min<uint64_t>(d.minor.summ.positions, d.minor.rows.size()));
     }
 
     // ---- --mst: the minimum spanning forest of the cohort the engine holds, found on the device; OUT/<genome>.mst.tsv ----
@@ -905,7 +922,7 @@ struct CallRun {
 
     // ---- --distances: the samples' consensus letters compared pair by pair, per selected genome, on one engine that is still alive ----
     void write_distances(bk_engine* e) {
-        constexpr uint64_t kBlockBytes = 256ull << 20;   // a block's two host buffers together
+        constexpr uint64_t kBlockBytes = 256ull << 20;   // a block's host buffers together: two, three under --contamination
         for (size_t i = 0; i < samples.size(); i++)
             if (cohort_genome[i] < 0) LOG_INFO(T, "Distances: " + clean_sample_id(samples[i][0]) + " selected no genome and is left out");
         for (size_t g = 0; g < ix.files.size(); g++) {
@@ -927,12 +944,27 @@ struct CallRun {
                 std::vector<uint8_t>().swap(l);   // (a sample's letters are held once)
             }
             hip_check(bk_cohort_set(e, letters.data(), n, positions), "bk_cohort_set");
+            if (a.contamination) {   // (the masks take the letters' place in the same buffer)
+                for (size_t r = 0; r < n; r++) {
+                    std::vector<uint8_t>& m = cohort_masks[group[r]];
+                    if (m.size() != positions) die(T, "Contamination: the minor alleles of " + names[r] + " are not as long as " + gname);
+                    std::copy(m.begin(), m.end(), letters.begin() + (ptrdiff_t)(r * positions));
+                    std::vector<uint8_t>().swap(m);
+                }
+                hip_check(bk_cohort_set_minor(e, letters.data(), n, positions), "bk_cohort_set_minor");
+            }
             std::vector<uint8_t>().swap(letters);
-            const uint64_t block_rows = std::max<uint64_t>(1, std::min<uint64_t>(n, kBlockBytes / (8 * n)));
-            std::vector<uint32_t> diff((size_t)(block_rows * n)), compared((size_t)(block_rows * n));
+            const uint64_t block_rows = std::max<uint64_t>(1, std::min<uint64_t>(n, kBlockBytes / ((a.contamination ? 12 : 8) * n)));
+            std::vector<uint32_t> diff((size_t)(block_rows * n)), compared((size_t)(block_rows * n)), explained(a.contamination ? (size_t)(block_rows * n) : 0);
+            std::vector<uint32_t> minor_sites(a.contamination ? (size_t)n : 0);
             uint64_t max_diff = 0, empty_pairs = 0;
             CohortClusters cl;
+            Contamination mix;
             try {
+                std::unique_ptr<CohortMatrixWriter> we;
+                if (a.contamination) we.reset(new CohortMatrixWriter(a.output + "/" + gname + ".explained.tsv", names));
+                std::unique_ptr<ContaminationScanner> scanner;
+                if (a.contamination) scanner.reset(new ContaminationScanner(n, cfg.contamination.min_sites, cfg.contamination.min_share));
                 CohortMatrixWriter wd(a.output + "/" + gname + ".distances.tsv", names), wc(a.output + "/" + gname + ".compared.tsv", names);
                 CohortClusterer clusterer(n, positions, (uint64_t)a.clusters, a.cluster_min_breadth);
                 for (uint64_t row0 = 0; row0 < n; row0 += block_rows) {
@@ -941,6 +973,11 @@ struct CallRun {
                     wd.add_rows(row0, rows, diff.data());
                     wc.add_rows(row0, rows, compared.data());
                     if (a.has_clusters()) clusterer.add_rows(row0, rows, diff.data(), compared.data());
+                    if (a.contamination) {
+                        hip_check(bk_cohort_explained(e, row0, rows, explained.data(), minor_sites.data() + row0), "bk_cohort_explained");
+                        we->add_rows(row0, rows, explained.data());
+                        scanner->add_rows(row0, rows, diff.data(), compared.data(), explained.data());
+                    }
                     for (uint64_t r = 0; r < rows; r++)
                         for (uint64_t j = row0 + r + 1; j < n; j++) {   // (each pair once)
                             max_diff = std::max<uint64_t>(max_diff, diff[r * n + j]);
@@ -952,6 +989,12 @@ struct CallRun {
                     cl = clusterer.finish();
                     write_cohort_clusters_tsv(a.output + "/" + gname + ".clusters.tsv", names, cl, (uint64_t)a.clusters, a.cluster_min_breadth);
                 }
+                if (a.contamination) {
+                    we->close();
+                    mix = scanner->finish();
+                    write_contamination_tsv(a.output + "/" + gname + ".contamination.tsv", names, mix, minor_sites, cfg.contamination);
+                    write_mixture_tsv(a.output + "/" + gname + ".mixture.tsv", names, mix, minor_sites, cfg.contamination);
+                }
             } catch (const std::exception& ex) { die(T, ex.what()); }
             char secs[32];
             snprintf(secs, sizeof secs, "%.3f", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -959,6 +1002,9 @@ struct CallRun {
                             std::to_string(empty_pairs) + " pairs with nothing compared" +
                             (a.has_clusters() ? ", " + std::to_string(cl.n_clusters) + " clusters, the largest of " + std::to_string(cl.largest) + " samples" : std::string()) +
                             " (" + secs + " s)");
+            if (a.contamination)
+                LOG_INFO(T, "Contamination for " + gname + ": " + std::to_string(n) + " samples, " + std::to_string(mix.flagged.size()) + " flagged pairs, " +
+                                std::to_string(mix.recipients) + " samples flagged at least once, largest explained " + std::to_string(mix.largest));
             if (a.mst) write_forest(e, gname, names, positions);   // (the cohort is still set)
         }
         hip_check(bk_cohort_clear(e), "bk_cohort_clear");

@@ -84,7 +84,8 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "            [--codon-min-reads N] [--codon-min-freq F] [--codon-max-mismatches M] [--haplotypes BED | --hap-window W [--hap-step S]]\n"
           "            [--hap-min-reads N] [--hap-min-freq F] [--hap-max-mismatches M] [--read-pileup] [--read-pileup-end E]\n"
           "            [--read-pileup-max-mismatches M] [--distances] [--clusters T] [--cluster-min-breadth B]\n"
-          "            [--mst] [--mst-min-breadth B]\n"
+          "            [--mst] [--mst-min-breadth B] [--contamination] [--minor-min-reads R] [--minor-min-freq F]\n"
+          "            [--contamination-min-sites S] [--contamination-min-share P]\n"
           "            [-t <THREADS>] [--debug] [--verbose]\n\n"
           "  --keep-kmer-info  write every reads file's k-mer counts to <DIR>/<stem>_counts.txt: \"KMER<TAB>COUNT\" per line,\n"
           "                    k-mers in ascending order, strand-specific, kept by --min-kmers, counts capped at 1000000\n"
@@ -196,7 +197,17 @@ bool check_fasta(const std::string& f) {   // util.rs:17-28
           "                    parent towards its component's first sample, that edge's distance and compared positions, its component and\n"
           "                    its nearest neighbour; a pair is an edge only if it compared at least one position and at least B of the\n"
           "                    genome's; equally distant candidates are chosen by sample order; a forest of consensus distances, not a phylogeny\n"
-          "  --mst-min-breadth B  share of the genome's positions a pair must have compared to be an edge; 0..1, default 0.9\n", stderr);
+          "  --mst-min-breadth B  share of the genome's positions a pair must have compared to be an edge; 0..1, default 0.9\n"
+          "  --contamination   find the samples that carry another sample's alleles as minor variants (needs --distances): a base is present at\n"
+          "                    a position when R reads and F of the depth carry it; <DIR>/<genome>.explained.tsv holds per recipient (row) and\n"
+          "                    source (column) the positions at which both consensus letters are one of ACGT, differ, and the source's is\n"
+          "                    present in the recipient; <DIR>/<genome>.contamination.tsv lists the pairs with at least S such positions that\n"
+          "                    make up at least P of their differences, <DIR>/<genome>.mixture.tsv every sample's best source; no noise, strand\n"
+          "                    or end filter; a related third sample is flagged along with the true source\n"
+          "  --minor-min-reads R  reads of a base for it to be present at a position; at least 1, default 10\n"
+          "  --minor-min-freq F   share of a position's depth a present base reaches; 0..1, default the value of --min-af\n"
+          "  --contamination-min-sites S  explained positions a flagged pair has at least; at least 1, default 3\n"
+          "  --contamination-min-share P  share of a pair's differences that are explained, at least; 0..1, default 0.75\n", stderr);
     exit(code);
 }
 
@@ -328,6 +339,11 @@ const Opt kOpts[] = {
     Opt("--cluster-min-breadth", &Args::cluster_min_breadth),
     Opt("--mst", &Args::mst),
     Opt("--mst-min-breadth", &Args::mst_min_breadth),
+    Opt("--contamination", &Args::contamination),
+    Opt("--minor-min-reads", kInt, &Args::minor_min_reads),
+    Opt("--minor-min-freq", &Args::minor_min_freq),
+    Opt("--contamination-min-sites", kInt, &Args::contamination_min_sites),
+    Opt("--contamination-min-share", &Args::contamination_min_share),
 };
 static_assert(sizeof kOpts / sizeof kOpts[0] <= 128, "Args::given_rows has a bit per row");
 
@@ -597,6 +613,14 @@ void one_m(const Args& a) {
                         std::to_string(r[N].m) + ") must be equal");
 }
 
+// --minor-min-freq not given: the value of --min-af stands in for it, and must lie in its range
+void minor_freq_from_min_af(const Args& a) {
+    if (!a.contamination || a.given("--minor-min-freq") || (a.min_af >= 0.0 && a.min_af <= 1.0)) return;
+    char got[64];
+    snprintf(got, sizeof got, "%g", a.min_af);
+    die(TC, std::string("--minor-min-freq must be between 0 and 1, got ") + got + " (the value of --min-af)");
+}
+
 const Rule kRules[] = {
     by_hand(reference_checks),
     range("--min-base-qual", 0, 93, "Minimum base quality", " (Phred+33)"),
@@ -669,6 +693,13 @@ const Rule kRules[] = {
     needs("--mst", on<&Args::distances>, "--distances"),
     needs("--mst-min-breadth", on<&Args::mst>, "--mst"),
     range("--mst-min-breadth", 0, 1),
+    needs("--contamination", on<&Args::distances>, "--distances"),
+    needs("--minor-min-reads --minor-min-freq --contamination-min-sites --contamination-min-share", on<&Args::contamination>, "--contamination"),
+    at_least("--minor-min-reads", 1),
+    range("--minor-min-freq", 0, 1).when_given(),
+    by_hand(minor_freq_from_min_af),
+    at_least("--contamination-min-sites", 1),
+    range("--contamination-min-share", 0, 1),
 };
 
 void check_call_args(const Args& a) {
@@ -720,6 +751,10 @@ CallConfig make_call_config(const Args& a) {
     d.min_depth = cp.min_depth; d.min_variant_depth = cp.min_variant_depth;
     bk_consensus_params_default(&c.consensus);
     c.consensus.min_depth = (uint64_t)a.consensus_min_depth; c.consensus.min_freq = a.consensus_min_freq;
+    bk_minor_params_default(&c.minor);
+    c.minor.min_reads = (uint64_t)a.minor_min_reads; c.minor.min_freq = a.given("--minor-min-freq") ? a.minor_min_freq : a.min_af;
+    c.contamination.minor_min_reads = c.minor.min_reads; c.contamination.minor_min_freq = c.minor.min_freq;
+    c.contamination.min_sites = (uint32_t)std::min<long>(a.contamination_min_sites, 0xffffffffl); c.contamination.min_share = a.contamination_min_share;
     // (the chrom names of the three BED files meet the index's in call_samples, once its metadata is known)
     auto bed_file = [&](bool given, const std::string& path, std::vector<BedLine> (*read)(const std::string&), const char* what, std::vector<BedLine>& lines, std::string& kept) {
         if (!given) return;

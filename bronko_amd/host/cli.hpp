@@ -127,6 +127,11 @@ struct Args {
     double cluster_min_breadth = 0.9;   // --cluster-min-breadth B: share of the genome's positions a pair must have compared to be linked (0..1)
     bool mst = false;               // --mst: <DIR>/<genome>.mst.tsv, the minimum spanning forest of the samples' distances (needs --distances)
     double mst_min_breadth = 0.9;   // --mst-min-breadth B: share of the genome's positions a pair must have compared to be an edge (0..1)
+    bool contamination = false;     // --contamination: <DIR>/<genome>.explained.tsv, .contamination.tsv and .mixture.tsv, which sample's alleles another carries (needs --distances)
+    long minor_min_reads = 10;      // --minor-min-reads R: reads of a base for it to be present at a position (at least 1)
+    double minor_min_freq = 0.03;   // --minor-min-freq F: share of the position's depth a present base reaches (0..1; not given: the value of --min-af)
+    long contamination_min_sites = 3;      // --contamination-min-sites S: explained positions a flagged pair has at least (at least 1)
+    double contamination_min_share = 0.75; // --contamination-min-share P: share of the pair's differences that are explained, at least (0..1)
     std::string output;             // default depends on the mode
     bool pileup = false, alignment = false, keep_kmer_info = false;
     long threads = 4;
@@ -155,6 +160,8 @@ struct CallConfig {
     CallParams cp;                          // the printed strand odds (strand_odds, caller.hpp)
     bk_call_params call;                    // bk_sample_call
     bk_consensus_params consensus;          // bk_sample_consensus (--consensus)
+    bk_minor_params minor;                  // bk_sample_minor_alleles (--contamination)
+    ContaminationParams contamination;      // ... the scanner's thresholds and the values the three files' header lines print
     // --regions: the file's data lines (resolved against the index once it is open, call_run.cpp); --region-window; neither: no report
     std::string regions_path;
     std::vector<BedLine> bed;

@@ -334,6 +334,157 @@ void write_cohort_compared_tsv(const std::string& path, const std::vector<std::s
     write_cohort_distances_tsv(path, names, compared);
 }
 
+// ---- --contamination --------------------------------------------------------------------------------------------------------------
+MinorSummary minor_mask_host(const uint64_t* fwd, const uint64_t* rev, uint64_t positions, uint64_t min_reads, double min_freq, uint8_t* masks) {
+    MinorSummary s;
+    s.positions = positions;
+    for (uint64_t p = 0; p < positions; p++) {
+        uint64_t tot[4], depth = 0;
+        for (int b = 0; b < 4; b++) { tot[b] = fwd[p * 4 + b] + rev[p * 4 + b]; depth += tot[b]; }
+        const double need = min_freq * (double)depth;
+        unsigned mask = 0;
+        for (int b = 0; b < 4; b++)
+            if (tot[b] >= min_reads && (double)tot[b] >= need) mask |= 1u << b;
+        s.mixed += (mask & (mask - 1)) != 0;
+        s.present += (uint64_t)__builtin_popcount(mask);
+        if (masks) masks[p] = (uint8_t)mask;
+    }
+    return s;
+}
+
+namespace {
+// one recipient row against all columns: M_X of the row, C_X of the columns made of their three planes
+#if defined(__x86_64__)
+__attribute__((target("popcnt")))
+#endif
+void explained_row(const CohortPlanes& p, const std::vector<uint64_t>& minor, uint64_t i, uint32_t* explained) {
+    const uint64_t W = p.W;
+    const uint64_t* m = minor.data() + i * 4 * W;   // [A C G T][W]
+    for (uint64_t j = 0; j < p.n; j++) {
+        const uint64_t *vj = p.valid.data() + j * W, *b0j = p.b0.data() + j * W, *b1j = p.b1.data() + j * W;
+        uint64_t ex = 0;
+        for (uint64_t w = 0; w < W; w++) {
+            const uint64_t v = vj[w], b0 = b0j[w], b1 = b1j[w];
+            ex += (uint64_t)__builtin_popcountll((m[w] & v & ~b0 & ~b1) | (m[W + w] & v & b0 & ~b1) | (m[2 * W + w] & v & ~b0 & b1) | (m[3 * W + w] & v & b0 & b1));
+        }
+        explained[j] = (uint32_t)ex;
+    }
+}
+}  // namespace
+
+void cohort_explained_host(const uint8_t* letters, const uint8_t* masks, uint64_t n, uint64_t positions, uint64_t row0, uint64_t n_rows, uint32_t* explained,
+                           uint32_t* minor_sites, unsigned threads) {
+    if (row0 > n || n_rows > n - row0) throw std::runtime_error("cohort_explained_host: the rows lie beyond the cohort");
+    const CohortPlanes p = cohort_pack_host(letters, n, positions, threads);
+    const uint64_t W = p.W;
+    std::vector<uint64_t> minor((size_t)(n_rows * 4 * W), 0);   // of the block's rows only
+    over_threads(n_rows, threads, [&](uint64_t r0, uint64_t r1) {
+        for (uint64_t r = r0; r < r1; r++) {
+            const uint64_t s = row0 + r;
+            uint64_t sites = 0;
+            for (uint64_t pos = 0; pos < positions; pos++) {
+                const size_t at = (size_t)(s * W + pos / 64);
+                const uint64_t bit = 1ull << (pos % 64);
+                if (!(p.valid[at] & bit)) continue;
+                const unsigned code = (p.b0[at] & bit ? 1u : 0u) | (p.b1[at] & bit ? 2u : 0u);
+                const unsigned m = masks[s * positions + pos] & 15u & ~(1u << code);
+                for (unsigned b = 0; b < 4; b++)
+                    if (m >> b & 1u) minor[(size_t)((r * 4 + b) * W + pos / 64)] |= bit;
+                sites += m != 0;
+            }
+            if (minor_sites) minor_sites[r] = (uint32_t)sites;
+        }
+    });
+    if (!explained) return;
+    over_threads(n_rows, threads, [&](uint64_t r0, uint64_t r1) {
+        for (uint64_t r = r0; r < r1; r++) explained_row(p, minor, r, explained + r * n);
+    });
+}
+
+ContaminationScanner::ContaminationScanner(uint64_t n, uint32_t min_sites, double min_share) : n_(n), min_sites_(min_sites), min_share_(min_share) {
+    c_.best.assign((size_t)n, ContaminationBest{});
+    c_.n_flagged.assign((size_t)n, 0);
+}
+
+void ContaminationScanner::add_rows(uint64_t row0, uint64_t n_rows, const uint32_t* diff, const uint32_t* compared, const uint32_t* explained) {
+    if (row0 > n_ || n_rows > n_ - row0) throw std::runtime_error("ContaminationScanner: the rows lie beyond the cohort");
+    for (uint64_t r = 0; r < n_rows; r++) {
+        const uint64_t i = row0 + r;
+        ContaminationBest& best = c_.best[i];
+        for (uint64_t j = 0; j < n_; j++) {   // (ascending j: the earlier of equals stays)
+            if (j == i) continue;
+            const uint32_t ex = explained[r * n_ + j], d = diff[r * n_ + j];
+            c_.largest = std::max(c_.largest, ex);
+            if (ex >= 1 && (best.source == kCohortNone || ex > best.explained || (ex == best.explained && d < best.diff))) best = ContaminationBest{(uint32_t)j, ex, d};
+            if (ex >= min_sites_ && (double)ex >= min_share_ * (double)d) {
+                c_.flagged.push_back(ContaminationPair{(uint32_t)i, (uint32_t)j, d, compared[r * n_ + j], ex});
+                c_.n_flagged[i]++;
+            }
+        }
+    }
+}
+
+Contamination ContaminationScanner::finish() {
+    std::sort(c_.flagged.begin(), c_.flagged.end(), [](const ContaminationPair& x, const ContaminationPair& y) {
+        return x.recipient != y.recipient ? x.recipient < y.recipient : x.source < y.source;
+    });
+    c_.recipients = 0;
+    for (uint32_t f : c_.n_flagged) c_.recipients += f != 0;
+    return c_;
+}
+
+void write_cohort_explained_tsv(const std::string& path, const std::vector<std::string>& names, const uint32_t* explained) {
+    write_cohort_distances_tsv(path, names, explained);
+}
+
+namespace {
+// x / y with four decimals, truncated, from the integers (y > 0)
+std::string ratio4(uint64_t x, uint64_t y) {
+    char buf[48];
+    snprintf(buf, sizeof buf, "%llu.%04llu", (unsigned long long)(x / y), (unsigned long long)(x % y * 10000 / y));
+    return buf;
+}
+FILE* open_contamination_file(const std::string& path, const char* what, const ContaminationParams& p) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error(std::string(strerror(errno)) + " | Failed to create " + what + " file " + path);
+    fprintf(f, "##minor_min_reads=%llu\n##minor_min_freq=%g\n##contamination_min_sites=%u\n##contamination_min_share=%g\n", (unsigned long long)p.minor_min_reads,
+            p.minor_min_freq, p.min_sites, p.min_share);
+    return f;
+}
+}  // namespace
+
+void write_contamination_tsv(const std::string& path, const std::vector<std::string>& names, const Contamination& c, const std::vector<uint32_t>& minor_sites,
+                             const ContaminationParams& p) {
+    const size_t n = names.size();
+    if (minor_sites.size() != n) throw std::runtime_error("write_contamination_tsv: one minor_sites per sample");
+    for (const auto& x : c.flagged)
+        if (x.recipient >= n || x.source >= n || x.diff == 0 || minor_sites[x.recipient] == 0)
+            throw std::runtime_error("write_contamination_tsv: a flagged pair beyond the samples, or without a difference or a minor site");
+    FILE* f = open_contamination_file(path, "contamination", p);
+    fputs("recipient\tsource\tdiff\tcompared\texplained\tshare\tminor_sites\tminor_share\n", f);
+    for (const auto& x : c.flagged)
+        fprintf(f, "%s\t%s\t%u\t%u\t%u\t%s\t%u\t%s\n", names[x.recipient].c_str(), names[x.source].c_str(), x.diff, x.compared, x.explained, ratio4(x.explained, x.diff).c_str(),
+                minor_sites[x.recipient], ratio4(x.explained, minor_sites[x.recipient]).c_str());
+    if (fclose(f) != 0) throw std::runtime_error(std::string(strerror(errno)) + " | Failed to write " + path);
+}
+
+void write_mixture_tsv(const std::string& path, const std::vector<std::string>& names, const Contamination& c, const std::vector<uint32_t>& minor_sites,
+                       const ContaminationParams& p) {
+    const size_t n = names.size();
+    if (minor_sites.size() != n || c.best.size() != n || c.n_flagged.size() != n) throw std::runtime_error("write_mixture_tsv: one line per sample");
+    for (const auto& b : c.best)
+        if (b.source != kCohortNone && (b.source >= n || b.diff == 0)) throw std::runtime_error("write_mixture_tsv: a best source beyond the samples, or without a difference");
+    FILE* f = open_contamination_file(path, "mixture", p);
+    fputs("sample\tminor_sites\tflagged\tbest_source\texplained\tdiff\tshare\n", f);
+    for (size_t i = 0; i < n; i++) {
+        const ContaminationBest& b = c.best[i];
+        fprintf(f, "%s\t%u\t%u\t", names[i].c_str(), minor_sites[i], c.n_flagged[i]);
+        if (b.source == kCohortNone) fputs(".\t.\t.\t.\n", f);
+        else fprintf(f, "%s\t%u\t%u\t%s\n", names[b.source].c_str(), b.explained, b.diff, ratio4(b.explained, b.diff).c_str());
+    }
+    if (fclose(f) != 0) throw std::runtime_error(std::string(strerror(errno)) + " | Failed to write " + path);
+}
+
 void write_cohort_clusters_tsv(const std::string& path, const std::vector<std::string>& names, const CohortClusters& c, uint64_t threshold, double min_breadth) {
     if (c.cluster.size() != names.size() || c.size.size() != names.size()) throw std::runtime_error("write_cohort_clusters_tsv: one cluster per sample");
     FILE* f = fopen(path.c_str(), "wb");

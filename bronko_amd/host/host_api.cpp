@@ -700,6 +700,73 @@ int bh_write_cohort_clusters_tsv(const char* path, const char* names, const uint
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }
 
+// ---- --contamination: the host twins, the scanner and the three writers (cohort.cpp) ------------------------------------------------
+// fwd, rev: four counts a position; masks: a byte a position (may be null); tallies: positions, mixed, present
+int bh_minor_mask(const uint64_t* fwd, const uint64_t* rev, uint64_t positions, uint64_t min_reads, double min_freq, uint8_t* masks, uint64_t* tallies) {
+    try {
+        if (!fwd || !rev) throw std::runtime_error("bh_minor_mask: fwd or rev is null");
+        const bronko::MinorSummary s = bronko::minor_mask_host(fwd, rev, positions, min_reads, min_freq, masks);
+        if (tallies) { tallies[0] = s.positions; tallies[1] = s.mixed; tallies[2] = s.present; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// letters, masks: n rows of `positions` bytes; explained: [n_rows][n], minor_sites: [n_rows], either may be null
+int bh_cohort_explained(const uint8_t* letters, const uint8_t* masks, uint64_t n, uint64_t positions, uint64_t row0, uint64_t n_rows, uint32_t* explained,
+                        uint32_t* minor_sites, uint32_t threads) {
+    try {
+        if (!letters || !masks) throw std::runtime_error("bh_cohort_explained: letters or masks is null");
+        bronko::cohort_explained_host(letters, masks, n, positions, row0, n_rows, explained, minor_sites, threads);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+namespace {
+bronko::Contamination scan_contamination(uint64_t n, const uint32_t* diff, const uint32_t* compared, const uint32_t* explained, uint32_t min_sites, double min_share,
+                                         uint64_t block_rows) {
+    bronko::ContaminationScanner sc(n, min_sites, min_share);
+    const uint64_t step = block_rows ? block_rows : std::max<uint64_t>(n, 1);
+    for (uint64_t r = 0; r < n; r += step) sc.add_rows(r, std::min(step, n - r), diff + r * n, compared + r * n, explained + r * n);
+    return sc.finish();
+}
+}  // namespace
+// the three [n][n] matrices go to the scanner in blocks of block_rows rows (0: all at once).  flagged: [cap][5] recipient, source, diff,
+// compared, explained, written where they fit; *n_flagged: how many; best: [n][3] source (0xffffffff: none), explained, diff; counts: [n];
+// stats: recipients, the largest explained
+int bh_contamination_scan(uint64_t n, const uint32_t* diff, const uint32_t* compared, const uint32_t* explained, uint32_t min_sites, double min_share, uint64_t block_rows,
+                          uint32_t* flagged, uint64_t cap, uint64_t* n_flagged, uint32_t* best, uint32_t* counts, uint32_t* stats) {
+    try {
+        const bronko::Contamination c = scan_contamination(n, diff, compared, explained, min_sites, min_share, block_rows);
+        if (n_flagged) *n_flagged = c.flagged.size();
+        for (size_t k = 0; flagged && k < c.flagged.size() && k < cap; k++) {
+            const auto& x = c.flagged[k];
+            flagged[5 * k] = x.recipient; flagged[5 * k + 1] = x.source; flagged[5 * k + 2] = x.diff; flagged[5 * k + 3] = x.compared; flagged[5 * k + 4] = x.explained;
+        }
+        for (uint64_t i = 0; i < n; i++) {
+            if (best) { best[3 * i] = c.best[i].source; best[3 * i + 1] = c.best[i].explained; best[3 * i + 2] = c.best[i].diff; }
+            if (counts) counts[i] = c.n_flagged[i];
+        }
+        if (stats) { stats[0] = c.recipients; stats[1] = c.largest; }
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int bh_write_cohort_explained_tsv(const char* path, const char* names, const uint32_t* explained) {
+    try { bronko::write_cohort_explained_tsv(path, split_lines(names), explained); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// which: 0 OUT/<genome>.contamination.tsv, 1 OUT/<genome>.mixture.tsv, of the scanner's result over the three matrices
+int bh_write_contamination_tsv(int which, const char* path, const char* names, const uint32_t* diff, const uint32_t* compared, const uint32_t* explained,
+                               const uint32_t* minor_sites, uint64_t minor_min_reads, double minor_min_freq, uint32_t min_sites, double min_share, uint64_t block_rows) {
+    try {
+        const std::vector<std::string> nm = split_lines(names);
+        bronko::ContaminationParams p;
+        p.minor_min_reads = minor_min_reads; p.minor_min_freq = minor_min_freq; p.min_sites = min_sites; p.min_share = min_share;
+        const bronko::Contamination c = scan_contamination(nm.size(), diff, compared, explained, min_sites, min_share, block_rows);
+        const std::vector<uint32_t> ms(minor_sites, minor_sites + nm.size());
+        if (which == 0) bronko::write_contamination_tsv(path, nm, c, ms, p);
+        else bronko::write_mixture_tsv(path, nm, c, ms, p);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
 void bh_clean_sample_id(const char* path, char* buf, size_t n) {
     const std::string s = bronko::clean_sample_id(path);
     snprintf(buf, n, "%s", s.c_str());

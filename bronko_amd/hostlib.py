@@ -892,3 +892,96 @@ def write_cohort_clusters_tsv(path, names, cluster, size, threshold, min_breadth
     sz = np.ascontiguousarray(size, np.uint32)
     if L.bh_write_cohort_clusters_tsv(path.encode(), "\n".join(names).encode(), cl.ctypes.data, sz.ctypes.data, int(threshold), float(min_breadth)) != 0:
         raise _host_error(L)
+
+
+# ---- --contamination: the host twins, the scanner and the three writers (cohort.cpp) ------------------------------------------------
+def _contamination_lib():
+    vp, u64, u32 = _VP, _U64, _U32
+    return _bound("_contamination_ready", {
+        "bh_minor_mask": [vp, vp, u64, u64, C.c_double, vp, vp],
+        "bh_cohort_explained": [vp, vp, u64, u64, u64, u64, vp, vp, u32],
+        "bh_contamination_scan": [u64, vp, vp, vp, u32, C.c_double, u64, vp, u64, vp, vp, vp, vp],
+        "bh_write_cohort_explained_tsv": [C.c_char_p, C.c_char_p, vp],
+        "bh_write_contamination_tsv": [C.c_int, C.c_char_p, C.c_char_p, vp, vp, vp, vp, u64, C.c_double, u32, C.c_double, u64]})
+
+
+def minor_mask(fwd, rev, min_reads=10, min_freq=0.03):
+    """The host twin of bk_sample_minor_alleles (cohort.cpp minor_mask_host) over the positions of two (positions * 4) uint64 depth
+    arrays: (masks as a uint8 array, (positions, mixed, present))."""
+    L = _contamination_lib()
+    f = np.ascontiguousarray(fwd, np.uint64).reshape(-1)
+    r = np.ascontiguousarray(rev, np.uint64).reshape(-1)
+    if len(f) != len(r) or len(f) % 4:
+        raise ValueError("minor_mask: four counts a position on either strand")
+    positions = len(f) // 4
+    masks = np.zeros(max(1, positions), np.uint8)
+    tallies = np.zeros(3, np.uint64)
+    if L.bh_minor_mask(f.ctypes.data, r.ctypes.data, positions, int(min_reads), float(min_freq), masks.ctypes.data, tallies.ctypes.data) != 0:
+        raise _host_error(L)
+    return masks[:positions], tuple(int(v) for v in tallies)
+
+
+def cohort_explained(letters, masks, row0=0, n_rows=None, threads=4):
+    """The host twin of bk_cohort_set_minor and bk_cohort_explained (cohort.cpp cohort_explained_host): (explained, minor_sites) of the
+    rows [row0, row0 + n_rows) of two (n_samples, positions) uint8 arrays -- an (n_rows, n_samples) and an (n_rows,) uint32 array."""
+    L = _contamination_lib()
+    a = np.ascontiguousarray(letters, np.uint8)
+    m = np.ascontiguousarray(masks, np.uint8)
+    if a.shape != m.shape or a.ndim != 2:
+        raise ValueError("cohort_explained: a mask per letter")
+    n, positions = a.shape
+    n_rows = n - row0 if n_rows is None else n_rows
+    explained = np.zeros((max(1, n_rows), max(1, n)), np.uint32)
+    sites = np.zeros(max(1, n_rows), np.uint32)
+    if L.bh_cohort_explained(a.ctypes.data, m.ctypes.data, n, positions, int(row0), int(n_rows), explained.ctypes.data, sites.ctypes.data, int(threads)) != 0:
+        raise _host_error(L)
+    return explained[:n_rows, :n], sites[:n_rows]
+
+
+def _three_matrices(diff, compared, explained):
+    d, c, x = (np.ascontiguousarray(v, np.uint32) for v in (diff, compared, explained))
+    if not (d.ndim == 2 and d.shape[0] == d.shape[1] and d.shape == c.shape == x.shape):
+        raise ValueError("three (n, n) matrices")
+    return d, c, x
+
+
+def contamination_scan(diff, compared, explained, min_sites=3, min_share=0.75, block_rows=0):
+    """The --contamination scanner (cohort.cpp ContaminationScanner) fed the three (n, n) matrices in blocks of block_rows rows (0: at
+    once): (flagged, best, counts, recipients, largest) -- flagged an (F, 5) uint32 array of recipient, source, diff, compared,
+    explained, ordered by (recipient, source); best an (n, 3) array of source (0xffffffff: none), explained, diff; counts the sources
+    every sample is flagged for."""
+    L = _contamination_lib()
+    d, c, x = _three_matrices(diff, compared, explained)
+    n = d.shape[0]
+    cap = max(1, n * n)
+    flagged = np.zeros((cap, 5), np.uint32)
+    best = np.zeros((max(1, n), 3), np.uint32)
+    counts = np.zeros(max(1, n), np.uint32)
+    stats = np.zeros(2, np.uint32)
+    n_flagged = C.c_uint64(0)
+    if L.bh_contamination_scan(n, d.ctypes.data, c.ctypes.data, x.ctypes.data, int(min_sites), float(min_share), int(block_rows), flagged.ctypes.data, cap,
+                               C.addressof(n_flagged), best.ctypes.data, counts.ctypes.data, stats.ctypes.data) != 0:
+        raise _host_error(L)
+    return flagged[:int(n_flagged.value)], best[:n], counts[:n], int(stats[0]), int(stats[1])
+
+
+def write_cohort_explained_tsv(path, names, explained):
+    """The --contamination matrix writer (cohort.cpp): OUT/<genome>.explained.tsv of an (n, n) matrix."""
+    L = _contamination_lib()
+    m = np.ascontiguousarray(explained, np.uint32)
+    if L.bh_write_cohort_explained_tsv(path.encode(), "\n".join(names).encode(), m.ctypes.data) != 0:
+        raise _host_error(L)
+
+
+def write_contamination_tsv(path, names, diff, compared, explained, minor_sites, minor_min_reads=10, minor_min_freq=0.03, min_sites=3, min_share=0.75,
+                            mixture=False, block_rows=0):
+    """The --contamination writers (cohort.cpp): OUT/<genome>.contamination.tsv, or .mixture.tsv with mixture=True, of the scanner's
+    result over the three (n, n) matrices."""
+    L = _contamination_lib()
+    d, c, x = _three_matrices(diff, compared, explained)
+    ms = np.ascontiguousarray(minor_sites, np.uint32)
+    if len(ms) != len(names) or d.shape[0] != len(names):
+        raise ValueError("write_contamination_tsv: one row and one minor_sites per sample")
+    if L.bh_write_contamination_tsv(1 if mixture else 0, path.encode(), "\n".join(names).encode(), d.ctypes.data, c.ctypes.data, x.ctypes.data, ms.ctypes.data,
+                                    int(minor_min_reads), float(minor_min_freq), int(min_sites), float(min_share), int(block_rows)) != 0:
+        raise _host_error(L)

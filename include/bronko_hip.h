@@ -409,6 +409,36 @@ void bk_consensus_params_default(bk_consensus_params* p);   /* 10, 0.5 */
 int  bk_sample_consensus(bk_engine* e, const bk_consensus_params* p);
 int  bk_sample_download_consensus(bk_engine* e, bk_consensus_summary* summary, uint8_t* letters, uint64_t cap);
 
+/* ---- per-sample minor alleles (`bronko call --contamination`; additive, still v8) --------------------------------------------------
+ * Which bases are present at every position of the genome bk_sample_call selected: one byte per position, the present mask, made
+ * from the two depth planes where they are; only the bytes travel.  With tot[b] and depth as bk_sample_consensus defines them, bit b
+ * of the byte (A = 1, C = 2, G = 4, T = 8) is set iff both hold:
+ *   tot[b] >= min_reads
+ *   (double)tot[b] >= min_freq * (double)depth
+ * The upper four bits are 0.  Integer arithmetic but for the one product.  No end, strand or noise filter, as for the consensus; the
+ * bytes lie in (sequence, position) order, as the consensus letters do.  The summary: positions, mixed = the positions with at least
+ * two bits set, present = the number of set bits.
+ * min_reads >= 1 and 0 <= min_freq <= 1 (BK_ERR_INVALID otherwise, the parameter named).
+ *   bk_sample_minor_alleles            the call order of bk_sample_consensus: after the sample's bk_sample_call (BK_ERR_STATE before
+ *                                      it, inside a sample, and after a later bk_sample_begin); asynchronous on the engine's stream
+ *                                      (minor_alleles_kernel, bk_caller.hip).  Its buffers -- a byte per cell of the largest genome,
+ *                                      and the summary -- are allocated at the engine's first call: an engine that never asks
+ *                                      allocates and launches nothing.  Per engine: forks own theirs.  Independent of
+ *                                      bk_sample_consensus: either may run without the other, in either order.
+ *   bk_sample_download_minor_alleles   synchronises; copies min(cap, positions) bytes (masks may be NULL).  No genome selected:
+ *                                      file_id = -1, every tally 0, no bytes. */
+typedef struct { uint64_t min_reads; double min_freq; } bk_minor_params;
+typedef struct {
+    int32_t  file_id;               /* the genome bk_sample_call selected, -1 = none */
+    uint32_t pad;
+    uint64_t positions;             /* bytes there are = positions of the genome */
+    uint64_t mixed;                 /* positions with at least two bases present */
+    uint64_t present;               /* set bits over all positions */
+} bk_minor_summary;
+void bk_minor_params_default(bk_minor_params* p);   /* 10, 0.03 */
+int  bk_sample_minor_alleles(bk_engine* e, const bk_minor_params* p);
+int  bk_sample_download_minor_alleles(bk_engine* e, bk_minor_summary* summary, uint8_t* masks, uint64_t cap);
+
 /* ---- per-region depth report (`bronko call --regions / --region-window`; additive, still v8) -------------------------------
  * Which stretches of the selected genome dropped out, and how deep the rest is, from the two depth planes where they are; a few
  * numbers per region travel.  The rule, all of it integer arithmetic:
@@ -1090,6 +1120,38 @@ typedef struct { uint32_t lo, hi, diff, compared; } bk_mst_edge;        /* lo < 
 typedef struct { uint32_t sample, diff, compared; } bk_mst_nearest;     /* sample = 0xffffffff: none */
 int  bk_cohort_mst(bk_engine* e, uint32_t min_compared, bk_mst_edge* edges, uint64_t cap_edges, uint64_t* n_edges,
                    bk_mst_nearest* nearest /* [n_samples] or NULL */, uint32_t* rounds /* or NULL */);
+
+/* ---- which sample's alleles another carries (`bronko call --distances --contamination`; additive, still v8) -----------------------
+ * A sample that holds a share of another one has that one's alleles as minor variants, at exactly the positions where the two
+ * consensuses differ.  Over the cohort bk_cohort_set holds and one present mask per sample and position (bk_sample_minor_alleles;
+ * only the low four bits of a byte count: A = 1, C = 2, G = 4, T = 8), all of it integer arithmetic.  For sample i and position p:
+ *   cons_i(p)     its consensus letter if that is a base (exactly one of ACGT, as above), else none.
+ *   minor_i(p)    empty if cons_i(p) is none; otherwise the mask's low four bits without the bit of cons_i(p).
+ *   explained     explained[i][j] = the positions p at which cons_i(p) and cons_j(p) are both bases, differ, and the bit of
+ *                 cons_j(p) is in minor_i(p).  Row i is the recipient, column j the source.  u32 and NOT symmetric;
+ *                 explained[i][i] = 0, explained[i][j] <= diff[i][j].
+ *   minor_sites   minor_sites[i] = the positions with minor_i(p) not empty; explained[i][j] <= minor_sites[i].
+ *   best          best[i] = the j != i with the largest explained[i][j] >= 1; ties go to the smaller diff[i][j], then to the
+ *                 earlier sample; there may be none.
+ *   flagged       with two parameters S (u32) and P (double), an ordered pair (i, j), i != j, is flagged iff
+ *                 explained[i][j] >= S and (double)explained[i][j] >= P * (double)diff[i][j].
+ * best and flagged are the host's (bronko_amd/host/cohort.hpp, ContaminationScanner); the device counts.
+ *   bk_cohort_set_minor  after bk_cohort_set, with the same n_samples and positions: uploads the masks (host memory, n rows of
+ *                        `positions` bytes, in batches of at most 256 MB) and packs them with the letters' planes that are there
+ *                        into four minor planes per sample (cohort_minor_pack_kernel, bk_cohort.hip): M_X = "X is present, the
+ *                        sample's consensus is a base, and it is not X"; 32 more bytes per 64 positions and sample, and
+ *                        minor_sites (4 bytes per sample), counted in the pack.  Synchronises: the masks may go when it returns.
+ *                        A second call replaces the planes of the first.  A later bk_cohort_set or bk_cohort_clear drops them.
+ *                        BK_ERR_STATE without a cohort or inside a sample; BK_ERR_INVALID, with the parameter named: a null
+ *                        masks, n_samples or positions other than the cohort's.  bk_cohort_distances and bk_cohort_mst give the
+ *                        same results before and after it.
+ *   bk_cohort_explained  rows [row0, row0 + n_rows) against all n_samples columns (cohort_explained_kernel); synchronises and
+ *                        copies n_rows x n_samples values, row-major, into `explained` and n_rows values into `minor_sites`, each
+ *                        where it is not NULL (no launch without `explained`).  Blocks and their errors as for
+ *                        bk_cohort_distances; BK_ERR_STATE without minor planes.  Its output block is its own: the block of the
+ *                        last bk_cohort_distances stays. */
+int  bk_cohort_set_minor(bk_engine* e, const uint8_t* masks, uint64_t n_samples, uint64_t positions);
+int  bk_cohort_explained(bk_engine* e, uint64_t row0, uint64_t n_rows, uint32_t* explained, uint32_t* minor_sites);
 
 /* ---- build_indexes on the device (optional) -----------------------------------------------------
  * build.rs:145-231 for the metadata sequences given like bk_index_desc gives them: one thread per k-mer writes its k

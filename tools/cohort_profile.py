@@ -7,7 +7,11 @@ time of bk_cohort_set and of each bk_cohort_distances (host clock around calls t
     python tools/cohort_profile.py host N [REPS] [THREADS]
 times the host twin (cohort_distances_host: packing and pairs) on THREADS threads, 16 by default, on the same letters: the yardstick.
 `device` also checks its matrices against the host twin's.  With BK_COHORT_SLICE_WORDS set it binds the testing library, which reads
-it: 468 makes every tile one slice."""
+it: 468 makes every tile one slice.
+    ... python tools/cohort_profile.py device-explained N [REPS]      python tools/cohort_profile.py host-explained N [REPS] [THREADS]
+are the same for --contamination: the cohort with a present mask per letter -- the consensus base and, at five
+positions a sample, a second base --, bk_cohort_set_minor once, then per repetition bk_cohort_distances and bk_cohort_explained, so that
+one trace holds cohort_minor_pack_kernel, cohort_explained_kernel and cohort_pairs_kernel side by side; and cohort_explained_host."""
 import os
 import sys
 import time
@@ -41,6 +45,18 @@ def letters(n, positions, seed=17):
     return np.ascontiguousarray(a)
 
 
+def masks_of(a, seed=18):
+    """The consensus base present everywhere it is a base, and a second base at five positions a sample: a few mixed positions."""
+    rng = np.random.default_rng(seed)
+    m = np.zeros(a.shape, np.uint8)
+    for ch, bit in ((ord("A"), 1), (ord("C"), 2), (ord("G"), 4), (ord("T"), 8)):
+        m[a == ch] = bit
+    for s in range(a.shape[0]):
+        at = rng.integers(0, a.shape[1], 5)
+        m[s, at] |= (1 << rng.integers(0, 4, 5)).astype(np.uint8)
+    return m
+
+
 a = letters(N, POSITIONS)
 pair_positions = float(N) * N * POSITIONS
 if MODE == "host":
@@ -52,6 +68,40 @@ if MODE == "host":
         best = dt if best is None else min(best, dt)
         print("host n=%d threads=%d rep %d: %.3f ms" % (N, THREADS, rep, dt * 1e3))
     print("host n=%d threads=%d best %.3f ms, %.3e pair-positions/s, largest distance %d" % (N, THREADS, best * 1e3, pair_positions / best, int(d.max())))
+elif MODE == "host-explained":
+    m = masks_of(a)
+    best = None
+    for rep in range(REPS):
+        t0 = time.perf_counter()
+        ex, sites = hostlib.cohort_explained(a, m, threads=THREADS)
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+        print("host-explained n=%d threads=%d rep %d: %.3f ms" % (N, THREADS, rep, dt * 1e3))
+    print("host-explained n=%d threads=%d best %.3f ms, %.3e pair-positions/s, largest explained %d" % (N, THREADS, best * 1e3, pair_positions / best, int(ex.max())))
+elif MODE == "device-explained":
+    m = masks_of(a)
+    ix = hostlib.HostIndex.load(os.path.join(ROOT, "tests", "golden", "hpv.bkdb"))
+    eng = ix.engine()
+    eng.cohort_set(a)
+    t0 = time.perf_counter()
+    eng.cohort_set_minor(m)
+    print("device-explained n=%d bk_cohort_set_minor: %.3f ms" % (N, (time.perf_counter() - t0) * 1e3))
+    best = None
+    for rep in range(REPS):
+        t0 = time.perf_counter()
+        eng.cohort_distances()
+        t1 = time.perf_counter()
+        ex, sites = eng.cohort_explained()
+        dt = time.perf_counter() - t1
+        best = dt if best is None else min(best, dt)
+        print("device-explained n=%d rep %d bk_cohort_distances: %.3f ms, bk_cohort_explained: %.3f ms" % (N, rep, (t1 - t0) * 1e3, dt * 1e3))
+    print("device-explained n=%d best call %.3f ms, %.3e pair-positions/s by the call's wall time, largest explained %d" % (N, best * 1e3, pair_positions / best, int(ex.max())))
+    hex_, hsites = hostlib.cohort_explained(a, m, threads=THREADS)
+    if not (np.array_equal(ex, hex_) and np.array_equal(sites, hsites)):
+        raise SystemExit("cohort_profile: the device's explained matrix differs from the host twin's")
+    print("device-explained n=%d: equal to the host twin" % N)
+    eng.close()
+    ix.close()
 else:
     ix = hostlib.HostIndex.load(os.path.join(ROOT, "tests", "golden", "hpv.bkdb"))
     eng = ix.engine()
